@@ -4,6 +4,12 @@
     python bench.py --gpus N --steps K --warmup W            # N > 1: spawns its own N ranks (one per GPU)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
            bench.py --gpus N --steps K --warmup W            # …or is launched as one of them
+    python bench.py --gpus 1 --steps K --warmup W --full     # + every extra figure listed below
+    python bench.py --gpus 1 --steps K --warmup W --dump-outputs DIR   # + what the last timed step computed, as DIR/*.npy
+
+A plain run sets up, warms up, times the K steps and prints the JSON line (`metric`, `value`, `unit`, `higher_is_better`,
+`dtype`, `ms_per_step`, `check`, `config`, the host's per-step loop times); the extra objects below are null in it. `--full`
+adds them: each takes passes, processes or solves of its own after the timed steps.
 
 Workload `c3` (default; config C3 of BASELINE.md, the configuration the metric is quoted on): 2-D Bratu n = 1024²
 (N = 1 048 576 unknowns, nnz = 5 238 784, λ = 6, u0 = 0), NewtonRaphson with the *fixed-work* Krylov protocol of
@@ -17,24 +23,30 @@ and the same minimisation as column-by-column CGS2, iterates equal to 1e-10 over
 very protocol at full size against the C oracle); `--ortho dcgs2` runs the column-by-column form of rounds 1–2 (delayed CGS2:
 two sweeps and one reduction per column), `--sstep 6 --sstep-basis monomial` round 2's blocks. A "step" is one such Newton step:
 Jacobian value fill + 30 SpMVs + the orthogonalisation sweeps + solution update + u += δu + residual + ‖·‖∞ + termination
-bookkeeping, everything resident in HBM. Defaults: 300 timed steps after 20 warm-up steps (≈ 0.3 s of GPU time; the CPU leg's
-bounded sample and the time-to-tolerance extras dominate the wall clock of the default run).
+bookkeeping, everything resident in HBM. Defaults: 300 timed steps after 20 warm-up steps (≈ 0.3 s of GPU time; with `--full`
+the CPU leg's bounded sample and the time-to-tolerance extras dominate the wall clock).
 
 N > 1 is STRONG scaling on the metric's configuration: the same 1024² problem row-partitioned by grid lines over N
 ranks (halo lines + Krylov inner products over xGMI: peer-mapped buffers, RCCL as fallback); `value` is the plain
 global Newton steps/s. `--workload c4` is Bratu 4096² (config C4), `--workload c5` the Brusselator 512² TrustRegion
-step (config C5) — both row-partitioned over N ranks as well. A weak-scaling run (every rank owns ≈1024² unknowns of a
-(1024·√N)² grid) is reported under the extra key `weak_scaling` when N > 1.
+step (config C5) — both row-partitioned over N ranks as well. With `--full`, a weak-scaling run (every rank owns ≈1024²
+unknowns of a (1024·√N)² grid) is reported under the extra key `weak_scaling` when N > 1.
 
-Extra objects on the JSON line: `roofline` (the time-dominant kernel family of the step — the CSR SpMV — HIP-event timed on
-the launch stream in a second, instrumented pass of the same K steps; `traffic` from the newest PMC summary under profiles/),
-`roofline_step` (bytes every kernel of the step must move ÷ ms_per_step), `step_time_stats` (the host's per-step loop times of the
-timed region, the time of its closing barrier, and median / p10 / p90 of the per-step device times from one event per step in a
-pass of its own — round 6 took the events, which are marker packets between the steps' kernels, and the interpreter's garbage
-collector out of the timed region), `kernels` (every kernel family of the step), `cpu_baseline` (the oracle's
-tuned C/OpenMP restatements of the same step — delayed CGS2 and the Newton-basis s-step form, median of 5 sustained samples
-each at a thread count chosen by sustained samples; value = the faster — next to the box's STREAM triad, its CSR SpMV rate and
-a single-thread figure), `config.comm_selfcheck` for N > 1 (tools/multi_gpu_selfcheck.py's verdict on the negotiated transport).
+`--dump-outputs DIR` writes, after the timed steps, what the last of them handed to a caller of the solver cache: the iterate
+`u.npy`, the residual `fu.npy` (both float64; with N ranks the local slices in rank order) and `fnorm_inf.npy`. A vector of more
+than 2²¹ entries is written as a fixed, seeded sample of them, its positions in `sample_index.npy` (3 × 16 MiB at most). The
+inputs are fixed (u0 = 0, or the problem's own initial guess for c5), so two builds compare output for output.
+
+Extra objects on the JSON line (`--full` only): `roofline` (the time-dominant kernel family of the step — the CSR SpMV —
+HIP-event timed on the launch stream in a second, instrumented pass of the same K steps; `traffic` from the newest PMC summary
+under profiles/), `roofline_step` (bytes every kernel of the step must move ÷ ms_per_step), `kernels` (every kernel family of
+the step), `cpu_baseline` (the oracle's tuned C/OpenMP restatements of the same step — delayed CGS2 and the Newton-basis s-step
+form, median of 5 sustained samples each at a thread count chosen by sustained samples; value = the faster — next to the box's
+STREAM triad, its CSR SpMV rate and a single-thread figure), `time_to_tolerance`, `weak_scaling`, and in `step_time_stats`
+median / p10 / p90 of the per-step device times from one event per step in a pass of its own. Every run reports in
+`step_time_stats` the host's per-step loop times of the timed region and the time of its closing barrier (round 6 took the
+events, which are marker packets between the steps' kernels, and the interpreter's garbage collector out of the timed region),
+and for N > 1 `config.comm_selfcheck` (tools/multi_gpu_selfcheck.py's verdict on the negotiated transport).
 """
 import argparse
 import json
@@ -75,7 +87,16 @@ def parse_args():
     ap.add_argument("--pmc", default="auto", choices=["auto", "off"],
                     help="auto: at N = 1 measure roofline.traffic in this run (two short rocprofv3 --pmc child passes of this "
                          "script: FETCH_SIZE, WRITE_SIZE); falls back to the newest PMC summary under profiles/")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure every extra figure (per-step device times, the instrumented kernel "
+                         "pass and rooflines, the weak-scaling run, the CPU baseline, time to tolerance); a plain run measures "
+                         "the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (u, F(u), ‖F(u)‖∞) as DIR/<name>.npy")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
 
 
 def free_port():
@@ -243,6 +264,48 @@ def spmv_hbm_resident(nls, torch, ctx, reps=30):
             "note": "Bratu 4096² Jacobian (1.07 GB): nothing fits the Infinity Cache — the streaming kernel against HBM itself"}
 
 
+DUMP_SAMPLE = 1 << 21     # --dump-outputs: entries kept of a longer vector (a fixed, seeded sample)
+DUMP_SEED = 1024
+
+
+def capture_outputs(cache):
+    """what a caller of the timed path receives after its last step: the iterate, the residual, ‖F‖∞ (copied to the host)"""
+    host = lambda a: a.cpu().numpy() if hasattr(a, "cpu") else a  # noqa: E731
+    return {"u": host(cache.u), "fu": host(cache.fu), "fnorm_inf": cache.fnorm_inf}
+
+
+def dump_outputs(dirpath, outs, world, rank, dist):
+    """--dump-outputs DIR: outs (capture_outputs) as DIR/<name>.npy in float64; with N ranks the vectors are the local slices
+    in rank order. A vector longer than DUMP_SAMPLE is written as the sample at DUMP_SEED's positions (DIR/sample_index.npy),
+    the same from run to run: 3 × 16 MiB at most."""
+    import numpy as np
+    n_loc = len(outs["u"])
+    counts = [n_loc]
+    if world > 1:
+        counts = [None] * world
+        dist.all_gather_object(counts, n_loc)
+    off, n = sum(counts[:rank]), sum(counts)
+    idx = np.sort(np.random.default_rng(DUMP_SEED).choice(n, DUMP_SAMPLE, replace=False)) if n > DUMP_SAMPLE else None
+    mine = {}
+    for name in ("u", "fu"):
+        v = np.asarray(outs[name], dtype=np.float64)
+        mine[name] = v if idx is None else v[idx[(idx >= off) & (idx < off + n_loc)] - off]
+    parts = [mine]
+    if world > 1:
+        parts = [None] * world
+        dist.all_gather_object(parts, mine)
+    if rank != 0:
+        return
+    arrays = {name: np.concatenate([p[name] for p in parts]) for name in ("u", "fu")}
+    arrays["fnorm_inf"] = np.array([outs["fnorm_inf"]], dtype=np.float64)
+    if idx is not None:
+        arrays["sample_index"] = idx.astype(np.float64)
+    assert sum(a.nbytes for a in arrays.values()) <= 64 << 20
+    os.makedirs(dirpath, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(dirpath, name + ".npy"), a)
+
+
 def cpu_baseline(ns, arnoldi, matfree, budget_s):
     """The oracle's tuned CPU leg on this box's host cores (rank 0, N = 1 only): bounded sample of the same workload, in a
     child process so that the OpenMP runtime starts bound to the cores and waits actively (oracle/cpu_leg.py)."""
@@ -353,12 +416,15 @@ def main():
     steps_per_s = args.steps / dt
     stats = cache.stats
     fnorm = cache.fnorm_inf
-    step_time_distribution(cache, min(args.steps, 200), barrier, torch)
+    outputs = capture_outputs(cache) if args.dump_outputs else None
+    # everything from here to the result line that runs more steps, passes or solves is an extra of `--full`
+    if args.full:
+        step_time_distribution(cache, min(args.steps, 200), barrier, torch)
 
     # ---- second, instrumented pass of the same K steps: HIP events on the launch stream around every
     # kernel family (not part of `value`)
     kernels = {}
-    if not args.no_profile_pass:
+    if args.full and not args.no_profile_pass:
         ctx.profile_enable(True)
         for _ in range(args.steps):
             cache.step()
@@ -399,7 +465,7 @@ def main():
         roof = family_roofline(dom)
     # ---- the operator itself (the metric's second half: SpMV GB/s against the HBM roofline), whatever dominates the step
     roof_spmv = None
-    if rank == 0 and world == 1 and args.workload == "c3" and not args.matfree:
+    if args.full and rank == 0 and world == 1 and args.workload == "c3" and not args.matfree:
         roof_spmv = {}
         if "spmv_powers" in kernels:
             k = kernels["spmv_powers"]
@@ -457,6 +523,8 @@ def main():
                        "reported": "overlapped" if (ok and dt2 < dt) else "serial"}
             if ok and dt2 < dt:
                 dt, steps_per_s = dt2, args.steps / dt2
+                if args.dump_outputs:
+                    outputs = capture_outputs(cache)
             else:
                 ctx.set_halo_overlap(False)
         except Exception as ex:  # noqa: BLE001
@@ -466,7 +534,7 @@ def main():
 
     # ---- N > 1: the weak-scaling run as an extra key (every rank owns ≈ ns² unknowns of a (ns·√N)² grid)
     weak = None
-    if world > 1 and not args.no_weak and args.workload == "c3":
+    if args.full and world > 1 and not args.no_weak and args.workload == "c3":
         nsw = int(round(ns * math.sqrt(world)))
         cache.close()
         probw, cachew = make_cache("c3", nsw)
@@ -481,7 +549,7 @@ def main():
 
     # ---- CPU baseline (rank 0, N = 1): the oracle's tuned C/OpenMP leg on this box's host cores, bounded sample
     cpu = None
-    if rank == 0 and world == 1 and args.cpu_seconds > 0 and args.workload != "c5":
+    if args.full and rank == 0 and world == 1 and args.cpu_seconds > 0 and args.workload != "c5":
         try:
             cpu = cpu_baseline(ns, args.arnoldi, args.matfree, args.cpu_seconds if ns <= 1024 else 2.5 * args.cpu_seconds)
         except Exception as ex:  # noqa: BLE001
@@ -490,7 +558,7 @@ def main():
     # ---- time to tolerance (extra, not `value`): the §3 protocol (NewtonRaphson + GMRES(30) + Eisenstat–Walker,
     # inner cap 300, ‖h²F‖∞ ≤ 1e-8) with the built-in right preconditioners behind the `precs` hook
     ttt = None
-    if rank == 0 and world == 1 and not args.no_ttt and args.workload == "c3":
+    if args.full and rank == 0 and world == 1 and not args.no_ttt and args.workload == "c3":
         prob2 = nls.NonlinearProblem(nls.Bratu2D(ns, 6.0), u0=torch.zeros(n_local, dtype=torch.float64, device="cuda"))
         ttt = {"protocol": "NewtonRaphson+GMRES(30)+EisenstatWalkerForcing2 to |h^2 F|inf<=1e-8"}
         for name, precs in (("chebyshev_32_300", nls.ChebyshevPrecs(32, 300.0)), ("multigrid_2_31", nls.MultigridPrecs(2, 31)),
@@ -533,7 +601,7 @@ def main():
             ttt["extras_error"] = str(ex)
 
     roof_step = None
-    if args.workload != "c5":
+    if args.full and args.workload != "c5":
         nnz_l = 5 * n_global - 4 * ns
         newton_basis = args.ortho == "sstep" and args.sstep_basis != "monomial"
         hbm_b, alg_b = bytes_per_step(args, n_global, nnz_l, newton_basis, "spmv_powers" in kernels)
@@ -551,6 +619,8 @@ def main():
                              "(tools/step_model.py lists them; the resident matrix-powers kernel reads the matrix once per block) ÷ "
                              "ms_per_step → frac. algorithmic_bytes_per_step: the same with every operator application charged at "
                              "the CSR SpMV's 80 N bytes (SURVEY.md §8d) → frac_algorithmic, which on-chip reuse can push past 1"}
+    if outputs is not None:
+        dump_outputs(args.dump_outputs, outputs, world, rank, dist)
     if rank == 0:
         op = "matfree_jvp" if args.matfree else "csr_spmv"
         if args.workload == "c5":
@@ -561,7 +631,7 @@ def main():
             wl += f"_x{world}"
         line = {
             "metric": "newton_steps_per_sec", "value": round(steps_per_s, 3), "unit": "newton_steps/s",
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "full": args.full,
             "ms_per_step": round(1e3 * dt / args.steps, 4), "higher_is_better": True,
             # N > 1 partitions the SAME 1024² system over the ranks (total work fixed): strong scaling, also as the N = 1 point
             "scaling": "strong",
@@ -572,7 +642,7 @@ def main():
                        "parallelism": f"row-range x{world}", "comm": comm, "comm_selfcheck": selfchecks, "halo_overlap": overlap,
                        # several ranks on ONE device (a code-path run, not a rate: DESIGN §7)
                        "ranks_share_a_device": bool(ctx.comm_device_shared()) if world > 1 else False},
-            "roofline": roof, "roofline_spmv": roof_spmv, "roofline_step": roof_step, "kernels": ksum, "cpu_baseline": cpu, "time_to_tolerance": ttt, "weak_scaling": weak,
+            "roofline": roof, "roofline_spmv": roof_spmv, "roofline_step": roof_step, "kernels": ksum if args.full else None, "cpu_baseline": cpu, "time_to_tolerance": ttt, "weak_scaling": weak,
             # against the best SUSTAINED figure the CPU leg produced (the median of its samples or a validation run; scan samples
             # can be bursts a container's CPU quota does not sustain and are reported, not used)
             "gpu_vs_cpu": round(steps_per_s / max([cpu["value"]] + list(cpu.get("thread_count_validation_steps_per_s", {}).values())), 1)

@@ -1,6 +1,7 @@
 """CPU tests of the C-ABI boundary: the shared library loads, exports every symbol include/mi355x_nk.h declares,
 its host-only logic works without a GPU, and it fails loudly (no CPU fallback) when no HIP device exists."""
 import ctypes as C
+import json
 import os
 import re
 
@@ -264,7 +265,7 @@ def test_every_julia_ccall_matches_the_header_signature():
 
 def test_julia_package_manifest_declares_what_the_sources_load():
     """julia/ is a package (Next #5): Project.toml with name / uuid / [deps] / [weakdeps] / [extensions] / [compat]
-    after the reference's own manifest (/root/reference/Project.toml:32-68), the module under src/, the AMDGPU extension under
+    after the reference's own manifest (its Project.toml:32-68), the module under src/, the AMDGPU extension under
     ext/. Every package a `using` / `import` of the two files names is declared ([deps] for src/, [deps] ∪ [weakdeps] ∪ the
     package itself for ext/), every dependency has a [compat] entry, the extension's trigger is a weak dependency, and the
     UUIDs that can be checked against the reference's manifests agree with them."""
@@ -294,17 +295,13 @@ def test_julia_package_manifest_declares_what_the_sources_load():
     for d in list(deps) + list(weak):
         assert d in proj["compat"], f"no [compat] entry for {d}"
     assert "julia" in proj["compat"]
-    ref = "/root/reference"
-    if os.path.isdir(ref):   # the UUIDs the reference's own manifests carry
-        known = {}
-        for rel in ("Project.toml", "lib/NonlinearSolveBase/Project.toml", "lib/SciMLJacobianOperators/Project.toml"):
-            t = tomli.load(open(os.path.join(ref, rel), "rb"))
-            known[t["name"]] = t["uuid"]
-            for sec in ("deps", "weakdeps", "extras"):
-                known.update(t.get(sec, {}))
-        for d, u in deps.items():
-            assert d in known and known[d] == u, f"[deps] {d}: {u} vs the reference's {known.get(d)}"
-        assert proj["compat"]["LinearSolve"] == tomli.load(open(os.path.join(ref, "Project.toml"), "rb"))["compat"]["LinearSolve"]
+    # the UUIDs the reference's own manifests carry (Project.toml, lib/NonlinearSolveBase, lib/SciMLJacobianOperators), read
+    # into tests/golden/reference_api.json by tests/golden/make_reference_api.py
+    api = json.load(open(os.path.join(root, "tests", "golden", "reference_api.json"), encoding="utf-8"))
+    known = api["manifest_uuids"]
+    for d, u in deps.items():
+        assert d in known and known[d] == u, f"[deps] {d}: {u} vs the reference's {known.get(d)}"
+    assert proj["compat"]["LinearSolve"] == api["LinearSolve_compat"]
     # the ADVICE r03 finding: the device trampolines order their work on the stream the library hands over
     extsrc = open(os.path.join(root, "julia", "ext", "MI355XNewtonKrylovAMDGPUExt.jl")).read()
     for tr in ("device_matvec_trampoline", "device_prec_trampoline"):

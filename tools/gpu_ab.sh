@@ -13,7 +13,7 @@ mkdir -p gpurun_out
 : > $OUT
 for r in $(seq 1 $ROUNDS); do
   for v in "${VARS[@]}"; do
-    line=$(env $v timeout 300 python bench.py --steps 300 --warmup 20 --cpu-seconds 0 --no-profile-pass --no-ttt --no-spmv-hbm --pmc off "$@" 2>/dev/null | tail -1)
+    line=$(env $v timeout 300 python bench.py --full --steps 300 --warmup 20 --cpu-seconds 0 --no-profile-pass --no-ttt --no-spmv-hbm --pmc off "$@" 2>/dev/null | tail -1)
     python - "$v" "$line" >> $OUT <<'PY'
 import json, sys
 v, line = sys.argv[1], sys.argv[2]

@@ -11,25 +11,25 @@ O=gpurun_out/$TAG; mkdir -p $O
 timeout 1500 python -m pytest tests -m gpu -q < /dev/null > $O/pytest_gpu.log 2>&1; tail -5 $O/pytest_gpu.log
 timeout 120 python -c "import __graft_entry__ as g; g.smoke()" < /dev/null 2>&1 | tail -1 | tee $O/smoke.txt
 B0="--cpu-seconds 0 --no-ttt --no-spmv-hbm --pmc off --steps 100 --warmup 10"
-timeout 700 python bench.py < /dev/null > $O/bench_csr.json 2> $O/bench_csr.err
-NK_SS_IMPLICIT=0 timeout 200 python bench.py $B0 < /dev/null > $O/bench_csr_explicit_second_pass.json 2> /dev/null
+timeout 700 python bench.py --full < /dev/null > $O/bench_csr.json 2> $O/bench_csr.err
+NK_SS_IMPLICIT=0 timeout 200 python bench.py --full $B0 < /dev/null > $O/bench_csr_explicit_second_pass.json 2> /dev/null
 B="--cpu-seconds 0 --no-ttt --no-spmv-hbm --pmc off --steps 100 --warmup 10"
-NK_SPMV_POWERS=0 timeout 200 python bench.py $B < /dev/null > $O/bench_csr_streaming_spmv.json 2> /dev/null
-timeout 200 python bench.py $B --matfree < /dev/null > $O/bench_matfree.json 2> /dev/null
-timeout 200 python bench.py $B --workload c5 < /dev/null > $O/bench_c5_1gpu.json 2> /dev/null
-NK_SPMV_POWERS=0 timeout 200 python bench.py $B --workload c5 < /dev/null > $O/bench_c5_1gpu_streaming_spmv.json 2> /dev/null
-NK_SS_MM=0 NK_SS_KCONST=0 timeout 200 python bench.py $B0 < /dev/null > $O/bench_csr_round3_sweeps.json 2> /dev/null
+NK_SPMV_POWERS=0 timeout 200 python bench.py --full $B < /dev/null > $O/bench_csr_streaming_spmv.json 2> /dev/null
+timeout 200 python bench.py --full $B --matfree < /dev/null > $O/bench_matfree.json 2> /dev/null
+timeout 200 python bench.py --full $B --workload c5 < /dev/null > $O/bench_c5_1gpu.json 2> /dev/null
+NK_SPMV_POWERS=0 timeout 200 python bench.py --full $B --workload c5 < /dev/null > $O/bench_c5_1gpu_streaming_spmv.json 2> /dev/null
+NK_SS_MM=0 NK_SS_KCONST=0 timeout 200 python bench.py --full $B0 < /dev/null > $O/bench_csr_round3_sweeps.json 2> /dev/null
 ( echo "== round-3 sweep kernels (NK_SS_MM=0 NK_SS_KCONST=0)"; NK_SS_MM=0 NK_SS_KCONST=0 timeout 200 python tools/sweep_shapes_bench.py 1048576 16777216 2>&1 | grep sweep;
   echo "== round-4 sweep kernels (default)"; timeout 200 python tools/sweep_shapes_bench.py 1048576 16777216 2>&1 | grep sweep ) > $O/sweep_shapes.txt
 if [ "$MODE" = "full" ]; then
-  timeout 200 python bench.py $B --ortho dcgs2 < /dev/null > $O/bench_csr_dcgs2.json 2> /dev/null
-  timeout 300 python bench.py $B --workload c4 --steps 10 --warmup 2 < /dev/null > $O/bench_c4size_1gpu.json 2> /dev/null
+  timeout 200 python bench.py --full $B --ortho dcgs2 < /dev/null > $O/bench_csr_dcgs2.json 2> /dev/null
+  timeout 300 python bench.py --full $B --workload c4 --steps 10 --warmup 2 < /dev/null > $O/bench_c4size_1gpu.json 2> /dev/null
   timeout 700 bash tools/profile_round.sh ${TAG}_c4size_1gpu --workload c4 --steps 4 --warmup 1 < /dev/null
   timeout 300 python tools/spmv_bench.py 100 < /dev/null > $O/spmv_bench.jsonl 2>/dev/null
   timeout 300 python tools/amg_time.py < /dev/null > $O/amg_time.txt 2>&1
   timeout 200 python tools/ss_stamps.py < /dev/null > $O/ss_stamps.txt 2>/dev/null
   for n in 2 8; do
-    BENCH_BACKEND=gloo NK_COMM=peer timeout 500 python bench.py --gpus $n --steps 20 --warmup 3 $B --no-weak < /dev/null > $O/bench_x${n}_peer_shared_gpu.json 2> $O/bench_x${n}.err
+    BENCH_BACKEND=gloo NK_COMM=peer timeout 500 python bench.py --full --gpus $n --steps 20 --warmup 3 $B --no-weak < /dev/null > $O/bench_x${n}_peer_shared_gpu.json 2> $O/bench_x${n}.err
   done
 fi
 timeout 500 bash tools/profile_round.sh ${TAG} < /dev/null

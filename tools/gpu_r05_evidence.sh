@@ -7,15 +7,15 @@ TAG=${1:-r05_z}
 cd $GRAFT_REPO_ROOT
 O=gpurun_out/$TAG; mkdir -p $O
 timeout 60 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > $O/smoke.log 2>&1; tail -2 $O/smoke.log
-timeout 300 python bench.py < /dev/null > $O/bench_default.json 2> $O/bench_default.err; tail -c 400 $O/bench_default.json
+timeout 300 python bench.py --full < /dev/null > $O/bench_default.json 2> $O/bench_default.err; tail -c 400 $O/bench_default.json
 timeout 200 bash tools/profile_round.sh ${TAG} < /dev/null
 timeout 120 bash tools/step_timeline.sh ${TAG} < /dev/null | head -24
 B="--cpu-seconds 0 --no-ttt --no-spmv-hbm --pmc off --steps 200 --warmup 20 --no-profile-pass"
-timeout 100 python bench.py $B --matfree < /dev/null > $O/bench_matfree.json 2> /dev/null
-timeout 100 python bench.py $B --workload c5 < /dev/null > $O/bench_c5.json 2> /dev/null
-NK_SS_HOST_A=0 NK_FUSED_UPDATE=0 NK_FUSED_RESIDUAL_NORMS=0 NK_PRELOADED_RHS=0 timeout 100 python bench.py $B < /dev/null > $O/bench_without_late_round5_fusions.json 2> /dev/null
-NK_SS_DEFER=0 NK_SS_HOST_A=0 NK_FUSED_UPDATE=0 NK_FUSED_RESIDUAL_NORMS=0 NK_PRELOADED_RHS=0 timeout 100 python bench.py $B < /dev/null > $O/bench_round4_dispatch.json 2> /dev/null
-timeout 100 python bench.py --workload c4 --steps 10 --warmup 2 --cpu-seconds 0 --no-ttt --no-spmv-hbm --pmc off --no-profile-pass < /dev/null > $O/bench_c4size_1gpu.json 2> /dev/null
+timeout 100 python bench.py --full $B --matfree < /dev/null > $O/bench_matfree.json 2> /dev/null
+timeout 100 python bench.py --full $B --workload c5 < /dev/null > $O/bench_c5.json 2> /dev/null
+NK_SS_HOST_A=0 NK_FUSED_UPDATE=0 NK_FUSED_RESIDUAL_NORMS=0 NK_PRELOADED_RHS=0 timeout 100 python bench.py --full $B < /dev/null > $O/bench_without_late_round5_fusions.json 2> /dev/null
+NK_SS_DEFER=0 NK_SS_HOST_A=0 NK_FUSED_UPDATE=0 NK_FUSED_RESIDUAL_NORMS=0 NK_PRELOADED_RHS=0 timeout 100 python bench.py --full $B < /dev/null > $O/bench_round4_dispatch.json 2> /dev/null
+timeout 100 python bench.py --full --workload c4 --steps 10 --warmup 2 --cpu-seconds 0 --no-ttt --no-spmv-hbm --pmc off --no-profile-pass < /dev/null > $O/bench_c4size_1gpu.json 2> /dev/null
 for g in 512 1024 2048; do timeout 60 python tools/amg_setup_time.py $g 2>&1 | tail -2; done > $O/amg_setup.txt; cat $O/amg_setup.txt
 timeout 100 python tools/amg_time.py > $O/amg_time.txt 2>&1; tail -9 $O/amg_time.txt
 for f in $O/bench_*.json; do python -c "
