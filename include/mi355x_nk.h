@@ -626,19 +626,33 @@ int nk_newton_solve(nk_problem *P, const double *u0, int memspace, const nk_opti
  * SimpleNewtonRaphson (lib/SimpleNonlinearSolve/src/raphson.jl:39-83) for thousands of small (n ≤ 64) systems
  * f(u, p_b) = 0, one system per GPU thread. `source` is HIP C++ defining
  *     template <typename T> __device__ void nk_f(const T *u, const double *p, T *f);
- * (and, with flags & 1, `__device__ void nk_jac(const double *u, const double *p, double *J)`, row-major n×n). It is
- * compiled at run time (hiprtc, gfx950) with the solver kernel; without nk_jac the Jacobian comes from forward-mode dual
- * numbers (AutoForwardDiff, the reference default). Semantics per system: iszero(f(u0)) ⇒ Success; δ = J \ f (partial
+ * (and, with flags & NK_BATCH_ANALYTIC_JAC, `__device__ void nk_jac(const double *u, const double *p, double *J)`, row-major
+ * n×n). It is compiled at run time (hiprtc, gfx950) with the solver kernel; without nk_jac the Jacobian comes from forward-mode
+ * dual numbers (AutoForwardDiff, the reference default). Semantics per system: iszero(f(u0)) ⇒ Success; δ = J \ f (partial
  * pivoting), u −= δ, then AbsNormTerminationMode(maximum∘abs) on the residual of the previous iterate; default abstol
  * eps^(4/5), maxiters 1000; per-system retcode (NK_RET_SUCCESS | NK_RET_MAXITERS) and iteration count.
- * nk_batch_compile_check compiles only (no device needed). */
+ * Float32 (flags & NK_BATCH_FLOAT32, the tutorial's element type): every kernel runs in single precision, constants and the
+ * default abstol eps(Float32)^(4/5) = 2.8909994e-6 included. The source then writes `nk_real` (= float) where it wrote double:
+ *     template <typename T> __device__ void nk_f(const T *u, const nk_real *p, T *f);
+ *     __device__ void nk_jac(const nk_real *u, const nk_real *p, nk_real *J);
+ * (a source written with nk_real compiles in both modes; one written with `const double *p` fails in Float32 mode with the
+ * contract in nk_last_error). Such an object is solved through the _f32 entry points, which take float arrays; scalar
+ * arguments stay double and are rounded to float (T(abstol)). Calling an object through the other precision's entry point is
+ * NK_E_INVALID. nk_batch_compile_check compiles only (no device needed). */
+enum { NK_BATCH_ANALYTIC_JAC = 1, NK_BATCH_FLOAT32 = 2 };   /* bits of `flags` */
 int nk_batch_compile_check(const char *source, int n, int nparams, int flags, int64_t *code_bytes);
+/* the compiled code object of one kernel set (wave = 0: nk_batch_newton and nk_batch_trust_region; 1: the one-system-per-
+ * wavefront nk_batch_newton_wave), for inspection; *bytes gets its size, buf = NULL asks for the size only */
+int nk_batch_code_object(const char *source, int n, int nparams, int flags, int wave, void *buf, int64_t capacity,
+                         int64_t *bytes);
 int nk_batch_create(nk_ctx *ctx, const char *source, int n, int nparams, int flags, nk_batch **out);
 int nk_batch_destroy(nk_batch *B);
 /* u0: n doubles shared by all systems (u0_per_system = 0) or nbatch×n; p: nbatch×nparams; outputs nbatch×n, nbatch×n,
  * nbatch, nbatch (retcode/iters nullable); abstol ≤ 0 and maxiters ≤ 0 select the defaults. */
 int nk_batch_solve(nk_batch *B, int64_t nbatch, const double *u0, int u0_per_system, const double *p, int memspace,
                    double abstol, int maxiters, double *u_out, double *resid_out, int32_t *retcode_out, int32_t *iters_out);
+int nk_batch_solve_f32(nk_batch *B, int64_t nbatch, const float *u0, int u0_per_system, const float *p, int memspace,
+                       double abstol, int maxiters, float *u_out, float *resid_out, int32_t *retcode_out, int32_t *iters_out);
 /* SimpleTrustRegion (lib/SimpleNonlinearSolve/src/trust_region.jl:57-229, default radius update) per system; thresholds and
  * factors ≤ 0, max_shrink_times < 0 select the reference defaults (1e-4, 0.25, 0.75, 0.25, 2, 32). Retcodes: NK_RET_SUCCESS,
  * NK_RET_MAXITERS, NK_RET_SHRINK_THRESHOLD_EXCEEDED. */
@@ -646,6 +660,10 @@ int nk_batch_solve_trust_region(nk_batch *B, int64_t nbatch, const double *u0, i
                                 double abstol, int maxiters, double step_threshold, double shrink_threshold,
                                 double expand_threshold, double shrink_factor, double expand_factor, int max_shrink_times,
                                 double *u_out, double *resid_out, int32_t *retcode_out, int32_t *iters_out);
+int nk_batch_solve_trust_region_f32(nk_batch *B, int64_t nbatch, const float *u0, int u0_per_system, const float *p,
+                                    int memspace, double abstol, int maxiters, double step_threshold, double shrink_threshold,
+                                    double expand_threshold, double shrink_factor, double expand_factor, int max_shrink_times,
+                                    float *u_out, float *resid_out, int32_t *retcode_out, int32_t *iters_out);
 
 /* ---------------------------------------------------------------- BLAS-1 building blocks (exported for
  * the bench / tests; all on the ctx stream, results of reductions are all-reduced over the ranks) */

@@ -586,15 +586,24 @@ end
 # (docs/src/tutorials/nonlinear_solve_gpus.md:106-114) behind one ccall: `f_source` is HIP C++ defining
 # `template <typename T> __device__ void nk_f(const T *u, const double *p, T *f)`; hiprtc specialises it into the solver kernel
 # the way GPUCompiler specialises a Julia `f` into the KernelAbstractions kernel. p: nparams × nbatch (one column per system).
+# `eltype = Float32` (the tutorial's element type) builds the kernels in single precision: the source then takes
+# `const nk_real *p` (nk_real = float, and `nk_jac(const nk_real *u, const nk_real *p, nk_real *J)` with has_jac), and the
+# object is solved with Float32 arrays, constants and default abstol eps(Float32)^(4/5).
+const NK_BATCH_ANALYTIC_JAC = Cint(1)
+const NK_BATCH_FLOAT32 = Cint(2)
+
 mutable struct EnsembleKernel
     ptr::Ptr{Cvoid}
     n::Int
     nparams::Int
-    function EnsembleKernel(ctx::Ctx, f_source::String, n::Integer, nparams::Integer; has_jac::Bool = false)
+    eltype::DataType
+    function EnsembleKernel(ctx::Ctx, f_source::String, n::Integer, nparams::Integer; has_jac::Bool = false,
+            eltype::Type{<:Union{Float32, Float64}} = Float64)
         h = Ref{Ptr{Cvoid}}(C_NULL)
+        flags = (has_jac ? NK_BATCH_ANALYTIC_JAC : Cint(0)) | (eltype === Float32 ? NK_BATCH_FLOAT32 : Cint(0))
         nkcheck(@ccall libnk.nk_batch_create(ctx.ptr::Ptr{Cvoid}, f_source::Cstring, n::Cint, nparams::Cint,
-            (has_jac ? 1 : 0)::Cint, h::Ptr{Ptr{Cvoid}})::Cint)
-        k = new(h[], n, nparams)
+            flags::Cint, h::Ptr{Ptr{Cvoid}})::Cint)
+        k = new(h[], n, nparams, eltype)
         finalizer(x -> @ccall(libnk.nk_batch_destroy(x.ptr::Ptr{Cvoid})::Cint), k)
         return k
     end
@@ -615,6 +624,28 @@ function vectorized_solve(k::EnsembleKernel, u0::Vector{Float64}, p::Matrix{Floa
     GC.@preserve u0 p u resid rc iters nkcheck(@ccall libnk.nk_batch_solve(k.ptr::Ptr{Cvoid}, nb::Int64,
         u0::Ptr{Float64}, 0::Cint, p::Ptr{Float64}, 0::Cint, abstol::Float64, maxiters::Cint, u::Ptr{Float64},
         resid::Ptr{Float64}, rc::Ptr{Int32}, iters::Ptr{Int32})::Cint)
+    return (; u, resid, retcode = [RETCODES[c + 1] for c in rc], iters)
+end
+
+# Float32 (the tutorial's `rand(Float32, 4)` parameters and `SA[1.0f0, 2.0f0, 3.0f0, 4.0f0]`): results in Float32. The scalar
+# arguments stay Float64 at the ABI; the library takes them as T(abstol), as the reference does.
+function vectorized_solve(k::EnsembleKernel, u0::Vector{Float32}, p::Matrix{Float32}; alg = :SimpleNewtonRaphson,
+        abstol = 0.0, maxiters = 1000)
+    k.eltype === Float32 || throw(ArgumentError("this EnsembleKernel was built for $(k.eltype): build it with eltype = Float32"))
+    nb = size(p, 2)
+    u = Matrix{Float32}(undef, k.n, nb); resid = similar(u)
+    rc = Vector{Int32}(undef, nb); iters = Vector{Int32}(undef, nb)
+    tol = Float64(abstol)
+    if alg === :SimpleTrustRegion
+        GC.@preserve u0 p u resid rc iters nkcheck(@ccall libnk.nk_batch_solve_trust_region_f32(k.ptr::Ptr{Cvoid}, nb::Int64,
+            u0::Ptr{Float32}, 0::Cint, p::Ptr{Float32}, 0::Cint, tol::Float64, maxiters::Cint, (-1.0)::Float64,
+            (-1.0)::Float64, (-1.0)::Float64, (-1.0)::Float64, (-1.0)::Float64, (-1)::Cint, u::Ptr{Float32},
+            resid::Ptr{Float32}, rc::Ptr{Int32}, iters::Ptr{Int32})::Cint)
+        return (; u, resid, retcode = [RETCODES[c + 1] for c in rc], iters)
+    end
+    GC.@preserve u0 p u resid rc iters nkcheck(@ccall libnk.nk_batch_solve_f32(k.ptr::Ptr{Cvoid}, nb::Int64,
+        u0::Ptr{Float32}, 0::Cint, p::Ptr{Float32}, 0::Cint, tol::Float64, maxiters::Cint, u::Ptr{Float32},
+        resid::Ptr{Float32}, rc::Ptr{Int32}, iters::Ptr{Int32})::Cint)
     return (; u, resid, retcode = [RETCODES[c + 1] for c in rc], iters)
 end
 

@@ -17,6 +17,7 @@ class NKError(RuntimeError):
 
 # ---------------------------------------------------------------------------- enums (mirror the header)
 HOST, DEVICE = 0, 1
+BATCH_ANALYTIC_JAC, BATCH_FLOAT32 = 1, 2   # nk_batch_create / nk_batch_compile_check flags
 RET_NAMES = ["Default", "Success", "MaxIters", "Unstable", "Stalled", "InternalLinearSolveFailed",
              "ShrinkThresholdExceeded", "MaxTime", "Failure", "InternalLineSearchFailed"]
 PROBLEM_QUADRATIC, PROBLEM_BRATU2D, PROBLEM_BRUSSELATOR2D, PROBLEM_USER = 1, 2, 3, 100
@@ -211,6 +212,9 @@ SIGNATURES = {
     "nk_batch_destroy": (_I, [_P]),
     "nk_batch_solve": (_I, [_P, _L, _P, _I, _P, _I, _D, _I, _P, _P, _P, _P]),
     "nk_batch_solve_trust_region": (_I, [_P, _L, _P, _I, _P, _I, _D, _I, _D, _D, _D, _D, _D, _I, _P, _P, _P, _P]),
+    "nk_batch_solve_f32": (_I, [_P, _L, _P, _I, _P, _I, _D, _I, _P, _P, _P, _P]),
+    "nk_batch_solve_trust_region_f32": (_I, [_P, _L, _P, _I, _P, _I, _D, _I, _D, _D, _D, _D, _D, _I, _P, _P, _P, _P]),
+    "nk_batch_code_object": (_I, [C.c_char_p, _I, _I, _I, _I, _P, _L, C.POINTER(_L)]),
     "nk_options_default": (_I, [C.POINTER(Options)]),
     "nk_solver_init": (_I, [_P, _P, _I, C.POINTER(Options), _PP]),
     "nk_solver_destroy": (_I, [_P]),

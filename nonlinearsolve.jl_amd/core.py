@@ -1489,11 +1489,17 @@ class ImmutableNonlinearProblem:
     """SciMLBase.ImmutableNonlinearProblem{false}(f, u0, p) for the kernel-generation path
     (docs/src/tutorials/nonlinear_solve_gpus.md:120-140). `f_source` is HIP C++ defining
     `template <typename T> __device__ void nk_f(const T *u, const double *p, T *f)`; `u0` has n entries (shared by
-    every system) or shape (nbatch, n); `p` has shape (nbatch, nparams) — one parameter set per system."""
+    every system) or shape (nbatch, n); `p` has shape (nbatch, nparams) — one parameter set per system.
 
-    def __init__(self, f_source: str, u0, p, ctx: Optional[Context] = None):
+    `eltype=None` solves in Float64 whatever the inputs' dtype. `eltype=float32` (numpy, torch or "float32") solves in
+    Float32, the tutorial's element type (nonlinear_solve_gpus.md:146-160): the kernels, constants and default abstol
+    (eps(Float32)^(4/5)) are single precision, the source writes `const nk_real *p` (nk_real = float), and `u` / `resid`
+    come back as float32."""
+
+    def __init__(self, f_source: str, u0, p, ctx: Optional[Context] = None, eltype=None):
         self.f_source, self.ctx = f_source, ctx or default_context()
         self.u0, self.p = u0, p
+        self.float32 = _is_float32(eltype)
         pshape = tuple(p.shape)
         if len(pshape) != 2:
             raise ValueError("p must have shape (nbatch, nparams)")
@@ -1514,6 +1520,17 @@ class EnsembleSolution:
     retcode_raw: np.ndarray = None
 
 
+def _is_float32(eltype) -> bool:
+    if eltype is None or eltype in (np.float64, "float64") or (torch is not None and eltype is torch.float64):
+        return False
+    if eltype in (np.float32, "float32") or (torch is not None and eltype is torch.float32) or \
+            (isinstance(eltype, np.dtype) and eltype == np.float32):
+        return True
+    if isinstance(eltype, np.dtype) and eltype == np.float64:
+        return False
+    raise ValueError(f"eltype {eltype!r}: the ensemble solvers work in float64 (None) or float32")
+
+
 class _BatchKernel:
     _cache: dict = {}
 
@@ -1529,38 +1546,45 @@ class _BatchKernel:
 
 def vectorized_solve(prob: ImmutableNonlinearProblem, alg=None, abstol=None, maxiters=1000):
     """`vectorized_solve(prob, alg; backend = ROCBackend())` of the tutorial (nonlinear_solve_gpus.md:106-114): solve
-    every parameter set with SimpleNewtonRaphson, one system per GPU thread, in one kernel launch."""
+    every parameter set with SimpleNewtonRaphson, one system per GPU thread, in one kernel launch. The problem's eltype
+    picks the precision (Float64 unless it was built with eltype=float32)."""
     alg = alg or SimpleNewtonRaphson()
-    h = _BatchKernel.get(prob.ctx, prob.f_source, prob.n, prob.nparams, 1 if alg.jac else 0)
+    f32 = prob.float32
+    flags = (L.BATCH_ANALYTIC_JAC if alg.jac else 0) | (L.BATCH_FLOAT32 if f32 else 0)
+    h = _BatchKernel.get(prob.ctx, prob.f_source, prob.n, prob.nparams, flags)
     on_dev = _is_torch(prob.p) and prob.p.is_cuda
     nb, n = prob.nbatch, prob.n
     if on_dev:
+        tdt = torch.float32 if f32 else torch.float64
         u0 = prob.u0 if (_is_torch(prob.u0) and prob.u0.is_cuda) else torch.as_tensor(np.asarray(prob.u0), device=prob.p.device)
-        u0 = u0.to(torch.float64).contiguous()
-        pp = prob.p.to(torch.float64).contiguous()
-        u = torch.empty((nb, n), dtype=torch.float64, device=pp.device)
+        u0 = u0.to(tdt).contiguous()
+        pp = prob.p.to(tdt).contiguous()
+        u = torch.empty((nb, n), dtype=tdt, device=pp.device)
         r = torch.empty_like(u)
         rc = torch.empty(nb, dtype=torch.int32, device=pp.device)
         it = torch.empty(nb, dtype=torch.int32, device=pp.device)
         ptr = lambda x: C.c_void_p(x.data_ptr())
         ms = L.DEVICE
     else:
-        u0 = np.ascontiguousarray(np.asarray(prob.u0.cpu() if _is_torch(prob.u0) else prob.u0), dtype=np.float64)
-        pp = np.ascontiguousarray(np.asarray(prob.p.cpu() if _is_torch(prob.p) else prob.p), dtype=np.float64)
-        u, r = np.empty((nb, n)), np.empty((nb, n))
+        ndt = np.float32 if f32 else np.float64
+        u0 = np.ascontiguousarray(np.asarray(prob.u0.cpu() if _is_torch(prob.u0) else prob.u0), dtype=ndt)
+        pp = np.ascontiguousarray(np.asarray(prob.p.cpu() if _is_torch(prob.p) else prob.p), dtype=ndt)
+        u, r = np.empty((nb, n), dtype=ndt), np.empty((nb, n), dtype=ndt)
         rc, it = np.empty(nb, dtype=np.int32), np.empty(nb, dtype=np.int32)
         ptr = lambda x: C.c_void_p(x.ctypes.data)
         ms = L.HOST
     if isinstance(alg, SimpleTrustRegion):
         d = lambda v: -1.0 if v is None else float(v)
-        check(L.lib().nk_batch_solve_trust_region(h, nb, ptr(u0), 1 if prob.u0_per_system else 0, ptr(pp), ms,
-                                                  0.0 if abstol is None else float(abstol), int(maxiters),
-                                                  d(alg.step_threshold), d(alg.shrink_threshold), d(alg.expand_threshold),
-                                                  d(alg.shrink_factor), d(alg.expand_factor), int(alg.max_shrink_times),
-                                                  ptr(u), ptr(r), ptr(rc), ptr(it)))
+        solve_tr = L.lib().nk_batch_solve_trust_region_f32 if f32 else L.lib().nk_batch_solve_trust_region
+        check(solve_tr(h, nb, ptr(u0), 1 if prob.u0_per_system else 0, ptr(pp), ms,
+                       0.0 if abstol is None else float(abstol), int(maxiters),
+                       d(alg.step_threshold), d(alg.shrink_threshold), d(alg.expand_threshold),
+                       d(alg.shrink_factor), d(alg.expand_factor), int(alg.max_shrink_times),
+                       ptr(u), ptr(r), ptr(rc), ptr(it)))
     else:
-        check(L.lib().nk_batch_solve(h, nb, ptr(u0), 1 if prob.u0_per_system else 0, ptr(pp), ms,
-                                     0.0 if abstol is None else float(abstol), int(maxiters), ptr(u), ptr(r), ptr(rc), ptr(it)))
+        solve = L.lib().nk_batch_solve_f32 if f32 else L.lib().nk_batch_solve
+        check(solve(h, nb, ptr(u0), 1 if prob.u0_per_system else 0, ptr(pp), ms,
+                    0.0 if abstol is None else float(abstol), int(maxiters), ptr(u), ptr(r), ptr(rc), ptr(it)))
     rch = rc.cpu().numpy() if on_dev else rc
     ith = it.cpu().numpy() if on_dev else it
     return EnsembleSolution(u, r, np.asarray(L.RET_NAMES)[rch], ith.copy(), rch.copy())

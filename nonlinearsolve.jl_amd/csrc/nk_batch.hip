@@ -22,14 +22,21 @@
 
 // ----------------------------------------------------------------------------- device source (compiled by hiprtc)
 static const char *k_prelude = R"NKSRC(
+// ---- the working precision: -DNK_F32 builds every solver kernel in single precision (flags & NK_BATCH_FLOAT32)
+#ifdef NK_F32
+typedef float nk_real;
+#else
+typedef double nk_real;
+#endif
+#define NK_R(x) ((nk_real)(x))
 // ---- forward-mode dual numbers with NK_CH partials (ForwardDiff.Dual analogue)
 struct Dual {
-  double v;
-  double d[NK_CH];
+  nk_real v;
+  nk_real d[NK_CH];
   __device__ Dual() {}
-  __device__ Dual(double x) : v(x) {
+  __device__ Dual(nk_real x) : v(x) {
 #pragma unroll
-    for (int k = 0; k < NK_CH; ++k) d[k] = 0.0;
+    for (int k = 0; k < NK_CH; ++k) d[k] = NK_R(0);
   }
 };
 #define NK_DUAL_LOOP _Pragma("unroll") for (int k = 0; k < NK_CH; ++k)
@@ -38,18 +45,19 @@ __device__ inline Dual operator-(const Dual &a, const Dual &b) { Dual r; r.v = a
 __device__ inline Dual operator-(const Dual &a) { Dual r; r.v = -a.v; NK_DUAL_LOOP r.d[k] = -a.d[k]; return r; }
 __device__ inline Dual operator*(const Dual &a, const Dual &b) { Dual r; r.v = a.v * b.v; NK_DUAL_LOOP r.d[k] = a.d[k] * b.v + a.v * b.d[k]; return r; }
 __device__ inline Dual operator/(const Dual &a, const Dual &b) {
-  Dual r; const double ib = 1.0 / b.v; r.v = a.v * ib;
+  Dual r; const nk_real ib = NK_R(1) / b.v; r.v = a.v * ib;
   NK_DUAL_LOOP r.d[k] = (a.d[k] - r.v * b.d[k]) * ib;
   return r;
 }
-__device__ inline Dual operator+(const Dual &a, double b) { Dual r = a; r.v += b; return r; }
-__device__ inline Dual operator+(double b, const Dual &a) { Dual r = a; r.v += b; return r; }
-__device__ inline Dual operator-(const Dual &a, double b) { Dual r = a; r.v -= b; return r; }
-__device__ inline Dual operator-(double b, const Dual &a) { Dual r = -a; r.v += b; return r; }
-__device__ inline Dual operator*(const Dual &a, double b) { Dual r; r.v = a.v * b; NK_DUAL_LOOP r.d[k] = a.d[k] * b; return r; }
-__device__ inline Dual operator*(double b, const Dual &a) { return a * b; }
-__device__ inline Dual operator/(const Dual &a, double b) { return a * (1.0 / b); }
-__device__ inline Dual operator/(double b, const Dual &a) { return Dual(b) / a; }
+// scalar operands are taken in nk_real, so that `0.05 * u[i]` stays in the working precision on the dual path
+__device__ inline Dual operator+(const Dual &a, nk_real b) { Dual r = a; r.v += b; return r; }
+__device__ inline Dual operator+(nk_real b, const Dual &a) { Dual r = a; r.v += b; return r; }
+__device__ inline Dual operator-(const Dual &a, nk_real b) { Dual r = a; r.v -= b; return r; }
+__device__ inline Dual operator-(nk_real b, const Dual &a) { Dual r = -a; r.v += b; return r; }
+__device__ inline Dual operator*(const Dual &a, nk_real b) { Dual r; r.v = a.v * b; NK_DUAL_LOOP r.d[k] = a.d[k] * b; return r; }
+__device__ inline Dual operator*(nk_real b, const Dual &a) { return a * b; }
+__device__ inline Dual operator/(const Dual &a, nk_real b) { return a * (NK_R(1) / b); }
+__device__ inline Dual operator/(nk_real b, const Dual &a) { return Dual(b) / a; }
 __device__ inline Dual &operator+=(Dual &a, const Dual &b) { a = a + b; return a; }
 __device__ inline Dual &operator-=(Dual &a, const Dual &b) { a = a - b; return a; }
 __device__ inline Dual &operator*=(Dual &a, const Dual &b) { a = a * b; return a; }
@@ -58,18 +66,21 @@ __device__ inline bool operator<(const Dual &a, const Dual &b) { return a.v < b.
 __device__ inline bool operator>(const Dual &a, const Dual &b) { return a.v > b.v; }
 __device__ inline bool operator<=(const Dual &a, const Dual &b) { return a.v <= b.v; }
 __device__ inline bool operator>=(const Dual &a, const Dual &b) { return a.v >= b.v; }
-__device__ inline Dual nk_chain(const Dual &a, double fv, double dfv) { Dual r; r.v = fv; NK_DUAL_LOOP r.d[k] = dfv * a.d[k]; return r; }
-__device__ inline Dual sqrt(const Dual &a) { const double s = sqrt(a.v); return nk_chain(a, s, 0.5 / s); }
-__device__ inline Dual exp(const Dual &a) { const double e = exp(a.v); return nk_chain(a, e, e); }
-__device__ inline Dual log(const Dual &a) { return nk_chain(a, log(a.v), 1.0 / a.v); }
+__device__ inline Dual nk_chain(const Dual &a, nk_real fv, nk_real dfv) { Dual r; r.v = fv; NK_DUAL_LOOP r.d[k] = dfv * a.d[k]; return r; }
+__device__ inline Dual sqrt(const Dual &a) { const nk_real s = sqrt(a.v); return nk_chain(a, s, NK_R(0.5) / s); }
+__device__ inline Dual exp(const Dual &a) { const nk_real e = exp(a.v); return nk_chain(a, e, e); }
+__device__ inline Dual log(const Dual &a) { return nk_chain(a, log(a.v), NK_R(1) / a.v); }
 __device__ inline Dual sin(const Dual &a) { return nk_chain(a, sin(a.v), cos(a.v)); }
 __device__ inline Dual cos(const Dual &a) { return nk_chain(a, cos(a.v), -sin(a.v)); }
-__device__ inline Dual tan(const Dual &a) { const double t = tan(a.v); return nk_chain(a, t, 1.0 + t * t); }
-__device__ inline Dual tanh(const Dual &a) { const double t = tanh(a.v); return nk_chain(a, t, 1.0 - t * t); }
-__device__ inline Dual atan(const Dual &a) { return nk_chain(a, atan(a.v), 1.0 / (1.0 + a.v * a.v)); }
-__device__ inline Dual fabs(const Dual &a) { return nk_chain(a, fabs(a.v), a.v < 0.0 ? -1.0 : 1.0); }
-__device__ inline Dual pow(const Dual &a, double e) { const double pw = pow(a.v, e - 1.0); return nk_chain(a, pw * a.v, e * pw); }
-__device__ inline Dual pow(const Dual &a, int e) { return pow(a, (double)e); }
+__device__ inline Dual tan(const Dual &a) { const nk_real t = tan(a.v); return nk_chain(a, t, NK_R(1) + t * t); }
+__device__ inline Dual tanh(const Dual &a) { const nk_real t = tanh(a.v); return nk_chain(a, t, NK_R(1) - t * t); }
+__device__ inline Dual atan(const Dual &a) { return nk_chain(a, atan(a.v), NK_R(1) / (NK_R(1) + a.v * a.v)); }
+__device__ inline Dual fabs(const Dual &a) { return nk_chain(a, fabs(a.v), a.v < NK_R(0) ? NK_R(-1) : NK_R(1)); }
+__device__ inline Dual pow(const Dual &a, nk_real e) { const nk_real pw = pow(a.v, e - NK_R(1)); return nk_chain(a, pw * a.v, e * pw); }
+__device__ inline Dual pow(const Dual &a, int e) { return pow(a, (nk_real)e); }
+#ifdef NK_F32
+__device__ inline Dual pow(const Dual &a, double e) { return pow(a, (nk_real)e); }  // (else pow(u, 2.0) is ambiguous)
+#endif
 __device__ inline Dual pow(const Dual &a, const Dual &b) { return exp(b * log(a)); }
 )NKSRC";
 
@@ -80,7 +91,7 @@ static const char *k_kernel = R"NKSRC(
 #define NK_UNROLL _Pragma("nounroll")
 #endif
 
-__device__ inline void nk_jacobian(const double *x, const double *p, double (*J)[NK_N]) {
+__device__ inline void nk_jacobian(const nk_real *x, const nk_real *p, nk_real (*J)[NK_N]) {
 #ifdef NK_HAS_JAC
   nk_jac(x, p, &J[0][0]);  // user-supplied analytic Jacobian, row-major N×N (SciMLBase.has_jac, utils.jl:98-99)
 #else
@@ -89,7 +100,7 @@ __device__ inline void nk_jacobian(const double *x, const double *p, double (*J)
     Dual xd[NK_N], fd[NK_N];
     NK_UNROLL for (int i = 0; i < NK_N; ++i) {
       xd[i].v = x[i];
-      NK_DUAL_LOOP xd[i].d[k] = (i == c0 + k) ? 1.0 : 0.0;
+      NK_DUAL_LOOP xd[i].d[k] = (i == c0 + k) ? NK_R(1) : NK_R(0);
     }
     nk_f<Dual>(xd, p, fd);
     NK_UNROLL for (int i = 0; i < NK_N; ++i) {
@@ -100,12 +111,12 @@ __device__ inline void nk_jacobian(const double *x, const double *p, double (*J)
 }
 
 // dx = A \ b by Gaussian elimination with partial pivoting (A and b are destroyed)
-__device__ inline void nk_lu_solve(double (*A)[NK_N], double *b, double *dx) {
+__device__ inline void nk_lu_solve(nk_real (*A)[NK_N], nk_real *b, nk_real *dx) {
   NK_UNROLL for (int c = 0; c < NK_N; ++c) {
     int piv = c;
-    double best = fabs(A[c][c]);
+    nk_real best = fabs(A[c][c]);
     NK_UNROLL for (int r = c + 1; r < NK_N; ++r) {
-      const double v = fabs(A[r][c]);
+      const nk_real v = fabs(A[r][c]);
       if (v > best) { best = v; piv = r; }
     }
 #if NK_N <= 8
@@ -113,51 +124,51 @@ __device__ inline void nk_lu_solve(double (*A)[NK_N], double *b, double *dx) {
     NK_UNROLL for (int r = c + 1; r < NK_N; ++r) {
       const bool s = (r == piv);
       NK_UNROLL for (int k = c; k < NK_N; ++k) {
-        const double t1 = A[c][k], t2 = A[r][k];
+        const nk_real t1 = A[c][k], t2 = A[r][k];
         A[c][k] = s ? t2 : t1;
         A[r][k] = s ? t1 : t2;
       }
-      const double b1 = b[c], b2 = b[r];
+      const nk_real b1 = b[c], b2 = b[r];
       b[c] = s ? b2 : b1;
       b[r] = s ? b1 : b2;
     }
 #else
     if (piv != c) {
-      for (int k = c; k < NK_N; ++k) { const double t = A[c][k]; A[c][k] = A[piv][k]; A[piv][k] = t; }
-      const double t = b[c]; b[c] = b[piv]; b[piv] = t;
+      for (int k = c; k < NK_N; ++k) { const nk_real t = A[c][k]; A[c][k] = A[piv][k]; A[piv][k] = t; }
+      const nk_real t = b[c]; b[c] = b[piv]; b[piv] = t;
     }
 #endif
-    const double inv = 1.0 / A[c][c];
+    const nk_real inv = NK_R(1) / A[c][c];
     NK_UNROLL for (int r = c + 1; r < NK_N; ++r) {
-      const double l = A[r][c] * inv;
+      const nk_real l = A[r][c] * inv;
       NK_UNROLL for (int k = c + 1; k < NK_N; ++k) A[r][k] -= l * A[c][k];
       b[r] -= l * b[c];
     }
   }
   NK_UNROLL for (int r = NK_N - 1; r >= 0; --r) {
-    double s = b[r];
+    nk_real s = b[r];
     NK_UNROLL for (int k = r + 1; k < NK_N; ++k) s -= A[r][k] * dx[k];
     dx[r] = s / A[r][r];
   }
 }
 
 extern "C" __global__ void __launch_bounds__(NK_BLOCK_T)
-nk_batch_newton(long nbatch, const double *__restrict__ u0, int u0_per_system, const double *__restrict__ p, double abstol,
-                int maxiters, double *__restrict__ u_out, double *__restrict__ r_out, int *__restrict__ retcode,
+nk_batch_newton(long nbatch, const nk_real *__restrict__ u0, int u0_per_system, const nk_real *__restrict__ p, nk_real abstol,
+                int maxiters, nk_real *__restrict__ u_out, nk_real *__restrict__ r_out, int *__restrict__ retcode,
                 int *__restrict__ iters) {
   const long b = (long)blockIdx.x * NK_BLOCK_T + threadIdx.x;
   if (b >= nbatch) return;
-  double x[NK_N], fx[NK_N], dx[NK_N], pp[NK_NP > 0 ? NK_NP : 1];
+  nk_real x[NK_N], fx[NK_N], dx[NK_N], pp[NK_NP > 0 ? NK_NP : 1];
   NK_UNROLL for (int i = 0; i < NK_N; ++i) x[i] = u0[(u0_per_system ? b * NK_N : 0) + i];
   NK_UNROLL for (int i = 0; i < NK_NP; ++i) pp[i] = p[b * NK_NP + i];
-  nk_f<double>(x, pp, fx);
+  nk_f<nk_real>(x, pp, fx);
   bool allzero = true;
-  NK_UNROLL for (int i = 0; i < NK_N; ++i) allzero = allzero && (fx[i] == 0.0);
+  NK_UNROLL for (int i = 0; i < NK_N; ++i) allzero = allzero && (fx[i] == NK_R(0));
   int rc = 2 /* MaxIters */, it = 0;
   if (allzero) {
     rc = 1;  // Success (raphson.jl:55-56)
   } else {
-    double J[NK_N][NK_N], A[NK_N][NK_N], rhs[NK_N];
+    nk_real J[NK_N][NK_N], A[NK_N][NK_N], rhs[NK_N];
     nk_jacobian(x, pp, J);
     for (it = 1; it <= maxiters; ++it) {
       NK_UNROLL for (int i = 0; i < NK_N; ++i) {
@@ -168,11 +179,11 @@ nk_batch_newton(long nbatch, const double *__restrict__ u0, int u0_per_system, c
       NK_UNROLL for (int i = 0; i < NK_N; ++i) x[i] -= dx[i];
       // AbsNormTerminationMode(maximum∘abs) on the residual of the PREVIOUS iterate (the check precedes evaluate_f!!);
       // maximum propagates NaN, and NaN <= abstol is false
-      double nrm = 0.0;
+      nk_real nrm = NK_R(0);
       bool nan = false;
-      NK_UNROLL for (int i = 0; i < NK_N; ++i) { const double a = fabs(fx[i]); nan = nan || (a != a); nrm = a > nrm ? a : nrm; }
+      NK_UNROLL for (int i = 0; i < NK_N; ++i) { const nk_real a = fabs(fx[i]); nan = nan || (a != a); nrm = a > nrm ? a : nrm; }
       if (!nan && nrm <= abstol) { rc = 1; break; }
-      nk_f<double>(x, pp, fx);
+      nk_f<nk_real>(x, pp, fx);
       nk_jacobian(x, pp, J);
     }
     if (it > maxiters) it = maxiters;
@@ -186,34 +197,34 @@ nk_batch_newton(long nbatch, const double *__restrict__ u0, int u0_per_system, c
 // r = (f_{k+1} − f_k)/(δ·g + δ·Hδ/2) with H = JᵀJ, g = Jᵀf; shrink by t₁ when r < η₂ (ShrinkThresholdExceeded after
 // max_shrink consecutive shrinks), accept when r ≥ η₁ (termination test on the NEW residual, then J, g at the new point,
 // expand by t₂ up to Δmax when r > η₃). Δmax = max(‖f(u0)‖₂, max(u0) − min(u0)), Δ0 = Δmax/11.
-__device__ inline double nk_norm2(const double *v) {
-  double s = 0.0;
+__device__ inline nk_real nk_norm2(const nk_real *v) {
+  nk_real s = NK_R(0);
   NK_UNROLL for (int i = 0; i < NK_N; ++i) s += v[i] * v[i];
   return sqrt(s);
 }
 extern "C" __global__ void __launch_bounds__(NK_BLOCK_T)
-nk_batch_trust_region(long nbatch, const double *__restrict__ u0, int u0_per_system, const double *__restrict__ p, double abstol,
-                      int maxiters, double eta1, double eta2, double eta3, double t1, double t2, int max_shrink,
-                      double *__restrict__ u_out, double *__restrict__ r_out, int *__restrict__ retcode, int *__restrict__ iters) {
+nk_batch_trust_region(long nbatch, const nk_real *__restrict__ u0, int u0_per_system, const nk_real *__restrict__ p, nk_real abstol,
+                      int maxiters, nk_real eta1, nk_real eta2, nk_real eta3, nk_real t1, nk_real t2, int max_shrink,
+                      nk_real *__restrict__ u_out, nk_real *__restrict__ r_out, int *__restrict__ retcode, int *__restrict__ iters) {
   const long b = (long)blockIdx.x * NK_BLOCK_T + threadIdx.x;
   if (b >= nbatch) return;
-  double x[NK_N], xo[NK_N], fx[NK_N], g[NK_N], dl[NK_N], dN[NK_N], dsd[NK_N], tmp[NK_N], pp[NK_NP > 0 ? NK_NP : 1];
-  double J[NK_N][NK_N], A[NK_N][NK_N];
+  nk_real x[NK_N], xo[NK_N], fx[NK_N], g[NK_N], dl[NK_N], dN[NK_N], dsd[NK_N], tmp[NK_N], pp[NK_NP > 0 ? NK_NP : 1];
+  nk_real J[NK_N][NK_N], A[NK_N][NK_N];
   NK_UNROLL for (int i = 0; i < NK_N; ++i) { x[i] = u0[(u0_per_system ? b * NK_N : 0) + i]; xo[i] = x[i]; }
   NK_UNROLL for (int i = 0; i < NK_NP; ++i) pp[i] = p[b * NK_NP + i];
-  nk_f<double>(x, pp, fx);
-  const double norm_fx = nk_norm2(fx);
+  nk_f<nk_real>(x, pp, fx);
+  const nk_real norm_fx = nk_norm2(fx);
   nk_jacobian(x, pp, J);
-  double xmax = x[0], xmin = x[0];
+  nk_real xmax = x[0], xmin = x[0];
   NK_UNROLL for (int i = 1; i < NK_N; ++i) { xmax = x[i] > xmax ? x[i] : xmax; xmin = x[i] < xmin ? x[i] : xmin; }
-  const double dmax = norm_fx > xmax - xmin ? norm_fx : xmax - xmin;
-  double delta = dmax / 11.0;
-  double fk = 0.5 * norm_fx * norm_fx;
-  NK_UNROLL for (int i = 0; i < NK_N; ++i) { double s = 0.0; NK_UNROLL for (int k = 0; k < NK_N; ++k) s += J[k][i] * fx[k]; g[i] = s; }
+  const nk_real dmax = norm_fx > xmax - xmin ? norm_fx : xmax - xmin;
+  nk_real delta = dmax / NK_R(11);
+  nk_real fk = NK_R(0.5) * norm_fx * norm_fx;
+  NK_UNROLL for (int i = 0; i < NK_N; ++i) { nk_real s = NK_R(0); NK_UNROLL for (int k = 0; k < NK_N; ++k) s += J[k][i] * fx[k]; g[i] = s; }
   int shrink = 0, rc = 2, it = 0;
-  auto absmax_ok = [&](const double *f) {
-    double nrm = 0.0; bool nan = false;
-    NK_UNROLL for (int i = 0; i < NK_N; ++i) { const double a = fabs(f[i]); nan = nan || (a != a); nrm = a > nrm ? a : nrm; }
+  auto absmax_ok = [&](const nk_real *f) {
+    nk_real nrm = NK_R(0); bool nan = false;
+    NK_UNROLL for (int i = 0; i < NK_N; ++i) { const nk_real a = fabs(f[i]); nan = nan || (a != a); nrm = a > nrm ? a : nrm; }
     return !nan && nrm <= abstol;
   };
   if (absmax_ok(fx)) rc = 1;
@@ -227,31 +238,31 @@ nk_batch_trust_region(long nbatch, const double *__restrict__ u0, int u0_per_sys
         NK_UNROLL for (int i = 0; i < NK_N; ++i) dl[i] = dN[i];
       } else {
         NK_UNROLL for (int i = 0; i < NK_N; ++i) dsd[i] = -g[i];
-        const double nsd = nk_norm2(dsd);
+        const nk_real nsd = nk_norm2(dsd);
         if (nsd >= delta) {
           NK_UNROLL for (int i = 0; i < NK_N; ++i) dl[i] = dsd[i] * (delta / nsd);
         } else {
-          double dNN = 0.0, dSN = 0.0, dSS = 0.0;
-          NK_UNROLL for (int i = 0; i < NK_N; ++i) { const double q = dN[i] - dsd[i]; dNN += q * q; dSN += dsd[i] * q; dSS += dsd[i] * dsd[i]; }
-          const double fact = dSN * dSN - dNN * (dSS - delta * delta);
-          const double tau = (-dSN + sqrt(fact)) / dNN;
+          nk_real dNN = NK_R(0), dSN = NK_R(0), dSS = NK_R(0);
+          NK_UNROLL for (int i = 0; i < NK_N; ++i) { const nk_real q = dN[i] - dsd[i]; dNN += q * q; dSN += dsd[i] * q; dSS += dsd[i] * dsd[i]; }
+          const nk_real fact = dSN * dSN - dNN * (dSS - delta * delta);
+          const nk_real tau = (-dSN + sqrt(fact)) / dNN;
           NK_UNROLL for (int i = 0; i < NK_N; ++i) dl[i] = dsd[i] + tau * (dN[i] - dsd[i]);
         }
       }
       NK_UNROLL for (int i = 0; i < NK_N; ++i) x[i] = xo[i] + dl[i];
-      nk_f<double>(x, pp, fx);
-      const double nf = nk_norm2(fx);
-      const double fk1 = nf * nf / 2.0;
+      nk_f<nk_real>(x, pp, fx);
+      const nk_real nf = nk_norm2(fx);
+      const nk_real fk1 = nf * nf / NK_R(2);
       // Hδ = Jᵀ(Jδ)
-      NK_UNROLL for (int i = 0; i < NK_N; ++i) { double s = 0.0; NK_UNROLL for (int k = 0; k < NK_N; ++k) s += J[i][k] * dl[k]; tmp[i] = s; }
-      double dg = 0.0, dHd = 0.0;
+      NK_UNROLL for (int i = 0; i < NK_N; ++i) { nk_real s = NK_R(0); NK_UNROLL for (int k = 0; k < NK_N; ++k) s += J[i][k] * dl[k]; tmp[i] = s; }
+      nk_real dg = NK_R(0), dHd = NK_R(0);
       NK_UNROLL for (int i = 0; i < NK_N; ++i) {
-        double s = 0.0;
+        nk_real s = NK_R(0);
         NK_UNROLL for (int k = 0; k < NK_N; ++k) s += J[k][i] * tmp[k];
         dHd += dl[i] * s;
         dg += dl[i] * g[i];
       }
-      const double r = (fk1 - fk) / (dg + dHd / 2.0);
+      const nk_real r = (fk1 - fk) / (dg + dHd / NK_R(2));
       if (r >= eta2) shrink = 0;
       else {
         delta = t1 * delta;
@@ -263,7 +274,7 @@ nk_batch_trust_region(long nbatch, const double *__restrict__ u0, int u0_per_sys
         nk_jacobian(x, pp, J);
         if (r > eta3) delta = t2 * delta < dmax ? t2 * delta : dmax;
         fk = fk1;
-        NK_UNROLL for (int i = 0; i < NK_N; ++i) { double s = 0.0; NK_UNROLL for (int k = 0; k < NK_N; ++k) s += J[k][i] * fx[k]; g[i] = s; }
+        NK_UNROLL for (int i = 0; i < NK_N; ++i) { nk_real s = NK_R(0); NK_UNROLL for (int k = 0; k < NK_N; ++k) s += J[k][i] * fx[k]; g[i] = s; }
       }
     }
     if (it > maxiters) it = maxiters;
@@ -284,32 +295,36 @@ nk_batch_trust_region(long nbatch, const double *__restrict__ u0, int u0_per_sys
 // v_readlane with a scalar lane index; every lane then updates its own column with register indices that are compile-time
 // constants. The right-hand side, x and f(x) are replicated in all lanes. (nk_jac, if supplied, is not used by this kernel.)
 static const char *k_kernel_wave = R"NKSRC(
-__device__ inline double nk_rl(double v, int lane) {
+__device__ inline nk_real nk_rl(nk_real v, int lane) {
+#ifdef NK_F32
+  return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), lane));   // one 32-bit readlane
+#else
   const int lo = __builtin_amdgcn_readlane(__double2loint(v), lane);
   const int hi = __builtin_amdgcn_readlane(__double2hiint(v), lane);
   return __hiloint2double(hi, lo);
+#endif
 }
-__device__ inline double nk_wave_max(double v) {
+__device__ inline nk_real nk_wave_max(nk_real v) {
 #pragma unroll
-  for (int o = 32; o > 0; o >>= 1) { const double w = __shfl_xor(v, o, 64); v = w > v ? w : v; }
+  for (int o = 32; o > 0; o >>= 1) { const nk_real w = __shfl_xor(v, o, 64); v = w > v ? w : v; }
   return v;
 }
 extern "C" __global__ void __launch_bounds__(NK_BLOCK_T)
-nk_batch_newton_wave(long nbatch, const double *__restrict__ u0, int u0_per_system, const double *__restrict__ p, double abstol,
-                     int maxiters, double *__restrict__ u_out, double *__restrict__ r_out, int *__restrict__ retcode,
+nk_batch_newton_wave(long nbatch, const nk_real *__restrict__ u0, int u0_per_system, const nk_real *__restrict__ p, nk_real abstol,
+                     int maxiters, nk_real *__restrict__ u_out, nk_real *__restrict__ r_out, int *__restrict__ retcode,
                      int *__restrict__ iters) {
   const int lane = threadIdx.x & 63;
   const long b = (long)blockIdx.x * (NK_BLOCK_T / 64) + (threadIdx.x >> 6);
   if (b >= nbatch) return;   // whole wavefronts leave together
-  double x[NK_N], fx[NK_N], col[NK_N], pp[NK_NP > 0 ? NK_NP : 1];  // fx doubles as the right-hand side of the solve
+  nk_real x[NK_N], fx[NK_N], col[NK_N], pp[NK_NP > 0 ? NK_NP : 1];  // fx doubles as the right-hand side of the solve
 #pragma unroll
   for (int i = 0; i < NK_N; ++i) x[i] = u0[(u0_per_system ? b * NK_N : 0) + i];
 #pragma unroll
   for (int i = 0; i < NK_NP; ++i) pp[i] = p[b * NK_NP + i];
-  nk_f<double>(x, pp, fx);
+  nk_f<nk_real>(x, pp, fx);
   bool allzero = true;
 #pragma unroll
-  for (int i = 0; i < NK_N; ++i) allzero = allzero && (fx[i] == 0.0);
+  for (int i = 0; i < NK_N; ++i) allzero = allzero && (fx[i] == NK_R(0));
   int rc = 2, it = 0;
   if (allzero) rc = 1;
   else {
@@ -317,46 +332,46 @@ nk_batch_newton_wave(long nbatch, const double *__restrict__ u0, int u0_per_syst
       {  // column `lane` of J by one dual-number sweep (AutoForwardDiff with a single partial per lane)
         Dual xd[NK_N], fd[NK_N];
 #pragma unroll
-        for (int i = 0; i < NK_N; ++i) { xd[i].v = x[i]; xd[i].d[0] = (i == lane) ? 1.0 : 0.0; }
+        for (int i = 0; i < NK_N; ++i) { xd[i].v = x[i]; xd[i].d[0] = (i == lane) ? NK_R(1) : NK_R(0); }
         nk_f<Dual>(xd, pp, fd);
 #pragma unroll
-        for (int i = 0; i < NK_N; ++i) col[i] = (lane < NK_N) ? fd[i].d[0] : 0.0;
+        for (int i = 0; i < NK_N; ++i) col[i] = (lane < NK_N) ? fd[i].d[0] : NK_R(0);
       }
       // AbsNormTerminationMode(maximum∘abs) on the residual of the iterate the step starts from — the quantity the reference
       // tests AFTER the update (raphson.jl:72-75); taken here because the solve below overwrites fx
-      double nrm = 0.0;
+      nk_real nrm = NK_R(0);
       bool nan = false;
 #pragma unroll
-      for (int i = 0; i < NK_N; ++i) { const double a = fabs(fx[i]); nan = nan || (a != a); nrm = a > nrm ? a : nrm; }
+      for (int i = 0; i < NK_N; ++i) { const nk_real a = fabs(fx[i]); nan = nan || (a != a); nrm = a > nrm ? a : nrm; }
       const bool converged = !nan && nrm <= abstol;
-      double *rhs = fx;
+      nk_real *rhs = fx;
       // ---- LU with column pivoting, applied to the right-hand side on the fly
       bool used = lane >= NK_N;   // lanes without a column never pivot
       int perm[NK_N];
 #pragma unroll
       for (int c = 0; c < NK_N; ++c) {
-        const double mine = used ? -1.0 : fabs(col[c]);
-        const double best = nk_wave_max(mine);
+        const nk_real mine = used ? -NK_R(1) : fabs(col[c]);
+        const nk_real best = nk_wave_max(mine);
         const unsigned long long m = __ballot(!used && mine == best);
         const int pl = m ? (int)__ffsll((long long)m) - 1 : 0;   // (a NaN row: every compare fails — take lane 0, NaNs propagate)
         const int pv = __builtin_amdgcn_readfirstlane(pl);
         perm[c] = pv;
-        const double inv = 1.0 / nk_rl(col[c], pv);
+        const nk_real inv = NK_R(1) / nk_rl(col[c], pv);
         if (lane == pv) used = true;
-        const double cc = col[c];
+        const nk_real cc = col[c];
 #pragma unroll
         for (int r = c + 1; r < NK_N; ++r) {
-          const double l = nk_rl(col[r], pv) * inv;
+          const nk_real l = nk_rl(col[r], pv) * inv;
           if (!used) col[r] -= l * cc;
           rhs[r] -= l * rhs[c];
         }
       }
       // ---- back substitution: the unknown of step c belongs to lane perm[c]
-      double mydx = 0.0;
+      nk_real mydx = NK_R(0);
 #pragma unroll
       for (int c = NK_N - 1; c >= 0; --c) {
         const int pv = perm[c];
-        const double xc = rhs[c] / nk_rl(col[c], pv);
+        const nk_real xc = rhs[c] / nk_rl(col[c], pv);
         if (lane == pv) mydx = xc;
 #pragma unroll
         for (int r = 0; r < c; ++r) rhs[r] -= nk_rl(col[r], pv) * xc;
@@ -365,13 +380,13 @@ nk_batch_newton_wave(long nbatch, const double *__restrict__ u0, int u0_per_syst
       for (int i = 0; i < NK_N; ++i) x[i] -= nk_rl(mydx, i);
       if (converged) {  // the reference returns the residual of the iterate the last step started from: rebuild it (x + δ)
         rc = 1;
-        double xp[NK_N];
+        nk_real xp[NK_N];
 #pragma unroll
         for (int i = 0; i < NK_N; ++i) xp[i] = x[i] + nk_rl(mydx, i);
-        nk_f<double>(xp, pp, fx);
+        nk_f<nk_real>(xp, pp, fx);
         break;
       }
-      nk_f<double>(x, pp, fx);
+      nk_f<nk_real>(x, pp, fx);
     }
     if (it > maxiters) it = maxiters;
   }
@@ -424,7 +439,8 @@ struct nk_batch {
   int n = 0, np = 0, block = 64;
   hipModule_t mod = nullptr, mod_wave = nullptr;
   hipFunction_t fn = nullptr, fn_tr = nullptr, fn_wave = nullptr;  // fn_wave: one system per wavefront (8 < n ≤ 64)
-  // staging for host-memspace calls
+  bool f32 = false;  // kernels built with -DNK_F32 (flags & NK_BATCH_FLOAT32): float arrays and scalar arguments
+  // staging for host-memspace calls (sized in doubles; a Float32 object uses the first half of each)
   double *d_u0 = nullptr, *d_p = nullptr, *d_u = nullptr, *d_r = nullptr;
   int *d_rc = nullptr, *d_it = nullptr;
   int64_t cap = 0;
@@ -445,14 +461,20 @@ static int batch_compile(const char *source, int n, int np, int flags, std::vect
                     db = wave ? "-DNK_BLOCK_T=256" : "-DNK_BLOCK_T=64";
   std::vector<const char *> opts = {"--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-std=c++17", dn.c_str(), dp.c_str(), dc.c_str(),
                                     db.c_str()};
-  if ((flags & 1) && !wave) opts.push_back("-DNK_HAS_JAC=1");
+  if ((flags & NK_BATCH_ANALYTIC_JAC) && !wave) opts.push_back("-DNK_HAS_JAC=1");
+  if (flags & NK_BATCH_FLOAT32) opts.push_back("-DNK_F32=1");
   const int rc = RTC.Compile(prog, (int)opts.size(), opts.data());
   size_t ls = 0;
   RTC.LogSize(prog, &ls);
   if (ls > 1 && log) { log->resize(ls); RTC.Log(prog, &(*log)[0]); }
   if (rc != 0) {
     RTC.Destroy(&prog);
-    NK_FAIL(NK_E_INVALID, "residual source does not compile: %.900s", log && !log->empty() ? log->c_str() : "(no log)");
+    const char *lg = log && !log->empty() ? log->c_str() : "(no log)";
+    if (flags & NK_BATCH_FLOAT32)   // the usual cause: a source written against the Float64 contract (const double *p)
+      NK_FAIL(NK_E_INVALID, "residual source does not compile in Float32 mode, whose contract is `template <typename T> "
+              "__device__ void nk_f(const T *u, const nk_real *p, T *f)` (and `__device__ void nk_jac(const nk_real *u, "
+              "const nk_real *p, nk_real *J)`) with nk_real = float: %.900s", lg);
+    NK_FAIL(NK_E_INVALID, "residual source does not compile: %.900s", lg);
   }
   size_t cs = 0;
   RTC.CodeSize(prog, &cs);
@@ -477,6 +499,21 @@ extern "C" int nk_batch_compile_check(const char *source, int n, int nparams, in
   return NK_OK;
 }
 
+// the code object hiprtc makes for one kernel set (wave = 0: nk_batch_newton + nk_batch_trust_region; 1: nk_batch_newton_wave),
+// for inspection (disassembly, resource notes). *bytes gets its size; buf may be NULL to ask for the size only.
+extern "C" int nk_batch_code_object(const char *source, int n, int nparams, int flags, int wave, void *buf, int64_t capacity,
+                                    int64_t *bytes) {
+  NK_REQUIRE(bytes, "NULL argument");
+  std::vector<char> code;
+  std::string log;
+  NK_TRY(batch_compile(source, n, nparams, flags, &code, &log, wave != 0));
+  *bytes = (int64_t)code.size();
+  if (!buf) return NK_OK;
+  NK_REQUIRE(capacity >= *bytes, "buffer of %lld bytes, the code object has %lld", (long long)capacity, (long long)*bytes);
+  memcpy(buf, code.data(), code.size());
+  return NK_OK;
+}
+
 extern "C" int nk_batch_create(nk_ctx *ctx, const char *source, int n, int nparams, int flags, nk_batch **out) {
   NK_REQUIRE(ctx && out, "NULL argument");
   NK_HIP(hipSetDevice(ctx->device));
@@ -487,6 +524,7 @@ extern "C" int nk_batch_create(nk_ctx *ctx, const char *source, int n, int npara
   B->ctx = ctx;
   B->n = n;
   B->np = nparams;
+  B->f32 = (flags & NK_BATCH_FLOAT32) != 0;
   if (hipModuleLoadData(&B->mod, code.data()) != hipSuccess) { delete B; NK_FAIL(NK_E_HIP, "hipModuleLoadData failed"); }
   if (hipModuleGetFunction(&B->fn, B->mod, "nk_batch_newton") != hipSuccess) {
     hipModuleUnload(B->mod);
@@ -517,22 +555,26 @@ extern "C" int nk_batch_destroy(nk_batch *B) {
   return NK_OK;
 }
 
-// Solve all systems. u0: n doubles shared by every system (u0_per_system = 0, the tutorial's case) or nbatch×n;
-// p: nbatch×nparams. Outputs (nbatch×n, nbatch×n, nbatch, nbatch); retcode/iters may be NULL.
+// Solve all systems. u0: n values shared by every system (u0_per_system = 0, the tutorial's case) or nbatch×n;
+// p: nbatch×nparams. Outputs (nbatch×n, nbatch×n, nbatch, nbatch); retcode/iters may be NULL. The arrays hold doubles, or
+// floats for an object built with NK_BATCH_FLOAT32 (f32 says which entry point the caller used); the scalars arrive as double
+// and reach the kernels in the object's precision, T(abstol) as the reference takes them.
 // tr == nullptr: SimpleNewtonRaphson; else SimpleTrustRegion with tr = {η₁, η₂, η₃, t₁, t₂, max_shrink_times}.
-static int batch_run(nk_batch *B, int64_t nbatch, const double *u0, int u0_per_system, const double *p, int memspace,
-                     double abstol, int maxiters, const double *tr, double *u_out, double *resid_out, int32_t *retcode_out,
+static int batch_run(nk_batch *B, bool f32, int64_t nbatch, const void *u0, int u0_per_system, const void *p, int memspace,
+                     double abstol, int maxiters, const double *tr, void *u_out, void *resid_out, int32_t *retcode_out,
                      int32_t *iters_out) {
   NK_REQUIRE(B && u0 && u_out && resid_out, "NULL argument");
+  NK_REQUIRE(B->f32 == f32, B->f32 ? "this ensemble was compiled for Float32 (NK_BATCH_FLOAT32): call the _f32 entry points"
+                                   : "this ensemble was compiled for Float64: the _f32 entry points need NK_BATCH_FLOAT32");
   NK_REQUIRE(nbatch >= 0, "negative batch size");
   NK_REQUIRE(B->np == 0 || p, "parameters are required (nparams = %d)", B->np);
   NK_REQUIRE(!tr || B->fn_tr, "the compiled module lacks the trust-region kernel");
   nk_ctx *ctx = B->ctx;
   NK_HIP(hipSetDevice(ctx->device));
   if (nbatch == 0) return NK_OK;
-  if (!(abstol > 0.0)) abstol = pow(2.220446049250313e-16, 0.8);  // common_defaults.jl:39-48
   if (maxiters <= 0) maxiters = 1000;                             // raphson.jl:42 / trust_region.jl:60
   const int n = B->n, np = B->np;
+  const size_t es = f32 ? sizeof(float) : sizeof(double);
   if (B->cap < nbatch) {
     hipFree(B->d_u0); hipFree(B->d_p); hipFree(B->d_u); hipFree(B->d_r); hipFree(B->d_rc); hipFree(B->d_it);
     B->d_u0 = B->d_p = B->d_u = B->d_r = nullptr;
@@ -545,12 +587,12 @@ static int batch_run(nk_batch *B, int64_t nbatch, const double *u0, int u0_per_s
     NK_TRY(nk_dev_alloc(&B->d_it, (size_t)nbatch));
     B->cap = nbatch;
   }
-  const double *du0 = u0, *dp = p;
-  double *du = u_out, *dr = resid_out;
+  const void *du0 = u0, *dp = p;
+  void *du = u_out, *dr = resid_out;
   const size_t nu0 = (size_t)(u0_per_system ? nbatch : 1) * n;
   if (memspace != NK_DEVICE) {
-    NK_HIP(hipMemcpyAsync(B->d_u0, u0, nu0 * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-    if (np > 0) NK_HIP(hipMemcpyAsync(B->d_p, p, (size_t)nbatch * np * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    NK_HIP(hipMemcpyAsync(B->d_u0, u0, nu0 * es, hipMemcpyHostToDevice, ctx->stream));
+    if (np > 0) NK_HIP(hipMemcpyAsync(B->d_p, p, (size_t)nbatch * np * es, hipMemcpyHostToDevice, ctx->stream));
     du0 = B->d_u0;
     dp = B->d_p;
     du = B->d_u;
@@ -559,26 +601,34 @@ static int batch_run(nk_batch *B, int64_t nbatch, const double *u0, int u0_per_s
   long nb = (long)nbatch;
   int ups = u0_per_system ? 1 : 0;
   int *drc = B->d_rc, *dit = B->d_it;
+  // the kernels' real scalars: abstol, then η₁, η₂, η₃, t₁, t₂ (trust region); the defaults are the element type's
+  // (common_defaults.jl:39-53: eps(T)^(4/5), taken in T)
+  double sd[6];
+  float sf[6];
+  sd[0] = abstol > 0.0 ? abstol : pow(2.220446049250313e-16, 0.8);
+  sf[0] = abstol > 0.0 ? (float)abstol : powf(1.1920929e-7f, 0.8f);
+  for (int k = 0; k < 5; ++k) { sd[k + 1] = tr ? tr[k] : 0.0; sf[k + 1] = (float)sd[k + 1]; }
+  void *sa[6];
+  for (int k = 0; k < 6; ++k) sa[k] = f32 ? (void *)&sf[k] : (void *)&sd[k];
   const unsigned grid = (unsigned)((nbatch + B->block - 1) / B->block);
   if (!tr && B->fn_wave) {
-    void *args[] = {&nb, &du0, &ups, &dp, &abstol, &maxiters, &du, &dr, &drc, &dit};
+    void *args[] = {&nb, &du0, &ups, &dp, sa[0], &maxiters, &du, &dr, &drc, &dit};
     const unsigned wgrid = (unsigned)((nbatch + 3) / 4);  // 4 wavefronts = 4 systems per 256-thread workgroup
     if (hipModuleLaunchKernel(B->fn_wave, wgrid, 1, 1, 256, 1, 1, 0, ctx->stream, args, nullptr) != hipSuccess)
       NK_FAIL(NK_E_HIP, "launch of nk_batch_newton_wave failed");
   } else if (!tr) {
-    void *args[] = {&nb, &du0, &ups, &dp, &abstol, &maxiters, &du, &dr, &drc, &dit};
+    void *args[] = {&nb, &du0, &ups, &dp, sa[0], &maxiters, &du, &dr, &drc, &dit};
     if (hipModuleLaunchKernel(B->fn, grid, 1, 1, B->block, 1, 1, 0, ctx->stream, args, nullptr) != hipSuccess)
       NK_FAIL(NK_E_HIP, "launch of nk_batch_newton failed");
   } else {
-    double e1 = tr[0], e2 = tr[1], e3 = tr[2], t1 = tr[3], t2 = tr[4];
     int ms = (int)tr[5];
-    void *args[] = {&nb, &du0, &ups, &dp, &abstol, &maxiters, &e1, &e2, &e3, &t1, &t2, &ms, &du, &dr, &drc, &dit};
+    void *args[] = {&nb, &du0, &ups, &dp, sa[0], &maxiters, sa[1], sa[2], sa[3], sa[4], sa[5], &ms, &du, &dr, &drc, &dit};
     if (hipModuleLaunchKernel(B->fn_tr, grid, 1, 1, B->block, 1, 1, 0, ctx->stream, args, nullptr) != hipSuccess)
       NK_FAIL(NK_E_HIP, "launch of nk_batch_trust_region failed");
   }
   if (memspace != NK_DEVICE) {
-    NK_HIP(hipMemcpyAsync(u_out, du, (size_t)nbatch * n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    NK_HIP(hipMemcpyAsync(resid_out, dr, (size_t)nbatch * n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    NK_HIP(hipMemcpyAsync(u_out, du, (size_t)nbatch * n * es, hipMemcpyDeviceToHost, ctx->stream));
+    NK_HIP(hipMemcpyAsync(resid_out, dr, (size_t)nbatch * n * es, hipMemcpyDeviceToHost, ctx->stream));
   }
   // retcode / iteration outputs follow the memory space of the other arrays
   if (retcode_out)
@@ -594,19 +644,48 @@ static int batch_run(nk_batch *B, int64_t nbatch, const double *u0, int u0_per_s
 extern "C" int nk_batch_solve(nk_batch *B, int64_t nbatch, const double *u0, int u0_per_system, const double *p, int memspace,
                               double abstol, int maxiters, double *u_out, double *resid_out, int32_t *retcode_out,
                               int32_t *iters_out) {
-  return batch_run(B, nbatch, u0, u0_per_system, p, memspace, abstol, maxiters, nullptr, u_out, resid_out, retcode_out, iters_out);
+  return batch_run(B, false, nbatch, u0, u0_per_system, p, memspace, abstol, maxiters, nullptr, u_out, resid_out, retcode_out,
+                   iters_out);
+}
+
+extern "C" int nk_batch_solve_f32(nk_batch *B, int64_t nbatch, const float *u0, int u0_per_system, const float *p, int memspace,
+                                  double abstol, int maxiters, float *u_out, float *resid_out, int32_t *retcode_out,
+                                  int32_t *iters_out) {
+  return batch_run(B, true, nbatch, u0, u0_per_system, p, memspace, abstol, maxiters, nullptr, u_out, resid_out, retcode_out,
+                   iters_out);
 }
 
 // SimpleTrustRegion (lib/SimpleNonlinearSolve/src/trust_region.jl); thresholds/factors ≤ 0 and max_shrink_times < 0 select
 // the reference defaults η₁ = 1e-4, η₂ = 0.25, η₃ = 0.75, t₁ = 0.25, t₂ = 2, 32. Retcodes: Success, MaxIters,
 // ShrinkThresholdExceeded.
+static void trust_region_params(double *tr, double step_threshold, double shrink_threshold, double expand_threshold,
+                                double shrink_factor, double expand_factor, int max_shrink_times) {
+  tr[0] = step_threshold > 0 ? step_threshold : 1e-4;
+  tr[1] = shrink_threshold > 0 ? shrink_threshold : 0.25;
+  tr[2] = expand_threshold > 0 ? expand_threshold : 0.75;
+  tr[3] = shrink_factor > 0 ? shrink_factor : 0.25;
+  tr[4] = expand_factor > 0 ? expand_factor : 2.0;
+  tr[5] = (double)(max_shrink_times >= 0 ? max_shrink_times : 32);
+}
+
 extern "C" int nk_batch_solve_trust_region(nk_batch *B, int64_t nbatch, const double *u0, int u0_per_system, const double *p,
                                            int memspace, double abstol, int maxiters, double step_threshold,
                                            double shrink_threshold, double expand_threshold, double shrink_factor,
                                            double expand_factor, int max_shrink_times, double *u_out, double *resid_out,
                                            int32_t *retcode_out, int32_t *iters_out) {
-  const double tr[6] = {step_threshold > 0 ? step_threshold : 1e-4, shrink_threshold > 0 ? shrink_threshold : 0.25,
-                        expand_threshold > 0 ? expand_threshold : 0.75, shrink_factor > 0 ? shrink_factor : 0.25,
-                        expand_factor > 0 ? expand_factor : 2.0, (double)(max_shrink_times >= 0 ? max_shrink_times : 32)};
-  return batch_run(B, nbatch, u0, u0_per_system, p, memspace, abstol, maxiters, tr, u_out, resid_out, retcode_out, iters_out);
+  double tr[6];
+  trust_region_params(tr, step_threshold, shrink_threshold, expand_threshold, shrink_factor, expand_factor, max_shrink_times);
+  return batch_run(B, false, nbatch, u0, u0_per_system, p, memspace, abstol, maxiters, tr, u_out, resid_out, retcode_out,
+                   iters_out);
+}
+
+extern "C" int nk_batch_solve_trust_region_f32(nk_batch *B, int64_t nbatch, const float *u0, int u0_per_system, const float *p,
+                                               int memspace, double abstol, int maxiters, double step_threshold,
+                                               double shrink_threshold, double expand_threshold, double shrink_factor,
+                                               double expand_factor, int max_shrink_times, float *u_out, float *resid_out,
+                                               int32_t *retcode_out, int32_t *iters_out) {
+  double tr[6];
+  trust_region_params(tr, step_threshold, shrink_threshold, expand_threshold, shrink_factor, expand_factor, max_shrink_times);
+  return batch_run(B, true, nbatch, u0, u0_per_system, p, memspace, abstol, maxiters, tr, u_out, resid_out, retcode_out,
+                   iters_out);
 }
