@@ -564,8 +564,8 @@ int nk_gmres_solve(nk_gmres *G, const double *b, double *x, int memspace, int us
  * Direct factorisation of a concrete banded sparse J on the device; factor once, solve many
  * (reuse_A_if_factorization, lib/NonlinearSolveBase/ext/NonlinearSolveBaseLinearSolveExt.jl:81-86). Single rank.
  * Engine (nk_lu_engine): block cyclic reduction — batched dense blocks of order b = bandwidth rounded to 32 (b <= 512) on FP64
- * MFMA, log2(n/b) dependent levels — or, for matrices of fewer than four block rows, a right-looking band LU (lower
- * bandwidth <= ~550). Pivots: on the diagonal first; the cyclic-reduction engine switches to row pivoting inside its dense
+ * MFMA, log2(n/b) dependent levels — or, for matrices of fewer than four block rows, a right-looking band LU (kl <= 447,
+ * ku <= 512; a matrix of fewer block rows with 447 < kl <= 512 goes to block cyclic reduction). Pivots: on the diagonal first; the cyclic-reduction engine switches to row pivoting inside its dense
  * blocks when a diagonal pivot vanishes (NK_BCR_PIVOT=auto|always|never); *ok = 0 when the factorisation still broke down. */
 int nk_lu_create(nk_csr *A, nk_lu **out);
 int nk_lu_destroy(nk_lu *F);
@@ -574,7 +574,8 @@ int nk_lu_solve(nk_lu *F, const double *b, double *x, int memspace);
 int nk_lu_info(nk_lu *F, int *kl, int *ku, int64_t *band_bytes);   /* band_bytes: device memory held by the factorisation */
 /* which engine the factorisation object runs on: 0 = right-looking band LU (a chain of n/32 dependent block columns),
  * 1 = block cyclic reduction (log2(n/b) levels of batched dense b x b algebra on FP64 MFMA; chosen automatically when the
- * matrix has >= 4 block rows of order b = bandwidth rounded to 32, b <= 512; NK_DIRECT=band in the environment forces 0);
+ * matrix has >= 4 block rows of order b = bandwidth rounded to 32, b <= 512, or when kl > 447 and b <= 512 whatever the
+ * number of block rows; NK_DIRECT=band in the environment forces 0 wherever the band LU can hold the matrix);
  * `block` = b (0 for the band LU), `levels` = number of reduction levels. */
 int nk_lu_engine(nk_lu *F, int *engine, int *block, int *levels);
 

@@ -493,12 +493,17 @@ int nk_bandlu_create(nk_csr *A, nk_bandlu **out, int engine) {
       if (-d > kl) kl = (int)(-d);
     }
   const int64_t n = A->nrows;
+  // the band LU's LDS panel holds (NB + kl + 1) × NB doubles in 120 KiB: kl ≤ 447
+  const bool band_fits = (size_t)(NB + kl + 1) * NB * sizeof(double) <= 120 * 1024;
   // Block cyclic reduction (nk_bcr.hip) wherever the matrix has enough block rows to shorten the dependency chain and its
-  // dense blocks fit: log₂(n/b) levels of batched dense algebra instead of n/32 dependent block columns.
+  // dense blocks fit: log₂(n/b) levels of batched dense algebra instead of n/32 dependent block columns. It also takes a
+  // matrix of fewer block rows whose lower bandwidth the band LU cannot hold (447 < kl ≤ 512; the reduction runs through
+  // levels of 3, 2 and 1 block rows anyway), with NK_DIRECT=band too.
   {
     static const bool force_band = getenv("NK_DIRECT") && !strcmp(getenv("NK_DIRECT"), "band");
     const int b = ((std::max(std::max(kl, ku), 1) + 31) / 32) * 32;
-    if (engine == 0 && !force_band && b <= 512 && (n + b - 1) / b >= 4 && nk_bcr_bytes(n, b) < ((int64_t)24 << 30)) {
+    const bool many_blocks = !force_band && (n + b - 1) / b >= 4;
+    if (engine == 0 && b <= 512 && (many_blocks || !band_fits) && nk_bcr_bytes(n, b) < ((int64_t)24 << 30)) {
       nk_bandlu *B = new nk_bandlu();
       auto guard = nk_make_guard(B, [](nk_bandlu *b_) { nk_bandlu_destroy(b_); });
       B->ctx = ctx;
@@ -514,8 +519,7 @@ int nk_bandlu_create(nk_csr *A, nk_bandlu **out, int engine) {
   }
   const size_t band_bytes = (size_t)(kl + ku + 1) * n * sizeof(double);
   NK_REQUIRE(band_bytes < ((size_t)64 << 30), "band storage of %zu bytes is too large (bandwidth %d+%d)", band_bytes, kl, ku);
-  NK_REQUIRE((size_t)(NB + kl + 1) * NB * sizeof(double) <= 120 * 1024,
-             "lower bandwidth %d too large for the LDS panel", kl);
+  NK_REQUIRE(band_fits, "lower bandwidth %d too large for the LDS panel (band LU: kl <= 447)", kl);
   NK_REQUIRE(kl <= 512 && ku <= 512, "bandwidth %d+%d too large for the device band solver", kl, ku);
   nk_bandlu *B = new nk_bandlu();
   auto guard = nk_make_guard(B, [](nk_bandlu *b) { nk_bandlu_destroy(b); });
