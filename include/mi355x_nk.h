@@ -665,6 +665,52 @@ int nk_batch_solve_trust_region_f32(nk_batch *B, int64_t nbatch, const float *u0
                                     int memspace, double abstol, int maxiters, double step_threshold, double shrink_threshold,
                                     double expand_threshold, double shrink_factor, double expand_factor, int max_shrink_times,
                                     float *u_out, float *resid_out, int32_t *retcode_out, int32_t *iters_out);
+/* Jacobian-free methods (lib/SimpleNonlinearSolve/src/broyden.jl, klement.jl, dfsane.jl), one system per thread, n = 1..64
+ * (registers while n <= 8, scratch above). Their kernels are a module of their own, compiled by hiprtc on the first call of
+ * one of these entry points on an object and kept on it: nk_batch_create and the Newton kernels do not change. Common to
+ * all three: AbsNormTerminationMode(maximum∘abs) on the NEW residual, right after it is evaluated (the Newton kernel checks
+ * before its evaluation); a NaN residual never terminates; default abstol eps(T)^(4/5), maxiters 1000; resid = f(u) at the
+ * returned u; retcodes NK_RET_SUCCESS / NK_RET_MAXITERS. Argument conventions as nk_batch_solve; real parameters <= 0
+ * select the defaults; the _f32 twins take float arrays (scalars stay double and are rounded to float, T(x)).
+ * SimpleBroyden (linesearch = nothing): iszero(f(u0)) ⇒ Success with iters 0; J⁻¹ = init_α·I with init_α = 1/alpha, or, for
+ *   alpha <= 0 (`nothing`), max(‖u0‖₂, 1)/(2‖f(u0)‖₂) when ‖f(u0)‖₂ >= 1e-5, else 1; per iteration δx = −J⁻¹f_prev,
+ *   u += δx, f, check, J⁻¹ += ((δx − J⁻¹δf)/(δx·J⁻¹δf)) (J⁻¹ᵀδx)ᵀ with no guard on a zero denominator.
+ * SimpleKlement: diagonal J = 1 at start and wherever any entry is 0 (all reset); δx = f_prev ./ J, u −= δx, f, check,
+ *   J += (f − f_prev − J·δ)/(δ²J² or 1e-5 where that is 0)·δ·J² with δ = −δx. No iszero shortcut.
+ * For both, iters is the 1-based iteration that passed the check, or maxiters.
+ * SimpleDFSane (η_k = f₁/k², the default eta_strategy): spectral steps d = −σ_k f with sign(σ)·clamp(|σ|, σ_min, σ_max)
+ *   (NaN kept), the non-monotone line search against max of the last M merit values ‖f‖₂^n_exp (NaN propagates), step
+ *   factors clamped to [τ_min, τ_max]·α. The counter k is the reference's: it counts outer iterations and inner line-search
+ *   passes, both loops stop at k = maxiters (the last trial point is then taken and checked), and the merit value is stored
+ *   in slot mod1(k, M). iters is k + 1 on Success (the iteration that passed the check) and maxiters otherwise, never more
+ *   than maxiters. M is accepted in 1..32 and n_exp as 1 or 2; 0 selects the default (10, 2), any other value is
+ *   NK_E_INVALID. Defaults σ_min = 1e-10, σ_max = 1e10, σ₁ = 1, γ = 1e-4, τ_min = 0.1, τ_max = 0.5.
+ * Not offered: SimpleLimitedMemoryBroyden — its static (kernel) path keeps 2·threshold·n values (threshold 27) and, in its
+ * unrolled first iterations, never advances xo (lbroyden.jl:256), a reference defect a port would have to copy or knowingly
+ * diverge from; SimpleHalley — it needs second derivatives, and the reference leaves it out of its own kernel tests. */
+int nk_batch_solve_broyden(nk_batch *B, int64_t nbatch, const double *u0, int u0_per_system, const double *p, int memspace,
+                           double abstol, int maxiters, double alpha, double *u_out, double *resid_out, int32_t *retcode_out,
+                           int32_t *iters_out);
+int nk_batch_solve_broyden_f32(nk_batch *B, int64_t nbatch, const float *u0, int u0_per_system, const float *p, int memspace,
+                               double abstol, int maxiters, double alpha, float *u_out, float *resid_out, int32_t *retcode_out,
+                               int32_t *iters_out);
+int nk_batch_solve_klement(nk_batch *B, int64_t nbatch, const double *u0, int u0_per_system, const double *p, int memspace,
+                           double abstol, int maxiters, double *u_out, double *resid_out, int32_t *retcode_out,
+                           int32_t *iters_out);
+int nk_batch_solve_klement_f32(nk_batch *B, int64_t nbatch, const float *u0, int u0_per_system, const float *p, int memspace,
+                               double abstol, int maxiters, float *u_out, float *resid_out, int32_t *retcode_out,
+                               int32_t *iters_out);
+int nk_batch_solve_dfsane(nk_batch *B, int64_t nbatch, const double *u0, int u0_per_system, const double *p, int memspace,
+                          double abstol, int maxiters, double sigma_min, double sigma_max, double sigma_1, int M, double gamma,
+                          double tau_min, double tau_max, int n_exp, double *u_out, double *resid_out, int32_t *retcode_out,
+                          int32_t *iters_out);
+int nk_batch_solve_dfsane_f32(nk_batch *B, int64_t nbatch, const float *u0, int u0_per_system, const float *p, int memspace,
+                              double abstol, int maxiters, double sigma_min, double sigma_max, double sigma_1, int M,
+                              double gamma, double tau_min, double tau_max, int n_exp, float *u_out, float *resid_out,
+                              int32_t *retcode_out, int32_t *iters_out);
+/* the Jacobian-free module's code object (nk_batch_broyden, nk_batch_klement, nk_batch_dfsane) for inspection, as
+ * nk_batch_code_object; no device needed */
+int nk_batch_jf_code_object(const char *source, int n, int nparams, int flags, void *buf, int64_t capacity, int64_t *bytes);
 
 /* ---------------------------------------------------------------- BLAS-1 building blocks (exported for
  * the bench / tests; all on the ctx stream, results of reductions are all-reduced over the ranks) */

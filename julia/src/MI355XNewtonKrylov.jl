@@ -610,7 +610,8 @@ mutable struct EnsembleKernel
 end
 
 function vectorized_solve(k::EnsembleKernel, u0::Vector{Float64}, p::Matrix{Float64}; alg = :SimpleNewtonRaphson,
-        abstol = 0.0, maxiters = 1000)
+        abstol = 0.0, maxiters = 1000, kwargs...)
+    alg in JACOBIAN_FREE_ALGS && return jacobian_free_solve(k, u0, p, alg, Float64(abstol), maxiters; kwargs...)
     nb = size(p, 2)
     u = Matrix{Float64}(undef, k.n, nb); resid = similar(u)
     rc = Vector{Int32}(undef, nb); iters = Vector{Int32}(undef, nb)
@@ -630,8 +631,9 @@ end
 # Float32 (the tutorial's `rand(Float32, 4)` parameters and `SA[1.0f0, 2.0f0, 3.0f0, 4.0f0]`): results in Float32. The scalar
 # arguments stay Float64 at the ABI; the library takes them as T(abstol), as the reference does.
 function vectorized_solve(k::EnsembleKernel, u0::Vector{Float32}, p::Matrix{Float32}; alg = :SimpleNewtonRaphson,
-        abstol = 0.0, maxiters = 1000)
+        abstol = 0.0, maxiters = 1000, kwargs...)
     k.eltype === Float32 || throw(ArgumentError("this EnsembleKernel was built for $(k.eltype): build it with eltype = Float32"))
+    alg in JACOBIAN_FREE_ALGS && return jacobian_free_solve(k, u0, p, alg, Float64(abstol), maxiters; kwargs...)
     nb = size(p, 2)
     u = Matrix{Float32}(undef, k.n, nb); resid = similar(u)
     rc = Vector{Int32}(undef, nb); iters = Vector{Int32}(undef, nb)
@@ -646,6 +648,54 @@ function vectorized_solve(k::EnsembleKernel, u0::Vector{Float32}, p::Matrix{Floa
     GC.@preserve u0 p u resid rc iters nkcheck(@ccall libnk.nk_batch_solve_f32(k.ptr::Ptr{Cvoid}, nb::Int64,
         u0::Ptr{Float32}, 0::Cint, p::Ptr{Float32}, 0::Cint, tol::Float64, maxiters::Cint, u::Ptr{Float32},
         resid::Ptr{Float32}, rc::Ptr{Int32}, iters::Ptr{Int32})::Cint)
+    return (; u, resid, retcode = [RETCODES[c + 1] for c in rc], iters)
+end
+
+# The Jacobian-free methods (lib/SimpleNonlinearSolve/src/broyden.jl, klement.jl, dfsane.jl) with the reference's keyword
+# names: `alg = :SimpleBroyden` (alpha = nothing), `:SimpleKlement`, `:SimpleDFSane` (sigma_min, sigma_max, sigma_1, M in 1:32,
+# gamma, tau_min, tau_max, n_exp in (1, 2); eta_strategy is the default f₁/k²). Their kernels are compiled on the first call.
+const JACOBIAN_FREE_ALGS = (:SimpleBroyden, :SimpleKlement, :SimpleDFSane)
+
+function jacobian_free_solve(k::EnsembleKernel, u0::Vector{T}, p::Matrix{T}, alg::Symbol, tol::Float64, maxiters;
+        alpha = nothing, sigma_min = 1.0e-10, sigma_max = 1.0e10, sigma_1 = 1.0, M = 10, gamma = 1.0e-4, tau_min = 0.1,
+        tau_max = 0.5, n_exp = 2) where {T <: Union{Float32, Float64}}
+    (1 <= M <= 32 && n_exp in (1, 2)) || throw(ArgumentError("SimpleDFSane: M must lie in 1:32 and n_exp be 1 or 2"))
+    nb = size(p, 2)
+    u = Matrix{T}(undef, k.n, nb); resid = similar(u)
+    rc = Vector{Int32}(undef, nb); iters = Vector{Int32}(undef, nb)
+    a = alpha === nothing ? -1.0 : Float64(alpha)
+    s1, s2, s3, g, t1, t2 = Float64(sigma_min), Float64(sigma_max), Float64(sigma_1), Float64(gamma), Float64(tau_min),
+        Float64(tau_max)
+    GC.@preserve u0 p u resid rc iters begin
+        st = if T === Float64 && alg === :SimpleBroyden
+            @ccall libnk.nk_batch_solve_broyden(k.ptr::Ptr{Cvoid}, nb::Int64, u0::Ptr{Float64}, 0::Cint, p::Ptr{Float64},
+                0::Cint, tol::Float64, maxiters::Cint, a::Float64, u::Ptr{Float64}, resid::Ptr{Float64}, rc::Ptr{Int32},
+                iters::Ptr{Int32})::Cint
+        elseif T === Float64 && alg === :SimpleKlement
+            @ccall libnk.nk_batch_solve_klement(k.ptr::Ptr{Cvoid}, nb::Int64, u0::Ptr{Float64}, 0::Cint, p::Ptr{Float64},
+                0::Cint, tol::Float64, maxiters::Cint, u::Ptr{Float64}, resid::Ptr{Float64}, rc::Ptr{Int32},
+                iters::Ptr{Int32})::Cint
+        elseif T === Float64
+            @ccall libnk.nk_batch_solve_dfsane(k.ptr::Ptr{Cvoid}, nb::Int64, u0::Ptr{Float64}, 0::Cint, p::Ptr{Float64},
+                0::Cint, tol::Float64, maxiters::Cint, s1::Float64, s2::Float64, s3::Float64, M::Cint, g::Float64,
+                t1::Float64, t2::Float64, n_exp::Cint, u::Ptr{Float64}, resid::Ptr{Float64}, rc::Ptr{Int32},
+                iters::Ptr{Int32})::Cint
+        elseif alg === :SimpleBroyden
+            @ccall libnk.nk_batch_solve_broyden_f32(k.ptr::Ptr{Cvoid}, nb::Int64, u0::Ptr{Float32}, 0::Cint,
+                p::Ptr{Float32}, 0::Cint, tol::Float64, maxiters::Cint, a::Float64, u::Ptr{Float32}, resid::Ptr{Float32},
+                rc::Ptr{Int32}, iters::Ptr{Int32})::Cint
+        elseif alg === :SimpleKlement
+            @ccall libnk.nk_batch_solve_klement_f32(k.ptr::Ptr{Cvoid}, nb::Int64, u0::Ptr{Float32}, 0::Cint,
+                p::Ptr{Float32}, 0::Cint, tol::Float64, maxiters::Cint, u::Ptr{Float32}, resid::Ptr{Float32},
+                rc::Ptr{Int32}, iters::Ptr{Int32})::Cint
+        else
+            @ccall libnk.nk_batch_solve_dfsane_f32(k.ptr::Ptr{Cvoid}, nb::Int64, u0::Ptr{Float32}, 0::Cint,
+                p::Ptr{Float32}, 0::Cint, tol::Float64, maxiters::Cint, s1::Float64, s2::Float64, s3::Float64, M::Cint,
+                g::Float64, t1::Float64, t2::Float64, n_exp::Cint, u::Ptr{Float32}, resid::Ptr{Float32}, rc::Ptr{Int32},
+                iters::Ptr{Int32})::Cint
+        end
+        nkcheck(st)
+    end
     return (; u, resid, retcode = [RETCODES[c + 1] for c in rc], iters)
 end
 

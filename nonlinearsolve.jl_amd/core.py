@@ -1485,6 +1485,35 @@ class SimpleTrustRegion:
     name: str = "SimpleTrustRegion"
 
 
+@dataclass
+class SimpleBroyden:
+    """lib/SimpleNonlinearSolve/src/broyden.jl:15-24 with linesearch = nothing: Jacobian-free, one n×n inverse per system.
+    `alpha=None` scales J⁻¹ from the norms of f(u0) and u0; otherwise J⁻¹ starts as I/alpha."""
+    alpha: Optional[float] = None
+    name: str = "SimpleBroyden"
+
+
+@dataclass
+class SimpleKlement:
+    """lib/SimpleNonlinearSolve/src/klement.jl:7: Jacobian-free, a diagonal Jacobian estimate per system."""
+    name: str = "SimpleKlement"
+
+
+@dataclass
+class SimpleDFSane:
+    """lib/SimpleNonlinearSolve/src/dfsane.jl:53-64 (eta_strategy fixed at its default f₁/k²): spectral residual steps with a
+    non-monotone line search over the last M merit values ‖f‖₂^n_exp. M in 1..32, n_exp 1 or 2."""
+    sigma_min: float = 1e-10
+    sigma_max: float = 1e10
+    sigma_1: float = 1.0
+    M: int = 10
+    gamma: float = 1e-4
+    tau_min: float = 0.1
+    tau_max: float = 0.5
+    n_exp: int = 2
+    name: str = "SimpleDFSane"
+
+
 class ImmutableNonlinearProblem:
     """SciMLBase.ImmutableNonlinearProblem{false}(f, u0, p) for the kernel-generation path
     (docs/src/tutorials/nonlinear_solve_gpus.md:120-140). `f_source` is HIP C++ defining
@@ -1547,10 +1576,15 @@ class _BatchKernel:
 def vectorized_solve(prob: ImmutableNonlinearProblem, alg=None, abstol=None, maxiters=1000):
     """`vectorized_solve(prob, alg; backend = ROCBackend())` of the tutorial (nonlinear_solve_gpus.md:106-114): solve
     every parameter set with SimpleNewtonRaphson, one system per GPU thread, in one kernel launch. The problem's eltype
-    picks the precision (Float64 unless it was built with eltype=float32)."""
+    picks the precision (Float64 unless it was built with eltype=float32). `alg` may also be SimpleTrustRegion or one of the
+    Jacobian-free SimpleBroyden, SimpleKlement, SimpleDFSane (their kernels are compiled on first use)."""
     alg = alg or SimpleNewtonRaphson()
+    if isinstance(alg, SimpleBroyden) and alg.alpha is not None and not alg.alpha > 0:
+        raise ValueError(f"SimpleBroyden: alpha = {alg.alpha} must be positive (or None)")
+    if isinstance(alg, SimpleDFSane) and not (1 <= int(alg.M) <= 32 and int(alg.n_exp) in (1, 2)):
+        raise ValueError(f"SimpleDFSane: M = {alg.M} must lie in 1..32 and n_exp = {alg.n_exp} must be 1 or 2")
     f32 = prob.float32
-    flags = (L.BATCH_ANALYTIC_JAC if alg.jac else 0) | (L.BATCH_FLOAT32 if f32 else 0)
+    flags = (L.BATCH_ANALYTIC_JAC if getattr(alg, "jac", False) else 0) | (L.BATCH_FLOAT32 if f32 else 0)
     h = _BatchKernel.get(prob.ctx, prob.f_source, prob.n, prob.nparams, flags)
     on_dev = _is_torch(prob.p) and prob.p.is_cuda
     nb, n = prob.nbatch, prob.n
@@ -1581,6 +1615,20 @@ def vectorized_solve(prob: ImmutableNonlinearProblem, alg=None, abstol=None, max
                        d(alg.step_threshold), d(alg.shrink_threshold), d(alg.expand_threshold),
                        d(alg.shrink_factor), d(alg.expand_factor), int(alg.max_shrink_times),
                        ptr(u), ptr(r), ptr(rc), ptr(it)))
+    elif isinstance(alg, (SimpleBroyden, SimpleKlement, SimpleDFSane)):
+        sfx = "_f32" if f32 else ""
+        head = (h, nb, ptr(u0), 1 if prob.u0_per_system else 0, ptr(pp), ms, 0.0 if abstol is None else float(abstol),
+                int(maxiters))
+        outs = (ptr(u), ptr(r), ptr(rc), ptr(it))
+        if isinstance(alg, SimpleBroyden):
+            check(getattr(L.lib(), "nk_batch_solve_broyden" + sfx)(*head, -1.0 if alg.alpha is None else float(alg.alpha),
+                                                                    *outs))
+        elif isinstance(alg, SimpleKlement):
+            check(getattr(L.lib(), "nk_batch_solve_klement" + sfx)(*head, *outs))
+        else:
+            check(getattr(L.lib(), "nk_batch_solve_dfsane" + sfx)(
+                *head, float(alg.sigma_min), float(alg.sigma_max), float(alg.sigma_1), int(alg.M), float(alg.gamma),
+                float(alg.tau_min), float(alg.tau_max), int(alg.n_exp), *outs))
     else:
         solve = L.lib().nk_batch_solve_f32 if f32 else L.lib().nk_batch_solve
         check(solve(h, nb, ptr(u0), 1 if prob.u0_per_system else 0, ptr(pp), ms,

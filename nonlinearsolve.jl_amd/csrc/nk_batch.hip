@@ -399,6 +399,227 @@ nk_batch_newton_wave(long nbatch, const nk_real *__restrict__ u0, int u0_per_sys
 }
 )NKSRC";
 
+// ----------------------------------------------------------------------------- Jacobian-free methods, one system per thread
+// SimpleBroyden (broyden.jl:31-108, linesearch = nothing), SimpleKlement (klement.jl:9-56) and SimpleDFSane (dfsane.jl:66-172,
+// η_k = f₁/k²). A module of their own (nk_batch::mod_jf), compiled on first use, so that the Newton kernels' code objects and
+// compile time stay as they were. All three test AbsNormTerminationMode(maximum∘abs) on the NEW residual right after it is
+// evaluated (NaN never terminates) and return f at the returned u. No Jacobian, no LU: Klement and DFSane keep O(n) state,
+// Broyden one n×n inverse. While n ≤ 8 every index is a compile-time constant and everything lives in registers (DFSane's
+// history of up to 32 values too: select-writes, never a dynamic index); above that the arrays go to scratch.
+static const char *k_kernel_jf = R"NKSRC(
+#if NK_N <= 8
+#define NK_UNROLL _Pragma("unroll")
+#else
+#define NK_UNROLL _Pragma("nounroll")
+#endif
+#define NK_HIST 32   // DFSane's M is at most this
+
+__device__ inline nk_real nk_norm2(const nk_real *v) {
+  nk_real s = NK_R(0);
+  NK_UNROLL for (int i = 0; i < NK_N; ++i) s += v[i] * v[i];
+  return sqrt(s);
+}
+// AbsNormTerminationMode(maximum∘abs): maximum propagates NaN, and NaN <= abstol is false
+__device__ inline bool nk_absmax_ok(const nk_real *f, nk_real abstol) {
+  nk_real nrm = NK_R(0);
+  bool nan = false;
+  NK_UNROLL for (int i = 0; i < NK_N; ++i) { const nk_real a = fabs(f[i]); nan = nan || (a != a); nrm = a > nrm ? a : nrm; }
+  return !nan && nrm <= abstol;
+}
+// Julia's max / clamp / sign on floats: NaN propagates (fmax / fmin would drop it)
+__device__ inline nk_real nk_jl_max(nk_real a, nk_real b) { return (a != a) ? a : ((b > a || b != b) ? b : a); }
+__device__ inline nk_real nk_jl_clamp(nk_real x, nk_real lo, nk_real hi) { return x > hi ? hi : (x < lo ? lo : x); }
+__device__ inline nk_real nk_jl_sign(nk_real x) { return x > NK_R(0) ? NK_R(1) : (x < NK_R(0) ? NK_R(-1) : x); }
+
+// ---- SimpleBroyden: J⁻¹ = init_α·I; δx = −J⁻¹ fprev, x += δx, f, check; J⁻¹ += ((δx − J⁻¹δf)/(δx·J⁻¹δf)) (J⁻¹ᵀδx)ᵀ.
+// alpha_inv > 0 is 1/alpha (computed on the host in double, as Julia's inv(alpha) is); else init_α comes from the norms.
+extern "C" __global__ void __launch_bounds__(NK_BLOCK_T)
+nk_batch_broyden(long nbatch, const nk_real *__restrict__ u0, int u0_per_system, const nk_real *__restrict__ p, nk_real abstol,
+                 int maxiters, nk_real alpha_inv, nk_real *__restrict__ u_out, nk_real *__restrict__ r_out,
+                 int *__restrict__ retcode, int *__restrict__ iters) {
+  const long b = (long)blockIdx.x * NK_BLOCK_T + threadIdx.x;
+  if (b >= nbatch) return;
+  nk_real x[NK_N], fx[NK_N], fprev[NK_N], dx[NK_N], t[NK_N], xJ[NK_N], pp[NK_NP > 0 ? NK_NP : 1];
+  NK_UNROLL for (int i = 0; i < NK_N; ++i) x[i] = u0[(u0_per_system ? b * NK_N : 0) + i];
+  NK_UNROLL for (int i = 0; i < NK_NP; ++i) pp[i] = p[b * NK_NP + i];
+  nk_f<nk_real>(x, pp, fx);
+  bool allzero = true;
+  NK_UNROLL for (int i = 0; i < NK_N; ++i) allzero = allzero && (fx[i] == NK_R(0));
+  int rc = 2, it = 0;
+  if (allzero) {
+    rc = 1;  // iszero(fx) (broyden.jl:44-45)
+  } else {
+    nk_real init_a = alpha_inv;
+    if (!(alpha_inv > NK_R(0))) {
+      // Julia compares fx_norm ≥ 1.0e-5 in Float64; for a Float32 norm that is fx_norm ≥ the smallest float ≥ 1e-5
+#ifdef NK_F32
+      const nk_real thresh = 0x1.4f8b5ap-17f;
+#else
+      const nk_real thresh = 1.0e-5;
+#endif
+      const nk_real fn = nk_norm2(fx), xn = nk_norm2(x);
+      init_a = fn >= thresh ? nk_jl_max(xn, NK_R(1)) / (NK_R(2) * fn) : NK_R(1);
+    }
+    nk_real Ji[NK_N][NK_N];
+    NK_UNROLL for (int i = 0; i < NK_N; ++i) {
+      fprev[i] = fx[i];
+      NK_UNROLL for (int k = 0; k < NK_N; ++k) Ji[i][k] = (i == k) ? init_a : NK_R(0);
+    }
+    for (it = 1; it <= maxiters; ++it) {
+      NK_UNROLL for (int i = 0; i < NK_N; ++i) {
+        nk_real s = NK_R(0);
+        NK_UNROLL for (int k = 0; k < NK_N; ++k) s += Ji[i][k] * fprev[k];
+        dx[i] = -s;
+      }
+      NK_UNROLL for (int i = 0; i < NK_N; ++i) x[i] += dx[i];   // x = xo + δx (xo is always the previous x)
+      nk_f<nk_real>(x, pp, fx);
+      if (nk_absmax_ok(fx, abstol)) { rc = 1; break; }
+      NK_UNROLL for (int i = 0; i < NK_N; ++i) xJ[i] = fx[i] - fprev[i];   // δf (xJ is free until below)
+      nk_real d = NK_R(0);
+      NK_UNROLL for (int i = 0; i < NK_N; ++i) {
+        nk_real s = NK_R(0);
+        NK_UNROLL for (int k = 0; k < NK_N; ++k) s += Ji[i][k] * xJ[k];
+        t[i] = s;                                                  // J⁻¹δf
+        d += dx[i] * s;
+      }
+      NK_UNROLL for (int j = 0; j < NK_N; ++j) {
+        nk_real s = NK_R(0);
+        NK_UNROLL for (int i = 0; i < NK_N; ++i) s += Ji[i][j] * dx[i];
+        xJ[j] = s;                                                 // J⁻¹ᵀδx
+      }
+      // no guard on d = 0: inf / NaN propagate as in Julia
+      NK_UNROLL for (int i = 0; i < NK_N; ++i) {
+        const nk_real w = (dx[i] - t[i]) / d;
+        NK_UNROLL for (int j = 0; j < NK_N; ++j) Ji[i][j] += w * xJ[j];
+        fprev[i] = fx[i];
+      }
+    }
+    if (it > maxiters) it = maxiters;
+  }
+  NK_UNROLL for (int i = 0; i < NK_N; ++i) { u_out[b * NK_N + i] = x[i]; r_out[b * NK_N + i] = fx[i]; }
+  retcode[b] = rc;
+  iters[b] = it;
+}
+
+// ---- SimpleKlement: diagonal J, starting at ones and reset to ones when any entry is 0; δx = fprev ./ J, x −= δx, f, check;
+// J += (f − fprev − J·δ)/(δ²J², or 1e-5 where that is 0)·δ·J² with δ = −δx.
+extern "C" __global__ void __launch_bounds__(NK_BLOCK_T)
+nk_batch_klement(long nbatch, const nk_real *__restrict__ u0, int u0_per_system, const nk_real *__restrict__ p, nk_real abstol,
+                 int maxiters, nk_real *__restrict__ u_out, nk_real *__restrict__ r_out, int *__restrict__ retcode,
+                 int *__restrict__ iters) {
+  const long b = (long)blockIdx.x * NK_BLOCK_T + threadIdx.x;
+  if (b >= nbatch) return;
+  nk_real x[NK_N], fx[NK_N], fprev[NK_N], J[NK_N], dx[NK_N], pp[NK_NP > 0 ? NK_NP : 1];
+  NK_UNROLL for (int i = 0; i < NK_N; ++i) x[i] = u0[(u0_per_system ? b * NK_N : 0) + i];
+  NK_UNROLL for (int i = 0; i < NK_NP; ++i) pp[i] = p[b * NK_NP + i];
+  nk_f<nk_real>(x, pp, fx);
+  NK_UNROLL for (int i = 0; i < NK_N; ++i) { fprev[i] = fx[i]; J[i] = NK_R(1); }
+  int rc = 2, it;
+  for (it = 1; it <= maxiters; ++it) {
+    bool anyzero = false;
+    NK_UNROLL for (int i = 0; i < NK_N; ++i) anyzero = anyzero || (J[i] == NK_R(0));
+    if (anyzero) {
+      NK_UNROLL for (int i = 0; i < NK_N; ++i) J[i] = NK_R(1);
+    }
+    NK_UNROLL for (int i = 0; i < NK_N; ++i) { dx[i] = fprev[i] / J[i]; x[i] -= dx[i]; }
+    nk_f<nk_real>(x, pp, fx);
+    if (nk_absmax_ok(fx, abstol)) { rc = 1; break; }
+    NK_UNROLL for (int i = 0; i < NK_N; ++i) {
+      const nk_real d = -dx[i], j2 = J[i] * J[i];
+      const nk_real d2 = (d * d) * j2;
+      const nk_real den = d2 == NK_R(0) ? NK_R(1.0e-5) : d2;
+      J[i] = J[i] + (((fx[i] - fprev[i]) - J[i] * d) / den) * d * j2;
+      fprev[i] = fx[i];
+    }
+  }
+  if (it > maxiters) it = maxiters;
+  NK_UNROLL for (int i = 0; i < NK_N; ++i) { u_out[b * NK_N + i] = x[i]; r_out[b * NK_N + i] = fx[i]; }
+  retcode[b] = rc;
+  iters[b] = it;
+}
+
+// ---- SimpleDFSane: spectral residual steps d = −σF with the Grippo–Lampariello–Lucidi non-monotone line search over the
+// last M merit values f = ‖F‖₂^n_exp. The counter k is the reference's: it counts outer iterations AND inner line-search
+// passes, both loops run while k < maxiters, and the history slot written is mod1(k, M) with k after the inner increments.
+__device__ inline nk_real nk_merit(const nk_real *f, int nexp) {
+  const nk_real s = nk_norm2(f);
+  return nexp == 1 ? s : s * s;
+}
+extern "C" __global__ void __launch_bounds__(NK_BLOCK_T)
+nk_batch_dfsane(long nbatch, const nk_real *__restrict__ u0, int u0_per_system, const nk_real *__restrict__ p, nk_real abstol,
+                int maxiters, nk_real sigma_min, nk_real sigma_max, nk_real sigma_1, int M, nk_real gamma, nk_real tau_min,
+                nk_real tau_max, int nexp, nk_real *__restrict__ u_out, nk_real *__restrict__ r_out, int *__restrict__ retcode,
+                int *__restrict__ iters) {
+  const long b = (long)blockIdx.x * NK_BLOCK_T + threadIdx.x;
+  if (b >= nbatch) return;
+  // fp: F at x (the reference's δf between iterations; d = −σ·fp); xc: the trial point (x_cache)
+  nk_real x[NK_N], fx[NK_N], fp[NK_N], xc[NK_N], hist[NK_HIST], pp[NK_NP > 0 ? NK_NP : 1];
+  NK_UNROLL for (int i = 0; i < NK_N; ++i) x[i] = u0[(u0_per_system ? b * NK_N : 0) + i];
+  NK_UNROLL for (int i = 0; i < NK_NP; ++i) pp[i] = p[b * NK_NP + i];
+  nk_f<nk_real>(x, pp, fx);
+  nk_real fn = nk_merit(fx, nexp);
+  const nk_real f1 = fn;
+#pragma unroll
+  for (int j = 0; j < NK_HIST; ++j) hist[j] = fn;
+  NK_UNROLL for (int i = 0; i < NK_N; ++i) { fp[i] = fx[i]; xc[i] = x[i]; }
+  nk_real sk = sigma_1;
+  int rc = 2, k = 0;
+  while (k < maxiters) {
+    sk = nk_jl_sign(sk) * nk_jl_clamp(fabs(sk), sigma_min, sigma_max);
+    const nk_real ms = -sk;
+    const long k1 = (long)k + 1;
+    const nk_real eta = f1 / (nk_real)(k1 * k1);
+    nk_real fbar = hist[0];
+#pragma unroll
+    for (int j = 1; j < NK_HIST; ++j) fbar = j < M ? nk_jl_max(fbar, hist[j]) : fbar;
+    const nk_real fbe = fbar + eta;
+    nk_real ap = NK_R(1), am = NK_R(1);
+    NK_UNROLL for (int i = 0; i < NK_N; ++i) xc[i] = x[i] + ap * (ms * fp[i]);
+    nk_f<nk_real>(xc, pp, fx);
+    nk_real fnew = nk_merit(fx, nexp);
+    while (k < maxiters) {
+      if (fnew <= fbe - gamma * (ap * ap) * fn) break;
+      const nk_real atp = (ap * ap) * fn / (fnew + (NK_R(2) * ap - NK_R(1)) * fn);
+      NK_UNROLL for (int i = 0; i < NK_N; ++i) xc[i] = x[i] - am * (ms * fp[i]);
+      nk_f<nk_real>(xc, pp, fx);
+      fnew = nk_merit(fx, nexp);
+      if (fnew <= fbe - gamma * (am * am) * fn) break;
+      const nk_real atm = (am * am) * fn / (fnew + (NK_R(2) * am - NK_R(1)) * fn);
+      ap = nk_jl_clamp(atp, tau_min * ap, tau_max * ap);
+      am = nk_jl_clamp(atm, tau_min * am, tau_max * am);
+      NK_UNROLL for (int i = 0; i < NK_N; ++i) xc[i] = x[i] + ap * (ms * fp[i]);
+      nk_f<nk_real>(xc, pp, fx);
+      fnew = nk_merit(fx, nexp);
+      ++k;
+    }
+    if (nk_absmax_ok(fx, abstol)) {
+      NK_UNROLL for (int i = 0; i < NK_N; ++i) x[i] = xc[i];
+      rc = 1;
+      ++k;   // counts the iteration that passed the check
+      break;
+    }
+    // σ = δx·δx / δx·δf with δx = x_new − x, δf = F(x_new) − F(x)
+    nk_real sxx = NK_R(0), sxf = NK_R(0);
+    NK_UNROLL for (int i = 0; i < NK_N; ++i) {
+      const nk_real dxi = xc[i] - x[i], dfi = fx[i] - fp[i];
+      sxx += dxi * dxi;
+      sxf += dxi * dfi;
+      x[i] = xc[i];
+      fp[i] = fx[i];
+    }
+    sk = sxx / sxf;
+    fn = fnew;
+    const int slot = (k + M - 1) % M;   // mod1(k, M), 0-based
+#pragma unroll
+    for (int j = 0; j < NK_HIST; ++j) hist[j] = j == slot ? fnew : hist[j];
+    ++k;
+  }
+  NK_UNROLL for (int i = 0; i < NK_N; ++i) { u_out[b * NK_N + i] = x[i]; r_out[b * NK_N + i] = fx[i]; }
+  retcode[b] = rc;
+  iters[b] = k < maxiters ? k : maxiters;
+}
+)NKSRC";
+
 // ----------------------------------------------------------------------------- hiprtc through dlopen
 typedef void *rtc_program;
 static struct {
@@ -439,6 +660,11 @@ struct nk_batch {
   int n = 0, np = 0, block = 64;
   hipModule_t mod = nullptr, mod_wave = nullptr;
   hipFunction_t fn = nullptr, fn_tr = nullptr, fn_wave = nullptr;  // fn_wave: one system per wavefront (8 < n ≤ 64)
+  // the Jacobian-free kernels: a module of their own, compiled on the first call that needs it (from source / flags)
+  hipModule_t mod_jf = nullptr;
+  hipFunction_t fn_broyden = nullptr, fn_klement = nullptr, fn_dfsane = nullptr;
+  std::string source;
+  int flags = 0;
   bool f32 = false;  // kernels built with -DNK_F32 (flags & NK_BATCH_FLOAT32): float arrays and scalar arguments
   // staging for host-memspace calls (sized in doubles; a Float32 object uses the first half of each)
   double *d_u0 = nullptr, *d_p = nullptr, *d_u = nullptr, *d_r = nullptr;
@@ -446,22 +672,29 @@ struct nk_batch {
   int64_t cap = 0;
 };
 
-// compile `source` (+ prelude + solver kernel) for n unknowns / np parameters; code object into `code`, log into `log`
+// the kernel sets, one hiprtc program each
+enum { KSET_NEWTON = 0 /* nk_batch_newton + nk_batch_trust_region */, KSET_WAVE = 1 /* nk_batch_newton_wave */,
+       KSET_JF = 2 /* nk_batch_broyden + nk_batch_klement + nk_batch_dfsane */ };
+
+// compile `source` (+ prelude + solver kernels) for n unknowns / np parameters; code object into `code`, log into `log`
 static int batch_compile(const char *source, int n, int np, int flags, std::vector<char> *code, std::string *log,
-                         bool wave = false) {
+                         int kset = KSET_NEWTON) {
+  const bool wave = kset == KSET_WAVE;
   NK_REQUIRE(source, "NULL source");
   NK_REQUIRE(n >= 1 && n <= 64, "n = %d outside 1..64 (one system per thread)", n);
   NK_REQUIRE(np >= 0 && np <= 256, "nparams = %d outside 0..256", np);
   NK_TRY(rtc_load());
-  std::string full = std::string(k_prelude) + "\n// ---- user source\n" + source + "\n" + (wave ? k_kernel_wave : k_kernel);
+  std::string full = std::string(k_prelude) + "\n// ---- user source\n" + source + "\n" +
+                     (wave ? k_kernel_wave : kset == KSET_JF ? k_kernel_jf : k_kernel);
   rtc_program prog = nullptr;
   if (RTC.Create(&prog, full.c_str(), "nk_batch_user.hip", 0, nullptr, nullptr) != 0) NK_FAIL(NK_E_HIP, "hiprtcCreateProgram failed");
-  const int ch = wave ? 1 : (n < 8 ? n : 8);  // dual-number partials per residual sweep (wave kernel: one per lane)
+  // dual-number partials per residual sweep (wave kernel: one per lane; the Jacobian-free kernels sweep no duals)
+  const int ch = wave || kset == KSET_JF ? 1 : (n < 8 ? n : 8);
   const std::string dn = "-DNK_N=" + std::to_string(n), dp = "-DNK_NP=" + std::to_string(np), dc = "-DNK_CH=" + std::to_string(ch),
                     db = wave ? "-DNK_BLOCK_T=256" : "-DNK_BLOCK_T=64";
   std::vector<const char *> opts = {"--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-std=c++17", dn.c_str(), dp.c_str(), dc.c_str(),
                                     db.c_str()};
-  if ((flags & NK_BATCH_ANALYTIC_JAC) && !wave) opts.push_back("-DNK_HAS_JAC=1");
+  if ((flags & NK_BATCH_ANALYTIC_JAC) && kset == KSET_NEWTON) opts.push_back("-DNK_HAS_JAC=1");
   if (flags & NK_BATCH_FLOAT32) opts.push_back("-DNK_F32=1");
   const int rc = RTC.Compile(prog, (int)opts.size(), opts.data());
   size_t ls = 0;
@@ -493,7 +726,7 @@ extern "C" int nk_batch_compile_check(const char *source, int n, int nparams, in
   if (n > 8) {  // medium systems also get the per-wavefront Newton kernel
     std::vector<char> wcode;
     std::string wlog;
-    NK_TRY(batch_compile(source, n, nparams, flags, &wcode, &wlog, true));
+    NK_TRY(batch_compile(source, n, nparams, flags, &wcode, &wlog, KSET_WAVE));
     if (code_bytes) *code_bytes += (int64_t)wcode.size();
   }
   return NK_OK;
@@ -506,7 +739,21 @@ extern "C" int nk_batch_code_object(const char *source, int n, int nparams, int 
   NK_REQUIRE(bytes, "NULL argument");
   std::vector<char> code;
   std::string log;
-  NK_TRY(batch_compile(source, n, nparams, flags, &code, &log, wave != 0));
+  NK_TRY(batch_compile(source, n, nparams, flags, &code, &log, wave != 0 ? KSET_WAVE : KSET_NEWTON));
+  *bytes = (int64_t)code.size();
+  if (!buf) return NK_OK;
+  NK_REQUIRE(capacity >= *bytes, "buffer of %lld bytes, the code object has %lld", (long long)capacity, (long long)*bytes);
+  memcpy(buf, code.data(), code.size());
+  return NK_OK;
+}
+
+// the same for the Jacobian-free kernel set (nk_batch_broyden, nk_batch_klement, nk_batch_dfsane)
+extern "C" int nk_batch_jf_code_object(const char *source, int n, int nparams, int flags, void *buf, int64_t capacity,
+                                       int64_t *bytes) {
+  NK_REQUIRE(bytes, "NULL argument");
+  std::vector<char> code;
+  std::string log;
+  NK_TRY(batch_compile(source, n, nparams, flags, &code, &log, KSET_JF));
   *bytes = (int64_t)code.size();
   if (!buf) return NK_OK;
   NK_REQUIRE(capacity >= *bytes, "buffer of %lld bytes, the code object has %lld", (long long)capacity, (long long)*bytes);
@@ -525,6 +772,8 @@ extern "C" int nk_batch_create(nk_ctx *ctx, const char *source, int n, int npara
   B->n = n;
   B->np = nparams;
   B->f32 = (flags & NK_BATCH_FLOAT32) != 0;
+  B->source = source;
+  B->flags = flags;
   if (hipModuleLoadData(&B->mod, code.data()) != hipSuccess) { delete B; NK_FAIL(NK_E_HIP, "hipModuleLoadData failed"); }
   if (hipModuleGetFunction(&B->fn, B->mod, "nk_batch_newton") != hipSuccess) {
     hipModuleUnload(B->mod);
@@ -535,7 +784,7 @@ extern "C" int nk_batch_create(nk_ctx *ctx, const char *source, int n, int npara
   if (n > 8) {  // Newton for medium systems: the per-wavefront kernel
     std::vector<char> wcode;
     std::string wlog;
-    if (batch_compile(source, n, nparams, flags, &wcode, &wlog, true) == NK_OK &&
+    if (batch_compile(source, n, nparams, flags, &wcode, &wlog, KSET_WAVE) == NK_OK &&
         hipModuleLoadData(&B->mod_wave, wcode.data()) == hipSuccess) {
       if (hipModuleGetFunction(&B->fn_wave, B->mod_wave, "nk_batch_newton_wave") != hipSuccess) B->fn_wave = nullptr;
     }
@@ -551,6 +800,7 @@ extern "C" int nk_batch_destroy(nk_batch *B) {
   hipFree(B->d_u0); hipFree(B->d_p); hipFree(B->d_u); hipFree(B->d_r); hipFree(B->d_rc); hipFree(B->d_it);
   if (B->mod) hipModuleUnload(B->mod);
   if (B->mod_wave) hipModuleUnload(B->mod_wave);
+  if (B->mod_jf) hipModuleUnload(B->mod_jf);
   delete B;
   return NK_OK;
 }
@@ -559,20 +809,46 @@ extern "C" int nk_batch_destroy(nk_batch *B) {
 // p: nbatch×nparams. Outputs (nbatch×n, nbatch×n, nbatch, nbatch); retcode/iters may be NULL. The arrays hold doubles, or
 // floats for an object built with NK_BATCH_FLOAT32 (f32 says which entry point the caller used); the scalars arrive as double
 // and reach the kernels in the object's precision, T(abstol) as the reference takes them.
-// tr == nullptr: SimpleNewtonRaphson; else SimpleTrustRegion with tr = {η₁, η₂, η₃, t₁, t₂, max_shrink_times}.
-static int batch_run(nk_batch *B, bool f32, int64_t nbatch, const void *u0, int u0_per_system, const void *p, int memspace,
-                     double abstol, int maxiters, const double *tr, void *u_out, void *resid_out, int32_t *retcode_out,
-                     int32_t *iters_out) {
+// prm holds the method's parameters, defaults applied (reals and integers alike as double):
+//   BATCH_TRUST_REGION {η₁, η₂, η₃, t₁, t₂, max_shrink_times}; BATCH_BROYDEN {1/alpha, or 0 for `nothing`};
+//   BATCH_DFSANE {σ_min, σ_max, σ₁, M, γ, τ_min, τ_max, n_exp}; nothing for BATCH_NEWTON and BATCH_KLEMENT.
+enum { BATCH_NEWTON, BATCH_TRUST_REGION, BATCH_BROYDEN, BATCH_KLEMENT, BATCH_DFSANE };
+
+// the Jacobian-free module, compiled and loaded on the first call that needs it, then kept on the object
+static int batch_load_jf(nk_batch *B) {
+  if (B->mod_jf) return NK_OK;
+  std::vector<char> code;
+  std::string log;
+  NK_TRY(batch_compile(B->source.c_str(), B->n, B->np, B->flags, &code, &log, KSET_JF));
+  hipModule_t m = nullptr;
+  if (hipModuleLoadData(&m, code.data()) != hipSuccess) NK_FAIL(NK_E_HIP, "hipModuleLoadData failed (Jacobian-free kernels)");
+  hipFunction_t fb = nullptr, fk = nullptr, fd = nullptr;
+  if (hipModuleGetFunction(&fb, m, "nk_batch_broyden") != hipSuccess || hipModuleGetFunction(&fk, m, "nk_batch_klement") != hipSuccess ||
+      hipModuleGetFunction(&fd, m, "nk_batch_dfsane") != hipSuccess) {
+    hipModuleUnload(m);
+    NK_FAIL(NK_E_HIP, "a Jacobian-free kernel is missing from the compiled module");
+  }
+  B->mod_jf = m;
+  B->fn_broyden = fb;
+  B->fn_klement = fk;
+  B->fn_dfsane = fd;
+  return NK_OK;
+}
+
+static int batch_run(nk_batch *B, bool f32, int method, int64_t nbatch, const void *u0, int u0_per_system, const void *p,
+                     int memspace, double abstol, int maxiters, const double *prm, void *u_out, void *resid_out,
+                     int32_t *retcode_out, int32_t *iters_out) {
   NK_REQUIRE(B && u0 && u_out && resid_out, "NULL argument");
   NK_REQUIRE(B->f32 == f32, B->f32 ? "this ensemble was compiled for Float32 (NK_BATCH_FLOAT32): call the _f32 entry points"
                                    : "this ensemble was compiled for Float64: the _f32 entry points need NK_BATCH_FLOAT32");
   NK_REQUIRE(nbatch >= 0, "negative batch size");
   NK_REQUIRE(B->np == 0 || p, "parameters are required (nparams = %d)", B->np);
-  NK_REQUIRE(!tr || B->fn_tr, "the compiled module lacks the trust-region kernel");
+  NK_REQUIRE(method != BATCH_TRUST_REGION || B->fn_tr, "the compiled module lacks the trust-region kernel");
   nk_ctx *ctx = B->ctx;
   NK_HIP(hipSetDevice(ctx->device));
   if (nbatch == 0) return NK_OK;
-  if (maxiters <= 0) maxiters = 1000;                             // raphson.jl:42 / trust_region.jl:60
+  if (method >= BATCH_BROYDEN) NK_TRY(batch_load_jf(B));
+  if (maxiters <= 0) maxiters = 1000;                             // raphson.jl:42 / trust_region.jl:60 / broyden.jl:33 / ...
   const int n = B->n, np = B->np;
   const size_t es = f32 ? sizeof(float) : sizeof(double);
   if (B->cap < nbatch) {
@@ -601,31 +877,49 @@ static int batch_run(nk_batch *B, bool f32, int64_t nbatch, const void *u0, int 
   long nb = (long)nbatch;
   int ups = u0_per_system ? 1 : 0;
   int *drc = B->d_rc, *dit = B->d_it;
-  // the kernels' real scalars: abstol, then η₁, η₂, η₃, t₁, t₂ (trust region); the defaults are the element type's
+  // the kernels' real scalars: abstol, then the method's parameters; the defaults are the element type's
   // (common_defaults.jl:39-53: eps(T)^(4/5), taken in T)
-  double sd[6];
-  float sf[6];
+  const int nprm = method == BATCH_TRUST_REGION ? 6 : method == BATCH_BROYDEN ? 1 : method == BATCH_DFSANE ? 8 : 0;
+  double sd[9];
+  float sf[9];
   sd[0] = abstol > 0.0 ? abstol : pow(2.220446049250313e-16, 0.8);
   sf[0] = abstol > 0.0 ? (float)abstol : powf(1.1920929e-7f, 0.8f);
-  for (int k = 0; k < 5; ++k) { sd[k + 1] = tr ? tr[k] : 0.0; sf[k + 1] = (float)sd[k + 1]; }
-  void *sa[6];
-  for (int k = 0; k < 6; ++k) sa[k] = f32 ? (void *)&sf[k] : (void *)&sd[k];
+  for (int k = 0; k < 8; ++k) { sd[k + 1] = k < nprm ? prm[k] : 0.0; sf[k + 1] = (float)sd[k + 1]; }
+  void *sa[9];
+  for (int k = 0; k < 9; ++k) sa[k] = f32 ? (void *)&sf[k] : (void *)&sd[k];
   const unsigned grid = (unsigned)((nbatch + B->block - 1) / B->block);
-  if (!tr && B->fn_wave) {
+  hipError_t st = hipSuccess;
+  const char *kname = "";
+  if (method == BATCH_NEWTON && B->fn_wave) {
     void *args[] = {&nb, &du0, &ups, &dp, sa[0], &maxiters, &du, &dr, &drc, &dit};
     const unsigned wgrid = (unsigned)((nbatch + 3) / 4);  // 4 wavefronts = 4 systems per 256-thread workgroup
-    if (hipModuleLaunchKernel(B->fn_wave, wgrid, 1, 1, 256, 1, 1, 0, ctx->stream, args, nullptr) != hipSuccess)
-      NK_FAIL(NK_E_HIP, "launch of nk_batch_newton_wave failed");
-  } else if (!tr) {
+    st = hipModuleLaunchKernel(B->fn_wave, wgrid, 1, 1, 256, 1, 1, 0, ctx->stream, args, nullptr);
+    kname = "nk_batch_newton_wave";
+  } else if (method == BATCH_NEWTON) {
     void *args[] = {&nb, &du0, &ups, &dp, sa[0], &maxiters, &du, &dr, &drc, &dit};
-    if (hipModuleLaunchKernel(B->fn, grid, 1, 1, B->block, 1, 1, 0, ctx->stream, args, nullptr) != hipSuccess)
-      NK_FAIL(NK_E_HIP, "launch of nk_batch_newton failed");
-  } else {
-    int ms = (int)tr[5];
+    st = hipModuleLaunchKernel(B->fn, grid, 1, 1, B->block, 1, 1, 0, ctx->stream, args, nullptr);
+    kname = "nk_batch_newton";
+  } else if (method == BATCH_TRUST_REGION) {
+    int ms = (int)prm[5];
     void *args[] = {&nb, &du0, &ups, &dp, sa[0], &maxiters, sa[1], sa[2], sa[3], sa[4], sa[5], &ms, &du, &dr, &drc, &dit};
-    if (hipModuleLaunchKernel(B->fn_tr, grid, 1, 1, B->block, 1, 1, 0, ctx->stream, args, nullptr) != hipSuccess)
-      NK_FAIL(NK_E_HIP, "launch of nk_batch_trust_region failed");
+    st = hipModuleLaunchKernel(B->fn_tr, grid, 1, 1, B->block, 1, 1, 0, ctx->stream, args, nullptr);
+    kname = "nk_batch_trust_region";
+  } else if (method == BATCH_BROYDEN) {
+    void *args[] = {&nb, &du0, &ups, &dp, sa[0], &maxiters, sa[1], &du, &dr, &drc, &dit};
+    st = hipModuleLaunchKernel(B->fn_broyden, grid, 1, 1, B->block, 1, 1, 0, ctx->stream, args, nullptr);
+    kname = "nk_batch_broyden";
+  } else if (method == BATCH_KLEMENT) {
+    void *args[] = {&nb, &du0, &ups, &dp, sa[0], &maxiters, &du, &dr, &drc, &dit};
+    st = hipModuleLaunchKernel(B->fn_klement, grid, 1, 1, B->block, 1, 1, 0, ctx->stream, args, nullptr);
+    kname = "nk_batch_klement";
+  } else {
+    int M = (int)prm[3], ne = (int)prm[7];
+    void *args[] = {&nb, &du0, &ups, &dp, sa[0], &maxiters, sa[1], sa[2], sa[3], &M, sa[5], sa[6], sa[7], &ne,
+                    &du, &dr, &drc, &dit};
+    st = hipModuleLaunchKernel(B->fn_dfsane, grid, 1, 1, B->block, 1, 1, 0, ctx->stream, args, nullptr);
+    kname = "nk_batch_dfsane";
   }
+  if (st != hipSuccess) NK_FAIL(NK_E_HIP, "launch of %s failed", kname);
   if (memspace != NK_DEVICE) {
     NK_HIP(hipMemcpyAsync(u_out, du, (size_t)nbatch * n * es, hipMemcpyDeviceToHost, ctx->stream));
     NK_HIP(hipMemcpyAsync(resid_out, dr, (size_t)nbatch * n * es, hipMemcpyDeviceToHost, ctx->stream));
@@ -644,15 +938,15 @@ static int batch_run(nk_batch *B, bool f32, int64_t nbatch, const void *u0, int 
 extern "C" int nk_batch_solve(nk_batch *B, int64_t nbatch, const double *u0, int u0_per_system, const double *p, int memspace,
                               double abstol, int maxiters, double *u_out, double *resid_out, int32_t *retcode_out,
                               int32_t *iters_out) {
-  return batch_run(B, false, nbatch, u0, u0_per_system, p, memspace, abstol, maxiters, nullptr, u_out, resid_out, retcode_out,
-                   iters_out);
+  return batch_run(B, false, BATCH_NEWTON, nbatch, u0, u0_per_system, p, memspace, abstol, maxiters, nullptr, u_out, resid_out,
+                   retcode_out, iters_out);
 }
 
 extern "C" int nk_batch_solve_f32(nk_batch *B, int64_t nbatch, const float *u0, int u0_per_system, const float *p, int memspace,
                                   double abstol, int maxiters, float *u_out, float *resid_out, int32_t *retcode_out,
                                   int32_t *iters_out) {
-  return batch_run(B, true, nbatch, u0, u0_per_system, p, memspace, abstol, maxiters, nullptr, u_out, resid_out, retcode_out,
-                   iters_out);
+  return batch_run(B, true, BATCH_NEWTON, nbatch, u0, u0_per_system, p, memspace, abstol, maxiters, nullptr, u_out, resid_out,
+                   retcode_out, iters_out);
 }
 
 // SimpleTrustRegion (lib/SimpleNonlinearSolve/src/trust_region.jl); thresholds/factors ≤ 0 and max_shrink_times < 0 select
@@ -675,8 +969,8 @@ extern "C" int nk_batch_solve_trust_region(nk_batch *B, int64_t nbatch, const do
                                            int32_t *retcode_out, int32_t *iters_out) {
   double tr[6];
   trust_region_params(tr, step_threshold, shrink_threshold, expand_threshold, shrink_factor, expand_factor, max_shrink_times);
-  return batch_run(B, false, nbatch, u0, u0_per_system, p, memspace, abstol, maxiters, tr, u_out, resid_out, retcode_out,
-                   iters_out);
+  return batch_run(B, false, BATCH_TRUST_REGION, nbatch, u0, u0_per_system, p, memspace, abstol, maxiters, tr, u_out,
+                   resid_out, retcode_out, iters_out);
 }
 
 extern "C" int nk_batch_solve_trust_region_f32(nk_batch *B, int64_t nbatch, const float *u0, int u0_per_system, const float *p,
@@ -686,6 +980,76 @@ extern "C" int nk_batch_solve_trust_region_f32(nk_batch *B, int64_t nbatch, cons
                                                int32_t *retcode_out, int32_t *iters_out) {
   double tr[6];
   trust_region_params(tr, step_threshold, shrink_threshold, expand_threshold, shrink_factor, expand_factor, max_shrink_times);
-  return batch_run(B, true, nbatch, u0, u0_per_system, p, memspace, abstol, maxiters, tr, u_out, resid_out, retcode_out,
-                   iters_out);
+  return batch_run(B, true, BATCH_TRUST_REGION, nbatch, u0, u0_per_system, p, memspace, abstol, maxiters, tr, u_out,
+                   resid_out, retcode_out, iters_out);
+}
+
+// SimpleBroyden (broyden.jl:31-108, linesearch = nothing): alpha ≤ 0 is `nothing` (init_α from the norms of f(u0) and u0),
+// else init_α = inv(alpha), taken in double as Julia takes it for a Float64 alpha.
+extern "C" int nk_batch_solve_broyden(nk_batch *B, int64_t nbatch, const double *u0, int u0_per_system, const double *p,
+                                      int memspace, double abstol, int maxiters, double alpha, double *u_out, double *resid_out,
+                                      int32_t *retcode_out, int32_t *iters_out) {
+  const double prm[1] = {alpha > 0 ? 1.0 / alpha : 0.0};
+  return batch_run(B, false, BATCH_BROYDEN, nbatch, u0, u0_per_system, p, memspace, abstol, maxiters, prm, u_out, resid_out,
+                   retcode_out, iters_out);
+}
+
+extern "C" int nk_batch_solve_broyden_f32(nk_batch *B, int64_t nbatch, const float *u0, int u0_per_system, const float *p,
+                                          int memspace, double abstol, int maxiters, double alpha, float *u_out,
+                                          float *resid_out, int32_t *retcode_out, int32_t *iters_out) {
+  const double prm[1] = {alpha > 0 ? 1.0 / alpha : 0.0};
+  return batch_run(B, true, BATCH_BROYDEN, nbatch, u0, u0_per_system, p, memspace, abstol, maxiters, prm, u_out, resid_out,
+                   retcode_out, iters_out);
+}
+
+// SimpleKlement (klement.jl:9-56): no parameters
+extern "C" int nk_batch_solve_klement(nk_batch *B, int64_t nbatch, const double *u0, int u0_per_system, const double *p,
+                                      int memspace, double abstol, int maxiters, double *u_out, double *resid_out,
+                                      int32_t *retcode_out, int32_t *iters_out) {
+  return batch_run(B, false, BATCH_KLEMENT, nbatch, u0, u0_per_system, p, memspace, abstol, maxiters, nullptr, u_out, resid_out,
+                   retcode_out, iters_out);
+}
+
+extern "C" int nk_batch_solve_klement_f32(nk_batch *B, int64_t nbatch, const float *u0, int u0_per_system, const float *p,
+                                          int memspace, double abstol, int maxiters, float *u_out, float *resid_out,
+                                          int32_t *retcode_out, int32_t *iters_out) {
+  return batch_run(B, true, BATCH_KLEMENT, nbatch, u0, u0_per_system, p, memspace, abstol, maxiters, nullptr, u_out, resid_out,
+                   retcode_out, iters_out);
+}
+
+// SimpleDFSane (dfsane.jl:66-172): reals ≤ 0 select the defaults σ_min = 1e-10, σ_max = 1e10, σ₁ = 1, γ = 1e-4, τ_min = 0.1,
+// τ_max = 0.5; M (1..32) and n_exp (1 or 2) take 0 for their defaults 10 and 2; any other value is NK_E_INVALID.
+static int dfsane_params(double *prm, double sigma_min, double sigma_max, double sigma_1, int M, double gamma, double tau_min,
+                         double tau_max, int n_exp) {
+  NK_REQUIRE(M >= 0 && M <= 32, "M = %d outside 1..32 (0 selects the default, 10)", M);
+  NK_REQUIRE(n_exp >= 0 && n_exp <= 2, "n_exp = %d: 1 or 2 (0 selects the default, 2)", n_exp);
+  prm[0] = sigma_min > 0 ? sigma_min : 1e-10;
+  prm[1] = sigma_max > 0 ? sigma_max : 1e10;
+  prm[2] = sigma_1 > 0 ? sigma_1 : 1.0;
+  prm[3] = M > 0 ? M : 10;
+  prm[4] = gamma > 0 ? gamma : 1e-4;
+  prm[5] = tau_min > 0 ? tau_min : 0.1;
+  prm[6] = tau_max > 0 ? tau_max : 0.5;
+  prm[7] = n_exp > 0 ? n_exp : 2;
+  return NK_OK;
+}
+
+extern "C" int nk_batch_solve_dfsane(nk_batch *B, int64_t nbatch, const double *u0, int u0_per_system, const double *p,
+                                     int memspace, double abstol, int maxiters, double sigma_min, double sigma_max,
+                                     double sigma_1, int M, double gamma, double tau_min, double tau_max, int n_exp,
+                                     double *u_out, double *resid_out, int32_t *retcode_out, int32_t *iters_out) {
+  double prm[8];
+  NK_TRY(dfsane_params(prm, sigma_min, sigma_max, sigma_1, M, gamma, tau_min, tau_max, n_exp));
+  return batch_run(B, false, BATCH_DFSANE, nbatch, u0, u0_per_system, p, memspace, abstol, maxiters, prm, u_out, resid_out,
+                   retcode_out, iters_out);
+}
+
+extern "C" int nk_batch_solve_dfsane_f32(nk_batch *B, int64_t nbatch, const float *u0, int u0_per_system, const float *p,
+                                         int memspace, double abstol, int maxiters, double sigma_min, double sigma_max,
+                                         double sigma_1, int M, double gamma, double tau_min, double tau_max, int n_exp,
+                                         float *u_out, float *resid_out, int32_t *retcode_out, int32_t *iters_out) {
+  double prm[8];
+  NK_TRY(dfsane_params(prm, sigma_min, sigma_max, sigma_1, M, gamma, tau_min, tau_max, n_exp));
+  return batch_run(B, true, BATCH_DFSANE, nbatch, u0, u0_per_system, p, memspace, abstol, maxiters, prm, u_out, resid_out,
+                   retcode_out, iters_out);
 }
