@@ -181,13 +181,16 @@ __global__ __launch_bounds__(512) void k_bcr_inv128(double *__restrict__ mats, i
       int p = k;
       if (PIVOT) {
         __syncthreads();
-        // Every wavefront finds the pivot row for itself (same data, same order: same answer). The magnitudes are compared as
-        // float bit patterns (+2; a NaN ranks 1, a used row 0: the choice always falls on an unused row, so the pivot rows form
-        // a permutation whatever the data — the permuted store below relies on that) through a DPP max reduction — six
-        // v_max_u32_dpp; a shuffle butterfly on (double, index) pairs cost 18 LDS round trips per pivot, 3× the whole step.
+        // Every wavefront finds the pivot row for itself (same data, same order: same answer). The magnitudes are compared by
+        // the high word of the double without its sign (exponent and 20 mantissa bits: monotone in |x| over the WHOLE exponent
+        // range — a float conversion turned everything above 2^128 into inf and below 2^-149 into 0, and the choice into "first
+        // unused row", zero or not; +2; a NaN ranks 1, a used row 0: the choice always falls on an unused row, so the pivot
+        // rows form a permutation whatever the data — the permuted store below relies on that) through a DPP max reduction —
+        // six v_max_u32_dpp; a shuffle butterfly on (double, index) pairs cost 18 LDS round trips per pivot, 3× the whole step.
         const int l = t & 63;
-        const float f0 = fabsf((float)colb[buf][l]), f1 = fabsf((float)colb[buf][l + 64]);
-        unsigned k0 = (f0 == f0) ? __float_as_uint(f0) + 2u : 1u, k1 = (f1 == f1) ? __float_as_uint(f1) + 2u : 1u;
+        const double c0 = colb[buf][l], c1 = colb[buf][l + 64];
+        unsigned k0 = (c0 == c0) ? ((unsigned)__double2hiint(c0) & 0x7fffffffu) + 2u : 1u;
+        unsigned k1 = (c1 == c1) ? ((unsigned)__double2hiint(c1) & 0x7fffffffu) + 2u : 1u;
         if (usedf[l]) k0 = 0u;
         if (usedf[l + 64]) k1 = 0u;
         const unsigned km = bcr_wave_max_u32(k0 > k1 ? k0 : k1);
@@ -211,8 +214,10 @@ __global__ __launch_bounds__(512) void k_bcr_inv128(double *__restrict__ mats, i
       // (the bookkeeping is written only now: before the barrier other wavefronts may still be reading usedf for THIS pivot)
       if (PIVOT && t == 0) { prow[k] = p; usedf[p] = 1; }
       const double piv = colb[buf][p];
-      bad = bad || !(fabs(piv) > 1e-290);  // zero, denormal-small or NaN
       const double pinv = bcr_rcp(piv);
+      // zero, NaN or inf (0 · NaN in the Newton steps), or so small that the reciprocal overflows; a pivot is NOT refused for
+      // being small in absolute terms: 2^-1000 A is as well conditioned as A
+      bad = bad || !(fabs(piv) > 0.0) || !(fabs(pinv) < INFINITY);
       double mr[8], rk[4];
 #pragma unroll
       for (int q = 0; q < 8; ++q) mr[q] = colb[buf][ti * 8 + q];
