@@ -712,6 +712,61 @@ int nk_batch_solve_dfsane_f32(nk_batch *B, int64_t nbatch, const float *u0, int 
  * nk_batch_code_object; no device needed */
 int nk_batch_jf_code_object(const char *source, int n, int nparams, int flags, void *buf, int64_t capacity, int64_t *bytes);
 
+/* ---------------------------------------------------------------- ensembles of small nonlinear least-squares problems
+ * m residuals, n unknowns, 1 <= n <= m <= 64, one problem per GPU thread: fitting a small model to each of many data sets.
+ * SimpleGaussNewton — the reference's alias of SimpleNewtonRaphson (lib/SimpleNonlinearSolve/src/raphson.jl:31), declared on
+ * Union{ImmutableNonlinearProblem, NonlinearLeastSquaresProblem} (raphson.jl:41-43) — and SimpleTrustRegion
+ * (trust_region.jl:60-62). The source contract is that of nk_batch_create; only the output length differs:
+ *     template <typename T> __device__ void nk_f(const T *u, const nk_real *p, T *f);   // u: n values, f: m values
+ *     __device__ void nk_jac(const nk_real *u, const nk_real *p, nk_real *J);           // optional, row-major m×n
+ * compiled with -DNK_N=n -DNK_M=m (nk_real = double, or float with NK_BATCH_FLOAT32); entries of f that the source does
+ * not write are zero. Each fit's data travels in p (e.g. nparams = 2m for (x_i, y_i) pairs; nparams <= 256; p is read in
+ * place when nparams > 32). m < n is NK_E_INVALID: the minimum-norm solution of an underdetermined problem is not offered.
+ * m == n is accepted and runs the same kernels. These objects are a kind of their own: nk_batch_destroy frees them, the
+ * square entry points (nk_batch_solve*) refuse them and the entry points below refuse square objects (NK_E_INVALID), as does
+ * either precision's entry point on an object of the other.
+ * Per problem:
+ *  - termination is AbsNormTerminationMode(Base.Fix2(norm, 2)), the reference's :simple default for a
+ *    NonlinearLeastSquaresProblem (lib/NonlinearSolveBase/src/termination_conditions.jl:381-383): ‖f‖₂ <= abstol, not
+ *    max-abs; default abstol eps(T)^(4/5), maxiters 1000; a NaN norm never terminates. Consequence: a fit whose minimum
+ *    residual is not zero never reports Success — it ends in NK_RET_MAXITERS (Gauss–Newton) or
+ *    NK_RET_SHRINK_THRESHOLD_EXCEEDED / NK_RET_MAXITERS (trust region), as in the reference.
+ *  - SimpleGaussNewton (raphson.jl:52-81): iszero(f(u0)) ⇒ Success with 0 iterations; per iteration δ = J \ f, u −= δ, the
+ *    check on the residual of the previous iterate, then f and J at the new u.
+ *  - SimpleTrustRegion (trust_region.jl:60-229, default radius update; the nlsolve_update_rule variant is not offered, as
+ *    for the square kernel): a check before the loop, no iszero shortcut; H = JᵀJ (n×n), g = Jᵀf, dogleg with
+ *    δN = −(J \ f); ratio, radius updates, defaults and retcodes as nk_batch_solve_trust_region;
+ *    Δmax = max(‖f(u0)‖₂, max(u0) − min(u0)) over the n unknowns, Δ0 = Δmax/11.
+ *  - J \ f is the least-squares solution by Householder QR with column pivoting, in place, with no normal equations.
+ *    Divergence from the reference, which leaves rank deficiency to LAPACK's rank truncation: a column whose pivot has
+ *    |r_kk| <= max(m, n)·eps(T)·|r_11| gets a zero step component (the basic solution, not the minimum-norm one). Column
+ *    norms are taken without scaling, so entries beyond sqrt(floatmax(T)) overflow them.
+ *  - resid_out is nbatch×m (f at the last evaluated iterate); the other outputs are as for nk_batch_solve.
+ * Everything lives in registers while n <= 8 and m·(n + 2) <= 80 (Float64) or 128 (Float32) — e.g. 5×4, 8×3, 16×3, 8×8 in
+ * both, 32×2 and 12×8 in Float32 only; found with the compiler's resource notes, not timed. Larger shapes run from scratch
+ * memory. One problem per thread only: a per-wavefront form would need a
+ * per-residual user function, a second source contract. */
+int nk_batch_nlls_compile_check(const char *source, int n, int m, int nparams, int flags, int64_t *code_bytes);
+/* the code object of the least-squares kernel set (nk_batch_gauss_newton, nk_batch_trust_region_nlls), as nk_batch_code_object */
+int nk_batch_nlls_code_object(const char *source, int n, int m, int nparams, int flags, void *buf, int64_t capacity,
+                              int64_t *bytes);
+int nk_batch_create_nlls(nk_ctx *ctx, const char *source, int n, int m, int nparams, int flags, nk_batch **out);
+int nk_batch_solve_gauss_newton(nk_batch *B, int64_t nbatch, const double *u0, int u0_per_system, const double *p, int memspace,
+                                double abstol, int maxiters, double *u_out, double *resid_out, int32_t *retcode_out,
+                                int32_t *iters_out);
+int nk_batch_solve_gauss_newton_f32(nk_batch *B, int64_t nbatch, const float *u0, int u0_per_system, const float *p,
+                                    int memspace, double abstol, int maxiters, float *u_out, float *resid_out,
+                                    int32_t *retcode_out, int32_t *iters_out);
+int nk_batch_solve_trust_region_nlls(nk_batch *B, int64_t nbatch, const double *u0, int u0_per_system, const double *p,
+                                     int memspace, double abstol, int maxiters, double step_threshold, double shrink_threshold,
+                                     double expand_threshold, double shrink_factor, double expand_factor, int max_shrink_times,
+                                     double *u_out, double *resid_out, int32_t *retcode_out, int32_t *iters_out);
+int nk_batch_solve_trust_region_nlls_f32(nk_batch *B, int64_t nbatch, const float *u0, int u0_per_system, const float *p,
+                                         int memspace, double abstol, int maxiters, double step_threshold,
+                                         double shrink_threshold, double expand_threshold, double shrink_factor,
+                                         double expand_factor, int max_shrink_times, float *u_out, float *resid_out,
+                                         int32_t *retcode_out, int32_t *iters_out);
+
 /* ---------------------------------------------------------------- BLAS-1 building blocks (exported for
  * the bench / tests; all on the ctx stream, results of reductions are all-reduced over the ranks) */
 int nk_dot(nk_ctx *ctx, int64_t n, const double *x, const double *y, double *result);

@@ -699,12 +699,70 @@ function jacobian_free_solve(k::EnsembleKernel, u0::Vector{T}, p::Matrix{T}, alg
     return (; u, resid, retcode = [RETCODES[c + 1] for c in rc], iters)
 end
 
+# Least squares on the ensemble path: m = resid_size residuals for n unknowns, n ≤ m ≤ 64, one problem per GPU thread — the
+# reference's SimpleGaussNewton (`const SimpleGaussNewton = SimpleNewtonRaphson`, raphson.jl:31) and SimpleTrustRegion on a
+# NonlinearLeastSquaresProblem. `f_source` writes m values into f (and `nk_jac` the row-major m×n Jacobian with has_jac);
+# termination is ‖f‖₂ ≤ abstol, so a fit with a non-zero minimum ends in MaxIters / ShrinkThresholdExceeded. resid is m × nbatch.
+const SimpleGaussNewton = :SimpleNewtonRaphson
+
+mutable struct LeastSquaresEnsembleKernel
+    ptr::Ptr{Cvoid}
+    n::Int
+    m::Int
+    nparams::Int
+    eltype::DataType
+    function LeastSquaresEnsembleKernel(ctx::Ctx, f_source::String, n::Integer, resid_size::Integer, nparams::Integer;
+            has_jac::Bool = false, eltype::Type{<:Union{Float32, Float64}} = Float64)
+        h = Ref{Ptr{Cvoid}}(C_NULL)
+        flags = (has_jac ? NK_BATCH_ANALYTIC_JAC : Cint(0)) | (eltype === Float32 ? NK_BATCH_FLOAT32 : Cint(0))
+        nkcheck(@ccall libnk.nk_batch_create_nlls(ctx.ptr::Ptr{Cvoid}, f_source::Cstring, n::Cint, resid_size::Cint,
+            nparams::Cint, flags::Cint, h::Ptr{Ptr{Cvoid}})::Cint)
+        k = new(h[], n, resid_size, nparams, eltype)
+        finalizer(x -> @ccall(libnk.nk_batch_destroy(x.ptr::Ptr{Cvoid})::Cint), k)
+        return k
+    end
+end
+
+function vectorized_solve(k::LeastSquaresEnsembleKernel, u0::Vector{T}, p::Matrix{T}; alg = SimpleGaussNewton, abstol = 0.0,
+        maxiters = 1000) where {T <: Union{Float32, Float64}}
+    k.eltype === T || throw(ArgumentError("this LeastSquaresEnsembleKernel was built for $(k.eltype)"))
+    alg in (:SimpleNewtonRaphson, :SimpleTrustRegion) ||
+        throw(ArgumentError("$alg is not defined on a least-squares problem: use SimpleGaussNewton or :SimpleTrustRegion"))
+    nb = size(p, 2)
+    u = Matrix{T}(undef, k.n, nb); resid = Matrix{T}(undef, k.m, nb)
+    rc = Vector{Int32}(undef, nb); iters = Vector{Int32}(undef, nb)
+    tol = Float64(abstol)
+    GC.@preserve u0 p u resid rc iters begin
+        st = if T === Float64 && alg === :SimpleTrustRegion
+            @ccall libnk.nk_batch_solve_trust_region_nlls(k.ptr::Ptr{Cvoid}, nb::Int64, u0::Ptr{Float64}, 0::Cint,
+                p::Ptr{Float64}, 0::Cint, tol::Float64, maxiters::Cint, (-1.0)::Float64, (-1.0)::Float64, (-1.0)::Float64,
+                (-1.0)::Float64, (-1.0)::Float64, (-1)::Cint, u::Ptr{Float64}, resid::Ptr{Float64}, rc::Ptr{Int32},
+                iters::Ptr{Int32})::Cint
+        elseif T === Float64
+            @ccall libnk.nk_batch_solve_gauss_newton(k.ptr::Ptr{Cvoid}, nb::Int64, u0::Ptr{Float64}, 0::Cint,
+                p::Ptr{Float64}, 0::Cint, tol::Float64, maxiters::Cint, u::Ptr{Float64}, resid::Ptr{Float64}, rc::Ptr{Int32},
+                iters::Ptr{Int32})::Cint
+        elseif alg === :SimpleTrustRegion
+            @ccall libnk.nk_batch_solve_trust_region_nlls_f32(k.ptr::Ptr{Cvoid}, nb::Int64, u0::Ptr{Float32}, 0::Cint,
+                p::Ptr{Float32}, 0::Cint, tol::Float64, maxiters::Cint, (-1.0)::Float64, (-1.0)::Float64, (-1.0)::Float64,
+                (-1.0)::Float64, (-1.0)::Float64, (-1)::Cint, u::Ptr{Float32}, resid::Ptr{Float32}, rc::Ptr{Int32},
+                iters::Ptr{Int32})::Cint
+        else
+            @ccall libnk.nk_batch_solve_gauss_newton_f32(k.ptr::Ptr{Cvoid}, nb::Int64, u0::Ptr{Float32}, 0::Cint,
+                p::Ptr{Float32}, 0::Cint, tol::Float64, maxiters::Cint, u::Ptr{Float32}, resid::Ptr{Float32}, rc::Ptr{Int32},
+                iters::Ptr{Int32})::Cint
+        end
+        nkcheck(st)
+    end
+    return (; u, resid, retcode = [RETCODES[c + 1] for c in rc], iters)
+end
+
 # ------------------------------------------------------------------------------------------ AMDGPU.jl arrays (optional)
 # ext/MI355XNewtonKrylovAMDGPUExt.jl (a package extension, AMDGPU as a weak dependency): ROCArrays pass through every entry
 # point with memspace = NK_DEVICE, and device-resident Julia operators / preconditioners serve through the device-pointer
 # callback contract (nk_matvec_fn proper).
 
 export Ctx, DeviceVector, DeviceCSR, DeviceProblem, bratu2d, brusselator2d, mi355x_function, MI355XGMRES,
-    MI355XNewtonKrylovAlg, EnsembleKernel, vectorized_solve, DevicePreconditioner, DeviceILU0, DeviceILUT, DeviceAMG, DeviceJacobi, update!, update_values!
+    MI355XNewtonKrylovAlg, EnsembleKernel, LeastSquaresEnsembleKernel, SimpleGaussNewton, vectorized_solve, DevicePreconditioner, DeviceILU0, DeviceILUT, DeviceAMG, DeviceJacobi, update!, update_values!
 
 end # module

@@ -17,7 +17,8 @@ from .core import (  # noqa: F401
     AbsNormSafeTerminationMode, TERMINATION_CONDITIONS,
     NLStats, NonlinearSolution, FirstOrderCache, init, solve, step_, solve_, reinit_,
     supports_deferred_residual, refresh_residual,
-    SimpleNewtonRaphson, SimpleTrustRegion, SimpleBroyden, SimpleKlement, SimpleDFSane, ImmutableNonlinearProblem, EnsembleSolution, vectorized_solve,
+    SimpleNewtonRaphson, SimpleGaussNewton, SimpleTrustRegion, SimpleBroyden, SimpleKlement, SimpleDFSane, ImmutableNonlinearProblem,
+    ImmutableNonlinearLeastSquaresProblem, EnsembleSolution, vectorized_solve,
     GMRES, BandedLU, JacobianOperator, JacVecOperator, VecJacOperator, StatefulJacobianOperator,
     StatefulJacobianNormalFormOperator,
 )

@@ -222,6 +222,13 @@ SIGNATURES = {
     "nk_batch_solve_dfsane": (_I, [_P, _L, _P, _I, _P, _I, _D, _I, _D, _D, _D, _I, _D, _D, _D, _I, _P, _P, _P, _P]),
     "nk_batch_solve_dfsane_f32": (_I, [_P, _L, _P, _I, _P, _I, _D, _I, _D, _D, _D, _I, _D, _D, _D, _I, _P, _P, _P, _P]),
     "nk_batch_jf_code_object": (_I, [C.c_char_p, _I, _I, _I, _P, _L, C.POINTER(_L)]),
+    "nk_batch_nlls_compile_check": (_I, [C.c_char_p, _I, _I, _I, _I, C.POINTER(_L)]),
+    "nk_batch_nlls_code_object": (_I, [C.c_char_p, _I, _I, _I, _I, _P, _L, C.POINTER(_L)]),
+    "nk_batch_create_nlls": (_I, [_P, C.c_char_p, _I, _I, _I, _I, _PP]),
+    "nk_batch_solve_gauss_newton": (_I, [_P, _L, _P, _I, _P, _I, _D, _I, _P, _P, _P, _P]),
+    "nk_batch_solve_gauss_newton_f32": (_I, [_P, _L, _P, _I, _P, _I, _D, _I, _P, _P, _P, _P]),
+    "nk_batch_solve_trust_region_nlls": (_I, [_P, _L, _P, _I, _P, _I, _D, _I, _D, _D, _D, _D, _D, _I, _P, _P, _P, _P]),
+    "nk_batch_solve_trust_region_nlls_f32": (_I, [_P, _L, _P, _I, _P, _I, _D, _I, _D, _D, _D, _D, _D, _I, _P, _P, _P, _P]),
     "nk_options_default": (_I, [C.POINTER(Options)]),
     "nk_solver_init": (_I, [_P, _P, _I, C.POINTER(Options), _PP]),
     "nk_solver_destroy": (_I, [_P]),

@@ -1472,6 +1472,11 @@ class SimpleNewtonRaphson:
     name: str = "SimpleNewtonRaphson"
 
 
+# lib/SimpleNonlinearSolve/src/raphson.jl:31 — `const SimpleGaussNewton = SimpleNewtonRaphson`: the name used on least-squares
+# problems, the same algorithm object
+SimpleGaussNewton = SimpleNewtonRaphson
+
+
 @dataclass
 class SimpleTrustRegion:
     """lib/SimpleNonlinearSolve/src/trust_region.jl:44-55 (default radius update rule); None = reference default."""
@@ -1540,10 +1545,27 @@ class ImmutableNonlinearProblem:
             raise ValueError("u0 and p disagree on the number of systems")
 
 
+class ImmutableNonlinearLeastSquaresProblem(ImmutableNonlinearProblem):
+    """NonlinearLeastSquaresProblem{false}(f, u0, p) for the kernel-generation path: `resid_size` = m residuals for the n
+    unknowns of `u0`, n ≤ m ≤ 64, one problem per GPU thread (a small model fitted to each of many data sets; each fit's data
+    travels in its row of `p`). `f_source` defines `template <typename T> __device__ void nk_f(const T *u, const nk_real *p,
+    T *f)` writing m values (and, for `jac=True`, `nk_jac` writing the row-major m×n Jacobian). Solved by
+    `vectorized_solve` with SimpleGaussNewton (= SimpleNewtonRaphson) or SimpleTrustRegion; termination is ‖f‖₂ ≤ abstol, so a
+    fit whose minimum residual is not zero ends in MaxIters or ShrinkThresholdExceeded, as in the reference. (The large-system
+    class is NonlinearLeastSquaresProblem.)"""
+
+    def __init__(self, f_source: str, u0, p, resid_size: int, ctx: Optional[Context] = None, eltype=None):
+        super().__init__(f_source, u0, p, ctx, eltype)
+        self.m = int(resid_size)
+        if self.m < self.n:
+            raise ValueError(f"resid_size = {self.m} < {self.n} unknowns: the minimum-norm solution of an underdetermined "
+                             "problem is not offered")
+
+
 @dataclass
 class EnsembleSolution:
     u: object          # (nbatch, n)
-    resid: object      # (nbatch, n): residual at the last evaluated iterate (reference: `fx` returned by check_termination)
+    resid: object      # (nbatch, n), or (nbatch, m) for a least-squares problem: residual at the last evaluated iterate (reference: `fx` returned by check_termination)
     retcode: np.ndarray  # (nbatch,) strings
     iters: np.ndarray    # (nbatch,)
     retcode_raw: np.ndarray = None
@@ -1564,11 +1586,15 @@ class _BatchKernel:
     _cache: dict = {}
 
     @classmethod
-    def get(cls, ctx, source, n, nparams, flags):
-        key = (id(ctx), source, n, nparams, flags)
+    def get(cls, ctx, source, n, nparams, flags, m=None):
+        """m = None: a square ensemble (nk_batch_create); else a least-squares one with m residuals (nk_batch_create_nlls)"""
+        key = (id(ctx), source, n, nparams, flags, m)
         if key not in cls._cache:
             h = C.c_void_p()
-            check(L.lib().nk_batch_create(ctx._h, source.encode(), n, nparams, flags, C.byref(h)))
+            if m is None:
+                check(L.lib().nk_batch_create(ctx._h, source.encode(), n, nparams, flags, C.byref(h)))
+            else:
+                check(L.lib().nk_batch_create_nlls(ctx._h, source.encode(), n, m, nparams, flags, C.byref(h)))
             cls._cache[key] = h
         return cls._cache[key]
 
@@ -1577,24 +1603,31 @@ def vectorized_solve(prob: ImmutableNonlinearProblem, alg=None, abstol=None, max
     """`vectorized_solve(prob, alg; backend = ROCBackend())` of the tutorial (nonlinear_solve_gpus.md:106-114): solve
     every parameter set with SimpleNewtonRaphson, one system per GPU thread, in one kernel launch. The problem's eltype
     picks the precision (Float64 unless it was built with eltype=float32). `alg` may also be SimpleTrustRegion or one of the
-    Jacobian-free SimpleBroyden, SimpleKlement, SimpleDFSane (their kernels are compiled on first use)."""
+    Jacobian-free SimpleBroyden, SimpleKlement, SimpleDFSane (their kernels are compiled on first use). On an
+    ImmutableNonlinearLeastSquaresProblem `alg` is SimpleGaussNewton (= SimpleNewtonRaphson) or SimpleTrustRegion, and
+    `resid` has shape (nbatch, m)."""
     alg = alg or SimpleNewtonRaphson()
+    nlls = isinstance(prob, ImmutableNonlinearLeastSquaresProblem)
+    if nlls and not isinstance(alg, (SimpleNewtonRaphson, SimpleTrustRegion)):
+        raise TypeError(f"{getattr(alg, 'name', type(alg).__name__)} is not defined on a least-squares problem (nor is it in "
+                        "the reference): use SimpleGaussNewton or SimpleTrustRegion")
     if isinstance(alg, SimpleBroyden) and alg.alpha is not None and not alg.alpha > 0:
         raise ValueError(f"SimpleBroyden: alpha = {alg.alpha} must be positive (or None)")
     if isinstance(alg, SimpleDFSane) and not (1 <= int(alg.M) <= 32 and int(alg.n_exp) in (1, 2)):
         raise ValueError(f"SimpleDFSane: M = {alg.M} must lie in 1..32 and n_exp = {alg.n_exp} must be 1 or 2")
     f32 = prob.float32
     flags = (L.BATCH_ANALYTIC_JAC if getattr(alg, "jac", False) else 0) | (L.BATCH_FLOAT32 if f32 else 0)
-    h = _BatchKernel.get(prob.ctx, prob.f_source, prob.n, prob.nparams, flags)
+    h = _BatchKernel.get(prob.ctx, prob.f_source, prob.n, prob.nparams, flags, prob.m if nlls else None)
     on_dev = _is_torch(prob.p) and prob.p.is_cuda
     nb, n = prob.nbatch, prob.n
+    nr = prob.m if nlls else n
     if on_dev:
         tdt = torch.float32 if f32 else torch.float64
         u0 = prob.u0 if (_is_torch(prob.u0) and prob.u0.is_cuda) else torch.as_tensor(np.asarray(prob.u0), device=prob.p.device)
         u0 = u0.to(tdt).contiguous()
         pp = prob.p.to(tdt).contiguous()
         u = torch.empty((nb, n), dtype=tdt, device=pp.device)
-        r = torch.empty_like(u)
+        r = torch.empty((nb, nr), dtype=tdt, device=pp.device)
         rc = torch.empty(nb, dtype=torch.int32, device=pp.device)
         it = torch.empty(nb, dtype=torch.int32, device=pp.device)
         ptr = lambda x: C.c_void_p(x.data_ptr())
@@ -1603,13 +1636,13 @@ def vectorized_solve(prob: ImmutableNonlinearProblem, alg=None, abstol=None, max
         ndt = np.float32 if f32 else np.float64
         u0 = np.ascontiguousarray(np.asarray(prob.u0.cpu() if _is_torch(prob.u0) else prob.u0), dtype=ndt)
         pp = np.ascontiguousarray(np.asarray(prob.p.cpu() if _is_torch(prob.p) else prob.p), dtype=ndt)
-        u, r = np.empty((nb, n), dtype=ndt), np.empty((nb, n), dtype=ndt)
+        u, r = np.empty((nb, n), dtype=ndt), np.empty((nb, nr), dtype=ndt)
         rc, it = np.empty(nb, dtype=np.int32), np.empty(nb, dtype=np.int32)
         ptr = lambda x: C.c_void_p(x.ctypes.data)
         ms = L.HOST
     if isinstance(alg, SimpleTrustRegion):
         d = lambda v: -1.0 if v is None else float(v)
-        solve_tr = L.lib().nk_batch_solve_trust_region_f32 if f32 else L.lib().nk_batch_solve_trust_region
+        solve_tr = getattr(L.lib(), "nk_batch_solve_trust_region" + ("_nlls" if nlls else "") + ("_f32" if f32 else ""))
         check(solve_tr(h, nb, ptr(u0), 1 if prob.u0_per_system else 0, ptr(pp), ms,
                        0.0 if abstol is None else float(abstol), int(maxiters),
                        d(alg.step_threshold), d(alg.shrink_threshold), d(alg.expand_threshold),
@@ -1630,7 +1663,7 @@ def vectorized_solve(prob: ImmutableNonlinearProblem, alg=None, abstol=None, max
                 *head, float(alg.sigma_min), float(alg.sigma_max), float(alg.sigma_1), int(alg.M), float(alg.gamma),
                 float(alg.tau_min), float(alg.tau_max), int(alg.n_exp), *outs))
     else:
-        solve = L.lib().nk_batch_solve_f32 if f32 else L.lib().nk_batch_solve
+        solve = getattr(L.lib(), ("nk_batch_solve_gauss_newton" if nlls else "nk_batch_solve") + ("_f32" if f32 else ""))
         check(solve(h, nb, ptr(u0), 1 if prob.u0_per_system else 0, ptr(pp), ms,
                     0.0 if abstol is None else float(abstol), int(maxiters), ptr(u), ptr(r), ptr(rc), ptr(it)))
     rch = rc.cpu().numpy() if on_dev else rc

@@ -620,6 +620,304 @@ nk_batch_dfsane(long nbatch, const nk_real *__restrict__ u0, int u0_per_system, 
 }
 )NKSRC";
 
+// ----------------------------------------------------------------------------- nonlinear least squares, one problem per thread
+// m residuals, n unknowns, m ≥ n (-DNK_M, -DNK_N): SimpleGaussNewton = SimpleNewtonRaphson on a NonlinearLeastSquaresProblem
+// (raphson.jl:31, 41-82) and SimpleTrustRegion on one (trust_region.jl:60-229, default update rule). A kernel set and an object
+// kind of their own (nk_batch_create_nlls); the square kernels above are not touched. What differs from them:
+//  * J is m×n. One dual-number sweep with NK_CH = n partials returns all of it while n ≤ 8 (chunks of 8 above).
+//  * `J \ f` is the least-squares solution by Householder QR with column pivoting — what `\` does for a non-square dense
+//    matrix in the reference's language — in place on J: the reflector vectors stay below the diagonal, Q is never formed.
+//    No normal equations in the Newton step. Divergence from the reference, which leaves rank deficiency to LAPACK's rank
+//    truncation: here a column whose pivot has |r_kk| ≤ m·eps·|r_11| gets a zero step component (the basic solution).
+//    The column norms are recomputed at every step (no downdating) and taken without scaling: entries beyond
+//    sqrt(floatmax) overflow them.
+//  * termination is AbsNormTerminationMode(Base.Fix2(norm, 2)), the :simple default for a NonlinearLeastSquaresProblem
+//    (termination_conditions.jl:381-383): ‖f‖₂ ≤ abstol; NaN ≤ abstol is false. A fit whose minimum residual is not zero
+//    therefore never reports Success.
+//  * the trust region keeps H = JᵀJ (n×n) and g = Jᵀf, formed before the factorisation overwrites J, and takes Hδ from H
+//    as trust_region.jl:151 does. As there, a rejected trial point leaves its residual in fx, and the next dogleg solves
+//    with the unchanged factorisation against that residual.
+// While n ≤ 8 and m·(n + 2) ≤ NK_NLLS_REG_LIMIT every index is a compile-time constant (column exchange by selects) and J lives in
+// registers; above that the arrays go to scratch. p is copied into a private array while nparams ≤ 32 and read in place
+// beyond (a fit's data travels in p: 2m values for (x_i, y_i) pairs). One problem per thread only: a per-wavefront form would
+// need a per-residual user function, a second source contract.
+static const char *k_kernel_nlls = R"NKSRC(
+// register-resident shapes: n ≤ 8 and m·(n + 2) ≤ 80 (Float64) or 128 (Float32) — J, the duals of the sweep and the
+// residual copies make about m·(2n + 3) live values. Found with the compiler's resource notes (no private segment for either
+// kernel at the largest m of every n); not timed.
+#ifndef NK_NLLS_REG_LIMIT
+#ifdef NK_F32
+#define NK_NLLS_REG_LIMIT 128
+#else
+#define NK_NLLS_REG_LIMIT 80
+#endif
+#endif
+#if NK_N <= 8 && NK_M * (NK_N + 2) <= NK_NLLS_REG_LIMIT
+#define NK_REGS 1
+#define NK_UNROLL _Pragma("unroll")
+#else
+#define NK_UNROLL _Pragma("nounroll")
+#endif
+#ifdef NK_F32
+#define NK_EPS 1.1920929e-7f
+#else
+#define NK_EPS 2.220446049250313e-16
+#endif
+#if NK_NP <= 32
+#define NK_P_DECL nk_real pp[NK_NP > 0 ? NK_NP : 1]; NK_UNROLL for (int i = 0; i < NK_NP; ++i) pp[i] = p[b * NK_NP + i];
+#else
+#define NK_P_DECL const nk_real *pp = p + b * NK_NP;   // read in place: a private copy of this size would spill
+#endif
+
+__device__ inline nk_real nk_norm2_n(const nk_real *v) {
+  nk_real s = NK_R(0);
+  NK_UNROLL for (int i = 0; i < NK_N; ++i) s += v[i] * v[i];
+  return sqrt(s);
+}
+__device__ inline nk_real nk_norm2_m(const nk_real *v) {
+  nk_real s = NK_R(0);
+  NK_UNROLL for (int i = 0; i < NK_M; ++i) s += v[i] * v[i];
+  return sqrt(s);
+}
+// the residual; entries the source does not write (one written for n outputs, built with m > n) are zero
+__device__ inline void nk_resid(const nk_real *x, const nk_real *p, nk_real *f) {
+  NK_UNROLL for (int i = 0; i < NK_M; ++i) f[i] = NK_R(0);
+  nk_f<nk_real>(x, p, f);
+}
+__device__ inline void nk_jacobian(const nk_real *x, const nk_real *p, nk_real (*J)[NK_N]) {
+#ifdef NK_HAS_JAC
+  nk_jac(x, p, &J[0][0]);  // user-supplied analytic Jacobian, row-major M×N (SciMLBase.has_jac, utils.jl:98-99)
+#else
+  // AutoForwardDiff: NK_CH directions per sweep of the residual on dual numbers (all of J in one sweep while N ≤ 8)
+  NK_UNROLL for (int c0 = 0; c0 < NK_N; c0 += NK_CH) {
+    Dual xd[NK_N], fd[NK_M];
+    NK_UNROLL for (int i = 0; i < NK_N; ++i) {
+      xd[i].v = x[i];
+      NK_DUAL_LOOP xd[i].d[k] = (i == c0 + k) ? NK_R(1) : NK_R(0);
+    }
+    NK_UNROLL for (int i = 0; i < NK_M; ++i) fd[i] = Dual(NK_R(0));
+    nk_f<Dual>(xd, p, fd);
+    NK_UNROLL for (int i = 0; i < NK_M; ++i) {
+      NK_DUAL_LOOP if (c0 + k < NK_N) J[i][c0 + k] = fd[i].d[k];
+    }
+  }
+#endif
+}
+
+// Householder QR with column pivoting, in place. On return the upper triangle of J holds R, the part below the diagonal
+// the reflector vectors (v_kk = 1 implied), H_k = I − tau_k v vᵀ, and piv[k] the column exchanged with column k at step k.
+__device__ inline void nk_qr_factor(nk_real (*J)[NK_N], nk_real *tau, int *piv) {
+  NK_UNROLL for (int k = 0; k < NK_N; ++k) {
+    // the remaining column of largest 2-norm over rows k..M-1; the first one on ties, and a NaN norm never displaces column k
+    int pv = k;
+    nk_real best = NK_R(0);
+    NK_UNROLL for (int j = k; j < NK_N; ++j) {
+      nk_real s = NK_R(0);
+      NK_UNROLL for (int i = k; i < NK_M; ++i) s += J[i][j] * J[i][j];
+      if (j == k) best = s;
+      else if (s > best) { best = s; pv = j; }
+    }
+    piv[k] = pv;
+#ifdef NK_REGS
+    // column exchange by selects, so that every index stays a compile-time constant and the matrix lives in registers
+    NK_UNROLL for (int j = k + 1; j < NK_N; ++j) {
+      const bool s = (j == pv);
+      NK_UNROLL for (int i = 0; i < NK_M; ++i) {
+        const nk_real t1 = J[i][k], t2 = J[i][j];
+        J[i][k] = s ? t2 : t1;
+        J[i][j] = s ? t1 : t2;
+      }
+    }
+#else
+    if (pv != k) {
+      for (int i = 0; i < NK_M; ++i) { const nk_real t = J[i][k]; J[i][k] = J[i][pv]; J[i][pv] = t; }
+    }
+#endif
+    // reflector: beta = −sign(alpha)·‖x‖, tau = (beta − alpha)/beta, v = x/(alpha − beta) below the diagonal; a zero column
+    // gives tau = 0 (H = I)
+    const nk_real alpha = J[k][k];
+    const nk_real nrm = sqrt(best);
+    const bool z = (nrm == NK_R(0));
+    const nk_real beta = alpha >= NK_R(0) ? -nrm : nrm;
+    const nk_real t = z ? NK_R(0) : (beta - alpha) / beta;
+    const nk_real sc = z ? NK_R(0) : NK_R(1) / (alpha - beta);
+    tau[k] = t;
+    J[k][k] = beta;
+    NK_UNROLL for (int i = k + 1; i < NK_M; ++i) J[i][k] *= sc;
+    NK_UNROLL for (int j = k + 1; j < NK_N; ++j) {
+      nk_real w = J[k][j];
+      NK_UNROLL for (int i = k + 1; i < NK_M; ++i) w += J[i][k] * J[i][j];
+      w *= t;
+      J[k][j] -= w;
+      NK_UNROLL for (int i = k + 1; i < NK_M; ++i) J[i][j] -= J[i][k] * w;
+    }
+  }
+}
+// dx = argmin ‖J dx − c‖₂ from the factorisation: c ← Qᵀc (destroyed), back substitution with R, columns below the rank
+// threshold get 0, then the column exchanges are undone in reverse order
+__device__ inline void nk_qr_solve(const nk_real (*J)[NK_N], const nk_real *tau, const int *piv, nk_real *c, nk_real *dx) {
+  NK_UNROLL for (int k = 0; k < NK_N; ++k) {
+    nk_real w = c[k];
+    NK_UNROLL for (int i = k + 1; i < NK_M; ++i) w += J[i][k] * c[i];
+    w *= tau[k];
+    c[k] -= w;
+    NK_UNROLL for (int i = k + 1; i < NK_M; ++i) c[i] -= J[i][k] * w;
+  }
+  const nk_real thr = (NK_R(NK_M) * NK_R(NK_EPS)) * fabs(J[0][0]);   // max(m, n)·eps·|r_11|
+  NK_UNROLL for (int k = NK_N - 1; k >= 0; --k) {
+    nk_real s = c[k];
+    NK_UNROLL for (int j = k + 1; j < NK_N; ++j) s -= J[k][j] * dx[j];
+    dx[k] = fabs(J[k][k]) <= thr ? NK_R(0) : s / J[k][k];
+  }
+  NK_UNROLL for (int k = NK_N - 1; k >= 0; --k) {
+#ifdef NK_REGS
+    NK_UNROLL for (int j = k + 1; j < NK_N; ++j) {
+      const bool s = (j == piv[k]);
+      const nk_real t1 = dx[k], t2 = dx[j];
+      dx[k] = s ? t2 : t1;
+      dx[j] = s ? t1 : t2;
+    }
+#else
+    const int pv = piv[k];
+    if (pv != k) { const nk_real t = dx[k]; dx[k] = dx[pv]; dx[pv] = t; }
+#endif
+  }
+}
+
+// ---- SimpleGaussNewton (raphson.jl:52-81 on a NonlinearLeastSquaresProblem)
+extern "C" __global__ void __launch_bounds__(NK_BLOCK_T)
+nk_batch_gauss_newton(long nbatch, const nk_real *__restrict__ u0, int u0_per_system, const nk_real *__restrict__ p, nk_real abstol,
+                      int maxiters, nk_real *__restrict__ u_out, nk_real *__restrict__ r_out, int *__restrict__ retcode,
+                      int *__restrict__ iters) {
+  const long b = (long)blockIdx.x * NK_BLOCK_T + threadIdx.x;
+  if (b >= nbatch) return;
+  nk_real x[NK_N], fx[NK_M], dx[NK_N], c[NK_M], tau[NK_N];
+  int piv[NK_N];
+  NK_UNROLL for (int i = 0; i < NK_N; ++i) x[i] = u0[(u0_per_system ? b * NK_N : 0) + i];
+  NK_P_DECL
+  nk_resid(x, pp, fx);
+  bool allzero = true;
+  NK_UNROLL for (int i = 0; i < NK_M; ++i) allzero = allzero && (fx[i] == NK_R(0));
+  int rc = 2 /* MaxIters */, it = 0;
+  if (allzero) {
+    rc = 1;  // Success (raphson.jl:55-56)
+  } else {
+    nk_real J[NK_M][NK_N];
+    nk_jacobian(x, pp, J);
+    for (it = 1; it <= maxiters; ++it) {
+      NK_UNROLL for (int i = 0; i < NK_M; ++i) c[i] = fx[i];
+      nk_qr_factor(J, tau, piv);       // δx = J \ fx (raphson.jl:71)
+      nk_qr_solve(J, tau, piv, c, dx);
+      NK_UNROLL for (int i = 0; i < NK_N; ++i) x[i] -= dx[i];
+      // ‖fx‖₂ ≤ abstol on the residual of the PREVIOUS iterate (check_termination precedes evaluate_f!!, raphson.jl:74-77)
+      if (nk_norm2_m(fx) <= abstol) { rc = 1; break; }
+      nk_resid(x, pp, fx);
+      nk_jacobian(x, pp, J);
+    }
+    if (it > maxiters) it = maxiters;
+  }
+  NK_UNROLL for (int i = 0; i < NK_N; ++i) u_out[b * NK_N + i] = x[i];
+  NK_UNROLL for (int i = 0; i < NK_M; ++i) r_out[b * NK_M + i] = fx[i];
+  retcode[b] = rc;
+  iters[b] = it;
+}
+
+// ---- SimpleTrustRegion (trust_region.jl:60-229, default update rule) on m residuals
+// H = JᵀJ and g = Jᵀf from the unfactored J (trust_region.jl:126-127, 185-186), then J is factored for the dogleg's Newton step
+__device__ inline void nk_normal_forms(const nk_real (*J)[NK_N], const nk_real *fx, nk_real (*H)[NK_N], nk_real *g) {
+  NK_UNROLL for (int i = 0; i < NK_N; ++i) {
+    NK_UNROLL for (int j = 0; j < NK_N; ++j) {
+      nk_real s = NK_R(0);
+      NK_UNROLL for (int k = 0; k < NK_M; ++k) s += J[k][i] * J[k][j];
+      H[i][j] = s;
+    }
+    nk_real s = NK_R(0);
+    NK_UNROLL for (int k = 0; k < NK_M; ++k) s += J[k][i] * fx[k];
+    g[i] = s;
+  }
+}
+extern "C" __global__ void __launch_bounds__(NK_BLOCK_T)
+nk_batch_trust_region_nlls(long nbatch, const nk_real *__restrict__ u0, int u0_per_system, const nk_real *__restrict__ p,
+                           nk_real abstol, int maxiters, nk_real eta1, nk_real eta2, nk_real eta3, nk_real t1, nk_real t2,
+                           int max_shrink, nk_real *__restrict__ u_out, nk_real *__restrict__ r_out, int *__restrict__ retcode,
+                           int *__restrict__ iters) {
+  const long b = (long)blockIdx.x * NK_BLOCK_T + threadIdx.x;
+  if (b >= nbatch) return;
+  nk_real x[NK_N], xo[NK_N], fx[NK_M], c[NK_M], g[NK_N], dl[NK_N], dN[NK_N], dsd[NK_N], tau[NK_N];
+  nk_real J[NK_M][NK_N], H[NK_N][NK_N];
+  int piv[NK_N];
+  NK_UNROLL for (int i = 0; i < NK_N; ++i) { x[i] = u0[(u0_per_system ? b * NK_N : 0) + i]; xo[i] = x[i]; }
+  NK_P_DECL
+  nk_resid(x, pp, fx);
+  const nk_real norm_fx = nk_norm2_m(fx);
+  nk_jacobian(x, pp, J);
+  nk_real xmax = x[0], xmin = x[0];
+  NK_UNROLL for (int i = 1; i < NK_N; ++i) { xmax = x[i] > xmax ? x[i] : xmax; xmin = x[i] < xmin ? x[i] : xmin; }
+  const nk_real dmax = norm_fx > xmax - xmin ? norm_fx : xmax - xmin;   // trust_region.jl:115
+  nk_real delta = dmax / NK_R(11);
+  nk_real fk = NK_R(0.5) * norm_fx * norm_fx;
+  nk_normal_forms(J, fx, H, g);
+  nk_qr_factor(J, tau, piv);
+  int shrink = 0, rc = 2, it = 0;
+  if (norm_fx <= abstol) rc = 1;   // the check before the loop (trust_region.jl:136-139); no iszero shortcut
+  else {
+    for (it = 1; it <= maxiters; ++it) {
+      // dogleg (trust_region.jl:201-229): δN = −(J \ fx)
+      NK_UNROLL for (int i = 0; i < NK_M; ++i) c[i] = fx[i];
+      nk_qr_solve(J, tau, piv, c, dN);
+      NK_UNROLL for (int i = 0; i < NK_N; ++i) dN[i] = -dN[i];
+      if (nk_norm2_n(dN) <= delta) {
+        NK_UNROLL for (int i = 0; i < NK_N; ++i) dl[i] = dN[i];
+      } else {
+        NK_UNROLL for (int i = 0; i < NK_N; ++i) dsd[i] = -g[i];
+        const nk_real nsd = nk_norm2_n(dsd);
+        if (nsd >= delta) {
+          NK_UNROLL for (int i = 0; i < NK_N; ++i) dl[i] = dsd[i] * (delta / nsd);
+        } else {
+          nk_real dNN = NK_R(0), dSN = NK_R(0), dSS = NK_R(0);
+          NK_UNROLL for (int i = 0; i < NK_N; ++i) { const nk_real q = dN[i] - dsd[i]; dNN += q * q; dSN += dsd[i] * q; dSS += dsd[i] * dsd[i]; }
+          const nk_real fact = dSN * dSN - dNN * (dSS - delta * delta);
+          const nk_real tu = (-dSN + sqrt(fact)) / dNN;
+          NK_UNROLL for (int i = 0; i < NK_N; ++i) dl[i] = dsd[i] + tu * (dN[i] - dsd[i]);
+        }
+      }
+      NK_UNROLL for (int i = 0; i < NK_N; ++i) x[i] = xo[i] + dl[i];
+      nk_resid(x, pp, fx);
+      const nk_real nf = nk_norm2_m(fx);
+      const nk_real fk1 = nf * nf / NK_R(2);
+      // r = (f_{k+1} − f_k)/(δ·g + δ·Hδ/2) (trust_region.jl:151-152)
+      nk_real dg = NK_R(0), dHd = NK_R(0);
+      NK_UNROLL for (int i = 0; i < NK_N; ++i) {
+        nk_real s = NK_R(0);
+        NK_UNROLL for (int k = 0; k < NK_N; ++k) s += H[i][k] * dl[k];
+        dHd += dl[i] * s;
+        dg += dl[i] * g[i];
+      }
+      const nk_real r = (fk1 - fk) / (dg + dHd / NK_R(2));
+      if (r >= eta2) shrink = 0;
+      else {
+        delta = t1 * delta;
+        if (++shrink > max_shrink) { rc = 6; break; }   // ShrinkThresholdExceeded
+      }
+      if (r >= eta1) {
+        if (nf <= abstol) { rc = 1; break; }
+        NK_UNROLL for (int i = 0; i < NK_N; ++i) xo[i] = x[i];
+        nk_jacobian(x, pp, J);
+        if (r > eta3) delta = t2 * delta < dmax ? t2 * delta : dmax;
+        fk = fk1;
+        nk_normal_forms(J, fx, H, g);
+        nk_qr_factor(J, tau, piv);
+      }
+    }
+    if (it > maxiters) it = maxiters;
+  }
+  NK_UNROLL for (int i = 0; i < NK_N; ++i) u_out[b * NK_N + i] = x[i];
+  NK_UNROLL for (int i = 0; i < NK_M; ++i) r_out[b * NK_M + i] = fx[i];
+  retcode[b] = rc;
+  iters[b] = it;
+}
+)NKSRC";
+
 // ----------------------------------------------------------------------------- hiprtc through dlopen
 typedef void *rtc_program;
 static struct {
@@ -658,6 +956,8 @@ static int rtc_load() {
 struct nk_batch {
   nk_ctx *ctx = nullptr;
   int n = 0, np = 0, block = 64;
+  int m = 0;  // residuals of a least-squares object (nk_batch_create_nlls: mod holds the NLLS kernel set); 0 = a square object
+  hipFunction_t fn_gn = nullptr, fn_tr_nlls = nullptr;
   hipModule_t mod = nullptr, mod_wave = nullptr;
   hipFunction_t fn = nullptr, fn_tr = nullptr, fn_wave = nullptr;  // fn_wave: one system per wavefront (8 < n ≤ 64)
   // the Jacobian-free kernels: a module of their own, compiled on the first call that needs it (from source / flags)
@@ -674,18 +974,24 @@ struct nk_batch {
 
 // the kernel sets, one hiprtc program each
 enum { KSET_NEWTON = 0 /* nk_batch_newton + nk_batch_trust_region */, KSET_WAVE = 1 /* nk_batch_newton_wave */,
-       KSET_JF = 2 /* nk_batch_broyden + nk_batch_klement + nk_batch_dfsane */ };
+       KSET_JF = 2 /* nk_batch_broyden + nk_batch_klement + nk_batch_dfsane */,
+       KSET_NLLS = 3 /* nk_batch_gauss_newton + nk_batch_trust_region_nlls (m residuals, -DNK_M) */ };
 
-// compile `source` (+ prelude + solver kernels) for n unknowns / np parameters; code object into `code`, log into `log`
+// compile `source` (+ prelude + solver kernels) for n unknowns / np parameters (and, for KSET_NLLS, m residuals); code
+// object into `code`, log into `log`
 static int batch_compile(const char *source, int n, int np, int flags, std::vector<char> *code, std::string *log,
-                         int kset = KSET_NEWTON) {
-  const bool wave = kset == KSET_WAVE;
+                         int kset = KSET_NEWTON, int m = 0) {
+  const bool wave = kset == KSET_WAVE, nlls = kset == KSET_NLLS;
   NK_REQUIRE(source, "NULL source");
   NK_REQUIRE(n >= 1 && n <= 64, "n = %d outside 1..64 (one system per thread)", n);
+  NK_REQUIRE(!nlls || (m >= n && m <= 64),
+             "m = %d residuals for n = %d unknowns: a least-squares ensemble needs n <= m <= 64 (the contract is `template "
+             "<typename T> __device__ void nk_f(const T *u, const nk_real *p, T *f)` with u: n values, f: m values; the "
+             "minimum-norm solution of an underdetermined problem is not offered)", m, n);
   NK_REQUIRE(np >= 0 && np <= 256, "nparams = %d outside 0..256", np);
   NK_TRY(rtc_load());
   std::string full = std::string(k_prelude) + "\n// ---- user source\n" + source + "\n" +
-                     (wave ? k_kernel_wave : kset == KSET_JF ? k_kernel_jf : k_kernel);
+                     (wave ? k_kernel_wave : kset == KSET_JF ? k_kernel_jf : nlls ? k_kernel_nlls : k_kernel);
   rtc_program prog = nullptr;
   if (RTC.Create(&prog, full.c_str(), "nk_batch_user.hip", 0, nullptr, nullptr) != 0) NK_FAIL(NK_E_HIP, "hiprtcCreateProgram failed");
   // dual-number partials per residual sweep (wave kernel: one per lane; the Jacobian-free kernels sweep no duals)
@@ -694,7 +1000,9 @@ static int batch_compile(const char *source, int n, int np, int flags, std::vect
                     db = wave ? "-DNK_BLOCK_T=256" : "-DNK_BLOCK_T=64";
   std::vector<const char *> opts = {"--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-std=c++17", dn.c_str(), dp.c_str(), dc.c_str(),
                                     db.c_str()};
-  if ((flags & NK_BATCH_ANALYTIC_JAC) && kset == KSET_NEWTON) opts.push_back("-DNK_HAS_JAC=1");
+  const std::string dm = "-DNK_M=" + std::to_string(m);
+  if (nlls) opts.push_back(dm.c_str());
+  if ((flags & NK_BATCH_ANALYTIC_JAC) && (kset == KSET_NEWTON || nlls)) opts.push_back("-DNK_HAS_JAC=1");
   if (flags & NK_BATCH_FLOAT32) opts.push_back("-DNK_F32=1");
   const int rc = RTC.Compile(prog, (int)opts.size(), opts.data());
   size_t ls = 0;
@@ -761,6 +1069,53 @@ extern "C" int nk_batch_jf_code_object(const char *source, int n, int nparams, i
   return NK_OK;
 }
 
+// ---- least squares: compile check, code object and object creation for the NLLS kernel set
+extern "C" int nk_batch_nlls_compile_check(const char *source, int n, int m, int nparams, int flags, int64_t *code_bytes) {
+  std::vector<char> code;
+  std::string log;
+  NK_TRY(batch_compile(source, n, nparams, flags, &code, &log, KSET_NLLS, m));
+  if (code_bytes) *code_bytes = (int64_t)code.size();
+  return NK_OK;
+}
+
+extern "C" int nk_batch_nlls_code_object(const char *source, int n, int m, int nparams, int flags, void *buf, int64_t capacity,
+                                         int64_t *bytes) {
+  NK_REQUIRE(bytes, "NULL argument");
+  std::vector<char> code;
+  std::string log;
+  NK_TRY(batch_compile(source, n, nparams, flags, &code, &log, KSET_NLLS, m));
+  *bytes = (int64_t)code.size();
+  if (!buf) return NK_OK;
+  NK_REQUIRE(capacity >= *bytes, "buffer of %lld bytes, the code object has %lld", (long long)capacity, (long long)*bytes);
+  memcpy(buf, code.data(), code.size());
+  return NK_OK;
+}
+
+extern "C" int nk_batch_create_nlls(nk_ctx *ctx, const char *source, int n, int m, int nparams, int flags, nk_batch **out) {
+  NK_REQUIRE(ctx && out, "NULL argument");
+  NK_HIP(hipSetDevice(ctx->device));
+  std::vector<char> code;
+  std::string log;
+  NK_TRY(batch_compile(source, n, nparams, flags, &code, &log, KSET_NLLS, m));
+  nk_batch *B = new nk_batch();
+  B->ctx = ctx;
+  B->n = n;
+  B->m = m;
+  B->np = nparams;
+  B->f32 = (flags & NK_BATCH_FLOAT32) != 0;
+  B->source = source;
+  B->flags = flags;
+  if (hipModuleLoadData(&B->mod, code.data()) != hipSuccess) { delete B; NK_FAIL(NK_E_HIP, "hipModuleLoadData failed"); }
+  if (hipModuleGetFunction(&B->fn_gn, B->mod, "nk_batch_gauss_newton") != hipSuccess ||
+      hipModuleGetFunction(&B->fn_tr_nlls, B->mod, "nk_batch_trust_region_nlls") != hipSuccess) {
+    hipModuleUnload(B->mod);
+    delete B;
+    NK_FAIL(NK_E_HIP, "a least-squares kernel is missing from the compiled module");
+  }
+  *out = B;
+  return NK_OK;
+}
+
 extern "C" int nk_batch_create(nk_ctx *ctx, const char *source, int n, int nparams, int flags, nk_batch **out) {
   NK_REQUIRE(ctx && out, "NULL argument");
   NK_HIP(hipSetDevice(ctx->device));
@@ -812,7 +1167,9 @@ extern "C" int nk_batch_destroy(nk_batch *B) {
 // prm holds the method's parameters, defaults applied (reals and integers alike as double):
 //   BATCH_TRUST_REGION {η₁, η₂, η₃, t₁, t₂, max_shrink_times}; BATCH_BROYDEN {1/alpha, or 0 for `nothing`};
 //   BATCH_DFSANE {σ_min, σ_max, σ₁, M, γ, τ_min, τ_max, n_exp}; nothing for BATCH_NEWTON and BATCH_KLEMENT.
-enum { BATCH_NEWTON, BATCH_TRUST_REGION, BATCH_BROYDEN, BATCH_KLEMENT, BATCH_DFSANE };
+//   BATCH_TR_NLLS as BATCH_TRUST_REGION; nothing for BATCH_GAUSS_NEWTON. The last two run on a least-squares object
+//   (nk_batch_create_nlls) only, the others on a square one only; resid_out is nbatch×m there.
+enum { BATCH_NEWTON, BATCH_TRUST_REGION, BATCH_BROYDEN, BATCH_KLEMENT, BATCH_DFSANE, BATCH_GAUSS_NEWTON, BATCH_TR_NLLS };
 
 // the Jacobian-free module, compiled and loaded on the first call that needs it, then kept on the object
 static int batch_load_jf(nk_batch *B) {
@@ -841,15 +1198,20 @@ static int batch_run(nk_batch *B, bool f32, int method, int64_t nbatch, const vo
   NK_REQUIRE(B && u0 && u_out && resid_out, "NULL argument");
   NK_REQUIRE(B->f32 == f32, B->f32 ? "this ensemble was compiled for Float32 (NK_BATCH_FLOAT32): call the _f32 entry points"
                                    : "this ensemble was compiled for Float64: the _f32 entry points need NK_BATCH_FLOAT32");
+  NK_REQUIRE((method >= BATCH_GAUSS_NEWTON) == (B->m > 0),
+             B->m > 0 ? "this is a least-squares ensemble (nk_batch_create_nlls): call nk_batch_solve_gauss_newton or "
+                        "nk_batch_solve_trust_region_nlls"
+                      : "this is a square ensemble (nk_batch_create): the least-squares entry points need nk_batch_create_nlls");
   NK_REQUIRE(nbatch >= 0, "negative batch size");
   NK_REQUIRE(B->np == 0 || p, "parameters are required (nparams = %d)", B->np);
   NK_REQUIRE(method != BATCH_TRUST_REGION || B->fn_tr, "the compiled module lacks the trust-region kernel");
   nk_ctx *ctx = B->ctx;
   NK_HIP(hipSetDevice(ctx->device));
   if (nbatch == 0) return NK_OK;
-  if (method >= BATCH_BROYDEN) NK_TRY(batch_load_jf(B));
+  if (method >= BATCH_BROYDEN && method <= BATCH_DFSANE) NK_TRY(batch_load_jf(B));
   if (maxiters <= 0) maxiters = 1000;                             // raphson.jl:42 / trust_region.jl:60 / broyden.jl:33 / ...
   const int n = B->n, np = B->np;
+  const int nr = B->m > 0 ? B->m : n;   // residuals per system
   const size_t es = f32 ? sizeof(float) : sizeof(double);
   if (B->cap < nbatch) {
     hipFree(B->d_u0); hipFree(B->d_p); hipFree(B->d_u); hipFree(B->d_r); hipFree(B->d_rc); hipFree(B->d_it);
@@ -858,7 +1220,7 @@ static int batch_run(nk_batch *B, bool f32, int method, int64_t nbatch, const vo
     NK_TRY(nk_dev_alloc(&B->d_u0, (size_t)nbatch * n));
     NK_TRY(nk_dev_alloc(&B->d_p, (size_t)nbatch * (np > 0 ? np : 1)));
     NK_TRY(nk_dev_alloc(&B->d_u, (size_t)nbatch * n));
-    NK_TRY(nk_dev_alloc(&B->d_r, (size_t)nbatch * n));
+    NK_TRY(nk_dev_alloc(&B->d_r, (size_t)nbatch * nr));
     NK_TRY(nk_dev_alloc(&B->d_rc, (size_t)nbatch));
     NK_TRY(nk_dev_alloc(&B->d_it, (size_t)nbatch));
     B->cap = nbatch;
@@ -879,7 +1241,7 @@ static int batch_run(nk_batch *B, bool f32, int method, int64_t nbatch, const vo
   int *drc = B->d_rc, *dit = B->d_it;
   // the kernels' real scalars: abstol, then the method's parameters; the defaults are the element type's
   // (common_defaults.jl:39-53: eps(T)^(4/5), taken in T)
-  const int nprm = method == BATCH_TRUST_REGION ? 6 : method == BATCH_BROYDEN ? 1 : method == BATCH_DFSANE ? 8 : 0;
+  const int nprm = method == BATCH_TRUST_REGION || method == BATCH_TR_NLLS ? 6 : method == BATCH_BROYDEN ? 1 : method == BATCH_DFSANE ? 8 : 0;
   double sd[9];
   float sf[9];
   sd[0] = abstol > 0.0 ? abstol : pow(2.220446049250313e-16, 0.8);
@@ -904,6 +1266,15 @@ static int batch_run(nk_batch *B, bool f32, int method, int64_t nbatch, const vo
     void *args[] = {&nb, &du0, &ups, &dp, sa[0], &maxiters, sa[1], sa[2], sa[3], sa[4], sa[5], &ms, &du, &dr, &drc, &dit};
     st = hipModuleLaunchKernel(B->fn_tr, grid, 1, 1, B->block, 1, 1, 0, ctx->stream, args, nullptr);
     kname = "nk_batch_trust_region";
+  } else if (method == BATCH_GAUSS_NEWTON) {
+    void *args[] = {&nb, &du0, &ups, &dp, sa[0], &maxiters, &du, &dr, &drc, &dit};
+    st = hipModuleLaunchKernel(B->fn_gn, grid, 1, 1, B->block, 1, 1, 0, ctx->stream, args, nullptr);
+    kname = "nk_batch_gauss_newton";
+  } else if (method == BATCH_TR_NLLS) {
+    int ms = (int)prm[5];
+    void *args[] = {&nb, &du0, &ups, &dp, sa[0], &maxiters, sa[1], sa[2], sa[3], sa[4], sa[5], &ms, &du, &dr, &drc, &dit};
+    st = hipModuleLaunchKernel(B->fn_tr_nlls, grid, 1, 1, B->block, 1, 1, 0, ctx->stream, args, nullptr);
+    kname = "nk_batch_trust_region_nlls";
   } else if (method == BATCH_BROYDEN) {
     void *args[] = {&nb, &du0, &ups, &dp, sa[0], &maxiters, sa[1], &du, &dr, &drc, &dit};
     st = hipModuleLaunchKernel(B->fn_broyden, grid, 1, 1, B->block, 1, 1, 0, ctx->stream, args, nullptr);
@@ -922,7 +1293,7 @@ static int batch_run(nk_batch *B, bool f32, int method, int64_t nbatch, const vo
   if (st != hipSuccess) NK_FAIL(NK_E_HIP, "launch of %s failed", kname);
   if (memspace != NK_DEVICE) {
     NK_HIP(hipMemcpyAsync(u_out, du, (size_t)nbatch * n * es, hipMemcpyDeviceToHost, ctx->stream));
-    NK_HIP(hipMemcpyAsync(resid_out, dr, (size_t)nbatch * n * es, hipMemcpyDeviceToHost, ctx->stream));
+    NK_HIP(hipMemcpyAsync(resid_out, dr, (size_t)nbatch * nr * es, hipMemcpyDeviceToHost, ctx->stream));
   }
   // retcode / iteration outputs follow the memory space of the other arrays
   if (retcode_out)
@@ -982,6 +1353,44 @@ extern "C" int nk_batch_solve_trust_region_f32(nk_batch *B, int64_t nbatch, cons
   trust_region_params(tr, step_threshold, shrink_threshold, expand_threshold, shrink_factor, expand_factor, max_shrink_times);
   return batch_run(B, true, BATCH_TRUST_REGION, nbatch, u0, u0_per_system, p, memspace, abstol, maxiters, tr, u_out,
                    resid_out, retcode_out, iters_out);
+}
+
+// Least squares (m residuals, n unknowns; objects of nk_batch_create_nlls): SimpleGaussNewton and SimpleTrustRegion with
+// ‖f‖₂ ≤ abstol termination; resid_out is nbatch×m
+extern "C" int nk_batch_solve_gauss_newton(nk_batch *B, int64_t nbatch, const double *u0, int u0_per_system, const double *p,
+                                           int memspace, double abstol, int maxiters, double *u_out, double *resid_out,
+                                           int32_t *retcode_out, int32_t *iters_out) {
+  return batch_run(B, false, BATCH_GAUSS_NEWTON, nbatch, u0, u0_per_system, p, memspace, abstol, maxiters, nullptr, u_out,
+                   resid_out, retcode_out, iters_out);
+}
+
+extern "C" int nk_batch_solve_gauss_newton_f32(nk_batch *B, int64_t nbatch, const float *u0, int u0_per_system, const float *p,
+                                               int memspace, double abstol, int maxiters, float *u_out, float *resid_out,
+                                               int32_t *retcode_out, int32_t *iters_out) {
+  return batch_run(B, true, BATCH_GAUSS_NEWTON, nbatch, u0, u0_per_system, p, memspace, abstol, maxiters, nullptr, u_out,
+                   resid_out, retcode_out, iters_out);
+}
+
+extern "C" int nk_batch_solve_trust_region_nlls(nk_batch *B, int64_t nbatch, const double *u0, int u0_per_system, const double *p,
+                                                int memspace, double abstol, int maxiters, double step_threshold,
+                                                double shrink_threshold, double expand_threshold, double shrink_factor,
+                                                double expand_factor, int max_shrink_times, double *u_out, double *resid_out,
+                                                int32_t *retcode_out, int32_t *iters_out) {
+  double tr[6];
+  trust_region_params(tr, step_threshold, shrink_threshold, expand_threshold, shrink_factor, expand_factor, max_shrink_times);
+  return batch_run(B, false, BATCH_TR_NLLS, nbatch, u0, u0_per_system, p, memspace, abstol, maxiters, tr, u_out, resid_out,
+                   retcode_out, iters_out);
+}
+
+extern "C" int nk_batch_solve_trust_region_nlls_f32(nk_batch *B, int64_t nbatch, const float *u0, int u0_per_system,
+                                                    const float *p, int memspace, double abstol, int maxiters,
+                                                    double step_threshold, double shrink_threshold, double expand_threshold,
+                                                    double shrink_factor, double expand_factor, int max_shrink_times,
+                                                    float *u_out, float *resid_out, int32_t *retcode_out, int32_t *iters_out) {
+  double tr[6];
+  trust_region_params(tr, step_threshold, shrink_threshold, expand_threshold, shrink_factor, expand_factor, max_shrink_times);
+  return batch_run(B, true, BATCH_TR_NLLS, nbatch, u0, u0_per_system, p, memspace, abstol, maxiters, tr, u_out, resid_out,
+                   retcode_out, iters_out);
 }
 
 // SimpleBroyden (broyden.jl:31-108, linesearch = nothing): alpha ≤ 0 is `nothing` (init_α from the norms of f(u0) and u0),
