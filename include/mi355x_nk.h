@@ -391,7 +391,10 @@ int nk_csr_set_values(nk_csr *A, const double *vals, int memspace);
 int nk_csr_set_values_csc(nk_csr *A, const double *nzval, int64_t nnz_csc, int memspace);
 int nk_csr_get_values(nk_csr *A, double *vals, int memspace);
 int nk_csr_info(nk_csr *A, int64_t *nrows_local, int64_t *n_global, int64_t *nnz, int64_t *n_halo);
-double *nk_csr_values_device(nk_csr *A);      /* device pointer of the local values (nnz doubles) */
+/* Device pointer of the local values (nnz doubles). From this call on the library cannot see when the values change, so it
+ * treats every value-dependent cache of this matrix as always stale: the transposed values are permuted again before every
+ * nk_spmv_t, cached spectrum bounds are recomputed, the speculative Jacobian fill is off. */
+double *nk_csr_values_device(nk_csr *A);
 /* y = A x  (x, y local slices; halo exchanged internally).  nk_spmv_t: y = Aᵀ x (the contributions to entries other
  * ranks own return through the halo plan in reverse and are added in rank order: bitwise reproducible). */
 int nk_spmv(nk_csr *A, const double *x, double *y, int memspace);
@@ -463,6 +466,10 @@ int nk_gmres_set_spectrum_interval(nk_gmres *G, double lo, double hi);
  * the last solve built Newton-basis blocks, and how many blocks have lost rank so far (each made its cycle run again —
  * narrower, or column by column). Any pointer may be NULL. */
 int nk_gmres_get_sstep_state(nk_gmres *G, int *block_size, int *newton_basis, int *breakdowns);
+/* NK_ORTHO_SSTEP diagnostics: the bounds lo < hi of the spectrum the last solve placed its Newton-basis shifts on (Gershgorin
+ * discs of a CSR operator, closed-form or caller's bounds). An error if the last solve built no Newton-basis blocks. Read it
+ * before the next solve is prepared. */
+int nk_gmres_get_sstep_interval(nk_gmres *G, double *lo, double *hi);
 /* Damped normal form: the operator becomes AᵀA + lambda·diag(d) (d: DEVICE vector of local length n, kept by reference;
  * NULL switches the damping off) — `dampen_jacobian!!(J_cache, JᵀJ, λ·DᵀD)` of DampedNewtonDescent's :normal_form mode
  * (lib/NonlinearSolveBase/src/descent/damped_newton.jl:297-313,356-370) without assembling JᵀJ. */

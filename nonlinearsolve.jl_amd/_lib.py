@@ -153,6 +153,7 @@ SIGNATURES = {
     "nk_gmres_set_sstep_basis": (_I, [_P, _I]),
     "nk_gmres_set_spectrum_interval": (_I, [_P, C.c_double, C.c_double]),
     "nk_gmres_get_sstep_state": (_I, [_P, C.POINTER(_I), C.POINTER(_I), C.POINTER(_I)]),
+    "nk_gmres_get_sstep_interval": (_I, [_P, C.POINTER(_D), C.POINTER(_D)]),
     "nk_gmres_set_shift_weights": (_I, [_P, _P]),
     "nk_problem_create": (_I, [_P, _I, C.POINTER(_D), _I, _PP]),
     "nk_problem_create_user": (_I, [_P, _L, _L, _L, C.POINTER(UserCallbacks), _P, _P, _PP]),

@@ -1390,6 +1390,12 @@ class GMRES:
         check(L.lib().nk_gmres_get_sstep_state(self._h, C.byref(bs), C.byref(nb), C.byref(bd)))
         return bs.value, bool(nb.value), bd.value
 
+    def sstep_interval(self):
+        """(lo, hi): the bounds of the spectrum the last solve placed its Newton-basis shifts on"""
+        a, b = C.c_double(), C.c_double()
+        check(L.lib().nk_gmres_get_sstep_interval(self._h, C.byref(a), C.byref(b)))
+        return a.value, b.value
+
     def chebyshev_interval(self):
         a, b = C.c_double(), C.c_double()
         check(L.lib().nk_gmres_get_chebyshev_interval(self._h, C.byref(a), C.byref(b)))

@@ -820,14 +820,9 @@ static int build_transpose(nk_csr *A) {
   return NK_OK;
 }
 
-int nk_csr_spmv_t_dev(nk_csr *A, const double *d_x, double *d_y) {
+// y = T x with whatever values T holds (the transposed values, or their squares for nk_csr_colsumsq_dev)
+static int spmv_t_apply(nk_csr *A, const double *d_x, double *d_y) {
   nk_ctx *ctx = A->ctx;
-  if (!A->T) NK_TRY(build_transpose(A));
-  if (A->t_values_stale && A->nnz) {
-    const int grid = (int)((A->nnz + NK_BLOCK - 1) / NK_BLOCK);
-    NK_LAUNCH(ctx, k_permute_vals, dim3(grid), dim3(NK_BLOCK), A->nnz, A->d_tperm, A->d_val, A->T->d_val);
-    A->t_values_stale = false;
-  }
   const int64_t n = A->nrows, nh = (int64_t)A->halo_gcols.size();
   if (nh == 0 && A->halo.n_send == 0) return nk_csr_spmv_dev(A->T, d_x, d_y, nullptr);
   // T x: (n + nh) outputs. (T's SpMV reads x as a vector of n + nh entries only through its column ids, all < n.)
@@ -860,6 +855,17 @@ int nk_csr_spmv_t_dev(nk_csr *A, const double *d_x, double *d_y) {
   NK_HIP(hipGetLastError());
   return NK_OK;
 }
+int nk_csr_spmv_t_dev(nk_csr *A, const double *d_x, double *d_y) {
+  if (!A->T) NK_TRY(build_transpose(A));
+  // (raw_exposed: the caller holds the value array and may have written it since the last product — always stale, the rule the
+  //  bounds cache follows)
+  if ((A->t_values_stale || A->raw_exposed) && A->nnz) {
+    const int grid = (int)((A->nnz + NK_BLOCK - 1) / NK_BLOCK);
+    NK_LAUNCH(A->ctx, k_permute_vals, dim3(grid), dim3(NK_BLOCK), A->nnz, A->d_tperm, A->d_val, A->T->d_val);
+    A->t_values_stale = false;
+  }
+  return spmv_t_apply(A, d_x, d_y);
+}
 
 // out_j = Σ_i A_ij² = ((A∘A)ᵀ·1)_j — the transposed product with squared values and a vector of ones, so it inherits the
 // fixed summation order and the rank-ordered reverse exchange of nk_csr_spmv_t_dev (bitwise reproducible, any partition)
@@ -879,8 +885,7 @@ int nk_csr_colsumsq_dev(nk_csr *A, double *d_out) {
     const int grid = (int)((A->nnz + NK_BLOCK - 1) / NK_BLOCK);
     NK_LAUNCH(ctx, k_permute_vals_sq, dim3(grid), dim3(NK_BLOCK), A->nnz, A->d_tperm, A->d_val, A->T->d_val);
   }
-  A->t_values_stale = false;                    // T holds the squares for this one product …
-  const int st = nk_csr_spmv_t_dev(A, A->d_ones, d_out);
+  const int st = spmv_t_apply(A, A->d_ones, d_out);   // T holds the squares for this one product …
   A->t_values_stale = true; A->bounds_valid = false; A->bounds_pending = false;                     // … and must be refreshed before the next Aᵀ x
   return st;
 }
@@ -1055,3 +1060,87 @@ static int spmv_any(nk_csr *A, const double *x, double *y, int memspace, bool tr
 }
 extern "C" int nk_spmv(nk_csr *A, const double *x, double *y, int memspace) { return spmv_any(A, x, y, memspace, false); }
 extern "C" int nk_spmv_t(nk_csr *A, const double *x, double *y, int memspace) { return spmv_any(A, x, y, memspace, true); }
+
+// ----------------------------------------------------------------------------- development harness (not in the public header)
+// Test hooks of tests/test_gpu_csr.py, exported like nk_ss_sweep_test. All vectors are HOST arrays of nrows doubles.
+//
+// One SpMV launch with the row epilogue `mode` of spmv_store_row: x is the input; y, r, dnew, yacc (each may be NULL when the
+// mode does not touch it) are uploaded, handed to the kernel and downloaded again; dinv and out_scale (one double) may be NULL.
+extern "C" int nk_spmv_epilogue_test(nk_csr *A, int mode, const double *x, double *y, double *r, double *dnew, double *yacc,
+                                     const double *dinv, double c1, double c2, double theta, const double *out_scale) {
+  NK_REQUIRE(A && x, "NULL argument");
+  NK_REQUIRE(mode >= 0 && mode <= 4, "mode must be 0 … 4");
+  NK_REQUIRE((mode == 1 || mode == 4) || y != nullptr, "this mode writes y");
+  NK_REQUIRE(mode == 0 || mode == 3 || r != nullptr, "this mode reads r");
+  NK_REQUIRE(mode != 1 || (dnew && yacc), "mode 1 writes dnew and yacc");
+  nk_ctx *ctx = A->ctx;
+  NK_HIP(hipSetDevice(ctx->device));
+  const size_t n = (size_t)A->nrows;
+  std::vector<double *> d(7, nullptr);   // x, y, r, dnew, yacc, dinv, {theta, out_scale}
+  auto guard = nk_make_guard(&d, [](std::vector<double *> *p) { for (double *q : *p) hipFree(q); });
+  const double *h[6] = {x, y, r, dnew, yacc, dinv};
+  for (int i = 0; i < 6; ++i) {
+    if (!h[i]) continue;
+    NK_TRY(nk_dev_alloc(&d[i], n + 1));
+    if (n) NK_HIP(nk_memcpy(ctx, d[i], h[i], n * sizeof(double), hipMemcpyHostToDevice));
+  }
+  NK_TRY(nk_dev_alloc(&d[6], (size_t)2));
+  double *d_sc = d[6];
+  const double sc[2] = {theta, out_scale ? *out_scale : 1.0};
+  NK_HIP(nk_memcpy(ctx, d_sc, sc, sizeof(sc), hipMemcpyHostToDevice));
+  nk_spmv_epi ep{};
+  ep.mode = mode; ep.c1 = c1; ep.c2 = c2;
+  ep.r = d[2]; ep.dnew = d[3]; ep.yacc = d[4]; ep.dinv = d[5];
+  ep.theta = d_sc;
+  NK_TRY(nk_csr_spmv_dev(A, d[0], d[1], nullptr, out_scale ? d_sc + 1 : nullptr, &ep));
+  NK_HIP(hipStreamSynchronize(ctx->stream));
+  double *back[4] = {y, r, dnew, yacc};
+  for (int i = 0; i < 4; ++i)
+    if (back[i] && n) NK_HIP(nk_memcpy(ctx, back[i], d[i + 1], n * sizeof(double), hipMemcpyDeviceToHost));
+  return NK_OK;
+}
+// {−lo, hi} as nk_csr_gershgorin_dev hands them to the s-step begin: the cached pair when the cache holds (a pending reduction
+// of a fill kernel's partials is settled first), a fresh k_csr_gershgorin pass otherwise.
+extern "C" int nk_csr_gershgorin_test(nk_csr *A, double *out2) {
+  NK_REQUIRE(A && out2, "NULL argument");
+  nk_ctx *ctx = A->ctx;
+  NK_HIP(hipSetDevice(ctx->device));
+  double *d_tmp = nullptr;
+  NK_TRY(nk_dev_alloc(&d_tmp, (size_t)2));
+  auto guard = nk_make_guard(d_tmp, [](double *p) { hipFree(p); });
+  const double *where = nullptr;
+  NK_TRY(nk_csr_gershgorin_dev(A, d_tmp, &where));
+  NK_HIP(hipStreamSynchronize(ctx->stream));
+  NK_HIP(nk_memcpy(ctx, out2, where, 2 * sizeof(double), hipMemcpyDeviceToHost));
+  return NK_OK;
+}
+// The assembled normal matrix N = JᵀJ + λ·diag(d) (d: HOST, nrows doubles, may be NULL) as LevenbergMarquardt's factorising
+// path builds it. First call with rowptr = NULL: *nnz_out = nnz(N). Second call: rowptr (nrows + 1), col (nnz) and vals (nnz)
+// receive the pattern and the values.
+extern "C" int nk_normal_plan_test(nk_csr *J, double lambda, const double *d, int64_t *nnz_out, int32_t *rowptr, int32_t *col,
+                                   double *vals) {
+  NK_REQUIRE(J && nnz_out, "NULL argument");
+  nk_ctx *ctx = J->ctx;
+  NK_HIP(hipSetDevice(ctx->device));
+  nk_normal_plan *Pn = nullptr;
+  NK_TRY(nk_normal_plan_create(J, &Pn));
+  auto guard = nk_make_guard(Pn, [](nk_normal_plan *q) { nk_normal_plan_destroy(q); });
+  nk_csr *N = Pn->N;
+  *nnz_out = N->nnz;
+  if (!rowptr) return NK_OK;
+  NK_REQUIRE(col && vals, "NULL argument");
+  double *d_d = nullptr;
+  auto guard2 = nk_make_guard(&d_d, [](double **p) { hipFree(*p); });
+  if (d) {
+    NK_TRY(nk_dev_alloc(&d_d, (size_t)J->nrows + 1));
+    if (J->nrows) NK_HIP(nk_memcpy(ctx, d_d, d, J->nrows * sizeof(double), hipMemcpyHostToDevice));
+  }
+  NK_TRY(nk_normal_plan_values(Pn, J, lambda, d_d));
+  NK_HIP(hipStreamSynchronize(ctx->stream));
+  memcpy(rowptr, N->h_rowptr.data(), (N->nrows + 1) * sizeof(int32_t));
+  if (N->nnz) {
+    memcpy(col, N->h_col.data(), N->nnz * sizeof(int32_t));
+    NK_HIP(nk_memcpy(ctx, vals, N->d_val, N->nnz * sizeof(double), hipMemcpyDeviceToHost));
+  }
+  return NK_OK;
+}

@@ -2272,6 +2272,22 @@ extern "C" int nk_gmres_get_sstep_state(nk_gmres *G, int *block_size, int *newto
   return NK_OK;
 }
 
+// {lo, hi} the last solve's begin kernel placed the Newton-basis shifts on, read back from where that solve took them: the
+// matrix's bounds word (a Jacobian fill's partials, reduced by the begin kernel or by nk_csr_gershgorin_dev), the workspace's
+// own pair (a fresh Gershgorin pass, closed-form or caller's bounds). Valid until the next solve begins — a Jacobian fill that
+// carries the next solve's begin (nk_gmres_begin_ahead) counts as that.
+extern "C" int nk_gmres_get_sstep_interval(nk_gmres *G, double *lo, double *hi) {
+  NK_REQUIRE(G && lo && hi, "NULL argument");
+  NK_REQUIRE(G->ss && G->ss->newton && G->ss->ival_use, "the last solve built no Newton-basis blocks");
+  NK_HIP(hipSetDevice(G->ctx->device));
+  NK_HIP(hipStreamSynchronize(G->ctx->stream));
+  double v[2];
+  NK_HIP(nk_memcpy(G->ctx, v, G->ss->ival_use, sizeof(v), hipMemcpyDeviceToHost));
+  *lo = -v[0];
+  *hi = v[1];
+  return NK_OK;
+}
+
 // Implicit second pass (A/B switch NK_SS_IMPLICIT=0): a block that is not the cycle's last is left at its first pass as well —
 // no sweep C; the next blocks carry their Gram products through its (C₂, R₂) (ss_fix_to_true / _to_stored), its Hessenberg
 // columns are a launch of their own, the back-substitution adapts y block by block. One sweep over k + 2s columns less per block.
