@@ -65,7 +65,8 @@ typedef enum {
   NK_RET_SHRINK_THRESHOLD_EXCEEDED = 6,
   NK_RET_MAXTIME = 7,
   NK_RET_FAILURE = 8,
-  NK_RET_INTERNAL_LINESEARCH_FAILED = 9
+  NK_RET_INTERNAL_LINESEARCH_FAILED = 9,
+  NK_RET_CONVERGENCE_FAILURE = 10   /* NK_ALG_LIMITED_MEMORY_BROYDEN: the reset count reached max_resets (QuasiNewton/src/solve.jl:342-348) */
 } nk_retcode;
 
 typedef enum {
@@ -85,8 +86,12 @@ typedef enum {
 /* NK_ALG_PSEUDO_TRANSIENT: DampedNewtonDescent with SwitchedEvolutionRelaxation damping in :simple mode
  * (descent/damped_newton.jl:283-288): the Newton step on J + α⁻¹ I — the shift is added to the diagonal of the concrete J
  * (`dampen_jacobian!!`) or to the matrix-free operator. */
+/* NK_ALG_LIMITED_MEMORY_BROYDEN: LimitedMemoryBroyden without a line search (lib/NonlinearSolveQuasiNewton/src/lbroyden.jl): the
+ * inverse Jacobian is a·I + U Vᵀ with `lb_threshold` columns, good-Broyden updates, NoChangeInStateReset(nsteps = 3). Needs
+ * only the residual: no Jacobian, no JVP, no linear solve — nk_options.linsolve, the Krylov, forcing, preconditioner and
+ * line-search fields are not read (linesearch != 0 is NK_E_INVALID: the line-search form is not built). One rank. */
 typedef enum { NK_ALG_NEWTON_RAPHSON = 0, NK_ALG_TRUST_REGION = 1, NK_ALG_GAUSS_NEWTON = 2,
-               NK_ALG_LEVENBERG_MARQUARDT = 3, NK_ALG_PSEUDO_TRANSIENT = 4 } nk_algorithm;
+               NK_ALG_LEVENBERG_MARQUARDT = 3, NK_ALG_PSEUDO_TRANSIENT = 4, NK_ALG_LIMITED_MEMORY_BROYDEN = 5 } nk_algorithm;
 
 /* which operator the Krylov solver sees as A (lib/NonlinearSolveBase/src/jacobian.jl:43-47,90-102) */
 typedef enum {
@@ -260,6 +265,11 @@ typedef struct {
    *     4 aggregation algebraic multigrid (nk_precond_create_amg with its defaults) */
   int32_t precond_kind;                 /* [0]                                                                        */
   int32_t precond_side;                 /* [1]    nk_side: the reference's tutorial precs return (Pl, I): left        */
+  /* --- LimitedMemoryBroyden (lib/NonlinearSolveQuasiNewton/src/lbroyden.jl:20-35); a value <= 0 selects the default */
+  int32_t lb_threshold;                 /* [10]   columns of U and V, 1..32 (more: NK_E_INVALID); clamped to maxiters          */
+  int32_t lb_max_resets;                /* [3]    the reset that brings the count to this ends the solve (ConvergenceFailure) */
+  double  lb_reset_tolerance;           /* [eps^(3/4)] NoChangeInStateReset's tolerance (reset_conditions.jl:34)              */
+  double  lb_alpha;                     /* [nothing] J⁻¹ starts as I/alpha; default alpha = 2‖fu‖₂/max(‖u‖₂, 1), 1 if ‖fu‖₂ < 1e-5 */
 } nk_options;
 
 /* in-place callbacks of a user problem: NonlinearFunction{true}(f!; jvp, vjp, jac)
@@ -623,6 +633,11 @@ int nk_solver_set_precs(nk_solver *S, nk_precs_fn fn, void *user);
 nk_gmres *nk_solver_gmres(nk_solver *S);
 nk_csr *nk_solver_jacobian(nk_solver *S);
 int nk_solver_get_retcode(nk_solver *S, int *retcode, int *nsteps, int *force_stop);
+/* NK_ALG_LIMITED_MEMORY_BROYDEN: the state of the low-rank inverse Jacobian (nk_stats has no slot for it): resets counted so
+ * far, updates since the last reset (`idx`; min(idx, threshold) columns are in use), the scaling a of a·I + U Vᵀ, the
+ * threshold in effect, and the reset test's two counters. Any pointer may be NULL. NK_E_INVALID for another algorithm. */
+int nk_solver_get_lbroyden_state(nk_solver *S, int *nresets, int *idx, double *a, int *threshold, int *since_du,
+                                 int *since_dfu);
 int nk_solver_get_scalars(nk_solver *S, double *fnorm_inf, double *trust_region, double *eta);
 int nk_solver_get_trace(nk_solver *S, nk_trace_entry *rows, int capacity, int *nrows);
 /* one call: init + solve + results (what SciMLBase.__solve of the extension algorithm does) */

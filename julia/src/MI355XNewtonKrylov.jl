@@ -519,16 +519,17 @@ Base.@kwdef mutable struct NKOptions
     pt_alpha_initial::Float64 = 1e-3
     gmres_sstep::Int32 = 0; gmres_sstep_basis::Int32 = 0
     precond_kind::Int32 = 0; precond_side::Int32 = 1
+    lb_threshold::Int32 = 0; lb_max_resets::Int32 = 0; lb_reset_tolerance::Float64 = 0.0; lb_alpha::Float64 = 0.0
 end
 
 const RETCODES = (ReturnCode.Default, ReturnCode.Success, ReturnCode.MaxIters, ReturnCode.Unstable,
     ReturnCode.Stalled, ReturnCode.InternalLinearSolveFailed, ReturnCode.ShrinkThresholdExceeded,
-    ReturnCode.MaxTime, ReturnCode.Failure, ReturnCode.InternalLineSearchFailed)
+    ReturnCode.MaxTime, ReturnCode.Failure, ReturnCode.InternalLineSearchFailed, ReturnCode.ConvergenceFailure)
 
 function SciMLBase.__solve(prob::NonlinearProblem, alg::MI355XNewtonKrylovAlg, args...;
         abstol = nothing, reltol = nothing, maxiters = 1000, maxtime = nothing, termination_condition = nothing,
         kwargs...)
-    algorithm = alg.method === :PseudoTransient ? 4 : alg.method === :LevenbergMarquardt ? 3 : alg.method === :GaussNewton ? 2 : (alg.trust_region ? 1 : 0)
+    algorithm = alg.method === :LimitedMemoryBroyden ? 5 : alg.method === :PseudoTransient ? 4 : alg.method === :LevenbergMarquardt ? 3 : alg.method === :GaussNewton ? 2 : (alg.trust_region ? 1 : 0)
     o = NKOptions(; algorithm = algorithm,
         linsolve = alg.direct ? 2 : ((alg.concrete_jac || algorithm == 3) ? 1 : 0),
         lm_disable_geodesic = alg.lm_disable_geodesic ? 1 : 0, lm_damping_initial = alg.lm_damping_initial,

@@ -857,6 +857,25 @@ class PseudoTransient:  # pseudo_transient.jl:37-57
     name: str = "PseudoTransient"
 
 
+class LimitedMemoryBroyden:  # lib/NonlinearSolveQuasiNewton/src/lbroyden.jl:20-35
+    """LimitedMemoryBroyden(; max_resets = 3, linesearch = nothing, threshold = 10, reset_tolerance = nothing, alpha = nothing):
+    J⁻¹ = I/α + U Vᵀ with `threshold` columns (1..32, clamped to maxiters), good-Broyden updates, NoChangeInStateReset.
+    Needs only the residual — a problem without jvp / jac is accepted. The line-search form is not built."""
+    linsolve = None
+    name = "LimitedMemoryBroyden"
+
+    def __init__(self, max_resets: int = 3, linesearch=None, threshold: int = 10, reset_tolerance: Optional[float] = None,
+                 alpha: Optional[float] = None):
+        if linesearch is not None:
+            raise NotImplementedError("LimitedMemoryBroyden(linesearch=…): only the form without a line search is built")
+        self.max_resets, self.threshold = int(max_resets), int(threshold)
+        self.reset_tolerance, self.alpha = reset_tolerance, alpha
+
+    def __repr__(self):
+        return (f"LimitedMemoryBroyden(max_resets={self.max_resets}, threshold={self.threshold}, "
+                f"reset_tolerance={self.reset_tolerance}, alpha={self.alpha})")
+
+
 @dataclass
 class _TerminationMode:
     """SciMLBase termination modes (lib/NonlinearSolveBase/src/termination_conditions.jl); `internalnorm` is
@@ -941,7 +960,16 @@ def _options(alg, abstol, reltol, maxiters, maxtime, store_trace, termination_kw
         o.lm_alpha_geodesic = float(alg.alpha_geodesic)
         o.lm_finite_diff_step_geodesic = float(alg.finite_diff_step_geodesic)
         o.lm_b_uphill = float(alg.b_uphill)
-    if ls is None:
+    if isinstance(alg, LimitedMemoryBroyden):   # no Jacobian, no linear solve: `linsolve` and the Krylov fields are not read
+        o.algorithm = L.ALG_LIMITED_MEMORY_BROYDEN
+        if alg.threshold < 1 or alg.max_resets < 1:
+            raise ValueError("LimitedMemoryBroyden: threshold and max_resets must be positive")
+        o.lb_threshold, o.lb_max_resets = alg.threshold, alg.max_resets
+        o.lb_reset_tolerance = 0.0 if alg.reset_tolerance is None else float(alg.reset_tolerance)
+        o.lb_alpha = 0.0 if alg.alpha is None else float(alg.alpha)
+        ls = KrylovJL_GMRES()
+        o.linsolve = L.LINSOLVE_GMRES_MATFREE
+    elif ls is None:
         # linsolve = nothing: LinearSolve's default factorisation of the concrete sparse J → banded LU on device
         o.linsolve = L.LINSOLVE_BANDED_LU
         ls = KrylovJL_GMRES()  # unused Krylov fields keep their defaults
@@ -1113,6 +1141,16 @@ class FirstOrderCache:
         a, b, c = C.c_double(), C.c_double(), C.c_double()
         check(L.lib().nk_solver_get_scalars(self._h, C.byref(a), C.byref(b), C.byref(c)))
         return c.value
+
+    @property
+    def lbroyden_state(self) -> dict:
+        """LimitedMemoryBroyden: resets counted, updates since the last reset (idx), the scaling a of a·I + U Vᵀ, the threshold
+        in effect and the reset test's two counters"""
+        r, i, t, d, f = C.c_int(), C.c_int(), C.c_int(), C.c_int(), C.c_int()
+        a = C.c_double()
+        check(L.lib().nk_solver_get_lbroyden_state(self._h, C.byref(r), C.byref(i), C.byref(a), C.byref(t), C.byref(d),
+                                                   C.byref(f)))
+        return dict(nresets=r.value, idx=i.value, a=a.value, threshold=t.value, since_du=d.value, since_dfu=f.value)
 
     @property
     def fnorm_inf(self):

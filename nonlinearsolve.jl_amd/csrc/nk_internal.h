@@ -866,6 +866,23 @@ void nk_bandlu_destroy(nk_bandlu *B);
 int nk_bandlu_factor(nk_bandlu *B, nk_csr *A, int *ok);
 int nk_bandlu_solve(nk_bandlu *B, const double *d_b, double *d_x);
 
+// ----------------------------------------------------------------------------- LimitedMemoryBroyden (nk_qn.hip)
+// the low-rank inverse Jacobian a·I + U Vᵀ and the three launches a step makes on it (the driver is nk_solver.hip: lb_step)
+struct nk_lbroyden;
+int nk_lb_create(nk_ctx *ctx, int64_t n, int threshold, nk_lbroyden **out);   // threshold 1..32
+void nk_lb_destroy(nk_lbroyden *W);
+int nk_lb_restart(nk_lbroyden *W);                 // idx = 0
+int nk_lb_index(const nk_lbroyden *W);             // updates since the last restart
+int nk_lb_columns(const nk_lbroyden *W);           // min(idx, threshold)
+const double *nk_lb_du(const nk_lbroyden *W);      // δu of the last nk_lb_direction
+int nk_lb_direction(nk_lbroyden *W, double a, const double *fu, const double *u, double *u_new);
+int nk_lb_reduce(nk_lbroyden *W, const double *fu_new, const double *ref, double tol);
+// device scalars of the last nk_lb_reduce: [0] max|fu| (NaN-propagating), [1] ‖fu‖², [2] ‖δu‖², [3] any(|δu_i| ≤ tol),
+// [4] any(|fu_i − ref_i| ≤ tol), [5] ‖u_new‖²
+double *nk_lb_scalars(nk_lbroyden *W);
+int nk_lb_combine(nk_lbroyden *W, double a, const double *fu_new);
+double nk_lb_pass_bytes(int64_t n, int m);
+
 // ----------------------------------------------------------------------------- misc helpers
 // The library's "synchronous" memsets and copies, ORDERED ON THE CONTEXT'S STREAM. hipMemset / hipMemcpy run on the null stream:
 // a caller's stream created with hipStreamNonBlocking (PyTorch's, AMDGPU.jl's) is not ordered against it, and hipMemset of device

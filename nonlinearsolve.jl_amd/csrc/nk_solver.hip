@@ -86,6 +86,15 @@ struct nk_solver {
   nk_csr_valstate spec_state{};                 // the filled set (valid) / the spare buffers (not valid)
   nk_precs_fn precs = nullptr;
   void *precs_user = nullptr;
+  // LimitedMemoryBroyden (nk_qn.hip): the low-rank inverse Jacobian, J⁻¹ = lb_a·I + U Vᵀ; the residual lives in a pool of three
+  // buffers — `fu` (current), `lb_ref` (the residual NoChangeInStateReset last looked at: normally the previous one, one step
+  // older after the early return of its `du` branch) and a spare the next evaluation writes into
+  nk_lbroyden *lb = nullptr;
+  double *lb_fupool[3] = {nullptr, nullptr, nullptr};
+  const double *lb_ref = nullptr;
+  double lb_a = 1.0, lb_tol = 0.0, lb_u_ss = 0.0;
+  int lb_threshold = 0, lb_max_resets = 0, lb_nresets = 0, lb_since_du = 0, lb_since_dfu = 0;
+  bool lb_flag_du = false, lb_flag_dfu = false;   // the reset test's any(…) flags for the NEXT step (left by this step's reduce pass)
 };
 
 // u_new = u + sign·du (out of place: the old iterate stays intact in its buffer) ; partial Σ (u_new − u_old)²  (the stall
@@ -245,6 +254,10 @@ extern "C" int nk_options_default(nk_options *o) {
   o->gmres_sstep_basis = NK_SS_BASIS_AUTO;
   o->precond_kind = 0;
   o->precond_side = NK_SIDE_LEFT;
+  o->lb_threshold = 10;  // LimitedMemoryBroyden() (lbroyden.jl:20-23); reset_tolerance and alpha: 0 = `nothing`
+  o->lb_max_resets = 3;
+  o->lb_reset_tolerance = 0.0;
+  o->lb_alpha = 0.0;
   return NK_OK;
 }
 
@@ -258,6 +271,7 @@ static bool normal_form(const nk_solver *S) {
 }
 static bool is_lm(const nk_solver *S) { return S->o.algorithm == NK_ALG_LEVENBERG_MARQUARDT; }
 static bool is_pt(const nk_solver *S) { return S->o.algorithm == NK_ALG_PSEUDO_TRANSIENT; }
+static bool is_lb(const nk_solver *S) { return S->o.algorithm == NK_ALG_LIMITED_MEMORY_BROYDEN; }
 static bool concrete(const nk_solver *S) { return S->o.linsolve != NK_LINSOLVE_GMRES_MATFREE; }
 static bool direct(const nk_solver *S) { return S->o.linsolve == NK_LINSOLVE_BANDED_LU; }
 
@@ -558,6 +572,111 @@ static int rollback_to_best(nk_solver *S) {
   return residual_norms(S, nullptr, 0, nullptr);
 }
 
+// ---- LimitedMemoryBroyden (lib/NonlinearSolveQuasiNewton/src/solve.jl:296-486 on BroydenLowRankJacobian)
+// Utils.initial_jacobian_scaling_alpha (NonlinearSolveBase/src/utils.jl:307-314), inverted: a = 1/α
+static double lb_scaling(const nk_solver *S, double fnorm2, double u_ss) {
+  if (S->o.lb_alpha > 0.0) return 1.0 / S->o.lb_alpha;
+  if (fnorm2 < 1.0e-5) return 1.0;
+  return 1.0 / ((2.0 * fnorm2) / fmax(sqrt(u_ss), 1.0));
+}
+// init and reinit!: idx = 0, the reset count and the reset test's counters are zero, the reset test's residual copy is f(u0)
+// (the reference's reinit! leaves that copy at the previous solve's last residual, reset_conditions.jl:47-53 — not kept:
+// a solve from the same u0 repeats itself here). a is computed by the first step, from ‖u0‖₂ and ‖f(u0)‖₂.
+static int lb_start(nk_solver *S) {
+  NK_TRY(nk_lb_restart(S->lb));
+  S->lb_nresets = S->lb_since_du = S->lb_since_dfu = 0;
+  S->lb_flag_du = S->lb_flag_dfu = false;
+  S->lb_ref = S->fu;
+  S->lb_a = 1.0;
+  NK_TRY(nk_blas_sumsq(S->ctx, S->n, S->u, slot(S, 0)));
+  NK_TRY(fetch(S, 1, &S->lb_u_ss));
+  return NK_OK;
+}
+// NoChangeInStateReset(nsteps = 3) (reset_conditions.jl:55-87) on the flags the last step's reduce pass left
+static bool lb_reset_test(nk_solver *S) {
+  if (S->lb_flag_du) {
+    if (++S->lb_since_du >= 3) {
+      S->lb_since_du = S->lb_since_dfu = 0;
+      return true;   // (the early return: the residual copy stays where it was)
+    }
+  } else {
+    S->lb_since_du = S->lb_since_dfu = 0;
+  }
+  bool reset = false;
+  if (S->lb_flag_dfu) {
+    if (++S->lb_since_dfu >= 3) {
+      S->lb_since_dfu = S->lb_since_du = 0;
+      reset = true;
+    }
+  } else {
+    S->lb_since_dfu = S->lb_since_du = 0;
+  }
+  S->lb_ref = S->fu;   // copyto!(cache.dfu, fu)
+  return reset;
+}
+static int check_and_update(nk_solver *S, double step_norm);
+static int lb_step(nk_solver *S, int recompute) {
+  nk_ctx *ctx = S->ctx;
+  NK_REQUIRE(recompute != 0, "LimitedMemoryBroyden: recompute_jacobian = false (a step without the update) is not offered");
+  if (S->nsteps == 0) {   // the first step initialises J⁻¹ whatever the arguments say (solve.jl:301-323)
+    S->lb_a = lb_scaling(S, S->fnorm2, S->lb_u_ss);
+  } else {
+    bool reinit = true;
+    if (recompute < 0) {  // the standard step: the reset test decides, and its resets count
+      reinit = lb_reset_test(S);
+      if (reinit && ++S->lb_nresets >= S->lb_max_resets) {
+        S->retcode = NK_RET_CONVERGENCE_FAILURE;
+        S->force_stop = true;
+        return NK_OK;
+      }
+    }
+    if (reinit) {
+      NK_TRY(nk_lb_restart(S->lb));
+      S->lb_a = lb_scaling(S, S->fnorm2, S->lb_u_ss);
+    }
+  }
+  // δu = −J⁻¹ fu, u += δu (out of place: a retained best iterate stays intact)
+  double *un = spare_u(S);
+  NK_TRY(nk_lb_direction(S->lb, S->lb_a, S->fu, S->u, un));
+  S->u = un;
+  S->u_version++;
+  nk_problem_invalidate(S->P);
+  double *fnew = nullptr;
+  for (double *b : S->lb_fupool)
+    if (b != S->fu && b != S->lb_ref) { fnew = b; break; }
+  NK_TRY(nk_problem_residual_dev(S->P, S->u, fnew));
+  S->stats.nf++;
+  const double *fprev = S->fu;
+  if (S->lb_ref == nullptr) S->lb_ref = fprev;
+  S->fu = fnew;
+  // one pass over U and V: the update's coefficients, and everything the host reads for this step
+  NK_TRY(nk_lb_reduce(S->lb, S->fu, S->lb_ref, S->lb_tol));
+  double v[6];
+  NK_TRY(nk_scalars_to_host(ctx, nk_lb_scalars(S->lb), 6, v));
+  S->fnorm_inf = v[0];
+  S->fnorm2 = sqrt(v[1]);
+  const double step_norm = sqrt(v[2]);
+  S->lb_flag_du = v[3] != 0.0;
+  S->lb_flag_dfu = v[4] != 0.0;
+  S->lb_u_ss = v[5];
+  NK_TRY(check_and_update(S, step_norm));
+  if (S->o.store_trace) {
+    nk_trace_entry e;
+    memset(&e, 0, sizeof(e));
+    e.iter = S->nsteps + 1;
+    e.accepted = 1;
+    e.fnorm_inf = S->fnorm_inf;
+    e.step_norm2 = step_norm;
+    e.eta = NAN;
+    e.trust_region = NAN;
+    e.rho = NAN;
+    S->trace.push_back(e);
+  }
+  if (S->force_stop) return NK_OK;
+  // GoodBroydenUpdateRule: the second pass over U and V writes the new column pair
+  return nk_lb_combine(S->lb, S->lb_a, S->fu);
+}
+
 // ---- init
 static int solver_start(nk_solver *S, bool first = true) {  // everything after u has been set (first = init, else reinit!)
   nk_ctx *ctx = S->ctx;
@@ -602,6 +721,7 @@ static int solver_start(nk_solver *S, bool first = true) {  // everything after 
     if (first) S->pt_applied = 0.0;  // (the Jacobian values were just refilled; after reinit! the first step's refill resets it)
     if (S->G) NK_TRY(nk_gmres_set_shift(S->G, 0.0));
   }
+  if (is_lb(S)) NK_TRY(lb_start(S));
   if (is_lm(S)) {  // init / reinit! of the damping cache, the LM trust region and the geodesic cache
     S->lm_lam = S->o.lm_damping_initial;                    // levenberg_marquardt.jl:72-89,119-131
     S->lm_lam_factor = S->o.lm_damping_increase_factor;
@@ -622,7 +742,12 @@ extern "C" int nk_solver_init(nk_problem *P, const double *u0, int memspace, con
   NK_HIP(hipSetDevice(ctx->device));
   NK_REQUIRE(opts->algorithm == NK_ALG_NEWTON_RAPHSON || opts->algorithm == NK_ALG_TRUST_REGION ||
                  opts->algorithm == NK_ALG_GAUSS_NEWTON || opts->algorithm == NK_ALG_LEVENBERG_MARQUARDT ||
-                 opts->algorithm == NK_ALG_PSEUDO_TRANSIENT, "bad algorithm");
+                 opts->algorithm == NK_ALG_PSEUDO_TRANSIENT || opts->algorithm == NK_ALG_LIMITED_MEMORY_BROYDEN, "bad algorithm");
+  if (opts->algorithm == NK_ALG_LIMITED_MEMORY_BROYDEN) {
+    NK_REQUIRE(opts->linesearch == 0, "LimitedMemoryBroyden: the line-search form is not built (linesearch must be 0)");
+    NK_REQUIRE(opts->lb_threshold <= 32, "LimitedMemoryBroyden: threshold %d is outside 1..32", opts->lb_threshold);
+    NK_REQUIRE(ctx->nranks == 1, "LimitedMemoryBroyden runs on one rank");
+  }
   NK_REQUIRE(!(opts->algorithm == NK_ALG_PSEUDO_TRANSIENT && !(opts->pt_alpha_initial > 0.0)),
              "PseudoTransient: alpha_initial must be positive");
   NK_REQUIRE(!(opts->algorithm == NK_ALG_PSEUDO_TRANSIENT && opts->forcing != NK_FORCING_NONE),
@@ -639,7 +764,8 @@ extern "C" int nk_solver_init(nk_problem *P, const double *u0, int memspace, con
   NK_REQUIRE(opts->linsolve == NK_LINSOLVE_GMRES_MATFREE || opts->linsolve == NK_LINSOLVE_GMRES_CSR ||
                  opts->linsolve == NK_LINSOLVE_BANDED_LU,
              "unknown linsolve %d", opts->linsolve);
-  NK_REQUIRE(!(opts->linsolve == NK_LINSOLVE_BANDED_LU && opts->forcing != NK_FORCING_NONE),
+  NK_REQUIRE(!(opts->linsolve == NK_LINSOLVE_BANDED_LU && opts->forcing != NK_FORCING_NONE) ||
+                 opts->algorithm == NK_ALG_LIMITED_MEMORY_BROYDEN,
              "a forcing term needs an iterative linear solver");
   NK_REQUIRE(opts->termination_mode >= 0 && opts->termination_mode <= 8, "bad termination_mode %d", opts->termination_mode);
   NK_REQUIRE(opts->termination_norm == 0 || opts->termination_norm == 1, "bad termination_norm %d", opts->termination_norm);
@@ -653,6 +779,8 @@ extern "C" int nk_solver_init(nk_problem *P, const double *u0, int memspace, con
   S->ctx = ctx;
   auto guard = nk_make_guard(S, [](nk_solver *s) { nk_solver_destroy(s); });
   S->o = *opts;
+  // LimitedMemoryBroyden reads no Jacobian: whatever `linsolve` says, nothing below builds one, or a Krylov workspace
+  if (is_lb(S)) { S->o.linsolve = NK_LINSOLVE_GMRES_MATFREE; S->o.forcing = NK_FORCING_NONE; }
   if (S->o.maxiters <= 0) S->o.maxiters = 1000;
   if (S->o.gmres_restart <= 0) S->o.gmres_restart = 30;
   if (S->o.gmres_maxiters <= 0) S->o.gmres_maxiters = 300;
@@ -689,7 +817,16 @@ extern "C" int nk_solver_init(nk_problem *P, const double *u0, int memspace, con
     NK_TRY(nk_problem_jac_csr(P, &S->J));
     S->own_J = (P->kind != NK_PROBLEM_USER);
   }
-  if (direct(S)) {
+  if (is_lb(S)) {
+    S->lb_threshold = S->o.lb_threshold > 0 ? S->o.lb_threshold : 10;
+    if (S->lb_threshold > S->o.maxiters) S->lb_threshold = S->o.maxiters;   // initialization.jl:180
+    S->lb_max_resets = S->o.lb_max_resets > 0 ? S->o.lb_max_resets : 3;
+    S->lb_tol = S->o.lb_reset_tolerance > 0.0 ? S->o.lb_reset_tolerance : pow(2.220446049250313e-16, 0.75);
+    NK_TRY(nk_lb_create(ctx, n, S->lb_threshold, &S->lb));
+    S->lb_fupool[0] = S->fu;
+    NK_TRY(nk_dev_alloc(&S->lb_fupool[1], na));
+    NK_TRY(nk_dev_alloc(&S->lb_fupool[2], na));
+  } else if (direct(S)) {
     if (is_lm(S)) {  // the factorising solver gets the assembled normal matrix JᵀJ + λDᵀD (see lm_damped_solve)
       NK_TRY(nk_normal_plan_create(S->J, &S->nplan));
       NK_TRY(nk_bandlu_create(nk_normal_plan_matrix(S->nplan), &S->B));
@@ -714,6 +851,10 @@ extern "C" int nk_solver_destroy(nk_solver *S) {
   if (!S) return NK_OK;
   hipStreamSynchronize(S->ctx->stream);
   if (S->P) nk_problem_invalidate(S->P);  // the vectors the problem was linearised at are about to be freed
+  if (S->lb_fupool[0]) S->fu = S->lb_fupool[0];   // (fu rotates through the pool)
+  hipFree(S->lb_fupool[1]);
+  hipFree(S->lb_fupool[2]);
+  nk_lb_destroy(S->lb);
   double *bufs[] = {S->ubuf[0], S->ubuf[1], S->ubuf[2], S->fu, S->du, S->fu_trial, S->du_newton, S->du_cauchy,
                     S->Jdu, S->JTfu, S->c1, S->c2, S->tr_du, S->stage, S->stage2, S->lm_dtd, S->lm_diag, S->lm_v,
                     S->lm_a, S->lm_vcache, S->lm_rhs, S->pt_mass};
@@ -1696,7 +1837,7 @@ static int check_and_update(nk_solver *S, double step_norm) {
 // supports_deferred_residual (FirstOrder/src/solve.jl:303-316): only the unglobalised step, only a residual-only
 // termination mode (AbsTerminationMode / AbsNormTerminationMode, termination_conditions.jl:43-45), only without a trace
 static bool supports_deferred_residual(const nk_solver *S) {
-  if (is_tr(S) || is_lm(S) || S->o.linesearch) return false;
+  if (is_tr(S) || is_lm(S) || is_lb(S) || S->o.linesearch) return false;
   if (!(S->o.termination_mode == TM_ABS || S->o.termination_mode == TM_ABSNORM)) return false;
   return !S->o.store_trace;
 }
@@ -1748,6 +1889,7 @@ static int internal_step(nk_solver *S, int recompute /*-1 nothing, 0 false, 1 tr
   const int64_t n = S->n;
   // the descent is taken from the residual at the iterate it starts from: settle an outstanding deferral first
   NK_TRY(refresh_residual(S));  // (as in the reference, the step goes on even if this check terminated the solve)
+  if (is_lb(S)) return lb_step(S, recompute);
   const bool defer_residual = !evaluate_residual && supports_deferred_residual(S);
   bool new_jacobian;
   if ((recompute < 0 || recompute == 1) && S->make_new_jacobian) {
@@ -2012,6 +2154,18 @@ extern "C" int nk_solver_get_retcode(nk_solver *S, int *retcode, int *nsteps, in
   if (retcode) *retcode = S->retcode;
   if (nsteps) *nsteps = S->nsteps;
   if (force_stop) *force_stop = S->force_stop ? 1 : 0;
+  return NK_OK;
+}
+extern "C" int nk_solver_get_lbroyden_state(nk_solver *S, int *nresets, int *idx, double *a, int *threshold, int *since_du,
+                                            int *since_dfu) {
+  NK_REQUIRE(S, "NULL argument");
+  NK_REQUIRE(is_lb(S), "not a LimitedMemoryBroyden cache");
+  if (nresets) *nresets = S->lb_nresets;
+  if (idx) *idx = nk_lb_index(S->lb);
+  if (a) *a = S->lb_a;
+  if (threshold) *threshold = S->lb_threshold;
+  if (since_du) *since_du = S->lb_since_du;
+  if (since_dfu) *since_dfu = S->lb_since_dfu;
   return NK_OK;
 }
 extern "C" int nk_solver_get_scalars(nk_solver *S, double *fnorm_inf, double *trust_region, double *eta) {
