@@ -90,8 +90,13 @@ typedef enum {
  * inverse Jacobian is a·I + U Vᵀ with `lb_threshold` columns, good-Broyden updates, NoChangeInStateReset(nsteps = 3). Needs
  * only the residual: no Jacobian, no JVP, no linear solve — nk_options.linsolve, the Krylov, forcing, preconditioner and
  * line-search fields are not read (linesearch != 0 is NK_E_INVALID: the line-search form is not built). One rank. */
+/* NK_ALG_DFSANE: DFSane (lib/NonlinearSolveSpectralMethods: GeneralizedDFSane with the RobustNonMonotone line search): the step
+ * is −ασ f with the spectral coefficient σ = ⟨δu,δu⟩/⟨δu,δf⟩. Needs only the residual, like algorithm 5: no Jacobian, no linear
+ * solve; nk_options.linesearch != 0 (the search is part of the method), a forcing term or more than one rank are NK_E_INVALID.
+ * A failed line search ends the solve with NK_RET_INTERNAL_LINESEARCH_FAILED. recompute_jacobian is ignored. */
 typedef enum { NK_ALG_NEWTON_RAPHSON = 0, NK_ALG_TRUST_REGION = 1, NK_ALG_GAUSS_NEWTON = 2,
-               NK_ALG_LEVENBERG_MARQUARDT = 3, NK_ALG_PSEUDO_TRANSIENT = 4, NK_ALG_LIMITED_MEMORY_BROYDEN = 5 } nk_algorithm;
+               NK_ALG_LEVENBERG_MARQUARDT = 3, NK_ALG_PSEUDO_TRANSIENT = 4, NK_ALG_LIMITED_MEMORY_BROYDEN = 5,
+               NK_ALG_DFSANE = 6 } nk_algorithm;
 
 /* which operator the Krylov solver sees as A (lib/NonlinearSolveBase/src/jacobian.jl:43-47,90-102) */
 typedef enum {
@@ -270,6 +275,16 @@ typedef struct {
   int32_t lb_max_resets;                /* [3]    the reset that brings the count to this ends the solve (ConvergenceFailure) */
   double  lb_reset_tolerance;           /* [eps^(3/4)] NoChangeInStateReset's tolerance (reset_conditions.jl:34)              */
   double  lb_alpha;                     /* [nothing] J⁻¹ starts as I/alpha; default alpha = 2‖fu‖₂/max(‖u‖₂, 1), 1 if ‖fu‖₂ < 1e-5 */
+  /* --- DFSane (lib/NonlinearSolveSpectralMethods/src/dfsane.jl:21-35); a value <= 0 selects the default */
+  double  sane_sigma_min;               /* [1e-10] |σ| outside [sigma_min, sigma_max] is replaced by clamp(1/‖f‖₂, 1, 1e5)     */
+  double  sane_sigma_max;               /* [1e10]                                                                              */
+  double  sane_sigma_1;                 /* [0 = nothing] the first σ; nothing: ⟨u,u⟩/⟨u,f⟩ (then the bounds test). Any sign.   */
+  int32_t sane_M;                       /* [10]   length of the merit history, 1..32 (more: NK_E_INVALID)                      */
+  double  sane_gamma;                   /* [1e-4]                                                                              */
+  double  sane_tau_min;                 /* [0.1]                                                                               */
+  double  sane_tau_max;                 /* [0.5]                                                                               */
+  int32_t sane_n_exp;                   /* [2]    merit ‖f‖₂^n_exp, 1 or 2 (else NK_E_INVALID)                                 */
+  int32_t sane_max_inner_iterations;    /* [100]  (minus trial, plus trial) pairs of one line search before it has failed      */
 } nk_options;
 
 /* in-place callbacks of a user problem: NonlinearFunction{true}(f!; jvp, vjp, jac)
@@ -638,6 +653,12 @@ int nk_solver_get_retcode(nk_solver *S, int *retcode, int *nsteps, int *force_st
  * threshold in effect, and the reset test's two counters. Any pointer may be NULL. NK_E_INVALID for another algorithm. */
 int nk_solver_get_lbroyden_state(nk_solver *S, int *nresets, int *idx, double *a, int *threshold, int *since_du,
                                  int *since_dfu);
+/* NK_ALG_DFSANE: the spectral coefficient σ the next step starts from, the step length of the last step with its sign (+α₊ or
+ * −α₋; 0 before the first step, NaN after a failed search), the residual evaluations of the last line search and of all of
+ * them, the history length M and the merit history itself (`history`: room for 32 doubles, M are written). Any pointer may
+ * be NULL. NK_E_INVALID for another algorithm. */
+int nk_solver_get_dfsane_state(nk_solver *S, double *sigma, double *alpha, int *trials, int *total_trials, int *M,
+                               double *history);
 int nk_solver_get_scalars(nk_solver *S, double *fnorm_inf, double *trust_region, double *eta);
 int nk_solver_get_trace(nk_solver *S, nk_trace_entry *rows, int capacity, int *nrows);
 /* one call: init + solve + results (what SciMLBase.__solve of the extension algorithm does) */

@@ -520,6 +520,10 @@ Base.@kwdef mutable struct NKOptions
     gmres_sstep::Int32 = 0; gmres_sstep_basis::Int32 = 0
     precond_kind::Int32 = 0; precond_side::Int32 = 1
     lb_threshold::Int32 = 0; lb_max_resets::Int32 = 0; lb_reset_tolerance::Float64 = 0.0; lb_alpha::Float64 = 0.0
+    sane_sigma_min::Float64 = 0.0; sane_sigma_max::Float64 = 0.0; sane_sigma_1::Float64 = 0.0
+    sane_M::Int32 = 0
+    sane_gamma::Float64 = 0.0; sane_tau_min::Float64 = 0.0; sane_tau_max::Float64 = 0.0
+    sane_n_exp::Int32 = 0; sane_max_inner_iterations::Int32 = 0
 end
 
 const RETCODES = (ReturnCode.Default, ReturnCode.Success, ReturnCode.MaxIters, ReturnCode.Unstable,
@@ -529,7 +533,7 @@ const RETCODES = (ReturnCode.Default, ReturnCode.Success, ReturnCode.MaxIters, R
 function SciMLBase.__solve(prob::NonlinearProblem, alg::MI355XNewtonKrylovAlg, args...;
         abstol = nothing, reltol = nothing, maxiters = 1000, maxtime = nothing, termination_condition = nothing,
         kwargs...)
-    algorithm = alg.method === :LimitedMemoryBroyden ? 5 : alg.method === :PseudoTransient ? 4 : alg.method === :LevenbergMarquardt ? 3 : alg.method === :GaussNewton ? 2 : (alg.trust_region ? 1 : 0)
+    algorithm = alg.method === :DFSane ? 6 : alg.method === :LimitedMemoryBroyden ? 5 : alg.method === :PseudoTransient ? 4 : alg.method === :LevenbergMarquardt ? 3 : alg.method === :GaussNewton ? 2 : (alg.trust_region ? 1 : 0)
     o = NKOptions(; algorithm = algorithm,
         linsolve = alg.direct ? 2 : ((alg.concrete_jac || algorithm == 3) ? 1 : 0),
         lm_disable_geodesic = alg.lm_disable_geodesic ? 1 : 0, lm_damping_initial = alg.lm_damping_initial,

@@ -23,6 +23,7 @@ RET_NAMES = ["Default", "Success", "MaxIters", "Unstable", "Stalled", "InternalL
 PROBLEM_QUADRATIC, PROBLEM_BRATU2D, PROBLEM_BRUSSELATOR2D, PROBLEM_USER = 1, 2, 3, 100
 ALG_NEWTON_RAPHSON, ALG_TRUST_REGION, ALG_GAUSS_NEWTON, ALG_LEVENBERG_MARQUARDT, ALG_PSEUDO_TRANSIENT = 0, 1, 2, 3, 4
 ALG_LIMITED_MEMORY_BROYDEN = 5
+ALG_DFSANE = 6
 LINSOLVE_GMRES_MATFREE, LINSOLVE_GMRES_CSR, LINSOLVE_BANDED_LU = 0, 1, 2
 ORTHO_MGS, ORTHO_CGS2, ORTHO_CGS, ORTHO_DCGS2, ORTHO_DCGS2_1R, ORTHO_SSTEP = 0, 1, 2, 3, 4, 5
 FORCING_NONE, FORCING_EW2 = 0, 1
@@ -85,6 +86,10 @@ class Options(C.Structure):
         ("precond_side", C.c_int32),
         ("lb_threshold", C.c_int32), ("lb_max_resets", C.c_int32),
         ("lb_reset_tolerance", C.c_double), ("lb_alpha", C.c_double),
+        ("sane_sigma_min", C.c_double), ("sane_sigma_max", C.c_double), ("sane_sigma_1", C.c_double),
+        ("sane_M", C.c_int32),
+        ("sane_gamma", C.c_double), ("sane_tau_min", C.c_double), ("sane_tau_max", C.c_double),
+        ("sane_n_exp", C.c_int32), ("sane_max_inner_iterations", C.c_int32),
     ]
 
 
@@ -250,6 +255,8 @@ SIGNATURES = {
     "nk_solver_get_scalars": (_I, [_P, C.POINTER(_D), C.POINTER(_D), C.POINTER(_D)]),
     "nk_solver_get_lbroyden_state": (_I, [_P, C.POINTER(_I), C.POINTER(_I), C.POINTER(_D), C.POINTER(_I), C.POINTER(_I),
                                          C.POINTER(_I)]),
+    "nk_solver_get_dfsane_state": (_I, [_P, C.POINTER(_D), C.POINTER(_D), C.POINTER(_I), C.POINTER(_I), C.POINTER(_I),
+                                       C.POINTER(_D)]),
     "nk_solver_get_trace": (_I, [_P, C.POINTER(TraceEntry), _I, C.POINTER(_I)]),
     "nk_newton_solve": (_I, [_P, _P, _I, C.POINTER(Options), _P, _P, C.POINTER(Stats), C.POINTER(_I)]),
     "nk_dot": (_I, [_P, _L, _P, _P, C.POINTER(_D)]),

@@ -876,6 +876,30 @@ class LimitedMemoryBroyden:  # lib/NonlinearSolveQuasiNewton/src/lbroyden.jl:20-
                 f"reset_tolerance={self.reset_tolerance}, alpha={self.alpha})")
 
 
+class DFSane:  # lib/NonlinearSolveSpectralMethods/src/dfsane.jl:21-35
+    """DFSane(; sigma_min = 1e-10, sigma_max = 1e10, sigma_1 = nothing, M = 10, gamma = 1e-4, tau_min = 0.1, tau_max = 0.5,
+    n_exp = 2, max_inner_iterations = 100): the spectral residual method, step −ασ f with σ = ⟨δu,δu⟩/⟨δu,δf⟩ and the
+    RobustNonMonotone line search for α. Needs only the residual — a problem without jvp / jac is accepted. `sigma_1 = None`
+    is what the reference's DFSane hands to GeneralizedDFSane (σ = ⟨u,u⟩/⟨u,f⟩ at the start); a number is taken as the first
+    σ. M is 1..32, n_exp 1 or 2; `eta_strategy` is fixed at f₁/k²."""
+    linsolve = None
+    name = "DFSane"
+
+    def __init__(self, sigma_min: float = 1e-10, sigma_max: float = 1e10, sigma_1: Optional[float] = None, M: int = 10,
+                 gamma: float = 1e-4, tau_min: float = 0.1, tau_max: float = 0.5, n_exp: int = 2,
+                 max_inner_iterations: int = 100, eta_strategy=None):
+        if eta_strategy is not None:
+            raise NotImplementedError("DFSane(eta_strategy=…): only the default f₁/k² is built")
+        self.sigma_min, self.sigma_max, self.sigma_1 = float(sigma_min), float(sigma_max), sigma_1
+        self.M, self.n_exp, self.max_inner_iterations = int(M), int(n_exp), int(max_inner_iterations)
+        self.gamma, self.tau_min, self.tau_max = float(gamma), float(tau_min), float(tau_max)
+
+    def __repr__(self):
+        return (f"DFSane(sigma_min={self.sigma_min}, sigma_max={self.sigma_max}, sigma_1={self.sigma_1}, M={self.M}, "
+                f"gamma={self.gamma}, tau_min={self.tau_min}, tau_max={self.tau_max}, n_exp={self.n_exp}, "
+                f"max_inner_iterations={self.max_inner_iterations})")
+
+
 @dataclass
 class _TerminationMode:
     """SciMLBase termination modes (lib/NonlinearSolveBase/src/termination_conditions.jl); `internalnorm` is
@@ -967,6 +991,20 @@ def _options(alg, abstol, reltol, maxiters, maxtime, store_trace, termination_kw
         o.lb_threshold, o.lb_max_resets = alg.threshold, alg.max_resets
         o.lb_reset_tolerance = 0.0 if alg.reset_tolerance is None else float(alg.reset_tolerance)
         o.lb_alpha = 0.0 if alg.alpha is None else float(alg.alpha)
+        ls = KrylovJL_GMRES()
+        o.linsolve = L.LINSOLVE_GMRES_MATFREE
+    elif isinstance(alg, DFSane):   # likewise: the residual and nothing else
+        o.algorithm = L.ALG_DFSANE
+        if alg.M < 1 or alg.n_exp < 1 or alg.max_inner_iterations < 1:
+            raise ValueError("DFSane: M, n_exp and max_inner_iterations must be positive")
+        if not (alg.sigma_min > 0 and alg.sigma_max > 0 and alg.gamma > 0 and alg.tau_min > 0 and alg.tau_max > 0):
+            raise ValueError("DFSane: sigma_min, sigma_max, gamma, tau_min and tau_max must be positive")
+        if alg.sigma_1 is not None and not (float(alg.sigma_1) != 0.0):
+            raise ValueError("DFSane: sigma_1 = 0 is no spectral coefficient (None selects ⟨u,u⟩/⟨u,f⟩)")
+        o.sane_sigma_min, o.sane_sigma_max = alg.sigma_min, alg.sigma_max
+        o.sane_sigma_1 = 0.0 if alg.sigma_1 is None else float(alg.sigma_1)
+        o.sane_M, o.sane_n_exp, o.sane_max_inner_iterations = alg.M, alg.n_exp, alg.max_inner_iterations
+        o.sane_gamma, o.sane_tau_min, o.sane_tau_max = alg.gamma, alg.tau_min, alg.tau_max
         ls = KrylovJL_GMRES()
         o.linsolve = L.LINSOLVE_GMRES_MATFREE
     elif ls is None:
@@ -1151,6 +1189,17 @@ class FirstOrderCache:
         check(L.lib().nk_solver_get_lbroyden_state(self._h, C.byref(r), C.byref(i), C.byref(a), C.byref(t), C.byref(d),
                                                    C.byref(f)))
         return dict(nresets=r.value, idx=i.value, a=a.value, threshold=t.value, since_du=d.value, since_dfu=f.value)
+
+    @property
+    def dfsane_state(self) -> dict:
+        """DFSane: the spectral coefficient σ the next step starts from, the last step's length with its sign (+α₊ or −α₋; NaN
+        after a failed line search), the residual evaluations of the last line search and of all of them, M and the merit
+        history (M values)"""
+        s, a = C.c_double(), C.c_double()
+        t, tt, m = C.c_int(), C.c_int(), C.c_int()
+        h = (C.c_double * 32)()
+        check(L.lib().nk_solver_get_dfsane_state(self._h, C.byref(s), C.byref(a), C.byref(t), C.byref(tt), C.byref(m), h))
+        return dict(sigma=s.value, alpha=a.value, trials=t.value, total_trials=tt.value, M=m.value, history=list(h[:m.value]))
 
     @property
     def fnorm_inf(self):

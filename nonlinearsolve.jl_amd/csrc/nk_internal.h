@@ -883,6 +883,17 @@ double *nk_lb_scalars(nk_lbroyden *W);
 int nk_lb_combine(nk_lbroyden *W, double a, const double *fu_new);
 double nk_lb_pass_bytes(int64_t n, int m);
 
+// ----------------------------------------------------------------------------- DFSane (nk_qn.hip)
+// the two launches a trial of the RobustNonMonotone line search makes beside the residual (the driver is nk_solver.hip: sane_step)
+struct nk_sane;
+int nk_sane_create(nk_ctx *ctx, int64_t n, nk_sane **out);
+void nk_sane_destroy(nk_sane *W);
+int nk_sane_restart(nk_sane *W);
+int nk_sane_trial(nk_sane *W, double sigma, double a, const double *x, const double *f, double *xt);   // x_t = x + a·(−(σ·f))
+int nk_sane_reduce(nk_sane *W, const double *ft, const double *f);
+double *nk_sane_scalars(nk_sane *W);   // device: [0] Σf_t², [1] max|f_t| (NaN-propagating), [2] Σ f·(f_t − f)
+double nk_sane_pass_bytes(int64_t n);
+
 // ----------------------------------------------------------------------------- misc helpers
 // The library's "synchronous" memsets and copies, ORDERED ON THE CONTEXT'S STREAM. hipMemset / hipMemcpy run on the null stream:
 // a caller's stream created with hipStreamNonBlocking (PyTorch's, AMDGPU.jl's) is not ordered against it, and hipMemset of device

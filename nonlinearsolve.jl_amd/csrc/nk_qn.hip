@@ -400,3 +400,141 @@ int nk_lb_combine(nk_lbroyden *W, double a, const double *fu_new) {
 }
 // algorithmic bytes of the two passes over U and V for m active columns (what tools/lbroyden_bench.py divides by)
 double nk_lb_pass_bytes(int64_t n, int m) { return ((16.0 * m + 24.0) + (16.0 * m + 40.0)) * (double)n; }
+
+// ============================================================================= DFSane (nk_solver.hip: sane_step)
+// GeneralizedDFSane with RobustNonMonotoneLineSearch (lib/NonlinearSolveSpectralMethods/src/solve.jl:201-259, the line search as
+// lib/SimpleNonlinearSolve/src/dfsane.jl:114-144 states it). The whole state is u, fu and a handful of host scalars. A trial of
+// the line search is the residual kernel plus
+//   k_sane_trial    x_t = x + a·(−(σ·f)), a = α₊ or −α₋: the two products are rounded one after the other, as `d = −σ f` and
+//                   `x + α d` are in the literal form, so the iterate carries the literal form's bits. 16 B read, 8 B written.
+//   k_sane_reduce   ONE read of f_t and f: Σf_t², max|f_t| (NaN-propagating) and Σ f·(f_t − f), the last accumulated elementwise.
+// With δu = c·f, c = −aσ: ⟨δu,δu⟩ = c²·Σf², ⟨δu,δf⟩ = c·Σ f(f_t − f), ‖δu‖₂ = |c|·‖f‖₂ — acceptance, termination and the spectral
+// update need nothing else, so no pass reads u to form δu or δf and the caches of the literal form are pointer swaps.
+enum { SANE_SS = 0, SANE_MAX = 1, SANE_DOT = 2, SANE_NSCAL = 3 };
+
+struct nk_sane {
+  nk_ctx *ctx = nullptr;
+  int64_t n = 0;
+  double *sc = nullptr, *part = nullptr;
+  unsigned int *ticket = nullptr;
+};
+
+__global__ __launch_bounds__(NK_BLOCK) void k_sane_trial(int64_t n, double sigma, double a, const double *__restrict__ x,
+                                                         const double *__restrict__ f, double *__restrict__ xt) {
+  const int64_t npair = n >> 1, stride = (int64_t)gridDim.x * NK_BLOCK;
+  const double2 *x2 = reinterpret_cast<const double2 *>(x), *f2 = reinterpret_cast<const double2 *>(f);
+  double2 *t2 = reinterpret_cast<double2 *>(xt);
+  for (int64_t i = (int64_t)blockIdx.x * NK_BLOCK + threadIdx.x; i < npair; i += stride) {
+    const double2 xv = x2[i], fv = f2[i];
+    t2[i] = make_double2(xv.x + a * (-(sigma * fv.x)), xv.y + a * (-(sigma * fv.y)));
+  }
+  if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) {  // odd tail
+    const int64_t i = n - 1;
+    xt[i] = x[i] + a * (-(sigma * f[i]));
+  }
+}
+
+struct sane_reduce_args {
+  int64_t n;
+  const double *ft, *f;   // the trial residual, the residual of the iterate the search started from
+  double *part, *sc;
+  unsigned int *ticket;
+};
+__global__ __launch_bounds__(NK_BLOCK) void k_sane_reduce(sane_reduce_args a) {
+  constexpr int NS = SANE_NSCAL;
+  __shared__ double sm[4 * NS + 1];
+  double ss = 0.0, mx = 0.0, dt = 0.0;
+  const int64_t npair = a.n >> 1, stride = (int64_t)gridDim.x * NK_BLOCK;
+  const double2 *t2 = reinterpret_cast<const double2 *>(a.ft), *f2 = reinterpret_cast<const double2 *>(a.f);
+  for (int64_t i = (int64_t)blockIdx.x * NK_BLOCK + threadIdx.x; i < npair; i += stride) {
+    const double2 tv = t2[i], fv = f2[i];
+    ss += tv.x * tv.x + tv.y * tv.y;
+    mx = nk_nanmax(mx, nk_nanmax(fabs(tv.x), fabs(tv.y)));
+    dt += fv.x * (tv.x - fv.x) + fv.y * (tv.y - fv.y);
+  }
+  if ((a.n & 1) && blockIdx.x == 0 && threadIdx.x == 0) {  // odd tail
+    const int64_t i = a.n - 1;
+    const double tv = a.ft[i], fv = a.f[i];
+    ss += tv * tv;
+    mx = nk_nanmax(mx, fabs(tv));
+    dt += fv * (tv - fv);
+  }
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+  {
+    const double s = lb_wave_sum(ss), m = lb_wave_nanmax(mx), d = lb_wave_sum(dt);
+    if (lane == 0) { sm[wid * NS + SANE_SS] = s; sm[wid * NS + SANE_MAX] = m; sm[wid * NS + SANE_DOT] = d; }
+  }
+  __syncthreads();
+  if ((int)threadIdx.x < NS) {
+    const int s = threadIdx.x;
+    const double p0 = sm[s], p1 = sm[NS + s], p2 = sm[2 * NS + s], p3 = sm[3 * NS + s];
+    a.part[(size_t)s * gridDim.x + blockIdx.x] = (s == SANE_MAX) ? nk_nanmax(nk_nanmax(p0, p1), nk_nanmax(p2, p3)) : (p0 + p1) + (p2 + p3);
+  }
+  if (!lb_arrive_last(a.ticket, gridDim.x, &sm[4 * NS])) return;
+  // ---- the last workgroup: slot s is combined by wavefront s, workgroup partials in ascending order per lane
+  const int nwg = gridDim.x;
+  if (wid < NS) {
+    const bool is_max = wid == SANE_MAX;
+    const double *p = a.part + (size_t)wid * nwg;
+    double v = 0.0;
+    for (int b = lane; b < nwg; b += 64) v = is_max ? nk_nanmax(v, p[b]) : v + p[b];
+    v = is_max ? lb_wave_nanmax(v) : lb_wave_sum(v);
+    if (lane == 0) a.sc[wid] = v;
+  }
+  if (threadIdx.x == 0) *a.ticket = 0u;   // (for the next launch: the kernel boundary publishes it)
+}
+
+static int sane_grid(const nk_sane *W) {   // sized to the CUs: at most two workgroups each
+  int cap = 2 * W->ctx->num_cus;
+  if (cap > LB_MAX_GRID) cap = LB_MAX_GRID;
+  if (cap < 1) cap = 1;
+  return nk_grid_for(W->n >> 1, NK_BLOCK * 2, cap);
+}
+
+int nk_sane_create(nk_ctx *ctx, int64_t n, nk_sane **out) {
+  NK_REQUIRE(ctx && out && n > 0, "bad argument");
+  nk_sane *W = new nk_sane();
+  auto guard = nk_make_guard(W, [](nk_sane *w) { nk_sane_destroy(w); });
+  W->ctx = ctx;
+  W->n = n;
+  NK_TRY(nk_dev_alloc(&W->sc, (size_t)SANE_NSCAL + 1));
+  NK_TRY(nk_dev_alloc(&W->part, (size_t)SANE_NSCAL * LB_MAX_GRID));
+  NK_TRY(nk_dev_alloc(&W->ticket, (size_t)1));
+  NK_HIP(nk_memset(ctx, W->sc, 0, (SANE_NSCAL + 1) * sizeof(double)));
+  NK_TRY(nk_sane_restart(W));
+  *out = guard.release();
+  return NK_OK;
+}
+void nk_sane_destroy(nk_sane *W) {
+  if (!W) return;
+  hipFree(W->sc); hipFree(W->part); hipFree(W->ticket);
+  delete W;
+}
+// a new solve: the ticket is zeroed, in stream order
+int nk_sane_restart(nk_sane *W) {
+  NK_HIP(nk_memset(W->ctx, W->ticket, 0, sizeof(unsigned int)));
+  return NK_OK;
+}
+// x_t = x + a·(−(σ·f)); out of place (x stays intact)
+int nk_sane_trial(nk_sane *W, double sigma, double a, const double *x, const double *f, double *xt) {
+  nk_ctx *ctx = W->ctx;
+  NK_REQUIRE(xt != x && xt != f, "DFSane: the trial point is written out of place");
+  const int grid = nk_grid_for(W->n >> 1, NK_BLOCK * 2, 8 * (ctx->num_cus > 0 ? ctx->num_cus : 1));
+  nk_prof_scope prof_(ctx, NK_K_NEWTON_UPDATE, 24.0 * (double)W->n);
+  NK_LAUNCH(ctx, k_sane_trial, dim3(grid), dim3(NK_BLOCK), W->n, sigma, a, x, f, xt);
+  NK_HIP(hipGetLastError());
+  return NK_OK;
+}
+// one read of f_t and f; the three scalars the host fetches are nk_sane_scalars()[0..2]: Σf_t², max|f_t|, Σ f·(f_t − f)
+int nk_sane_reduce(nk_sane *W, const double *ft, const double *f) {
+  nk_ctx *ctx = W->ctx;
+  const int grid = sane_grid(W);
+  sane_reduce_args a{W->n, ft, f, W->part, W->sc, W->ticket};
+  nk_prof_scope prof_(ctx, NK_K_MULTIDOT, 16.0 * (double)W->n);
+  NK_LAUNCH(ctx, k_sane_reduce, dim3(grid), dim3(NK_BLOCK), a);
+  NK_HIP(hipGetLastError());
+  return NK_OK;
+}
+double *nk_sane_scalars(nk_sane *W) { return W->sc; }
+// algorithmic bytes of the two passes of one trial (what tools/dfsane_bench.py divides by)
+double nk_sane_pass_bytes(int64_t n) { return 40.0 * (double)n; }

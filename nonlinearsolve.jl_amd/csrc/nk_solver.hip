@@ -95,6 +95,12 @@ struct nk_solver {
   double lb_a = 1.0, lb_tol = 0.0, lb_u_ss = 0.0;
   int lb_threshold = 0, lb_max_resets = 0, lb_nresets = 0, lb_since_du = 0, lb_since_dfu = 0;
   bool lb_flag_du = false, lb_flag_dfu = false;   // the reset test's any(…) flags for the NEXT step (left by this step's reduce pass)
+  // DFSane (nk_qn.hip): everything but u and fu is host scalars. `sane_ss` is Σfu² of the current residual (the reduce pass of
+  // the accepted trial left it), `sane_fn` the merit ‖fu‖₂^n_exp, `sane_hist` the last M merits; trials write into fu_trial
+  nk_sane *sane = nullptr;
+  double sane_sigma = 0.0, sane_alpha = 0.0, sane_ss = 0.0, sane_fn = 0.0, sane_f1 = 0.0, sane_hist[32] = {0};
+  double sane_smin = 0.0, sane_smax = 0.0, sane_gamma = 0.0, sane_tmin = 0.0, sane_tmax = 0.0;
+  int sane_M = 0, sane_nexp = 2, sane_max_inner = 0, sane_k = 0, sane_trials = 0, sane_total_trials = 0;
 };
 
 // u_new = u + sign·du (out of place: the old iterate stays intact in its buffer) ; partial Σ (u_new − u_old)²  (the stall
@@ -258,6 +264,15 @@ extern "C" int nk_options_default(nk_options *o) {
   o->lb_max_resets = 3;
   o->lb_reset_tolerance = 0.0;
   o->lb_alpha = 0.0;
+  o->sane_sigma_min = 1.0e-10;  // DFSane() (dfsane.jl:21-27); sigma_1: 0 = `nothing`, as GeneralizedDFSane receives it (:33)
+  o->sane_sigma_max = 1.0e10;
+  o->sane_sigma_1 = 0.0;
+  o->sane_M = 10;
+  o->sane_gamma = 1.0e-4;
+  o->sane_tau_min = 0.1;
+  o->sane_tau_max = 0.5;
+  o->sane_n_exp = 2;
+  o->sane_max_inner_iterations = 100;
   return NK_OK;
 }
 
@@ -272,6 +287,8 @@ static bool normal_form(const nk_solver *S) {
 static bool is_lm(const nk_solver *S) { return S->o.algorithm == NK_ALG_LEVENBERG_MARQUARDT; }
 static bool is_pt(const nk_solver *S) { return S->o.algorithm == NK_ALG_PSEUDO_TRANSIENT; }
 static bool is_lb(const nk_solver *S) { return S->o.algorithm == NK_ALG_LIMITED_MEMORY_BROYDEN; }
+static bool is_sane(const nk_solver *S) { return S->o.algorithm == NK_ALG_DFSANE; }
+static bool residual_only(const nk_solver *S) { return is_lb(S) || is_sane(S); }   // no Jacobian, no linear solve
 static bool concrete(const nk_solver *S) { return S->o.linsolve != NK_LINSOLVE_GMRES_MATFREE; }
 static bool direct(const nk_solver *S) { return S->o.linsolve == NK_LINSOLVE_BANDED_LU; }
 
@@ -677,6 +694,105 @@ static int lb_step(nk_solver *S, int recompute) {
   return nk_lb_combine(S->lb, S->lb_a, S->fu);
 }
 
+// ---- DFSane (lib/NonlinearSolveSpectralMethods/src/solve.jl:127-259; the line search as SimpleNonlinearSolve/src/dfsane.jl:114-144)
+static double jl_clamp(double x, double lo, double hi) { return x > hi ? hi : (x < lo ? lo : x); }   // NaN stays NaN
+static double sane_merit(const nk_solver *S, double ss) {   // L2_NORM(f)^n_exp
+  const double nrm = sqrt(ss);
+  return S->sane_nexp == 1 ? nrm : nrm * nrm;
+}
+// the spectral parameter's bounds test (solve.jl:171-174, :245-249)
+static double sane_bounded(const nk_solver *S, double sigma, double ss) {
+  if (!(S->sane_smin <= fabs(sigma) && fabs(sigma) <= S->sane_smax)) return jl_clamp(1.0 / sqrt(ss), 1.0, 1.0e5);
+  return sigma;
+}
+// init and reinit!: σ from (u0, f(u0)) or sigma_1, the history filled with f₁, the step counter of η at 0
+static int sane_start(nk_solver *S) {
+  NK_TRY(nk_sane_restart(S->sane));
+  NK_TRY(nk_blas_sumsq(S->ctx, S->n, S->fu, slot(S, 0)));
+  NK_TRY(nk_blas_sumsq(S->ctx, S->n, S->u, slot(S, 1)));
+  NK_TRY(nk_blas_dot(S->ctx, S->n, S->u, S->fu, slot(S, 2)));
+  double v[3];
+  NK_TRY(fetch(S, 3, v));
+  S->sane_ss = v[0];
+  S->sane_fn = S->sane_f1 = sane_merit(S, v[0]);
+  for (int i = 0; i < S->sane_M; ++i) S->sane_hist[i] = S->sane_f1;
+  S->sane_sigma = S->o.sane_sigma_1 != 0.0 ? S->o.sane_sigma_1 : sane_bounded(S, v[1] / v[2], v[0]);
+  S->sane_alpha = 0.0;
+  S->sane_k = S->sane_trials = S->sane_total_trials = 0;
+  return NK_OK;
+}
+static int check_and_update(nk_solver *S, double step_norm);
+// one trial: x_t = u + a·(−σ fu), f_t = f(x_t), one reduce pass, one fetch: v = {Σf_t², max|f_t|, Σ fu·(f_t − fu)}
+static int sane_trial(nk_solver *S, double a, double *xt, double v[3]) {
+  NK_TRY(nk_sane_trial(S->sane, S->sane_sigma, a, S->u, S->fu, xt));
+  nk_problem_invalidate(S->P);
+  NK_TRY(nk_problem_residual_dev(S->P, xt, S->fu_trial));
+  S->stats.nf++;
+  S->sane_trials++;
+  S->sane_total_trials++;
+  NK_TRY(nk_sane_reduce(S->sane, S->fu_trial, S->fu));
+  return nk_scalars_to_host(S->ctx, nk_sane_scalars(S->sane), 3, v);
+}
+static int sane_step(nk_solver *S) {
+  const int k = ++S->sane_k;                     // the outer step's number: η_k = f₁/k²
+  const double eta = S->sane_f1 / ((double)k * (double)k);
+  double fbar = S->sane_hist[0];                 // maximum(history): NaN propagates
+  for (int i = 1; i < S->sane_M; ++i) fbar = (fbar != fbar || S->sane_hist[i] != S->sane_hist[i]) ? NAN : fmax(fbar, S->sane_hist[i]);
+  const double fn = S->sane_fn, gam = S->sane_gamma;
+  double ap = 1.0, am = 1.0, a = NAN, fnew, v[3];
+  double *xt = spare_u(S);   // out of place: u and a retained best iterate stay intact through every trial
+  S->sane_trials = 0;
+  NK_TRY(sane_trial(S, ap, xt, v));
+  fnew = sane_merit(S, v[0]);
+  for (int inner = 0;;) {
+    if (fnew <= (fbar + eta) - gam * (ap * ap) * fn) { a = ap; break; }
+    const double atp = (ap * ap) * fn / (fnew + (2.0 * ap - 1.0) * fn);
+    NK_TRY(sane_trial(S, -am, xt, v));
+    fnew = sane_merit(S, v[0]);
+    if (fnew <= (fbar + eta) - gam * (am * am) * fn) { a = -am; break; }
+    const double atm = (am * am) * fn / (fnew + (2.0 * am - 1.0) * fn);
+    ap = jl_clamp(atp, S->sane_tmin * ap, S->sane_tmax * ap);
+    am = jl_clamp(atm, S->sane_tmin * am, S->sane_tmax * am);
+    NK_TRY(sane_trial(S, ap, xt, v));
+    fnew = sane_merit(S, v[0]);
+    if (++inner >= S->sane_max_inner) break;     // the search has failed (its last trial is not looked at)
+  }
+  S->sane_alpha = a;
+  if (a != a) {
+    S->retcode = NK_RET_INTERNAL_LINESEARCH_FAILED;
+    S->force_stop = true;
+    return NK_OK;
+  }
+  // the accepted trial becomes the iterate: pointer swaps, no copies
+  const double c = -(a * S->sane_sigma);         // δu = c·fu_prev
+  const double ss_prev = S->sane_ss;
+  S->u = xt;
+  S->u_version++;
+  { double *t = S->fu; S->fu = S->fu_trial; S->fu_trial = t; }
+  S->fnorm_inf = v[1];
+  S->fnorm2 = sqrt(v[0]);
+  S->sane_ss = v[0];
+  S->sane_fn = fnew;
+  const double step_norm = fabs(c) * sqrt(ss_prev);
+  // the spectral update and the history, from the scalars of the accepted trial (before a *Best mode may roll the iterate back)
+  S->sane_sigma = sane_bounded(S, ((c * c) * ss_prev) / (c * v[2]), v[0]);
+  S->sane_hist[(k - 1) % S->sane_M] = fnew;      // history[mod1(k, M)]
+  NK_TRY(check_and_update(S, step_norm));
+  if (S->o.store_trace) {
+    nk_trace_entry e;
+    memset(&e, 0, sizeof(e));
+    e.iter = S->nsteps + 1;
+    e.accepted = 1;
+    e.fnorm_inf = S->fnorm_inf;
+    e.step_norm2 = step_norm;
+    e.eta = NAN;
+    e.trust_region = NAN;
+    e.rho = NAN;
+    S->trace.push_back(e);
+  }
+  return NK_OK;
+}
+
 // ---- init
 static int solver_start(nk_solver *S, bool first = true) {  // everything after u has been set (first = init, else reinit!)
   nk_ctx *ctx = S->ctx;
@@ -722,6 +838,7 @@ static int solver_start(nk_solver *S, bool first = true) {  // everything after 
     if (S->G) NK_TRY(nk_gmres_set_shift(S->G, 0.0));
   }
   if (is_lb(S)) NK_TRY(lb_start(S));
+  if (is_sane(S)) NK_TRY(sane_start(S));
   if (is_lm(S)) {  // init / reinit! of the damping cache, the LM trust region and the geodesic cache
     S->lm_lam = S->o.lm_damping_initial;                    // levenberg_marquardt.jl:72-89,119-131
     S->lm_lam_factor = S->o.lm_damping_increase_factor;
@@ -742,7 +859,15 @@ extern "C" int nk_solver_init(nk_problem *P, const double *u0, int memspace, con
   NK_HIP(hipSetDevice(ctx->device));
   NK_REQUIRE(opts->algorithm == NK_ALG_NEWTON_RAPHSON || opts->algorithm == NK_ALG_TRUST_REGION ||
                  opts->algorithm == NK_ALG_GAUSS_NEWTON || opts->algorithm == NK_ALG_LEVENBERG_MARQUARDT ||
-                 opts->algorithm == NK_ALG_PSEUDO_TRANSIENT || opts->algorithm == NK_ALG_LIMITED_MEMORY_BROYDEN, "bad algorithm");
+                 opts->algorithm == NK_ALG_PSEUDO_TRANSIENT || opts->algorithm == NK_ALG_LIMITED_MEMORY_BROYDEN ||
+                 opts->algorithm == NK_ALG_DFSANE, "bad algorithm");
+  if (opts->algorithm == NK_ALG_DFSANE) {
+    NK_REQUIRE(opts->linesearch == 0, "DFSane: the RobustNonMonotone line search is part of the method (linesearch must be 0)");
+    NK_REQUIRE(opts->forcing == NK_FORCING_NONE, "DFSane takes no forcing term: it solves no linear system");
+    NK_REQUIRE(opts->sane_M <= 32, "DFSane: M = %d is outside 1..32", opts->sane_M);
+    NK_REQUIRE(opts->sane_n_exp <= 2, "DFSane: n_exp = %d is neither 1 nor 2", opts->sane_n_exp);
+    NK_REQUIRE(ctx->nranks == 1, "DFSane runs on one rank");
+  }
   if (opts->algorithm == NK_ALG_LIMITED_MEMORY_BROYDEN) {
     NK_REQUIRE(opts->linesearch == 0, "LimitedMemoryBroyden: the line-search form is not built (linesearch must be 0)");
     NK_REQUIRE(opts->lb_threshold <= 32, "LimitedMemoryBroyden: threshold %d is outside 1..32", opts->lb_threshold);
@@ -765,7 +890,7 @@ extern "C" int nk_solver_init(nk_problem *P, const double *u0, int memspace, con
                  opts->linsolve == NK_LINSOLVE_BANDED_LU,
              "unknown linsolve %d", opts->linsolve);
   NK_REQUIRE(!(opts->linsolve == NK_LINSOLVE_BANDED_LU && opts->forcing != NK_FORCING_NONE) ||
-                 opts->algorithm == NK_ALG_LIMITED_MEMORY_BROYDEN,
+                 opts->algorithm == NK_ALG_LIMITED_MEMORY_BROYDEN || opts->algorithm == NK_ALG_DFSANE,
              "a forcing term needs an iterative linear solver");
   NK_REQUIRE(opts->termination_mode >= 0 && opts->termination_mode <= 8, "bad termination_mode %d", opts->termination_mode);
   NK_REQUIRE(opts->termination_norm == 0 || opts->termination_norm == 1, "bad termination_norm %d", opts->termination_norm);
@@ -781,6 +906,7 @@ extern "C" int nk_solver_init(nk_problem *P, const double *u0, int memspace, con
   S->o = *opts;
   // LimitedMemoryBroyden reads no Jacobian: whatever `linsolve` says, nothing below builds one, or a Krylov workspace
   if (is_lb(S)) { S->o.linsolve = NK_LINSOLVE_GMRES_MATFREE; S->o.forcing = NK_FORCING_NONE; }
+  if (is_sane(S)) S->o.linsolve = NK_LINSOLVE_GMRES_MATFREE;   // DFSane likewise
   if (S->o.maxiters <= 0) S->o.maxiters = 1000;
   if (S->o.gmres_restart <= 0) S->o.gmres_restart = 30;
   if (S->o.gmres_maxiters <= 0) S->o.gmres_maxiters = 300;
@@ -826,6 +952,18 @@ extern "C" int nk_solver_init(nk_problem *P, const double *u0, int memspace, con
     S->lb_fupool[0] = S->fu;
     NK_TRY(nk_dev_alloc(&S->lb_fupool[1], na));
     NK_TRY(nk_dev_alloc(&S->lb_fupool[2], na));
+  } else if (is_sane(S)) {
+    const nk_options &o = S->o;
+    S->sane_smin = o.sane_sigma_min > 0.0 ? o.sane_sigma_min : 1.0e-10;
+    S->sane_smax = o.sane_sigma_max > 0.0 ? o.sane_sigma_max : 1.0e10;
+    S->sane_M = o.sane_M > 0 ? o.sane_M : 10;
+    S->sane_gamma = o.sane_gamma > 0.0 ? o.sane_gamma : 1.0e-4;
+    S->sane_tmin = o.sane_tau_min > 0.0 ? o.sane_tau_min : 0.1;
+    S->sane_tmax = o.sane_tau_max > 0.0 ? o.sane_tau_max : 0.5;
+    S->sane_nexp = o.sane_n_exp > 0 ? o.sane_n_exp : 2;
+    S->sane_max_inner = o.sane_max_inner_iterations > 0 ? o.sane_max_inner_iterations : 100;
+    NK_TRY(nk_sane_create(ctx, n, &S->sane));
+    NK_TRY(nk_dev_alloc(&S->fu_trial, na));
   } else if (direct(S)) {
     if (is_lm(S)) {  // the factorising solver gets the assembled normal matrix JᵀJ + λDᵀD (see lm_damped_solve)
       NK_TRY(nk_normal_plan_create(S->J, &S->nplan));
@@ -855,6 +993,7 @@ extern "C" int nk_solver_destroy(nk_solver *S) {
   hipFree(S->lb_fupool[1]);
   hipFree(S->lb_fupool[2]);
   nk_lb_destroy(S->lb);
+  nk_sane_destroy(S->sane);
   double *bufs[] = {S->ubuf[0], S->ubuf[1], S->ubuf[2], S->fu, S->du, S->fu_trial, S->du_newton, S->du_cauchy,
                     S->Jdu, S->JTfu, S->c1, S->c2, S->tr_du, S->stage, S->stage2, S->lm_dtd, S->lm_diag, S->lm_v,
                     S->lm_a, S->lm_vcache, S->lm_rhs, S->pt_mass};
@@ -1837,7 +1976,7 @@ static int check_and_update(nk_solver *S, double step_norm) {
 // supports_deferred_residual (FirstOrder/src/solve.jl:303-316): only the unglobalised step, only a residual-only
 // termination mode (AbsTerminationMode / AbsNormTerminationMode, termination_conditions.jl:43-45), only without a trace
 static bool supports_deferred_residual(const nk_solver *S) {
-  if (is_tr(S) || is_lm(S) || is_lb(S) || S->o.linesearch) return false;
+  if (is_tr(S) || is_lm(S) || residual_only(S) || S->o.linesearch) return false;
   if (!(S->o.termination_mode == TM_ABS || S->o.termination_mode == TM_ABSNORM)) return false;
   return !S->o.store_trace;
 }
@@ -1890,6 +2029,7 @@ static int internal_step(nk_solver *S, int recompute /*-1 nothing, 0 false, 1 tr
   // the descent is taken from the residual at the iterate it starts from: settle an outstanding deferral first
   NK_TRY(refresh_residual(S));  // (as in the reference, the step goes on even if this check terminated the solve)
   if (is_lb(S)) return lb_step(S, recompute);
+  if (is_sane(S)) return sane_step(S);   // recompute_jacobian is ignored (the reference warns, solve.jl:205-208)
   const bool defer_residual = !evaluate_residual && supports_deferred_residual(S);
   bool new_jacobian;
   if ((recompute < 0 || recompute == 1) && S->make_new_jacobian) {
@@ -2166,6 +2306,18 @@ extern "C" int nk_solver_get_lbroyden_state(nk_solver *S, int *nresets, int *idx
   if (threshold) *threshold = S->lb_threshold;
   if (since_du) *since_du = S->lb_since_du;
   if (since_dfu) *since_dfu = S->lb_since_dfu;
+  return NK_OK;
+}
+extern "C" int nk_solver_get_dfsane_state(nk_solver *S, double *sigma, double *alpha, int *trials, int *total_trials, int *M,
+                                          double *history) {
+  NK_REQUIRE(S, "NULL argument");
+  NK_REQUIRE(is_sane(S), "not a DFSane cache");
+  if (sigma) *sigma = S->sane_sigma;
+  if (alpha) *alpha = S->sane_alpha;
+  if (trials) *trials = S->sane_trials;
+  if (total_trials) *total_trials = S->sane_total_trials;
+  if (M) *M = S->sane_M;
+  if (history) memcpy(history, S->sane_hist, (size_t)S->sane_M * sizeof(double));
   return NK_OK;
 }
 extern "C" int nk_solver_get_scalars(nk_solver *S, double *fnorm_inf, double *trust_region, double *eta) {
