@@ -24,18 +24,17 @@
 // the MFMA operand reads — 16 columns × 4 rows per instruction — are conflict-free), and the four wavefronts accumulate the
 // Gram tile from LDS. Workgroups are persistent (2 per CU), so the partial sums leave the chip once per launch.
 #include "nk_internal.h"
+#include "nk_ss_plan.h"
 
 #include <cmath>
 #include <cstdio>
 #include <cstring>
 #include <vector>
 
-constexpr int SS_R = 256;        // rows per tile = threads per workgroup
 constexpr int SS_P = SS_R + 1;   // LDS pitch in doubles (odd)
 constexpr int SS_MTMAX = 5;      // Gram tiles of 16 rows: k + s ≤ 80
 constexpr int SS_SMAX = NK_SS_SMAX;   // one 16-wide matrix-core tile of new columns
 constexpr int SS_TH = NK_SS_TH;   // scal[SS_TH + j] = θ_j; scal[0..5): first-application scale, 1/σ, σ, carried σ estimate, Newton flag
-constexpr int SS_MAX_WG_PER_CU = 4;
 typedef double ss_d4 __attribute__((ext_vector_type(4)));
 typedef unsigned int ss_u2 __attribute__((ext_vector_type(2)));
 // development: phase time stamps of the scalar work (nk_ss_debug_stamps, tools/ss_stamps.py) — in builds with -DNK_SS_STAMPS only
@@ -667,7 +666,6 @@ __global__ __launch_bounds__(256) void k_ss_hess(int k, int sb, ss_tail_args ta)
 // kernel (k_backsolve's `fx`, nk_gmres.hip).
 
 // The scalar work of the block scheme as ONE kind of launch (k_ss_job, behind the sweeps): what a job does
-constexpr int SSJ_F1 = 1, SSJ_F2 = 2, SSJ_HESS = 4, SSJ_BACK = 8, SSJ_COEF2 = 16, SSJ_PREP = 32;
 struct ss_job {
   const double *part0, *part1;
   int nblk0, nblk1, nslots0, nslots1;
@@ -1358,71 +1356,35 @@ static size_t ss_tile_doubles(int k, int s, bool gram, int nt) {
   const size_t a = (size_t)(k + s) * SS_P, b = (size_t)4 * nt * 256;
   return a > b ? a : b;
 }
-static int ss_class(int k, int s) { return k + s <= 16 ? 1 : (k + s <= 32 ? 2 : (k + s <= 48 ? 3 : 0)); }
 static size_t ss_lds_bytes(int k, int s, bool gram) {
   const int c = ss_class(k, s);
   return ss_tile_doubles(k, s, gram, c ? c : SS_MTMAX) * sizeof(double);
 }
-bool nk_ss_fusable(int k, int s) {
-  static const bool off = getenv("NK_SS_FUSED") && atoi(getenv("NK_SS_FUSED")) == 0;
-  return !off && ss_class(k, s) != 0;
-}
-// persistent workgroups per CU = what the runtime says a CU holds of the instance that will run (LDS tile and register
-// footprint: 190–196 VGPRs for the Gram sweeps of a 15-column block behind 16 columns — two workgroups, not the three a table
-// of size classes once said; the third of every CU ran as a second round on a third of the chip), queried once per shape
+bool nk_ss_fusable(int k, int s) { return ss_fusable(ss_env_switches(), k, s); }
+// the grid rules (nk_ss_plan.h) on this device: how many workgroups of a sweep a CU holds is what the runtime says, queried once per shape
 int nk_ss_sweep_occupancy(nk_ctx *ctx, int mode, int k, int s);
-static int ss_per_cu(nk_ctx *ctx, int k, int s) {
-  static const int forced = getenv("NK_SS_PER_CU") ? atoi(getenv("NK_SS_PER_CU")) : 0;   // A/B switch
-  if (forced > 0) return forced > SS_MAX_WG_PER_CU ? SS_MAX_WG_PER_CU : forced;
-  const int a = nk_ss_sweep_occupancy(ctx, 0, k, s), b = nk_ss_sweep_occupancy(ctx, 1, k, s);
-  int per_cu = a < b ? a : b;
-  return per_cu < 1 ? 1 : (per_cu > SS_MAX_WG_PER_CU ? SS_MAX_WG_PER_CU : per_cu);
+static ss_cycle_cfg ss_grid_cfg(nk_ctx *ctx, int64_t n) {
+  ss_cycle_cfg c;
+  c.n = n;
+  c.num_cus = ctx->num_cus;
+  c.occupancy = [](void *user, int mode, int k, int s) { return nk_ss_sweep_occupancy(static_cast<nk_ctx *>(user), mode, k, s); };
+  c.occ_user = ctx;
+  return c;
 }
-// Workgroups of a sweep: as many per CU as fit — but not more than divide the tiles evenly. A workgroup walks ⌈tiles / grid⌉
-// tiles, so a CU is busy for per_cu·⌈tiles / (CUs·per_cu)⌉ of them: with 4096 tiles (n = 2²⁰) on 256 CUs three workgroups per CU
-// (what the 15-column block behind one column fits) make that 18 where two or four make it 16 — measured 25.6 → 24.2 and
-// 47.4 → 45.7 µs for sweeps A and B of that shape with two. The largest count that reaches the minimum is taken.
-int nk_ss_grid(nk_ctx *ctx, int64_t n, int k, int s) {
-  const int ntiles = (int)((n + SS_R - 1) / SS_R);
-  const int occ = ss_per_cu(ctx, k, s);
-  int best = occ;
-  int64_t best_cost = INT64_MAX;
-  for (int p = occ; p >= 1; --p) {
-    const int64_t g = (int64_t)ctx->num_cus * p;
-    const int64_t cost = (int64_t)p * ((ntiles + g - 1) / g);
-    if (cost < best_cost) { best_cost = cost; best = p; }
-  }
-  int g = ctx->num_cus * best;
-  if (g > ntiles) g = ntiles;
-  return g > 0 ? g : 1;
-}
-// Sweep A (read-only) of the default cycle's shapes runs ONE workgroup per CU — measured on the same box, stand-alone:
-// 24.1 → 22.0 µs behind one column, 45.9 → 42.1 µs behind 16 (6.1–6.2 TB/s; the writing sweep B gains nothing from it). When it
-// hosts the previous block's Hessenberg work the hosting workgroup is one of these (it streams nothing and has a CU to itself:
-// 49 µs; as a 257th workgroup beside a streaming one 54 µs, inside a grid of 512 52 µs — the hosted scalar work, ≈ 45 µs under
-// load against 29 µs as a launch of its own, is what that launch waits for, not its 255 streaming workgroups).
-// Other shapes: the grid of sweep B.
+int nk_ss_grid(nk_ctx *ctx, int64_t n, int k, int s) { return ss_grid(ss_grid_cfg(ctx, n), ss_env_switches(), k, s); }
 int nk_ss_grid_a(nk_ctx *ctx, int64_t n, int k, int s, bool hosting) {
-  static const bool off = getenv("NK_SS_GRID_A") && atoi(getenv("NK_SS_GRID_A")) == 0;   // A/B switch
-  static const bool kc_off = getenv("NK_SS_KCONST") && atoi(getenv("NK_SS_KCONST")) == 0;
-  const int ntiles = (int)((n + SS_R - 1) / SS_R);
-  if (off || kc_off || s != 15 || (k != 1 && k != 16) || ntiles < 2 * ctx->num_cus) return nk_ss_grid(ctx, n, k, s);
-  static const int host_extra = getenv("NK_SS_GRID_A_HOST") ? atoi(getenv("NK_SS_GRID_A_HOST")) : 0;   // A/B switch (1: a 257th workgroup)
-  return ctx->num_cus + (hosting ? host_extra : 0);
+  return ss_grid_a(ss_grid_cfg(ctx, n), ss_env_switches(), k, s, hosting);
 }
 
-// Sweep B that stores nothing takes the read-only kernel (k_ss_block_ro): behind 16 columns, 32-bit byte offsets over the whole
-// basis, 16-byte row pairs
-static bool ss_b_is_read_only(const double *V, int64_t ldv, int k, int s) {
-  static const bool ro_on = !(getenv("NK_SS_RO") && atoi(getenv("NK_SS_RO")) == 0);   // A/B switch
-  return ro_on && k == 16 && s == 15 && (int64_t)(k + s) * ldv * 8 < ((int64_t)1 << 32) - 8 && (ldv & 1) == 0 && ((uintptr_t)V & 15) == 0;
-}
 template <int S>
 static int ss_launch_s(nk_ctx *ctx, int mode, int64_t n, int k, double *V, int64_t ldv, const double *coef, double *partials,
                        const int *d_skip, int grid, const ss_tail_args *tap, int *mark, int *occ_out = nullptr, int hk = 0,
                        int hs = 0, const ss_job *hjp = nullptr, int flags = 0) {
   const int ntiles = (int)((n + SS_R - 1) / SS_R);
   const int cls = ss_class(k, S);
+  const ss_switches &sw = ss_env_switches();
+  [[maybe_unused]] const bool kc_on = sw.kconst;
+  const int ws_off = sw.barriers ? 1 : 0;
   // "fused": a sweep whose workgroup 0 derives a block's Hessenberg columns while the others stream (its LDS: the scalar
   // workspace) — sweep C for its own block (hk = k, hs = S), sweep A for the PREVIOUS block when that was left at its first
   // pass (hk, hs: that block). The update coefficients always arrive through scalar loads from `coef`, where the reduction's
@@ -1470,11 +1432,9 @@ static int ss_launch_s(nk_ctx *ctx, int mode, int64_t n, int k, double *V, int64
     else if (cls == 3) { if (fuse) SS_GO3(UPD, GRM, 3, (UPD != GRM)); else SS_GO3(UPD, GRM, 3, false); }                  \
     else SS_GO3(UPD, GRM, 0, false);                                                                                      \
   } while (0)
-  static const int ws_off = (getenv("NK_SS_BARRIERS") && atoi(getenv("NK_SS_BARRIERS")) != 0) ? 1 : 0;
   int g = grid + (hjp ? hjv.host_wgs : 0);
   if constexpr (S == 15) {
-    static const bool mm_on = !(getenv("NK_SS_MM") && atoi(getenv("NK_SS_MM")) == 0);   // A/B switch
-    if (mode == 1 && mm_on && (k == 1 || k == 16) &&
+    if (mode == 1 && sw.mm && (k == 1 || k == 16) &&
         (occ_out || (int64_t)S * ldv * 8 < ((int64_t)1 << 32) - 8)) {
       const size_t tile_b = (size_t)(k + S + 1) * SS_P * sizeof(double);   // the tile + the spare column
       // tap: workgroup 0 hosts the previous block's Hessenberg work (hk, hs); its workspace overlays the tile it does not use
@@ -1496,7 +1456,7 @@ static int ss_launch_s(nk_ctx *ctx, int mode, int64_t n, int k, double *V, int64
   } while (0)
       const bool nostore = (flags & 1) != 0;   // (the cycle's last block: nk_ss_cycle)
       // the read-only form behind 16 columns (k_ss_block_ro): 32-bit byte offsets over the whole basis, 16-byte row pairs
-      const bool ro = nostore && (occ_out ? k == 16 : ss_b_is_read_only(V, ldv, k, S));
+      const bool ro = nostore && (occ_out ? k == 16 : ss_b_read_only(sw, ldv, ((uintptr_t)V & 15) == 0, k, S));
       if (ro) {
         const size_t tile_r = (size_t)16 * SS_P2 * sizeof(double), red_r = (size_t)4 * 2 * 256 * sizeof(double);
         size_t lds_r = tile_r > red_r ? tile_r : red_r;
@@ -1525,7 +1485,6 @@ static int ss_launch_s(nk_ctx *ctx, int mode, int64_t n, int k, double *V, int64
       return NK_OK;
     }
   }
-  static const bool kc_on = !(getenv("NK_SS_KCONST") && atoi(getenv("NK_SS_KCONST")) == 0);   // A/B switch
   NK_REQUIRE(!(mode == 1 && tap != nullptr), "internal: sweep B of this shape (k = %d, s = %d) cannot host a Hessenberg workgroup", k, S);
   NK_REQUIRE((flags & 1) == 0, "internal: sweep B of this shape (k = %d, s = %d) has no form that stores nothing", k, S);
   if (mode == 0) SS_GO(false, true);        // sweep A: Gram only
@@ -1589,14 +1548,7 @@ int nk_ss_sweep_occupancy(nk_ctx *ctx, int mode, int k, int s) {
   }
   return c;
 }
-// widths the sweeps are compiled for; any other block is cut into these (the last block of a cycle, odd block sizes)
-int nk_ss_block_width(int want) {   // (round 6: 3, 5, 7, 10 and 12 left the list — 45 % of the sweep instantiations for ragged tails only)
-  if (want >= 15) return 15;
-  if (want >= 8) return 8;
-  if (want >= 6) return 6;
-  if (want >= 4) return 4;
-  return want >= 2 ? 2 : 1;
-}
+int nk_ss_block_width(int want) { return ss_block_width(want); }
 
 // ----------------------------------------------------------------------------- the scalar work of the block scheme: one launch
 // Everything between two sweeps that is NOT a sweep, in one kind of launch (round 5; rounds 3–4: k_ss_reduce_factor after every
@@ -2288,17 +2240,6 @@ extern "C" int nk_gmres_get_sstep_interval(nk_gmres *G, double *lo, double *hi) 
   return NK_OK;
 }
 
-// Implicit second pass (A/B switch NK_SS_IMPLICIT=0): a block that is not the cycle's last is left at its first pass as well —
-// no sweep C; the next blocks carry their Gram products through its (C₂, R₂) (ss_fix_to_true / _to_stored), its Hessenberg
-// columns are a launch of their own, the back-substitution adapts y block by block. One sweep over k + 2s columns less per block.
-static bool ss_implicit_on() {
-  static const bool off = getenv("NK_SS_IMPLICIT") && atoi(getenv("NK_SS_IMPLICIT")) == 0;
-  return !off;
-}
-static bool ss_skip_last_sweep() {
-  static const bool off = getenv("NK_SS_LAST_SWEEP") && atoi(getenv("NK_SS_LAST_SWEEP")) != 0;   // A/B switch: run it anyway
-  return !off;
-}
 // for the back-substitution of a cycle whose last block was left at its first pass: what turns y into coefficients on the
 // stored columns (k_backsolve, nk_gmres.hip)
 nk_ss_fix nk_ss_take_last_block(nk_gmres *G) {
@@ -2410,28 +2351,6 @@ static int ss_launch_job(nk_ctx *ctx, const ss_job &j, const ss_tail_args &ta0, 
   NK_HIP(hipGetLastError());
   return NK_OK;
 }
-// Sweep B of this shape can host a Hessenberg workgroup (the matrix-core form of the default cycle's shapes)
-static bool ss_b_can_host(int64_t ldv, int k, int s) {
-  static const bool mm_on = !(getenv("NK_SS_MM") && atoi(getenv("NK_SS_MM")) == 0);
-  static const bool host_on = !(getenv("NK_SS_HOST_B") && atoi(getenv("NK_SS_HOST_B")) == 0);   // A/B switch
-  return host_on && mm_on && s == 15 && (k == 1 || k == 16) && (int64_t)s * ldv * 8 < ((int64_t)1 << 32) - 8;
-}
-
-// Sweep A of this shape can host the scalar launch that closes the previous block in extra workgroups (k_ss_block's JOBHOST
-// instance: the compile-time-k form of the default cycle's second block). One rank only: a hosted job cannot wait for peers
-// while the streaming workgroups of its own launch hold the chip.
-// The job's workgroups take the place of streaming ones (the sweep's LDS tile admits two workgroups per CU and the grid fills
-// them: workgroups added to a full grid start when the sweep is over).
-static int ss_host_a_wgs() {
-  static const int n = getenv("NK_SS_HOST_A_WGS") ? atoi(getenv("NK_SS_HOST_A_WGS")) : 20;   // 240 entries: three rounds of 4 × 20 wavefronts (8 left the job longer than the sweep, 30 cost the sweep)
-  return n < 1 ? 1 : (n > 64 ? 64 : n);
-}
-static bool ss_a_can_host_job(nk_ctx *ctx, int k, int s) {
-  static const bool host_on = !(getenv("NK_SS_HOST_A") && atoi(getenv("NK_SS_HOST_A")) == 0);   // A/B switch
-  static const bool kc_on = !(getenv("NK_SS_KCONST") && atoi(getenv("NK_SS_KCONST")) == 0);
-  return host_on && kc_on && nk_ctx_is_single(ctx) && s == 15 && k == 16 && ss_class(k, s) == 2;
-}
-
 // Enqueues the Arnoldi part of one cycle: `steps` columns in blocks of ≤ s (cut to the widths the sweeps are compiled for;
 // the last block may be shorter). k_gmres_begin has run. `wait_progress(need)` (may be empty) blocks the host until `need`
 // columns are closed or the cycle is done and returns false when no further block should be enqueued.
@@ -2454,83 +2373,132 @@ int nk_ss_cycle(nk_gmres *G, int steps, const std::function<bool(int)> &wait_pro
   NK_TRY(ss_workspace(G));
   nk_sstep *W = G->ss;
   const int64_t n = G->n, ldv = G->ldv;
-  const int s = nk_ss_block_size(G);
   const int *done = &G->d_ctl->done, *skipC = &G->d_ctl->pad1;
-  ss_tail_args ta;
-  std::memset(&ta, 0, sizeof(ta));
-  ta.ctl = G->d_ctl; ta.red = W->red; ta.sc = G->d_s; ta.C1 = W->C1; ta.R1 = W->R1; ta.C2 = W->C2; ta.R2 = W->R2; ta.H = W->H; ta.m = G->m;
-  ta.Rg = G->d_R; ta.cs = G->d_cs; ta.sn = G->d_sn; ta.g = G->d_g; ta.scal = W->scal; ta.pub = G->h_pub_dev; ta.seq = G->cycle_seq;
-  G->ss_fix = nk_ss_fix{};
-  // Blocks are left at their first pass with the NEWTON basis only (monomial blocks of 6–8 columns live near the rank-loss bar
-  // and keep the explicit second update), and only while the first pass leaves them NEARLY orthonormal: the Hessenberg recovery
-  // of the next block starts from a stored column, a combination u of true basis vectors whose images carry this block's
-  // recovery errors — harmless for u ≈ e_k, amplified column by column when pass 1 was far off (a block within a factor of ≈ 30
-  // of losing rank: oracle, Arnoldi residual 5e-2 against 1e-7 for the explicit update at a departure of 0.75, equal up to 0.2).
-  // ss_first_pass_departure measures max(|C₂|, |R₂ − I|) in the reduction's tail; above 0.1 the block counts as broken and
-  // takes the fall-back (narrower blocks), exactly like a lost pivot.
-  const bool implicit_mode = ss_implicit_on() && W->newton;
-  static const bool defer_off = getenv("NK_SS_DEFER") && atoi(getenv("NK_SS_DEFER")) == 0;            // A/B switches
-  static const bool tail_back_off = getenv("NK_SS_TAIL_BACK") && atoi(getenv("NK_SS_TAIL_BACK")) == 0;
-  static const int hess_where = getenv("NK_SS_DEFER_HESS") ? atoi(getenv("NK_SS_DEFER_HESS")) : -1;   // 0: in the job, 1: hosted by sweep B
+  // everything the dispatch depends on; the decisions themselves: ss_plan_block / ss_plan_finish (nk_ss_plan.h)
+  const ss_switches &sw = ss_env_switches();
+  ss_cycle_cfg cfg = ss_grid_cfg(ctx, n);
+  cfg.steps = steps; cfg.s = nk_ss_block_size(G); cfg.ldv = ldv; cfg.v_aligned16 = ((uintptr_t)G->V & 15) == 0;
+  cfg.single_rank = nk_ctx_is_single(ctx);
   // several ranks: the fused scalar launches are also the all-reduce — on peer-mapped arenas only
   // (one message may carry two partial blocks: ≤ 2·(steps + 1)·s values — 930 for GMRES(30) in blocks of 15)
-  const bool peer_ok = nk_ctx_is_single(ctx) || nk_peer_ar_available(ctx, 2 * (steps + 1) * s);
-  const bool deferred = !defer_off && implicit_mode && peer_ok && nk_ss_fusable(1, 1);
-  const bool fixed_work = !G->ss_grow;
+  cfg.peer_ok = cfg.single_rank || nk_peer_ar_available(ctx, 2 * (steps + 1) * cfg.s);
+  cfg.newton = W->newton; cfg.auto_grow = G->ss_s == 0 && G->ss_grow; cfg.fixed_work = !G->ss_grow;
+  cfg.accepts_back = backsolved != nullptr; cfg.audit_on = ctx->audit.on;
+  cfg.nblk_slots = W->nblk_slots; cfg.nfix = NK_SS_NFIX;
+  ss_cycle_state st = ss_plan_begin(cfg);
+  ss_tail_args ta;        // the block under construction; the deferred block's; the block's whose Hessenberg columns are pending
+  ss_tail_args dp_ta, pend_ta;
+  std::memset(&ta, 0, sizeof(ta));
+  std::memset(&dp_ta, 0, sizeof(dp_ta));
+  std::memset(&pend_ta, 0, sizeof(pend_ta));
+  ta.ctl = G->d_ctl; ta.red = W->red; ta.sc = G->d_s; ta.C1 = W->C1; ta.R1 = W->R1; ta.C2 = W->C2; ta.R2 = W->R2; ta.H = W->H; ta.m = G->m;
+  ta.Rg = G->d_R; ta.cs = G->d_cs; ta.sn = G->d_sn; ta.g = G->d_g; ta.scal = W->scal; ta.pub = G->h_pub_dev; ta.seq = G->cycle_seq;
   ta.ptol = 1e-12;
+  G->ss_fix = nk_ss_fix{};
   ss_job jb;   // what every scalar launch of this cycle shares
   std::memset(&jb, 0, sizeof(jb));
   jb.m = G->m; jb.red = W->red; jb.coef = W->coef; jb.d_skip = done; jb.ticket = W->ticket;
   jb.ctl = G->d_ctl; jb.sc = G->d_s; jb.pub = G->h_pub_dev; jb.seq = G->cycle_seq;
   jb.y = G->d_y; jb.Rg = G->d_R; jb.g = G->d_g;
   jb.peer_err = ctx->peer.on ? nk_peer_err_ptr(ctx) : nullptr;
-  int blk = 0;            // index of the block within the cycle = its slot of pass-2 factors
-  int prev_k0 = 0, prev_sb2 = 0;  // the previous block if it was left at its first pass (prev_sb2 = 0: it was not)
-  ss_tail_args pend_ta;           // … and, while its Hessenberg columns wait for a sweep A to host them, its arguments
-  std::memset(&pend_ta, 0, sizeof(pend_ta));
-  int pend_k = 0, pend_sb = 0;
-  // deferred form: the block whose sweep B has run and whose second factorisation has not (its partial Gram block: W->part2)
-  struct { bool on; int k, sb, grid; ss_tail_args ta; } dp;
-  std::memset(&dp, 0, sizeof(dp));
-  // closes the pending block in a launch of its own: second factorisation, Wi / D, Hessenberg columns — and, at the cycle's end,
-  // the back-substitution
-  // the cycle's last block with a sweep B that stores nothing (k_ss_block_mm<…, NOSTORE>): its columns in memory stay as the matrix
-  // powers left them, X; the back-substitution of the cycle's last launch takes the block's COMBINED factors (C, R) — which the
-  // Hessenberg recovery forms anyway — where it takes (C₂, R₂) for a block whose first-pass columns were stored (ss_job.raw_last)
-  bool raw_on = false;
-  auto close_pending = [&](bool with_back) -> int {
-    ss_job j = jb;
-    j.part1 = W->part2; j.nblk1 = dp.grid; j.nslots1 = (dp.k + dp.sb) * dp.sb; j.k1 = dp.k; j.sb1 = dp.sb;
-    j.mode = SSJ_F2 | SSJ_PREP | SSJ_HESS | (with_back ? SSJ_BACK : 0);
-    j.cfix = dp.ta.fix;
-    NK_REQUIRE(!raw_on || with_back, "internal: a block whose sweep B stored nothing needs the back-substitution of its cycle's last launch");
-    if (with_back) {
-      j.bfx = G->ss_fix;
-      j.raw_last = raw_on ? 1 : 0;
+  // binds buffers and argument sets to the plan's launches, in order
+  auto run = [&](const ss_block_plan &p) -> int {
+    const int k = p.k, sb = p.sb, nslots = (k + sb) * sb;
+    for (int i = 0; i < p.nl; ++i) {
+      const ss_launch &l = p.l[i];
+      const ss_tail_args &lta = l.who == SS_DEFERRED ? dp_ta : (l.who == SS_PENDING ? pend_ta : ta);
+      switch (l.op) {
+        case SS_SWEEP_A: {
+          nk_prof_scope prof_(ctx, NK_K_MULTIDOT, 8.0 * (double)n * (k + sb));
+          if (l.mode) {   // … whose last host_wgs workgroups close the deferred block
+            ss_job hj = jb;
+            hj.part1 = W->part2; hj.nblk1 = l.wgrid; hj.nslots1 = (l.wk + l.wsb) * l.wsb; hj.k1 = l.wk; hj.sb1 = l.wsb;
+            hj.mode = l.mode;
+            hj.cfix = dp_ta.fix;
+            hj.host_wgs = l.host_wgs;
+            NK_TRY(ss_sweep_a_hosting_job(ctx, n, k, sb, G->V, ldv, W->part, done, l.grid, dp_ta, &G->d_ctl->pad1, hj));
+          } else
+            NK_TRY(nk_ss_sweep(ctx, 0, n, k, sb, G->V, ldv, W->coef, W->part, done, l.grid, l.who == SS_PENDING ? &pend_ta : nullptr,
+                               &G->d_ctl->pad1, l.wk, l.wsb));
+          break;
+        }
+        case SS_SWEEP_B: {   // (deferred: its partial Gram block waits in part2 for the next scalar launch)
+          nk_prof_scope prof_(ctx, NK_K_MULTIDOT, 8.0 * (double)n * (k + (l.nostore ? 1 : 2) * sb));
+          ss_tail_args hta = dp_ta;
+          hta.Wi = nullptr; hta.D = nullptr;   // (prepared by the job already)
+          NK_TRY(nk_ss_sweep(ctx, 1, n, k, sb, G->V, ldv, W->coef, p.defer_this ? W->part2 : W->part, done, l.grid,
+                             l.who == SS_DEFERRED ? &hta : nullptr, nullptr, l.wk, l.wsb, l.nostore ? 1 : 0));
+          break;
+        }
+        case SS_SWEEP_C: {
+          nk_prof_scope prof_(ctx, NK_K_MULTIAXPY, 8.0 * (double)n * (k + 2 * sb));
+          NK_TRY(nk_ss_sweep(ctx, 2, n, k, sb, G->V, ldv, W->coef, W->part, skipC, l.grid, l.who == SS_THIS ? &ta : nullptr, nullptr));
+          break;
+        }
+        case SS_JOB: {   // set 0: this block's first pass; set 1: a second pass — the deferred block's (part2) or this block's own
+          ss_job j = jb;
+          if (l.mode & SSJ_F1) { j.part0 = W->part; j.nblk0 = l.grid; j.nslots0 = nslots; j.k0 = k; j.sb0 = sb; }
+          if (l.mode & SSJ_F2) {
+            j.part1 = l.who == SS_DEFERRED ? W->part2 : W->part; j.nblk1 = l.wgrid; j.nslots1 = (l.wk + l.wsb) * l.wsb;
+            j.k1 = l.wk; j.sb1 = l.wsb;
+          }
+          j.mode = l.mode;
+          const ss_tail_args &ta0 = (l.mode & SSJ_F1) ? ta : lta;
+          j.cfix = ta0.fix;
+          const bool closes_deferred = l.who == SS_DEFERRED && !(l.mode & SSJ_F1);   // (a launch of its own, not the next block's job)
+          NK_REQUIRE(!(closes_deferred && st.raw_on) || (l.mode & SSJ_BACK),
+                     "internal: a block whose sweep B stored nothing needs the back-substitution of its cycle's last launch");
+          if (l.mode & SSJ_BACK) {
+            j.bfx = G->ss_fix;
+            j.raw_last = l.raw_last ? 1 : 0;
+          }
+          NK_TRY(ss_launch_job(ctx, j, ta0, lta));
+          break;
+        }
+        case SS_TAIL1:
+        case SS_TAIL2: {   // the unfused scalar work: reduction (all-reduce), then the factorisation as a launch of its own
+          const int pass = l.op == SS_TAIL2 ? 1 : 0, grid = l.grid;
+          double *Wk = G->V + (size_t)k * ldv;
+          if (ctx->audit.on) {
+            nk_audit(ctx, 1000 * (pass + 1) + 10 * p.blk + 1, W->part, (size_t)nslots * grid);            // the sweep's partial Gram blocks
+            if (pass == 1) for (int j = 0; j < sb; ++j) nk_audit(ctx, 200 + k + j, Wk + (size_t)j * ldv, (size_t)n);   // … and updated columns
+          }
+          {
+            nk_prof_scope prof_(ctx, NK_K_REDUCE_SMALL, 8.0 * nslots * grid);
+            NK_TRY(nk_blas_reduce_slots_allreduce(ctx, W->part, grid, nslots, W->red, done));  // (k + s)·s values, one message
+          }
+          if (ctx->audit.on) nk_audit(ctx, 1000 * (pass + 1) + 10 * p.blk + 2, W->red, (size_t)nslots);   // the reduced (all-reduced) block
+          const size_t lds = (ss_ws_doubles(k, sb, pass == 1) + ss_fixc_doubles(ta.fix)) * sizeof(double);
+          if (pass == 0) {
+            if (lds > 64 * 1024)
+              NK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_ss_tail1), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+            hipLaunchKernelGGL(k_ss_tail1, dim3(1), dim3(256), lds, ctx->stream, k, sb, W->coef, ta);
+          } else {
+            if (lds > 64 * 1024)
+              NK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_ss_tail2), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+            hipLaunchKernelGGL(k_ss_tail2, dim3(1), dim3(256), lds, ctx->stream, k, sb, W->coef, ta);
+          }
+          if (ctx->audit.on) {   // what the tail left: the next sweep's coefficients, the factors, the control block
+            nk_audit(ctx, 1000 * (pass + 1) + 10 * p.blk + 3, W->coef, (size_t)k * sb + (size_t)sb * sb);
+            nk_audit(ctx, 1000 * (pass + 1) + 10 * p.blk + 4, pass == 0 ? ta.C1 : ta.C2, (size_t)k * sb);
+            nk_audit(ctx, 1000 * (pass + 1) + 10 * p.blk + 5, pass == 0 ? ta.R1 : ta.R2, (size_t)sb * sb);
+            nk_audit(ctx, 1000 * (pass + 1) + 10 * p.blk + 6, G->d_ctl, sizeof(nk_gmres_ctl) / 8);
+          }
+          break;
+        }
+        case SS_HESS:
+          NK_TRY(ss_launch_hess(ctx, l.wk, l.wsb, lta));
+          break;
+      }
     }
-    NK_TRY(ss_launch_job(ctx, j, dp.ta, dp.ta));
-    dp.on = false;
-    if (with_back && backsolved) *backsolved = true;
     return NK_OK;
   };
   if (G->ss_force_break_cycle >= 0 && G->ss_force_break_cycle == G->ss_cycle_idx)
     NK_LAUNCH(ctx, k_ss_force_fail, dim3(1), dim3(64), G->d_ctl, G->h_pub_dev, G->cycle_seq);
-  int k = 1;  // orthonormal columns so far (column 0 = r₀, un-normalised, scale s[0])
-  int prev_sb = s;
-  // A solve that stops on a tolerance may need 2 iterations or 200: a block's operator applications past the column that meets
-  // the tolerance are wasted (a multigrid V-cycle each, under that preconditioner). Automatic block sizes therefore start small
-  // in every cycle and double — 4, 8, 15, 15 … with the Newton basis, 2, 4, 6, 6 … with the monomial one —: a solve that needs
-  // k iterations applies the operator < 2k times, and one that fills the cycle builds most of it in full-width blocks. The
-  // fixed-work protocol and explicit block sizes take full blocks from the start.
-  int grow = (G->ss_s == 0 && G->ss_grow) ? (W->newton ? 4 : 2) : s;
-  while (k - 1 < steps) {
-    int sb = (steps - (k - 1)) < s ? (steps - (k - 1)) : s;
-    if (grow < sb) sb = grow;
-    grow = grow * 2 > s ? s : grow * 2;
-    sb = nk_ss_block_width(sb);
-    if (k + sb > 48 && sb > 8) sb = 8;  // the streaming size class keeps its scalar workspace within the LDS
-    if (wait_progress && k > 1 && !wait_progress(k - 1 - prev_sb)) break;
-    prev_sb = sb;
+  while (ss_plan_more(cfg, st)) {
+    if (wait_progress && st.k > 1 && !wait_progress(st.k - 1 - st.prev_sb)) break;
+    const ss_block_plan p = ss_plan_block(cfg, sw, st);
+    const int k = p.k, sb = p.sb;
     double *Wk = G->V + (size_t)k * ldv;
     // the block's basis vectors: (A − θ_j I) applied s times (right-preconditioned operator), scaled by 1/σ — in one launch
     // with the matrix held on the chip where that applies (nk_powers.hip), else one operator launch per column
@@ -2540,185 +2508,35 @@ int nk_ss_cycle(nk_gmres *G, int steps, const std::function<bool(int)> &wait_pro
     for (int j = 0; j < sb && !powers; ++j)
       NK_TRY(nk_gmres_op_apply(G, G->V + (size_t)(k - 1 + j) * ldv, Wk + (size_t)j * ldv, done, W->scal + (j == 0 ? 0 : 1),
                                W->newton ? W->scal + SS_TH + j : nullptr));
-    const int grid = nk_ss_grid(ctx, n, k, sb);
-    const int nslots = (k + sb) * sb;
     if (ctx->audit.on)   // (development) the block's new columns as the operator left them
       for (int j = 0; j < sb; ++j) nk_audit(ctx, 100 + k - 1 + j, Wk + (size_t)j * ldv, (size_t)n);
-    // fused: the block's scalar work rides in the stage-2 reduction (its last workgroup factors the reduced block and leaves
-    // the update coefficients for the next sweep's scalar loads) and in sweep C (workgroup 0: the Hessenberg columns) — one
-    // rank, or several on peer-mapped arenas (the reduction is then the all-reduce as well). Other transports and the
-    // streaming size class (k + s > 48): reduction, all-reduce and the scalar work as launches of their own.
-    const bool fused = nk_ss_fusable(k, sb) && peer_ok;
-    if (pend_sb > 0 && !fused) {   // nobody to host it: the previous block's Hessenberg columns as a launch of their own
-      NK_TRY(ss_launch_hess(ctx, pend_k, pend_sb, pend_ta));
-      pend_sb = 0;
-    }
     // this block's slots of factors; the blocks before it that were left at their first pass; the start vector's origin
-    NK_REQUIRE(blk < W->nblk_slots, "internal: more s-step blocks in a cycle than factor slots");
-    ta.C1 = W->C1 + (size_t)blk * W->c2_stride;
-    ta.R1 = W->R1 + (size_t)blk * SS_SS;
-    ta.C2 = W->C2 + (size_t)blk * W->c2_stride;
-    ta.R2 = W->R2 + (size_t)blk * SS_SS;
+    NK_REQUIRE(p.blk < W->nblk_slots, "internal: more s-step blocks in a cycle than factor slots");
+    ta.C1 = W->C1 + (size_t)p.blk * W->c2_stride;
+    ta.R1 = W->R1 + (size_t)p.blk * SS_SS;
+    ta.C2 = W->C2 + (size_t)p.blk * W->c2_stride;
+    ta.R2 = W->R2 + (size_t)p.blk * SS_SS;
     ta.fix = G->ss_fix;
-    ta.usb = prev_sb2; ta.uk0 = prev_k0;
-    ta.uC2 = prev_sb2 ? W->C2 + (size_t)(blk - 1) * W->c2_stride : nullptr;
-    ta.uR2 = prev_sb2 ? W->R2 + (size_t)(blk - 1) * SS_SS : nullptr;
-    // left at its first pass (no sweep C): the cycle's last block always; any other block while the list has room — whatever
-    // the transport and the size class, so that every path runs the same arithmetic (results are compared bit for bit)
-    const bool last_block = (k - 1 + sb >= steps) && ss_skip_last_sweep();
-    const bool implicit = !last_block && implicit_mode && G->ss_fix.n < NK_SS_NFIX - 1;
-    ta.Wi = implicit ? W->Wi + (size_t)blk * SS_SS : nullptr;
-    ta.D = implicit ? W->D + (size_t)blk * W->c2_stride : nullptr;
-    const bool defer_this = deferred && fused && (last_block || implicit);
-    if (dp.on && !defer_this) NK_TRY(close_pending(false));   // (this block takes the older form: nobody to carry the pending one)
-    if (defer_this) {
-      // ---- sweep A, the job [second factorisation of the pending block ; first factorisation of this one], sweep B
-      int grid_a = nk_ss_grid_a(ctx, n, k, sb, false);
-      // the fixed-work protocol, second block of the default cycle: the pending block is closed (reduction, second factorisation,
-      // Wi / D, Hessenberg columns) by extra workgroups of THIS sweep — nothing it writes is read by the streaming ones — and the
-      // launch behind the sweep only factors this block's first pass
-      const bool host_a = dp.on && grid_a > 4 * ss_host_a_wgs() && fixed_work && hess_where < 0 && ss_a_can_host_job(ctx, k, sb);
-      if (host_a) grid_a -= ss_host_a_wgs();   // (streaming workgroups: the pitch of the partial blocks)
-      {
-        nk_prof_scope prof_(ctx, NK_K_MULTIDOT, 8.0 * (double)n * (k + sb));
-        if (host_a) {
-          ss_job hj = jb;
-          hj.part1 = W->part2; hj.nblk1 = dp.grid; hj.nslots1 = (dp.k + dp.sb) * dp.sb; hj.k1 = dp.k; hj.sb1 = dp.sb;
-          hj.mode = SSJ_F2 | SSJ_PREP | SSJ_HESS;
-          hj.cfix = dp.ta.fix;
-          hj.host_wgs = ss_host_a_wgs();
-          NK_TRY(ss_sweep_a_hosting_job(ctx, n, k, sb, G->V, ldv, W->part, done, grid_a, dp.ta, &G->d_ctl->pad1, hj));
-        } else
-          NK_TRY(nk_ss_sweep(ctx, 0, n, k, sb, G->V, ldv, W->coef, W->part, done, grid_a, nullptr, &G->d_ctl->pad1, 0, 0));
-      }
-      // where the pending block's Hessenberg columns are derived: in workgroup 0 of this block's sweep B when nothing can stop
-      // the cycle early (fixed work) and that sweep has the hosting form; else in the job itself (the verdict arrives before sweep B)
-      const bool host_b = !host_a && dp.on && grid > 1 && ss_b_can_host(ldv, k, sb) &&
-                          (hess_where < 0 ? fixed_work : hess_where == 1);
-      // the last block's sweep B stores nothing where the matrix-core form runs it, the cycle's last scalar launch
-      // back-substitutes, the list has room and nothing else wants the columns (development audit)
-      static const bool nostore_off = getenv("NK_SS_NOSTORE") && atoi(getenv("NK_SS_NOSTORE")) == 0;   // A/B switch
-      const bool raw_last = last_block && !nostore_off && !(host_b && k != 16) && ss_b_can_host(ldv, k, sb) && !tail_back_off &&
-                            backsolved != nullptr && !ctx->audit.on;
-      {
-        ss_job j = jb;
-        j.part0 = W->part; j.nblk0 = grid_a; j.nslots0 = nslots; j.k0 = k; j.sb0 = sb;
-        j.mode = SSJ_F1;
-        j.cfix = ta.fix;
-        if (dp.on && !host_a) {
-          j.part1 = W->part2; j.nblk1 = dp.grid; j.nslots1 = (dp.k + dp.sb) * dp.sb; j.k1 = dp.k; j.sb1 = dp.sb;
-          j.mode |= SSJ_F2 | SSJ_PREP | (host_b ? 0 : SSJ_HESS);
-        }
-        NK_TRY(ss_launch_job(ctx, j, ta, (dp.on && !host_a) ? dp.ta : ta));
-      }
-      // the read-only sweep runs ONE workgroup per CU where the tiles allow (as the read-only sweeps A do: stand-alone 52 → 48 µs
-      // at 1024² — half the prologues and partial sums, one wavefront per SIMD on the matrix pipe)
-      static const bool ro_grid_off = getenv("NK_SS_RO_GRID") && atoi(getenv("NK_SS_RO_GRID")) == 0;   // A/B switch
-      int grid_b = grid;
-      if (raw_last && !host_b && !ro_grid_off && ss_b_is_read_only(G->V, ldv, k, sb) && (n + SS_R - 1) / SS_R >= 2 * (int64_t)ctx->num_cus &&
-          grid > ctx->num_cus)
-        grid_b = ctx->num_cus;
-      {
-        nk_prof_scope prof_(ctx, NK_K_MULTIDOT, 8.0 * (double)n * (k + (raw_last ? 1 : 2) * sb));
-        ss_tail_args hta = dp.ta;
-        hta.Wi = nullptr; hta.D = nullptr;   // (prepared by the job already)
-        NK_TRY(nk_ss_sweep(ctx, 1, n, k, sb, G->V, ldv, W->coef, W->part2, done, grid_b, host_b ? &hta : nullptr, nullptr,
-                           host_b ? dp.k : 0, host_b ? dp.sb : 0, raw_last ? 1 : 0));
-      }
-      if (raw_last) raw_on = true;
-      dp.on = true; dp.k = k; dp.sb = sb; dp.grid = grid_b; dp.ta = ta;
-      {
-        nk_ss_fix &fx = G->ss_fix;
-        NK_REQUIRE(fx.n < NK_SS_NFIX, "internal: too many s-step blocks left at their first pass");
-        fx.k0[fx.n] = k; fx.sb[fx.n] = sb; fx.C2[fx.n] = ta.C2; fx.R2[fx.n] = ta.R2;
-        fx.Wi[fx.n] = implicit ? ta.Wi : nullptr; fx.D[fx.n] = implicit ? ta.D : nullptr;
-        fx.n++;
-      }
-      NK_HIP(hipGetLastError());
-      prev_k0 = k;
-      prev_sb2 = sb;
-      k += sb;
-      ++blk;
-      continue;
-    }
-    const int grid_b = grid;
-    for (int pass = 0; pass < 2; ++pass) {
-      int grid = grid_b;   // (of THIS pass: the sweep, and the reduction behind it, which sums one partial per workgroup)
-      {
-        nk_prof_scope prof_(ctx, NK_K_MULTIDOT, 8.0 * (double)n * (k + sb + (pass ? sb : 0)));
-        const bool host_prev = pass == 0 && pend_sb > 0 && fused;   // sweep A hosts the previous block's Hessenberg columns
-        if (pass == 0) grid = nk_ss_grid_a(ctx, n, k, sb, host_prev);
-        NK_TRY(nk_ss_sweep(ctx, pass, n, k, sb, G->V, ldv, W->coef, W->part, done, grid, host_prev ? &pend_ta : nullptr,
-                           pass == 0 ? &G->d_ctl->pad1 : nullptr, pend_k, pend_sb));
-        if (host_prev) pend_sb = 0;
-      }
-      if (fused) {
-        ss_job j = jb;
-        j.cfix = ta.fix;
-        if (pass == 0) {
-          j.part0 = W->part; j.nblk0 = grid; j.nslots0 = nslots; j.k0 = k; j.sb0 = sb;
-          j.mode = SSJ_F1;
-        } else {   // the block's own second factorisation: coefficients for sweep C, C₂ / R₂ for whoever derives its Hessenberg columns
-          j.part1 = W->part; j.nblk1 = grid; j.nslots1 = nslots; j.k1 = k; j.sb1 = sb;
-          j.mode = SSJ_F2 | SSJ_COEF2;
-        }
-        NK_TRY(ss_launch_job(ctx, j, ta, ta));
-      } else {
-        if (ctx->audit.on) {
-          nk_audit(ctx, 1000 * (pass + 1) + 10 * blk + 1, W->part, (size_t)nslots * grid);            // the sweep's partial Gram blocks
-          if (pass == 1) for (int j = 0; j < sb; ++j) nk_audit(ctx, 200 + k + j, Wk + (size_t)j * ldv, (size_t)n);   // … and updated columns
-        }
-        {
-          nk_prof_scope prof_(ctx, NK_K_REDUCE_SMALL, 8.0 * nslots * grid);
-          NK_TRY(nk_blas_reduce_slots_allreduce(ctx, W->part, grid, nslots, W->red, done));  // (k + s)·s values, one message
-        }
-        if (ctx->audit.on) nk_audit(ctx, 1000 * (pass + 1) + 10 * blk + 2, W->red, (size_t)nslots);   // the reduced (all-reduced) block
-        const size_t lds = (ss_ws_doubles(k, sb, pass == 1) + ss_fixc_doubles(ta.fix)) * sizeof(double);
-        if (pass == 0) {
-          if (lds > 64 * 1024)
-            NK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_ss_tail1), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-          hipLaunchKernelGGL(k_ss_tail1, dim3(1), dim3(256), lds, ctx->stream, k, sb, W->coef, ta);
-        } else {
-          if (lds > 64 * 1024)
-            NK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_ss_tail2), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-          hipLaunchKernelGGL(k_ss_tail2, dim3(1), dim3(256), lds, ctx->stream, k, sb, W->coef, ta);
-        }
-        if (ctx->audit.on) {   // what the tail left: the next sweep's coefficients, the factors, the control block
-          nk_audit(ctx, 1000 * (pass + 1) + 10 * blk + 3, W->coef, (size_t)k * sb + (size_t)sb * sb);
-          nk_audit(ctx, 1000 * (pass + 1) + 10 * blk + 4, pass == 0 ? ta.C1 : ta.C2, (size_t)k * sb);
-          nk_audit(ctx, 1000 * (pass + 1) + 10 * blk + 5, pass == 0 ? ta.R1 : ta.R2, (size_t)sb * sb);
-          nk_audit(ctx, 1000 * (pass + 1) + 10 * blk + 6, G->d_ctl, sizeof(nk_gmres_ctl) / 8);
-        }
-      }
-    }
-    if (!last_block && !implicit) {
-      nk_prof_scope prof_(ctx, NK_K_MULTIAXPY, 8.0 * (double)n * (k + 2 * sb));
-      NK_TRY(nk_ss_sweep(ctx, 2, n, k, sb, G->V, ldv, W->coef, W->part, skipC, grid, fused ? &ta : nullptr, nullptr));
-    } else {
-      // left at its first pass: no third sweep (k_backsolve turns y into coefficients on the columns as they are; later blocks
-      // carry their Gram products through this block's factors). Its Hessenberg columns — the work of sweep C's workgroup 0,
-      // or already done by k_ss_tail2 on the unfused path —: the cycle's last block as a launch of its own, any other block
-      // inside the NEXT block's sweep A (which also leaves Wi, D for the reductions behind it).
-      if (implicit && fused) {
-        pend_ta = ta; pend_k = k; pend_sb = sb;
-      } else if (fused) {
-        NK_TRY(ss_launch_hess(ctx, k, sb, ta));
-      }   // (unfused: k_ss_tail2 has derived the Hessenberg columns — and Wi, D — already)
-      {
-        nk_ss_fix &fx = G->ss_fix;
-        NK_REQUIRE(fx.n < NK_SS_NFIX, "internal: too many s-step blocks left at their first pass");
-        fx.k0[fx.n] = k; fx.sb[fx.n] = sb; fx.C2[fx.n] = ta.C2; fx.R2[fx.n] = ta.R2;
-        fx.Wi[fx.n] = implicit ? ta.Wi : nullptr; fx.D[fx.n] = implicit ? ta.D : nullptr;
-        fx.n++;
-      }
+    ta.usb = p.usb; ta.uk0 = p.uk0;
+    ta.uC2 = p.usb ? W->C2 + (size_t)(p.blk - 1) * W->c2_stride : nullptr;
+    ta.uR2 = p.usb ? W->R2 + (size_t)(p.blk - 1) * SS_SS : nullptr;
+    ta.Wi = p.implicit ? W->Wi + (size_t)p.blk * SS_SS : nullptr;
+    ta.D = p.implicit ? W->D + (size_t)p.blk * W->c2_stride : nullptr;
+    NK_TRY(run(p));
+    if (p.becomes == SS_DEFERRED) dp_ta = ta;
+    if (p.becomes == SS_PENDING) pend_ta = ta;
+    if (p.joins_fix_list) {
+      nk_ss_fix &fx = G->ss_fix;
+      NK_REQUIRE(fx.n < NK_SS_NFIX, "internal: too many s-step blocks left at their first pass");
+      fx.k0[fx.n] = k; fx.sb[fx.n] = sb; fx.C2[fx.n] = ta.C2; fx.R2[fx.n] = ta.R2;
+      fx.Wi[fx.n] = p.implicit ? ta.Wi : nullptr; fx.D[fx.n] = p.implicit ? ta.D : nullptr;
+      fx.n++;
     }
     NK_HIP(hipGetLastError());
-    prev_k0 = k;
-    prev_sb2 = (last_block || implicit) ? sb : 0;
-    k += sb;
-    ++blk;
   }
-  if (pend_sb > 0) NK_TRY(ss_launch_hess(ctx, pend_k, pend_sb, pend_ta));   // (the host stopped enqueueing blocks early)
-  if (dp.on) NK_TRY(close_pending(!tail_back_off && backsolved != nullptr));
+  // (also when the host stopped enqueueing blocks early)
+  const ss_block_plan fin = ss_plan_finish(cfg, sw, st);
+  NK_TRY(run(fin));
+  if (fin.backsolved) *backsolved = true;
   return NK_OK;
 }
