@@ -66,7 +66,7 @@ typedef enum {
   NK_RET_MAXTIME = 7,
   NK_RET_FAILURE = 8,
   NK_RET_INTERNAL_LINESEARCH_FAILED = 9,
-  NK_RET_CONVERGENCE_FAILURE = 10   /* NK_ALG_LIMITED_MEMORY_BROYDEN: the reset count reached max_resets (QuasiNewton/src/solve.jl:342-348) */
+  NK_RET_CONVERGENCE_FAILURE = 10   /* NK_ALG_LIMITED_MEMORY_BROYDEN, NK_ALG_BROYDEN, NK_ALG_KLEMENT: the reset count reached max_resets (QuasiNewton/src/solve.jl:342-348) */
 } nk_retcode;
 
 typedef enum {
@@ -94,9 +94,19 @@ typedef enum {
  * is −ασ f with the spectral coefficient σ = ⟨δu,δu⟩/⟨δu,δf⟩. Needs only the residual, like algorithm 5: no Jacobian, no linear
  * solve; nk_options.linesearch != 0 (the search is part of the method), a forcing term or more than one rank are NK_E_INVALID.
  * A failed line search ends the solve with NK_RET_INTERNAL_LINESEARCH_FAILED. recompute_jacobian is ignored. */
+/* NK_ALG_BROYDEN: Broyden without a line search (lib/NonlinearSolveQuasiNewton/src/broyden.jl) with init_jacobian = identity: the
+ * inverse Jacobian is a dense n×n matrix on the device (nk_options.broyden_update_rule: good or bad Broyden), allocated by the
+ * first step, or its diagonal (DiagonalStructure); NoChangeInStateReset(nsteps = 3). Needs only the residual, like algorithm 5:
+ * the Krylov, forcing and preconditioner fields are not read; linesearch != 0 or more than one rank are NK_E_INVALID. A dense
+ * structure with n above NK_BROYDEN_MAX_N is NK_E_UNSUPPORTED at init, before anything is allocated. */
+/* NK_ALG_KLEMENT: Klement (klement.jl) with init_jacobian = identity: J is the vector α·1 (DiagonalStructure, not inverted), the
+ * step is −fu ./ J, the reset test is IllConditionedJacobianReset (any(iszero, J)). The same restrictions as algorithm 7. */
 typedef enum { NK_ALG_NEWTON_RAPHSON = 0, NK_ALG_TRUST_REGION = 1, NK_ALG_GAUSS_NEWTON = 2,
                NK_ALG_LEVENBERG_MARQUARDT = 3, NK_ALG_PSEUDO_TRANSIENT = 4, NK_ALG_LIMITED_MEMORY_BROYDEN = 5,
-               NK_ALG_DFSANE = 6 } nk_algorithm;
+               NK_ALG_DFSANE = 6, NK_ALG_BROYDEN = 7, NK_ALG_KLEMENT = 8 } nk_algorithm;
+#define NK_BROYDEN_MAX_N 32768   /* the dense inverse Jacobian of NK_ALG_BROYDEN at this size is 8 GiB */
+/* nk_options.broyden_update_rule (broyden.jl:26-32); init_jacobian = true_jacobian is not built: NK_E_UNSUPPORTED */
+typedef enum { NK_BROYDEN_GOOD = 0, NK_BROYDEN_BAD = 1, NK_BROYDEN_DIAGONAL = 2, NK_BROYDEN_TRUE_JACOBIAN = 16 } nk_broyden_rule;
 
 /* which operator the Krylov solver sees as A (lib/NonlinearSolveBase/src/jacobian.jl:43-47,90-102) */
 typedef enum {
@@ -285,6 +295,11 @@ typedef struct {
   double  sane_tau_max;                 /* [0.5]                                                                               */
   int32_t sane_n_exp;                   /* [2]    merit ‖f‖₂^n_exp, 1 or 2 (else NK_E_INVALID)                                 */
   int32_t sane_max_inner_iterations;    /* [100]  (minus trial, plus trial) pairs of one line search before it has failed      */
+  /* --- Broyden and Klement (lib/NonlinearSolveQuasiNewton/src/broyden.jl:34-49, klement.jl:29-48); a value <= 0 selects the default */
+  int32_t broyden_update_rule;          /* [0]    nk_broyden_rule; + NK_BROYDEN_TRUE_JACOBIAN: init_jacobian = true_jacobian(_diagonal), NK_E_UNSUPPORTED */
+  int32_t qn_max_resets;                /* [100]  the reset that brings the count to this ends the solve (ConvergenceFailure) */
+  double  qn_reset_tolerance;           /* [eps^(3/4)] NoChangeInStateReset's tolerance (Broyden)                             */
+  double  qn_alpha;                     /* [nothing] J starts as alpha·I; default alpha = 2‖fu‖₂/max(‖u‖₂, 1), 1 if ‖fu‖₂ < 1e-5 */
 } nk_options;
 
 /* in-place callbacks of a user problem: NonlinearFunction{true}(f!; jvp, vjp, jac)
@@ -653,6 +668,13 @@ int nk_solver_get_retcode(nk_solver *S, int *retcode, int *nsteps, int *force_st
  * threshold in effect, and the reset test's two counters. Any pointer may be NULL. NK_E_INVALID for another algorithm. */
 int nk_solver_get_lbroyden_state(nk_solver *S, int *nresets, int *idx, double *a, int *threshold, int *since_du,
                                  int *since_dfu);
+/* NK_ALG_BROYDEN, NK_ALG_KLEMENT: resets counted so far, the scaling the last (re)initialisation used (Broyden: a = 1/α of
+ * J⁻¹ = a·I; Klement: α of J = α·1), the reset test's two counters (0 for Klement) and the steps since the last reset. Any
+ * pointer may be NULL. NK_E_INVALID for another algorithm. */
+int nk_solver_get_qn_state(nk_solver *S, int *nresets, double *a, int *since_du, int *since_dfu, int *steps_since_reset);
+/* NK_ALG_BROYDEN: the inverse Jacobian as it stands, row-major n×n with leading dimension ldo >= n (it exists from the first step
+ * on: NK_E_INVALID before), or its n diagonal entries for the diagonal structure; NK_ALG_KLEMENT: the n diagonal entries of J. */
+int nk_solver_get_broyden_inverse(nk_solver *S, double *out, int64_t ldo, int memspace);
 /* NK_ALG_DFSANE: the spectral coefficient σ the next step starts from, the step length of the last step with its sign (+α₊ or
  * −α₋; 0 before the first step, NaN after a failed search), the residual evaluations of the last line search and of all of
  * them, the history length M and the merit history itself (`history`: room for 32 doubles, M are written). Any pointer may

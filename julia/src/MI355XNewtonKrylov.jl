@@ -524,6 +524,7 @@ Base.@kwdef mutable struct NKOptions
     sane_M::Int32 = 0
     sane_gamma::Float64 = 0.0; sane_tau_min::Float64 = 0.0; sane_tau_max::Float64 = 0.0
     sane_n_exp::Int32 = 0; sane_max_inner_iterations::Int32 = 0
+    broyden_update_rule::Int32 = 0; qn_max_resets::Int32 = 0; qn_reset_tolerance::Float64 = 0.0; qn_alpha::Float64 = 0.0
 end
 
 const RETCODES = (ReturnCode.Default, ReturnCode.Success, ReturnCode.MaxIters, ReturnCode.Unstable,

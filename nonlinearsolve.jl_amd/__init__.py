@@ -10,7 +10,7 @@ from .core import (  # noqa: F401
     CSRMatrix, DeviceProblem, Quadratic, Bratu2D, Brusselator2D,
     NonlinearFunction, NonlinearProblem,
     KrylovJL_GMRES, ChebyshevPrecs, MultigridPrecs, ObjectPrecs, LinearSolveParameters, Preconditioner, JacobiPreconditioner,
-    ILU0Preconditioner, ILUTPreconditioner, AMGPreconditioner, IDENTITY, EisenstatWalkerForcing2, RadiusUpdateSchemes, BackTracking, LineSearchesJL, NewtonRaphson, TrustRegion, GaussNewton, LevenbergMarquardt, PseudoTransient, LimitedMemoryBroyden, DFSane,
+    ILU0Preconditioner, ILUTPreconditioner, AMGPreconditioner, IDENTITY, EisenstatWalkerForcing2, RadiusUpdateSchemes, BackTracking, LineSearchesJL, NewtonRaphson, TrustRegion, GaussNewton, LevenbergMarquardt, PseudoTransient, LimitedMemoryBroyden, DFSane, Broyden, Klement,
     NonlinearLeastSquaresProblem,
     AbsNormSafeBestTerminationMode, NormTerminationMode, RelTerminationMode, RelNormTerminationMode,
     RelNormSafeTerminationMode, RelNormSafeBestTerminationMode, AbsTerminationMode, AbsNormTerminationMode,
@@ -22,4 +22,4 @@ from .core import (  # noqa: F401
     GMRES, BandedLU, JacobianOperator, JacVecOperator, VecJacOperator, StatefulJacobianOperator,
     StatefulJacobianNormalFormOperator,
 )
-from .polyalg import NonlinearSolvePolyAlgorithm, RobustMultiNewton, FastShortcutNLLSPolyalg, PolyAlgorithmCache  # noqa: F401
+from .polyalg import NonlinearSolvePolyAlgorithm, RobustMultiNewton, FastShortcutNLLSPolyalg, FastShortcutNonlinearPolyalg, PolyAlgorithmCache  # noqa: F401

@@ -24,6 +24,11 @@ PROBLEM_QUADRATIC, PROBLEM_BRATU2D, PROBLEM_BRUSSELATOR2D, PROBLEM_USER = 1, 2, 
 ALG_NEWTON_RAPHSON, ALG_TRUST_REGION, ALG_GAUSS_NEWTON, ALG_LEVENBERG_MARQUARDT, ALG_PSEUDO_TRANSIENT = 0, 1, 2, 3, 4
 ALG_LIMITED_MEMORY_BROYDEN = 5
 ALG_DFSANE = 6
+ALG_BROYDEN = 7
+ALG_KLEMENT = 8
+BROYDEN_MAX_N = 32768
+BROYDEN_RULES = {"good_broyden": 0, "bad_broyden": 1, "diagonal": 2}
+BROYDEN_TRUE_JACOBIAN = 16
 LINSOLVE_GMRES_MATFREE, LINSOLVE_GMRES_CSR, LINSOLVE_BANDED_LU = 0, 1, 2
 ORTHO_MGS, ORTHO_CGS2, ORTHO_CGS, ORTHO_DCGS2, ORTHO_DCGS2_1R, ORTHO_SSTEP = 0, 1, 2, 3, 4, 5
 FORCING_NONE, FORCING_EW2 = 0, 1
@@ -90,6 +95,8 @@ class Options(C.Structure):
         ("sane_M", C.c_int32),
         ("sane_gamma", C.c_double), ("sane_tau_min", C.c_double), ("sane_tau_max", C.c_double),
         ("sane_n_exp", C.c_int32), ("sane_max_inner_iterations", C.c_int32),
+        ("broyden_update_rule", C.c_int32), ("qn_max_resets", C.c_int32),
+        ("qn_reset_tolerance", C.c_double), ("qn_alpha", C.c_double),
     ]
 
 
@@ -257,6 +264,8 @@ SIGNATURES = {
                                          C.POINTER(_I)]),
     "nk_solver_get_dfsane_state": (_I, [_P, C.POINTER(_D), C.POINTER(_D), C.POINTER(_I), C.POINTER(_I), C.POINTER(_I),
                                        C.POINTER(_D)]),
+    "nk_solver_get_qn_state": (_I, [_P, C.POINTER(_I), C.POINTER(_D), C.POINTER(_I), C.POINTER(_I), C.POINTER(_I)]),
+    "nk_solver_get_broyden_inverse": (_I, [_P, _P, _L, _I]),
     "nk_solver_get_trace": (_I, [_P, C.POINTER(TraceEntry), _I, C.POINTER(_I)]),
     "nk_newton_solve": (_I, [_P, _P, _I, C.POINTER(Options), _P, _P, C.POINTER(Stats), C.POINTER(_I)]),
     "nk_dot": (_I, [_P, _L, _P, _P, C.POINTER(_D)]),

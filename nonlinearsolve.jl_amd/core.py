@@ -876,6 +876,46 @@ class LimitedMemoryBroyden:  # lib/NonlinearSolveQuasiNewton/src/lbroyden.jl:20-
                 f"reset_tolerance={self.reset_tolerance}, alpha={self.alpha})")
 
 
+class Broyden:  # lib/NonlinearSolveQuasiNewton/src/broyden.jl:34-49
+    """Broyden(; max_resets = 100, linesearch = nothing, reset_tolerance = nothing, init_jacobian = Val(:identity), alpha = nothing,
+    update_rule = Val(:good_broyden)): the inverse Jacobian itself, a dense n×n matrix on the device that starts as I/α
+    (`update_rule` "good_broyden" or "bad_broyden"), or its diagonal ("diagonal"), with NoChangeInStateReset. Needs only the
+    residual. The dense matrix is allocated by the first step and is limited to n ≤ 32768 (8 GiB); `init` raises above that.
+    init_jacobian = "true_jacobian" and the line-search form are not built."""
+    linsolve = None
+    name = "Broyden"
+
+    def __init__(self, max_resets: int = 100, linesearch=None, reset_tolerance: Optional[float] = None,
+                 init_jacobian: str = "identity", alpha: Optional[float] = None, update_rule: str = "good_broyden"):
+        if update_rule not in L.BROYDEN_RULES:
+            raise ValueError(f"Unknown update rule `update_rule = {update_rule!r}`. Please choose a valid update rule.")
+        if init_jacobian not in ("identity", "true_jacobian"):
+            raise ValueError(f"Unknown `init_jacobian = {init_jacobian!r}`. Please choose a valid `init_jacobian`.")
+        self.max_resets, self.linesearch, self.reset_tolerance = int(max_resets), linesearch, reset_tolerance
+        self.init_jacobian, self.alpha, self.update_rule = init_jacobian, alpha, update_rule
+
+    def __repr__(self):
+        return (f"Broyden(max_resets={self.max_resets}, reset_tolerance={self.reset_tolerance}, "
+                f"init_jacobian={self.init_jacobian!r}, alpha={self.alpha}, update_rule={self.update_rule!r})")
+
+
+class Klement:  # lib/NonlinearSolveQuasiNewton/src/klement.jl:29-48
+    """Klement(; max_resets = 100, linsolve = nothing, linesearch = nothing, alpha = nothing, init_jacobian = Val(:identity)): J is
+    the vector α·1 (DiagonalStructure, not inverted), the step −fu ./ J, the reset test any(iszero, J). Needs only the residual;
+    `linsolve` is not read (a diagonal J needs none). The true-Jacobian initialisations and the line-search form are not built."""
+    name = "Klement"
+
+    def __init__(self, max_resets: int = 100, linsolve=None, linesearch=None, alpha: Optional[float] = None,
+                 init_jacobian: str = "identity"):
+        if init_jacobian not in ("identity", "true_jacobian", "true_jacobian_diagonal"):
+            raise ValueError(f"Unknown `init_jacobian = {init_jacobian!r}`. Please choose a valid `init_jacobian`.")
+        self.max_resets, self.linsolve, self.linesearch = int(max_resets), linsolve, linesearch
+        self.alpha, self.init_jacobian = alpha, init_jacobian
+
+    def __repr__(self):
+        return f"Klement(max_resets={self.max_resets}, alpha={self.alpha}, init_jacobian={self.init_jacobian!r})"
+
+
 class DFSane:  # lib/NonlinearSolveSpectralMethods/src/dfsane.jl:21-35
     """DFSane(; sigma_min = 1e-10, sigma_max = 1e10, sigma_1 = nothing, M = 10, gamma = 1e-4, tau_min = 0.1, tau_max = 0.5,
     n_exp = 2, max_inner_iterations = 100): the spectral residual method, step −ασ f with σ = ⟨δu,δu⟩/⟨δu,δf⟩ and the
@@ -991,6 +1031,18 @@ def _options(alg, abstol, reltol, maxiters, maxtime, store_trace, termination_kw
         o.lb_threshold, o.lb_max_resets = alg.threshold, alg.max_resets
         o.lb_reset_tolerance = 0.0 if alg.reset_tolerance is None else float(alg.reset_tolerance)
         o.lb_alpha = 0.0 if alg.alpha is None else float(alg.alpha)
+        ls = KrylovJL_GMRES()
+        o.linsolve = L.LINSOLVE_GMRES_MATFREE
+    elif isinstance(alg, (Broyden, Klement)):   # likewise; a line search reaches the library, which refuses it (NK_E_INVALID)
+        o.algorithm = L.ALG_BROYDEN if isinstance(alg, Broyden) else L.ALG_KLEMENT
+        if alg.max_resets < 1:
+            raise ValueError(f"{alg.name}: max_resets must be positive")
+        o.broyden_update_rule = L.BROYDEN_RULES[getattr(alg, "update_rule", "good_broyden")]
+        if alg.init_jacobian != "identity":
+            o.broyden_update_rule += L.BROYDEN_TRUE_JACOBIAN
+        o.qn_max_resets = alg.max_resets
+        o.qn_reset_tolerance = 0.0 if getattr(alg, "reset_tolerance", None) is None else float(alg.reset_tolerance)
+        o.qn_alpha = 0.0 if alg.alpha is None else float(alg.alpha)
         ls = KrylovJL_GMRES()
         o.linsolve = L.LINSOLVE_GMRES_MATFREE
     elif isinstance(alg, DFSane):   # likewise: the residual and nothing else
@@ -1189,6 +1241,29 @@ class FirstOrderCache:
         check(L.lib().nk_solver_get_lbroyden_state(self._h, C.byref(r), C.byref(i), C.byref(a), C.byref(t), C.byref(d),
                                                    C.byref(f)))
         return dict(nresets=r.value, idx=i.value, a=a.value, threshold=t.value, since_du=d.value, since_dfu=f.value)
+
+    @property
+    def qn_state(self) -> dict:
+        """Broyden / Klement: resets counted, the scaling of the last (re)initialisation (Broyden: a of J⁻¹ = a·I; Klement: α
+        of J = α·1), the reset test's two counters and the steps since the last reset"""
+        r, d, f, k = C.c_int(), C.c_int(), C.c_int(), C.c_int()
+        a = C.c_double()
+        check(L.lib().nk_solver_get_qn_state(self._h, C.byref(r), C.byref(a), C.byref(d), C.byref(f), C.byref(k)))
+        return dict(nresets=r.value, a=a.value, since_du=d.value, since_dfu=f.value, steps_since_reset=k.value)
+
+    def broyden_inverse(self):
+        """Broyden: J⁻¹ as it stands — an n×n tensor (array for a host u0), or the n diagonal entries for update_rule =
+        "diagonal"; Klement: the n diagonal entries of J. It exists from the first step on."""
+        dense = isinstance(self.alg, Broyden) and self.alg.update_rule != "diagonal"
+        shape = (self.n, self.n) if dense else (self.n,)
+        if self._u0_is_torch and self.prob.u0.is_cuda:
+            out = torch.empty(shape, dtype=torch.float64, device=self.prob.u0.device)
+            p, ms = C.c_void_p(out.data_ptr()), L.DEVICE
+        else:
+            out = np.empty(shape)
+            p, ms = out.ctypes.data_as(C.c_void_p), L.HOST
+        check(L.lib().nk_solver_get_broyden_inverse(self._h, p, self.n, ms))
+        return out
 
     @property
     def dfsane_state(self) -> dict:

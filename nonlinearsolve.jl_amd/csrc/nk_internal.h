@@ -894,6 +894,25 @@ int nk_sane_reduce(nk_sane *W, const double *ft, const double *f);
 double *nk_sane_scalars(nk_sane *W);   // device: [0] Σf_t², [1] max|f_t| (NaN-propagating), [2] Σ f·(f_t − f)
 double nk_sane_pass_bytes(int64_t n);
 
+// ---- Broyden and Klement (nk_qn.hip): the dense inverse Jacobian (good / bad Broyden), its diagonal (DiagonalStructure), or
+// Klement's diagonal J. The driver is nk_solver.hip: qn_step. The dense matrix is allocated by the first nk_qn_fill.
+enum { NK_QN_GOOD = 0, NK_QN_BAD = 1, NK_QN_DIAGONAL = 2, NK_QN_KLEMENT = 3 };
+struct nk_qn;
+int nk_qn_create(nk_ctx *ctx, int64_t n, int kind, nk_qn **out);   // dense and n > NK_BROYDEN_MAX_N: NK_E_UNSUPPORTED, nothing allocated
+void nk_qn_destroy(nk_qn *W);
+int nk_qn_restart(nk_qn *W);
+int nk_qn_fill(nk_qn *W, double a);                                // dense: J⁻¹ = a·I
+int nk_qn_direction(nk_qn *W, int mode, int fill, double a, double tol, const double *fu, const double *u, double *u_new);
+int nk_qn_reduce(nk_qn *W, const double *fu_new, const double *fu_prev, const double *ref, double tol);
+// device scalars: [0] max|fu| (NaN-propagating), [1] ‖fu‖², [2] ‖δu‖², [3] any(|δu_i| ≤ tol), [4] any(|fu_i − ref_i| ≤ tol),
+// [5] ‖u‖² of the iterate fu belongs to; Klement: [9] any(J_i == 0), [10] ‖δu_next‖²
+double *nk_qn_scalars(nk_qn *W);
+const double *nk_qn_du(const nk_qn *W);
+int nk_qn_update(nk_qn *W, const double *fu_new);
+int nk_qn_klement_step(nk_qn *W, const double *fu_new, const double *fu_prev, const double *u, double *u_next);
+int nk_qn_copy_matrix(nk_qn *W, double *out, int64_t ldo, int memspace);
+void nk_qn_pass_bytes(int64_t n, int kind, double bytes[3]);
+
 // ----------------------------------------------------------------------------- misc helpers
 // The library's "synchronous" memsets and copies, ORDERED ON THE CONTEXT'S STREAM. hipMemset / hipMemcpy run on the null stream:
 // a caller's stream created with hipStreamNonBlocking (PyTorch's, AMDGPU.jl's) is not ordered against it, and hipMemset of device

@@ -538,3 +538,551 @@ int nk_sane_reduce(nk_sane *W, const double *ft, const double *f) {
 double *nk_sane_scalars(nk_sane *W) { return W->sc; }
 // algorithmic bytes of the two passes of one trial (what tools/dfsane_bench.py divides by)
 double nk_sane_pass_bytes(int64_t n) { return 40.0 * (double)n; }
+
+// ============================================================================= Broyden and Klement (nk_solver.hip: qn_step)
+// Broyden (lib/NonlinearSolveQuasiNewton/src/broyden.jl:129-167) keeps the inverse Jacobian itself: a dense n×n matrix, row-major
+// with ld = n rounded up to even + NK_LDV_PAD_DEFAULT so that every row starts 16-byte aligned, or its diagonal (DiagonalStructure).
+// Klement (klement.jl:116-128) keeps the diagonal of J, not inverted. A step of the dense form is the residual kernel plus
+//   k_qn_update   vectors: δu = −(row sums pass B left) — or −(a·fu) after a reset —, u_new = u + δu, partials of ‖δu‖², ‖u_new‖², any(|δu| ≤ tol)
+//   k_qn_reduce   vectors: dfu = fu_new − fu_prev, max|fu|, ‖fu‖², ‖dfu‖², the reset test's dfu flag: what the host reads for this step
+//   k_bd_pass_a   ONE READ of J⁻¹: a workgroup owns BD_R rows across all columns; it completes w = J⁻¹dfu for its rows and
+//                 δu·w over them, and writes its partial column sums of z = J⁻ᵀδu to zpart[tile][·]
+//   k_bd_fold     z = Σ_tiles zpart, tiles in ascending order; denom = Σ_tiles (δu·w), 1e-5 if exactly 0     (good Broyden only)
+//   k_bd_pass_b   ONE READ + ONE WRITE: J⁻¹ᵢⱼ += cᵢ zⱼ, c = (δu − w)/denom, and in the same pass the row sums (J⁻¹_new fu)ᵢ
+// 24·n² bytes plus 16·n²/BD_R for zpart. Bad Broyden has z = dfu and denom = ‖dfu‖²: no z pass. A reset is k_bd_fill. No workgroup
+// waits for another, every sum has a fixed order, nothing is accumulated with atomics: two runs give the same bits.
+constexpr int BD_R = 32;   // rows of a tile: 32 row accumulators per lane
+enum { QN_FNORM_INF = 0, QN_FNORM_SS = 1, QN_DU_SS = 2, QN_FLAG_DU = 3, QN_FLAG_DFU = 4, QN_U_SS = 5, QN_DFU_SS = 6, QN_DIAG_DEN = 7,
+       QN_DENOM = 8, QN_FLAG_ZERO = 9, QN_NEXT_SS = 10, QN_NSCAL = 11 };
+constexpr int QN_NRED = 5;   // slots a reduce pass writes per workgroup
+
+struct nk_qn {
+  nk_ctx *ctx = nullptr;
+  int64_t n = 0, ld = 0, ldz = 0;
+  int kind = 0, tiles = 0;
+  double *Jm = nullptr, *zpart = nullptr;                     // the dense form: allocated by the first fill
+  double *Jd = nullptr, *du = nullptr, *dnext = nullptr, *w = nullptr, *z = nullptr, *dfu = nullptr, *dpart = nullptr;
+  double *sc = nullptr, *part = nullptr, *part0 = nullptr;
+  unsigned int *ticket = nullptr;
+  int grid0 = 0;       // workgroups of the last k_qn_update whose partial sums nobody has folded yet (0: none)
+};
+
+__device__ __forceinline__ double qn_denom(double v) { return v == 0.0 ? 1.0e-5 : v; }   // ifelse(iszero(denom), T(1.0e-5), denom)
+
+// ----------------------------------------------------------------------------- vectors: the step
+// mode 0: δu = −(a·fu)   mode 1: δu = −src   mode 2: δu = −(Jd·fu)   mode 3: δu = −(fu/Jd);   fill: Jd = a first (a reset)
+__global__ __launch_bounds__(NK_BLOCK) void k_qn_update(int64_t n, int mode, int fill, double a, double tol,
+                                                        const double *__restrict__ fu, const double *__restrict__ src,
+                                                        double *__restrict__ Jd, const double *__restrict__ u,
+                                                        double *__restrict__ unew, double *__restrict__ du,
+                                                        double *__restrict__ part0) {
+  __shared__ double sm[12];
+  double sd = 0.0, su = 0.0, fl = 0.0;
+  const int64_t stride = (int64_t)gridDim.x * NK_BLOCK;
+  for (int64_t i = (int64_t)blockIdx.x * NK_BLOCK + threadIdx.x; i < n; i += stride) {
+    double d;
+    if (mode == 0) d = -(a * fu[i]);
+    else if (mode == 1) d = -src[i];
+    else {
+      double j = a;
+      if (fill) Jd[i] = a; else j = Jd[i];
+      d = mode == 2 ? -(j * fu[i]) : -(fu[i] / j);
+    }
+    const double un = u[i] + d;
+    du[i] = d;
+    unew[i] = un;
+    sd += d * d;
+    su += un * un;
+    if (fabs(d) <= tol) fl = 1.0;
+  }
+  sd = lb_wave_sum(sd);
+  su = lb_wave_sum(su);
+  fl = lb_wave_nanmax(fl);
+  const int w = threadIdx.x >> 6;
+  if ((threadIdx.x & 63) == 0) { sm[w] = sd; sm[4 + w] = su; sm[8 + w] = fl; }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    part0[blockIdx.x] = (sm[0] + sm[1]) + (sm[2] + sm[3]);
+    part0[gridDim.x + blockIdx.x] = (sm[4] + sm[5]) + (sm[6] + sm[7]);
+    part0[2 * gridDim.x + blockIdx.x] = nk_nanmax(nk_nanmax(sm[8], sm[9]), nk_nanmax(sm[10], sm[11]));
+  }
+}
+
+// the last workgroup of a reduce pass: slot s < QN_NRED of `part` and the three slots of an unfolded k_qn_update, one wavefront
+// per slot in turn, workgroup partials in ascending order per lane. dst[s]: the scalar slot s lands in (QN_NRED + 3 entries);
+// maxmask: the slots of `part` combined with the NaN-propagating maximum.
+__device__ __forceinline__ void qn_fold_slots(const double *part, int nwg, const double *part0, int grid0, double *sc,
+                                              const int *dst, unsigned int maxmask) {
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+  for (int s = wid; s < QN_NRED + 3; s += 4) {
+    if (s >= QN_NRED && grid0 == 0) continue;
+    const bool is_max = s < QN_NRED ? ((maxmask >> s) & 1u) != 0u : s == QN_NRED + 2;
+    const double *p = s < QN_NRED ? part + (size_t)s * nwg : part0 + (size_t)(s - QN_NRED) * grid0;
+    const int cnt = s < QN_NRED ? nwg : grid0;
+    double v = 0.0;
+    for (int b = lane; b < cnt; b += 64) v = is_max ? nk_nanmax(v, p[b]) : v + p[b];
+    v = is_max ? lb_wave_nanmax(v) : lb_wave_sum(v);
+    if (lane == 0) sc[dst[s]] = v;
+  }
+}
+
+// ----------------------------------------------------------------------------- vectors: what the host reads (Broyden)
+struct qn_reduce_args {
+  int64_t n;
+  const double *x, *xp, *y, *r, *Jd;   // fu_new, fu_prev, δu, the residual the reset test compares with; Jd: NULL or the diagonal
+  double tol;
+  int den;                              // what sc[QN_DENOM] becomes: 0 nothing (pass A's fold writes it), 1 ‖dfu‖², 2 Σ Jd·dfu·δu
+  double *dfu;
+  const double *part0;
+  int grid0;
+  double *part, *sc;
+  unsigned int *ticket;
+};
+__global__ __launch_bounds__(NK_BLOCK) void k_qn_reduce(qn_reduce_args a) {
+  constexpr int NS = QN_NRED;   // max|x|, Σx², flag dfu, Σdfu², Σ (Jd·dfu)·δu
+  __shared__ double sm[4 * NS + 1];
+  double mx = 0.0, ss = 0.0, fdf = 0.0, sd = 0.0, dd = 0.0;
+  const int64_t stride = (int64_t)gridDim.x * NK_BLOCK;
+  for (int64_t i = (int64_t)blockIdx.x * NK_BLOCK + threadIdx.x; i < a.n; i += stride) {
+    const double xv = a.x[i], df = xv - a.xp[i];
+    a.dfu[i] = df;
+    mx = nk_nanmax(mx, fabs(xv));
+    ss += xv * xv;
+    if (fabs(xv - a.r[i]) <= a.tol) fdf = 1.0;
+    sd += df * df;
+    if (a.Jd) dd += (a.Jd[i] * df) * a.y[i];
+  }
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+  {
+    const double v0 = lb_wave_nanmax(mx), v1 = lb_wave_sum(ss), v2 = lb_wave_nanmax(fdf), v3 = lb_wave_sum(sd), v4 = lb_wave_sum(dd);
+    if (lane == 0) { sm[wid * NS] = v0; sm[wid * NS + 1] = v1; sm[wid * NS + 2] = v2; sm[wid * NS + 3] = v3; sm[wid * NS + 4] = v4; }
+  }
+  __syncthreads();
+  if ((int)threadIdx.x < NS) {
+    const int s = threadIdx.x;
+    const double p0 = sm[s], p1 = sm[NS + s], p2 = sm[2 * NS + s], p3 = sm[3 * NS + s];
+    a.part[(size_t)s * gridDim.x + blockIdx.x] = (s == 0 || s == 2) ? nk_nanmax(nk_nanmax(p0, p1), nk_nanmax(p2, p3)) : (p0 + p1) + (p2 + p3);
+  }
+  if (!lb_arrive_last(a.ticket, gridDim.x, &sm[4 * NS])) return;
+  __shared__ int dst[NS + 3];
+  if (threadIdx.x == 0) {
+    dst[0] = QN_FNORM_INF; dst[1] = QN_FNORM_SS; dst[2] = QN_FLAG_DFU; dst[3] = QN_DFU_SS; dst[4] = QN_DIAG_DEN;
+    dst[5] = QN_DU_SS; dst[6] = QN_U_SS; dst[7] = QN_FLAG_DU;
+  }
+  __syncthreads();
+  qn_fold_slots(a.part, gridDim.x, a.part0, a.grid0, a.sc, dst, 0x5u);
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    if (a.den) a.sc[QN_DENOM] = qn_denom(a.sc[a.den == 1 ? QN_DFU_SS : QN_DIAG_DEN]);
+    *a.ticket = 0u;   // (for the next launch: the kernel boundary publishes it)
+  }
+}
+
+// ----------------------------------------------------------------------------- the dense inverse: fill, pass A, fold, pass B
+__global__ __launch_bounds__(NK_BLOCK) void k_bd_fill(int64_t n, int64_t ld, int64_t ldz, double a, double *__restrict__ J) {
+  const int64_t hp = ldz >> 1, total = n * hp, stride = (int64_t)gridDim.x * NK_BLOCK;
+  for (int64_t t = (int64_t)blockIdx.x * NK_BLOCK + threadIdx.x; t < total; t += stride) {
+    const int64_t i = t / hp, p = t - i * hp;
+    reinterpret_cast<double2 *>(J + (size_t)i * ld)[p] = make_double2(2 * p == i ? a : 0.0, 2 * p + 1 == i ? a : 0.0);
+  }
+}
+
+struct bd_args {
+  int64_t n, ld, ldz;
+  double *J;
+  const double *x;       // pass A: dfu.   pass B: fu_new
+  const double *du;
+  double *w;             // pass A writes it, pass B reads it
+  const double *z;       // pass B: z (good Broyden) or dfu (bad Broyden)
+  double *zpart, *dpart; // pass A, good Broyden only (zpart NULL: no z pass)
+  double *dnext;         // pass B: (J⁻¹_new fu)ᵢ
+  const double *sc;
+};
+
+// a tile's sweep over all column pairs. FULL: all BD_R rows exist (no row predicate around the loads).
+template <bool FULL>
+__device__ __forceinline__ void bd_sweep_a(const bd_args &a, int64_t row0, int nr, const double *sdu, double (&acc)[BD_R]) {
+  const int64_t npair = a.n >> 1;
+  const double2 *x2 = reinterpret_cast<const double2 *>(a.x);
+  double2 *zp2 = a.zpart ? reinterpret_cast<double2 *>(a.zpart + (size_t)blockIdx.x * a.ldz) : nullptr;
+  for (int64_t p = threadIdx.x; p < npair; p += NK_BLOCK) {
+    const double2 xv = x2[p];
+    double2 zz = make_double2(0.0, 0.0);
+#pragma unroll
+    for (int c = 0; c < BD_R; c += 8) {
+      double2 jv[8];
+#pragma unroll
+      for (int k = 0; k < 8; ++k)
+        if (FULL || c + k < nr) jv[k] = reinterpret_cast<const double2 *>(a.J + (size_t)(row0 + c + k) * a.ld)[p];
+#pragma unroll
+      for (int k = 0; k < 8; ++k)
+        if (FULL || c + k < nr) {
+          acc[c + k] += jv[k].x * xv.x + jv[k].y * xv.y;
+          zz.x += jv[k].x * sdu[c + k];
+          zz.y += jv[k].y * sdu[c + k];
+        }
+    }
+    if (zp2) zp2[p] = zz;
+  }
+}
+template <bool FULL>
+__device__ __forceinline__ void bd_sweep_b(const bd_args &a, int64_t row0, int nr, const double *sc_, double (&acc)[BD_R]) {
+  const int64_t npair = a.n >> 1;
+  const double2 *x2 = reinterpret_cast<const double2 *>(a.x), *z2 = reinterpret_cast<const double2 *>(a.z);
+  for (int64_t p = threadIdx.x; p < npair; p += NK_BLOCK) {
+    const double2 xv = x2[p], zv = z2[p];
+#pragma unroll
+    for (int c = 0; c < BD_R; c += 8) {
+      double2 jv[8];
+#pragma unroll
+      for (int k = 0; k < 8; ++k)
+        if (FULL || c + k < nr) jv[k] = reinterpret_cast<const double2 *>(a.J + (size_t)(row0 + c + k) * a.ld)[p];
+#pragma unroll
+      for (int k = 0; k < 8; ++k)
+        if (FULL || c + k < nr) {
+          jv[k].x += sc_[c + k] * zv.x;
+          jv[k].y += sc_[c + k] * zv.y;
+          reinterpret_cast<double2 *>(a.J + (size_t)(row0 + c + k) * a.ld)[p] = jv[k];
+          acc[c + k] += jv[k].x * xv.x + jv[k].y * xv.y;
+        }
+    }
+  }
+}
+// the workgroup's row sums: acc[r] over all lanes → out[r] in lanes r < BD_R of wavefront 0 (returned), fixed order
+__device__ __forceinline__ double bd_row_sums(double (&acc)[BD_R], double *sm) {
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+#pragma unroll
+  for (int r = 0; r < BD_R; ++r) {
+    const double s = lb_wave_sum(acc[r]);
+    if (lane == 0) sm[wid * BD_R + r] = s;
+  }
+  __syncthreads();
+  const int r = threadIdx.x & (BD_R - 1);
+  return (sm[r] + sm[BD_R + r]) + (sm[2 * BD_R + r] + sm[3 * BD_R + r]);
+}
+
+__global__ __launch_bounds__(NK_BLOCK) void k_bd_pass_a(bd_args a) {
+  __shared__ double sdu[BD_R], sm[4 * BD_R];
+  const int64_t row0 = (int64_t)blockIdx.x * BD_R;
+  const int nr = (int)((a.n - row0) < BD_R ? (a.n - row0) : BD_R);
+  if ((int)threadIdx.x < BD_R) sdu[threadIdx.x] = (int)threadIdx.x < nr ? a.du[row0 + threadIdx.x] : 0.0;
+  __syncthreads();
+  double acc[BD_R];
+#pragma unroll
+  for (int r = 0; r < BD_R; ++r) acc[r] = 0.0;
+  if (nr == BD_R) bd_sweep_a<true>(a, row0, nr, sdu, acc);
+  else bd_sweep_a<false>(a, row0, nr, sdu, acc);
+  if ((a.n & 1) && threadIdx.x == 0) {  // odd tail: the last column
+    const int64_t j = a.n - 1;
+    const double xv = a.x[j];
+    double zt = 0.0;
+#pragma unroll
+    for (int r = 0; r < BD_R; ++r)
+      if (r < nr) {
+        const double v = a.J[(size_t)(row0 + r) * a.ld + j];
+        acc[r] += v * xv;
+        zt += v * sdu[r];
+      }
+    if (a.zpart) a.zpart[(size_t)blockIdx.x * a.ldz + j] = zt;
+  }
+  const double wr = bd_row_sums(acc, sm);
+  if (threadIdx.x < 64) {
+    const int r = threadIdx.x;
+    double dp = 0.0;
+    if (r < nr) { a.w[row0 + r] = wr; dp = sdu[r] * wr; }
+    dp = lb_wave_sum(dp);
+    if (r == 0 && a.dpart) a.dpart[blockIdx.x] = dp;
+  }
+}
+
+// z = Σ_tiles zpart (ascending); workgroup 0 also folds δu·w and writes the denominator
+__global__ __launch_bounds__(NK_BLOCK) void k_bd_fold(int64_t n, int64_t ldz, int tiles, const double *__restrict__ zpart,
+                                                      const double *__restrict__ dpart, double *__restrict__ z,
+                                                      double *__restrict__ sc) {
+  const int64_t npair = n >> 1, p = (int64_t)blockIdx.x * NK_BLOCK + threadIdx.x;
+  if (p < npair) {
+    double2 zz = make_double2(0.0, 0.0);
+    for (int t = 0; t < tiles; ++t) {
+      const double2 v = reinterpret_cast<const double2 *>(zpart + (size_t)t * ldz)[p];
+      zz.x += v.x;
+      zz.y += v.y;
+    }
+    reinterpret_cast<double2 *>(z)[p] = zz;
+  }
+  if ((n & 1) && p == npair) {   // odd tail (npair < gridDim.x·NK_BLOCK: the grid covers npair + 1 lanes)
+    double zt = 0.0;
+    for (int t = 0; t < tiles; ++t) zt += zpart[(size_t)t * ldz + (n - 1)];
+    z[n - 1] = zt;
+  }
+  if (blockIdx.x == 0 && threadIdx.x < 64) {
+    double v = 0.0;
+    for (int b = threadIdx.x; b < tiles; b += 64) v += dpart[b];
+    v = lb_wave_sum(v);
+    if (threadIdx.x == 0) sc[QN_DENOM] = qn_denom(v);
+  }
+}
+
+__global__ __launch_bounds__(NK_BLOCK) void k_bd_pass_b(bd_args a) {
+  __shared__ double scf[BD_R], sm[4 * BD_R];
+  const int64_t row0 = (int64_t)blockIdx.x * BD_R;
+  const int nr = (int)((a.n - row0) < BD_R ? (a.n - row0) : BD_R);
+  if ((int)threadIdx.x < BD_R)
+    scf[threadIdx.x] = (int)threadIdx.x < nr ? (a.du[row0 + threadIdx.x] - a.w[row0 + threadIdx.x]) / a.sc[QN_DENOM] : 0.0;
+  __syncthreads();
+  double acc[BD_R];
+#pragma unroll
+  for (int r = 0; r < BD_R; ++r) acc[r] = 0.0;
+  if (nr == BD_R) bd_sweep_b<true>(a, row0, nr, scf, acc);
+  else bd_sweep_b<false>(a, row0, nr, scf, acc);
+  if ((a.n & 1) && threadIdx.x == 0) {  // odd tail: the last column
+    const int64_t j = a.n - 1;
+    const double xv = a.x[j], zv = a.z[j];
+#pragma unroll
+    for (int r = 0; r < BD_R; ++r)
+      if (r < nr) {
+        const double v = a.J[(size_t)(row0 + r) * a.ld + j] + scf[r] * zv;
+        a.J[(size_t)(row0 + r) * a.ld + j] = v;
+        acc[r] += v * xv;
+      }
+  }
+  const double s = bd_row_sums(acc, sm);
+  if ((int)threadIdx.x < nr) a.dnext[row0 + threadIdx.x] = s;
+}
+
+// the diagonal form of good Broyden (broyden.jl:149-167): J⁻¹ += (δu − t)·δu·J⁻¹/denom, t = J⁻¹·dfu·δu, denom = Σt (k_qn_reduce)
+__global__ __launch_bounds__(NK_BLOCK) void k_bd_diag_update(int64_t n, double *__restrict__ Jd, const double *__restrict__ du,
+                                                             const double *__restrict__ dfu, const double *__restrict__ sc) {
+  const double den = sc[QN_DENOM];
+  const int64_t stride = (int64_t)gridDim.x * NK_BLOCK;
+  for (int64_t i = (int64_t)blockIdx.x * NK_BLOCK + threadIdx.x; i < n; i += stride) {
+    const double j = Jd[i], d = du[i], t = (j * dfu[i]) * d;
+    Jd[i] = j + (((d - t) * d) * j) / den;
+  }
+}
+
+// ----------------------------------------------------------------------------- Klement: the whole step in one launch
+// the update of J from the step just taken (klement.jl:116-128), any(iszero, J), the NEXT δu = −(fu ./ J) and u + δu, and every
+// sum the host reads: max|fu|, ‖fu‖², ‖δu_next‖², ‖u‖² (for the scaling of a reset), folded by the workgroup that arrives last
+struct kl_args {
+  int64_t n;
+  double *J, *du;                // δu: the step just taken in, the next one out
+  const double *f, *fp, *u;      // fu_new, fu_prev, the iterate fu_new belongs to
+  double *unew;
+  const double *part0;
+  int grid0;
+  double *part, *sc;
+  unsigned int *ticket;
+};
+__global__ __launch_bounds__(NK_BLOCK) void k_kl_step(kl_args a) {
+  constexpr int NS = QN_NRED;   // max|f|, Σf², flag zero, Σδu_next², Σu²
+  __shared__ double sm[4 * NS + 1];
+  double mx = 0.0, ss = 0.0, fz = 0.0, sd = 0.0, su = 0.0;
+  const int64_t stride = (int64_t)gridDim.x * NK_BLOCK;
+  for (int64_t i = (int64_t)blockIdx.x * NK_BLOCK + threadIdx.x; i < a.n; i += stride) {
+    const double f = a.f[i], d = a.du[i], uu = a.u[i];
+    double j = a.J[i];
+    const double j2 = j * j;
+    const double jdu = j2 * (d * d);
+    j = j + (((f - a.fp[i] - j * d) / (jdu == 0.0 ? 1.0e-5 : jdu)) * d) * j2;
+    a.J[i] = j;
+    if (j == 0.0) fz = 1.0;
+    const double dn = -(f / j);
+    a.du[i] = dn;
+    a.unew[i] = uu + dn;
+    mx = nk_nanmax(mx, fabs(f));
+    ss += f * f;
+    sd += dn * dn;
+    su += uu * uu;
+  }
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+  {
+    const double v0 = lb_wave_nanmax(mx), v1 = lb_wave_sum(ss), v2 = lb_wave_nanmax(fz), v3 = lb_wave_sum(sd), v4 = lb_wave_sum(su);
+    if (lane == 0) { sm[wid * NS] = v0; sm[wid * NS + 1] = v1; sm[wid * NS + 2] = v2; sm[wid * NS + 3] = v3; sm[wid * NS + 4] = v4; }
+  }
+  __syncthreads();
+  if ((int)threadIdx.x < NS) {
+    const int s = threadIdx.x;
+    const double p0 = sm[s], p1 = sm[NS + s], p2 = sm[2 * NS + s], p3 = sm[3 * NS + s];
+    a.part[(size_t)s * gridDim.x + blockIdx.x] = (s == 0 || s == 2) ? nk_nanmax(nk_nanmax(p0, p1), nk_nanmax(p2, p3)) : (p0 + p1) + (p2 + p3);
+  }
+  if (!lb_arrive_last(a.ticket, gridDim.x, &sm[4 * NS])) return;
+  __shared__ int dst[NS + 3];
+  if (threadIdx.x == 0) {   // (an unfolded k_qn_update's ‖u_new‖² is this launch's Σu² summed in another order: it goes to a slot Klement does not read)
+    dst[0] = QN_FNORM_INF; dst[1] = QN_FNORM_SS; dst[2] = QN_FLAG_ZERO; dst[3] = QN_NEXT_SS; dst[4] = QN_U_SS;
+    dst[5] = QN_DU_SS; dst[6] = QN_DIAG_DEN; dst[7] = QN_FLAG_DU;
+  }
+  __syncthreads();
+  qn_fold_slots(a.part, gridDim.x, a.part0, a.grid0, a.sc, dst, 0x5u);
+  if (threadIdx.x == 0) *a.ticket = 0u;
+}
+
+// ----------------------------------------------------------------------------- host side
+static int qn_vec_grid(const nk_qn *W) {   // reduce passes: at most two workgroups per CU
+  int cap = 2 * W->ctx->num_cus;
+  if (cap > LB_MAX_GRID) cap = LB_MAX_GRID;
+  if (cap < 1) cap = 1;
+  return nk_grid_for(W->n, NK_BLOCK * 4, cap);
+}
+static bool qn_dense(const nk_qn *W) { return W->kind == NK_QN_GOOD || W->kind == NK_QN_BAD; }
+
+int nk_qn_create(nk_ctx *ctx, int64_t n, int kind, nk_qn **out) {
+  NK_REQUIRE(ctx && out && n > 0, "bad argument");
+  NK_REQUIRE(kind >= NK_QN_GOOD && kind <= NK_QN_KLEMENT, "bad quasi-Newton kind %d", kind);
+  if ((kind == NK_QN_GOOD || kind == NK_QN_BAD) && n > NK_BROYDEN_MAX_N)
+    NK_FAIL(NK_E_UNSUPPORTED, "Broyden: n = %lld is above NK_BROYDEN_MAX_N = %d (the dense inverse Jacobian would exceed 8 GiB); "
+            "update_rule = diagonal, LimitedMemoryBroyden or a Jacobian-based method take such sizes", (long long)n, NK_BROYDEN_MAX_N);
+  nk_qn *W = new nk_qn();
+  auto guard = nk_make_guard(W, [](nk_qn *w) { nk_qn_destroy(w); });
+  W->ctx = ctx;
+  W->n = n;
+  W->kind = kind;
+  W->ldz = (n + 1) & ~(int64_t)1;
+  W->ld = W->ldz + NK_LDV_PAD_DEFAULT;
+  W->tiles = (int)((n + BD_R - 1) / BD_R);
+  const size_t na = (size_t)n + 2;
+  NK_TRY(nk_dev_alloc(&W->du, na));
+  NK_TRY(nk_dev_alloc(&W->dfu, na));
+  if (qn_dense(W)) {
+    NK_TRY(nk_dev_alloc(&W->dnext, na));
+    NK_TRY(nk_dev_alloc(&W->w, na));
+    NK_TRY(nk_dev_alloc(&W->z, na));
+    NK_TRY(nk_dev_alloc(&W->dpart, (size_t)W->tiles));
+  } else {
+    NK_TRY(nk_dev_alloc(&W->Jd, na));
+    NK_HIP(nk_memset(ctx, W->Jd, 0, na * sizeof(double)));
+  }
+  NK_TRY(nk_dev_alloc(&W->sc, (size_t)QN_NSCAL));
+  NK_TRY(nk_dev_alloc(&W->part, (size_t)QN_NRED * LB_MAX_GRID));
+  NK_TRY(nk_dev_alloc(&W->part0, (size_t)3 * NK_MAX_RED_BLOCKS));
+  NK_TRY(nk_dev_alloc(&W->ticket, (size_t)1));
+  NK_HIP(nk_memset(ctx, W->sc, 0, QN_NSCAL * sizeof(double)));
+  NK_HIP(nk_memset(ctx, W->du, 0, na * sizeof(double)));
+  NK_TRY(nk_qn_restart(W));
+  *out = guard.release();
+  return NK_OK;
+}
+void nk_qn_destroy(nk_qn *W) {
+  if (!W) return;
+  hipFree(W->Jm); hipFree(W->zpart); hipFree(W->Jd); hipFree(W->du); hipFree(W->dnext); hipFree(W->w); hipFree(W->z);
+  hipFree(W->dfu); hipFree(W->dpart); hipFree(W->sc); hipFree(W->part); hipFree(W->part0); hipFree(W->ticket);
+  delete W;
+}
+// a new solve: the ticket is zeroed, in stream order
+int nk_qn_restart(nk_qn *W) {
+  W->grid0 = 0;
+  NK_HIP(nk_memset(W->ctx, W->ticket, 0, sizeof(unsigned int)));
+  return NK_OK;
+}
+// J⁻¹ = a·I, write-only; the dense matrix (and zpart for good Broyden) is allocated here, by the first step of the first solve
+int nk_qn_fill(nk_qn *W, double a) {
+  nk_ctx *ctx = W->ctx;
+  NK_REQUIRE(qn_dense(W), "not a dense Broyden workspace");
+  if (!W->Jm) {
+    NK_TRY(nk_dev_alloc(&W->Jm, (size_t)W->n * (size_t)W->ld));
+    if (W->kind == NK_QN_GOOD) NK_TRY(nk_dev_alloc(&W->zpart, (size_t)W->tiles * (size_t)W->ldz));
+  }
+  const int grid = nk_grid_for(W->n * (W->ldz >> 1), NK_BLOCK * 4, 16 * (ctx->num_cus > 0 ? ctx->num_cus : 1));
+  nk_prof_scope prof_(ctx, NK_K_SCALE, 8.0 * (double)W->n * (double)W->ldz);
+  NK_LAUNCH(ctx, k_bd_fill, dim3(grid), dim3(NK_BLOCK), W->n, W->ld, W->ldz, a, W->Jm);
+  NK_HIP(hipGetLastError());
+  return NK_OK;
+}
+// δu and u_new = u + δu. mode 0: −(a·fu) (the dense form after nk_qn_fill); 1: −(the row sums the last dense update left);
+// 2: −(Jd·fu); 3: −(fu ./ Jd); fill: Jd = a first (modes 2, 3)
+int nk_qn_direction(nk_qn *W, int mode, int fill, double a, double tol, const double *fu, const double *u, double *u_new) {
+  nk_ctx *ctx = W->ctx;
+  NK_REQUIRE(mode >= 0 && mode <= 3 && (mode < 2) == qn_dense(W), "quasi-Newton: direction mode %d does not fit the structure", mode);
+  const int grid = nk_grid_for(W->n, NK_BLOCK * 4, NK_MAX_RED_BLOCKS);
+  nk_prof_scope prof_(ctx, NK_K_NEWTON_UPDATE, 40.0 * (double)W->n);
+  NK_LAUNCH(ctx, k_qn_update, dim3(grid), dim3(NK_BLOCK), W->n, mode, fill, a, tol, fu, (const double *)W->dnext, W->Jd, u, u_new,
+            W->du, W->part0);
+  NK_HIP(hipGetLastError());
+  W->grid0 = grid;
+  return NK_OK;
+}
+// Broyden: dfu and everything the host reads for this step (nk_qn_scalars: QN_FNORM_INF … QN_U_SS)
+int nk_qn_reduce(nk_qn *W, const double *fu_new, const double *fu_prev, const double *ref, double tol) {
+  nk_ctx *ctx = W->ctx;
+  NK_REQUIRE(W->kind != NK_QN_KLEMENT, "Klement has no reduce pass of its own");
+  const int grid = qn_vec_grid(W);
+  qn_reduce_args a{W->n, fu_new, fu_prev, W->du, ref, W->kind == NK_QN_DIAGONAL ? W->Jd : nullptr, tol,
+                   W->kind == NK_QN_BAD ? 1 : (W->kind == NK_QN_DIAGONAL ? 2 : 0), W->dfu, W->part0, W->grid0, W->part, W->sc, W->ticket};
+  nk_prof_scope prof_(ctx, NK_K_OTHER, 40.0 * (double)W->n);
+  NK_LAUNCH(ctx, k_qn_reduce, dim3(grid), dim3(NK_BLOCK), a);
+  NK_HIP(hipGetLastError());
+  W->grid0 = 0;
+  return NK_OK;
+}
+double *nk_qn_scalars(nk_qn *W) { return W->sc; }
+const double *nk_qn_du(const nk_qn *W) { return W->du; }
+// the update of J⁻¹ from the step nk_qn_reduce looked at, and (dense) the row sums J⁻¹_new·fu_new for the next direction
+int nk_qn_update(nk_qn *W, const double *fu_new) {
+  nk_ctx *ctx = W->ctx;
+  if (W->kind == NK_QN_DIAGONAL) {
+    const int grid = nk_grid_for(W->n, NK_BLOCK * 4, NK_MAX_RED_BLOCKS);
+    nk_prof_scope prof_(ctx, NK_K_MULTIAXPY, 32.0 * (double)W->n);
+    NK_LAUNCH(ctx, k_bd_diag_update, dim3(grid), dim3(NK_BLOCK), W->n, W->Jd, (const double *)W->du, (const double *)W->dfu,
+              (const double *)W->sc);
+    NK_HIP(hipGetLastError());
+    return NK_OK;
+  }
+  NK_REQUIRE(qn_dense(W) && W->Jm, "Broyden: no inverse Jacobian to update");
+  const bool good = W->kind == NK_QN_GOOD;
+  const double nn = (double)W->n * (double)W->n;
+  bd_args a{W->n, W->ld, W->ldz, W->Jm, W->dfu, W->du, W->w, good ? W->z : W->dfu, good ? W->zpart : nullptr,
+            good ? W->dpart : nullptr, W->dnext, W->sc};
+  {
+    nk_prof_scope prof_(ctx, NK_K_MULTIDOT, 8.0 * nn + (good ? 8.0 * nn / BD_R : 0.0));
+    NK_LAUNCH(ctx, k_bd_pass_a, dim3(W->tiles), dim3(NK_BLOCK), a);
+    NK_HIP(hipGetLastError());
+  }
+  if (good) {
+    const int grid = (int)(((W->n >> 1) + 1 + NK_BLOCK - 1) / NK_BLOCK);
+    nk_prof_scope prof_(ctx, NK_K_REDUCE_SMALL, 8.0 * nn / BD_R);
+    NK_LAUNCH(ctx, k_bd_fold, dim3(grid), dim3(NK_BLOCK), W->n, W->ldz, W->tiles, (const double *)W->zpart, (const double *)W->dpart,
+              W->z, W->sc);
+    NK_HIP(hipGetLastError());
+  }
+  a.x = fu_new;
+  {
+    nk_prof_scope prof_(ctx, NK_K_MULTIAXPY, 16.0 * nn);
+    NK_LAUNCH(ctx, k_bd_pass_b, dim3(W->tiles), dim3(NK_BLOCK), a);
+    NK_HIP(hipGetLastError());
+  }
+  return NK_OK;
+}
+// Klement's one launch per step: the update of J from (fu_new, fu_prev, δu), the zero flag, the next δu and u_next = u + δu
+int nk_qn_klement_step(nk_qn *W, const double *fu_new, const double *fu_prev, const double *u, double *u_next) {
+  nk_ctx *ctx = W->ctx;
+  NK_REQUIRE(W->kind == NK_QN_KLEMENT, "not a Klement workspace");
+  const int grid = qn_vec_grid(W);
+  kl_args a{W->n, W->Jd, W->du, fu_new, fu_prev, u, u_next, W->part0, W->grid0, W->part, W->sc, W->ticket};
+  nk_prof_scope prof_(ctx, NK_K_MULTIAXPY, 64.0 * (double)W->n);
+  NK_LAUNCH(ctx, k_kl_step, dim3(grid), dim3(NK_BLOCK), a);
+  NK_HIP(hipGetLastError());
+  W->grid0 = 0;
+  return NK_OK;
+}
+// J⁻¹ as the caller's row-major n×n matrix with leading dimension ldo, or the n diagonal entries (Klement: of J)
+int nk_qn_copy_matrix(nk_qn *W, double *out, int64_t ldo, int memspace) {
+  nk_ctx *ctx = W->ctx;
+  const hipMemcpyKind kind = memspace == NK_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+  if (qn_dense(W)) {
+    NK_REQUIRE(W->Jm, "Broyden: the inverse Jacobian exists from the first step on");
+    NK_REQUIRE(ldo >= W->n, "leading dimension %lld is below n = %lld", (long long)ldo, (long long)W->n);
+    NK_HIP(hipMemcpy2DAsync(out, (size_t)ldo * sizeof(double), W->Jm, (size_t)W->ld * sizeof(double), (size_t)W->n * sizeof(double),
+                            (size_t)W->n, kind, ctx->stream));
+  } else {
+    NK_HIP(hipMemcpyAsync(out, W->Jd, (size_t)W->n * sizeof(double), kind, ctx->stream));
+  }
+  NK_HIP(hipStreamSynchronize(ctx->stream));
+  return NK_OK;
+}
+// algorithmic bytes of the dense update's passes (what tools/broyden_bench.py divides by): pass A, the fold, pass B
+void nk_qn_pass_bytes(int64_t n, int kind, double bytes[3]) {
+  const double nn = (double)n * (double)n;
+  const bool good = kind == NK_QN_GOOD;
+  bytes[0] = 8.0 * nn + (good ? 8.0 * nn / BD_R : 0.0);
+  bytes[1] = good ? 8.0 * nn / BD_R : 0.0;
+  bytes[2] = 16.0 * nn;
+}

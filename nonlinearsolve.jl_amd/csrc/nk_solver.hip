@@ -95,6 +95,12 @@ struct nk_solver {
   double lb_a = 1.0, lb_tol = 0.0, lb_u_ss = 0.0;
   int lb_threshold = 0, lb_max_resets = 0, lb_nresets = 0, lb_since_du = 0, lb_since_dfu = 0;
   bool lb_flag_du = false, lb_flag_dfu = false;   // the reset test's any(…) flags for the NEXT step (left by this step's reduce pass)
+  // Broyden and Klement (nk_qn.hip): the reset test's state, the residual pool and the scaling are the lb_* fields above;
+  // qn_next: the iterate Klement's fused launch has prepared (u + the next δu) and ‖that δu‖²
+  nk_qn *qn = nullptr;
+  double *qn_next = nullptr, qn_next_ss = 0.0;
+  bool qn_flag_zero = false;
+  int qn_since_reset = 0;
   // DFSane (nk_qn.hip): everything but u and fu is host scalars. `sane_ss` is Σfu² of the current residual (the reduce pass of
   // the accepted trial left it), `sane_fn` the merit ‖fu‖₂^n_exp, `sane_hist` the last M merits; trials write into fu_trial
   nk_sane *sane = nullptr;
@@ -273,6 +279,10 @@ extern "C" int nk_options_default(nk_options *o) {
   o->sane_tau_max = 0.5;
   o->sane_n_exp = 2;
   o->sane_max_inner_iterations = 100;
+  o->broyden_update_rule = NK_BROYDEN_GOOD;  // Broyden() / Klement() (broyden.jl:34-38, klement.jl:29-33); tolerance and alpha: 0 = `nothing`
+  o->qn_max_resets = 100;
+  o->qn_reset_tolerance = 0.0;
+  o->qn_alpha = 0.0;
   return NK_OK;
 }
 
@@ -288,7 +298,9 @@ static bool is_lm(const nk_solver *S) { return S->o.algorithm == NK_ALG_LEVENBER
 static bool is_pt(const nk_solver *S) { return S->o.algorithm == NK_ALG_PSEUDO_TRANSIENT; }
 static bool is_lb(const nk_solver *S) { return S->o.algorithm == NK_ALG_LIMITED_MEMORY_BROYDEN; }
 static bool is_sane(const nk_solver *S) { return S->o.algorithm == NK_ALG_DFSANE; }
-static bool residual_only(const nk_solver *S) { return is_lb(S) || is_sane(S); }   // no Jacobian, no linear solve
+static bool is_klement(const nk_solver *S) { return S->o.algorithm == NK_ALG_KLEMENT; }
+static bool is_qn(const nk_solver *S) { return S->o.algorithm == NK_ALG_BROYDEN || is_klement(S); }
+static bool residual_only(const nk_solver *S) { return is_lb(S) || is_sane(S) || is_qn(S); }   // no Jacobian, no linear solve
 static bool concrete(const nk_solver *S) { return S->o.linsolve != NK_LINSOLVE_GMRES_MATFREE; }
 static bool direct(const nk_solver *S) { return S->o.linsolve == NK_LINSOLVE_BANDED_LU; }
 
@@ -591,16 +603,23 @@ static int rollback_to_best(nk_solver *S) {
 
 // ---- LimitedMemoryBroyden (lib/NonlinearSolveQuasiNewton/src/solve.jl:296-486 on BroydenLowRankJacobian)
 // Utils.initial_jacobian_scaling_alpha (NonlinearSolveBase/src/utils.jl:307-314), inverted: a = 1/α
-static double lb_scaling(const nk_solver *S, double fnorm2, double u_ss) {
-  if (S->o.lb_alpha > 0.0) return 1.0 / S->o.lb_alpha;
+static double qn_alpha(double alpha, double fnorm2, double u_ss) {
+  if (alpha > 0.0) return alpha;
   if (fnorm2 < 1.0e-5) return 1.0;
-  return 1.0 / ((2.0 * fnorm2) / fmax(sqrt(u_ss), 1.0));
+  return (2.0 * fnorm2) / fmax(sqrt(u_ss), 1.0);
+}
+static double lb_scaling(const nk_solver *S, double fnorm2, double u_ss) {
+  return 1.0 / qn_alpha(is_qn(S) ? S->o.qn_alpha : S->o.lb_alpha, fnorm2, u_ss);
 }
 // init and reinit!: idx = 0, the reset count and the reset test's counters are zero, the reset test's residual copy is f(u0)
 // (the reference's reinit! leaves that copy at the previous solve's last residual, reset_conditions.jl:47-53 — not kept:
 // a solve from the same u0 repeats itself here). a is computed by the first step, from ‖u0‖₂ and ‖f(u0)‖₂.
 static int lb_start(nk_solver *S) {
-  NK_TRY(nk_lb_restart(S->lb));
+  if (S->lb) NK_TRY(nk_lb_restart(S->lb));
+  if (S->qn) NK_TRY(nk_qn_restart(S->qn));
+  S->qn_next = nullptr;
+  S->qn_flag_zero = false;
+  S->qn_since_reset = 0;
   S->lb_nresets = S->lb_since_du = S->lb_since_dfu = 0;
   S->lb_flag_du = S->lb_flag_dfu = false;
   S->lb_ref = S->fu;
@@ -692,6 +711,107 @@ static int lb_step(nk_solver *S, int recompute) {
   if (S->force_stop) return NK_OK;
   // GoodBroydenUpdateRule: the second pass over U and V writes the new column pair
   return nk_lb_combine(S->lb, S->lb_a, S->fu);
+}
+
+// ---- Broyden and Klement (lib/NonlinearSolveQuasiNewton/src/solve.jl:296-486 on a dense or diagonal J⁻¹, or Klement's diagonal J).
+// The reset bookkeeping is LimitedMemoryBroyden's (lb_reset_test, lb_scaling, the residual pool); Klement's reset test is the
+// zero flag its fused launch left.
+static void qn_trace(nk_solver *S, double step_norm) {
+  if (!S->o.store_trace) return;
+  nk_trace_entry e;
+  memset(&e, 0, sizeof(e));
+  e.iter = S->nsteps + 1;
+  e.accepted = 1;
+  e.fnorm_inf = S->fnorm_inf;
+  e.step_norm2 = step_norm;
+  e.eta = NAN;
+  e.trust_region = NAN;
+  e.rho = NAN;
+  S->trace.push_back(e);
+}
+static int qn_step(nk_solver *S, int recompute) {
+  nk_ctx *ctx = S->ctx;
+  nk_qn *W = S->qn;
+  const bool klement = is_klement(S);
+  const int rule = S->o.broyden_update_rule;
+  const bool dense = !klement && rule != NK_BROYDEN_DIAGONAL;
+  NK_REQUIRE(recompute != 0, "%s: recompute_jacobian = false (a step without the update) is not offered", klement ? "Klement" : "Broyden");
+  bool reinit = true;
+  if (S->nsteps > 0) {
+    if (recompute < 0) {  // the standard step: the reset test decides, and its resets count
+      reinit = klement ? S->qn_flag_zero : lb_reset_test(S);
+      if (reinit && ++S->lb_nresets >= S->lb_max_resets) {
+        S->retcode = NK_RET_CONVERGENCE_FAILURE;
+        S->force_stop = true;
+        return NK_OK;
+      }
+    }
+  }
+  double *un = nullptr;
+  double next_ss = -1.0;   // ‖δu‖² of this step where a fused launch has left it already
+  if (reinit) {
+    S->qn_since_reset = S->nsteps == 0 ? 1 : 0;
+    un = spare_u(S);
+    if (klement) {         // J = α·1, δu = −(fu ./ J)
+      S->lb_a = qn_alpha(S->o.qn_alpha, S->fnorm2, S->lb_u_ss);
+      NK_TRY(nk_qn_direction(W, 3, 1, S->lb_a, S->lb_tol, S->fu, S->u, un));
+    } else {               // J⁻¹ = I/α
+      S->lb_a = lb_scaling(S, S->fnorm2, S->lb_u_ss);
+      if (dense) {
+        NK_TRY(nk_qn_fill(W, S->lb_a));
+        NK_TRY(nk_qn_direction(W, 0, 0, S->lb_a, S->lb_tol, S->fu, S->u, un));
+      } else {
+        NK_TRY(nk_qn_direction(W, 2, 1, S->lb_a, S->lb_tol, S->fu, S->u, un));
+      }
+    }
+  } else {
+    S->qn_since_reset++;
+    if (klement) {         // the last step's launch has prepared u + δu already
+      un = S->qn_next;
+      next_ss = S->qn_next_ss;
+      NK_REQUIRE(un && un != S->best_u, "Klement: the prepared iterate is gone");
+    } else {
+      un = spare_u(S);
+      NK_TRY(nk_qn_direction(W, dense ? 1 : 2, 0, S->lb_a, S->lb_tol, S->fu, S->u, un));
+    }
+  }
+  S->qn_next = nullptr;
+  S->u = un;
+  S->u_version++;
+  nk_problem_invalidate(S->P);
+  double *fnew = nullptr;
+  for (double *b : S->lb_fupool)
+    if (b != S->fu && b != S->lb_ref) { fnew = b; break; }
+  NK_TRY(nk_problem_residual_dev(S->P, S->u, fnew));
+  S->stats.nf++;
+  const double *fprev = S->fu;
+  if (S->lb_ref == nullptr) S->lb_ref = fprev;
+  S->fu = fnew;
+  double v[11];
+  double step_norm;
+  if (klement) {
+    double *nxt = spare_u(S);
+    NK_TRY(nk_qn_klement_step(W, S->fu, fprev, S->u, nxt));
+    NK_TRY(nk_scalars_to_host(ctx, nk_qn_scalars(W), 11, v));
+    S->lb_ref = S->fu;     // (Klement's reset test keeps no residual: the pool needs two buffers only)
+    S->qn_flag_zero = v[9] != 0.0;
+    S->qn_next = nxt;
+    S->qn_next_ss = v[10];
+    step_norm = sqrt(next_ss >= 0.0 ? next_ss : v[2]);
+  } else {
+    NK_TRY(nk_qn_reduce(W, S->fu, fprev, S->lb_ref, S->lb_tol));
+    NK_TRY(nk_scalars_to_host(ctx, nk_qn_scalars(W), 6, v));
+    step_norm = sqrt(v[2]);
+    S->lb_flag_du = v[3] != 0.0;
+    S->lb_flag_dfu = v[4] != 0.0;
+  }
+  S->fnorm_inf = v[0];
+  S->fnorm2 = sqrt(v[1]);
+  S->lb_u_ss = v[5];
+  NK_TRY(check_and_update(S, step_norm));
+  qn_trace(S, step_norm);
+  if (S->force_stop || klement) return NK_OK;
+  return nk_qn_update(W, S->fu);
 }
 
 // ---- DFSane (lib/NonlinearSolveSpectralMethods/src/solve.jl:127-259; the line search as SimpleNonlinearSolve/src/dfsane.jl:114-144)
@@ -837,7 +957,7 @@ static int solver_start(nk_solver *S, bool first = true) {  // everything after 
     if (first) S->pt_applied = 0.0;  // (the Jacobian values were just refilled; after reinit! the first step's refill resets it)
     if (S->G) NK_TRY(nk_gmres_set_shift(S->G, 0.0));
   }
-  if (is_lb(S)) NK_TRY(lb_start(S));
+  if (is_lb(S) || is_qn(S)) NK_TRY(lb_start(S));
   if (is_sane(S)) NK_TRY(sane_start(S));
   if (is_lm(S)) {  // init / reinit! of the damping cache, the LM trust region and the geodesic cache
     S->lm_lam = S->o.lm_damping_initial;                    // levenberg_marquardt.jl:72-89,119-131
@@ -860,7 +980,20 @@ extern "C" int nk_solver_init(nk_problem *P, const double *u0, int memspace, con
   NK_REQUIRE(opts->algorithm == NK_ALG_NEWTON_RAPHSON || opts->algorithm == NK_ALG_TRUST_REGION ||
                  opts->algorithm == NK_ALG_GAUSS_NEWTON || opts->algorithm == NK_ALG_LEVENBERG_MARQUARDT ||
                  opts->algorithm == NK_ALG_PSEUDO_TRANSIENT || opts->algorithm == NK_ALG_LIMITED_MEMORY_BROYDEN ||
-                 opts->algorithm == NK_ALG_DFSANE, "bad algorithm");
+                 opts->algorithm == NK_ALG_DFSANE || opts->algorithm == NK_ALG_BROYDEN || opts->algorithm == NK_ALG_KLEMENT,
+             "bad algorithm");
+  if (opts->algorithm == NK_ALG_BROYDEN || opts->algorithm == NK_ALG_KLEMENT) {
+    const char *nm = opts->algorithm == NK_ALG_KLEMENT ? "Klement" : "Broyden";
+    NK_REQUIRE(opts->linesearch == 0, "%s: the line-search form is not built (linesearch must be 0)", nm);
+    NK_REQUIRE(ctx->nranks == 1, "%s runs on one rank", nm);
+    if (opts->broyden_update_rule >= NK_BROYDEN_TRUE_JACOBIAN)
+      NK_FAIL(NK_E_UNSUPPORTED, "%s: init_jacobian = true_jacobian is not built (identity only)", nm);
+    NK_REQUIRE(opts->broyden_update_rule >= 0 && opts->broyden_update_rule <= NK_BROYDEN_DIAGONAL, "Broyden: unknown update rule %d",
+               opts->broyden_update_rule);
+    if (opts->algorithm == NK_ALG_BROYDEN && opts->broyden_update_rule != NK_BROYDEN_DIAGONAL && P->n_local > NK_BROYDEN_MAX_N)
+      NK_FAIL(NK_E_UNSUPPORTED, "Broyden: n = %lld is above NK_BROYDEN_MAX_N = %d (the dense inverse Jacobian would exceed 8 GiB)",
+              (long long)P->n_local, NK_BROYDEN_MAX_N);
+  }
   if (opts->algorithm == NK_ALG_DFSANE) {
     NK_REQUIRE(opts->linesearch == 0, "DFSane: the RobustNonMonotone line search is part of the method (linesearch must be 0)");
     NK_REQUIRE(opts->forcing == NK_FORCING_NONE, "DFSane takes no forcing term: it solves no linear system");
@@ -890,7 +1023,8 @@ extern "C" int nk_solver_init(nk_problem *P, const double *u0, int memspace, con
                  opts->linsolve == NK_LINSOLVE_BANDED_LU,
              "unknown linsolve %d", opts->linsolve);
   NK_REQUIRE(!(opts->linsolve == NK_LINSOLVE_BANDED_LU && opts->forcing != NK_FORCING_NONE) ||
-                 opts->algorithm == NK_ALG_LIMITED_MEMORY_BROYDEN || opts->algorithm == NK_ALG_DFSANE,
+                 opts->algorithm == NK_ALG_LIMITED_MEMORY_BROYDEN || opts->algorithm == NK_ALG_DFSANE ||
+                 opts->algorithm == NK_ALG_BROYDEN || opts->algorithm == NK_ALG_KLEMENT,
              "a forcing term needs an iterative linear solver");
   NK_REQUIRE(opts->termination_mode >= 0 && opts->termination_mode <= 8, "bad termination_mode %d", opts->termination_mode);
   NK_REQUIRE(opts->termination_norm == 0 || opts->termination_norm == 1, "bad termination_norm %d", opts->termination_norm);
@@ -907,6 +1041,7 @@ extern "C" int nk_solver_init(nk_problem *P, const double *u0, int memspace, con
   // LimitedMemoryBroyden reads no Jacobian: whatever `linsolve` says, nothing below builds one, or a Krylov workspace
   if (is_lb(S)) { S->o.linsolve = NK_LINSOLVE_GMRES_MATFREE; S->o.forcing = NK_FORCING_NONE; }
   if (is_sane(S)) S->o.linsolve = NK_LINSOLVE_GMRES_MATFREE;   // DFSane likewise
+  if (is_qn(S)) { S->o.linsolve = NK_LINSOLVE_GMRES_MATFREE; S->o.forcing = NK_FORCING_NONE; }   // Broyden and Klement likewise
   if (S->o.maxiters <= 0) S->o.maxiters = 1000;
   if (S->o.gmres_restart <= 0) S->o.gmres_restart = 30;
   if (S->o.gmres_maxiters <= 0) S->o.gmres_maxiters = 300;
@@ -952,6 +1087,13 @@ extern "C" int nk_solver_init(nk_problem *P, const double *u0, int memspace, con
     S->lb_fupool[0] = S->fu;
     NK_TRY(nk_dev_alloc(&S->lb_fupool[1], na));
     NK_TRY(nk_dev_alloc(&S->lb_fupool[2], na));
+  } else if (is_qn(S)) {
+    S->lb_max_resets = S->o.qn_max_resets > 0 ? S->o.qn_max_resets : 100;
+    S->lb_tol = S->o.qn_reset_tolerance > 0.0 ? S->o.qn_reset_tolerance : pow(2.220446049250313e-16, 0.75);
+    NK_TRY(nk_qn_create(ctx, n, is_klement(S) ? NK_QN_KLEMENT : S->o.broyden_update_rule, &S->qn));
+    S->lb_fupool[0] = S->fu;
+    NK_TRY(nk_dev_alloc(&S->lb_fupool[1], na));
+    NK_TRY(nk_dev_alloc(&S->lb_fupool[2], na));
   } else if (is_sane(S)) {
     const nk_options &o = S->o;
     S->sane_smin = o.sane_sigma_min > 0.0 ? o.sane_sigma_min : 1.0e-10;
@@ -993,6 +1135,7 @@ extern "C" int nk_solver_destroy(nk_solver *S) {
   hipFree(S->lb_fupool[1]);
   hipFree(S->lb_fupool[2]);
   nk_lb_destroy(S->lb);
+  nk_qn_destroy(S->qn);
   nk_sane_destroy(S->sane);
   double *bufs[] = {S->ubuf[0], S->ubuf[1], S->ubuf[2], S->fu, S->du, S->fu_trial, S->du_newton, S->du_cauchy,
                     S->Jdu, S->JTfu, S->c1, S->c2, S->tr_du, S->stage, S->stage2, S->lm_dtd, S->lm_diag, S->lm_v,
@@ -2029,6 +2172,7 @@ static int internal_step(nk_solver *S, int recompute /*-1 nothing, 0 false, 1 tr
   // the descent is taken from the residual at the iterate it starts from: settle an outstanding deferral first
   NK_TRY(refresh_residual(S));  // (as in the reference, the step goes on even if this check terminated the solve)
   if (is_lb(S)) return lb_step(S, recompute);
+  if (is_qn(S)) return qn_step(S, recompute);
   if (is_sane(S)) return sane_step(S);   // recompute_jacobian is ignored (the reference warns, solve.jl:205-208)
   const bool defer_residual = !evaluate_residual && supports_deferred_residual(S);
   bool new_jacobian;
@@ -2307,6 +2451,23 @@ extern "C" int nk_solver_get_lbroyden_state(nk_solver *S, int *nresets, int *idx
   if (since_du) *since_du = S->lb_since_du;
   if (since_dfu) *since_dfu = S->lb_since_dfu;
   return NK_OK;
+}
+extern "C" int nk_solver_get_qn_state(nk_solver *S, int *nresets, double *a, int *since_du, int *since_dfu, int *steps_since_reset) {
+  NK_REQUIRE(S, "NULL solver");
+  NK_REQUIRE(is_qn(S), "neither a Broyden nor a Klement cache");
+  if (nresets) *nresets = S->lb_nresets;
+  if (a) *a = S->lb_a;
+  if (since_du) *since_du = S->lb_since_du;
+  if (since_dfu) *since_dfu = S->lb_since_dfu;
+  if (steps_since_reset) *steps_since_reset = S->qn_since_reset;
+  return NK_OK;
+}
+extern "C" int nk_solver_get_broyden_inverse(nk_solver *S, double *out, int64_t ldo, int memspace) {
+  NK_REQUIRE(S && out, "NULL argument");
+  NK_REQUIRE(is_qn(S), "neither a Broyden nor a Klement cache");
+  NK_REQUIRE(S->nsteps > 0, "the matrix exists from the first step on");
+  NK_HIP(hipSetDevice(S->ctx->device));
+  return nk_qn_copy_matrix(S->qn, out, ldo, memspace);
 }
 extern "C" int nk_solver_get_dfsane_state(nk_solver *S, double *sigma, double *alpha, int *trials, int *total_trials, int *M,
                                           double *history) {

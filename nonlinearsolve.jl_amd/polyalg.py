@@ -1,6 +1,6 @@
 """Polyalgorithms over the device caches: NonlinearSolvePolyAlgorithm (lib/NonlinearSolveBase/src/polyalg.jl:62-121,188-371,
 solve! in lib/NonlinearSolveBase/src/solve.jl:465-614, one-shot `__generated_polysolve` :657-790), RobustMultiNewton and
-FastShortcutNLLSPolyalg (lib/NonlinearSolveFirstOrder/src/poly_algs.jl:21-88). Host control logic only — every rung of the
+FastShortcutNLLSPolyalg (lib/NonlinearSolveFirstOrder/src/poly_algs.jl:21-88), FastShortcutNonlinearPolyalg (src/poly_algs.jl:26-92). Host control logic only — every rung of the
 ladder is an nk_solver on the device; no arithmetic on vectors happens here (residual norms come from the solver's own
 reduced scalars).  From Julia the reference's own NonlinearSolvePolyAlgorithm wraps the plugin algorithm unchanged (it only
 needs `__solve` / `__init` of the sub-algorithms), see INTEGRATION.md."""
@@ -42,6 +42,21 @@ def FastShortcutNLLSPolyalg(concrete_jac=None, linsolve=None):
         K.GaussNewton(linsolve=linsolve, linesearch=K.BackTracking(), concrete_jac=concrete_jac),
         K.TrustRegion(linsolve=linsolve, radius_update_scheme=RUS.Fan, concrete_jac=concrete_jac),
         K.LevenbergMarquardt(linsolve=linsolve)))
+
+
+def FastShortcutNonlinearPolyalg(concrete_jac=None, linsolve=None, must_use_jacobian=False, u0_len=None):
+    """The reference's default algorithm (src/poly_algs.jl:26-92, the real-valued branches): Broyden(), Klement(linsolve),
+    NewtonRaphson, TrustRegion, TrustRegion(Fan), LevenbergMarquardt — the two quasi-Newton rungs first, started at the third
+    rung when `u0_len` ≤ 25. `must_use_jacobian=True` keeps the four Jacobian-based rungs only. The Broyden rung holds a dense
+    n×n inverse Jacobian: above n = 32768 its `init` raises, and such problems take `must_use_jacobian=True`, the reference's
+    own switch. The Complex and prefer_simplenonlinearsolve branches are not offered."""
+    kw = dict(concrete_jac=concrete_jac, linsolve=linsolve)
+    jac = (K.NewtonRaphson(**kw), K.TrustRegion(**kw), K.TrustRegion(radius_update_scheme=K.RadiusUpdateSchemes.Fan, **kw),
+           K.LevenbergMarquardt(linsolve=linsolve))
+    if must_use_jacobian:
+        return NonlinearSolvePolyAlgorithm(jac)
+    start_index = 3 if (u0_len is not None and u0_len <= 25) else 1
+    return NonlinearSolvePolyAlgorithm((K.Broyden(), K.Klement(linsolve=linsolve)) + jac, start_index=start_index)
 
 
 def _sum_stats(parts):
