@@ -14,6 +14,8 @@
 #include <chrono>
 
 #include "nk_internal.h"
+#include "nk_linesearch.h"
+#include "nk_termination.h"
 
 struct nk_solver {
   nk_problem *P = nullptr;
@@ -42,11 +44,10 @@ struct nk_solver {
   nk_stats stats{};
   double total_time = 0.0;
   uint64_t u_version = 0;
-  // termination cache
-  double abstol = 0, reltol = 0, best_obj = 0, initial_obj = 0, fnorm_inf = 0;
-  double tc_u0_norm = 0;  // ‖u0‖₂ for the relative stall test
-  int tc_nsteps = 0, tc_retcode = NK_RET_DEFAULT;
-  std::vector<double> objectives_trace, step_norm_trace;
+  // termination cache (nk_termination.h)
+  tc_config tcc{};
+  tc_state tcs{};
+  double fnorm_inf = 0;
   // forcing
   double eta = 0, rnorm = 0, rnorm_prev = 0, lin_abstol = 0, lin_reltol = 0;
   // trust region
@@ -472,33 +473,18 @@ static int tr_radii(nk_solver *S) {
   return NK_OK;
 }
 
-// ---- termination cache: the nine SciMLBase termination modes (termination_conditions.jl:243-376)
-enum {
-  TM_ABSNORM_SAFEBEST = 0,  // default_termination_mode(::NonlinearProblem, Val(:regular))  (:385-389)
-  TM_NORM = 1, TM_REL = 2, TM_RELNORM = 3, TM_RELNORM_SAFE = 4, TM_RELNORM_SAFEBEST = 5,
-  TM_ABS = 6, TM_ABSNORM = 7, TM_ABSNORM_SAFE = 8
-};
-static bool tm_safe(int m) { return m == TM_ABSNORM_SAFEBEST || m == TM_ABSNORM_SAFE || m == TM_RELNORM_SAFE || m == TM_RELNORM_SAFEBEST; }
-static bool tm_best(int m) { return m == TM_ABSNORM_SAFEBEST || m == TM_RELNORM_SAFEBEST; }
-static bool tm_rel(int m) { return m == TM_RELNORM_SAFE || m == TM_RELNORM_SAFEBEST; }
-static bool tm_needs_pair(int m) { return m == TM_NORM || m == TM_REL || m == TM_RELNORM || tm_rel(m); }
-
-struct tc_quant {
-  double nf = 0;      // internalnorm(fu)
-  double nfu = 0;     // internalnorm(fu .+ u)
-  double relviol = 0; // max_i(|fu_i| − reltol |u_i + fu_i|)  (RelTerminationMode: converged iff ≤ 0)
-};
+// ---- termination cache: the modes and their arithmetic are nk_termination.h; here, what they read from the device
 // device reductions for the current (fu, u); ‖fu‖∞ is already in S->fnorm_inf
 static int tc_quantities(nk_solver *S, tc_quant *q) {
   nk_ctx *ctx = S->ctx;
-  const int mode = S->o.termination_mode;
+  const int mode = S->tcc.mode;
   const bool l2 = S->o.termination_norm == 1;
-  q->nf = S->fnorm_inf;
+  q->nf = q->nf_inf = S->fnorm_inf;
   int cnt = 0;
   if (l2) { NK_TRY(nk_blas_sumsq(ctx, S->n, S->fu, slot(S, 8))); cnt = 1; }
   if (tm_needs_pair(mode)) {
     const int grid = nk_grid_for(S->n, NK_BLOCK * 4, NK_MAX_RED_BLOCKS);
-    NK_LAUNCH(ctx, k_tc_pair, dim3(grid), dim3(NK_BLOCK), S->n, S->fu, S->u, S->reltol, ctx->d_partials);
+    NK_LAUNCH(ctx, k_tc_pair, dim3(grid), dim3(NK_BLOCK), S->n, S->fu, S->u, S->tcc.reltol, ctx->d_partials);
     NK_LAUNCH(ctx, k_tc_pair_reduce, dim3(1), dim3(NK_BLOCK), (const double *)ctx->d_partials, grid, slot(S, 9));
     NK_HIP(hipGetLastError());
     NK_TRY(nk_comm_allreduce(ctx, slot(S, 9), 1, 0));
@@ -513,80 +499,16 @@ static int tc_quantities(nk_solver *S, tc_quant *q) {
   }
   return NK_OK;
 }
-static double tc_objective(const nk_solver *S, const tc_quant &q) {
-  if (tm_rel(S->o.termination_mode)) return q.nf / (q.nfu + 2.220446049250313e-16 * S->reltol);  // eps(reltol)
-  return q.nf;
-}
 
 static int tc_reinit(nk_solver *S) {
-  S->tc_retcode = NK_RET_DEFAULT;
-  S->tc_nsteps = 0;
   tc_quant q;
   NK_TRY(tc_quantities(S, &q));
-  S->initial_obj = tm_safe(S->o.termination_mode) ? tc_objective(S, q) : INFINITY;
-  S->best_obj = S->initial_obj;
-  S->objectives_trace.assign(S->o.patience_steps > 0 ? S->o.patience_steps : 1, 0.0);
-  if (S->o.max_stalled_steps >= 0) S->step_norm_trace.assign(S->o.max_stalled_steps > 0 ? S->o.max_stalled_steps : 1, 0.0);
-  else S->step_norm_trace.clear();
-  if (tm_rel(S->o.termination_mode) && !S->step_norm_trace.empty()) {
+  double u0_ss = 0.0;
+  if (tm_rel(S->tcc.mode) && S->tcc.max_stalled_steps >= 0) {
     NK_TRY(nk_blas_sumsq(S->ctx, S->n, S->u, slot(S, 0)));
-    double v;
-    NK_TRY(fetch(S, 1, &v));
-    S->tc_u0_norm = sqrt(v);
+    NK_TRY(fetch(S, 1, &u0_ss));
   }
-  return NK_OK;
-}
-// sets *stop when the solve must end; step_norm = ‖u − uprev‖₂
-static int tc_check(nk_solver *S, double step_norm, bool *stop) {
-  *stop = false;
-  const int mode = S->o.termination_mode;
-  tc_quant q;
-  NK_TRY(tc_quantities(S, &q));
-  if (!tm_safe(mode)) {  // plain modes: check_convergence only (termination_conditions.jl:232-241)
-    bool conv = false;
-    switch (mode) {
-      case TM_NORM: conv = (q.nf <= S->abstol) || (q.nf <= S->reltol * q.nfu); break;
-      case TM_REL: conv = (q.relviol <= 0.0); break;
-      case TM_RELNORM: conv = (q.nf <= S->reltol * q.nfu); break;
-      case TM_ABS: conv = (S->fnorm_inf <= S->abstol); break;
-      case TM_ABSNORM: conv = (q.nf <= S->abstol); break;
-      default: break;
-    }
-    if (conv) { S->tc_retcode = NK_RET_SUCCESS; *stop = true; }
-    return NK_OK;
-  }
-  const double objective = tc_objective(S, q);
-  const double criteria = tm_rel(mode) ? S->reltol : S->abstol;
-  if (!isfinite(objective)) { S->tc_retcode = NK_RET_UNSTABLE; *stop = true; return NK_OK; }
-  if (S->o.protective_threshold > 0.0 &&
-      objective > S->initial_obj * S->o.protective_threshold * (double)S->P->n_global) {
-    S->tc_retcode = NK_RET_UNSTABLE; *stop = true; return NK_OK;
-  }
-  if (tm_best(mode) && objective < S->best_obj) {
-    S->best_obj = objective;
-    S->best_u = S->u;  // the buffer stays untouched until a better iterate replaces it (spare_u never hands it out)
-  }
-  if (objective <= criteria) { S->tc_retcode = NK_RET_SUCCESS; *stop = true; return NK_OK; }
-  S->tc_nsteps += 1;
-  const int L = (int)S->objectives_trace.size();
-  S->objectives_trace[(S->tc_nsteps - 1) % L] = objective;
-  if (objective <= S->o.patience_objective_multiplier * criteria && S->tc_nsteps > S->o.patience_steps) {
-    const int cnt = S->tc_nsteps < L ? S->tc_nsteps : L;
-    double mn = INFINITY, mx = -INFINITY;
-    for (int i = 0; i < cnt; ++i) { mn = fmin(mn, S->objectives_trace[i]); mx = fmax(mx, S->objectives_trace[i]); }
-    if (mn < S->o.min_max_factor * mx) { S->tc_retcode = NK_RET_STALLED; *stop = true; return NK_OK; }
-  }
-  if (!S->step_norm_trace.empty()) {
-    const int L2 = (int)S->step_norm_trace.size();
-    S->step_norm_trace[(S->tc_nsteps - 1) % L2] = step_norm;
-    if (S->tc_nsteps > S->o.max_stalled_steps) {
-      double mx = -INFINITY;
-      for (double v : S->step_norm_trace) mx = fmax(mx, v);
-      const bool stalled = tm_rel(mode) ? (mx <= S->reltol * (mx + S->tc_u0_norm)) : (mx <= S->abstol);
-      if (stalled) { S->tc_retcode = NK_RET_STALLED; *stop = true; return NK_OK; }
-    }
-  }
-  S->tc_retcode = NK_RET_FAILURE;
+  tc_reset(S->tcc, S->tcs, q, sqrt(u0_ss));
   return NK_OK;
 }
 // update_from_termination_cache! (termination_conditions.jl:440-453)
@@ -941,8 +863,8 @@ static int solver_start(nk_solver *S, bool first = true) {  // everything after 
   NK_TRY(nk_blas_fill(ctx, S->n, 0.0, S->du));  // descent/newton.jl:34-36
   S->eta = S->o.ew_eta0;
   S->rnorm = S->rnorm_prev = S->fnorm2;
-  S->lin_abstol = S->o.lin_abstol >= 0.0 ? S->o.lin_abstol : S->abstol;  // FirstOrder/src/solve.jl:203
-  S->lin_reltol = S->o.lin_reltol >= 0.0 ? S->o.lin_reltol : S->reltol;
+  S->lin_abstol = S->o.lin_abstol >= 0.0 ? S->o.lin_abstol : S->tcc.abstol;  // FirstOrder/src/solve.jl:203
+  S->lin_reltol = S->o.lin_reltol >= 0.0 ? S->o.lin_reltol : S->tcc.reltol;
   if (is_tr(S)) {
     tr_defaults(S);
     NK_TRY(tr_radii(S));
@@ -1047,8 +969,9 @@ extern "C" int nk_solver_init(nk_problem *P, const double *u0, int memspace, con
   if (S->o.gmres_maxiters <= 0) S->o.gmres_maxiters = 300;
   if (S->o.patience_steps <= 0) S->o.patience_steps = 100;
   if (S->o.max_shrink_times <= 0) S->o.max_shrink_times = 32;
-  S->abstol = opts->abstol > 0.0 ? opts->abstol : DEFAULT_TOL;
-  S->reltol = opts->reltol > 0.0 ? opts->reltol : DEFAULT_TOL;
+  S->tcc = tc_config{S->o.termination_mode, opts->abstol > 0.0 ? opts->abstol : DEFAULT_TOL, opts->reltol > 0.0 ? opts->reltol : DEFAULT_TOL,
+                     S->o.patience_steps, S->o.patience_objective_multiplier, S->o.min_max_factor, S->o.max_stalled_steps,
+                     S->o.protective_threshold, P->n_global};
   const int64_t n = S->n = P->n_local;
   const size_t na = (size_t)n + 2;
   for (int b = 0; b < 3; ++b) NK_TRY(nk_dev_alloc(&S->ubuf[b], na));
@@ -1492,75 +1415,9 @@ static int tr_solve(nk_solver *S, double duJJdu, bool have_JTfu, bool *accepted,
   return NK_OK;
 }
 
-// ---- BackTracking line search on ϕ(α) = ½‖f(u + α δu)‖² (LineSearches.jl BackTracking restated, [EXT]):
-// sufficient decrease ϕ(α) ≤ ϕ(0) + c₁ α ϕ'(0); quadratic, then cubic interpolation, safeguarded to
-// [ρ_lo α, ρ_hi α]. Every ϕ evaluation is one residual (stats.nf += 1, as the reference's line-search cache does).
-static int ls_phi(nk_solver *S, double alpha, double *phi) {
-  S->u_trial = spare_u(S);
-  nk_problem_invalidate(S->P);
-  NK_TRY(nk_blas_lincomb(S->ctx, S->n, 1.0, S->u, alpha, S->du, S->u_trial));
-  NK_TRY(nk_problem_residual_dev(S->P, S->u_trial, S->fu_trial));
-  S->stats.nf++;
-  NK_TRY(nk_blas_sumsq(S->ctx, S->n, S->fu_trial, slot(S, 0)));
-  double v;
-  NK_TRY(fetch(S, 1, &v));
-  *phi = 0.5 * v;
-  return NK_OK;
-}
-static int backtracking(nk_solver *S, double *alpha_out, bool *failed) {
-  const nk_options &o = S->o;
-  *failed = false;
-  // ϕ(0) and ϕ'(0) = fuᵀ (J δu)   (PseudoTransient: the stored J carries the damping α⁻¹ I — take the true product)
-  if (is_pt(S)) NK_TRY(nk_problem_jvp_dev(S->P, S->u, S->du, S->Jdu, nullptr));
-  else NK_TRY(apply_J(S, S->du, S->Jdu));
-  NK_TRY(nk_blas_sumsq(S->ctx, S->n, S->fu, slot(S, 0)));
-  NK_TRY(nk_blas_dot(S->ctx, S->n, S->fu, S->Jdu, slot(S, 1)));
-  double v[2];
-  NK_TRY(fetch(S, 2, v));
-  const double phi0 = 0.5 * v[0], dphi0 = v[1];
-  double a1 = 1.0, a2 = 1.0, phx0 = phi0, phx1 = phi0;
-  NK_TRY(ls_phi(S, a1, &phx1));
-  int iterfinite = 0;
-  const int iterfinitemax = 1074;  // -log2(eps(Float64)) style bound used by LineSearches.jl
-  while (!isfinite(phx1) && iterfinite < iterfinitemax) {
-    ++iterfinite;
-    a1 = a2;
-    a2 = a1 / 2.0;
-    NK_TRY(ls_phi(S, a2, &phx1));
-  }
-  int iteration = 0;
-  while (phx1 > phi0 + o.ls_c1 * a2 * dphi0) {
-    ++iteration;
-    if (iteration > o.ls_maxiters) { *failed = true; break; }
-    double atmp;
-    if (o.ls_order == 2 || iteration == 1) {
-      atmp = -(dphi0 * a2 * a2) / (2.0 * (phx1 - phi0 - dphi0 * a2));
-    } else {
-      const double div = 1.0 / (a1 * a1 * a2 * a2 * (a2 - a1));
-      const double ca = (a1 * a1 * (phx1 - phi0 - dphi0 * a2) - a2 * a2 * (phx0 - phi0 - dphi0 * a1)) * div;
-      const double cb = (-a1 * a1 * a1 * (phx1 - phi0 - dphi0 * a2) + a2 * a2 * a2 * (phx0 - phi0 - dphi0 * a1)) * div;
-      if (fabs(ca) <= 2.220446049250313e-16) atmp = dphi0 / (2.0 * cb);  // isapprox(a, 0; atol = eps)
-      else {
-        const double disc = fmax(cb * cb - 3.0 * ca * dphi0, 0.0);
-        atmp = (-cb + sqrt(disc)) / (3.0 * ca);
-      }
-    }
-    a1 = a2;
-    atmp = (atmp == atmp) ? fmin(atmp, a2 * o.ls_rho_hi) : a2 * o.ls_rho_hi;  // NaNMath.min
-    a2 = (atmp == atmp) ? fmax(atmp, a2 * o.ls_rho_lo) : a2 * o.ls_rho_lo;    // NaNMath.max
-    phx0 = phx1;
-    NK_TRY(ls_phi(S, a2, &phx1));
-  }
-  *alpha_out = a2;
-  return NK_OK;
-}
-
-// ---- LineSearchesJL(; method = Static | StrongWolfe | MoreThuente | HagerZhang) [EXT: LineSearch.jl's wrapper around LineSearches.jl,
-// the methods of lib/NonlinearSolveFirstOrder/test/rootfind_tests__item2.jl:40-46] on ϕ(α) = ½‖f(u + α δu)‖²,
-// ϕ'(α) = f(u + α δu)ᵀ J(u + α δu) δu. Restated from the published algorithms with LineSearches.jl's default parameters
-// (oracle/reference_restatement.py::_lsjl is the same code in Python; its Moré–Thuente step function is pinned against SciPy's
-// MINPACK-2 dcstep). Every ϕ / ϕ' / (ϕ, ϕ') evaluation is one residual at the trial point (nf += 1) — plus, for ϕ', one
-// Jacobian-vector product there — one fused two-scalar reduction, one fetch.
+// ---- line searches (nk_linesearch.h) on ϕ(α) = ½‖f(u + α δu)‖², ϕ'(α) = f(u + α δu)ᵀ J(u + α δu) δu. This is their one
+// evaluator: every ϕ / (ϕ, ϕ') evaluation is one residual at the trial point (nf += 1, as the reference's line-search cache
+// does) — plus, for ϕ', one Jacobian-vector product there — one fused two-scalar reduction, one fetch.
 static int ls_phidphi(nk_solver *S, double alpha, double *phi, double *dphi) {
   S->u_trial = spare_u(S);
   nk_problem_invalidate(S->P);
@@ -1581,360 +1438,22 @@ static int ls_phidphi(nk_solver *S, double alpha, double *phi, double *dphi) {
   *phi = 0.5 * v[0];
   return NK_OK;
 }
-// LineSearches.Static: the proposed step, halved while ϕ is not finite
-static int ls_static(nk_solver *S, double *alpha) {
-  double a = 1.0, pa;
-  NK_TRY(ls_phidphi(S, a, &pa, nullptr));
-  for (int it = 0; !isfinite(pa) && it < 52; ++it) {
-    a /= 2.0;
-    NK_TRY(ls_phidphi(S, a, &pa, nullptr));
+static int linesearch(nk_solver *S, double *alpha, bool *failed) {
+  const nk_options &o = S->o;
+  const auto eval = [S](double a, double *phi, double *dphi) { return ls_phidphi(S, a, phi, dphi); };
+  if (o.linesearch != 1) {
+    const int rc = ls_lsjl(eval, o.linesearch, alpha, failed);
+    if (rc == LS_BAD_METHOD) NK_FAIL(NK_E_INVALID, "bad linesearch %d", o.linesearch);
+    return rc;
   }
-  *alpha = a;
-  return NK_OK;
-}
-// LineSearches.StrongWolfe (Nocedal & Wright alg. 3.5 / 3.6, cubic interpolation, c₁ = 1e-4, c₂ = 0.9, ρ = 2)
-static double ls_sw_interp(double a1, double a2, double p1, double p2, double d1, double d2) {
-  const double q1 = d1 + d2 - 3.0 * (p1 - p2) / (a1 - a2);
-  const double rad = q1 * q1 - d1 * d2;
-  const double q2 = rad >= 0.0 ? sqrt(rad) : NAN;
-  return a2 - (a2 - a1) * ((d2 + q2 - q1) / (d2 - d1 + 2.0 * q2));
-}
-static int ls_sw_zoom(nk_solver *S, double alo, double ahi, double phi0, double dphi0, double *out) {
-  const double c1 = 1e-4, c2 = 0.9;
-  double aj = NAN;
-  for (int it = 0; it < 10; ++it) {
-    double plo, dlo, phi_, dhi, pj, dj;
-    NK_TRY(ls_phidphi(S, alo, &plo, &dlo));
-    NK_TRY(ls_phidphi(S, ahi, &phi_, &dhi));
-    aj = (alo < ahi) ? ls_sw_interp(alo, ahi, plo, phi_, dlo, dhi) : ls_sw_interp(ahi, alo, phi_, plo, dhi, dlo);
-    NK_TRY(ls_phidphi(S, aj, &pj, nullptr));
-    if (pj > phi0 + c1 * aj * dphi0 || pj > plo) {
-      ahi = aj;
-    } else {
-      NK_TRY(ls_phidphi(S, aj, &pj, &dj));
-      if (fabs(dj) <= -c2 * dphi0) break;
-      if (dj * (ahi - alo) >= 0.0) ahi = alo;
-      alo = aj;
-    }
-  }
-  *out = aj;
-  return NK_OK;
-}
-static int ls_strongwolfe(nk_solver *S, double phi0, double dphi0, double *alpha) {
-  const double c1 = 1e-4, c2 = 0.9, rho = 2.0, a_max = 65536.0;
-  double a_prev = 0.0, a_i = 1.0, p_prev = phi0, p_i, d_i, tmp;
-  for (int i = 1; a_i < a_max; ++i) {
-    NK_TRY(ls_phidphi(S, a_i, &p_i, nullptr));
-    if (p_i > phi0 + c1 * a_i * dphi0 || (p_i >= p_prev && i > 1)) {
-      NK_TRY(ls_sw_zoom(S, a_prev, a_i, phi0, dphi0, alpha));
-      return ls_phidphi(S, *alpha, &tmp, nullptr);  // the method returns (α*, ϕ(α*)): one more evaluation
-    }
-    NK_TRY(ls_phidphi(S, a_i, &p_i, &d_i));
-    if (fabs(d_i) <= -c2 * dphi0) { *alpha = a_i; return NK_OK; }
-    if (d_i >= 0.0) {
-      NK_TRY(ls_sw_zoom(S, a_i, a_prev, phi0, dphi0, alpha));
-      return ls_phidphi(S, *alpha, &tmp, nullptr);
-    }
-    a_prev = a_i;
-    p_prev = p_i;
-    a_i *= rho;
-  }
-  *alpha = a_max;
-  return ls_phidphi(S, a_max, &tmp, nullptr);
-}
-// MINPACK cstep (Moré & Thuente 1994): safeguarded cubic / quadratic step + update of the interval of uncertainty
-struct mt_state { double stx, fx, dgx, sty, fy, dgy, alpha, f, dg; bool bracketed; int info; };
-static void ls_cstep(mt_state &m, double amin, double amax) {
-  double &stx = m.stx, &fx = m.fx, &dgx = m.dgx, &sty = m.sty, &fy = m.fy, &dgy = m.dgy, &alpha = m.alpha;
-  const double f = m.f, dg = m.dg;
-  m.info = 0;
-  if ((m.bracketed && (alpha <= fmin(stx, sty) || alpha >= fmax(stx, sty))) || dgx * (alpha - stx) >= 0.0 || amax < amin) return;
-  const double sgnd = dg * (dgx / fabs(dgx));
-  bool bound;
-  double af;
-  if (f > fx) {
-    m.info = 1; bound = true;
-    const double theta = 3.0 * (fx - f) / (alpha - stx) + dgx + dg;
-    const double sc = fmax(fabs(theta), fmax(fabs(dgx), fabs(dg)));
-    double gamma = sc * sqrt((theta / sc) * (theta / sc) - (dgx / sc) * (dg / sc));
-    if (alpha < stx) gamma = -gamma;
-    const double pp = gamma - dgx + theta, q = gamma - dgx + gamma + dg, r = pp / q;
-    const double ac = stx + r * (alpha - stx);
-    const double aq = stx + ((dgx / ((fx - f) / (alpha - stx) + dgx)) / 2.0) * (alpha - stx);
-    af = (fabs(ac - stx) < fabs(aq - stx)) ? ac : (ac + aq) / 2.0;
-    m.bracketed = true;
-  } else if (sgnd < 0.0) {
-    m.info = 2; bound = false;
-    const double theta = 3.0 * (fx - f) / (alpha - stx) + dgx + dg;
-    const double sc = fmax(fabs(theta), fmax(fabs(dgx), fabs(dg)));
-    double gamma = sc * sqrt((theta / sc) * (theta / sc) - (dgx / sc) * (dg / sc));
-    if (alpha > stx) gamma = -gamma;
-    const double pp = gamma - dg + theta, q = gamma - dg + gamma + dgx, r = pp / q;
-    const double ac = alpha + r * (stx - alpha);
-    const double aq = alpha + (dg / (dg - dgx)) * (stx - alpha);
-    af = (fabs(ac - alpha) > fabs(aq - alpha)) ? ac : aq;
-    m.bracketed = true;
-  } else if (fabs(dg) < fabs(dgx)) {
-    m.info = 3; bound = true;
-    const double theta = 3.0 * (fx - f) / (alpha - stx) + dgx + dg;
-    const double sc = fmax(fabs(theta), fmax(fabs(dgx), fabs(dg)));
-    double gamma = sc * sqrt(fmax(0.0, (theta / sc) * (theta / sc) - (dgx / sc) * (dg / sc)));
-    if (alpha > stx) gamma = -gamma;
-    const double pp = gamma - dg + theta, q = gamma + dgx - dg + gamma, r = pp / q;
-    double ac;
-    if (r < 0.0 && gamma != 0.0) ac = alpha + r * (stx - alpha);
-    else if (alpha > stx) ac = amax;
-    else ac = amin;
-    const double aq = alpha + (dg / (dg - dgx)) * (stx - alpha);
-    if (m.bracketed) af = (fabs(alpha - ac) < fabs(alpha - aq)) ? ac : aq;
-    else af = (fabs(alpha - ac) > fabs(alpha - aq)) ? ac : aq;
-  } else {
-    m.info = 4; bound = false;
-    if (m.bracketed) {
-      const double theta = 3.0 * (f - fy) / (sty - alpha) + dgy + dg;
-      const double sc = fmax(fabs(theta), fmax(fabs(dgy), fabs(dg)));
-      double gamma = sc * sqrt((theta / sc) * (theta / sc) - (dgy / sc) * (dg / sc));
-      if (alpha > sty) gamma = -gamma;
-      const double pp = gamma - dg + theta, q = gamma - dg + gamma + dgy, r = pp / q;
-      af = alpha + r * (sty - alpha);
-    } else if (alpha > stx) af = amax;
-    else af = amin;
-  }
-  if (f > fx) { sty = alpha; fy = f; dgy = dg; }
-  else {
-    if (sgnd < 0.0) { sty = stx; fy = fx; dgy = dgx; }
-    stx = alpha; fx = f; dgx = dg;
-  }
-  af = fmax(amin, fmin(amax, af));
-  alpha = af;
-  if (m.bracketed && bound) {
-    if (sty > stx) alpha = fmin(stx + (2.0 / 3.0) * (sty - stx), alpha);
-    else alpha = fmax(stx + (2.0 / 3.0) * (sty - stx), alpha);
-  }
-}
-// LineSearches.MoreThuente (f_tol = 1e-4, gtol = 0.9, x_tol = 1e-8, alphamin = 1e-16, alphamax = 65536, maxfev = 100)
-static int ls_morethuente(nk_solver *S, double phi0, double dphi0, double *alpha_out) {
-  const double f_tol = 1e-4, gtol = 0.9, x_tol = 1e-8, amin = 1e-16, amax = 65536.0;
-  const int maxfev = 100;
-  int info = 0, info_cstep = 1, nfev = 0;
-  bool stage1 = true;
-  const double finit = phi0, dgtest = f_tol * dphi0;
-  double width = amax - amin, width1 = 2.0 * width;
-  mt_state m;
-  m.stx = 0.0; m.fx = finit; m.dgx = dphi0;
-  m.sty = 0.0; m.fy = finit; m.dgy = dphi0;
-  m.bracketed = false;
-  m.info = 1;
-  double alpha = fmin(fmax(1.0, amin), amax), f, dg, stmin, stmax;
-  NK_TRY(ls_phidphi(S, alpha, &f, &dg));
-  nfev++;
-  for (int itf = 0; (!isfinite(f) || !isfinite(dg)) && itf < 52; ++itf) {
-    alpha /= 2.0;
-    NK_TRY(ls_phidphi(S, alpha, &f, &dg));
-    nfev++;
-    m.stx = 0.875 * alpha;
-  }
-  for (;;) {
-    if (m.bracketed) { stmin = fmin(m.stx, m.sty); stmax = fmax(m.stx, m.sty); }
-    else { stmin = m.stx; stmax = alpha + 4.0 * (alpha - m.stx); }
-    stmin = fmax(amin, stmin);
-    stmax = fmin(amax, stmax);
-    alpha = fmin(fmax(alpha, amin), amax);
-    if ((m.bracketed && (alpha <= stmin || alpha >= stmax)) || nfev >= maxfev - 1 || info_cstep == 0 ||
-        (m.bracketed && stmax - stmin <= x_tol * stmax))
-      alpha = m.stx;
-    NK_TRY(ls_phidphi(S, alpha, &f, &dg));  // (the first pass evaluates the initial step a second time, as LineSearches.jl does)
-    nfev++;
-    const double ftest1 = finit + alpha * dgtest;
-    if ((m.bracketed && (alpha <= stmin || alpha >= stmax)) || info_cstep == 0) info = 6;
-    if (alpha == amax && f <= ftest1 && dg <= dgtest) info = 5;
-    if (alpha == amin && (f > ftest1 || dg >= dgtest)) info = 4;
-    if (nfev >= maxfev) info = 3;
-    if (m.bracketed && stmax - stmin <= x_tol * stmax) info = 2;
-    if (f <= ftest1 && fabs(dg) <= -gtol * dphi0) info = 1;
-    if (info != 0) break;
-    if (stage1 && f <= ftest1 && dg >= fmin(f_tol, gtol) * dphi0) stage1 = false;
-    m.alpha = alpha;
-    if (stage1 && f <= m.fx && f > ftest1) {  // the modified function ψ(α) = ϕ(α) − ϕ(0) − f_tol ϕ'(0) α
-      mt_state mm = m;
-      mm.fx = m.fx - m.stx * dgtest; mm.fy = m.fy - m.sty * dgtest; mm.f = f - alpha * dgtest;
-      mm.dgx = m.dgx - dgtest; mm.dgy = m.dgy - dgtest; mm.dg = dg - dgtest;
-      ls_cstep(mm, stmin, stmax);
-      m.stx = mm.stx; m.sty = mm.sty; m.alpha = mm.alpha; m.bracketed = mm.bracketed; m.info = mm.info;
-      m.fx = mm.fx + mm.stx * dgtest; m.fy = mm.fy + mm.sty * dgtest;
-      m.dgx = mm.dgx + dgtest; m.dgy = mm.dgy + dgtest;
-    } else {
-      m.f = f; m.dg = dg;
-      ls_cstep(m, stmin, stmax);
-    }
-    alpha = m.alpha;
-    info_cstep = m.info;
-    if (m.bracketed) {
-      if (fabs(m.sty - m.stx) >= (2.0 / 3.0) * width1) alpha = m.stx + (m.sty - m.stx) / 2.0;
-      width1 = width;
-      width = fabs(m.sty - m.stx);
-    }
-  }
-  *alpha_out = alpha;
-  return NK_OK;
-}
-// LineSearches.HagerZhang (Hager & Zhang 2005: bracket B0–B3, secant² S1–S4, update U0–U3 with bisection θ = ½, Wolfe /
-// approximate Wolfe tests; δ = 0.1, σ = 0.9, ρ = 5, ε = 1e-6, γ = 0.66, ≤ 50 iterations, ψ₃ = 0.1). The method's exceptions
-// (non-descent direction, iteration limit, lost bracket) are reported as a failed line search at the best step so far.
-struct hz_state {
-  nk_solver *S;
-  std::vector<double> a, v, d;  // step lengths, ϕ, ϕ′ of every evaluation (index 0: α = 0)
-  double phi_0, dphi_0, phi_lim;
-  bool lost = false;
-};
-static int hz_eval(hz_state &h, double alpha, double *p, double *dp) {
-  NK_TRY(ls_phidphi(h.S, alpha, p, dp));
-  h.a.push_back(alpha); h.v.push_back(*p); h.d.push_back(*dp);
-  return NK_OK;
-}
-static bool hz_wolfe(const hz_state &h, double c, double pc, double dc) {
-  const double delta = 0.1, sigma = 0.9;
-  const bool w1 = delta * h.dphi_0 >= (pc - h.phi_0) / c && dc >= sigma * h.dphi_0;
-  const bool w2 = (2.0 * delta - 1.0) * h.dphi_0 >= dc && dc >= sigma * h.dphi_0 && pc <= h.phi_lim;
-  return w1 || w2;
-}
-static int hz_bisect(hz_state &h, int *ia, int *ib) {
-  double a = h.a[*ia], b = h.a[*ib];
-  while (b - a > nextafter(b, INFINITY) - b) {
-    const double dd = (a + b) / 2.0;
-    double pd, gd;
-    NK_TRY(hz_eval(h, dd, &pd, &gd));
-    const int id = (int)h.a.size() - 1;
-    if (gd >= 0.0) { *ib = id; return NK_OK; }
-    if (pd <= h.phi_lim) { a = dd; *ia = id; }
-    else { b = dd; *ib = id; }
-  }
-  return NK_OK;
-}
-static int hz_update(hz_state &h, int ia, int ib, int ic, int *oa, int *ob) {
-  const double a = h.a[ia], b = h.a[ib], c = h.a[ic];
-  *oa = ia; *ob = ib;
-  if (c < a || c > b) return NK_OK;
-  if (h.d[ic] >= 0.0) { *ob = ic; return NK_OK; }
-  if (h.v[ic] <= h.phi_lim) { *oa = ic; return NK_OK; }
-  *ob = ic;
-  return hz_bisect(h, oa, ob);
-}
-static double hz_secant(double a, double b, double da, double db) { return (a * db - b * da) / (db - da); }
-static int hz_secant2(hz_state &h, int ia, int ib, bool *iswolfe, int *oA, int *oB) {
-  const double a0 = h.a[ia], b0 = h.a[ib], da = h.d[ia], db = h.d[ib];
-  *iswolfe = false;
-  if (!(da < 0.0 && db >= 0.0)) { h.lost = true; *oA = ia; *oB = ib; return NK_OK; }
-  double c = hz_secant(a0, b0, da, db), pc, dc;
-  NK_TRY(hz_eval(h, c, &pc, &dc));
-  int ic = (int)h.a.size() - 1;
-  if (hz_wolfe(h, c, pc, dc)) { *iswolfe = true; *oA = *oB = ic; return NK_OK; }
-  int iA, iB;
-  NK_TRY(hz_update(h, ia, ib, ic, &iA, &iB));
-  const double a = h.a[iA], b = h.a[iB];
-  if (iB == ic) c = hz_secant(h.a[ib], h.a[iB], h.d[ib], h.d[iB]);
-  else if (iA == ic) c = hz_secant(h.a[ia], h.a[iA], h.d[ia], h.d[iA]);
-  if ((iA == ic || iB == ic) && a <= c && c <= b) {
-    NK_TRY(hz_eval(h, c, &pc, &dc));
-    ic = (int)h.a.size() - 1;
-    if (hz_wolfe(h, c, pc, dc)) { *iswolfe = true; *oA = *oB = ic; return NK_OK; }
-    int jA, jB;
-    NK_TRY(hz_update(h, iA, iB, ic, &jA, &jB));
-    iA = jA; iB = jB;
-  }
-  *oA = iA; *oB = iB;
-  return NK_OK;
-}
-static int ls_hagerzhang(nk_solver *S, double phi_0, double dphi_0, double *alpha_out, bool *failed) {
-  const double rho = 5.0, eps_hz = 1e-6, gamma = 0.66, psi3 = 0.1, feps = 2.220446049250313e-16;
-  const int lsmax = 50;
-  double alphamax = INFINITY;
-  *failed = false;
-  if (!(isfinite(phi_0) && isfinite(dphi_0)) || dphi_0 >= feps * fabs(phi_0)) { *alpha_out = 0.0; *failed = true; return NK_OK; }
-  hz_state h;
-  h.S = S;
-  h.a.push_back(0.0); h.v.push_back(phi_0); h.d.push_back(dphi_0);
-  h.phi_0 = phi_0; h.dphi_0 = dphi_0;
-  h.phi_lim = phi_0 + eps_hz * fabs(phi_0);
-  double c = 1.0, phi_c, dphi_c;
-  NK_TRY(ls_phidphi(S, c, &phi_c, &dphi_c));
-  for (int itf = 1; !(isfinite(phi_c) && isfinite(dphi_c)) && itf < 53; ++itf) {
-    c *= psi3;
-    NK_TRY(ls_phidphi(S, c, &phi_c, &dphi_c));
-  }
-  if (!(isfinite(phi_c) && isfinite(dphi_c))) { *alpha_out = 0.0; return NK_OK; }
-  h.a.push_back(c); h.v.push_back(phi_c); h.d.push_back(dphi_c);
-  bool bracketed = false;
-  int ia = 0, ib = 1, it = 1;
-  while (!bracketed && it < lsmax) {  // B0–B3
-    if (dphi_c >= 0.0) {
-      ib = (int)h.a.size() - 1;
-      for (int i = ib - 1; i >= 0; --i)
-        if (h.v[i] <= h.phi_lim) { ia = i; break; }
-      bracketed = true;
-    } else if (h.v.back() > h.phi_lim) {
-      ib = (int)h.a.size() - 1;
-      ia = 0;
-      NK_TRY(hz_bisect(h, &ia, &ib));
-      bracketed = true;
-    } else {
-      const double cold = c;
-      if (nextafter(cold, INFINITY) >= alphamax) { *alpha_out = cold; return NK_OK; }
-      c = fmin(c * rho, alphamax);
-      NK_TRY(ls_phidphi(S, c, &phi_c, &dphi_c));
-      for (int itf = 1; !(isfinite(phi_c) && isfinite(dphi_c)) && c > nextafter(cold, INFINITY) && itf < 53; ++itf) {
-        alphamax = c;
-        c = (cold + c) / 2.0;
-        NK_TRY(ls_phidphi(S, c, &phi_c, &dphi_c));
-      }
-      if (!(isfinite(phi_c) && isfinite(dphi_c))) { *alpha_out = cold; return NK_OK; }
-      if (dphi_c < 0.0 && c == alphamax) { *alpha_out = c; return NK_OK; }
-      h.a.push_back(c); h.v.push_back(phi_c); h.d.push_back(dphi_c);
-    }
-    ++it;
-  }
-  while (it < lsmax) {  // L1–L3
-    const double a = h.a[ia], b = h.a[ib];
-    if (b - a <= nextafter(b, INFINITY) - b) { *alpha_out = a; return NK_OK; }
-    bool isw;
-    int iA, iB;
-    NK_TRY(hz_secant2(h, ia, ib, &isw, &iA, &iB));
-    if (h.lost) { *alpha_out = h.a[ia]; *failed = true; return NK_OK; }
-    if (isw) { *alpha_out = h.a[iA]; return NK_OK; }
-    const double A = h.a[iA], B = h.a[iB];
-    if (B - A < gamma * (b - a)) {
-      if (nextafter(h.v[ia], INFINITY) >= h.v[ib] && nextafter(h.v[iA], INFINITY) >= h.v[iB]) { *alpha_out = A; return NK_OK; }
-      ia = iA; ib = iB;
-    } else {
-      double pc, dc;
-      NK_TRY(hz_eval(h, (A + B) / 2.0, &pc, &dc));
-      int ja, jb;
-      NK_TRY(hz_update(h, iA, iB, (int)h.a.size() - 1, &ja, &jb));
-      ia = ja; ib = jb;
-    }
-    ++it;
-  }
-  *alpha_out = h.a[ia];  // iteration limit: LineSearchException in LineSearches.jl
-  *failed = true;
-  return NK_OK;
-}
-
-static int linesearch_lsjl(nk_solver *S, double *alpha_out, bool *failed) {
-  *failed = false;
-  double phi0, dphi0;
-  NK_TRY(ls_phidphi(S, 0.0, &phi0, &dphi0));
-  if (dphi0 >= 0.0) {  // not a descent direction: the full step, reported as a failed line search
-    *alpha_out = 1.0;
-    *failed = true;
-    return NK_OK;
-  }
-  switch (S->o.linesearch) {
-    case 2: return ls_static(S, alpha_out);
-    case 3: return ls_strongwolfe(S, phi0, dphi0, alpha_out);
-    case 4: return ls_morethuente(S, phi0, dphi0, alpha_out);
-    case 5: return ls_hagerzhang(S, phi0, dphi0, alpha_out, failed);
-    default: NK_FAIL(NK_E_INVALID, "bad linesearch %d", S->o.linesearch);
-  }
+  // BackTracking: ϕ(0) and ϕ'(0) = fuᵀ (J δu)   (PseudoTransient: the stored J carries the damping α⁻¹ I — take the true product)
+  if (is_pt(S)) NK_TRY(nk_problem_jvp_dev(S->P, S->u, S->du, S->Jdu, nullptr));
+  else NK_TRY(apply_J(S, S->du, S->Jdu));
+  NK_TRY(nk_blas_sumsq(S->ctx, S->n, S->fu, slot(S, 0)));
+  NK_TRY(nk_blas_dot(S->ctx, S->n, S->fu, S->Jdu, slot(S, 1)));
+  double v[2];
+  NK_TRY(fetch(S, 2, v));
+  return ls_backtracking(eval, 0.5 * v[0], v[1], o.ls_c1, o.ls_rho_hi, o.ls_rho_lo, o.ls_maxiters, o.ls_order, alpha, failed);
 }
 
 // ---- LevenbergMarquardt
@@ -2107,10 +1626,12 @@ static int lm_step(nk_solver *S, bool new_jacobian, bool evaluate_residual) {
 
 // check_and_update! (termination_conditions.jl:414-426)
 static int check_and_update(nk_solver *S, double step_norm) {
-  bool stop = false;
-  NK_TRY(tc_check(S, step_norm, &stop));
-  if (stop) {
-    S->retcode = S->tc_retcode;
+  tc_quant q;
+  NK_TRY(tc_quantities(S, &q));
+  const tc_verdict v = tc_check(S->tcc, S->tcs, q, step_norm);
+  if (v.new_best) S->best_u = S->u;  // the buffer stays untouched until a better iterate replaces it (spare_u never hands it out)
+  if (v.stop) {
+    S->retcode = S->tcs.retcode;
     NK_TRY(rollback_to_best(S));
     S->force_stop = true;
   }
@@ -2247,8 +1768,7 @@ static int internal_step(nk_solver *S, int recompute /*-1 nothing, 0 false, 1 tr
     if (S->o.linesearch) {  // Val(:LineSearch): α from the line search, then axpy!(α, δu, u)  (solve.jl:392-408)
       double alpha = 1.0;
       bool lsfail = false;
-      if (S->o.linesearch == 1) NK_TRY(backtracking(S, &alpha, &lsfail));
-      else NK_TRY(linesearch_lsjl(S, &alpha, &lsfail));
+      NK_TRY(linesearch(S, &alpha, &lsfail));
       if (lsfail) {
         S->retcode = NK_RET_INTERNAL_LINESEARCH_FAILED;
         S->force_stop = true;

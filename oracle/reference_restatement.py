@@ -2011,6 +2011,10 @@ class FirstOrderCache:
             return 0.5 * float(np.dot(f, f))
         phi0 = 0.5 * float(np.dot(self.fu, self.fu))
         dphi0 = float(np.dot(self.fu, self._apply_J(du, self.u)))
+        return self._ls_backtracking(phi, phi0, dphi0, ls)
+
+    @staticmethod
+    def _ls_backtracking(phi, phi0, dphi0, ls):
         a1 = a2 = 1.0
         phx0 = phi0
         phx1 = phi(a1)
@@ -2030,7 +2034,7 @@ class FirstOrderCache:
             else:
                 div = 1.0 / (a1 * a1 * a2 * a2 * (a2 - a1))
                 ca = (a1 * a1 * (phx1 - phi0 - dphi0 * a2) - a2 * a2 * (phx0 - phi0 - dphi0 * a1)) * div
-                cb = (-a1 ** 3 * (phx1 - phi0 - dphi0 * a2) + a2 ** 3 * (phx0 - phi0 - dphi0 * a1)) * div
+                cb = (-a1 * a1 * a1 * (phx1 - phi0 - dphi0 * a2) + a2 * a2 * a2 * (phx0 - phi0 - dphi0 * a1)) * div
                 if abs(ca) <= np.finfo(float).eps:
                     atmp = dphi0 / (2.0 * cb)
                 else:
