@@ -406,6 +406,12 @@ static int ilut_update(nk_precond *P) {
     }
     diag[k] = piv;
     std::sort(idx.begin(), idx.end());
+    // (a NaN fails `|z| ≥ τ`: without this test it would be dropped as if it were small)
+    for (int32_t j : idx)
+      if (!std::isfinite(wz[j])) {
+        P->factored = false;
+        NK_FAIL(NK_E_SINGULAR, "ILU(τ): non-finite entry (%lld, %lld)", (long long)k, (long long)j);
+      }
     for (int32_t j : idx) {
       mark[j] = 0;
       if (j > k && std::fabs(wz[j]) >= tau && wz[j] != 0.0) {
@@ -433,6 +439,11 @@ static int ilut_update(nk_precond *P) {
       }
     }
     std::sort(idx.begin(), idx.end());
+    for (int32_t r : idx)
+      if (!std::isfinite(wz[r])) {
+        P->factored = false;
+        NK_FAIL(NK_E_SINGULAR, "ILU(τ): non-finite entry (%lld, %lld)", (long long)r, (long long)k);
+      }
     for (int32_t r : idx) {
       mark[r] = 0;
       if (std::fabs(wz[r]) >= tau && wz[r] != 0.0) {

@@ -671,8 +671,7 @@ def ilut(A, tau):
         for j, v in zip(A.indices[A.indptr[k]:A.indptr[k + 1]], A.data[A.indptr[k]:A.indptr[k + 1]]):
             if j >= k:
                 z[j] = z.get(j, 0.0) + v
-        if k not in z:
-            raise ArithmeticError(f"ILU(τ): row {k} has no stored diagonal entry")
+        z.setdefault(k, 0.0)    # no stored diagonal entry: the pivot starts from 0 and fill may create it (ilut_update does the same)
         for i, lki in Lrow[k]:
             for j, uij in Urow[i].items():
                 if j >= k:
@@ -681,6 +680,8 @@ def ilut(A, tau):
         if piv == 0.0 or not math.isfinite(piv):
             raise ArithmeticError("ILU(τ): zero or non-finite pivot")
         diag[k] = piv
+        if not all(math.isfinite(v) for v in z.values()):       # (a NaN fails |z| ≥ τ: it must not pass as a small entry)
+            raise ArithmeticError("ILU(τ): non-finite entry")
         for j in sorted(z):
             if j > k and abs(z[j]) >= tau and z[j] != 0.0:
                 Urow[k][j] = z[j]
@@ -693,6 +694,8 @@ def ilut(A, tau):
             for r, lri in Lcol[i].items():
                 if r > k:
                     w[r] = w.get(r, 0.0) - uik * lri
+        if not all(math.isfinite(v) for v in w.values()):
+            raise ArithmeticError("ILU(τ): non-finite entry")
         for r in sorted(w):
             if abs(w[r]) >= tau and w[r] != 0.0:
                 l = w[r] / piv

@@ -306,12 +306,12 @@ def test_ilut_factors_and_apply_match_the_oracle(nls, dev, case):
     # new values, same object
     A2 = A.copy(); A2.data = A.data * (1.0 + 0.1 * rng.standard_normal(A.nnz)) ; A2 = (A2 + sp.diags(np.full(A.shape[0], 0.5 * abs(A).max()))).tocsr()
     A2.sort_indices()
-    if A2.nnz == A.nnz:
-        M.set_values(A2.data)
-        P.update()
-        want2 = R.ilut_preconditioner(A2, tau)(x)
-        got2 = P.apply(torch.tensor(x, device=dev)).cpu().numpy()
-        assert np.max(np.abs(got2 - want2)) <= 1e-11 * np.max(np.abs(want2))
+    assert A2.nnz == A.nnz
+    M.set_values(A2.data)
+    P.update()
+    want2 = R.ilut_preconditioner(A2, tau)(x)
+    got2 = P.apply(torch.tensor(x, device=dev)).cpu().numpy()
+    assert np.max(np.abs(got2 - want2)) <= 1e-11 * np.max(np.abs(want2))
 
 
 def test_newton_with_ilut_as_left_preconditioner_as_in_the_tutorial(nls, dev):
