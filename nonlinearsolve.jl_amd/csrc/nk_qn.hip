@@ -14,8 +14,11 @@
 //                 δu = −J⁻¹fu_prev under the same J⁻¹, w = J⁻¹(fu_new − fu_prev) = g + δu and δu − w = −g: the new column pair
 //                 is (−g, z) with denom = δu·w, and the next direction is −(d₀ + Ũ_new·(z·fu_new)/denom) with
 //                 d₀ = g minus the evicted column's term — written by this pass, finished by the next k_lb_update.
-// Reductions: per-workgroup partial sums in a fixed order, combined in a fixed order by the workgroup that draws the last
-// ticket (an integer counter; no floating-point atomics): two runs give the same bits.
+//
+// Reductions, for the three families of this file alike: qn_block_partials leaves a workgroup's partial of every
+// slot in part[slot][workgroup]; the workgroup that draws the last ticket (an integer counter; no floating-point atomics) folds
+// each slot with qn_fold_slot, one wavefront per slot, and lane 0 puts the scalar where the host reads it. Every order is fixed:
+// two runs give the same bits.
 #include "nk_internal.h"
 
 constexpr int LB_MAX_T = 32;        // supported threshold
@@ -24,14 +27,43 @@ constexpr int LB_MAX_GRID = 512;    // two workgroups per CU at most: the last w
 enum { LB_FNORM_INF = 0, LB_FNORM_SS = 1, LB_DU_SS = 2, LB_FLAG_DU = 3, LB_FLAG_DFU = 4, LB_U_SS = 5, LB_DENOM = 6, LB_ZETA = 7,
        LB_C1 = 8, LB_C2 = LB_C1 + LB_MAX_T, LB_NSCAL = LB_C2 + LB_MAX_T };
 
+// the reduction workspace of a family: the scalars the host reads, the partials of its reduce passes, the partials of its
+// vector (update) launch with the number of workgroups that wrote them and that nobody has folded yet (0: none), the tickets
+struct qn_red {
+  double *sc = nullptr, *part = nullptr, *part0 = nullptr;
+  unsigned int *ticket = nullptr;
+  int ntickets = 0, grid0 = 0;
+};
+// the tickets are zeroed in stream order (a new solve, or a reset)
+static int qn_red_restart(const nk_ctx *ctx, qn_red *r) {
+  r->grid0 = 0;
+  NK_HIP(nk_memset(ctx, r->ticket, 0, r->ntickets * sizeof(unsigned int)));
+  return NK_OK;
+}
+static int qn_red_alloc(const nk_ctx *ctx, qn_red *r, int nscal, int nslots, int nslots0, int ntickets) {
+  r->ntickets = ntickets;
+  NK_TRY(nk_dev_alloc(&r->sc, (size_t)nscal));
+  NK_TRY(nk_dev_alloc(&r->part, (size_t)nslots * LB_MAX_GRID));
+  NK_TRY(nk_dev_alloc(&r->part0, (size_t)nslots0 * NK_MAX_RED_BLOCKS));
+  NK_TRY(nk_dev_alloc(&r->ticket, (size_t)ntickets));
+  NK_HIP(nk_memset(ctx, r->sc, 0, nscal * sizeof(double)));
+  return qn_red_restart(ctx, r);
+}
+static void qn_red_free(qn_red *r) { hipFree(r->sc); hipFree(r->part); hipFree(r->part0); hipFree(r->ticket); }
+// workgroups of a reduce pass, each taking `per_wg` of `items`: sized to the CUs, at most two workgroups each
+static int qn_red_grid(const nk_ctx *ctx, int64_t items, int per_wg) {
+  int cap = 2 * ctx->num_cus;
+  if (cap > LB_MAX_GRID) cap = LB_MAX_GRID;
+  if (cap < 1) cap = 1;
+  return nk_grid_for(items, per_wg, cap);
+}
+
 struct nk_lbroyden {
   nk_ctx *ctx = nullptr;
   int64_t n = 0, ld = 0;
   int T = 0, idx = 0;
-  double *U = nullptr, *V = nullptr, *d0 = nullptr, *du = nullptr;
-  double *sc = nullptr, *dn = nullptr, *part = nullptr, *part0 = nullptr;
-  unsigned int *ticket = nullptr;
-  int grid0 = 0;      // workgroups of the last k_lb_update (its partial sums are folded by the next k_lb_reduce)
+  double *U = nullptr, *V = nullptr, *d0 = nullptr, *du = nullptr, *dn = nullptr;
+  qn_red red;         // grid0: the last k_lb_update's, folded by the next k_lb_reduce
   int last_col = -1;  // column the last k_lb_combine wrote
 };
 
@@ -45,9 +77,10 @@ __device__ __forceinline__ double lb_wave_nanmax(double v) {
   for (int o = 32; o > 0; o >>= 1) v = nk_nanmax(v, __shfl_xor(v, o, 64));
   return v;
 }
+__device__ __forceinline__ double qn_denom(double v) { return v == 0.0 ? 1.0e-5 : v; }   // ifelse(iszero(denom), T(1.0e-5), denom)
 // Hand-off of a workgroup's partial results to the workgroup that arrives last: stores drained by their wavefronts → barrier →
 // agent-scope release → ticket; the last arriver acquires before anybody in it reads. True in every thread of that workgroup.
-__device__ __forceinline__ bool lb_arrive_last(unsigned int *ticket, unsigned int nwg, double *s_flag) {
+__device__ __forceinline__ bool qn_arrive_last(unsigned int *ticket, unsigned int nwg, double *s_flag) {
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
   if (threadIdx.x == 0) {
@@ -64,6 +97,42 @@ __device__ __forceinline__ bool lb_arrive_last(unsigned int *ticket, unsigned in
   __syncthreads();
   return *s_flag != 0.0;
 }
+// (the last workgroup, once its folds are issued; for the next launch: the kernel boundary publishes it)
+__device__ __forceinline__ void qn_ticket_reset(unsigned int *ticket) {
+  if (threadIdx.x == 0) *ticket = 0u;
+}
+// A workgroup's partials of NS slots; slots s < NSUM are sums, the others NaN-propagating maxima. sm: 4·NS doubles.
+// qn_store_partials: the wavefronts' values are in sm[wid·NS + s]; the four are combined pairwise, first with second and third
+// with fourth, into part[s·gridDim.x + blockIdx.x]. The caller's barrier (qn_arrive_last's, or the end of the kernel) follows the store.
+template <int NS, int NSUM>
+__device__ __forceinline__ void qn_store_partials(const double *sm, double *part) {
+  __syncthreads();
+  if ((int)threadIdx.x < NS) {
+    const int s = threadIdx.x;
+    const double p0 = sm[s], p1 = sm[NS + s], p2 = sm[2 * NS + s], p3 = sm[3 * NS + s];
+    part[(size_t)s * gridDim.x + blockIdx.x] = s < NSUM ? (p0 + p1) + (p2 + p3) : nk_nanmax(nk_nanmax(p0, p1), nk_nanmax(p2, p3));
+  }
+}
+// qn_block_partials: from v[s] per thread — the wave butterfly first
+template <int NS, int NSUM>
+__device__ __forceinline__ void qn_block_partials(const double (&v)[NS], double *sm, double *part) {
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+  double r[NS];   // (all butterflies, then one block of stores: a store between two butterflies is a branch of its own)
+#pragma unroll
+  for (int s = 0; s < NS; ++s) r[s] = s < NSUM ? lb_wave_sum(v[s]) : lb_wave_nanmax(v[s]);
+  if (lane == 0) {
+#pragma unroll
+    for (int s = 0; s < NS; ++s) sm[wid * NS + s] = r[s];
+  }
+  qn_store_partials<NS, NSUM>(sm, part);
+}
+// One wavefront folds one slot over the cnt workgroups that wrote it: lane b takes p[b], p[b + 64], … in ascending order, then
+// the butterfly. The value is in every lane.
+__device__ __forceinline__ double qn_fold_slot(const double *p, int cnt, bool is_max) {
+  double v = 0.0;
+  for (int b = threadIdx.x & 63; b < cnt; b += 64) v = is_max ? nk_nanmax(v, p[b]) : v + p[b];
+  return is_max ? lb_wave_nanmax(v) : lb_wave_sum(v);
+}
 
 // ----------------------------------------------------------------------------- update (vectors only)
 // mode 0: δu = −(a·fu)                      (idx = 0: the first step and the step after a reset)
@@ -73,27 +142,19 @@ __global__ __launch_bounds__(NK_BLOCK) void k_lb_update(int64_t n, int mode, dou
                                                         const double *__restrict__ sc, const double *__restrict__ u,
                                                         double *__restrict__ unew, double *__restrict__ du,
                                                         double *__restrict__ part0) {
-  __shared__ double sm[8];
+  __shared__ double sm[4 * 2];
   const double beta = mode ? sc[LB_ZETA] / sc[LB_DENOM] : 0.0;
-  double sd = 0.0, su = 0.0;
+  double acc[2] = {0.0, 0.0};   // Σδu², Σu_new²
   const int64_t stride = (int64_t)gridDim.x * NK_BLOCK;
   for (int64_t i = (int64_t)blockIdx.x * NK_BLOCK + threadIdx.x; i < n; i += stride) {
     const double d = mode ? -(d0[i] + ucol[i] * beta) : -(a * fu[i]);
     const double un = u[i] + d;
     du[i] = d;
     unew[i] = un;
-    sd += d * d;
-    su += un * un;
+    acc[0] += d * d;
+    acc[1] += un * un;
   }
-  sd = lb_wave_sum(sd);
-  su = lb_wave_sum(su);
-  const int w = threadIdx.x >> 6;
-  if ((threadIdx.x & 63) == 0) { sm[w] = sd; sm[4 + w] = su; }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    part0[blockIdx.x] = (sm[0] + sm[1]) + (sm[2] + sm[3]);
-    part0[gridDim.x + blockIdx.x] = (sm[4] + sm[5]) + (sm[6] + sm[7]);
-  }
+  qn_block_partials<2, 2>(acc, sm, part0);
 }
 
 // ----------------------------------------------------------------------------- reduce pass
@@ -109,8 +170,8 @@ struct lb_reduce_args {
 // M = number of active columns (exact: no per-column predicate around the loads)
 template <int M>
 __global__ __launch_bounds__(NK_BLOCK) void k_lb_reduce(lb_reduce_args a) {
-  constexpr int MA = M > 0 ? M : 1, NS = 2 * M + 4;   // slots: Vᵀx (M), Ũᵀy (M), Σx², max|x|, flag du, flag dfu
-  constexpr int CH = 8;                                // columns requested together
+  constexpr int MA = M > 0 ? M : 1, NS = 2 * M + 4;   // slots: Vᵀx (M), Ũᵀy (M), Σx² — sums; max|x|, flag du, flag dfu — maxima
+  constexpr int NSUM = 2 * M + 1, CH = 8;              // CH: columns requested together
   __shared__ double sm[4 * NS + 1];
   double av[MA], au[MA];
 #pragma unroll
@@ -155,7 +216,8 @@ __global__ __launch_bounds__(NK_BLOCK) void k_lb_reduce(lb_reduce_args a) {
     if (fabs(yv) <= a.tol) fdu = 1.0;
     if (fabs(xv - a.r[i]) <= a.tol) fdf = 1.0;
   }
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+  // (the wave stage by hand: 2M + 4 accumulators handed to qn_block_partials as one array cost occupancy from M = 5 on)
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6, nwg = gridDim.x;
 #pragma unroll
   for (int j = 0; j < M; ++j) {
     const double s1 = lb_wave_sum(av[j]), s2 = lb_wave_sum(au[j]);
@@ -165,22 +227,13 @@ __global__ __launch_bounds__(NK_BLOCK) void k_lb_reduce(lb_reduce_args a) {
     const double s = lb_wave_sum(ss), m = lb_wave_nanmax(mx), f1 = lb_wave_nanmax(fdu), f2 = lb_wave_nanmax(fdf);
     if (lane == 0) { sm[wid * NS + 2 * M] = s; sm[wid * NS + 2 * M + 1] = m; sm[wid * NS + 2 * M + 2] = f1; sm[wid * NS + 2 * M + 3] = f2; }
   }
-  __syncthreads();
-  if ((int)threadIdx.x < NS) {
-    const int s = threadIdx.x;
-    const double p0 = sm[s], p1 = sm[NS + s], p2 = sm[2 * NS + s], p3 = sm[3 * NS + s];
-    a.part[(size_t)s * gridDim.x + blockIdx.x] = (s <= 2 * M) ? (p0 + p1) + (p2 + p3) : nk_nanmax(nk_nanmax(p0, p1), nk_nanmax(p2, p3));
-  }
-  if (!lb_arrive_last(a.ticket, gridDim.x, &sm[4 * NS])) return;
-  // ---- the last workgroup: slot s is combined by wavefront s mod 4, workgroup partials in ascending order per lane
-  const int nwg = gridDim.x;
+  qn_store_partials<NS, NSUM>(sm, a.part);
+  if (!qn_arrive_last(a.ticket, gridDim.x, &sm[4 * NS])) return;
+  // ---- the last workgroup: its NS slots, then the two sums k_lb_update left in part0
   for (int s = wid; s < NS + 2; s += 4) {
-    const bool is_max = s > 2 * M && s < NS;
-    const double *p = s < NS ? a.part + (size_t)s * nwg : a.part0 + (size_t)(s - NS) * a.grid0;
-    const int cnt = s < NS ? nwg : a.grid0;
-    double v = 0.0;
-    for (int b = lane; b < cnt; b += 64) v = is_max ? nk_nanmax(v, p[b]) : v + p[b];
-    v = is_max ? lb_wave_nanmax(v) : lb_wave_sum(v);
+    const bool own = s < NS;
+    const double v = qn_fold_slot(own ? a.part + (size_t)s * nwg : a.part0 + (size_t)(s - NS) * a.grid0, own ? nwg : a.grid0,
+                                  own && s >= NSUM);
     if (lane == 0) {
       if (s < M) a.sc[LB_C1 + s] = v / a.dn[s];
       else if (s < 2 * M) a.sc[LB_C2 + (s - M)] = v / a.dn[s - M];
@@ -192,7 +245,7 @@ __global__ __launch_bounds__(NK_BLOCK) void k_lb_reduce(lb_reduce_args a) {
       else a.sc[LB_U_SS] = v;
     }
   }
-  if (threadIdx.x == 0) *a.ticket = 0u;   // (for the next launch: the kernel boundary publishes it)
+  qn_ticket_reset(a.ticket);
 }
 
 // ----------------------------------------------------------------------------- combine pass
@@ -231,11 +284,12 @@ __device__ __forceinline__ void lb_combine_one(const lb_combine_args &a, const d
 template <int M>
 __global__ __launch_bounds__(NK_BLOCK) void k_lb_combine(lb_combine_args a) {
   constexpr int MA = M > 0 ? M : 1;
-  __shared__ double sm[9];
+  __shared__ double sm[4 * 2 + 1];
   __shared__ double2 c[MA];
   if ((int)threadIdx.x < M) c[threadIdx.x] = make_double2(a.sc[LB_C1 + threadIdx.x], a.sc[LB_C2 + threadIdx.x]);
   __syncthreads();
-  double den = 0.0, zeta = 0.0;
+  double acc[2] = {0.0, 0.0};
+  double &den = acc[0], &zeta = acc[1];
   const int64_t npair = a.n >> 1, stride = (int64_t)gridDim.x * NK_BLOCK;
   const double2 *x2 = reinterpret_cast<const double2 *>(a.x), *y2 = reinterpret_cast<const double2 *>(a.y);
   double2 *uw = reinterpret_cast<double2 *>(a.U + (size_t)a.jw * a.ld), *vw = reinterpret_cast<double2 *>(a.V + (size_t)a.jw * a.ld),
@@ -267,33 +321,17 @@ __global__ __launch_bounds__(NK_BLOCK) void k_lb_combine(lb_combine_args a) {
     a.V[(size_t)a.jw * a.ld + i] = z;
     a.d0[i] = d;
   }
-  den = lb_wave_sum(den);
-  zeta = lb_wave_sum(zeta);
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-  if (lane == 0) { sm[wid] = den; sm[4 + wid] = zeta; }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    a.part[blockIdx.x] = (sm[0] + sm[1]) + (sm[2] + sm[3]);
-    a.part[gridDim.x + blockIdx.x] = (sm[4] + sm[5]) + (sm[6] + sm[7]);
-  }
-  if (!lb_arrive_last(a.ticket, gridDim.x, &sm[8])) return;
-  const int nwg = gridDim.x;
-  if (wid < 2) {
-    const double *p = a.part + (size_t)wid * nwg;
-    double v = 0.0;
-    for (int b = lane; b < nwg; b += 64) v += p[b];
-    v = lb_wave_sum(v);
+  qn_block_partials<2, 2>(acc, sm, a.part);
+  if (!qn_arrive_last(a.ticket, gridDim.x, &sm[4 * 2])) return;
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6, nwg = gridDim.x;
+  for (int s = wid; s < 2; s += 4) {
+    const double v = qn_fold_slot(a.part + (size_t)s * nwg, nwg, false);
     if (lane == 0) {
-      if (wid == 0) {
-        if (v == 0.0) v = 1.0e-5;   // ifelse(iszero(denom), T(1.0e-5), denom)  (broyden.jl:143)
-        a.sc[LB_DENOM] = v;
-        a.dn[a.jw] = v;
-      } else {
-        a.sc[LB_ZETA] = v;
-      }
+      if (s == 0) a.sc[LB_DENOM] = a.dn[a.jw] = qn_denom(v);   // (broyden.jl:143)
+      else a.sc[LB_ZETA] = v;
     }
   }
-  if (threadIdx.x == 0) *a.ticket = 0u;
+  qn_ticket_reset(a.ticket);
 }
 
 // ----------------------------------------------------------------------------- host side
@@ -309,12 +347,6 @@ __global__ __launch_bounds__(NK_BLOCK) void k_lb_combine(lb_combine_args a) {
     default: NK_FAIL(NK_E_INVALID, "LimitedMemoryBroyden: %d active columns", (int)(m));                              \
   }
 
-static int lb_grid(const nk_lbroyden *W) {   // sized to the CUs: at most two workgroups each
-  int cap = 2 * W->ctx->num_cus;
-  if (cap > LB_MAX_GRID) cap = LB_MAX_GRID;
-  return nk_grid_for(W->n >> 1, NK_BLOCK * 2, cap);
-}
-
 int nk_lb_create(nk_ctx *ctx, int64_t n, int threshold, nk_lbroyden **out) {
   NK_REQUIRE(ctx && out && n > 0, "bad argument");
   NK_REQUIRE(threshold >= 1 && threshold <= LB_MAX_T, "LimitedMemoryBroyden: threshold %d is outside 1..%d", threshold, LB_MAX_T);
@@ -328,29 +360,23 @@ int nk_lb_create(nk_ctx *ctx, int64_t n, int threshold, nk_lbroyden **out) {
   NK_TRY(nk_dev_alloc(&W->V, (size_t)W->ld * threshold));
   NK_TRY(nk_dev_alloc(&W->d0, (size_t)n + 2));
   NK_TRY(nk_dev_alloc(&W->du, (size_t)n + 2));
-  NK_TRY(nk_dev_alloc(&W->sc, (size_t)LB_NSCAL));
   NK_TRY(nk_dev_alloc(&W->dn, (size_t)LB_MAX_T));
-  NK_TRY(nk_dev_alloc(&W->part, (size_t)(2 * LB_MAX_T + 4) * LB_MAX_GRID));
-  NK_TRY(nk_dev_alloc(&W->part0, (size_t)2 * NK_MAX_RED_BLOCKS));
-  NK_TRY(nk_dev_alloc(&W->ticket, (size_t)2));
-  NK_HIP(nk_memset(ctx, W->sc, 0, LB_NSCAL * sizeof(double)));
+  NK_TRY(qn_red_alloc(ctx, &W->red, LB_NSCAL, 2 * LB_MAX_T + 4, 2, 2));   // tickets: the reduce pass's, the combine pass's
   NK_HIP(nk_memset(ctx, W->du, 0, ((size_t)n + 2) * sizeof(double)));
-  NK_TRY(nk_lb_restart(W));
   *out = guard.release();
   return NK_OK;
 }
 void nk_lb_destroy(nk_lbroyden *W) {
   if (!W) return;
-  hipFree(W->U); hipFree(W->V); hipFree(W->d0); hipFree(W->du); hipFree(W->sc); hipFree(W->dn); hipFree(W->part);
-  hipFree(W->part0); hipFree(W->ticket);
+  hipFree(W->U); hipFree(W->V); hipFree(W->d0); hipFree(W->du); hipFree(W->dn);
+  qn_red_free(&W->red);
   delete W;
 }
-// idx = 0 (a reset, or a new solve); the tickets are zeroed as well, in stream order
+// idx = 0 (a reset, or a new solve)
 int nk_lb_restart(nk_lbroyden *W) {
   W->idx = 0;
   W->last_col = -1;
-  NK_HIP(nk_memset(W->ctx, W->ticket, 0, 2 * sizeof(unsigned int)));
-  return NK_OK;
+  return qn_red_restart(W->ctx, &W->red);
 }
 int nk_lb_columns(const nk_lbroyden *W) { return W->idx < W->T ? W->idx : W->T; }
 int nk_lb_index(const nk_lbroyden *W) { return W->idx; }
@@ -365,17 +391,18 @@ int nk_lb_direction(nk_lbroyden *W, double a, const double *fu, const double *u,
   const int grid = nk_grid_for(W->n, NK_BLOCK * 4, NK_MAX_RED_BLOCKS);
   nk_prof_scope prof_(ctx, NK_K_NEWTON_UPDATE, (mode ? 40.0 : 32.0) * (double)W->n);
   NK_LAUNCH(ctx, k_lb_update, dim3(grid), dim3(NK_BLOCK), W->n, mode, a, fu, (const double *)W->d0,
-            (const double *)(W->U + (size_t)(mode ? W->last_col : 0) * W->ld), (const double *)W->sc, u, u_new, W->du, W->part0);
+            (const double *)(W->U + (size_t)(mode ? W->last_col : 0) * W->ld), (const double *)W->red.sc, u, u_new, W->du, W->red.part0);
   NK_HIP(hipGetLastError());
-  W->grid0 = grid;
+  W->red.grid0 = grid;
   return NK_OK;
 }
 // one read of U and V: the coefficients of the update, the residual's norms, the step's norms and the reset test's flags.
 // `ref` is the residual the reset test last looked at. The six leading scalars are what the host fetches (nk_lb_scalars).
 int nk_lb_reduce(nk_lbroyden *W, const double *fu_new, const double *ref, double tol) {
   nk_ctx *ctx = W->ctx;
-  const int m = nk_lb_columns(W), grid = lb_grid(W);
-  lb_reduce_args a{W->n, W->ld, W->U, W->V, fu_new, W->du, ref, tol, W->dn, W->part0, W->grid0, W->part, W->sc, W->ticket};
+  const int m = nk_lb_columns(W), grid = qn_red_grid(ctx, W->n >> 1, NK_BLOCK * 2);
+  const qn_red &r = W->red;
+  lb_reduce_args a{W->n, W->ld, W->U, W->V, fu_new, W->du, ref, tol, W->dn, r.part0, r.grid0, r.part, r.sc, r.ticket};
   nk_prof_scope prof_(ctx, NK_K_MULTIDOT, (16.0 * m + 24.0) * (double)W->n);
 #define LB_F(M) NK_LAUNCH(ctx, k_lb_reduce<M>, dim3(grid), dim3(NK_BLOCK), a)
   LB_SWITCH_0_32(m, LB_F)
@@ -383,12 +410,12 @@ int nk_lb_reduce(nk_lbroyden *W, const double *fu_new, const double *ref, double
   NK_HIP(hipGetLastError());
   return NK_OK;
 }
-double *nk_lb_scalars(nk_lbroyden *W) { return W->sc; }
+double *nk_lb_scalars(nk_lbroyden *W) { return W->red.sc; }
 // one read of U and V: the new column pair (column mod1(idx + 1, threshold)), d₀, denom and z·fu_new; idx += 1
 int nk_lb_combine(nk_lbroyden *W, double a, const double *fu_new) {
   nk_ctx *ctx = W->ctx;
-  const int m = nk_lb_columns(W), grid = lb_grid(W), jw = W->idx % W->T;
-  lb_combine_args c{W->n, W->ld, W->U, W->V, fu_new, W->du, a, jw, W->d0, W->part, W->sc, W->dn, W->ticket + 1};
+  const int m = nk_lb_columns(W), grid = qn_red_grid(ctx, W->n >> 1, NK_BLOCK * 2), jw = W->idx % W->T;
+  lb_combine_args c{W->n, W->ld, W->U, W->V, fu_new, W->du, a, jw, W->d0, W->red.part, W->red.sc, W->dn, W->red.ticket + 1};
   nk_prof_scope prof_(ctx, NK_K_MULTIAXPY, (16.0 * m + 40.0) * (double)W->n);
 #define LB_F(M) NK_LAUNCH(ctx, k_lb_combine<M>, dim3(grid), dim3(NK_BLOCK), c)
   LB_SWITCH_0_32(m, LB_F)
@@ -415,8 +442,7 @@ enum { SANE_SS = 0, SANE_MAX = 1, SANE_DOT = 2, SANE_NSCAL = 3 };
 struct nk_sane {
   nk_ctx *ctx = nullptr;
   int64_t n = 0;
-  double *sc = nullptr, *part = nullptr;
-  unsigned int *ticket = nullptr;
+  qn_red red;   // (no vector launch leaves partials: part0 is empty)
 };
 
 __global__ __launch_bounds__(NK_BLOCK) void k_sane_trial(int64_t n, double sigma, double a, const double *__restrict__ x,
@@ -441,9 +467,10 @@ struct sane_reduce_args {
   unsigned int *ticket;
 };
 __global__ __launch_bounds__(NK_BLOCK) void k_sane_reduce(sane_reduce_args a) {
-  constexpr int NS = SANE_NSCAL;
+  constexpr int NS = SANE_NSCAL, NSUM = 2;   // slots: Σf_t², Σ f·(f_t − f) — sums; max|f_t| — a maximum
   __shared__ double sm[4 * NS + 1];
-  double ss = 0.0, mx = 0.0, dt = 0.0;
+  double acc[NS] = {0.0, 0.0, 0.0};
+  double &ss = acc[0], &dt = acc[1], &mx = acc[2];
   const int64_t npair = a.n >> 1, stride = (int64_t)gridDim.x * NK_BLOCK;
   const double2 *t2 = reinterpret_cast<const double2 *>(a.ft), *f2 = reinterpret_cast<const double2 *>(a.f);
   for (int64_t i = (int64_t)blockIdx.x * NK_BLOCK + threadIdx.x; i < npair; i += stride) {
@@ -459,36 +486,14 @@ __global__ __launch_bounds__(NK_BLOCK) void k_sane_reduce(sane_reduce_args a) {
     mx = nk_nanmax(mx, fabs(tv));
     dt += fv * (tv - fv);
   }
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-  {
-    const double s = lb_wave_sum(ss), m = lb_wave_nanmax(mx), d = lb_wave_sum(dt);
-    if (lane == 0) { sm[wid * NS + SANE_SS] = s; sm[wid * NS + SANE_MAX] = m; sm[wid * NS + SANE_DOT] = d; }
+  qn_block_partials<NS, NSUM>(acc, sm, a.part);
+  if (!qn_arrive_last(a.ticket, gridDim.x, &sm[4 * NS])) return;
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6, nwg = gridDim.x;
+  for (int s = wid; s < NS; s += 4) {
+    const double v = qn_fold_slot(a.part + (size_t)s * nwg, nwg, s >= NSUM);
+    if (lane == 0) a.sc[s == 0 ? SANE_SS : (s == 1 ? SANE_DOT : SANE_MAX)] = v;
   }
-  __syncthreads();
-  if ((int)threadIdx.x < NS) {
-    const int s = threadIdx.x;
-    const double p0 = sm[s], p1 = sm[NS + s], p2 = sm[2 * NS + s], p3 = sm[3 * NS + s];
-    a.part[(size_t)s * gridDim.x + blockIdx.x] = (s == SANE_MAX) ? nk_nanmax(nk_nanmax(p0, p1), nk_nanmax(p2, p3)) : (p0 + p1) + (p2 + p3);
-  }
-  if (!lb_arrive_last(a.ticket, gridDim.x, &sm[4 * NS])) return;
-  // ---- the last workgroup: slot s is combined by wavefront s, workgroup partials in ascending order per lane
-  const int nwg = gridDim.x;
-  if (wid < NS) {
-    const bool is_max = wid == SANE_MAX;
-    const double *p = a.part + (size_t)wid * nwg;
-    double v = 0.0;
-    for (int b = lane; b < nwg; b += 64) v = is_max ? nk_nanmax(v, p[b]) : v + p[b];
-    v = is_max ? lb_wave_nanmax(v) : lb_wave_sum(v);
-    if (lane == 0) a.sc[wid] = v;
-  }
-  if (threadIdx.x == 0) *a.ticket = 0u;   // (for the next launch: the kernel boundary publishes it)
-}
-
-static int sane_grid(const nk_sane *W) {   // sized to the CUs: at most two workgroups each
-  int cap = 2 * W->ctx->num_cus;
-  if (cap > LB_MAX_GRID) cap = LB_MAX_GRID;
-  if (cap < 1) cap = 1;
-  return nk_grid_for(W->n >> 1, NK_BLOCK * 2, cap);
+  qn_ticket_reset(a.ticket);
 }
 
 int nk_sane_create(nk_ctx *ctx, int64_t n, nk_sane **out) {
@@ -497,24 +502,16 @@ int nk_sane_create(nk_ctx *ctx, int64_t n, nk_sane **out) {
   auto guard = nk_make_guard(W, [](nk_sane *w) { nk_sane_destroy(w); });
   W->ctx = ctx;
   W->n = n;
-  NK_TRY(nk_dev_alloc(&W->sc, (size_t)SANE_NSCAL + 1));
-  NK_TRY(nk_dev_alloc(&W->part, (size_t)SANE_NSCAL * LB_MAX_GRID));
-  NK_TRY(nk_dev_alloc(&W->ticket, (size_t)1));
-  NK_HIP(nk_memset(ctx, W->sc, 0, (SANE_NSCAL + 1) * sizeof(double)));
-  NK_TRY(nk_sane_restart(W));
+  NK_TRY(qn_red_alloc(ctx, &W->red, SANE_NSCAL + 1, SANE_NSCAL, 0, 1));
   *out = guard.release();
   return NK_OK;
 }
 void nk_sane_destroy(nk_sane *W) {
   if (!W) return;
-  hipFree(W->sc); hipFree(W->part); hipFree(W->ticket);
+  qn_red_free(&W->red);
   delete W;
 }
-// a new solve: the ticket is zeroed, in stream order
-int nk_sane_restart(nk_sane *W) {
-  NK_HIP(nk_memset(W->ctx, W->ticket, 0, sizeof(unsigned int)));
-  return NK_OK;
-}
+int nk_sane_restart(nk_sane *W) { return qn_red_restart(W->ctx, &W->red); }   // a new solve
 // x_t = x + a·(−(σ·f)); out of place (x stays intact)
 int nk_sane_trial(nk_sane *W, double sigma, double a, const double *x, const double *f, double *xt) {
   nk_ctx *ctx = W->ctx;
@@ -528,14 +525,14 @@ int nk_sane_trial(nk_sane *W, double sigma, double a, const double *x, const dou
 // one read of f_t and f; the three scalars the host fetches are nk_sane_scalars()[0..2]: Σf_t², max|f_t|, Σ f·(f_t − f)
 int nk_sane_reduce(nk_sane *W, const double *ft, const double *f) {
   nk_ctx *ctx = W->ctx;
-  const int grid = sane_grid(W);
-  sane_reduce_args a{W->n, ft, f, W->part, W->sc, W->ticket};
+  const int grid = qn_red_grid(ctx, W->n >> 1, NK_BLOCK * 2);
+  sane_reduce_args a{W->n, ft, f, W->red.part, W->red.sc, W->red.ticket};
   nk_prof_scope prof_(ctx, NK_K_MULTIDOT, 16.0 * (double)W->n);
   NK_LAUNCH(ctx, k_sane_reduce, dim3(grid), dim3(NK_BLOCK), a);
   NK_HIP(hipGetLastError());
   return NK_OK;
 }
-double *nk_sane_scalars(nk_sane *W) { return W->sc; }
+double *nk_sane_scalars(nk_sane *W) { return W->red.sc; }
 // algorithmic bytes of the two passes of one trial (what tools/dfsane_bench.py divides by)
 double nk_sane_pass_bytes(int64_t n) { return 40.0 * (double)n; }
 
@@ -550,11 +547,11 @@ double nk_sane_pass_bytes(int64_t n) { return 40.0 * (double)n; }
 //   k_bd_fold     z = Σ_tiles zpart, tiles in ascending order; denom = Σ_tiles (δu·w), 1e-5 if exactly 0     (good Broyden only)
 //   k_bd_pass_b   ONE READ + ONE WRITE: J⁻¹ᵢⱼ += cᵢ zⱼ, c = (δu − w)/denom, and in the same pass the row sums (J⁻¹_new fu)ᵢ
 // 24·n² bytes plus 16·n²/BD_R for zpart. Bad Broyden has z = dfu and denom = ‖dfu‖²: no z pass. A reset is k_bd_fill. No workgroup
-// waits for another, every sum has a fixed order, nothing is accumulated with atomics: two runs give the same bits.
+// waits for another.
 constexpr int BD_R = 32;   // rows of a tile: 32 row accumulators per lane
 enum { QN_FNORM_INF = 0, QN_FNORM_SS = 1, QN_DU_SS = 2, QN_FLAG_DU = 3, QN_FLAG_DFU = 4, QN_U_SS = 5, QN_DFU_SS = 6, QN_DIAG_DEN = 7,
        QN_DENOM = 8, QN_FLAG_ZERO = 9, QN_NEXT_SS = 10, QN_NSCAL = 11 };
-constexpr int QN_NRED = 5;   // slots a reduce pass writes per workgroup
+constexpr int QN_NRED = 5, QN_NSUM = 3;   // slots a reduce pass writes per workgroup: three sums, then two maxima
 
 struct nk_qn {
   nk_ctx *ctx = nullptr;
@@ -562,12 +559,8 @@ struct nk_qn {
   int kind = 0, tiles = 0;
   double *Jm = nullptr, *zpart = nullptr;                     // the dense form: allocated by the first fill
   double *Jd = nullptr, *du = nullptr, *dnext = nullptr, *w = nullptr, *z = nullptr, *dfu = nullptr, *dpart = nullptr;
-  double *sc = nullptr, *part = nullptr, *part0 = nullptr;
-  unsigned int *ticket = nullptr;
-  int grid0 = 0;       // workgroups of the last k_qn_update whose partial sums nobody has folded yet (0: none)
+  qn_red red;          // grid0: the last k_qn_update's, until k_qn_reduce or k_kl_step has folded it
 };
-
-__device__ __forceinline__ double qn_denom(double v) { return v == 0.0 ? 1.0e-5 : v; }   // ifelse(iszero(denom), T(1.0e-5), denom)
 
 // ----------------------------------------------------------------------------- vectors: the step
 // mode 0: δu = −(a·fu)   mode 1: δu = −src   mode 2: δu = −(Jd·fu)   mode 3: δu = −(fu/Jd);   fill: Jd = a first (a reset)
@@ -576,8 +569,8 @@ __global__ __launch_bounds__(NK_BLOCK) void k_qn_update(int64_t n, int mode, int
                                                         double *__restrict__ Jd, const double *__restrict__ u,
                                                         double *__restrict__ unew, double *__restrict__ du,
                                                         double *__restrict__ part0) {
-  __shared__ double sm[12];
-  double sd = 0.0, su = 0.0, fl = 0.0;
+  __shared__ double sm[4 * 3];
+  double acc[3] = {0.0, 0.0, 0.0};   // Σδu², Σu_new², any(|δu| ≤ tol)
   const int64_t stride = (int64_t)gridDim.x * NK_BLOCK;
   for (int64_t i = (int64_t)blockIdx.x * NK_BLOCK + threadIdx.x; i < n; i += stride) {
     double d;
@@ -591,39 +584,19 @@ __global__ __launch_bounds__(NK_BLOCK) void k_qn_update(int64_t n, int mode, int
     const double un = u[i] + d;
     du[i] = d;
     unew[i] = un;
-    sd += d * d;
-    su += un * un;
-    if (fabs(d) <= tol) fl = 1.0;
+    acc[0] += d * d;
+    acc[1] += un * un;
+    if (fabs(d) <= tol) acc[2] = 1.0;
   }
-  sd = lb_wave_sum(sd);
-  su = lb_wave_sum(su);
-  fl = lb_wave_nanmax(fl);
-  const int w = threadIdx.x >> 6;
-  if ((threadIdx.x & 63) == 0) { sm[w] = sd; sm[4 + w] = su; sm[8 + w] = fl; }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    part0[blockIdx.x] = (sm[0] + sm[1]) + (sm[2] + sm[3]);
-    part0[gridDim.x + blockIdx.x] = (sm[4] + sm[5]) + (sm[6] + sm[7]);
-    part0[2 * gridDim.x + blockIdx.x] = nk_nanmax(nk_nanmax(sm[8], sm[9]), nk_nanmax(sm[10], sm[11]));
-  }
+  qn_block_partials<3, 2>(acc, sm, part0);
 }
 
-// the last workgroup of a reduce pass: slot s < QN_NRED of `part` and the three slots of an unfolded k_qn_update, one wavefront
-// per slot in turn, workgroup partials in ascending order per lane. dst[s]: the scalar slot s lands in (QN_NRED + 3 entries);
-// maxmask: the slots of `part` combined with the NaN-propagating maximum.
-__device__ __forceinline__ void qn_fold_slots(const double *part, int nwg, const double *part0, int grid0, double *sc,
-                                              const int *dst, unsigned int maxmask) {
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-  for (int s = wid; s < QN_NRED + 3; s += 4) {
-    if (s >= QN_NRED && grid0 == 0) continue;
-    const bool is_max = s < QN_NRED ? ((maxmask >> s) & 1u) != 0u : s == QN_NRED + 2;
-    const double *p = s < QN_NRED ? part + (size_t)s * nwg : part0 + (size_t)(s - QN_NRED) * grid0;
-    const int cnt = s < QN_NRED ? nwg : grid0;
-    double v = 0.0;
-    for (int b = lane; b < cnt; b += 64) v = is_max ? nk_nanmax(v, p[b]) : v + p[b];
-    v = is_max ? lb_wave_nanmax(v) : lb_wave_sum(v);
-    if (lane == 0) sc[dst[s]] = v;
-  }
+// the last workgroup of k_qn_reduce and k_kl_step: slot s < QN_NRED of `part`, or slot s − QN_NRED of an unfolded k_qn_update
+// (the caller skips those when grid0 = 0)
+__device__ __forceinline__ double qn_fold_red(const double *part, int nwg, const double *part0, int grid0, int s) {
+  const bool own = s < QN_NRED;
+  return qn_fold_slot(own ? part + (size_t)s * nwg : part0 + (size_t)(s - QN_NRED) * grid0, own ? nwg : grid0,
+                      own ? s >= QN_NSUM : s == QN_NRED + 2);
 }
 
 // ----------------------------------------------------------------------------- vectors: what the host reads (Broyden)
@@ -631,7 +604,7 @@ struct qn_reduce_args {
   int64_t n;
   const double *x, *xp, *y, *r, *Jd;   // fu_new, fu_prev, δu, the residual the reset test compares with; Jd: NULL or the diagonal
   double tol;
-  int den;                              // what sc[QN_DENOM] becomes: 0 nothing (pass A's fold writes it), 1 ‖dfu‖², 2 Σ Jd·dfu·δu
+  int den;                              // what sc[QN_DENOM] becomes: 0 nothing (k_bd_fold writes it), 1 ‖dfu‖² (slot 1), 2 Σ Jd·dfu·δu (slot 2)
   double *dfu;
   const double *part0;
   int grid0;
@@ -639,9 +612,10 @@ struct qn_reduce_args {
   unsigned int *ticket;
 };
 __global__ __launch_bounds__(NK_BLOCK) void k_qn_reduce(qn_reduce_args a) {
-  constexpr int NS = QN_NRED;   // max|x|, Σx², flag dfu, Σdfu², Σ (Jd·dfu)·δu
+  constexpr int NS = QN_NRED;   // Σx², Σdfu², Σ (Jd·dfu)·δu, max|x|, flag dfu
   __shared__ double sm[4 * NS + 1];
-  double mx = 0.0, ss = 0.0, fdf = 0.0, sd = 0.0, dd = 0.0;
+  double acc[NS] = {0.0, 0.0, 0.0, 0.0, 0.0};
+  double &ss = acc[0], &sd = acc[1], &dd = acc[2], &mx = acc[3], &fdf = acc[4];
   const int64_t stride = (int64_t)gridDim.x * NK_BLOCK;
   for (int64_t i = (int64_t)blockIdx.x * NK_BLOCK + threadIdx.x; i < a.n; i += stride) {
     const double xv = a.x[i], df = xv - a.xp[i];
@@ -652,30 +626,23 @@ __global__ __launch_bounds__(NK_BLOCK) void k_qn_reduce(qn_reduce_args a) {
     sd += df * df;
     if (a.Jd) dd += (a.Jd[i] * df) * a.y[i];
   }
+  qn_block_partials<NS, QN_NSUM>(acc, sm, a.part);
+  if (!qn_arrive_last(a.ticket, gridDim.x, &sm[4 * NS])) return;
   const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-  {
-    const double v0 = lb_wave_nanmax(mx), v1 = lb_wave_sum(ss), v2 = lb_wave_nanmax(fdf), v3 = lb_wave_sum(sd), v4 = lb_wave_sum(dd);
-    if (lane == 0) { sm[wid * NS] = v0; sm[wid * NS + 1] = v1; sm[wid * NS + 2] = v2; sm[wid * NS + 3] = v3; sm[wid * NS + 4] = v4; }
+  for (int s = wid; s < NS + (a.grid0 ? 3 : 0); s += 4) {
+    const double v = qn_fold_red(a.part, gridDim.x, a.part0, a.grid0, s);
+    if (lane == 0) switch (s) {
+      case 0: a.sc[QN_FNORM_SS] = v; break;
+      case 1: a.sc[QN_DFU_SS] = v; if (a.den == 1) a.sc[QN_DENOM] = qn_denom(v); break;
+      case 2: a.sc[QN_DIAG_DEN] = v; if (a.den == 2) a.sc[QN_DENOM] = qn_denom(v); break;
+      case 3: a.sc[QN_FNORM_INF] = v; break;
+      case 4: a.sc[QN_FLAG_DFU] = v; break;
+      case 5: a.sc[QN_DU_SS] = v; break;
+      case 6: a.sc[QN_U_SS] = v; break;
+      default: a.sc[QN_FLAG_DU] = v;
+    }
   }
-  __syncthreads();
-  if ((int)threadIdx.x < NS) {
-    const int s = threadIdx.x;
-    const double p0 = sm[s], p1 = sm[NS + s], p2 = sm[2 * NS + s], p3 = sm[3 * NS + s];
-    a.part[(size_t)s * gridDim.x + blockIdx.x] = (s == 0 || s == 2) ? nk_nanmax(nk_nanmax(p0, p1), nk_nanmax(p2, p3)) : (p0 + p1) + (p2 + p3);
-  }
-  if (!lb_arrive_last(a.ticket, gridDim.x, &sm[4 * NS])) return;
-  __shared__ int dst[NS + 3];
-  if (threadIdx.x == 0) {
-    dst[0] = QN_FNORM_INF; dst[1] = QN_FNORM_SS; dst[2] = QN_FLAG_DFU; dst[3] = QN_DFU_SS; dst[4] = QN_DIAG_DEN;
-    dst[5] = QN_DU_SS; dst[6] = QN_U_SS; dst[7] = QN_FLAG_DU;
-  }
-  __syncthreads();
-  qn_fold_slots(a.part, gridDim.x, a.part0, a.grid0, a.sc, dst, 0x5u);
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    if (a.den) a.sc[QN_DENOM] = qn_denom(a.sc[a.den == 1 ? QN_DFU_SS : QN_DIAG_DEN]);
-    *a.ticket = 0u;   // (for the next launch: the kernel boundary publishes it)
-  }
+  qn_ticket_reset(a.ticket);
 }
 
 // ----------------------------------------------------------------------------- the dense inverse: fill, pass A, fold, pass B
@@ -815,9 +782,7 @@ __global__ __launch_bounds__(NK_BLOCK) void k_bd_fold(int64_t n, int64_t ldz, in
     z[n - 1] = zt;
   }
   if (blockIdx.x == 0 && threadIdx.x < 64) {
-    double v = 0.0;
-    for (int b = threadIdx.x; b < tiles; b += 64) v += dpart[b];
-    v = lb_wave_sum(v);
+    const double v = qn_fold_slot(dpart, tiles, false);
     if (threadIdx.x == 0) sc[QN_DENOM] = qn_denom(v);
   }
 }
@@ -874,9 +839,10 @@ struct kl_args {
   unsigned int *ticket;
 };
 __global__ __launch_bounds__(NK_BLOCK) void k_kl_step(kl_args a) {
-  constexpr int NS = QN_NRED;   // max|f|, Σf², flag zero, Σδu_next², Σu²
+  constexpr int NS = QN_NRED;   // Σf², Σδu_next², Σu², max|f|, flag zero
   __shared__ double sm[4 * NS + 1];
-  double mx = 0.0, ss = 0.0, fz = 0.0, sd = 0.0, su = 0.0;
+  double acc[NS] = {0.0, 0.0, 0.0, 0.0, 0.0};
+  double &ss = acc[0], &sd = acc[1], &su = acc[2], &mx = acc[3], &fz = acc[4];
   const int64_t stride = (int64_t)gridDim.x * NK_BLOCK;
   for (int64_t i = (int64_t)blockIdx.x * NK_BLOCK + threadIdx.x; i < a.n; i += stride) {
     const double f = a.f[i], d = a.du[i], uu = a.u[i];
@@ -894,35 +860,26 @@ __global__ __launch_bounds__(NK_BLOCK) void k_kl_step(kl_args a) {
     sd += dn * dn;
     su += uu * uu;
   }
+  qn_block_partials<NS, QN_NSUM>(acc, sm, a.part);
+  if (!qn_arrive_last(a.ticket, gridDim.x, &sm[4 * NS])) return;
   const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-  {
-    const double v0 = lb_wave_nanmax(mx), v1 = lb_wave_sum(ss), v2 = lb_wave_nanmax(fz), v3 = lb_wave_sum(sd), v4 = lb_wave_sum(su);
-    if (lane == 0) { sm[wid * NS] = v0; sm[wid * NS + 1] = v1; sm[wid * NS + 2] = v2; sm[wid * NS + 3] = v3; sm[wid * NS + 4] = v4; }
+  for (int s = wid; s < NS + (a.grid0 ? 3 : 0); s += 4) {
+    const double v = qn_fold_red(a.part, gridDim.x, a.part0, a.grid0, s);
+    if (lane == 0) switch (s) {
+      case 0: a.sc[QN_FNORM_SS] = v; break;
+      case 1: a.sc[QN_NEXT_SS] = v; break;
+      case 2: a.sc[QN_U_SS] = v; break;
+      case 3: a.sc[QN_FNORM_INF] = v; break;
+      case 4: a.sc[QN_FLAG_ZERO] = v; break;
+      case 5: a.sc[QN_DU_SS] = v; break;
+      case 6: a.sc[QN_DIAG_DEN] = v; break;   // (an unfolded k_qn_update's ‖u_new‖² is this launch's Σu² summed in another order: a slot Klement does not read)
+      default: a.sc[QN_FLAG_DU] = v;
+    }
   }
-  __syncthreads();
-  if ((int)threadIdx.x < NS) {
-    const int s = threadIdx.x;
-    const double p0 = sm[s], p1 = sm[NS + s], p2 = sm[2 * NS + s], p3 = sm[3 * NS + s];
-    a.part[(size_t)s * gridDim.x + blockIdx.x] = (s == 0 || s == 2) ? nk_nanmax(nk_nanmax(p0, p1), nk_nanmax(p2, p3)) : (p0 + p1) + (p2 + p3);
-  }
-  if (!lb_arrive_last(a.ticket, gridDim.x, &sm[4 * NS])) return;
-  __shared__ int dst[NS + 3];
-  if (threadIdx.x == 0) {   // (an unfolded k_qn_update's ‖u_new‖² is this launch's Σu² summed in another order: it goes to a slot Klement does not read)
-    dst[0] = QN_FNORM_INF; dst[1] = QN_FNORM_SS; dst[2] = QN_FLAG_ZERO; dst[3] = QN_NEXT_SS; dst[4] = QN_U_SS;
-    dst[5] = QN_DU_SS; dst[6] = QN_DIAG_DEN; dst[7] = QN_FLAG_DU;
-  }
-  __syncthreads();
-  qn_fold_slots(a.part, gridDim.x, a.part0, a.grid0, a.sc, dst, 0x5u);
-  if (threadIdx.x == 0) *a.ticket = 0u;
+  qn_ticket_reset(a.ticket);
 }
 
 // ----------------------------------------------------------------------------- host side
-static int qn_vec_grid(const nk_qn *W) {   // reduce passes: at most two workgroups per CU
-  int cap = 2 * W->ctx->num_cus;
-  if (cap > LB_MAX_GRID) cap = LB_MAX_GRID;
-  if (cap < 1) cap = 1;
-  return nk_grid_for(W->n, NK_BLOCK * 4, cap);
-}
 static bool qn_dense(const nk_qn *W) { return W->kind == NK_QN_GOOD || W->kind == NK_QN_BAD; }
 
 int nk_qn_create(nk_ctx *ctx, int64_t n, int kind, nk_qn **out) {
@@ -951,28 +908,19 @@ int nk_qn_create(nk_ctx *ctx, int64_t n, int kind, nk_qn **out) {
     NK_TRY(nk_dev_alloc(&W->Jd, na));
     NK_HIP(nk_memset(ctx, W->Jd, 0, na * sizeof(double)));
   }
-  NK_TRY(nk_dev_alloc(&W->sc, (size_t)QN_NSCAL));
-  NK_TRY(nk_dev_alloc(&W->part, (size_t)QN_NRED * LB_MAX_GRID));
-  NK_TRY(nk_dev_alloc(&W->part0, (size_t)3 * NK_MAX_RED_BLOCKS));
-  NK_TRY(nk_dev_alloc(&W->ticket, (size_t)1));
-  NK_HIP(nk_memset(ctx, W->sc, 0, QN_NSCAL * sizeof(double)));
+  NK_TRY(qn_red_alloc(ctx, &W->red, QN_NSCAL, QN_NRED, 3, 1));
   NK_HIP(nk_memset(ctx, W->du, 0, na * sizeof(double)));
-  NK_TRY(nk_qn_restart(W));
   *out = guard.release();
   return NK_OK;
 }
 void nk_qn_destroy(nk_qn *W) {
   if (!W) return;
   hipFree(W->Jm); hipFree(W->zpart); hipFree(W->Jd); hipFree(W->du); hipFree(W->dnext); hipFree(W->w); hipFree(W->z);
-  hipFree(W->dfu); hipFree(W->dpart); hipFree(W->sc); hipFree(W->part); hipFree(W->part0); hipFree(W->ticket);
+  hipFree(W->dfu); hipFree(W->dpart);
+  qn_red_free(&W->red);
   delete W;
 }
-// a new solve: the ticket is zeroed, in stream order
-int nk_qn_restart(nk_qn *W) {
-  W->grid0 = 0;
-  NK_HIP(nk_memset(W->ctx, W->ticket, 0, sizeof(unsigned int)));
-  return NK_OK;
-}
+int nk_qn_restart(nk_qn *W) { return qn_red_restart(W->ctx, &W->red); }   // a new solve
 // J⁻¹ = a·I, write-only; the dense matrix (and zpart for good Broyden) is allocated here, by the first step of the first solve
 int nk_qn_fill(nk_qn *W, double a) {
   nk_ctx *ctx = W->ctx;
@@ -995,25 +943,26 @@ int nk_qn_direction(nk_qn *W, int mode, int fill, double a, double tol, const do
   const int grid = nk_grid_for(W->n, NK_BLOCK * 4, NK_MAX_RED_BLOCKS);
   nk_prof_scope prof_(ctx, NK_K_NEWTON_UPDATE, 40.0 * (double)W->n);
   NK_LAUNCH(ctx, k_qn_update, dim3(grid), dim3(NK_BLOCK), W->n, mode, fill, a, tol, fu, (const double *)W->dnext, W->Jd, u, u_new,
-            W->du, W->part0);
+            W->du, W->red.part0);
   NK_HIP(hipGetLastError());
-  W->grid0 = grid;
+  W->red.grid0 = grid;
   return NK_OK;
 }
 // Broyden: dfu and everything the host reads for this step (nk_qn_scalars: QN_FNORM_INF … QN_U_SS)
 int nk_qn_reduce(nk_qn *W, const double *fu_new, const double *fu_prev, const double *ref, double tol) {
   nk_ctx *ctx = W->ctx;
   NK_REQUIRE(W->kind != NK_QN_KLEMENT, "Klement has no reduce pass of its own");
-  const int grid = qn_vec_grid(W);
+  const int grid = qn_red_grid(ctx, W->n, NK_BLOCK * 4);
+  qn_red &r = W->red;
   qn_reduce_args a{W->n, fu_new, fu_prev, W->du, ref, W->kind == NK_QN_DIAGONAL ? W->Jd : nullptr, tol,
-                   W->kind == NK_QN_BAD ? 1 : (W->kind == NK_QN_DIAGONAL ? 2 : 0), W->dfu, W->part0, W->grid0, W->part, W->sc, W->ticket};
+                   W->kind == NK_QN_BAD ? 1 : (W->kind == NK_QN_DIAGONAL ? 2 : 0), W->dfu, r.part0, r.grid0, r.part, r.sc, r.ticket};
   nk_prof_scope prof_(ctx, NK_K_OTHER, 40.0 * (double)W->n);
   NK_LAUNCH(ctx, k_qn_reduce, dim3(grid), dim3(NK_BLOCK), a);
   NK_HIP(hipGetLastError());
-  W->grid0 = 0;
+  r.grid0 = 0;
   return NK_OK;
 }
-double *nk_qn_scalars(nk_qn *W) { return W->sc; }
+double *nk_qn_scalars(nk_qn *W) { return W->red.sc; }
 const double *nk_qn_du(const nk_qn *W) { return W->du; }
 // the update of J⁻¹ from the step nk_qn_reduce looked at, and (dense) the row sums J⁻¹_new·fu_new for the next direction
 int nk_qn_update(nk_qn *W, const double *fu_new) {
@@ -1022,7 +971,7 @@ int nk_qn_update(nk_qn *W, const double *fu_new) {
     const int grid = nk_grid_for(W->n, NK_BLOCK * 4, NK_MAX_RED_BLOCKS);
     nk_prof_scope prof_(ctx, NK_K_MULTIAXPY, 32.0 * (double)W->n);
     NK_LAUNCH(ctx, k_bd_diag_update, dim3(grid), dim3(NK_BLOCK), W->n, W->Jd, (const double *)W->du, (const double *)W->dfu,
-              (const double *)W->sc);
+              (const double *)W->red.sc);
     NK_HIP(hipGetLastError());
     return NK_OK;
   }
@@ -1030,7 +979,7 @@ int nk_qn_update(nk_qn *W, const double *fu_new) {
   const bool good = W->kind == NK_QN_GOOD;
   const double nn = (double)W->n * (double)W->n;
   bd_args a{W->n, W->ld, W->ldz, W->Jm, W->dfu, W->du, W->w, good ? W->z : W->dfu, good ? W->zpart : nullptr,
-            good ? W->dpart : nullptr, W->dnext, W->sc};
+            good ? W->dpart : nullptr, W->dnext, W->red.sc};
   {
     nk_prof_scope prof_(ctx, NK_K_MULTIDOT, 8.0 * nn + (good ? 8.0 * nn / BD_R : 0.0));
     NK_LAUNCH(ctx, k_bd_pass_a, dim3(W->tiles), dim3(NK_BLOCK), a);
@@ -1040,7 +989,7 @@ int nk_qn_update(nk_qn *W, const double *fu_new) {
     const int grid = (int)(((W->n >> 1) + 1 + NK_BLOCK - 1) / NK_BLOCK);
     nk_prof_scope prof_(ctx, NK_K_REDUCE_SMALL, 8.0 * nn / BD_R);
     NK_LAUNCH(ctx, k_bd_fold, dim3(grid), dim3(NK_BLOCK), W->n, W->ldz, W->tiles, (const double *)W->zpart, (const double *)W->dpart,
-              W->z, W->sc);
+              W->z, W->red.sc);
     NK_HIP(hipGetLastError());
   }
   a.x = fu_new;
@@ -1055,12 +1004,13 @@ int nk_qn_update(nk_qn *W, const double *fu_new) {
 int nk_qn_klement_step(nk_qn *W, const double *fu_new, const double *fu_prev, const double *u, double *u_next) {
   nk_ctx *ctx = W->ctx;
   NK_REQUIRE(W->kind == NK_QN_KLEMENT, "not a Klement workspace");
-  const int grid = qn_vec_grid(W);
-  kl_args a{W->n, W->Jd, W->du, fu_new, fu_prev, u, u_next, W->part0, W->grid0, W->part, W->sc, W->ticket};
+  const int grid = qn_red_grid(ctx, W->n, NK_BLOCK * 4);
+  qn_red &r = W->red;
+  kl_args a{W->n, W->Jd, W->du, fu_new, fu_prev, u, u_next, r.part0, r.grid0, r.part, r.sc, r.ticket};
   nk_prof_scope prof_(ctx, NK_K_MULTIAXPY, 64.0 * (double)W->n);
   NK_LAUNCH(ctx, k_kl_step, dim3(grid), dim3(NK_BLOCK), a);
   NK_HIP(hipGetLastError());
-  W->grid0 = 0;
+  r.grid0 = 0;
   return NK_OK;
 }
 // J⁻¹ as the caller's row-major n×n matrix with leading dimension ldo, or the n diagonal entries (Klement: of J)

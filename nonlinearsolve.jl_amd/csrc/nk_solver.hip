@@ -87,17 +87,19 @@ struct nk_solver {
   nk_csr_valstate spec_state{};                 // the filled set (valid) / the spare buffers (not valid)
   nk_precs_fn precs = nullptr;
   void *precs_user = nullptr;
-  // LimitedMemoryBroyden (nk_qn.hip): the low-rank inverse Jacobian, J⁻¹ = lb_a·I + U Vᵀ; the residual lives in a pool of three
-  // buffers — `fu` (current), `lb_ref` (the residual NoChangeInStateReset last looked at: normally the previous one, one step
-  // older after the early return of its `du` branch) and a spare the next evaluation writes into
+  // What the residual-only quasi-Newton drivers share (LimitedMemoryBroyden, Broyden, Klement): the scaling ro_a of the identity
+  // a reset starts from, the reset count and NoChangeInStateReset's state, and the residual pool of three buffers — `fu`
+  // (current), `ro_ref` (the residual the reset test last looked at: normally the previous one, one step older after the early
+  // return of its `du` branch) and a spare the next evaluation writes into
+  double *ro_fupool[3] = {nullptr, nullptr, nullptr};
+  const double *ro_ref = nullptr;
+  double ro_a = 1.0, ro_tol = 0.0, ro_u_ss = 0.0;
+  int ro_max_resets = 0, ro_nresets = 0, ro_since_du = 0, ro_since_dfu = 0;
+  bool ro_flag_du = false, ro_flag_dfu = false;   // the reset test's any(…) flags for the NEXT step (left by this step's reduce pass)
+  // LimitedMemoryBroyden (nk_qn.hip): the low-rank inverse Jacobian, J⁻¹ = ro_a·I + U Vᵀ
   nk_lbroyden *lb = nullptr;
-  double *lb_fupool[3] = {nullptr, nullptr, nullptr};
-  const double *lb_ref = nullptr;
-  double lb_a = 1.0, lb_tol = 0.0, lb_u_ss = 0.0;
-  int lb_threshold = 0, lb_max_resets = 0, lb_nresets = 0, lb_since_du = 0, lb_since_dfu = 0;
-  bool lb_flag_du = false, lb_flag_dfu = false;   // the reset test's any(…) flags for the NEXT step (left by this step's reduce pass)
-  // Broyden and Klement (nk_qn.hip): the reset test's state, the residual pool and the scaling are the lb_* fields above;
-  // qn_next: the iterate Klement's fused launch has prepared (u + the next δu) and ‖that δu‖²
+  int lb_threshold = 0;
+  // Broyden and Klement (nk_qn.hip). qn_next: the iterate Klement's fused launch has prepared (u + the next δu) and ‖that δu‖²
   nk_qn *qn = nullptr;
   double *qn_next = nullptr, qn_next_ss = 0.0;
   bool qn_flag_zero = false;
@@ -530,115 +532,51 @@ static double qn_alpha(double alpha, double fnorm2, double u_ss) {
   if (fnorm2 < 1.0e-5) return 1.0;
   return (2.0 * fnorm2) / fmax(sqrt(u_ss), 1.0);
 }
-static double lb_scaling(const nk_solver *S, double fnorm2, double u_ss) {
+static double ro_scaling(const nk_solver *S, double fnorm2, double u_ss) {
   return 1.0 / qn_alpha(is_qn(S) ? S->o.qn_alpha : S->o.lb_alpha, fnorm2, u_ss);
 }
 // init and reinit!: idx = 0, the reset count and the reset test's counters are zero, the reset test's residual copy is f(u0)
 // (the reference's reinit! leaves that copy at the previous solve's last residual, reset_conditions.jl:47-53 — not kept:
 // a solve from the same u0 repeats itself here). a is computed by the first step, from ‖u0‖₂ and ‖f(u0)‖₂.
-static int lb_start(nk_solver *S) {
+static int ro_start(nk_solver *S) {
   if (S->lb) NK_TRY(nk_lb_restart(S->lb));
   if (S->qn) NK_TRY(nk_qn_restart(S->qn));
   S->qn_next = nullptr;
   S->qn_flag_zero = false;
   S->qn_since_reset = 0;
-  S->lb_nresets = S->lb_since_du = S->lb_since_dfu = 0;
-  S->lb_flag_du = S->lb_flag_dfu = false;
-  S->lb_ref = S->fu;
-  S->lb_a = 1.0;
+  S->ro_nresets = S->ro_since_du = S->ro_since_dfu = 0;
+  S->ro_flag_du = S->ro_flag_dfu = false;
+  S->ro_ref = S->fu;
+  S->ro_a = 1.0;
   NK_TRY(nk_blas_sumsq(S->ctx, S->n, S->u, slot(S, 0)));
-  NK_TRY(fetch(S, 1, &S->lb_u_ss));
+  NK_TRY(fetch(S, 1, &S->ro_u_ss));
   return NK_OK;
 }
 // NoChangeInStateReset(nsteps = 3) (reset_conditions.jl:55-87) on the flags the last step's reduce pass left
-static bool lb_reset_test(nk_solver *S) {
-  if (S->lb_flag_du) {
-    if (++S->lb_since_du >= 3) {
-      S->lb_since_du = S->lb_since_dfu = 0;
+static bool ro_reset_test(nk_solver *S) {
+  if (S->ro_flag_du) {
+    if (++S->ro_since_du >= 3) {
+      S->ro_since_du = S->ro_since_dfu = 0;
       return true;   // (the early return: the residual copy stays where it was)
     }
   } else {
-    S->lb_since_du = S->lb_since_dfu = 0;
+    S->ro_since_du = S->ro_since_dfu = 0;
   }
   bool reset = false;
-  if (S->lb_flag_dfu) {
-    if (++S->lb_since_dfu >= 3) {
-      S->lb_since_dfu = S->lb_since_du = 0;
+  if (S->ro_flag_dfu) {
+    if (++S->ro_since_dfu >= 3) {
+      S->ro_since_dfu = S->ro_since_du = 0;
       reset = true;
     }
   } else {
-    S->lb_since_dfu = S->lb_since_du = 0;
+    S->ro_since_dfu = S->ro_since_du = 0;
   }
-  S->lb_ref = S->fu;   // copyto!(cache.dfu, fu)
+  S->ro_ref = S->fu;   // copyto!(cache.dfu, fu)
   return reset;
 }
 static int check_and_update(nk_solver *S, double step_norm);
-static int lb_step(nk_solver *S, int recompute) {
-  nk_ctx *ctx = S->ctx;
-  NK_REQUIRE(recompute != 0, "LimitedMemoryBroyden: recompute_jacobian = false (a step without the update) is not offered");
-  if (S->nsteps == 0) {   // the first step initialises J⁻¹ whatever the arguments say (solve.jl:301-323)
-    S->lb_a = lb_scaling(S, S->fnorm2, S->lb_u_ss);
-  } else {
-    bool reinit = true;
-    if (recompute < 0) {  // the standard step: the reset test decides, and its resets count
-      reinit = lb_reset_test(S);
-      if (reinit && ++S->lb_nresets >= S->lb_max_resets) {
-        S->retcode = NK_RET_CONVERGENCE_FAILURE;
-        S->force_stop = true;
-        return NK_OK;
-      }
-    }
-    if (reinit) {
-      NK_TRY(nk_lb_restart(S->lb));
-      S->lb_a = lb_scaling(S, S->fnorm2, S->lb_u_ss);
-    }
-  }
-  // δu = −J⁻¹ fu, u += δu (out of place: a retained best iterate stays intact)
-  double *un = spare_u(S);
-  NK_TRY(nk_lb_direction(S->lb, S->lb_a, S->fu, S->u, un));
-  S->u = un;
-  S->u_version++;
-  nk_problem_invalidate(S->P);
-  double *fnew = nullptr;
-  for (double *b : S->lb_fupool)
-    if (b != S->fu && b != S->lb_ref) { fnew = b; break; }
-  NK_TRY(nk_problem_residual_dev(S->P, S->u, fnew));
-  S->stats.nf++;
-  const double *fprev = S->fu;
-  if (S->lb_ref == nullptr) S->lb_ref = fprev;
-  S->fu = fnew;
-  // one pass over U and V: the update's coefficients, and everything the host reads for this step
-  NK_TRY(nk_lb_reduce(S->lb, S->fu, S->lb_ref, S->lb_tol));
-  double v[6];
-  NK_TRY(nk_scalars_to_host(ctx, nk_lb_scalars(S->lb), 6, v));
-  S->fnorm_inf = v[0];
-  S->fnorm2 = sqrt(v[1]);
-  const double step_norm = sqrt(v[2]);
-  S->lb_flag_du = v[3] != 0.0;
-  S->lb_flag_dfu = v[4] != 0.0;
-  S->lb_u_ss = v[5];
-  NK_TRY(check_and_update(S, step_norm));
-  if (S->o.store_trace) {
-    nk_trace_entry e;
-    memset(&e, 0, sizeof(e));
-    e.iter = S->nsteps + 1;
-    e.accepted = 1;
-    e.fnorm_inf = S->fnorm_inf;
-    e.step_norm2 = step_norm;
-    e.eta = NAN;
-    e.trust_region = NAN;
-    e.rho = NAN;
-    S->trace.push_back(e);
-  }
-  if (S->force_stop) return NK_OK;
-  // GoodBroydenUpdateRule: the second pass over U and V writes the new column pair
-  return nk_lb_combine(S->lb, S->lb_a, S->fu);
-}
-
-// ---- Broyden and Klement (lib/NonlinearSolveQuasiNewton/src/solve.jl:296-486 on a dense or diagonal J⁻¹, or Klement's diagonal J).
-// The reset bookkeeping is LimitedMemoryBroyden's (lb_reset_test, lb_scaling, the residual pool); Klement's reset test is the
-// zero flag its fused launch left.
-static void qn_trace(nk_solver *S, double step_norm) {
+// the trace entry of a step that has no forcing term, trust region or gain ratio
+static void push_trace(nk_solver *S, double step_norm) {
   if (!S->o.store_trace) return;
   nk_trace_entry e;
   memset(&e, 0, sizeof(e));
@@ -651,39 +589,95 @@ static void qn_trace(nk_solver *S, double step_norm) {
   e.rho = NAN;
   S->trace.push_back(e);
 }
+// Does this step start from the identity again? The first step does, whatever the arguments say (solve.jl:301-323), and so does
+// recompute_jacobian = true. The standard step (recompute < 0) asks the reset test (`asked`: Klement's zero flag), and its resets
+// count: the one that brings the count to max_resets ends the solve instead (*stop).
+static bool ro_reinit(nk_solver *S, int recompute, const bool *asked, bool *stop) {
+  *stop = false;
+  if (S->nsteps == 0 || recompute > 0) return true;
+  const bool reinit = asked ? *asked : ro_reset_test(S);
+  if (reinit && ++S->ro_nresets >= S->ro_max_resets) {
+    S->retcode = NK_RET_CONVERGENCE_FAILURE;
+    S->force_stop = *stop = true;
+  }
+  return reinit;
+}
+// The step is taken: un becomes the iterate (out of place: a retained best iterate stays intact) and its residual goes into the
+// pool buffer that is neither the current residual nor the reset test's copy. *fprev: the residual of the iterate left behind.
+static int ro_take_step(nk_solver *S, double *un, const double **fprev) {
+  S->u = un;
+  S->u_version++;
+  nk_problem_invalidate(S->P);
+  double *fnew = nullptr;
+  for (double *b : S->ro_fupool)
+    if (b != S->fu && b != S->ro_ref) { fnew = b; break; }
+  NK_TRY(nk_problem_residual_dev(S->P, S->u, fnew));
+  S->stats.nf++;
+  *fprev = S->fu;
+  if (S->ro_ref == nullptr) S->ro_ref = *fprev;
+  S->fu = fnew;
+  return NK_OK;
+}
+// Of the scalars a step's reduce pass left, those every family keeps in the same places: v[0] = max|fu|, v[1] = Σfu², v[5] = Σu²
+static void ro_apply_scalars(nk_solver *S, const double *v) {
+  S->fnorm_inf = v[0];
+  S->fnorm2 = sqrt(v[1]);
+  S->ro_u_ss = v[5];
+}
+static int lb_step(nk_solver *S, int recompute) {
+  NK_REQUIRE(recompute != 0, "LimitedMemoryBroyden: recompute_jacobian = false (a step without the update) is not offered");
+  bool stop;
+  if (ro_reinit(S, recompute, nullptr, &stop)) {
+    if (stop) return NK_OK;
+    if (S->nsteps > 0) NK_TRY(nk_lb_restart(S->lb));   // (a new solve has restarted it already)
+    S->ro_a = ro_scaling(S, S->fnorm2, S->ro_u_ss);
+  }
+  // δu = −J⁻¹ fu, u += δu
+  double *un = spare_u(S);
+  NK_TRY(nk_lb_direction(S->lb, S->ro_a, S->fu, S->u, un));
+  const double *fprev;
+  NK_TRY(ro_take_step(S, un, &fprev));
+  // one pass over U and V: the update's coefficients, and everything the host reads for this step
+  NK_TRY(nk_lb_reduce(S->lb, S->fu, S->ro_ref, S->ro_tol));
+  double v[6];
+  NK_TRY(nk_scalars_to_host(S->ctx, nk_lb_scalars(S->lb), 6, v));
+  ro_apply_scalars(S, v);
+  const double step_norm = sqrt(v[2]);
+  S->ro_flag_du = v[3] != 0.0;
+  S->ro_flag_dfu = v[4] != 0.0;
+  NK_TRY(check_and_update(S, step_norm));
+  push_trace(S, step_norm);
+  if (S->force_stop) return NK_OK;
+  // GoodBroydenUpdateRule: the second pass over U and V writes the new column pair
+  return nk_lb_combine(S->lb, S->ro_a, S->fu);
+}
+
+// ---- Broyden and Klement (lib/NonlinearSolveQuasiNewton/src/solve.jl:296-486 on a dense or diagonal J⁻¹, or Klement's diagonal J).
+// Klement's reset test is the zero flag its fused launch left.
 static int qn_step(nk_solver *S, int recompute) {
-  nk_ctx *ctx = S->ctx;
   nk_qn *W = S->qn;
   const bool klement = is_klement(S);
   const int rule = S->o.broyden_update_rule;
   const bool dense = !klement && rule != NK_BROYDEN_DIAGONAL;
   NK_REQUIRE(recompute != 0, "%s: recompute_jacobian = false (a step without the update) is not offered", klement ? "Klement" : "Broyden");
-  bool reinit = true;
-  if (S->nsteps > 0) {
-    if (recompute < 0) {  // the standard step: the reset test decides, and its resets count
-      reinit = klement ? S->qn_flag_zero : lb_reset_test(S);
-      if (reinit && ++S->lb_nresets >= S->lb_max_resets) {
-        S->retcode = NK_RET_CONVERGENCE_FAILURE;
-        S->force_stop = true;
-        return NK_OK;
-      }
-    }
-  }
+  bool stop;
+  const bool reinit = ro_reinit(S, recompute, klement ? &S->qn_flag_zero : nullptr, &stop);
+  if (stop) return NK_OK;
   double *un = nullptr;
   double next_ss = -1.0;   // ‖δu‖² of this step where a fused launch has left it already
   if (reinit) {
     S->qn_since_reset = S->nsteps == 0 ? 1 : 0;
     un = spare_u(S);
     if (klement) {         // J = α·1, δu = −(fu ./ J)
-      S->lb_a = qn_alpha(S->o.qn_alpha, S->fnorm2, S->lb_u_ss);
-      NK_TRY(nk_qn_direction(W, 3, 1, S->lb_a, S->lb_tol, S->fu, S->u, un));
+      S->ro_a = qn_alpha(S->o.qn_alpha, S->fnorm2, S->ro_u_ss);
+      NK_TRY(nk_qn_direction(W, 3, 1, S->ro_a, S->ro_tol, S->fu, S->u, un));
     } else {               // J⁻¹ = I/α
-      S->lb_a = lb_scaling(S, S->fnorm2, S->lb_u_ss);
+      S->ro_a = ro_scaling(S, S->fnorm2, S->ro_u_ss);
       if (dense) {
-        NK_TRY(nk_qn_fill(W, S->lb_a));
-        NK_TRY(nk_qn_direction(W, 0, 0, S->lb_a, S->lb_tol, S->fu, S->u, un));
+        NK_TRY(nk_qn_fill(W, S->ro_a));
+        NK_TRY(nk_qn_direction(W, 0, 0, S->ro_a, S->ro_tol, S->fu, S->u, un));
       } else {
-        NK_TRY(nk_qn_direction(W, 2, 1, S->lb_a, S->lb_tol, S->fu, S->u, un));
+        NK_TRY(nk_qn_direction(W, 2, 1, S->ro_a, S->ro_tol, S->fu, S->u, un));
       }
     }
   } else {
@@ -694,44 +688,33 @@ static int qn_step(nk_solver *S, int recompute) {
       NK_REQUIRE(un && un != S->best_u, "Klement: the prepared iterate is gone");
     } else {
       un = spare_u(S);
-      NK_TRY(nk_qn_direction(W, dense ? 1 : 2, 0, S->lb_a, S->lb_tol, S->fu, S->u, un));
+      NK_TRY(nk_qn_direction(W, dense ? 1 : 2, 0, S->ro_a, S->ro_tol, S->fu, S->u, un));
     }
   }
   S->qn_next = nullptr;
-  S->u = un;
-  S->u_version++;
-  nk_problem_invalidate(S->P);
-  double *fnew = nullptr;
-  for (double *b : S->lb_fupool)
-    if (b != S->fu && b != S->lb_ref) { fnew = b; break; }
-  NK_TRY(nk_problem_residual_dev(S->P, S->u, fnew));
-  S->stats.nf++;
-  const double *fprev = S->fu;
-  if (S->lb_ref == nullptr) S->lb_ref = fprev;
-  S->fu = fnew;
+  const double *fprev;
+  NK_TRY(ro_take_step(S, un, &fprev));
   double v[11];
   double step_norm;
   if (klement) {
     double *nxt = spare_u(S);
     NK_TRY(nk_qn_klement_step(W, S->fu, fprev, S->u, nxt));
-    NK_TRY(nk_scalars_to_host(ctx, nk_qn_scalars(W), 11, v));
-    S->lb_ref = S->fu;     // (Klement's reset test keeps no residual: the pool needs two buffers only)
+    NK_TRY(nk_scalars_to_host(S->ctx, nk_qn_scalars(W), 11, v));
+    S->ro_ref = S->fu;     // (Klement's reset test keeps no residual: the pool needs two buffers only)
     S->qn_flag_zero = v[9] != 0.0;
     S->qn_next = nxt;
     S->qn_next_ss = v[10];
     step_norm = sqrt(next_ss >= 0.0 ? next_ss : v[2]);
   } else {
-    NK_TRY(nk_qn_reduce(W, S->fu, fprev, S->lb_ref, S->lb_tol));
-    NK_TRY(nk_scalars_to_host(ctx, nk_qn_scalars(W), 6, v));
+    NK_TRY(nk_qn_reduce(W, S->fu, fprev, S->ro_ref, S->ro_tol));
+    NK_TRY(nk_scalars_to_host(S->ctx, nk_qn_scalars(W), 6, v));
     step_norm = sqrt(v[2]);
-    S->lb_flag_du = v[3] != 0.0;
-    S->lb_flag_dfu = v[4] != 0.0;
+    S->ro_flag_du = v[3] != 0.0;
+    S->ro_flag_dfu = v[4] != 0.0;
   }
-  S->fnorm_inf = v[0];
-  S->fnorm2 = sqrt(v[1]);
-  S->lb_u_ss = v[5];
+  ro_apply_scalars(S, v);
   NK_TRY(check_and_update(S, step_norm));
-  qn_trace(S, step_norm);
+  push_trace(S, step_norm);
   if (S->force_stop || klement) return NK_OK;
   return nk_qn_update(W, S->fu);
 }
@@ -820,18 +803,7 @@ static int sane_step(nk_solver *S) {
   S->sane_sigma = sane_bounded(S, ((c * c) * ss_prev) / (c * v[2]), v[0]);
   S->sane_hist[(k - 1) % S->sane_M] = fnew;      // history[mod1(k, M)]
   NK_TRY(check_and_update(S, step_norm));
-  if (S->o.store_trace) {
-    nk_trace_entry e;
-    memset(&e, 0, sizeof(e));
-    e.iter = S->nsteps + 1;
-    e.accepted = 1;
-    e.fnorm_inf = S->fnorm_inf;
-    e.step_norm2 = step_norm;
-    e.eta = NAN;
-    e.trust_region = NAN;
-    e.rho = NAN;
-    S->trace.push_back(e);
-  }
+  push_trace(S, step_norm);
   return NK_OK;
 }
 
@@ -879,7 +851,7 @@ static int solver_start(nk_solver *S, bool first = true) {  // everything after 
     if (first) S->pt_applied = 0.0;  // (the Jacobian values were just refilled; after reinit! the first step's refill resets it)
     if (S->G) NK_TRY(nk_gmres_set_shift(S->G, 0.0));
   }
-  if (is_lb(S) || is_qn(S)) NK_TRY(lb_start(S));
+  if (is_lb(S) || is_qn(S)) NK_TRY(ro_start(S));
   if (is_sane(S)) NK_TRY(sane_start(S));
   if (is_lm(S)) {  // init / reinit! of the damping cache, the LM trust region and the geodesic cache
     S->lm_lam = S->o.lm_damping_initial;                    // levenberg_marquardt.jl:72-89,119-131
@@ -1004,19 +976,19 @@ extern "C" int nk_solver_init(nk_problem *P, const double *u0, int memspace, con
   if (is_lb(S)) {
     S->lb_threshold = S->o.lb_threshold > 0 ? S->o.lb_threshold : 10;
     if (S->lb_threshold > S->o.maxiters) S->lb_threshold = S->o.maxiters;   // initialization.jl:180
-    S->lb_max_resets = S->o.lb_max_resets > 0 ? S->o.lb_max_resets : 3;
-    S->lb_tol = S->o.lb_reset_tolerance > 0.0 ? S->o.lb_reset_tolerance : pow(2.220446049250313e-16, 0.75);
+    S->ro_max_resets = S->o.lb_max_resets > 0 ? S->o.lb_max_resets : 3;
+    S->ro_tol = S->o.lb_reset_tolerance > 0.0 ? S->o.lb_reset_tolerance : pow(2.220446049250313e-16, 0.75);
     NK_TRY(nk_lb_create(ctx, n, S->lb_threshold, &S->lb));
-    S->lb_fupool[0] = S->fu;
-    NK_TRY(nk_dev_alloc(&S->lb_fupool[1], na));
-    NK_TRY(nk_dev_alloc(&S->lb_fupool[2], na));
+    S->ro_fupool[0] = S->fu;
+    NK_TRY(nk_dev_alloc(&S->ro_fupool[1], na));
+    NK_TRY(nk_dev_alloc(&S->ro_fupool[2], na));
   } else if (is_qn(S)) {
-    S->lb_max_resets = S->o.qn_max_resets > 0 ? S->o.qn_max_resets : 100;
-    S->lb_tol = S->o.qn_reset_tolerance > 0.0 ? S->o.qn_reset_tolerance : pow(2.220446049250313e-16, 0.75);
+    S->ro_max_resets = S->o.qn_max_resets > 0 ? S->o.qn_max_resets : 100;
+    S->ro_tol = S->o.qn_reset_tolerance > 0.0 ? S->o.qn_reset_tolerance : pow(2.220446049250313e-16, 0.75);
     NK_TRY(nk_qn_create(ctx, n, is_klement(S) ? NK_QN_KLEMENT : S->o.broyden_update_rule, &S->qn));
-    S->lb_fupool[0] = S->fu;
-    NK_TRY(nk_dev_alloc(&S->lb_fupool[1], na));
-    NK_TRY(nk_dev_alloc(&S->lb_fupool[2], na));
+    S->ro_fupool[0] = S->fu;
+    NK_TRY(nk_dev_alloc(&S->ro_fupool[1], na));
+    NK_TRY(nk_dev_alloc(&S->ro_fupool[2], na));
   } else if (is_sane(S)) {
     const nk_options &o = S->o;
     S->sane_smin = o.sane_sigma_min > 0.0 ? o.sane_sigma_min : 1.0e-10;
@@ -1054,9 +1026,9 @@ extern "C" int nk_solver_destroy(nk_solver *S) {
   if (!S) return NK_OK;
   hipStreamSynchronize(S->ctx->stream);
   if (S->P) nk_problem_invalidate(S->P);  // the vectors the problem was linearised at are about to be freed
-  if (S->lb_fupool[0]) S->fu = S->lb_fupool[0];   // (fu rotates through the pool)
-  hipFree(S->lb_fupool[1]);
-  hipFree(S->lb_fupool[2]);
+  if (S->ro_fupool[0]) S->fu = S->ro_fupool[0];   // (fu rotates through the pool)
+  hipFree(S->ro_fupool[1]);
+  hipFree(S->ro_fupool[2]);
   nk_lb_destroy(S->lb);
   nk_qn_destroy(S->qn);
   nk_sane_destroy(S->sane);
@@ -1964,21 +1936,21 @@ extern "C" int nk_solver_get_lbroyden_state(nk_solver *S, int *nresets, int *idx
                                             int *since_dfu) {
   NK_REQUIRE(S, "NULL argument");
   NK_REQUIRE(is_lb(S), "not a LimitedMemoryBroyden cache");
-  if (nresets) *nresets = S->lb_nresets;
+  if (nresets) *nresets = S->ro_nresets;
   if (idx) *idx = nk_lb_index(S->lb);
-  if (a) *a = S->lb_a;
+  if (a) *a = S->ro_a;
   if (threshold) *threshold = S->lb_threshold;
-  if (since_du) *since_du = S->lb_since_du;
-  if (since_dfu) *since_dfu = S->lb_since_dfu;
+  if (since_du) *since_du = S->ro_since_du;
+  if (since_dfu) *since_dfu = S->ro_since_dfu;
   return NK_OK;
 }
 extern "C" int nk_solver_get_qn_state(nk_solver *S, int *nresets, double *a, int *since_du, int *since_dfu, int *steps_since_reset) {
   NK_REQUIRE(S, "NULL solver");
   NK_REQUIRE(is_qn(S), "neither a Broyden nor a Klement cache");
-  if (nresets) *nresets = S->lb_nresets;
-  if (a) *a = S->lb_a;
-  if (since_du) *since_du = S->lb_since_du;
-  if (since_dfu) *since_dfu = S->lb_since_dfu;
+  if (nresets) *nresets = S->ro_nresets;
+  if (a) *a = S->ro_a;
+  if (since_du) *since_du = S->ro_since_du;
+  if (since_dfu) *since_dfu = S->ro_since_dfu;
   if (steps_since_reset) *steps_since_reset = S->qn_since_reset;
   return NK_OK;
 }

@@ -32,6 +32,7 @@ double; abstol = eps^(4/5):
     broyden1000_bad              13  Success             —            8.40e-16    2.26e-15      1.47e-14      4.54e-14
     broyden1000_diagonal          9  Success             9            1.94e-16    6.83e-16      4.36e-15      1.95e-14
     broyden2049_good             13  Success             —            1.10e-15    3.00e-15      1.89e-14      5.73e-14
+    broyden4099_diagonal          8  Success             —            1.90e-16    6.56e-16      4.29e-15      1.91e-14
     broyden64_alpha               7  Success             —            1.83e-16    5.35e-16      4.19e-15      1.72e-14
     broyden64_small_fu            2  Success             —            2.17e-16    7.24e-16      4.74e-15      2.02e-14
     broyden130_nonsym             4  (stopped)           —            3.45e-15    9.79e-15      5.66e-14      1.67e-13
@@ -40,6 +41,7 @@ double; abstol = eps^(4/5):
     klement64                     7  Success             —            2.48e-16    9.05e-16      5.48e-15      2.56e-14
     klement65                     7  Success             —            2.80e-16    9.32e-16      5.98e-15      2.60e-14
     klement1000                   7  Success             —            3.60e-16    1.37e-15      7.27e-15      3.31e-14
+    klement4099                   7  Success             —            3.40e-16    1.31e-15      6.94e-15      3.21e-14
     klement64_alpha               6  Success             —            1.75e-16    5.27e-16      4.06e-15      1.71e-14
     klement_reset64               4  ConvergenceFailure  2, 3, 4      0.00e+00    0.00e+00      1.78e-15      1.42e-14
 
@@ -182,6 +184,7 @@ CASES = {
     "broyden1000_bad": (quadratic(2.0), _lin(1000), dict(update_rule="bad_broyden"), None),
     "broyden1000_diagonal": (quadratic(2.0), _lin(1000, 1.2), dict(update_rule="diagonal", alpha=2.8), None),
     "broyden2049_good": (quadratic(2.0), _lin(2049), dict(), None),
+    "broyden4099_diagonal": (quadratic(2.0), _lin(4099, 1.2), dict(update_rule="diagonal", alpha=2.8), None),   # 5 workgroups
     "broyden64_alpha": (quadratic(2.0), _lin(64, 1.5), dict(alpha=2.5), None),
     "broyden64_small_fu": (quadratic(2.0), np.sqrt(2.0) + 1.0e-7 * _lin(64, 2.0), dict(), None),   # ‖fu‖₂ < 1e-5: α = 1
     "broyden130_nonsym": (coupled(2.0, 0.1), _lin(130, 1.5), dict(), 4),
@@ -190,6 +193,7 @@ CASES = {
     "klement64": (quadratic(2.0), _lin(64, 1.2), dict(method="klement"), None),
     "klement65": (quadratic(2.0), _lin(65, 1.2), dict(method="klement"), None),
     "klement1000": (quadratic(2.0), _lin(1000, 1.2), dict(method="klement"), None),
+    "klement4099": (quadratic(2.0), _lin(4099, 1.2), dict(method="klement"), None),   # 5 workgroups in every vector kernel
     "klement64_alpha": (quadratic(2.0), _lin(64, 1.2), dict(method="klement", alpha=2.8), None),
     "klement_reset64": (klement_stall(2.0), np.ones(64), dict(method="klement", alpha=1.0, max_resets=3), None),
 }

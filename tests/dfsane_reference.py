@@ -244,6 +244,7 @@ CASES = {
     # (34 steps to Success; by step 10 the trajectory has amplified a rounding by 10⁵ and by step 26 by 10⁹: six steps — with
     #  both minus-side acceptances — are compared on the device, the whole solve's decisions are checked here)
     "quadratic1000_spread": (quadratic(2.0), spread_start(1000), dict(), 6),
+    "quadratic4099_spread": (quadratic(2.0), spread_start(4099), dict(), 6),   # 5 workgroups, an odd tail; six steps likewise
     "bratu16_g2": (bratu(16, 6.0), np.zeros(256), dict(gamma=2.0, tau_min=0.3), 12),   # (first steps only: twelve are compared)
     "quadratic1": (quadratic(2.0), np.ones(1), dict(), None),
     "quadratic2": (quadratic(2.0), np.ones(2), dict(), None),

@@ -40,6 +40,7 @@ table holds the maximum over the steps of each case, measured with x87 long doub
     quadratic64_t10            1.10e-16    2.63e-16      3.02e-15      1.28e-14
     quadratic64_t3             1.51e-16    4.49e-16      3.67e-15      1.58e-14
     quadratic1000_spread       5.23e-16    1.45e-15      9.71e-15      3.17e-14
+    quadratic4099_spread       6.30e-16    1.44e-15      1.14e-14      3.22e-14
     bratu16_t10                7.41e-15    3.62e-14      1.20e-13      6.04e-13
     quadratic64_alpha_t1       1.32e-16    3.80e-16      3.37e-15      1.47e-14
     quadratic64_clamped        1.17e-16    3.54e-16      3.13e-15      1.42e-14
@@ -271,6 +272,7 @@ CASES = {
     "quadratic64_t10": (quadratic(2.0), np.ones(64), dict(threshold=10), None),
     "quadratic64_t3": (quadratic(2.0), np.ones(64), dict(threshold=3), None),
     "quadratic1000_spread": (quadratic(2.0), spread_start(1000), dict(threshold=10), None),
+    "quadratic4099_spread": (quadratic(2.0), spread_start(4099), dict(threshold=10), None),   # 5 workgroups, an odd tail
     "bratu16_t10": (bratu(16, 6.0), np.zeros(256), dict(threshold=10), 6),     # (diverges later: six steps are compared)
     "quadratic64_alpha_t1": (quadratic(2.0), np.ones(64), dict(threshold=1, alpha=2.5), None),
     "quadratic64_clamped": (quadratic(2.0), np.ones(64), dict(threshold=32, alpha=2.5, maxiters=4), None),

@@ -29,6 +29,7 @@ def test_the_python_class_and_the_enum_exist():
 def test_case_list():
     assert sorted(R.CASES) == sorted([
         "quadratic64", "quadratic64_M3", "quadratic64_nexp1", "quadratic64_sigma1", "quadratic64_smin", "quadratic1000_spread",
+        "quadratic4099_spread",
         "bratu16_g2", "quadratic1", "quadratic2", "quadratic63", "quadratic257", "quadratic65539", "quadratic262145",
         "root_domain_nan"])
 

@@ -11,9 +11,10 @@ pytestmark = pytest.mark.gpu
 
 
 @pytest.mark.parametrize("name", ["broyden64_good", "broyden64_bad", "broyden64_diagonal", "broyden65_good", "broyden1000_good",
-                                  "broyden1000_bad", "broyden1000_diagonal", "broyden64_alpha", "broyden64_small_fu"])
+                                  "broyden1000_bad", "broyden1000_diagonal", "broyden4099_diagonal", "broyden64_alpha", "broyden64_small_fu"])
 def test_parity_every_step(nls, dev, name):
-    """n = 64: two row tiles; 65: the odd column tail and the padded ld; 1000: no multiple of wave, workgroup or tile"""
+    """n = 64: two row tiles; 65: the odd column tail and the padded ld; 1000: no multiple of wave, workgroup or tile;
+    4099: five workgroups in the vector and reduce kernels"""
     cache, us, fus, resets = D.run(nls, name, dev)
     D.assert_control_flow(name, cache, resets)
     D.assert_parity(name, us, fus)

@@ -60,7 +60,7 @@ def _assert_parity(name, us, fus, states):
         assert st["total_trials"] == total and st["M"] == len(ref.histories[k - 1])
 
 
-SMALL = ["quadratic1", "quadratic2", "quadratic63", "quadratic257", "quadratic1000_spread"]
+SMALL = ["quadratic1", "quadratic2", "quadratic63", "quadratic257", "quadratic1000_spread", "quadratic4099_spread"]
 OPTIONS = ["quadratic64", "quadratic64_M3", "quadratic64_nexp1", "quadratic64_sigma1", "quadratic64_smin", "bratu16_g2"]
 
 

@@ -9,7 +9,7 @@ import qn_device_cases as D
 pytestmark = pytest.mark.gpu
 
 
-@pytest.mark.parametrize("name", ["klement64", "klement65", "klement1000", "klement64_alpha"])
+@pytest.mark.parametrize("name", ["klement64", "klement65", "klement1000", "klement4099", "klement64_alpha"])
 def test_parity_every_step(nls, dev, name):
     cache, us, fus, resets = D.run(nls, name, dev)
     D.assert_control_flow(name, cache, resets)

@@ -71,8 +71,7 @@ def test_quadratic_parity_every_step(nls, dev, name):
     cache.close()
 
 
-def test_spread_start_resets_where_the_restatement_does(nls, dev):
-    name = "quadratic1000_spread"   # n = 1000: no multiple of the wave or the workgroup
+def _assert_spread_start(nls, dev, name):
     cache, us, fus, resets = _run(nls, name, dev)
     ref = R.run(name)
     assert ref.reset_steps == [14] and ref.nsteps == 15
@@ -80,6 +79,14 @@ def test_spread_start_resets_where_the_restatement_does(nls, dev):
     assert _reset_steps(resets) == ref.reset_steps
     _assert_parity(name, us, fus)
     cache.close()
+
+
+def test_spread_start_resets_where_the_restatement_does(nls, dev):
+    _assert_spread_start(nls, dev, "quadratic1000_spread")   # n = 1000: no multiple of the wave or the workgroup
+
+
+def test_spread_start_at_five_workgroups(nls, dev):
+    _assert_spread_start(nls, dev, "quadratic4099_spread")   # five workgroups in every kernel, an odd tail, the reset step included
 
 
 @pytest.mark.parametrize("name", ["quadratic65539", "quadratic262145"])

@@ -23,6 +23,7 @@ def test_the_python_class_and_the_enum_exist():
     ("quadratic64_t10", 6, [], [0, 1, 2, 3, 4]),
     ("quadratic64_t3", 11, [], [0, 1, 2, 0, 1, 2, 0, 1, 2, 0]),          # the column index wraps
     ("quadratic1000_spread", 15, [14], list(range(10)) + [0, 1, 2, 0]),   # wraps, then restarts at column 0 after the reset
+    ("quadratic4099_spread", 15, [14], list(range(10)) + [0, 1, 2, 0]),   # the same at five workgroups
 ])
 def test_quadratic_step_counts_and_reset_steps(name, steps, resets, cols):
     r = R.run(name)
