@@ -484,6 +484,47 @@ int nk_jac_values(nk_problem *P, const double *u, int memspace, nk_csr *J);
  * DI.jacobian! with AutoSparse (jacobian.jl:244-247; colouring ext/...SparseMatrixColoringsExt.jl:13-28) */
 int nk_jac_values_colored(nk_problem *P, const double *u, int memspace, nk_csr *J, int *ncolors);
 
+/* ---------------------------------------------------------------- compiled grid problems (kernel generation, full size)
+ * A residual given pointwise on a 2-D grid through a radius-1 stencil: what the reference's user writes as `f` and lets
+ * SciMLJacobianOperators differentiate with forward-mode duals (J·v) and sparse AD fill into `jac_prototype`. `source` is HIP C++
+ * defining
+ *     template <typename T> __device__ void nk_point(const nk_nbhd<T> &u, const nk_real *p, nk_site s, T *f);
+ * with  u(di, dj, c = 0)  component c at node (i + di, j + dj), di, dj ∈ {−1, 0, 1} (write them as constants). With
+ *                         NK_GRID_STAR a corner read (di != 0 && dj != 0) returns NaN, so a source written for the box shows
+ *                         at the first residual;
+ *       s                 {i, j, nx, ny}: the node and the grid;
+ *       p                 nparams doubles, 0..32 (nk_problem_set_params replaces them);
+ *       f                 receives the node's dof residuals (entries the source does not write are zero);
+ *       nk_real           double — there is no Float32 mode.
+ * It is compiled at run time (hiprtc, gfx950, -O3 -ffp-contract=off -std=c++17) behind the dual-number prelude of the ensemble
+ * kernels (the same operators and elementary functions as for nk_f) into three kernels, one grid node per thread: the residual
+ * (T = double), the exact J·v (T = a dual with one partial: value from u, partial from v) and the values of J on the stencil's
+ * CSR pattern (a dual with npts·dof partials, unit seeds). No finite differences anywhere.
+ * Geometry: nx × ny nodes, nx, ny >= 3 (not necessarily square); dof = 1..4 components per node; stencil NK_GRID_STAR (5 points)
+ * or NK_GRID_BOX (9 points, dof <= 2: a row has at most 20 partials); boundary NK_GRID_DIRICHLET0 (a neighbour outside the grid
+ * reads as the constant 0 and has no column) or NK_GRID_PERIODIC (indices wrap in both directions). Unknown c of node (i, j) is
+ * element c·nx·ny + j·nx + i (the Brusselator's layout). Radius 1 only; one rank only: NK_E_UNSUPPORTED on a context with more.
+ * The object is an nk_problem of kind NK_PROBLEM_USER whose callbacks launch the generated kernels: every algorithm, linear
+ * solver and preconditioner object takes it as it takes any callback problem — so the matrix-free GMRES keeps the callback
+ * kind's two reductions per Arnoldi step and unfused output scale, and Jᵀv (TrustRegion, normal forms) is the filled Jacobian's
+ * transposed SpMV. nk_problem_destroy frees the problem, its modules and its pattern; nk_problem_jac_csr returns the pattern
+ * the problem owns (do not destroy it); nk_problem_initial_guess gives zeros.
+ * A source that does not compile is NK_E_INVALID with the contract and the compiler's log in nk_last_error. */
+enum { NK_GRID_STAR = 0, NK_GRID_BOX = 1 };           /* stencil  */
+enum { NK_GRID_DIRICHLET0 = 0, NK_GRID_PERIODIC = 1 }; /* boundary */
+/* The CSR pattern of the Jacobian (host only, no device needed): rowptr dof·nx·ny + 1 entries, colind *nnz entries, 0-based,
+ * columns ascending within a row. Every (stencil point in the domain) × (component) entry is kept — structural even where a
+ * derivative is zero. colind = NULL (and / or rowptr = NULL) asks for the sizes only. */
+int nk_grid_pattern(int64_t nx, int64_t ny, int dof, int stencil, int boundary, int32_t *rowptr, int32_t *colind, int64_t *nnz);
+/* compile only (no device needed); *code_bytes = size of the two code objects together */
+int nk_grid_compile_check(const char *source, int dof, int stencil, int boundary, int nparams, int64_t *code_bytes);
+/* the code object of one of the two programs, for inspection (jac = 0: nk_grid_residual and nk_grid_jvp; 1: nk_grid_jac);
+ * buf = NULL asks for the size only; no device needed */
+int nk_grid_code_object(const char *source, int dof, int stencil, int boundary, int nparams, int jac, void *buf,
+                        int64_t capacity, int64_t *bytes);
+int nk_problem_create_grid(nk_ctx *ctx, const char *source, int64_t nx, int64_t ny, int dof, int stencil, int boundary,
+                           const double *params, int nparams, nk_problem **out);
+
 /* ---------------------------------------------------------------- GMRES (seam 1) */
 int nk_gmres_create(nk_ctx *ctx, int64_t n_local, int restart_m, int ortho, nk_gmres **out);
 int nk_gmres_destroy(nk_gmres *G);

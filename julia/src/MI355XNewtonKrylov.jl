@@ -169,6 +169,47 @@ end
 bratu2d(n; λ = 6.0, scale = 0.0, kw...) = DeviceProblem(2, Float64[n, λ, scale]; kw...)
 brusselator2d(N; A = 3.4, B = 1.0, α = 10.0, dx = 1 / (N - 1), kw...) = DeviceProblem(3, Float64[N, A, B, α, dx]; kw...)
 
+
+const GRID_STENCILS = Dict(:star => 0, :box => 1)
+const GRID_BOUNDARIES = Dict(:dirichlet => 0, :periodic => 1)
+"""`CompiledGridProblem(source, nx, ny; dof = 1, stencil = :star, boundary = :dirichlet, params = Float64[])`: a residual given
+pointwise on an nx × ny grid through a radius-1 stencil as HIP source
+`template <typename T> __device__ void nk_point(const nk_nbhd<T> &u, const nk_real *p, nk_site s, T *f)`; the library compiles
+the residual kernel, the exact dual-number JVP kernel and the Jacobian fill from it (nk_problem_create_grid). One rank, Float64,
+dof ≤ 4 (box: ≤ 2), at most 32 parameters."""
+function CompiledGridProblem(source::AbstractString, nx::Integer, ny::Integer; dof::Integer = 1, stencil::Symbol = :star,
+                             boundary::Symbol = :dirichlet, params::Vector{Float64} = Float64[], ctx = default_ctx())
+    out = Ref{Ptr{Cvoid}}(C_NULL)
+    par = isempty(params) ? Float64[0.0] : params
+    GC.@preserve par nkcheck(@ccall libnk.nk_problem_create_grid(ctx.ptr::Ptr{Cvoid}, String(source)::Cstring, Int64(nx)::Int64,
+        Int64(ny)::Int64, dof::Cint, GRID_STENCILS[stencil]::Cint, GRID_BOUNDARIES[boundary]::Cint, par::Ptr{Float64},
+        length(params)::Cint, out::Ptr{Ptr{Cvoid}})::Cint)
+    nl = Ref{Int64}(0)
+    nkcheck(@ccall libnk.nk_problem_size(out[]::Ptr{Cvoid}, nl::Ptr{Int64}, C_NULL::Ptr{Int64}, C_NULL::Ptr{Int64})::Cint)
+    p = DeviceProblem(out[], nl[])
+    finalizer(x -> @ccall(libnk.nk_problem_destroy(x.ptr::Ptr{Cvoid})::Cint), p)
+    return p
+end
+"""`grid_pattern(nx, ny; dof, stencil, boundary)` → `(rowptr, colind)`, 0-based `Int32`: the CSR pattern of that Jacobian (host only)."""
+function grid_pattern(nx::Integer, ny::Integer; dof::Integer = 1, stencil::Symbol = :star, boundary::Symbol = :dirichlet)
+    nnz = Ref{Int64}(0)
+    st, bd = GRID_STENCILS[stencil], GRID_BOUNDARIES[boundary]
+    nkcheck(@ccall libnk.nk_grid_pattern(Int64(nx)::Int64, Int64(ny)::Int64, dof::Cint, st::Cint, bd::Cint, C_NULL::Ptr{Int32},
+        C_NULL::Ptr{Int32}, nnz::Ptr{Int64})::Cint)
+    rowptr, colind = Vector{Int32}(undef, dof * nx * ny + 1), Vector{Int32}(undef, nnz[])
+    nkcheck(@ccall libnk.nk_grid_pattern(Int64(nx)::Int64, Int64(ny)::Int64, dof::Cint, st::Cint, bd::Cint, rowptr::Ptr{Int32},
+        colind::Ptr{Int32}, nnz::Ptr{Int64})::Cint)
+    return rowptr, colind
+end
+"""`grid_compile_check(source; dof, stencil, boundary, nparams)`: compile the three kernels for gfx950 (no device needed); bytes of code."""
+function grid_compile_check(source::AbstractString; dof::Integer = 1, stencil::Symbol = :star, boundary::Symbol = :dirichlet,
+                            nparams::Integer = 0)
+    nb = Ref{Int64}(0)
+    nkcheck(@ccall libnk.nk_grid_compile_check(String(source)::Cstring, dof::Cint, GRID_STENCILS[stencil]::Cint,
+        GRID_BOUNDARIES[boundary]::Cint, nparams::Cint, nb::Ptr{Int64})::Cint)
+    return nb[]
+end
+
 # ------------------------------------------------------------------ preconditioner objects (what `precs(A, p)` may return)
 """`DeviceILU0(A::DeviceCSR; ordering = :multicolor)` / `DeviceJacobi(A)` / `DeviceILUT(A; τ)` / `DeviceAMG(A; …)`: nk_precond objects — usable as `Pl` or `Pr` of
 `MI355XGMRES` without a host round trip per application, and as `ldiv!(y, P, x)` on host or resident vectors."""
@@ -768,7 +809,7 @@ end
 # point with memspace = NK_DEVICE, and device-resident Julia operators / preconditioners serve through the device-pointer
 # callback contract (nk_matvec_fn proper).
 
-export Ctx, DeviceVector, DeviceCSR, DeviceProblem, bratu2d, brusselator2d, mi355x_function, MI355XGMRES,
+export Ctx, DeviceVector, DeviceCSR, DeviceProblem, bratu2d, brusselator2d, CompiledGridProblem, grid_pattern, grid_compile_check, mi355x_function, MI355XGMRES,
     MI355XNewtonKrylovAlg, EnsembleKernel, LeastSquaresEnsembleKernel, SimpleGaussNewton, vectorized_solve, DevicePreconditioner, DeviceILU0, DeviceILUT, DeviceAMG, DeviceJacobi, update!, update_values!
 
 end # module

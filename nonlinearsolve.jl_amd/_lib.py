@@ -18,6 +18,8 @@ class NKError(RuntimeError):
 # ---------------------------------------------------------------------------- enums (mirror the header)
 HOST, DEVICE = 0, 1
 BATCH_ANALYTIC_JAC, BATCH_FLOAT32 = 1, 2   # nk_batch_create / nk_batch_compile_check flags
+GRID_STENCILS = {"star": 0, "box": 1}               # nk_problem_create_grid / nk_grid_pattern
+GRID_BOUNDARIES = {"dirichlet": 0, "periodic": 1}
 RET_NAMES = ["Default", "Success", "MaxIters", "Unstable", "Stalled", "InternalLinearSolveFailed",
              "ShrinkThresholdExceeded", "MaxTime", "Failure", "InternalLineSearchFailed", "ConvergenceFailure"]
 PROBLEM_QUADRATIC, PROBLEM_BRATU2D, PROBLEM_BRUSSELATOR2D, PROBLEM_USER = 1, 2, 3, 100
@@ -182,6 +184,10 @@ SIGNATURES = {
     "nk_problem_jac_csr": (_I, [_P, _PP]),
     "nk_jac_values": (_I, [_P, _P, _I, _P]),
     "nk_jac_values_colored": (_I, [_P, _P, _I, _P, C.POINTER(_I)]),
+    "nk_grid_pattern": (_I, [_L, _L, _I, _I, _I, _P, _P, C.POINTER(_L)]),
+    "nk_grid_compile_check": (_I, [C.c_char_p, _I, _I, _I, _I, C.POINTER(_L)]),
+    "nk_grid_code_object": (_I, [C.c_char_p, _I, _I, _I, _I, _I, _P, _L, C.POINTER(_L)]),
+    "nk_problem_create_grid": (_I, [_P, C.c_char_p, _L, _L, _I, _I, _I, C.POINTER(_D), _I, _PP]),
     "nk_gmres_create": (_I, [_P, _L, _I, _I, _PP]),
     "nk_gmres_destroy": (_I, [_P]),
     "nk_gmres_set_operator_csr": (_I, [_P, _P]),

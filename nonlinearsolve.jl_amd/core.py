@@ -478,6 +478,70 @@ def Brusselator2D(N: int, A=3.4, B=1.0, alpha=10.0, dx=None, ctx=None) -> Device
     return P
 
 
+# ------------------------------------------------------------------------------------------- compiled grid problems
+def _grid_ids(stencil, boundary):
+    if stencil not in L.GRID_STENCILS:
+        raise ValueError(f"stencil = {stencil!r}: expected one of {sorted(L.GRID_STENCILS)}")
+    if boundary not in L.GRID_BOUNDARIES:
+        raise ValueError(f"boundary = {boundary!r}: expected one of {sorted(L.GRID_BOUNDARIES)}")
+    return L.GRID_STENCILS[stencil], L.GRID_BOUNDARIES[boundary]
+
+
+def grid_pattern(nx: int, ny: int, dof: int = 1, stencil: str = "star", boundary: str = "dirichlet"):
+    """(rowptr, colind), int32, of the Jacobian of a compiled grid problem: columns ascending within a row, every
+    (stencil point in the domain) × (component) entry kept. Host only."""
+    st, bd = _grid_ids(stencil, boundary)
+    nnz = C.c_int64()
+    check(L.lib().nk_grid_pattern(nx, ny, dof, st, bd, None, None, C.byref(nnz)))
+    rowptr, colind = np.empty(dof * nx * ny + 1, dtype=np.int32), np.empty(nnz.value, dtype=np.int32)
+    check(L.lib().nk_grid_pattern(nx, ny, dof, st, bd, C.c_void_p(rowptr.ctypes.data), C.c_void_p(colind.ctypes.data),
+                                  C.byref(nnz)))
+    return rowptr, colind
+
+
+def grid_compile_check(source: str, dof: int = 1, stencil: str = "star", boundary: str = "dirichlet", nparams: int = 0) -> int:
+    """Compile the residual, JVP and Jacobian kernels of `source` for gfx950 (no device needed); the size of the code objects.
+    A source that does not compile raises NKError with the contract and the compiler's log."""
+    st, bd = _grid_ids(stencil, boundary)
+    nb = C.c_int64()
+    check(L.lib().nk_grid_compile_check(source.encode(), dof, st, bd, nparams, C.byref(nb)))
+    return nb.value
+
+
+class _GridDeviceProblem(DeviceProblem):
+    """the nk_problem of CompiledGridProblem: the Jacobian pattern belongs to the problem, and `p` is the source's whole p"""
+
+    def jac_csr(self) -> CSRMatrix:
+        h = C.c_void_p()
+        check(L.lib().nk_problem_jac_csr(self._h, C.byref(h)))
+        return CSRMatrix(h, self.ctx, owned=False)   # freed with the problem
+
+    def set_p(self, p):
+        p = [float(p)] if isinstance(p, (int, float)) else [float(x) for x in p]
+        if len(p) != len(self.p):
+            raise ValueError(f"the source was compiled for {len(self.p)} parameters, got {len(p)}")
+        self.set_params(p)
+        self.p = p
+
+
+def CompiledGridProblem(source: str, nx: int, ny: int, dof: int = 1, stencil: str = "star", boundary: str = "dirichlet",
+                        params: Sequence[float] = (), ctx=None) -> DeviceProblem:
+    """A residual given pointwise on an nx × ny grid through a radius-1 stencil, as HIP source
+        template <typename T> __device__ void nk_point(const nk_nbhd<T> &u, const nk_real *p, nk_site s, T *f);
+    compiled (hiprtc, gfx950) into the residual kernel, the exact dual-number JVP kernel and the Jacobian fill on the stencil's
+    CSR pattern (include/mi355x_nk.h, "compiled grid problems"). u0 defaults to zeros; NonlinearProblem(..., p) and
+    reinit_(cache, p=...) replace the source's p[0..nparams). dof <= 4 (box: <= 2), Float64, one rank."""
+    ctx = ctx or default_context()
+    st, bd = _grid_ids(stencil, boundary)
+    params = [float(x) for x in params]
+    arr = (C.c_double * max(len(params), 1))(*params)
+    h = C.c_void_p()
+    check(L.lib().nk_problem_create_grid(ctx._h, source.encode(), nx, ny, dof, st, bd, arr, len(params), C.byref(h)))
+    P = _GridDeviceProblem(h, ctx)
+    P.p, P.nx, P.ny, P.dof, P.stencil, P.boundary = params, nx, ny, dof, stencil, boundary
+    return P
+
+
 @dataclass
 class NonlinearFunction:
     """NonlinearFunction{true}(f!; jvp, vjp, jac, jac_prototype) with torch-tensor callbacks on the device:
@@ -560,7 +624,9 @@ class NonlinearProblem:
     def set_p(self, p):
         self.p = p
         dp = self.device_problem
-        if hasattr(dp, "params"):
+        if isinstance(dp, _GridDeviceProblem):   # a compiled grid problem: p is the source's p[0..nparams)
+            dp.set_p(p)
+        elif hasattr(dp, "params"):
             params = list(dp.params)
             if isinstance(p, (int, float)):
                 params[1] = float(p)           # quadratic p / Bratu λ

@@ -10,7 +10,6 @@
 // δx = J \ fx, x −= δx, THEN the termination check on the residual of the previous iterate (`check_termination` precedes
 // `evaluate_f!!`), default mode AbsNormTerminationMode(maximum∘abs) (termination_conditions.jl:376-380), default abstol
 // eps^(4/5) (common_defaults.jl:39-48), maxiters 1000; retcodes Success / MaxIters; a NaN residual never terminates.
-#include <dlfcn.h>
 #include <math.h>
 #include <stdlib.h>
 #include <string.h>
@@ -21,68 +20,6 @@
 #include "nk_internal.h"
 
 // ----------------------------------------------------------------------------- device source (compiled by hiprtc)
-static const char *k_prelude = R"NKSRC(
-// ---- the working precision: -DNK_F32 builds every solver kernel in single precision (flags & NK_BATCH_FLOAT32)
-#ifdef NK_F32
-typedef float nk_real;
-#else
-typedef double nk_real;
-#endif
-#define NK_R(x) ((nk_real)(x))
-// ---- forward-mode dual numbers with NK_CH partials (ForwardDiff.Dual analogue)
-struct Dual {
-  nk_real v;
-  nk_real d[NK_CH];
-  __device__ Dual() {}
-  __device__ Dual(nk_real x) : v(x) {
-#pragma unroll
-    for (int k = 0; k < NK_CH; ++k) d[k] = NK_R(0);
-  }
-};
-#define NK_DUAL_LOOP _Pragma("unroll") for (int k = 0; k < NK_CH; ++k)
-__device__ inline Dual operator+(const Dual &a, const Dual &b) { Dual r; r.v = a.v + b.v; NK_DUAL_LOOP r.d[k] = a.d[k] + b.d[k]; return r; }
-__device__ inline Dual operator-(const Dual &a, const Dual &b) { Dual r; r.v = a.v - b.v; NK_DUAL_LOOP r.d[k] = a.d[k] - b.d[k]; return r; }
-__device__ inline Dual operator-(const Dual &a) { Dual r; r.v = -a.v; NK_DUAL_LOOP r.d[k] = -a.d[k]; return r; }
-__device__ inline Dual operator*(const Dual &a, const Dual &b) { Dual r; r.v = a.v * b.v; NK_DUAL_LOOP r.d[k] = a.d[k] * b.v + a.v * b.d[k]; return r; }
-__device__ inline Dual operator/(const Dual &a, const Dual &b) {
-  Dual r; const nk_real ib = NK_R(1) / b.v; r.v = a.v * ib;
-  NK_DUAL_LOOP r.d[k] = (a.d[k] - r.v * b.d[k]) * ib;
-  return r;
-}
-// scalar operands are taken in nk_real, so that `0.05 * u[i]` stays in the working precision on the dual path
-__device__ inline Dual operator+(const Dual &a, nk_real b) { Dual r = a; r.v += b; return r; }
-__device__ inline Dual operator+(nk_real b, const Dual &a) { Dual r = a; r.v += b; return r; }
-__device__ inline Dual operator-(const Dual &a, nk_real b) { Dual r = a; r.v -= b; return r; }
-__device__ inline Dual operator-(nk_real b, const Dual &a) { Dual r = -a; r.v += b; return r; }
-__device__ inline Dual operator*(const Dual &a, nk_real b) { Dual r; r.v = a.v * b; NK_DUAL_LOOP r.d[k] = a.d[k] * b; return r; }
-__device__ inline Dual operator*(nk_real b, const Dual &a) { return a * b; }
-__device__ inline Dual operator/(const Dual &a, nk_real b) { return a * (NK_R(1) / b); }
-__device__ inline Dual operator/(nk_real b, const Dual &a) { return Dual(b) / a; }
-__device__ inline Dual &operator+=(Dual &a, const Dual &b) { a = a + b; return a; }
-__device__ inline Dual &operator-=(Dual &a, const Dual &b) { a = a - b; return a; }
-__device__ inline Dual &operator*=(Dual &a, const Dual &b) { a = a * b; return a; }
-__device__ inline Dual &operator/=(Dual &a, const Dual &b) { a = a / b; return a; }
-__device__ inline bool operator<(const Dual &a, const Dual &b) { return a.v < b.v; }
-__device__ inline bool operator>(const Dual &a, const Dual &b) { return a.v > b.v; }
-__device__ inline bool operator<=(const Dual &a, const Dual &b) { return a.v <= b.v; }
-__device__ inline bool operator>=(const Dual &a, const Dual &b) { return a.v >= b.v; }
-__device__ inline Dual nk_chain(const Dual &a, nk_real fv, nk_real dfv) { Dual r; r.v = fv; NK_DUAL_LOOP r.d[k] = dfv * a.d[k]; return r; }
-__device__ inline Dual sqrt(const Dual &a) { const nk_real s = sqrt(a.v); return nk_chain(a, s, NK_R(0.5) / s); }
-__device__ inline Dual exp(const Dual &a) { const nk_real e = exp(a.v); return nk_chain(a, e, e); }
-__device__ inline Dual log(const Dual &a) { return nk_chain(a, log(a.v), NK_R(1) / a.v); }
-__device__ inline Dual sin(const Dual &a) { return nk_chain(a, sin(a.v), cos(a.v)); }
-__device__ inline Dual cos(const Dual &a) { return nk_chain(a, cos(a.v), -sin(a.v)); }
-__device__ inline Dual tan(const Dual &a) { const nk_real t = tan(a.v); return nk_chain(a, t, NK_R(1) + t * t); }
-__device__ inline Dual tanh(const Dual &a) { const nk_real t = tanh(a.v); return nk_chain(a, t, NK_R(1) - t * t); }
-__device__ inline Dual atan(const Dual &a) { return nk_chain(a, atan(a.v), NK_R(1) / (NK_R(1) + a.v * a.v)); }
-__device__ inline Dual fabs(const Dual &a) { return nk_chain(a, fabs(a.v), a.v < NK_R(0) ? NK_R(-1) : NK_R(1)); }
-__device__ inline Dual pow(const Dual &a, nk_real e) { const nk_real pw = pow(a.v, e - NK_R(1)); return nk_chain(a, pw * a.v, e * pw); }
-__device__ inline Dual pow(const Dual &a, int e) { return pow(a, (nk_real)e); }
-#ifdef NK_F32
-__device__ inline Dual pow(const Dual &a, double e) { return pow(a, (nk_real)e); }  // (else pow(u, 2.0) is ambiguous)
-#endif
-__device__ inline Dual pow(const Dual &a, const Dual &b) { return exp(b * log(a)); }
-)NKSRC";
 
 static const char *k_kernel = R"NKSRC(
 #if NK_N <= 8
@@ -918,40 +855,6 @@ nk_batch_trust_region_nlls(long nbatch, const nk_real *__restrict__ u0, int u0_p
 }
 )NKSRC";
 
-// ----------------------------------------------------------------------------- hiprtc through dlopen
-typedef void *rtc_program;
-static struct {
-  void *h = nullptr;
-  int (*Create)(rtc_program *, const char *, const char *, int, const char **, const char **) = nullptr;
-  int (*Compile)(rtc_program, int, const char **) = nullptr;
-  int (*LogSize)(rtc_program, size_t *) = nullptr;
-  int (*Log)(rtc_program, char *) = nullptr;
-  int (*CodeSize)(rtc_program, size_t *) = nullptr;
-  int (*Code)(rtc_program, char *) = nullptr;
-  int (*Destroy)(rtc_program *) = nullptr;
-} RTC;
-
-static int rtc_load() {
-  if (RTC.h) return NK_OK;
-  const char *names[] = {"libhiprtc.so.7", "libhiprtc.so", "/opt/rocm/lib/libhiprtc.so"};
-  for (const char *nm : names) {
-    RTC.h = dlopen(nm, RTLD_NOW | RTLD_GLOBAL);
-    if (RTC.h) break;
-  }
-  if (!RTC.h) NK_FAIL(NK_E_UNSUPPORTED, "cannot dlopen libhiprtc (needed to compile the residual): %s", dlerror());
-#define RTC_SYM(field, name)                                                          \
-  RTC.field = (decltype(RTC.field))dlsym(RTC.h, name);                                \
-  if (!RTC.field) { RTC.h = nullptr; NK_FAIL(NK_E_UNSUPPORTED, "libhiprtc lacks symbol %s", name); }
-  RTC_SYM(Create, "hiprtcCreateProgram");
-  RTC_SYM(Compile, "hiprtcCompileProgram");
-  RTC_SYM(LogSize, "hiprtcGetProgramLogSize");
-  RTC_SYM(Log, "hiprtcGetProgramLog");
-  RTC_SYM(CodeSize, "hiprtcGetCodeSize");
-  RTC_SYM(Code, "hiprtcGetCode");
-  RTC_SYM(Destroy, "hiprtcDestroyProgram");
-#undef RTC_SYM
-  return NK_OK;
-}
 
 struct nk_batch {
   nk_ctx *ctx = nullptr;
@@ -989,11 +892,8 @@ static int batch_compile(const char *source, int n, int np, int flags, std::vect
              "<typename T> __device__ void nk_f(const T *u, const nk_real *p, T *f)` with u: n values, f: m values; the "
              "minimum-norm solution of an underdetermined problem is not offered)", m, n);
   NK_REQUIRE(np >= 0 && np <= 256, "nparams = %d outside 0..256", np);
-  NK_TRY(rtc_load());
-  std::string full = std::string(k_prelude) + "\n// ---- user source\n" + source + "\n" +
+  std::string full = std::string(nk_dual_prelude) + "\n// ---- user source\n" + source + "\n" +
                      (wave ? k_kernel_wave : kset == KSET_JF ? k_kernel_jf : nlls ? k_kernel_nlls : k_kernel);
-  rtc_program prog = nullptr;
-  if (RTC.Create(&prog, full.c_str(), "nk_batch_user.hip", 0, nullptr, nullptr) != 0) NK_FAIL(NK_E_HIP, "hiprtcCreateProgram failed");
   // dual-number partials per residual sweep (wave kernel: one per lane; the Jacobian-free kernels sweep no duals)
   const int ch = wave || kset == KSET_JF ? 1 : (n < 8 ? n : 8);
   const std::string dn = "-DNK_N=" + std::to_string(n), dp = "-DNK_NP=" + std::to_string(np), dc = "-DNK_CH=" + std::to_string(ch),
@@ -1004,12 +904,9 @@ static int batch_compile(const char *source, int n, int np, int flags, std::vect
   if (nlls) opts.push_back(dm.c_str());
   if ((flags & NK_BATCH_ANALYTIC_JAC) && (kset == KSET_NEWTON || nlls)) opts.push_back("-DNK_HAS_JAC=1");
   if (flags & NK_BATCH_FLOAT32) opts.push_back("-DNK_F32=1");
-  const int rc = RTC.Compile(prog, (int)opts.size(), opts.data());
-  size_t ls = 0;
-  RTC.LogSize(prog, &ls);
-  if (ls > 1 && log) { log->resize(ls); RTC.Log(prog, &(*log)[0]); }
-  if (rc != 0) {
-    RTC.Destroy(&prog);
+  bool failed = false;
+  NK_TRY(nk_rtc_compile(full, "nk_batch_user.hip", opts, code, log, &failed));
+  if (failed) {
     const char *lg = log && !log->empty() ? log->c_str() : "(no log)";
     if (flags & NK_BATCH_FLOAT32)   // the usual cause: a source written against the Float64 contract (const double *p)
       NK_FAIL(NK_E_INVALID, "residual source does not compile in Float32 mode, whose contract is `template <typename T> "
@@ -1017,11 +914,6 @@ static int batch_compile(const char *source, int n, int np, int flags, std::vect
               "const nk_real *p, nk_real *J)`) with nk_real = float: %.900s", lg);
     NK_FAIL(NK_E_INVALID, "residual source does not compile: %.900s", lg);
   }
-  size_t cs = 0;
-  RTC.CodeSize(prog, &cs);
-  code->resize(cs);
-  RTC.Code(prog, code->data());
-  RTC.Destroy(&prog);
   return NK_OK;
 }
 

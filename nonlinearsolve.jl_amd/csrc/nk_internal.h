@@ -46,6 +46,13 @@ struct nk_scope_guard {
 template <class T, class D>
 nk_scope_guard<T, D> nk_make_guard(T *p, D d) { return {p, d}; }
 
+// ----------------------------------------------------------------------------- run-time compilation (nk_rtc.hip)
+// the prelude of every generated kernel set: nk_real and the forward-mode dual numbers with NK_CH partials
+extern const char *const nk_dual_prelude;
+// hiprtc (through dlopen) on `full`: code object into `code`, compiler log into `log` (nullable); *failed = it did not compile
+int nk_rtc_compile(const std::string &full, const char *name, const std::vector<const char *> &opts, std::vector<char> *code,
+                   std::string *log, bool *failed);
+
 // ----------------------------------------------------------------------------- context
 constexpr int NK_BLOCK = 256;          // 4 wavefronts of 64
 constexpr int NK_MAX_RED_BLOCKS = 1024; // stage-1 reduction blocks (4 per CU)
@@ -362,6 +369,9 @@ struct nk_problem {
   nk_user_callbacks cb{};
   void *user = nullptr;
   nk_csr *user_pattern = nullptr;
+  // compiled grid problem (nk_problem_create_grid, nk_grid.hip): a user problem whose callbacks launch kernels generated from
+  // the user's pointwise source; owns its modules, its parameter buffer and user_pattern (nk_grid_state_destroy)
+  struct nk_grid_state *grid = nullptr;
   // forward-difference JVP for user problems without a jvp callback: f(u) at the linearisation point, u + εv, f(u + εv)
   double *d_fd_f0 = nullptr, *d_fd_up = nullptr, *d_fd_f1 = nullptr;
   // operator fallbacks through the Jacobian (prepare_jvp / prepare_vjp, SciMLJacobianOperators.jl:296-362,373-431): a private
@@ -374,6 +384,8 @@ struct nk_problem {
   struct nk_powers_plan *pw = nullptr;
   bool pw_tried = false;
 };
+void nk_grid_state_destroy(struct nk_grid_state *S);
+int nk_grid_set_params(nk_problem *P, const double *params, int nparams);   // nk_problem_set_params of a compiled grid problem
 bool nk_problem_powers_ready(nk_problem *P);
 int nk_problem_powers_dev(nk_problem *P, const double *d_u, const double *d_x0, double *d_Y, int64_t ldy, int s,
                           const double *d_scal_first, const double *d_scal_rest, const double *d_theta, const int *d_skip);

@@ -582,6 +582,7 @@ extern "C" int nk_problem_destroy(nk_problem *P) {
   for (double *&t : P->d_tmp) hipFree(t);
   nk_halo_free(&P->halo);
   nk_csr_destroy(P->lin_J);
+  nk_grid_state_destroy(P->grid);
   delete P;
   return NK_OK;
 }
@@ -593,7 +594,8 @@ extern "C" int nk_problem_size(nk_problem *P, int64_t *n_local, int64_t *n_globa
   return NK_OK;
 }
 extern "C" int nk_problem_set_params(nk_problem *P, const double *params, int nparams) {
-  NK_REQUIRE(P && params, "NULL argument");
+  NK_REQUIRE(P && (params || (P->grid && nparams == 0)), "NULL argument");
+  if (P->grid) return nk_grid_set_params(P, params, nparams);   // up to 32 values, kept on the device for the generated kernels
   NK_REQUIRE(nparams == P->nparams, "nparams mismatch (%d vs %d)", nparams, P->nparams);
   if (P->kind == NK_PROBLEM_QUADRATIC) {
     NK_REQUIRE((int64_t)params[0] == P->n_global, "cannot change the problem size");
@@ -1055,7 +1057,10 @@ extern "C" int nk_problem_initial_guess(nk_problem *P, double *u0, int memspace)
         NK_LAUNCH(P->ctx, k_brus_u0, dim3(grid1(P->n_local / 2)), dim3(NK_BLOCK), brus_params(P), d);
       NK_HIP(hipGetLastError());
       break;
-    default: NK_FAIL(NK_E_UNSUPPORTED, "no built-in initial guess for this problem kind");
+    default:
+      if (!P->grid) NK_FAIL(NK_E_UNSUPPORTED, "no built-in initial guess for this problem kind");
+      NK_TRY(nk_blas_fill(P->ctx, P->n_local, 0.0, d));   // compiled grid problem
+      break;
   }
   return out_end(P, u0, memspace, d);
 }

@@ -1,0 +1,131 @@
+"""The generated kernels of a compiled grid problem (csrc/nk_grid.hip) against the hand-written Bratu kernels, in one process:
+the Bratu source of tests/grid_reference.py compiled at 1024² next to Bratu2D(1024).
+
+Kernel times are the kernels' own begin → end device timestamps (the library's per-kernel event timing, which the generated
+launches join): one launch per sample, the two problems alternating, the median of `--reps` samples after a warm-up; GB/s on
+the algorithmic bytes — residual 16 n, JVP 24 n (the built-in JVP reads a precomputed diagonal where the generated one reads u:
+the same 24 n), fill 8 nnz + 8 n. The fill is timed in both of its forms: rows put together in LDS and stored as whole lines
+(the default), and every thread storing its own partials (NK_GRID_FILL_DIRECT=1).
+
+Then bench.py's protocol — NewtonRaphson, exactly 30 Arnoldi steps of GMRES(30) per Newton step, nothing terminates — matrix-free
+and on the concrete Jacobian, on both problems: `--steps` timed steps after `--warmup`, three runs each, alternating.
+
+    python tools/grid_problem_bench.py [--out profiles/grid_problem_bench.txt] [--grid 1024] [--reps 200] [--steps 300]
+"""
+import argparse
+import os
+import statistics
+import sys
+import time
+
+ROOT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+import torch
+
+import grid_reference as R
+import nonlinearsolve_jl_amd as nls
+
+
+def kernel_samples(ctx, calls, reps, warm=20):
+    """calls: {label: (callable, profile family)}; per label the sorted per-launch device times in µs"""
+    out = {k: [] for k in calls}
+    for i in range(warm + reps):
+        for label, (fn, family) in calls.items():
+            ctx.profile_enable(True)       # (also resets the accumulators)
+            fn()
+            r = ctx.profile_report()[family]
+            if i >= warm:
+                out[label].append(1e3 * r["total_ms"])   # (every launch of the family the call made: one)
+    ctx.profile_enable(False)
+    return {k: sorted(v) for k, v in out.items()}
+
+
+def steps_per_second(make_problem, u0, concrete, steps, warmup):
+    alg = nls.NewtonRaphson(linsolve=nls.KrylovJL_GMRES(gmres_restart=30, maxiters=30, fixed_iters=30), concrete_jac=concrete)
+    cache = nls.init(nls.NonlinearProblem(make_problem(), u0.clone()), alg, abstol=1e-300, maxiters=10 ** 9)
+    for _ in range(warmup):
+        cache.step()
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(steps):
+        cache.step()
+    torch.cuda.synchronize()
+    dt = time.perf_counter() - t0
+    fn = cache.fnorm_inf
+    cache.close()
+    return steps / dt, fn
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "grid_problem_bench.txt"))
+    ap.add_argument("--grid", type=int, default=1024)
+    ap.add_argument("--reps", type=int, default=200)
+    ap.add_argument("--steps", type=int, default=300)
+    ap.add_argument("--warmup", type=int, default=20)
+    args = ap.parse_args()
+    ns = args.grid
+    n, nnz = ns * ns, 5 * ns * ns - 4 * ns
+    ctx = nls.default_context()
+    par = R.bratu_params(ns, 6.0)
+    B = nls.Bratu2D(ns, 6.0)
+    P = nls.CompiledGridProblem(R.BRATU_SRC, ns, ns, params=par)
+    os.environ["NK_GRID_FILL_DIRECT"] = "1"
+    Pd = nls.CompiledGridProblem(R.BRATU_SRC, ns, ns, params=par)
+    del os.environ["NK_GRID_FILL_DIRECT"]
+    g = torch.Generator(device="cuda").manual_seed(1)
+    u = 2.0 * torch.rand(n, dtype=torch.float64, device="cuda", generator=g) - 1.0
+    v = 2.0 * torch.rand(n, dtype=torch.float64, device="cuda", generator=g) - 1.0
+    JB, JP, JPd = B.jac_csr(), P.jac_csr(), Pd.jac_csr()
+    # the two problems compute the same numbers before anything is timed
+    assert float((P.residual(u) - B.residual(u)).abs().max()) <= 1e-12
+    assert float((P.jvp(v, u) - B.jvp(v, u)).abs().max()) <= 1e-12
+    for PP, JJ in ((B, JB), (P, JP), (Pd, JPd)):
+        PP.jac_values(u, JJ)
+    assert float((JP.matvec(v) - JB.matvec(v)).abs().max()) <= 1e-12 and torch.equal(JP.matvec(v), JPd.matvec(v))
+    calls = {
+        "residual built-in  k_bratu_residual": (lambda: B.residual(u), "residual"),
+        "residual generated nk_grid_residual": (lambda: P.residual(u), "residual"),
+        "JVP      built-in  k_bratu_jvp_tile": (lambda: B.jvp(v, u), "jvp"),
+        "JVP      generated nk_grid_jvp": (lambda: P.jvp(v, u), "jvp"),
+        "fill     built-in  k_bratu_jac": (lambda: B.jac_values(u, JB), "jacfill"),
+        "fill     generated nk_grid_jac (LDS-staged rows)": (lambda: P.jac_values(u, JP), "jacfill"),
+        "fill     generated nk_grid_jac (direct stores)": (lambda: Pd.jac_values(u, JPd), "jacfill"),
+    }
+    bytes_of = {"residual": 16.0 * n, "jvp": 24.0 * n, "jacfill": 8.0 * nnz + 8.0 * n}
+    ts = kernel_samples(ctx, calls, args.reps)
+    lines = [f"Compiled grid problem against the built-in Bratu kernels: {ns} x {ns}, n = {n}, nnz = {nnz}, "
+             f"{torch.cuda.get_device_name(0)}",
+             f"kernel begin -> end device timestamps, one launch per sample, problems alternating, {args.reps} samples after 20", "",
+             f"  {'kernel':52s} {'median us':>10s} {'p10':>8s} {'p90':>8s} {'GB/s (median)':>14s}  algorithmic MB"]
+    for label, (_fn, fam) in calls.items():
+        t = ts[label]
+        med = statistics.median(t)
+        lines.append(f"  {label:52s} {med:10.2f} {t[len(t) // 10]:8.2f} {t[(9 * len(t)) // 10]:8.2f} "
+                     f"{bytes_of[fam] / med / 1e3:14.1f}  {bytes_of[fam] / 1e6:.1f}")
+    lines += ["", f"Newton steps/s, bench.py's fixed-work protocol (30 Arnoldi steps of GMRES(30) per step), {args.steps} steps after "
+              f"{args.warmup}, three runs each, alternating:"]
+    u0 = torch.zeros(n, dtype=torch.float64, device="cuda")
+    for concrete, what in ((False, "matrix-free (JVP operator)"), (True, "concrete Jacobian (fill + CSR SpMV)")):
+        rb, rp = [], []
+        for _ in range(3):
+            sb, fb = steps_per_second(lambda: B, u0, concrete, args.steps, args.warmup)
+            sp, fp = steps_per_second(lambda: P, u0, concrete, args.steps, args.warmup)
+            rb.append(sb)
+            rp.append(sp)
+        lines += [f"  {what}",
+                  f"    built-in Bratu2D      median {statistics.median(rb):9.1f} steps/s  (runs: {', '.join('%.1f' % x for x in rb)}; |f|inf after {fb:.3e})",
+                  f"    compiled Bratu source median {statistics.median(rp):9.1f} steps/s  (runs: {', '.join('%.1f' % x for x in rp)}; |f|inf after {fp:.3e})",
+                  f"    compiled / built-in   {statistics.median(rp) / statistics.median(rb):9.3f}"]
+    text = "\n".join(lines) + "\n"
+    print(text)
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, "w") as f:
+        f.write(text)
+    for PP in (B, P, Pd):
+        PP.close()
+
+
+if __name__ == "__main__":
+    main()
