@@ -19,6 +19,13 @@
 // release / acquire pair spelled out instruction by instruction: a compiler-emitted agent-scope release would write back the whole
 // L2 (`buffer_wbl2`) once per power and band — measured in rounds 3–5 as the slow form (MI355X_MICROARCH.md, hand-off forms) —, so
 // the contract is tied to this target, checked by tests that compare every word under uneven load (tests/test_gpu_powers.py).
+// Where a power's time goes (profiles/r07_powers_gathers_and_ghost_depth2.md): the LDS gathers. The stamps of wavefront 0 (make
+// stamps) show 1.04 µs of arithmetic per power at 1024², but wavefront 0 is the oldest on its SIMD and is served first — all 16
+// wavefronts need ≈ 0.43 µs per slice. So a row's gathers are issued back to back before its row sum starts, and the powers'
+// scalars (scale, shift) are kept in scalar registers so that no row's epilogue waits for the column stores before it.
+// Tried and NOT kept (same file): ghost rows two slices deep — two powers per hand-off, the neighbours' adjacent slices computed
+// redundantly. Half the hand-off chains, but the two extra slices per round cost what the saved chain cost: 68.6 – 70.0 µs per
+// 15-power launch against 59.4 (4 slices per band), 50.4 against 49.3 (2 slices per band).
 // Eligibility (host, once per pattern — nk_csr_powers_plan): one rank, no halo; rows ≤ #CUs × 1024 × RPT_max; every row ≤ W
 // entries; every column of band b inside [first row of b − 1024, last row of b + 1024]. Everything else keeps the streaming
 // kernel. All workgroups must be resident at once (grid ≤ #CUs, one per CU by its LDS footprint); every wait is bounded by a
@@ -131,6 +138,13 @@ __device__ __forceinline__ void pw_store_sys(double *p, double v) {
 __device__ __forceinline__ double pw_load_sys(const double *p) {
   return __longlong_as_double((long long)__hip_atomic_load(reinterpret_cast<const unsigned long long *>(p), __ATOMIC_RELAXED,
                                                            __HIP_MEMORY_SCOPE_SYSTEM));
+}
+// a wave-uniform value → scalar registers: a later use does not wait on the vector-memory counter (which on gfx9 counts the
+// column stores in flight as well as the load that brought the value)
+__device__ __forceinline__ double pw_uniform(double x) {
+  const unsigned long long u = (unsigned long long)__double_as_longlong(x);
+  const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)u), hi = __builtin_amdgcn_readfirstlane((unsigned)(u >> 32));
+  return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
 }
 // order in which a power visits the band's slices: the two the neighbours read first, the interior ones behind them
 template <int RPT>
@@ -263,12 +277,15 @@ __global__ __launch_bounds__(PW_T) void k_spmv_powers(const pw_args a) {
   }
 
   const bool shifted = a.theta != nullptr;
+  // the powers' scalars live in scalar registers: the scales are read once, the shift of power p + 1 comes in with the halo rows
+  // of power p — no row's epilogue waits on memory (a wait for a loaded scalar is a wait for the stores before it as well)
+  const double os_first = pw_uniform(a.scal_first ? *a.scal_first : 1.0), os_rest = pw_uniform(a.scal_rest ? *a.scal_rest : 1.0);
+  double th = pw_uniform(shifted ? a.theta[0] : 0.0);
   for (int p = 0; p < a.s; ++p) {
     const double *xin = (p & 1) ? xb : xa;
     double *xout = (p & 1) ? xa : xb;
     const double *osp = (p == 0) ? a.scal_first : a.scal_rest;
-    const double os = osp ? *osp : 1.0;
-    const double th = shifted ? a.theta[p] : 0.0;
+    const double os = (p == 0) ? os_first : os_rest;
     double *ycol = a.Y + (int64_t)p * a.ldy;
     const bool pub = p + 1 < a.s;
     PW_STAMP(p, 0);
@@ -276,13 +293,27 @@ __global__ __launch_bounds__(PW_T) void k_spmv_powers(const pw_args a) {
     for (int q = 0; q < RPT; ++q) {
       const int i = pw_slice<RPT>(q);
       const int lr = t + PW_T * i, r = r0 + lr;
+      // the row's W gathers (and its own entry) are issued back to back, the row sum consumes them as they arrive: left to
+      // itself the compiler waits for every gather before it issues the next, and a slice costs W + 1 LDS latencies per wavefront
+      // (6 × 5 slots: no registers to spare for the batch — the gathers stay where the compiler puts them)
+      constexpr bool BATCH = RPT * W < 30;
+      double xv[BATCH ? W : 1], xo = 0.0;
+      if constexpr (BATCH) {
+#pragma unroll
+        for (int j = 0; j < W; ++j) xv[j] = xin[ci[i][j]];
+        xo = xin[PW_HALO + lr];
+        __builtin_amdgcn_sched_barrier(0);
+      }
       double sum = 0.0;
 #pragma unroll
       for (int j = 0; j < W; ++j) {
-        const double pr = v[i][j] * xin[ci[i][j]];
+        double xj;
+        if constexpr (BATCH) xj = xv[j]; else xj = xin[ci[i][j]];
+        const double pr = v[i][j] * xj;
         sum = (j < len[i]) ? sum + pr : sum;
       }
-      double out = shifted ? sum - th * xin[PW_HALO + lr] : sum;
+      if constexpr (!BATCH) xo = xin[PW_HALO + lr];
+      double out = shifted ? sum - th * xo : sum;
       out = osp ? os * out : out;
       if (r < a.nrows) {
         xout[PW_HALO + lr] = out;
@@ -350,6 +381,7 @@ __global__ __launch_bounds__(PW_T) void k_spmv_powers(const pw_args a) {
       else if (PEER && pup) hu = pw_load_sys(a.pr.recv_up + (size_t)(a.pr.ebuf + ((p + 1) & 1)) * PW_T + t);
       if (gd < a.nrows) hd = pw_load_sc1(ycol + gd);
       else if (PEER && pdn) hd = pw_load_sys(a.pr.recv_dn + (size_t)(a.pr.ebuf + ((p + 1) & 1)) * PW_T + t);
+      th = pw_uniform(shifted ? a.theta[p + 1] : 0.0);   // (p + 1 < s here)
 #ifdef NK_PW_STAMPS
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       PW_STAMP(p, 7);                        // this wavefront's halo rows are in

@@ -2,7 +2,8 @@
 """(needs the stamps build: make -C nonlinearsolve.jl_amd/csrc stamps; NK_LIB_PATH=nonlinearsolve.jl_amd/lib/libmi355x_nk_stamps.so)
 Development: where the time of ONE POWER of the resident matrix-powers kernel goes — phase stamps of every band's wavefront 0
 (100 MHz wall clock, 10 ns resolution), Bratu 1024² (256 bands of 4 slices, W = 5), 15 powers per launch, the steady-state powers
-2 … 13 of the last of `reps` launches. NK_PW_GRAN=0 / 1 selects the hand-off form (a process each).
+2 … 13 of the last of `reps` launches. Wavefront 0 is the oldest wavefront of its SIMD and is served first: what the other fifteen
+still have to do shows up in the barrier rows (profiles/r07_powers_gathers_and_ghost_depth2.md).
 
     python tools/pw_stamps.py [grid=1024] [s=15] [reps=20]
 """
@@ -40,7 +41,7 @@ nb = (n + 4095) // 4096
 out = (C.c_ulonglong * (nb * STP * NST))()
 f(1, out, nb)
 st = np.array(list(out), dtype=np.float64).reshape(nb, STP, NST) / 100.0   # µs
-gran = os.environ.get("NK_PW_GRAN", "1") != "0"
+gran = False   # (the granule hand-off of round 6 is gone: the flag form is the only one)
 names = {0: "power starts", 1: "boundary slices computed, stores issued", 2: "write-through stores drained (vmcnt 0)",
          3: "barrier behind the drain", 4: "interior slices computed, stores issued", 5: "upper neighbour's flag seen",
          6: "both flags seen (barrier)", 7: "halo rows / granules in (this wavefront)", 9: "power ends (barrier)"}
