@@ -525,6 +525,31 @@ int nk_grid_code_object(const char *source, int dof, int stencil, int boundary, 
 int nk_problem_create_grid(nk_ctx *ctx, const char *source, int64_t nx, int64_t ny, int dof, int stencil, int boundary,
                            const double *params, int nparams, nk_problem **out);
 
+/* Three dimensions. The same three kernels, generated from a source written against the 3-D neighbourhood:
+ *     template <typename T> __device__ void nk_point(const nk_nbhd3<T> &u, const nk_real *p, nk_site3 s, T *f);
+ * with  u(di, dj, dk, c = 0)  component c at node (i + di, j + dj, k + dk), every offset ∈ {−1, 0, 1} (constants, or the
+ *                             counters of `#pragma unroll` loops). With NK_GRID_STAR a read with more than one non-zero offset
+ *                             (an edge or a corner) returns NaN, as the 2-D star's corner read does;
+ *       s                     nk_site3 {i, j, k, nx, ny, nz};
+ *       p, f, nk_real         as in 2-D.
+ * Geometry: nx × ny × nz nodes, nx, ny, nz >= 3; unknown c of node (i, j, k) is element c·nx·ny·nz + (k·ny + j)·nx + i
+ * (component-major, as in 2-D). NK_GRID_STAR is the 7-point star with dof = 1..4, NK_GRID_BOX the 27-point box with dof = 1:
+ * a row has at most 28 partials (this cap replaces 2-D's 20 for these entry points only; no permitted combination spills —
+ * the generated kernels have no private segment). The boundary — NK_GRID_DIRICHLET0 or NK_GRID_PERIODIC — applies to all three
+ * directions. The pattern's 32-bit indices are checked: nx·ny·nz·dof·npts·dof <= INT32_MAX.
+ * Stencil points are numbered by ascending node index inside the grid — star: (0,0,−1) (0,−1,0) (−1,0,0) C (1,0,0) (0,1,0)
+ * (0,0,1); box: dk outermost, di innermost — and the pattern keeps every (point in the domain) × (component) entry in ascending
+ * column order, as in 2-D. The object is the same NK_PROBLEM_USER problem owning its pattern: nk_problem_set_params,
+ * nk_problem_jac_csr, nk_problem_initial_guess and nk_problem_destroy work unchanged. One rank, Float64. The kernels are
+ * nk_grid3_residual, nk_grid3_jvp (jac = 0) and nk_grid3_jac (jac = 1); NK_GRID_FILL_DIRECT keeps its meaning. */
+int nk_grid3_pattern(int64_t nx, int64_t ny, int64_t nz, int dof, int stencil, int boundary, int32_t *rowptr, int32_t *colind,
+                     int64_t *nnz);
+int nk_grid3_compile_check(const char *source, int dof, int stencil, int boundary, int nparams, int64_t *code_bytes);
+int nk_grid3_code_object(const char *source, int dof, int stencil, int boundary, int nparams, int jac, void *buf,
+                         int64_t capacity, int64_t *bytes);
+int nk_problem_create_grid3(nk_ctx *ctx, const char *source, int64_t nx, int64_t ny, int64_t nz, int dof, int stencil,
+                            int boundary, const double *params, int nparams, nk_problem **out);
+
 /* ---------------------------------------------------------------- GMRES (seam 1) */
 int nk_gmres_create(nk_ctx *ctx, int64_t n_local, int restart_m, int ortho, nk_gmres **out);
 int nk_gmres_destroy(nk_gmres *G);

@@ -176,24 +176,42 @@ const GRID_BOUNDARIES = Dict(:dirichlet => 0, :periodic => 1)
 pointwise on an nx × ny grid through a radius-1 stencil as HIP source
 `template <typename T> __device__ void nk_point(const nk_nbhd<T> &u, const nk_real *p, nk_site s, T *f)`; the library compiles
 the residual kernel, the exact dual-number JVP kernel and the Jacobian fill from it (nk_problem_create_grid). One rank, Float64,
-dof ≤ 4 (box: ≤ 2), at most 32 parameters."""
+dof ≤ 4 (box: ≤ 2), at most 32 parameters. With `nz = n` the grid is nx × ny × nz and the source is written against
+`nk_nbhd3<T>` / `nk_site3` (`u(di, dj, dk, c)`; nk_problem_create_grid3): the 7-point star with dof ≤ 4 or the 27-point box with dof = 1."""
 function CompiledGridProblem(source::AbstractString, nx::Integer, ny::Integer; dof::Integer = 1, stencil::Symbol = :star,
-                             boundary::Symbol = :dirichlet, params::Vector{Float64} = Float64[], ctx = default_ctx())
+                             boundary::Symbol = :dirichlet, params::Vector{Float64} = Float64[], ctx = default_ctx(),
+                             nz::Union{Nothing, Integer} = nothing)
     out = Ref{Ptr{Cvoid}}(C_NULL)
     par = isempty(params) ? Float64[0.0] : params
-    GC.@preserve par nkcheck(@ccall libnk.nk_problem_create_grid(ctx.ptr::Ptr{Cvoid}, String(source)::Cstring, Int64(nx)::Int64,
-        Int64(ny)::Int64, dof::Cint, GRID_STENCILS[stencil]::Cint, GRID_BOUNDARIES[boundary]::Cint, par::Ptr{Float64},
-        length(params)::Cint, out::Ptr{Ptr{Cvoid}})::Cint)
+    if nz === nothing
+        GC.@preserve par nkcheck(@ccall libnk.nk_problem_create_grid(ctx.ptr::Ptr{Cvoid}, String(source)::Cstring, Int64(nx)::Int64,
+            Int64(ny)::Int64, dof::Cint, GRID_STENCILS[stencil]::Cint, GRID_BOUNDARIES[boundary]::Cint, par::Ptr{Float64},
+            length(params)::Cint, out::Ptr{Ptr{Cvoid}})::Cint)
+    else
+        GC.@preserve par nkcheck(@ccall libnk.nk_problem_create_grid3(ctx.ptr::Ptr{Cvoid}, String(source)::Cstring, Int64(nx)::Int64,
+            Int64(ny)::Int64, Int64(nz)::Int64, dof::Cint, GRID_STENCILS[stencil]::Cint, GRID_BOUNDARIES[boundary]::Cint,
+            par::Ptr{Float64}, length(params)::Cint, out::Ptr{Ptr{Cvoid}})::Cint)
+    end
     nl = Ref{Int64}(0)
     nkcheck(@ccall libnk.nk_problem_size(out[]::Ptr{Cvoid}, nl::Ptr{Int64}, C_NULL::Ptr{Int64}, C_NULL::Ptr{Int64})::Cint)
     p = DeviceProblem(out[], nl[])
     finalizer(x -> @ccall(libnk.nk_problem_destroy(x.ptr::Ptr{Cvoid})::Cint), p)
     return p
 end
-"""`grid_pattern(nx, ny; dof, stencil, boundary)` → `(rowptr, colind)`, 0-based `Int32`: the CSR pattern of that Jacobian (host only)."""
-function grid_pattern(nx::Integer, ny::Integer; dof::Integer = 1, stencil::Symbol = :star, boundary::Symbol = :dirichlet)
+"""`grid_pattern(nx, ny; dof, stencil, boundary, nz)` → `(rowptr, colind)`, 0-based `Int32`: the CSR pattern of that Jacobian (host
+only); with `nz` the pattern of the nx × ny × nz grid."""
+function grid_pattern(nx::Integer, ny::Integer; dof::Integer = 1, stencil::Symbol = :star, boundary::Symbol = :dirichlet,
+                      nz::Union{Nothing, Integer} = nothing)
     nnz = Ref{Int64}(0)
     st, bd = GRID_STENCILS[stencil], GRID_BOUNDARIES[boundary]
+    if nz !== nothing
+        nkcheck(@ccall libnk.nk_grid3_pattern(Int64(nx)::Int64, Int64(ny)::Int64, Int64(nz)::Int64, dof::Cint, st::Cint, bd::Cint,
+            C_NULL::Ptr{Int32}, C_NULL::Ptr{Int32}, nnz::Ptr{Int64})::Cint)
+        rowptr, colind = Vector{Int32}(undef, dof * nx * ny * nz + 1), Vector{Int32}(undef, nnz[])
+        nkcheck(@ccall libnk.nk_grid3_pattern(Int64(nx)::Int64, Int64(ny)::Int64, Int64(nz)::Int64, dof::Cint, st::Cint, bd::Cint,
+            rowptr::Ptr{Int32}, colind::Ptr{Int32}, nnz::Ptr{Int64})::Cint)
+        return rowptr, colind
+    end
     nkcheck(@ccall libnk.nk_grid_pattern(Int64(nx)::Int64, Int64(ny)::Int64, dof::Cint, st::Cint, bd::Cint, C_NULL::Ptr{Int32},
         C_NULL::Ptr{Int32}, nnz::Ptr{Int64})::Cint)
     rowptr, colind = Vector{Int32}(undef, dof * nx * ny + 1), Vector{Int32}(undef, nnz[])
@@ -201,10 +219,17 @@ function grid_pattern(nx::Integer, ny::Integer; dof::Integer = 1, stencil::Symbo
         colind::Ptr{Int32}, nnz::Ptr{Int64})::Cint)
     return rowptr, colind
 end
-"""`grid_compile_check(source; dof, stencil, boundary, nparams)`: compile the three kernels for gfx950 (no device needed); bytes of code."""
+"""`grid_compile_check(source; dof, stencil, boundary, nparams, dim = 2)`: compile the three kernels for gfx950 (no device needed);
+bytes of code. `dim = 3`: the 3-D contract."""
 function grid_compile_check(source::AbstractString; dof::Integer = 1, stencil::Symbol = :star, boundary::Symbol = :dirichlet,
-                            nparams::Integer = 0)
+                            nparams::Integer = 0, dim::Integer = 2)
     nb = Ref{Int64}(0)
+    dim in (2, 3) || throw(ArgumentError("dim = $dim: expected 2 or 3"))
+    if dim == 3
+        nkcheck(@ccall libnk.nk_grid3_compile_check(String(source)::Cstring, dof::Cint, GRID_STENCILS[stencil]::Cint,
+            GRID_BOUNDARIES[boundary]::Cint, nparams::Cint, nb::Ptr{Int64})::Cint)
+        return nb[]
+    end
     nkcheck(@ccall libnk.nk_grid_compile_check(String(source)::Cstring, dof::Cint, GRID_STENCILS[stencil]::Cint,
         GRID_BOUNDARIES[boundary]::Cint, nparams::Cint, nb::Ptr{Int64})::Cint)
     return nb[]

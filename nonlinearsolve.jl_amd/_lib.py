@@ -188,6 +188,10 @@ SIGNATURES = {
     "nk_grid_compile_check": (_I, [C.c_char_p, _I, _I, _I, _I, C.POINTER(_L)]),
     "nk_grid_code_object": (_I, [C.c_char_p, _I, _I, _I, _I, _I, _P, _L, C.POINTER(_L)]),
     "nk_problem_create_grid": (_I, [_P, C.c_char_p, _L, _L, _I, _I, _I, C.POINTER(_D), _I, _PP]),
+    "nk_grid3_pattern": (_I, [_L, _L, _L, _I, _I, _I, _P, _P, C.POINTER(_L)]),
+    "nk_grid3_compile_check": (_I, [C.c_char_p, _I, _I, _I, _I, C.POINTER(_L)]),
+    "nk_grid3_code_object": (_I, [C.c_char_p, _I, _I, _I, _I, _I, _P, _L, C.POINTER(_L)]),
+    "nk_problem_create_grid3": (_I, [_P, C.c_char_p, _L, _L, _L, _I, _I, _I, C.POINTER(_D), _I, _PP]),
     "nk_gmres_create": (_I, [_P, _L, _I, _I, _PP]),
     "nk_gmres_destroy": (_I, [_P]),
     "nk_gmres_set_operator_csr": (_I, [_P, _P]),

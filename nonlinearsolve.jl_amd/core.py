@@ -487,24 +487,36 @@ def _grid_ids(stencil, boundary):
     return L.GRID_STENCILS[stencil], L.GRID_BOUNDARIES[boundary]
 
 
-def grid_pattern(nx: int, ny: int, dof: int = 1, stencil: str = "star", boundary: str = "dirichlet"):
+def grid_pattern(nx: int, ny: int, dof: int = 1, stencil: str = "star", boundary: str = "dirichlet", *, nz: Optional[int] = None):
     """(rowptr, colind), int32, of the Jacobian of a compiled grid problem: columns ascending within a row, every
-    (stencil point in the domain) × (component) entry kept. Host only."""
+    (stencil point in the domain) × (component) entry kept. Host only. With nz: the nx × ny × nz grid (7-point star or
+    27-point box)."""
     st, bd = _grid_ids(stencil, boundary)
     nnz = C.c_int64()
-    check(L.lib().nk_grid_pattern(nx, ny, dof, st, bd, None, None, C.byref(nnz)))
-    rowptr, colind = np.empty(dof * nx * ny + 1, dtype=np.int32), np.empty(nnz.value, dtype=np.int32)
-    check(L.lib().nk_grid_pattern(nx, ny, dof, st, bd, C.c_void_p(rowptr.ctypes.data), C.c_void_p(colind.ctypes.data),
-                                  C.byref(nnz)))
+    if nz is None:
+        def pattern(rp, ci):
+            return L.lib().nk_grid_pattern(nx, ny, dof, st, bd, rp, ci, C.byref(nnz))
+    else:
+        def pattern(rp, ci):
+            return L.lib().nk_grid3_pattern(nx, ny, nz, dof, st, bd, rp, ci, C.byref(nnz))
+    check(pattern(None, None))
+    rowptr = np.empty(dof * nx * ny * (1 if nz is None else nz) + 1, dtype=np.int32)
+    colind = np.empty(nnz.value, dtype=np.int32)
+    check(pattern(C.c_void_p(rowptr.ctypes.data), C.c_void_p(colind.ctypes.data)))
     return rowptr, colind
 
 
-def grid_compile_check(source: str, dof: int = 1, stencil: str = "star", boundary: str = "dirichlet", nparams: int = 0) -> int:
+def grid_compile_check(source: str, dof: int = 1, stencil: str = "star", boundary: str = "dirichlet", nparams: int = 0, *,
+                       dim: int = 2) -> int:
     """Compile the residual, JVP and Jacobian kernels of `source` for gfx950 (no device needed); the size of the code objects.
-    A source that does not compile raises NKError with the contract and the compiler's log."""
+    A source that does not compile raises NKError with the contract and the compiler's log. dim = 3: the 3-D contract
+    (nk_nbhd3, nk_site3)."""
+    if dim not in (2, 3):
+        raise ValueError(f"dim = {dim!r}: expected 2 or 3")
     st, bd = _grid_ids(stencil, boundary)
     nb = C.c_int64()
-    check(L.lib().nk_grid_compile_check(source.encode(), dof, st, bd, nparams, C.byref(nb)))
+    fn = L.lib().nk_grid3_compile_check if dim == 3 else L.lib().nk_grid_compile_check
+    check(fn(source.encode(), dof, st, bd, nparams, C.byref(nb)))
     return nb.value
 
 
@@ -525,20 +537,28 @@ class _GridDeviceProblem(DeviceProblem):
 
 
 def CompiledGridProblem(source: str, nx: int, ny: int, dof: int = 1, stencil: str = "star", boundary: str = "dirichlet",
-                        params: Sequence[float] = (), ctx=None) -> DeviceProblem:
+                        params: Sequence[float] = (), ctx=None, *, nz: Optional[int] = None) -> DeviceProblem:
     """A residual given pointwise on an nx × ny grid through a radius-1 stencil, as HIP source
         template <typename T> __device__ void nk_point(const nk_nbhd<T> &u, const nk_real *p, nk_site s, T *f);
     compiled (hiprtc, gfx950) into the residual kernel, the exact dual-number JVP kernel and the Jacobian fill on the stencil's
     CSR pattern (include/mi355x_nk.h, "compiled grid problems"). u0 defaults to zeros; NonlinearProblem(..., p) and
-    reinit_(cache, p=...) replace the source's p[0..nparams). dof <= 4 (box: <= 2), Float64, one rank."""
+    reinit_(cache, p=...) replace the source's p[0..nparams). dof <= 4 (box: <= 2), Float64, one rank.
+    With nz the grid is nx × ny × nz and the source follows the 3-D contract
+        template <typename T> __device__ void nk_point(const nk_nbhd3<T> &u, const nk_real *p, nk_site3 s, T *f);
+    with u(di, dj, dk, c): the 7-point star (dof <= 4) or the 27-point box (dof = 1)."""
     ctx = ctx or default_context()
     st, bd = _grid_ids(stencil, boundary)
     params = [float(x) for x in params]
     arr = (C.c_double * max(len(params), 1))(*params)
     h = C.c_void_p()
-    check(L.lib().nk_problem_create_grid(ctx._h, source.encode(), nx, ny, dof, st, bd, arr, len(params), C.byref(h)))
+    if nz is None:
+        check(L.lib().nk_problem_create_grid(ctx._h, source.encode(), nx, ny, dof, st, bd, arr, len(params), C.byref(h)))
+    else:
+        check(L.lib().nk_problem_create_grid3(ctx._h, source.encode(), nx, ny, nz, dof, st, bd, arr, len(params), C.byref(h)))
     P = _GridDeviceProblem(h, ctx)
     P.p, P.nx, P.ny, P.dof, P.stencil, P.boundary = params, nx, ny, dof, stencil, boundary
+    if nz is not None:
+        P.nz = nz
     return P
 
 

@@ -24,6 +24,12 @@
 // are missing. Each thread counts, for every stencil point, the in-domain points with a smaller node index (npts² integer
 // compares on registers) instead of reading a per-node slot table: the fill is bound by its 8·nnz bytes of stores, and a table
 // would add npts bytes per node to the stream for something 25 (81) compares give.
+//
+// Three dimensions (nk_problem_create_grid3): the same three kernels over nk_nbhd3<T> / nk_site3 = {i, j, k, nx, ny, nz} —
+// nk_grid3_residual, nk_grid3_jvp, nk_grid3_jac — from source strings of their own, so the 2-D programs are compiled from the
+// text and the options they always had. 7-point star (dof 1..4) or 27-point box (dof 1): at most 28 partials per row, and the
+// staged fill's LDS is at most 256·28 doubles (57344 bytes). Unknown c of node (i, j, k) is element c·nn + (k·ny + j)·nx + i;
+// the flat 256-thread workgroups walk that order, so a wavefront still loads 64 consecutive doubles per stencil point.
 #include <math.h>
 #include <string.h>
 
@@ -223,6 +229,206 @@ static const char *k_grid_contract =
     "with u(di, dj, c) the component c at node (i + di, j + dj), s = {i, j, nx, ny}, p the parameters and f the node's dof "
     "residuals (nk_real = double)";
 
+// ----------------------------------------------------------------------------- device source, three dimensions
+static const char *k_grid3_types = R"NKSRC(
+// ---- compiled grid problems in 3-D: the node's position and its neighbourhood
+#if NK_BOX
+#define NK_NPTS 27
+#else
+#define NK_NPTS 7
+#endif
+struct nk_site3 { int i, j, k, nx, ny, nz; };
+// stencil point q → offset; q ascends with the node index ((k·ny + j)·nx + i) of the point inside the grid:
+// star (0,0,−1) (0,−1,0) (−1,0,0) C (1,0,0) (0,1,0) (0,0,1); box plane by plane, row by row (dk outermost, di innermost)
+__device__ constexpr int nk_pt_di(int q) { return NK_BOX ? q % 3 - 1 : (q == 2 ? -1 : (q == 4 ? 1 : 0)); }
+__device__ constexpr int nk_pt_dj(int q) { return NK_BOX ? (q / 3) % 3 - 1 : (q == 1 ? -1 : (q == 5 ? 1 : 0)); }
+__device__ constexpr int nk_pt_dk(int q) { return NK_BOX ? q / 9 - 1 : (q == 0 ? -1 : (q == 6 ? 1 : 0)); }
+template <typename T>
+struct nk_nbhd3 {
+  T val[NK_NPTS * NK_DOF];
+  // component c at node (i + di, j + dj, k + dk); di, dj, dk ∈ {−1, 0, 1} (compile-time constants keep val in registers)
+  __device__ __forceinline__ T operator()(int di, int dj, int dk, int c = 0) const {
+#if NK_BOX
+    return val[(((dk + 1) * 3 + (dj + 1)) * 3 + (di + 1)) * NK_DOF + c];
+#else
+    // the star has neither edges nor corners: a wrong source shows at once
+    if ((di != 0) + (dj != 0) + (dk != 0) > 1) return T(NK_R(__builtin_nan("")));
+    return val[(dk != 0 ? 3 + 3 * dk : (dj != 0 ? 3 + 2 * dj : 3 + di)) * NK_DOF + c];
+#endif
+  }
+};
+)NKSRC";
+
+static const char *k_grid3_kernels = R"NKSRC(
+// ---- generated kernels: one node per thread
+#define NK_GRID_BLOCK 256
+// node index of every stencil point (clamped to the node itself outside a Dirichlet boundary, wrapped at a periodic one) and
+// whether the point is in the domain
+__device__ __forceinline__ void nk_grid3_geom(int i, int j, int k, int nx, int ny, int nz, int (&idx)[NK_NPTS],
+                                              bool (&in)[NK_NPTS]) {
+#pragma unroll
+  for (int q = 0; q < NK_NPTS; ++q) {
+    int ii = i + nk_pt_di(q), jj = j + nk_pt_dj(q), kk = k + nk_pt_dk(q);
+#if NK_PERIODIC
+    ii = ii < 0 ? nx - 1 : (ii >= nx ? 0 : ii);
+    jj = jj < 0 ? ny - 1 : (jj >= ny ? 0 : jj);
+    kk = kk < 0 ? nz - 1 : (kk >= nz ? 0 : kk);
+    in[q] = true;
+#else
+    in[q] = ii >= 0 && ii < nx && jj >= 0 && jj < ny && kk >= 0 && kk < nz;
+    ii = in[q] ? ii : i;
+    jj = in[q] ? jj : j;
+    kk = in[q] ? kk : k;
+#endif
+    idx[q] = (kk * ny + jj) * nx + ii;
+  }
+}
+// node → (i, j, k): node = (k·ny + j)·nx + i
+#define NK_GRID3_SITE(node)                                                      \
+  const int k = (int)((unsigned)(node) / (unsigned)(nx * ny));                   \
+  const int rem_ = (node) - k * (nx * ny);                                       \
+  const int j = (int)((unsigned)rem_ / (unsigned)nx), i = rem_ - j * nx
+
+#if NK_GRID_SET == 0
+extern "C" __global__ void __launch_bounds__(NK_GRID_BLOCK)
+nk_grid3_residual(int nx, int ny, int nz, const nk_real *__restrict__ p, const nk_real *__restrict__ u,
+                  nk_real *__restrict__ f) {
+  const int nn = nx * ny * nz, node = (int)blockIdx.x * NK_GRID_BLOCK + (int)threadIdx.x;
+  if (node >= nn) return;
+  NK_GRID3_SITE(node);
+  int idx[NK_NPTS];
+  bool in[NK_NPTS];
+  nk_grid3_geom(i, j, k, nx, ny, nz, idx, in);
+  nk_nbhd3<nk_real> nb;
+#pragma unroll
+  for (int q = 0; q < NK_NPTS; ++q) {
+#pragma unroll
+    for (int c = 0; c < NK_DOF; ++c) {
+      const nk_real x = u[c * nn + idx[q]];
+      nb.val[q * NK_DOF + c] = in[q] ? x : NK_R(0);
+    }
+  }
+  nk_real out[NK_DOF];
+#pragma unroll
+  for (int c = 0; c < NK_DOF; ++c) out[c] = NK_R(0);
+  const nk_site3 s = {i, j, k, nx, ny, nz};
+  nk_point<nk_real>(nb, p, s, out);
+#pragma unroll
+  for (int c = 0; c < NK_DOF; ++c) f[c * nn + node] = out[c];
+}
+
+// J(u)·v exactly: the value of every neighbour from u, its one partial from v
+extern "C" __global__ void __launch_bounds__(NK_GRID_BLOCK)
+nk_grid3_jvp(int nx, int ny, int nz, const nk_real *__restrict__ p, const nk_real *__restrict__ u,
+             const nk_real *__restrict__ v, nk_real *__restrict__ jv) {
+  const int nn = nx * ny * nz, node = (int)blockIdx.x * NK_GRID_BLOCK + (int)threadIdx.x;
+  if (node >= nn) return;
+  NK_GRID3_SITE(node);
+  int idx[NK_NPTS];
+  bool in[NK_NPTS];
+  nk_grid3_geom(i, j, k, nx, ny, nz, idx, in);
+  nk_nbhd3<Dual> nb;
+#pragma unroll
+  for (int q = 0; q < NK_NPTS; ++q) {
+#pragma unroll
+    for (int c = 0; c < NK_DOF; ++c) {
+      const nk_real x = u[c * nn + idx[q]], d = v[c * nn + idx[q]];
+      nb.val[q * NK_DOF + c].v = in[q] ? x : NK_R(0);
+      nb.val[q * NK_DOF + c].d[0] = in[q] ? d : NK_R(0);
+    }
+  }
+  Dual out[NK_DOF];
+#pragma unroll
+  for (int c = 0; c < NK_DOF; ++c) out[c] = Dual(NK_R(0));
+  const nk_site3 s = {i, j, k, nx, ny, nz};
+  nk_point<Dual>(nb, p, s, out);
+#pragma unroll
+  for (int c = 0; c < NK_DOF; ++c) jv[c * nn + node] = out[c].d[0];
+}
+#else
+// The values of J(u) on the stencil's CSR pattern (ascending columns): slot q·dof + c of the duals carries ∂/∂u_c(point q).
+// Row c·nn + node holds, for c' = 0 … dof−1, its in-domain points in ascending node order: position c'·cnt + rank[q].
+// NK_GRID_DIRECT = 0: the workgroup's rows of one component are one contiguous piece of the value array — they are put together
+// in LDS and stored as whole lines; 1: every thread stores its own partials, 8 bytes at a stride of a row.
+extern "C" __global__ void __launch_bounds__(NK_GRID_BLOCK)
+nk_grid3_jac(int nx, int ny, int nz, const nk_real *__restrict__ p, const nk_real *__restrict__ u,
+             const int *__restrict__ rowptr, nk_real *__restrict__ vals) {
+  const int nn = nx * ny * nz, node0 = (int)blockIdx.x * NK_GRID_BLOCK, node_t = node0 + (int)threadIdx.x;
+  if (node0 >= nn) return;   // (a workgroup past the grid; the launch has none)
+  const bool live = node_t < nn;
+#if NK_GRID_DIRECT
+  if (!live) return;
+#else
+  __shared__ nk_real sv[NK_GRID_BLOCK * NK_NPTS * NK_DOF];   // (at most 256·28 doubles: the star at dof 4)
+#endif
+  const int node = live ? node_t : nn - 1;   // (past the end: the last node again, nothing of it is kept)
+  NK_GRID3_SITE(node);
+  int idx[NK_NPTS];
+  bool in[NK_NPTS];
+  nk_grid3_geom(i, j, k, nx, ny, nz, idx, in);
+  nk_nbhd3<Dual> nb;
+#pragma unroll
+  for (int q = 0; q < NK_NPTS; ++q) {
+#pragma unroll
+    for (int c = 0; c < NK_DOF; ++c) {
+      const nk_real x = u[c * nn + idx[q]];
+      nb.val[q * NK_DOF + c].v = in[q] ? x : NK_R(0);
+#pragma unroll
+      for (int t = 0; t < NK_CH; ++t) nb.val[q * NK_DOF + c].d[t] = (t == q * NK_DOF + c) ? NK_R(1) : NK_R(0);
+    }
+  }
+  Dual out[NK_DOF];
+#pragma unroll
+  for (int c = 0; c < NK_DOF; ++c) out[c] = Dual(NK_R(0));
+  const nk_site3 s = {i, j, k, nx, ny, nz};
+  nk_point<Dual>(nb, p, s, out);
+  int rank[NK_NPTS], cnt = 0;
+#pragma unroll
+  for (int q = 0; q < NK_NPTS; ++q) {
+    int r = 0;
+#pragma unroll
+    for (int t = 0; t < NK_NPTS; ++t) r += (in[t] && idx[t] < idx[q]) ? 1 : 0;
+    rank[q] = r;
+    cnt += in[q] ? 1 : 0;
+  }
+#pragma unroll
+  for (int c = 0; c < NK_DOF; ++c) {
+    const int base = rowptr[c * nn + node];
+#if NK_GRID_DIRECT
+#pragma unroll
+    for (int q = 0; q < NK_NPTS; ++q) {
+      if (in[q]) {
+#pragma unroll
+        for (int c2 = 0; c2 < NK_DOF; ++c2) vals[base + c2 * cnt + rank[q]] = out[c].d[q * NK_DOF + c2];
+      }
+    }
+#else
+    // this workgroup's piece of component c: [p0, p1) ⊂ [0, nnz), at most NK_GRID_BLOCK·npts·dof values
+    const int last = node0 + NK_GRID_BLOCK < nn ? node0 + NK_GRID_BLOCK : nn;
+    const int p0 = rowptr[c * nn + node0], p1 = rowptr[c * nn + last];
+    if (live) {
+#pragma unroll
+      for (int q = 0; q < NK_NPTS; ++q) {
+        if (in[q]) {
+#pragma unroll
+          for (int c2 = 0; c2 < NK_DOF; ++c2) sv[base - p0 + c2 * cnt + rank[q]] = out[c].d[q * NK_DOF + c2];
+        }
+      }
+    }
+    __syncthreads();
+    for (int t = (int)threadIdx.x; t < p1 - p0; t += NK_GRID_BLOCK) vals[p0 + t] = sv[t];
+    __syncthreads();
+#endif
+  }
+}
+#endif
+)NKSRC";
+
+static const char *k_grid3_contract =
+    "the contract is `template <typename T> __device__ void nk_point(const nk_nbhd3<T> &u, const nk_real *p, nk_site3 s, T *f)` "
+    "with u(di, dj, dk, c) the component c at node (i + di, j + dj, k + dk), s = {i, j, k, nx, ny, nz}, p the parameters and f "
+    "the node's dof residuals (nk_real = double)";
+
 // ----------------------------------------------------------------------------- the stencil's CSR pattern (host only)
 static int grid_check_shape(int dof, int stencil, int boundary) {
   NK_REQUIRE(stencil == NK_GRID_STAR || stencil == NK_GRID_BOX, "stencil = %d is neither NK_GRID_STAR nor NK_GRID_BOX", stencil);
@@ -277,22 +483,84 @@ extern "C" int nk_grid_pattern(int64_t nx, int64_t ny, int dof, int stencil, int
   return NK_OK;
 }
 
+// three dimensions: the 7-point star with dof 1..4, the 27-point box with dof 1 — at most 28 partials per row
+static int grid3_check_shape(int dof, int stencil, int boundary) {
+  NK_REQUIRE(stencil == NK_GRID_STAR || stencil == NK_GRID_BOX, "stencil = %d is neither NK_GRID_STAR nor NK_GRID_BOX", stencil);
+  NK_REQUIRE(boundary == NK_GRID_DIRICHLET0 || boundary == NK_GRID_PERIODIC,
+             "boundary = %d is neither NK_GRID_DIRICHLET0 nor NK_GRID_PERIODIC", boundary);
+  NK_REQUIRE(dof >= 1 && dof <= 4, "dof = %d outside 1..4 (components per grid node)", dof);
+  NK_REQUIRE(stencil != NK_GRID_BOX || dof == 1, "dof = %d with the box stencil: the 27-point box is offered for dof = 1 "
+             "(a row has at most 28 partials)", dof);
+  return NK_OK;
+}
+static inline int grid3_pt_di(int stencil, int q) { return stencil == NK_GRID_BOX ? q % 3 - 1 : (q == 2 ? -1 : (q == 4 ? 1 : 0)); }
+static inline int grid3_pt_dj(int stencil, int q) { return stencil == NK_GRID_BOX ? (q / 3) % 3 - 1 : (q == 1 ? -1 : (q == 5 ? 1 : 0)); }
+static inline int grid3_pt_dk(int stencil, int q) { return stencil == NK_GRID_BOX ? q / 9 - 1 : (q == 0 ? -1 : (q == 6 ? 1 : 0)); }
+
+extern "C" int nk_grid3_pattern(int64_t nx, int64_t ny, int64_t nz, int dof, int stencil, int boundary, int32_t *rowptr,
+                                int32_t *colind, int64_t *nnz) {
+  NK_REQUIRE(rowptr || nnz, "NULL argument");
+  NK_TRY(grid3_check_shape(dof, stencil, boundary));
+  NK_REQUIRE(nx >= 3 && ny >= 3 && nz >= 3, "grid %lld x %lld x %lld: a radius-1 stencil needs nx >= 3, ny >= 3 and nz >= 3 "
+             "(three distinct columns per direction at a periodic edge)", (long long)nx, (long long)ny, (long long)nz);
+  const int npts = stencil == NK_GRID_BOX ? 27 : 7;
+  NK_REQUIRE(nx <= INT32_MAX / ny && nx * ny <= INT32_MAX / nz && nx * ny * nz <= (int64_t)INT32_MAX / (dof * npts * dof),
+             "grid %lld x %lld x %lld with dof = %d: the pattern's 32-bit indices cannot hold it", (long long)nx, (long long)ny,
+             (long long)nz, dof);
+  const int64_t nn = nx * ny * nz;
+  int64_t pos = 0;
+  for (int c = 0; c < dof; ++c)
+    for (int64_t k = 0; k < nz; ++k)
+      for (int64_t j = 0; j < ny; ++j)
+        for (int64_t i = 0; i < nx; ++i) {
+          int64_t nb[27];
+          int cnt = 0;
+          for (int q = 0; q < npts; ++q) {
+            int64_t ii = i + grid3_pt_di(stencil, q), jj = j + grid3_pt_dj(stencil, q), kk = k + grid3_pt_dk(stencil, q);
+            if (boundary == NK_GRID_PERIODIC) {
+              ii = ii < 0 ? nx - 1 : (ii >= nx ? 0 : ii);
+              jj = jj < 0 ? ny - 1 : (jj >= ny ? 0 : jj);
+              kk = kk < 0 ? nz - 1 : (kk >= nz ? 0 : kk);
+            } else if (ii < 0 || ii >= nx || jj < 0 || jj >= ny || kk < 0 || kk >= nz) {
+              continue;
+            }
+            // insertion keeps the node indices ascending (wrap-around reorders the points at a periodic edge)
+            const int64_t m = (kk * ny + jj) * nx + ii;
+            int t = cnt++;
+            while (t > 0 && nb[t - 1] > m) { nb[t] = nb[t - 1]; --t; }
+            nb[t] = m;
+          }
+          if (rowptr) rowptr[c * nn + (k * ny + j) * nx + i] = (int32_t)pos;
+          if (colind)
+            for (int c2 = 0; c2 < dof; ++c2)
+              for (int t = 0; t < cnt; ++t) colind[pos + (int64_t)c2 * cnt + t] = (int32_t)(c2 * nn + nb[t]);
+          pos += (int64_t)cnt * dof;
+        }
+  if (rowptr) rowptr[dof * nn] = (int32_t)pos;
+  if (nnz) *nnz = pos;
+  return NK_OK;
+}
+
 // ----------------------------------------------------------------------------- compilation
 enum { GSET_F = 0 /* nk_grid_residual + nk_grid_jvp, NK_CH = 1 */, GSET_JAC = 1 /* nk_grid_jac, NK_CH = npts·dof */ };
 
-static int grid_compile(const char *source, int dof, int stencil, int boundary, int np, int gset, bool direct,
+// dim = 2: nk_grid_residual / nk_grid_jvp / nk_grid_jac; dim = 3: the nk_grid3_ kernels. The 3-D programs carry -DNK_DIM=3 (it
+// tells their cache entries from the 2-D ones of the same source); the 2-D programs get the text and the options they always had.
+static int grid_compile(const char *source, int dim, int dof, int stencil, int boundary, int np, int gset, bool direct,
                         std::vector<char> *code, std::string *log) {
   NK_REQUIRE(source, "NULL source");
-  NK_TRY(grid_check_shape(dof, stencil, boundary));
+  NK_TRY(dim == 3 ? grid3_check_shape(dof, stencil, boundary) : grid_check_shape(dof, stencil, boundary));
   NK_REQUIRE(np >= 0 && np <= 32, "nparams = %d outside 0..32", np);
-  const int npts = stencil == NK_GRID_BOX ? 9 : 5;
-  const std::string full = std::string(nk_dual_prelude) + k_grid_types + "\n// ---- user source\n" + source + "\n" + k_grid_kernels;
+  const int npts = dim == 3 ? (stencil == NK_GRID_BOX ? 27 : 7) : (stencil == NK_GRID_BOX ? 9 : 5);
+  const std::string full = std::string(nk_dual_prelude) + (dim == 3 ? k_grid3_types : k_grid_types) + "\n// ---- user source\n" +
+                           source + "\n" + (dim == 3 ? k_grid3_kernels : k_grid_kernels);
   const std::string dd = "-DNK_DOF=" + std::to_string(dof), db = std::string("-DNK_BOX=") + (stencil == NK_GRID_BOX ? "1" : "0"),
                     dp = std::string("-DNK_PERIODIC=") + (boundary == NK_GRID_PERIODIC ? "1" : "0"),
                     dc = "-DNK_CH=" + std::to_string(gset == GSET_JAC ? npts * dof : 1), ds = "-DNK_GRID_SET=" + std::to_string(gset),
                     dr = std::string("-DNK_GRID_DIRECT=") + (direct ? "1" : "0");
-  const std::vector<const char *> opts = {"--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-std=c++17", dd.c_str(), db.c_str(),
-                                          dp.c_str(), dc.c_str(), ds.c_str(), dr.c_str()};
+  std::vector<const char *> opts = {"--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-std=c++17", dd.c_str(), db.c_str(),
+                                    dp.c_str(), dc.c_str(), ds.c_str(), dr.c_str()};
+  if (dim == 3) opts.push_back("-DNK_DIM=3");
   // the same source with the same options gives the same code object: problems created again (another grid size, another
   // context) skip the compiler
   static std::mutex mtx;
@@ -309,7 +577,7 @@ static int grid_compile(const char *source, int dof, int stencil, int boundary, 
   bool failed = false;
   NK_TRY(nk_rtc_compile(full, "nk_grid_user.hip", opts, code, log, &failed));
   if (failed)
-    NK_FAIL(NK_E_INVALID, "grid residual source does not compile (%s): %.900s", k_grid_contract,
+    NK_FAIL(NK_E_INVALID, "grid residual source does not compile (%s): %.900s", dim == 3 ? k_grid3_contract : k_grid_contract,
             log && !log->empty() ? log->c_str() : "(no log)");
   std::lock_guard<std::mutex> lock(mtx);
   cache[key] = *code;
@@ -323,37 +591,51 @@ static bool grid_fill_direct() {   // (read at every create: tools/grid_problem_
 }
 
 // compile only (no device needed): both programs
-extern "C" int nk_grid_compile_check(const char *source, int dof, int stencil, int boundary, int nparams, int64_t *code_bytes) {
+static int grid_compile_check(const char *source, int dim, int dof, int stencil, int boundary, int nparams, int64_t *code_bytes) {
   std::vector<char> code;
   std::string log;
   int64_t total = 0;
   for (int gset : {GSET_F, GSET_JAC}) {
     log.clear();
-    NK_TRY(grid_compile(source, dof, stencil, boundary, nparams, gset, grid_fill_direct(), &code, &log));
+    NK_TRY(grid_compile(source, dim, dof, stencil, boundary, nparams, gset, grid_fill_direct(), &code, &log));
     total += (int64_t)code.size();
   }
   if (code_bytes) *code_bytes = total;
   return NK_OK;
 }
+extern "C" int nk_grid_compile_check(const char *source, int dof, int stencil, int boundary, int nparams, int64_t *code_bytes) {
+  return grid_compile_check(source, 2, dof, stencil, boundary, nparams, code_bytes);
+}
+extern "C" int nk_grid3_compile_check(const char *source, int dof, int stencil, int boundary, int nparams, int64_t *code_bytes) {
+  return grid_compile_check(source, 3, dof, stencil, boundary, nparams, code_bytes);
+}
 
-// the code object of one program (jac = 0: nk_grid_residual and nk_grid_jvp; 1: nk_grid_jac) for inspection
-extern "C" int nk_grid_code_object(const char *source, int dof, int stencil, int boundary, int nparams, int jac, void *buf,
-                                   int64_t capacity, int64_t *bytes) {
+// the code object of one program (jac = 0: the residual and JVP kernels; 1: the Jacobian fill) for inspection
+static int grid_code_object(const char *source, int dim, int dof, int stencil, int boundary, int nparams, int jac, void *buf,
+                            int64_t capacity, int64_t *bytes) {
   NK_REQUIRE(bytes, "NULL argument");
   std::vector<char> code;
   std::string log;
-  NK_TRY(grid_compile(source, dof, stencil, boundary, nparams, jac != 0 ? GSET_JAC : GSET_F, grid_fill_direct(), &code, &log));
+  NK_TRY(grid_compile(source, dim, dof, stencil, boundary, nparams, jac != 0 ? GSET_JAC : GSET_F, grid_fill_direct(), &code, &log));
   *bytes = (int64_t)code.size();
   if (!buf) return NK_OK;
   NK_REQUIRE(capacity >= *bytes, "buffer of %lld bytes, the code object has %lld", (long long)capacity, (long long)*bytes);
   memcpy(buf, code.data(), code.size());
   return NK_OK;
 }
+extern "C" int nk_grid_code_object(const char *source, int dof, int stencil, int boundary, int nparams, int jac, void *buf,
+                                   int64_t capacity, int64_t *bytes) {
+  return grid_code_object(source, 2, dof, stencil, boundary, nparams, jac, buf, capacity, bytes);
+}
+extern "C" int nk_grid3_code_object(const char *source, int dof, int stencil, int boundary, int nparams, int jac, void *buf,
+                                    int64_t capacity, int64_t *bytes) {
+  return grid_code_object(source, 3, dof, stencil, boundary, nparams, jac, buf, capacity, bytes);
+}
 
 // ----------------------------------------------------------------------------- the problem object
 struct nk_grid_state {
   nk_ctx *ctx = nullptr;
-  int nx = 0, ny = 0, dof = 0, np = 0;
+  int nx = 0, ny = 0, nz = 0 /* 0: a 2-D problem */, dof = 0, np = 0;
   hipModule_t mod_f = nullptr, mod_jac = nullptr;
   hipFunction_t fn_res = nullptr, fn_jvp = nullptr, fn_jac = nullptr;
   double *d_params = nullptr;   // np doubles (at least one allocated): the source's p
@@ -373,7 +655,7 @@ void nk_grid_state_destroy(nk_grid_state *S) {
 // nk_problem_jvp_dev and nk_problem_jac_values_dev open one around the callback) the launch carries start / stop events like
 // every NK_LAUNCH, so the generated kernels are timed by the same clock as the built-in ones.
 static int grid_launch(nk_grid_state *S, hipFunction_t fn, void **args, void *stream) {
-  const unsigned blocks = (unsigned)(((int64_t)S->nx * S->ny + 255) / 256);
+  const unsigned blocks = (unsigned)(((int64_t)S->nx * S->ny * (S->nz > 0 ? S->nz : 1) + 255) / 256);
   hipEvent_t e0, e1;
   hipError_t e;
   if (S->ctx->prof.on && (hipStream_t)stream == S->ctx->stream && nk_prof_next(S->ctx, &e0, &e1))
@@ -386,19 +668,20 @@ static int grid_launch(nk_grid_state *S, hipFunction_t fn, void **args, void *st
 // the callbacks of the problem: launches of the generated kernels on the stream they are handed
 static int grid_cb_residual(void *user, const double *u, double *f, void *stream) {
   nk_grid_state *S = (nk_grid_state *)user;
-  void *args[] = {&S->nx, &S->ny, &S->d_params, &u, &f};
-  return grid_launch(S, S->fn_res, args, stream);
+  void *args[] = {&S->nx, &S->ny, &S->d_params, &u, &f}, *args3[] = {&S->nx, &S->ny, &S->nz, &S->d_params, &u, &f};
+  return grid_launch(S, S->fn_res, S->nz > 0 ? args3 : args, stream);
 }
 static int grid_cb_jvp(void *user, const double *v, const double *u, double *jv, void *stream) {
   nk_grid_state *S = (nk_grid_state *)user;
-  void *args[] = {&S->nx, &S->ny, &S->d_params, &u, &v, &jv};
-  return grid_launch(S, S->fn_jvp, args, stream);
+  void *args[] = {&S->nx, &S->ny, &S->d_params, &u, &v, &jv}, *args3[] = {&S->nx, &S->ny, &S->nz, &S->d_params, &u, &v, &jv};
+  return grid_launch(S, S->fn_jvp, S->nz > 0 ? args3 : args, stream);
 }
 static int grid_cb_jac(void *user, const double *u, double *vals, void *stream) {
   nk_grid_state *S = (nk_grid_state *)user;
   const int32_t *rowptr = S->pattern->d_rowptr;
-  void *args[] = {&S->nx, &S->ny, &S->d_params, &u, &rowptr, &vals};
-  return grid_launch(S, S->fn_jac, args, stream);
+  void *args[] = {&S->nx, &S->ny, &S->d_params, &u, &rowptr, &vals},
+       *args3[] = {&S->nx, &S->ny, &S->nz, &S->d_params, &u, &rowptr, &vals};
+  return grid_launch(S, S->fn_jac, S->nz > 0 ? args3 : args, stream);
 }
 
 int nk_grid_set_params(nk_problem *P, const double *params, int nparams) {
@@ -412,8 +695,10 @@ int nk_grid_set_params(nk_problem *P, const double *params, int nparams) {
   return NK_OK;
 }
 
-extern "C" int nk_problem_create_grid(nk_ctx *ctx, const char *source, int64_t nx, int64_t ny, int dof, int stencil, int boundary,
-                                      const double *params, int nparams, nk_problem **out) {
+// nz = 0: a 2-D problem (nk_problem_create_grid); nz > 0: a 3-D one (nk_problem_create_grid3)
+static int grid_create(nk_ctx *ctx, const char *source, int64_t nx, int64_t ny, int64_t nz, int dof, int stencil, int boundary,
+                       const double *params, int nparams, nk_problem **out) {
+  const int dim = nz > 0 ? 3 : 2;
   NK_REQUIRE(ctx && source && out, "NULL argument");
   NK_REQUIRE(params || nparams == 0, "NULL params with nparams = %d", nparams);
   if (ctx->nranks > 1)
@@ -422,28 +707,33 @@ extern "C" int nk_problem_create_grid(nk_ctx *ctx, const char *source, int64_t n
   NK_HIP(hipSetDevice(ctx->device));
   // the pattern first: it validates the geometry before anything is compiled
   int64_t nnz = 0;
-  NK_TRY(nk_grid_pattern(nx, ny, dof, stencil, boundary, nullptr, nullptr, &nnz));
-  const int64_t n = nx * ny * dof;
+  const auto pattern = [&](int32_t *rowptr, int32_t *colind) {
+    return dim == 3 ? nk_grid3_pattern(nx, ny, nz, dof, stencil, boundary, rowptr, colind, &nnz)
+                    : nk_grid_pattern(nx, ny, dof, stencil, boundary, rowptr, colind, &nnz);
+  };
+  NK_TRY(pattern(nullptr, nullptr));
+  const int64_t n = nx * ny * (dim == 3 ? nz : 1) * dof;
   std::vector<int32_t> rp((size_t)n + 1), ci((size_t)nnz);
-  NK_TRY(nk_grid_pattern(nx, ny, dof, stencil, boundary, rp.data(), ci.data(), &nnz));
+  NK_TRY(pattern(rp.data(), ci.data()));
   std::vector<char> code_f, code_j;
   std::string log;
-  NK_TRY(grid_compile(source, dof, stencil, boundary, nparams, GSET_F, false, &code_f, &log));
+  NK_TRY(grid_compile(source, dim, dof, stencil, boundary, nparams, GSET_F, false, &code_f, &log));
   log.clear();
-  NK_TRY(grid_compile(source, dof, stencil, boundary, nparams, GSET_JAC, grid_fill_direct(), &code_j, &log));
+  NK_TRY(grid_compile(source, dim, dof, stencil, boundary, nparams, GSET_JAC, grid_fill_direct(), &code_j, &log));
 
   nk_grid_state *S = new nk_grid_state();
   auto guard = nk_make_guard(S, nk_grid_state_destroy);
   S->ctx = ctx;
   S->nx = (int)nx;
   S->ny = (int)ny;
+  S->nz = dim == 3 ? (int)nz : 0;
   S->dof = dof;
   S->np = nparams;
   if (hipModuleLoadData(&S->mod_f, code_f.data()) != hipSuccess || hipModuleLoadData(&S->mod_jac, code_j.data()) != hipSuccess)
     NK_FAIL(NK_E_HIP, "hipModuleLoadData failed");
-  if (hipModuleGetFunction(&S->fn_res, S->mod_f, "nk_grid_residual") != hipSuccess ||
-      hipModuleGetFunction(&S->fn_jvp, S->mod_f, "nk_grid_jvp") != hipSuccess ||
-      hipModuleGetFunction(&S->fn_jac, S->mod_jac, "nk_grid_jac") != hipSuccess)
+  if (hipModuleGetFunction(&S->fn_res, S->mod_f, dim == 3 ? "nk_grid3_residual" : "nk_grid_residual") != hipSuccess ||
+      hipModuleGetFunction(&S->fn_jvp, S->mod_f, dim == 3 ? "nk_grid3_jvp" : "nk_grid_jvp") != hipSuccess ||
+      hipModuleGetFunction(&S->fn_jac, S->mod_jac, dim == 3 ? "nk_grid3_jac" : "nk_grid_jac") != hipSuccess)
     NK_FAIL(NK_E_HIP, "a generated grid kernel is missing from the compiled module");
   NK_TRY(nk_dev_alloc(&S->d_params, (size_t)(nparams > 0 ? nparams : 1)));
   if (nparams > 0) NK_HIP(nk_memcpy(ctx, S->d_params, params, (size_t)nparams * sizeof(double), hipMemcpyHostToDevice));
@@ -466,4 +756,17 @@ extern "C" int nk_problem_create_grid(nk_ctx *ctx, const char *source, int64_t n
   P->grid = guard.release();
   *out = P;
   return NK_OK;
+}
+
+extern "C" int nk_problem_create_grid(nk_ctx *ctx, const char *source, int64_t nx, int64_t ny, int dof, int stencil, int boundary,
+                                      const double *params, int nparams, nk_problem **out) {
+  return grid_create(ctx, source, nx, ny, 0, dof, stencil, boundary, params, nparams, out);
+}
+
+extern "C" int nk_problem_create_grid3(nk_ctx *ctx, const char *source, int64_t nx, int64_t ny, int64_t nz, int dof, int stencil,
+                                       int boundary, const double *params, int nparams, nk_problem **out) {
+  // (grid_create tells the dimensions apart by nz > 0: a side below 3 must not fall through to the 2-D path)
+  NK_REQUIRE(nz >= 3, "grid %lld x %lld x %lld: a radius-1 stencil needs nx >= 3, ny >= 3 and nz >= 3 (three distinct columns "
+             "per direction at a periodic edge)", (long long)nx, (long long)ny, (long long)nz);
+  return grid_create(ctx, source, nx, ny, nz, dof, stencil, boundary, params, nparams, out);
 }

@@ -11,6 +11,13 @@ Then bench.py's protocol — NewtonRaphson, exactly 30 Arnoldi steps of GMRES(30
 and on the concrete Jacobian, on both problems: `--steps` timed steps after `--warmup`, three runs each, alternating.
 
     python tools/grid_problem_bench.py [--out profiles/grid_problem_bench.txt] [--grid 1024] [--reps 200] [--steps 300]
+
+`--dim 3` measures the 3-D generated kernels instead (nk_grid3_residual, nk_grid3_jvp, nk_grid3_jac in both forms of the fill):
+the bratu3 source of tests/grid3_reference.py at `--grid3`³ (256³ = 16.8 M unknowns), the 27-point box3 source at `--box3`³,
+and as the yardstick the 2-D Bratu source at `--grid2`² (4096², the same unknown count) — same process, same protocol, the
+problems alternating. Fill bytes are 8 nnz + (8 dof + 4) n: the values, u and the row pointer.
+
+    python tools/grid_problem_bench.py --dim 3 [--out profiles/grid3_problem_bench.txt] [--grid3 256] [--box3 160] [--grid2 4096]
 """
 import argparse
 import os
@@ -57,14 +64,81 @@ def steps_per_second(make_problem, u0, concrete, steps, warmup):
     return steps / dt, fn
 
 
+def main3(args):
+    """the 3-D kernels beside the 2-D generated kernels at equal unknowns"""
+    import grid3_reference as R3
+    ctx = nls.default_context()
+    g3, b3, g2 = args.grid3, args.box3, args.grid2
+    cases = [   # label, source, (nx, ny, nz), stencil, parameters
+        (f"2-D bratu {g2}^2", R.BRATU_SRC, (g2, g2, None), "star", R.bratu_params(g2, 6.0)),
+        (f"bratu3 {g3}^3", R3.BRATU3_SRC, (g3, g3, g3), "star", R3.bratu3_params(g3, 3.0)),
+        (f"box3 {b3}^3", R3.BOX3_SRC, (b3, b3, b3), "box", R3.BOX3_PARAMS),
+    ]
+    gen = torch.Generator(device="cuda").manual_seed(1)
+    calls, meta, problems, sizes = {}, {}, [], []   # meta: label → (kind rank, algorithmic bytes, unknowns)
+    for label, src, (nx, ny, nz), stencil, par in cases:
+        P = nls.CompiledGridProblem(src, nx, ny, stencil=stencil, params=par, nz=nz)
+        os.environ["NK_GRID_FILL_DIRECT"] = "1"
+        Pd = nls.CompiledGridProblem(src, nx, ny, stencil=stencil, params=par, nz=nz)
+        del os.environ["NK_GRID_FILL_DIRECT"]
+        n = P.n_local
+        u = 2.0 * torch.rand(n, dtype=torch.float64, device="cuda", generator=gen) - 1.0
+        v = 2.0 * torch.rand(n, dtype=torch.float64, device="cuda", generator=gen) - 1.0
+        J, Jd = P.jac_csr(), Pd.jac_csr()
+        nnz = J.info()["nnz"]
+        # the fill agrees with the dual JVP, and its two forms with each other, before anything is timed
+        P.jac_values(u, J)
+        Pd.jac_values(u, Jd)
+        jv = P.jvp(v, u)
+        assert float((J.matvec(v) - jv).abs().max()) <= 1e-10 * max(1.0, float(jv.abs().max()))
+        assert torch.equal(J.matvec(v), Jd.matvec(v))
+        sizes.append(f"{label}: n = {n}, nnz = {nnz} ({nnz / n:.2f} per row)")
+        kinds = [("residual", lambda P=P, u=u: P.residual(u), "residual", 16.0 * n),
+                 ("JVP", lambda P=P, u=u, v=v: P.jvp(v, u), "jvp", 24.0 * n),
+                 ("fill (LDS-staged rows)", lambda P=P, u=u, J=J: P.jac_values(u, J), "jacfill", 8.0 * nnz + 12.0 * n),
+                 ("fill (direct stores)", lambda Pd=Pd, u=u, Jd=Jd: Pd.jac_values(u, Jd), "jacfill", 8.0 * nnz + 12.0 * n)]
+        for what, fn, fam, b in kinds:
+            calls[f"{what:24s} {label}"] = (fn, fam)
+            meta[f"{what:24s} {label}"] = (("res", "JVP", "fill (L", "fill (d").index(what[:7] if what[:4] == "fill" else what[:3]), b, n)
+        problems += [P, Pd]
+    # (ordered by kernel, so that the 2-D yardstick and the 3-D kernels of one kind alternate)
+    order = sorted(calls, key=lambda k: meta[k][0])
+    ts = kernel_samples(ctx, {k: calls[k] for k in order}, args.reps)
+    lines = [f"Compiled grid problems in 3-D beside the 2-D generated kernels at equal unknowns, {torch.cuda.get_device_name(0)}"] + sizes + [
+             f"kernel begin -> end device timestamps, one launch per sample, problems alternating, {args.reps} samples after 20;",
+             "GB/s on algorithmic bytes: residual 16 n, JVP 24 n, fill 8 nnz + 12 n (dof = 1)", "",
+             f"  {'kernel':44s} {'median us':>10s} {'p10':>9s} {'p90':>9s} {'GB/s (median)':>14s}  {'ns/unknown':>10s}  algorithmic MB"]
+    for label in order:
+        t = ts[label]
+        med = statistics.median(t)
+        _rank, b, n = meta[label]
+        lines.append(f"  {label:44s} {med:10.2f} {t[len(t) // 10]:9.2f} {t[(9 * len(t)) // 10]:9.2f} "
+                     f"{b / med / 1e3:14.1f}  {1e3 * med / n:10.4f}  {b / 1e6:.1f}")
+    text = "\n".join(lines) + "\n"
+    print(text)
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, "w") as f:
+        f.write(text)
+    for PP in problems:
+        PP.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "grid_problem_bench.txt"))
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--dim", type=int, default=2, choices=(2, 3))
+    ap.add_argument("--grid3", type=int, default=256)
+    ap.add_argument("--box3", type=int, default=160)
+    ap.add_argument("--grid2", type=int, default=4096)
     ap.add_argument("--grid", type=int, default=1024)
     ap.add_argument("--reps", type=int, default=200)
     ap.add_argument("--steps", type=int, default=300)
     ap.add_argument("--warmup", type=int, default=20)
     args = ap.parse_args()
+    if args.out is None:
+        args.out = os.path.join(ROOT, "profiles", "grid3_problem_bench.txt" if args.dim == 3 else "grid_problem_bench.txt")
+    if args.dim == 3:
+        return main3(args)
     ns = args.grid
     n, nnz = ns * ns, 5 * ns * ns - 4 * ns
     ctx = nls.default_context()
