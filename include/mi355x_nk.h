@@ -503,14 +503,24 @@ int nk_jac_values_colored(nk_problem *P, const double *u, int memspace, nk_csr *
  * Geometry: nx × ny nodes, nx, ny >= 3 (not necessarily square); dof = 1..4 components per node; stencil NK_GRID_STAR (5 points)
  * or NK_GRID_BOX (9 points, dof <= 2: a row has at most 20 partials); boundary NK_GRID_DIRICHLET0 (a neighbour outside the grid
  * reads as the constant 0 and has no column) or NK_GRID_PERIODIC (indices wrap in both directions). Unknown c of node (i, j) is
- * element c·nx·ny + j·nx + i (the Brusselator's layout). Radius 1 only; one rank only: NK_E_UNSUPPORTED on a context with more.
+ * element c·nx·ny + j·nx + i (the Brusselator's layout). One rank only: NK_E_UNSUPPORTED on a context with more.
  * The object is an nk_problem of kind NK_PROBLEM_USER whose callbacks launch the generated kernels: every algorithm, linear
  * solver and preconditioner object takes it as it takes any callback problem — so the matrix-free GMRES keeps the callback
  * kind's two reductions per Arnoldi step and unfused output scale, and Jᵀv (TrustRegion, normal forms) is the filled Jacobian's
  * transposed SpMV. nk_problem_destroy frees the problem, its modules and its pattern; nk_problem_jac_csr returns the pattern
  * the problem owns (do not destroy it); nk_problem_initial_guess gives zeros.
- * A source that does not compile is NK_E_INVALID with the contract and the compiler's log in nk_last_error. */
-enum { NK_GRID_STAR = 0, NK_GRID_BOX = 1 };           /* stencil  */
+ * A source that does not compile is NK_E_INVALID with the contract and the compiler's log in nk_last_error.
+ * Radius 2 (bit 16 of the stencil code): NK_GRID_STAR2, the 9 points (0,±1) (0,±2) (±1,0) (±2,0) and the centre with
+ * dof = 1..2 (18 partials), and NK_GRID_DIAMOND2, the 13 points with |di| + |dj| <= 2 — the support of the discrete biharmonic
+ * — with dof = 1. With them u(di, dj, c) takes di, dj ∈ {−2, …, 2}; a read outside the stencil's shape (STAR2: more than one
+ * non-zero offset; DIAMOND2: |di| + |dj| > 2) returns NaN. A Dirichlet neighbour up to two layers outside the grid reads 0 and
+ * has no column; a periodic index wraps by ± n; nx, ny >= 5, with both boundaries, so that the five offsets of a direction are
+ * five distinct columns on the torus. Points in pattern order (ascending node index inside the grid), as (di, dj):
+ *   STAR2     (0,−2) (0,−1) (−2,0) (−1,0) C (1,0) (2,0) (0,1) (0,2)
+ *   DIAMOND2  (0,−2) (−1,−1) (0,−1) (1,−1) (−2,0) (−1,0) C (1,0) (2,0) (−1,1) (0,1) (1,1) (0,2)
+ * Their programs carry one more option, -DNK_STENCIL=<code>; the radius-1 programs are compiled from the text and the options
+ * they always had. Every other code (2, 18, …) is NK_E_INVALID. */
+enum { NK_GRID_STAR = 0, NK_GRID_BOX = 1, NK_GRID_STAR2 = 16, NK_GRID_DIAMOND2 = 17 }; /* stencil  */
 enum { NK_GRID_DIRICHLET0 = 0, NK_GRID_PERIODIC = 1 }; /* boundary */
 /* The CSR pattern of the Jacobian (host only, no device needed): rowptr dof·nx·ny + 1 entries, colind *nnz entries, 0-based,
  * columns ascending within a row. Every (stencil point in the domain) × (component) entry is kept — structural even where a
@@ -541,7 +551,10 @@ int nk_problem_create_grid(nk_ctx *ctx, const char *source, int64_t nx, int64_t 
  * (0,0,1); box: dk outermost, di innermost — and the pattern keeps every (point in the domain) × (component) entry in ascending
  * column order, as in 2-D. The object is the same NK_PROBLEM_USER problem owning its pattern: nk_problem_set_params,
  * nk_problem_jac_csr, nk_problem_initial_guess and nk_problem_destroy work unchanged. One rank, Float64. The kernels are
- * nk_grid3_residual, nk_grid3_jvp (jac = 0) and nk_grid3_jac (jac = 1); NK_GRID_FILL_DIRECT keeps its meaning. */
+ * nk_grid3_residual, nk_grid3_jvp (jac = 0) and nk_grid3_jac (jac = 1); NK_GRID_FILL_DIRECT keeps its meaning.
+ * Radius 2: NK_GRID_STAR2 is the 13-point star with dof = 1..2 (26 partials) — one offset ∈ {−2, …, 2}, the others 0, anything
+ * else reads NaN — in the order (0,0,−2) (0,0,−1) (0,−2,0) (0,−1,0) (−2,0,0) (−1,0,0) C (1,0,0) (2,0,0) (0,1,0) (0,2,0) (0,0,1)
+ * (0,0,2); nx, ny, nz >= 5. NK_GRID_DIAMOND2 (25 points in 3-D) is not offered: NK_E_INVALID. */
 int nk_grid3_pattern(int64_t nx, int64_t ny, int64_t nz, int dof, int stencil, int boundary, int32_t *rowptr, int32_t *colind,
                      int64_t *nnz);
 int nk_grid3_compile_check(const char *source, int dof, int stencil, int boundary, int nparams, int64_t *code_bytes);

@@ -170,14 +170,16 @@ bratu2d(n; λ = 6.0, scale = 0.0, kw...) = DeviceProblem(2, Float64[n, λ, scale
 brusselator2d(N; A = 3.4, B = 1.0, α = 10.0, dx = 1 / (N - 1), kw...) = DeviceProblem(3, Float64[N, A, B, α, dx]; kw...)
 
 
-const GRID_STENCILS = Dict(:star => 0, :box => 1)
+const GRID_STENCILS = Dict(:star => 0, :box => 1, :star2 => 16, :diamond2 => 17)
 const GRID_BOUNDARIES = Dict(:dirichlet => 0, :periodic => 1)
 """`CompiledGridProblem(source, nx, ny; dof = 1, stencil = :star, boundary = :dirichlet, params = Float64[])`: a residual given
-pointwise on an nx × ny grid through a radius-1 stencil as HIP source
+pointwise on an nx × ny grid through a radius-1 or radius-2 stencil as HIP source
 `template <typename T> __device__ void nk_point(const nk_nbhd<T> &u, const nk_real *p, nk_site s, T *f)`; the library compiles
 the residual kernel, the exact dual-number JVP kernel and the Jacobian fill from it (nk_problem_create_grid). One rank, Float64,
 dof ≤ 4 (box: ≤ 2), at most 32 parameters. With `nz = n` the grid is nx × ny × nz and the source is written against
-`nk_nbhd3<T>` / `nk_site3` (`u(di, dj, dk, c)`; nk_problem_create_grid3): the 7-point star with dof ≤ 4 or the 27-point box with dof = 1."""
+`nk_nbhd3<T>` / `nk_site3` (`u(di, dj, dk, c)`; nk_problem_create_grid3): the 7-point star with dof ≤ 4 or the 27-point box with dof = 1.
+Radius 2 (offsets in −2 … 2, sides ≥ 5): `stencil = :star2`, the 9-point star in 2-D and the 13-point star in 3-D with dof ≤ 2, and
+`stencil = :diamond2`, the 13 points with |di| + |dj| ≤ 2, 2-D only, dof = 1."""
 function CompiledGridProblem(source::AbstractString, nx::Integer, ny::Integer; dof::Integer = 1, stencil::Symbol = :star,
                              boundary::Symbol = :dirichlet, params::Vector{Float64} = Float64[], ctx = default_ctx(),
                              nz::Union{Nothing, Integer} = nothing)

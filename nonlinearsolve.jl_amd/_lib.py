@@ -18,7 +18,7 @@ class NKError(RuntimeError):
 # ---------------------------------------------------------------------------- enums (mirror the header)
 HOST, DEVICE = 0, 1
 BATCH_ANALYTIC_JAC, BATCH_FLOAT32 = 1, 2   # nk_batch_create / nk_batch_compile_check flags
-GRID_STENCILS = {"star": 0, "box": 1}               # nk_problem_create_grid / nk_grid_pattern
+GRID_STENCILS = {"star": 0, "box": 1, "star2": 16, "diamond2": 17}               # nk_problem_create_grid / nk_grid_pattern
 GRID_BOUNDARIES = {"dirichlet": 0, "periodic": 1}
 RET_NAMES = ["Default", "Success", "MaxIters", "Unstable", "Stalled", "InternalLinearSolveFailed",
              "ShrinkThresholdExceeded", "MaxTime", "Failure", "InternalLineSearchFailed", "ConvergenceFailure"]

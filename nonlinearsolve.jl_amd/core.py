@@ -490,7 +490,7 @@ def _grid_ids(stencil, boundary):
 def grid_pattern(nx: int, ny: int, dof: int = 1, stencil: str = "star", boundary: str = "dirichlet", *, nz: Optional[int] = None):
     """(rowptr, colind), int32, of the Jacobian of a compiled grid problem: columns ascending within a row, every
     (stencil point in the domain) × (component) entry kept. Host only. With nz: the nx × ny × nz grid (7-point star or
-    27-point box)."""
+    27-point box). stencil = "star2" / "diamond2": the radius-2 stencils of CompiledGridProblem (every side >= 5)."""
     st, bd = _grid_ids(stencil, boundary)
     nnz = C.c_int64()
     if nz is None:
@@ -510,7 +510,7 @@ def grid_compile_check(source: str, dof: int = 1, stencil: str = "star", boundar
                        dim: int = 2) -> int:
     """Compile the residual, JVP and Jacobian kernels of `source` for gfx950 (no device needed); the size of the code objects.
     A source that does not compile raises NKError with the contract and the compiler's log. dim = 3: the 3-D contract
-    (nk_nbhd3, nk_site3)."""
+    (nk_nbhd3, nk_site3). stencil = "star2" / "diamond2": the radius-2 neighbourhoods (offsets in −2 … 2)."""
     if dim not in (2, 3):
         raise ValueError(f"dim = {dim!r}: expected 2 or 3")
     st, bd = _grid_ids(stencil, boundary)
@@ -538,14 +538,18 @@ class _GridDeviceProblem(DeviceProblem):
 
 def CompiledGridProblem(source: str, nx: int, ny: int, dof: int = 1, stencil: str = "star", boundary: str = "dirichlet",
                         params: Sequence[float] = (), ctx=None, *, nz: Optional[int] = None) -> DeviceProblem:
-    """A residual given pointwise on an nx × ny grid through a radius-1 stencil, as HIP source
+    """A residual given pointwise on an nx × ny grid through a radius-1 or radius-2 stencil, as HIP source
         template <typename T> __device__ void nk_point(const nk_nbhd<T> &u, const nk_real *p, nk_site s, T *f);
     compiled (hiprtc, gfx950) into the residual kernel, the exact dual-number JVP kernel and the Jacobian fill on the stencil's
     CSR pattern (include/mi355x_nk.h, "compiled grid problems"). u0 defaults to zeros; NonlinearProblem(..., p) and
     reinit_(cache, p=...) replace the source's p[0..nparams). dof <= 4 (box: <= 2), Float64, one rank.
     With nz the grid is nx × ny × nz and the source follows the 3-D contract
         template <typename T> __device__ void nk_point(const nk_nbhd3<T> &u, const nk_real *p, nk_site3 s, T *f);
-    with u(di, dj, dk, c): the 7-point star (dof <= 4) or the 27-point box (dof = 1)."""
+    with u(di, dj, dk, c): the 7-point star (dof <= 4) or the 27-point box (dof = 1).
+    Radius 2: stencil = "star2" — the points (0,±1) (0,±2) (±1,0) (±2,0) and the centre, in 3-D the 13-point star; dof <= 2 —
+    and stencil = "diamond2" — the 13 points with |di| + |dj| <= 2, the support of the discrete biharmonic; 2-D only, dof = 1.
+    Offsets then run over −2 … 2, a read outside the stencil's shape gives NaN, a Dirichlet neighbour up to two layers outside
+    the grid reads 0, a periodic index wraps by ± n, and every side is >= 5."""
     ctx = ctx or default_context()
     st, bd = _grid_ids(stencil, boundary)
     params = [float(x) for x in params]

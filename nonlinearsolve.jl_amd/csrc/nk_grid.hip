@@ -30,6 +30,15 @@
 // text and the options they always had. 7-point star (dof 1..4) or 27-point box (dof 1): at most 28 partials per row, and the
 // staged fill's LDS is at most 256·28 doubles (57344 bytes). Unknown c of node (i, j, k) is element c·nn + (k·ny + j)·nx + i;
 // the flat 256-thread workgroups walk that order, so a wavefront still loads 64 consecutive doubles per stencil point.
+//
+// Radius 2 (NK_GRID_STAR2 = 16, NK_GRID_DIAMOND2 = 17; bit 16 of the stencil code): the same kernels once more. Only four things
+// know the radius — the offset tables nk_pt_di/dj/dk, nk_nbhd::operator() with its NaN rule, the periodic wrap (± n instead of
+// "the other end") and the argument checks — so the radius-2 programs get types strings of their own (k_grid_types_r2,
+// k_grid3_types_r2), the wrap piece k_grid_wrap_r2 between the two pieces of the kernels' text, and one more option,
+// -DNK_STENCIL=<code>. The radius-1 programs are put together from the same bytes and options as before (hiprtc derives a unit id
+// from the text, comments included: even a changed comment would change their code objects). 2-D: the 9-point star with dof 1..2
+// (18 partials) and the 13-point diamond |di| + |dj| <= 2 with dof 1; 3-D: the 13-point star with dof 1..2 (26 partials, staged
+// LDS 53248 bytes). Every side >= 5, so that the five offsets of a direction are five distinct columns on the torus.
 #include <math.h>
 #include <string.h>
 
@@ -68,7 +77,45 @@ struct nk_nbhd {
 };
 )NKSRC";
 
-static const char *k_grid_kernels = R"NKSRC(
+// radius 2 (NK_GRID_STAR2, NK_GRID_DIAMOND2): the programs of these stencils carry -DNK_STENCIL=<code> and get this text in
+// place of k_grid_types; the radius-1 programs are compiled from the text and the options they always had.
+static const char *k_grid_types_r2 = R"NKSRC(
+// ---- compiled grid problems, radius 2: the node's position and its neighbourhood
+#if NK_STENCIL == 17
+#define NK_NPTS 13
+#else
+#define NK_NPTS 9
+#endif
+struct nk_site { int i, j, nx, ny; };
+// stencil point q → offset; q ascends with the node index (j·nx + i) of the point inside the grid:
+// star2    (0,−2) (0,−1) (−2,0) (−1,0) C (1,0) (2,0) (0,1) (0,2)
+// diamond2 (0,−2) (−1,−1) (0,−1) (1,−1) (−2,0) (−1,0) C (1,0) (2,0) (−1,1) (0,1) (1,1) (0,2)
+#if NK_STENCIL == 17
+__device__ constexpr int nk_pt_di(int q) { return q == 0 || q == 12 ? 0 : (q <= 3 ? q - 2 : (q <= 8 ? q - 6 : q - 10)); }
+__device__ constexpr int nk_pt_dj(int q) { return q == 0 ? -2 : (q <= 3 ? -1 : (q <= 8 ? 0 : (q <= 11 ? 1 : 2))); }
+#else
+__device__ constexpr int nk_pt_di(int q) { return q >= 2 && q <= 6 ? q - 4 : 0; }
+__device__ constexpr int nk_pt_dj(int q) { return q < 2 ? q - 2 : (q > 6 ? q - 6 : 0); }
+#endif
+template <typename T>
+struct nk_nbhd {
+  T val[NK_NPTS * NK_DOF];
+  // component c at node (i + di, j + dj); di, dj ∈ {−2, …, 2} (compile-time constants keep val in registers). A read outside
+  // the stencil's shape returns NaN: a wrong source shows at once
+  __device__ __forceinline__ T operator()(int di, int dj, int c = 0) const {
+    const int ai = di < 0 ? -di : di, aj = dj < 0 ? -dj : dj;
+#if NK_STENCIL == 17
+    if (ai + aj > 2) return T(NK_R(__builtin_nan("")));
+    return val[(aj == 2 ? 6 + 3 * dj : 6 + 4 * dj + di) * NK_DOF + c];
+#else
+    if ((di != 0 && dj != 0) || ai > 2 || aj > 2) return T(NK_R(__builtin_nan("")));
+    return val[(dj != 0 ? (dj < 0 ? 2 + dj : 6 + dj) : 4 + di) * NK_DOF + c];
+#endif
+  }
+};
+)NKSRC";
+
+static const char *k_grid_kernels_a = R"NKSRC(
 // ---- generated kernels: one node per thread
 #define NK_GRID_BLOCK 256
 // node index of every stencil point (clamped to the node itself outside a Dirichlet boundary, wrapped at a periodic one) and
@@ -78,9 +125,16 @@ __device__ __forceinline__ void nk_grid_geom(int i, int j, int nx, int ny, int (
   for (int q = 0; q < NK_NPTS; ++q) {
     int ii = i + nk_pt_di(q), jj = j + nk_pt_dj(q);
 #if NK_PERIODIC
-    ii = ii < 0 ? nx - 1 : (ii >= nx ? 0 : ii);
+)NKSRC";
+// the periodic wrap, the one piece of the kernels' text that depends on the radius: with k_grid_wrap_r1 between the two pieces
+// the radius-1 programs are compiled from the very text they always had; an offset of ±2 wraps by ± n
+static const char *k_grid_wrap_r1 = R"NKSRC(    ii = ii < 0 ? nx - 1 : (ii >= nx ? 0 : ii);
     jj = jj < 0 ? ny - 1 : (jj >= ny ? 0 : jj);
-    in[q] = true;
+)NKSRC";
+static const char *k_grid_wrap_r2 = R"NKSRC(    ii = ii < 0 ? ii + nx : (ii >= nx ? ii - nx : ii);
+    jj = jj < 0 ? jj + ny : (jj >= ny ? jj - ny : jj);
+)NKSRC";
+static const char *k_grid_kernels_b = R"NKSRC(    in[q] = true;
 #else
     in[q] = ii >= 0 && ii < nx && jj >= 0 && jj < ny;
     ii = in[q] ? ii : i;
@@ -259,7 +313,29 @@ struct nk_nbhd3 {
 };
 )NKSRC";
 
-static const char *k_grid3_kernels = R"NKSRC(
+static const char *k_grid3_types_r2 = R"NKSRC(
+// ---- compiled grid problems in 3-D, radius 2 (the 13-point star): the node's position and its neighbourhood
+#define NK_NPTS 13
+struct nk_site3 { int i, j, k, nx, ny, nz; };
+// stencil point q → offset; q ascends with the node index ((k·ny + j)·nx + i) of the point inside the grid:
+// (0,0,−2) (0,0,−1) (0,−2,0) (0,−1,0) (−2,0,0) (−1,0,0) C (1,0,0) (2,0,0) (0,1,0) (0,2,0) (0,0,1) (0,0,2)
+__device__ constexpr int nk_pt_di(int q) { return q >= 4 && q <= 8 ? q - 6 : 0; }
+__device__ constexpr int nk_pt_dj(int q) { return q == 2 || q == 3 ? q - 4 : (q == 9 || q == 10 ? q - 8 : 0); }
+__device__ constexpr int nk_pt_dk(int q) { return q < 2 ? q - 2 : (q > 10 ? q - 10 : 0); }
+template <typename T>
+struct nk_nbhd3 {
+  T val[NK_NPTS * NK_DOF];
+  // component c at node (i + di, j + dj, k + dk); one offset ∈ {−2, …, 2}, the others 0 (compile-time constants keep val in
+  // registers). A read with more than one non-zero offset returns NaN: a wrong source shows at once
+  __device__ __forceinline__ T operator()(int di, int dj, int dk, int c = 0) const {
+    if ((di != 0) + (dj != 0) + (dk != 0) > 1 || di < -2 || di > 2 || dj < -2 || dj > 2 || dk < -2 || dk > 2)
+      return T(NK_R(__builtin_nan("")));
+    return val[(dk != 0 ? (dk < 0 ? 2 + dk : 10 + dk) : (dj != 0 ? (dj < 0 ? 4 + dj : 8 + dj) : 6 + di)) * NK_DOF + c];
+  }
+};
+)NKSRC";
+
+static const char *k_grid3_kernels_a = R"NKSRC(
 // ---- generated kernels: one node per thread
 #define NK_GRID_BLOCK 256
 // node index of every stencil point (clamped to the node itself outside a Dirichlet boundary, wrapped at a periodic one) and
@@ -270,10 +346,16 @@ __device__ __forceinline__ void nk_grid3_geom(int i, int j, int k, int nx, int n
   for (int q = 0; q < NK_NPTS; ++q) {
     int ii = i + nk_pt_di(q), jj = j + nk_pt_dj(q), kk = k + nk_pt_dk(q);
 #if NK_PERIODIC
-    ii = ii < 0 ? nx - 1 : (ii >= nx ? 0 : ii);
+)NKSRC";
+static const char *k_grid3_wrap_r1 = R"NKSRC(    ii = ii < 0 ? nx - 1 : (ii >= nx ? 0 : ii);
     jj = jj < 0 ? ny - 1 : (jj >= ny ? 0 : jj);
     kk = kk < 0 ? nz - 1 : (kk >= nz ? 0 : kk);
-    in[q] = true;
+)NKSRC";
+static const char *k_grid3_wrap_r2 = R"NKSRC(    ii = ii < 0 ? ii + nx : (ii >= nx ? ii - nx : ii);
+    jj = jj < 0 ? jj + ny : (jj >= ny ? jj - ny : jj);
+    kk = kk < 0 ? kk + nz : (kk >= nz ? kk - nz : kk);
+)NKSRC";
+static const char *k_grid3_kernels_b = R"NKSRC(    in[q] = true;
 #else
     in[q] = ii >= 0 && ii < nx && jj >= 0 && jj < ny && kk >= 0 && kk < nz;
     ii = in[q] ? ii : i;
@@ -430,25 +512,56 @@ static const char *k_grid3_contract =
     "the node's dof residuals (nk_real = double)";
 
 // ----------------------------------------------------------------------------- the stencil's CSR pattern (host only)
+static inline int grid_radius(int stencil) { return stencil == NK_GRID_STAR2 || stencil == NK_GRID_DIAMOND2 ? 2 : 1; }
+// points of a stencil (0: the dimension does not offer it)
+static inline int grid_npts(int dim, int stencil) {
+  switch (stencil) {
+    case NK_GRID_STAR: return dim == 3 ? 7 : 5;
+    case NK_GRID_BOX: return dim == 3 ? 27 : 9;
+    case NK_GRID_STAR2: return dim == 3 ? 13 : 9;
+    case NK_GRID_DIAMOND2: return dim == 3 ? 0 : 13;
+  }
+  return 0;
+}
+
 static int grid_check_shape(int dof, int stencil, int boundary) {
-  NK_REQUIRE(stencil == NK_GRID_STAR || stencil == NK_GRID_BOX, "stencil = %d is neither NK_GRID_STAR nor NK_GRID_BOX", stencil);
+  NK_REQUIRE(stencil == NK_GRID_STAR || stencil == NK_GRID_BOX || stencil == NK_GRID_STAR2 || stencil == NK_GRID_DIAMOND2,
+             "stencil = %d is none of NK_GRID_STAR, NK_GRID_BOX, NK_GRID_STAR2, NK_GRID_DIAMOND2", stencil);
   NK_REQUIRE(boundary == NK_GRID_DIRICHLET0 || boundary == NK_GRID_PERIODIC,
              "boundary = %d is neither NK_GRID_DIRICHLET0 nor NK_GRID_PERIODIC", boundary);
   NK_REQUIRE(dof >= 1 && dof <= 4, "dof = %d outside 1..4 (components per grid node)", dof);
   NK_REQUIRE(stencil != NK_GRID_BOX || dof <= 2, "dof = %d with the box stencil: the 9-point box is offered for dof <= 2 "
              "(a row has at most 20 partials)", dof);
+  NK_REQUIRE(stencil != NK_GRID_STAR2 || dof <= 2, "dof = %d with the star2 stencil: the 9-point radius-2 star is offered for "
+             "dof <= 2 (a row has at most 20 partials)", dof);
+  NK_REQUIRE(stencil != NK_GRID_DIAMOND2 || dof == 1, "dof = %d with the diamond2 stencil: the 13-point diamond is offered for "
+             "dof = 1 (a row has at most 20 partials)", dof);
   return NK_OK;
 }
-static inline int grid_pt_di(int stencil, int q) { return stencil == NK_GRID_BOX ? q % 3 - 1 : (q == 1 ? -1 : (q == 3 ? 1 : 0)); }
-static inline int grid_pt_dj(int stencil, int q) { return stencil == NK_GRID_BOX ? q / 3 - 1 : (q == 0 ? -1 : (q == 4 ? 1 : 0)); }
+// stencil point q → offset, in pattern order (the device tables of k_grid_types / k_grid_types_r2)
+static inline int grid_pt_di(int stencil, int q) {
+  if (stencil == NK_GRID_STAR2) return q >= 2 && q <= 6 ? q - 4 : 0;
+  if (stencil == NK_GRID_DIAMOND2) return q == 0 || q == 12 ? 0 : (q <= 3 ? q - 2 : (q <= 8 ? q - 6 : q - 10));
+  return stencil == NK_GRID_BOX ? q % 3 - 1 : (q == 1 ? -1 : (q == 3 ? 1 : 0));
+}
+static inline int grid_pt_dj(int stencil, int q) {
+  if (stencil == NK_GRID_STAR2) return q < 2 ? q - 2 : (q > 6 ? q - 6 : 0);
+  if (stencil == NK_GRID_DIAMOND2) return q == 0 ? -2 : (q <= 3 ? -1 : (q <= 8 ? 0 : (q <= 11 ? 1 : 2)));
+  return stencil == NK_GRID_BOX ? q / 3 - 1 : (q == 0 ? -1 : (q == 4 ? 1 : 0));
+}
+// periodic wrap of an index at most n outside [0, n)
+static inline int64_t grid_wrap(int64_t ii, int64_t n) { return ii < 0 ? ii + n : (ii >= n ? ii - n : ii); }
 
 extern "C" int nk_grid_pattern(int64_t nx, int64_t ny, int dof, int stencil, int boundary, int32_t *rowptr, int32_t *colind,
                                int64_t *nnz) {
   NK_REQUIRE(rowptr || nnz, "NULL argument");
   NK_TRY(grid_check_shape(dof, stencil, boundary));
+  if (grid_radius(stencil) == 2)
+    NK_REQUIRE(nx >= 5 && ny >= 5, "grid %lld x %lld: a radius-2 stencil needs nx >= 5 and ny >= 5 (five distinct columns per "
+               "direction at a periodic edge)", (long long)nx, (long long)ny);
   NK_REQUIRE(nx >= 3 && ny >= 3, "grid %lld x %lld: a radius-1 stencil needs nx >= 3 and ny >= 3 (three distinct columns per "
              "row at a periodic edge)", (long long)nx, (long long)ny);
-  const int npts = stencil == NK_GRID_BOX ? 9 : 5;
+  const int npts = grid_npts(2, stencil);
   NK_REQUIRE(nx <= INT32_MAX / ny && nx * ny <= (int64_t)INT32_MAX / (dof * npts * dof),
              "grid %lld x %lld with dof = %d: the pattern's 32-bit indices cannot hold it", (long long)nx, (long long)ny, dof);
   const int64_t nn = nx * ny;
@@ -456,13 +569,13 @@ extern "C" int nk_grid_pattern(int64_t nx, int64_t ny, int dof, int stencil, int
   for (int c = 0; c < dof; ++c)
     for (int64_t j = 0; j < ny; ++j)
       for (int64_t i = 0; i < nx; ++i) {
-        int64_t nb[9];
+        int64_t nb[13];
         int cnt = 0;
         for (int q = 0; q < npts; ++q) {
           int64_t ii = i + grid_pt_di(stencil, q), jj = j + grid_pt_dj(stencil, q);
           if (boundary == NK_GRID_PERIODIC) {
-            ii = ii < 0 ? nx - 1 : (ii >= nx ? 0 : ii);
-            jj = jj < 0 ? ny - 1 : (jj >= ny ? 0 : jj);
+            ii = grid_wrap(ii, nx);
+            jj = grid_wrap(jj, ny);
           } else if (ii < 0 || ii >= nx || jj < 0 || jj >= ny) {
             continue;
           }
@@ -483,27 +596,50 @@ extern "C" int nk_grid_pattern(int64_t nx, int64_t ny, int dof, int stencil, int
   return NK_OK;
 }
 
-// three dimensions: the 7-point star with dof 1..4, the 27-point box with dof 1 — at most 28 partials per row
+// three dimensions: the 7-point star with dof 1..4, the 27-point box with dof 1, the 13-point radius-2 star with dof 1..2 — at
+// most 28 partials per row
 static int grid3_check_shape(int dof, int stencil, int boundary) {
-  NK_REQUIRE(stencil == NK_GRID_STAR || stencil == NK_GRID_BOX, "stencil = %d is neither NK_GRID_STAR nor NK_GRID_BOX", stencil);
+  NK_REQUIRE(stencil != NK_GRID_DIAMOND2, "stencil = NK_GRID_DIAMOND2 (%d) is not offered in three dimensions (25 points); "
+             "the radius-2 stencil of nk_problem_create_grid3 is NK_GRID_STAR2", stencil);
+  NK_REQUIRE(stencil == NK_GRID_STAR || stencil == NK_GRID_BOX || stencil == NK_GRID_STAR2,
+             "stencil = %d is none of NK_GRID_STAR, NK_GRID_BOX, NK_GRID_STAR2", stencil);
   NK_REQUIRE(boundary == NK_GRID_DIRICHLET0 || boundary == NK_GRID_PERIODIC,
              "boundary = %d is neither NK_GRID_DIRICHLET0 nor NK_GRID_PERIODIC", boundary);
   NK_REQUIRE(dof >= 1 && dof <= 4, "dof = %d outside 1..4 (components per grid node)", dof);
   NK_REQUIRE(stencil != NK_GRID_BOX || dof == 1, "dof = %d with the box stencil: the 27-point box is offered for dof = 1 "
              "(a row has at most 28 partials)", dof);
+  NK_REQUIRE(stencil != NK_GRID_STAR2 || dof <= 2, "dof = %d with the star2 stencil: the 13-point radius-2 star is offered for "
+             "dof <= 2 (a row has at most 28 partials)", dof);
   return NK_OK;
 }
-static inline int grid3_pt_di(int stencil, int q) { return stencil == NK_GRID_BOX ? q % 3 - 1 : (q == 2 ? -1 : (q == 4 ? 1 : 0)); }
-static inline int grid3_pt_dj(int stencil, int q) { return stencil == NK_GRID_BOX ? (q / 3) % 3 - 1 : (q == 1 ? -1 : (q == 5 ? 1 : 0)); }
-static inline int grid3_pt_dk(int stencil, int q) { return stencil == NK_GRID_BOX ? q / 9 - 1 : (q == 0 ? -1 : (q == 6 ? 1 : 0)); }
+static inline int grid3_pt_di(int stencil, int q) {
+  if (stencil == NK_GRID_STAR2) return q >= 4 && q <= 8 ? q - 6 : 0;
+  return stencil == NK_GRID_BOX ? q % 3 - 1 : (q == 2 ? -1 : (q == 4 ? 1 : 0));
+}
+static inline int grid3_pt_dj(int stencil, int q) {
+  if (stencil == NK_GRID_STAR2) return q == 2 || q == 3 ? q - 4 : (q == 9 || q == 10 ? q - 8 : 0);
+  return stencil == NK_GRID_BOX ? (q / 3) % 3 - 1 : (q == 1 ? -1 : (q == 5 ? 1 : 0));
+}
+static inline int grid3_pt_dk(int stencil, int q) {
+  if (stencil == NK_GRID_STAR2) return q < 2 ? q - 2 : (q > 10 ? q - 10 : 0);
+  return stencil == NK_GRID_BOX ? q / 9 - 1 : (q == 0 ? -1 : (q == 6 ? 1 : 0));
+}
+// the refusal of a grid too small for the stencil's radius (both boundaries: 2·radius + 1 distinct columns per direction)
+static int grid3_check_size(int64_t nx, int64_t ny, int64_t nz, int stencil) {
+  if (grid_radius(stencil) == 2)
+    NK_REQUIRE(nx >= 5 && ny >= 5 && nz >= 5, "grid %lld x %lld x %lld: a radius-2 stencil needs nx >= 5, ny >= 5 and nz >= 5 "
+               "(five distinct columns per direction at a periodic edge)", (long long)nx, (long long)ny, (long long)nz);
+  NK_REQUIRE(nx >= 3 && ny >= 3 && nz >= 3, "grid %lld x %lld x %lld: a radius-1 stencil needs nx >= 3, ny >= 3 and nz >= 3 "
+             "(three distinct columns per direction at a periodic edge)", (long long)nx, (long long)ny, (long long)nz);
+  return NK_OK;
+}
 
 extern "C" int nk_grid3_pattern(int64_t nx, int64_t ny, int64_t nz, int dof, int stencil, int boundary, int32_t *rowptr,
                                 int32_t *colind, int64_t *nnz) {
   NK_REQUIRE(rowptr || nnz, "NULL argument");
   NK_TRY(grid3_check_shape(dof, stencil, boundary));
-  NK_REQUIRE(nx >= 3 && ny >= 3 && nz >= 3, "grid %lld x %lld x %lld: a radius-1 stencil needs nx >= 3, ny >= 3 and nz >= 3 "
-             "(three distinct columns per direction at a periodic edge)", (long long)nx, (long long)ny, (long long)nz);
-  const int npts = stencil == NK_GRID_BOX ? 27 : 7;
+  NK_TRY(grid3_check_size(nx, ny, nz, stencil));
+  const int npts = grid_npts(3, stencil);
   NK_REQUIRE(nx <= INT32_MAX / ny && nx * ny <= INT32_MAX / nz && nx * ny * nz <= (int64_t)INT32_MAX / (dof * npts * dof),
              "grid %lld x %lld x %lld with dof = %d: the pattern's 32-bit indices cannot hold it", (long long)nx, (long long)ny,
              (long long)nz, dof);
@@ -518,9 +654,9 @@ extern "C" int nk_grid3_pattern(int64_t nx, int64_t ny, int64_t nz, int dof, int
           for (int q = 0; q < npts; ++q) {
             int64_t ii = i + grid3_pt_di(stencil, q), jj = j + grid3_pt_dj(stencil, q), kk = k + grid3_pt_dk(stencil, q);
             if (boundary == NK_GRID_PERIODIC) {
-              ii = ii < 0 ? nx - 1 : (ii >= nx ? 0 : ii);
-              jj = jj < 0 ? ny - 1 : (jj >= ny ? 0 : jj);
-              kk = kk < 0 ? nz - 1 : (kk >= nz ? 0 : kk);
+              ii = grid_wrap(ii, nx);
+              jj = grid_wrap(jj, ny);
+              kk = grid_wrap(kk, nz);
             } else if (ii < 0 || ii >= nx || jj < 0 || jj >= ny || kk < 0 || kk >= nz) {
               continue;
             }
@@ -551,9 +687,13 @@ static int grid_compile(const char *source, int dim, int dof, int stencil, int b
   NK_REQUIRE(source, "NULL source");
   NK_TRY(dim == 3 ? grid3_check_shape(dof, stencil, boundary) : grid_check_shape(dof, stencil, boundary));
   NK_REQUIRE(np >= 0 && np <= 32, "nparams = %d outside 0..32", np);
-  const int npts = dim == 3 ? (stencil == NK_GRID_BOX ? 27 : 7) : (stencil == NK_GRID_BOX ? 9 : 5);
-  const std::string full = std::string(nk_dual_prelude) + (dim == 3 ? k_grid3_types : k_grid_types) + "\n// ---- user source\n" +
-                           source + "\n" + (dim == 3 ? k_grid3_kernels : k_grid_kernels);
+  const int npts = grid_npts(dim, stencil);
+  const bool r2 = grid_radius(stencil) == 2;
+  const char *types = dim == 3 ? (r2 ? k_grid3_types_r2 : k_grid3_types) : (r2 ? k_grid_types_r2 : k_grid_types);
+  const std::string full = std::string(nk_dual_prelude) + types + "\n// ---- user source\n" + source + "\n" +
+                           (dim == 3 ? k_grid3_kernels_a : k_grid_kernels_a) +
+                           (dim == 3 ? (r2 ? k_grid3_wrap_r2 : k_grid3_wrap_r1) : (r2 ? k_grid_wrap_r2 : k_grid_wrap_r1)) +
+                           (dim == 3 ? k_grid3_kernels_b : k_grid_kernels_b);
   const std::string dd = "-DNK_DOF=" + std::to_string(dof), db = std::string("-DNK_BOX=") + (stencil == NK_GRID_BOX ? "1" : "0"),
                     dp = std::string("-DNK_PERIODIC=") + (boundary == NK_GRID_PERIODIC ? "1" : "0"),
                     dc = "-DNK_CH=" + std::to_string(gset == GSET_JAC ? npts * dof : 1), ds = "-DNK_GRID_SET=" + std::to_string(gset),
@@ -561,6 +701,10 @@ static int grid_compile(const char *source, int dim, int dof, int stencil, int b
   std::vector<const char *> opts = {"--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-std=c++17", dd.c_str(), db.c_str(),
                                     dp.c_str(), dc.c_str(), ds.c_str(), dr.c_str()};
   if (dim == 3) opts.push_back("-DNK_DIM=3");
+  // radius 2: the stencil's code, which only these programs carry (it tells star2 from diamond2 in k_grid_types_r2 and keeps
+  // their cache entries apart from the radius-1 programs of the same source)
+  const std::string dn = "-DNK_STENCIL=" + std::to_string(stencil);
+  if (r2) opts.push_back(dn.c_str());
   // the same source with the same options gives the same code object: problems created again (another grid size, another
   // context) skip the compiler
   static std::mutex mtx;
@@ -766,7 +910,6 @@ extern "C" int nk_problem_create_grid(nk_ctx *ctx, const char *source, int64_t n
 extern "C" int nk_problem_create_grid3(nk_ctx *ctx, const char *source, int64_t nx, int64_t ny, int64_t nz, int dof, int stencil,
                                        int boundary, const double *params, int nparams, nk_problem **out) {
   // (grid_create tells the dimensions apart by nz > 0: a side below 3 must not fall through to the 2-D path)
-  NK_REQUIRE(nz >= 3, "grid %lld x %lld x %lld: a radius-1 stencil needs nx >= 3, ny >= 3 and nz >= 3 (three distinct columns "
-             "per direction at a periodic edge)", (long long)nx, (long long)ny, (long long)nz);
+  if (nz < 3) NK_TRY(grid3_check_size(nx, ny, nz, stencil));
   return grid_create(ctx, source, nx, ny, nz, dof, stencil, boundary, params, nparams, out);
 }

@@ -18,6 +18,14 @@ and as the yardstick the 2-D Bratu source at `--grid2`² (4096², the same unkno
 problems alternating. Fill bytes are 8 nnz + (8 dof + 4) n: the values, u and the row pointer.
 
     python tools/grid_problem_bench.py --dim 3 [--out profiles/grid3_problem_bench.txt] [--grid3 256] [--box3 160] [--grid2 4096]
+
+`--radius 2` measures the radius-2 generated kernels beside their radius-1 twins at equal unknowns: the fourth-order Bratu
+source lap4 of tests/grid_r2_reference.py (9-point star2) beside the radius-1 compiled Bratu source at `--grid`² (1024²), and
+lap4_3 (13-point star2) beside bratu3 at `--grid3`³ (256³) — same process, same protocol, the problems alternating. Residual
+and JVP move the same algorithmic bytes in both (16 n, 24 n): a time ratio above 1 is load-path cost. The fill grows with
+8 nnz / n and is compared in GB/s.
+
+    python tools/grid_problem_bench.py --radius 2 [--out profiles/grid_r2_problem_bench.txt] [--grid 1024] [--grid3 256]
 """
 import argparse
 import os
@@ -67,13 +75,32 @@ def steps_per_second(make_problem, u0, concrete, steps, warmup):
 def main3(args):
     """the 3-D kernels beside the 2-D generated kernels at equal unknowns"""
     import grid3_reference as R3
-    ctx = nls.default_context()
     g3, b3, g2 = args.grid3, args.box3, args.grid2
     cases = [   # label, source, (nx, ny, nz), stencil, parameters
         (f"2-D bratu {g2}^2", R.BRATU_SRC, (g2, g2, None), "star", R.bratu_params(g2, 6.0)),
         (f"bratu3 {g3}^3", R3.BRATU3_SRC, (g3, g3, g3), "star", R3.bratu3_params(g3, 3.0)),
         (f"box3 {b3}^3", R3.BOX3_SRC, (b3, b3, b3), "box", R3.BOX3_PARAMS),
     ]
+    generated_kernels(args, "Compiled grid problems in 3-D beside the 2-D generated kernels at equal unknowns", cases)
+
+
+def main_radius2(args):
+    """the radius-2 kernels beside the radius-1 generated kernels at equal unknowns, in 2-D and in 3-D"""
+    import grid3_reference as R3
+    import grid_r2_reference as R2
+    g, g3 = args.grid, args.grid3
+    cases = [
+        (f"bratu {g}^2 (5-point)", R.BRATU_SRC, (g, g, None), "star", R.bratu_params(g, 6.0)),
+        (f"lap4 {g}^2 (9-point star2)", R2.LAP4_SRC, (g, g, None), "star2", R2.lap4_params(g, 3.0)),
+        (f"bratu3 {g3}^3 (7-point)", R3.BRATU3_SRC, (g3, g3, g3), "star", R3.bratu3_params(g3, 3.0)),
+        (f"lap4_3 {g3}^3 (13-point star2)", R2.LAP4_3_SRC, (g3, g3, g3), "star2", R2.lap4_params(g3, 3.0)),
+    ]
+    generated_kernels(args, "Compiled grid problems with a radius-2 stencil beside their radius-1 twins at equal unknowns", cases)
+
+
+def generated_kernels(args, title, cases):
+    """the three generated kernels of every case, the fill in both forms, ordered by kernel so that the cases alternate"""
+    ctx = nls.default_context()
     gen = torch.Generator(device="cuda").manual_seed(1)
     calls, meta, problems, sizes = {}, {}, [], []   # meta: label → (kind rank, algorithmic bytes, unknowns)
     for label, src, (nx, ny, nz), stencil, par in cases:
@@ -93,6 +120,7 @@ def main3(args):
         assert float((J.matvec(v) - jv).abs().max()) <= 1e-10 * max(1.0, float(jv.abs().max()))
         assert torch.equal(J.matvec(v), Jd.matvec(v))
         sizes.append(f"{label}: n = {n}, nnz = {nnz} ({nnz / n:.2f} per row)")
+        print("built and checked " + sizes[-1], flush=True)
         kinds = [("residual", lambda P=P, u=u: P.residual(u), "residual", 16.0 * n),
                  ("JVP", lambda P=P, u=u, v=v: P.jvp(v, u), "jvp", 24.0 * n),
                  ("fill (LDS-staged rows)", lambda P=P, u=u, J=J: P.jac_values(u, J), "jacfill", 8.0 * nnz + 12.0 * n),
@@ -104,15 +132,15 @@ def main3(args):
     # (ordered by kernel, so that the 2-D yardstick and the 3-D kernels of one kind alternate)
     order = sorted(calls, key=lambda k: meta[k][0])
     ts = kernel_samples(ctx, {k: calls[k] for k in order}, args.reps)
-    lines = [f"Compiled grid problems in 3-D beside the 2-D generated kernels at equal unknowns, {torch.cuda.get_device_name(0)}"] + sizes + [
+    lines = [f"{title}, {torch.cuda.get_device_name(0)}"] + sizes + [
              f"kernel begin -> end device timestamps, one launch per sample, problems alternating, {args.reps} samples after 20;",
              "GB/s on algorithmic bytes: residual 16 n, JVP 24 n, fill 8 nnz + 12 n (dof = 1)", "",
-             f"  {'kernel':44s} {'median us':>10s} {'p10':>9s} {'p90':>9s} {'GB/s (median)':>14s}  {'ns/unknown':>10s}  algorithmic MB"]
+             f"  {'kernel':56s} {'median us':>10s} {'p10':>9s} {'p90':>9s} {'GB/s (median)':>14s}  {'ns/unknown':>10s}  algorithmic MB"]
     for label in order:
         t = ts[label]
         med = statistics.median(t)
         _rank, b, n = meta[label]
-        lines.append(f"  {label:44s} {med:10.2f} {t[len(t) // 10]:9.2f} {t[(9 * len(t)) // 10]:9.2f} "
+        lines.append(f"  {label:56s} {med:10.2f} {t[len(t) // 10]:9.2f} {t[(9 * len(t)) // 10]:9.2f} "
                      f"{b / med / 1e3:14.1f}  {1e3 * med / n:10.4f}  {b / 1e6:.1f}")
     text = "\n".join(lines) + "\n"
     print(text)
@@ -127,6 +155,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None)
     ap.add_argument("--dim", type=int, default=2, choices=(2, 3))
+    ap.add_argument("--radius", type=int, default=1, choices=(1, 2))
     ap.add_argument("--grid3", type=int, default=256)
     ap.add_argument("--box3", type=int, default=160)
     ap.add_argument("--grid2", type=int, default=4096)
@@ -136,7 +165,10 @@ def main():
     ap.add_argument("--warmup", type=int, default=20)
     args = ap.parse_args()
     if args.out is None:
-        args.out = os.path.join(ROOT, "profiles", "grid3_problem_bench.txt" if args.dim == 3 else "grid_problem_bench.txt")
+        name = "grid_r2_problem_bench.txt" if args.radius == 2 else ("grid3_problem_bench.txt" if args.dim == 3 else "grid_problem_bench.txt")
+        args.out = os.path.join(ROOT, "profiles", name)
+    if args.radius == 2:
+        return main_radius2(args)
     if args.dim == 3:
         return main3(args)
     ns = args.grid
