@@ -563,6 +563,42 @@ int nk_grid3_code_object(const char *source, int dof, int stencil, int boundary,
 int nk_problem_create_grid3(nk_ctx *ctx, const char *source, int64_t nx, int64_t ny, int64_t nz, int dof, int stencil,
                             int boundary, const double *params, int nparams, nk_problem **out);
 
+/* Fields: read-only data on the grid. A problem created with nfields = 1..4 owns that many arrays of one double per node — a
+ * previous time level for implicit time stepping, a variable coefficient, a source term, a mask — and compiles a source written
+ * against one more argument:
+ *     2-D: template <typename T> __device__ void nk_point(const nk_nbhd<T> &u, const nk_flds &a, const nk_real *p, nk_site s, T *f);
+ *     3-D: template <typename T> __device__ void nk_point(const nk_nbhd3<T> &u, const nk_flds3 &a, const nk_real *p, nk_site3 s, T *f);
+ * with  a(di, dj, k = 0)  (3-D: a(di, dj, dk, k = 0)) field k at the neighbouring node, as an nk_real. It is never a dual: fields
+ *                         are constants of the differentiation, they add no column to the pattern and no partial to J·v.
+ * Offsets and shape rule are the stencil's own: a read outside the shape (a corner of the star, |di| + |dj| > 2 of the diamond)
+ * returns NaN, exactly as u does. Boundary rule for fields: at a periodic boundary the index wraps, as for u; outside a
+ * Dirichlet boundary a field reads as THE FIELD AT THE NODE ITSELF (not 0: the clamped address the u load already computes,
+ * without the select that zeroes u), so a face coefficient 0.5·(a(0,0) + a(1,0)) degenerates to a(0,0) at the wall. A source that
+ * wants something else tests s.
+ * Storage: field k of node m (m = j·nx + i, 3-D (k·ny + j)·nx + i) is element k·nn + m of one device buffer of nfields·nn
+ * doubles which the problem owns; it is zero-filled at creation, so nothing is ever read uninitialised. nk_problem_set_field
+ * copies nn doubles from host or device memory into field k on the context's stream and, like nk_problem_set_params, marks the
+ * problem changed: a Jacobian cached for the same u belongs to the old field and is filled again. nk_problem_get_field copies
+ * field k out. Both are NK_E_INVALID — the message names the value — for k outside 0..nfields−1, for a problem that is not a
+ * compiled grid problem and for one created without fields; nfields outside 0..4 is NK_E_INVALID at creation.
+ * nz = 0 makes the 2-D problem, nz >= 3 the 3-D one; nfields = 0 gives the program and the problem of nk_problem_create_grid /
+ * nk_problem_create_grid3. Everything else is unchanged: stencils, dof limits, side minimums, p, the pattern (nk_grid_pattern /
+ * nk_grid3_pattern: fields add no columns), one rank, Float64, kind NK_PROBLEM_USER, every consumer. The programs with fields
+ * carry one more option, -DNK_NFIELDS=<nfields>; the kernels keep their names and their thread map (one node per thread, 256
+ * per workgroup), and the staged fill's LDS is unchanged. The field neighbourhood is loaded with u's, unconditionally; a load
+ * whose value the source does not read is removed by the compiler, so declaring a field costs nothing until it is read.
+ * Algorithmic bytes per unknown, r = number of distinct fields the source reads: residual 16 + 8·r/dof, J·v 24 + 8·r/dof, the
+ * fill its figure + 8·r/dof. A source with the other contract is NK_E_INVALID with the contract that applies in the message. */
+int nk_problem_create_grid_fields(nk_ctx *ctx, const char *source, int64_t nx, int64_t ny, int64_t nz, int dof, int stencil,
+                                  int boundary, const double *params, int nparams, int nfields, nk_problem **out);
+int nk_problem_set_field(nk_problem *P, int k, const double *data, int memspace);
+int nk_problem_get_field(nk_problem *P, int k, double *out, int memspace);
+/* compile only / the code object of one program, as nk_grid_compile_check and nk_grid_code_object; dim = 2 or 3; no device needed */
+int nk_grid_fields_compile_check(const char *source, int dim, int dof, int stencil, int boundary, int nparams, int nfields,
+                                 int64_t *code_bytes);
+int nk_grid_fields_code_object(const char *source, int dim, int dof, int stencil, int boundary, int nparams, int nfields, int jac,
+                               void *buf, int64_t capacity, int64_t *bytes);
+
 /* ---------------------------------------------------------------- GMRES (seam 1) */
 int nk_gmres_create(nk_ctx *ctx, int64_t n_local, int restart_m, int ortho, nk_gmres **out);
 int nk_gmres_destroy(nk_gmres *G);

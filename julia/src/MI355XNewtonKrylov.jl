@@ -179,13 +179,21 @@ the residual kernel, the exact dual-number JVP kernel and the Jacobian fill from
 dof ≤ 4 (box: ≤ 2), at most 32 parameters. With `nz = n` the grid is nx × ny × nz and the source is written against
 `nk_nbhd3<T>` / `nk_site3` (`u(di, dj, dk, c)`; nk_problem_create_grid3): the 7-point star with dof ≤ 4 or the 27-point box with dof = 1.
 Radius 2 (offsets in −2 … 2, sides ≥ 5): `stencil = :star2`, the 9-point star in 2-D and the 13-point star in 3-D with dof ≤ 2, and
-`stencil = :diamond2`, the 13 points with |di| + |dj| ≤ 2, 2-D only, dof = 1."""
+`stencil = :diamond2`, the 13 points with |di| + |dj| ≤ 2, 2-D only, dof = 1.
+Fields: with `fields = 1..4` the problem owns that many read-only arrays of one Float64 per node and the source takes
+`const nk_flds &a` (3-D: `const nk_flds3 &a`) after `u`; `a(di, dj, k)` is field k at the neighbouring node, a constant of the
+differentiation. A periodic index wraps; outside a Dirichlet boundary a field reads as the field at the node itself. Fields are
+zero until `set_field!(P, k, x)` (k is 0-based, as in the source); `get_field(P, k)` copies one out (nk_problem_create_grid_fields)."""
 function CompiledGridProblem(source::AbstractString, nx::Integer, ny::Integer; dof::Integer = 1, stencil::Symbol = :star,
                              boundary::Symbol = :dirichlet, params::Vector{Float64} = Float64[], ctx = default_ctx(),
-                             nz::Union{Nothing, Integer} = nothing)
+                             nz::Union{Nothing, Integer} = nothing, fields::Integer = 0)
     out = Ref{Ptr{Cvoid}}(C_NULL)
     par = isempty(params) ? Float64[0.0] : params
-    if nz === nothing
+    if fields != 0
+        GC.@preserve par nkcheck(@ccall libnk.nk_problem_create_grid_fields(ctx.ptr::Ptr{Cvoid}, String(source)::Cstring,
+            Int64(nx)::Int64, Int64(ny)::Int64, Int64(nz === nothing ? 0 : nz)::Int64, dof::Cint, GRID_STENCILS[stencil]::Cint,
+            GRID_BOUNDARIES[boundary]::Cint, par::Ptr{Float64}, length(params)::Cint, fields::Cint, out::Ptr{Ptr{Cvoid}})::Cint)
+    elseif nz === nothing
         GC.@preserve par nkcheck(@ccall libnk.nk_problem_create_grid(ctx.ptr::Ptr{Cvoid}, String(source)::Cstring, Int64(nx)::Int64,
             Int64(ny)::Int64, dof::Cint, GRID_STENCILS[stencil]::Cint, GRID_BOUNDARIES[boundary]::Cint, par::Ptr{Float64},
             length(params)::Cint, out::Ptr{Ptr{Cvoid}})::Cint)
@@ -199,6 +207,17 @@ function CompiledGridProblem(source::AbstractString, nx::Integer, ny::Integer; d
     p = DeviceProblem(out[], nl[])
     finalizer(x -> @ccall(libnk.nk_problem_destroy(x.ptr::Ptr{Cvoid})::Cint), p)
     return p
+end
+"""`set_field!(P, k, x)`: replace field k (0-based) of a compiled grid problem with fields by the host vector `x`, one Float64
+per node in the grid's order; `get_field(P, k, nn)` returns a host copy of its nn values."""
+function set_field!(P::DeviceProblem, k::Integer, x::Vector{Float64})
+    GC.@preserve x nkcheck(@ccall libnk.nk_problem_set_field(P.ptr::Ptr{Cvoid}, k::Cint, x::Ptr{Float64}, 0::Cint)::Cint)
+    return P
+end
+function get_field(P::DeviceProblem, k::Integer, nn::Integer)
+    x = Vector{Float64}(undef, nn)
+    GC.@preserve x nkcheck(@ccall libnk.nk_problem_get_field(P.ptr::Ptr{Cvoid}, k::Cint, x::Ptr{Float64}, 0::Cint)::Cint)
+    return x
 end
 """`grid_pattern(nx, ny; dof, stencil, boundary, nz)` → `(rowptr, colind)`, 0-based `Int32`: the CSR pattern of that Jacobian (host
 only); with `nz` the pattern of the nx × ny × nz grid."""
@@ -224,9 +243,14 @@ end
 """`grid_compile_check(source; dof, stencil, boundary, nparams, dim = 2)`: compile the three kernels for gfx950 (no device needed);
 bytes of code. `dim = 3`: the 3-D contract."""
 function grid_compile_check(source::AbstractString; dof::Integer = 1, stencil::Symbol = :star, boundary::Symbol = :dirichlet,
-                            nparams::Integer = 0, dim::Integer = 2)
+                            nparams::Integer = 0, dim::Integer = 2, fields::Integer = 0)
     nb = Ref{Int64}(0)
     dim in (2, 3) || throw(ArgumentError("dim = $dim: expected 2 or 3"))
+    if fields != 0
+        nkcheck(@ccall libnk.nk_grid_fields_compile_check(String(source)::Cstring, dim::Cint, dof::Cint, GRID_STENCILS[stencil]::Cint,
+            GRID_BOUNDARIES[boundary]::Cint, nparams::Cint, fields::Cint, nb::Ptr{Int64})::Cint)
+        return nb[]
+    end
     if dim == 3
         nkcheck(@ccall libnk.nk_grid3_compile_check(String(source)::Cstring, dof::Cint, GRID_STENCILS[stencil]::Cint,
             GRID_BOUNDARIES[boundary]::Cint, nparams::Cint, nb::Ptr{Int64})::Cint)
@@ -836,7 +860,7 @@ end
 # point with memspace = NK_DEVICE, and device-resident Julia operators / preconditioners serve through the device-pointer
 # callback contract (nk_matvec_fn proper).
 
-export Ctx, DeviceVector, DeviceCSR, DeviceProblem, bratu2d, brusselator2d, CompiledGridProblem, grid_pattern, grid_compile_check, mi355x_function, MI355XGMRES,
+export Ctx, DeviceVector, DeviceCSR, DeviceProblem, bratu2d, brusselator2d, CompiledGridProblem, grid_pattern, grid_compile_check, set_field!, get_field, mi355x_function, MI355XGMRES,
     MI355XNewtonKrylovAlg, EnsembleKernel, LeastSquaresEnsembleKernel, SimpleGaussNewton, vectorized_solve, DevicePreconditioner, DeviceILU0, DeviceILUT, DeviceAMG, DeviceJacobi, update!, update_values!
 
 end # module

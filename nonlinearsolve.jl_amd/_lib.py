@@ -192,6 +192,11 @@ SIGNATURES = {
     "nk_grid3_compile_check": (_I, [C.c_char_p, _I, _I, _I, _I, C.POINTER(_L)]),
     "nk_grid3_code_object": (_I, [C.c_char_p, _I, _I, _I, _I, _I, _P, _L, C.POINTER(_L)]),
     "nk_problem_create_grid3": (_I, [_P, C.c_char_p, _L, _L, _L, _I, _I, _I, C.POINTER(_D), _I, _PP]),
+    "nk_problem_create_grid_fields": (_I, [_P, C.c_char_p, _L, _L, _L, _I, _I, _I, C.POINTER(_D), _I, _I, _PP]),
+    "nk_problem_set_field": (_I, [_P, _I, _P, _I]),
+    "nk_problem_get_field": (_I, [_P, _I, _P, _I]),
+    "nk_grid_fields_compile_check": (_I, [C.c_char_p, _I, _I, _I, _I, _I, _I, C.POINTER(_L)]),
+    "nk_grid_fields_code_object": (_I, [C.c_char_p, _I, _I, _I, _I, _I, _I, _I, _P, _L, C.POINTER(_L)]),
     "nk_gmres_create": (_I, [_P, _L, _I, _I, _PP]),
     "nk_gmres_destroy": (_I, [_P]),
     "nk_gmres_set_operator_csr": (_I, [_P, _P]),

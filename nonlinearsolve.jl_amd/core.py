@@ -507,14 +507,18 @@ def grid_pattern(nx: int, ny: int, dof: int = 1, stencil: str = "star", boundary
 
 
 def grid_compile_check(source: str, dof: int = 1, stencil: str = "star", boundary: str = "dirichlet", nparams: int = 0, *,
-                       dim: int = 2) -> int:
+                       dim: int = 2, fields: int = 0) -> int:
     """Compile the residual, JVP and Jacobian kernels of `source` for gfx950 (no device needed); the size of the code objects.
     A source that does not compile raises NKError with the contract and the compiler's log. dim = 3: the 3-D contract
-    (nk_nbhd3, nk_site3). stencil = "star2" / "diamond2": the radius-2 neighbourhoods (offsets in −2 … 2)."""
+    (nk_nbhd3, nk_site3). stencil = "star2" / "diamond2": the radius-2 neighbourhoods (offsets in −2 … 2). fields = 1..4: the
+    contract with the field argument `const nk_flds &a` (3-D: nk_flds3) of CompiledGridProblem(..., fields=)."""
     if dim not in (2, 3):
         raise ValueError(f"dim = {dim!r}: expected 2 or 3")
     st, bd = _grid_ids(stencil, boundary)
     nb = C.c_int64()
+    if fields:
+        check(L.lib().nk_grid_fields_compile_check(source.encode(), dim, dof, st, bd, nparams, int(fields), C.byref(nb)))
+        return nb.value
     fn = L.lib().nk_grid3_compile_check if dim == 3 else L.lib().nk_grid_compile_check
     check(fn(source.encode(), dof, st, bd, nparams, C.byref(nb)))
     return nb.value
@@ -535,9 +539,31 @@ class _GridDeviceProblem(DeviceProblem):
         self.set_params(p)
         self.p = p
 
+    nfields = 0   # CompiledGridProblem(..., fields=k)
+
+    @property
+    def nn(self) -> int:
+        """grid nodes: the length of a field"""
+        return self.nx * self.ny * getattr(self, "nz", 1)
+
+    def set_field(self, k: int, x):
+        """Replace field k (0 .. nfields − 1) by x: a torch tensor on the device or a NumPy array with one float64 per grid
+        node, node (i, j[, k]) at (k·ny + j)·nx + i. The data is copied; a Jacobian cached for the same u is filled again."""
+        size = x.numel() if _is_torch(x) else np.size(x)
+        if size != self.nn:
+            raise ValueError(f"field {k}: expected {self.nn} elements (one per grid node), got {size}")
+        px, ms, _keep = _ptr(x, self.nn)
+        check(L.lib().nk_problem_set_field(self._h, int(k), px, ms))
+
+    def field(self, k: int):
+        """a copy of field k as a device tensor"""
+        out = torch.empty(self.nn, dtype=torch.float64, device=f"cuda:{self.ctx.device}")
+        check(L.lib().nk_problem_get_field(self._h, int(k), C.c_void_p(out.data_ptr()), L.DEVICE))
+        return out
+
 
 def CompiledGridProblem(source: str, nx: int, ny: int, dof: int = 1, stencil: str = "star", boundary: str = "dirichlet",
-                        params: Sequence[float] = (), ctx=None, *, nz: Optional[int] = None) -> DeviceProblem:
+                        params: Sequence[float] = (), ctx=None, *, nz: Optional[int] = None, fields: int = 0) -> DeviceProblem:
     """A residual given pointwise on an nx × ny grid through a radius-1 or radius-2 stencil, as HIP source
         template <typename T> __device__ void nk_point(const nk_nbhd<T> &u, const nk_real *p, nk_site s, T *f);
     compiled (hiprtc, gfx950) into the residual kernel, the exact dual-number JVP kernel and the Jacobian fill on the stencil's
@@ -549,13 +575,29 @@ def CompiledGridProblem(source: str, nx: int, ny: int, dof: int = 1, stencil: st
     Radius 2: stencil = "star2" — the points (0,±1) (0,±2) (±1,0) (±2,0) and the centre, in 3-D the 13-point star; dof <= 2 —
     and stencil = "diamond2" — the 13 points with |di| + |dj| <= 2, the support of the discrete biharmonic; 2-D only, dof = 1.
     Offsets then run over −2 … 2, a read outside the stencil's shape gives NaN, a Dirichlet neighbour up to two layers outside
-    the grid reads 0, a periodic index wraps by ± n, and every side is >= 5."""
+    the grid reads 0, a periodic index wraps by ± n, and every side is >= 5.
+    Fields: with fields = 1..4 the problem owns that many read-only arrays of one double per node (a previous time level, a
+    coefficient, a source term) and the source takes one more argument after u,
+        template <typename T> __device__ void nk_point(const nk_nbhd<T> &u, const nk_flds &a, const nk_real *p, nk_site s, T *f);
+    (3-D: const nk_nbhd3<T> &u, const nk_flds3 &a, …, nk_site3 s) where a(di, dj, k = 0) — 3-D a(di, dj, dk, k = 0) — is field k
+    at the neighbouring node: an nk_real, never a dual, so fields add no column and no partial. Offsets and the NaN rule are
+    the stencil's own. At a periodic boundary the index wraps; outside a Dirichlet boundary a field reads as the field at the
+    node itself (u reads 0 there), so a face coefficient 0.5·(a(0,0) + a(1,0)) becomes a(0,0) at the wall; a source that
+    wants something else tests s. Fields are zero until P.set_field(k, x) — x a device tensor or a NumPy array of nx·ny[·nz]
+    doubles, copied — and P.field(k) returns a device copy; P.nfields is their number. A field the source declares and does
+    not read costs nothing. Implicit time stepping, F(u) = (u − u_old)/dt − L(u) with u_old = a(0, 0, 0):
+        cache = init(NonlinearProblem(P, u0), alg)
+        for step in range(nsteps):
+            P.set_field(0, cache.u); reinit_(cache, u0=cache.u); solve_(cache)"""
     ctx = ctx or default_context()
     st, bd = _grid_ids(stencil, boundary)
     params = [float(x) for x in params]
     arr = (C.c_double * max(len(params), 1))(*params)
     h = C.c_void_p()
-    if nz is None:
+    if fields:
+        check(L.lib().nk_problem_create_grid_fields(ctx._h, source.encode(), nx, ny, 0 if nz is None else nz, dof, st, bd, arr,
+                                                    len(params), int(fields), C.byref(h)))
+    elif nz is None:
         check(L.lib().nk_problem_create_grid(ctx._h, source.encode(), nx, ny, dof, st, bd, arr, len(params), C.byref(h)))
     else:
         check(L.lib().nk_problem_create_grid3(ctx._h, source.encode(), nx, ny, nz, dof, st, bd, arr, len(params), C.byref(h)))
@@ -563,6 +605,7 @@ def CompiledGridProblem(source: str, nx: int, ny: int, dof: int = 1, stencil: st
     P.p, P.nx, P.ny, P.dof, P.stencil, P.boundary = params, nx, ny, dof, stencil, boundary
     if nz is not None:
         P.nz = nz
+    P.nfields = int(fields)
     return P
 
 

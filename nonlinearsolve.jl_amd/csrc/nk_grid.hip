@@ -39,9 +39,24 @@
 // from the text, comments included: even a changed comment would change their code objects). 2-D: the 9-point star with dof 1..2
 // (18 partials) and the 13-point diamond |di| + |dj| <= 2 with dof 1; 3-D: the 13-point star with dof 1..2 (26 partials, staged
 // LDS 53248 bytes). Every side >= 5, so that the five offsets of a direction are five distinct columns on the torus.
+//
+// Fields (nk_problem_create_grid_fields, nfields = 1..4): read-only arrays of one double per node — a previous time level, a
+// coefficient, a source term — which the source reads as a(di, dj, k) through the stencil's own offsets:
+//     template <typename T> __device__ void nk_point(const nk_nbhd<T> &u, const nk_flds &a, const nk_real *p, nk_site s, T *f);
+// Field k of node m is element k·nn + m of one buffer the problem owns (zero until nk_problem_set_field). The field neighbourhood
+// is loaded like u's — unconditionally, from the same idx[q], before the source runs — but without the select: outside a
+// Dirichlet boundary the clamped address is the node itself, and that value is what a field reads there (a face average
+// 0.5·(a(0,0) + a(1,0)) becomes a(0,0) at the wall); a periodic index wraps. A field value is an nk_real in all three kernels:
+// fields are constants of the differentiation. A load whose value the source never reads is dropped by the compiler (the
+// neighbourhood is a fully unrolled register array), so a declared field costs nothing until it is read. Per unknown, with r the
+// number of distinct fields the source reads: residual 16 + 8·r/dof bytes, JVP 24 + 8·r/dof, fill its figure + 8·r/dof (a field
+// line read by three lines of threads comes from cache, as for u). These programs carry -DNK_NFIELDS=<k>, one string of field
+// text after the types and two small pieces between the pieces of the kernels' text; the programs without fields are put
+// together from the same bytes and options as before.
 #include <math.h>
 #include <string.h>
 
+#include <initializer_list>
 #include <map>
 #include <mutex>
 #include <string>
@@ -134,7 +149,7 @@ static const char *k_grid_wrap_r1 = R"NKSRC(    ii = ii < 0 ? nx - 1 : (ii >= nx
 static const char *k_grid_wrap_r2 = R"NKSRC(    ii = ii < 0 ? ii + nx : (ii >= nx ? ii - nx : ii);
     jj = jj < 0 ? jj + ny : (jj >= ny ? jj - ny : jj);
 )NKSRC";
-static const char *k_grid_kernels_b = R"NKSRC(    in[q] = true;
+static const char *const k_grid_kernels_b[] = {R"NKSRC(    in[q] = true;
 #else
     in[q] = ii >= 0 && ii < nx && jj >= 0 && jj < ny;
     ii = in[q] ? ii : i;
@@ -146,7 +161,8 @@ static const char *k_grid_kernels_b = R"NKSRC(    in[q] = true;
 
 #if NK_GRID_SET == 0
 extern "C" __global__ void __launch_bounds__(NK_GRID_BLOCK)
-nk_grid_residual(int nx, int ny, const nk_real *__restrict__ p, const nk_real *__restrict__ u, nk_real *__restrict__ f) {
+nk_grid_residual(int nx, int ny, const nk_real *__restrict__ p, )NKSRC",
+    R"NKSRC(const nk_real *__restrict__ u, nk_real *__restrict__ f) {
   const int nn = nx * ny, node = (int)blockIdx.x * NK_GRID_BLOCK + (int)threadIdx.x;
   if (node >= nn) return;
   const int j = (int)((unsigned)node / (unsigned)nx), i = node - j * nx;
@@ -166,14 +182,15 @@ nk_grid_residual(int nx, int ny, const nk_real *__restrict__ p, const nk_real *_
 #pragma unroll
   for (int c = 0; c < NK_DOF; ++c) out[c] = NK_R(0);
   const nk_site s = {i, j, nx, ny};
-  nk_point<nk_real>(nb, p, s, out);
+  nk_point<nk_real>(nb, )NKSRC", R"NKSRC(p, s, out);
 #pragma unroll
   for (int c = 0; c < NK_DOF; ++c) f[c * nn + node] = out[c];
 }
 
 // J(u)·v exactly: the value of every neighbour from u, its one partial from v
 extern "C" __global__ void __launch_bounds__(NK_GRID_BLOCK)
-nk_grid_jvp(int nx, int ny, const nk_real *__restrict__ p, const nk_real *__restrict__ u, const nk_real *__restrict__ v,
+nk_grid_jvp(int nx, int ny, const nk_real *__restrict__ p, )NKSRC",
+    R"NKSRC(const nk_real *__restrict__ u, const nk_real *__restrict__ v,
             nk_real *__restrict__ jv) {
   const int nn = nx * ny, node = (int)blockIdx.x * NK_GRID_BLOCK + (int)threadIdx.x;
   if (node >= nn) return;
@@ -195,7 +212,7 @@ nk_grid_jvp(int nx, int ny, const nk_real *__restrict__ p, const nk_real *__rest
 #pragma unroll
   for (int c = 0; c < NK_DOF; ++c) out[c] = Dual(NK_R(0));
   const nk_site s = {i, j, nx, ny};
-  nk_point<Dual>(nb, p, s, out);
+  nk_point<Dual>(nb, )NKSRC", R"NKSRC(p, s, out);
 #pragma unroll
   for (int c = 0; c < NK_DOF; ++c) jv[c * nn + node] = out[c].d[0];
 }
@@ -205,7 +222,8 @@ nk_grid_jvp(int nx, int ny, const nk_real *__restrict__ p, const nk_real *__rest
 // NK_GRID_DIRECT = 0: the workgroup's rows of one component are one contiguous piece of the value array — they are put together
 // in LDS and stored as whole lines (k_bratu_jac's way); 1: every thread stores its own partials, 8 bytes at a stride of a row.
 extern "C" __global__ void __launch_bounds__(NK_GRID_BLOCK)
-nk_grid_jac(int nx, int ny, const nk_real *__restrict__ p, const nk_real *__restrict__ u, const int *__restrict__ rowptr,
+nk_grid_jac(int nx, int ny, const nk_real *__restrict__ p, )NKSRC",
+    R"NKSRC(const nk_real *__restrict__ u, const int *__restrict__ rowptr,
             nk_real *__restrict__ vals) {
   const int nn = nx * ny, node0 = (int)blockIdx.x * NK_GRID_BLOCK, node_t = node0 + (int)threadIdx.x;
   if (node0 >= nn) return;   // (a workgroup past the grid; the launch has none)
@@ -235,7 +253,7 @@ nk_grid_jac(int nx, int ny, const nk_real *__restrict__ p, const nk_real *__rest
 #pragma unroll
   for (int c = 0; c < NK_DOF; ++c) out[c] = Dual(NK_R(0));
   const nk_site s = {i, j, nx, ny};
-  nk_point<Dual>(nb, p, s, out);
+  nk_point<Dual>(nb, )NKSRC", R"NKSRC(p, s, out);
   int rank[NK_NPTS], cnt = 0;
 #pragma unroll
   for (int q = 0; q < NK_NPTS; ++q) {
@@ -276,11 +294,65 @@ nk_grid_jac(int nx, int ny, const nk_real *__restrict__ p, const nk_real *__rest
   }
 }
 #endif
-)NKSRC";
+)NKSRC"};
 
 static const char *k_grid_contract =
     "the contract is `template <typename T> __device__ void nk_point(const nk_nbhd<T> &u, const nk_real *p, nk_site s, T *f)` "
     "with u(di, dj, c) the component c at node (i + di, j + dj), s = {i, j, nx, ny}, p the parameters and f the node's dof "
+    "residuals (nk_real = double)";
+
+// ----------------------------------------------------------------------------- fields (programs with -DNK_NFIELDS=1..4 only)
+// Read-only data on the grid: NK_NFIELDS arrays of one double per node, read through the stencil's own offsets. This text follows
+// the types string (it needs NK_NPTS and the offset tables, whichever stencil they describe), and the two pieces below go between
+// the pieces of k_grid_kernels_b: one more pointer after `p` in every signature, the field neighbourhood in every nk_point call.
+// nk_flds_load is an argument of that call, so its loads — unconditional, from the addresses nk_grid_geom made for u — are issued
+// with u's, before the source runs; val is a fully unrolled register array filled from a __restrict__ const pointer, so a load
+// whose value the source never reads is dropped by the compiler. No select: outside a Dirichlet boundary idx[q] is the node
+// itself, and that is the value a field has there. A program without fields gets none of this text and neither piece.
+static const char *k_grid_fields = R"NKSRC(
+// ---- read-only fields on the grid: field k at the stencil's points (never a dual: a constant of the differentiation)
+__device__ constexpr int nk_pt_find(int di, int dj) {
+  for (int q = 0; q < NK_NPTS; ++q)
+    if (nk_pt_di(q) == di && nk_pt_dj(q) == dj) return q;
+  return -1;
+}
+struct nk_flds {
+  nk_real val[NK_NPTS * NK_NFIELDS];
+  // field k at node (i + di, j + dj): the offsets and the shape rule of u (outside the stencil's shape: NaN). Outside a
+  // Dirichlet boundary a field reads as at the node itself; at a periodic one the index wraps
+  __device__ __forceinline__ nk_real operator()(int di, int dj, int k = 0) const {
+    const int q = nk_pt_find(di, dj);
+    if (q < 0) return NK_R(__builtin_nan(""));
+    return val[q * NK_NFIELDS + k];
+  }
+};
+__device__ __forceinline__ nk_flds nk_flds_load(const nk_real *__restrict__ a, int nn, const int (&idx)[NK_NPTS]) {
+  nk_flds fl;
+#pragma unroll
+  for (int q = 0; q < NK_NPTS; ++q) {
+#pragma unroll
+    for (int k = 0; k < NK_NFIELDS; ++k) fl.val[q * NK_NFIELDS + k] = a[k * nn + idx[q]];
+  }
+  return fl;
+}
+)NKSRC";
+static const char *k_grid_fields_sig = "const nk_real *__restrict__ a, ";   // after `p` in the six kernel signatures
+static const char *k_grid_fields_call = "nk_flds_load(a, nn, idx), ";       // after `nb` in the six nk_point calls
+// the kernels' text: the pieces of k_grid_kernels_b / k_grid3_kernels_b with, for a program with fields, the signature piece
+// after every even piece and the call piece after every odd one (signature, call; three kernels)
+static std::string grid_join(const char *const (&pieces)[7], bool fields) {
+  std::string s;
+  for (int t = 0; t < 7; ++t) {
+    s += pieces[t];
+    if (fields && t < 6) s += t % 2 == 0 ? k_grid_fields_sig : k_grid_fields_call;
+  }
+  return s;
+}
+
+static const char *k_gridf_contract =
+    "the contract of a problem with fields is `template <typename T> __device__ void nk_point(const nk_nbhd<T> &u, "
+    "const nk_flds &a, const nk_real *p, nk_site s, T *f)` with u(di, dj, c) the component c at node (i + di, j + dj), "
+    "a(di, dj, k) the field k there (an nk_real, never a dual), s = {i, j, nx, ny}, p the parameters and f the node's dof "
     "residuals (nk_real = double)";
 
 // ----------------------------------------------------------------------------- device source, three dimensions
@@ -355,7 +427,7 @@ static const char *k_grid3_wrap_r2 = R"NKSRC(    ii = ii < 0 ? ii + nx : (ii >= 
     jj = jj < 0 ? jj + ny : (jj >= ny ? jj - ny : jj);
     kk = kk < 0 ? kk + nz : (kk >= nz ? kk - nz : kk);
 )NKSRC";
-static const char *k_grid3_kernels_b = R"NKSRC(    in[q] = true;
+static const char *const k_grid3_kernels_b[] = {R"NKSRC(    in[q] = true;
 #else
     in[q] = ii >= 0 && ii < nx && jj >= 0 && jj < ny && kk >= 0 && kk < nz;
     ii = in[q] ? ii : i;
@@ -373,7 +445,7 @@ static const char *k_grid3_kernels_b = R"NKSRC(    in[q] = true;
 
 #if NK_GRID_SET == 0
 extern "C" __global__ void __launch_bounds__(NK_GRID_BLOCK)
-nk_grid3_residual(int nx, int ny, int nz, const nk_real *__restrict__ p, const nk_real *__restrict__ u,
+nk_grid3_residual(int nx, int ny, int nz, const nk_real *__restrict__ p, )NKSRC", R"NKSRC(const nk_real *__restrict__ u,
                   nk_real *__restrict__ f) {
   const int nn = nx * ny * nz, node = (int)blockIdx.x * NK_GRID_BLOCK + (int)threadIdx.x;
   if (node >= nn) return;
@@ -394,14 +466,14 @@ nk_grid3_residual(int nx, int ny, int nz, const nk_real *__restrict__ p, const n
 #pragma unroll
   for (int c = 0; c < NK_DOF; ++c) out[c] = NK_R(0);
   const nk_site3 s = {i, j, k, nx, ny, nz};
-  nk_point<nk_real>(nb, p, s, out);
+  nk_point<nk_real>(nb, )NKSRC", R"NKSRC(p, s, out);
 #pragma unroll
   for (int c = 0; c < NK_DOF; ++c) f[c * nn + node] = out[c];
 }
 
 // J(u)·v exactly: the value of every neighbour from u, its one partial from v
 extern "C" __global__ void __launch_bounds__(NK_GRID_BLOCK)
-nk_grid3_jvp(int nx, int ny, int nz, const nk_real *__restrict__ p, const nk_real *__restrict__ u,
+nk_grid3_jvp(int nx, int ny, int nz, const nk_real *__restrict__ p, )NKSRC", R"NKSRC(const nk_real *__restrict__ u,
              const nk_real *__restrict__ v, nk_real *__restrict__ jv) {
   const int nn = nx * ny * nz, node = (int)blockIdx.x * NK_GRID_BLOCK + (int)threadIdx.x;
   if (node >= nn) return;
@@ -423,7 +495,7 @@ nk_grid3_jvp(int nx, int ny, int nz, const nk_real *__restrict__ p, const nk_rea
 #pragma unroll
   for (int c = 0; c < NK_DOF; ++c) out[c] = Dual(NK_R(0));
   const nk_site3 s = {i, j, k, nx, ny, nz};
-  nk_point<Dual>(nb, p, s, out);
+  nk_point<Dual>(nb, )NKSRC", R"NKSRC(p, s, out);
 #pragma unroll
   for (int c = 0; c < NK_DOF; ++c) jv[c * nn + node] = out[c].d[0];
 }
@@ -433,7 +505,7 @@ nk_grid3_jvp(int nx, int ny, int nz, const nk_real *__restrict__ p, const nk_rea
 // NK_GRID_DIRECT = 0: the workgroup's rows of one component are one contiguous piece of the value array — they are put together
 // in LDS and stored as whole lines; 1: every thread stores its own partials, 8 bytes at a stride of a row.
 extern "C" __global__ void __launch_bounds__(NK_GRID_BLOCK)
-nk_grid3_jac(int nx, int ny, int nz, const nk_real *__restrict__ p, const nk_real *__restrict__ u,
+nk_grid3_jac(int nx, int ny, int nz, const nk_real *__restrict__ p, )NKSRC", R"NKSRC(const nk_real *__restrict__ u,
              const int *__restrict__ rowptr, nk_real *__restrict__ vals) {
   const int nn = nx * ny * nz, node0 = (int)blockIdx.x * NK_GRID_BLOCK, node_t = node0 + (int)threadIdx.x;
   if (node0 >= nn) return;   // (a workgroup past the grid; the launch has none)
@@ -463,7 +535,7 @@ nk_grid3_jac(int nx, int ny, int nz, const nk_real *__restrict__ p, const nk_rea
 #pragma unroll
   for (int c = 0; c < NK_DOF; ++c) out[c] = Dual(NK_R(0));
   const nk_site3 s = {i, j, k, nx, ny, nz};
-  nk_point<Dual>(nb, p, s, out);
+  nk_point<Dual>(nb, )NKSRC", R"NKSRC(p, s, out);
   int rank[NK_NPTS], cnt = 0;
 #pragma unroll
   for (int q = 0; q < NK_NPTS; ++q) {
@@ -504,11 +576,45 @@ nk_grid3_jac(int nx, int ny, int nz, const nk_real *__restrict__ p, const nk_rea
   }
 }
 #endif
-)NKSRC";
+)NKSRC"};
 
 static const char *k_grid3_contract =
     "the contract is `template <typename T> __device__ void nk_point(const nk_nbhd3<T> &u, const nk_real *p, nk_site3 s, T *f)` "
     "with u(di, dj, dk, c) the component c at node (i + di, j + dj, k + dk), s = {i, j, k, nx, ny, nz}, p the parameters and f "
+    "the node's dof residuals (nk_real = double)";
+
+// fields in three dimensions: the same text over the 3-D offset tables, as nk_flds3 (the two pieces are the 2-D ones)
+static const char *k_grid3_fields = R"NKSRC(
+// ---- read-only fields on the grid: field k at the stencil's points (never a dual: a constant of the differentiation)
+__device__ constexpr int nk_pt_find(int di, int dj, int dk) {
+  for (int q = 0; q < NK_NPTS; ++q)
+    if (nk_pt_di(q) == di && nk_pt_dj(q) == dj && nk_pt_dk(q) == dk) return q;
+  return -1;
+}
+struct nk_flds3 {
+  nk_real val[NK_NPTS * NK_NFIELDS];
+  // field k at node (i + di, j + dj, k + dk): the offsets and the shape rule of u (outside the stencil's shape: NaN). Outside
+  // a Dirichlet boundary a field reads as at the node itself; at a periodic one the index wraps
+  __device__ __forceinline__ nk_real operator()(int di, int dj, int dk, int k = 0) const {
+    const int q = nk_pt_find(di, dj, dk);
+    if (q < 0) return NK_R(__builtin_nan(""));
+    return val[q * NK_NFIELDS + k];
+  }
+};
+__device__ __forceinline__ nk_flds3 nk_flds_load(const nk_real *__restrict__ a, int nn, const int (&idx)[NK_NPTS]) {
+  nk_flds3 fl;
+#pragma unroll
+  for (int q = 0; q < NK_NPTS; ++q) {
+#pragma unroll
+    for (int k = 0; k < NK_NFIELDS; ++k) fl.val[q * NK_NFIELDS + k] = a[k * nn + idx[q]];
+  }
+  return fl;
+}
+)NKSRC";
+static const char *k_grid3f_contract =
+    "the contract of a problem with fields is `template <typename T> __device__ void nk_point(const nk_nbhd3<T> &u, "
+    "const nk_flds3 &a, const nk_real *p, nk_site3 s, T *f)` with u(di, dj, dk, c) the component c at node (i + di, j + dj, "
+    "k + dk), a(di, dj, dk, k) the field k there (an nk_real, never a dual), s = {i, j, k, nx, ny, nz}, p the parameters and f "
     "the node's dof residuals (nk_real = double)";
 
 // ----------------------------------------------------------------------------- the stencil's CSR pattern (host only)
@@ -682,18 +788,22 @@ enum { GSET_F = 0 /* nk_grid_residual + nk_grid_jvp, NK_CH = 1 */, GSET_JAC = 1 
 
 // dim = 2: nk_grid_residual / nk_grid_jvp / nk_grid_jac; dim = 3: the nk_grid3_ kernels. The 3-D programs carry -DNK_DIM=3 (it
 // tells their cache entries from the 2-D ones of the same source); the 2-D programs get the text and the options they always had.
-static int grid_compile(const char *source, int dim, int dof, int stencil, int boundary, int np, int gset, bool direct,
+// nf = 0: the program without fields, from the text and the options it always had; nf = 1..4: the field text after the types,
+// the two field pieces in the kernels and one more option, -DNK_NFIELDS=<nf>, which also keeps the cache entries apart.
+static int grid_compile(const char *source, int dim, int dof, int stencil, int boundary, int np, int nf, int gset, bool direct,
                         std::vector<char> *code, std::string *log) {
   NK_REQUIRE(source, "NULL source");
   NK_TRY(dim == 3 ? grid3_check_shape(dof, stencil, boundary) : grid_check_shape(dof, stencil, boundary));
   NK_REQUIRE(np >= 0 && np <= 32, "nparams = %d outside 0..32", np);
+  NK_REQUIRE(nf >= 0 && nf <= 4, "nfields = %d outside 0..4 (read-only fields of one double per node)", nf);
   const int npts = grid_npts(dim, stencil);
   const bool r2 = grid_radius(stencil) == 2;
   const char *types = dim == 3 ? (r2 ? k_grid3_types_r2 : k_grid3_types) : (r2 ? k_grid_types_r2 : k_grid_types);
-  const std::string full = std::string(nk_dual_prelude) + types + "\n// ---- user source\n" + source + "\n" +
+  const std::string full = std::string(nk_dual_prelude) + types + (nf > 0 ? (dim == 3 ? k_grid3_fields : k_grid_fields) : "") +
+                           "\n// ---- user source\n" + source + "\n" +
                            (dim == 3 ? k_grid3_kernels_a : k_grid_kernels_a) +
                            (dim == 3 ? (r2 ? k_grid3_wrap_r2 : k_grid3_wrap_r1) : (r2 ? k_grid_wrap_r2 : k_grid_wrap_r1)) +
-                           (dim == 3 ? k_grid3_kernels_b : k_grid_kernels_b);
+                           (dim == 3 ? grid_join(k_grid3_kernels_b, nf > 0) : grid_join(k_grid_kernels_b, nf > 0));
   const std::string dd = "-DNK_DOF=" + std::to_string(dof), db = std::string("-DNK_BOX=") + (stencil == NK_GRID_BOX ? "1" : "0"),
                     dp = std::string("-DNK_PERIODIC=") + (boundary == NK_GRID_PERIODIC ? "1" : "0"),
                     dc = "-DNK_CH=" + std::to_string(gset == GSET_JAC ? npts * dof : 1), ds = "-DNK_GRID_SET=" + std::to_string(gset),
@@ -705,6 +815,8 @@ static int grid_compile(const char *source, int dim, int dof, int stencil, int b
   // their cache entries apart from the radius-1 programs of the same source)
   const std::string dn = "-DNK_STENCIL=" + std::to_string(stencil);
   if (r2) opts.push_back(dn.c_str());
+  const std::string df = "-DNK_NFIELDS=" + std::to_string(nf);
+  if (nf > 0) opts.push_back(df.c_str());
   // the same source with the same options gives the same code object: problems created again (another grid size, another
   // context) skip the compiler
   static std::mutex mtx;
@@ -721,7 +833,8 @@ static int grid_compile(const char *source, int dim, int dof, int stencil, int b
   bool failed = false;
   NK_TRY(nk_rtc_compile(full, "nk_grid_user.hip", opts, code, log, &failed));
   if (failed)
-    NK_FAIL(NK_E_INVALID, "grid residual source does not compile (%s): %.900s", dim == 3 ? k_grid3_contract : k_grid_contract,
+    NK_FAIL(NK_E_INVALID, "grid residual source does not compile (%s): %.900s",
+            dim == 3 ? (nf > 0 ? k_grid3f_contract : k_grid3_contract) : (nf > 0 ? k_gridf_contract : k_grid_contract),
             log && !log->empty() ? log->c_str() : "(no log)");
   std::lock_guard<std::mutex> lock(mtx);
   cache[key] = *code;
@@ -735,32 +848,39 @@ static bool grid_fill_direct() {   // (read at every create: tools/grid_problem_
 }
 
 // compile only (no device needed): both programs
-static int grid_compile_check(const char *source, int dim, int dof, int stencil, int boundary, int nparams, int64_t *code_bytes) {
+static int grid_compile_check(const char *source, int dim, int dof, int stencil, int boundary, int nparams, int nfields,
+                              int64_t *code_bytes) {
   std::vector<char> code;
   std::string log;
   int64_t total = 0;
   for (int gset : {GSET_F, GSET_JAC}) {
     log.clear();
-    NK_TRY(grid_compile(source, dim, dof, stencil, boundary, nparams, gset, grid_fill_direct(), &code, &log));
+    NK_TRY(grid_compile(source, dim, dof, stencil, boundary, nparams, nfields, gset, grid_fill_direct(), &code, &log));
     total += (int64_t)code.size();
   }
   if (code_bytes) *code_bytes = total;
   return NK_OK;
 }
 extern "C" int nk_grid_compile_check(const char *source, int dof, int stencil, int boundary, int nparams, int64_t *code_bytes) {
-  return grid_compile_check(source, 2, dof, stencil, boundary, nparams, code_bytes);
+  return grid_compile_check(source, 2, dof, stencil, boundary, nparams, 0, code_bytes);
 }
 extern "C" int nk_grid3_compile_check(const char *source, int dof, int stencil, int boundary, int nparams, int64_t *code_bytes) {
-  return grid_compile_check(source, 3, dof, stencil, boundary, nparams, code_bytes);
+  return grid_compile_check(source, 3, dof, stencil, boundary, nparams, 0, code_bytes);
+}
+extern "C" int nk_grid_fields_compile_check(const char *source, int dim, int dof, int stencil, int boundary, int nparams,
+                                            int nfields, int64_t *code_bytes) {
+  NK_REQUIRE(dim == 2 || dim == 3, "dim = %d is neither 2 nor 3", dim);
+  return grid_compile_check(source, dim, dof, stencil, boundary, nparams, nfields, code_bytes);
 }
 
 // the code object of one program (jac = 0: the residual and JVP kernels; 1: the Jacobian fill) for inspection
-static int grid_code_object(const char *source, int dim, int dof, int stencil, int boundary, int nparams, int jac, void *buf,
-                            int64_t capacity, int64_t *bytes) {
+static int grid_code_object(const char *source, int dim, int dof, int stencil, int boundary, int nparams, int nfields, int jac,
+                            void *buf, int64_t capacity, int64_t *bytes) {
   NK_REQUIRE(bytes, "NULL argument");
   std::vector<char> code;
   std::string log;
-  NK_TRY(grid_compile(source, dim, dof, stencil, boundary, nparams, jac != 0 ? GSET_JAC : GSET_F, grid_fill_direct(), &code, &log));
+  NK_TRY(grid_compile(source, dim, dof, stencil, boundary, nparams, nfields, jac != 0 ? GSET_JAC : GSET_F, grid_fill_direct(), &code,
+                      &log));
   *bytes = (int64_t)code.size();
   if (!buf) return NK_OK;
   NK_REQUIRE(capacity >= *bytes, "buffer of %lld bytes, the code object has %lld", (long long)capacity, (long long)*bytes);
@@ -769,20 +889,26 @@ static int grid_code_object(const char *source, int dim, int dof, int stencil, i
 }
 extern "C" int nk_grid_code_object(const char *source, int dof, int stencil, int boundary, int nparams, int jac, void *buf,
                                    int64_t capacity, int64_t *bytes) {
-  return grid_code_object(source, 2, dof, stencil, boundary, nparams, jac, buf, capacity, bytes);
+  return grid_code_object(source, 2, dof, stencil, boundary, nparams, 0, jac, buf, capacity, bytes);
 }
 extern "C" int nk_grid3_code_object(const char *source, int dof, int stencil, int boundary, int nparams, int jac, void *buf,
                                     int64_t capacity, int64_t *bytes) {
-  return grid_code_object(source, 3, dof, stencil, boundary, nparams, jac, buf, capacity, bytes);
+  return grid_code_object(source, 3, dof, stencil, boundary, nparams, 0, jac, buf, capacity, bytes);
+}
+extern "C" int nk_grid_fields_code_object(const char *source, int dim, int dof, int stencil, int boundary, int nparams, int nfields,
+                                          int jac, void *buf, int64_t capacity, int64_t *bytes) {
+  NK_REQUIRE(dim == 2 || dim == 3, "dim = %d is neither 2 nor 3", dim);
+  return grid_code_object(source, dim, dof, stencil, boundary, nparams, nfields, jac, buf, capacity, bytes);
 }
 
 // ----------------------------------------------------------------------------- the problem object
 struct nk_grid_state {
   nk_ctx *ctx = nullptr;
-  int nx = 0, ny = 0, nz = 0 /* 0: a 2-D problem */, dof = 0, np = 0;
+  int nx = 0, ny = 0, nz = 0 /* 0: a 2-D problem */, dof = 0, np = 0, nfields = 0;
   hipModule_t mod_f = nullptr, mod_jac = nullptr;
   hipFunction_t fn_res = nullptr, fn_jvp = nullptr, fn_jac = nullptr;
   double *d_params = nullptr;   // np doubles (at least one allocated): the source's p
+  double *d_fields = nullptr;   // nfields·nn doubles, field k of node m at k·nn + m (NULL without fields); zero at creation
   nk_csr *pattern = nullptr;    // the problem's user_pattern
 };
 
@@ -791,6 +917,7 @@ void nk_grid_state_destroy(nk_grid_state *S) {
   if (S->mod_f) hipModuleUnload(S->mod_f);
   if (S->mod_jac) hipModuleUnload(S->mod_jac);
   hipFree(S->d_params);
+  hipFree(S->d_fields);
   nk_csr_destroy(S->pattern);
   delete S;
 }
@@ -809,23 +936,31 @@ static int grid_launch(nk_grid_state *S, hipFunction_t fn, void **args, void *st
   return e != hipSuccess;
 }
 
-// the callbacks of the problem: launches of the generated kernels on the stream they are handed
+// the callbacks of the problem: launches of the generated kernels on the stream they are handed. The argument list is
+// nx, ny, [nz,] p, [fields,] and the kernel's own vectors: the sizes, then what the problem owns, then `rest`
+static int grid_launch_args(nk_grid_state *S, hipFunction_t fn, std::initializer_list<void *> rest, void *stream) {
+  void *args[10];
+  int n = 0;
+  args[n++] = &S->nx;
+  args[n++] = &S->ny;
+  if (S->nz > 0) args[n++] = &S->nz;
+  args[n++] = &S->d_params;
+  if (S->nfields > 0) args[n++] = &S->d_fields;
+  for (void *a : rest) args[n++] = a;
+  return grid_launch(S, fn, args, stream);
+}
 static int grid_cb_residual(void *user, const double *u, double *f, void *stream) {
   nk_grid_state *S = (nk_grid_state *)user;
-  void *args[] = {&S->nx, &S->ny, &S->d_params, &u, &f}, *args3[] = {&S->nx, &S->ny, &S->nz, &S->d_params, &u, &f};
-  return grid_launch(S, S->fn_res, S->nz > 0 ? args3 : args, stream);
+  return grid_launch_args(S, S->fn_res, {&u, &f}, stream);
 }
 static int grid_cb_jvp(void *user, const double *v, const double *u, double *jv, void *stream) {
   nk_grid_state *S = (nk_grid_state *)user;
-  void *args[] = {&S->nx, &S->ny, &S->d_params, &u, &v, &jv}, *args3[] = {&S->nx, &S->ny, &S->nz, &S->d_params, &u, &v, &jv};
-  return grid_launch(S, S->fn_jvp, S->nz > 0 ? args3 : args, stream);
+  return grid_launch_args(S, S->fn_jvp, {&u, &v, &jv}, stream);
 }
 static int grid_cb_jac(void *user, const double *u, double *vals, void *stream) {
   nk_grid_state *S = (nk_grid_state *)user;
   const int32_t *rowptr = S->pattern->d_rowptr;
-  void *args[] = {&S->nx, &S->ny, &S->d_params, &u, &rowptr, &vals},
-       *args3[] = {&S->nx, &S->ny, &S->nz, &S->d_params, &u, &rowptr, &vals};
-  return grid_launch(S, S->fn_jac, S->nz > 0 ? args3 : args, stream);
+  return grid_launch_args(S, S->fn_jac, {&u, &rowptr, &vals}, stream);
 }
 
 int nk_grid_set_params(nk_problem *P, const double *params, int nparams) {
@@ -839,12 +974,49 @@ int nk_grid_set_params(nk_problem *P, const double *params, int nparams) {
   return NK_OK;
 }
 
+// field k of a problem with fields: its nn doubles on the device
+static int grid_field_ptr(nk_problem *P, int k, double **d_field, size_t *bytes) {
+  NK_REQUIRE(P, "NULL argument");
+  NK_REQUIRE(P->grid, "the problem is not a compiled grid problem (kind %d): it has no fields", (int)P->kind);
+  nk_grid_state *S = P->grid;
+  NK_REQUIRE(S->nfields > 0, "the problem was created with nfields = %d: it has no fields (nk_problem_create_grid_fields)",
+             S->nfields);
+  NK_REQUIRE(k >= 0 && k < S->nfields, "field k = %d outside 0..%d", k, S->nfields - 1);
+  const size_t nn = (size_t)S->nx * S->ny * (S->nz > 0 ? S->nz : 1);
+  *d_field = S->d_fields + (size_t)k * nn;
+  *bytes = nn * sizeof(double);
+  return NK_OK;
+}
+extern "C" int nk_problem_set_field(nk_problem *P, int k, const double *data, int memspace) {
+  double *d = nullptr;
+  size_t bytes = 0;
+  NK_TRY(grid_field_ptr(P, k, &d, &bytes));
+  NK_REQUIRE(data, "NULL data");
+  NK_REQUIRE(memspace == NK_HOST || memspace == NK_DEVICE, "memspace = %d is neither NK_HOST nor NK_DEVICE", memspace);
+  NK_HIP(hipSetDevice(P->grid->ctx->device));
+  NK_HIP(nk_memcpy(P->grid->ctx, d, data, bytes, memspace == NK_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice));
+  P->params_version++;
+  nk_problem_invalidate(P);   // a Jacobian cached for the same u belongs to the old field
+  return NK_OK;
+}
+extern "C" int nk_problem_get_field(nk_problem *P, int k, double *out, int memspace) {
+  double *d = nullptr;
+  size_t bytes = 0;
+  NK_TRY(grid_field_ptr(P, k, &d, &bytes));
+  NK_REQUIRE(out, "NULL out");
+  NK_REQUIRE(memspace == NK_HOST || memspace == NK_DEVICE, "memspace = %d is neither NK_HOST nor NK_DEVICE", memspace);
+  NK_HIP(hipSetDevice(P->grid->ctx->device));
+  NK_HIP(nk_memcpy(P->grid->ctx, out, d, bytes, memspace == NK_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost));
+  return NK_OK;
+}
+
 // nz = 0: a 2-D problem (nk_problem_create_grid); nz > 0: a 3-D one (nk_problem_create_grid3)
 static int grid_create(nk_ctx *ctx, const char *source, int64_t nx, int64_t ny, int64_t nz, int dof, int stencil, int boundary,
-                       const double *params, int nparams, nk_problem **out) {
+                       const double *params, int nparams, int nfields, nk_problem **out) {
   const int dim = nz > 0 ? 3 : 2;
   NK_REQUIRE(ctx && source && out, "NULL argument");
   NK_REQUIRE(params || nparams == 0, "NULL params with nparams = %d", nparams);
+  NK_REQUIRE(nfields >= 0 && nfields <= 4, "nfields = %d outside 0..4 (read-only fields of one double per node)", nfields);
   if (ctx->nranks > 1)
     NK_FAIL(NK_E_UNSUPPORTED, "compiled grid problems run on one rank (this context has %d): no halo exchange is generated",
             ctx->nranks);
@@ -861,9 +1033,9 @@ static int grid_create(nk_ctx *ctx, const char *source, int64_t nx, int64_t ny, 
   NK_TRY(pattern(rp.data(), ci.data()));
   std::vector<char> code_f, code_j;
   std::string log;
-  NK_TRY(grid_compile(source, dim, dof, stencil, boundary, nparams, GSET_F, false, &code_f, &log));
+  NK_TRY(grid_compile(source, dim, dof, stencil, boundary, nparams, nfields, GSET_F, false, &code_f, &log));
   log.clear();
-  NK_TRY(grid_compile(source, dim, dof, stencil, boundary, nparams, GSET_JAC, grid_fill_direct(), &code_j, &log));
+  NK_TRY(grid_compile(source, dim, dof, stencil, boundary, nparams, nfields, GSET_JAC, grid_fill_direct(), &code_j, &log));
 
   nk_grid_state *S = new nk_grid_state();
   auto guard = nk_make_guard(S, nk_grid_state_destroy);
@@ -873,6 +1045,7 @@ static int grid_create(nk_ctx *ctx, const char *source, int64_t nx, int64_t ny, 
   S->nz = dim == 3 ? (int)nz : 0;
   S->dof = dof;
   S->np = nparams;
+  S->nfields = nfields;
   if (hipModuleLoadData(&S->mod_f, code_f.data()) != hipSuccess || hipModuleLoadData(&S->mod_jac, code_j.data()) != hipSuccess)
     NK_FAIL(NK_E_HIP, "hipModuleLoadData failed");
   if (hipModuleGetFunction(&S->fn_res, S->mod_f, dim == 3 ? "nk_grid3_residual" : "nk_grid_residual") != hipSuccess ||
@@ -881,6 +1054,11 @@ static int grid_create(nk_ctx *ctx, const char *source, int64_t nx, int64_t ny, 
     NK_FAIL(NK_E_HIP, "a generated grid kernel is missing from the compiled module");
   NK_TRY(nk_dev_alloc(&S->d_params, (size_t)(nparams > 0 ? nparams : 1)));
   if (nparams > 0) NK_HIP(nk_memcpy(ctx, S->d_params, params, (size_t)nparams * sizeof(double), hipMemcpyHostToDevice));
+  if (nfields > 0) {   // zero until nk_problem_set_field: nothing is ever read uninitialised
+    const size_t cnt = (size_t)nfields * (size_t)(n / dof);
+    NK_TRY(nk_dev_alloc(&S->d_fields, cnt));
+    NK_HIP(nk_memset(ctx, S->d_fields, 0, cnt * sizeof(double)));
+  }
   std::vector<int64_t> gc(ci.begin(), ci.end());
   NK_TRY(nk_csr_create_local(ctx, n, n, 0, rp, gc, nullptr, &S->pattern));
 
@@ -904,12 +1082,20 @@ static int grid_create(nk_ctx *ctx, const char *source, int64_t nx, int64_t ny, 
 
 extern "C" int nk_problem_create_grid(nk_ctx *ctx, const char *source, int64_t nx, int64_t ny, int dof, int stencil, int boundary,
                                       const double *params, int nparams, nk_problem **out) {
-  return grid_create(ctx, source, nx, ny, 0, dof, stencil, boundary, params, nparams, out);
+  return grid_create(ctx, source, nx, ny, 0, dof, stencil, boundary, params, nparams, 0, out);
 }
 
 extern "C" int nk_problem_create_grid3(nk_ctx *ctx, const char *source, int64_t nx, int64_t ny, int64_t nz, int dof, int stencil,
                                        int boundary, const double *params, int nparams, nk_problem **out) {
   // (grid_create tells the dimensions apart by nz > 0: a side below 3 must not fall through to the 2-D path)
   if (nz < 3) NK_TRY(grid3_check_size(nx, ny, nz, stencil));
-  return grid_create(ctx, source, nx, ny, nz, dof, stencil, boundary, params, nparams, out);
+  return grid_create(ctx, source, nx, ny, nz, dof, stencil, boundary, params, nparams, 0, out);
+}
+
+// fields: nz = 0 is the 2-D problem, nz >= 3 the 3-D one; nfields = 0 gives the problem of the two entry points above
+extern "C" int nk_problem_create_grid_fields(nk_ctx *ctx, const char *source, int64_t nx, int64_t ny, int64_t nz, int dof,
+                                             int stencil, int boundary, const double *params, int nparams, int nfields,
+                                             nk_problem **out) {
+  if (nz != 0 && nz < 3) NK_TRY(grid3_check_size(nx, ny, nz, stencil));
+  return grid_create(ctx, source, nx, ny, nz, dof, stencil, boundary, params, nparams, nfields, out);
 }

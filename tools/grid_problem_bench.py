@@ -26,6 +26,15 @@ and JVP move the same algorithmic bytes in both (16 n, 24 n): a time ratio above
 8 nnz / n and is compared in GB/s.
 
     python tools/grid_problem_bench.py --radius 2 [--out profiles/grid_r2_problem_bench.txt] [--grid 1024] [--grid3 256]
+
+`--fields` measures what a read-only field costs (nk_problem_create_grid_fields), at `--grid`² (1024²) and at `--grid2`² (4096²,
+which does not fit the Infinity Cache): (a) the Bratu source without fields as the yardstick, (b) bratu_f of
+tests/gridf_reference.py, one field read at the centre, (c) a source reading one field at all five points, (d) source (b)
+compiled with four fields declared — same process, same protocol, the problems alternating. Algorithmic bytes grow by 8 n per
+field read (dof = 1). Expected, and nothing is tuned to it: (b)/(a) near the byte ratio (24/16 residual, 32/24 JVP), (c) within
+the p10–p90 spread of (b) since the extra reads are cache hits, (d) indistinguishable from (b).
+
+    python tools/grid_problem_bench.py --fields [--out profiles/gridf_problem_bench.txt] [--grid 1024] [--grid2 4096]
 """
 import argparse
 import os
@@ -98,16 +107,53 @@ def main_radius2(args):
     generated_kernels(args, "Compiled grid problems with a radius-2 stencil beside their radius-1 twins at equal unknowns", cases)
 
 
-def generated_kernels(args, title, cases):
-    """the three generated kernels of every case, the fill in both forms, ordered by kernel so that the cases alternate"""
+# one field at all five points: Bratu with the source strength averaged over the star
+BRATU_F5_SRC = """
+template <typename T>
+__device__ void nk_point(const nk_nbhd<T> &u, const nk_flds &a, const nk_real *p, nk_site s, T *f) {
+  const T c = u(0, 0);
+  const nk_real w = 0.2 * (a(0, 0) + a(-1, 0) + a(1, 0) + a(0, -1) + a(0, 1));
+  f[0] = p[0] * (4.0 * c - u(-1, 0) - u(1, 0) - u(0, -1) - u(0, 1)) - (p[1] * w) * exp(c);
+}
+"""
+
+
+def main_fields(args):
+    """what a field costs: no field, one read at the centre, one read at five points, four declared and one read"""
+    import gridf_reference as RF
+    cases = []
+    for g in (args.grid, args.grid2):
+        par = R.bratu_params(g, 6.0)
+        cases += [   # label, source, shape, stencil, parameters, fields declared, fields read
+            (f"(a) bratu {g}^2, no field", R.BRATU_SRC, (g, g, None), "star", par, 0, 0),
+            (f"(b) bratu_f {g}^2, 1 field at the centre", RF.BRATU_F_SRC, (g, g, None), "star", par, 1, 1),
+            (f"(c) bratu_f5 {g}^2, 1 field at 5 points", BRATU_F5_SRC, (g, g, None), "star", par, 1, 1),
+            (f"(d) bratu_f {g}^2, 4 declared, 1 read", RF.BRATU_F_SRC, (g, g, None), "star", par, 4, 1),
+        ]
+    generated_kernels(args, "Compiled grid problems with read-only fields beside the same problem without", cases, direct=False)
+
+
+def generated_kernels(args, title, cases, direct=True):
+    """the three generated kernels of every case, the fill in both forms (direct = False: the default form only), ordered by
+    kernel so that the cases alternate. A case may end with (fields declared, fields read): the fields hold seeded positive
+    data, and every kernel's algorithmic bytes grow by 8 n per field read."""
     ctx = nls.default_context()
     gen = torch.Generator(device="cuda").manual_seed(1)
     calls, meta, problems, sizes = {}, {}, [], []   # meta: label → (kind rank, algorithmic bytes, unknowns)
-    for label, src, (nx, ny, nz), stencil, par in cases:
-        P = nls.CompiledGridProblem(src, nx, ny, stencil=stencil, params=par, nz=nz)
-        os.environ["NK_GRID_FILL_DIRECT"] = "1"
-        Pd = nls.CompiledGridProblem(src, nx, ny, stencil=stencil, params=par, nz=nz)
-        del os.environ["NK_GRID_FILL_DIRECT"]
+    for label, src, (nx, ny, nz), stencil, par, *fld in cases:
+        nf, nread = fld if fld else (0, 0)
+
+        def create():
+            P = nls.CompiledGridProblem(src, nx, ny, stencil=stencil, params=par, nz=nz, fields=nf)
+            for k in range(nf):
+                P.set_field(k, 0.5 + torch.rand(P.nn, dtype=torch.float64, device="cuda", generator=gen))
+            return P
+        P = create()
+        Pd = P
+        if direct:
+            os.environ["NK_GRID_FILL_DIRECT"] = "1"
+            Pd = create()
+            del os.environ["NK_GRID_FILL_DIRECT"]
         n = P.n_local
         u = 2.0 * torch.rand(n, dtype=torch.float64, device="cuda", generator=gen) - 1.0
         v = 2.0 * torch.rand(n, dtype=torch.float64, device="cuda", generator=gen) - 1.0
@@ -121,20 +167,24 @@ def generated_kernels(args, title, cases):
         assert torch.equal(J.matvec(v), Jd.matvec(v))
         sizes.append(f"{label}: n = {n}, nnz = {nnz} ({nnz / n:.2f} per row)")
         print("built and checked " + sizes[-1], flush=True)
-        kinds = [("residual", lambda P=P, u=u: P.residual(u), "residual", 16.0 * n),
-                 ("JVP", lambda P=P, u=u, v=v: P.jvp(v, u), "jvp", 24.0 * n),
-                 ("fill (LDS-staged rows)", lambda P=P, u=u, J=J: P.jac_values(u, J), "jacfill", 8.0 * nnz + 12.0 * n),
-                 ("fill (direct stores)", lambda Pd=Pd, u=u, Jd=Jd: Pd.jac_values(u, Jd), "jacfill", 8.0 * nnz + 12.0 * n)]
+        fb = 8.0 * nread * (n // P.dof)   # a field read once per node
+        kinds = [("residual", lambda P=P, u=u: P.residual(u), "residual", 16.0 * n + fb),
+                 ("JVP", lambda P=P, u=u, v=v: P.jvp(v, u), "jvp", 24.0 * n + fb),
+                 ("fill (LDS-staged rows)", lambda P=P, u=u, J=J: P.jac_values(u, J), "jacfill", 8.0 * nnz + 12.0 * n + fb),
+                 ("fill (direct stores)", lambda Pd=Pd, u=u, Jd=Jd: Pd.jac_values(u, Jd), "jacfill", 8.0 * nnz + 12.0 * n + fb)]
+        if not direct:
+            kinds.pop()
         for what, fn, fam, b in kinds:
             calls[f"{what:24s} {label}"] = (fn, fam)
             meta[f"{what:24s} {label}"] = (("res", "JVP", "fill (L", "fill (d").index(what[:7] if what[:4] == "fill" else what[:3]), b, n)
-        problems += [P, Pd]
+        problems += [P, Pd] if direct else [P]
     # (ordered by kernel, so that the 2-D yardstick and the 3-D kernels of one kind alternate)
     order = sorted(calls, key=lambda k: meta[k][0])
     ts = kernel_samples(ctx, {k: calls[k] for k in order}, args.reps)
     lines = [f"{title}, {torch.cuda.get_device_name(0)}"] + sizes + [
              f"kernel begin -> end device timestamps, one launch per sample, problems alternating, {args.reps} samples after 20;",
-             "GB/s on algorithmic bytes: residual 16 n, JVP 24 n, fill 8 nnz + 12 n (dof = 1)", "",
+             "GB/s on algorithmic bytes: residual 16 n, JVP 24 n, fill 8 nnz + 12 n (dof = 1)" +
+             (", each + 8 n per field read" if any(len(c) > 5 for c in cases) else ""), "",
              f"  {'kernel':56s} {'median us':>10s} {'p10':>9s} {'p90':>9s} {'GB/s (median)':>14s}  {'ns/unknown':>10s}  algorithmic MB"]
     for label in order:
         t = ts[label]
@@ -142,6 +192,14 @@ def generated_kernels(args, title, cases):
         _rank, b, n = meta[label]
         lines.append(f"  {label:56s} {med:10.2f} {t[len(t) // 10]:9.2f} {t[(9 * len(t)) // 10]:9.2f} "
                      f"{b / med / 1e3:14.1f}  {1e3 * med / n:10.4f}  {b / 1e6:.1f}")
+    if any(len(c) > 5 for c in cases):   # the fields protocol: time ratios between the cases (a) … (d) of one size
+        lines += ["", "time ratios of the medians (expected: (b)/(a) near the byte ratio 24/16 residual, 32/24 JVP; (c)/(b) and (d)/(b) near 1)"]
+        med = {k: statistics.median(ts[k]) for k in order}
+        for what in ("residual", "JVP", "fill (LDS-staged rows)"):
+            for size in sorted({c[2][0] for c in cases}):
+                m = {c[0][:3]: med[f"{what:24s} {c[0]}"] for c in cases if c[2][0] == size}
+                lines.append(f"  {what:24s} {size}^2: (b)/(a) {m['(b)'] / m['(a)']:.3f}   (c)/(b) {m['(c)'] / m['(b)']:.3f}   "
+                             f"(d)/(b) {m['(d)'] / m['(b)']:.3f}")
     text = "\n".join(lines) + "\n"
     print(text)
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
@@ -156,6 +214,7 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--dim", type=int, default=2, choices=(2, 3))
     ap.add_argument("--radius", type=int, default=1, choices=(1, 2))
+    ap.add_argument("--fields", action="store_true")
     ap.add_argument("--grid3", type=int, default=256)
     ap.add_argument("--box3", type=int, default=160)
     ap.add_argument("--grid2", type=int, default=4096)
@@ -166,7 +225,10 @@ def main():
     args = ap.parse_args()
     if args.out is None:
         name = "grid_r2_problem_bench.txt" if args.radius == 2 else ("grid3_problem_bench.txt" if args.dim == 3 else "grid_problem_bench.txt")
+        name = "gridf_problem_bench.txt" if args.fields else name
         args.out = os.path.join(ROOT, "profiles", name)
+    if args.fields:
+        return main_fields(args)
     if args.radius == 2:
         return main_radius2(args)
     if args.dim == 3:
