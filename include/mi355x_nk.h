@@ -489,9 +489,9 @@ int nk_jac_values_colored(nk_problem *P, const double *u, int memspace, nk_csr *
  * SciMLJacobianOperators differentiate with forward-mode duals (J·v) and sparse AD fill into `jac_prototype`. `source` is HIP C++
  * defining
  *     template <typename T> __device__ void nk_point(const nk_nbhd<T> &u, const nk_real *p, nk_site s, T *f);
- * with  u(di, dj, c = 0)  component c at node (i + di, j + dj), di, dj ∈ {−1, 0, 1} (write them as constants). With
- *                         NK_GRID_STAR a corner read (di != 0 && dj != 0) returns NaN, so a source written for the box shows
- *                         at the first residual;
+ * with  u(di, dj, c = 0)  component c at node (i + di, j + dj), di, dj ∈ {−1, 0, 1} (write them as constants). An offset
+ *                         that is no point of the stencil returns NaN — a corner (di != 0 && dj != 0) with NK_GRID_STAR,
+ *                         anything two nodes away with either stencil — so a wrong source shows at the first residual;
  *       s                 {i, j, nx, ny}: the node and the grid;
  *       p                 nparams doubles, 0..32 (nk_problem_set_params replaces them);
  *       f                 receives the node's dof residuals (entries the source does not write are zero);
@@ -518,8 +518,9 @@ int nk_jac_values_colored(nk_problem *P, const double *u, int memspace, nk_csr *
  * five distinct columns on the torus. Points in pattern order (ascending node index inside the grid), as (di, dj):
  *   STAR2     (0,−2) (0,−1) (−2,0) (−1,0) C (1,0) (2,0) (0,1) (0,2)
  *   DIAMOND2  (0,−2) (−1,−1) (0,−1) (1,−1) (−2,0) (−1,0) C (1,0) (2,0) (−1,1) (0,1) (1,1) (0,2)
- * Their programs carry one more option, -DNK_STENCIL=<code>; the radius-1 programs are compiled from the text and the options
- * they always had. Every other code (2, 18, …) is NK_E_INVALID. */
+ * Every program is compiled from one text, which starts with its stencil's point count and offsets, and with one full set of
+ * options (-DNK_DIM, -DNK_NFIELDS, -DNK_DOF, -DNK_PERIODIC, -DNK_CH, -DNK_GRID_SET, -DNK_GRID_DIRECT). Every other code
+ * (2, 18, …) is NK_E_INVALID. */
 enum { NK_GRID_STAR = 0, NK_GRID_BOX = 1, NK_GRID_STAR2 = 16, NK_GRID_DIAMOND2 = 17 }; /* stencil  */
 enum { NK_GRID_DIRICHLET0 = 0, NK_GRID_PERIODIC = 1 }; /* boundary */
 /* The CSR pattern of the Jacobian (host only, no device needed): rowptr dof·nx·ny + 1 entries, colind *nnz entries, 0-based,
@@ -538,8 +539,8 @@ int nk_problem_create_grid(nk_ctx *ctx, const char *source, int64_t nx, int64_t 
 /* Three dimensions. The same three kernels, generated from a source written against the 3-D neighbourhood:
  *     template <typename T> __device__ void nk_point(const nk_nbhd3<T> &u, const nk_real *p, nk_site3 s, T *f);
  * with  u(di, dj, dk, c = 0)  component c at node (i + di, j + dj, k + dk), every offset ∈ {−1, 0, 1} (constants, or the
- *                             counters of `#pragma unroll` loops). With NK_GRID_STAR a read with more than one non-zero offset
- *                             (an edge or a corner) returns NaN, as the 2-D star's corner read does;
+ *                             counters of `#pragma unroll` loops). An offset that is no point of the stencil returns NaN, as
+ *                             in 2-D: with NK_GRID_STAR a read with more than one non-zero offset (an edge or a corner);
  *       s                     nk_site3 {i, j, k, nx, ny, nz};
  *       p, f, nk_real         as in 2-D.
  * Geometry: nx × ny × nz nodes, nx, ny, nz >= 3; unknown c of node (i, j, k) is element c·nx·ny·nz + (k·ny + j)·nx + i
@@ -583,8 +584,8 @@ int nk_problem_create_grid3(nk_ctx *ctx, const char *source, int64_t nx, int64_t
  * compiled grid problem and for one created without fields; nfields outside 0..4 is NK_E_INVALID at creation.
  * nz = 0 makes the 2-D problem, nz >= 3 the 3-D one; nfields = 0 gives the program and the problem of nk_problem_create_grid /
  * nk_problem_create_grid3. Everything else is unchanged: stencils, dof limits, side minimums, p, the pattern (nk_grid_pattern /
- * nk_grid3_pattern: fields add no columns), one rank, Float64, kind NK_PROBLEM_USER, every consumer. The programs with fields
- * carry one more option, -DNK_NFIELDS=<nfields>; the kernels keep their names and their thread map (one node per thread, 256
+ * nk_grid3_pattern: fields add no columns), one rank, Float64, kind NK_PROBLEM_USER, every consumer. -DNK_NFIELDS=<nfields> is
+ * what tells the programs with fields from those without; the kernels keep their names and their thread map (one node per thread, 256
  * per workgroup), and the staged fill's LDS is unchanged. The field neighbourhood is loaded with u's, unconditionally; a load
  * whose value the source does not read is removed by the compiler, so declaring a field costs nothing until it is read.
  * Algorithmic bytes per unknown, r = number of distinct fields the source reads: residual 16 + 8·r/dof, J·v 24 + 8·r/dof, the

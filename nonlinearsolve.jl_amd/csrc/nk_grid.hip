@@ -1,4 +1,4 @@
-// Compiled grid problems: a residual given pointwise on a 2-D grid through a radius-1 stencil, handed over as HIP C++ source
+// Compiled grid problems: a residual given pointwise on a 2-D or 3-D grid through a stencil, handed over as HIP C++ source
 //     template <typename T> __device__ void nk_point(const nk_nbhd<T> &u, const nk_real *p, nk_site s, T *f);
 // and compiled at run time (hiprtc, gfx950) into three kernels — the full-size analogue of what nk_batch_create does for
 // ensembles, and of what the reference gets from `f` alone: SciMLJacobianOperators derives J·v with forward-mode duals, sparse
@@ -19,26 +19,27 @@
 // user_pattern set to the stencil's CSR pattern: every consumer (nk_problem_jvp_dev, user_lin_J, the solver, GMRES) treats it as
 // it treats any callback problem. Jᵀv is user_lin_J + nk_csr_spmv_t_dev. One rank.
 //
+// One table, one text. k_grid_stencils lists every stencil the library offers — dimension, code, name, largest dof and the
+// offsets (di, dj, dk) in pattern order — and everything that depends on the stencil is derived from it: the point count, the
+// radius, the smallest side, the dof limits and their messages, the host pattern, and the few lines of device text
+// (grid_stencil_text: NK_NPTS and the offset table nk_pt_off) that every program starts with. The device text proper is two
+// strings, k_grid_types before the user's source and k_grid_kernels after it, the same for every program; what a program is
+// comes from its options alone, and every program gets all of them: -DNK_DIM=2|3, -DNK_NFIELDS=0..4, -DNK_DOF, -DNK_PERIODIC,
+// -DNK_CH, -DNK_GRID_SET (0: residual and JVP, 1: the fill) and -DNK_GRID_DIRECT. The dimension decides one block of
+// k_grid_types (the site, the user-facing names, the arity of operator(), the node → site split and the index geometry) and
+// nothing else; in three dimensions the kernels are nk_grid3_residual / _jvp / _jac over nk_nbhd3<T> / nk_site3 =
+// {i, j, k, nx, ny, nz}, and unknown c of node (i, j, k) is element c·nn + (k·ny + j)·nx + i.
+//
 // Where a row's partials go: the pattern has ascending columns, i.e. component-major, then ascending node index. Inside the grid
 // the stencil points are numbered in that order already; at a periodic edge wrap-around reorders them, at a Dirichlet edge some
 // are missing. Each thread counts, for every stencil point, the in-domain points with a smaller node index (npts² integer
 // compares on registers) instead of reading a per-node slot table: the fill is bound by its 8·nnz bytes of stores, and a table
 // would add npts bytes per node to the stream for something 25 (81) compares give.
 //
-// Three dimensions (nk_problem_create_grid3): the same three kernels over nk_nbhd3<T> / nk_site3 = {i, j, k, nx, ny, nz} —
-// nk_grid3_residual, nk_grid3_jvp, nk_grid3_jac — from source strings of their own, so the 2-D programs are compiled from the
-// text and the options they always had. 7-point star (dof 1..4) or 27-point box (dof 1): at most 28 partials per row, and the
-// staged fill's LDS is at most 256·28 doubles (57344 bytes). Unknown c of node (i, j, k) is element c·nn + (k·ny + j)·nx + i;
-// the flat 256-thread workgroups walk that order, so a wavefront still loads 64 consecutive doubles per stencil point.
-//
-// Radius 2 (NK_GRID_STAR2 = 16, NK_GRID_DIAMOND2 = 17; bit 16 of the stencil code): the same kernels once more. Only four things
-// know the radius — the offset tables nk_pt_di/dj/dk, nk_nbhd::operator() with its NaN rule, the periodic wrap (± n instead of
-// "the other end") and the argument checks — so the radius-2 programs get types strings of their own (k_grid_types_r2,
-// k_grid3_types_r2), the wrap piece k_grid_wrap_r2 between the two pieces of the kernels' text, and one more option,
-// -DNK_STENCIL=<code>. The radius-1 programs are put together from the same bytes and options as before (hiprtc derives a unit id
-// from the text, comments included: even a changed comment would change their code objects). 2-D: the 9-point star with dof 1..2
-// (18 partials) and the 13-point diamond |di| + |dj| <= 2 with dof 1; 3-D: the 13-point star with dof 1..2 (26 partials, staged
-// LDS 53248 bytes). Every side >= 5, so that the five offsets of a direction are five distinct columns on the torus.
+// Reading the neighbourhood: u(di, dj[, dk], c) looks its offsets up in nk_pt_off (nk_pt_find, a constexpr search the compiler
+// folds: the offsets are literals in the user's source) and an offset that is no point of the stencil gives NaN, so a wrong
+// source shows at once. At most 20 partials per row in 2-D and 28 in 3-D (staged fill: at most 256·28 doubles of LDS, 57344
+// bytes). Every side >= 2·radius + 1, so that the offsets of a direction are distinct columns on the torus.
 //
 // Fields (nk_problem_create_grid_fields, nfields = 1..4): read-only arrays of one double per node — a previous time level, a
 // coefficient, a source term — which the source reads as a(di, dj, k) through the stencil's own offsets:
@@ -50,12 +51,14 @@
 // fields are constants of the differentiation. A load whose value the source never reads is dropped by the compiler (the
 // neighbourhood is a fully unrolled register array), so a declared field costs nothing until it is read. Per unknown, with r the
 // number of distinct fields the source reads: residual 16 + 8·r/dof bytes, JVP 24 + 8·r/dof, fill its figure + 8·r/dof (a field
-// line read by three lines of threads comes from cache, as for u). These programs carry -DNK_NFIELDS=<k>, one string of field
-// text after the types and two small pieces between the pieces of the kernels' text; the programs without fields are put
-// together from the same bytes and options as before.
+// line read by three lines of threads comes from cache, as for u). In the text a field is one more kernel parameter and one more
+// nk_point argument, NK_FLDS_PARAM and NK_FLDS_ARG, both empty at NK_NFIELDS == 0.
+#include <ctype.h>
 #include <math.h>
+#include <stdlib.h>
 #include <string.h>
 
+#include <algorithm>
 #include <initializer_list>
 #include <map>
 #include <mutex>
@@ -64,691 +67,113 @@
 
 #include "nk_internal.h"
 
-// ----------------------------------------------------------------------------- device source (compiled by hiprtc)
-static const char *k_grid_types = R"NKSRC(
-// ---- compiled grid problems: the node's position and its neighbourhood
-#if NK_BOX
-#define NK_NPTS 9
-#else
-#define NK_NPTS 5
-#endif
-struct nk_site { int i, j, nx, ny; };
-// stencil point q → offset; q ascends with the node index (j·nx + i) of the point inside the grid:
-// star S W C E N, box row by row
-__device__ constexpr int nk_pt_di(int q) { return NK_BOX ? q % 3 - 1 : (q == 1 ? -1 : (q == 3 ? 1 : 0)); }
-__device__ constexpr int nk_pt_dj(int q) { return NK_BOX ? q / 3 - 1 : (q == 0 ? -1 : (q == 4 ? 1 : 0)); }
-template <typename T>
-struct nk_nbhd {
-  T val[NK_NPTS * NK_DOF];
-  // component c at node (i + di, j + dj); di, dj ∈ {−1, 0, 1} (compile-time constants keep val in registers)
-  __device__ __forceinline__ T operator()(int di, int dj, int c = 0) const {
-#if NK_BOX
-    return val[((dj + 1) * 3 + (di + 1)) * NK_DOF + c];
-#else
-    if (di != 0 && dj != 0) return T(NK_R(__builtin_nan("")));   // the star has no corners: a wrong source shows at once
-    return val[(dj != 0 ? 2 + 2 * dj : 2 + di) * NK_DOF + c];
-#endif
-  }
+// ----------------------------------------------------------------------------- the stencils (host table)
+struct grid_stencil {
+  int dim, code;
+  const char *name;
+  int max_dof, npts;
+  signed char off[27][3];   // (di, dj, dk) of point q, q ascending with the node index (k·ny + j)·nx + i inside the grid
 };
-)NKSRC";
-
-// radius 2 (NK_GRID_STAR2, NK_GRID_DIAMOND2): the programs of these stencils carry -DNK_STENCIL=<code> and get this text in
-// place of k_grid_types; the radius-1 programs are compiled from the text and the options they always had.
-static const char *k_grid_types_r2 = R"NKSRC(
-// ---- compiled grid problems, radius 2: the node's position and its neighbourhood
-#if NK_STENCIL == 17
-#define NK_NPTS 13
-#else
-#define NK_NPTS 9
-#endif
-struct nk_site { int i, j, nx, ny; };
-// stencil point q → offset; q ascends with the node index (j·nx + i) of the point inside the grid:
-// star2    (0,−2) (0,−1) (−2,0) (−1,0) C (1,0) (2,0) (0,1) (0,2)
-// diamond2 (0,−2) (−1,−1) (0,−1) (1,−1) (−2,0) (−1,0) C (1,0) (2,0) (−1,1) (0,1) (1,1) (0,2)
-#if NK_STENCIL == 17
-__device__ constexpr int nk_pt_di(int q) { return q == 0 || q == 12 ? 0 : (q <= 3 ? q - 2 : (q <= 8 ? q - 6 : q - 10)); }
-__device__ constexpr int nk_pt_dj(int q) { return q == 0 ? -2 : (q <= 3 ? -1 : (q <= 8 ? 0 : (q <= 11 ? 1 : 2))); }
-#else
-__device__ constexpr int nk_pt_di(int q) { return q >= 2 && q <= 6 ? q - 4 : 0; }
-__device__ constexpr int nk_pt_dj(int q) { return q < 2 ? q - 2 : (q > 6 ? q - 6 : 0); }
-#endif
-template <typename T>
-struct nk_nbhd {
-  T val[NK_NPTS * NK_DOF];
-  // component c at node (i + di, j + dj); di, dj ∈ {−2, …, 2} (compile-time constants keep val in registers). A read outside
-  // the stencil's shape returns NaN: a wrong source shows at once
-  __device__ __forceinline__ T operator()(int di, int dj, int c = 0) const {
-    const int ai = di < 0 ? -di : di, aj = dj < 0 ? -dj : dj;
-#if NK_STENCIL == 17
-    if (ai + aj > 2) return T(NK_R(__builtin_nan("")));
-    return val[(aj == 2 ? 6 + 3 * dj : 6 + 4 * dj + di) * NK_DOF + c];
-#else
-    if ((di != 0 && dj != 0) || ai > 2 || aj > 2) return T(NK_R(__builtin_nan("")));
-    return val[(dj != 0 ? (dj < 0 ? 2 + dj : 6 + dj) : 4 + di) * NK_DOF + c];
-#endif
-  }
-};
-)NKSRC";
-
-static const char *k_grid_kernels_a = R"NKSRC(
-// ---- generated kernels: one node per thread
-#define NK_GRID_BLOCK 256
-// node index of every stencil point (clamped to the node itself outside a Dirichlet boundary, wrapped at a periodic one) and
-// whether the point is in the domain
-__device__ __forceinline__ void nk_grid_geom(int i, int j, int nx, int ny, int (&idx)[NK_NPTS], bool (&in)[NK_NPTS]) {
-#pragma unroll
-  for (int q = 0; q < NK_NPTS; ++q) {
-    int ii = i + nk_pt_di(q), jj = j + nk_pt_dj(q);
-#if NK_PERIODIC
-)NKSRC";
-// the periodic wrap, the one piece of the kernels' text that depends on the radius: with k_grid_wrap_r1 between the two pieces
-// the radius-1 programs are compiled from the very text they always had; an offset of ±2 wraps by ± n
-static const char *k_grid_wrap_r1 = R"NKSRC(    ii = ii < 0 ? nx - 1 : (ii >= nx ? 0 : ii);
-    jj = jj < 0 ? ny - 1 : (jj >= ny ? 0 : jj);
-)NKSRC";
-static const char *k_grid_wrap_r2 = R"NKSRC(    ii = ii < 0 ? ii + nx : (ii >= nx ? ii - nx : ii);
-    jj = jj < 0 ? jj + ny : (jj >= ny ? jj - ny : jj);
-)NKSRC";
-static const char *const k_grid_kernels_b[] = {R"NKSRC(    in[q] = true;
-#else
-    in[q] = ii >= 0 && ii < nx && jj >= 0 && jj < ny;
-    ii = in[q] ? ii : i;
-    jj = in[q] ? jj : j;
-#endif
-    idx[q] = jj * nx + ii;
-  }
-}
-
-#if NK_GRID_SET == 0
-extern "C" __global__ void __launch_bounds__(NK_GRID_BLOCK)
-nk_grid_residual(int nx, int ny, const nk_real *__restrict__ p, )NKSRC",
-    R"NKSRC(const nk_real *__restrict__ u, nk_real *__restrict__ f) {
-  const int nn = nx * ny, node = (int)blockIdx.x * NK_GRID_BLOCK + (int)threadIdx.x;
-  if (node >= nn) return;
-  const int j = (int)((unsigned)node / (unsigned)nx), i = node - j * nx;
-  int idx[NK_NPTS];
-  bool in[NK_NPTS];
-  nk_grid_geom(i, j, nx, ny, idx, in);
-  nk_nbhd<nk_real> nb;
-#pragma unroll
-  for (int q = 0; q < NK_NPTS; ++q) {
-#pragma unroll
-    for (int c = 0; c < NK_DOF; ++c) {
-      const nk_real x = u[c * nn + idx[q]];
-      nb.val[q * NK_DOF + c] = in[q] ? x : NK_R(0);
-    }
-  }
-  nk_real out[NK_DOF];
-#pragma unroll
-  for (int c = 0; c < NK_DOF; ++c) out[c] = NK_R(0);
-  const nk_site s = {i, j, nx, ny};
-  nk_point<nk_real>(nb, )NKSRC", R"NKSRC(p, s, out);
-#pragma unroll
-  for (int c = 0; c < NK_DOF; ++c) f[c * nn + node] = out[c];
-}
-
-// J(u)·v exactly: the value of every neighbour from u, its one partial from v
-extern "C" __global__ void __launch_bounds__(NK_GRID_BLOCK)
-nk_grid_jvp(int nx, int ny, const nk_real *__restrict__ p, )NKSRC",
-    R"NKSRC(const nk_real *__restrict__ u, const nk_real *__restrict__ v,
-            nk_real *__restrict__ jv) {
-  const int nn = nx * ny, node = (int)blockIdx.x * NK_GRID_BLOCK + (int)threadIdx.x;
-  if (node >= nn) return;
-  const int j = (int)((unsigned)node / (unsigned)nx), i = node - j * nx;
-  int idx[NK_NPTS];
-  bool in[NK_NPTS];
-  nk_grid_geom(i, j, nx, ny, idx, in);
-  nk_nbhd<Dual> nb;
-#pragma unroll
-  for (int q = 0; q < NK_NPTS; ++q) {
-#pragma unroll
-    for (int c = 0; c < NK_DOF; ++c) {
-      const nk_real x = u[c * nn + idx[q]], d = v[c * nn + idx[q]];
-      nb.val[q * NK_DOF + c].v = in[q] ? x : NK_R(0);
-      nb.val[q * NK_DOF + c].d[0] = in[q] ? d : NK_R(0);
-    }
-  }
-  Dual out[NK_DOF];
-#pragma unroll
-  for (int c = 0; c < NK_DOF; ++c) out[c] = Dual(NK_R(0));
-  const nk_site s = {i, j, nx, ny};
-  nk_point<Dual>(nb, )NKSRC", R"NKSRC(p, s, out);
-#pragma unroll
-  for (int c = 0; c < NK_DOF; ++c) jv[c * nn + node] = out[c].d[0];
-}
-#else
-// The values of J(u) on the stencil's CSR pattern (ascending columns): slot q·dof + c of the duals carries ∂/∂u_c(point q).
-// Row c·nn + node holds, for c' = 0 … dof−1, its in-domain points in ascending node order: position c'·cnt + rank[q].
-// NK_GRID_DIRECT = 0: the workgroup's rows of one component are one contiguous piece of the value array — they are put together
-// in LDS and stored as whole lines (k_bratu_jac's way); 1: every thread stores its own partials, 8 bytes at a stride of a row.
-extern "C" __global__ void __launch_bounds__(NK_GRID_BLOCK)
-nk_grid_jac(int nx, int ny, const nk_real *__restrict__ p, )NKSRC",
-    R"NKSRC(const nk_real *__restrict__ u, const int *__restrict__ rowptr,
-            nk_real *__restrict__ vals) {
-  const int nn = nx * ny, node0 = (int)blockIdx.x * NK_GRID_BLOCK, node_t = node0 + (int)threadIdx.x;
-  if (node0 >= nn) return;   // (a workgroup past the grid; the launch has none)
-  const bool live = node_t < nn;
-#if NK_GRID_DIRECT
-  if (!live) return;
-#else
-  __shared__ nk_real sv[NK_GRID_BLOCK * NK_NPTS * NK_DOF];
-#endif
-  const int node = live ? node_t : nn - 1;   // (past the end: the last node again, nothing of it is kept)
-  const int j = (int)((unsigned)node / (unsigned)nx), i = node - j * nx;
-  int idx[NK_NPTS];
-  bool in[NK_NPTS];
-  nk_grid_geom(i, j, nx, ny, idx, in);
-  nk_nbhd<Dual> nb;
-#pragma unroll
-  for (int q = 0; q < NK_NPTS; ++q) {
-#pragma unroll
-    for (int c = 0; c < NK_DOF; ++c) {
-      const nk_real x = u[c * nn + idx[q]];
-      nb.val[q * NK_DOF + c].v = in[q] ? x : NK_R(0);
-#pragma unroll
-      for (int k = 0; k < NK_CH; ++k) nb.val[q * NK_DOF + c].d[k] = (k == q * NK_DOF + c) ? NK_R(1) : NK_R(0);
-    }
-  }
-  Dual out[NK_DOF];
-#pragma unroll
-  for (int c = 0; c < NK_DOF; ++c) out[c] = Dual(NK_R(0));
-  const nk_site s = {i, j, nx, ny};
-  nk_point<Dual>(nb, )NKSRC", R"NKSRC(p, s, out);
-  int rank[NK_NPTS], cnt = 0;
-#pragma unroll
-  for (int q = 0; q < NK_NPTS; ++q) {
-    int r = 0;
-#pragma unroll
-    for (int t = 0; t < NK_NPTS; ++t) r += (in[t] && idx[t] < idx[q]) ? 1 : 0;
-    rank[q] = r;
-    cnt += in[q] ? 1 : 0;
-  }
-#pragma unroll
-  for (int c = 0; c < NK_DOF; ++c) {
-    const int base = rowptr[c * nn + node];
-#if NK_GRID_DIRECT
-#pragma unroll
-    for (int q = 0; q < NK_NPTS; ++q) {
-      if (in[q]) {
-#pragma unroll
-        for (int c2 = 0; c2 < NK_DOF; ++c2) vals[base + c2 * cnt + rank[q]] = out[c].d[q * NK_DOF + c2];
-      }
-    }
-#else
-    // this workgroup's piece of component c: [p0, p1) ⊂ [0, nnz), at most NK_GRID_BLOCK·npts·dof values
-    const int last = node0 + NK_GRID_BLOCK < nn ? node0 + NK_GRID_BLOCK : nn;
-    const int p0 = rowptr[c * nn + node0], p1 = rowptr[c * nn + last];
-    if (live) {
-#pragma unroll
-      for (int q = 0; q < NK_NPTS; ++q) {
-        if (in[q]) {
-#pragma unroll
-          for (int c2 = 0; c2 < NK_DOF; ++c2) sv[base - p0 + c2 * cnt + rank[q]] = out[c].d[q * NK_DOF + c2];
+static const std::vector<grid_stencil> k_grid_stencils = [] {
+  std::vector<grid_stencil> t = {
+      {2, NK_GRID_STAR, "star", 4, 5, {{0, -1, 0}, {-1, 0, 0}, {0, 0, 0}, {1, 0, 0}, {0, 1, 0}}},
+      {2, NK_GRID_STAR2, "star2", 2, 9,
+       {{0, -2, 0}, {0, -1, 0}, {-2, 0, 0}, {-1, 0, 0}, {0, 0, 0}, {1, 0, 0}, {2, 0, 0}, {0, 1, 0}, {0, 2, 0}}},
+      {2, NK_GRID_DIAMOND2, "diamond2", 1, 13,
+       {{0, -2, 0}, {-1, -1, 0}, {0, -1, 0}, {1, -1, 0}, {-2, 0, 0}, {-1, 0, 0}, {0, 0, 0}, {1, 0, 0}, {2, 0, 0}, {-1, 1, 0},
+        {0, 1, 0}, {1, 1, 0}, {0, 2, 0}}},
+      {3, NK_GRID_STAR, "star", 4, 7, {{0, 0, -1}, {0, -1, 0}, {-1, 0, 0}, {0, 0, 0}, {1, 0, 0}, {0, 1, 0}, {0, 0, 1}}},
+      {3, NK_GRID_STAR2, "star2", 2, 13,
+       {{0, 0, -2}, {0, 0, -1}, {0, -2, 0}, {0, -1, 0}, {-2, 0, 0}, {-1, 0, 0}, {0, 0, 0}, {1, 0, 0}, {2, 0, 0}, {0, 1, 0},
+        {0, 2, 0}, {0, 0, 1}, {0, 0, 2}}},
+  };
+  for (int dim : {2, 3}) {   // the boxes: plane by plane, row by row (dk outermost, di innermost)
+    grid_stencil b = {dim, NK_GRID_BOX, "box", dim == 3 ? 1 : 2, 0, {}};
+    for (int dk = (dim == 3 ? -1 : 0); dk <= (dim == 3 ? 1 : 0); ++dk)
+      for (int dj = -1; dj <= 1; ++dj)
+        for (int di = -1; di <= 1; ++di) {
+          signed char *o = b.off[b.npts++];
+          o[0] = (signed char)di, o[1] = (signed char)dj, o[2] = (signed char)dk;
         }
-      }
-    }
-    __syncthreads();
-    for (int t = (int)threadIdx.x; t < p1 - p0; t += NK_GRID_BLOCK) vals[p0 + t] = sv[t];
-    __syncthreads();
-#endif
+    t.push_back(b);
   }
-}
-#endif
-)NKSRC"};
+  return t;
+}();
 
-static const char *k_grid_contract =
-    "the contract is `template <typename T> __device__ void nk_point(const nk_nbhd<T> &u, const nk_real *p, nk_site s, T *f)` "
-    "with u(di, dj, c) the component c at node (i + di, j + dj), s = {i, j, nx, ny}, p the parameters and f the node's dof "
-    "residuals (nk_real = double)";
-
-// ----------------------------------------------------------------------------- fields (programs with -DNK_NFIELDS=1..4 only)
-// Read-only data on the grid: NK_NFIELDS arrays of one double per node, read through the stencil's own offsets. This text follows
-// the types string (it needs NK_NPTS and the offset tables, whichever stencil they describe), and the two pieces below go between
-// the pieces of k_grid_kernels_b: one more pointer after `p` in every signature, the field neighbourhood in every nk_point call.
-// nk_flds_load is an argument of that call, so its loads — unconditional, from the addresses nk_grid_geom made for u — are issued
-// with u's, before the source runs; val is a fully unrolled register array filled from a __restrict__ const pointer, so a load
-// whose value the source never reads is dropped by the compiler. No select: outside a Dirichlet boundary idx[q] is the node
-// itself, and that is the value a field has there. A program without fields gets none of this text and neither piece.
-static const char *k_grid_fields = R"NKSRC(
-// ---- read-only fields on the grid: field k at the stencil's points (never a dual: a constant of the differentiation)
-__device__ constexpr int nk_pt_find(int di, int dj) {
-  for (int q = 0; q < NK_NPTS; ++q)
-    if (nk_pt_di(q) == di && nk_pt_dj(q) == dj) return q;
-  return -1;
+static const grid_stencil *grid_find(int dim, int code) {
+  for (const grid_stencil &st : k_grid_stencils)
+    if (st.dim == dim && st.code == code) return &st;
+  return nullptr;
 }
-struct nk_flds {
-  nk_real val[NK_NPTS * NK_NFIELDS];
-  // field k at node (i + di, j + dj): the offsets and the shape rule of u (outside the stencil's shape: NaN). Outside a
-  // Dirichlet boundary a field reads as at the node itself; at a periodic one the index wraps
-  __device__ __forceinline__ nk_real operator()(int di, int dj, int k = 0) const {
-    const int q = nk_pt_find(di, dj);
-    if (q < 0) return NK_R(__builtin_nan(""));
-    return val[q * NK_NFIELDS + k];
-  }
-};
-__device__ __forceinline__ nk_flds nk_flds_load(const nk_real *__restrict__ a, int nn, const int (&idx)[NK_NPTS]) {
-  nk_flds fl;
-#pragma unroll
-  for (int q = 0; q < NK_NPTS; ++q) {
-#pragma unroll
-    for (int k = 0; k < NK_NFIELDS; ++k) fl.val[q * NK_NFIELDS + k] = a[k * nn + idx[q]];
-  }
-  return fl;
+// the largest |offset|; a side has at least 2·radius + 1 nodes
+static int grid_radius(const grid_stencil &st) {
+  int r = 0;
+  for (int q = 0; q < st.npts; ++q)
+    for (int a = 0; a < 3; ++a) r = std::max(r, abs((int)st.off[q][a]));
+  return r;
 }
-)NKSRC";
-static const char *k_grid_fields_sig = "const nk_real *__restrict__ a, ";   // after `p` in the six kernel signatures
-static const char *k_grid_fields_call = "nk_flds_load(a, nn, idx), ";       // after `nb` in the six nk_point calls
-// the kernels' text: the pieces of k_grid_kernels_b / k_grid3_kernels_b with, for a program with fields, the signature piece
-// after every even piece and the call piece after every odd one (signature, call; three kernels)
-static std::string grid_join(const char *const (&pieces)[7], bool fields) {
+// "NK_GRID_STAR, NK_GRID_BOX, …": the stencils of a dimension (dim = 0: of any), as the header names them
+static std::string grid_stencil_names(int dim, int code = -1) {
   std::string s;
-  for (int t = 0; t < 7; ++t) {
-    s += pieces[t];
-    if (fields && t < 6) s += t % 2 == 0 ? k_grid_fields_sig : k_grid_fields_call;
+  for (const grid_stencil &st : k_grid_stencils) {
+    if ((dim != 0 && st.dim != dim) || (code >= 0 && st.code != code)) continue;
+    std::string nm = "NK_GRID_";
+    for (const char *c = st.name; *c; ++c) nm += (char)toupper(*c);
+    if (s.find(nm) == std::string::npos) s += (s.empty() ? "" : ", ") + nm;
   }
   return s;
 }
-
-static const char *k_gridf_contract =
-    "the contract of a problem with fields is `template <typename T> __device__ void nk_point(const nk_nbhd<T> &u, "
-    "const nk_flds &a, const nk_real *p, nk_site s, T *f)` with u(di, dj, c) the component c at node (i + di, j + dj), "
-    "a(di, dj, k) the field k there (an nk_real, never a dual), s = {i, j, nx, ny}, p the parameters and f the node's dof "
-    "residuals (nk_real = double)";
-
-// ----------------------------------------------------------------------------- device source, three dimensions
-static const char *k_grid3_types = R"NKSRC(
-// ---- compiled grid problems in 3-D: the node's position and its neighbourhood
-#if NK_BOX
-#define NK_NPTS 27
-#else
-#define NK_NPTS 7
-#endif
-struct nk_site3 { int i, j, k, nx, ny, nz; };
-// stencil point q → offset; q ascends with the node index ((k·ny + j)·nx + i) of the point inside the grid:
-// star (0,0,−1) (0,−1,0) (−1,0,0) C (1,0,0) (0,1,0) (0,0,1); box plane by plane, row by row (dk outermost, di innermost)
-__device__ constexpr int nk_pt_di(int q) { return NK_BOX ? q % 3 - 1 : (q == 2 ? -1 : (q == 4 ? 1 : 0)); }
-__device__ constexpr int nk_pt_dj(int q) { return NK_BOX ? (q / 3) % 3 - 1 : (q == 1 ? -1 : (q == 5 ? 1 : 0)); }
-__device__ constexpr int nk_pt_dk(int q) { return NK_BOX ? q / 9 - 1 : (q == 0 ? -1 : (q == 6 ? 1 : 0)); }
-template <typename T>
-struct nk_nbhd3 {
-  T val[NK_NPTS * NK_DOF];
-  // component c at node (i + di, j + dj, k + dk); di, dj, dk ∈ {−1, 0, 1} (compile-time constants keep val in registers)
-  __device__ __forceinline__ T operator()(int di, int dj, int dk, int c = 0) const {
-#if NK_BOX
-    return val[(((dk + 1) * 3 + (dj + 1)) * 3 + (di + 1)) * NK_DOF + c];
-#else
-    // the star has neither edges nor corners: a wrong source shows at once
-    if ((di != 0) + (dj != 0) + (dk != 0) > 1) return T(NK_R(__builtin_nan("")));
-    return val[(dk != 0 ? 3 + 3 * dk : (dj != 0 ? 3 + 2 * dj : 3 + di)) * NK_DOF + c];
-#endif
-  }
-};
-)NKSRC";
-
-static const char *k_grid3_types_r2 = R"NKSRC(
-// ---- compiled grid problems in 3-D, radius 2 (the 13-point star): the node's position and its neighbourhood
-#define NK_NPTS 13
-struct nk_site3 { int i, j, k, nx, ny, nz; };
-// stencil point q → offset; q ascends with the node index ((k·ny + j)·nx + i) of the point inside the grid:
-// (0,0,−2) (0,0,−1) (0,−2,0) (0,−1,0) (−2,0,0) (−1,0,0) C (1,0,0) (2,0,0) (0,1,0) (0,2,0) (0,0,1) (0,0,2)
-__device__ constexpr int nk_pt_di(int q) { return q >= 4 && q <= 8 ? q - 6 : 0; }
-__device__ constexpr int nk_pt_dj(int q) { return q == 2 || q == 3 ? q - 4 : (q == 9 || q == 10 ? q - 8 : 0); }
-__device__ constexpr int nk_pt_dk(int q) { return q < 2 ? q - 2 : (q > 10 ? q - 10 : 0); }
-template <typename T>
-struct nk_nbhd3 {
-  T val[NK_NPTS * NK_DOF];
-  // component c at node (i + di, j + dj, k + dk); one offset ∈ {−2, …, 2}, the others 0 (compile-time constants keep val in
-  // registers). A read with more than one non-zero offset returns NaN: a wrong source shows at once
-  __device__ __forceinline__ T operator()(int di, int dj, int dk, int c = 0) const {
-    if ((di != 0) + (dj != 0) + (dk != 0) > 1 || di < -2 || di > 2 || dj < -2 || dj > 2 || dk < -2 || dk > 2)
-      return T(NK_R(__builtin_nan("")));
-    return val[(dk != 0 ? (dk < 0 ? 2 + dk : 10 + dk) : (dj != 0 ? (dj < 0 ? 4 + dj : 8 + dj) : 6 + di)) * NK_DOF + c];
-  }
-};
-)NKSRC";
-
-static const char *k_grid3_kernels_a = R"NKSRC(
-// ---- generated kernels: one node per thread
-#define NK_GRID_BLOCK 256
-// node index of every stencil point (clamped to the node itself outside a Dirichlet boundary, wrapped at a periodic one) and
-// whether the point is in the domain
-__device__ __forceinline__ void nk_grid3_geom(int i, int j, int k, int nx, int ny, int nz, int (&idx)[NK_NPTS],
-                                              bool (&in)[NK_NPTS]) {
-#pragma unroll
-  for (int q = 0; q < NK_NPTS; ++q) {
-    int ii = i + nk_pt_di(q), jj = j + nk_pt_dj(q), kk = k + nk_pt_dk(q);
-#if NK_PERIODIC
-)NKSRC";
-static const char *k_grid3_wrap_r1 = R"NKSRC(    ii = ii < 0 ? nx - 1 : (ii >= nx ? 0 : ii);
-    jj = jj < 0 ? ny - 1 : (jj >= ny ? 0 : jj);
-    kk = kk < 0 ? nz - 1 : (kk >= nz ? 0 : kk);
-)NKSRC";
-static const char *k_grid3_wrap_r2 = R"NKSRC(    ii = ii < 0 ? ii + nx : (ii >= nx ? ii - nx : ii);
-    jj = jj < 0 ? jj + ny : (jj >= ny ? jj - ny : jj);
-    kk = kk < 0 ? kk + nz : (kk >= nz ? kk - nz : kk);
-)NKSRC";
-static const char *const k_grid3_kernels_b[] = {R"NKSRC(    in[q] = true;
-#else
-    in[q] = ii >= 0 && ii < nx && jj >= 0 && jj < ny && kk >= 0 && kk < nz;
-    ii = in[q] ? ii : i;
-    jj = in[q] ? jj : j;
-    kk = in[q] ? kk : k;
-#endif
-    idx[q] = (kk * ny + jj) * nx + ii;
-  }
-}
-// node → (i, j, k): node = (k·ny + j)·nx + i
-#define NK_GRID3_SITE(node)                                                      \
-  const int k = (int)((unsigned)(node) / (unsigned)(nx * ny));                   \
-  const int rem_ = (node) - k * (nx * ny);                                       \
-  const int j = (int)((unsigned)rem_ / (unsigned)nx), i = rem_ - j * nx
-
-#if NK_GRID_SET == 0
-extern "C" __global__ void __launch_bounds__(NK_GRID_BLOCK)
-nk_grid3_residual(int nx, int ny, int nz, const nk_real *__restrict__ p, )NKSRC", R"NKSRC(const nk_real *__restrict__ u,
-                  nk_real *__restrict__ f) {
-  const int nn = nx * ny * nz, node = (int)blockIdx.x * NK_GRID_BLOCK + (int)threadIdx.x;
-  if (node >= nn) return;
-  NK_GRID3_SITE(node);
-  int idx[NK_NPTS];
-  bool in[NK_NPTS];
-  nk_grid3_geom(i, j, k, nx, ny, nz, idx, in);
-  nk_nbhd3<nk_real> nb;
-#pragma unroll
-  for (int q = 0; q < NK_NPTS; ++q) {
-#pragma unroll
-    for (int c = 0; c < NK_DOF; ++c) {
-      const nk_real x = u[c * nn + idx[q]];
-      nb.val[q * NK_DOF + c] = in[q] ? x : NK_R(0);
-    }
-  }
-  nk_real out[NK_DOF];
-#pragma unroll
-  for (int c = 0; c < NK_DOF; ++c) out[c] = NK_R(0);
-  const nk_site3 s = {i, j, k, nx, ny, nz};
-  nk_point<nk_real>(nb, )NKSRC", R"NKSRC(p, s, out);
-#pragma unroll
-  for (int c = 0; c < NK_DOF; ++c) f[c * nn + node] = out[c];
+// "nx x ny" or "nx x ny x nz"
+static std::string grid_dims(int dim, int64_t nx, int64_t ny, int64_t nz) {
+  return std::to_string(nx) + " x " + std::to_string(ny) + (dim == 3 ? " x " + std::to_string(nz) : "");
 }
 
-// J(u)·v exactly: the value of every neighbour from u, its one partial from v
-extern "C" __global__ void __launch_bounds__(NK_GRID_BLOCK)
-nk_grid3_jvp(int nx, int ny, int nz, const nk_real *__restrict__ p, )NKSRC", R"NKSRC(const nk_real *__restrict__ u,
-             const nk_real *__restrict__ v, nk_real *__restrict__ jv) {
-  const int nn = nx * ny * nz, node = (int)blockIdx.x * NK_GRID_BLOCK + (int)threadIdx.x;
-  if (node >= nn) return;
-  NK_GRID3_SITE(node);
-  int idx[NK_NPTS];
-  bool in[NK_NPTS];
-  nk_grid3_geom(i, j, k, nx, ny, nz, idx, in);
-  nk_nbhd3<Dual> nb;
-#pragma unroll
-  for (int q = 0; q < NK_NPTS; ++q) {
-#pragma unroll
-    for (int c = 0; c < NK_DOF; ++c) {
-      const nk_real x = u[c * nn + idx[q]], d = v[c * nn + idx[q]];
-      nb.val[q * NK_DOF + c].v = in[q] ? x : NK_R(0);
-      nb.val[q * NK_DOF + c].d[0] = in[q] ? d : NK_R(0);
-    }
+// what the table refuses: a stencil the dimension does not offer, a boundary that is none, a dof beyond the stencil's largest
+static int grid_check_shape(int dim, int dof, int stencil, int boundary, const grid_stencil **out) {
+  const grid_stencil *st = grid_find(dim, stencil);
+  if (!st) {
+    const std::string elsewhere = grid_stencil_names(0, stencil), offered = grid_stencil_names(dim);
+    NK_FAIL(NK_E_INVALID, "stencil = %d%s%s%s is none of %s, the stencils offered in %d dimensions", stencil,
+            elsewhere.empty() ? "" : " (", elsewhere.c_str(), elsewhere.empty() ? "" : ")", offered.c_str(), dim);
   }
-  Dual out[NK_DOF];
-#pragma unroll
-  for (int c = 0; c < NK_DOF; ++c) out[c] = Dual(NK_R(0));
-  const nk_site3 s = {i, j, k, nx, ny, nz};
-  nk_point<Dual>(nb, )NKSRC", R"NKSRC(p, s, out);
-#pragma unroll
-  for (int c = 0; c < NK_DOF; ++c) jv[c * nn + node] = out[c].d[0];
-}
-#else
-// The values of J(u) on the stencil's CSR pattern (ascending columns): slot q·dof + c of the duals carries ∂/∂u_c(point q).
-// Row c·nn + node holds, for c' = 0 … dof−1, its in-domain points in ascending node order: position c'·cnt + rank[q].
-// NK_GRID_DIRECT = 0: the workgroup's rows of one component are one contiguous piece of the value array — they are put together
-// in LDS and stored as whole lines; 1: every thread stores its own partials, 8 bytes at a stride of a row.
-extern "C" __global__ void __launch_bounds__(NK_GRID_BLOCK)
-nk_grid3_jac(int nx, int ny, int nz, const nk_real *__restrict__ p, )NKSRC", R"NKSRC(const nk_real *__restrict__ u,
-             const int *__restrict__ rowptr, nk_real *__restrict__ vals) {
-  const int nn = nx * ny * nz, node0 = (int)blockIdx.x * NK_GRID_BLOCK, node_t = node0 + (int)threadIdx.x;
-  if (node0 >= nn) return;   // (a workgroup past the grid; the launch has none)
-  const bool live = node_t < nn;
-#if NK_GRID_DIRECT
-  if (!live) return;
-#else
-  __shared__ nk_real sv[NK_GRID_BLOCK * NK_NPTS * NK_DOF];   // (at most 256·28 doubles: the star at dof 4)
-#endif
-  const int node = live ? node_t : nn - 1;   // (past the end: the last node again, nothing of it is kept)
-  NK_GRID3_SITE(node);
-  int idx[NK_NPTS];
-  bool in[NK_NPTS];
-  nk_grid3_geom(i, j, k, nx, ny, nz, idx, in);
-  nk_nbhd3<Dual> nb;
-#pragma unroll
-  for (int q = 0; q < NK_NPTS; ++q) {
-#pragma unroll
-    for (int c = 0; c < NK_DOF; ++c) {
-      const nk_real x = u[c * nn + idx[q]];
-      nb.val[q * NK_DOF + c].v = in[q] ? x : NK_R(0);
-#pragma unroll
-      for (int t = 0; t < NK_CH; ++t) nb.val[q * NK_DOF + c].d[t] = (t == q * NK_DOF + c) ? NK_R(1) : NK_R(0);
-    }
-  }
-  Dual out[NK_DOF];
-#pragma unroll
-  for (int c = 0; c < NK_DOF; ++c) out[c] = Dual(NK_R(0));
-  const nk_site3 s = {i, j, k, nx, ny, nz};
-  nk_point<Dual>(nb, )NKSRC", R"NKSRC(p, s, out);
-  int rank[NK_NPTS], cnt = 0;
-#pragma unroll
-  for (int q = 0; q < NK_NPTS; ++q) {
-    int r = 0;
-#pragma unroll
-    for (int t = 0; t < NK_NPTS; ++t) r += (in[t] && idx[t] < idx[q]) ? 1 : 0;
-    rank[q] = r;
-    cnt += in[q] ? 1 : 0;
-  }
-#pragma unroll
-  for (int c = 0; c < NK_DOF; ++c) {
-    const int base = rowptr[c * nn + node];
-#if NK_GRID_DIRECT
-#pragma unroll
-    for (int q = 0; q < NK_NPTS; ++q) {
-      if (in[q]) {
-#pragma unroll
-        for (int c2 = 0; c2 < NK_DOF; ++c2) vals[base + c2 * cnt + rank[q]] = out[c].d[q * NK_DOF + c2];
-      }
-    }
-#else
-    // this workgroup's piece of component c: [p0, p1) ⊂ [0, nnz), at most NK_GRID_BLOCK·npts·dof values
-    const int last = node0 + NK_GRID_BLOCK < nn ? node0 + NK_GRID_BLOCK : nn;
-    const int p0 = rowptr[c * nn + node0], p1 = rowptr[c * nn + last];
-    if (live) {
-#pragma unroll
-      for (int q = 0; q < NK_NPTS; ++q) {
-        if (in[q]) {
-#pragma unroll
-          for (int c2 = 0; c2 < NK_DOF; ++c2) sv[base - p0 + c2 * cnt + rank[q]] = out[c].d[q * NK_DOF + c2];
-        }
-      }
-    }
-    __syncthreads();
-    for (int t = (int)threadIdx.x; t < p1 - p0; t += NK_GRID_BLOCK) vals[p0 + t] = sv[t];
-    __syncthreads();
-#endif
-  }
-}
-#endif
-)NKSRC"};
-
-static const char *k_grid3_contract =
-    "the contract is `template <typename T> __device__ void nk_point(const nk_nbhd3<T> &u, const nk_real *p, nk_site3 s, T *f)` "
-    "with u(di, dj, dk, c) the component c at node (i + di, j + dj, k + dk), s = {i, j, k, nx, ny, nz}, p the parameters and f "
-    "the node's dof residuals (nk_real = double)";
-
-// fields in three dimensions: the same text over the 3-D offset tables, as nk_flds3 (the two pieces are the 2-D ones)
-static const char *k_grid3_fields = R"NKSRC(
-// ---- read-only fields on the grid: field k at the stencil's points (never a dual: a constant of the differentiation)
-__device__ constexpr int nk_pt_find(int di, int dj, int dk) {
-  for (int q = 0; q < NK_NPTS; ++q)
-    if (nk_pt_di(q) == di && nk_pt_dj(q) == dj && nk_pt_dk(q) == dk) return q;
-  return -1;
-}
-struct nk_flds3 {
-  nk_real val[NK_NPTS * NK_NFIELDS];
-  // field k at node (i + di, j + dj, k + dk): the offsets and the shape rule of u (outside the stencil's shape: NaN). Outside
-  // a Dirichlet boundary a field reads as at the node itself; at a periodic one the index wraps
-  __device__ __forceinline__ nk_real operator()(int di, int dj, int dk, int k = 0) const {
-    const int q = nk_pt_find(di, dj, dk);
-    if (q < 0) return NK_R(__builtin_nan(""));
-    return val[q * NK_NFIELDS + k];
-  }
-};
-__device__ __forceinline__ nk_flds3 nk_flds_load(const nk_real *__restrict__ a, int nn, const int (&idx)[NK_NPTS]) {
-  nk_flds3 fl;
-#pragma unroll
-  for (int q = 0; q < NK_NPTS; ++q) {
-#pragma unroll
-    for (int k = 0; k < NK_NFIELDS; ++k) fl.val[q * NK_NFIELDS + k] = a[k * nn + idx[q]];
-  }
-  return fl;
-}
-)NKSRC";
-static const char *k_grid3f_contract =
-    "the contract of a problem with fields is `template <typename T> __device__ void nk_point(const nk_nbhd3<T> &u, "
-    "const nk_flds3 &a, const nk_real *p, nk_site3 s, T *f)` with u(di, dj, dk, c) the component c at node (i + di, j + dj, "
-    "k + dk), a(di, dj, dk, k) the field k there (an nk_real, never a dual), s = {i, j, k, nx, ny, nz}, p the parameters and f "
-    "the node's dof residuals (nk_real = double)";
-
-// ----------------------------------------------------------------------------- the stencil's CSR pattern (host only)
-static inline int grid_radius(int stencil) { return stencil == NK_GRID_STAR2 || stencil == NK_GRID_DIAMOND2 ? 2 : 1; }
-// points of a stencil (0: the dimension does not offer it)
-static inline int grid_npts(int dim, int stencil) {
-  switch (stencil) {
-    case NK_GRID_STAR: return dim == 3 ? 7 : 5;
-    case NK_GRID_BOX: return dim == 3 ? 27 : 9;
-    case NK_GRID_STAR2: return dim == 3 ? 13 : 9;
-    case NK_GRID_DIAMOND2: return dim == 3 ? 0 : 13;
-  }
-  return 0;
-}
-
-static int grid_check_shape(int dof, int stencil, int boundary) {
-  NK_REQUIRE(stencil == NK_GRID_STAR || stencil == NK_GRID_BOX || stencil == NK_GRID_STAR2 || stencil == NK_GRID_DIAMOND2,
-             "stencil = %d is none of NK_GRID_STAR, NK_GRID_BOX, NK_GRID_STAR2, NK_GRID_DIAMOND2", stencil);
   NK_REQUIRE(boundary == NK_GRID_DIRICHLET0 || boundary == NK_GRID_PERIODIC,
              "boundary = %d is neither NK_GRID_DIRICHLET0 nor NK_GRID_PERIODIC", boundary);
   NK_REQUIRE(dof >= 1 && dof <= 4, "dof = %d outside 1..4 (components per grid node)", dof);
-  NK_REQUIRE(stencil != NK_GRID_BOX || dof <= 2, "dof = %d with the box stencil: the 9-point box is offered for dof <= 2 "
-             "(a row has at most 20 partials)", dof);
-  NK_REQUIRE(stencil != NK_GRID_STAR2 || dof <= 2, "dof = %d with the star2 stencil: the 9-point radius-2 star is offered for "
-             "dof <= 2 (a row has at most 20 partials)", dof);
-  NK_REQUIRE(stencil != NK_GRID_DIAMOND2 || dof == 1, "dof = %d with the diamond2 stencil: the 13-point diamond is offered for "
-             "dof = 1 (a row has at most 20 partials)", dof);
+  int most = 0;   // partials per row the dimension's programs are built for
+  for (const grid_stencil &s : k_grid_stencils)
+    if (s.dim == dim) most = std::max(most, s.npts * s.max_dof);
+  NK_REQUIRE(dof <= st->max_dof, "dof = %d with the %s stencil: the %d-point %s is offered for dof %s %d (a row has at most %d "
+             "partials)", dof, st->name, st->npts, st->name, st->max_dof == 1 ? "=" : "<=", st->max_dof, most);
+  *out = st;
   return NK_OK;
 }
-// stencil point q → offset, in pattern order (the device tables of k_grid_types / k_grid_types_r2)
-static inline int grid_pt_di(int stencil, int q) {
-  if (stencil == NK_GRID_STAR2) return q >= 2 && q <= 6 ? q - 4 : 0;
-  if (stencil == NK_GRID_DIAMOND2) return q == 0 || q == 12 ? 0 : (q <= 3 ? q - 2 : (q <= 8 ? q - 6 : q - 10));
-  return stencil == NK_GRID_BOX ? q % 3 - 1 : (q == 1 ? -1 : (q == 3 ? 1 : 0));
+// what the sizes add: every side >= 2·radius + 1 (both boundaries: that many distinct columns per direction), and a pattern
+// that 32-bit indices can hold
+static int grid_check_size(const grid_stencil &st, int64_t nx, int64_t ny, int64_t nz, int dof) {
+  const int r = grid_radius(st), side = 2 * r + 1;
+  const std::string dims = grid_dims(st.dim, nx, ny, nz);
+  if (st.dim == 3)
+    NK_REQUIRE(nx >= side && ny >= side && nz >= side, "grid %s: a radius-%d stencil needs nx >= %d, ny >= %d and nz >= %d (%d "
+               "distinct columns per direction at a periodic edge)", dims.c_str(), r, side, side, side, side);
+  else
+    NK_REQUIRE(nx >= side && ny >= side, "grid %s: a radius-%d stencil needs nx >= %d and ny >= %d (%d distinct columns per "
+               "direction at a periodic edge)", dims.c_str(), r, side, side, side);
+  NK_REQUIRE(nx <= INT32_MAX / ny && nx * ny <= INT32_MAX / nz && nx * ny * nz <= (int64_t)INT32_MAX / (dof * st.npts * dof),
+             "grid %s with dof = %d: the pattern's 32-bit indices cannot hold it", dims.c_str(), dof);
+  return NK_OK;
 }
-static inline int grid_pt_dj(int stencil, int q) {
-  if (stencil == NK_GRID_STAR2) return q < 2 ? q - 2 : (q > 6 ? q - 6 : 0);
-  if (stencil == NK_GRID_DIAMOND2) return q == 0 ? -2 : (q <= 3 ? -1 : (q <= 8 ? 0 : (q <= 11 ? 1 : 2)));
-  return stencil == NK_GRID_BOX ? q / 3 - 1 : (q == 0 ? -1 : (q == 4 ? 1 : 0));
-}
+
+// ----------------------------------------------------------------------------- the stencil's CSR pattern (host only)
 // periodic wrap of an index at most n outside [0, n)
 static inline int64_t grid_wrap(int64_t ii, int64_t n) { return ii < 0 ? ii + n : (ii >= n ? ii - n : ii); }
 
-extern "C" int nk_grid_pattern(int64_t nx, int64_t ny, int dof, int stencil, int boundary, int32_t *rowptr, int32_t *colind,
-                               int64_t *nnz) {
+// dim = 2: nz is 1 and every dk is 0
+static int grid_pattern(int dim, int64_t nx, int64_t ny, int64_t nz, int dof, int stencil, int boundary, int32_t *rowptr,
+                        int32_t *colind, int64_t *nnz) {
   NK_REQUIRE(rowptr || nnz, "NULL argument");
-  NK_TRY(grid_check_shape(dof, stencil, boundary));
-  if (grid_radius(stencil) == 2)
-    NK_REQUIRE(nx >= 5 && ny >= 5, "grid %lld x %lld: a radius-2 stencil needs nx >= 5 and ny >= 5 (five distinct columns per "
-               "direction at a periodic edge)", (long long)nx, (long long)ny);
-  NK_REQUIRE(nx >= 3 && ny >= 3, "grid %lld x %lld: a radius-1 stencil needs nx >= 3 and ny >= 3 (three distinct columns per "
-             "row at a periodic edge)", (long long)nx, (long long)ny);
-  const int npts = grid_npts(2, stencil);
-  NK_REQUIRE(nx <= INT32_MAX / ny && nx * ny <= (int64_t)INT32_MAX / (dof * npts * dof),
-             "grid %lld x %lld with dof = %d: the pattern's 32-bit indices cannot hold it", (long long)nx, (long long)ny, dof);
-  const int64_t nn = nx * ny;
-  int64_t pos = 0;
-  for (int c = 0; c < dof; ++c)
-    for (int64_t j = 0; j < ny; ++j)
-      for (int64_t i = 0; i < nx; ++i) {
-        int64_t nb[13];
-        int cnt = 0;
-        for (int q = 0; q < npts; ++q) {
-          int64_t ii = i + grid_pt_di(stencil, q), jj = j + grid_pt_dj(stencil, q);
-          if (boundary == NK_GRID_PERIODIC) {
-            ii = grid_wrap(ii, nx);
-            jj = grid_wrap(jj, ny);
-          } else if (ii < 0 || ii >= nx || jj < 0 || jj >= ny) {
-            continue;
-          }
-          // insertion keeps the node indices ascending (wrap-around reorders the points at a periodic edge)
-          const int64_t k = jj * nx + ii;
-          int t = cnt++;
-          while (t > 0 && nb[t - 1] > k) { nb[t] = nb[t - 1]; --t; }
-          nb[t] = k;
-        }
-        if (rowptr) rowptr[c * nn + j * nx + i] = (int32_t)pos;
-        if (colind)
-          for (int c2 = 0; c2 < dof; ++c2)
-            for (int t = 0; t < cnt; ++t) colind[pos + (int64_t)c2 * cnt + t] = (int32_t)(c2 * nn + nb[t]);
-        pos += (int64_t)cnt * dof;
-      }
-  if (rowptr) rowptr[dof * nn] = (int32_t)pos;
-  if (nnz) *nnz = pos;
-  return NK_OK;
-}
-
-// three dimensions: the 7-point star with dof 1..4, the 27-point box with dof 1, the 13-point radius-2 star with dof 1..2 — at
-// most 28 partials per row
-static int grid3_check_shape(int dof, int stencil, int boundary) {
-  NK_REQUIRE(stencil != NK_GRID_DIAMOND2, "stencil = NK_GRID_DIAMOND2 (%d) is not offered in three dimensions (25 points); "
-             "the radius-2 stencil of nk_problem_create_grid3 is NK_GRID_STAR2", stencil);
-  NK_REQUIRE(stencil == NK_GRID_STAR || stencil == NK_GRID_BOX || stencil == NK_GRID_STAR2,
-             "stencil = %d is none of NK_GRID_STAR, NK_GRID_BOX, NK_GRID_STAR2", stencil);
-  NK_REQUIRE(boundary == NK_GRID_DIRICHLET0 || boundary == NK_GRID_PERIODIC,
-             "boundary = %d is neither NK_GRID_DIRICHLET0 nor NK_GRID_PERIODIC", boundary);
-  NK_REQUIRE(dof >= 1 && dof <= 4, "dof = %d outside 1..4 (components per grid node)", dof);
-  NK_REQUIRE(stencil != NK_GRID_BOX || dof == 1, "dof = %d with the box stencil: the 27-point box is offered for dof = 1 "
-             "(a row has at most 28 partials)", dof);
-  NK_REQUIRE(stencil != NK_GRID_STAR2 || dof <= 2, "dof = %d with the star2 stencil: the 13-point radius-2 star is offered for "
-             "dof <= 2 (a row has at most 28 partials)", dof);
-  return NK_OK;
-}
-static inline int grid3_pt_di(int stencil, int q) {
-  if (stencil == NK_GRID_STAR2) return q >= 4 && q <= 8 ? q - 6 : 0;
-  return stencil == NK_GRID_BOX ? q % 3 - 1 : (q == 2 ? -1 : (q == 4 ? 1 : 0));
-}
-static inline int grid3_pt_dj(int stencil, int q) {
-  if (stencil == NK_GRID_STAR2) return q == 2 || q == 3 ? q - 4 : (q == 9 || q == 10 ? q - 8 : 0);
-  return stencil == NK_GRID_BOX ? (q / 3) % 3 - 1 : (q == 1 ? -1 : (q == 5 ? 1 : 0));
-}
-static inline int grid3_pt_dk(int stencil, int q) {
-  if (stencil == NK_GRID_STAR2) return q < 2 ? q - 2 : (q > 10 ? q - 10 : 0);
-  return stencil == NK_GRID_BOX ? q / 9 - 1 : (q == 0 ? -1 : (q == 6 ? 1 : 0));
-}
-// the refusal of a grid too small for the stencil's radius (both boundaries: 2·radius + 1 distinct columns per direction)
-static int grid3_check_size(int64_t nx, int64_t ny, int64_t nz, int stencil) {
-  if (grid_radius(stencil) == 2)
-    NK_REQUIRE(nx >= 5 && ny >= 5 && nz >= 5, "grid %lld x %lld x %lld: a radius-2 stencil needs nx >= 5, ny >= 5 and nz >= 5 "
-               "(five distinct columns per direction at a periodic edge)", (long long)nx, (long long)ny, (long long)nz);
-  NK_REQUIRE(nx >= 3 && ny >= 3 && nz >= 3, "grid %lld x %lld x %lld: a radius-1 stencil needs nx >= 3, ny >= 3 and nz >= 3 "
-             "(three distinct columns per direction at a periodic edge)", (long long)nx, (long long)ny, (long long)nz);
-  return NK_OK;
-}
-
-extern "C" int nk_grid3_pattern(int64_t nx, int64_t ny, int64_t nz, int dof, int stencil, int boundary, int32_t *rowptr,
-                                int32_t *colind, int64_t *nnz) {
-  NK_REQUIRE(rowptr || nnz, "NULL argument");
-  NK_TRY(grid3_check_shape(dof, stencil, boundary));
-  NK_TRY(grid3_check_size(nx, ny, nz, stencil));
-  const int npts = grid_npts(3, stencil);
-  NK_REQUIRE(nx <= INT32_MAX / ny && nx * ny <= INT32_MAX / nz && nx * ny * nz <= (int64_t)INT32_MAX / (dof * npts * dof),
-             "grid %lld x %lld x %lld with dof = %d: the pattern's 32-bit indices cannot hold it", (long long)nx, (long long)ny,
-             (long long)nz, dof);
+  const grid_stencil *st = nullptr;
+  NK_TRY(grid_check_shape(dim, dof, stencil, boundary, &st));
+  NK_TRY(grid_check_size(*st, nx, ny, nz, dof));
   const int64_t nn = nx * ny * nz;
   int64_t pos = 0;
   for (int c = 0; c < dof; ++c)
@@ -757,8 +182,8 @@ extern "C" int nk_grid3_pattern(int64_t nx, int64_t ny, int64_t nz, int dof, int
         for (int64_t i = 0; i < nx; ++i) {
           int64_t nb[27];
           int cnt = 0;
-          for (int q = 0; q < npts; ++q) {
-            int64_t ii = i + grid3_pt_di(stencil, q), jj = j + grid3_pt_dj(stencil, q), kk = k + grid3_pt_dk(stencil, q);
+          for (int q = 0; q < st->npts; ++q) {
+            int64_t ii = i + st->off[q][0], jj = j + st->off[q][1], kk = k + st->off[q][2];
             if (boundary == NK_GRID_PERIODIC) {
               ii = grid_wrap(ii, nx);
               jj = grid_wrap(jj, ny);
@@ -782,48 +207,340 @@ extern "C" int nk_grid3_pattern(int64_t nx, int64_t ny, int64_t nz, int dof, int
   if (nnz) *nnz = pos;
   return NK_OK;
 }
+extern "C" int nk_grid_pattern(int64_t nx, int64_t ny, int dof, int stencil, int boundary, int32_t *rowptr, int32_t *colind,
+                               int64_t *nnz) {
+  return grid_pattern(2, nx, ny, 1, dof, stencil, boundary, rowptr, colind, nnz);
+}
+extern "C" int nk_grid3_pattern(int64_t nx, int64_t ny, int64_t nz, int dof, int stencil, int boundary, int32_t *rowptr,
+                                int32_t *colind, int64_t *nnz) {
+  return grid_pattern(3, nx, ny, nz, dof, stencil, boundary, rowptr, colind, nnz);
+}
+
+// ----------------------------------------------------------------------------- device source (compiled by hiprtc)
+// The program is: nk_dual_prelude, the stencil's lines (grid_stencil_text), k_grid_types, k_grid_fields (every program gets it;
+// it is empty at NK_NFIELDS == 0), the user's source, k_grid_kernels.
+//
+// the stencil's lines, generated from its row of the table: NK_NPTS and the offsets in pattern order
+static std::string grid_stencil_text(const grid_stencil &st) {
+  std::string s = "\n// ---- the stencil: " + std::to_string(st.dim) + "-D " + st.name + ", point q -> (di, dj, dk), q ascending " +
+                  "with the node index inside the grid\n#define NK_NPTS " + std::to_string(st.npts) +
+                  "\n__device__ constexpr int nk_pt_off[NK_NPTS][3] = {";
+  for (int q = 0; q < st.npts; ++q)
+    s += std::string(q ? ", " : "") + "{" + std::to_string(st.off[q][0]) + ", " + std::to_string(st.off[q][1]) + ", " +
+         std::to_string(st.off[q][2]) + "}";
+  return s + "};\n";
+}
+
+static const char *k_grid_types = R"NKSRC(
+// ---- compiled grid problems: the node's position and its neighbourhood
+#define NK_GRID_BLOCK 256
+// everything the dimension decides: the site, the names the user's source sees, the arity of operator(), the sizes a kernel
+// takes, node -> site, and the node index of every stencil point (clamped to the node itself outside a Dirichlet boundary,
+// wrapped at a periodic one) with whether the point is in the domain
+#if NK_DIM == 3
+struct nk_site3 { int i, j, k, nx, ny, nz; };
+#define NK_SITE nk_site3
+#define NK_NBHD nk_nbhd3
+#define NK_FLDS nk_flds3
+#define NK_KERNEL(name) nk_grid3_##name
+#define NK_OFFSET int di, int dj, int dk
+#define NK_OFFSET_SLOT nk_pt_find(di, dj, dk)
+#define NK_SIZES int nx, int ny, int nz
+#define NK_SIZE_ARGS nx, ny, nz
+__device__ __forceinline__ int nk_grid_nn(int nx, int ny, int nz) { return nx * ny * nz; }
+// node = (k·ny + j)·nx + i
+__device__ __forceinline__ nk_site3 nk_grid_site(int node, int nx, int ny, int nz) {
+  const int k = (int)((unsigned)node / (unsigned)(nx * ny)), rem = node - k * (nx * ny);
+  const int j = (int)((unsigned)rem / (unsigned)nx), i = rem - j * nx;
+  return {i, j, k, nx, ny, nz};
+}
+__device__ __forceinline__ void nk_grid_geom(const nk_site3 s, int (&idx)[NK_NPTS], bool (&in)[NK_NPTS]) {
+#pragma unroll
+  for (int q = 0; q < NK_NPTS; ++q) {
+    int ii = s.i + nk_pt_off[q][0], jj = s.j + nk_pt_off[q][1], kk = s.k + nk_pt_off[q][2];
+#if NK_PERIODIC
+    ii = ii < 0 ? ii + s.nx : (ii >= s.nx ? ii - s.nx : ii);
+    jj = jj < 0 ? jj + s.ny : (jj >= s.ny ? jj - s.ny : jj);
+    kk = kk < 0 ? kk + s.nz : (kk >= s.nz ? kk - s.nz : kk);
+    in[q] = true;
+#else
+    in[q] = ii >= 0 && ii < s.nx && jj >= 0 && jj < s.ny && kk >= 0 && kk < s.nz;
+    ii = in[q] ? ii : s.i;
+    jj = in[q] ? jj : s.j;
+    kk = in[q] ? kk : s.k;
+#endif
+    idx[q] = (kk * s.ny + jj) * s.nx + ii;
+  }
+}
+#else
+struct nk_site { int i, j, nx, ny; };
+#define NK_SITE nk_site
+#define NK_NBHD nk_nbhd
+#define NK_FLDS nk_flds
+#define NK_KERNEL(name) nk_grid_##name
+#define NK_OFFSET int di, int dj
+#define NK_OFFSET_SLOT nk_pt_find(di, dj, 0)
+#define NK_SIZES int nx, int ny
+#define NK_SIZE_ARGS nx, ny
+__device__ __forceinline__ int nk_grid_nn(int nx, int ny) { return nx * ny; }
+// node = j·nx + i
+__device__ __forceinline__ nk_site nk_grid_site(int node, int nx, int ny) {
+  const int j = (int)((unsigned)node / (unsigned)nx), i = node - j * nx;
+  return {i, j, nx, ny};
+}
+__device__ __forceinline__ void nk_grid_geom(const nk_site s, int (&idx)[NK_NPTS], bool (&in)[NK_NPTS]) {
+#pragma unroll
+  for (int q = 0; q < NK_NPTS; ++q) {
+    int ii = s.i + nk_pt_off[q][0], jj = s.j + nk_pt_off[q][1];
+#if NK_PERIODIC
+    ii = ii < 0 ? ii + s.nx : (ii >= s.nx ? ii - s.nx : ii);
+    jj = jj < 0 ? jj + s.ny : (jj >= s.ny ? jj - s.ny : jj);
+    in[q] = true;
+#else
+    in[q] = ii >= 0 && ii < s.nx && jj >= 0 && jj < s.ny;
+    ii = in[q] ? ii : s.i;
+    jj = in[q] ? jj : s.j;
+#endif
+    idx[q] = jj * s.nx + ii;
+  }
+}
+#endif
+
+// the stencil point with this offset, -1 if the stencil has none (the offsets are literals in the user's source: the search
+// is folded at compile time)
+__device__ constexpr int nk_pt_find(int di, int dj, int dk) {
+  for (int q = 0; q < NK_NPTS; ++q)
+    if (nk_pt_off[q][0] == di && nk_pt_off[q][1] == dj && nk_pt_off[q][2] == dk) return q;
+  return -1;
+}
+template <typename T>
+struct NK_NBHD {
+  T val[NK_NPTS * NK_DOF];
+  // component c at the node offset by (di, dj[, dk]) (compile-time constants keep val in registers). An offset that is no
+  // point of the stencil gives NaN: a wrong source shows at once
+  __device__ __forceinline__ T operator()(NK_OFFSET, int c = 0) const {
+    const int q = NK_OFFSET_SLOT;
+    if (q < 0) return T(NK_R(__builtin_nan("")));
+    return val[q * NK_DOF + c];
+  }
+};
+)NKSRC";
+
+// Read-only data on the grid: NK_NFIELDS arrays of one double per node, read through the stencil's own offsets. A field is one
+// more pointer after `p` in every kernel's signature (NK_FLDS_PARAM) and the field neighbourhood in every nk_point call
+// (NK_FLDS_ARG). nk_flds_load is an argument of that call, so its loads — unconditional, from the addresses nk_grid_geom made for
+// u — are issued with u's, before the source runs; val is a fully unrolled register array filled from a __restrict__ const
+// pointer, so a load whose value the source never reads is dropped by the compiler. No select: outside a Dirichlet boundary
+// idx[q] is the node itself, and that is the value a field has there.
+static const char *k_grid_fields = R"NKSRC(
+#if NK_NFIELDS > 0
+// ---- read-only fields on the grid: field k at the stencil's points (never a dual: a constant of the differentiation)
+struct NK_FLDS {
+  nk_real val[NK_NPTS * NK_NFIELDS];
+  // field k at the node offset by (di, dj[, dk]): the offsets and the shape rule of u (no point of the stencil: NaN). Outside a
+  // Dirichlet boundary a field reads as at the node itself; at a periodic one the index wraps
+  __device__ __forceinline__ nk_real operator()(NK_OFFSET, int k = 0) const {
+    const int q = NK_OFFSET_SLOT;
+    if (q < 0) return NK_R(__builtin_nan(""));
+    return val[q * NK_NFIELDS + k];
+  }
+};
+__device__ __forceinline__ NK_FLDS nk_flds_load(const nk_real *__restrict__ a, int nn, const int (&idx)[NK_NPTS]) {
+  NK_FLDS fl;
+#pragma unroll
+  for (int q = 0; q < NK_NPTS; ++q) {
+#pragma unroll
+    for (int k = 0; k < NK_NFIELDS; ++k) fl.val[q * NK_NFIELDS + k] = a[k * nn + idx[q]];
+  }
+  return fl;
+}
+#define NK_FLDS_PARAM const nk_real *__restrict__ a,
+#define NK_FLDS_ARG nk_flds_load(a, nn, idx),
+#else
+#define NK_FLDS_PARAM
+#define NK_FLDS_ARG
+#endif
+)NKSRC";
+
+static const char *k_grid_kernels = R"NKSRC(
+// ---- generated kernels: one node per thread
+// The neighbourhood of a node: component c of point q from u[c·nn + idx[q]], every load unconditional, zero outside a
+// Dirichlet boundary. The partials of a dual: none to set (NK_SEED_NONE, T = nk_real), its one partial from v (NK_SEED_V),
+// or the unit seed of slot q·dof + c (NK_SEED_UNIT)
+enum { NK_SEED_NONE, NK_SEED_V, NK_SEED_UNIT };
+__device__ __forceinline__ nk_real &nk_value(nk_real &x) { return x; }
+__device__ __forceinline__ nk_real &nk_value(Dual &x) { return x.v; }
+template <int SEED, typename T>
+__device__ __forceinline__ void nk_grid_load(NK_NBHD<T> &nb, const nk_real *__restrict__ u, const nk_real *__restrict__ v,
+                                             int nn, const int (&idx)[NK_NPTS], const bool (&in)[NK_NPTS]) {
+#pragma unroll
+  for (int q = 0; q < NK_NPTS; ++q) {
+#pragma unroll
+    for (int c = 0; c < NK_DOF; ++c) {
+      const nk_real x = u[c * nn + idx[q]];
+      nk_value(nb.val[q * NK_DOF + c]) = in[q] ? x : NK_R(0);
+      if constexpr (SEED == NK_SEED_V) {
+        const nk_real d = v[c * nn + idx[q]];
+        nb.val[q * NK_DOF + c].d[0] = in[q] ? d : NK_R(0);
+      }
+      if constexpr (SEED == NK_SEED_UNIT) {
+#pragma unroll
+        for (int t = 0; t < NK_CH; ++t) nb.val[q * NK_DOF + c].d[t] = (t == q * NK_DOF + c) ? NK_R(1) : NK_R(0);
+      }
+    }
+  }
+}
+
+#if NK_GRID_SET == 0
+extern "C" __global__ void __launch_bounds__(NK_GRID_BLOCK)
+NK_KERNEL(residual)(NK_SIZES, const nk_real *__restrict__ p, NK_FLDS_PARAM const nk_real *__restrict__ u,
+                    nk_real *__restrict__ f) {
+  const int nn = nk_grid_nn(NK_SIZE_ARGS), node = (int)blockIdx.x * NK_GRID_BLOCK + (int)threadIdx.x;
+  if (node >= nn) return;
+  const NK_SITE s = nk_grid_site(node, NK_SIZE_ARGS);
+  int idx[NK_NPTS];
+  bool in[NK_NPTS];
+  nk_grid_geom(s, idx, in);
+  NK_NBHD<nk_real> nb;
+  nk_grid_load<NK_SEED_NONE>(nb, u, nullptr, nn, idx, in);
+  nk_real out[NK_DOF];
+#pragma unroll
+  for (int c = 0; c < NK_DOF; ++c) out[c] = NK_R(0);
+  nk_point<nk_real>(nb, NK_FLDS_ARG p, s, out);
+#pragma unroll
+  for (int c = 0; c < NK_DOF; ++c) f[c * nn + node] = out[c];
+}
+
+// J(u)·v exactly: the value of every neighbour from u, its one partial from v
+extern "C" __global__ void __launch_bounds__(NK_GRID_BLOCK)
+NK_KERNEL(jvp)(NK_SIZES, const nk_real *__restrict__ p, NK_FLDS_PARAM const nk_real *__restrict__ u,
+               const nk_real *__restrict__ v, nk_real *__restrict__ jv) {
+  const int nn = nk_grid_nn(NK_SIZE_ARGS), node = (int)blockIdx.x * NK_GRID_BLOCK + (int)threadIdx.x;
+  if (node >= nn) return;
+  const NK_SITE s = nk_grid_site(node, NK_SIZE_ARGS);
+  int idx[NK_NPTS];
+  bool in[NK_NPTS];
+  nk_grid_geom(s, idx, in);
+  NK_NBHD<Dual> nb;
+  nk_grid_load<NK_SEED_V>(nb, u, v, nn, idx, in);
+  Dual out[NK_DOF];
+#pragma unroll
+  for (int c = 0; c < NK_DOF; ++c) out[c] = Dual(NK_R(0));
+  nk_point<Dual>(nb, NK_FLDS_ARG p, s, out);
+#pragma unroll
+  for (int c = 0; c < NK_DOF; ++c) jv[c * nn + node] = out[c].d[0];
+}
+#else
+// The values of J(u) on the stencil's CSR pattern (ascending columns): slot q·dof + c of the duals carries ∂/∂u_c(point q).
+// Row c·nn + node holds, for c' = 0 … dof−1, its in-domain points in ascending node order: position c'·cnt + rank[q].
+// NK_GRID_DIRECT = 0: the workgroup's rows of one component are one contiguous piece of the value array — they are put together
+// in LDS and stored as whole lines (k_bratu_jac's way); 1: every thread stores its own partials, 8 bytes at a stride of a row.
+extern "C" __global__ void __launch_bounds__(NK_GRID_BLOCK)
+NK_KERNEL(jac)(NK_SIZES, const nk_real *__restrict__ p, NK_FLDS_PARAM const nk_real *__restrict__ u,
+               const int *__restrict__ rowptr, nk_real *__restrict__ vals) {
+  const int nn = nk_grid_nn(NK_SIZE_ARGS), node0 = (int)blockIdx.x * NK_GRID_BLOCK, node_t = node0 + (int)threadIdx.x;
+  if (node0 >= nn) return;   // (a workgroup past the grid; the launch has none)
+  const bool live = node_t < nn;
+#if NK_GRID_DIRECT
+  if (!live) return;
+#else
+  __shared__ nk_real sv[NK_GRID_BLOCK * NK_NPTS * NK_DOF];   // (at most 256·28 doubles: the 3-D star at dof 4)
+#endif
+  const int node = live ? node_t : nn - 1;   // (past the end: the last node again, nothing of it is kept)
+  const NK_SITE s = nk_grid_site(node, NK_SIZE_ARGS);
+  int idx[NK_NPTS];
+  bool in[NK_NPTS];
+  nk_grid_geom(s, idx, in);
+  NK_NBHD<Dual> nb;
+  nk_grid_load<NK_SEED_UNIT>(nb, u, nullptr, nn, idx, in);
+  Dual out[NK_DOF];
+#pragma unroll
+  for (int c = 0; c < NK_DOF; ++c) out[c] = Dual(NK_R(0));
+  nk_point<Dual>(nb, NK_FLDS_ARG p, s, out);
+  int rank[NK_NPTS], cnt = 0;
+#pragma unroll
+  for (int q = 0; q < NK_NPTS; ++q) {
+    int r = 0;
+#pragma unroll
+    for (int t = 0; t < NK_NPTS; ++t) r += (in[t] && idx[t] < idx[q]) ? 1 : 0;
+    rank[q] = r;
+    cnt += in[q] ? 1 : 0;
+  }
+#pragma unroll
+  for (int c = 0; c < NK_DOF; ++c) {
+    const int base = rowptr[c * nn + node];
+#if NK_GRID_DIRECT
+#pragma unroll
+    for (int q = 0; q < NK_NPTS; ++q) {
+      if (in[q]) {
+#pragma unroll
+        for (int c2 = 0; c2 < NK_DOF; ++c2) vals[base + c2 * cnt + rank[q]] = out[c].d[q * NK_DOF + c2];
+      }
+    }
+#else
+    // this workgroup's piece of component c: [p0, p1) ⊂ [0, nnz), at most NK_GRID_BLOCK·npts·dof values
+    const int last = node0 + NK_GRID_BLOCK < nn ? node0 + NK_GRID_BLOCK : nn;
+    const int p0 = rowptr[c * nn + node0], p1 = rowptr[c * nn + last];
+    if (live) {
+#pragma unroll
+      for (int q = 0; q < NK_NPTS; ++q) {
+        if (in[q]) {
+#pragma unroll
+          for (int c2 = 0; c2 < NK_DOF; ++c2) sv[base - p0 + c2 * cnt + rank[q]] = out[c].d[q * NK_DOF + c2];
+        }
+      }
+    }
+    __syncthreads();
+    for (int t = (int)threadIdx.x; t < p1 - p0; t += NK_GRID_BLOCK) vals[p0 + t] = sv[t];
+    __syncthreads();
+#endif
+  }
+}
+#endif
+)NKSRC";
+
+// what the user's source is held to, for the message of a source that does not compile
+static std::string grid_contract(int dim, int nfields) {
+  const bool d3 = dim == 3;
+  const std::string off = d3 ? "di, dj, dk" : "di, dj", flds = d3 ? "nk_flds3" : "nk_flds";
+  return std::string(nfields > 0 ? "the contract of a problem with fields is" : "the contract is") +
+         " `template <typename T> __device__ void nk_point(const " + (d3 ? "nk_nbhd3" : "nk_nbhd") + "<T> &u, " +
+         (nfields > 0 ? "const " + flds + " &a, " : "") + "const nk_real *p, " + (d3 ? "nk_site3" : "nk_site") +
+         " s, T *f)` with u(" + off + ", c) the component c at node " + (d3 ? "(i + di, j + dj, k + dk)" : "(i + di, j + dj)") +
+         (nfields > 0 ? ", a(" + off + ", k) the field k there (an nk_real, never a dual)" : "") + ", s = " +
+         (d3 ? "{i, j, k, nx, ny, nz}" : "{i, j, nx, ny}") + ", p the parameters and f the node's dof residuals (nk_real = double)";
+}
 
 // ----------------------------------------------------------------------------- compilation
 enum { GSET_F = 0 /* nk_grid_residual + nk_grid_jvp, NK_CH = 1 */, GSET_JAC = 1 /* nk_grid_jac, NK_CH = npts·dof */ };
 
-// dim = 2: nk_grid_residual / nk_grid_jvp / nk_grid_jac; dim = 3: the nk_grid3_ kernels. The 3-D programs carry -DNK_DIM=3 (it
-// tells their cache entries from the 2-D ones of the same source); the 2-D programs get the text and the options they always had.
-// nf = 0: the program without fields, from the text and the options it always had; nf = 1..4: the field text after the types,
-// the two field pieces in the kernels and one more option, -DNK_NFIELDS=<nf>, which also keeps the cache entries apart.
+// One program: its text is the same for every stencil but the stencil's lines, and all of what else it is comes from its
+// options, which every program gets in full (dim = 2: nk_grid_residual / nk_grid_jvp / nk_grid_jac; 3: the nk_grid3_ kernels)
 static int grid_compile(const char *source, int dim, int dof, int stencil, int boundary, int np, int nf, int gset, bool direct,
                         std::vector<char> *code, std::string *log) {
   NK_REQUIRE(source, "NULL source");
-  NK_TRY(dim == 3 ? grid3_check_shape(dof, stencil, boundary) : grid_check_shape(dof, stencil, boundary));
+  const grid_stencil *st = nullptr;
+  NK_TRY(grid_check_shape(dim, dof, stencil, boundary, &st));
   NK_REQUIRE(np >= 0 && np <= 32, "nparams = %d outside 0..32", np);
   NK_REQUIRE(nf >= 0 && nf <= 4, "nfields = %d outside 0..4 (read-only fields of one double per node)", nf);
-  const int npts = grid_npts(dim, stencil);
-  const bool r2 = grid_radius(stencil) == 2;
-  const char *types = dim == 3 ? (r2 ? k_grid3_types_r2 : k_grid3_types) : (r2 ? k_grid_types_r2 : k_grid_types);
-  const std::string full = std::string(nk_dual_prelude) + types + (nf > 0 ? (dim == 3 ? k_grid3_fields : k_grid_fields) : "") +
-                           "\n// ---- user source\n" + source + "\n" +
-                           (dim == 3 ? k_grid3_kernels_a : k_grid_kernels_a) +
-                           (dim == 3 ? (r2 ? k_grid3_wrap_r2 : k_grid3_wrap_r1) : (r2 ? k_grid_wrap_r2 : k_grid_wrap_r1)) +
-                           (dim == 3 ? grid_join(k_grid3_kernels_b, nf > 0) : grid_join(k_grid_kernels_b, nf > 0));
-  const std::string dd = "-DNK_DOF=" + std::to_string(dof), db = std::string("-DNK_BOX=") + (stencil == NK_GRID_BOX ? "1" : "0"),
-                    dp = std::string("-DNK_PERIODIC=") + (boundary == NK_GRID_PERIODIC ? "1" : "0"),
-                    dc = "-DNK_CH=" + std::to_string(gset == GSET_JAC ? npts * dof : 1), ds = "-DNK_GRID_SET=" + std::to_string(gset),
-                    dr = std::string("-DNK_GRID_DIRECT=") + (direct ? "1" : "0");
-  std::vector<const char *> opts = {"--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-std=c++17", dd.c_str(), db.c_str(),
-                                    dp.c_str(), dc.c_str(), ds.c_str(), dr.c_str()};
-  if (dim == 3) opts.push_back("-DNK_DIM=3");
-  // radius 2: the stencil's code, which only these programs carry (it tells star2 from diamond2 in k_grid_types_r2 and keeps
-  // their cache entries apart from the radius-1 programs of the same source)
-  const std::string dn = "-DNK_STENCIL=" + std::to_string(stencil);
-  if (r2) opts.push_back(dn.c_str());
-  const std::string df = "-DNK_NFIELDS=" + std::to_string(nf);
-  if (nf > 0) opts.push_back(df.c_str());
-  // the same source with the same options gives the same code object: problems created again (another grid size, another
-  // context) skip the compiler
+  const std::string stencil_text = grid_stencil_text(*st);
+  const std::string full = std::string(nk_dual_prelude) + stencil_text + k_grid_types + k_grid_fields + "\n// ---- user source\n" +
+                           source + "\n" + k_grid_kernels;
+  const std::string defs[] = {"-DNK_DIM=" + std::to_string(dim), "-DNK_NFIELDS=" + std::to_string(nf),
+                              "-DNK_DOF=" + std::to_string(dof),
+                              std::string("-DNK_PERIODIC=") + (boundary == NK_GRID_PERIODIC ? "1" : "0"),
+                              "-DNK_CH=" + std::to_string(gset == GSET_JAC ? st->npts * dof : 1),
+                              "-DNK_GRID_SET=" + std::to_string(gset), std::string("-DNK_GRID_DIRECT=") + (direct ? "1" : "0")};
+  std::vector<const char *> opts = {"--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-std=c++17"};
+  for (const std::string &d : defs) opts.push_back(d.c_str());
+  // the same source for the same stencil with the same options gives the same code object: problems created again (another grid
+  // size, another context) skip the compiler. The key holds all that varies between two programs: the options, the stencil's
+  // lines and the user's source (the rest of the text is the same for all)
   static std::mutex mtx;
   static std::map<std::string, std::vector<char>> cache;
   std::string key;
   for (const char *o : opts) { key += o; key += ' '; }
-  key += '\n';
+  key += stencil_text;
   key += source;
   {
     std::lock_guard<std::mutex> lock(mtx);
@@ -833,8 +550,7 @@ static int grid_compile(const char *source, int dim, int dof, int stencil, int b
   bool failed = false;
   NK_TRY(nk_rtc_compile(full, "nk_grid_user.hip", opts, code, log, &failed));
   if (failed)
-    NK_FAIL(NK_E_INVALID, "grid residual source does not compile (%s): %.900s",
-            dim == 3 ? (nf > 0 ? k_grid3f_contract : k_grid3_contract) : (nf > 0 ? k_gridf_contract : k_grid_contract),
+    NK_FAIL(NK_E_INVALID, "grid residual source does not compile (%s): %.900s", grid_contract(dim, nf).c_str(),
             log && !log->empty() ? log->c_str() : "(no log)");
   std::lock_guard<std::mutex> lock(mtx);
   cache[key] = *code;
@@ -1010,10 +726,9 @@ extern "C" int nk_problem_get_field(nk_problem *P, int k, double *out, int memsp
   return NK_OK;
 }
 
-// nz = 0: a 2-D problem (nk_problem_create_grid); nz > 0: a 3-D one (nk_problem_create_grid3)
-static int grid_create(nk_ctx *ctx, const char *source, int64_t nx, int64_t ny, int64_t nz, int dof, int stencil, int boundary,
-                       const double *params, int nparams, int nfields, nk_problem **out) {
-  const int dim = nz > 0 ? 3 : 2;
+// dim = 2: nz is not read (nk_problem_create_grid); dim = 3: nk_problem_create_grid3
+static int grid_create(nk_ctx *ctx, const char *source, int dim, int64_t nx, int64_t ny, int64_t nz, int dof, int stencil,
+                       int boundary, const double *params, int nparams, int nfields, nk_problem **out) {
   NK_REQUIRE(ctx && source && out, "NULL argument");
   NK_REQUIRE(params || nparams == 0, "NULL params with nparams = %d", nparams);
   NK_REQUIRE(nfields >= 0 && nfields <= 4, "nfields = %d outside 0..4 (read-only fields of one double per node)", nfields);
@@ -1021,16 +736,13 @@ static int grid_create(nk_ctx *ctx, const char *source, int64_t nx, int64_t ny, 
     NK_FAIL(NK_E_UNSUPPORTED, "compiled grid problems run on one rank (this context has %d): no halo exchange is generated",
             ctx->nranks);
   NK_HIP(hipSetDevice(ctx->device));
+  if (dim == 2) nz = 1;
   // the pattern first: it validates the geometry before anything is compiled
   int64_t nnz = 0;
-  const auto pattern = [&](int32_t *rowptr, int32_t *colind) {
-    return dim == 3 ? nk_grid3_pattern(nx, ny, nz, dof, stencil, boundary, rowptr, colind, &nnz)
-                    : nk_grid_pattern(nx, ny, dof, stencil, boundary, rowptr, colind, &nnz);
-  };
-  NK_TRY(pattern(nullptr, nullptr));
-  const int64_t n = nx * ny * (dim == 3 ? nz : 1) * dof;
+  NK_TRY(grid_pattern(dim, nx, ny, nz, dof, stencil, boundary, nullptr, nullptr, &nnz));
+  const int64_t n = nx * ny * nz * dof;
   std::vector<int32_t> rp((size_t)n + 1), ci((size_t)nnz);
-  NK_TRY(pattern(rp.data(), ci.data()));
+  NK_TRY(grid_pattern(dim, nx, ny, nz, dof, stencil, boundary, rp.data(), ci.data(), &nnz));
   std::vector<char> code_f, code_j;
   std::string log;
   NK_TRY(grid_compile(source, dim, dof, stencil, boundary, nparams, nfields, GSET_F, false, &code_f, &log));
@@ -1082,20 +794,18 @@ static int grid_create(nk_ctx *ctx, const char *source, int64_t nx, int64_t ny, 
 
 extern "C" int nk_problem_create_grid(nk_ctx *ctx, const char *source, int64_t nx, int64_t ny, int dof, int stencil, int boundary,
                                       const double *params, int nparams, nk_problem **out) {
-  return grid_create(ctx, source, nx, ny, 0, dof, stencil, boundary, params, nparams, 0, out);
+  return grid_create(ctx, source, 2, nx, ny, 1, dof, stencil, boundary, params, nparams, 0, out);
 }
 
 extern "C" int nk_problem_create_grid3(nk_ctx *ctx, const char *source, int64_t nx, int64_t ny, int64_t nz, int dof, int stencil,
                                        int boundary, const double *params, int nparams, nk_problem **out) {
-  // (grid_create tells the dimensions apart by nz > 0: a side below 3 must not fall through to the 2-D path)
-  if (nz < 3) NK_TRY(grid3_check_size(nx, ny, nz, stencil));
-  return grid_create(ctx, source, nx, ny, nz, dof, stencil, boundary, params, nparams, 0, out);
+  return grid_create(ctx, source, 3, nx, ny, nz, dof, stencil, boundary, params, nparams, 0, out);
 }
 
-// fields: nz = 0 is the 2-D problem, nz >= 3 the 3-D one; nfields = 0 gives the problem of the two entry points above
+// fields: nz = 0 is the 2-D problem, any other nz the 3-D one with that many planes (so nz = 1 or 2 is refused as a 3-D grid
+// too small, not taken for a 2-D one); nfields = 0 gives the problem of the two entry points above
 extern "C" int nk_problem_create_grid_fields(nk_ctx *ctx, const char *source, int64_t nx, int64_t ny, int64_t nz, int dof,
                                              int stencil, int boundary, const double *params, int nparams, int nfields,
                                              nk_problem **out) {
-  if (nz != 0 && nz < 3) NK_TRY(grid3_check_size(nx, ny, nz, stencil));
-  return grid_create(ctx, source, nx, ny, nz, dof, stencil, boundary, params, nparams, nfields, out);
+  return grid_create(ctx, source, nz != 0 ? 3 : 2, nx, ny, nz, dof, stencil, boundary, params, nparams, nfields, out);
 }

@@ -156,6 +156,29 @@ def test_star_source_that_reads_a_corner_gives_nan(nls, dev):
     Pb.close()
 
 
+# a radius-1 source that reads two nodes away
+TWO_AWAY_SRC = r"""
+template <typename T>
+__device__ void nk_point(const nk_nbhd<T> &u, const nk_real *p, nk_site s, T *f) {
+  f[0] = 4.0 * u(0, 0) - u(-1, 0) + u(2, 0);
+}
+"""
+
+
+@pytest.mark.parametrize("stencil", ["star", "box"])
+def test_radius_1_source_that_reads_two_nodes_away_gives_nan(nls, dev, stencil):
+    """every offset that is no point of the stencil reads NaN, at radius 1 as at radius 2: u(2, 0) on a 6 x 5 Dirichlet grid
+    (interior and boundary nodes) under star and box; the same source is a valid star2 problem"""
+    u = _t(np.linspace(-1, 1, 30), dev)
+    P = nls.CompiledGridProblem(TWO_AWAY_SRC, 6, 5, stencil=stencil)
+    f = _np(P.residual(u))
+    assert f.shape == (30,) and np.all(np.isnan(f))
+    P.close()
+    P2 = nls.CompiledGridProblem(TWO_AWAY_SRC, 6, 5, stencil="star2")
+    assert np.all(np.isfinite(_np(P2.residual(u))))
+    P2.close()
+
+
 def test_reinit_p_changes_the_residual_as_the_restatement_says(nls, dev):
     import torch
     name, (nx, ny) = "box_periodic", (37, 29)

@@ -1,0 +1,117 @@
+"""Resource notes of every generated grid kernel (csrc/nk_grid.hip) of this build against another build of the package, without
+a GPU: every problem of the four PROBLEMS tables under tests/, both programs, both forms of the fill.
+
+    python tools/grid_resources_ab.py --parent <root of the other checkout, built> [--out profiles/<name>.txt]
+
+For each kernel: LDS bytes equal, private segment and spilled VGPRs 0 in both, and the waves-per-SIMD step that VGPRs + AGPRs
+allow (allocation granule 8, min(8, 512 // allocation)) no lower than the parent's. Exit status 1 if a row fails.
+
+Each build is read in a child process of its own (two libraries of one name do not share a process); the problems are this
+checkout's tables in both."""
+import argparse
+import json
+import os
+import re
+import subprocess
+import sys
+import tempfile
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+READELF = "/opt/rocm/llvm/bin/llvm-readelf"
+KERNELS = {2: {0: ("nk_grid_residual", "nk_grid_jvp"), 1: ("nk_grid_jac",)},
+           3: {0: ("nk_grid3_residual", "nk_grid3_jvp"), 1: ("nk_grid3_jac",)}}
+STENCIL_ID = {"star": 0, "box": 1, "star2": 16, "diamond2": 17}
+BOUNDARY_ID = {"dirichlet": 0, "periodic": 1}
+
+
+def problems():
+    """(table, name, source, dim, dof, stencil, boundary, nparams, nfields) of every problem of the four tables"""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import grid3_reference as G3
+    import grid_r2_reference as G2
+    import grid_reference as G1
+    import gridf_reference as GF
+    out = []
+    for table, mod, dim in (("grid", G1, 2), ("grid3", G3, 3), ("grid_r2", G2, None), ("gridf", GF, None)):
+        for name in sorted(mod.PROBLEMS):
+            p = mod.PROBLEMS[name]
+            out.append((table, name, p.source, dim or p.dim, p.dof, p.stencil, p.boundary, len(p.params), getattr(p, "nfields", 0)))
+    return out
+
+
+def waves(vgprs, agprs):
+    alloc = -(-(vgprs + agprs) // 8) * 8
+    return min(8, 512 // max(alloc, 8))
+
+
+def collect(root):
+    """in a child: the notes of every kernel of the build at `root` → JSON on stdout"""
+    import ctypes as C
+    sys.path.insert(0, root)
+    from nonlinearsolve_jl_amd import _lib as L
+    lib, rows = L.lib(), {}
+    with tempfile.TemporaryDirectory() as tmp:
+        for direct in (0, 1):
+            os.environ["NK_GRID_FILL_DIRECT"] = str(direct)
+            for table, name, source, dim, dof, stencil, boundary, nparams, nfields in problems():
+                for jac in (0, 1):
+                    if jac == 0 and direct == 1:
+                        continue   # (the residual / JVP program does not depend on the form of the fill)
+                    args = (source.encode(), dim, dof, STENCIL_ID[stencil], BOUNDARY_ID[boundary], nparams, nfields, jac)
+                    nb = C.c_int64()
+                    assert lib.nk_grid_fields_code_object(*args, None, 0, C.byref(nb)) == 0, lib.nk_last_error()
+                    buf = C.create_string_buffer(nb.value)
+                    assert lib.nk_grid_fields_code_object(*args, buf, nb.value, C.byref(nb)) == 0
+                    path = os.path.join(tmp, "k.co")
+                    with open(path, "wb") as fh:
+                        fh.write(buf.raw[:nb.value])
+                    notes = subprocess.run([READELF, "--notes", path], capture_output=True, text=True, check=True).stdout
+                    for block in re.split(r"\n\s*- \.", notes)[1:]:
+                        get = lambda key: re.search(r"\.%s:\s+(\w+)" % key, block)
+                        if not (get("name") and get("private_segment_fixed_size")) or get("name").group(1) not in KERNELS[dim][jac]:
+                            continue
+                        program = "fill, direct" if jac and direct else ("fill, staged" if jac else "residual + JVP")
+                        rows[f"{table}/{name}|{get('name').group(1)}|{program}"] = {
+                            k: int(get(key).group(1)) if get(key) else 0
+                            for k, key in (("private", "private_segment_fixed_size"), ("vgprs", "vgpr_count"),
+                                           ("agprs", "agpr_count"), ("spills", "vgpr_spill_count"),
+                                           ("lds", "group_segment_fixed_size"))}
+    json.dump(rows, sys.stdout)
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--parent", help="root of the other checkout (built)")
+    ap.add_argument("--out", help="write the table here as well")
+    ap.add_argument("--collect", help=argparse.SUPPRESS)
+    a = ap.parse_args()
+    if a.collect:
+        return collect(a.collect)
+    if not a.parent:
+        ap.error("--parent is required")
+    both = [json.loads(subprocess.run([sys.executable, os.path.abspath(__file__), "--collect", os.path.abspath(r)],
+                                      capture_output=True, text=True, check=True).stdout) for r in (a.parent, ROOT)]
+    old, new = both
+    assert sorted(old) == sorted(new) and old, "the two builds do not have the same kernels"
+    lines = ["# problem | kernel | program | parent VGPRs (+AGPRs) -> waves/SIMD | new VGPRs (+AGPRs) -> waves/SIMD | LDS parent / new "
+             "| private, spills (new) | verdict"]
+    bad = 0
+    for key in sorted(old):
+        o, n = old[key], new[key]
+        wo, wn = waves(o["vgprs"], o["agprs"]), waves(n["vgprs"], n["agprs"])
+        ok = (o["lds"] == n["lds"] and n["private"] == 0 and n["spills"] == 0 and o["private"] == 0 and o["spills"] == 0
+              and wn >= wo)
+        bad += not ok
+        lines.append(f"{' | '.join(key.split('|'))} | {o['vgprs']} (+{o['agprs']}) -> {wo} | {n['vgprs']} (+{n['agprs']}) -> {wn} | "
+                     f"{o['lds']} / {n['lds']} | {n['private']}, {n['spills']} | {'ok' if ok else 'FAIL'}")
+    lines.append(f"# {len(old)} kernels, {bad} failed")
+    text = "\n".join(lines) + "\n"
+    sys.stdout.write(text)
+    if a.out:
+        with open(a.out, "w", encoding="utf-8") as fh:
+            fh.write(text)
+    return 1 if bad else 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
