@@ -502,7 +502,8 @@ int nk_jac_values_colored(nk_problem *P, const double *u, int memspace, nk_csr *
  * CSR pattern (a dual with npts·dof partials, unit seeds). No finite differences anywhere.
  * Geometry: nx × ny nodes, nx, ny >= 3 (not necessarily square); dof = 1..4 components per node; stencil NK_GRID_STAR (5 points)
  * or NK_GRID_BOX (9 points, dof <= 2: a row has at most 20 partials); boundary NK_GRID_DIRICHLET0 (a neighbour outside the grid
- * reads as the constant 0 and has no column) or NK_GRID_PERIODIC (indices wrap in both directions). Unknown c of node (i, j) is
+ * reads as the constant 0 and has no column), NK_GRID_PERIODIC (indices wrap in both directions) or a kind per side packed by
+ * NK_GRID_SIDES (mirror walls, a channel: see the enum below). Unknown c of node (i, j) is
  * element c·nx·ny + j·nx + i (the Brusselator's layout). One rank only: NK_E_UNSUPPORTED on a context with more.
  * The object is an nk_problem of kind NK_PROBLEM_USER whose callbacks launch the generated kernels: every algorithm, linear
  * solver and preconditioner object takes it as it takes any callback problem — so the matrix-free GMRES keeps the callback
@@ -519,10 +520,31 @@ int nk_jac_values_colored(nk_problem *P, const double *u, int memspace, nk_csr *
  *   STAR2     (0,−2) (0,−1) (−2,0) (−1,0) C (1,0) (2,0) (0,1) (0,2)
  *   DIAMOND2  (0,−2) (−1,−1) (0,−1) (1,−1) (−2,0) (−1,0) C (1,0) (2,0) (−1,1) (0,1) (1,1) (0,2)
  * Every program is compiled from one text, which starts with its stencil's point count and offsets, and with one full set of
- * options (-DNK_DIM, -DNK_NFIELDS, -DNK_DOF, -DNK_PERIODIC, -DNK_CH, -DNK_GRID_SET, -DNK_GRID_DIRECT). Every other code
+ * options (-DNK_DIM, -DNK_NFIELDS, -DNK_DOF, -DNK_XLO … -DNK_ZHI, -DNK_CH, -DNK_GRID_SET, -DNK_GRID_DIRECT). Every other code
  * (2, 18, …) is NK_E_INVALID. */
 enum { NK_GRID_STAR = 0, NK_GRID_BOX = 1, NK_GRID_STAR2 = 16, NK_GRID_DIAMOND2 = 17 }; /* stencil  */
-enum { NK_GRID_DIRICHLET0 = 0, NK_GRID_PERIODIC = 1 }; /* boundary */
+/* The boundary is one int wherever it appears. 0 and 1 are the two uniform boundaries. NK_GRID_SIDES(xlo, xhi, ylo, yhi, zlo,
+ * zhi) gives every side of every axis a kind of its own (4 bits each under the marker bit NK_GRID_SIDES_BIT); the z kinds are
+ * for 3-D grids — leave them 0 in 2-D, a set one is NK_E_INVALID there, so a typo shows. A ghost node at distance k = 1..radius
+ * outside a side of an axis of n nodes:
+ *   NK_GRID_DIRICHLET0   reads 0 and has no column;
+ *   NK_GRID_PERIODIC     wraps; both sides of the axis must be periodic, else NK_E_INVALID naming the axis;
+ *   NK_GRID_MIRROR_NODE  the wall is the outermost node: −k -> k and n−1+k -> n−1−k (NumPy's `reflect`);
+ *   NK_GRID_MIRROR_FACE  the wall is half a cell outside: −k -> k−1 and n−1+k -> n−k (NumPy's `symmetric`) — the zero-flux wall
+ *                        of a cell-centred grid.
+ * Axes are independent. A point that leaves the grid through a Dirichlet-0 side of ANY axis reads 0 and has no column, whatever
+ * the other axes do (its field read is the field at the node itself, the rule above). Otherwise every axis is wrapped or
+ * mirrored on its own, and u, v and the fields are read at the resulting node. A mirrored ghost is another unknown: the
+ * Jacobian is the true dF/du, the partials of all stencil points of a row that land on one node are added into one entry
+ * (in ascending point order) and the pattern holds that column once, columns ascending as before — at a mirror-node wall −1
+ * and +1 both land on node 1, at a mirror-face wall −1 lands on the centre, the box at a corner mirrored in two axes puts four
+ * points on one node. The side minimum stays 2·radius + 1: with it one reflection always lands inside the grid. A packed code
+ * whose sides are all Dirichlet-0 (all periodic) IS code 0 (1): same pattern, same program options, same code objects. */
+enum { NK_GRID_DIRICHLET0 = 0, NK_GRID_PERIODIC = 1, NK_GRID_MIRROR_NODE = 2, NK_GRID_MIRROR_FACE = 3 }; /* boundary */
+#define NK_GRID_SIDES_BIT (1 << 24)
+#define NK_GRID_SIDES(xlo, xhi, ylo, yhi, zlo, zhi)                                                                        \
+  (NK_GRID_SIDES_BIT | ((xlo) & 15) | (((xhi) & 15) << 4) | (((ylo) & 15) << 8) | (((yhi) & 15) << 12) | (((zlo) & 15) << 16) | \
+   (((zhi) & 15) << 20))
 /* The CSR pattern of the Jacobian (host only, no device needed): rowptr dof·nx·ny + 1 entries, colind *nnz entries, 0-based,
  * columns ascending within a row. Every (stencil point in the domain) × (component) entry is kept — structural even where a
  * derivative is zero. colind = NULL (and / or rowptr = NULL) asks for the sizes only. */
@@ -547,7 +569,7 @@ int nk_problem_create_grid(nk_ctx *ctx, const char *source, int64_t nx, int64_t 
  * (component-major, as in 2-D). NK_GRID_STAR is the 7-point star with dof = 1..4, NK_GRID_BOX the 27-point box with dof = 1:
  * a row has at most 28 partials (this cap replaces 2-D's 20 for these entry points only; no permitted combination spills —
  * the generated kernels have no private segment). The boundary — NK_GRID_DIRICHLET0 or NK_GRID_PERIODIC — applies to all three
- * directions. The pattern's 32-bit indices are checked: nx·ny·nz·dof·npts·dof <= INT32_MAX.
+ * directions; NK_GRID_SIDES gives each of the six sides its own kind. The pattern's 32-bit indices are checked: nx·ny·nz·dof·npts·dof <= INT32_MAX.
  * Stencil points are numbered by ascending node index inside the grid — star: (0,0,−1) (0,−1,0) (−1,0,0) C (1,0,0) (0,1,0)
  * (0,0,1); box: dk outermost, di innermost — and the pattern keeps every (point in the domain) × (component) entry in ascending
  * column order, as in 2-D. The object is the same NK_PROBLEM_USER problem owning its pattern: nk_problem_set_params,
@@ -574,8 +596,8 @@ int nk_problem_create_grid3(nk_ctx *ctx, const char *source, int64_t nx, int64_t
  * Offsets and shape rule are the stencil's own: a read outside the shape (a corner of the star, |di| + |dj| > 2 of the diamond)
  * returns NaN, exactly as u does. Boundary rule for fields: at a periodic boundary the index wraps, as for u; outside a
  * Dirichlet boundary a field reads as THE FIELD AT THE NODE ITSELF (not 0: the clamped address the u load already computes,
- * without the select that zeroes u), so a face coefficient 0.5·(a(0,0) + a(1,0)) degenerates to a(0,0) at the wall. A source that
- * wants something else tests s.
+ * without the select that zeroes u), so a face coefficient 0.5·(a(0,0) + a(1,0)) degenerates to a(0,0) at the wall; at a mirror
+ * side a field is read at the mirrored node, as u is. A source that wants something else tests s.
  * Storage: field k of node m (m = j·nx + i, 3-D (k·ny + j)·nx + i) is element k·nn + m of one device buffer of nfields·nn
  * doubles which the problem owns; it is zero-filled at creation, so nothing is ever read uninitialised. nk_problem_set_field
  * copies nn doubles from host or device memory into field k on the context's stream and, like nk_problem_set_params, marks the

@@ -172,6 +172,38 @@ brusselator2d(N; A = 3.4, B = 1.0, α = 10.0, dx = 1 / (N - 1), kw...) = DeviceP
 
 const GRID_STENCILS = Dict(:star => 0, :box => 1, :star2 => 16, :diamond2 => 17)
 const GRID_BOUNDARIES = Dict(:dirichlet => 0, :periodic => 1)
+const GRID_SIDE_KINDS = Dict(:dirichlet => 0, :periodic => 1, :mirror_node => 2, :mirror_face => 3)
+"""`grid_sides(xlo, xhi, ylo, yhi[, zlo, zhi])`: the header's `NK_GRID_SIDES` — one boundary kind per side of the grid
+(`:dirichlet`, `:periodic`, `:mirror_node`, `:mirror_face`), 4 bits each under the marker bit. `:mirror_node` mirrors about the
+outermost node (−k ↦ k), `:mirror_face` about the face half a cell outside it (−k ↦ k−1, the zero-flux wall of a cell-centred
+grid); both sides of a periodic axis must be periodic. A mirrored ghost is another unknown: the stencil points of a row that
+land on one node share one column of the pattern and their partials are added."""
+function grid_sides(kinds::Symbol...)
+    length(kinds) in (4, 6) || throw(ArgumentError("grid_sides takes 4 kinds (2-D) or 6 (3-D), got $(length(kinds))"))
+    code = 1 << 24
+    for (s, k) in enumerate(kinds)
+        haskey(GRID_SIDE_KINDS, k) || throw(ArgumentError("boundary side $k: expected one of $(sort(collect(keys(GRID_SIDE_KINDS))))"))
+        code |= GRID_SIDE_KINDS[k] << (4 * (s - 1))
+    end
+    return code
+end
+# boundary = :dirichlet | :periodic, a tuple of 2·dim kinds, or pairs by axis (:x => kind | (lo, hi), ...; missing axes :dirichlet)
+grid_boundary(b::Symbol, dim::Integer) = haskey(GRID_BOUNDARIES, b) ? GRID_BOUNDARIES[b] :
+    throw(ArgumentError("boundary = $b: expected :dirichlet, :periodic, a tuple of $(2dim) kinds or pairs by axis"))
+function grid_boundary(b::Tuple{Vararg{Symbol}}, dim::Integer)
+    length(b) == 2dim || throw(ArgumentError("boundary = $b: a $dim-D grid has $(2dim) sides (lo and hi of every axis)"))
+    return grid_sides(b...)
+end
+function grid_boundary(b::Union{AbstractDict, Tuple{Vararg{Pair}}, NamedTuple}, dim::Integer)
+    d, axes = Dict(pairs(b)), (:x, :y, :z)[1:dim]
+    all(a -> a in axes, keys(d)) || throw(ArgumentError("boundary = $b: the axes of a $dim-D grid are $axes"))
+    kinds = Symbol[]
+    for a in axes
+        k = get(d, a, :dirichlet)
+        append!(kinds, k isa Symbol ? (k, k) : Tuple(k))
+    end
+    return grid_boundary(Tuple(kinds), dim)
+end
 """`CompiledGridProblem(source, nx, ny; dof = 1, stencil = :star, boundary = :dirichlet, params = Float64[])`: a residual given
 pointwise on an nx × ny grid through a radius-1 or radius-2 stencil as HIP source
 `template <typename T> __device__ void nk_point(const nk_nbhd<T> &u, const nk_real *p, nk_site s, T *f)`; the library compiles
@@ -183,23 +215,27 @@ Radius 2 (offsets in −2 … 2, sides ≥ 5): `stencil = :star2`, the 9-point s
 Fields: with `fields = 1..4` the problem owns that many read-only arrays of one Float64 per node and the source takes
 `const nk_flds &a` (3-D: `const nk_flds3 &a`) after `u`; `a(di, dj, k)` is field k at the neighbouring node, a constant of the
 differentiation. A periodic index wraps; outside a Dirichlet boundary a field reads as the field at the node itself. Fields are
-zero until `set_field!(P, k, x)` (k is 0-based, as in the source); `get_field(P, k)` copies one out (nk_problem_create_grid_fields)."""
+zero until `set_field!(P, k, x)` (k is 0-based, as in the source); `get_field(P, k)` copies one out (nk_problem_create_grid_fields).
+Boundaries: `boundary = :dirichlet` or `:periodic` for the whole grid, or a kind per side — a tuple of 2·dim kinds
+`(xlo, xhi, ylo, yhi[, zlo, zhi])` or a NamedTuple / Dict by axis, `(x = :periodic, y = (:dirichlet, :mirror_face))`, whose
+missing axes are `:dirichlet` — see `grid_sides`."""
 function CompiledGridProblem(source::AbstractString, nx::Integer, ny::Integer; dof::Integer = 1, stencil::Symbol = :star,
-                             boundary::Symbol = :dirichlet, params::Vector{Float64} = Float64[], ctx = default_ctx(),
+                             boundary = :dirichlet, params::Vector{Float64} = Float64[], ctx = default_ctx(),
                              nz::Union{Nothing, Integer} = nothing, fields::Integer = 0)
     out = Ref{Ptr{Cvoid}}(C_NULL)
+    bd = grid_boundary(boundary, nz === nothing ? 2 : 3)
     par = isempty(params) ? Float64[0.0] : params
     if fields != 0
         GC.@preserve par nkcheck(@ccall libnk.nk_problem_create_grid_fields(ctx.ptr::Ptr{Cvoid}, String(source)::Cstring,
             Int64(nx)::Int64, Int64(ny)::Int64, Int64(nz === nothing ? 0 : nz)::Int64, dof::Cint, GRID_STENCILS[stencil]::Cint,
-            GRID_BOUNDARIES[boundary]::Cint, par::Ptr{Float64}, length(params)::Cint, fields::Cint, out::Ptr{Ptr{Cvoid}})::Cint)
+            bd::Cint, par::Ptr{Float64}, length(params)::Cint, fields::Cint, out::Ptr{Ptr{Cvoid}})::Cint)
     elseif nz === nothing
         GC.@preserve par nkcheck(@ccall libnk.nk_problem_create_grid(ctx.ptr::Ptr{Cvoid}, String(source)::Cstring, Int64(nx)::Int64,
-            Int64(ny)::Int64, dof::Cint, GRID_STENCILS[stencil]::Cint, GRID_BOUNDARIES[boundary]::Cint, par::Ptr{Float64},
+            Int64(ny)::Int64, dof::Cint, GRID_STENCILS[stencil]::Cint, bd::Cint, par::Ptr{Float64},
             length(params)::Cint, out::Ptr{Ptr{Cvoid}})::Cint)
     else
         GC.@preserve par nkcheck(@ccall libnk.nk_problem_create_grid3(ctx.ptr::Ptr{Cvoid}, String(source)::Cstring, Int64(nx)::Int64,
-            Int64(ny)::Int64, Int64(nz)::Int64, dof::Cint, GRID_STENCILS[stencil]::Cint, GRID_BOUNDARIES[boundary]::Cint,
+            Int64(ny)::Int64, Int64(nz)::Int64, dof::Cint, GRID_STENCILS[stencil]::Cint, bd::Cint,
             par::Ptr{Float64}, length(params)::Cint, out::Ptr{Ptr{Cvoid}})::Cint)
     end
     nl = Ref{Int64}(0)
@@ -220,11 +256,11 @@ function get_field(P::DeviceProblem, k::Integer, nn::Integer)
     return x
 end
 """`grid_pattern(nx, ny; dof, stencil, boundary, nz)` → `(rowptr, colind)`, 0-based `Int32`: the CSR pattern of that Jacobian (host
-only); with `nz` the pattern of the nx × ny × nz grid."""
-function grid_pattern(nx::Integer, ny::Integer; dof::Integer = 1, stencil::Symbol = :star, boundary::Symbol = :dirichlet,
+only); with `nz` the pattern of the nx × ny × nz grid. `boundary` as for `CompiledGridProblem`."""
+function grid_pattern(nx::Integer, ny::Integer; dof::Integer = 1, stencil::Symbol = :star, boundary = :dirichlet,
                       nz::Union{Nothing, Integer} = nothing)
     nnz = Ref{Int64}(0)
-    st, bd = GRID_STENCILS[stencil], GRID_BOUNDARIES[boundary]
+    st, bd = GRID_STENCILS[stencil], grid_boundary(boundary, nz === nothing ? 2 : 3)
     if nz !== nothing
         nkcheck(@ccall libnk.nk_grid3_pattern(Int64(nx)::Int64, Int64(ny)::Int64, Int64(nz)::Int64, dof::Cint, st::Cint, bd::Cint,
             C_NULL::Ptr{Int32}, C_NULL::Ptr{Int32}, nnz::Ptr{Int64})::Cint)
@@ -242,22 +278,23 @@ function grid_pattern(nx::Integer, ny::Integer; dof::Integer = 1, stencil::Symbo
 end
 """`grid_compile_check(source; dof, stencil, boundary, nparams, dim = 2)`: compile the three kernels for gfx950 (no device needed);
 bytes of code. `dim = 3`: the 3-D contract."""
-function grid_compile_check(source::AbstractString; dof::Integer = 1, stencil::Symbol = :star, boundary::Symbol = :dirichlet,
+function grid_compile_check(source::AbstractString; dof::Integer = 1, stencil::Symbol = :star, boundary = :dirichlet,
                             nparams::Integer = 0, dim::Integer = 2, fields::Integer = 0)
     nb = Ref{Int64}(0)
     dim in (2, 3) || throw(ArgumentError("dim = $dim: expected 2 or 3"))
+    bd = grid_boundary(boundary, dim)
     if fields != 0
         nkcheck(@ccall libnk.nk_grid_fields_compile_check(String(source)::Cstring, dim::Cint, dof::Cint, GRID_STENCILS[stencil]::Cint,
-            GRID_BOUNDARIES[boundary]::Cint, nparams::Cint, fields::Cint, nb::Ptr{Int64})::Cint)
+            bd::Cint, nparams::Cint, fields::Cint, nb::Ptr{Int64})::Cint)
         return nb[]
     end
     if dim == 3
         nkcheck(@ccall libnk.nk_grid3_compile_check(String(source)::Cstring, dof::Cint, GRID_STENCILS[stencil]::Cint,
-            GRID_BOUNDARIES[boundary]::Cint, nparams::Cint, nb::Ptr{Int64})::Cint)
+            bd::Cint, nparams::Cint, nb::Ptr{Int64})::Cint)
         return nb[]
     end
     nkcheck(@ccall libnk.nk_grid_compile_check(String(source)::Cstring, dof::Cint, GRID_STENCILS[stencil]::Cint,
-        GRID_BOUNDARIES[boundary]::Cint, nparams::Cint, nb::Ptr{Int64})::Cint)
+        bd::Cint, nparams::Cint, nb::Ptr{Int64})::Cint)
     return nb[]
 end
 
@@ -860,7 +897,7 @@ end
 # point with memspace = NK_DEVICE, and device-resident Julia operators / preconditioners serve through the device-pointer
 # callback contract (nk_matvec_fn proper).
 
-export Ctx, DeviceVector, DeviceCSR, DeviceProblem, bratu2d, brusselator2d, CompiledGridProblem, grid_pattern, grid_compile_check, set_field!, get_field, mi355x_function, MI355XGMRES,
+export Ctx, DeviceVector, DeviceCSR, DeviceProblem, bratu2d, brusselator2d, CompiledGridProblem, grid_pattern, grid_compile_check, grid_sides, set_field!, get_field, mi355x_function, MI355XGMRES,
     MI355XNewtonKrylovAlg, EnsembleKernel, LeastSquaresEnsembleKernel, SimpleGaussNewton, vectorized_solve, DevicePreconditioner, DeviceILU0, DeviceILUT, DeviceAMG, DeviceJacobi, update!, update_values!
 
 end # module

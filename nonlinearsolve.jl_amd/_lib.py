@@ -19,7 +19,17 @@ class NKError(RuntimeError):
 HOST, DEVICE = 0, 1
 BATCH_ANALYTIC_JAC, BATCH_FLOAT32 = 1, 2   # nk_batch_create / nk_batch_compile_check flags
 GRID_STENCILS = {"star": 0, "box": 1, "star2": 16, "diamond2": 17}               # nk_problem_create_grid / nk_grid_pattern
-GRID_BOUNDARIES = {"dirichlet": 0, "periodic": 1}
+GRID_BOUNDARIES = {"dirichlet": 0, "periodic": 1}                                 # the two uniform boundaries
+GRID_SIDE_KINDS = {"dirichlet": 0, "periodic": 1, "mirror_node": 2, "mirror_face": 3}   # NK_GRID_DIRICHLET0 … NK_GRID_MIRROR_FACE
+GRID_SIDES_BIT = 1 << 24
+
+
+def grid_sides(xlo, xhi, ylo, yhi, zlo=0, zhi=0) -> int:
+    """NK_GRID_SIDES: one kind per side, 4 bits each under the marker bit"""
+    code = GRID_SIDES_BIT
+    for s, k in enumerate((xlo, xhi, ylo, yhi, zlo, zhi)):
+        code |= (int(k) & 15) << (4 * s)
+    return code
 RET_NAMES = ["Default", "Success", "MaxIters", "Unstable", "Stalled", "InternalLinearSolveFailed",
              "ShrinkThresholdExceeded", "MaxTime", "Failure", "InternalLineSearchFailed", "ConvergenceFailure"]
 PROBLEM_QUADRATIC, PROBLEM_BRATU2D, PROBLEM_BRUSSELATOR2D, PROBLEM_USER = 1, 2, 3, 100

@@ -479,19 +479,44 @@ def Brusselator2D(N: int, A=3.4, B=1.0, alpha=10.0, dx=None, ctx=None) -> Device
 
 
 # ------------------------------------------------------------------------------------------- compiled grid problems
-def _grid_ids(stencil, boundary):
+def _grid_boundary(boundary, dim):
+    """the library's boundary code of boundary=: one of the two old strings, a tuple of 2·dim kinds (x-lo, x-hi, y-lo, y-hi[,
+    z-lo, z-hi]) or a dict {"x": kind | (lo, hi), ...} whose missing axes are "dirichlet" """
+    if isinstance(boundary, str):
+        if boundary not in L.GRID_BOUNDARIES:
+            raise ValueError(f"boundary = {boundary!r}: expected one of {sorted(L.GRID_BOUNDARIES)}, a tuple of {2 * dim} kinds "
+                             f"from {sorted(L.GRID_SIDE_KINDS)}, or a dict by axis")
+        return L.GRID_BOUNDARIES[boundary]
+    if isinstance(boundary, dict):
+        axes = "xyz"[:dim]
+        if any(a not in axes for a in boundary):
+            raise ValueError(f"boundary = {boundary!r}: the axes of a {dim}-D grid are {list(axes)}")
+        sides = []
+        for a in axes:
+            k = boundary.get(a, "dirichlet")
+            sides += [k, k] if isinstance(k, str) else list(k)
+    else:
+        sides = list(boundary)
+    if len(sides) != 2 * dim:
+        raise ValueError(f"boundary = {boundary!r}: a {dim}-D grid has {2 * dim} sides (lo and hi of every axis)")
+    for k in sides:
+        if k not in L.GRID_SIDE_KINDS:
+            raise ValueError(f"boundary side {k!r}: expected one of {sorted(L.GRID_SIDE_KINDS)}")
+    return L.grid_sides(*[L.GRID_SIDE_KINDS[k] for k in sides])
+
+
+def _grid_ids(stencil, boundary, dim=2):
     if stencil not in L.GRID_STENCILS:
         raise ValueError(f"stencil = {stencil!r}: expected one of {sorted(L.GRID_STENCILS)}")
-    if boundary not in L.GRID_BOUNDARIES:
-        raise ValueError(f"boundary = {boundary!r}: expected one of {sorted(L.GRID_BOUNDARIES)}")
-    return L.GRID_STENCILS[stencil], L.GRID_BOUNDARIES[boundary]
+    return L.GRID_STENCILS[stencil], _grid_boundary(boundary, dim)
 
 
-def grid_pattern(nx: int, ny: int, dof: int = 1, stencil: str = "star", boundary: str = "dirichlet", *, nz: Optional[int] = None):
+def grid_pattern(nx: int, ny: int, dof: int = 1, stencil: str = "star", boundary="dirichlet", *, nz: Optional[int] = None):
     """(rowptr, colind), int32, of the Jacobian of a compiled grid problem: columns ascending within a row, every
     (stencil point in the domain) × (component) entry kept. Host only. With nz: the nx × ny × nz grid (7-point star or
-    27-point box). stencil = "star2" / "diamond2": the radius-2 stencils of CompiledGridProblem (every side >= 5)."""
-    st, bd = _grid_ids(stencil, boundary)
+    27-point box). stencil = "star2" / "diamond2": the radius-2 stencils of CompiledGridProblem (every side >= 5). boundary: as
+    for CompiledGridProblem; at a mirror side the stencil points of a row that land on one node share one column."""
+    st, bd = _grid_ids(stencil, boundary, 2 if nz is None else 3)
     nnz = C.c_int64()
     if nz is None:
         def pattern(rp, ci):
@@ -506,7 +531,7 @@ def grid_pattern(nx: int, ny: int, dof: int = 1, stencil: str = "star", boundary
     return rowptr, colind
 
 
-def grid_compile_check(source: str, dof: int = 1, stencil: str = "star", boundary: str = "dirichlet", nparams: int = 0, *,
+def grid_compile_check(source: str, dof: int = 1, stencil: str = "star", boundary="dirichlet", nparams: int = 0, *,
                        dim: int = 2, fields: int = 0) -> int:
     """Compile the residual, JVP and Jacobian kernels of `source` for gfx950 (no device needed); the size of the code objects.
     A source that does not compile raises NKError with the contract and the compiler's log. dim = 3: the 3-D contract
@@ -514,7 +539,7 @@ def grid_compile_check(source: str, dof: int = 1, stencil: str = "star", boundar
     contract with the field argument `const nk_flds &a` (3-D: nk_flds3) of CompiledGridProblem(..., fields=)."""
     if dim not in (2, 3):
         raise ValueError(f"dim = {dim!r}: expected 2 or 3")
-    st, bd = _grid_ids(stencil, boundary)
+    st, bd = _grid_ids(stencil, boundary, dim)
     nb = C.c_int64()
     if fields:
         check(L.lib().nk_grid_fields_compile_check(source.encode(), dim, dof, st, bd, nparams, int(fields), C.byref(nb)))
@@ -562,7 +587,7 @@ class _GridDeviceProblem(DeviceProblem):
         return out
 
 
-def CompiledGridProblem(source: str, nx: int, ny: int, dof: int = 1, stencil: str = "star", boundary: str = "dirichlet",
+def CompiledGridProblem(source: str, nx: int, ny: int, dof: int = 1, stencil: str = "star", boundary="dirichlet",
                         params: Sequence[float] = (), ctx=None, *, nz: Optional[int] = None, fields: int = 0) -> DeviceProblem:
     """A residual given pointwise on an nx × ny grid through a radius-1 or radius-2 stencil, as HIP source
         template <typename T> __device__ void nk_point(const nk_nbhd<T> &u, const nk_real *p, nk_site s, T *f);
@@ -588,9 +613,17 @@ def CompiledGridProblem(source: str, nx: int, ny: int, dof: int = 1, stencil: st
     not read costs nothing. Implicit time stepping, F(u) = (u − u_old)/dt − L(u) with u_old = a(0, 0, 0):
         cache = init(NonlinearProblem(P, u0), alg)
         for step in range(nsteps):
-            P.set_field(0, cache.u); reinit_(cache, u0=cache.u); solve_(cache)"""
+            P.set_field(0, cache.u); reinit_(cache, u0=cache.u); solve_(cache)
+    Boundaries: boundary = "dirichlet" or "periodic" for the whole grid, or a kind per side — a tuple of 2·dim strings (x-lo,
+    x-hi, y-lo, y-hi[, z-lo, z-hi]) or a dict {"x": kind | (lo, hi), ...} whose missing axes are "dirichlet" — from
+    "dirichlet" (a ghost reads 0, no column), "periodic" (both sides of the axis), "mirror_node" (the wall is the outermost
+    node: −k ↦ k, NumPy's reflect) and "mirror_face" (the wall is half a cell outside: −k ↦ k−1, NumPy's symmetric — the
+    zero-flux wall of a cell-centred grid). Axes are independent; a point that leaves through a Dirichlet side of any axis
+    reads 0. A mirrored ghost is another unknown: J is the true dF/du, the partials of the stencil points of a row that land
+    on one node are added into one entry, and u, v and the fields are read at the mirrored node. A channel:
+    boundary={"x": "periodic", "y": "mirror_face"}. P.boundary keeps what was passed."""
     ctx = ctx or default_context()
-    st, bd = _grid_ids(stencil, boundary)
+    st, bd = _grid_ids(stencil, boundary, 2 if nz is None else 3)
     params = [float(x) for x in params]
     arr = (C.c_double * max(len(params), 1))(*params)
     h = C.c_void_p()

@@ -24,8 +24,8 @@
 // radius, the smallest side, the dof limits and their messages, the host pattern, and the few lines of device text
 // (grid_stencil_text: NK_NPTS and the offset table nk_pt_off) that every program starts with. The device text proper is two
 // strings, k_grid_types before the user's source and k_grid_kernels after it, the same for every program; what a program is
-// comes from its options alone, and every program gets all of them: -DNK_DIM=2|3, -DNK_NFIELDS=0..4, -DNK_DOF, -DNK_PERIODIC,
-// -DNK_CH, -DNK_GRID_SET (0: residual and JVP, 1: the fill) and -DNK_GRID_DIRECT. The dimension decides one block of
+// comes from its options alone, and every program gets all of them: -DNK_DIM=2|3, -DNK_NFIELDS=0..4, -DNK_DOF, the kinds of the
+// six sides -DNK_XLO … -DNK_ZHI, -DNK_CH, -DNK_GRID_SET (0: residual and JVP, 1: the fill) and -DNK_GRID_DIRECT. The dimension decides one block of
 // k_grid_types (the site, the user-facing names, the arity of operator(), the node → site split and the index geometry) and
 // nothing else; in three dimensions the kernels are nk_grid3_residual / _jvp / _jac over nk_nbhd3<T> / nk_site3 =
 // {i, j, k, nx, ny, nz}, and unknown c of node (i, j, k) is element c·nn + (k·ny + j)·nx + i.
@@ -35,6 +35,12 @@
 // are missing. Each thread counts, for every stencil point, the in-domain points with a smaller node index (npts² integer
 // compares on registers) instead of reading a per-node slot table: the fill is bound by its 8·nnz bytes of stores, and a table
 // would add npts bytes per node to the stream for something 25 (81) compares give.
+//
+// Sides: every side of every axis has a kind of its own (Dirichlet-0, periodic, mirror about the outermost node, mirror about
+// the face half a cell outside it), compile-time constants of the program. A mirrored ghost is another unknown, so several
+// points of a row can land on one node: the pattern keeps that column once, and the fill of a program with a mirror side adds
+// the partials of those points, in ascending point order, into the entry of the first of them (npts² more integer compares on
+// registers; the LDS piece only gets shorter). The programs of the two uniform boundaries do not contain that step.
 //
 // Reading the neighbourhood: u(di, dj[, dk], c) looks its offsets up in nk_pt_off (nk_pt_find, a constexpr search the compiler
 // folds: the offsets are literals in the user's source) and an offset that is no point of the stencil gives NaN, so a wrong
@@ -128,16 +134,68 @@ static std::string grid_dims(int dim, int64_t nx, int64_t ny, int64_t nz) {
   return std::to_string(nx) + " x " + std::to_string(ny) + (dim == 3 ? " x " + std::to_string(nz) : "");
 }
 
+// ----------------------------------------------------------------------------- the boundary code
+// One int everywhere: 0 and 1 are the two uniform boundaries; NK_GRID_SIDES(...) packs one kind per side, 4 bits each, under the
+// marker bit NK_GRID_SIDES_BIT. grid_sides is the canonical form, and the only one anything is keyed on: the kind of side
+// 2·axis + (0: lo, 1: hi). A packed code whose sides are all Dirichlet-0 (all periodic) decodes to what 0 (1) decodes to, so its
+// pattern, its program options, its code objects and its problem are those of the plain code.
+struct grid_sides {
+  int kind[6];   // x-lo, x-hi, y-lo, y-hi, z-lo, z-hi (2-D: the z sides are Dirichlet-0 and never met, every dk is 0)
+};
+static const char *const k_side_names[6] = {"x-lo", "x-hi", "y-lo", "y-hi", "z-lo", "z-hi"};
+static const char *const k_kind_names[4] = {"NK_GRID_DIRICHLET0", "NK_GRID_PERIODIC", "NK_GRID_MIRROR_NODE", "NK_GRID_MIRROR_FACE"};
+
+// the one decode and validate routine of the boundary code
+static int grid_decode_boundary(int dim, int boundary, grid_sides *out) {
+  grid_sides sd = {};
+  if (boundary == NK_GRID_DIRICHLET0 || boundary == NK_GRID_PERIODIC) {
+    for (int s = 0; s < 2 * dim; ++s) sd.kind[s] = boundary;
+  } else {
+    NK_REQUIRE(boundary > 0 && (boundary & NK_GRID_SIDES_BIT) != 0 && (boundary >> 25) == 0,
+               "boundary = %d is neither NK_GRID_DIRICHLET0, NK_GRID_PERIODIC nor a code packed by NK_GRID_SIDES", boundary);
+    for (int s = 0; s < 6; ++s) {
+      const int k = (boundary >> (4 * s)) & 15;
+      if (s >= 2 * dim) {   // (a typo shows: the z fields of a 2-D code are not silently dropped)
+        NK_REQUIRE(k == 0, "boundary side %s = %d: a 2-D grid has no z sides (leave both z kinds 0 in NK_GRID_SIDES)",
+                   k_side_names[s], k);
+        continue;
+      }
+      NK_REQUIRE(k <= NK_GRID_MIRROR_FACE, "boundary side %s = %d is an unknown kind: none of NK_GRID_DIRICHLET0 (0), "
+                 "NK_GRID_PERIODIC (1), NK_GRID_MIRROR_NODE (2), NK_GRID_MIRROR_FACE (3)", k_side_names[s], k);
+      sd.kind[s] = k;
+    }
+  }
+  for (int a = 0; a < dim; ++a) {
+    const int lo = sd.kind[2 * a], hi = sd.kind[2 * a + 1];
+    NK_REQUIRE((lo == NK_GRID_PERIODIC) == (hi == NK_GRID_PERIODIC), "boundary of the %c axis: %s is %s and %s is %s — an axis "
+               "wraps as a whole, both of its sides must be NK_GRID_PERIODIC", "xyz"[a], k_side_names[2 * a], k_kind_names[lo],
+               k_side_names[2 * a + 1], k_kind_names[hi]);
+  }
+  *out = sd;
+  return NK_OK;
+}
+
+// Where index x + (an offset of at most radius) of an axis of n nodes lands: inside, x itself; at most radius outside a side,
+// by that side's kind — wrapped, mirrored about the outermost node (−k ↦ k, n−1+k ↦ n−1−k) or about the face half a cell
+// outside it (−k ↦ k−1, n−1+k ↦ n−k) — or −1 outside a Dirichlet-0 side. One reflection always lands inside the grid: k <=
+// radius and n >= 2·radius + 1 give 0 <= k−1 < k <= radius < n and n−1−k >= n−1−radius >= radius >= 0.
+static inline int64_t grid_side_map(int64_t x, int64_t n, int lo, int hi) {
+  if (x < 0) return lo == NK_GRID_PERIODIC ? x + n : (lo == NK_GRID_MIRROR_NODE ? -x : (lo == NK_GRID_MIRROR_FACE ? -x - 1 : -1));
+  if (x >= n)
+    return hi == NK_GRID_PERIODIC ? x - n
+                                  : (hi == NK_GRID_MIRROR_NODE ? 2 * (n - 1) - x : (hi == NK_GRID_MIRROR_FACE ? 2 * n - 1 - x : -1));
+  return x;
+}
+
 // what the table refuses: a stencil the dimension does not offer, a boundary that is none, a dof beyond the stencil's largest
-static int grid_check_shape(int dim, int dof, int stencil, int boundary, const grid_stencil **out) {
+static int grid_check_shape(int dim, int dof, int stencil, int boundary, const grid_stencil **out, grid_sides *sides) {
   const grid_stencil *st = grid_find(dim, stencil);
   if (!st) {
     const std::string elsewhere = grid_stencil_names(0, stencil), offered = grid_stencil_names(dim);
     NK_FAIL(NK_E_INVALID, "stencil = %d%s%s%s is none of %s, the stencils offered in %d dimensions", stencil,
             elsewhere.empty() ? "" : " (", elsewhere.c_str(), elsewhere.empty() ? "" : ")", offered.c_str(), dim);
   }
-  NK_REQUIRE(boundary == NK_GRID_DIRICHLET0 || boundary == NK_GRID_PERIODIC,
-             "boundary = %d is neither NK_GRID_DIRICHLET0 nor NK_GRID_PERIODIC", boundary);
+  NK_TRY(grid_decode_boundary(dim, boundary, sides));
   NK_REQUIRE(dof >= 1 && dof <= 4, "dof = %d outside 1..4 (components per grid node)", dof);
   int most = 0;   // partials per row the dimension's programs are built for
   for (const grid_stencil &s : k_grid_stencils)
@@ -164,15 +222,13 @@ static int grid_check_size(const grid_stencil &st, int64_t nx, int64_t ny, int64
 }
 
 // ----------------------------------------------------------------------------- the stencil's CSR pattern (host only)
-// periodic wrap of an index at most n outside [0, n)
-static inline int64_t grid_wrap(int64_t ii, int64_t n) { return ii < 0 ? ii + n : (ii >= n ? ii - n : ii); }
-
 // dim = 2: nz is 1 and every dk is 0
 static int grid_pattern(int dim, int64_t nx, int64_t ny, int64_t nz, int dof, int stencil, int boundary, int32_t *rowptr,
                         int32_t *colind, int64_t *nnz) {
   NK_REQUIRE(rowptr || nnz, "NULL argument");
   const grid_stencil *st = nullptr;
-  NK_TRY(grid_check_shape(dim, dof, stencil, boundary, &st));
+  grid_sides sd;
+  NK_TRY(grid_check_shape(dim, dof, stencil, boundary, &st, &sd));
   NK_TRY(grid_check_size(*st, nx, ny, nz, dof));
   const int64_t nn = nx * ny * nz;
   int64_t pos = 0;
@@ -183,18 +239,18 @@ static int grid_pattern(int dim, int64_t nx, int64_t ny, int64_t nz, int dof, in
           int64_t nb[27];
           int cnt = 0;
           for (int q = 0; q < st->npts; ++q) {
-            int64_t ii = i + st->off[q][0], jj = j + st->off[q][1], kk = k + st->off[q][2];
-            if (boundary == NK_GRID_PERIODIC) {
-              ii = grid_wrap(ii, nx);
-              jj = grid_wrap(jj, ny);
-              kk = grid_wrap(kk, nz);
-            } else if (ii < 0 || ii >= nx || jj < 0 || jj >= ny || kk < 0 || kk >= nz) {
-              continue;
-            }
-            // insertion keeps the node indices ascending (wrap-around reorders the points at a periodic edge)
+            // every axis by the kinds of its two sides; a point that leaves through a Dirichlet-0 side of any axis has no column
+            const int64_t ii = grid_side_map(i + st->off[q][0], nx, sd.kind[0], sd.kind[1]);
+            const int64_t jj = grid_side_map(j + st->off[q][1], ny, sd.kind[2], sd.kind[3]);
+            const int64_t kk = grid_side_map(k + st->off[q][2], nz, sd.kind[4], sd.kind[5]);
+            if (ii < 0 || jj < 0 || kk < 0) continue;
+            // insertion keeps the node indices ascending (wrap-around and mirrors reorder the points at an edge) and a column
+            // once: at a mirror several points of a row land on one node
             const int64_t m = (kk * ny + jj) * nx + ii;
-            int t = cnt++;
-            while (t > 0 && nb[t - 1] > m) { nb[t] = nb[t - 1]; --t; }
+            int t = cnt;
+            while (t > 0 && nb[t - 1] > m) --t;
+            if (t > 0 && nb[t - 1] == m) continue;
+            for (int e = cnt++; e > t; --e) nb[e] = nb[e - 1];
             nb[t] = m;
           }
           if (rowptr) rowptr[c * nn + (k * ny + j) * nx + i] = (int32_t)pos;
@@ -234,9 +290,39 @@ static std::string grid_stencil_text(const grid_stencil &st) {
 static const char *k_grid_types = R"NKSRC(
 // ---- compiled grid problems: the node's position and its neighbourhood
 #define NK_GRID_BLOCK 256
+// the kinds of a side (the header's NK_GRID_DIRICHLET0 … NK_GRID_MIRROR_FACE); NK_XLO … NK_ZHI are the program's six
+enum { NK_BC_DIRICHLET0 = 0, NK_BC_PERIODIC = 1, NK_BC_MIRROR_NODE = 2, NK_BC_MIRROR_FACE = 3 };
+#define NK_BC_IS_MIRROR(k) ((k) == 2 || (k) == 3)
+// a mirror side lets several stencil points of a row land on one node: only then does the fill merge partials
+#define NK_ANY_MIRROR                                                                                           \
+  (NK_BC_IS_MIRROR(NK_XLO) || NK_BC_IS_MIRROR(NK_XHI) || NK_BC_IS_MIRROR(NK_YLO) || NK_BC_IS_MIRROR(NK_YHI) || \
+   (NK_DIM == 3 && (NK_BC_IS_MIRROR(NK_ZLO) || NK_BC_IS_MIRROR(NK_ZHI))))
+// Index x (a node's own plus an offset of at most the radius) of an axis of n nodes, by the kinds of the axis's two sides.
+// NK_GRID_INSIDE: false only where x is outside a Dirichlet-0 side (the test of a side of another kind is a constant the
+// front end drops; no outer parentheses: with the tests of the other axes it makes one && chain, the expression the programs of
+// the two uniform boundaries have always had, and they compile to the instructions they always did). nk_grid_land: x wrapped,
+// mirrored about the outermost node (−k -> k, n−1+k -> n−1−k) or about the face half a cell outside it (−k -> k−1, n−1+k -> n−k);
+// a Dirichlet-0 side leaves x as it is and the caller clamps to the node. n >= 2·radius + 1, so one reflection lands inside:
+// 0 <= k−1 < k <= radius < n and n−1−k >= radius.
+#define NK_GRID_INSIDE(LO, HI, x, n) ((LO) != NK_BC_DIRICHLET0 || (x) >= 0) && ((HI) != NK_BC_DIRICHLET0 || (x) < (n))
+template <int KIND>
+__device__ __forceinline__ int nk_grid_below(int x, int n) {   // x < 0
+  return KIND == NK_BC_PERIODIC ? x + n : (KIND == NK_BC_MIRROR_NODE ? -x : -x - 1);
+}
+template <int KIND>
+__device__ __forceinline__ int nk_grid_above(int x, int n) {   // x >= n
+  return KIND == NK_BC_PERIODIC ? x - n : (KIND == NK_BC_MIRROR_NODE ? 2 * (n - 1) - x : 2 * n - 1 - x);
+}
+template <int LO, int HI>
+__device__ __forceinline__ int nk_grid_land(int x, int n) {
+  if constexpr (LO == NK_BC_DIRICHLET0 && HI == NK_BC_DIRICHLET0) return x;
+  else if constexpr (HI == NK_BC_DIRICHLET0) return x < 0 ? nk_grid_below<LO>(x, n) : x;
+  else if constexpr (LO == NK_BC_DIRICHLET0) return x >= n ? nk_grid_above<HI>(x, n) : x;
+  else return x < 0 ? nk_grid_below<LO>(x, n) : (x >= n ? nk_grid_above<HI>(x, n) : x);
+}
 // everything the dimension decides: the site, the names the user's source sees, the arity of operator(), the sizes a kernel
-// takes, node -> site, and the node index of every stencil point (clamped to the node itself outside a Dirichlet boundary,
-// wrapped at a periodic one) with whether the point is in the domain
+// takes, node -> site, and the node index of every stencil point (clamped to the node itself outside a Dirichlet-0 side of any
+// axis, otherwise wrapped or mirrored axis by axis) with whether the point is in the domain
 #if NK_DIM == 3
 struct nk_site3 { int i, j, k, nx, ny, nz; };
 #define NK_SITE nk_site3
@@ -258,17 +344,14 @@ __device__ __forceinline__ void nk_grid_geom(const nk_site3 s, int (&idx)[NK_NPT
 #pragma unroll
   for (int q = 0; q < NK_NPTS; ++q) {
     int ii = s.i + nk_pt_off[q][0], jj = s.j + nk_pt_off[q][1], kk = s.k + nk_pt_off[q][2];
-#if NK_PERIODIC
-    ii = ii < 0 ? ii + s.nx : (ii >= s.nx ? ii - s.nx : ii);
-    jj = jj < 0 ? jj + s.ny : (jj >= s.ny ? jj - s.ny : jj);
-    kk = kk < 0 ? kk + s.nz : (kk >= s.nz ? kk - s.nz : kk);
-    in[q] = true;
-#else
-    in[q] = ii >= 0 && ii < s.nx && jj >= 0 && jj < s.ny && kk >= 0 && kk < s.nz;
+    in[q] = NK_GRID_INSIDE(NK_XLO, NK_XHI, ii, s.nx) && NK_GRID_INSIDE(NK_YLO, NK_YHI, jj, s.ny) &&
+            NK_GRID_INSIDE(NK_ZLO, NK_ZHI, kk, s.nz);
+    ii = nk_grid_land<NK_XLO, NK_XHI>(ii, s.nx);
+    jj = nk_grid_land<NK_YLO, NK_YHI>(jj, s.ny);
+    kk = nk_grid_land<NK_ZLO, NK_ZHI>(kk, s.nz);
     ii = in[q] ? ii : s.i;
     jj = in[q] ? jj : s.j;
     kk = in[q] ? kk : s.k;
-#endif
     idx[q] = (kk * s.ny + jj) * s.nx + ii;
   }
 }
@@ -292,15 +375,11 @@ __device__ __forceinline__ void nk_grid_geom(const nk_site s, int (&idx)[NK_NPTS
 #pragma unroll
   for (int q = 0; q < NK_NPTS; ++q) {
     int ii = s.i + nk_pt_off[q][0], jj = s.j + nk_pt_off[q][1];
-#if NK_PERIODIC
-    ii = ii < 0 ? ii + s.nx : (ii >= s.nx ? ii - s.nx : ii);
-    jj = jj < 0 ? jj + s.ny : (jj >= s.ny ? jj - s.ny : jj);
-    in[q] = true;
-#else
-    in[q] = ii >= 0 && ii < s.nx && jj >= 0 && jj < s.ny;
+    in[q] = NK_GRID_INSIDE(NK_XLO, NK_XHI, ii, s.nx) && NK_GRID_INSIDE(NK_YLO, NK_YHI, jj, s.ny);
+    ii = nk_grid_land<NK_XLO, NK_XHI>(ii, s.nx);
+    jj = nk_grid_land<NK_YLO, NK_YHI>(jj, s.ny);
     ii = in[q] ? ii : s.i;
     jj = in[q] ? jj : s.j;
-#endif
     idx[q] = jj * s.nx + ii;
   }
 }
@@ -458,6 +537,42 @@ NK_KERNEL(jac)(NK_SIZES, const nk_real *__restrict__ p, NK_FLDS_PARAM const nk_r
   for (int c = 0; c < NK_DOF; ++c) out[c] = Dual(NK_R(0));
   nk_point<Dual>(nb, NK_FLDS_ARG p, s, out);
   int rank[NK_NPTS], cnt = 0;
+#if NK_ANY_MIRROR
+  // Several points of a row may land on one node. The first of them (smallest q) is the primary: it alone has a column, and its
+  // value is the sum of the partials of all of them, added in ascending q. cnt and rank count primaries only
+  bool prim[NK_NPTS];
+#pragma unroll
+  for (int q = 0; q < NK_NPTS; ++q) {
+    bool first = in[q];
+#pragma unroll
+    for (int t = 0; t < q; ++t) first = first && !(in[t] && idx[t] == idx[q]);
+    prim[q] = first;
+  }
+#pragma unroll
+  for (int q = 0; q < NK_NPTS; ++q) {
+    int r = 0;
+#pragma unroll
+    for (int t = 0; t < NK_NPTS; ++t) r += (prim[t] && idx[t] < idx[q]) ? 1 : 0;
+    rank[q] = r;
+    cnt += prim[q] ? 1 : 0;
+  }
+#pragma unroll
+  for (int q = 0; q < NK_NPTS; ++q) {
+#pragma unroll
+    for (int t = q + 1; t < NK_NPTS; ++t) {
+      const bool same = in[t] && idx[t] == idx[q];   // (only a primary's sum is stored; another q's is dropped with it)
+#pragma unroll
+      for (int c = 0; c < NK_DOF; ++c) {
+#pragma unroll
+        for (int c2 = 0; c2 < NK_DOF; ++c2) {
+          const nk_real x = out[c].d[q * NK_DOF + c2];
+          out[c].d[q * NK_DOF + c2] = same ? x + out[c].d[t * NK_DOF + c2] : x;
+        }
+      }
+    }
+  }
+#define NK_FILL_KEEP(q) prim[q]
+#else
 #pragma unroll
   for (int q = 0; q < NK_NPTS; ++q) {
     int r = 0;
@@ -466,13 +581,15 @@ NK_KERNEL(jac)(NK_SIZES, const nk_real *__restrict__ p, NK_FLDS_PARAM const nk_r
     rank[q] = r;
     cnt += in[q] ? 1 : 0;
   }
+#define NK_FILL_KEEP(q) in[q]
+#endif
 #pragma unroll
   for (int c = 0; c < NK_DOF; ++c) {
     const int base = rowptr[c * nn + node];
 #if NK_GRID_DIRECT
 #pragma unroll
     for (int q = 0; q < NK_NPTS; ++q) {
-      if (in[q]) {
+      if (NK_FILL_KEEP(q)) {
 #pragma unroll
         for (int c2 = 0; c2 < NK_DOF; ++c2) vals[base + c2 * cnt + rank[q]] = out[c].d[q * NK_DOF + c2];
       }
@@ -484,7 +601,7 @@ NK_KERNEL(jac)(NK_SIZES, const nk_real *__restrict__ p, NK_FLDS_PARAM const nk_r
     if (live) {
 #pragma unroll
       for (int q = 0; q < NK_NPTS; ++q) {
-        if (in[q]) {
+        if (NK_FILL_KEEP(q)) {
 #pragma unroll
           for (int c2 = 0; c2 < NK_DOF; ++c2) sv[base - p0 + c2 * cnt + rank[q]] = out[c].d[q * NK_DOF + c2];
         }
@@ -520,7 +637,8 @@ static int grid_compile(const char *source, int dim, int dof, int stencil, int b
                         std::vector<char> *code, std::string *log) {
   NK_REQUIRE(source, "NULL source");
   const grid_stencil *st = nullptr;
-  NK_TRY(grid_check_shape(dim, dof, stencil, boundary, &st));
+  grid_sides sd;
+  NK_TRY(grid_check_shape(dim, dof, stencil, boundary, &st, &sd));
   NK_REQUIRE(np >= 0 && np <= 32, "nparams = %d outside 0..32", np);
   NK_REQUIRE(nf >= 0 && nf <= 4, "nfields = %d outside 0..4 (read-only fields of one double per node)", nf);
   const std::string stencil_text = grid_stencil_text(*st);
@@ -528,7 +646,9 @@ static int grid_compile(const char *source, int dim, int dof, int stencil, int b
                            source + "\n" + k_grid_kernels;
   const std::string defs[] = {"-DNK_DIM=" + std::to_string(dim), "-DNK_NFIELDS=" + std::to_string(nf),
                               "-DNK_DOF=" + std::to_string(dof),
-                              std::string("-DNK_PERIODIC=") + (boundary == NK_GRID_PERIODIC ? "1" : "0"),
+                              "-DNK_XLO=" + std::to_string(sd.kind[0]), "-DNK_XHI=" + std::to_string(sd.kind[1]),
+                              "-DNK_YLO=" + std::to_string(sd.kind[2]), "-DNK_YHI=" + std::to_string(sd.kind[3]),
+                              "-DNK_ZLO=" + std::to_string(sd.kind[4]), "-DNK_ZHI=" + std::to_string(sd.kind[5]),
                               "-DNK_CH=" + std::to_string(gset == GSET_JAC ? st->npts * dof : 1),
                               "-DNK_GRID_SET=" + std::to_string(gset), std::string("-DNK_GRID_DIRECT=") + (direct ? "1" : "0")};
   std::vector<const char *> opts = {"--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-std=c++17"};

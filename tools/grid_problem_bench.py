@@ -35,6 +35,15 @@ field read (dof = 1). Expected, and nothing is tuned to it: (b)/(a) near the byt
 the p10–p90 spread of (b) since the extra reads are cache hits, (d) indistinguishable from (b).
 
     python tools/grid_problem_bench.py --fields [--out profiles/gridf_problem_bench.txt] [--grid 1024] [--grid2 4096]
+
+`--sides` measures what a boundary kind per side costs (NK_GRID_SIDES), at `--grid`² (1024²): the Bratu source with (a) the
+Dirichlet-0 boundary as the yardstick, (b) mirror-node on all four sides, (c) x periodic and y mirror-face — same process, same
+protocol, the problems alternating, the fill in both forms. Expected, and nothing is tuned to it: residual and JVP move the
+bytes of (a) and cost the same; the fill of (b) and (c) stores slightly fewer or more values than (a) (a mirrored ghost is a
+column where the Dirichlet ghost is none, unless it lands on a column the row already has) and adds the merge's integer
+compares. The ratios to (a) are printed.
+
+    python tools/grid_problem_bench.py --sides [--out profiles/grid_sides_bench.txt] [--grid 1024]
 """
 import argparse
 import os
@@ -133,10 +142,24 @@ def main_fields(args):
     generated_kernels(args, "Compiled grid problems with read-only fields beside the same problem without", cases, direct=False)
 
 
-def generated_kernels(args, title, cases, direct=True):
+def main_sides(args):
+    """what a kind per side costs: Dirichlet-0, mirror-node all round, x periodic with y mirror-face"""
+    g = args.grid
+    par = R.bratu_params(g, 6.0)
+    cases = [(f"(a) bratu {g}^2, Dirichlet-0", R.BRATU_SRC, (g, g, None), "star", par),
+             (f"(b) bratu {g}^2, mirror-node all round", R.BRATU_SRC, (g, g, None), "star", par),
+             (f"(c) bratu {g}^2, x periodic, y mirror-face", R.BRATU_SRC, (g, g, None), "star", par)]
+    boundaries = {cases[0][0]: "dirichlet", cases[1][0]: ("mirror_node",) * 4,
+                  cases[2][0]: {"x": "periodic", "y": "mirror_face"}}
+    generated_kernels(args, "Compiled grid problems with a boundary kind per side beside the Dirichlet-0 form", cases,
+                      boundaries=boundaries)
+
+
+def generated_kernels(args, title, cases, direct=True, boundaries=None):
     """the three generated kernels of every case, the fill in both forms (direct = False: the default form only), ordered by
     kernel so that the cases alternate. A case may end with (fields declared, fields read): the fields hold seeded positive
-    data, and every kernel's algorithmic bytes grow by 8 n per field read."""
+    data, and every kernel's algorithmic bytes grow by 8 n per field read. boundaries: label → boundary= of the case (the
+    default: "dirichlet"); with it the time ratios of the cases (b), (c) to (a) are printed."""
     ctx = nls.default_context()
     gen = torch.Generator(device="cuda").manual_seed(1)
     calls, meta, problems, sizes = {}, {}, [], []   # meta: label → (kind rank, algorithmic bytes, unknowns)
@@ -144,7 +167,8 @@ def generated_kernels(args, title, cases, direct=True):
         nf, nread = fld if fld else (0, 0)
 
         def create():
-            P = nls.CompiledGridProblem(src, nx, ny, stencil=stencil, params=par, nz=nz, fields=nf)
+            P = nls.CompiledGridProblem(src, nx, ny, stencil=stencil, params=par, nz=nz, fields=nf,
+                                        boundary=(boundaries or {}).get(label, "dirichlet"))
             for k in range(nf):
                 P.set_field(k, 0.5 + torch.rand(P.nn, dtype=torch.float64, device="cuda", generator=gen))
             return P
@@ -200,6 +224,16 @@ def generated_kernels(args, title, cases, direct=True):
                 m = {c[0][:3]: med[f"{what:24s} {c[0]}"] for c in cases if c[2][0] == size}
                 lines.append(f"  {what:24s} {size}^2: (b)/(a) {m['(b)'] / m['(a)']:.3f}   (c)/(b) {m['(c)'] / m['(b)']:.3f}   "
                              f"(d)/(b) {m['(d)'] / m['(b)']:.3f}")
+    if boundaries:   # the sides protocol: time ratios of (b) and (c) to the Dirichlet-0 form (a), with (a)'s own spread
+        lines += ["", "time ratios of the medians to (a), and (a)'s own spread (p90 - p10) / median (expected: residual and JVP near 1; "
+                  "the fill near its byte ratio)"]
+        med = {k: statistics.median(ts[k]) for k in order}
+        for what in ("residual", "JVP", "fill (LDS-staged rows)", "fill (direct stores)"):
+            m = {c[0][:3]: f"{what:24s} {c[0]}" for c in cases}
+            ta = ts[m["(a)"]]
+            lines.append(f"  {what:24s} (b)/(a) {med[m['(b)']] / med[m['(a)']]:.3f}   (c)/(a) {med[m['(c)']] / med[m['(a)']]:.3f}   "
+                         f"spread of (a) {(ta[(9 * len(ta)) // 10] - ta[len(ta) // 10]) / med[m['(a)']]:.3f}   "
+                         f"bytes (b)/(a) {meta[m['(b)']][1] / meta[m['(a)']][1]:.3f}   (c)/(a) {meta[m['(c)']][1] / meta[m['(a)']][1]:.3f}")
     text = "\n".join(lines) + "\n"
     print(text)
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
@@ -215,6 +249,7 @@ def main():
     ap.add_argument("--dim", type=int, default=2, choices=(2, 3))
     ap.add_argument("--radius", type=int, default=1, choices=(1, 2))
     ap.add_argument("--fields", action="store_true")
+    ap.add_argument("--sides", action="store_true")
     ap.add_argument("--grid3", type=int, default=256)
     ap.add_argument("--box3", type=int, default=160)
     ap.add_argument("--grid2", type=int, default=4096)
@@ -225,8 +260,10 @@ def main():
     args = ap.parse_args()
     if args.out is None:
         name = "grid_r2_problem_bench.txt" if args.radius == 2 else ("grid3_problem_bench.txt" if args.dim == 3 else "grid_problem_bench.txt")
-        name = "gridf_problem_bench.txt" if args.fields else name
+        name = "gridf_problem_bench.txt" if args.fields else ("grid_sides_bench.txt" if args.sides else name)
         args.out = os.path.join(ROOT, "profiles", name)
+    if args.sides:
+        return main_sides(args)
     if args.fields:
         return main_fields(args)
     if args.radius == 2:
