@@ -1035,8 +1035,6 @@ extern "C" int nk_batch_create(nk_ctx *ctx, const char *source, int n, int npara
         hipModuleLoadData(&B->mod_wave, wcode.data()) == hipSuccess) {
       if (hipModuleGetFunction(&B->fn_wave, B->mod_wave, "nk_batch_newton_wave") != hipSuccess) B->fn_wave = nullptr;
     }
-    static const bool no_wave = getenv("NK_BATCH_NO_WAVE") != nullptr;  // A/B switch
-    if (no_wave) B->fn_wave = nullptr;
   }
   *out = B;
   return NK_OK;

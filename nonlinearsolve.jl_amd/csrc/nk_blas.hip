@@ -464,13 +464,12 @@ int nk_blas_dcgs2_pass_a(nk_ctx *ctx, int64_t n, int k, double *V, int64_t ldv, 
 }
 
 // ----------------------------------------------------------------------------- DCGS2 with one reduction per step
-// dot sweep: NV final columns, pending p = V[:,NV], z = V[:,NV+1] (absent when !WITHZ: the flush of a cycle).
+// dot sweep: NV final columns, pending p = V[:,NV], z = V[:,NV+1].
 // slots: [0,NV) ṽ_j·p | NV: p·p | [NV+1, 2NV+1) ṽ_j·z | 2NV+1: p·z
 // Every workgroup owns a contiguous tile of DR·256 rows: its slice of p (and z) stays in registers while the final
 // columns stream past eight at a time — 16 accumulators instead of 2·NV+2, so the kernel keeps its occupancy at any NV
 // (a first version with all accumulators live ran at 3.0 TB/s). nv is a run-time argument.
 constexpr int DR = 8;  // rows per thread
-template <bool WITHZ>
 __global__ __launch_bounds__(NK_BLOCK) void k_dcgs2r_dots(int64_t n, int nv, const double *__restrict__ V, int64_t ldv,
                                                           double *__restrict__ partials, const int *d_skip) {
   SKIP_GUARD(d_skip);
@@ -492,7 +491,7 @@ __global__ __launch_bounds__(NK_BLOCK) void k_dcgs2r_dots(int64_t n, int nv, con
 #pragma unroll
   for (int i = 0; i < DR; ++i) {
     pv[i] = pk[idx[i]] * msk[i];
-    zv[i] = WITHZ ? zk[idx[i]] * msk[i] : 0.0;
+    zv[i] = zk[idx[i]] * msk[i];
     aa += pv[i] * pv[i];
     dd += pv[i] * zv[i];
   }
@@ -511,20 +510,18 @@ __global__ __launch_bounds__(NK_BLOCK) void k_dcgs2r_dots(int64_t n, int nv, con
 #pragma unroll
       for (int i = 0; i < DR; ++i) {
         acc[2 * jj] += vj[i] * pv[i];
-        if (WITHZ) acc[2 * jj + 1] += vj[i] * zv[i];
+        acc[2 * jj + 1] += vj[i] * zv[i];
       }
     }
 #pragma unroll
     for (int q = 0; q < 2 * CH; ++q) {
-      if (WITHZ || (q & 1) == 0) {
-        const double v = wave_sum(acc[q]);
-        if (lane == 0) sm[wid * 2 * CH + q] = v;
-      }
+      const double v = wave_sum(acc[q]);
+      if (lane == 0) sm[wid * 2 * CH + q] = v;
     }
     __syncthreads();
     if (threadIdx.x < 2 * CH) {
       const int q = threadIdx.x, j = c0 + (q >> 1);
-      if (j < nv && (WITHZ || (q & 1) == 0)) {
+      if (j < nv) {
         const double v = (sm[q] + sm[2 * CH + q]) + (sm[4 * CH + q] + sm[6 * CH + q]);
         const int slot = (q & 1) ? zoff + j : j;
         partials[(size_t)slot * gridDim.x + blockIdx.x] = v;
@@ -538,74 +535,8 @@ __global__ __launch_bounds__(NK_BLOCK) void k_dcgs2r_dots(int64_t n, int nv, con
     __syncthreads();
     if (threadIdx.x == 0) {
       partials[(size_t)nv * gridDim.x + blockIdx.x] = (sm[0] + sm[1]) + (sm[2] + sm[3]);
-      if (WITHZ) partials[(size_t)(2 * nv + 1) * gridDim.x + blockIdx.x] = (sm[4] + sm[5]) + (sm[6] + sm[7]);
+      partials[(size_t)(2 * nv + 1) * gridDim.x + blockIdx.x] = (sm[4] + sm[5]) + (sm[6] + sm[7]);
     }
-  }
-}
-
-// axpy sweep: p ← p − Σ a_j ṽ_j ; z ← b_{nv+1}·z − Σ b_j ṽ_j − b_nv·p (no reduction). Same shape as the dot sweep: the
-// workgroup's row tile of p and z lives in registers, the final columns stream past two at a time.
-// ss_partials (last step of a cycle only): per-tile ‖z_new‖² — the norm that closes the cycle's last Hessenberg column.
-__global__ __launch_bounds__(NK_BLOCK) void k_dcgs2r_axpy(int64_t n, int nv, double *__restrict__ V, int64_t ldv,
-                                                          const double *__restrict__ ca_g, const double *__restrict__ cb_g,
-                                                          const int *d_skip, double *__restrict__ ss_partials) {
-  SKIP_GUARD(d_skip);
-  __shared__ double ca[NK_MAX_NV + 2], cb[NK_MAX_NV + 2];
-  __shared__ double s_bk, s_sz, s_w[4];
-  if ((int)threadIdx.x <= nv) {  // one zero entry past the end pads an odd column count
-    ca[threadIdx.x] = ((int)threadIdx.x < nv) ? ca_g[threadIdx.x] : 0.0;
-    cb[threadIdx.x] = ((int)threadIdx.x < nv) ? cb_g[threadIdx.x] : 0.0;
-  }
-  if (threadIdx.x == 0) { s_bk = cb_g[nv]; s_sz = cb_g[nv + 1]; }
-  __syncthreads();
-  double *__restrict__ pk = V + (size_t)nv * ldv;
-  double *__restrict__ zk = V + (size_t)(nv + 1) * ldv;
-  const unsigned nn = (unsigned)n, base = blockIdx.x * (NK_BLOCK * DR) + threadIdx.x;
-  unsigned idx[DR];
-  double pv[DR], zv[DR];
-  const double sz = s_sz, bk = s_bk;
-#pragma unroll
-  for (int i = 0; i < DR; ++i) {
-    const unsigned r = base + NK_BLOCK * i;
-    idx[i] = r < nn ? r : 0;
-  }
-#pragma unroll
-  for (int i = 0; i < DR; ++i) {
-    pv[i] = pk[idx[i]];
-    zv[i] = sz * zk[idx[i]];
-  }
-  for (int j = 0; j < nv; j += 2) {
-    const int j1 = min(j + 1, nv - 1);
-    const double *__restrict__ c0 = V + (size_t)j * ldv;
-    const double *__restrict__ c1 = V + (size_t)j1 * ldv;
-    const double a0 = ca[j], a1 = ca[j + 1], b0 = cb[j], b1 = cb[j + 1];
-    double v0[DR], v1[DR];
-#pragma unroll
-    for (int i = 0; i < DR; ++i) { v0[i] = c0[idx[i]]; v1[i] = c1[idx[i]]; }
-#pragma unroll
-    for (int i = 0; i < DR; ++i) {
-      pv[i] -= a0 * v0[i];
-      pv[i] -= a1 * v1[i];
-      zv[i] -= b0 * v0[i];
-      zv[i] -= b1 * v1[i];
-    }
-  }
-  double ss = 0.0;
-#pragma unroll
-  for (int i = 0; i < DR; ++i) {
-    const unsigned r = base + NK_BLOCK * i;
-    if (r < nn) {
-      if (nv > 0) pk[r] = pv[i];
-      const double zn = zv[i] - bk * pv[i];
-      zk[r] = zn;
-      ss += zn * zn;
-    }
-  }
-  if (ss_partials != nullptr) {  // uniform
-    ss = wave_sum(ss);
-    if ((threadIdx.x & 63) == 0) s_w[threadIdx.x >> 6] = ss;
-    __syncthreads();
-    if (threadIdx.x == 0) ss_partials[blockIdx.x] = (s_w[0] + s_w[1]) + (s_w[2] + s_w[3]);
   }
 }
 
@@ -621,7 +552,7 @@ __global__ __launch_bounds__(NK_BLOCK) void k_dcgs2r_axpy(int64_t n, int nv, dou
     case 28: F(28); break; case 29: F(29); break; case 30: F(30); break; default: F(31); break;                \
   }
 
-int nk_blas_dcgs2r_dots(nk_ctx *ctx, int64_t n, int k, bool flush, const double *V, int64_t ldv, double *d_red,
+int nk_blas_dcgs2r_dots(nk_ctx *ctx, int64_t n, int k, const double *V, int64_t ldv, double *d_red,
                         const int *d_skip) {
   NK_REQUIRE(k >= 0 && k <= NK_MAX_NV - 2, "DCGS2-1R handles 0..%d final columns (got %d)", NK_MAX_NV - 2, k);
   NK_REQUIRE(n < (1ll << 31), "fused pass: local vector too long for 32-bit offsets");
@@ -630,11 +561,10 @@ int nk_blas_dcgs2r_dots(nk_ctx *ctx, int64_t n, int k, bool flush, const double 
   NK_REQUIRE(g64 <= NK_MAX_ROW_TILES, "DCGS2-1R: %lld local rows exceed %d row tiles of %lld (use NK_ORTHO_DCGS2)",
              (long long)n, NK_MAX_ROW_TILES, (long long)tile);
   const int grid = g64 > 0 ? (int)g64 : 1;
-  const int nslots = flush ? k + 1 : 2 * k + 2;
+  const int nslots = 2 * k + 2;
   {
-    nk_prof_scope prof_(ctx, NK_K_MULTIDOT, 8.0 * (double)n * (k + (flush ? 1 : 2)));
-    if (flush) NK_LAUNCH(ctx, k_dcgs2r_dots<false>, dim3(grid), dim3(NK_BLOCK), n, k, V, ldv, ctx->d_partials, d_skip);
-    else NK_LAUNCH(ctx, k_dcgs2r_dots<true>, dim3(grid), dim3(NK_BLOCK), n, k, V, ldv, ctx->d_partials, d_skip);
+    nk_prof_scope prof_(ctx, NK_K_MULTIDOT, 8.0 * (double)n * (k + 2));
+    NK_LAUNCH(ctx, k_dcgs2r_dots, dim3(grid), dim3(NK_BLOCK), n, k, V, ldv, ctx->d_partials, d_skip);
   }
   const nk_peer_ar_view pv = nk_peer_ar_next(ctx, nslots);
   {
@@ -645,25 +575,6 @@ int nk_blas_dcgs2r_dots(nk_ctx *ctx, int64_t n, int k, bool flush, const double 
   }
   NK_HIP(hipGetLastError());
   return pv.seq ? NK_OK : nk_comm_allreduce(ctx, d_red, nslots, 0);
-}
-
-// d_ss_out != nullptr: also ‖z_new‖² (all-reduced) into *d_ss_out — the cycle's last step
-int nk_blas_dcgs2r_axpy(nk_ctx *ctx, int64_t n, int k, double *V, int64_t ldv, const double *d_a, const double *d_b,
-                        const int *d_skip, double *d_ss_out) {
-  NK_REQUIRE(k >= 0 && k <= NK_MAX_NV - 2, "DCGS2-1R handles 0..%d final columns (got %d)", NK_MAX_NV - 2, k);
-  const int64_t tile = (int64_t)NK_BLOCK * DR;
-  const int grid = (int)std::max<int64_t>(1, (n + tile - 1) / tile);
-  nk_prof_scope prof_(ctx, NK_K_MULTIAXPY, 8.0 * (double)n * (k + 4));
-  NK_LAUNCH(ctx, k_dcgs2r_axpy, dim3(grid), dim3(NK_BLOCK), n, k, V, ldv, d_a, d_b, d_skip,
-            d_ss_out ? ctx->d_partials : (double *)nullptr);
-  NK_HIP(hipGetLastError());
-  if (d_ss_out) {
-    NK_LAUNCH(ctx, k_reduce_sum, dim3(1), dim3(NK_BLOCK), ctx->d_partials, grid, d_ss_out, d_skip,
-              (const double *)nullptr, 0);
-    NK_HIP(hipGetLastError());
-    return nk_comm_allreduce(ctx, d_ss_out, 1, 0);
-  }
-  return NK_OK;
 }
 
 // *d_out = Σ partials[0..nblk) in the fixed stage-2 order, all-reduced
@@ -881,10 +792,8 @@ int nk_blas_norms_inf2_to_host(nk_ctx *ctx, int64_t n, const double *x, double *
                                double *h_out, const std::function<int()> &before_wait, int have_partials,
                                const std::function<int(const nk_fold_norms &, bool *)> &fold_into) {
   const int count = extra_partials ? 3 : 2;
-  static const bool legacy = getenv("NK_FETCH_MEMCPY") != nullptr || getenv("NK_NORMS_SEPARATE_PUBLISH") != nullptr;
-  if (!nk_ctx_is_single(ctx) || legacy) {
+  if (!nk_ctx_is_single(ctx)) {
     NK_TRY(nk_blas_norms_inf2(ctx, n, x, d_out, extra_partials, extra_n, have_partials));
-    if (legacy) return nk_scalars_to_host(ctx, d_out, count, h_out);
     // several ranks: the publish is a launch of its own; work the caller wants in the queue behind it goes in before the wait
     const uint64_t seq = ++ctx->seq;
     NK_LAUNCH(ctx, k_publish, dim3(1), dim3(NK_BLOCK), (const double *)d_out, count, ctx->h_pinned_dev, ctx->h_seq_dev, seq);
@@ -1080,18 +989,12 @@ __global__ __launch_bounds__(NK_BLOCK) void k_publish(const double *__restrict__
 }
 int nk_scalars_to_host(nk_ctx *ctx, const double *d_src, int count, double *h_dst, const std::function<int()> &before_wait) {
   NK_REQUIRE(count <= NK_BLOCK && count <= 4 * NK_MAX_NV, "too many scalars");
-  static const bool legacy = getenv("NK_FETCH_MEMCPY") != nullptr;  // A/B switch: copy + synchronise
-  if (legacy) {
-    NK_HIP(hipMemcpyAsync(ctx->h_pinned, d_src, count * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    NK_HIP(hipStreamSynchronize(ctx->stream));
-  } else {
-    const uint64_t seq = ++ctx->seq;
-    NK_LAUNCH(ctx, k_publish, dim3(1), dim3(NK_BLOCK), d_src, count, ctx->h_pinned_dev, ctx->h_seq_dev, seq);
-    NK_HIP(hipGetLastError());
-    if (before_wait) NK_TRY(before_wait());   // (work the caller wants in the queue while the host waits)
-    volatile uint64_t *hs = ctx->h_seq;
-    NK_TRY(nk_spin_wait(ctx, [&] { return __atomic_load_n(hs, __ATOMIC_ACQUIRE) == seq; }, "published scalars"));
-  }
+  const uint64_t seq = ++ctx->seq;
+  NK_LAUNCH(ctx, k_publish, dim3(1), dim3(NK_BLOCK), d_src, count, ctx->h_pinned_dev, ctx->h_seq_dev, seq);
+  NK_HIP(hipGetLastError());
+  if (before_wait) NK_TRY(before_wait());   // (work the caller wants in the queue while the host waits)
+  volatile uint64_t *hs = ctx->h_seq;
+  NK_TRY(nk_spin_wait(ctx, [&] { return __atomic_load_n(hs, __ATOMIC_ACQUIRE) == seq; }, "published scalars"));
   for (int i = 0; i < count; ++i) h_dst[i] = ctx->h_pinned[i];
   return NK_OK;
 }

@@ -175,83 +175,42 @@ __global__ __launch_bounds__(1024) void k_givens_dcgs2(nk_gmres_ctl *ctl, const 
   }
 }
 
-// DCGS2 with one reduction per step — the scalar work between the dot sweep and the axpy sweep of step k (one wave does
-// the serial part; k < NK_MAX_NV). red = [R_j = ṽ_j·u (k), a = u·u, G_j = ṽ_j·z (k), d = u·z], all-reduced, unscaled.
-//   r = s∘R, g = s∘G, β² = a − rᵀr, s_k = 1/β;  H[0:k, k−1] = t_prev + r, H[k, k−1] = β  → Givens on column k−1 (one step
-//   late), stopping test;  c = H̄_{k−1} r;  t = [(g − c_{0:k})/β ; (d − rᵀg − β c_k)/β²]  (first projection of A v_k)
-//   axpy coefficients: a_j = r_j s_j;  b_j = (s_k c_j + t_j) s_j (j<k), b_k = (s_k c_k + t_k) s_k, b_{k+1} = s_k (scale of z)
-// k = 0: column 0 is final, only t_0 = s_0² d. `last`: the flush after the cycle's last step — no z, no coefficients.
-// Latency matters here, not bandwidth (one workgroup between two sweeps): every global operand is requested up front with
-// clamped, unconditional addresses (a load behind a lane predicate costs a full round trip each — five of them in the first
-// version of this kernel), the two inner products run as wave reductions, and H̄ r is split four ways.
-// tprev is double-buffered by the parity of k (tprev_in = buffer k & 1, tprev_out = the other one): in the merged form
-// below every workgroup reads the old values while workgroup 0 writes the new ones.
-__global__ __launch_bounds__(256) void k_dcgs2r_tail(nk_gmres_ctl *ctl, int k, int last, const double *__restrict__ red,
-                                                     double *s, double *__restrict__ Hraw, int m,
-                                                     const double *__restrict__ tprev_in, double *__restrict__ tprev,
-                                                     double *R, double *cs, double *sn, double *g,
-                                                     double *__restrict__ a_out, double *__restrict__ b_out,
-                                                     nk_gmres_pub *pub, uint64_t seq) {
+// DCGS2 with one reduction per step — the flush after a cycle's last step (k = the number of steps, 1 ≤ k < NK_MAX_NV). The
+// pending column k is never used as a basis vector, so it closes WITHOUT its second projection (r = 0): the last Hessenberg
+// column is the first projection alone, H[0:k, k−1] = t_prev, and H[k, k−1] = β = ‖u‖ with red[k] = u·u left by the last
+// axpy sweep (k_dcgs2r_axpy_tail below, which does the same scalar work for every step before this one in its prologue).
+// Then the Givens rotations on column k−1 (one step late), the residual estimate and the stopping test. One workgroup, and
+// latency matters here, not bandwidth: every global operand is requested up front with clamped, unconditional addresses (a
+// load behind a lane predicate costs a full round trip each) and ‖r‖² runs as a wave reduction.
+// tprev is double-buffered by the parity of k (tprev_in = buffer k & 1): in k_dcgs2r_axpy_tail every workgroup reads the old
+// values while workgroup 0 writes the new ones.
+__global__ __launch_bounds__(256) void k_dcgs2r_tail(nk_gmres_ctl *ctl, int k, const double *__restrict__ red, double *s,
+                                                     double *__restrict__ Hraw, int m, const double *__restrict__ tprev_in,
+                                                     double *R, double *cs, double *sn, double *g, nk_gmres_pub *pub,
+                                                     uint64_t seq) {
   const int done = ctl->done;
-  constexpr int NH = NK_MAX_NV + 2, LH = NK_MAX_NV + 1;  // any restart the GMRES object accepts (m < NK_MAX_NV)
-  __shared__ double sr[NH], sg[NH], sc_[NH], sh[NH], scs[NH], ssn[NH], ssc[NH];
-  __shared__ double sH[NH * LH];  // H̄ rows 0..k, columns 0..k−1, staged in one round trip
-  __shared__ double spart[4 * 64];
+  constexpr int NH = NK_MAX_NV + 2;  // any restart the GMRES object accepts (m < NK_MAX_NV)
+  __shared__ double sh[NH], scs[NH], ssn[NH];
   const int t = threadIdx.x;
-  if (k == 0) {
-    if (t == 0 && !done) {
-      const double s0 = s[0], tl = s0 * s0 * red[1];
-      tprev[0] = tl;
-      b_out[0] = tl * s0;
-      b_out[1] = s0;
-    }
-    return;
-  }
   // ---- every global read, back to back
   const int tc = t < k ? t : k - 1;
   const int tr = t < k - 1 ? t : (k > 1 ? k - 2 : 0);
   const double st = s[tc];
-  const double r_raw = (last == 2) ? 0.0 : red[tc];  // last = 2: the pending column closes the cycle un-re-orthogonalised
-  const double g_raw = red[last ? tc : k + 1 + tc];
+  const double r_raw = 0.0;  // the pending column closes the cycle un-re-orthogonalised
   const double tp = tprev_in[tc];
   const double csv = cs[tr], snv = sn[tr];
-  const double gj = g[k - 1], ra = red[k], rd = red[last ? k : 2 * k + 1], tol = ctl->tol;
-  const int km1 = k > 1 ? k - 1 : 1;
-  const int tot = last ? 0 : (k + 1) * (k - 1);  // columns 0..k−2 (column k−1 is completed below)
-  for (int e0 = 0; e0 < tot; e0 += 1024) {
-    double hv[4];
-    int at[4];
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const int e = e0 + t + 256 * q, ec = e < tot ? e : 0;
-      const int i = ec / km1, j = ec - i * km1;
-      hv[q] = Hraw[(size_t)i * m + j];
-      at[q] = (e < tot) ? (i * LH + j) : -1;
-      if (i > j + 1) hv[q] = 0.0;
-    }
-#pragma unroll
-    for (int q = 0; q < 4; ++q)
-      if (at[q] >= 0) sH[at[q]] = hv[q];
-  }
-  const double rt = (t < k) ? st * r_raw : 0.0;
-  const double gt = (t < k && !last) ? st * g_raw : 0.0;
+  const double gj = g[k - 1], ra = red[k], tol = ctl->tol;
+  const double rt = (t < k) ? st * r_raw : 0.0;  // (not the constant 0: an infinite scale s_t has to show as NaN)
   const double ht = tp + rt;  // entry t of the Hessenberg column that completes now (t < k)
-  double rr = rt * rt, rg = rt * gt;  // wave 0 holds every t < k ≤ 62
+  double rr = rt * rt;  // wave 0 holds every t < k ≤ 62
 #pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    rr += __shfl_xor(rr, o, 64);
-    rg += __shfl_xor(rg, o, 64);
-  }
+  for (int o = 32; o > 0; o >>= 1) rr += __shfl_xor(rr, o, 64);
   if (done) return;  // uniform
   const int jc = k - 1;
   if (t < k) {
-    ssc[t] = st;
-    sr[t] = rt;
-    sg[t] = gt;
     sh[t] = ht;
     if (t < k - 1) { scs[t] = csv; ssn[t] = snv; }
     Hraw[(size_t)t * m + jc] = ht;
-    sH[t * LH + jc] = ht;
   }
   double b2 = ra - rr;  // ‖u − V r‖² by Pythagoras
   if (b2 < 0.0) b2 = 0.0;
@@ -259,7 +218,6 @@ __global__ __launch_bounds__(256) void k_dcgs2r_tail(nk_gmres_ctl *ctl, int k, i
   if (t == 0) {
     s[k] = sk;
     Hraw[(size_t)k * m + jc] = beta;
-    sH[k * LH + jc] = beta;
   }
   __syncthreads();
   if (t == 0) {
@@ -289,38 +247,18 @@ __global__ __launch_bounds__(256) void k_dcgs2r_tail(nk_gmres_ctl *ctl, int k, i
     else if (beta == 0.0) { ctl->converged = 1; ctl->done = 1; dn = 1; }
     pub_progress(pub, seq, k, dn);
   }
-  if (last) return;
-  {  // c = H̄_{k−1} r: rows 0..k, columns 0..k−1; the entries below the sub-diagonal are stored zeros
-    const int row = t & 63, part = t >> 6;
-    double c = 0.0;
-    if (row <= k) {
-#pragma unroll 4
-      for (int j = part; j < k; j += 4) c += sH[row * LH + j] * sr[j];
-    }
-    spart[part * 64 + row] = c;
-  }
-  __syncthreads();
-  if (t <= k) sc_[t] = (spart[t] + spart[64 + t]) + (spart[128 + t] + spart[192 + t]);
-  __syncthreads();
-  if (t < k) {
-    const double tt = (sg[t] - sc_[t]) * sk;
-    tprev[t] = tt;
-    a_out[t] = sr[t] * ssc[t];
-    b_out[t] = (sk * sc_[t] + tt) * ssc[t];
-  }
-  if (t == 0) {
-    const double tl = (rd - rg - beta * sc_[k]) * sk * sk;
-    tprev[k] = tl;
-    b_out[k] = (sk * sc_[k] + tl) * sk;
-    b_out[k + 1] = sk;
-  }
 }
 
 
-// The same scalar work as k_dcgs2r_tail (step k, not the flush) done in the PROLOGUE of the axpy sweep: every workgroup
-// derives the axpy coefficients from the reduced inner products itself (≈ 8 KB of L2-resident operands, one round trip,
-// issued behind the loads of its own row tile), so the one-workgroup launch between the reduction and the sweep —
-// ≈ 5 µs of a 69 µs Arnoldi step at the launch-latency floor — disappears. Workgroup 0 also carries the state forward
+// DCGS2 with one reduction per step — the scalar work between the dot sweep and the axpy sweep of step k (k < NK_MAX_NV), done
+// in the PROLOGUE of the axpy sweep. red = [R_j = ṽ_j·u (k), a = u·u, G_j = ṽ_j·z (k), d = u·z], all-reduced, unscaled.
+//   r = s∘R, g = s∘G, β² = a − rᵀr, s_k = 1/β;  H[0:k, k−1] = t_prev + r, H[k, k−1] = β  → Givens on column k−1 (one step
+//   late), stopping test;  c = H̄_{k−1} r;  t = [(g − c_{0:k})/β ; (d − rᵀg − β c_k)/β²]  (first projection of A v_k)
+//   axpy coefficients: a_j = r_j s_j;  b_j = (s_k c_j + t_j) s_j (j<k), b_k = (s_k c_k + t_k) s_k, b_{k+1} = s_k (scale of z)
+// k = 0: column 0 is final, only t_0 = s_0² d. The two inner products run as wave reductions, and H̄ r is split four ways.
+// Every workgroup derives the axpy coefficients from the reduced inner products itself (≈ 8 KB of L2-resident operands, one
+// round trip, issued behind the loads of its own row tile), so a one-workgroup launch between the reduction and the sweep —
+// ≈ 5 µs of a 69 µs Arnoldi step at the launch-latency floor — is not needed. Workgroup 0 also carries the state forward
 // (s_k, the Hessenberg column, tprev, Givens rotation, residual estimate, stopping test, progress word); the other
 // workgroups only read values that workgroup 0 does not write in this launch (tprev is double-buffered; `done` may flip
 // while the launch is in flight, which only decides whether columns k, k+1 — unused once the cycle is done — get updated).
@@ -332,7 +270,7 @@ __global__ __launch_bounds__(NK_BLOCK) void k_dcgs2r_axpy_tail(int64_t n, int k,
                                                                const double *__restrict__ tprev_in,
                                                                double *__restrict__ tprev_out, double *R, double *cs,
                                                                double *sn, double *g, double *__restrict__ ss_partials,
-                                                               nk_gmres_pub *pub, uint64_t seq, int desc) {
+                                                               nk_gmres_pub *pub, uint64_t seq) {
   constexpr int NH = MAXM + 2, LH = MAXM + 1;
   __shared__ double sr[NH], sg[NH], sc_[NH], sh[NH], scs[NH], ssn[NH], ssc[NH], ca[NH + 1], cb[NH + 1];
   __shared__ double sH[NH * LH];
@@ -449,17 +387,17 @@ __global__ __launch_bounds__(NK_BLOCK) void k_dcgs2r_axpy_tail(int64_t n, int k,
     }
     __syncthreads();
   }
-  // ---- the sweep: p ← p − Σ a_j ṽ_j ; z ← s_k z − Σ b_j ṽ_j − b_k p   (as k_dcgs2r_axpy)
+  // ---- the sweep: p ← p − Σ a_j ṽ_j ; z ← s_k z − Σ b_j ṽ_j − b_k p
   const double sz = s_sz, bk = s_bk;
 #pragma unroll
   for (int i = 0; i < DRT; ++i) zv[i] *= sz;
-  // column pairs (j, j+1), j even. `desc`: from the last pair down to the first — the dot sweep that ran just before
+  // column pairs (j, j+1), j even, from the last pair down to the first — the dot sweep that ran just before
   // this launch read the columns in ascending order, so the highest columns are the ones most recently brought into the
   // Infinity Cache (256 MiB against a basis of up to 260 MB + the 74 MB matrix at 1024²: a cyclic ascending/ascending
   // order evicts every line before it is read again, the zig-zag re-reads the freshest ≈ 150 MB).
   const int npair = (k + 1) >> 1;
   for (int q = 0; q < npair; ++q) {
-    const int j = 2 * (desc ? npair - 1 - q : q);
+    const int j = 2 * (npair - 1 - q);
     const int j1 = min(j + 1, k - 1);
     const double *__restrict__ c0 = V + (size_t)j * ldv;
     const double *__restrict__ c1 = V + (size_t)j1 * ldv;
@@ -757,8 +695,6 @@ extern "C" int nk_gmres_destroy(nk_gmres *G) {
   nk_mg_destroy(G->mg);
   nk_ss_destroy(G->ss);
   hipFree(G->x0_keep);
-  if (G->gexec) hipGraphExecDestroy(G->gexec);
-  if (G->cap_stream) hipStreamDestroy(G->cap_stream);
   hipFree(G->d_h); hipFree(G->d_h2); hipFree(G->d_s); hipFree(G->d_R); hipFree(G->d_cs); hipFree(G->d_sn);
   hipFree(G->d_g); hipFree(G->d_y); hipFree(G->d_ss); hipFree(G->d_ctl);
   hipFree(G->d_u_own); hipFree(G->d_b); hipFree(G->d_x);
@@ -1375,69 +1311,47 @@ static bool dcgs2r_eligible(const nk_gmres *G) {
          G->n <= (int64_t)NK_MAX_ROW_TILES * NK_BLOCK * 8;
 }
 static bool use_dcgs2r(const nk_gmres *G) {
-  if (!dcgs2r_eligible(G)) return false;
-  static const bool two = getenv("NK_DCGS2_TWO_REDUCTIONS") != nullptr;  // A/B switch: keep the two-reduction form
-  return G->ortho == NK_ORTHO_DCGS2_1R || (G->ortho == NK_ORTHO_DCGS2 && !two);
-}
-// The cycle's last Hessenberg column needs the norm of the pending column that the last step leaves behind. That column is
-// never used as a basis vector, so it is closed WITHOUT its second projection: β = ‖u‖ comes out of the last axpy sweep for
-// free and the column is the first projection alone (differs from the re-orthogonalised one by the re-orthogonalisation
-// correction, i.e. at rounding level: 1e-15 relative on the solutions, oracle/reference_restatement.py::gmres_dcgs2_1r).
-// NK_DCGS2_FULL_FLUSH=1 keeps the full form (one more dot sweep over all columns per cycle) for A/B runs.
-static bool dcgs2r_full_flush() {
-  static const bool full = getenv("NK_DCGS2_FULL_FLUSH") != nullptr;
-  return full;
+  return dcgs2r_eligible(G) && (G->ortho == NK_ORTHO_DCGS2 || G->ortho == NK_ORTHO_DCGS2_1R);
 }
 static double *tprev_buf(nk_gmres *G, int k) { return G->d_tprev + (size_t)(k & 1) * (NK_MAX_NV + 2); }
-static bool dcgs2r_split_tail() {
-  static const bool split = getenv("NK_DCGS2_SPLIT_TAIL") != nullptr;  // A/B switch: the scalar work as its own launch
-  return split;
-}
+// The scalar work of the step runs in the prologue of the axpy sweep (k_dcgs2r_axpy_tail): two launches per Arnoldi step after
+// the operator. The cycle's last Hessenberg column needs the norm of the pending column that the last step leaves behind. That
+// column is never used as a basis vector, so it is closed WITHOUT its second projection: β = ‖u‖ comes out of the last axpy
+// sweep for free and the column is the first projection alone (differs from the re-orthogonalised one by the
+// re-orthogonalisation correction, i.e. at rounding level: 1e-15 relative on the solutions,
+// oracle/reference_restatement.py::gmres_dcgs2_1r).
 static int arnoldi_step_1r(nk_gmres *G, int k, bool last_of_cycle) {
   nk_ctx *ctx = G->ctx;
   const int64_t n = G->n, ldv = G->ldv;
   const int *skip = &G->d_ctl->done;
   double *zk = G->V + (size_t)(k + 1) * ldv;
   NK_TRY(op_apply(G, G->V + (size_t)k * ldv, zk, skip, nullptr));  // z = A u on the pending (un-normalised) column
-  NK_TRY(nk_blas_dcgs2r_dots(ctx, n, k, false, G->V, ldv, G->d_red, skip));
-  double *ss_out = (last_of_cycle && !dcgs2r_full_flush()) ? G->d_red + (k + 1) : nullptr;  // slot of u·u at the flush
-  if (dcgs2r_split_tail()) {
-    NK_LAUNCH(ctx, k_dcgs2r_tail, dim3(1), dim3(256), G->d_ctl, k, 0, (const double *)G->d_red, G->d_s, G->d_Hraw, G->m,
-              (const double *)tprev_buf(G, k), tprev_buf(G, k + 1), G->d_R, G->d_cs, G->d_sn, G->d_g, G->d_ca, G->d_cb,
-              G->h_pub_dev, G->cycle_seq);
-    NK_TRY(nk_blas_dcgs2r_axpy(ctx, n, k, G->V, ldv, G->d_ca, G->d_cb, skip, ss_out));
-    return NK_OK;
-  }
-  // scalar work in the prologue of the sweep (k_dcgs2r_axpy_tail): one launch less per Arnoldi step
+  NK_TRY(nk_blas_dcgs2r_dots(ctx, n, k, G->V, ldv, G->d_red, skip));
+  double *ss_out = last_of_cycle ? G->d_red + (k + 1) : nullptr;  // slot of u·u at the flush
   const int64_t tile = (int64_t)NK_BLOCK * DRT;
   const int grid = (int)((n + tile - 1) / tile > 0 ? (n + tile - 1) / tile : 1);
   {
     nk_prof_scope prof_(ctx, NK_K_MULTIAXPY, 8.0 * (double)n * (k + 4));
     double *ssp = ss_out ? ctx->d_partials : (double *)nullptr;
-    static const int desc = getenv("NK_AXPY_DESC") ? atoi(getenv("NK_AXPY_DESC")) : 1;  // NK_AXPY_DESC=0: ascending (A/B)
     if (G->m <= 31)
       NK_LAUNCH(ctx, k_dcgs2r_axpy_tail<32>, dim3(grid), dim3(NK_BLOCK), n, k, G->V, ldv, G->d_ctl, (const double *)G->d_red,
                 G->d_s, G->d_Hraw, G->m, (const double *)tprev_buf(G, k), tprev_buf(G, k + 1), G->d_R, G->d_cs, G->d_sn,
-                G->d_g, ssp, G->h_pub_dev, G->cycle_seq, desc);
+                G->d_g, ssp, G->h_pub_dev, G->cycle_seq);
     else
       NK_LAUNCH(ctx, k_dcgs2r_axpy_tail<NK_MAX_NV>, dim3(grid), dim3(NK_BLOCK), n, k, G->V, ldv, G->d_ctl,
                 (const double *)G->d_red, G->d_s, G->d_Hraw, G->m, (const double *)tprev_buf(G, k), tprev_buf(G, k + 1),
-                G->d_R, G->d_cs, G->d_sn, G->d_g, ssp, G->h_pub_dev, G->cycle_seq, desc);
+                G->d_R, G->d_cs, G->d_sn, G->d_g, ssp, G->h_pub_dev, G->cycle_seq);
   }
   NK_HIP(hipGetLastError());
   if (ss_out) NK_TRY(nk_blas_reduce_one(ctx, ctx->d_partials, grid, ss_out, skip));
   return NK_OK;
 }
-// after the last step of a cycle: the pending column's reduction completes the last Hessenberg column
+// after the last step of a cycle: the pending column's norm completes the last Hessenberg column
 static int arnoldi_flush_1r(nk_gmres *G, int steps) {
   nk_ctx *ctx = G->ctx;
-  const int *skip = &G->d_ctl->done;
   if (steps <= 0) return NK_OK;
-  const bool full = dcgs2r_full_flush();
-  if (full) NK_TRY(nk_blas_dcgs2r_dots(ctx, G->n, steps, true, G->V, G->ldv, G->d_red, skip));
-  NK_LAUNCH(ctx, k_dcgs2r_tail, dim3(1), dim3(256), G->d_ctl, steps, full ? 1 : 2, (const double *)G->d_red, G->d_s,
-            G->d_Hraw, G->m, (const double *)tprev_buf(G, steps), tprev_buf(G, steps + 1), G->d_R, G->d_cs, G->d_sn, G->d_g,
-            G->d_ca, G->d_cb, G->h_pub_dev, G->cycle_seq);
+  NK_LAUNCH(ctx, k_dcgs2r_tail, dim3(1), dim3(256), G->d_ctl, steps, (const double *)G->d_red, G->d_s, G->d_Hraw, G->m,
+            (const double *)tprev_buf(G, steps), G->d_R, G->d_cs, G->d_sn, G->d_g, G->h_pub_dev, G->cycle_seq);
   NK_HIP(hipGetLastError());
   return NK_OK;
 }
@@ -1520,73 +1434,6 @@ static int arnoldi_step(nk_gmres *G, int k) {
   return NK_OK;
 }
 
-// A/B switch NK_GMRES_GRAPH=1: one fixed-work restart cycle (b → column 0, ≤ m Arnoldi steps of four launches, flush,
-// back-substitution, x = V y: ≈ 125 launches) captured ONCE into a HIP graph and replayed per linear solve, for operators whose
-// arguments do not change between solves (the concrete CSR Jacobian). The kernels' by-value cycle number is the captured one,
-// so the host waits with a stream synchronisation instead of polling the published sequence word. Measured on MI355X
-// (Bratu 1024², 30 Arnoldi steps per Newton step): see DESIGN.md §8 — the eager path keeps the queue full (a launch costs
-// the host 2–4 µs, a step's four kernels run for 64 µs), so the graph has nothing to remove; it stays an opt-in.
-static int gmres_solve_graph(nk_gmres *G, const double *d_b, double *d_x, double atol, double rtol, int steps,
-                             nk_gmres_info *info, bool *used) {
-  nk_ctx *ctx = G->ctx;
-  const int64_t n = G->n, ldv = G->ldv;
-  const int m = G->m;
-  *used = false;
-  const void *key[5] = {d_b, d_x, G->A, G->P, G->d_u};
-  const bool same = G->gexec && G->gsteps == steps && !memcmp(key, G->gkey, sizeof(key));
-  if (!same) {
-    if (G->gexec) { hipGraphExecDestroy(G->gexec); G->gexec = nullptr; }
-    if (!G->cap_stream && hipStreamCreateWithFlags(&G->cap_stream, hipStreamNonBlocking) != hipSuccess) {
-      G->graph_broken = true;
-      return NK_OK;
-    }
-    NK_HIP(hipStreamSynchronize(ctx->stream));
-    hipStream_t user_stream = ctx->stream;
-    ctx->stream = G->cap_stream;
-    hipGraph_t graph = nullptr;
-    hipError_t e = hipStreamBeginCapture(G->cap_stream, hipStreamCaptureModeThreadLocal);
-    int st = (e == hipSuccess) ? NK_OK : NK_E_HIP;
-    const uint64_t seq = ++G->cycle_seq;
-    auto body = [&]() -> int {
-      NK_TRY(nk_blas_copy_sumsq(ctx, n, d_b, G->V, G->d_ss));
-      NK_LAUNCH(ctx, k_gmres_begin, dim3(1), dim3(64), G->d_ctl, G->d_ss, atol, rtol, 1, 1, G->d_g, G->d_s, m, G->h_pub_dev, seq);
-      for (int k = 0; k < steps; ++k) NK_TRY(arnoldi_step_1r(G, k, k == steps - 1));
-      NK_TRY(arnoldi_flush_1r(G, steps));
-      NK_LAUNCH(ctx, k_backsolve, dim3(1), dim3(256), G->d_ctl, G->d_R, G->d_g, G->d_y, m, G->h_pub_dev, seq,
-              (const uint64_t *)(ctx->peer.on ? nk_peer_err_ptr(ctx) : nullptr), nk_ss_fix{});
-      NK_TRY(nk_blas_multiaxpy(ctx, n, m, G->V, ldv, G->d_y, 1.0, d_x, nullptr, nullptr, &G->d_ctl->k, G->d_s, true));
-      return NK_OK;
-    };
-    if (st == NK_OK) st = body();
-    if (e == hipSuccess) e = hipStreamEndCapture(G->cap_stream, &graph);
-    ctx->stream = user_stream;
-    if (st == NK_OK && e == hipSuccess && graph) e = hipGraphInstantiate(&G->gexec, graph, nullptr, nullptr, 0);
-    if (graph) hipGraphDestroy(graph);
-    if (st != NK_OK || e != hipSuccess || !G->gexec) {
-      G->gexec = nullptr;
-      G->graph_broken = true;
-      (void)hipGetLastError();
-      return NK_OK;  // the caller falls through to plain launches
-    }
-    memcpy(G->gkey, key, sizeof(key));
-    G->gsteps = steps;
-  }
-  NK_HIP(hipGraphLaunch(G->gexec, ctx->stream));
-  NK_HIP(hipStreamSynchronize(ctx->stream));
-  volatile nk_gmres_pub *pub = G->h_pub;
-  nk_gmres_info inf;
-  memset(&inf, 0, sizeof(inf));
-  inf.iters = pub->k;
-  inf.rnorm0 = pub->rnorm0;
-  inf.rnorm = pub->rnorm;
-  inf.converged = pub->converged;
-  inf.failed = pub->failed;
-  ctx->stats.gmres_iters += inf.iters;
-  if (info) *info = inf;
-  *used = true;
-  return NK_OK;
-}
-
 static int gmres_solve_once(nk_gmres *G, const double *d_b, double *d_x, int use_x0, double atol, double rtol, int maxiter,
                             int fixed_iters, nk_gmres_info *info);
 // The resident matrix-powers kernel needs all its workgroups on the chip at once; when something else holds compute units for
@@ -1624,7 +1471,7 @@ int nk_gmres_solve_dev(nk_gmres *G, const double *d_b, double *d_x, int use_x0, 
 }
 static bool gmres_can_preload(const nk_gmres *G) {
   static const bool off = (getenv("NK_PRELOADED_RHS") && atoi(getenv("NK_PRELOADED_RHS")) == 0) ||
-                          (getenv("NK_SS_FUSED_BEGIN") && atoi(getenv("NK_SS_FUSED_BEGIN")) == 0) || getenv("NK_GMRES_GRAPH");
+                          (getenv("NK_SS_FUSED_BEGIN") && atoi(getenv("NK_SS_FUSED_BEGIN")) == 0);
   return !off && nk_ctx_is_single(G->ctx) && G->ortho == NK_ORTHO_SSTEP && !G->lprec_kind && !G->normal && G->V != nullptr;
 }
 double *nk_gmres_rhs_column(nk_gmres *G) { return gmres_can_preload(G) ? G->V : nullptr; }
@@ -1644,10 +1491,6 @@ bool nk_gmres_take_fused_update(nk_gmres *G, int *grid) {
   return done;
 }
 void nk_gmres_drop_ahead(nk_gmres *G) { G->ahead.valid = false; }
-static bool gmres_graph_wanted() {
-  static const bool want_graph = getenv("NK_GMRES_GRAPH") && atoi(getenv("NK_GMRES_GRAPH")) != 0;
-  return want_graph;
-}
 int nk_gmres_begin_ahead(nk_gmres *G, const double *d_b, const double *ss_partials, int ss_grid, const double *bpart, int bnblk,
                          double atol, double rtol, int maxiter, int fixed_iters, nk_ss_begin_args *out, bool *done) {
   static const bool off = getenv("NK_BEGIN_AHEAD") && atoi(getenv("NK_BEGIN_AHEAD")) == 0;   // A/B switch
@@ -1659,7 +1502,7 @@ int nk_gmres_begin_ahead(nk_gmres *G, const double *d_b, const double *ss_partia
   if (off || !(fixed_iters > 0 && fixed_iters <= G->m) || G->op_kind != 1 || !G->A || G->prec_kind || G->lprec_kind || G->normal ||
       G->shift != 0.0 || G->ortho != NK_ORTHO_SSTEP || !nk_ss_eligible(G) || !gmres_can_preload(G) || ss_partials == nullptr ||
       ss_grid <= 0 || bpart == nullptr || bnblk <= 0 || G->ss_basis == NK_SS_BASIS_MONOMIAL || G->ss_ival_user ||
-      G->ss_force_break_cycle >= 0 || ctx->audit.on || gmres_graph_wanted())
+      G->ss_force_break_cycle >= 0 || ctx->audit.on)
     return NK_OK;
   double *dst = nk_csr_bounds_word(G->A);
   if (dst == nullptr) return NK_OK;
@@ -1688,15 +1531,6 @@ static int gmres_solve_once(nk_gmres *G, const double *d_b, double *d_x, int use
   // the arena's time-out counter is cumulative per CONTEXT: a solver object created after a time-out (or used after another
   // object's solve saw one) starts from what the context has already reported — not from zero
   if (ctx->peer.on && ctx->peer_err_reported > G->peer_err_seen) G->peer_err_seen = ctx->peer_err_reported;
-  {
-    const bool want_graph = gmres_graph_wanted();
-    if (want_graph && fixed_iters > 0 && fixed_iters <= m && !use_x0 && nk_ctx_is_single(ctx) && !ctx->prof.on &&
-        !G->prec_kind && !G->lprec_kind && !G->normal && G->op_kind != 3 && use_dcgs2r(G) && !G->graph_broken) {
-      bool used = false;
-      NK_TRY(gmres_solve_graph(G, d_b, d_x, atol, rtol, fixed_iters, info, &used));
-      if (used) return NK_OK;
-    }
-  }
   if (maxiter <= 0) maxiter = 300;
   const int cap = fixed_iters > 0 ? fixed_iters : maxiter;
   // a breakdown of the s-step form switches THIS solve to delayed CGS2; the object's choice comes back on every exit

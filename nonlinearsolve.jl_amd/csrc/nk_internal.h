@@ -477,14 +477,11 @@ int nk_blas_copy_sumsq(nk_ctx *ctx, int64_t n, const double *x, double *y, doubl
 int nk_blas_norms_inf2(nk_ctx *ctx, int64_t n, const double *x, double *d_out, const double *extra_partials, int extra_n,
                        int have_partials = 0);
 #define NK_SUMSQ_PARTIALS_ONLY ((double *)(uintptr_t)1)  // multiaxpy: leave ‖w‖² partials in ctx->d_partials_ss
+// DCGS2-1R dot sweep: the pending column p = V[:,k] and z = V[:,k+1] = A p against the k final columns:
+// d_red = [ṽ_j·p (k), p·p, ṽ_j·z (k), p·z], all-reduced, unscaled (the axpy sweep is nk_gmres.hip's k_dcgs2r_axpy_tail)
+int nk_blas_dcgs2r_dots(nk_ctx *ctx, int64_t n, int k, const double *V, int64_t ldv, double *d_red, const int *d_skip);
 // DCGS2 pass A: correct the pending column V[:,k] by −Σ a_j ṽ_j, turn V[:,k+1] (= s_k·A·pending) into the true next
 // vector by −Σ b_j ṽ_j − b_k·corrected, and return d_h[0..k] = s_j·(ṽ_j·w) over the corrected basis
-// DCGS2-1R sweeps: dots of the pending column p = V[:,k] (and, unless `flush`, of z = V[:,k+1] = A p) against the k final
-// columns: d_red = [ṽ_j·p (k), p·p, ṽ_j·z (k), p·z], all-reduced, unscaled; axpy: p −= Σ a_j ṽ_j, z = b_{k+1} z − Σ b_j ṽ_j − b_k p
-int nk_blas_dcgs2r_dots(nk_ctx *ctx, int64_t n, int k, bool flush, const double *V, int64_t ldv, double *d_red,
-                        const int *d_skip);
-int nk_blas_dcgs2r_axpy(nk_ctx *ctx, int64_t n, int k, double *V, int64_t ldv, const double *d_a, const double *d_b,
-                        const int *d_skip, double *d_ss_out = nullptr);
 int nk_blas_dcgs2_pass_a(nk_ctx *ctx, int64_t n, int k, double *V, int64_t ldv, const double *d_a, const double *d_b,
                          const double *d_scales, double *d_h, const int *d_skip);
 int nk_blas_fused_axpy_dot(nk_ctx *ctx, int64_t n, int nv, const double *V, int64_t ldv, const double *d_h,
@@ -586,12 +583,6 @@ struct nk_gmres {
   double cheb_lmin = 0, cheb_lmax = 0;
   double *cr = nullptr, *cd = nullptr, *ct = nullptr, *cd2 = nullptr;  // Chebyshev work vectors (cd/cd2 ping-pong)
   double *d_b = nullptr, *d_x = nullptr;  // staging for host-memspace calls
-  // NK_GMRES_GRAPH=1 (A/B switch): the fixed-work cycle captured once into a HIP graph and replayed
-  hipGraphExec_t gexec = nullptr;
-  hipStream_t cap_stream = nullptr;
-  bool graph_broken = false;
-  const void *gkey[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-  int gsteps = 0;
   // NK_ORTHO_SSTEP (nk_sstep.hip): s basis columns per block — matrix powers, then block CGS in Pythagorean form, twice
   struct nk_sstep *ss = nullptr;
   int ss_s = 0;           // block size s (1..16); 0 = automatic: 15 with the Newton basis, 6 with the monomial one

@@ -42,7 +42,7 @@ constexpr int PW_FLAG_STRIDE = 16;  // uint64 words between two bands' flags (12
 constexpr int PW_NXCD = 8;
 
 struct pw_args {
-  int nrows, nb, s, variant;   // variant bit 8 (development hook): band 0 never publishes — its neighbour times out
+  int nrows, nb, s, stall;   // stall (development hook): band 0 never publishes — its neighbour times out
   const int32_t *rowptr, *col;
   const double *val;
   const double *x0;
@@ -288,6 +288,9 @@ __global__ __launch_bounds__(PW_T) void k_spmv_powers(const pw_args a) {
     const double os = (p == 0) ? os_first : os_rest;
     double *ycol = a.Y + (int64_t)p * a.ldy;
     const bool pub = p + 1 < a.s;
+    // PEER: this power's slot in the receive areas — one offset for the push and both receives (as three copies of the expression
+    // the compiler kept two per-lane addresses across the loop, and the 6 × 5 form ran out of registers)
+    const size_t boff = (size_t)(a.pr.ebuf + ((p + 1) & 1)) * PW_T + t;
     PW_STAMP(p, 0);
 #pragma unroll
     for (int q = 0; q < RPT; ++q) {
@@ -321,18 +324,17 @@ __global__ __launch_bounds__(PW_T) void k_spmv_powers(const pw_args a) {
         else ycol[r] = out;
       }
       if (PEER && pub) {   // … and the slice a neighbour RANK reads: into its receive area (buffer ebuf + (p + 1) mod 2)
-        const size_t boff = (size_t)(a.pr.ebuf + ((p + 1) & 1)) * PW_T + t;
         if (pup && i == 0) pw_store_sys(a.pr.push_up + boff, out);
         if (pdn && i == RPT - 1) pw_store_sys(a.pr.push_dn + boff, out);
       }
       if (q == NBND - 1) PW_STAMP(p, 1);   // boundary slices computed, their stores issued
-      if (pub && (a.variant & 255) == 0 && q == NBND - 1) {   // publish as early as possible: behind the boundary slices
+      if (pub && q == NBND - 1) {   // publish as early as possible: behind the boundary slices
         if (PEER && (pup || pdn)) __threadfence_system();
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         PW_STAMP(p, 2);                      // … drained
         __syncthreads();
         PW_STAMP(p, 3);                      // … by every wavefront
-        if (t == 0 && !((a.variant & 256) && b == 0))
+        if (t == 0 && !(a.stall && b == 0))
           __hip_atomic_store(a.flags + (size_t)b * PW_FLAG_STRIDE, a.base + (uint64_t)p + 1, __ATOMIC_RELAXED,
                              __HIP_MEMORY_SCOPE_AGENT);
         if (PEER) {
@@ -343,18 +345,6 @@ __global__ __launch_bounds__(PW_T) void k_spmv_powers(const pw_args a) {
     }
     PW_STAMP(p, 4);                          // interior slices computed, their stores issued
     if (!pub) break;
-    if ((a.variant & 255) != 0) {   // publish behind the whole band: the interior rows overlap the boundary rows' write-through
-      if (PEER && (pup || pdn)) __threadfence_system();
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      __syncthreads();
-      if (t == 0)
-        __hip_atomic_store(a.flags + (size_t)b * PW_FLAG_STRIDE, a.base + (uint64_t)p + 1, __ATOMIC_RELAXED,
-                           __HIP_MEMORY_SCOPE_AGENT);
-      if (PEER) {
-        if (t == 64 && pup) __hip_atomic_store(a.pr.flag_up, a.base + (uint64_t)p + 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-        if (t == 128 && pdn) __hip_atomic_store(a.pr.flag_dn, a.base + (uint64_t)p + 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-      }
-    }
     // ---- the neighbours' boundary rows of power p → the halo parts of the next input buffer
     if (t == 0) {
       if (b > 0) {
@@ -378,9 +368,9 @@ __global__ __launch_bounds__(PW_T) void k_spmv_powers(const pw_args a) {
       const int gu = r0 - PW_HALO + t, gd = r0 + RB + t;
       double hu = 0.0, hd = 0.0;
       if (b > 0) hu = pw_load_sc1(ycol + gu);
-      else if (PEER && pup) hu = pw_load_sys(a.pr.recv_up + (size_t)(a.pr.ebuf + ((p + 1) & 1)) * PW_T + t);
+      else if (PEER && pup) hu = pw_load_sys(a.pr.recv_up + boff);
       if (gd < a.nrows) hd = pw_load_sc1(ycol + gd);
-      else if (PEER && pdn) hd = pw_load_sys(a.pr.recv_dn + (size_t)(a.pr.ebuf + ((p + 1) & 1)) * PW_T + t);
+      else if (PEER && pdn) hd = pw_load_sys(a.pr.recv_dn + boff);
       th = pw_uniform(shifted ? a.theta[p + 1] : 0.0);   // (p + 1 < s here)
 #ifdef NK_PW_STAMPS
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -499,7 +489,7 @@ __global__ __launch_bounds__(PW_T) void k_spmv_powers_seg(const pw_args a) {
     if (!pub) break;
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
-    if (t == 0 && !((a.variant & 256) && b == 0))
+    if (t == 0 && !(a.stall && b == 0))
       __hip_atomic_store(a.flags + (size_t)b * PW_FLAG_STRIDE, a.base + (uint64_t)p + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     if (t == 0 && nup >= 0) {
       if (!pw_wait(a.flags + (size_t)nup * PW_FLAG_STRIDE, a.base + (uint64_t)p + 1, a.err)) s_abort = 1;
@@ -549,8 +539,7 @@ void nk_powers_plan_destroy(nk_powers_plan *P) {
   if (P->h_err) hipHostFree(P->h_err);
   delete P;
 }
-static int pw_variant() {
-  static const int v = getenv("NK_PW_VARIANT") ? atoi(getenv("NK_PW_VARIANT")) : 0;
+static int pw_stall_hook() {
   // development hook: NK_PW_DEBUG_STALL_LAUNCH = n makes band 0 of the process's n-th launch withhold its flag (the time-out path)
   // (a comma-separated list: several torn launches)
   static const std::vector<long> stalls = [] {
@@ -569,7 +558,7 @@ static int pw_variant() {
   ++launches;
   bool stall = false;
   for (long x : stalls) stall = stall || (x > 0 && launches == x);
-  return (v & 255) | (stall ? 256 : 0);
+  return stall ? 1 : 0;
 }
 static bool pw_enabled() {
   static const bool on = !(getenv("NK_SPMV_POWERS") && atoi(getenv("NK_SPMV_POWERS")) == 0);
@@ -590,18 +579,12 @@ static int pw_launch(nk_ctx *ctx, const pw_args &a, bool query, int *occ) {
     return NK_OK;
   }
   hipEvent_t e0 = nullptr, e1 = nullptr;
-  // NK_PW_COOP=1: a cooperative launch — the runtime refuses a grid that cannot be resident on an EMPTY device and keeps cooperative
-  // launches of different streams apart; it does not keep ordinary kernels of other streams off the compute units (the time-out
-  // stays the safety net). Measured: profiles/r05_*_powers_coop_ab.txt.
-  static const bool coop = getenv("NK_PW_COOP") && atoi(getenv("NK_PW_COOP")) != 0;
+  // (a cooperative launch was measured and removed: the runtime only refuses a grid that cannot be resident on an EMPTY device; it
+  //  does not keep ordinary kernels of other streams off the compute units — the time-out stays the safety net.
+  //  Measured −8 %: profiles/r05_e_powers_handoff_ab.txt)
   if (ctx->prof.on && nk_prof_next(ctx, &e0, &e1))
     hipExtLaunchKernelGGL((k_spmv_powers<RPT, W, GEN, PEER>), dim3(a.nb), dim3(PW_T), lds, ctx->stream, e0, e1, 0, a);
-  else if (coop) {
-    pw_args ac = a;
-    void *args[] = {(void *)&ac};
-    NK_HIP(hipLaunchCooperativeKernel(reinterpret_cast<const void *>(&k_spmv_powers<RPT, W, GEN, PEER>), dim3(a.nb), dim3(PW_T), args,
-                                      (unsigned int)lds, ctx->stream));
-  } else
+  else
     hipLaunchKernelGGL((k_spmv_powers<RPT, W, GEN, PEER>), dim3(a.nb), dim3(PW_T), lds, ctx->stream, a);
   NK_HIP(hipGetLastError());
   return NK_OK;
@@ -835,7 +818,7 @@ int nk_csr_powers_dev(nk_csr *A, const double *d_x0, double *d_Y, int64_t ldy, i
   nk_ctx *ctx = A->ctx;
   nk_powers_plan *P = A->pw;
   pw_args a{};
-  a.nrows = (int)A->nrows; a.nb = P->nb; a.s = s; a.variant = pw_variant();
+  a.nrows = (int)A->nrows; a.nb = P->nb; a.s = s; a.stall = pw_stall_hook();
   a.rowptr = A->d_rowptr; a.col = A->d_col; a.val = A->d_val;
   a.x0 = d_x0; a.Y = d_Y; a.ldy = ldy;
   a.scal_first = d_scal_first; a.scal_rest = d_scal_rest; a.theta = d_theta; a.d_skip = d_skip;
@@ -898,7 +881,7 @@ int nk_problem_powers_dev(nk_problem *P, const double *d_u, const double *d_x0, 
   if (P->d_u_lin != d_u || !P->d_diag) NK_TRY(nk_problem_jvp_prepare(P, d_u));   // d = c_exp·exp(u) at the linearisation point
   nk_powers_plan *Q = P->pw;
   pw_args a{};
-  a.nrows = (int)P->n_local; a.nb = Q->nb; a.s = s; a.variant = pw_variant();
+  a.nrows = (int)P->n_local; a.nb = Q->nb; a.s = s; a.stall = pw_stall_hook();
   a.x0 = d_x0; a.Y = d_Y; a.ldy = ldy;
   a.scal_first = d_scal_first; a.scal_rest = d_scal_rest; a.theta = d_theta; a.d_skip = d_skip;
   a.flags = Q->d_flags; a.base = (++Q->epoch) << 8; a.err = Q->h_err_dev;

@@ -802,9 +802,8 @@ int nk_problem_jvp_dev(nk_problem *P, const double *d_u, const double *d_v, doub
       const double *lo, *hi;
       NK_TRY(nk_halo_exchange(ctx, &P->halo, d_v));
       halo_lines(P, 1, false, &lo, &hi);
-      static const bool flat = getenv("NK_BRATU_JVP_FLAT") != nullptr;  // A/B switch: one point per thread
       const int64_t nl = P->j1 - P->j0;
-      if (flat || P->ns >= (1ll << 30)) {
+      if (P->ns >= (1ll << 30)) {   // one point per thread: the tiled form indexes with int
         NK_LAUNCH(ctx, k_bratu_jvp, dim3(grid1(n)), dim3(NK_BLOCK), P->ns, nl, P->c_lap, P->d_diag, d_v, lo, hi, d_jv,
                   d_skip, d_out_scale, ep);
       } else {

@@ -334,7 +334,7 @@ static int residual_norms(nk_solver *S, const double *stall_partials, int stall_
 
 // jac_cache(u) for a concrete J: closed-form values, or — jac_colored — the colour-compressed assembly
 static bool speculation_allowed(const nk_solver *S) {
-  static const bool off = (getenv("NK_SPECULATIVE_JAC") && atoi(getenv("NK_SPECULATIVE_JAC")) == 0) || getenv("NK_GMRES_GRAPH");
+  static const bool off = getenv("NK_SPECULATIVE_JAC") && atoi(getenv("NK_SPECULATIVE_JAC")) == 0;
   // (TrustRegion — the fill at the trial point before the host knows whether it is accepted — was measured on config C5: no
   //  gain, the set is wasted on every rejected step; not enabled)
   return !off && S->o.algorithm == NK_ALG_NEWTON_RAPHSON && !S->o.linesearch && S->o.linsolve != NK_LINSOLVE_GMRES_MATFREE &&

@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Resident matrix-powers kernel vs s streaming SpMV launches on the Bratu Jacobian (the kernel's own begin→end device
-timestamps through the library's profile hooks). One JSON line per case; NK_PW_VARIANT / NK_SPMV_POWERS are read at load time,
-so variants are separate processes:
+timestamps through the library's profile hooks). One JSON line per case; NK_SPMV_POWERS is read at load time, so the two forms are
+separate processes:
 
     python tools/powers_bench.py [grid=1024] [s=15] [reps=100]
 """
@@ -41,7 +41,7 @@ ctx.profile_enable(False)
 t = np.array(ts)
 by = s * (12.0 * J.info()["nnz"] + 4.0 * (n + 1) + 16.0 * n)
 med = float(np.median(t))
-print(json.dumps(dict(grid=ns, s=s, resident=bool(resident), variant=os.environ.get("NK_PW_VARIANT", "0"), reps=reps,
+print(json.dumps(dict(grid=ns, s=s, resident=bool(resident), reps=reps,
                       median_us=round(med, 2), p10_us=round(float(np.percentile(t, 10)), 2),
                       p90_us=round(float(np.percentile(t, 90)), 2), us_per_power=round(med / s, 2),
                       algorithmic_MB=round(by / 1e6, 1), effective_GBps=round(by / med / 1e3, 1),
