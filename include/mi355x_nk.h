@@ -504,7 +504,7 @@ int nk_jac_values_colored(nk_problem *P, const double *u, int memspace, nk_csr *
  * or NK_GRID_BOX (9 points, dof <= 2: a row has at most 20 partials); boundary NK_GRID_DIRICHLET0 (a neighbour outside the grid
  * reads as the constant 0 and has no column), NK_GRID_PERIODIC (indices wrap in both directions) or a kind per side packed by
  * NK_GRID_SIDES (mirror walls, a channel: see the enum below). Unknown c of node (i, j) is
- * element c·nx·ny + j·nx + i (the Brusselator's layout). One rank only: NK_E_UNSUPPORTED on a context with more.
+ * element c·nx·ny + j·nx + i (the Brusselator's layout). Several ranks: "Several ranks" below.
  * The object is an nk_problem of kind NK_PROBLEM_USER whose callbacks launch the generated kernels: every algorithm, linear
  * solver and preconditioner object takes it as it takes any callback problem — so the matrix-free GMRES keeps the callback
  * kind's two reductions per Arnoldi step and unfused output scale, and Jᵀv (TrustRegion, normal forms) is the filled Jacobian's
@@ -573,7 +573,7 @@ int nk_problem_create_grid(nk_ctx *ctx, const char *source, int64_t nx, int64_t 
  * Stencil points are numbered by ascending node index inside the grid — star: (0,0,−1) (0,−1,0) (−1,0,0) C (1,0,0) (0,1,0)
  * (0,0,1); box: dk outermost, di innermost — and the pattern keeps every (point in the domain) × (component) entry in ascending
  * column order, as in 2-D. The object is the same NK_PROBLEM_USER problem owning its pattern: nk_problem_set_params,
- * nk_problem_jac_csr, nk_problem_initial_guess and nk_problem_destroy work unchanged. One rank, Float64. The kernels are
+ * nk_problem_jac_csr, nk_problem_initial_guess and nk_problem_destroy work unchanged. Float64. The kernels are
  * nk_grid3_residual, nk_grid3_jvp (jac = 0) and nk_grid3_jac (jac = 1); NK_GRID_FILL_DIRECT keeps its meaning.
  * Radius 2: NK_GRID_STAR2 is the 13-point star with dof = 1..2 (26 partials) — one offset ∈ {−2, …, 2}, the others 0, anything
  * else reads NaN — in the order (0,0,−2) (0,0,−1) (0,−2,0) (0,−1,0) (−2,0,0) (−1,0,0) C (1,0,0) (2,0,0) (0,1,0) (0,2,0) (0,0,1)
@@ -606,7 +606,7 @@ int nk_problem_create_grid3(nk_ctx *ctx, const char *source, int64_t nx, int64_t
  * compiled grid problem and for one created without fields; nfields outside 0..4 is NK_E_INVALID at creation.
  * nz = 0 makes the 2-D problem, nz >= 3 the 3-D one; nfields = 0 gives the program and the problem of nk_problem_create_grid /
  * nk_problem_create_grid3. Everything else is unchanged: stencils, dof limits, side minimums, p, the pattern (nk_grid_pattern /
- * nk_grid3_pattern: fields add no columns), one rank, Float64, kind NK_PROBLEM_USER, every consumer. -DNK_NFIELDS=<nfields> is
+ * nk_grid3_pattern: fields add no columns), Float64, kind NK_PROBLEM_USER, every consumer. -DNK_NFIELDS=<nfields> is
  * what tells the programs with fields from those without; the kernels keep their names and their thread map (one node per thread, 256
  * per workgroup), and the staged fill's LDS is unchanged. The field neighbourhood is loaded with u's, unconditionally; a load
  * whose value the source does not read is removed by the compiler, so declaring a field costs nothing until it is read.
@@ -621,6 +621,41 @@ int nk_grid_fields_compile_check(const char *source, int dim, int dof, int stenc
                                  int64_t *code_bytes);
 int nk_grid_fields_code_object(const char *source, int dim, int dof, int stencil, int boundary, int nparams, int nfields, int jac,
                                void *buf, int64_t capacity, int64_t *bytes);
+
+/* Several ranks. nk_problem_create_grid, _grid3 and _grid_fields accept a context of R > 1 ranks (the call is then collective):
+ * the grid is split into slabs along its OUTERMOST axis — y in 2-D, z in 3-D. Rank r owns the lines (3-D: planes)
+ * [l0, l1) = nk_partition_range(n_outer, 1, R, r), the rule of the built-in grid problems; nl = l1 − l0, nn_loc = the slab's nodes.
+ *   Local numbering   component-major on the slab: unknown c of slab node m is local element c·nn_loc + m, with
+ *                     m = jl·nx + i in 2-D and m = (kl·ny + j)·nx + i in 3-D (jl, kl: the line, the plane within the slab).
+ *   Global numbering  row_begin + local, row_begin = dof · (nodes of all lower slabs): one contiguous row range per rank (what
+ *                     nk_csr_create_local needs, the convention of the multi-rank Brusselator), a permutation of the one-rank
+ *                     numbering c·nn + node. Within a row of the pattern the columns ascend in this numbering: (owner rank,
+ *                     component, node within the owner's slab).
+ *   The site          handed to the source stays global: s.j (3-D: s.k) is the line's index on the whole grid and s.ny (s.nz)
+ *                     the whole extent, so a source that computes coefficients from its position means what it meant.
+ *   Refusal           every rank's slab holds at least radius + 1 lines — ghost lines then come from the adjacent ranks only and
+ *                     a mirror at a physical side of the split axis lands inside the rank's own slab — else NK_E_INVALID naming
+ *                     n_outer, R, the thinnest slab and the radius. R = 1 is exactly the problem of one rank.
+ * Each rank compiles programs whose two sides of the split axis are its own: a physical Dirichlet or mirror side keeps its kind,
+ * a cut between two ranks (both sides, if the axis is periodic) is a kind internal to the programs. A stencil point that leaves
+ * the slab through a cut is in the domain and reads u, v and the fields from that side's ghost lines — `radius` lines per
+ * component, exchanged through the context's halo exchange before each launch: the residual and the fill exchange u, J·v
+ * exchanges u and v; stats.halo_exchanges counts them and both transports carry them. Fields are split like u:
+ * nk_problem_set_field takes and nk_problem_get_field returns the rank's nn_loc doubles, and nk_problem_set_field exchanges the
+ * field's ghost lines once, there — on several ranks it is a collective call. Through a cut a field reads the neighbour's value;
+ * outside a physical Dirichlet side it still reads as at the node itself. Jᵀv goes through the filled pattern as on one rank.
+ * The first three calls below are host only (no device): the slab [line_begin, line_end) and its rows of the pattern with
+ * int64 columns in the global numbering (size query with NULL arrays, like nk_grid_pattern; nz is not read for dim = 2; it also
+ * reports the refusal), and the programs of rank `rank` of `nranks` — (nranks, rank) decide which sides are cuts and the order
+ * of the ghost zones among a row's columns; nranks = 1 gives the programs of the calls above, byte for byte.
+ * nk_problem_grid_slab: the lines of a compiled grid problem's own slab ([0, n_outer) on one rank). */
+int nk_grid_slab_pattern(int dim, int64_t nx, int64_t ny, int64_t nz, int dof, int stencil, int boundary, int nranks, int rank,
+                         int64_t *line_begin, int64_t *line_end, int32_t *rowptr, int64_t *colind_global, int64_t *nnz);
+int nk_grid_slab_compile_check(const char *source, int dim, int dof, int stencil, int boundary, int nparams, int nfields,
+                               int nranks, int rank, int64_t *code_bytes);
+int nk_grid_slab_code_object(const char *source, int dim, int dof, int stencil, int boundary, int nparams, int nfields, int nranks,
+                             int rank, int jac, void *buf, int64_t capacity, int64_t *bytes);
+int nk_problem_grid_slab(nk_problem *P, int64_t *line_begin, int64_t *line_end);
 
 /* ---------------------------------------------------------------- GMRES (seam 1) */
 int nk_gmres_create(nk_ctx *ctx, int64_t n_local, int restart_m, int ortho, nk_gmres **out);

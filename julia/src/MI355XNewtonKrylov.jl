@@ -207,8 +207,13 @@ end
 """`CompiledGridProblem(source, nx, ny; dof = 1, stencil = :star, boundary = :dirichlet, params = Float64[])`: a residual given
 pointwise on an nx × ny grid through a radius-1 or radius-2 stencil as HIP source
 `template <typename T> __device__ void nk_point(const nk_nbhd<T> &u, const nk_real *p, nk_site s, T *f)`; the library compiles
-the residual kernel, the exact dual-number JVP kernel and the Jacobian fill from it (nk_problem_create_grid). One rank, Float64,
-dof ≤ 4 (box: ≤ 2), at most 32 parameters. With `nz = n` the grid is nx × ny × nz and the source is written against
+the residual kernel, the exact dual-number JVP kernel and the Jacobian fill from it (nk_problem_create_grid). Float64,
+dof ≤ 4 (box: ≤ 2), at most 32 parameters. Several ranks: on a context of R > 1 ranks the call is collective and the grid is
+split into slabs along its outermost axis (y; with `nz`: z), rank r owning the lines `grid_slab(P)` = nk_partition_range(n_outer,
+1, R, r), at least radius + 1 of them. Local vectors are component-major on the slab (c·nn_loc + slab node), the global numbering
+is row_begin + local, slab after slab; the source still sees the site on the whole grid. Fields are split like u (`set_field!`
+takes the slab and is collective). `grid_slab_pattern`, `grid_slab_compile_check` and `grid_slab_code_object` are the host-only
+views of one rank's rows and programs. With `nz = n` the grid is nx × ny × nz and the source is written against
 `nk_nbhd3<T>` / `nk_site3` (`u(di, dj, dk, c)`; nk_problem_create_grid3): the 7-point star with dof ≤ 4 or the 27-point box with dof = 1.
 Radius 2 (offsets in −2 … 2, sides ≥ 5): `stencil = :star2`, the 9-point star in 2-D and the 13-point star in 3-D with dof ≤ 2, and
 `stencil = :diamond2`, the 13 points with |di| + |dj| ≤ 2, 2-D only, dof = 1.
@@ -245,7 +250,8 @@ function CompiledGridProblem(source::AbstractString, nx::Integer, ny::Integer; d
     return p
 end
 """`set_field!(P, k, x)`: replace field k (0-based) of a compiled grid problem with fields by the host vector `x`, one Float64
-per node in the grid's order; `get_field(P, k, nn)` returns a host copy of its nn values."""
+per node of this rank's slab (one rank: of the grid) in the grid's order; `get_field(P, k, nn)` returns a host copy of its nn
+values. On several ranks `set_field!` is collective: it exchanges the field's ghost lines."""
 function set_field!(P::DeviceProblem, k::Integer, x::Vector{Float64})
     GC.@preserve x nkcheck(@ccall libnk.nk_problem_set_field(P.ptr::Ptr{Cvoid}, k::Cint, x::Ptr{Float64}, 0::Cint)::Cint)
     return P
@@ -296,6 +302,58 @@ function grid_compile_check(source::AbstractString; dof::Integer = 1, stencil::S
     nkcheck(@ccall libnk.nk_grid_compile_check(String(source)::Cstring, dof::Cint, GRID_STENCILS[stencil]::Cint,
         bd::Cint, nparams::Cint, nb::Ptr{Int64})::Cint)
     return nb[]
+end
+
+"""`grid_slab(P)` → `(line_begin, line_end)`: the lines (3-D: planes) of the outermost axis this rank's slab of a compiled grid
+problem holds, 0-based and half-open; `(0, n_outer)` on one rank."""
+function grid_slab(P::DeviceProblem)
+    l0, l1 = Ref{Int64}(0), Ref{Int64}(0)
+    nkcheck(@ccall libnk.nk_problem_grid_slab(P.ptr::Ptr{Cvoid}, l0::Ptr{Int64}, l1::Ptr{Int64})::Cint)
+    return l0[], l1[]
+end
+"""`grid_slab_pattern(nx, ny; dof, stencil, boundary, nz, nranks, rank)` → `((line_begin, line_end), rowptr, colind)`: the slab of
+rank `rank` of `nranks` and its rows of the Jacobian's pattern — `rowptr` 0-based `Int32` over the slab's rows in local order,
+`colind` 0-based `Int64` in the global, rank-contiguous numbering, ascending within a row (host only). A slab thinner than
+radius + 1 lines is an error."""
+function grid_slab_pattern(nx::Integer, ny::Integer; dof::Integer = 1, stencil::Symbol = :star, boundary = :dirichlet,
+                           nz::Union{Nothing, Integer} = nothing, nranks::Integer, rank::Integer)
+    dim = nz === nothing ? 2 : 3
+    st, bd, nzz = GRID_STENCILS[stencil], grid_boundary(boundary, dim), nz === nothing ? 1 : nz
+    nnz, l0, l1 = Ref{Int64}(0), Ref{Int64}(0), Ref{Int64}(0)
+    nkcheck(@ccall libnk.nk_grid_slab_pattern(dim::Cint, Int64(nx)::Int64, Int64(ny)::Int64, Int64(nzz)::Int64, dof::Cint, st::Cint,
+        bd::Cint, nranks::Cint, rank::Cint, l0::Ptr{Int64}, l1::Ptr{Int64}, C_NULL::Ptr{Int32}, C_NULL::Ptr{Int64},
+        nnz::Ptr{Int64})::Cint)
+    nloc = dof * (l1[] - l0[]) * (nz === nothing ? nx : nx * ny)
+    rowptr, colind = Vector{Int32}(undef, nloc + 1), Vector{Int64}(undef, nnz[])
+    nkcheck(@ccall libnk.nk_grid_slab_pattern(dim::Cint, Int64(nx)::Int64, Int64(ny)::Int64, Int64(nzz)::Int64, dof::Cint, st::Cint,
+        bd::Cint, nranks::Cint, rank::Cint, l0::Ptr{Int64}, l1::Ptr{Int64}, rowptr::Ptr{Int32}, colind::Ptr{Int64},
+        nnz::Ptr{Int64})::Cint)
+    return (l0[], l1[]), rowptr, colind
+end
+"""`grid_slab_compile_check(source; dof, stencil, boundary, nparams, dim, fields, nranks, rank)`: compile the three kernels of
+rank `rank` of `nranks` for gfx950 (no device needed); bytes of code. `nranks = 1`: `grid_compile_check`'s programs."""
+function grid_slab_compile_check(source::AbstractString; dof::Integer = 1, stencil::Symbol = :star, boundary = :dirichlet,
+                                 nparams::Integer = 0, dim::Integer = 2, fields::Integer = 0, nranks::Integer, rank::Integer)
+    nb = Ref{Int64}(0)
+    dim in (2, 3) || throw(ArgumentError("dim = $dim: expected 2 or 3"))
+    nkcheck(@ccall libnk.nk_grid_slab_compile_check(String(source)::Cstring, dim::Cint, dof::Cint, GRID_STENCILS[stencil]::Cint,
+        grid_boundary(boundary, dim)::Cint, nparams::Cint, fields::Cint, nranks::Cint, rank::Cint, nb::Ptr{Int64})::Cint)
+    return nb[]
+end
+"""`grid_slab_code_object(source; …, nranks, rank, jac)` → `Vector{UInt8}`: the code object of one of the two programs of that
+rank (`jac = false`: residual and JVP kernels; `true`: the Jacobian fill), for inspection."""
+function grid_slab_code_object(source::AbstractString; dof::Integer = 1, stencil::Symbol = :star, boundary = :dirichlet,
+                               nparams::Integer = 0, dim::Integer = 2, fields::Integer = 0, nranks::Integer, rank::Integer,
+                               jac::Bool = false)
+    nb = Ref{Int64}(0)
+    dim in (2, 3) || throw(ArgumentError("dim = $dim: expected 2 or 3"))
+    st, bd = GRID_STENCILS[stencil], grid_boundary(boundary, dim)
+    nkcheck(@ccall libnk.nk_grid_slab_code_object(String(source)::Cstring, dim::Cint, dof::Cint, st::Cint, bd::Cint, nparams::Cint,
+        fields::Cint, nranks::Cint, rank::Cint, Cint(jac)::Cint, C_NULL::Ptr{Cvoid}, Int64(0)::Int64, nb::Ptr{Int64})::Cint)
+    buf = Vector{UInt8}(undef, nb[])
+    nkcheck(@ccall libnk.nk_grid_slab_code_object(String(source)::Cstring, dim::Cint, dof::Cint, st::Cint, bd::Cint, nparams::Cint,
+        fields::Cint, nranks::Cint, rank::Cint, Cint(jac)::Cint, buf::Ptr{Cvoid}, Int64(nb[])::Int64, nb::Ptr{Int64})::Cint)
+    return buf
 end
 
 # ------------------------------------------------------------------ preconditioner objects (what `precs(A, p)` may return)
@@ -897,7 +955,7 @@ end
 # point with memspace = NK_DEVICE, and device-resident Julia operators / preconditioners serve through the device-pointer
 # callback contract (nk_matvec_fn proper).
 
-export Ctx, DeviceVector, DeviceCSR, DeviceProblem, bratu2d, brusselator2d, CompiledGridProblem, grid_pattern, grid_compile_check, grid_sides, set_field!, get_field, mi355x_function, MI355XGMRES,
+export Ctx, DeviceVector, DeviceCSR, DeviceProblem, bratu2d, brusselator2d, CompiledGridProblem, grid_pattern, grid_compile_check, grid_sides, grid_slab, grid_slab_pattern, grid_slab_compile_check, grid_slab_code_object, set_field!, get_field, mi355x_function, MI355XGMRES,
     MI355XNewtonKrylovAlg, EnsembleKernel, LeastSquaresEnsembleKernel, SimpleGaussNewton, vectorized_solve, DevicePreconditioner, DeviceILU0, DeviceILUT, DeviceAMG, DeviceJacobi, update!, update_values!
 
 end # module

@@ -207,6 +207,10 @@ SIGNATURES = {
     "nk_problem_get_field": (_I, [_P, _I, _P, _I]),
     "nk_grid_fields_compile_check": (_I, [C.c_char_p, _I, _I, _I, _I, _I, _I, C.POINTER(_L)]),
     "nk_grid_fields_code_object": (_I, [C.c_char_p, _I, _I, _I, _I, _I, _I, _I, _P, _L, C.POINTER(_L)]),
+    "nk_grid_slab_pattern": (_I, [_I, _L, _L, _L, _I, _I, _I, _I, _I, C.POINTER(_L), C.POINTER(_L), _P, _P, C.POINTER(_L)]),
+    "nk_grid_slab_compile_check": (_I, [C.c_char_p, _I, _I, _I, _I, _I, _I, _I, _I, C.POINTER(_L)]),
+    "nk_grid_slab_code_object": (_I, [C.c_char_p, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _L, C.POINTER(_L)]),
+    "nk_problem_grid_slab": (_I, [_P, C.POINTER(_L), C.POINTER(_L)]),
     "nk_gmres_create": (_I, [_P, _L, _I, _I, _PP]),
     "nk_gmres_destroy": (_I, [_P]),
     "nk_gmres_set_operator_csr": (_I, [_P, _P]),

@@ -531,16 +531,58 @@ def grid_pattern(nx: int, ny: int, dof: int = 1, stencil: str = "star", boundary
     return rowptr, colind
 
 
+def _slab_lines(n_outer: int, nranks: int):
+    """the first line (plane) of every rank's slab and the end: nk_partition_range(n_outer, 1, R, r)"""
+    return [partition_range(n_outer, 1, nranks, r)[0] for r in range(nranks)] + [n_outer]
+
+
+def _slab_permutation(nx, ny, nz, dof, nranks):
+    """perm[g] = the one-rank index c·nn + node of the unknown with the global (rank-contiguous) index g: slab after slab,
+    component-major on each"""
+    line, n_outer = (nx, ny) if nz is None else (nx * ny, nz)
+    nn, begin = line * n_outer, _slab_lines(n_outer, nranks)
+    return np.concatenate([c * nn + np.arange(begin[r] * line, begin[r + 1] * line, dtype=np.int64)
+                           for r in range(nranks) for c in range(dof)])
+
+
+def grid_slab_pattern(nx: int, ny: int, dof: int = 1, stencil: str = "star", boundary="dirichlet", *, nz: Optional[int] = None,
+                      nranks: int, rank: int):
+    """(lines, rowptr, colind): the slab of rank `rank` of `nranks` of a compiled grid problem — lines = (l0, l1) of the
+    outermost axis (y; with nz: z), nk_partition_range's — and its rows of the Jacobian's pattern: rowptr int32 over the slab's
+    dof·nn_loc rows in local order (c·nn_loc + slab node), colind int64 in the global, rank-contiguous numbering (row_begin of
+    the owner + c·nn_loc of the owner + node within its slab), ascending within a row. Host only. A slab thinner than
+    radius + 1 lines raises NKError (NK_E_INVALID). nranks = 1: grid_pattern's."""
+    dim = 2 if nz is None else 3
+    st, bd = _grid_ids(stencil, boundary, dim)
+    nnz, l0, l1 = C.c_int64(), C.c_int64(), C.c_int64()
+
+    def pattern(rp, ci):
+        return L.lib().nk_grid_slab_pattern(dim, nx, ny, 1 if nz is None else nz, dof, st, bd, int(nranks), int(rank),
+                                            C.byref(l0), C.byref(l1), rp, ci, C.byref(nnz))
+    check(pattern(None, None))
+    nn_loc = (l1.value - l0.value) * (nx if nz is None else nx * ny)
+    rowptr = np.empty(dof * nn_loc + 1, dtype=np.int32)
+    colind = np.empty(nnz.value, dtype=np.int64)
+    check(pattern(C.c_void_p(rowptr.ctypes.data), C.c_void_p(colind.ctypes.data)))
+    return (l0.value, l1.value), rowptr, colind
+
+
 def grid_compile_check(source: str, dof: int = 1, stencil: str = "star", boundary="dirichlet", nparams: int = 0, *,
-                       dim: int = 2, fields: int = 0) -> int:
+                       dim: int = 2, fields: int = 0, nranks: int = 1, rank: int = 0) -> int:
     """Compile the residual, JVP and Jacobian kernels of `source` for gfx950 (no device needed); the size of the code objects.
     A source that does not compile raises NKError with the contract and the compiler's log. dim = 3: the 3-D contract
     (nk_nbhd3, nk_site3). stencil = "star2" / "diamond2": the radius-2 neighbourhoods (offsets in −2 … 2). fields = 1..4: the
-    contract with the field argument `const nk_flds &a` (3-D: nk_flds3) of CompiledGridProblem(..., fields=)."""
+    contract with the field argument `const nk_flds &a` (3-D: nk_flds3) of CompiledGridProblem(..., fields=). nranks, rank:
+    the programs of that rank of a grid split over several — its sides of the outermost axis that are cuts between two ranks
+    read ghost lines; nranks = 1 are the programs of one rank."""
     if dim not in (2, 3):
         raise ValueError(f"dim = {dim!r}: expected 2 or 3")
     st, bd = _grid_ids(stencil, boundary, dim)
     nb = C.c_int64()
+    if nranks != 1:
+        check(L.lib().nk_grid_slab_compile_check(source.encode(), dim, dof, st, bd, nparams, int(fields), int(nranks), int(rank),
+                                                 C.byref(nb)))
+        return nb.value
     if fields:
         check(L.lib().nk_grid_fields_compile_check(source.encode(), dim, dof, st, bd, nparams, int(fields), C.byref(nb)))
         return nb.value
@@ -566,17 +608,41 @@ class _GridDeviceProblem(DeviceProblem):
 
     nfields = 0   # CompiledGridProblem(..., fields=k)
 
+    lines = (0, 0)   # the lines (3-D: planes) [l0, l1) of the outermost axis this rank owns; one rank: all of them
+
     @property
     def nn(self) -> int:
-        """grid nodes: the length of a field"""
-        return self.nx * self.ny * getattr(self, "nz", 1)
+        """nodes of this rank's slab (one rank: of the grid): the length of a field"""
+        return self.nx * (self.lines[1] - self.lines[0]) * (self.ny if hasattr(self, "nz") else 1)
+
+    def _local_index(self):
+        """the one-rank index c·nn + node of every local unknown, in local order"""
+        line = self.nx * (self.ny if hasattr(self, "nz") else 1)
+        nn = line * (self.nz if hasattr(self, "nz") else self.ny)
+        return np.concatenate([c * nn + np.arange(self.lines[0] * line, self.lines[1] * line, dtype=np.int64)
+                               for c in range(self.dof)])
+
+    def local_of(self, full):
+        """this rank's local vector (c·nn_loc + slab node) of an array in one-rank order (c·nn + node); a torch tensor stays one"""
+        idx = self._local_index()
+        return full[torch.as_tensor(idx, device=full.device)] if _is_torch(full) else np.asarray(full)[idx]
+
+    def to_full(self, gathered):
+        """the inverse on a gathered global vector (rank-contiguous: dist.gather_vector's): the array in one-rank order"""
+        perm = _slab_permutation(self.nx, self.ny, getattr(self, "nz", None), self.dof, self.ctx.comm_info()[1])
+        gathered = np.asarray(gathered)
+        out = np.empty_like(gathered)
+        out[perm] = gathered
+        return out
 
     def set_field(self, k: int, x):
-        """Replace field k (0 .. nfields − 1) by x: a torch tensor on the device or a NumPy array with one float64 per grid
-        node, node (i, j[, k]) at (k·ny + j)·nx + i. The data is copied; a Jacobian cached for the same u is filled again."""
+        """Replace field k (0 .. nfields − 1) by x: a torch tensor on the device or a NumPy array with one float64 per node of
+        this rank's slab (one rank: per grid node), node (i, j[, k]) at (k·ny + j)·nx + i with the slab's own lines. The data
+        is copied; a Jacobian cached for the same u is filled again. On several ranks the call is collective: the ghost lines
+        of the field are exchanged here, once."""
         size = x.numel() if _is_torch(x) else np.size(x)
         if size != self.nn:
-            raise ValueError(f"field {k}: expected {self.nn} elements (one per grid node), got {size}")
+            raise ValueError(f"field {k}: expected {self.nn} elements (one per node of the rank's slab), got {size}")
         px, ms, _keep = _ptr(x, self.nn)
         check(L.lib().nk_problem_set_field(self._h, int(k), px, ms))
 
@@ -593,7 +659,14 @@ def CompiledGridProblem(source: str, nx: int, ny: int, dof: int = 1, stencil: st
         template <typename T> __device__ void nk_point(const nk_nbhd<T> &u, const nk_real *p, nk_site s, T *f);
     compiled (hiprtc, gfx950) into the residual kernel, the exact dual-number JVP kernel and the Jacobian fill on the stencil's
     CSR pattern (include/mi355x_nk.h, "compiled grid problems"). u0 defaults to zeros; NonlinearProblem(..., p) and
-    reinit_(cache, p=...) replace the source's p[0..nparams). dof <= 4 (box: <= 2), Float64, one rank.
+    reinit_(cache, p=...) replace the source's p[0..nparams). dof <= 4 (box: <= 2), Float64.
+    Several ranks: on a context with a communicator of R > 1 ranks the grid is split into slabs along its outermost axis (y; with
+    nz: z) and the call is collective. P.lines = (l0, l1) are this rank's lines (planes), nk_partition_range(n_outer, 1, R, r);
+    every slab has at least radius + 1 of them (else NKError). Local vectors — u, f, v, what P.residual takes and returns — are
+    component-major on the slab, element c·P.nn + slab node with P.nn the slab's nodes; the global numbering is P.row_begin +
+    local, slab after slab. P.local_of(full) slices an array in one-rank order (c·nn + node) to the local vector,
+    P.to_full(gathered) turns a gathered global vector back, dist.gather_grid(P, local) does both steps. The source still sees
+    the site on the whole grid (s.j, s.ny; 3-D s.k, s.nz). Fields are split like u: set_field takes and field returns the slab.
     With nz the grid is nx × ny × nz and the source follows the 3-D contract
         template <typename T> __device__ void nk_point(const nk_nbhd3<T> &u, const nk_real *p, nk_site3 s, T *f);
     with u(di, dj, dk, c): the 7-point star (dof <= 4) or the 27-point box (dof = 1).
@@ -639,6 +712,9 @@ def CompiledGridProblem(source: str, nx: int, ny: int, dof: int = 1, stencil: st
     if nz is not None:
         P.nz = nz
     P.nfields = int(fields)
+    l0, l1 = C.c_int64(), C.c_int64()
+    check(L.lib().nk_problem_grid_slab(h, C.byref(l0), C.byref(l1)))
+    P.lines = (l0.value, l1.value)
     return P
 
 

@@ -17,7 +17,8 @@
 //
 // The result is an nk_problem of the callback kind NK_PROBLEM_USER whose callbacks are the three launchers below, with
 // user_pattern set to the stencil's CSR pattern: every consumer (nk_problem_jvp_dev, user_lin_J, the solver, GMRES) treats it as
-// it treats any callback problem. Jᵀv is user_lin_J + nk_csr_spmv_t_dev. One rank.
+// it treats any callback problem. Jᵀv is user_lin_J + nk_csr_spmv_t_dev. On several ranks the grid is split into slabs of its
+// outermost axis and a stencil point that leaves the slab through a cut reads ghost lines ("several ranks" below).
 //
 // One table, one text. k_grid_stencils lists every stencil the library offers — dimension, code, name, largest dof and the
 // offsets (di, dj, dk) in pattern order — and everything that depends on the stencil is derived from it: the point count, the
@@ -272,6 +273,141 @@ extern "C" int nk_grid3_pattern(int64_t nx, int64_t ny, int64_t nz, int dof, int
   return grid_pattern(3, nx, ny, nz, dof, stencil, boundary, rowptr, colind, nnz);
 }
 
+// ----------------------------------------------------------------------------- several ranks: slabs of the outermost axis
+// On a context of R > 1 ranks the grid is split along its outermost axis (y in 2-D, z in 3-D): rank r owns the lines (planes)
+// [l0, l1) = nk_partition_range(n_outer, 1, R, r), the rule of the built-in grid problems. Local numbering is component-major on
+// the slab — unknown c of slab node m is c·nn_loc + m, m = (kl·ny + j)·nx + i with kl the plane within the slab — and global
+// numbering is row_begin + local with row_begin = dof · (nodes of all lower slabs): one contiguous row range per rank, a
+// permutation of the one-rank numbering c·nn + node. What a rank's programs are is decided by (sides, R, r) alone (grid_cut): a
+// side of the outermost axis that is a cut between two ranks gets the kind NK_BC_HALO, both sides if the axis is periodic, and
+// the three zones of the slab extended by its ghost lines — low neighbour's, own, high neighbour's — get their order among
+// the global columns. Every slab holds at least radius + 1 lines: ghost lines then come from the adjacent ranks only, and a
+// mirror at a physical side of the split axis lands inside the rank's own slab.
+enum { GRID_BC_HALO = 4 };   // NK_BC_HALO of the device text
+struct grid_cut {
+  int lo = 0, hi = 0;          // the program's kinds of the two sides of the outermost axis
+  int zord[3] = {1, 0, 2};     // [own, low, high]: the zone's place among the row's columns
+  int zgrp[3] = {1, 0, 2};     // the same with the zones of one owner sharing a number
+  bool any() const { return lo == GRID_BC_HALO || hi == GRID_BC_HALO; }
+};
+static int grid_cut_make(int dim, const grid_sides &sd, int R, int r, grid_cut *out) {
+  NK_REQUIRE(R >= 1 && r >= 0 && r < R, "rank %d of %d ranks", r, R);
+  grid_cut c;
+  const int klo = sd.kind[2 * (dim - 1)], khi = sd.kind[2 * (dim - 1) + 1];
+  const bool periodic = klo == NK_GRID_PERIODIC;
+  const bool cut_lo = R > 1 && (r > 0 || periodic), cut_hi = R > 1 && (r < R - 1 || periodic);
+  c.lo = cut_lo ? (int)GRID_BC_HALO : klo;
+  c.hi = cut_hi ? (int)GRID_BC_HALO : khi;
+  // owners: a zone that is not there sorts where it would be on an interior rank. Equal owners (two ranks, periodic): the
+  // peer's first lines — my high zone — come before its last
+  const int owner[3] = {r, cut_lo ? (r > 0 ? r - 1 : R - 1) : -1, cut_hi ? (r < R - 1 ? r + 1 : 0) : R};
+  const int tie[3] = {0, 1, 0};
+  for (int z = 0; z < 3; ++z) {
+    c.zord[z] = c.zgrp[z] = 0;
+    for (int y = 0; y < 3; ++y) {
+      c.zord[z] += (owner[y] < owner[z] || (owner[y] == owner[z] && tie[y] < tie[z])) ? 1 : 0;
+      c.zgrp[z] += owner[y] < owner[z] ? 1 : 0;
+    }
+  }
+  *out = c;
+  return NK_OK;
+}
+
+struct grid_slab {
+  int R = 1, r = 0, radius = 0;
+  int64_t n_outer = 0, line = 0;     // lines (planes) of the split axis; nodes per line
+  std::vector<int64_t> begin;        // begin[p] … begin[p + 1]: the lines of rank p
+  int64_t l0 = 0, l1 = 0;
+};
+static int grid_slab_make(const grid_stencil &st, int64_t nx, int64_t ny, int64_t nz, int R, int r, grid_slab *out) {
+  NK_REQUIRE(R >= 1 && r >= 0 && r < R, "rank %d of %d ranks", r, R);
+  grid_slab sl;
+  sl.R = R;
+  sl.r = r;
+  sl.radius = grid_radius(st);
+  sl.n_outer = st.dim == 3 ? nz : ny;
+  sl.line = st.dim == 3 ? nx * ny : nx;
+  sl.begin.assign((size_t)R + 1, 0);
+  int64_t thinnest = sl.n_outer;
+  for (int p = 0; p < R; ++p) {
+    int64_t b, e;
+    NK_TRY(nk_partition_range(sl.n_outer, 1, R, p, &b, &e));
+    sl.begin[p] = b;
+    sl.begin[p + 1] = e;
+    thinnest = std::min(thinnest, e - b);
+  }
+  if (R > 1)
+    NK_REQUIRE(thinnest >= sl.radius + 1, "n_outer = %lld %s over %d ranks: the thinnest slab has %lld, a radius-%d stencil needs "
+               "at least %d in every slab (ghost lines come from the adjacent ranks only, and a mirror at a wall lands inside the "
+               "rank's own slab)", (long long)sl.n_outer, st.dim == 3 ? "planes" : "lines", R, (long long)thinnest, sl.radius,
+               sl.radius + 1);
+  sl.l0 = sl.begin[r];
+  sl.l1 = sl.begin[r + 1];
+  *out = sl;
+  return NK_OK;
+}
+
+// the slab's rows of the pattern, columns in the global (rank-contiguous) numbering, ascending
+static int grid_slab_pattern(int dim, int64_t nx, int64_t ny, int64_t nz, int dof, int stencil, int boundary, int R, int r,
+                             int64_t *line_begin, int64_t *line_end, int32_t *rowptr, int64_t *colind, int64_t *nnz) {
+  NK_REQUIRE(rowptr || nnz || line_begin, "NULL argument");
+  NK_REQUIRE(dim == 2 || dim == 3, "dim = %d is neither 2 nor 3", dim);
+  if (dim == 2) nz = 1;
+  const grid_stencil *st = nullptr;
+  grid_sides sd;
+  NK_TRY(grid_check_shape(dim, dof, stencil, boundary, &st, &sd));
+  NK_TRY(grid_check_size(*st, nx, ny, nz, dof));
+  grid_slab sl;
+  NK_TRY(grid_slab_make(*st, nx, ny, nz, R, r, &sl));
+  if (line_begin) *line_begin = sl.l0;
+  if (line_end) *line_end = sl.l1;
+  const int64_t nl = sl.l1 - sl.l0, nn_loc = sl.line * nl;
+  int64_t pos = 0;
+  for (int c = 0; c < dof; ++c)
+    for (int64_t ol = 0; ol < nl; ++ol)          // the line (plane) within the slab
+      for (int64_t m = 0; m < sl.line; ++m) {    // the node within the line
+        const int64_t i = m % nx, j = dim == 3 ? m / nx : sl.l0 + ol, k = dim == 3 ? sl.l0 + ol : 0;
+        struct landed { int owner; int64_t w; } nb[27];
+        int cnt = 0;
+        for (int q = 0; q < st->npts; ++q) {
+          const int64_t ii = grid_side_map(i + st->off[q][0], nx, sd.kind[0], sd.kind[1]);
+          const int64_t jj = grid_side_map(j + st->off[q][1], ny, sd.kind[2], sd.kind[3]);
+          const int64_t kk = grid_side_map(k + st->off[q][2], nz, sd.kind[4], sd.kind[5]);
+          if (ii < 0 || jj < 0 || kk < 0) continue;
+          const int64_t o = dim == 3 ? kk : jj, in_line = dim == 3 ? jj * nx + ii : ii;
+          const int owner = (int)(std::upper_bound(sl.begin.begin(), sl.begin.end(), o) - sl.begin.begin()) - 1;
+          const landed e = {owner, (o - sl.begin[owner]) * sl.line + in_line};
+          int t = cnt;
+          while (t > 0 && (nb[t - 1].owner > e.owner || (nb[t - 1].owner == e.owner && nb[t - 1].w > e.w))) --t;
+          if (t > 0 && nb[t - 1].owner == e.owner && nb[t - 1].w == e.w) continue;
+          for (int x = cnt++; x > t; --x) nb[x] = nb[x - 1];
+          nb[t] = e;
+        }
+        if (rowptr) rowptr[c * nn_loc + ol * sl.line + m] = (int32_t)pos;
+        if (colind) {
+          int64_t at = pos;
+          for (int t0 = 0; t0 < cnt;) {   // one owner after the other: component-major on the owner's slab
+            int t1 = t0;
+            while (t1 < cnt && nb[t1].owner == nb[t0].owner) ++t1;
+            const int64_t nn_p = (sl.begin[nb[t0].owner + 1] - sl.begin[nb[t0].owner]) * sl.line;
+            const int64_t rb_p = (int64_t)dof * sl.begin[nb[t0].owner] * sl.line;
+            for (int c2 = 0; c2 < dof; ++c2)
+              for (int t = t0; t < t1; ++t) colind[at++] = rb_p + (int64_t)c2 * nn_p + nb[t].w;
+            t0 = t1;
+          }
+        }
+        pos += (int64_t)cnt * dof;
+      }
+  if (rowptr) rowptr[dof * nn_loc] = (int32_t)pos;
+  if (nnz) *nnz = pos;
+  return NK_OK;
+}
+extern "C" int nk_grid_slab_pattern(int dim, int64_t nx, int64_t ny, int64_t nz, int dof, int stencil, int boundary, int nranks,
+                                    int rank, int64_t *line_begin, int64_t *line_end, int32_t *rowptr, int64_t *colind_global,
+                                    int64_t *nnz) {
+  return grid_slab_pattern(dim, nx, ny, nz, dof, stencil, boundary, nranks, rank, line_begin, line_end, rowptr, colind_global, nnz);
+}
+
 // ----------------------------------------------------------------------------- device source (compiled by hiprtc)
 // The program is: nk_dual_prelude, the stencil's lines (grid_stencil_text), k_grid_types, k_grid_fields (every program gets it;
 // it is empty at NK_NFIELDS == 0), the user's source, k_grid_kernels.
@@ -291,8 +427,22 @@ static const char *k_grid_types = R"NKSRC(
 // ---- compiled grid problems: the node's position and its neighbourhood
 #define NK_GRID_BLOCK 256
 // the kinds of a side (the header's NK_GRID_DIRICHLET0 … NK_GRID_MIRROR_FACE); NK_XLO … NK_ZHI are the program's six
-enum { NK_BC_DIRICHLET0 = 0, NK_BC_PERIODIC = 1, NK_BC_MIRROR_NODE = 2, NK_BC_MIRROR_FACE = 3 };
+enum { NK_BC_DIRICHLET0 = 0, NK_BC_PERIODIC = 1, NK_BC_MIRROR_NODE = 2, NK_BC_MIRROR_FACE = 3, NK_BC_HALO = 4 };
 #define NK_BC_IS_MIRROR(k) ((k) == 2 || (k) == 3)
+// NK_BC_HALO is no kind a user can ask for: it is what a side of the outermost axis (y in 2-D, z in 3-D: NK_OLO, NK_OHI) is in
+// the program of a rank whose slab ends at a cut between two ranks. A point that leaves the slab through a cut is in the domain
+// and keeps its index (nk_grid_land leaves it where it is, as it does outside a Dirichlet-0 side): the index is then one on the
+// slab extended by the ghost lines, negative in the low ones and >= the slab's node count in the high ones
+#define NK_BC_IS_HALO(k) ((k) == 4)
+#define NK_BC_STAYS(k) ((k) == NK_BC_DIRICHLET0 || (k) == NK_BC_HALO)
+#if NK_DIM == 3
+#define NK_OLO NK_ZLO
+#define NK_OHI NK_ZHI
+#else
+#define NK_OLO NK_YLO
+#define NK_OHI NK_YHI
+#endif
+#define NK_ANY_CUT (NK_BC_IS_HALO(NK_OLO) || NK_BC_IS_HALO(NK_OHI))
 // a mirror side lets several stencil points of a row land on one node: only then does the fill merge partials
 #define NK_ANY_MIRROR                                                                                           \
   (NK_BC_IS_MIRROR(NK_XLO) || NK_BC_IS_MIRROR(NK_XHI) || NK_BC_IS_MIRROR(NK_YLO) || NK_BC_IS_MIRROR(NK_YHI) || \
@@ -315,9 +465,9 @@ __device__ __forceinline__ int nk_grid_above(int x, int n) {   // x >= n
 }
 template <int LO, int HI>
 __device__ __forceinline__ int nk_grid_land(int x, int n) {
-  if constexpr (LO == NK_BC_DIRICHLET0 && HI == NK_BC_DIRICHLET0) return x;
-  else if constexpr (HI == NK_BC_DIRICHLET0) return x < 0 ? nk_grid_below<LO>(x, n) : x;
-  else if constexpr (LO == NK_BC_DIRICHLET0) return x >= n ? nk_grid_above<HI>(x, n) : x;
+  if constexpr (NK_BC_STAYS(LO) && NK_BC_STAYS(HI)) return x;
+  else if constexpr (NK_BC_STAYS(HI)) return x < 0 ? nk_grid_below<LO>(x, n) : x;
+  else if constexpr (NK_BC_STAYS(LO)) return x >= n ? nk_grid_above<HI>(x, n) : x;
   else return x < 0 ? nk_grid_below<LO>(x, n) : (x >= n ? nk_grid_above<HI>(x, n) : x);
 }
 // everything the dimension decides: the site, the names the user's source sees, the arity of operator(), the sizes a kernel
@@ -333,6 +483,8 @@ struct nk_site3 { int i, j, k, nx, ny, nz; };
 #define NK_OFFSET_SLOT nk_pt_find(di, dj, dk)
 #define NK_SIZES int nx, int ny, int nz
 #define NK_SIZE_ARGS nx, ny, nz
+#define NK_SLAB_SIZES nx, ny, sl.nl
+#define NK_SLAB_SITE(s) nk_site3{s.i, s.j, s.k + sl.l0, nx, ny, nz}
 __device__ __forceinline__ int nk_grid_nn(int nx, int ny, int nz) { return nx * ny * nz; }
 // node = (k·ny + j)·nx + i
 __device__ __forceinline__ nk_site3 nk_grid_site(int node, int nx, int ny, int nz) {
@@ -365,6 +517,8 @@ struct nk_site { int i, j, nx, ny; };
 #define NK_OFFSET_SLOT nk_pt_find(di, dj, 0)
 #define NK_SIZES int nx, int ny
 #define NK_SIZE_ARGS nx, ny
+#define NK_SLAB_SIZES nx, sl.nl
+#define NK_SLAB_SITE(s) nk_site{s.i, s.j + sl.l0, nx, ny}
 __device__ __forceinline__ int nk_grid_nn(int nx, int ny) { return nx * ny; }
 // node = j·nx + i
 __device__ __forceinline__ nk_site nk_grid_site(int node, int nx, int ny) {
@@ -383,6 +537,43 @@ __device__ __forceinline__ void nk_grid_geom(const nk_site s, int (&idx)[NK_NPTS
     idx[q] = jj * s.nx + ii;
   }
 }
+#endif
+
+// A slab of a grid split over several ranks along the outermost axis: its lines [l0, l0 + nl) of that axis and the ghost lines
+// of each cut, `radius` lines per component as the neighbour sent them (gz nodes per component). The kernels of such a
+// program run on the slab — nk_grid_site and nk_grid_geom get the slab's sizes, the own vectors have the component stride
+// nn = the slab's nodes — and hand the user's source the site on the whole grid (NK_SLAB_SITE). A program without a cut has
+// none of this: its kernels have the parameters and the instructions they always had.
+#if NK_ANY_CUT
+struct nk_slab {
+  int l0, nl, gz, pad;
+  const nk_real *ulo, *uhi, *vlo, *vhi, *alo, *ahi;   // ghost lines of u, v and the fields below and above (NULL: no cut there)
+};
+#define NK_SLAB_PARAM nk_slab sl,
+#define NK_SLAB_ARG , sl
+#define NK_LOCAL_SIZES NK_SLAB_SIZES
+#define NK_USER_SITE(s) NK_SLAB_SITE(s)
+// where the slab-extended index e of point q is: 0 the own slab, 1 the low ghost lines, 2 the high ones. Only a point with an
+// offset along the outermost axis can leave through a cut, so for every other point this is the constant 0
+__device__ __forceinline__ int nk_slab_zone(int q, int e, int nn) {
+  int z = 0;
+  if (NK_BC_IS_HALO(NK_OLO) && nk_pt_off[q][NK_DIM - 1] < 0) z = e < 0 ? 1 : z;
+  if (NK_BC_IS_HALO(NK_OHI) && nk_pt_off[q][NK_DIM - 1] > 0) z = e >= nn ? 2 : z;
+  return z;
+}
+// the element of component c (of `own` with stride nn, or of a ghost buffer with stride gz): base pointer and offset are
+// selected, the load itself is unconditional
+__device__ __forceinline__ nk_real nk_slab_read(const nk_real *__restrict__ own, const nk_real *lo, const nk_real *hi, int c, int z,
+                                                int e, int nn, int gz) {
+  const nk_real *b = z == 1 ? lo : (z == 2 ? hi : own);
+  const int o = z == 1 ? e + gz : (z == 2 ? e - nn : e);
+  return b[c * (z == 0 ? nn : gz) + o];
+}
+#else
+#define NK_SLAB_PARAM
+#define NK_SLAB_ARG
+#define NK_LOCAL_SIZES NK_SIZE_ARGS
+#define NK_USER_SITE(s) s
 #endif
 
 // the stencil point with this offset, -1 if the stencil has none (the offsets are literals in the user's source: the search
@@ -424,6 +615,19 @@ struct NK_FLDS {
     return val[q * NK_NFIELDS + k];
   }
 };
+#if NK_ANY_CUT
+// through a cut a field reads the neighbour's value, from the ghost lines exchanged when the field was set
+__device__ __forceinline__ NK_FLDS nk_flds_load(const nk_real *__restrict__ a, int nn, const int (&idx)[NK_NPTS], const nk_slab &sl) {
+  NK_FLDS fl;
+#pragma unroll
+  for (int q = 0; q < NK_NPTS; ++q) {
+    const int z = nk_slab_zone(q, idx[q], nn);
+#pragma unroll
+    for (int k = 0; k < NK_NFIELDS; ++k) fl.val[q * NK_NFIELDS + k] = nk_slab_read(a, sl.alo, sl.ahi, k, z, idx[q], nn, sl.gz);
+  }
+  return fl;
+}
+#else
 __device__ __forceinline__ NK_FLDS nk_flds_load(const nk_real *__restrict__ a, int nn, const int (&idx)[NK_NPTS]) {
   NK_FLDS fl;
 #pragma unroll
@@ -433,8 +637,9 @@ __device__ __forceinline__ NK_FLDS nk_flds_load(const nk_real *__restrict__ a, i
   }
   return fl;
 }
+#endif
 #define NK_FLDS_PARAM const nk_real *__restrict__ a,
-#define NK_FLDS_ARG nk_flds_load(a, nn, idx),
+#define NK_FLDS_ARG nk_flds_load(a, nn, idx NK_SLAB_ARG),
 #else
 #define NK_FLDS_PARAM
 #define NK_FLDS_ARG
@@ -447,19 +652,31 @@ static const char *k_grid_kernels = R"NKSRC(
 // Dirichlet boundary. The partials of a dual: none to set (NK_SEED_NONE, T = nk_real), its one partial from v (NK_SEED_V),
 // or the unit seed of slot q·dof + c (NK_SEED_UNIT)
 enum { NK_SEED_NONE, NK_SEED_V, NK_SEED_UNIT };
+#if NK_ANY_CUT
+#define NK_SLAB_LOAD_PARAM , const nk_slab &sl
+#define NK_READ_U(c, q) nk_slab_read(u, sl.ulo, sl.uhi, c, z, idx[q], nn, sl.gz)
+#define NK_READ_V(c, q) nk_slab_read(v, sl.vlo, sl.vhi, c, z, idx[q], nn, sl.gz)
+#else
+#define NK_SLAB_LOAD_PARAM
+#define NK_READ_U(c, q) u[c * nn + idx[q]]
+#define NK_READ_V(c, q) v[c * nn + idx[q]]
+#endif
 __device__ __forceinline__ nk_real &nk_value(nk_real &x) { return x; }
 __device__ __forceinline__ nk_real &nk_value(Dual &x) { return x.v; }
 template <int SEED, typename T>
 __device__ __forceinline__ void nk_grid_load(NK_NBHD<T> &nb, const nk_real *__restrict__ u, const nk_real *__restrict__ v,
-                                             int nn, const int (&idx)[NK_NPTS], const bool (&in)[NK_NPTS]) {
+                                             int nn, const int (&idx)[NK_NPTS], const bool (&in)[NK_NPTS] NK_SLAB_LOAD_PARAM) {
 #pragma unroll
   for (int q = 0; q < NK_NPTS; ++q) {
+#if NK_ANY_CUT
+    const int z = nk_slab_zone(q, idx[q], nn);
+#endif
 #pragma unroll
     for (int c = 0; c < NK_DOF; ++c) {
-      const nk_real x = u[c * nn + idx[q]];
+      const nk_real x = NK_READ_U(c, q);
       nk_value(nb.val[q * NK_DOF + c]) = in[q] ? x : NK_R(0);
       if constexpr (SEED == NK_SEED_V) {
-        const nk_real d = v[c * nn + idx[q]];
+        const nk_real d = NK_READ_V(c, q);
         nb.val[q * NK_DOF + c].d[0] = in[q] ? d : NK_R(0);
       }
       if constexpr (SEED == NK_SEED_UNIT) {
@@ -472,40 +689,40 @@ __device__ __forceinline__ void nk_grid_load(NK_NBHD<T> &nb, const nk_real *__re
 
 #if NK_GRID_SET == 0
 extern "C" __global__ void __launch_bounds__(NK_GRID_BLOCK)
-NK_KERNEL(residual)(NK_SIZES, const nk_real *__restrict__ p, NK_FLDS_PARAM const nk_real *__restrict__ u,
+NK_KERNEL(residual)(NK_SIZES, NK_SLAB_PARAM const nk_real *__restrict__ p, NK_FLDS_PARAM const nk_real *__restrict__ u,
                     nk_real *__restrict__ f) {
-  const int nn = nk_grid_nn(NK_SIZE_ARGS), node = (int)blockIdx.x * NK_GRID_BLOCK + (int)threadIdx.x;
+  const int nn = nk_grid_nn(NK_LOCAL_SIZES), node = (int)blockIdx.x * NK_GRID_BLOCK + (int)threadIdx.x;
   if (node >= nn) return;
-  const NK_SITE s = nk_grid_site(node, NK_SIZE_ARGS);
+  const NK_SITE s = nk_grid_site(node, NK_LOCAL_SIZES);
   int idx[NK_NPTS];
   bool in[NK_NPTS];
   nk_grid_geom(s, idx, in);
   NK_NBHD<nk_real> nb;
-  nk_grid_load<NK_SEED_NONE>(nb, u, nullptr, nn, idx, in);
+  nk_grid_load<NK_SEED_NONE>(nb, u, nullptr, nn, idx, in NK_SLAB_ARG);
   nk_real out[NK_DOF];
 #pragma unroll
   for (int c = 0; c < NK_DOF; ++c) out[c] = NK_R(0);
-  nk_point<nk_real>(nb, NK_FLDS_ARG p, s, out);
+  nk_point<nk_real>(nb, NK_FLDS_ARG p, NK_USER_SITE(s), out);
 #pragma unroll
   for (int c = 0; c < NK_DOF; ++c) f[c * nn + node] = out[c];
 }
 
 // J(u)·v exactly: the value of every neighbour from u, its one partial from v
 extern "C" __global__ void __launch_bounds__(NK_GRID_BLOCK)
-NK_KERNEL(jvp)(NK_SIZES, const nk_real *__restrict__ p, NK_FLDS_PARAM const nk_real *__restrict__ u,
+NK_KERNEL(jvp)(NK_SIZES, NK_SLAB_PARAM const nk_real *__restrict__ p, NK_FLDS_PARAM const nk_real *__restrict__ u,
                const nk_real *__restrict__ v, nk_real *__restrict__ jv) {
-  const int nn = nk_grid_nn(NK_SIZE_ARGS), node = (int)blockIdx.x * NK_GRID_BLOCK + (int)threadIdx.x;
+  const int nn = nk_grid_nn(NK_LOCAL_SIZES), node = (int)blockIdx.x * NK_GRID_BLOCK + (int)threadIdx.x;
   if (node >= nn) return;
-  const NK_SITE s = nk_grid_site(node, NK_SIZE_ARGS);
+  const NK_SITE s = nk_grid_site(node, NK_LOCAL_SIZES);
   int idx[NK_NPTS];
   bool in[NK_NPTS];
   nk_grid_geom(s, idx, in);
   NK_NBHD<Dual> nb;
-  nk_grid_load<NK_SEED_V>(nb, u, v, nn, idx, in);
+  nk_grid_load<NK_SEED_V>(nb, u, v, nn, idx, in NK_SLAB_ARG);
   Dual out[NK_DOF];
 #pragma unroll
   for (int c = 0; c < NK_DOF; ++c) out[c] = Dual(NK_R(0));
-  nk_point<Dual>(nb, NK_FLDS_ARG p, s, out);
+  nk_point<Dual>(nb, NK_FLDS_ARG p, NK_USER_SITE(s), out);
 #pragma unroll
   for (int c = 0; c < NK_DOF; ++c) jv[c * nn + node] = out[c].d[0];
 }
@@ -515,9 +732,9 @@ NK_KERNEL(jvp)(NK_SIZES, const nk_real *__restrict__ p, NK_FLDS_PARAM const nk_r
 // NK_GRID_DIRECT = 0: the workgroup's rows of one component are one contiguous piece of the value array — they are put together
 // in LDS and stored as whole lines (k_bratu_jac's way); 1: every thread stores its own partials, 8 bytes at a stride of a row.
 extern "C" __global__ void __launch_bounds__(NK_GRID_BLOCK)
-NK_KERNEL(jac)(NK_SIZES, const nk_real *__restrict__ p, NK_FLDS_PARAM const nk_real *__restrict__ u,
+NK_KERNEL(jac)(NK_SIZES, NK_SLAB_PARAM const nk_real *__restrict__ p, NK_FLDS_PARAM const nk_real *__restrict__ u,
                const int *__restrict__ rowptr, nk_real *__restrict__ vals) {
-  const int nn = nk_grid_nn(NK_SIZE_ARGS), node0 = (int)blockIdx.x * NK_GRID_BLOCK, node_t = node0 + (int)threadIdx.x;
+  const int nn = nk_grid_nn(NK_LOCAL_SIZES), node0 = (int)blockIdx.x * NK_GRID_BLOCK, node_t = node0 + (int)threadIdx.x;
   if (node0 >= nn) return;   // (a workgroup past the grid; the launch has none)
   const bool live = node_t < nn;
 #if NK_GRID_DIRECT
@@ -526,17 +743,32 @@ NK_KERNEL(jac)(NK_SIZES, const nk_real *__restrict__ p, NK_FLDS_PARAM const nk_r
   __shared__ nk_real sv[NK_GRID_BLOCK * NK_NPTS * NK_DOF];   // (at most 256·28 doubles: the 3-D star at dof 4)
 #endif
   const int node = live ? node_t : nn - 1;   // (past the end: the last node again, nothing of it is kept)
-  const NK_SITE s = nk_grid_site(node, NK_SIZE_ARGS);
+  const NK_SITE s = nk_grid_site(node, NK_LOCAL_SIZES);
   int idx[NK_NPTS];
   bool in[NK_NPTS];
   nk_grid_geom(s, idx, in);
   NK_NBHD<Dual> nb;
-  nk_grid_load<NK_SEED_UNIT>(nb, u, nullptr, nn, idx, in);
+  nk_grid_load<NK_SEED_UNIT>(nb, u, nullptr, nn, idx, in NK_SLAB_ARG);
   Dual out[NK_DOF];
 #pragma unroll
   for (int c = 0; c < NK_DOF; ++c) out[c] = Dual(NK_R(0));
-  nk_point<Dual>(nb, NK_FLDS_ARG p, s, out);
+  nk_point<Dual>(nb, NK_FLDS_ARG p, NK_USER_SITE(s), out);
   int rank[NK_NPTS], cnt = 0;
+#if NK_ANY_CUT
+  // Columns ascend in the global numbering, which is (owner rank, component, node within the owner's slab): the three zones
+  // of the extended slab — the low neighbour's lines, the own slab, the high neighbour's — come in an order that is a constant
+  // of the rank (NK_ZORD_*: under periodic wrap rank 0's low zone sorts after its slab, the last rank's high zone before its
+  // own). key = ordinal of the zone · 2^29 + the offset within the zone orders and identifies the landed nodes (a grid has fewer
+  // than 2^29 nodes: INT32_MAX / 5 at most), so everything below that compared idx compares key instead
+  int key[NK_NPTS];
+#pragma unroll
+  for (int q = 0; q < NK_NPTS; ++q) {
+    const int z = nk_slab_zone(q, idx[q], nn);
+    key[q] = z == 1 ? (NK_ZORD_LO << 29) + idx[q] + sl.gz : (z == 2 ? (NK_ZORD_HI << 29) + idx[q] - nn : (NK_ZORD_OWN << 29) + idx[q]);
+  }
+#else
+  const int (&key)[NK_NPTS] = idx;
+#endif
 #if NK_ANY_MIRROR
   // Several points of a row may land on one node. The first of them (smallest q) is the primary: it alone has a column, and its
   // value is the sum of the partials of all of them, added in ascending q. cnt and rank count primaries only
@@ -545,14 +777,14 @@ NK_KERNEL(jac)(NK_SIZES, const nk_real *__restrict__ p, NK_FLDS_PARAM const nk_r
   for (int q = 0; q < NK_NPTS; ++q) {
     bool first = in[q];
 #pragma unroll
-    for (int t = 0; t < q; ++t) first = first && !(in[t] && idx[t] == idx[q]);
+    for (int t = 0; t < q; ++t) first = first && !(in[t] && key[t] == key[q]);
     prim[q] = first;
   }
 #pragma unroll
   for (int q = 0; q < NK_NPTS; ++q) {
     int r = 0;
 #pragma unroll
-    for (int t = 0; t < NK_NPTS; ++t) r += (prim[t] && idx[t] < idx[q]) ? 1 : 0;
+    for (int t = 0; t < NK_NPTS; ++t) r += (prim[t] && key[t] < key[q]) ? 1 : 0;
     rank[q] = r;
     cnt += prim[q] ? 1 : 0;
   }
@@ -560,7 +792,7 @@ NK_KERNEL(jac)(NK_SIZES, const nk_real *__restrict__ p, NK_FLDS_PARAM const nk_r
   for (int q = 0; q < NK_NPTS; ++q) {
 #pragma unroll
     for (int t = q + 1; t < NK_NPTS; ++t) {
-      const bool same = in[t] && idx[t] == idx[q];   // (only a primary's sum is stored; another q's is dropped with it)
+      const bool same = in[t] && key[t] == key[q];   // (only a primary's sum is stored; another q's is dropped with it)
 #pragma unroll
       for (int c = 0; c < NK_DOF; ++c) {
 #pragma unroll
@@ -577,11 +809,48 @@ NK_KERNEL(jac)(NK_SIZES, const nk_real *__restrict__ p, NK_FLDS_PARAM const nk_r
   for (int q = 0; q < NK_NPTS; ++q) {
     int r = 0;
 #pragma unroll
-    for (int t = 0; t < NK_NPTS; ++t) r += (in[t] && idx[t] < idx[q]) ? 1 : 0;
+    for (int t = 0; t < NK_NPTS; ++t) r += (in[t] && key[t] < key[q]) ? 1 : 0;
     rank[q] = r;
     cnt += in[q] ? 1 : 0;
   }
 #define NK_FILL_KEEP(q) in[q]
+#endif
+#if NK_ANY_CUT
+  // Where a zone's columns start and how many each component has there. Zones of one owner form one group (NK_ZGRP_*: with two
+  // ranks and a periodic axis both ghost zones are the one peer's, its first lines — the high zone — before its last): a row is
+  // (group, component, node), so an entry sits at dof · (columns of earlier groups) + c' · (columns of its group) + its rank
+  // within the group, and that rank is rank[q] less the columns of earlier groups, because key orders the groups too
+  int slot[NK_NPTS], same[NK_NPTS];
+  {
+    int nz[3] = {0, 0, 0};   // columns per zone: own, low, high
+#pragma unroll
+    for (int q = 0; q < NK_NPTS; ++q) {
+      const int z = nk_slab_zone(q, idx[q], nn);
+#pragma unroll
+      for (int y = 0; y < 3; ++y) nz[y] += (NK_FILL_KEEP(q) && z == y) ? 1 : 0;
+    }
+    constexpr int grp[3] = {NK_ZGRP_OWN, NK_ZGRP_LO, NK_ZGRP_HI};
+    int before[3], with[3];
+#pragma unroll
+    for (int z = 0; z < 3; ++z) {
+      before[z] = with[z] = 0;
+#pragma unroll
+      for (int y = 0; y < 3; ++y) {
+        before[z] += grp[y] < grp[z] ? nz[y] : 0;
+        with[z] += grp[y] == grp[z] ? nz[y] : 0;
+      }
+    }
+#pragma unroll
+    for (int q = 0; q < NK_NPTS; ++q) {
+      const int z = nk_slab_zone(q, idx[q], nn);
+      const int b = z == 1 ? before[1] : (z == 2 ? before[2] : before[0]);
+      same[q] = z == 1 ? with[1] : (z == 2 ? with[2] : with[0]);
+      slot[q] = NK_DOF * b + rank[q] - b;
+    }
+  }
+#define NK_FILL_AT(q, c2) ((c2) * same[q] + slot[q])
+#else
+#define NK_FILL_AT(q, c2) ((c2) * cnt + rank[q])
 #endif
 #pragma unroll
   for (int c = 0; c < NK_DOF; ++c) {
@@ -591,7 +860,7 @@ NK_KERNEL(jac)(NK_SIZES, const nk_real *__restrict__ p, NK_FLDS_PARAM const nk_r
     for (int q = 0; q < NK_NPTS; ++q) {
       if (NK_FILL_KEEP(q)) {
 #pragma unroll
-        for (int c2 = 0; c2 < NK_DOF; ++c2) vals[base + c2 * cnt + rank[q]] = out[c].d[q * NK_DOF + c2];
+        for (int c2 = 0; c2 < NK_DOF; ++c2) vals[base + NK_FILL_AT(q, c2)] = out[c].d[q * NK_DOF + c2];
       }
     }
 #else
@@ -603,7 +872,7 @@ NK_KERNEL(jac)(NK_SIZES, const nk_real *__restrict__ p, NK_FLDS_PARAM const nk_r
       for (int q = 0; q < NK_NPTS; ++q) {
         if (NK_FILL_KEEP(q)) {
 #pragma unroll
-          for (int c2 = 0; c2 < NK_DOF; ++c2) sv[base - p0 + c2 * cnt + rank[q]] = out[c].d[q * NK_DOF + c2];
+          for (int c2 = 0; c2 < NK_DOF; ++c2) sv[base - p0 + NK_FILL_AT(q, c2)] = out[c].d[q * NK_DOF + c2];
         }
       }
     }
@@ -634,13 +903,19 @@ enum { GSET_F = 0 /* nk_grid_residual + nk_grid_jvp, NK_CH = 1 */, GSET_JAC = 1 
 // One program: its text is the same for every stencil but the stencil's lines, and all of what else it is comes from its
 // options, which every program gets in full (dim = 2: nk_grid_residual / nk_grid_jvp / nk_grid_jac; 3: the nk_grid3_ kernels)
 static int grid_compile(const char *source, int dim, int dof, int stencil, int boundary, int np, int nf, int gset, bool direct,
-                        std::vector<char> *code, std::string *log) {
+                        std::vector<char> *code, std::string *log, int nranks = 1, int rank = 0) {
   NK_REQUIRE(source, "NULL source");
   const grid_stencil *st = nullptr;
   grid_sides sd;
   NK_TRY(grid_check_shape(dim, dof, stencil, boundary, &st, &sd));
   NK_REQUIRE(np >= 0 && np <= 32, "nparams = %d outside 0..32", np);
   NK_REQUIRE(nf >= 0 && nf <= 4, "nfields = %d outside 0..4 (read-only fields of one double per node)", nf);
+  // several ranks: the two sides of the outermost axis are the rank's own, and a program with a cut gets the zone order too
+  // (a program without one gets the options it always got)
+  grid_cut cut;
+  NK_TRY(grid_cut_make(dim, sd, nranks, rank, &cut));
+  sd.kind[2 * (dim - 1)] = cut.lo;
+  sd.kind[2 * (dim - 1) + 1] = cut.hi;
   const std::string stencil_text = grid_stencil_text(*st);
   const std::string full = std::string(nk_dual_prelude) + stencil_text + k_grid_types + k_grid_fields + "\n// ---- user source\n" +
                            source + "\n" + k_grid_kernels;
@@ -653,6 +928,15 @@ static int grid_compile(const char *source, int dim, int dof, int stencil, int b
                               "-DNK_GRID_SET=" + std::to_string(gset), std::string("-DNK_GRID_DIRECT=") + (direct ? "1" : "0")};
   std::vector<const char *> opts = {"--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-std=c++17"};
   for (const std::string &d : defs) opts.push_back(d.c_str());
+  std::string zdefs[6];
+  if (cut.any()) {
+    const char *const zn[3] = {"OWN", "LO", "HI"};
+    for (int z = 0; z < 3; ++z) {
+      zdefs[2 * z] = std::string("-DNK_ZORD_") + zn[z] + "=" + std::to_string(cut.zord[z]);
+      zdefs[2 * z + 1] = std::string("-DNK_ZGRP_") + zn[z] + "=" + std::to_string(cut.zgrp[z]);
+    }
+    for (const std::string &d : zdefs) opts.push_back(d.c_str());
+  }
   // the same source for the same stencil with the same options gives the same code object: problems created again (another grid
   // size, another context) skip the compiler. The key holds all that varies between two programs: the options, the stencil's
   // lines and the user's source (the rest of the text is the same for all)
@@ -685,13 +969,13 @@ static bool grid_fill_direct() {   // (read at every create: tools/grid_problem_
 
 // compile only (no device needed): both programs
 static int grid_compile_check(const char *source, int dim, int dof, int stencil, int boundary, int nparams, int nfields,
-                              int64_t *code_bytes) {
+                              int64_t *code_bytes, int nranks = 1, int rank = 0) {
   std::vector<char> code;
   std::string log;
   int64_t total = 0;
   for (int gset : {GSET_F, GSET_JAC}) {
     log.clear();
-    NK_TRY(grid_compile(source, dim, dof, stencil, boundary, nparams, nfields, gset, grid_fill_direct(), &code, &log));
+    NK_TRY(grid_compile(source, dim, dof, stencil, boundary, nparams, nfields, gset, grid_fill_direct(), &code, &log, nranks, rank));
     total += (int64_t)code.size();
   }
   if (code_bytes) *code_bytes = total;
@@ -711,12 +995,12 @@ extern "C" int nk_grid_fields_compile_check(const char *source, int dim, int dof
 
 // the code object of one program (jac = 0: the residual and JVP kernels; 1: the Jacobian fill) for inspection
 static int grid_code_object(const char *source, int dim, int dof, int stencil, int boundary, int nparams, int nfields, int jac,
-                            void *buf, int64_t capacity, int64_t *bytes) {
+                            void *buf, int64_t capacity, int64_t *bytes, int nranks = 1, int rank = 0) {
   NK_REQUIRE(bytes, "NULL argument");
   std::vector<char> code;
   std::string log;
   NK_TRY(grid_compile(source, dim, dof, stencil, boundary, nparams, nfields, jac != 0 ? GSET_JAC : GSET_F, grid_fill_direct(), &code,
-                      &log));
+                      &log, nranks, rank));
   *bytes = (int64_t)code.size();
   if (!buf) return NK_OK;
   NK_REQUIRE(capacity >= *bytes, "buffer of %lld bytes, the code object has %lld", (long long)capacity, (long long)*bytes);
@@ -737,7 +1021,25 @@ extern "C" int nk_grid_fields_code_object(const char *source, int dim, int dof, 
   return grid_code_object(source, dim, dof, stencil, boundary, nparams, nfields, jac, buf, capacity, bytes);
 }
 
+// the programs of rank `rank` of `nranks`: (nranks, rank) decide which sides of the outermost axis are cuts and the zone order;
+// nranks = 1 gives the programs of the calls above
+extern "C" int nk_grid_slab_compile_check(const char *source, int dim, int dof, int stencil, int boundary, int nparams, int nfields,
+                                          int nranks, int rank, int64_t *code_bytes) {
+  NK_REQUIRE(dim == 2 || dim == 3, "dim = %d is neither 2 nor 3", dim);
+  return grid_compile_check(source, dim, dof, stencil, boundary, nparams, nfields, code_bytes, nranks, rank);
+}
+extern "C" int nk_grid_slab_code_object(const char *source, int dim, int dof, int stencil, int boundary, int nparams, int nfields,
+                                        int nranks, int rank, int jac, void *buf, int64_t capacity, int64_t *bytes) {
+  NK_REQUIRE(dim == 2 || dim == 3, "dim = %d is neither 2 nor 3", dim);
+  return grid_code_object(source, dim, dof, stencil, boundary, nparams, nfields, jac, buf, capacity, bytes, nranks, rank);
+}
+
 // ----------------------------------------------------------------------------- the problem object
+// the device text's nk_slab, member for member: one kernel argument of a program with a cut
+struct grid_slab_arg {
+  int l0 = 0, nl = 0, gz = 0, pad = 0;
+  const double *ulo = nullptr, *uhi = nullptr, *vlo = nullptr, *vhi = nullptr, *alo = nullptr, *ahi = nullptr;
+};
 struct nk_grid_state {
   nk_ctx *ctx = nullptr;
   int nx = 0, ny = 0, nz = 0 /* 0: a 2-D problem */, dof = 0, np = 0, nfields = 0;
@@ -746,6 +1048,14 @@ struct nk_grid_state {
   double *d_params = nullptr;   // np doubles (at least one allocated): the source's p
   double *d_fields = nullptr;   // nfields·nn doubles, field k of node m at k·nn + m (NULL without fields); zero at creation
   nk_csr *pattern = nullptr;    // the problem's user_pattern
+  // several ranks (nranks > 1; on one rank the slab is the grid and none of the rest is used)
+  int64_t l0 = 0, l1 = 0, nn_loc = 0;   // the slab's lines (planes) of the outermost axis and its nodes
+  bool cut = false, cut_lo = false, cut_hi = false;
+  int below = -1, above = -1;           // the ranks the ghost lines come from
+  int64_t ghost = 0;                    // ghost nodes per component and cut: radius lines
+  grid_slab_arg slab;                   // what the kernels of a program with a cut are handed
+  nk_halo halo_u, halo_v, halo_a;       // ghost lines of u, of v (the JVP reads both: two receive areas) and of the fields
+  hipEvent_t ev = nullptr;              // orders an exchange against a stream that is not the context's
 };
 
 void nk_grid_state_destroy(nk_grid_state *S) {
@@ -755,6 +1065,10 @@ void nk_grid_state_destroy(nk_grid_state *S) {
   hipFree(S->d_params);
   hipFree(S->d_fields);
   nk_csr_destroy(S->pattern);
+  nk_halo_free(&S->halo_u);
+  nk_halo_free(&S->halo_v);
+  nk_halo_free(&S->halo_a);
+  if (S->ev) hipEventDestroy(S->ev);
   delete S;
 }
 
@@ -762,7 +1076,7 @@ void nk_grid_state_destroy(nk_grid_state *S) {
 // nk_problem_jvp_dev and nk_problem_jac_values_dev open one around the callback) the launch carries start / stop events like
 // every NK_LAUNCH, so the generated kernels are timed by the same clock as the built-in ones.
 static int grid_launch(nk_grid_state *S, hipFunction_t fn, void **args, void *stream) {
-  const unsigned blocks = (unsigned)(((int64_t)S->nx * S->ny * (S->nz > 0 ? S->nz : 1) + 255) / 256);
+  const unsigned blocks = (unsigned)((S->nn_loc + 255) / 256);   // (one rank: the slab is the grid)
   hipEvent_t e0, e1;
   hipError_t e;
   if (S->ctx->prof.on && (hipStream_t)stream == S->ctx->stream && nk_prof_next(S->ctx, &e0, &e1))
@@ -773,28 +1087,61 @@ static int grid_launch(nk_grid_state *S, hipFunction_t fn, void **args, void *st
 }
 
 // the callbacks of the problem: launches of the generated kernels on the stream they are handed. The argument list is
-// nx, ny, [nz,] p, [fields,] and the kernel's own vectors: the sizes, then what the problem owns, then `rest`
+// nx, ny, [nz,] [the slab,] p, [fields,] and the kernel's own vectors: the sizes, then what the problem owns, then `rest`
 static int grid_launch_args(nk_grid_state *S, hipFunction_t fn, std::initializer_list<void *> rest, void *stream) {
-  void *args[10];
+  void *args[11];
   int n = 0;
   args[n++] = &S->nx;
   args[n++] = &S->ny;
   if (S->nz > 0) args[n++] = &S->nz;
+  if (S->cut) args[n++] = &S->slab;
   args[n++] = &S->d_params;
   if (S->nfields > 0) args[n++] = &S->d_fields;
   for (void *a : rest) args[n++] = a;
   return grid_launch(S, fn, args, stream);
 }
+// Where the low and the high ghost lines of a plan are in its receive area, after an exchange (the peer transport alternates
+// between two areas). The layout rule of the built-in grid problems: a peer's block is [what serves as my low ghost][what
+// serves as my high ghost], so with two ranks and a periodic axis, where the one peer is both, the high lines come second
+static void grid_ghost_ptrs(const nk_grid_state *S, const nk_halo &H, int ncomp, const double **lo, const double **hi) {
+  *lo = S->cut_lo ? H.d_recv + H.recv_off[S->below] : nullptr;
+  *hi = S->cut_hi ? H.d_recv + H.recv_off[S->above] + (S->cut_lo && S->above == S->below ? S->ghost * ncomp : 0) : nullptr;
+}
+// The exchanges of a callback run on the context's stream (nk_halo_exchange: both transports, counted in stats.halo_exchanges).
+// Every caller in the library hands that stream; another one is ordered against it with an event on both sides
+static int grid_stream_order(nk_grid_state *S, hipStream_t from, hipStream_t to) {
+  if (from == to) return NK_OK;
+  if (!S->ev) NK_HIP(hipEventCreateWithFlags(&S->ev, hipEventDisableTiming));
+  NK_HIP(hipEventRecord(S->ev, from));
+  NK_HIP(hipStreamWaitEvent(to, S->ev, 0));
+  return NK_OK;
+}
+// what a callback reads across the cuts, exchanged before its launch: u, and v for the JVP
+static int grid_exchange(nk_grid_state *S, const double *u, const double *v, void *stream) {
+  if (!S->cut) return NK_OK;
+  nk_ctx *ctx = S->ctx;
+  NK_TRY(grid_stream_order(S, (hipStream_t)stream, ctx->stream));
+  NK_TRY(nk_halo_exchange(ctx, &S->halo_u, u));
+  grid_ghost_ptrs(S, S->halo_u, S->dof, &S->slab.ulo, &S->slab.uhi);
+  if (v) {
+    NK_TRY(nk_halo_exchange(ctx, &S->halo_v, v));
+    grid_ghost_ptrs(S, S->halo_v, S->dof, &S->slab.vlo, &S->slab.vhi);
+  }
+  return grid_stream_order(S, ctx->stream, (hipStream_t)stream);
+}
 static int grid_cb_residual(void *user, const double *u, double *f, void *stream) {
   nk_grid_state *S = (nk_grid_state *)user;
+  if (grid_exchange(S, u, nullptr, stream) != NK_OK) return 1;
   return grid_launch_args(S, S->fn_res, {&u, &f}, stream);
 }
 static int grid_cb_jvp(void *user, const double *v, const double *u, double *jv, void *stream) {
   nk_grid_state *S = (nk_grid_state *)user;
+  if (grid_exchange(S, u, v, stream) != NK_OK) return 1;
   return grid_launch_args(S, S->fn_jvp, {&u, &v, &jv}, stream);
 }
 static int grid_cb_jac(void *user, const double *u, double *vals, void *stream) {
   nk_grid_state *S = (nk_grid_state *)user;
+  if (grid_exchange(S, u, nullptr, stream) != NK_OK) return 1;
   const int32_t *rowptr = S->pattern->d_rowptr;
   return grid_launch_args(S, S->fn_jac, {&u, &rowptr, &vals}, stream);
 }
@@ -810,7 +1157,7 @@ int nk_grid_set_params(nk_problem *P, const double *params, int nparams) {
   return NK_OK;
 }
 
-// field k of a problem with fields: its nn doubles on the device
+// field k of a problem with fields: its doubles on the device, one per node of the rank's slab (one rank: of the grid)
 static int grid_field_ptr(nk_problem *P, int k, double **d_field, size_t *bytes) {
   NK_REQUIRE(P, "NULL argument");
   NK_REQUIRE(P->grid, "the problem is not a compiled grid problem (kind %d): it has no fields", (int)P->kind);
@@ -818,9 +1165,15 @@ static int grid_field_ptr(nk_problem *P, int k, double **d_field, size_t *bytes)
   NK_REQUIRE(S->nfields > 0, "the problem was created with nfields = %d: it has no fields (nk_problem_create_grid_fields)",
              S->nfields);
   NK_REQUIRE(k >= 0 && k < S->nfields, "field k = %d outside 0..%d", k, S->nfields - 1);
-  const size_t nn = (size_t)S->nx * S->ny * (S->nz > 0 ? S->nz : 1);
+  const size_t nn = (size_t)S->nn_loc;
   *d_field = S->d_fields + (size_t)k * nn;
   *bytes = nn * sizeof(double);
+  return NK_OK;
+}
+static int grid_exchange_fields(nk_grid_state *S) {
+  if (!S->cut || S->nfields == 0) return NK_OK;
+  NK_TRY(nk_halo_exchange(S->ctx, &S->halo_a, S->d_fields));
+  grid_ghost_ptrs(S, S->halo_a, S->nfields, &S->slab.alo, &S->slab.ahi);
   return NK_OK;
 }
 extern "C" int nk_problem_set_field(nk_problem *P, int k, const double *data, int memspace) {
@@ -831,6 +1184,7 @@ extern "C" int nk_problem_set_field(nk_problem *P, int k, const double *data, in
   NK_REQUIRE(memspace == NK_HOST || memspace == NK_DEVICE, "memspace = %d is neither NK_HOST nor NK_DEVICE", memspace);
   NK_HIP(hipSetDevice(P->grid->ctx->device));
   NK_HIP(nk_memcpy(P->grid->ctx, d, data, bytes, memspace == NK_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice));
+  NK_TRY(grid_exchange_fields(P->grid));   // several ranks: the ghost lines of the fields, once, here (collective)
   P->params_version++;
   nk_problem_invalidate(P);   // a Jacobian cached for the same u belongs to the old field
   return NK_OK;
@@ -846,28 +1200,84 @@ extern "C" int nk_problem_get_field(nk_problem *P, int k, double *out, int memsp
   return NK_OK;
 }
 
+// Several ranks: the halo plans of a slab. The last `radius` lines (planes) of every component go up, the first `radius` down
+// — to the rank above they are its low ghost lines, to the rank below its high ones — component-major, radius·line nodes per
+// component. A peer is sent first what serves as its low ghost, then what serves as its high one (two ranks, periodic: both).
+// One plan per vector a launch reads (nk_halo has one receive area) and one over all fields; the fields' ghost lines are
+// exchanged here once, so that they are the zeros of the fields themselves.
+static int grid_setup_halos(nk_grid_state *S, int dim, int stencil, int boundary) {
+  nk_ctx *ctx = S->ctx;
+  const int R = ctx->nranks, r = ctx->rank;
+  const grid_stencil *st = grid_find(dim, stencil);
+  grid_sides sd;
+  NK_TRY(grid_decode_boundary(dim, boundary, &sd));
+  grid_cut cut;
+  NK_TRY(grid_cut_make(dim, sd, R, r, &cut));
+  const int radius = grid_radius(*st);
+  const int64_t nl = S->l1 - S->l0, line = S->nn_loc / nl;
+  S->cut_lo = cut.lo == GRID_BC_HALO;
+  S->cut_hi = cut.hi == GRID_BC_HALO;
+  S->cut = cut.any();
+  S->below = S->cut_lo ? (r > 0 ? r - 1 : R - 1) : -1;
+  S->above = S->cut_hi ? (r < R - 1 ? r + 1 : 0) : -1;
+  S->ghost = radius * line;
+  S->slab.l0 = (int)S->l0;
+  S->slab.nl = (int)nl;
+  S->slab.gz = (int)S->ghost;
+  auto plan = [&](int ncomp, nk_halo *H) {
+    std::vector<std::vector<int32_t>> send((size_t)R);
+    std::vector<int64_t> recv((size_t)R, 0);
+    auto push_lines = [&](std::vector<int32_t> &v, int64_t first) {   // `radius` lines from line `first` of the slab on
+      for (int c = 0; c < ncomp; ++c)
+        for (int64_t m = 0; m < S->ghost; ++m) v.push_back((int32_t)(c * S->nn_loc + first * line + m));
+    };
+    if (S->above >= 0) push_lines(send[S->above], nl - radius);
+    if (S->below >= 0) push_lines(send[S->below], 0);
+    if (S->below >= 0) recv[S->below] += S->ghost * ncomp;
+    if (S->above >= 0) recv[S->above] += S->ghost * ncomp;
+    return nk_halo_setup(ctx, H, send, recv);
+  };
+  NK_TRY(plan(S->dof, &S->halo_u));
+  NK_TRY(plan(S->dof, &S->halo_v));
+  if (S->nfields > 0) {
+    NK_TRY(plan(S->nfields, &S->halo_a));
+    NK_TRY(nk_halo_exchange(ctx, &S->halo_a, S->d_fields));
+    grid_ghost_ptrs(S, S->halo_a, S->nfields, &S->slab.alo, &S->slab.ahi);
+  }
+  return NK_OK;
+}
+
+extern "C" int nk_problem_grid_slab(nk_problem *P, int64_t *line_begin, int64_t *line_end) {
+  NK_REQUIRE(P && line_begin && line_end, "NULL argument");
+  NK_REQUIRE(P->grid, "the problem is not a compiled grid problem (kind %d)", (int)P->kind);
+  *line_begin = P->grid->l0;
+  *line_end = P->grid->l1;
+  return NK_OK;
+}
+
 // dim = 2: nz is not read (nk_problem_create_grid); dim = 3: nk_problem_create_grid3
 static int grid_create(nk_ctx *ctx, const char *source, int dim, int64_t nx, int64_t ny, int64_t nz, int dof, int stencil,
                        int boundary, const double *params, int nparams, int nfields, nk_problem **out) {
   NK_REQUIRE(ctx && source && out, "NULL argument");
   NK_REQUIRE(params || nparams == 0, "NULL params with nparams = %d", nparams);
   NK_REQUIRE(nfields >= 0 && nfields <= 4, "nfields = %d outside 0..4 (read-only fields of one double per node)", nfields);
-  if (ctx->nranks > 1)
-    NK_FAIL(NK_E_UNSUPPORTED, "compiled grid problems run on one rank (this context has %d): no halo exchange is generated",
-            ctx->nranks);
   NK_HIP(hipSetDevice(ctx->device));
   if (dim == 2) nz = 1;
-  // the pattern first: it validates the geometry before anything is compiled
-  int64_t nnz = 0;
-  NK_TRY(grid_pattern(dim, nx, ny, nz, dof, stencil, boundary, nullptr, nullptr, &nnz));
-  const int64_t n = nx * ny * nz * dof;
-  std::vector<int32_t> rp((size_t)n + 1), ci((size_t)nnz);
-  NK_TRY(grid_pattern(dim, nx, ny, nz, dof, stencil, boundary, rp.data(), ci.data(), &nnz));
+  const int R = ctx->nranks, r = ctx->rank;
+  // the pattern first: it validates the geometry (several ranks: and the slabs) before anything is compiled. On one rank the
+  // slab is the grid, its pattern nk_grid_pattern's and its programs the ones without a cut
+  int64_t nnz = 0, l0 = 0, l1 = 0;
+  NK_TRY(grid_slab_pattern(dim, nx, ny, nz, dof, stencil, boundary, R, r, &l0, &l1, nullptr, nullptr, &nnz));
+  const int64_t line = dim == 3 ? nx * ny : nx, nn_loc = line * (l1 - l0);
+  const int64_t n = nn_loc * dof, n_global = nx * ny * nz * dof;
+  std::vector<int32_t> rp((size_t)n + 1);
+  std::vector<int64_t> gc((size_t)nnz);
+  NK_TRY(grid_slab_pattern(dim, nx, ny, nz, dof, stencil, boundary, R, r, &l0, &l1, rp.data(), gc.data(), &nnz));
   std::vector<char> code_f, code_j;
   std::string log;
-  NK_TRY(grid_compile(source, dim, dof, stencil, boundary, nparams, nfields, GSET_F, false, &code_f, &log));
+  NK_TRY(grid_compile(source, dim, dof, stencil, boundary, nparams, nfields, GSET_F, false, &code_f, &log, R, r));
   log.clear();
-  NK_TRY(grid_compile(source, dim, dof, stencil, boundary, nparams, nfields, GSET_JAC, grid_fill_direct(), &code_j, &log));
+  NK_TRY(grid_compile(source, dim, dof, stencil, boundary, nparams, nfields, GSET_JAC, grid_fill_direct(), &code_j, &log, R, r));
 
   nk_grid_state *S = new nk_grid_state();
   auto guard = nk_make_guard(S, nk_grid_state_destroy);
@@ -878,6 +1288,9 @@ static int grid_create(nk_ctx *ctx, const char *source, int dim, int64_t nx, int
   S->dof = dof;
   S->np = nparams;
   S->nfields = nfields;
+  S->l0 = l0;
+  S->l1 = l1;
+  S->nn_loc = nn_loc;
   if (hipModuleLoadData(&S->mod_f, code_f.data()) != hipSuccess || hipModuleLoadData(&S->mod_jac, code_j.data()) != hipSuccess)
     NK_FAIL(NK_E_HIP, "hipModuleLoadData failed");
   if (hipModuleGetFunction(&S->fn_res, S->mod_f, dim == 3 ? "nk_grid3_residual" : "nk_grid_residual") != hipSuccess ||
@@ -887,18 +1300,19 @@ static int grid_create(nk_ctx *ctx, const char *source, int dim, int64_t nx, int
   NK_TRY(nk_dev_alloc(&S->d_params, (size_t)(nparams > 0 ? nparams : 1)));
   if (nparams > 0) NK_HIP(nk_memcpy(ctx, S->d_params, params, (size_t)nparams * sizeof(double), hipMemcpyHostToDevice));
   if (nfields > 0) {   // zero until nk_problem_set_field: nothing is ever read uninitialised
-    const size_t cnt = (size_t)nfields * (size_t)(n / dof);
+    const size_t cnt = (size_t)nfields * (size_t)nn_loc;
     NK_TRY(nk_dev_alloc(&S->d_fields, cnt));
     NK_HIP(nk_memset(ctx, S->d_fields, 0, cnt * sizeof(double)));
   }
-  std::vector<int64_t> gc(ci.begin(), ci.end());
-  NK_TRY(nk_csr_create_local(ctx, n, n, 0, rp, gc, nullptr, &S->pattern));
+  if (R > 1) NK_TRY(grid_setup_halos(S, dim, stencil, boundary));   // (collective, like the pattern's own plan below)
+  NK_TRY(nk_csr_create_local(ctx, n, n_global, dof * line * l0, rp, gc, nullptr, &S->pattern));
 
   nk_problem *P = new nk_problem();
   P->ctx = ctx;
   P->kind = NK_PROBLEM_USER;
-  P->n_local = P->n_global = n;
-  P->row_begin = 0;
+  P->n_local = n;
+  P->n_global = n_global;
+  P->row_begin = dof * line * l0;
   P->nparams = nparams;
   for (int i = 0; i < nparams && i < 8; ++i) P->params[i] = params[i];
   P->cb.residual = grid_cb_residual;

@@ -162,3 +162,9 @@ def gather_vector(local, n_global: int, row_begin: int):
     for b, a in parts:
         out[b:b + a.size] = a
     return out
+
+
+def gather_grid(P, local):
+    """The whole vector of a compiled grid problem in one-rank order (c·nn + node) on every rank, from every rank's local
+    vector (component-major on its slab)."""
+    return P.to_full(gather_vector(local, P.n_global, P.row_begin))

@@ -10,7 +10,14 @@ allow (allocation granule 8, min(8, 512 // allocation)) no lower than the parent
 spills. Exit status 1 if a row fails.
 
 Each build is read in a child process of its own (two libraries of one name do not share a process); the problems are this
-checkout's tables in both."""
+checkout's tables in both.
+
+    python tools/grid_resources_ab.py --slab [--out profiles/<name>.txt]
+
+The programs of a grid split over several ranks (nk_grid_slab_code_object) beside the one-rank program of the same problem, this
+build alone: VGPRs and LDS of rank 0, the middle rank and the last rank of three and of rank 0 of two. A cut adds the address
+select of the points that can leave through it and, in the fill, the zone counting; the table shows what that costs in
+registers. Exit status 1 if a cut program has a private segment or spills, or more LDS than its one-rank program."""
 import argparse
 import json
 import os
@@ -98,14 +105,70 @@ def collect(root):
     json.dump(rows, sys.stdout)
 
 
+def notes_of(code, names, tmp):
+    """{kernel: {private, vgprs, agprs, spills, lds}} of a code object"""
+    path = os.path.join(tmp, "k.co")
+    with open(path, "wb") as fh:
+        fh.write(code)
+    notes = subprocess.run([READELF, "--notes", path], capture_output=True, text=True, check=True).stdout
+    out = {}
+    for block in re.split(r"\n\s*- \.", notes)[1:]:
+        get = lambda key: re.search(r"\.%s:\s+(\w+)" % key, block)
+        if get("name") and get("private_segment_fixed_size") and get("name").group(1) in names:
+            out[get("name").group(1)] = {k: int(get(key).group(1)) if get(key) else 0
+                                         for k, key in (("private", "private_segment_fixed_size"), ("vgprs", "vgpr_count"),
+                                                        ("agprs", "agpr_count"), ("spills", "vgpr_spill_count"),
+                                                        ("lds", "group_segment_fixed_size"))}
+    return out
+
+
+def slab_table(out_path):
+    """cut programs beside the one-rank program of every problem of the five tables (the staged fill)"""
+    import ctypes as C
+    sys.path.insert(0, ROOT)
+    from nonlinearsolve_jl_amd import _lib as L
+    lib = L.lib()
+    ranks = ((1, 0), (3, 0), (3, 1), (3, 2), (2, 0))
+    lines = ["# problem | kernel | one rank: VGPRs, LDS | " + " | ".join(f"rank {r} of {R}: VGPRs, LDS" for R, r in ranks[1:]) +
+             " | verdict"]
+    bad = 0
+    with tempfile.TemporaryDirectory() as tmp:
+        for table, name, source, dim, dof, stencil, boundary, nparams, nfields in problems():
+            for jac in (0, 1):
+                rows = []
+                for R, r in ranks:
+                    args = (source.encode(), dim, dof, STENCIL_ID[stencil], boundary_code(boundary), nparams, nfields, R, r, jac)
+                    nb = C.c_int64()
+                    assert lib.nk_grid_slab_code_object(*args, None, 0, C.byref(nb)) == 0, lib.nk_last_error()
+                    buf = C.create_string_buffer(nb.value)
+                    assert lib.nk_grid_slab_code_object(*args, buf, nb.value, C.byref(nb)) == 0
+                    rows.append(notes_of(buf.raw[:nb.value], KERNELS[dim][jac], tmp))
+                for kernel in KERNELS[dim][jac]:
+                    ok = all(x[kernel]["private"] == 0 and x[kernel]["spills"] == 0 and x[kernel]["lds"] <= rows[0][kernel]["lds"]
+                             for x in rows)
+                    bad += not ok
+                    lines.append(f"{table}/{name} | {kernel} | " + " | ".join(f"{x[kernel]['vgprs']}, {x[kernel]['lds']}" for x in rows)
+                                 + f" | {'ok' if ok else 'FAIL'}")
+    lines.append(f"# {len(lines) - 1} kernels, {bad} failed (a private segment, spills, or more LDS than on one rank)")
+    text = "\n".join(lines) + "\n"
+    sys.stdout.write(text)
+    if out_path:
+        with open(out_path, "w", encoding="utf-8") as fh:
+            fh.write(text)
+    return 1 if bad else 0
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--slab", action="store_true", help="the cut programs beside the one-rank programs of this build")
     ap.add_argument("--parent", help="root of the other checkout (built)")
     ap.add_argument("--out", help="write the table here as well")
     ap.add_argument("--collect", help=argparse.SUPPRESS)
     a = ap.parse_args()
     if a.collect:
         return collect(a.collect)
+    if a.slab:
+        return slab_table(a.out)
     if not a.parent:
         ap.error("--parent is required")
     both = [json.loads(subprocess.run([sys.executable, os.path.abspath(__file__), "--collect", os.path.abspath(r)],
