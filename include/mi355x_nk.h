@@ -251,8 +251,9 @@ typedef struct {
   double  ls_c1, ls_rho_hi, ls_rho_lo;
   int32_t ls_order;             /* 2 | 3 */
   int32_t ls_maxiters;
-  /* --- built-in multigrid V-cycle as the Krylov right preconditioner (BRATU2D, single rank), re-linearised for every
-   *     new Jacobian like `precs(A, p)`: mg_nu smoothing steps (0 = off), coarsest grid side ≤ mg_coarse (0 → 31) */
+  /* --- built-in multigrid V-cycle as the Krylov right preconditioner (BRATU2D, BRUSSELATOR2D; compiled grid problems on one
+   *     rank), re-linearised for every new Jacobian like `precs(A, p)`: mg_nu smoothing steps (0 = off), coarsest grid side
+   *     ≤ mg_coarse (0 → the problem kind's default: nk_gmres_set_multigrid_preconditioner) */
   int32_t mg_nu;
   int32_t mg_coarse;
   /* --- concrete Jacobian of the built-in problems: 0 = closed-form values (what `f.jac` would supply), 1 = the
@@ -773,8 +774,44 @@ int nk_gmres_get_chebyshev_interval(nk_gmres *G, double *lambda_min, double *lam
  * (level operators by rediscretisation, bilinear transfers between non-nested grids, `nu` Chebyshev smoothing steps before
  * and after, banded LU on the coarsest grid of side ≤ coarse_max; 0 → 2 and 31) — the device counterpart of an algebraic-
  * multigrid `precs` (docs/src/tutorials/large_systems.md:244-316). Mesh-independent Krylov iteration counts. Call it again
- * for every new linearisation point; nu ≤ 0 or P == NULL removes it. Single rank. */
+ * for every new linearisation point; nu ≤ 0 or P == NULL removes it. Single rank.
+ *
+ * A compiled grid problem (nk_problem_create_grid …, one rank; more ranks: NK_E_INVALID) gets the same V-cycle for its own PDE
+ * (csrc/nk_gridmg.hip): 2-D and 3-D, every stencil, dof <= 4, fields, every combination of side kinds.
+ *   levels     by rediscretisation: level l is the same problem — same source, options and p, the fine problem's code objects
+ *              loaded again — on smaller sides; A_l is its Jacobian fill at u_l = R u_{l−1}, its fields are the restriction of
+ *              the finer level's. Every call restricts u and the fields, copies the current p, refills every A_l and refactors
+ *              the coarsest level, so nk_problem_set_field / nk_problem_set_params between solves are picked up.
+ *   CONTRACT   a source used with the multigrid takes its spacing from s.nx, s.ny, s.nz (the level it runs on), not from p.
+ *              A source that does not follow this gets a poor preconditioner, not a wrong answer; the AMG object remains for it.
+ *   geometry   per axis (nk_grid_mg_axis), in units of the fine spacing: a side's offset a is 1 (Dirichlet-0: the wall is one
+ *              spacing outside the outermost node), 0 (mirror_node) or 1/2 (mirror_face); L = n − 1 + a_lo + a_hi, node i sits at
+ *              a_lo + i, nc = floor(L/2 + 1.5 − a_lo − a_hi); periodic: L = n, nc = floor(n/2 + 0.5). An axis is coarsened while
+ *              n > coarse_max and nc >= the stencil's smallest side (3; radius 2: 5); the hierarchy ends when none is.
+ *   transfers  tensor products of the 1-D tables: linear interpolation at the nodes' positions, restriction = its row-normalised
+ *              transpose (residuals, u and fields alike), component by component.
+ *   smoother   nu Chebyshev steps on D⁻¹A_l over [rho/4, rho], rho = max_i sum_j |a_ij| / |a_ii| (computed at every call); a zero
+ *              or non-finite diagonal entry fails the call with the level and the row. Coarsest level: the banded LU.
+ * coarse_max < 3 → 8 for a compiled grid problem. A solver object holds one hierarchy, that of its last call: a call with a
+ * compiled grid problem builds it again when the problem, nu or coarse_max differ from the call that built it, and a call with a
+ * problem of the other kind (built-in after compiled, or the reverse) replaces it. For BRATU2D and BRUSSELATOR2D the hierarchy is
+ * built by the first call and later calls only re-linearise it: nu, coarse_max and P of those calls are not looked at again. */
+
 int nk_gmres_set_multigrid_preconditioner(nk_gmres *G, nk_problem *P, const double *u, int memspace, int nu, int coarse_max);
+/* The folded prolongation table of one axis of n nodes with the side kinds (lo_kind, hi_kind) onto its coarser axis of *nc
+ * nodes (host only, like nk_grid_pattern): fine node i takes w[2i] of coarse node idx[2i] and w[2i + 1] of idx[2i + 1], where
+ * t = (a_lo + i)·(nc − 1 + a_lo + a_hi)/L − a_lo (periodic: i·nc/n), J0 = floor(t), the weights 1 − (t − J0) on J0 and t − J0 on
+ * J0 + 1, a weight within 1e-12 of 0 or 1 snapped to the node. A coarse index outside 0 … nc−1 goes through the grid's own side
+ * map (Dirichlet-0 drops it, periodic wraps, the mirrors reflect); two weights landing on one coarse node are added into the
+ * first entry. A dropped, merged or zero-weight entry has the index −1 and the weight 0. idx = w = NULL: only *nc. */
+int nk_grid_mg_axis(int64_t n, int lo_kind, int hi_kind, int64_t *nc, int32_t *idx, double *w);
+/* The hierarchy behind nk_gmres_set_multigrid_preconditioner on a compiled grid problem: *levels, and for the first `cap` of
+ * them (arrays nullable) the sides nx, ny, nz (3 per level; 2-D: nz = 1), the unknowns, the non-zeros of A_l and rho.
+ * nk_gmres_multigrid_level_matrix: A_l itself (owned by the hierarchy: do not destroy; valid until the solver object goes).
+ * nk_gmres_multigrid_level_field: a copy of field k of level l (n/dof doubles). */
+int nk_gmres_multigrid_levels(nk_gmres *G, int *levels, int cap, int64_t *sides, int64_t *n, int64_t *nnz, double *rho);
+int nk_gmres_multigrid_level_matrix(nk_gmres *G, int level, nk_csr **out);
+int nk_gmres_multigrid_level_field(nk_gmres *G, int level, int k, double *out, int memspace);
 /* Solve A x = b. use_x0 = 0 ⇒ zero initial guess (our protocol); 1 ⇒ x holds x0.
  * Stop when ‖r‖₂ ≤ atol + rtol‖r0‖₂ or after maxiter Arnoldi steps; fixed_iters>0 overrides both. */
 int nk_gmres_solve(nk_gmres *G, const double *b, double *x, int memspace, int use_x0,

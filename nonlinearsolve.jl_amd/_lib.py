@@ -244,6 +244,10 @@ SIGNATURES = {
     "nk_device_copy": (_I, [_P, _P, _P, _L, _I]),
     "nk_gmres_set_chebyshev_preconditioner": (_I, [_P, _I, _D, _D, _D]),
     "nk_gmres_set_multigrid_preconditioner": (_I, [_P, _P, _P, _I, _I, _I]),
+    "nk_grid_mg_axis": (_I, [_L, _I, _I, C.POINTER(_L), _P, _P]),
+    "nk_gmres_multigrid_levels": (_I, [_P, C.POINTER(_I), _I, _P, _P, _P, _P]),
+    "nk_gmres_multigrid_level_matrix": (_I, [_P, _I, _PP]),
+    "nk_gmres_multigrid_level_field": (_I, [_P, _I, _I, _P, _I]),
     "nk_gmres_get_chebyshev_interval": (_I, [_P, C.POINTER(_D), C.POINTER(_D)]),
     "nk_gmres_solve": (_I, [_P, _P, _P, _I, _I, _D, _D, _I, _I, C.POINTER(GmresInfo)]),
     "nk_lu_create": (_I, [_P, _PP]),

@@ -531,6 +531,21 @@ def grid_pattern(nx: int, ny: int, dof: int = 1, stencil: str = "star", boundary
     return rowptr, colind
 
 
+def grid_mg_axis(n: int, lo: str = "dirichlet", hi: str = "dirichlet"):
+    """(nc, idx, w): the folded prolongation table of one axis of n nodes with the side kinds lo, hi ("dirichlet", "periodic",
+    "mirror_node", "mirror_face") onto the coarser axis of nc nodes that the multigrid `precs` of a compiled grid problem builds
+    (MultigridPrecs): fine node i takes w[i, 0] of coarse node idx[i, 0] and w[i, 1] of idx[i, 1]; a dropped entry (outside a
+    Dirichlet side, merged into the other one at a mirror, or of weight 0) has the index −1 and the weight 0. Host only."""
+    for k in (lo, hi):
+        if k not in L.GRID_SIDE_KINDS:
+            raise ValueError(f"side kind {k!r}: expected one of {sorted(L.GRID_SIDE_KINDS)}")
+    nc = C.c_int64()
+    idx, w = np.empty((int(n), 2), dtype=np.int32), np.empty((int(n), 2), dtype=np.float64)
+    check(L.lib().nk_grid_mg_axis(int(n), L.GRID_SIDE_KINDS[lo], L.GRID_SIDE_KINDS[hi], C.byref(nc), C.c_void_p(idx.ctypes.data),
+                                  C.c_void_p(w.ctypes.data)))
+    return nc.value, idx, w
+
+
 def _slab_lines(n_outer: int, nranks: int):
     """the first line (plane) of every rank's slab and the end: nk_partition_range(n_outer, 1, R, r)"""
     return [partition_range(n_outer, 1, nranks, r)[0] for r in range(nranks)] + [n_outer]
@@ -694,7 +709,11 @@ def CompiledGridProblem(source: str, nx: int, ny: int, dof: int = 1, stencil: st
     zero-flux wall of a cell-centred grid). Axes are independent; a point that leaves through a Dirichlet side of any axis
     reads 0. A mirrored ghost is another unknown: J is the true dF/du, the partials of the stencil points of a row that land
     on one node are added into one entry, and u, v and the fields are read at the mirrored node. A channel:
-    boundary={"x": "periodic", "y": "mirror_face"}. P.boundary keeps what was passed."""
+    boundary={"x": "periodic", "y": "mirror_face"}. P.boundary keeps what was passed.
+    Multigrid: on one rank KrylovJL_GMRES(precs=MultigridPrecs(nu, coarse_max)) and GMRES.set_multigrid_preconditioner take a
+    compiled grid problem; the levels are this problem on smaller grids — the same source, the same code objects, p copied, u
+    and the fields restricted. A source used that way takes its spacing from the site, h = 1/(s.nx + 1) and the like, not from p:
+    s.nx, s.ny[, s.nz] are the sides of the level the kernel runs on (see MultigridPrecs)."""
     ctx = ctx or default_context()
     st, bd = _grid_ids(stencil, boundary, 2 if nz is None else 3)
     params = [float(x) for x in params]
@@ -831,11 +850,23 @@ class ChebyshevPrecs:
 
 @dataclass
 class MultigridPrecs:
-    """`precs` for KrylovJL_GMRES on Bratu2D problems: one geometric multigrid V-cycle as the right preconditioner
-    (nu Chebyshev smoothing steps, coarsest grid side ≤ coarse_max, banded LU there) — the device counterpart of an
-    algebraic-multigrid `precs` (docs/src/tutorials/large_systems.md:244-316). Mesh-independent iteration counts."""
+    """`precs` for KrylovJL_GMRES on Bratu2D and Brusselator2D problems and on compiled grid problems: one geometric multigrid
+    V-cycle as the right preconditioner (nu Chebyshev smoothing steps, coarsest grid side ≤ coarse_max, banded LU there) — the
+    device counterpart of an algebraic-multigrid `precs` (docs/src/tutorials/large_systems.md:244-316). Mesh-independent
+    iteration counts.
+    CompiledGridProblem (one rank; more ranks raise NKError): 2-D and 3-D, every stencil, dof <= 4, fields, every combination of
+    side kinds. Level l is the same problem — same source, options and p, the fine problem's code objects — on smaller sides,
+    its matrix that problem's Jacobian fill at the restricted u, its fields the restricted fields; every new Jacobian restricts
+    u and the fields again, copies p, refills every level and refactors the coarsest, so set_field and set_p between solves are
+    picked up. CONTRACT: the source takes its spacing from s.nx, s.ny, s.nz (the level it runs on), not from p. A source that
+    does not gets a poor preconditioner, not a wrong answer; ObjectPrecs("amg") remains for it. Per axis (grid_mg_axis), in
+    units of the fine spacing: a side's offset a is 1 (dirichlet), 0 (mirror_node), 1/2 (mirror_face), L = n − 1 + a_lo + a_hi,
+    nc = floor(L/2 + 1.5 − a_lo − a_hi); periodic nc = floor(n/2 + 0.5); an axis is coarsened while n > coarse_max and nc >= 3
+    (radius 2: 5). Transfers: tensor products of linear interpolation at the nodes' positions and its row-normalised transpose.
+    Smoother: Chebyshev on D⁻¹A over [rho/4, rho], rho = max_i sum_j |a_ij|/|a_ii|. coarse_max < 3: the library's default for a
+    compiled grid problem, 8; coarse_max = None selects the problem kind's default."""
     nu: int = 2
-    coarse_max: int = 31
+    coarse_max: Optional[int] = None   # None: the problem kind's default — 31 for Bratu2D and Brusselator2D, 8 for a compiled grid problem
 
 
 @dataclass
@@ -1327,7 +1358,7 @@ def _options(alg, abstol, reltol, maxiters, maxtime, store_trace, termination_kw
         o.ls_order, o.ls_maxiters = int(lsr.order), int(lsr.maxiters)
     precs = getattr(ls, "precs", None)
     if isinstance(precs, MultigridPrecs):
-        o.mg_nu, o.mg_coarse = int(precs.nu), int(precs.coarse_max)
+        o.mg_nu, o.mg_coarse = int(precs.nu), 31 if precs.coarse_max is None else int(precs.coarse_max)   # (grid problems: FirstOrderCache)
     elif isinstance(precs, ChebyshevPrecs):
         o.cheb_degree, o.cheb_ratio = int(precs.degree), float(precs.ratio)
     elif isinstance(precs, ObjectPrecs):
@@ -1399,6 +1430,9 @@ class FirstOrderCache:
         self.prob, self.alg = prob, alg
         self._opts = _options(alg, abstol, reltol, maxiters, maxtime, store_trace, termination_kwargs,
                               termination_condition, least_squares=getattr(prob, "least_squares", False))
+        precs = getattr(getattr(alg, "linsolve", None), "precs", None)
+        if isinstance(precs, MultigridPrecs) and precs.coarse_max is None and isinstance(prob.device_problem, _GridDeviceProblem):
+            self._opts.mg_coarse = 0   # the library's default for a compiled grid problem
         self._u0_is_torch = _is_torch(prob.u0)
         p, ms, _k = _ptr(prob.u0, prob.device_problem.n_local)
         h = C.c_void_p()
@@ -1775,13 +1809,46 @@ class GMRES:
                                                             float(ratio)))
         return self
 
-    def set_multigrid_preconditioner(self, problem, u, nu: int = 2, coarse_max: int = 31):
-        """One V-cycle of the built-in geometric multigrid (Bratu2D problems) as the right preconditioner, linearised at u."""
+    def set_multigrid_preconditioner(self, problem, u, nu: int = 2, coarse_max: Optional[int] = None):
+        """One V-cycle of the built-in geometric multigrid (Bratu2D, Brusselator2D, CompiledGridProblem on one rank: see
+        MultigridPrecs) as the right preconditioner, linearised at u. Call it again after a new u, set_field or set_p.
+        coarse_max = None: the problem kind's default (31 for the built-in problems, 8 for a compiled grid problem). The solver
+        object holds one hierarchy; for a compiled grid problem it is built again when the problem, nu or coarse_max change."""
         dp = problem.device_problem if hasattr(problem, "device_problem") else problem
+        if coarse_max is None:
+            coarse_max = 0 if isinstance(dp, _GridDeviceProblem) else 31
         pu, ms, keep = _ptr(u, self.n)
-        self._mg_u = (u, keep)  # the hierarchy keeps reading the fine-level u: keep it alive
+        self._mg_u = (u, keep, dp)  # the hierarchy keeps reading the fine-level u and the problem's own arrays: keep both alive
         check(L.lib().nk_gmres_set_multigrid_preconditioner(self._h, dp._h, pu, ms, int(nu), int(coarse_max)))
         return self
+
+    def multigrid_levels(self):
+        """the hierarchy of the multigrid preconditioner of a compiled grid problem, finest first: per level a dict with
+        sides (nx, ny[, nz]), n (unknowns), nnz (of A_l) and rho (the smoother's bound of D⁻¹A_l)"""
+        nl = C.c_int(0)
+        check(L.lib().nk_gmres_multigrid_levels(self._h, C.byref(nl), 0, None, None, None, None))
+        sides, n, nnz = np.zeros((nl.value, 3), dtype=np.int64), np.zeros(nl.value, dtype=np.int64), np.zeros(nl.value, dtype=np.int64)
+        rho = np.zeros(nl.value)
+        check(L.lib().nk_gmres_multigrid_levels(self._h, C.byref(nl), nl.value, C.c_void_p(sides.ctypes.data),
+                                                C.c_void_p(n.ctypes.data), C.c_void_p(nnz.ctypes.data), C.c_void_p(rho.ctypes.data)))
+        dim = 3 if sides[0, 2] > 1 else 2
+        return [dict(sides=tuple(int(x) for x in sides[l, :dim]), n=int(n[l]), nnz=int(nnz[l]), rho=float(rho[l]))
+                for l in range(nl.value)]
+
+    def multigrid_level_matrix(self, level: int) -> CSRMatrix:
+        """A_l of that hierarchy: a non-owning view (it lives as long as this solver object)"""
+        h = C.c_void_p()
+        check(L.lib().nk_gmres_multigrid_level_matrix(self._h, int(level), C.byref(h)))
+        A = CSRMatrix(h, self.ctx, owned=False)
+        A._keep = self   # the view reads this object's arrays
+        return A
+
+    def multigrid_level_field(self, level: int, k: int):
+        """a host copy of field k of level `level` of that hierarchy (one double per node of the level)"""
+        lv = self.multigrid_levels()[level]
+        out = np.empty(int(np.prod(lv["sides"])))
+        check(L.lib().nk_gmres_multigrid_level_field(self._h, int(level), int(k), C.c_void_p(out.ctypes.data), L.HOST))
+        return out
 
     def set_spectrum_interval(self, lo: float, hi: float):
         """Real bounds of the operator's spectrum for operators the library cannot bound itself (callbacks, matrix-free):

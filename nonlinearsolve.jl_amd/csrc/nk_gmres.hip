@@ -693,6 +693,7 @@ extern "C" int nk_gmres_destroy(nk_gmres *G) {
   hipFree(G->V); hipFree(G->w); hipFree(G->z); hipFree(G->r); hipFree(G->lz);
   hipFree(G->d_Hraw); hipFree(G->d_ca); hipFree(G->d_cb); hipFree(G->d_tprev); hipFree(G->d_red);
   nk_mg_destroy(G->mg);
+  nk_gridmg_destroy(G->gmg);
   nk_ss_destroy(G->ss);
   hipFree(G->x0_keep);
   hipFree(G->d_h); hipFree(G->d_h2); hipFree(G->d_s); hipFree(G->d_R); hipFree(G->d_cs); hipFree(G->d_sn);
@@ -1126,8 +1127,9 @@ extern "C" int nk_gmres_get_chebyshev_interval(nk_gmres *G, double *lambda_min, 
   return NK_OK;
 }
 
-// Built-in multigrid V-cycle as the right preconditioner (Bratu problems, single rank): builds the hierarchy on first use,
-// afterwards only re-linearises it at `u` — call it again for every new Jacobian, like `precs(A, p)`.
+// Built-in multigrid V-cycle as the right preconditioner (Bratu and Brusselator problems; compiled grid problems on one rank:
+// nk_gridmg.hip): builds the hierarchy on first use, afterwards only re-linearises it at `u` — call it again for every new
+// Jacobian, like `precs(A, p)`.
 extern "C" int nk_gmres_set_multigrid_preconditioner(nk_gmres *G, nk_problem *P, const double *u, int memspace, int nu,
                                                      int coarse_max) {
   if (G) G->ahead.valid = false;   // (a cycle begin run ahead of the next solve belongs to the old setting)
@@ -1146,12 +1148,57 @@ extern "C" int nk_gmres_set_multigrid_preconditioner(nk_gmres *G, nk_problem *P,
     NK_HIP(hipMemcpyAsync(G->d_u_own, u, G->n * sizeof(double), hipMemcpyHostToDevice, G->ctx->stream));
     du = G->d_u_own;
   }
-  if (!G->mg) NK_TRY(nk_mg_create(P, nu, coarse_max, &G->mg));
-  NK_TRY(nk_problem_jvp_prepare(P, du));
-  NK_TRY(nk_mg_update(G->mg, du));
+  if (P->grid) {   // a compiled grid problem: levels by rediscretisation of its source, smoothing on its CSR Jacobian
+    if (G->mg) {   // (the object serves the problem of the last call: a hierarchy of the other kind goes)
+      nk_mg_destroy(G->mg);
+      G->mg = nullptr;
+      if (G->prec_kind == 3) G->prec_kind = G->rprec_obj ? 4 : (G->prec ? 1 : 0);
+    }
+    if (G->gmg && !nk_gridmg_matches(G->gmg, P, nu, coarse_max)) {   // another problem, nu or coarse_max: built again
+      nk_gridmg_destroy(G->gmg);
+      G->gmg = nullptr;
+      if (G->prec_kind == 3) G->prec_kind = G->rprec_obj ? 4 : (G->prec ? 1 : 0);
+    }
+    if (!G->gmg) NK_TRY(nk_gridmg_create(P, nu, coarse_max, &G->gmg));
+    NK_TRY(nk_gridmg_update(G->gmg, du));
+  } else {
+    if (G->gmg) {
+      nk_gridmg_destroy(G->gmg);
+      G->gmg = nullptr;
+      if (G->prec_kind == 3) G->prec_kind = G->rprec_obj ? 4 : (G->prec ? 1 : 0);
+    }
+    if (!G->mg) NK_TRY(nk_mg_create(P, nu, coarse_max, &G->mg));
+    NK_TRY(nk_problem_jvp_prepare(P, du));
+    NK_TRY(nk_mg_update(G->mg, du));
+  }
   if (!G->z) NK_TRY(nk_dev_alloc(&G->z, (size_t)G->ldv));
   G->prec_kind = 3;
   return NK_OK;
+}
+
+// the hierarchy of the multigrid preconditioner of a compiled grid problem, for inspection
+extern "C" int nk_gmres_multigrid_levels(nk_gmres *G, int *levels, int cap, int64_t *sides, int64_t *n, int64_t *nnz, double *rho) {
+  NK_REQUIRE(G && levels, "NULL argument");
+  NK_REQUIRE(G->gmg, "no multigrid preconditioner of a compiled grid problem is set (nk_gmres_set_multigrid_preconditioner)");
+  *levels = nk_gridmg_levels(G->gmg);
+  for (int l = 0; l < *levels && l < cap; ++l)
+    NK_TRY(nk_gridmg_level_info(G->gmg, l, sides ? sides + 3 * l : nullptr, n ? n + l : nullptr, nnz ? nnz + l : nullptr,
+                                rho ? rho + l : nullptr));
+  return NK_OK;
+}
+extern "C" int nk_gmres_multigrid_level_matrix(nk_gmres *G, int level, nk_csr **out) {
+  NK_REQUIRE(G && out, "NULL argument");
+  NK_REQUIRE(G->gmg, "no multigrid preconditioner of a compiled grid problem is set (nk_gmres_set_multigrid_preconditioner)");
+  *out = nk_gridmg_level_matrix(G->gmg, level);
+  NK_REQUIRE(*out, "level %d outside 0..%d", level, nk_gridmg_levels(G->gmg) - 1);
+  return NK_OK;
+}
+extern "C" int nk_gmres_multigrid_level_field(nk_gmres *G, int level, int k, double *out, int memspace) {
+  NK_REQUIRE(G && out, "NULL argument");
+  NK_REQUIRE(G->gmg, "no multigrid preconditioner of a compiled grid problem is set (nk_gmres_set_multigrid_preconditioner)");
+  nk_problem *P = nk_gridmg_level_problem(G->gmg, level);
+  NK_REQUIRE(P, "level %d outside 0..%d", level, nk_gridmg_levels(G->gmg) - 1);
+  return nk_problem_get_field(P, k, out, memspace);
 }
 
 static int lprec_apply(nk_gmres *G, const double *src, double *dst, const int *d_skip) {
@@ -1162,7 +1209,7 @@ static int lprec_apply(nk_gmres *G, const double *src, double *dst, const int *d
 }
 static int prec_apply(nk_gmres *G, const double *src, double *dst, const int *d_skip) {
   if (G->prec_kind == 2) return cheb_apply(G, src, dst, d_skip);
-  if (G->prec_kind == 3) return nk_mg_apply(G->mg, src, dst, d_skip);
+  if (G->prec_kind == 3) return G->gmg ? nk_gridmg_apply(G->gmg, src, dst, d_skip) : nk_mg_apply(G->mg, src, dst, d_skip);
   if (G->prec_kind == 4) return nk_precond_apply_dev(G->rprec_obj, src, dst, d_skip);
   if (G->prec_host) return host_callback(G, G->prec, G->prec_user, src, dst, "preconditioner");
   if (G->prec(G->prec_user, src, dst, (void *)G->ctx->stream) != 0) NK_FAIL(NK_E_CALLBACK, "preconditioner failed");

@@ -60,6 +60,10 @@
 // number of distinct fields the source reads: residual 16 + 8·r/dof bytes, JVP 24 + 8·r/dof, fill its figure + 8·r/dof (a field
 // line read by three lines of threads comes from cache, as for u). In the text a field is one more kernel parameter and one more
 // nk_point argument, NK_FLDS_PARAM and NK_FLDS_ARG, both empty at NK_NFIELDS == 0.
+//
+// Levels (nk_grid_level_create): the state keeps the two code objects, and the same problem on smaller sides — a level of the
+// geometric multigrid, nk_gridmg.hip — loads them again instead of compiling: the sides are kernel arguments, and a source that
+// takes its spacing from the site (s.nx, s.ny, s.nz) discretises the same PDE on every level.
 #include <ctype.h>
 #include <math.h>
 #include <stdlib.h>
@@ -1043,6 +1047,9 @@ struct grid_slab_arg {
 struct nk_grid_state {
   nk_ctx *ctx = nullptr;
   int nx = 0, ny = 0, nz = 0 /* 0: a 2-D problem */, dof = 0, np = 0, nfields = 0;
+  int stencil = 0, boundary = 0;   // as the problem was created (nk_grid_level_create builds the same problem on a smaller grid)
+  std::vector<char> code_f, code_j;   // the two code objects, kept by a problem made from source: a level of the geometric multigrid
+                                      // loads them again (nothing is compiled twice) and keeps no copy of its own
   hipModule_t mod_f = nullptr, mod_jac = nullptr;
   hipFunction_t fn_res = nullptr, fn_jvp = nullptr, fn_jac = nullptr;
   double *d_params = nullptr;   // np doubles (at least one allocated): the source's p
@@ -1255,29 +1262,21 @@ extern "C" int nk_problem_grid_slab(nk_problem *P, int64_t *line_begin, int64_t 
   return NK_OK;
 }
 
-// dim = 2: nz is not read (nk_problem_create_grid); dim = 3: nk_problem_create_grid3
-static int grid_create(nk_ctx *ctx, const char *source, int dim, int64_t nx, int64_t ny, int64_t nz, int dof, int stencil,
-                       int boundary, const double *params, int nparams, int nfields, nk_problem **out) {
-  NK_REQUIRE(ctx && source && out, "NULL argument");
-  NK_REQUIRE(params || nparams == 0, "NULL params with nparams = %d", nparams);
-  NK_REQUIRE(nfields >= 0 && nfields <= 4, "nfields = %d outside 0..4 (read-only fields of one double per node)", nfields);
-  NK_HIP(hipSetDevice(ctx->device));
-  if (dim == 2) nz = 1;
+// The problem object from its pattern and its two code objects. params: nparams host doubles, or NULL for a parameter buffer
+// the caller fills on the device (nk_grid_level_create). nnz, l0, l1: the pattern's count and the slab's lines if the caller has them
+// (its validating pass), nnz = −1 if not. keep_code: the state keeps the code objects (a problem made from source; a level reads its
+// fine problem's)
+static int grid_assemble(nk_ctx *ctx, int dim, int64_t nx, int64_t ny, int64_t nz, int dof, int stencil, int boundary,
+                         const double *params, int nparams, int nfields, const std::vector<char> &code_f,
+                         const std::vector<char> &code_j, int64_t nnz, int64_t l0, int64_t l1, bool keep_code, nk_problem **out) {
   const int R = ctx->nranks, r = ctx->rank;
-  // the pattern first: it validates the geometry (several ranks: and the slabs) before anything is compiled. On one rank the
-  // slab is the grid, its pattern nk_grid_pattern's and its programs the ones without a cut
-  int64_t nnz = 0, l0 = 0, l1 = 0;
-  NK_TRY(grid_slab_pattern(dim, nx, ny, nz, dof, stencil, boundary, R, r, &l0, &l1, nullptr, nullptr, &nnz));
+  // on one rank the slab is the grid, its pattern nk_grid_pattern's and its programs the ones without a cut
+  if (nnz < 0) NK_TRY(grid_slab_pattern(dim, nx, ny, nz, dof, stencil, boundary, R, r, &l0, &l1, nullptr, nullptr, &nnz));
   const int64_t line = dim == 3 ? nx * ny : nx, nn_loc = line * (l1 - l0);
   const int64_t n = nn_loc * dof, n_global = nx * ny * nz * dof;
   std::vector<int32_t> rp((size_t)n + 1);
   std::vector<int64_t> gc((size_t)nnz);
   NK_TRY(grid_slab_pattern(dim, nx, ny, nz, dof, stencil, boundary, R, r, &l0, &l1, rp.data(), gc.data(), &nnz));
-  std::vector<char> code_f, code_j;
-  std::string log;
-  NK_TRY(grid_compile(source, dim, dof, stencil, boundary, nparams, nfields, GSET_F, false, &code_f, &log, R, r));
-  log.clear();
-  NK_TRY(grid_compile(source, dim, dof, stencil, boundary, nparams, nfields, GSET_JAC, grid_fill_direct(), &code_j, &log, R, r));
 
   nk_grid_state *S = new nk_grid_state();
   auto guard = nk_make_guard(S, nk_grid_state_destroy);
@@ -1288,6 +1287,12 @@ static int grid_create(nk_ctx *ctx, const char *source, int dim, int64_t nx, int
   S->dof = dof;
   S->np = nparams;
   S->nfields = nfields;
+  S->stencil = stencil;
+  S->boundary = boundary;
+  if (keep_code) {
+    S->code_f = code_f;
+    S->code_j = code_j;
+  }
   S->l0 = l0;
   S->l1 = l1;
   S->nn_loc = nn_loc;
@@ -1298,7 +1303,7 @@ static int grid_create(nk_ctx *ctx, const char *source, int dim, int64_t nx, int
       hipModuleGetFunction(&S->fn_jac, S->mod_jac, dim == 3 ? "nk_grid3_jac" : "nk_grid_jac") != hipSuccess)
     NK_FAIL(NK_E_HIP, "a generated grid kernel is missing from the compiled module");
   NK_TRY(nk_dev_alloc(&S->d_params, (size_t)(nparams > 0 ? nparams : 1)));
-  if (nparams > 0) NK_HIP(nk_memcpy(ctx, S->d_params, params, (size_t)nparams * sizeof(double), hipMemcpyHostToDevice));
+  if (nparams > 0 && params) NK_HIP(nk_memcpy(ctx, S->d_params, params, (size_t)nparams * sizeof(double), hipMemcpyHostToDevice));
   if (nfields > 0) {   // zero until nk_problem_set_field: nothing is ever read uninitialised
     const size_t cnt = (size_t)nfields * (size_t)nn_loc;
     NK_TRY(nk_dev_alloc(&S->d_fields, cnt));
@@ -1314,7 +1319,7 @@ static int grid_create(nk_ctx *ctx, const char *source, int dim, int64_t nx, int
   P->n_global = n_global;
   P->row_begin = dof * line * l0;
   P->nparams = nparams;
-  for (int i = 0; i < nparams && i < 8; ++i) P->params[i] = params[i];
+  for (int i = 0; params && i < nparams && i < 8; ++i) P->params[i] = params[i];
   P->cb.residual = grid_cb_residual;
   P->cb.jvp = grid_cb_jvp;
   P->cb.vjp = nullptr;   // Jᵀv: user_lin_J + the transposed SpMV
@@ -1323,6 +1328,69 @@ static int grid_create(nk_ctx *ctx, const char *source, int dim, int64_t nx, int
   P->user_pattern = S->pattern;
   P->grid = guard.release();
   *out = P;
+  return NK_OK;
+}
+
+// dim = 2: nz is not read (nk_problem_create_grid); dim = 3: nk_problem_create_grid3
+static int grid_create(nk_ctx *ctx, const char *source, int dim, int64_t nx, int64_t ny, int64_t nz, int dof, int stencil,
+                       int boundary, const double *params, int nparams, int nfields, nk_problem **out) {
+  NK_REQUIRE(ctx && source && out, "NULL argument");
+  NK_REQUIRE(params || nparams == 0, "NULL params with nparams = %d", nparams);
+  NK_REQUIRE(nfields >= 0 && nfields <= 4, "nfields = %d outside 0..4 (read-only fields of one double per node)", nfields);
+  NK_HIP(hipSetDevice(ctx->device));
+  if (dim == 2) nz = 1;
+  const int R = ctx->nranks, r = ctx->rank;
+  // the pattern first: it validates the geometry (several ranks: and the slabs) before anything is compiled
+  int64_t nnz = 0, l0 = 0, l1 = 0;
+  NK_TRY(grid_slab_pattern(dim, nx, ny, nz, dof, stencil, boundary, R, r, &l0, &l1, nullptr, nullptr, &nnz));
+  std::vector<char> code_f, code_j;
+  std::string log;
+  NK_TRY(grid_compile(source, dim, dof, stencil, boundary, nparams, nfields, GSET_F, false, &code_f, &log, R, r));
+  log.clear();
+  NK_TRY(grid_compile(source, dim, dof, stencil, boundary, nparams, nfields, GSET_JAC, grid_fill_direct(), &code_j, &log, R, r));
+  return grid_assemble(ctx, dim, nx, ny, nz, dof, stencil, boundary, params, nparams, nfields, code_f, code_j, nnz, l0, l1, true, out);
+}
+
+// ----------------------------------------------------------------------------- what the geometric multigrid asks (nk_gridmg.hip)
+int64_t nk_grid_side_map(int64_t x, int64_t n, int lo, int hi) { return grid_side_map(x, n, lo, hi); }
+
+int nk_grid_shape(const nk_problem *P, nk_grid_shape_info *out) {
+  NK_REQUIRE(P && P->grid && out, "the problem is not a compiled grid problem");
+  const nk_grid_state *S = P->grid;
+  const int dim = S->nz > 0 ? 3 : 2;
+  grid_sides sd;
+  NK_TRY(grid_decode_boundary(dim, S->boundary, &sd));
+  out->dim = dim;
+  out->n[0] = S->nx, out->n[1] = S->ny, out->n[2] = dim == 3 ? S->nz : 1;
+  out->dof = S->dof;
+  out->nfields = S->nfields;
+  out->radius = grid_radius(*grid_find(dim, S->stencil));
+  for (int s = 0; s < 6; ++s) out->kind[s] = sd.kind[s];
+  out->d_fields = S->d_fields;
+  return NK_OK;
+}
+
+// The problem of `fine` on an nx × ny [× nz] grid: same source, options and parameter count, the fine problem's code objects
+// loaded again (the sizes are kernel arguments). One rank. Its p is a device copy of the fine problem's, its fields are zero.
+int nk_grid_level_create(nk_problem *fine, int64_t nx, int64_t ny, int64_t nz, nk_problem **out) {
+  NK_REQUIRE(fine && fine->grid && out, "the problem is not a compiled grid problem");
+  nk_grid_state *F = fine->grid;
+  NK_REQUIRE(!F->code_f.empty() && !F->code_j.empty(), "a level is built from a problem made from source, not from another level");
+  NK_REQUIRE(F->ctx->nranks == 1, "a level of a compiled grid problem is built on one rank, the context has %d", F->ctx->nranks);
+  NK_HIP(hipSetDevice(F->ctx->device));
+  const int dim = F->nz > 0 ? 3 : 2;
+  NK_TRY(grid_assemble(F->ctx, dim, nx, ny, dim == 3 ? nz : 1, F->dof, F->stencil, F->boundary, nullptr, F->np, F->nfields, F->code_f,
+                       F->code_j, -1, 0, 0, false, out));
+  const int st = nk_grid_level_sync_params(fine, *out);
+  if (st != NK_OK) { nk_problem_destroy(*out); *out = nullptr; }
+  return st;
+}
+// p of the fine problem, as it is now, into a level's
+int nk_grid_level_sync_params(nk_problem *fine, nk_problem *level) {
+  nk_grid_state *F = fine->grid, *S = level->grid;
+  if (F->np > 0) NK_HIP(hipMemcpyAsync(S->d_params, F->d_params, (size_t)F->np * sizeof(double), hipMemcpyDeviceToDevice, F->ctx->stream));
+  for (int i = 0; i < 8; ++i) level->params[i] = fine->params[i];
+  nk_problem_invalidate(level);
   return NK_OK;
 }
 

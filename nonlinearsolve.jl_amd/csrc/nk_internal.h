@@ -386,6 +386,15 @@ struct nk_problem {
 };
 void nk_grid_state_destroy(struct nk_grid_state *S);
 int nk_grid_set_params(nk_problem *P, const double *params, int nparams);   // nk_problem_set_params of a compiled grid problem
+// what the geometric multigrid of compiled grid problems (nk_gridmg.hip) asks of nk_grid.hip
+struct nk_grid_shape_info {
+  int dim, n[3] /* nx, ny, nz (2-D: nz = 1) */, dof, nfields, radius, kind[6] /* x-lo, x-hi, y-lo, y-hi, z-lo, z-hi */;
+  double *d_fields;   // nfields·nn doubles (NULL without fields)
+};
+int nk_grid_shape(const nk_problem *P, nk_grid_shape_info *out);
+int64_t nk_grid_side_map(int64_t x, int64_t n, int lo, int hi);   // where index x of an axis of n nodes lands (−1: dropped)
+int nk_grid_level_create(nk_problem *fine, int64_t nx, int64_t ny, int64_t nz, nk_problem **out);   // shares the code objects
+int nk_grid_level_sync_params(nk_problem *fine, nk_problem *level);
 bool nk_problem_powers_ready(nk_problem *P);
 int nk_problem_powers_dev(nk_problem *P, const double *d_u, const double *d_x0, double *d_Y, int64_t ldy, int s,
                           const double *d_scal_first, const double *d_scal_rest, const double *d_theta, const int *d_skip);
@@ -402,6 +411,8 @@ int nk_problem_residual_norms_dev(nk_problem *P, const double *d_u, double *d_f,
 // forget what the problem was linearised at: the caller wrote new contents into a buffer it may have been keyed on
 static inline void nk_problem_invalidate(nk_problem *P) { P->d_u_lin = nullptr; P->d_u_linJ = nullptr; }
 int nk_csr_clone_pattern(nk_csr *A, nk_csr **out);  // same pattern and partition, own values (collective on several ranks)
+int nk_csr_share_pattern(nk_csr *A, nk_csr **out);   // one rank: A's own index arrays, new values; A must outlive the result
+void nk_csr_destroy_shared(nk_csr *V);               // the only way to free what nk_csr_share_pattern made
 int nk_problem_jvp_prepare(nk_problem *P, const double *d_u);  // linearise at u (u must stay alive)
 int nk_problem_jvp_dev(nk_problem *P, const double *d_u, const double *d_v, double *d_jv, const int *d_skip,
                        const double *d_out_scale = nullptr, const struct nk_spmv_epi *epi = nullptr);
@@ -504,6 +515,17 @@ int nk_mg_update(nk_mg *M, const double *d_u);
 int nk_mg_apply(nk_mg *M, const double *src, double *dst, const int *d_skip);
 int nk_mg_levels(const nk_mg *M);
 void nk_mg_destroy(nk_mg *M);
+// the same V-cycle for any compiled grid problem on one rank (nk_gridmg.hip): levels by rediscretisation of the user's source
+struct nk_gridmg;
+int nk_gridmg_create(nk_problem *P, int nu, int coarse_max, nk_gridmg **out);
+int nk_gridmg_update(nk_gridmg *M, const double *d_u);
+int nk_gridmg_apply(nk_gridmg *M, const double *src, double *dst, const int *d_skip);
+int nk_gridmg_levels(const nk_gridmg *M);
+bool nk_gridmg_matches(const nk_gridmg *M, const nk_problem *P, int nu, int coarse_max);
+int nk_gridmg_level_info(const nk_gridmg *M, int l, int64_t *sides3, int64_t *n, int64_t *nnz, double *rho);
+nk_csr *nk_gridmg_level_matrix(const nk_gridmg *M, int l);
+nk_problem *nk_gridmg_level_problem(const nk_gridmg *M, int l);
+void nk_gridmg_destroy(nk_gridmg *M);
 
 // ----------------------------------------------------------------------------- GMRES
 struct nk_gmres_ctl {  // lives in device memory, mirrored to pinned host memory
@@ -579,6 +601,7 @@ struct nk_gmres {
   struct nk_precond *lprec_obj = nullptr;
   double *lz = nullptr;  // A Pr⁻¹ x before Pl⁻¹
   struct nk_mg *mg = nullptr;
+  struct nk_gridmg *gmg = nullptr;   // prec_kind 3 on a compiled grid problem (at most one of mg, gmg exists: the last set call's)
   int cheb_degree = 0;
   double cheb_lmin = 0, cheb_lmax = 0;
   double *cr = nullptr, *cd = nullptr, *ct = nullptr, *cd2 = nullptr;  // Chebyshev work vectors (cd/cd2 ping-pong)
