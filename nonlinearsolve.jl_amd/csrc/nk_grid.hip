@@ -226,57 +226,6 @@ static int grid_check_size(const grid_stencil &st, int64_t nx, int64_t ny, int64
   return NK_OK;
 }
 
-// ----------------------------------------------------------------------------- the stencil's CSR pattern (host only)
-// dim = 2: nz is 1 and every dk is 0
-static int grid_pattern(int dim, int64_t nx, int64_t ny, int64_t nz, int dof, int stencil, int boundary, int32_t *rowptr,
-                        int32_t *colind, int64_t *nnz) {
-  NK_REQUIRE(rowptr || nnz, "NULL argument");
-  const grid_stencil *st = nullptr;
-  grid_sides sd;
-  NK_TRY(grid_check_shape(dim, dof, stencil, boundary, &st, &sd));
-  NK_TRY(grid_check_size(*st, nx, ny, nz, dof));
-  const int64_t nn = nx * ny * nz;
-  int64_t pos = 0;
-  for (int c = 0; c < dof; ++c)
-    for (int64_t k = 0; k < nz; ++k)
-      for (int64_t j = 0; j < ny; ++j)
-        for (int64_t i = 0; i < nx; ++i) {
-          int64_t nb[27];
-          int cnt = 0;
-          for (int q = 0; q < st->npts; ++q) {
-            // every axis by the kinds of its two sides; a point that leaves through a Dirichlet-0 side of any axis has no column
-            const int64_t ii = grid_side_map(i + st->off[q][0], nx, sd.kind[0], sd.kind[1]);
-            const int64_t jj = grid_side_map(j + st->off[q][1], ny, sd.kind[2], sd.kind[3]);
-            const int64_t kk = grid_side_map(k + st->off[q][2], nz, sd.kind[4], sd.kind[5]);
-            if (ii < 0 || jj < 0 || kk < 0) continue;
-            // insertion keeps the node indices ascending (wrap-around and mirrors reorder the points at an edge) and a column
-            // once: at a mirror several points of a row land on one node
-            const int64_t m = (kk * ny + jj) * nx + ii;
-            int t = cnt;
-            while (t > 0 && nb[t - 1] > m) --t;
-            if (t > 0 && nb[t - 1] == m) continue;
-            for (int e = cnt++; e > t; --e) nb[e] = nb[e - 1];
-            nb[t] = m;
-          }
-          if (rowptr) rowptr[c * nn + (k * ny + j) * nx + i] = (int32_t)pos;
-          if (colind)
-            for (int c2 = 0; c2 < dof; ++c2)
-              for (int t = 0; t < cnt; ++t) colind[pos + (int64_t)c2 * cnt + t] = (int32_t)(c2 * nn + nb[t]);
-          pos += (int64_t)cnt * dof;
-        }
-  if (rowptr) rowptr[dof * nn] = (int32_t)pos;
-  if (nnz) *nnz = pos;
-  return NK_OK;
-}
-extern "C" int nk_grid_pattern(int64_t nx, int64_t ny, int dof, int stencil, int boundary, int32_t *rowptr, int32_t *colind,
-                               int64_t *nnz) {
-  return grid_pattern(2, nx, ny, 1, dof, stencil, boundary, rowptr, colind, nnz);
-}
-extern "C" int nk_grid3_pattern(int64_t nx, int64_t ny, int64_t nz, int dof, int stencil, int boundary, int32_t *rowptr,
-                                int32_t *colind, int64_t *nnz) {
-  return grid_pattern(3, nx, ny, nz, dof, stencil, boundary, rowptr, colind, nnz);
-}
-
 // ----------------------------------------------------------------------------- several ranks: slabs of the outermost axis
 // On a context of R > 1 ranks the grid is split along its outermost axis (y in 2-D, z in 3-D): rank r owns the lines (planes)
 // [l0, l1) = nk_partition_range(n_outer, 1, R, r), the rule of the built-in grid problems. Local numbering is component-major on
@@ -410,6 +359,34 @@ extern "C" int nk_grid_slab_pattern(int dim, int64_t nx, int64_t ny, int64_t nz,
                                     int rank, int64_t *line_begin, int64_t *line_end, int32_t *rowptr, int64_t *colind_global,
                                     int64_t *nnz) {
   return grid_slab_pattern(dim, nx, ny, nz, dof, stencil, boundary, nranks, rank, line_begin, line_end, rowptr, colind_global, nnz);
+}
+
+// ----------------------------------------------------------------------------- the stencil's CSR pattern (host only)
+// The whole grid's pattern is the slab pattern of one rank of one (R = 1, r = 0): the global column of component c2 of a node is
+// then c2·nn + node. The columns come back as int64 and are narrowed into the caller's 32-bit array: grid_check_size has made
+// sure they fit. dim = 2: nz is 1 and every dk is 0
+static int grid_pattern_narrow(int dim, int64_t nx, int64_t ny, int64_t nz, int dof, int stencil, int boundary, int32_t *rowptr,
+                               int32_t *colind, int64_t *nnz) {
+  NK_REQUIRE(rowptr || nnz, "NULL argument");
+  int64_t n = 0;
+  std::vector<int64_t> wide;
+  if (colind) {   // (the sizes first: every refusal comes before anything is allocated)
+    NK_TRY(grid_slab_pattern(dim, nx, ny, nz, dof, stencil, boundary, 1, 0, nullptr, nullptr, nullptr, nullptr, &n));
+    wide.resize((size_t)n);
+  }
+  NK_TRY(grid_slab_pattern(dim, nx, ny, nz, dof, stencil, boundary, 1, 0, nullptr, nullptr, rowptr, colind ? wide.data() : nullptr,
+                           &n));
+  for (int64_t e = 0; colind && e < n; ++e) colind[e] = (int32_t)wide[(size_t)e];
+  if (nnz) *nnz = n;
+  return NK_OK;
+}
+extern "C" int nk_grid_pattern(int64_t nx, int64_t ny, int dof, int stencil, int boundary, int32_t *rowptr, int32_t *colind,
+                               int64_t *nnz) {
+  return grid_pattern_narrow(2, nx, ny, 1, dof, stencil, boundary, rowptr, colind, nnz);
+}
+extern "C" int nk_grid3_pattern(int64_t nx, int64_t ny, int64_t nz, int dof, int stencil, int boundary, int32_t *rowptr,
+                                int32_t *colind, int64_t *nnz) {
+  return grid_pattern_narrow(3, nx, ny, nz, dof, stencil, boundary, rowptr, colind, nnz);
 }
 
 // ----------------------------------------------------------------------------- device source (compiled by hiprtc)

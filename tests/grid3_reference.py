@@ -1,5 +1,5 @@
 """NumPy restatement of the compiled grid problems in three dimensions (csrc/nk_grid.hip, nk_problem_create_grid3), in the
-style of tests/grid_reference.py: the stencil's CSR pattern, four pointwise problems — Bratu, a Brusselator with upwinded
+style of tests/grid_reference.py: four pointwise problems — Bratu, a Brusselator with upwinded
 (direction- and sign-dependent) weights and a site-dependent forcing, a 27-point box problem with 27 distinct coefficients, a
 four-component star problem coupled at the centre — each written once as HIP source (what the library compiles) and once as
 NumPy formulas with their ANALYTIC derivatives, evaluated in float64 and in long double. From the formulas: the residual, J·v
@@ -10,90 +10,17 @@ entry the gap |float64 − long double| and the sum of the absolute values of th
 
 Layout: unknown c of node (i, j, k) is element c·nx·ny·nz + (k·ny + j)·nx + i. Seeded inputs have |u| <= 1.
 Stencil points in pattern order (ascending node index inside the grid), as (di, dj, dk):
-star (0,0,−1) (0,−1,0) (−1,0,0) C (1,0,0) (0,1,0) (0,0,1); box dk outermost, di innermost."""
+star (0,0,−1) (0,−1,0) (−1,0,0) C (1,0,0) (0,1,0) (0,0,1); box dk outermost, di innermost.
+This module is the table: sources, formulas, problems and sizes. The pattern, the access to u and v, the evaluation in both
+arithmetics and the bound are tests/grid_core.py's."""
 import numpy as np
 
-from grid_reference import BOUNDARY_ID, EPS, FLOOR_ULPS, LD, MARGIN, STENCIL_ID, _sum   # noqa: F401  (shared with 2-D)
+from grid_core import STENCILS, Problem, _site, _sum, _wsum
 
-STAR = [(0, 0, -1), (0, -1, 0), (-1, 0, 0), (0, 0, 0), (1, 0, 0), (0, 1, 0), (0, 0, 1)]   # (di, dj, dk)
-BOX = [(di, dj, dk) for dk in (-1, 0, 1) for dj in (-1, 0, 1) for di in (-1, 0, 1)]
-STENCILS = {"star": STAR, "box": BOX}
+BOX = STENCILS[(3, "box")]
 PERMITTED = [("star", 1), ("star", 2), ("star", 3), ("star", 4), ("box", 1)]                # (stencil, dof)
 # the six neighbours in the order the sources add them: −i +i −j +j −k +k
 SIX = [(-1, 0, 0), (1, 0, 0), (0, -1, 0), (0, 1, 0), (0, 0, -1), (0, 0, 1)]
-
-
-# ------------------------------------------------------------------------------------------------ pattern
-def neighbours(nx, ny, nz, stencil, boundary):
-    """(idx, inside): node index of every stencil point of every node ([nn, npts]; −1 outside a Dirichlet boundary)"""
-    offs, nn = STENCILS[stencil], nx * ny * nz
-    node = np.arange(nn, dtype=np.int64)
-    k, rem = np.divmod(node, nx * ny)
-    j, i = np.divmod(rem, nx)
-    idx = np.empty((nn, len(offs)), dtype=np.int64)
-    inside = np.empty((nn, len(offs)), dtype=bool)
-    for q, (di, dj, dk) in enumerate(offs):
-        ii, jj, kk = i + di, j + dj, k + dk
-        if boundary == "periodic":
-            ii, jj, kk = ii % nx, jj % ny, kk % nz
-            ok = np.ones(nn, dtype=bool)
-        else:
-            ok = (ii >= 0) & (ii < nx) & (jj >= 0) & (jj < ny) & (kk >= 0) & (kk < nz)
-        idx[:, q] = np.where(ok, (kk * ny + jj) * nx + ii, -1)
-        inside[:, q] = ok
-    return idx, inside
-
-
-def slots(nx, ny, nz, dof, stencil, boundary):
-    """(rowptr, cnt, rank, idx, inside, order): rank[node, q] = position of stencil point q among the node's in-domain points by
-    ascending node index; the entry (row c·nn + node, point q, component c2) sits at
-    rowptr[c·nn + node] + c2·cnt[node] + rank[node, q]"""
-    idx, inside = neighbours(nx, ny, nz, stencil, boundary)
-    key = np.where(inside, idx, np.iinfo(np.int64).max)
-    order = np.argsort(key, axis=1, kind="stable")
-    rank = np.empty_like(order)
-    np.put_along_axis(rank, order, np.broadcast_to(np.arange(order.shape[1]), order.shape), axis=1)
-    cnt = inside.sum(axis=1)
-    rowptr = np.concatenate([[0], np.cumsum(np.tile(cnt * dof, dof))]).astype(np.int64)
-    return rowptr, cnt, rank, idx, inside, order
-
-
-def pattern(nx, ny, nz, dof=1, stencil="star", boundary="dirichlet"):
-    """CSR pattern (rowptr, colind), int32, columns ascending within a row, every (in-domain point) × (component) entry kept"""
-    nn = nx * ny * nz
-    rowptr, cnt, rank, idx, inside, order = slots(nx, ny, nz, dof, stencil, boundary)
-    sorted_idx = np.take_along_axis(idx, order, axis=1)                      # in-domain points first, ascending
-    valid = np.arange(sorted_idx.shape[1])[None, :] < cnt[:, None]           # [nn, npts]
-    cols = sorted_idx[:, None, :] + (np.arange(dof) * nn)[None, :, None]     # [nn, dof(c2), npts]
-    row0 = cols[np.broadcast_to(valid[:, None, :], cols.shape)]              # rows of component 0, flattened (node, c2, t)
-    return rowptr.astype(np.int32), np.tile(row0, dof).astype(np.int32)      # a row's columns do not depend on its component
-
-
-# ------------------------------------------------------------------------------------------------ grid access
-class Grid3:
-    """neighbour access N(di, dj, dk, c) on whole-grid arrays [dof, nz, ny, nx] of one floating-point type"""
-
-    def __init__(self, U, boundary):
-        self.U, self.boundary = U, boundary
-        self.dof, self.nz, self.ny, self.nx = U.shape
-
-    def __call__(self, di, dj, dk, c=0):
-        A = self.U[c]
-        if self.boundary == "periodic":
-            return np.roll(A, (-dk, -dj, -di), axis=(0, 1, 2))
-        P = np.zeros((self.nz + 2, self.ny + 2, self.nx + 2), dtype=A.dtype)
-        P[1:-1, 1:-1, 1:-1] = A
-        return P[1 + dk:1 + dk + self.nz, 1 + dj:1 + dj + self.ny, 1 + di:1 + di + self.nx]
-
-
-def _site(nx, ny, nz):
-    k, j, i = np.meshgrid(np.arange(nz), np.arange(ny), np.arange(nx), indexing="ij")
-    return i.astype(np.float64), j.astype(np.float64), k.astype(np.float64)
-
-
-def _wsum(N, offs, w, c):
-    """Σ w[t]·N(offs[t], c), left to right, and Σ|terms|"""
-    return _sum([w[t] * N(*offs[t], c) for t in range(len(offs))])
 
 
 # ------------------------------------------------------------------------------------------------ bratu3
@@ -119,19 +46,19 @@ def _bratu3_lap(N, T):
     return _sum([T(6) * N(0, 0, 0)] + [-N(*o) for o in SIX])
 
 
-def _bratu3_resid(N, p, shape, T):
+def _bratu3_resid(N, _A, p, shape, T):
     lap, ml = _bratu3_lap(N, T)
     e = p[1] * np.exp(N(0, 0, 0))
     return [p[0] * lap - e], [np.abs(p[0]) * ml + np.abs(e)]
 
 
-def _bratu3_jvp(N, V, p, shape, T):
+def _bratu3_jvp(N, V, _A, p, shape, T):
     lap, ml = _bratu3_lap(V, T)
     e = p[1] * (np.exp(N(0, 0, 0)) * V(0, 0, 0))
     return [p[0] * lap - e], [np.abs(p[0]) * ml + np.abs(e)]
 
 
-def _bratu3_jac(N, p, shape, T):
+def _bratu3_jac(N, _A, p, shape, T):
     c = N(0, 0, 0)
     one = np.ones_like(c)
     e = p[1] * np.exp(c)
@@ -165,7 +92,7 @@ BRUSSELATOR3_PARAMS = [3.4, 1.0, 11.0, 7.5, 9.25, 6.0, 13.5, 4.75, 52.0]
 
 def _brus3_forcing(shape, T):
     nx, ny, nz = shape
-    i, j, k = _site(nx, ny, nz)
+    i, j, k = _site(shape)
     x, y, z = i / np.float64(nx), j / np.float64(ny), k / np.float64(nz)
     return ((x + 2.0 * y) * z + 0.25 * x - 0.5 * y).astype(T)
 
@@ -176,7 +103,7 @@ def _brus3_lap(N, p, c):
     return s - t, m + np.abs(t)
 
 
-def _brus3_resid(N, p, shape, T):
+def _brus3_resid(N, _A, p, shape, T):
     A, B = p[0], p[1]
     uu, vv = N(0, 0, 0, 0), N(0, 0, 0, 1)
     lu, mu = _brus3_lap(N, p, 0)
@@ -187,7 +114,7 @@ def _brus3_resid(N, p, shape, T):
     return [f0, f1], [m0 - np.abs(lu) + mu, m1 - np.abs(lv) + mv]
 
 
-def _brus3_jvp(N, V, p, shape, T):
+def _brus3_jvp(N, V, _A, p, shape, T):
     A = p[0]
     uu, vv, a, b = N(0, 0, 0, 0), N(0, 0, 0, 1), V(0, 0, 0, 0), V(0, 0, 0, 1)
     la, ma = _brus3_lap(V, p, 0)
@@ -200,7 +127,7 @@ def _brus3_jvp(N, V, p, shape, T):
     return [la + d3 - t4, lb + A * a - d3], [ma + m3 + np.abs(t4), mb + np.abs(A * a) + m3]
 
 
-def _brus3_jac(N, p, shape, T):
+def _brus3_jac(N, _A, p, shape, T):
     A = p[0]
     uu, vv = N(0, 0, 0, 0), N(0, 0, 0, 1)
     one = np.ones_like(uu)
@@ -245,21 +172,21 @@ def _box3_w(p, T):
     return [p[0] + p[1] * T(di + 3 * dj + 9 * dk) for (di, dj, dk) in BOX]
 
 
-def _box3_resid(N, p, shape, T):
+def _box3_resid(N, _A, p, shape, T):
     acc, m = _wsum(N, BOX, _box3_w(p, T), 0)
     c = N(0, 0, 0)
     e = (p[2] * c) * c
     return [acc + e], [m + np.abs(e)]
 
 
-def _box3_jvp(N, V, p, shape, T):
+def _box3_jvp(N, V, _A, p, shape, T):
     acc, m = _wsum(V, BOX, _box3_w(p, T), 0)
     c, dc = N(0, 0, 0), V(0, 0, 0)
     e1, e2 = (dc * p[2]) * c, (c * p[2]) * dc          # the dual's product rule in the source's order
     return [acc + (e1 + e2)], [m + np.abs(e1) + np.abs(e2)]
 
 
-def _box3_jac(N, p, shape, T):
+def _box3_jac(N, _A, p, shape, T):
     c = N(0, 0, 0)
     one = np.ones_like(c)
     w = _box3_w(p, T)
@@ -296,7 +223,7 @@ def _four3_lap(N, p, c):
     return s - t, m + np.abs(t)
 
 
-def _four3_resid(N, p, shape, T):
+def _four3_resid(N, _A, p, shape, T):
     f, fm = [], []
     for c in range(4):
         uc, a, b, d = (N(0, 0, 0, (c + t) % 4) for t in range(4))
@@ -307,7 +234,7 @@ def _four3_resid(N, p, shape, T):
     return f, fm
 
 
-def _four3_jvp(N, V, p, shape, T):
+def _four3_jvp(N, V, _A, p, shape, T):
     jv, jm = [], []
     for c in range(4):
         uc, a, b, d = (N(0, 0, 0, (c + t) % 4) for t in range(4))
@@ -320,7 +247,7 @@ def _four3_jvp(N, V, p, shape, T):
     return jv, jm
 
 
-def _four3_jac(N, p, shape, T):
+def _four3_jac(N, _A, p, shape, T):
     J = {}
     one = np.ones_like(N(0, 0, 0, 0))
     for c in range(4):
@@ -337,19 +264,13 @@ def _four3_jac(N, p, shape, T):
 
 
 # ------------------------------------------------------------------------------------------------ the cases
-class Problem:
-    def __init__(self, name, source, dof, stencil, boundary, params, resid, jvp, jac):
-        self.name, self.source, self.dof, self.stencil, self.boundary = name, source, dof, stencil, boundary
-        self.params, self._resid, self._jvp, self._jac = list(params), resid, jvp, jac
-
-
 PROBLEMS = {
-    "bratu3": Problem("bratu3", BRATU3_SRC, 1, "star", "dirichlet", [1.0, 0.04], _bratu3_resid, _bratu3_jvp, _bratu3_jac),
-    "brusselator3": Problem("brusselator3", BRUSSELATOR3_SRC, 2, "star", "periodic", BRUSSELATOR3_PARAMS, _brus3_resid,
+    "bratu3": Problem("bratu3", BRATU3_SRC, 3, 1, "star", "dirichlet", [1.0, 0.04], _bratu3_resid, _bratu3_jvp, _bratu3_jac),
+    "brusselator3": Problem("brusselator3", BRUSSELATOR3_SRC, 3, 2, "star", "periodic", BRUSSELATOR3_PARAMS, _brus3_resid,
                             _brus3_jvp, _brus3_jac),
-    "box3_dirichlet": Problem("box3_dirichlet", BOX3_SRC, 1, "box", "dirichlet", BOX3_PARAMS, _box3_resid, _box3_jvp, _box3_jac),
-    "box3_periodic": Problem("box3_periodic", BOX3_SRC, 1, "box", "periodic", BOX3_PARAMS, _box3_resid, _box3_jvp, _box3_jac),
-    "four3": Problem("four3", FOUR3_SRC, 4, "star", "dirichlet", FOUR3_PARAMS, _four3_resid, _four3_jvp, _four3_jac),
+    "box3_dirichlet": Problem("box3_dirichlet", BOX3_SRC, 3, 1, "box", "dirichlet", BOX3_PARAMS, _box3_resid, _box3_jvp, _box3_jac),
+    "box3_periodic": Problem("box3_periodic", BOX3_SRC, 3, 1, "box", "periodic", BOX3_PARAMS, _box3_resid, _box3_jvp, _box3_jac),
+    "four3": Problem("four3", FOUR3_SRC, 3, 4, "star", "dirichlet", FOUR3_PARAMS, _four3_resid, _four3_jvp, _four3_jac),
 }
 # 7·6·5: one ragged workgroup; 3·3·3: every node on the boundary; 37·29·3: 13 workgroups, planes of 1073 nodes;
 # 5·3·70: planes of 15 nodes, a wavefront spans more than four planes
@@ -367,90 +288,3 @@ __device__ void nk_point(const nk_nbhd3<T> &u, const nk_real *p, nk_site3 s, T *
   f[0] = u(0, 0, 0) * no_such_symbol;
 }
 """
-
-
-def inputs(prob, nx, ny, nz, seed=0):
-    """seeded u and v in [−1, 1], float64, length dof·nx·ny·nz"""
-    rng = np.random.default_rng(1000 * seed + 49 * nx + 7 * ny + nz + len(prob.name))
-    n = prob.dof * nx * ny * nz
-    return rng.uniform(-1.0, 1.0, n), rng.uniform(-1.0, 1.0, n)
-
-
-class Evaluation:
-    """one problem at one (u, v, p) in one arithmetic: f, Jv, CSR values, Jᵀv and the Σ|terms| of each entry"""
-
-
-def evaluate(prob, nx, ny, nz, u, v, T=np.float64, params=None):
-    p = [T(x) for x in (prob.params if params is None else params)]
-    dof, nn, shape = prob.dof, nx * ny * nz, (nx, ny, nz)
-    N = Grid3(np.asarray(u, dtype=T).reshape(dof, nz, ny, nx), prob.boundary)
-    V = Grid3(np.asarray(v, dtype=T).reshape(dof, nz, ny, nx), prob.boundary)
-    E = Evaluation()
-    f, fm = prob._resid(N, p, shape, T)
-    E.f, E.f_mag = np.concatenate([x.ravel() for x in f]), np.concatenate([x.ravel() for x in fm])
-    jv, jm = prob._jvp(N, V, p, shape, T)
-    E.jv, E.jv_mag = np.concatenate([x.ravel() for x in jv]), np.concatenate([x.ravel() for x in jm])
-    # CSR values: every analytic entry at the position the pattern assigns it; entries the formulas do not name are
-    # structural zeros
-    rowptr, cnt, rank, idx, inside, _o = slots(nx, ny, nz, dof, prob.stencil, prob.boundary)
-    offs = STENCILS[prob.stencil]
-    vals, mags = np.zeros(int(rowptr[-1]), dtype=T), np.zeros(int(rowptr[-1]), dtype=T)
-    for (r, di, dj, dk, c2), (val, mag) in prob._jac(N, p, shape, T).items():
-        q = offs.index((di, dj, dk))
-        nodes = np.nonzero(inside[:, q])[0]
-        pos = rowptr[r * nn + nodes] + c2 * cnt[nodes] + rank[nodes, q]
-        vals[pos] = np.broadcast_to(val, (nz, ny, nx)).ravel()[nodes]
-        mags[pos] = np.broadcast_to(mag, (nz, ny, nx)).ravel()[nodes]
-    E.vals, E.vals_mag = vals, mags
-    # Jᵀv and J·v from the values (the consistency test's matvec)
-    rp, ci = pattern(nx, ny, nz, dof, prob.stencil, prob.boundary)
-    rows = np.repeat(np.arange(dof * nn), np.diff(rp))
-    vv = np.asarray(v, dtype=T)
-    E.jtv, E.jtv_mag = np.zeros(dof * nn, dtype=T), np.zeros(dof * nn, dtype=T)
-    np.add.at(E.jtv, ci, vals * vv[rows])
-    np.add.at(E.jtv_mag, ci, np.abs(vals * vv[rows]))
-    E.spmv, E.spmv_mag = np.zeros(dof * nn, dtype=T), np.zeros(dof * nn, dtype=T)
-    np.add.at(E.spmv, rows, vals * vv[ci])
-    np.add.at(E.spmv_mag, rows, np.abs(vals * vv[ci]))
-    return E
-
-
-class Reference:
-    """float64 restatement, per-entry gap to long double and the bound 16·gap + 4 eps·Σ|terms| for f, jv, vals, jtv, spmv"""
-
-    def __init__(self, prob, nx, ny, nz, u, v, params=None):
-        a, b = evaluate(prob, nx, ny, nz, u, v, np.float64, params), evaluate(prob, nx, ny, nz, u, v, LD, params)
-        for k in ("f", "jv", "vals", "jtv", "spmv"):
-            x64, x80 = getattr(a, k), getattr(b, k)
-            gap = np.abs(x64.astype(LD) - x80).astype(np.float64)
-            setattr(self, k, x64)
-            setattr(self, k + "_gap", gap)
-            setattr(self, k + "_bound", MARGIN * gap + FLOOR_ULPS * EPS * getattr(a, k + "_mag"))
-
-
-_CACHE = {}
-
-
-def reference(name, nx, ny, nz, seed=0, params=None):
-    """the shared reference of a case (computed once, not modified by its users)"""
-    key = (name, nx, ny, nz, seed, None if params is None else tuple(params))
-    if key not in _CACHE:
-        prob = PROBLEMS[name]
-        u, v = inputs(prob, nx, ny, nz, seed)
-        R = Reference(prob, nx, ny, nz, u, v, params)
-        R.u, R.v = u, v
-        for arr in vars(R).values():
-            if isinstance(arr, np.ndarray):
-                arr.setflags(write=False)
-        _CACHE[key] = R
-    return _CACHE[key]
-
-
-def dense_jacobian(prob, nx, ny, nz, u, params=None):
-    """the float64 restatement's Jacobian as a dense matrix (small grids: the reference Newton of the solver tests)"""
-    E = evaluate(prob, nx, ny, nz, u, np.zeros_like(u), np.float64, params)
-    rp, ci = pattern(nx, ny, nz, prob.dof, prob.stencil, prob.boundary)
-    n = rp.size - 1
-    J = np.zeros((n, n))
-    J[np.repeat(np.arange(n), np.diff(rp)), ci] = E.vals
-    return J, E.f

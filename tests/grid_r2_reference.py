@@ -1,5 +1,5 @@
 """NumPy restatement of the compiled grid problems with a radius-2 stencil (csrc/nk_grid.hip: NK_GRID_STAR2 in 2-D and 3-D,
-NK_GRID_DIAMOND2 in 2-D), in the style of tests/grid_reference.py and tests/grid3_reference.py: the stencil's CSR pattern and
+NK_GRID_DIAMOND2 in 2-D), in the style of tests/grid_reference.py and tests/grid3_reference.py:
 eight pointwise problems, each written once as HIP source (what the library compiles) and once as NumPy formulas with their
 ANALYTIC derivatives, evaluated in float64 and in long double. From the formulas: the residual, J·v (the tangent written out by
 hand, term for term in the source's order), the values of J on the pattern, Jᵀv, and for every entry the gap
@@ -13,17 +13,14 @@ outside the grid reads 0 and has no column; a periodic index wraps by ± n.
 Stencil points in pattern order (ascending node index inside the grid):
 star2, 2-D     (0,−2) (0,−1) (−2,0) (−1,0) C (1,0) (2,0) (0,1) (0,2)
 diamond2, 2-D  (0,−2) (−1,−1) (0,−1) (1,−1) (−2,0) (−1,0) C (1,0) (2,0) (−1,1) (0,1) (1,1) (0,2)
-star2, 3-D     (0,0,−2) (0,0,−1) (0,−2,0) (0,−1,0) (−2,0,0) (−1,0,0) C (1,0,0) (2,0,0) (0,1,0) (0,2,0) (0,0,1) (0,0,2)"""
+star2, 3-D     (0,0,−2) (0,0,−1) (0,−2,0) (0,−1,0) (−2,0,0) (−1,0,0) C (1,0,0) (2,0,0) (0,1,0) (0,2,0) (0,0,1) (0,0,2)
+This module is the table: sources, formulas, problems and sizes. The pattern, the access to u and v, the evaluation in both
+arithmetics and the bound are tests/grid_core.py's."""
 import numpy as np
 
-from grid_reference import BOUNDARY_ID, EPS, FLOOR_ULPS, LD, MARGIN, _sum   # noqa: F401  (shared with radius 1)
+from grid_core import STENCILS, Problem, _site, _sum, _wsum
 
-STAR2 = [(0, -2), (0, -1), (-2, 0), (-1, 0), (0, 0), (1, 0), (2, 0), (0, 1), (0, 2)]
-DIAMOND2 = [(di, dj) for dj in range(-2, 3) for di in range(-2, 3) if abs(di) + abs(dj) <= 2]
-STAR2_3 = [(0, 0, -2), (0, 0, -1), (0, -2, 0), (0, -1, 0), (-2, 0, 0), (-1, 0, 0), (0, 0, 0), (1, 0, 0), (2, 0, 0), (0, 1, 0),
-           (0, 2, 0), (0, 0, 1), (0, 0, 2)]
-STENCILS = {(2, "star2"): STAR2, (2, "diamond2"): DIAMOND2, (3, "star2"): STAR2_3}
-STENCIL_ID = {"star2": 16, "diamond2": 17}
+DIAMOND2 = STENCILS[(2, "diamond2")]
 PERMITTED = [(2, "star2", 1), (2, "star2", 2), (2, "diamond2", 1), (3, "star2", 1), (3, "star2", 2)]   # (dim, stencil, dof)
 # the off-centre points of the stars in the order the sources add them: per direction −1 +1 −2 +2
 EIGHT = [(-1, 0), (1, 0), (-2, 0), (2, 0), (0, -1), (0, 1), (0, -2), (0, 2)]
@@ -32,88 +29,6 @@ NEAR2, FAR2 = [(-1, 0), (1, 0), (0, -1), (0, 1)], [(-2, 0), (2, 0), (0, -2), (0,
 DIAG2 = [(-1, -1), (1, -1), (-1, 1), (1, 1)]
 NEAR3 = [(-1, 0, 0), (1, 0, 0), (0, -1, 0), (0, 1, 0), (0, 0, -1), (0, 0, 1)]
 FAR3 = [(-2, 0, 0), (2, 0, 0), (0, -2, 0), (0, 2, 0), (0, 0, -2), (0, 0, 2)]
-
-
-# ------------------------------------------------------------------------------------------------ pattern
-def _coords(shape):
-    """(i, j[, k]) of every node, node = ((k·ny) + j)·nx + i"""
-    nn = int(np.prod(shape))
-    return np.unravel_index(np.arange(nn, dtype=np.int64), shape[::-1])[::-1]
-
-
-def neighbours(shape, stencil, boundary):
-    """(idx, inside): node index of every stencil point of every node ([nn, npts]; −1 outside a Dirichlet boundary)"""
-    offs, nn = STENCILS[(len(shape), stencil)], int(np.prod(shape))
-    at = _coords(shape)
-    idx = np.empty((nn, len(offs)), dtype=np.int64)
-    inside = np.empty((nn, len(offs)), dtype=bool)
-    for q, off in enumerate(offs):
-        pos = [x + d for x, d in zip(at, off)]
-        if boundary == "periodic":
-            pos = [x % n for x, n in zip(pos, shape)]
-            ok = np.ones(nn, dtype=bool)
-        else:
-            ok = np.logical_and.reduce([(x >= 0) & (x < n) for x, n in zip(pos, shape)])
-        lin = np.zeros(nn, dtype=np.int64)
-        for x, n in zip(pos[::-1], shape[::-1]):   # outermost direction first
-            lin = lin * n + np.where(ok, x, 0)
-        idx[:, q] = np.where(ok, lin, -1)
-        inside[:, q] = ok
-    return idx, inside
-
-
-def slots(shape, dof, stencil, boundary):
-    """(rowptr, cnt, rank, idx, inside, order): rank[node, q] = position of stencil point q among the node's in-domain points by
-    ascending node index; the entry (row c·nn + node, point q, component c2) sits at
-    rowptr[c·nn + node] + c2·cnt[node] + rank[node, q]"""
-    idx, inside = neighbours(shape, stencil, boundary)
-    key = np.where(inside, idx, np.iinfo(np.int64).max)
-    order = np.argsort(key, axis=1, kind="stable")
-    rank = np.empty_like(order)
-    np.put_along_axis(rank, order, np.broadcast_to(np.arange(order.shape[1]), order.shape), axis=1)
-    cnt = inside.sum(axis=1)
-    rowptr = np.concatenate([[0], np.cumsum(np.tile(cnt * dof, dof))]).astype(np.int64)
-    return rowptr, cnt, rank, idx, inside, order
-
-
-def pattern(shape, dof=1, stencil="star2", boundary="dirichlet"):
-    """CSR pattern (rowptr, colind), int32, columns ascending within a row, every (in-domain point) × (component) entry kept"""
-    nn = int(np.prod(shape))
-    rowptr, cnt, rank, idx, inside, order = slots(shape, dof, stencil, boundary)
-    sorted_idx = np.take_along_axis(idx, order, axis=1)                      # in-domain points first, ascending
-    valid = np.arange(sorted_idx.shape[1])[None, :] < cnt[:, None]           # [nn, npts]
-    cols = sorted_idx[:, None, :] + (np.arange(dof) * nn)[None, :, None]     # [nn, dof(c2), npts]
-    row0 = cols[np.broadcast_to(valid[:, None, :], cols.shape)]              # rows of component 0, flattened (node, c2, t)
-    return rowptr.astype(np.int32), np.tile(row0, dof).astype(np.int32)      # a row's columns do not depend on its component
-
-
-# ------------------------------------------------------------------------------------------------ grid access
-class Grid:
-    """neighbour access N(di, dj[, dk][, c]) on whole-grid arrays [dof, (nz,) ny, nx] of one floating-point type"""
-
-    def __init__(self, U, boundary):
-        self.U, self.boundary, self.dim = U, boundary, U.ndim - 1
-
-    def __call__(self, *a):
-        off, c = a[:self.dim], (a[self.dim] if len(a) > self.dim else 0)
-        A = self.U[c]
-        axes = tuple(range(self.dim))
-        if self.boundary == "periodic":
-            return np.roll(A, tuple(-d for d in off[::-1]), axis=axes)
-        P = np.zeros(tuple(n + 4 for n in A.shape), dtype=A.dtype)
-        P[(slice(2, -2),) * self.dim] = A
-        return P[tuple(slice(2 + d, 2 + d + n) for d, n in zip(off[::-1], A.shape))]
-
-
-def _site(shape):
-    """(i, j[, k]) as float64 arrays of the grid's shape [(nz,) ny, nx]"""
-    at = np.meshgrid(*[np.arange(n) for n in shape[::-1]], indexing="ij")[::-1]
-    return [x.astype(np.float64) for x in at]
-
-
-def _wsum(N, offs, w, c):
-    """Σ w[t]·N(offs[t], c), left to right, and Σ|terms|"""
-    return _sum([w[t] * N(*offs[t], c) for t in range(len(offs))])
 
 
 def _args(dim):
@@ -158,20 +73,20 @@ def _lap4_lin(N, T):
     return T(diag) * c - T(16) * s1 + s2, T(diag) * np.abs(c) + T(16) * m1 + m2
 
 
-def _lap4_resid(N, p, shape, T):
+def _lap4_resid(N, _A, p, shape, T):
     lap, ml = _lap4_lin(N, T)
     e = p[1] * np.exp(N(*(0,) * N.dim))
     return [p[0] * lap - e], [np.abs(p[0]) * ml + np.abs(e)]
 
 
-def _lap4_jvp(N, V, p, shape, T):
+def _lap4_jvp(N, V, _A, p, shape, T):
     z = (0,) * N.dim
     lap, ml = _lap4_lin(V, T)
     e = p[1] * (np.exp(N(*z)) * V(*z))
     return [p[0] * lap - e], [np.abs(p[0]) * ml + np.abs(e)]
 
 
-def _lap4_jac(N, p, shape, T):
+def _lap4_jac(N, _A, p, shape, T):
     dim = N.dim
     near, far, diag = (NEAR2, FAR2, 60) if dim == 2 else (NEAR3, FAR3, 90)
     z = (0,) * dim
@@ -238,7 +153,7 @@ def _upwind_lin(N, p, c):
     return s - t, ms + np.abs(t)
 
 
-def _upwind_resid(N, p, shape, T):
+def _upwind_resid(N, _A, p, shape, T):
     m, z = (8 if N.dim == 2 else 12), (0,) * N.dim
     la, ma = _upwind_lin(N, p, 0)
     lb, mb = _upwind_lin(N, p, 1)
@@ -247,7 +162,7 @@ def _upwind_resid(N, p, shape, T):
     return [la + ab + g, lb - ab], [ma + np.abs(ab) + np.abs(g), mb + np.abs(ab)]
 
 
-def _upwind_jvp(N, V, p, shape, T):
+def _upwind_jvp(N, V, _A, p, shape, T):
     m, z = (8 if N.dim == 2 else 12), (0,) * N.dim
     la, ma = _upwind_lin(V, p, 0)
     lb, mb = _upwind_lin(V, p, 1)
@@ -258,7 +173,7 @@ def _upwind_jvp(N, V, p, shape, T):
     return [la + d, lb - d], [ma + md, mb + md]
 
 
-def _upwind_jac(N, p, shape, T):
+def _upwind_jac(N, _A, p, shape, T):
     dim = N.dim
     offs = EIGHT if dim == 2 else TWELVE
     m, z = len(offs), (0,) * dim
@@ -302,14 +217,14 @@ def _sh_lin(N, p, T):
     return t0 - T(2) * lap - bih, np.abs(t0) + T(2) * mlap + mbih
 
 
-def _sh_resid(N, p, shape, T):
+def _sh_resid(N, _A, p, shape, T):
     c = N(0, 0)
     lin, ml = _sh_lin(N, p, T)
     c3 = c * c * c
     return [lin - c3], [ml + np.abs(c3)]
 
 
-def _sh_jvp(N, V, p, shape, T):
+def _sh_jvp(N, V, _A, p, shape, T):
     c, dc = N(0, 0), V(0, 0)
     lin, ml = _sh_lin(V, p, T)
     t1, t2, t3 = dc * c, c * dc, (c * c) * dc         # d(c·c) = dc·c + c·dc ; d((c·c)·c) = d(c·c)·c + (c·c)·dc
@@ -317,7 +232,7 @@ def _sh_jvp(N, V, p, shape, T):
     return [lin - d3], [ml + (np.abs(t1) + np.abs(t2)) * np.abs(c) + np.abs(t3)]
 
 
-def _sh_jac(N, p, shape, T):
+def _sh_jac(N, _A, p, shape, T):
     c = N(0, 0)
     one = np.ones_like(c)
     d3 = (c + c) * c + c * c
@@ -357,14 +272,14 @@ def _diamond_w(p, T):
     return [p[0] + p[1] * T(di + 5 * dj) for (di, dj) in DIAMOND2]
 
 
-def _diamond_resid(N, p, shape, T):
+def _diamond_resid(N, _A, p, shape, T):
     acc, m = _wsum(N, DIAMOND2, _diamond_w(p, T), 0)
     c = N(0, 0)
     e = ((p[2] * c) * c) * c
     return [acc + e], [m + np.abs(e)]
 
 
-def _diamond_jvp(N, V, p, shape, T):
+def _diamond_jvp(N, V, _A, p, shape, T):
     acc, m = _wsum(V, DIAMOND2, _diamond_w(p, T), 0)
     c, dc = N(0, 0), V(0, 0)
     t1, t2, t3 = (dc * p[2]) * c, (p[2] * c) * dc, ((p[2] * c) * c) * dc     # the dual's product rule in the source's order
@@ -372,7 +287,7 @@ def _diamond_jvp(N, V, p, shape, T):
     return [acc + e], [m + (np.abs(t1) + np.abs(t2)) * np.abs(c) + np.abs(t3)]
 
 
-def _diamond_jac(N, p, shape, T):
+def _diamond_jac(N, _A, p, shape, T):
     c = N(0, 0)
     one = np.ones_like(c)
     w = _diamond_w(p, T)
@@ -386,23 +301,17 @@ def _diamond_jac(N, p, shape, T):
 
 
 # ------------------------------------------------------------------------------------------------ the cases
-class Problem:
-    def __init__(self, name, dim, source, dof, stencil, boundary, params, resid, jvp, jac):
-        self.name, self.dim, self.source, self.dof, self.stencil, self.boundary = name, dim, source, dof, stencil, boundary
-        self.params, self._resid, self._jvp, self._jac = list(params), resid, jvp, jac
-
-
 _UP = (_upwind_resid, _upwind_jvp, _upwind_jac)
 PROBLEMS = {
-    "lap4": Problem("lap4", 2, LAP4_SRC, 1, "star2", "dirichlet", [1.0, 0.04], _lap4_resid, _lap4_jvp, _lap4_jac),
-    "upwind2_dirichlet": Problem("upwind2_dirichlet", 2, UPWIND2_SRC, 2, "star2", "dirichlet", UPWIND2_PARAMS, *_UP),
-    "upwind2_periodic": Problem("upwind2_periodic", 2, UPWIND2_SRC, 2, "star2", "periodic", UPWIND2_PARAMS, *_UP),
-    "sh": Problem("sh", 2, SH_SRC, 1, "diamond2", "periodic", SH_PARAMS, _sh_resid, _sh_jvp, _sh_jac),
-    "diamond_dirichlet": Problem("diamond_dirichlet", 2, DIAMOND_SRC, 1, "diamond2", "dirichlet", DIAMOND_PARAMS, _diamond_resid,
+    "lap4": Problem("lap4", LAP4_SRC, 2, 1, "star2", "dirichlet", [1.0, 0.04], _lap4_resid, _lap4_jvp, _lap4_jac),
+    "upwind2_dirichlet": Problem("upwind2_dirichlet", UPWIND2_SRC, 2, 2, "star2", "dirichlet", UPWIND2_PARAMS, *_UP),
+    "upwind2_periodic": Problem("upwind2_periodic", UPWIND2_SRC, 2, 2, "star2", "periodic", UPWIND2_PARAMS, *_UP),
+    "sh": Problem("sh", SH_SRC, 2, 1, "diamond2", "periodic", SH_PARAMS, _sh_resid, _sh_jvp, _sh_jac),
+    "diamond_dirichlet": Problem("diamond_dirichlet", DIAMOND_SRC, 2, 1, "diamond2", "dirichlet", DIAMOND_PARAMS, _diamond_resid,
                                  _diamond_jvp, _diamond_jac),
-    "lap4_3": Problem("lap4_3", 3, LAP4_3_SRC, 1, "star2", "dirichlet", [1.0, 0.04], _lap4_resid, _lap4_jvp, _lap4_jac),
-    "upwind3_dirichlet": Problem("upwind3_dirichlet", 3, UPWIND3_SRC, 2, "star2", "dirichlet", UPWIND3_PARAMS, *_UP),
-    "upwind3_periodic": Problem("upwind3_periodic", 3, UPWIND3_SRC, 2, "star2", "periodic", UPWIND3_PARAMS, *_UP),
+    "lap4_3": Problem("lap4_3", LAP4_3_SRC, 3, 1, "star2", "dirichlet", [1.0, 0.04], _lap4_resid, _lap4_jvp, _lap4_jac),
+    "upwind3_dirichlet": Problem("upwind3_dirichlet", UPWIND3_SRC, 3, 2, "star2", "dirichlet", UPWIND3_PARAMS, *_UP),
+    "upwind3_periodic": Problem("upwind3_periodic", UPWIND3_SRC, 3, 2, "star2", "periodic", UPWIND3_PARAMS, *_UP),
 }
 # 5 × 5: every periodic row wraps in both layers both ways, every Dirichlet node misses points; 37 × 29 = 1073 nodes: five
 # workgroups, the last ragged; 300 × 5: a wavefront spans lines
@@ -417,93 +326,3 @@ OUTSIDE_SRC = {
     "star2_3": _head(3) + "  f[0] = 6.0 * u(0, 0, 0) - u(1, 1, 0) - u(0, 0, -2);\n}\n",
 }
 SYNTAX_ERROR_SRC = _head(2) + "  f[0] = u(0, 2) * no_such_symbol;\n}\n"
-
-
-def inputs(prob, shape, seed=0):
-    """seeded u and v in [−1, 1], float64, length dof·nn"""
-    rng = np.random.default_rng(1000 * seed + sum(w * n for w, n in zip((49, 7, 1), shape)) + len(prob.name))
-    n = prob.dof * int(np.prod(shape))
-    return rng.uniform(-1.0, 1.0, n), rng.uniform(-1.0, 1.0, n)
-
-
-class Evaluation:
-    """one problem at one (u, v, p) in one arithmetic: f, Jv, CSR values, Jᵀv and the Σ|terms| of each entry"""
-
-
-def evaluate(prob, shape, u, v, T=np.float64, params=None):
-    shape = tuple(shape)
-    p = [T(x) for x in (prob.params if params is None else params)]
-    dof, nn, dim = prob.dof, int(np.prod(shape)), len(shape)
-    N = Grid(np.asarray(u, dtype=T).reshape(dof, *shape[::-1]), prob.boundary)
-    V = Grid(np.asarray(v, dtype=T).reshape(dof, *shape[::-1]), prob.boundary)
-    E = Evaluation()
-    f, fm = prob._resid(N, p, shape, T)
-    E.f, E.f_mag = np.concatenate([x.ravel() for x in f]), np.concatenate([x.ravel() for x in fm])
-    jv, jm = prob._jvp(N, V, p, shape, T)
-    E.jv, E.jv_mag = np.concatenate([x.ravel() for x in jv]), np.concatenate([x.ravel() for x in jm])
-    # CSR values: every analytic entry at the position the pattern assigns it; entries the formulas do not name are
-    # structural zeros
-    rowptr, cnt, rank, idx, inside, _o = slots(shape, dof, prob.stencil, prob.boundary)
-    offs = STENCILS[(dim, prob.stencil)]
-    vals, mags = np.zeros(int(rowptr[-1]), dtype=T), np.zeros(int(rowptr[-1]), dtype=T)
-    for key, (val, mag) in prob._jac(N, p, shape, T).items():
-        r, off, c2 = key[0], tuple(key[1:1 + dim]), key[1 + dim]
-        q = offs.index(off)
-        nodes = np.nonzero(inside[:, q])[0]
-        pos = rowptr[r * nn + nodes] + c2 * cnt[nodes] + rank[nodes, q]
-        vals[pos] = np.broadcast_to(val, shape[::-1]).ravel()[nodes]
-        mags[pos] = np.broadcast_to(mag, shape[::-1]).ravel()[nodes]
-    E.vals, E.vals_mag = vals, mags
-    # Jᵀv and J·v from the values (the consistency test's matvec)
-    rp, ci = pattern(shape, dof, prob.stencil, prob.boundary)
-    rows = np.repeat(np.arange(dof * nn), np.diff(rp))
-    vv = np.asarray(v, dtype=T)
-    E.jtv, E.jtv_mag = np.zeros(dof * nn, dtype=T), np.zeros(dof * nn, dtype=T)
-    np.add.at(E.jtv, ci, vals * vv[rows])
-    np.add.at(E.jtv_mag, ci, np.abs(vals * vv[rows]))
-    E.spmv, E.spmv_mag = np.zeros(dof * nn, dtype=T), np.zeros(dof * nn, dtype=T)
-    np.add.at(E.spmv, rows, vals * vv[ci])
-    np.add.at(E.spmv_mag, rows, np.abs(vals * vv[ci]))
-    return E
-
-
-class Reference:
-    """float64 restatement, per-entry gap to long double and the bound 16·gap + 4 eps·Σ|terms| for f, jv, vals, jtv, spmv"""
-
-    def __init__(self, prob, shape, u, v, params=None):
-        a, b = evaluate(prob, shape, u, v, np.float64, params), evaluate(prob, shape, u, v, LD, params)
-        for k in ("f", "jv", "vals", "jtv", "spmv"):
-            x64, x80 = getattr(a, k), getattr(b, k)
-            gap = np.abs(x64.astype(LD) - x80).astype(np.float64)
-            setattr(self, k, x64)
-            setattr(self, k + "_gap", gap)
-            setattr(self, k + "_bound", MARGIN * gap + FLOOR_ULPS * EPS * getattr(a, k + "_mag"))
-
-
-_CACHE = {}
-
-
-def reference(name, shape, seed=0, params=None):
-    """the shared reference of a case (computed once, not modified by its users)"""
-    shape = tuple(shape)
-    key = (name, shape, seed, None if params is None else tuple(params))
-    if key not in _CACHE:
-        prob = PROBLEMS[name]
-        u, v = inputs(prob, shape, seed)
-        R = Reference(prob, shape, u, v, params)
-        R.u, R.v = u, v
-        for arr in vars(R).values():
-            if isinstance(arr, np.ndarray):
-                arr.setflags(write=False)
-        _CACHE[key] = R
-    return _CACHE[key]
-
-
-def dense_jacobian(prob, shape, u, params=None):
-    """the float64 restatement's Jacobian as a dense matrix (small grids: the reference Newton of the solver tests)"""
-    E = evaluate(prob, shape, u, np.zeros_like(u), np.float64, params)
-    rp, ci = pattern(shape, prob.dof, prob.stencil, prob.boundary)
-    n = rp.size - 1
-    J = np.zeros((n, n))
-    J[np.repeat(np.arange(n), np.diff(rp)), ci] = E.vals
-    return J, E.f

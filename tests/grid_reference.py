@@ -1,4 +1,4 @@
-"""NumPy restatement of the compiled grid problems (csrc/nk_grid.hip): the stencil's CSR pattern, three pointwise problems —
+"""NumPy restatement of the compiled grid problems (csrc/nk_grid.hip): three pointwise problems —
 Bratu, the Brusselator with its disc forcing, a two-component 9-point box problem with a cross term — each written once as HIP
 source (what the library compiles) and once as NumPy formulas with their ANALYTIC derivatives, evaluated in float64 and in long
 double. From the formulas: the residual, J·v (the tangent of the residual written out by hand, term for term in the source's
@@ -8,94 +8,12 @@ values of the entry's terms, which together make the bound the device tests use 
     |device − float64 restatement| <= 16 × gap + 4 eps × Σ|terms|
 
 Layout: unknown c of node (i, j) is element c·nx·ny + j·nx + i. Seeded inputs have |u| <= 1.
-Stencil points in pattern order (ascending node index inside the grid): star S W C E N, box row by row."""
+Stencil points in pattern order (ascending node index inside the grid): star S W C E N, box row by row.
+This module is the table: sources, formulas, problems and sizes. The pattern, the access to u and v, the evaluation in both
+arithmetics and the bound are tests/grid_core.py's."""
 import numpy as np
 
-EPS = float(np.finfo(np.float64).eps)
-LD = np.longdouble
-MARGIN, FLOOR_ULPS = 16.0, 4.0
-
-STAR = [(0, -1), (-1, 0), (0, 0), (1, 0), (0, 1)]                       # (di, dj)
-BOX = [(di, dj) for dj in (-1, 0, 1) for di in (-1, 0, 1)]
-STENCILS = {"star": STAR, "box": BOX}
-STENCIL_ID = {"star": 0, "box": 1}
-BOUNDARY_ID = {"dirichlet": 0, "periodic": 1}
-
-
-# ------------------------------------------------------------------------------------------------ pattern
-def neighbours(nx, ny, stencil, boundary):
-    """(idx, inside): node index of every stencil point of every node ([nn, npts]; −1 outside a Dirichlet boundary)"""
-    offs = STENCILS[stencil]
-    j, i = np.divmod(np.arange(nx * ny, dtype=np.int64), nx)
-    idx = np.empty((nx * ny, len(offs)), dtype=np.int64)
-    inside = np.empty((nx * ny, len(offs)), dtype=bool)
-    for q, (di, dj) in enumerate(offs):
-        ii, jj = i + di, j + dj
-        if boundary == "periodic":
-            ii, jj = ii % nx, jj % ny
-            ok = np.ones(nx * ny, dtype=bool)
-        else:
-            ok = (ii >= 0) & (ii < nx) & (jj >= 0) & (jj < ny)
-        idx[:, q] = np.where(ok, jj * nx + ii, -1)
-        inside[:, q] = ok
-    return idx, inside
-
-
-def slots(nx, ny, dof, stencil, boundary):
-    """(rowptr, cnt, rank): rank[node, q] = position of stencil point q among the node's in-domain points by ascending node index;
-    the entry (row c·nn + node, point q, component c2) sits at rowptr[c·nn + node] + c2·cnt[node] + rank[node, q]"""
-    idx, inside = neighbours(nx, ny, stencil, boundary)
-    key = np.where(inside, idx, np.iinfo(np.int64).max)
-    order = np.argsort(key, axis=1, kind="stable")
-    rank = np.empty_like(order)
-    np.put_along_axis(rank, order, np.broadcast_to(np.arange(order.shape[1]), order.shape), axis=1)
-    cnt = inside.sum(axis=1)
-    rowlen = np.tile(cnt * dof, dof)
-    rowptr = np.concatenate([[0], np.cumsum(rowlen)]).astype(np.int64)
-    return rowptr, cnt, rank, idx, inside, order
-
-
-def pattern(nx, ny, dof=1, stencil="star", boundary="dirichlet"):
-    """CSR pattern (rowptr, colind), int32, columns ascending within a row, every (in-domain point) × (component) entry kept"""
-    nn = nx * ny
-    rowptr, cnt, rank, idx, inside, order = slots(nx, ny, dof, stencil, boundary)
-    sorted_idx = np.take_along_axis(idx, order, axis=1)                      # in-domain points first, ascending
-    valid = np.arange(sorted_idx.shape[1])[None, :] < cnt[:, None]           # [nn, npts]
-    cols = sorted_idx[:, None, :] + (np.arange(dof) * nn)[None, :, None]     # [nn, dof(c2), npts]
-    row0 = cols[np.broadcast_to(valid[:, None, :], cols.shape)]              # rows of component 0, flattened (node, c2, t)
-    colind = np.tile(row0, dof)                                              # a row's columns do not depend on its component
-    return rowptr.astype(np.int32), colind.astype(np.int32)
-
-
-# ------------------------------------------------------------------------------------------------ grid access
-class Grid:
-    """neighbour access N(di, dj, c) on whole-grid arrays [dof, ny, nx] of one floating-point type"""
-
-    def __init__(self, U, boundary):
-        self.U, self.boundary = U, boundary
-        self.dof, self.ny, self.nx = U.shape
-
-    def __call__(self, di, dj, c=0):
-        A = self.U[c]
-        if self.boundary == "periodic":
-            return np.roll(A, (-dj, -di), axis=(0, 1))
-        P = np.zeros((self.ny + 2, self.nx + 2), dtype=A.dtype)
-        P[1:-1, 1:-1] = A
-        return P[1 + dj:1 + dj + self.ny, 1 + di:1 + di + self.nx]
-
-
-def _site(nx, ny, T):
-    j, i = np.meshgrid(np.arange(ny), np.arange(nx), indexing="ij")
-    return i.astype(T), j.astype(T)
-
-
-def _sum(terms):
-    """left-to-right sum of the terms and the sum of their absolute values"""
-    s, m = terms[0], np.abs(terms[0])
-    for t in terms[1:]:
-        s = s + t
-        m = m + np.abs(t)
-    return s, m
+from grid_core import Problem, _site, _sum
 
 
 # ------------------------------------------------------------------------------------------------ Bratu
@@ -114,21 +32,21 @@ def bratu_params(n, lam=6.0):
     return [(h * h) / (h * h), (h * h) * lam]
 
 
-def _bratu_resid(N, p, nx, ny, T):
+def _bratu_resid(N, _A, p, shape, T):
     c = N(0, 0)
     lap, ml = _sum([T(4) * c, -N(-1, 0), -N(1, 0), -N(0, -1), -N(0, 1)])
     e = p[1] * np.exp(c)
     return [p[0] * lap - e], [np.abs(p[0]) * ml + np.abs(e)]
 
 
-def _bratu_jvp(N, V, p, nx, ny, T):
+def _bratu_jvp(N, V, _A, p, shape, T):
     c = N(0, 0)
     lap, ml = _sum([T(4) * V(0, 0), -V(-1, 0), -V(1, 0), -V(0, -1), -V(0, 1)])
     e = p[1] * (np.exp(c) * V(0, 0))
     return [p[0] * lap - e], [np.abs(p[0]) * ml + np.abs(e)]
 
 
-def _bratu_jac(N, p, nx, ny, T):
+def _bratu_jac(N, _A, p, shape, T):
     c = N(0, 0)
     one = np.ones_like(c)
     e = p[1] * np.exp(c)
@@ -161,10 +79,11 @@ def brusselator_params(N, A=3.4, B=1.0, alpha=10.0, dx=None):
     return [A, B, alpha / (dx * dx)]
 
 
-def _brus_forcing(nx, ny, T):
+def _brus_forcing(shape, T):
+    nx, ny = shape
     # the disc is decided in float64 in both arithmetics (the source decides it in double): the two restatements then differ by
     # rounding only
-    i, j = _site(nx, ny, np.float64)
+    i, j = _site(shape)
     x, y = i / np.float64(nx - 1), j / np.float64(ny - 1)
     return np.where(((x - 0.3) * (x - 0.3) + (y - 0.6) * (y - 0.6)) <= 0.1 * 0.1, 5.0, 0.0).astype(T)
 
@@ -173,18 +92,18 @@ def _brus_lap(N, c, T):
     return _sum([N(-1, 0, c), N(1, 0, c), -(T(4) * N(0, 0, c)), N(0, 1, c), N(0, -1, c)])
 
 
-def _brus_resid(N, p, nx, ny, T):
+def _brus_resid(N, _A, p, shape, T):
     A, B, al = p
     uu, vv = N(0, 0, 0), N(0, 0, 1)
     lu, mu = _brus_lap(N, 0, T)
     lv, mv = _brus_lap(N, 1, T)
-    bf = _brus_forcing(nx, ny, T)
+    bf = _brus_forcing(shape, T)
     f0, m0 = _sum([al * lu, B * np.ones_like(uu), uu * uu * vv, -((A + T(1)) * uu), bf])
     f1, m1 = _sum([al * lv, A * uu, -(uu * uu * vv)])
     return [f0, f1], [m0 - np.abs(al * lu) + np.abs(al) * mu, m1 - np.abs(al * lv) + np.abs(al) * mv]
 
 
-def _brus_jvp(N, V, p, nx, ny, T):
+def _brus_jvp(N, V, _A, p, shape, T):
     A, B, al = p
     uu, vv, a, b = N(0, 0, 0), N(0, 0, 1), V(0, 0, 0), V(0, 0, 1)
     la, ma = _brus_lap(V, 0, T)
@@ -199,7 +118,7 @@ def _brus_jvp(N, V, p, nx, ny, T):
     return [jv0, jv1], [np.abs(al) * ma + m3 + np.abs(t4), np.abs(al) * mb + np.abs(A * a) + m3]
 
 
-def _brus_jac(N, p, nx, ny, T):
+def _brus_jac(N, _A, p, shape, T):
     A, B, al = p
     uu, vv = N(0, 0, 0), N(0, 0, 1)
     one = np.ones_like(uu)
@@ -242,7 +161,7 @@ def _box_cross(N, c):
     return _sum([N(1, 1, c), -N(1, -1, c), -N(-1, 1, c), N(-1, -1, c)])
 
 
-def _box_resid(N, p, nx, ny, T):
+def _box_resid(N, _A, p, shape, T):
     a, b = N(0, 0, 0), N(0, 0, 1)
     la, mla = _box_lap(N, 0, T)
     lb, mlb = _box_lap(N, 1, T)
@@ -255,7 +174,7 @@ def _box_resid(N, p, nx, ny, T):
                       np.abs(p[0]) * mlb + np.abs(p[1]) * mxb * np.abs(a) + np.abs(a * b)]
 
 
-def _box_jvp(N, V, p, nx, ny, T):
+def _box_jvp(N, V, _A, p, shape, T):
     a, b, da, db = N(0, 0, 0), N(0, 0, 1), V(0, 0, 0), V(0, 0, 1)
     la, mla = _box_lap(V, 0, T)
     lb, mlb = _box_lap(V, 1, T)
@@ -272,7 +191,7 @@ def _box_jvp(N, V, p, nx, ny, T):
     return [p[0] * la + t0 + e, p[0] * lb + t1 - ab], [m0, m1]
 
 
-def _box_jac(N, p, nx, ny, T):
+def _box_jac(N, _A, p, shape, T):
     a, b = N(0, 0, 0), N(0, 0, 1)
     one = np.ones_like(a)
     xa, mxa = _box_cross(N, 0)
@@ -294,18 +213,17 @@ def _box_jac(N, p, nx, ny, T):
 
 
 # ------------------------------------------------------------------------------------------------ the cases
-class Problem:
-    def __init__(self, name, source, dof, stencil, boundary, params, resid, jvp, jac):
-        self.name, self.source, self.dof, self.stencil, self.boundary = name, source, dof, stencil, boundary
-        self.params, self._resid, self._jvp, self._jac = list(params), resid, jvp, jac
+def _problem(name, source, dof, stencil, boundary, params, *formulas):
+    """(this table's inputs are seeded with 7·nx + ny)"""
+    return Problem(name, source, 2, dof, stencil, boundary, params, *formulas, seed_weights=(7, 1))
 
 
 PROBLEMS = {
-    "bratu": Problem("bratu", BRATU_SRC, 1, "star", "dirichlet", [1.0, 0.04], _bratu_resid, _bratu_jvp, _bratu_jac),
-    "brusselator": Problem("brusselator", BRUSSELATOR_SRC, 2, "star", "periodic", [3.4, 1.0, 40.0], _brus_resid, _brus_jvp,
-                           _brus_jac),
-    "box_dirichlet": Problem("box_dirichlet", BOX_SRC, 2, "box", "dirichlet", BOX_PARAMS, _box_resid, _box_jvp, _box_jac),
-    "box_periodic": Problem("box_periodic", BOX_SRC, 2, "box", "periodic", BOX_PARAMS, _box_resid, _box_jvp, _box_jac),
+    "bratu": _problem("bratu", BRATU_SRC, 1, "star", "dirichlet", [1.0, 0.04], _bratu_resid, _bratu_jvp, _bratu_jac),
+    "brusselator": _problem("brusselator", BRUSSELATOR_SRC, 2, "star", "periodic", [3.4, 1.0, 40.0], _brus_resid, _brus_jvp,
+                            _brus_jac),
+    "box_dirichlet": _problem("box_dirichlet", BOX_SRC, 2, "box", "dirichlet", BOX_PARAMS, _box_resid, _box_jvp, _box_jac),
+    "box_periodic": _problem("box_periodic", BOX_SRC, 2, "box", "periodic", BOX_PARAMS, _box_resid, _box_jvp, _box_jac),
 }
 SIZES = [(37, 29), (3, 3), (300, 5)]   # 37 × 29 = 1073 nodes: five workgroups of 256, the last one ragged
 # a star source that reads a corner: the residual is NaN at every node
@@ -321,83 +239,6 @@ __device__ void nk_point(const nk_nbhd<T> &u, const nk_real *p, nk_site s, T *f)
   f[0] = u(0, 0) * no_such_symbol;
 }
 """
-
-
-def inputs(prob, nx, ny, seed=0):
-    """seeded u and v in [−1, 1], float64, length dof·nx·ny"""
-    rng = np.random.default_rng(1000 * seed + 7 * nx + ny + len(prob.name))
-    n = prob.dof * nx * ny
-    return rng.uniform(-1.0, 1.0, n), rng.uniform(-1.0, 1.0, n)
-
-
-class Evaluation:
-    """one problem at one (u, v, p) in one arithmetic: f, Jv, CSR values, Jᵀv and the Σ|terms| of each entry"""
-
-
-def evaluate(prob, nx, ny, u, v, T=np.float64, params=None):
-    p = [T(x) for x in (prob.params if params is None else params)]
-    dof, nn = prob.dof, nx * ny
-    N = Grid(np.asarray(u, dtype=T).reshape(dof, ny, nx), prob.boundary)
-    V = Grid(np.asarray(v, dtype=T).reshape(dof, ny, nx), prob.boundary)
-    E = Evaluation()
-    f, fm = prob._resid(N, p, nx, ny, T)
-    E.f, E.f_mag = np.concatenate([x.ravel() for x in f]), np.concatenate([x.ravel() for x in fm])
-    jv, jm = prob._jvp(N, V, p, nx, ny, T)
-    E.jv, E.jv_mag = np.concatenate([x.ravel() for x in jv]), np.concatenate([x.ravel() for x in jm])
-    # CSR values: every analytic entry at the position the pattern assigns it; entries the formulas do not name are
-    # structural zeros
-    rowptr, cnt, rank, idx, inside, _o = slots(nx, ny, dof, prob.stencil, prob.boundary)
-    offs = STENCILS[prob.stencil]
-    vals, mags = np.zeros(int(rowptr[-1]), dtype=T), np.zeros(int(rowptr[-1]), dtype=T)
-    for (r, di, dj, c2), (val, mag) in prob._jac(N, p, nx, ny, T).items():
-        q = offs.index((di, dj))
-        nodes = np.nonzero(inside[:, q])[0]
-        pos = rowptr[r * nn + nodes] + c2 * cnt[nodes] + rank[nodes, q]
-        vals[pos] = np.broadcast_to(val, (ny, nx)).ravel()[nodes]
-        mags[pos] = np.broadcast_to(mag, (ny, nx)).ravel()[nodes]
-    E.vals, E.vals_mag = vals, mags
-    # Jᵀv and J·v from the values (the consistency test's matvec)
-    rp, ci = pattern(nx, ny, dof, prob.stencil, prob.boundary)
-    rows = np.repeat(np.arange(dof * nn), np.diff(rp))
-    vv = np.asarray(v, dtype=T)
-    E.jtv, E.jtv_mag = np.zeros(dof * nn, dtype=T), np.zeros(dof * nn, dtype=T)
-    np.add.at(E.jtv, ci, vals * vv[rows])
-    np.add.at(E.jtv_mag, ci, np.abs(vals * vv[rows]))
-    E.spmv, E.spmv_mag = np.zeros(dof * nn, dtype=T), np.zeros(dof * nn, dtype=T)
-    np.add.at(E.spmv, rows, vals * vv[ci])
-    np.add.at(E.spmv_mag, rows, np.abs(vals * vv[ci]))
-    return E
-
-
-class Reference:
-    """float64 restatement, per-entry gap to long double and the bound 16·gap + 4 eps·Σ|terms| for f, jv, vals, jtv, spmv"""
-
-    def __init__(self, prob, nx, ny, u, v, params=None):
-        a, b = evaluate(prob, nx, ny, u, v, np.float64, params), evaluate(prob, nx, ny, u, v, LD, params)
-        for k in ("f", "jv", "vals", "jtv", "spmv"):
-            x64, x80 = getattr(a, k), getattr(b, k)
-            gap = np.abs(x64.astype(LD) - x80).astype(np.float64)
-            setattr(self, k, x64)
-            setattr(self, k + "_gap", gap)
-            setattr(self, k + "_bound", MARGIN * gap + FLOOR_ULPS * EPS * getattr(a, k + "_mag"))
-
-
-_CACHE = {}
-
-
-def reference(name, nx, ny, seed=0, params=None):
-    """the shared reference of a case (computed once, not modified by its users)"""
-    key = (name, nx, ny, seed, None if params is None else tuple(params))
-    if key not in _CACHE:
-        prob = PROBLEMS[name]
-        u, v = inputs(prob, nx, ny, seed)
-        R = Reference(prob, nx, ny, u, v, params)
-        R.u, R.v = u, v
-        for arr in vars(R).values():
-            if isinstance(arr, np.ndarray):
-                arr.setflags(write=False)
-        _CACHE[key] = R
-    return _CACHE[key]
 
 
 def bratu_builtin_pattern(ns):

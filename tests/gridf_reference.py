@@ -1,5 +1,5 @@
 """NumPy restatement of the compiled grid problems WITH FIELDS (csrc/nk_grid.hip, nk_problem_create_grid_fields), in the style
-of tests/grid_reference.py, whose patterns and slots (and those of grid3_reference / grid_r2_reference) it imports: problems that
+of tests/grid_reference.py: problems that
 read read-only data on the grid — a previous time level, a face-averaged coefficient, a source term — each written once as HIP
 source (what the library compiles) and once as NumPy formulas with their ANALYTIC derivatives, evaluated in float64 and in long
 double. From the formulas: the residual, J·v (the tangent written out by hand, term for term in the source's order), the values
@@ -10,63 +10,15 @@ terms — the bound the device tests use:
 
 Fields: field k of node m is element k·nn + m. A field is read through the stencil's offsets; at a periodic boundary the index
 wraps, outside a Dirichlet boundary the read returns THE FIELD AT THE NODE ITSELF (u reads 0 there). Fields are constants of the
-differentiation: no column, no partial. Seeded fields are 1 + 0.37·sin(0.9·m + k): positive, distinct at every node."""
+differentiation: no column, no partial. Seeded fields are 1 + 0.37·sin(0.9·m + k): positive, distinct at every node.
+This module is the table: sources, formulas, problems and sizes. The pattern, the access to u, v and the fields, the evaluation in both
+arithmetics and the bound are tests/grid_core.py's."""
 import numpy as np
 
 import grid3_reference as G3
 import grid_r2_reference as G2
 import grid_reference as G1
-from grid_reference import BOUNDARY_ID, EPS, FLOOR_ULPS, LD, MARGIN, _sum   # noqa: F401  (shared)
-from grid_r2_reference import Grid                                          # u's access: 0 outside a Dirichlet boundary
-
-STENCIL_ID = {"star": 0, "box": 1, "star2": 16, "diamond2": 17}
-
-
-# ------------------------------------------------------------------------------------------------ pattern (imported, by shape)
-def offsets(dim, stencil):
-    if stencil in G2.STENCIL_ID:
-        return G2.STENCILS[(dim, stencil)]
-    return (G3 if dim == 3 else G1).STENCILS[stencil]
-
-
-def slots(shape, dof, stencil, boundary):
-    if stencil in G2.STENCIL_ID:
-        return G2.slots(tuple(shape), dof, stencil, boundary)
-    return (G3 if len(shape) == 3 else G1).slots(*shape, dof, stencil, boundary)
-
-
-def pattern(shape, dof, stencil, boundary):
-    if stencil in G2.STENCIL_ID:
-        return G2.pattern(tuple(shape), dof, stencil, boundary)
-    return (G3 if len(shape) == 3 else G1).pattern(*shape, dof, stencil, boundary)
-
-
-# ------------------------------------------------------------------------------------------------ field access
-class Fields:
-    """A(di, dj[, dk][, k]) on whole-grid arrays [nfields, (nz,) ny, nx]: field k at the neighbouring node. Periodic: the index
-    wraps. Dirichlet: a neighbour outside the grid reads as the field at the node itself."""
-
-    def __init__(self, A, boundary):
-        self.A, self.boundary, self.dim = A, boundary, A.ndim - 1
-
-    def __call__(self, *a):
-        off, k = a[:self.dim], (a[self.dim] if len(a) > self.dim else 0)
-        F = self.A[k]
-        if self.boundary == "periodic":
-            return np.roll(F, tuple(-d for d in off[::-1]), axis=tuple(range(self.dim)))
-        P = np.zeros(tuple(n + 4 for n in F.shape), dtype=F.dtype)
-        P[(slice(2, -2),) * self.dim] = F
-        moved = P[tuple(slice(2 + d, 2 + d + n) for d, n in zip(off[::-1], F.shape))]
-        inside = np.ones(F.shape, dtype=bool)
-        for at, d, n in zip(np.indices(F.shape), off[::-1], F.shape):
-            inside &= (at + d >= 0) & (at + d < n)
-        return np.where(inside, moved, F)
-
-
-def seeded_fields(nfields, shape, shift=0.0):
-    """[nfields, nn] float64: 1 + 0.37·sin(0.9·m + k + shift)"""
-    m = np.arange(int(np.prod(shape)), dtype=np.float64)
-    return np.stack([1.0 + 0.37 * np.sin(0.9 * m + k + shift) for k in range(nfields)])
+from grid_core import RADIUS, Problem, _sum
 
 
 # ------------------------------------------------------------------------------------------------ sources
@@ -267,15 +219,9 @@ def _bratu_f_jac(N, A, p, shape, T):
 
 
 # ------------------------------------------------------------------------------------------------ the cases
-class Problem:
-    def __init__(self, name, dim, source, dof, stencil, boundary, params, nfields, resid, jvp, jac):
-        self.name, self.dim, self.source, self.dof, self.stencil, self.boundary = name, dim, source, dof, stencil, boundary
-        self.params, self.nfields, self._resid, self._jvp, self._jac = list(params), nfields, resid, jvp, jac
-
-
 def _diffusion_problem(name, stencil, boundary, params, nfields, **spec):
     source, resid, jvp, jac = _diffusion(spec)
-    return Problem(name, spec["dim"], source, 1, stencil, boundary, params, nfields, resid, jvp, jac)
+    return Problem(name, source, spec["dim"], 1, stencil, boundary, params, resid, jvp, jac, nfields)
 
 
 _BF = (_bratu_f_resid, _bratu_f_jvp, _bratu_f_jac)
@@ -286,14 +232,14 @@ PROBLEMS = {
     # … + p2·u³: the nonlinear problem of the time-stepping test
     "vardiff_r": _diffusion_problem("vardiff_r", "star", "dirichlet", [4.0, 1.5, 0.75], 3, dim=2, offs=FOUR, g=HALF4, coef=1,
                                     prev=0, src=2, cubic=True),
-    "react2": Problem("react2", 2, REACT2_SRC, 2, "star", "periodic", [3.4, 1.0, 40.0], 1, _react2_resid, _react2_jvp, _react2_jac),
+    "react2": Problem("react2", REACT2_SRC, 2, 2, "star", "periodic", [3.4, 1.0, 40.0], _react2_resid, _react2_jvp, _react2_jac, 1),
     "vardiff_box_dirichlet": _diffusion_problem("vardiff_box_dirichlet", "box", "dirichlet", [1.25, 0.75], 1, **_BOXSPEC),
     "vardiff_box_periodic": _diffusion_problem("vardiff_box_periodic", "box", "periodic", [1.25, 0.75], 1, **_BOXSPEC),
     "vardiff_s2": _diffusion_problem("vardiff_s2", "star2", "dirichlet", [0.5, 1.5], 1, dim=2, offs=G2.EIGHT, g=G_EIGHT, coef=0),
     "vardiff3": _diffusion_problem("vardiff3", "star", "dirichlet", [4.0, 1.5], 2, dim=3, offs=G3.SIX, g=G_SIX, coef=1, prev=0),
-    "bratu_f": Problem("bratu_f", 2, BRATU_F_SRC, 1, "star", "dirichlet", [1.0, 0.04], 1, *_BF),
+    "bratu_f": Problem("bratu_f", BRATU_F_SRC, 2, 1, "star", "dirichlet", [1.0, 0.04], *_BF, 1),
     # the same source with four fields declared: three of them are never read
-    "bratu_f4": Problem("bratu_f4", 2, BRATU_F_SRC, 1, "star", "dirichlet", [1.0, 0.04], 4, *_BF),
+    "bratu_f4": Problem("bratu_f4", BRATU_F_SRC, 2, 1, "star", "dirichlet", [1.0, 0.04], *_BF, 4),
 }
 SIZES_R1 = [(37, 29), (3, 3), (300, 5)]   # 37 × 29 = 1073 nodes: five workgroups of 256, the last one ragged
 SIZES_R2 = [(5, 5), (37, 29)]
@@ -301,101 +247,8 @@ SIZES_3 = [(7, 6, 5), (3, 3, 3), (37, 29, 3)]
 
 
 def sizes(prob):
-    return SIZES_3 if prob.dim == 3 else (SIZES_R2 if prob.stencil in G2.STENCIL_ID else SIZES_R1)
+    return SIZES_3 if prob.dim == 3 else (SIZES_R2 if RADIUS[prob.stencil] == 2 else SIZES_R1)
 
 
 # the pre-field contract, for the error message test
 OLD_SIGNATURE_SRC = G1.BRATU_SRC
-
-
-def inputs(prob, shape, seed=0):
-    """seeded u and v in [−1, 1], float64, length dof·nn"""
-    rng = np.random.default_rng(1000 * seed + sum(w * n for w, n in zip((49, 7, 1), shape)) + len(prob.name))
-    n = prob.dof * int(np.prod(shape))
-    return rng.uniform(-1.0, 1.0, n), rng.uniform(-1.0, 1.0, n)
-
-
-class Evaluation:
-    """one problem at one (u, v, fields, p) in one arithmetic: f, Jv, CSR values, Jᵀv and the Σ|terms| of each entry"""
-
-
-def evaluate(prob, shape, u, v, fields, T=np.float64, params=None):
-    """fields: [nfields, nn] float64 (the data the device holds: converted, not recomputed, in long double)"""
-    shape = tuple(shape)
-    p = [T(x) for x in (prob.params if params is None else params)]
-    dof, nn, dim = prob.dof, int(np.prod(shape)), len(shape)
-    N = Grid(np.asarray(u, dtype=T).reshape(dof, *shape[::-1]), prob.boundary)
-    V = Grid(np.asarray(v, dtype=T).reshape(dof, *shape[::-1]), prob.boundary)
-    A = Fields(np.asarray(fields, dtype=T).reshape(prob.nfields, *shape[::-1]), prob.boundary)
-    E = Evaluation()
-    f, fm = prob._resid(N, A, p, shape, T)
-    E.f, E.f_mag = np.concatenate([x.ravel() for x in f]), np.concatenate([x.ravel() for x in fm])
-    jv, jm = prob._jvp(N, V, A, p, shape, T)
-    E.jv, E.jv_mag = np.concatenate([x.ravel() for x in jv]), np.concatenate([x.ravel() for x in jm])
-    # CSR values: every analytic entry at the position the pattern assigns it; entries the formulas do not name are
-    # structural zeros
-    rowptr, cnt, rank, idx, inside, _o2 = slots(shape, dof, prob.stencil, prob.boundary)
-    offs = offsets(dim, prob.stencil)
-    vals, mags = np.zeros(int(rowptr[-1]), dtype=T), np.zeros(int(rowptr[-1]), dtype=T)
-    for key, (val, mag) in prob._jac(N, A, p, shape, T).items():
-        r, off, c2 = key[0], tuple(key[1:1 + dim]), key[1 + dim]
-        q = offs.index(off)
-        nodes = np.nonzero(inside[:, q])[0]
-        pos = rowptr[r * nn + nodes] + c2 * cnt[nodes] + rank[nodes, q]
-        vals[pos] = np.broadcast_to(val, shape[::-1]).ravel()[nodes]
-        mags[pos] = np.broadcast_to(mag, shape[::-1]).ravel()[nodes]
-    E.vals, E.vals_mag = vals, mags
-    rp, ci = pattern(shape, dof, prob.stencil, prob.boundary)
-    rows = np.repeat(np.arange(dof * nn), np.diff(rp))
-    vv = np.asarray(v, dtype=T)
-    E.jtv, E.jtv_mag = np.zeros(dof * nn, dtype=T), np.zeros(dof * nn, dtype=T)
-    np.add.at(E.jtv, ci, vals * vv[rows])
-    np.add.at(E.jtv_mag, ci, np.abs(vals * vv[rows]))
-    E.spmv, E.spmv_mag = np.zeros(dof * nn, dtype=T), np.zeros(dof * nn, dtype=T)
-    np.add.at(E.spmv, rows, vals * vv[ci])
-    np.add.at(E.spmv_mag, rows, np.abs(vals * vv[ci]))
-    return E
-
-
-class Reference:
-    """float64 restatement, per-entry gap to long double and the bound 16·gap + 4 eps·Σ|terms| for f, jv, vals, jtv, spmv"""
-
-    def __init__(self, prob, shape, u, v, fields, params=None):
-        a, b = evaluate(prob, shape, u, v, fields, np.float64, params), evaluate(prob, shape, u, v, fields, LD, params)
-        for k in ("f", "jv", "vals", "jtv", "spmv"):
-            x64, x80 = getattr(a, k), getattr(b, k)
-            gap = np.abs(x64.astype(LD) - x80).astype(np.float64)
-            setattr(self, k, x64)
-            setattr(self, k + "_gap", gap)
-            setattr(self, k + "_bound", MARGIN * gap + FLOOR_ULPS * EPS * getattr(a, k + "_mag"))
-
-
-_CACHE = {}
-
-
-def reference(name, shape, seed=0, shift=0.0, zero_fields=False):
-    """the shared reference of a case (computed once, not modified by its users): seeded u, v and fields (shift moves the
-    fields' phase: another set of data; zero_fields: the fields as a fresh problem holds them)"""
-    shape = tuple(shape)
-    key = (name, shape, seed, shift, zero_fields)
-    if key not in _CACHE:
-        prob = PROBLEMS[name]
-        u, v = inputs(prob, shape, seed)
-        fields = seeded_fields(prob.nfields, shape, shift) * (0.0 if zero_fields else 1.0)
-        R = Reference(prob, shape, u, v, fields)
-        R.u, R.v, R.fields = u, v, fields
-        for arr in vars(R).values():
-            if isinstance(arr, np.ndarray):
-                arr.setflags(write=False)
-        _CACHE[key] = R
-    return _CACHE[key]
-
-
-def dense_jacobian(prob, shape, u, fields, params=None):
-    """the float64 restatement's Jacobian as a dense matrix and its residual (small grids: the reference Newton)"""
-    E = evaluate(prob, shape, u, np.zeros_like(u), fields, np.float64, params)
-    rp, ci = pattern(shape, prob.dof, prob.stencil, prob.boundary)
-    n = rp.size - 1
-    J = np.zeros((n, n))
-    J[np.repeat(np.arange(n), np.diff(rp)), ci] = E.vals
-    return J, E.f

@@ -12,7 +12,7 @@ side, and the hierarchy ends when no axis is coarsened.
 
 Prolongation on one axis: t = (a_lo + i)·(nc − 1 + a_lo + a_hi)/L − a_lo (periodic: i·nc/n), J0 = ⌊t⌋, weights 1 − w1 on J0 and
 w1 = t − J0 on J0 + 1, a weight within 1e-12 of 0 or 1 snapped to the node; a coarse index outside 0 … nc−1 goes through the
-grid's own side map (gridbc_reference.axis_map: Dirichlet drops, periodic wraps, the mirrors reflect); weights landing on one
+grid's own side map (grid_core.axis_map: Dirichlet drops, periodic wraps, the mirrors reflect); weights landing on one
 coarse node are added. Restriction = the row-normalised transpose, on every axis, for residuals, u and fields alike. Transfers
 of a grid are tensor products (node = (k·ny + j)·nx + i: the outermost axis is the first Kronecker factor), components one by
 one (vectors are component-major).
@@ -26,11 +26,13 @@ on the coarsest level; a single level is smoothed only.
 The problems take their spacing from the level they run on (s.nx, s.ny, s.nz), as the multigrid's contract asks: the unit
 interval per axis, h = 1/(n − 1 + a_lo + a_hi) (periodic: 1/n). Every one is  F_c(u) = Σ_points coef·u(point) + g_c(u at the node),
 so its Jacobian is the stencil matrix plus a pointwise block."""
+import functools
+
 import numpy as np
 import scipy.sparse as sp
 import scipy.sparse.linalg as spla
 
-import gridbc_reference as BC
+import grid_core as GC
 
 OFFSET = {"dirichlet": 1.0, "periodic": 0.0, "mirror_node": 0.0, "mirror_face": 0.5}
 ALL_KINDS = ("dirichlet", "mirror_node", "mirror_face")
@@ -53,7 +55,7 @@ def axis_table(n, lo, hi):
     alo, ahi = OFFSET[lo], OFFSET[hi]
     L = float(n) if per else n - 1 + alo + ahi
     Lc = float(nc) if per else nc - 1 + alo + ahi
-    land = BC.axis_map(nc, lo, hi)                 # positions −PAD … nc−1+PAD
+    land = GC.axis_map(nc, lo, hi)                 # positions −PAD … nc−1+PAD
     idx, w = -np.ones((n, 2), dtype=np.int64), np.zeros((n, 2))
     for i in range(n):
         t = i * Lc / L if per else (alo + i) * Lc / L - alo
@@ -66,7 +68,7 @@ def axis_table(n, lo, hi):
         for s, wt in enumerate((1.0 - w1, w1)):
             if wt == 0.0:
                 continue
-            J = int(land[J0 + s + BC.PAD])
+            J = int(land[J0 + s + GC.PAD])
             if J < 0:
                 continue
             if s == 1 and idx[i, 0] == J:
@@ -122,9 +124,7 @@ def transfers(fine, coarse, sides):
 
 
 # ------------------------------------------------------------------------------------------------ the problems
-STAR2 = [(0, -1), (-1, 0), (0, 0), (1, 0), (0, 1)]
-STAR3 = [(0, 0, -1), (0, -1, 0), (-1, 0, 0), (0, 0, 0), (1, 0, 0), (0, 1, 0), (0, 0, 1)]
-STAR2_R2 = [(0, -2), (0, -1), (-2, 0), (-1, 0), (0, 0), (1, 0), (2, 0), (0, 1), (0, 2)]
+STAR2, STAR3, STAR2_R2 = GC.STENCILS[(2, "star")], GC.STENCILS[(3, "star")], GC.STENCILS[(2, "star2")]
 
 
 def spacing(shape, sides):
@@ -145,7 +145,7 @@ class Problem:
     def linear(self, shape, fields, p):
         """the stencil part as a sparse matrix (a point that left through a Dirichlet side has no column, points on one node add)"""
         nn = int(np.prod(shape))
-        idx, inside = BC.neighbours(shape, self.offs, self.boundary)
+        idx, inside = GC.neighbours(shape, self.offs, self.boundary)
         coef = self.stencil_coef(shape, fields, p, idx)
         rows, cols, vals = [], [], []
         nodes = np.arange(nn)
@@ -451,36 +451,31 @@ def sparse_newton(prob, shape, u0, fields=None, p=None, tol=1e-12, maxiters=50):
     return u
 
 
-_CACHE = {}
-
-
+@functools.lru_cache(maxsize=None)
 def reference(name, shape, coarse_max, nu=2, variant=0):
     """the shared reference of a case (computed once, not modified by its users): u, fields, b, the hierarchy, the result of
     one GMRES iteration with the V-cycle as right preconditioner and the iteration count to rtol 1e-9. variant = 1: other fields
     and another p (what the update tests switch to)"""
     from oracle import reference_restatement as R
-    key = (name, tuple(shape), coarse_max, nu, variant)
-    if key not in _CACHE:
-        prob = PROBLEMS[name]
-        u = linearisation_point(prob, shape)
-        fields, p = prob.fields(shape), list(prob.params)
-        if variant == 1:
-            p[0] = 1.5 * p[0]
-            if fields is not None:
-                x, y = prob.coords(shape)[:2]
-                fields = fields + np.concatenate([0.3 * np.cos(2 * np.pi * x) * np.cos(2 * np.pi * y), 0.1 * np.sin(2 * np.pi * x)])
-        M = GridMultigrid(prob, shape, u, fields, p, nu, coarse_max)
-        J = M.levels[0]["A"]
-        b = np.random.default_rng(7 + len(name)).standard_normal(J.shape[0])
-        x1, _ = R.gmres(lambda z: J @ z, b, restart=30, fixed_iters=1, M=M, ortho="cgs2")
-        x, info = R.gmres(lambda z: J @ z, b, rtol=1e-9, restart=30, itmax=300, M=M, ortho="cgs2")
+    prob = PROBLEMS[name]
+    u = linearisation_point(prob, shape)
+    fields, p = prob.fields(shape), list(prob.params)
+    if variant == 1:
+        p[0] = 1.5 * p[0]
+        if fields is not None:
+            x, y = prob.coords(shape)[:2]
+            fields = fields + np.concatenate([0.3 * np.cos(2 * np.pi * x) * np.cos(2 * np.pi * y), 0.1 * np.sin(2 * np.pi * x)])
+    M = GridMultigrid(prob, shape, u, fields, p, nu, coarse_max)
+    J = M.levels[0]["A"]
+    b = np.random.default_rng(7 + len(name)).standard_normal(J.shape[0])
+    x1, _ = R.gmres(lambda z: J @ z, b, restart=30, fixed_iters=1, M=M, ortho="cgs2")
+    x, info = R.gmres(lambda z: J @ z, b, rtol=1e-9, restart=30, itmax=300, M=M, ortho="cgs2")
 
-        class Ref:
-            pass
-        ref = Ref()
-        ref.prob, ref.u, ref.fields, ref.p, ref.M, ref.J, ref.b, ref.x1, ref.x, ref.iters = prob, u, fields, p, M, J, b, x1, x, info.iters
-        for arr in (u, fields, b, x1, x):
-            if isinstance(arr, np.ndarray):
-                arr.setflags(write=False)
-        _CACHE[key] = ref
-    return _CACHE[key]
+    class Ref:
+        pass
+    ref = Ref()
+    ref.prob, ref.u, ref.fields, ref.p, ref.M, ref.J, ref.b, ref.x1, ref.x, ref.iters = prob, u, fields, p, M, J, b, x1, x, info.iters
+    for arr in (u, fields, b, x1, x):
+        if isinstance(arr, np.ndarray):
+            arr.setflags(write=False)
+    return ref

@@ -1,6 +1,6 @@
 """NumPy restatement of the compiled grid problems ON SEVERAL RANKS (csrc/nk_grid.hip, "several ranks: slabs of the outermost
-axis"), built on the five earlier restatements — grid_reference, grid3_reference, grid_r2_reference, gridf_reference and
-gridbc_reference — whose sources, formulas, index maps, pattern and bound it takes as they are. Nothing is computed here that
+axis"), built on the tables grid_reference, grid3_reference, grid_r2_reference and gridf_reference,
+whose sources and formulas it takes as they are, and on grid_core's index maps, pattern and bound. Nothing is computed here that
 they do not compute: a rank's residual, J·v, Jᵀv and fill values are the one-rank restatement's entries MOVED by a permutation.
 
     slabs        rank r of R owns the lines (3-D: planes) [n_outer·r // R, n_outer·(r + 1) // R) of the outermost axis
@@ -11,19 +11,19 @@ they do not compute: a rank's residual, J·v, Jᵀv and fill values are the one-
 
 permutation(shape, dof, R)[g] is the one-rank index of the unknown with global index g. A rank's rows of the pattern are the
 permuted one-rank pattern's rows with the columns renumbered to global and sorted ascending; `src` remembers where each entry
-came from, so the expected fill values (and their bounds) are vals[src]. The bound is the project's, from gridbc_reference:
+came from, so the expected fill values (and their bounds) are vals[src]. The bound is the project's, from grid_core:
 
     |device − float64 restatement| <= 16 × |float64 − long double| + 4 eps × Σ|terms|"""
+import functools
+
 import numpy as np
 
 import grid3_reference as G3
 import grid_r2_reference as G2
 import grid_reference as G1
-import gridbc_reference as GB
 import gridf_reference as GF
+from grid_core import RADIUS, pattern, reference
 from gridbc_reference import DI, MF, MN, PE
-
-RADIUS = {"star": 1, "box": 1, "star2": 2, "diamond2": 2}
 
 
 def slab_ranges(n_outer, R):
@@ -59,7 +59,7 @@ class Slab:
         inv = np.empty_like(perm)
         inv[perm] = np.arange(perm.size)
         self.rows = perm[self.row_begin:self.row_begin + self.n_local]
-        rp, ci = GB.pattern(shape, dof, offs, sides)
+        rp, ci = pattern(shape, dof, offs, sides)
         rp, ci = rp.astype(np.int64), ci.astype(np.int64)
         counts = rp[self.rows + 1] - rp[self.rows]
         self.rowptr = np.concatenate([[0], np.cumsum(counts)]).astype(np.int32)
@@ -96,34 +96,30 @@ def union_pattern(slabs):
 
 
 # ------------------------------------------------------------------------------------------------ the cases
-def _p(name, base, sides, style, dim, params=None):
-    return GB.Problem(name, base, sides, style, dim, params)
-
-
 # the five kinds of the split axis (2-D: y), Bratu's source, x Dirichlet-0
 Y_KINDS = {"ydir": (DI, DI), "yper": (PE, PE), "ymnode": (MN, MN), "ymface": (MF, MF), "ymixed": (MF, DI)}
 PROBLEMS = {p.name: p for p in [
-    *[_p("bratu_" + k, G1.PROBLEMS["bratu"], (DI, DI) + v, "g1", 2) for k, v in Y_KINDS.items()],
+    *[G1.PROBLEMS["bratu"].with_boundary("bratu_" + k, (DI, DI) + v) for k, v in Y_KINDS.items()],
     # the x axis periodic and mirrored: at the slab's first line the points (−1, −1) and (0, −1) of the box land on ONE ghost node
-    _p("bratu_xper_yper", G1.PROBLEMS["bratu"], (PE, PE, PE, PE), "g1", 2),
-    _p("bratu_xmface_ymixed", G1.PROBLEMS["bratu"], (MF, MF, MF, DI), "g1", 2),
+    G1.PROBLEMS["bratu"].with_boundary("bratu_xper_yper", (PE, PE, PE, PE)),
+    G1.PROBLEMS["bratu"].with_boundary("bratu_xmface_ymixed", (MF, MF, MF, DI)),
     # star and box at dof 2; the Brusselator's source reads s.i, s.j, s.nx and s.ny
-    _p("brus_site_yper", G1.PROBLEMS["brusselator"], (MF, MF, PE, PE), "g1", 2),
-    _p("brus_site_ydir", G1.PROBLEMS["brusselator"], (PE, PE, DI, DI), "g1", 2),
-    _p("box_xmface_yper", G1.PROBLEMS["box_dirichlet"], (MF, MF, PE, PE), "g1", 2),
-    _p("box_xmnode_ymixed", G1.PROBLEMS["box_dirichlet"], (MN, MN, MF, DI), "g1", 2),
+    G1.PROBLEMS["brusselator"].with_boundary("brus_site_yper", (MF, MF, PE, PE)),
+    G1.PROBLEMS["brusselator"].with_boundary("brus_site_ydir", (PE, PE, DI, DI)),
+    G1.PROBLEMS["box_dirichlet"].with_boundary("box_xmface_yper", (MF, MF, PE, PE)),
+    G1.PROBLEMS["box_dirichlet"].with_boundary("box_xmnode_ymixed", (MN, MN, MF, DI)),
     # radius 2
-    _p("star2_yper", G2.PROBLEMS["upwind2_dirichlet"], (MN, MF, PE, PE), "g2", 2),
-    _p("star2_ydir", G2.PROBLEMS["upwind2_dirichlet"], (PE, PE, DI, DI), "g2", 2),
-    _p("diamond2_ymnode", G2.PROBLEMS["diamond_dirichlet"], (MF, MF, MN, MN), "g2", 2),
-    _p("diamond2_yper", G2.PROBLEMS["diamond_dirichlet"], (DI, DI, PE, PE), "g2", 2),
+    G2.PROBLEMS["upwind2_dirichlet"].with_boundary("star2_yper", (MN, MF, PE, PE)),
+    G2.PROBLEMS["upwind2_dirichlet"].with_boundary("star2_ydir", (PE, PE, DI, DI)),
+    G2.PROBLEMS["diamond_dirichlet"].with_boundary("diamond2_ymnode", (MF, MF, MN, MN)),
+    G2.PROBLEMS["diamond_dirichlet"].with_boundary("diamond2_yper", (DI, DI, PE, PE)),
     # 3-D: the star at dof 2 (its source reads the site) and the radius-2 star
-    _p("star3_zper", G3.PROBLEMS["brusselator3"], (PE, PE, DI, MN, PE, PE), "g3", 3),
-    _p("star3_zmixed", G3.PROBLEMS["brusselator3"], (MF, MF, PE, PE, MF, DI), "g3", 3),
-    _p("star2_3_zmnode", G2.PROBLEMS["upwind3_dirichlet"], (PE, PE, DI, DI, MN, MN), "g2", 3),
+    G3.PROBLEMS["brusselator3"].with_boundary("star3_zper", (PE, PE, DI, MN, PE, PE)),
+    G3.PROBLEMS["brusselator3"].with_boundary("star3_zmixed", (MF, MF, PE, PE, MF, DI)),
+    G2.PROBLEMS["upwind3_dirichlet"].with_boundary("star2_3_zmnode", (PE, PE, DI, DI, MN, MN)),
     # fields: κ (field 1) is read at all four offsets, so across the cut
-    _p("vardiff_yper", GF.PROBLEMS["vardiff"], (DI, DI, PE, PE), "gf", 2),
-    _p("vardiff_ymface", GF.PROBLEMS["vardiff"], (MF, MF, MF, MF), "gf", 2),
+    GF.PROBLEMS["vardiff"].with_boundary("vardiff_yper", (DI, DI, PE, PE)),
+    GF.PROBLEMS["vardiff"].with_boundary("vardiff_ymface", (MF, MF, MF, MF)),
 ]}
 # sources without an elementary function: the same nk_point on the same inputs, bit for bit on any number of ranks
 HAS_EXP = tuple(n for n, p in PROBLEMS.items() if "exp(" in p.source)
@@ -139,38 +135,15 @@ def small_shape(prob, R):
     return inner + (n_outer,)
 
 
-_CACHE = {}
-
-
-def reference(name, shape, seed=0):
-    """the one-rank reference of a case (gridbc_reference.Reference: float64 restatement, gap to long double, bound), computed
-    once and shared read-only"""
-    shape = tuple(shape)
-    key = (name, shape, seed)
-    if key not in _CACHE:
-        prob = PROBLEMS[name]
-        u, v = GB.inputs(prob, shape, seed)
-        fields = GF.seeded_fields(prob.nfields, shape) if prob.nfields else None
-        ref = GB.Reference(prob, shape, u, v, fields)
-        ref.u, ref.v, ref.fields = u, v, fields
-        for arr in vars(ref).values():
-            if isinstance(arr, np.ndarray):
-                arr.setflags(write=False)
-        _CACHE[key] = ref
-    return _CACHE[key]
-
-
+@functools.lru_cache(maxsize=None)
 def slab(name, shape, R, r):
     prob = PROBLEMS[name]
-    key = ("slab", name, tuple(shape), R, r)
-    if key not in _CACHE:
-        _CACHE[key] = Slab(shape, prob.dof, prob.offsets(), prob.boundary, R, r)
-    return _CACHE[key]
+    return Slab(shape, prob.dof, prob.offsets(), prob.sides, R, r)
 
 
 def expected(name, shape, R, r, seed=0):
     """{quantity: (expected local array, its bound)} for f, jv, vals, jtv, spmv: the one-rank reference's entries, moved"""
-    ref, S = reference(name, shape, seed), slab(name, shape, R, r)
+    ref, S = reference(PROBLEMS[name], shape, seed), slab(name, shape, R, r)
     out = {k: (S.local(getattr(ref, k)), S.local(getattr(ref, k + "_bound"))) for k in ("f", "jv", "jtv", "spmv")}
     out["vals"] = (S.values(ref.vals), S.values(ref.vals_bound))
     return out

@@ -1,5 +1,5 @@
 """Compiled grid problems in three dimensions on the device (csrc/nk_grid.hip, nk_problem_create_grid3): the generated
-residual, dual-number JVP and Jacobian-fill kernels against the NumPy restatement tests/grid3_reference.py, entry by entry
+residual, dual-number JVP and Jacobian-fill kernels against the NumPy restatement (tests/grid_core.py, tests/grid3_reference.py), entry by entry
 within the restatement's own bound
 
     |device − float64 restatement| <= 16 × |float64 − long double| + 4 eps × Σ|terms of the entry|
@@ -10,53 +10,13 @@ import numpy as np
 import pytest
 
 import grid3_reference as R
+import grid_core as GC
 import grid_reference as R2
+from grid_device import assert_parity, check, close_problems, device_quantities, problem, to_device, to_numpy
 
 pytestmark = pytest.mark.gpu
 
-_PROBLEMS = {}
 LAMBDA = 3.0   # Bratu on (a box inside) the unit cube: well below the 3-D turning point (grid3_reference.bratu3_params)
-
-
-def _t(x, dev):
-    import torch
-    return torch.tensor(np.asarray(x, dtype=np.float64), dtype=torch.float64, device=dev)
-
-
-def _np(x):
-    return x.detach().cpu().numpy() if hasattr(x, "detach") else np.asarray(x)
-
-
-def _problem(nls, name, nx, ny, nz):
-    """one compiled problem per case for the whole module (the parameters are put back by whoever changes them)"""
-    key = (name, nx, ny, nz)
-    if key not in _PROBLEMS:
-        p = R.PROBLEMS[name]
-        _PROBLEMS[key] = nls.CompiledGridProblem(p.source, nx, ny, dof=p.dof, stencil=p.stencil, boundary=p.boundary,
-                                                 params=p.params, nz=nz)
-    return _PROBLEMS[key]
-
-
-def _check(what, got, ref, bound, exact=False):
-    """exact: the case agrees bit for bit (measured on the MI355X), so that is what is asserted"""
-    err = np.abs(got - ref)
-    worst = float(np.max(err - bound))
-    same = int(np.sum(got == ref))
-    print(f"{what}: max err {err.max():.3e}, max bound {bound.max():.3e}, min bound {bound.min():.3e}, worst err - bound "
-          f"{worst:.3e}, bitwise equal {same}/{got.size}")
-    assert np.all(np.isfinite(got)), what
-    assert np.all(err <= bound), (what, worst)
-    if exact:
-        assert np.array_equal(got, ref), what
-
-
-def _device_quantities(P, u, v, dev):
-    """residual, J·v, CSR values of the fill, Jᵀv and the filled matrix times v"""
-    du, dv = _t(u, dev), _t(v, dev)
-    J = P.jac_csr()
-    P.jac_values(du, J)
-    return dict(f=_np(P.residual(du)), jv=_np(P.jvp(dv, du)), vals=np.array(J.values()), jtv=_np(P.vjp(dv, du)),
-                spmv=_np(J.matvec(dv)))
 
 
 # ------------------------------------------------------------------------------------------------ parity with the restatement
@@ -70,15 +30,8 @@ def test_parity_with_the_restatement(nls, dev, name, nx, ny, nz):
     bounds.
     brusselator3, four3 and box3 have no elementary function in them: with -ffp-contract=off the device's +, −, × are the
     restatement's in the restatement's order. What the MI355X showed is recorded at EXACT below and asserted."""
-    ref = R.reference(name, nx, ny, nz)
-    P = _problem(nls, name, nx, ny, nz)
-    assert P.nz == nz and P.n_local == ref.u.size and P.jac_csr().info()["nnz"] == ref.vals.size
-    got = _device_quantities(P, ref.u, ref.v, dev)
-    for k in ("f", "jv", "vals", "jtv", "spmv"):
-        _check(f"{name} {nx}x{ny}x{nz} {k}", got[k], getattr(ref, k), getattr(ref, k + "_bound"), exact=name in EXACT)
-    diff = np.abs(got["spmv"] - got["jv"])
-    print(f"{name} {nx}x{ny}x{nz} fill·v vs dual JVP: max {diff.max():.3e}")
-    assert np.all(diff <= ref.spmv_bound + ref.jv_bound)
+    P, _ref = assert_parity(nls, dev, R.PROBLEMS[name], (nx, ny, nz), exact=name in EXACT)
+    assert P.nz == nz
 
 
 # The problems whose five quantities agreed BIT FOR BIT with the restatement at all four shapes on the MI355X (100 of 100
@@ -91,11 +44,11 @@ EXACT = ("brusselator3", "four3", "box3_dirichlet", "box3_periodic")
 # ------------------------------------------------------------------------------------------------ contract
 def test_star_source_that_reads_an_edge_gives_nan(nls, dev):
     P = nls.CompiledGridProblem(R.EDGE_SRC, 5, 4, nz=3)
-    f = _np(P.residual(_t(np.linspace(-1, 1, 60), dev)))
+    f = to_numpy(P.residual(to_device(np.linspace(-1, 1, 60), dev)))
     assert f.shape == (60,) and np.all(np.isnan(f))
     P.close()
     Pb = nls.CompiledGridProblem(R.EDGE_SRC, 5, 4, stencil="box", nz=3)   # the same source is a valid box problem
-    assert np.all(np.isfinite(_np(Pb.residual(_t(np.linspace(-1, 1, 60), dev)))))
+    assert np.all(np.isfinite(to_numpy(Pb.residual(to_device(np.linspace(-1, 1, 60), dev)))))
     Pb.close()
 
 
@@ -112,32 +65,32 @@ __device__ void nk_point(const nk_nbhd3<T> &u, const nk_real *p, nk_site3 s, T *
 def test_radius_1_source_that_reads_two_nodes_away_gives_nan(nls, dev, stencil):
     """every offset that is no point of the stencil reads NaN, at radius 1 as at radius 2: u(0, 0, 2) on a 6 x 5 x 5 Dirichlet
     grid (interior and boundary nodes) under star and box; the same source is a valid star2 problem"""
-    u = _t(np.linspace(-1, 1, 150), dev)
+    u = to_device(np.linspace(-1, 1, 150), dev)
     P = nls.CompiledGridProblem(TWO_AWAY_SRC, 6, 5, stencil=stencil, nz=5)
-    f = _np(P.residual(u))
+    f = to_numpy(P.residual(u))
     assert f.shape == (150,) and np.all(np.isnan(f))
     P.close()
     P2 = nls.CompiledGridProblem(TWO_AWAY_SRC, 6, 5, stencil="star2", nz=5)
-    assert np.all(np.isfinite(_np(P2.residual(u))))
+    assert np.all(np.isfinite(to_numpy(P2.residual(u))))
     P2.close()
 
 
 def test_reinit_p_changes_the_residual_as_the_restatement_says(nls, dev):
-    name, (nx, ny, nz) = "box3_periodic", (7, 6, 5)
+    case, shape = R.PROBLEMS["box3_periodic"], (7, 6, 5)
     p0, p1 = R.BOX3_PARAMS, [-0.5, 0.125, 2.0]
-    P = _problem(nls, name, nx, ny, nz)
-    ref0, ref1 = R.reference(name, nx, ny, nz), R.reference(name, nx, ny, nz, params=p1)
-    prob = nls.NonlinearProblem(P, _t(ref0.u, dev), p0)
+    P = problem(nls, case, shape)
+    ref0, ref1 = GC.reference(case, shape), GC.reference(case, shape, params=p1)
+    prob = nls.NonlinearProblem(P, to_device(ref0.u, dev), p0)
     cache = nls.init(prob, nls.NewtonRaphson(linsolve=nls.KrylovJL_GMRES()), abstol=1e-10)
-    _check("fu after init", _np(cache.fu), ref0.f, ref0.f_bound)
-    nls.reinit_(cache, u0=_t(ref0.u, dev), p=p1)
-    _check("fu after reinit_(p=...)", _np(cache.fu), ref1.f, ref1.f_bound)
+    check("fu after init", to_numpy(cache.fu), ref0.f, ref0.f_bound)
+    nls.reinit_(cache, u0=to_device(ref0.u, dev), p=p1)
+    check("fu after reinit_(p=...)", to_numpy(cache.fu), ref1.f, ref1.f_bound)
     assert float(np.max(np.abs(ref1.f - ref0.f))) > 1e6 * float(ref1.f_bound.max())
     # the Jacobian follows the parameters too (a fill cached for the same u is not reused)
-    u = _t(ref0.u, dev)
-    _check("Jᵀv with the new p", _np(P.vjp(_t(ref0.v, dev), u)), ref1.jtv, ref1.jtv_bound)
+    u = to_device(ref0.u, dev)
+    check("Jᵀv with the new p", to_numpy(P.vjp(to_device(ref0.v, dev), u)), ref1.jtv, ref1.jtv_bound)
     P.set_p(p0)
-    _check("Jᵀv with the old p, same u buffer", _np(P.vjp(_t(ref0.v, dev), u)), ref0.jtv, ref0.jtv_bound)
+    check("Jᵀv with the old p, same u buffer", to_numpy(P.vjp(to_device(ref0.v, dev), u)), ref0.jtv, ref0.jtv_bound)
     with pytest.raises(ValueError):
         P.set_p([1.0])
     cache.close()
@@ -145,18 +98,18 @@ def test_reinit_p_changes_the_residual_as_the_restatement_says(nls, dev):
 
 def test_two_sources_alive_at_once_and_a_fresh_problem_after_close(nls, dev):
     s = (7, 6, 5)
-    a, b = R.reference("bratu3", *s), R.reference("box3_dirichlet", *s)
+    a, b = GC.reference(R.PROBLEMS["bratu3"], s), GC.reference(R.PROBLEMS["box3_dirichlet"], s)
     Pa = nls.CompiledGridProblem(R.BRATU3_SRC, s[0], s[1], params=R.PROBLEMS["bratu3"].params, nz=s[2])
     Pb = nls.CompiledGridProblem(R.BOX3_SRC, s[0], s[1], stencil="box", params=R.BOX3_PARAMS, nz=s[2])
     for _ in range(2):   # interleaved: each keeps its own kernels
-        _check("bratu3 beside box3", _np(Pa.residual(_t(a.u, dev))), a.f, a.f_bound)
-        _check("box3 beside bratu3", _np(Pb.jvp(_t(b.v, dev), _t(b.u, dev))), b.jv, b.jv_bound)
+        check("bratu3 beside box3", to_numpy(Pa.residual(to_device(a.u, dev))), a.f, a.f_bound)
+        check("box3 beside bratu3", to_numpy(Pb.jvp(to_device(b.v, dev), to_device(b.u, dev))), b.jv, b.jv_bound)
     Pa.close()
-    _check("box3 after bratu3 closed", _np(Pb.residual(_t(b.u, dev))), b.f, b.f_bound)
+    check("box3 after bratu3 closed", to_numpy(Pb.residual(to_device(b.u, dev))), b.f, b.f_bound)
     Pb.close()
     Pc = nls.CompiledGridProblem(R.BRATU3_SRC, s[0], s[1], params=R.PROBLEMS["bratu3"].params, nz=s[2])
-    _check("a fresh bratu3 after close", _np(Pc.residual(_t(a.u, dev))), a.f, a.f_bound)
-    assert np.array_equal(_np(Pc.initial_guess(device=True)), np.zeros(7 * 6 * 5))
+    check("a fresh bratu3 after close", to_numpy(Pc.residual(to_device(a.u, dev))), a.f, a.f_bound)
+    assert np.array_equal(to_numpy(Pc.initial_guess(device=True)), np.zeros(7 * 6 * 5))
     Pc.close()
 
 
@@ -177,30 +130,30 @@ __device__ void nk_point(const nk_nbhd3<T> &u, const nk_real *p, nk_site3 s, T *
     k, rem = np.divmod(np.arange(nx * ny * nz), nx * ny)
     j, i = np.divmod(rem, nx)
     site = (i + 10 * j + 100 * k) + (1000 * nx + 10000 * ny + 100000 * nz)
-    assert np.array_equal(_np(P.residual(_t(u, dev))), w * u + site)   # small integers: exact
+    assert np.array_equal(to_numpy(P.residual(to_device(u, dev))), w * u + site)   # small integers: exact
     par2 = [x + 1.0 for x in par]
     P.set_p(par2)
     w2 = float(sum((k + 1) * par2[k] for k in range(32)))
-    assert np.array_equal(_np(P.residual(_t(u, dev))), w2 * u + site)
+    assert np.array_equal(to_numpy(P.residual(to_device(u, dev))), w2 * u + site)
     P.close()
 
 
 def test_a_2d_and_a_3d_problem_side_by_side(nls, dev):
     """the Bratu source of each dimension, alive together and called in turn: each keeps its kernels, its pattern and its
     parameters (the 3-D programs are cached apart from the 2-D ones of a related source)"""
-    a2, a3 = R2.reference("bratu", 37, 29), R.reference("bratu3", 7, 6, 5)
+    a2, a3 = GC.reference(R2.PROBLEMS["bratu"], (37, 29)), GC.reference(R.PROBLEMS["bratu3"], (7, 6, 5))
     P2 = nls.CompiledGridProblem(R2.BRATU_SRC, 37, 29, params=R2.PROBLEMS["bratu"].params)
     P3 = nls.CompiledGridProblem(R.BRATU3_SRC, 7, 6, params=R.PROBLEMS["bratu3"].params, nz=5)
     assert not hasattr(P2, "nz") and P3.nz == 5
     for _ in range(2):
-        g2, g3 = _device_quantities(P2, a2.u, a2.v, dev), _device_quantities(P3, a3.u, a3.v, dev)
+        g2, g3 = device_quantities(P2, a2.u, a2.v, dev), device_quantities(P3, a3.u, a3.v, dev)
         for k in ("f", "jv", "vals", "jtv"):
-            _check(f"2-D bratu beside 3-D {k}", g2[k], getattr(a2, k), getattr(a2, k + "_bound"))
-            _check(f"3-D bratu beside 2-D {k}", g3[k], getattr(a3, k), getattr(a3, k + "_bound"))
+            check(f"2-D bratu beside 3-D {k}", g2[k], getattr(a2, k), getattr(a2, k + "_bound"))
+            check(f"3-D bratu beside 2-D {k}", g3[k], getattr(a3, k), getattr(a3, k + "_bound"))
     P2.set_p([2.0, 0.5])   # the 2-D problem's parameters are its own
-    _check("3-D after the 2-D set_p", _np(P3.residual(_t(a3.u, dev))), a3.f, a3.f_bound)
+    check("3-D after the 2-D set_p", to_numpy(P3.residual(to_device(a3.u, dev))), a3.f, a3.f_bound)
     P2.close()
-    _check("3-D after the 2-D close", _np(P3.jvp(_t(a3.v, dev), _t(a3.u, dev))), a3.jv, a3.jv_bound)
+    check("3-D after the 2-D close", to_numpy(P3.jvp(to_device(a3.v, dev), to_device(a3.u, dev))), a3.jv, a3.jv_bound)
     P3.close()
 
 
@@ -209,7 +162,7 @@ _NEWTON = {}
 
 
 def _bratu3(nls, shape):
-    P = _problem(nls, "bratu3", *shape)
+    P = problem(nls, R.PROBLEMS["bratu3"], shape)
     par = R.bratu3_params(shape[0], LAMBDA)
     P.set_p(par)
     return P, par
@@ -217,7 +170,7 @@ def _bratu3(nls, shape):
 
 def _restated_residual(shape, u, par):
     """the restatement's residual at u with its entrywise bound"""
-    at = R.Reference(R.PROBLEMS["bratu3"], *shape, u, np.zeros(u.size), par)
+    at = GC.Reference(R.PROBLEMS["bratu3"], shape, u, np.zeros(u.size), params=par)
     return at.f, at.f_bound
 
 
@@ -226,7 +179,7 @@ def _dense_newton(shape, par):
     if shape not in _NEWTON:
         prob, u = R.PROBLEMS["bratu3"], np.zeros(shape[0] * shape[1] * shape[2])
         for _it in range(30):
-            J, f = R.dense_jacobian(prob, *shape, u, par)
+            J, f = GC.dense_jacobian(prob, shape, u, params=par)
             if np.abs(f).max() <= 1e-12:
                 break
             u = u - np.linalg.solve(J, f)
@@ -266,8 +219,8 @@ def test_solves_bratu3_like_a_dense_newton(nls, dev, algname):
     kw = dict(abstol=abstol, maxiters=60)
     if algname in ("dfsane", "lbroyden"):   # residual-only methods: more, cheaper steps; the plain ‖F‖∞ <= abstol test
         kw = dict(abstol=abstol, maxiters=2000, termination_condition=nls.AbsNormTerminationMode())
-    sol = nls.solve(nls.NonlinearProblem(P, _t(np.zeros(u_ref.size), dev)), _algorithms(nls)[algname], **kw)
-    u_dev = _np(sol.u)
+    sol = nls.solve(nls.NonlinearProblem(P, to_device(np.zeros(u_ref.size), dev)), _algorithms(nls)[algname], **kw)
+    u_dev = to_numpy(sol.u)
     f_dev = float(np.abs(_restated_residual(shape, u_dev, par)[0]).max())
     err, bound = float(np.abs(u_dev - u_ref).max()), 2.0 * jinv * (f_dev + f_ref)
     print(f"bratu3 {algname}: {sol.retcode} {sol.stats}; |u_dev - u_ref| {err:.3e}, bound {bound:.3e} "
@@ -293,11 +246,11 @@ def test_default_sstep_gmres_on_the_filled_jacobian(nls, dev, shape):
     n = shape[0] * shape[1] * shape[2]
     alg = nls.NewtonRaphson(linsolve=nls.KrylovJL_GMRES(), concrete_jac=True)
     assert alg.linsolve.ortho == "sstep"
-    sol = nls.solve(nls.NonlinearProblem(P, _t(np.zeros(n), dev)), alg, abstol=abstol, maxiters=60)
-    f, fb = _restated_residual(shape, _np(sol.u), par)
+    sol = nls.solve(nls.NonlinearProblem(P, to_device(np.zeros(n), dev)), alg, abstol=abstol, maxiters=60)
+    f, fb = _restated_residual(shape, to_numpy(sol.u), par)
     J = P.jac_csr()
     P.jac_values(sol.u, J)
-    _Y, resident = J.powers(_t(np.ones(n), dev), 4)
+    _Y, resident = J.powers(to_device(np.ones(n), dev), 4)
     print(f"bratu3 {shape}: {sol.retcode} {sol.stats}; restated |F| {np.abs(f).max():.3e}, bound {fb.max():.3e}; "
           f"matrix powers of this Jacobian: {'resident' if resident else 'streaming'} kernel")
     assert sol.retcode == "Success" and sol.stats.njacs >= sol.stats.nsteps > 0 and sol.stats.gmres_iters > 0
@@ -312,21 +265,18 @@ def test_step_and_init_interface(nls, dev):
     P, par = _bratu3(nls, shape)
     u_ref, f_ref, jinv = _dense_newton(shape, par)
     alg = nls.NewtonRaphson(linsolve=nls.KrylovJL_GMRES(), concrete_jac=True)
-    c = nls.init(nls.NonlinearProblem(P, _t(np.zeros(u_ref.size), dev)), alg, abstol=1e-10)
+    c = nls.init(nls.NonlinearProblem(P, to_device(np.zeros(u_ref.size), dev)), alg, abstol=1e-10)
     f0 = c.fnorm_inf
     assert f0 == par[1]   # f(0) = −c_exp·e⁰ at every node
     nls.step_(c)
     print(f"after one step: fnorm {c.fnorm_inf:.6e} (from {f0:.6e})")
     assert c.nsteps == 1 and c.fnorm_inf < 0.5 * f0
     assert nls.solve_(c).retcode == "Success"
-    f_dev = float(np.abs(_restated_residual(shape, _np(c.u), par)[0]).max())
-    assert float(np.abs(_np(c.u) - u_ref).max()) <= 2.0 * jinv * (f_dev + f_ref)
+    f_dev = float(np.abs(_restated_residual(shape, to_numpy(c.u), par)[0]).max())
+    assert float(np.abs(to_numpy(c.u) - u_ref).max()) <= 2.0 * jinv * (f_dev + f_ref)
     c.close()
 
 
 def test_close_module_problems(nls):
     """(last in the file) the problems the module shared are freed; a double close is harmless"""
-    for P in _PROBLEMS.values():
-        P.close()
-        P.close()
-    _PROBLEMS.clear()
+    close_problems()

@@ -1,5 +1,5 @@
 """Compiled grid problems on the device (csrc/nk_grid.hip): the generated residual, dual-number JVP and Jacobian-fill kernels
-against the NumPy restatement tests/grid_reference.py and against the built-in Bratu and Brusselator problems, entry by entry
+against the NumPy restatement (tests/grid_core.py, tests/grid_reference.py) and against the built-in Bratu and Brusselator problems, entry by entry
 within the restatement's own bound
 
     |device − float64 restatement| <= 16 × |float64 − long double| + 4 eps × Σ|terms of the entry|
@@ -9,53 +9,11 @@ public interface. Every figure is printed before it is asserted."""
 import numpy as np
 import pytest
 
+import grid_core as GC
 import grid_reference as R
+from grid_device import assert_parity, check, close_problems, device_quantities, problem, to_device, to_numpy
 
 pytestmark = pytest.mark.gpu
-
-_PROBLEMS = {}
-
-
-def _t(x, dev):
-    import torch
-    return torch.tensor(np.asarray(x, dtype=np.float64), dtype=torch.float64, device=dev)
-
-
-def _np(x):
-    return x.detach().cpu().numpy() if hasattr(x, "detach") else np.asarray(x)
-
-
-def _problem(nls, name, nx, ny, params=None):
-    """one compiled problem per case for the whole module (the parameters are put back by whoever changes them)"""
-    key = (name, nx, ny)
-    if key not in _PROBLEMS:
-        p = R.PROBLEMS[name]
-        _PROBLEMS[key] = nls.CompiledGridProblem(p.source, nx, ny, dof=p.dof, stencil=p.stencil, boundary=p.boundary,
-                                                 params=p.params if params is None else params)
-    return _PROBLEMS[key]
-
-
-def _check(what, got, ref, bound, exact=False):
-    """exact: the case agrees bit for bit (measured on the MI355X), so that is what is asserted"""
-    err = np.abs(got - ref)
-    worst = float(np.max(err - bound))
-    same = int(np.sum(got == ref))
-    print(f"{what}: max err {err.max():.3e}, max bound {bound.max():.3e}, min bound {bound.min():.3e}, worst err - bound "
-          f"{worst:.3e}, bitwise equal {same}/{got.size}")
-    assert np.all(np.isfinite(got)), what
-    assert np.all(err <= bound), (what, worst)
-    if exact:
-        assert np.array_equal(got, ref), what
-
-
-def _device_quantities(P, u, v, dev):
-    """residual, J·v, CSR values of the fill, Jᵀv and the filled matrix times v"""
-    du, dv = _t(u, dev), _t(v, dev)
-    J = P.jac_csr()
-    P.jac_values(du, J)
-    return dict(f=_np(P.residual(du)), jv=_np(P.jvp(dv, du)), vals=np.array(J.values()), jtv=_np(P.vjp(dv, du)),
-                spmv=_np(J.matvec(dv)))
-
 
 # ------------------------------------------------------------------------------------------------ parity with the restatement
 @pytest.mark.parametrize("nx,ny", R.SIZES)
@@ -68,15 +26,7 @@ def test_parity_with_the_restatement(nls, dev, name, nx, ny):
     the restatement's order, and every entry of all five quantities agrees BIT FOR BIT at all three sizes — asserted. The
     Bratu and box problems differ from NumPy in the last bit of exp at a few entries (≤ 2 ulp; measured max error 1.8e-15
     against bounds of 1e-15 … 5e-14) and are held to the rule."""
-    ref = R.reference(name, nx, ny)
-    P = _problem(nls, name, nx, ny)
-    assert P.n_local == ref.u.size and P.jac_csr().info()["nnz"] == ref.vals.size
-    got = _device_quantities(P, ref.u, ref.v, dev)
-    for k in ("f", "jv", "vals", "jtv", "spmv"):
-        _check(f"{name} {nx}x{ny} {k}", got[k], getattr(ref, k), getattr(ref, k + "_bound"), exact=(name == "brusselator"))
-    diff = np.abs(got["spmv"] - got["jv"])
-    print(f"{name} {nx}x{ny} fill·v vs dual JVP: max {diff.max():.3e}")
-    assert np.all(diff <= ref.spmv_bound + ref.jv_bound)
+    assert_parity(nls, dev, R.PROBLEMS[name], (nx, ny), exact=(name == "brusselator"))
 
 
 # ------------------------------------------------------------------------------------------------ parity with the built-ins
@@ -88,21 +38,21 @@ def _same_pattern(nls, Ja, Jb, dev, n):
     w = np.arange(1, ia["nnz"] + 1, dtype=np.float64)
     Ja.set_values(w)
     Jb.set_values(w)
-    x = _t(np.random.default_rng(5).uniform(-1, 1, n), dev)
-    assert np.array_equal(_np(Ja.matvec(x)), _np(Jb.matvec(x)))
+    x = to_device(np.random.default_rng(5).uniform(-1, 1, n), dev)
+    assert np.array_equal(to_numpy(Ja.matvec(x)), to_numpy(Jb.matvec(x)))
 
 
 def test_bratu_source_against_the_built_in(nls, dev):
     ns, name = 33, "bratu"
     B = nls.Bratu2D(ns, 6.0)
-    P = _problem(nls, name, ns, ns)
+    P = problem(nls, R.PROBLEMS[name], (ns, ns))
     P.set_p(R.bratu_params(ns, 6.0))
-    ref = R.reference(name, ns, ns, params=R.bratu_params(ns, 6.0))
+    ref = GC.reference(R.PROBLEMS[name], (ns, ns), params=R.bratu_params(ns, 6.0))
     _same_pattern(nls, P.jac_csr(), B.jac_csr(), dev, ns * ns)
-    got, blt = _device_quantities(P, ref.u, ref.v, dev), _device_quantities(B, ref.u, ref.v, dev)
+    got, blt = device_quantities(P, ref.u, ref.v, dev), device_quantities(B, ref.u, ref.v, dev)
     for k in ("f", "jv", "vals", "jtv"):
-        _check(f"bratu source vs restatement {k}", got[k], getattr(ref, k), getattr(ref, k + "_bound"))
-        _check(f"bratu source vs built-in {k}", got[k], blt[k], getattr(ref, k + "_bound"))
+        check(f"bratu source vs restatement {k}", got[k], getattr(ref, k), getattr(ref, k + "_bound"))
+        check(f"bratu source vs built-in {k}", got[k], blt[k], getattr(ref, k + "_bound"))
     B.close()
 
 
@@ -114,14 +64,14 @@ def test_brusselator_source_against_the_built_in(nls, dev):
     N, name = 24, "brusselator"
     B = nls.Brusselator2D(N)
     par = R.brusselator_params(N)
-    P = _problem(nls, name, N, N)
+    P = problem(nls, R.PROBLEMS[name], (N, N))
     P.set_p(par)
-    ref = R.reference(name, N, N, params=par)
-    got, blt = _device_quantities(P, ref.u, ref.v, dev), _device_quantities(B, ref.u, ref.v, dev)
+    ref = GC.reference(R.PROBLEMS[name], (N, N), params=par)
+    got, blt = device_quantities(P, ref.u, ref.v, dev), device_quantities(B, ref.u, ref.v, dev)
     for k in ("f", "jv", "jtv"):
-        _check(f"brusselator source vs restatement {k}", got[k], getattr(ref, k), getattr(ref, k + "_bound"))
-        _check(f"brusselator source vs built-in {k}", got[k], blt[k], getattr(ref, k + "_bound"))
-    _check("brusselator source vs restatement vals", got["vals"], ref.vals, ref.vals_bound)
+        check(f"brusselator source vs restatement {k}", got[k], getattr(ref, k), getattr(ref, k + "_bound"))
+        check(f"brusselator source vs built-in {k}", got[k], blt[k], getattr(ref, k + "_bound"))
+    check("brusselator source vs restatement vals", got["vals"], ref.vals, ref.vals_bound)
     # the built-in matrix, column by column of the identity restricted to what a 6-per-row pattern can hold: probe with the
     # compiled pattern's own columns
     rp, ci = nls.grid_pattern(N, N, dof=2, stencil="star", boundary="periodic")
@@ -132,14 +82,14 @@ def test_brusselator_source_against_the_built_in(nls, dev):
     j, i = np.divmod(np.arange(N * N), N)
     colour = np.tile((i % 3) + 3 * (j % 3), 2) + 9 * np.repeat([0, 1], N * N)
     JB = B.jac_csr()
-    B.jac_values(_t(ref.u, dev), JB)
+    B.jac_values(to_device(ref.u, dev), JB)
     dense_vals = np.empty(10 * n)
     for c in range(18):
         seed = (colour == c).astype(np.float64)
-        y = _np(JB.matvec(_t(seed, dev)))
+        y = to_numpy(JB.matvec(to_device(seed, dev)))
         sel = colour[ci] == c
         dense_vals[sel] = y[rows[sel]]
-    _check("brusselator built-in matrix on the compiled pattern", got["vals"], dense_vals, ref.vals_bound)
+    check("brusselator built-in matrix on the compiled pattern", got["vals"], dense_vals, ref.vals_bound)
     structural = ref.vals_bound == 0.0
     assert structural.sum() == 4 * n and np.all(got["vals"][structural] == 0.0) and np.all(dense_vals[structural] == 0.0)
     B.close()
@@ -148,11 +98,11 @@ def test_brusselator_source_against_the_built_in(nls, dev):
 # ------------------------------------------------------------------------------------------------ contract
 def test_star_source_that_reads_a_corner_gives_nan(nls, dev):
     P = nls.CompiledGridProblem(R.CORNER_SRC, 5, 4)
-    f = _np(P.residual(_t(np.linspace(-1, 1, 20), dev)))
+    f = to_numpy(P.residual(to_device(np.linspace(-1, 1, 20), dev)))
     assert f.shape == (20,) and np.all(np.isnan(f))
     P.close()
     Pb = nls.CompiledGridProblem(R.CORNER_SRC, 5, 4, stencil="box")   # the same source is a valid box problem
-    assert np.all(np.isfinite(_np(Pb.residual(_t(np.linspace(-1, 1, 20), dev)))))
+    assert np.all(np.isfinite(to_numpy(Pb.residual(to_device(np.linspace(-1, 1, 20), dev)))))
     Pb.close()
 
 
@@ -169,33 +119,33 @@ __device__ void nk_point(const nk_nbhd<T> &u, const nk_real *p, nk_site s, T *f)
 def test_radius_1_source_that_reads_two_nodes_away_gives_nan(nls, dev, stencil):
     """every offset that is no point of the stencil reads NaN, at radius 1 as at radius 2: u(2, 0) on a 6 x 5 Dirichlet grid
     (interior and boundary nodes) under star and box; the same source is a valid star2 problem"""
-    u = _t(np.linspace(-1, 1, 30), dev)
+    u = to_device(np.linspace(-1, 1, 30), dev)
     P = nls.CompiledGridProblem(TWO_AWAY_SRC, 6, 5, stencil=stencil)
-    f = _np(P.residual(u))
+    f = to_numpy(P.residual(u))
     assert f.shape == (30,) and np.all(np.isnan(f))
     P.close()
     P2 = nls.CompiledGridProblem(TWO_AWAY_SRC, 6, 5, stencil="star2")
-    assert np.all(np.isfinite(_np(P2.residual(u))))
+    assert np.all(np.isfinite(to_numpy(P2.residual(u))))
     P2.close()
 
 
 def test_reinit_p_changes_the_residual_as_the_restatement_says(nls, dev):
     import torch
-    name, (nx, ny) = "box_periodic", (37, 29)
+    case, shape = R.PROBLEMS["box_periodic"], (37, 29)
     p0, p1 = R.BOX_PARAMS, [0.5, -1.5, 2.0]
-    P = _problem(nls, name, nx, ny)
-    ref0, ref1 = R.reference(name, nx, ny), R.reference(name, nx, ny, params=p1)
-    prob = nls.NonlinearProblem(P, _t(ref0.u, dev), p0)
+    P = problem(nls, case, shape)
+    ref0, ref1 = GC.reference(case, shape), GC.reference(case, shape, params=p1)
+    prob = nls.NonlinearProblem(P, to_device(ref0.u, dev), p0)
     cache = nls.init(prob, nls.NewtonRaphson(linsolve=nls.KrylovJL_GMRES()), abstol=1e-10)
-    _check("fu after init", _np(cache.fu), ref0.f, ref0.f_bound)
-    nls.reinit_(cache, u0=_t(ref0.u, dev), p=p1)
-    _check("fu after reinit_(p=...)", _np(cache.fu), ref1.f, ref1.f_bound)
+    check("fu after init", to_numpy(cache.fu), ref0.f, ref0.f_bound)
+    nls.reinit_(cache, u0=to_device(ref0.u, dev), p=p1)
+    check("fu after reinit_(p=...)", to_numpy(cache.fu), ref1.f, ref1.f_bound)
     assert float(np.max(np.abs(ref1.f - ref0.f))) > 1e6 * float(ref1.f_bound.max())
     # the Jacobian follows the parameters too (a fill cached for the same u is not reused)
-    u = _t(ref0.u, dev)
-    _check("Jᵀv with the new p", _np(P.vjp(_t(ref0.v, dev), u)), ref1.jtv, ref1.jtv_bound)
+    u = to_device(ref0.u, dev)
+    check("Jᵀv with the new p", to_numpy(P.vjp(to_device(ref0.v, dev), u)), ref1.jtv, ref1.jtv_bound)
     P.set_p(p0)
-    _check("Jᵀv with the old p, same u buffer", _np(P.vjp(_t(ref0.v, dev), u)), ref0.jtv, ref0.jtv_bound)
+    check("Jᵀv with the old p, same u buffer", to_numpy(P.vjp(to_device(ref0.v, dev), u)), ref0.jtv, ref0.jtv_bound)
     with pytest.raises(ValueError):
         P.set_p([1.0])
     cache.close()
@@ -203,18 +153,18 @@ def test_reinit_p_changes_the_residual_as_the_restatement_says(nls, dev):
 
 
 def test_two_sources_alive_at_once_and_a_fresh_problem_after_close(nls, dev):
-    a, b = R.reference("bratu", 37, 29), R.reference("box_dirichlet", 37, 29)
+    a, b = GC.reference(R.PROBLEMS["bratu"], (37, 29)), GC.reference(R.PROBLEMS["box_dirichlet"], (37, 29))
     Pa = nls.CompiledGridProblem(R.BRATU_SRC, 37, 29, params=R.PROBLEMS["bratu"].params)
     Pb = nls.CompiledGridProblem(R.BOX_SRC, 37, 29, dof=2, stencil="box", params=R.BOX_PARAMS)
     for _ in range(2):   # interleaved: each keeps its own kernels
-        _check("bratu beside box", _np(Pa.residual(_t(a.u, dev))), a.f, a.f_bound)
-        _check("box beside bratu", _np(Pb.jvp(_t(b.v, dev), _t(b.u, dev))), b.jv, b.jv_bound)
+        check("bratu beside box", to_numpy(Pa.residual(to_device(a.u, dev))), a.f, a.f_bound)
+        check("box beside bratu", to_numpy(Pb.jvp(to_device(b.v, dev), to_device(b.u, dev))), b.jv, b.jv_bound)
     Pa.close()
-    _check("box after bratu closed", _np(Pb.residual(_t(b.u, dev))), b.f, b.f_bound)
+    check("box after bratu closed", to_numpy(Pb.residual(to_device(b.u, dev))), b.f, b.f_bound)
     Pb.close()
     Pc = nls.CompiledGridProblem(R.BRATU_SRC, 37, 29, params=R.PROBLEMS["bratu"].params)
-    _check("a fresh bratu after close", _np(Pc.residual(_t(a.u, dev))), a.f, a.f_bound)
-    assert np.array_equal(_np(Pc.initial_guess(device=True)), np.zeros(37 * 29))
+    check("a fresh bratu after close", to_numpy(Pc.residual(to_device(a.u, dev))), a.f, a.f_bound)
+    assert np.array_equal(to_numpy(Pc.initial_guess(device=True)), np.zeros(37 * 29))
     Pc.close()
 
 
@@ -232,11 +182,11 @@ __device__ void nk_point(const nk_nbhd<T> &u, const nk_real *p, nk_site s, T *f)
     w = float(sum((k + 1) * par[k] for k in range(32)))
     u = np.linspace(-1, 1, 12)
     j, i = np.divmod(np.arange(12), 4)
-    assert np.array_equal(_np(P.residual(_t(u, dev))), w * u + (i + 10 * j) + (4 + 100 * 3))   # small integers: exact
+    assert np.array_equal(to_numpy(P.residual(to_device(u, dev))), w * u + (i + 10 * j) + (4 + 100 * 3))   # small integers: exact
     par2 = [x + 1.0 for x in par]
     P.set_p(par2)
     w2 = float(sum((k + 1) * par2[k] for k in range(32)))
-    assert np.array_equal(_np(P.residual(_t(u, dev))), w2 * u + (i + 10 * j) + (4 + 100 * 3))
+    assert np.array_equal(to_numpy(P.residual(to_device(u, dev))), w2 * u + (i + 10 * j) + (4 + 100 * 3))
     P.close()
 
 
@@ -246,12 +196,12 @@ def _pair(nls, dev, which):
     if which == "bratu":
         ns = 33
         par = R.bratu_params(ns, 6.0)
-        P = _problem(nls, "bratu", ns, ns)
+        P = problem(nls, R.PROBLEMS["bratu"], (ns, ns))
         P.set_p(par)
-        return P, nls.Bratu2D(ns, 6.0), _t(np.zeros(ns * ns), dev), par, ns
+        return P, nls.Bratu2D(ns, 6.0), to_device(np.zeros(ns * ns), dev), par, ns
     N = 24
     par = R.brusselator_params(N)
-    P = _problem(nls, "brusselator", N, N)
+    P = problem(nls, R.PROBLEMS["brusselator"], (N, N))
     P.set_p(par)
     B = nls.Brusselator2D(N)
     return P, B, B.initial_guess(device=True), par, N
@@ -307,9 +257,9 @@ def test_solves_like_the_built_in(nls, dev, which, algname):
     print(f"{which} {algname}: compiled {sol.retcode} {sol.stats}, built-in {blt.retcode} {blt.stats}")
     assert sol.retcode == "Success" == blt.retcode
     assert sol.stats.nsteps == blt.stats.nsteps
-    fb = _np(B.residual(sol.u))
+    fb = to_numpy(B.residual(sol.u))
     name = "bratu" if which == "bratu" else "brusselator"
-    at_root = R.Reference(R.PROBLEMS[name], nx, nx, _np(sol.u), np.zeros(sol.u.numel()), par)
+    at_root = GC.Reference(R.PROBLEMS[name], (nx, nx), to_numpy(sol.u), np.zeros(sol.u.numel()), params=par)
     print(f"  built-in residual at the compiled problem's root: {np.abs(fb).max():.3e}; residual bound there {at_root.f_bound.max():.3e}")
     assert float(np.abs(fb).max()) <= abstol + float(at_root.f_bound.max())
     assert sol.stats.nf == blt.stats.nf
@@ -332,7 +282,7 @@ def test_step_and_init_interface(nls, dev):
     assert f0 == cb.fnorm_inf == R.bratu_params(ns, 6.0)[1]   # f(0) = −c_exp·e⁰ at every node
     nls.step_(c)
     nls.step_(cb)
-    print(f"after one step: |u - u_builtin| {np.abs(_np(c.u) - _np(cb.u)).max():.3e}, fnorm {c.fnorm_inf:.6e} vs {cb.fnorm_inf:.6e}")
+    print(f"after one step: |u - u_builtin| {np.abs(to_numpy(c.u) - to_numpy(cb.u)).max():.3e}, fnorm {c.fnorm_inf:.6e} vs {cb.fnorm_inf:.6e}")
     assert c.nsteps == cb.nsteps == 1 and c.fnorm_inf < 0.5 * f0
     assert nls.solve_(c).retcode == "Success" == nls.solve_(cb).retcode
     assert c.nsteps == cb.nsteps
@@ -343,7 +293,4 @@ def test_step_and_init_interface(nls, dev):
 
 def test_close_module_problems(nls):
     """(last in the file) the problems the module shared are freed; a double close is harmless"""
-    for P in _PROBLEMS.values():
-        P.close()
-        P.close()
-    _PROBLEMS.clear()
+    close_problems()

@@ -1,6 +1,6 @@
 """Compiled grid problems with a radius-2 stencil on the device (csrc/nk_grid.hip: NK_GRID_STAR2 in 2-D and 3-D,
 NK_GRID_DIAMOND2 in 2-D): the generated residual, dual-number JVP and Jacobian-fill kernels against the NumPy restatement
-tests/grid_r2_reference.py, entry by entry within the restatement's own bound
+(tests/grid_core.py, tests/grid_r2_reference.py), entry by entry within the restatement's own bound
 
     |device − float64 restatement| <= 16 × |float64 − long double| + 4 eps × Σ|terms of the entry|
 
@@ -10,57 +10,18 @@ asserted."""
 import numpy as np
 import pytest
 
+import grid_core as GC
 import grid_r2_reference as R
 import grid_reference as R1
+from grid_device import assert_parity, check, close_problems, device_quantities, problem, to_device, to_numpy
 
 pytestmark = pytest.mark.gpu
 
-_PROBLEMS = {}
 LAMBDA = 3.0   # Bratu on (a box inside) the unit square / cube: well below the turning point in both dimensions
-
-
-def _t(x, dev):
-    import torch
-    return torch.tensor(np.asarray(x, dtype=np.float64), dtype=torch.float64, device=dev)
-
-
-def _np(x):
-    return x.detach().cpu().numpy() if hasattr(x, "detach") else np.asarray(x)
 
 
 def _create(nls, source, shape, **kw):
     return nls.CompiledGridProblem(source, shape[0], shape[1], nz=shape[2] if len(shape) == 3 else None, **kw)
-
-
-def _problem(nls, name, shape):
-    """one compiled problem per case for the whole module (the parameters are put back by whoever changes them)"""
-    key = (name, tuple(shape))
-    if key not in _PROBLEMS:
-        p = R.PROBLEMS[name]
-        _PROBLEMS[key] = _create(nls, p.source, shape, dof=p.dof, stencil=p.stencil, boundary=p.boundary, params=p.params)
-    return _PROBLEMS[key]
-
-
-def _check(what, got, ref, bound, exact=False):
-    """exact: the case agrees bit for bit (measured on the MI355X), so that is what is asserted"""
-    err = np.abs(got - ref)
-    worst = float(np.max(err - bound))
-    same = int(np.sum(got == ref))
-    print(f"{what}: max err {err.max():.3e}, max bound {bound.max():.3e}, min bound {bound.min():.3e}, worst err - bound "
-          f"{worst:.3e}, bitwise equal {same}/{got.size}")
-    assert np.all(np.isfinite(got)), what
-    assert np.all(err <= bound), (what, worst)
-    if exact:
-        assert np.array_equal(got, ref), what
-
-
-def _device_quantities(P, u, v, dev):
-    """residual, J·v, CSR values of the fill, Jᵀv and the filled matrix times v"""
-    du, dv = _t(u, dev), _t(v, dev)
-    J = P.jac_csr()
-    P.jac_values(du, J)
-    return dict(f=_np(P.residual(du)), jv=_np(P.jvp(dv, du)), vals=np.array(J.values()), jtv=_np(P.vjp(dv, du)),
-                spmv=_np(J.matvec(dv)))
 
 
 # ------------------------------------------------------------------------------------------------ parity with the restatement
@@ -75,16 +36,7 @@ def test_parity_with_the_restatement(nls, dev, name, shape):
     then the consistency of fill and JVP: the filled matrix times v against the dual JVP within the sum of the two bounds.
     The upwind problems, sh and diamond_dirichlet have no elementary function in them: with -ffp-contract=off the device's
     +, −, × are the restatement's in the restatement's order. What the MI355X showed is recorded at EXACT below and asserted."""
-    ref = R.reference(name, shape)
-    P = _problem(nls, name, shape)
-    assert P.n_local == ref.u.size and P.jac_csr().info()["nnz"] == ref.vals.size
-    got = _device_quantities(P, ref.u, ref.v, dev)
-    tag = f"{name} {'x'.join(map(str, shape))}"
-    for k in ("f", "jv", "vals", "jtv", "spmv"):
-        _check(f"{tag} {k}", got[k], getattr(ref, k), getattr(ref, k + "_bound"), exact=name in EXACT)
-    diff = np.abs(got["spmv"] - got["jv"])
-    print(f"{tag} fill·v vs dual JVP: max {diff.max():.3e}")
-    assert np.all(diff <= ref.spmv_bound + ref.jv_bound)
+    assert_parity(nls, dev, R.PROBLEMS[name], shape, exact=name in EXACT)
 
 
 # The problems whose five quantities agreed BIT FOR BIT with the restatement at every shape of their dimension on the MI355X
@@ -100,7 +52,7 @@ EXACT = ("upwind2_dirichlet", "upwind2_periodic", "sh", "diamond_dirichlet", "up
 def test_source_that_reads_outside_its_stencil_gives_nan(nls, dev, key, stencil, shape):
     n = int(np.prod(shape))
     P = _create(nls, R.OUTSIDE_SRC[key], shape, stencil=stencil)
-    f = _np(P.residual(_t(np.linspace(-1, 1, n), dev)))
+    f = to_numpy(P.residual(to_device(np.linspace(-1, 1, n), dev)))
     assert f.shape == (n,) and np.all(np.isnan(f))
     P.close()
 
@@ -109,32 +61,32 @@ def test_star2_source_is_finite_under_diamond2(nls, dev):
     """the diamond contains the star: a source written for star2 is a valid diamond2 problem, with the same residual; and the
     star2 source that reads (1, 1) — NaN under star2 — is finite under diamond2"""
     shape = (37, 29)
-    ref = R.reference("lap4", shape)
+    ref = GC.reference(R.PROBLEMS["lap4"], shape)
     P = _create(nls, R.LAP4_SRC, shape, stencil="diamond2", params=R.PROBLEMS["lap4"].params)
-    _check("lap4 under diamond2", _np(P.residual(_t(ref.u, dev))), ref.f, ref.f_bound)
-    assert P.jac_csr().info()["nnz"] == R.pattern(shape, 1, "diamond2", "dirichlet")[1].size
+    check("lap4 under diamond2", to_numpy(P.residual(to_device(ref.u, dev))), ref.f, ref.f_bound)
+    assert P.jac_csr().info()["nnz"] == GC.stencil_pattern(shape, 1, "diamond2", "dirichlet")[1].size
     P.close()
     Pd = _create(nls, R.OUTSIDE_SRC["star2"], (6, 5), stencil="diamond2")
-    assert np.all(np.isfinite(_np(Pd.residual(_t(np.linspace(-1, 1, 30), dev)))))
+    assert np.all(np.isfinite(to_numpy(Pd.residual(to_device(np.linspace(-1, 1, 30), dev)))))
     Pd.close()
 
 
 def test_reinit_p_changes_the_residual_as_the_restatement_says(nls, dev):
-    name, shape = "diamond_dirichlet", (37, 29)
+    case, shape = R.PROBLEMS["diamond_dirichlet"], (37, 29)
     p0, p1 = R.DIAMOND_PARAMS, [-0.5, 0.125, 2.0]
-    P = _problem(nls, name, shape)
-    ref0, ref1 = R.reference(name, shape), R.reference(name, shape, params=p1)
-    prob = nls.NonlinearProblem(P, _t(ref0.u, dev), p0)
+    P = problem(nls, case, shape)
+    ref0, ref1 = GC.reference(case, shape), GC.reference(case, shape, params=p1)
+    prob = nls.NonlinearProblem(P, to_device(ref0.u, dev), p0)
     cache = nls.init(prob, nls.NewtonRaphson(linsolve=nls.KrylovJL_GMRES()), abstol=1e-10)
-    _check("fu after init", _np(cache.fu), ref0.f, ref0.f_bound)
-    nls.reinit_(cache, u0=_t(ref0.u, dev), p=p1)
-    _check("fu after reinit_(p=...)", _np(cache.fu), ref1.f, ref1.f_bound)
+    check("fu after init", to_numpy(cache.fu), ref0.f, ref0.f_bound)
+    nls.reinit_(cache, u0=to_device(ref0.u, dev), p=p1)
+    check("fu after reinit_(p=...)", to_numpy(cache.fu), ref1.f, ref1.f_bound)
     assert float(np.max(np.abs(ref1.f - ref0.f))) > 1e6 * float(ref1.f_bound.max())
     # the Jacobian follows the parameters too (a fill cached for the same u is not reused)
-    u = _t(ref0.u, dev)
-    _check("Jᵀv with the new p", _np(P.vjp(_t(ref0.v, dev), u)), ref1.jtv, ref1.jtv_bound)
+    u = to_device(ref0.u, dev)
+    check("Jᵀv with the new p", to_numpy(P.vjp(to_device(ref0.v, dev), u)), ref1.jtv, ref1.jtv_bound)
     P.set_p(p0)
-    _check("Jᵀv with the old p, same u buffer", _np(P.vjp(_t(ref0.v, dev), u)), ref0.jtv, ref0.jtv_bound)
+    check("Jᵀv with the old p, same u buffer", to_numpy(P.vjp(to_device(ref0.v, dev), u)), ref0.jtv, ref0.jtv_bound)
     with pytest.raises(ValueError):
         P.set_p([1.0])
     cache.close()
@@ -144,41 +96,42 @@ def test_radius_1_beside_radius_2_and_a_fresh_problem_after_close(nls, dev):
     """the radius-1 Bratu source and the fourth-order one, alive together and called in turn: each keeps its kernels, its
     pattern and its parameters (the radius-2 programs carry an option of their own, so the cache keeps them apart)"""
     shape = (37, 29)
-    a1, a2 = R1.reference("bratu", *shape), R.reference("lap4", shape)
+    a1, a2 = GC.reference(R1.PROBLEMS["bratu"], shape), GC.reference(R.PROBLEMS["lap4"], shape)
     P1 = nls.CompiledGridProblem(R1.BRATU_SRC, *shape, params=R1.PROBLEMS["bratu"].params)
     P2 = _create(nls, R.LAP4_SRC, shape, stencil="star2", params=R.PROBLEMS["lap4"].params)
     assert P1.jac_csr().info()["nnz"] == a1.vals.size and P2.jac_csr().info()["nnz"] == a2.vals.size
     for _ in range(2):
-        g1, g2 = _device_quantities(P1, a1.u, a1.v, dev), _device_quantities(P2, a2.u, a2.v, dev)
+        g1, g2 = device_quantities(P1, a1.u, a1.v, dev), device_quantities(P2, a2.u, a2.v, dev)
         for k in ("f", "jv", "vals", "jtv"):
-            _check(f"radius-1 bratu beside lap4 {k}", g1[k], getattr(a1, k), getattr(a1, k + "_bound"))
-            _check(f"lap4 beside radius-1 bratu {k}", g2[k], getattr(a2, k), getattr(a2, k + "_bound"))
+            check(f"radius-1 bratu beside lap4 {k}", g1[k], getattr(a1, k), getattr(a1, k + "_bound"))
+            check(f"lap4 beside radius-1 bratu {k}", g2[k], getattr(a2, k), getattr(a2, k + "_bound"))
     P1.set_p([2.0, 0.5])   # the radius-1 problem's parameters are its own
-    _check("lap4 after the radius-1 set_p", _np(P2.residual(_t(a2.u, dev))), a2.f, a2.f_bound)
+    check("lap4 after the radius-1 set_p", to_numpy(P2.residual(to_device(a2.u, dev))), a2.f, a2.f_bound)
     P1.close()
-    _check("lap4 after the radius-1 close", _np(P2.jvp(_t(a2.v, dev), _t(a2.u, dev))), a2.jv, a2.jv_bound)
+    check("lap4 after the radius-1 close", to_numpy(P2.jvp(to_device(a2.v, dev), to_device(a2.u, dev))), a2.jv, a2.jv_bound)
     P2.close()
     P3 = _create(nls, R.LAP4_SRC, shape, stencil="star2", params=R.PROBLEMS["lap4"].params)
-    _check("a fresh lap4 after close", _np(P3.residual(_t(a2.u, dev))), a2.f, a2.f_bound)
-    assert np.array_equal(_np(P3.initial_guess(device=True)), np.zeros(37 * 29))
+    check("a fresh lap4 after close", to_numpy(P3.residual(to_device(a2.u, dev))), a2.f, a2.f_bound)
+    assert np.array_equal(to_numpy(P3.initial_guess(device=True)), np.zeros(37 * 29))
     P3.close()
 
 
 def test_a_2d_and_a_3d_radius_2_problem_side_by_side(nls, dev):
     s2, s3 = (37, 29), (7, 6, 5)
-    a2, a3 = R.reference("upwind2_periodic", s2), R.reference("upwind3_periodic", s3)
-    P2, P3 = _problem(nls, "upwind2_periodic", s2), _problem(nls, "upwind3_periodic", s3)
+    c2, c3 = R.PROBLEMS["upwind2_periodic"], R.PROBLEMS["upwind3_periodic"]
+    a2, a3 = GC.reference(c2, s2), GC.reference(c3, s3)
+    P2, P3 = problem(nls, c2, s2), problem(nls, c3, s3)
     assert not hasattr(P2, "nz") and P3.nz == 5
     for _ in range(2):
-        g2, g3 = _device_quantities(P2, a2.u, a2.v, dev), _device_quantities(P3, a3.u, a3.v, dev)
+        g2, g3 = device_quantities(P2, a2.u, a2.v, dev), device_quantities(P3, a3.u, a3.v, dev)
         for k in ("f", "jv", "vals", "jtv"):
-            _check(f"2-D upwind beside 3-D {k}", g2[k], getattr(a2, k), getattr(a2, k + "_bound"))
-            _check(f"3-D upwind beside 2-D {k}", g3[k], getattr(a3, k), getattr(a3, k + "_bound"))
+            check(f"2-D upwind beside 3-D {k}", g2[k], getattr(a2, k), getattr(a2, k + "_bound"))
+            check(f"3-D upwind beside 2-D {k}", g3[k], getattr(a3, k), getattr(a3, k + "_bound"))
     q = [x + 1.0 for x in R.UPWIND2_PARAMS]
     P2.set_p(q)            # the 2-D problem's parameters are its own
-    _check("3-D after the 2-D set_p", _np(P3.residual(_t(a3.u, dev))), a3.f, a3.f_bound)
-    b2 = R.reference("upwind2_periodic", s2, params=q)
-    _check("2-D with its new p", _np(P2.residual(_t(a2.u, dev))), b2.f, b2.f_bound)
+    check("3-D after the 2-D set_p", to_numpy(P3.residual(to_device(a3.u, dev))), a3.f, a3.f_bound)
+    b2 = GC.reference(c2, s2, params=q)
+    check("2-D with its new p", to_numpy(P2.residual(to_device(a2.u, dev))), b2.f, b2.f_bound)
     P2.set_p(R.UPWIND2_PARAMS)
 
 
@@ -188,7 +141,7 @@ SOLVE_SHAPES = {"lap4": (9, 8), "lap4_3": (8, 7, 6)}
 
 
 def _bratu(nls, name, shape):
-    P = _problem(nls, name, shape)
+    P = problem(nls, R.PROBLEMS[name], shape)
     par = R.lap4_params(shape[0], LAMBDA)
     P.set_p(par)
     return P, par
@@ -196,7 +149,7 @@ def _bratu(nls, name, shape):
 
 def _restated_residual(name, shape, u, par):
     """the restatement's residual at u with its entrywise bound"""
-    at = R.Reference(R.PROBLEMS[name], shape, u, np.zeros(u.size), par)
+    at = GC.Reference(R.PROBLEMS[name], shape, u, np.zeros(u.size), params=par)
     return at.f, at.f_bound
 
 
@@ -205,7 +158,7 @@ def _dense_newton(name, shape, par):
     if (name, shape) not in _NEWTON:
         prob, u = R.PROBLEMS[name], np.zeros(int(np.prod(shape)))
         for _it in range(30):
-            J, f = R.dense_jacobian(prob, shape, u, par)
+            J, f = GC.dense_jacobian(prob, shape, u, params=par)
             if np.abs(f).max() <= 1e-12:
                 break
             u = u - np.linalg.solve(J, f)
@@ -249,8 +202,8 @@ def test_solves_lap4_like_a_dense_newton(nls, dev, name, algname):
     kw = dict(abstol=abstol, maxiters=60)
     if algname == "dfsane":   # a residual-only method: more, cheaper steps; the plain ‖F‖∞ <= abstol test
         kw = dict(abstol=abstol, maxiters=2000, termination_condition=nls.AbsNormTerminationMode())
-    sol = nls.solve(nls.NonlinearProblem(P, _t(np.zeros(u_ref.size), dev)), _algorithms(nls)[algname], **kw)
-    u_dev = _np(sol.u)
+    sol = nls.solve(nls.NonlinearProblem(P, to_device(np.zeros(u_ref.size), dev)), _algorithms(nls)[algname], **kw)
+    u_dev = to_numpy(sol.u)
     f_at, f_bound = _restated_residual(name, shape, u_dev, par)
     f_dev = float(np.abs(f_at).max())
     err, bound = float(np.abs(u_dev - u_ref).max()), 2.0 * jinv * (f_dev + f_ref)
@@ -277,11 +230,11 @@ def test_default_sstep_gmres_on_the_filled_jacobian(nls, dev, shape):
     n = shape[0] * shape[1]
     alg = nls.NewtonRaphson(linsolve=nls.KrylovJL_GMRES(), concrete_jac=True)
     assert alg.linsolve.ortho == "sstep"
-    sol = nls.solve(nls.NonlinearProblem(P, _t(np.zeros(n), dev)), alg, abstol=abstol, maxiters=60)
-    f, fb = _restated_residual("lap4", shape, _np(sol.u), par)
+    sol = nls.solve(nls.NonlinearProblem(P, to_device(np.zeros(n), dev)), alg, abstol=abstol, maxiters=60)
+    f, fb = _restated_residual("lap4", shape, to_numpy(sol.u), par)
     J = P.jac_csr()
     P.jac_values(sol.u, J)
-    _Y, resident = J.powers(_t(np.ones(n), dev), 4)
+    _Y, resident = J.powers(to_device(np.ones(n), dev), 4)
     print(f"lap4 {shape}: {sol.retcode} {sol.stats}; restated |F| {np.abs(f).max():.3e}, bound {fb.max():.3e}; "
           f"matrix powers of this Jacobian: {'resident' if resident else 'streaming'} kernel")
     assert sol.retcode == "Success" and sol.stats.njacs >= sol.stats.nsteps > 0 and sol.stats.gmres_iters > 0
@@ -292,7 +245,4 @@ def test_default_sstep_gmres_on_the_filled_jacobian(nls, dev, shape):
 
 def test_close_module_problems(nls):
     """(last in the file) the problems the module shared are freed; a double close is harmless"""
-    for P in _PROBLEMS.values():
-        P.close()
-        P.close()
-    _PROBLEMS.clear()
+    close_problems()

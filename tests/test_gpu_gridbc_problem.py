@@ -1,6 +1,6 @@
 """Compiled grid problems with a boundary kind per side on the device (csrc/nk_grid.hip, NK_GRID_SIDES): the generated residual,
 dual-number JVP and Jacobian-fill kernels under mirror walls, channels and mixed sides, against the NumPy restatement
-tests/gridbc_reference.py, entry by entry within the restatement's own bound
+(tests/grid_core.py, tests/gridbc_reference.py), entry by entry within the restatement's own bound
 
     |device − float64 restatement| <= 16 × |float64 − long double| + 4 eps × Σ|terms of the entry|
 
@@ -14,65 +14,17 @@ import sys
 import numpy as np
 import pytest
 
+import grid_core as GC
 import grid_reference as G1
 import gridbc_reference as R
-import gridf_reference as GF
+from grid_device import (QUANTITIES, assert_parity, check, close_problems, create, device_quantities, problem, to_device,
+                         to_numpy)
 
 pytestmark = pytest.mark.gpu
 
-_PROBLEMS = {}
+_SOLVE_PROBLEMS = {}   # the problems of the solves, with their own parameters
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
-
-def _t(x, dev):
-    import torch
-    return torch.tensor(np.asarray(x, dtype=np.float64), dtype=torch.float64, device=dev)
-
-
-def _np(x):
-    return x.detach().cpu().numpy() if hasattr(x, "detach") else np.asarray(x)
-
-
-def _create(nls, prob, shape, params=None):
-    return nls.CompiledGridProblem(prob.source, shape[0], shape[1], dof=prob.dof, stencil=prob.stencil, boundary=prob.boundary,
-                                   params=prob.params if params is None else params, nz=shape[2] if prob.dim == 3 else None,
-                                   fields=prob.nfields)
-
-
-def _problem(nls, name, shape):
-    """one compiled problem per case for the whole module, holding the seeded fields"""
-    key = (name, tuple(shape))
-    if key not in _PROBLEMS:
-        prob = R.PROBLEMS[name]
-        P = _PROBLEMS[key] = _create(nls, prob, shape)
-        for k in range(prob.nfields):
-            P.set_field(k, GF.seeded_fields(prob.nfields, shape)[k])
-    return _PROBLEMS[key]
-
-
-def _check(what, got, ref, bound, exact=False):
-    """exact: the case agrees bit for bit (measured on the MI355X), so that is what is asserted"""
-    err = np.abs(got - ref)
-    worst = float(np.max(err - bound))
-    same = int(np.sum(got == ref))
-    print(f"{what}: max err {err.max():.3e}, max bound {bound.max():.3e}, min bound {bound.min():.3e}, worst err - bound "
-          f"{worst:.3e}, bitwise equal {same}/{got.size}")
-    assert np.all(np.isfinite(got)), what
-    assert np.all(err <= bound), (what, worst)
-    if exact:
-        assert np.array_equal(got, ref), what
-
-
-def _device_quantities(P, u, v, dev):
-    """residual, J·v, CSR values of the fill, Jᵀv and the filled matrix times v"""
-    du, dv = _t(u, dev), _t(v, dev)
-    J = P.jac_csr()
-    P.jac_values(du, J)
-    return dict(f=_np(P.residual(du)), jv=_np(P.jvp(dv, du)), vals=np.array(J.values()), jtv=_np(P.vjp(dv, du)),
-                spmv=_np(J.matvec(dv)))
-
-
-QUANTITIES = ("f", "jv", "vals", "jtv", "spmv")
 
 # ------------------------------------------------------------------------------------------------ parity with the restatement
 _CASES = [(name, shape) for name in sorted(R.PROBLEMS) for shape in R.sizes(R.PROBLEMS[name])]
@@ -86,17 +38,9 @@ def test_parity_with_the_restatement(nls, dev, name, shape):
     JVP within the sum of the two bounds. The merge is plain additions in the restatement's order (ascending stencil point), so
     sources without an elementary function are expected to agree bit for bit; what the MI355X showed is recorded at EXACT
     below and asserted."""
-    prob, ref = R.PROBLEMS[name], R.reference(name, shape)
-    P = _problem(nls, name, shape)
-    assert P.boundary == prob.boundary
-    assert P.n_local == ref.u.size and P.jac_csr().info()["nnz"] == ref.vals.size
-    got = _device_quantities(P, ref.u, ref.v, dev)
-    tag = f"{name} {'x'.join(map(str, shape))}"
-    for k in QUANTITIES:
-        _check(f"{tag} {k}", got[k], getattr(ref, k), getattr(ref, k + "_bound"), exact=name in EXACT)
-    diff = np.abs(got["spmv"] - got["jv"])
-    print(f"{tag} fill·v vs dual JVP: max {diff.max():.3e}")
-    assert np.all(diff <= ref.spmv_bound + ref.jv_bound)
+    prob = R.PROBLEMS[name]
+    assert problem(nls, prob, shape).boundary == prob.boundary
+    assert_parity(nls, dev, prob, shape, exact=name in EXACT)
 
 
 # The problems whose five quantities agreed BIT FOR BIT with the restatement at all their shapes on the MI355X: every problem
@@ -113,9 +57,11 @@ import sys
 import numpy as np, torch
 sys.path.insert(0, sys.argv[1]); sys.path.insert(0, sys.argv[1] + "/tests")
 import nonlinearsolve_jl_amd as nls
+import grid_core as GC
 import gridbc_reference as R
 name, shape = sys.argv[2], tuple(int(x) for x in sys.argv[3].split("x"))
-prob, ref = R.PROBLEMS[name], R.reference(name, shape)
+prob = R.PROBLEMS[name]
+ref = GC.reference(prob, shape)
 P = nls.CompiledGridProblem(prob.source, shape[0], shape[1], dof=prob.dof, stencil=prob.stencil, boundary=prob.boundary,
                             params=prob.params)
 u = torch.tensor(ref.u, dtype=torch.float64, device="cuda:0")
@@ -130,7 +76,7 @@ def test_direct_fill_in_a_fresh_process(nls, dev, tmp_path):
     """NK_GRID_FILL_DIRECT=1 (every thread stores its own merged partials, no staging in LDS): the box mirrored in both axes at
     37 × 29, once, in a child process of its own; the values under the restatement's bound and equal to the staged form's"""
     name, shape = "box_mirror", (37, 29)
-    ref = R.reference(name, shape)
+    ref = GC.reference(R.PROBLEMS[name], shape)
     out = tmp_path / "vals.npy"
     env = dict(os.environ, NK_GRID_FILL_DIRECT="1")
     done = subprocess.run([sys.executable, "-c", _CHILD, ROOT, name, "x".join(map(str, shape)), str(out)], env=env,
@@ -138,16 +84,16 @@ def test_direct_fill_in_a_fresh_process(nls, dev, tmp_path):
     print(done.stdout[-2000:], done.stderr[-2000:])
     assert done.returncode == 0
     direct = np.load(out)
-    _check("box_mirror 37x29 vals, direct fill", direct, ref.vals, ref.vals_bound)
-    P = _problem(nls, name, shape)
+    check("box_mirror 37x29 vals, direct fill", direct, ref.vals, ref.vals_bound)
+    P = problem(nls, R.PROBLEMS[name], shape)
     J = P.jac_csr()
-    P.jac_values(_t(ref.u, dev), J)
+    P.jac_values(to_device(ref.u, dev), J)
     assert np.array_equal(direct, np.array(J.values()))
 
 
 # ------------------------------------------------------------------------------------------------ conservation
 def _heat_fields(shape, level):
-    f = GF.seeded_fields(3, shape)
+    f = GC.seeded_fields(3, shape)
     return np.stack([level, f[1], np.zeros_like(level)])
 
 
@@ -162,21 +108,21 @@ def test_implicit_euler_between_zero_flux_walls_conserves_the_sum(nls, dev):
     alg = nls.NewtonRaphson(linsolve=nls.KrylovJL_GMRES(), concrete_jac=True)
     worst = {}
     for tag, prob in (("mirror_face", R.PROBLEMS["vardiff_mirror_face"]), ("dirichlet", R.DIRICHLET_TWIN["vardiff_mirror_face"])):
-        P = _create(nls, prob, shape, params)
+        P = create(nls, prob, shape, params)
         fields = _heat_fields(shape, a_start)
         for k in range(3):
             P.set_field(k, fields[k])
-        cache = nls.init(nls.NonlinearProblem(P, _t(a_start, dev)), alg, abstol=1e-10, maxiters=40)
+        cache = nls.init(nls.NonlinearProblem(P, to_device(a_start, dev)), alg, abstol=1e-10, maxiters=40)
         ratios = []
         for step in range(3):
             P.set_field(0, cache.u)
             nls.reinit_(cache, u0=cache.u)
             sol = nls.solve_(cache)
-            a0, u = _np(P.field(0)), _np(cache.u)
+            a0, u = to_numpy(P.field(0)), to_numpy(cache.u)
             fields = _heat_fields(shape, a0)
-            f = R.evaluate(prob, shape, u, u, fields, params=params).f
-            drift = abs(float(np.sum(u.astype(R.LD)) - np.sum(a0.astype(R.LD))))
-            bound = dt * float(np.abs(f).sum()) + 8 * nn * R.EPS * float(np.abs(u).sum())
+            f = GC.evaluate(prob, shape, u, u, fields, params=params).f
+            drift = abs(float(np.sum(u.astype(GC.LD)) - np.sum(a0.astype(GC.LD))))
+            bound = dt * float(np.abs(f).sum()) + 8 * nn * GC.EPS * float(np.abs(u).sum())
             print(f"{tag} step {step}: {sol.retcode}; |sum u - sum a0| {drift:.3e}, bound {bound:.3e}, |F|_1 {np.abs(f).sum():.3e}, "
                   f"|u - a0| {np.abs(u - a0).max():.3e}")
             assert sol.retcode == "Success"
@@ -212,7 +158,7 @@ def _start(name, shape):
     """the initial guess of the solves: half the case's seeded u, |u0| <= 0.5. Not zero: TrustRegion's largest radius is
     max(‖F(u0)‖₂, max u0 − min u0) (the reference's rule), which at u0 = 0 of the channel is ‖F(0)‖₂ = 0.022 against a root 4
     away in the 2-norm — sixty steps of that length end as MaxIters, as the first device run showed"""
-    return 0.5 * R.inputs(R.PROBLEMS[name], shape)[0]
+    return 0.5 * GC.inputs(R.PROBLEMS[name], shape)[0]
 
 
 def _reference_root(name, shape):
@@ -220,8 +166,8 @@ def _reference_root(name, shape):
     ‖J(u_ref)⁻¹‖∞"""
     if (name, shape) not in _REFERENCE_ROOTS:
         prob, par = R.PROBLEMS[name], SOLVE_PARAMS[name]
-        u = R.dense_newton(prob, shape, _start(name, shape), params=par, tol=1e-12, maxiters=40)
-        J, f = R.dense_jacobian(prob, shape, u, params=par)
+        u = GC.dense_newton(prob, shape, _start(name, shape), params=par, tol=1e-12, maxiters=40)
+        J, f = GC.dense_jacobian(prob, shape, u, params=par)
         assert np.abs(f).max() <= 1e-12
         _REFERENCE_ROOTS[(name, shape)] = (u, float(np.abs(f).max()), float(np.linalg.norm(np.linalg.inv(J), np.inf)))
     return _REFERENCE_ROOTS[(name, shape)]
@@ -235,41 +181,43 @@ def test_solves_like_a_dense_newton(nls, dev, name, shape, algname):
     residuals by the restatement, the factor 2 for the second-order term — the tolerance of tests/test_gpu_gridf_problem.py"""
     prob, par, abstol = R.PROBLEMS[name], SOLVE_PARAMS[name], 1e-10
     u_ref, f_ref, jinv = _reference_root(name, shape)
-    if ("solve", name) not in _PROBLEMS:
-        _PROBLEMS[("solve", name)] = _create(nls, prob, shape, par)
-    P = _PROBLEMS[("solve", name)]
-    sol = nls.solve(nls.NonlinearProblem(P, _t(_start(name, shape), dev)), _algorithms(nls)[algname], abstol=abstol, maxiters=60)
-    u_dev = _np(sol.u)
-    f_dev = float(np.abs(R.evaluate(prob, shape, u_dev, u_dev, params=par).f).max())
+    if name not in _SOLVE_PROBLEMS:
+        _SOLVE_PROBLEMS[name] = create(nls, prob, shape, par)
+    P = _SOLVE_PROBLEMS[name]
+    sol = nls.solve(nls.NonlinearProblem(P, to_device(_start(name, shape), dev)), _algorithms(nls)[algname], abstol=abstol, maxiters=60)
+    u_dev = to_numpy(sol.u)
+    f_dev = float(np.abs(GC.evaluate(prob, shape, u_dev, u_dev, params=par).f).max())
     err, bound = float(np.abs(u_dev - u_ref).max()), 2.0 * jinv * (f_dev + f_ref)
     print(f"{name} {algname}: {sol.retcode} {sol.stats}; |u_dev - u_ref| {err:.3e}, bound {bound:.3e} (|J^-1| {jinv:.3e}, "
           f"|F(u_dev)| {f_dev:.3e}, |F(u_ref)| {f_ref:.3e}); |u_ref| {np.abs(u_ref).max():.3e}")
     assert sol.retcode == "Success"
     assert np.abs(u_ref - _start(name, shape)).max() > 1e-3          # (the root is not the initial guess)
     assert err <= bound
-    assert f_dev <= abstol + float(R.Reference(prob, shape, u_dev, u_dev, params=par).f_bound.max())
+    assert f_dev <= abstol + float(GC.Reference(prob, shape, u_dev, u_dev, params=par).f_bound.max())
 
 
 # ------------------------------------------------------------------------------------------------ the old paths
 def test_a_packed_all_periodic_code_is_the_periodic_problem(nls, dev):
     """created with a kind per side, all periodic: the five arrays of the problem created with "periodic", bit for bit"""
     name, shape = "box_periodic", (37, 29)
-    p, ref = G1.PROBLEMS[name], G1.reference(name, *shape)
+    p = G1.PROBLEMS[name]
+    ref = GC.reference(p, shape)
     plain = nls.CompiledGridProblem(p.source, *shape, dof=p.dof, stencil=p.stencil, boundary="periodic", params=p.params)
     packed = nls.CompiledGridProblem(p.source, *shape, dof=p.dof, stencil=p.stencil, boundary=("periodic",) * 4, params=p.params)
     assert packed.boundary == ("periodic",) * 4
-    a, b = _device_quantities(plain, ref.u, ref.v, dev), _device_quantities(packed, ref.u, ref.v, dev)
+    a, b = device_quantities(plain, ref.u, ref.v, dev), device_quantities(packed, ref.u, ref.v, dev)
     for k in QUANTITIES:
         print(f"packed vs plain periodic {k}: max difference {np.abs(a[k] - b[k]).max():.3e}")
         assert np.array_equal(a[k], b[k])
-        _check(f"packed periodic {k}", b[k], getattr(ref, k), getattr(ref, k + "_bound"))
+        check(f"packed periodic {k}", b[k], getattr(ref, k), getattr(ref, k + "_bound"))
     plain.close()
     packed.close()
 
 
 def test_close_module_problems(nls):
     """(last in the file) the problems the module shared are freed; a double close is harmless"""
-    for P in _PROBLEMS.values():
+    close_problems()
+    for P in _SOLVE_PROBLEMS.values():
         P.close()
         P.close()
-    _PROBLEMS.clear()
+    _SOLVE_PROBLEMS.clear()

@@ -1,6 +1,6 @@
 """Compiled grid problems with fields on the device (csrc/nk_grid.hip, nk_problem_create_grid_fields): the generated residual,
 dual-number JVP and Jacobian-fill kernels of sources that read read-only data on the grid, against the NumPy restatement
-tests/gridf_reference.py, entry by entry within the restatement's own bound
+(tests/grid_core.py, tests/gridf_reference.py), entry by entry within the restatement's own bound
 
     |device − float64 restatement| <= 16 × |float64 − long double| + 4 eps × Σ|terms of the entry|
 
@@ -12,64 +12,13 @@ import ctypes as C
 import numpy as np
 import pytest
 
+import grid_core as GC
 import grid_reference as G1
 import gridf_reference as R
+from grid_device import (assert_parity, check, close_problems, create, device_quantities, problem, set_fields, to_device,
+                         to_numpy)
 
 pytestmark = pytest.mark.gpu
-
-_PROBLEMS = {}
-
-
-def _t(x, dev):
-    import torch
-    return torch.tensor(np.asarray(x, dtype=np.float64), dtype=torch.float64, device=dev)
-
-
-def _np(x):
-    return x.detach().cpu().numpy() if hasattr(x, "detach") else np.asarray(x)
-
-
-def _create(nls, name, shape):
-    p = R.PROBLEMS[name]
-    return nls.CompiledGridProblem(p.source, shape[0], shape[1], dof=p.dof, stencil=p.stencil, boundary=p.boundary,
-                                   params=p.params, nz=shape[2] if p.dim == 3 else None, fields=p.nfields)
-
-
-def _set_fields(P, fields):
-    for k in range(P.nfields):
-        P.set_field(k, fields[k])
-
-
-def _problem(nls, name, shape):
-    """one compiled problem per case for the whole module, holding the seeded fields (whoever changes them puts them back)"""
-    key = (name, tuple(shape))
-    if key not in _PROBLEMS:
-        _PROBLEMS[key] = _create(nls, name, shape)
-        _set_fields(_PROBLEMS[key], R.seeded_fields(R.PROBLEMS[name].nfields, shape))
-    return _PROBLEMS[key]
-
-
-def _check(what, got, ref, bound, exact=False):
-    """exact: the case agrees bit for bit (measured on the MI355X), so that is what is asserted"""
-    err = np.abs(got - ref)
-    worst = float(np.max(err - bound))
-    same = int(np.sum(got == ref))
-    print(f"{what}: max err {err.max():.3e}, max bound {bound.max():.3e}, min bound {bound.min():.3e}, worst err - bound "
-          f"{worst:.3e}, bitwise equal {same}/{got.size}")
-    assert np.all(np.isfinite(got)), what
-    assert np.all(err <= bound), (what, worst)
-    if exact:
-        assert np.array_equal(got, ref), what
-
-
-def _device_quantities(P, u, v, dev):
-    """residual, J·v, CSR values of the fill, Jᵀv and the filled matrix times v"""
-    du, dv = _t(u, dev), _t(v, dev)
-    J = P.jac_csr()
-    P.jac_values(du, J)
-    return dict(f=_np(P.residual(du)), jv=_np(P.jvp(dv, du)), vals=np.array(J.values()), jtv=_np(P.vjp(dv, du)),
-                spmv=_np(J.matvec(dv)))
-
 
 # ------------------------------------------------------------------------------------------------ parity with the restatement
 _CASES = [(name, shape) for name in sorted(R.PROBLEMS) for shape in R.sizes(R.PROBLEMS[name])]
@@ -83,17 +32,9 @@ def test_parity_with_the_restatement(nls, dev, name, shape):
     then the consistency of fill and JVP: the filled matrix times v against the dual JVP within the sum of the two bounds.
     Only bratu_f / bratu_f4 have an elementary function: with -ffp-contract=off the device's +, −, × are the restatement's in
     the restatement's order. What the MI355X showed is recorded at EXACT below and asserted."""
-    ref = R.reference(name, shape)
-    P = _problem(nls, name, shape)
+    P = problem(nls, R.PROBLEMS[name], shape)
     assert P.nfields == R.PROBLEMS[name].nfields and P.nn == int(np.prod(shape))
-    assert P.n_local == ref.u.size and P.jac_csr().info()["nnz"] == ref.vals.size
-    got = _device_quantities(P, ref.u, ref.v, dev)
-    tag = f"{name} {'x'.join(map(str, shape))}"
-    for k in ("f", "jv", "vals", "jtv", "spmv"):
-        _check(f"{tag} {k}", got[k], getattr(ref, k), getattr(ref, k + "_bound"), exact=name in EXACT)
-    diff = np.abs(got["spmv"] - got["jv"])
-    print(f"{tag} fill·v vs dual JVP: max {diff.max():.3e}")
-    assert np.all(diff <= ref.spmv_bound + ref.jv_bound)
+    assert_parity(nls, dev, R.PROBLEMS[name], shape, exact=name in EXACT)
 
 
 # The problems whose five quantities agreed BIT FOR BIT with the restatement at all their shapes on the MI355X: every problem
@@ -105,52 +46,52 @@ EXACT = ("react2", "vardiff", "vardiff_r", "vardiff3", "vardiff_box_dirichlet", 
 
 # ------------------------------------------------------------------------------------------------ the fields' contract
 def test_fields_are_zero_at_creation_and_set_field_stores_what_it_is_given(nls, dev):
-    name, shape = "vardiff", (37, 29)
-    P = _create(nls, name, shape)
-    zero, ref = R.reference(name, shape, zero_fields=True), R.reference(name, shape)
+    case, shape = R.PROBLEMS["vardiff"], (37, 29)
+    P = create(nls, case, shape)
+    zero, ref = GC.reference(case, shape, zero_fields=True), GC.reference(case, shape)
     for k in range(3):
-        assert np.array_equal(_np(P.field(k)), np.zeros(37 * 29))
-    _check("residual before any set_field", _np(P.residual(_t(ref.u, dev))), zero.f, zero.f_bound)
+        assert np.array_equal(to_numpy(P.field(k)), np.zeros(37 * 29))
+    check("residual before any set_field", to_numpy(P.residual(to_device(ref.u, dev))), zero.f, zero.f_bound)
     assert float(np.max(np.abs(zero.f - ref.f))) > 1e6 * float(ref.f_bound.max())   # (the fields matter to this residual)
     P.set_field(0, ref.fields[0])                      # a host array
-    P.set_field(1, _t(ref.fields[1], dev))             # a device tensor
+    P.set_field(1, to_device(ref.fields[1], dev))      # a device tensor
     P.set_field(2, list(ref.fields[2]))                # anything NumPy makes a float64 vector of
     for k in range(3):
         got = P.field(k)
-        assert got.is_cuda and np.array_equal(_np(got), ref.fields[k])
+        assert got.is_cuda and np.array_equal(to_numpy(got), ref.fields[k])
     got = P.field(1)
     got.zero_()                                        # a copy: the problem's field is its own
-    assert np.array_equal(_np(P.field(1)), ref.fields[1])
-    _check("residual after set_field", _np(P.residual(_t(ref.u, dev))), ref.f, ref.f_bound)
+    assert np.array_equal(to_numpy(P.field(1)), ref.fields[1])
+    check("residual after set_field", to_numpy(P.residual(to_device(ref.u, dev))), ref.f, ref.f_bound)
     P.close()
     P.close()
 
 
-def _mixed_reference(name, shape, k, ref, other):
+def _mixed_reference(case, shape, k, ref, other):
     """the case's reference with field k taken from `other`"""
     fields = np.array(ref.fields)
     fields[k] = other.fields[k]
-    return R.Reference(R.PROBLEMS[name], shape, ref.u, ref.v, fields), fields
+    return GC.Reference(case, shape, ref.u, ref.v, fields), fields
 
 
 def test_a_changed_field_is_not_met_by_a_stale_jacobian(nls, dev):
     """fill J at u, set_field(1, other), fill again at the SAME u buffer: the second matrix is the restatement's for the new
     coefficient, not the first matrix; the same for Jᵀv, which goes through the problem's cached linearisation"""
-    name, shape = "vardiff", (37, 29)
-    P, ref = _problem(nls, name, shape), R.reference(name, shape)
-    new, fields = _mixed_reference(name, shape, 1, ref, R.reference(name, shape, shift=1.0))
-    u, v, J = _t(ref.u, dev), _t(ref.v, dev), P.jac_csr()
+    case, shape = R.PROBLEMS["vardiff"], (37, 29)
+    P, ref = problem(nls, case, shape), GC.reference(case, shape)
+    new, fields = _mixed_reference(case, shape, 1, ref, GC.reference(case, shape, shift=1.0))
+    u, v, J = to_device(ref.u, dev), to_device(ref.v, dev), P.jac_csr()
     try:
         P.jac_values(u, J)
         first = np.array(J.values())
-        _check("fill with the seeded coefficient", first, ref.vals, ref.vals_bound)
-        _check("Jᵀv with the seeded coefficient", _np(P.vjp(v, u)), ref.jtv, ref.jtv_bound)
+        check("fill with the seeded coefficient", first, ref.vals, ref.vals_bound)
+        check("Jᵀv with the seeded coefficient", to_numpy(P.vjp(v, u)), ref.jtv, ref.jtv_bound)
         P.set_field(1, fields[1])
         P.jac_values(u, J)
         second = np.array(J.values())
-        _check("fill after set_field, same u buffer", second, new.vals, new.vals_bound)
-        _check("Jᵀv after set_field, same u buffer", _np(P.vjp(v, u)), new.jtv, new.jtv_bound)
-        _check("J·v after set_field", _np(P.jvp(v, u)), new.jv, new.jv_bound)
+        check("fill after set_field, same u buffer", second, new.vals, new.vals_bound)
+        check("Jᵀv after set_field, same u buffer", to_numpy(P.vjp(v, u)), new.jtv, new.jtv_bound)
+        check("J·v after set_field", to_numpy(P.jvp(v, u)), new.jv, new.jv_bound)
         assert float(np.max(np.abs(second - first))) > 1e6 * float(new.vals_bound.max())
     finally:
         P.set_field(1, ref.fields[1])
@@ -162,24 +103,23 @@ def test_a_changed_field_reaches_the_solver_cache_step(nls, dev):
     GMRES stops at ‖r‖₂ <= 1e-10·‖F‖₂, hence ‖F_new(u₁)‖∞ <= 1e-10·√n·‖F_new(u)‖∞ (n = 72: 8.5e-10) plus rounding; 1e-8 is
     asserted. A step with the Jacobian kept from the old field leaves (I − J_new J_old⁻¹)F_new(u): computed here in NumPy, it
     is more than a million times that."""
-    name, shape = "vardiff", (9, 8)
-    P, ref = _problem(nls, name, shape), R.reference(name, shape)
-    new, fields = _mixed_reference(name, shape, 1, ref, R.reference(name, shape, shift=1.0))
-    prob = R.PROBLEMS[name]
+    prob, shape = R.PROBLEMS["vardiff"], (9, 8)
+    P, ref = problem(nls, prob, shape), GC.reference(prob, shape)
+    new, fields = _mixed_reference(prob, shape, 1, ref, GC.reference(prob, shape, shift=1.0))
     alg = nls.NewtonRaphson(linsolve=nls.KrylovJL_GMRES(reltol=1e-10), concrete_jac=True)
     try:
-        cache = nls.init(nls.NonlinearProblem(P, _t(ref.u, dev)), alg, abstol=1e-13)
+        cache = nls.init(nls.NonlinearProblem(P, to_device(ref.u, dev)), alg, abstol=1e-13)
         nls.step_(cache)
-        f_old = R.evaluate(prob, shape, _np(cache.u), ref.v, ref.fields).f
+        f_old = GC.evaluate(prob, shape, to_numpy(cache.u), ref.v, ref.fields).f
         print(f"old field: |F(u)| {np.abs(ref.f).max():.3e} -> |F(u1)| {np.abs(f_old).max():.3e}")
         assert np.abs(f_old).max() <= 1e-8 * np.abs(ref.f).max()
         P.set_field(1, fields[1])
-        nls.reinit_(cache, u0=_t(ref.u, dev))
-        _check("fu after set_field and reinit_", _np(cache.fu), new.f, new.f_bound)
+        nls.reinit_(cache, u0=to_device(ref.u, dev))
+        check("fu after set_field and reinit_", to_numpy(cache.fu), new.f, new.f_bound)
         nls.step_(cache)
-        f_new = R.evaluate(prob, shape, _np(cache.u), ref.v, fields).f
-        J_old, _f = R.dense_jacobian(prob, shape, ref.u, ref.fields)
-        stale = R.evaluate(prob, shape, ref.u - np.linalg.solve(J_old, new.f), ref.v, fields).f
+        f_new = GC.evaluate(prob, shape, to_numpy(cache.u), ref.v, fields).f
+        J_old, _f = GC.dense_jacobian(prob, shape, ref.u, ref.fields)
+        stale = GC.evaluate(prob, shape, ref.u - np.linalg.solve(J_old, new.f), ref.v, fields).f
         print(f"new field: |F(u)| {np.abs(new.f).max():.3e} -> |F(u1)| {np.abs(f_new).max():.3e}; a stale Jacobian would leave "
               f"{np.abs(stale).max():.3e}")
         assert np.abs(stale).max() > 1e6 * 1e-8 * np.abs(new.f).max()
@@ -191,7 +131,7 @@ def test_a_changed_field_reaches_the_solver_cache_step(nls, dev):
 
 def test_bad_arguments_name_the_value(nls, dev):
     from nonlinearsolve_jl_amd import _lib as L
-    P = _problem(nls, "vardiff", (9, 8))
+    P = problem(nls, R.PROBLEMS["vardiff"], (9, 8))
     good = np.ones(72)
     with pytest.raises(nls.NKError, match="k = 3 outside 0..2"):
         P.set_field(3, good)
@@ -200,8 +140,8 @@ def test_bad_arguments_name_the_value(nls, dev):
     with pytest.raises(ValueError, match="expected 72 elements.*got 71"):
         P.set_field(0, np.ones(71))
     with pytest.raises(ValueError, match="expected 72 elements.*got 144"):
-        P.set_field(0, _t(np.ones(144), dev))
-    assert np.array_equal(_np(P.field(0)), R.seeded_fields(3, (9, 8))[0])     # nothing was stored by the refused calls
+        P.set_field(0, to_device(np.ones(144), dev))
+    assert np.array_equal(to_numpy(P.field(0)), GC.seeded_fields(3, (9, 8))[0])     # nothing was stored by the refused calls
     Q = nls.CompiledGridProblem(G1.BRATU_SRC, 9, 8, params=[1.0, 0.04])       # a compiled grid problem without fields
     assert Q.nfields == 0
     with pytest.raises(nls.NKError, match="nfields = 0"):
@@ -225,10 +165,10 @@ def test_declared_fields_that_are_not_read_change_nothing(nls, dev):
     """the bratu_f source compiled with four fields declared, three of them holding other data: the five quantities of the
     one-field problem, bit for bit (the same instructions on the same data)"""
     shape = (37, 29)
-    ref = R.reference("bratu_f", shape)
-    P1, P4 = _problem(nls, "bratu_f", shape), _problem(nls, "bratu_f4", shape)
-    assert np.array_equal(_np(P4.field(0)), _np(P1.field(0))) and not np.array_equal(_np(P4.field(1)), _np(P1.field(0)))
-    g1, g4 = _device_quantities(P1, ref.u, ref.v, dev), _device_quantities(P4, ref.u, ref.v, dev)
+    ref = GC.reference(R.PROBLEMS["bratu_f"], shape)
+    P1, P4 = problem(nls, R.PROBLEMS["bratu_f"], shape), problem(nls, R.PROBLEMS["bratu_f4"], shape)
+    assert np.array_equal(to_numpy(P4.field(0)), to_numpy(P1.field(0))) and not np.array_equal(to_numpy(P4.field(1)), to_numpy(P1.field(0)))
+    g1, g4 = device_quantities(P1, ref.u, ref.v, dev), device_quantities(P4, ref.u, ref.v, dev)
     for k in ("f", "jv", "vals", "jtv", "spmv"):
         print(f"bratu_f4 vs bratu_f {k}: max difference {np.abs(g4[k] - g1[k]).max():.3e}")
         assert np.array_equal(g4[k], g1[k])
@@ -253,7 +193,7 @@ def _dense_newton(prob, shape, u0, fields):
     """u_ref with ‖F(u_ref)‖∞ <= 1e-12 by a dense NumPy Newton on the restatement, ‖F(u_ref)‖∞ and ‖J(u_ref)⁻¹‖∞"""
     u = np.array(u0)
     for _it in range(30):
-        J, f = R.dense_jacobian(prob, shape, u, fields)
+        J, f = GC.dense_jacobian(prob, shape, u, fields)
         if np.abs(f).max() <= 1e-12:
             break
         u = u - np.linalg.solve(J, f)
@@ -267,31 +207,31 @@ def _time_steps(nls, dev, name, shape, algname, nsteps):
     the restatement WITH THE FIELDS THE DEVICE HOLDS (the previous level is the device's own, read back with field(0)): both
     residuals by the restatement, the factor 2 for the second-order term, as tests/test_gpu_grid3_problem.py has it."""
     prob, abstol = R.PROBLEMS[name], 1e-10
-    P = _problem(nls, name, shape)
-    fields = R.seeded_fields(prob.nfields, shape)
-    _set_fields(P, fields)
+    P = problem(nls, prob, shape)
+    fields = GC.seeded_fields(prob.nfields, shape)
+    set_fields(P, fields)
     u_init = 0.5 * fields[0]
-    cache = nls.init(nls.NonlinearProblem(P, _t(u_init, dev)), _algorithms(nls)[algname], abstol=abstol, maxiters=60)
+    cache = nls.init(nls.NonlinearProblem(P, to_device(u_init, dev)), _algorithms(nls)[algname], abstol=abstol, maxiters=60)
     moved = 0.0
     for step in range(nsteps):
         P.set_field(0, cache.u)
         nls.reinit_(cache, u0=cache.u)
         sol = nls.solve_(cache)
-        held = np.stack([_np(P.field(k)) for k in range(prob.nfields)])
+        held = np.stack([to_numpy(P.field(k)) for k in range(prob.nfields)])
         assert np.array_equal(held[1:], fields[1:])
-        u_dev = _np(cache.u)
+        u_dev = to_numpy(cache.u)
         u_ref, f_ref, jinv = _dense_newton(prob, shape, held[0], held)
-        f_dev = float(np.abs(R.evaluate(prob, shape, u_dev, u_dev, held).f).max())
+        f_dev = float(np.abs(GC.evaluate(prob, shape, u_dev, u_dev, held).f).max())
         err, bound = float(np.abs(u_dev - u_ref).max()), 2.0 * jinv * (f_dev + f_ref)
         moved = max(moved, float(np.abs(u_dev - held[0]).max()))
         print(f"{name} {algname} step {step}: {sol.retcode} {sol.stats}; |u_dev - u_ref| {err:.3e}, bound {bound:.3e} "
               f"(|J^-1| {jinv:.3e}, |F(u_dev)| {f_dev:.3e}, |F(u_ref)| {f_ref:.3e}); |u - u_old| {np.abs(u_dev - held[0]).max():.3e}")
         assert sol.retcode == "Success"
         assert err <= bound
-        assert f_dev <= abstol + float(R.Reference(prob, shape, u_dev, u_dev, held).f_bound.max())
+        assert f_dev <= abstol + float(GC.Reference(prob, shape, u_dev, u_dev, held).f_bound.max())
     assert moved > 1e-3   # (the levels differ: a step that kept the old level would show)
     cache.close()
-    _set_fields(P, fields)
+    set_fields(P, fields)
 
 
 @pytest.mark.parametrize("algname", ["newton_matfree", "newton_jacobi", "newton_ilu0", "trust_region"])
@@ -308,7 +248,4 @@ def test_one_implicit_euler_step_in_three_dimensions(nls, dev, algname):
 
 def test_close_module_problems(nls):
     """(last in the file) the problems the module shared are freed; a double close is harmless"""
-    for P in _PROBLEMS.values():
-        P.close()
-        P.close()
-    _PROBLEMS.clear()
+    close_problems()

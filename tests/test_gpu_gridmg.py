@@ -10,6 +10,7 @@ import pytest
 import scipy.sparse as sp
 
 import gridmg_reference as GM
+from grid_device import create
 
 pytestmark = pytest.mark.gpu
 
@@ -23,12 +24,6 @@ CASES = {
     "fourth": ((21, 21), 4),
 }
 _SETUPS = {}
-
-
-def _create(nls, prob, shape, params=None):
-    return nls.CompiledGridProblem(prob.source, shape[0], shape[1], dof=prob.dof, stencil=prob.stencil, boundary=prob.boundary,
-                                   params=prob.params if params is None else params, nz=shape[2] if prob.dim == 3 else None,
-                                   fields=prob.nfields)
 
 
 def _set_fields(P, prob, fields):
@@ -50,7 +45,7 @@ def _setup(nls, name):
     if name not in _SETUPS:
         shape, cm = CASES[name]
         ref = GM.reference(name, shape, cm)
-        P = _create(nls, ref.prob, shape)
+        P = create(nls, ref.prob, shape)
         if ref.prob.nfields:
             _set_fields(P, ref.prob, ref.fields)
         _SETUPS[name] = (P, _solver(nls, P, ref, cm), ref)
@@ -64,7 +59,7 @@ def _level_matrix(nls, G, prob, l, shape):
     return sp.csr_matrix((vals, ci.astype(np.int64), rp.astype(np.int64)), shape=(n, n))
 
 
-def _check_levels(nls, G, ref):
+def _assert_levels(nls, G, ref):
     lv = G.multigrid_levels()
     print("levels", [x["sides"] for x in lv], "reference", ref.M.shapes)
     assert [x["sides"] for x in lv] == ref.M.shapes
@@ -83,7 +78,7 @@ def _check_levels(nls, G, ref):
 @pytest.mark.parametrize("name", sorted(CASES))
 def test_level_shapes_and_matrices(nls, name):
     _P, G, ref = _setup(nls, name)
-    _check_levels(nls, G, ref)
+    _assert_levels(nls, G, ref)
 
 
 @pytest.mark.parametrize("name", sorted(CASES))
@@ -104,11 +99,11 @@ def test_one_vcycle_and_iteration_count(nls, name):
 def test_newton_with_multigrid_precs_reaches_the_direct_solution(nls):
     """case (a): NewtonRaphson + GMRES with MultigridPrecs(2, 5) against plain Newton with direct solves on the restatement, and
     every step's Krylov count against the restatement's count + 1. The direct Newton is GM.sparse_newton, the loop of
-    gridbc_reference.dense_newton with a sparse LU in place of the dense solve: dense_newton takes the problems of the
+    grid_core.dense_newton with a sparse LU in place of the dense solve: dense_newton takes the problems of the
     earlier tables, whose sources get their spacing from p, and 1056² dense matrices per step buy nothing."""
     prob, shape = GM.PROBLEMS["bratu"], CASES["bratu"][0]
     ref = GM.reference("bratu", shape, 5)
-    P = _create(nls, prob, shape)
+    P = create(nls, prob, shape)
     alg = nls.NewtonRaphson(linsolve=nls.KrylovJL_GMRES(gmres_restart=30, maxiters=300, reltol=1e-9, abstol=0.0,
                                                         precs=nls.MultigridPrecs(2, 5)))
     sol = nls.solve(nls.NonlinearProblem(P), alg, abstol=1e-8, maxiters=30, store_trace=True)
@@ -131,10 +126,10 @@ def test_update_after_set_field_and_set_p(nls):
     shape, cm = CASES[name]
     ref0, ref1 = GM.reference(name, shape, cm), GM.reference(name, shape, cm, variant=1)
     prob = ref0.prob
-    P = _create(nls, prob, shape)
+    P = create(nls, prob, shape)
     _set_fields(P, prob, ref0.fields)
     G = _solver(nls, P, ref0, cm)
-    _check_levels(nls, G, ref0)
+    _assert_levels(nls, G, ref0)
     _set_fields(P, prob, ref1.fields)
     P.set_p(ref1.p)
     G.set_multigrid_preconditioner(P, ref1.u, nu=2, coarse_max=cm)
@@ -145,7 +140,7 @@ def test_update_after_set_field_and_set_p(nls):
             err = np.max(np.abs(got - want))
             print(f"  level {l} field {k}: max err {err:.3e}")
             assert err <= 1e-13 * max(1.0, np.max(np.abs(want)))
-    _check_levels(nls, G, ref1)
+    _assert_levels(nls, G, ref1)
     x1, _ = G.solve(ref1.b, fixed_iters=1)
     e1 = np.linalg.norm(x1 - ref1.x1) / np.linalg.norm(ref1.x1)
     moved = np.linalg.norm(ref1.x1 - ref0.x1) / np.linalg.norm(ref0.x1)
@@ -164,7 +159,7 @@ def test_default_coarse_max_and_smoothing_steps(nls):
     """coarse_max left out and nu = 3 through the same entry point: the default coarse_max for grid problems is 8"""
     prob, shape = GM.PROBLEMS["mixed"], (33, 28)
     ref = GM.reference("mixed", shape, 8, nu=3)
-    P = _create(nls, prob, shape)
+    P = create(nls, prob, shape)
     G = _solver(nls, P, ref, None, nu=3)
     assert [x["sides"] for x in G.multigrid_levels()] == ref.M.shapes
     x1, _ = G.solve(ref.b, fixed_iters=1)
@@ -178,7 +173,7 @@ def test_hierarchy_follows_the_last_call(nls):
     back) is served by its own hierarchy, with the results of a solver object that never saw the other"""
     prob, shape = GM.PROBLEMS["mixed"], CASES["mixed"][0]
     ref4, ref5, ref3 = GM.reference("mixed", shape, 4), GM.reference("mixed", shape, 5), GM.reference("mixed", shape, 4, nu=3)
-    P = _create(nls, prob, shape)
+    P = create(nls, prob, shape)
     G = _solver(nls, P, ref4, 4)
     assert [x["sides"] for x in G.multigrid_levels()] == ref4.M.shapes
     G.set_multigrid_preconditioner(P, ref5.u, nu=2, coarse_max=5)
@@ -194,7 +189,7 @@ def test_hierarchy_follows_the_last_call(nls):
     assert e3 <= 1e-9
     # a Bratu2D problem of the same size on a solver object that holds a grid hierarchy, and back
     n = 16
-    Pg = _create(nls, GM.PROBLEMS["bratu"], (n, n))
+    Pg = create(nls, GM.PROBLEMS["bratu"], (n, n))
     B = nls.Bratu2D(n, 1.0)
     u, b = np.zeros(n * n), np.random.default_rng(5).standard_normal(n * n)
     opg = nls.StatefulJacobianOperator(nls.JacobianOperator(nls.NonlinearProblem(Pg)), u)

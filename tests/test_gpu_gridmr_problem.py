@@ -61,8 +61,8 @@ def _worker(rank, world, port, q, transport, plan):
 
     try:
         import nonlinearsolve_jl_amd as nls
-        import gridbc_reference as GB
-        import gridf_reference as GF
+        import grid_core as GC
+        import grid_device as D
         import gridmr_reference as R
         torch.cuda.set_device(0)
         ctx = nls.Context(device=0)
@@ -74,24 +74,15 @@ def _worker(rank, world, port, q, transport, plan):
         dev = torch.device("cuda:0")
 
         def t(x):
-            return torch.tensor(np.asarray(x, dtype=np.float64), dtype=torch.float64, device=dev)
+            return D.to_device(x, dev)
 
         def create(prob, shape, c, params=None):
-            return nls.CompiledGridProblem(prob.source, shape[0], shape[1], dof=prob.dof, stencil=prob.stencil,
-                                           boundary=prob.boundary, params=prob.params if params is None else params,
-                                           nz=shape[2] if prob.dim == 3 else None, fields=prob.nfields, ctx=c)
-
-        def quantities(P, u, v):
-            du, dv = t(u), t(v)
-            J = P.jac_csr()
-            P.jac_values(du, J)
-            return dict(f=P.residual(du).cpu().numpy(), jv=P.jvp(dv, du).cpu().numpy(), vals=np.array(J.values()),
-                        jtv=P.vjp(dv, du).cpu().numpy(), spmv=J.matvec(dv).cpu().numpy()), J
+            return D.create(nls, prob, shape, params, ctx=c)
 
         def parity(name, shape):
             prob = R.PROBLEMS[name]
             shape = tuple(shape or R.small_shape(prob, world))
-            ref, S = R.reference(name, shape), R.slab(name, shape, world, rank)
+            ref, S = GC.reference(prob, shape), R.slab(name, shape, world, rank)
             tag = f"{name} {'x'.join(map(str, shape))} rank {rank}/{world}"
             Pm, P1 = create(prob, shape, ctx), create(prob, shape, one)
             assert Pm.lines == S.lines and P1.lines == (0, shape[-1])
@@ -103,12 +94,12 @@ def _worker(rank, world, port, q, transport, plan):
                     mine = ref.fields[k][S.rows[:S.nn_loc]]
                     Pm.set_field(k, mine)
                     assert np.array_equal(Pm.field(k).cpu().numpy(), mine)           # round trip of the slab
-            got, J = quantities(Pm, S.local(ref.u), S.local(ref.v))
-            full, _J1 = quantities(P1, ref.u, ref.v)
-            info = J.info()
+            got = D.device_quantities(Pm, S.local(ref.u), S.local(ref.v), dev)
+            full = D.device_quantities(P1, ref.u, ref.v, dev)
+            info = Pm.jac_csr().info()
             assert info["nrows_local"] == S.n_local and info["nnz"] == S.colind.size and info["n_halo"] == S.n_halo, (tag, info)
             want = R.expected(name, shape, world, rank)
-            for k in ("f", "jv", "vals", "jtv", "spmv"):
+            for k in D.QUANTITIES:
                 exp, bound = want[k]
                 err = np.abs(got[k] - exp)
                 log.append(f"{tag} {k}: max err {err.max():.3e}, max bound {bound.max():.3e}, worst err - bound "
@@ -147,15 +138,16 @@ def _worker(rank, world, port, q, transport, plan):
         def bratu_solve():
             import grid_reference as G1
             shape, params = (24, 20), [1.0, 1e-3]
-            prob = GB.Problem("bratu_channel_mr", G1.PROBLEMS["bratu"], (GB.PE, GB.PE, GB.MF, GB.DI), "g1", 2)
-            solve_pair("bratu_channel", prob, shape, params, 0.5 * GB.inputs(prob, shape)[0])
+            prob = G1.PROBLEMS["bratu"].with_boundary("bratu_channel_mr", (R.PE, R.PE, R.MF, R.DI))
+            solve_pair("bratu_channel", prob, shape, params, 0.5 * GC.inputs(prob, shape)[0])
 
         if plan == "full2":
             for name, shape in CASES_2:
                 parity(name, shape)
             # ---------------- a field changed on one rank changes the neighbour's residual on its boundary line (and only there)
             name, shape = "vardiff_yper", (4, 5)
-            prob, ref, S = R.PROBLEMS[name], R.reference(name, shape), R.slab(name, shape, world, rank)
+            prob, S = R.PROBLEMS[name], R.slab(name, shape, world, rank)
+            ref = GC.reference(prob, shape)
             Pm = create(prob, shape, ctx)
             for k in range(prob.nfields):
                 Pm.set_field(k, ref.fields[k][S.rows[:S.nn_loc]])
@@ -174,18 +166,18 @@ def _worker(rank, world, port, q, transport, plan):
             bratu_solve()
             import grid_reference as G1
             shape = (16, 12)
-            prob = GB.Problem("brus_mr", G1.PROBLEMS["brusselator"], (GB.PE, GB.PE, GB.MF, GB.MF), "g1", 2)
+            prob = G1.PROBLEMS["brusselator"].with_boundary("brus_mr", (R.PE, R.PE, R.MF, R.MF))
             nn = shape[0] * shape[1]
-            start = np.concatenate([np.full(nn, 1.0), np.full(nn, 3.4)]) + 0.05 * GB.inputs(prob, shape)[0]
+            start = np.concatenate([np.full(nn, 1.0), np.full(nn, 3.4)]) + 0.05 * GC.inputs(prob, shape)[0]
             solve_pair("brusselator", prob, shape, None, start)
             # ---------------- conservation: zero-flux walls on all sides, a divergence-form source — the fluxes telescope
             # to zero over the whole grid, so the all-reduced sum of the residual is the reaction part's alone, here
             # Σ p0·(u − a0) − Σ a2; the bound is the rounding of the sums (gridbc's conservation test, split across the cut)
             name, shape = "vardiff_ymface", (24, 20)
             prob = R.PROBLEMS[name]
-            S = R.Slab(shape, prob.dof, prob.offsets(), prob.boundary, world, rank)
-            u = GB.inputs(prob, shape)[0]
-            fields = GF.seeded_fields(3, shape)
+            S = R.Slab(shape, prob.dof, prob.offsets(), prob.sides, world, rank)
+            u = GC.inputs(prob, shape)[0]
+            fields = GC.seeded_fields(3, shape)
             fields[0], fields[2] = u, 0.0 * u          # a0 = u and no source: F is the flux divergence alone
             Pm = create(prob, shape, ctx)
             for k in range(3):
@@ -199,7 +191,7 @@ def _worker(rank, world, port, q, transport, plan):
             # 8 eps × Σ|terms of the node| (the project's floor with the accumulation's depth for margin). Σ over the nodes of
             # Σ|terms| <= p1 · κ̄ · Σ_faces (|u| + |u_nb|) <= p1 · 1.5 · 8 · Σ|u| (4 faces, κ̄ <= 1.37)
             terms = 8.0 * prob.params[1] * 1.5 * float(np.abs(u).sum())
-            bound = 8 * GB.EPS * terms
+            bound = 8 * GC.EPS * terms
             log.append(f"conservation rank {rank}: |sum F| {abs(total):.3e}, bound {bound:.3e}, |F|_1 {mag:.3e}")
             assert mag > 1e6 * bound and abs(total) <= bound
             Pm.close()
@@ -218,11 +210,12 @@ def _worker(rank, world, port, q, transport, plan):
         elif plan == "one":
             # a one-rank context of the multi-rank-capable build: the slab is the grid
             name, shape = "brus_site_yper", (4, 5)
-            prob, ref = R.PROBLEMS[name], R.reference(name, shape)
+            prob = R.PROBLEMS[name]
+            ref = GC.reference(prob, shape)
             P1 = create(prob, shape, ctx)
             assert P1.lines == (0, 5) and P1.row_begin == 0 and P1.n_local == P1.n_global == ref.u.size
-            got, _J = quantities(P1, ref.u, ref.v)
-            for k in ("f", "jv", "vals", "jtv", "spmv"):
+            got = D.device_quantities(P1, ref.u, ref.v, dev)
+            for k in D.QUANTITIES:
                 assert np.all(np.abs(got[k] - getattr(ref, k)) <= getattr(ref, k + "_bound")), k
             assert np.array_equal(P1.to_full(P1.local_of(ref.u)), ref.u)
         q.put((rank, "ok", digest, log))

@@ -1,5 +1,5 @@
 """Compiled grid problems in three dimensions without a GPU: nk_grid3_pattern against the NumPy restatement
-(tests/grid3_reference.py), the restatement against itself (analytic Jacobians against differences of its own residual), the
+(tests/grid_core.py, tests/grid3_reference.py), the restatement against itself (analytic Jacobians against differences of its own residual), the
 sources through hiprtc for gfx950, the argument errors with their messages, and the generated kernels' resource notes (no
 private segment). The 2-D entry points are still what a call without `nz` reaches."""
 import ctypes as C
@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 import grid3_reference as R
+import grid_core as GC
 import grid_reference as R2
 from nonlinearsolve_jl_amd import _lib as L
 
@@ -30,14 +31,14 @@ def _lib_pattern(nx, ny, nz, dof, stencil, boundary):
 def test_pattern_equals_the_restatement(nx, ny, nz, stencil, dof, boundary):
     """(the box stops at dof 1: dof 2 with the box is an argument error, test_argument_errors_name_their_cause)"""
     rp, ci = _lib_pattern(nx, ny, nz, dof, stencil, boundary)
-    rp_ref, ci_ref = R.pattern(nx, ny, nz, dof, stencil, boundary)
+    rp_ref, ci_ref = GC.stencil_pattern((nx, ny, nz), dof, stencil, boundary)
     assert rp.dtype == np.int32 and ci.dtype == np.int32
     assert np.array_equal(rp, rp_ref) and np.array_equal(ci, ci_ref)
     # columns ascend strictly within every row
     inner = np.ones(ci.size, dtype=bool)
     inner[rp[:-1]] = False
     assert np.all(np.diff(ci.astype(np.int64))[inner[1:]] > 0)
-    npts = len(R.STENCILS[stencil])
+    npts = len(GC.STENCILS[(3, stencil)])
     if boundary == "periodic":
         assert np.all(np.diff(rp) == npts * dof)
     else:   # every shape has an interior node and a corner node
@@ -47,7 +48,7 @@ def test_pattern_equals_the_restatement(nx, ny, nz, stencil, dof, boundary):
 @pytest.mark.parametrize("stencil,dof", [("star", 1), ("star", 4), ("box", 1)])
 def test_periodic_3x3x3_rows_have_distinct_columns(stencil, dof):
     rp, ci = _lib_pattern(3, 3, 3, dof, stencil, "periodic")
-    npts = len(R.STENCILS[stencil])
+    npts = len(GC.STENCILS[(3, stencil)])
     for r in range(rp.size - 1):
         row = ci[rp[r]:rp[r + 1]]
         assert row.size == npts * dof == np.unique(row).size
@@ -58,7 +59,7 @@ def test_periodic_3x3x3_rows_have_distinct_columns(stencil, dof):
 def test_pattern_sizes_only():
     nnz = C.c_int64()
     assert L.lib().nk_grid3_pattern(7, 6, 5, 1, 1, 0, None, None, C.byref(nnz)) == 0
-    assert nnz.value == R.pattern(7, 6, 5, 1, "box", "dirichlet")[1].size
+    assert nnz.value == GC.stencil_pattern((7, 6, 5), 1, "box", "dirichlet")[1].size
     rp = np.zeros(2 * 7 * 6 * 5 + 1, dtype=np.int32)
     assert L.lib().nk_grid3_pattern(7, 6, 5, 2, 0, 1, C.c_void_p(rp.ctypes.data), None, C.byref(nnz)) == 0
     assert rp[-1] == nnz.value == 2 * 7 * 6 * 5 * 14
@@ -69,7 +70,7 @@ def test_two_dimensional_calls_are_unchanged():
     """without nz the 2-D entry points answer: the 5-point pattern of a 5 × 4 grid, and the 2-D contract in the messages"""
     import nonlinearsolve_jl_amd as nls
     rp, ci = nls.grid_pattern(5, 4)
-    rp2, ci2 = R2.pattern(5, 4)
+    rp2, ci2 = GC.stencil_pattern((5, 4))
     assert np.array_equal(rp, rp2) and np.array_equal(ci, ci2) and rp.size == 21
     assert nls.grid_compile_check(R2.BRATU_SRC, nparams=2) == nls.grid_compile_check(R2.BRATU_SRC, nparams=2, dim=2) > 2000
     with pytest.raises(nls.NKError, match="nk_nbhd<T>"):          # a 3-D source is no 2-D source
@@ -87,33 +88,33 @@ def test_two_dimensional_calls_are_unchanged():
 def test_restatement_jacobians_against_its_own_residual(name):
     """the analytic formulas the device is held against: J·v and the CSR values against central differences of the
     restatement's residual in long double, Jᵀv against the values"""
-    prob, (nx, ny, nz) = R.PROBLEMS[name], (5, 4, 3)
-    ref = R.reference(name, nx, ny, nz)
-    h = R.LD(2.0) ** -20
-    up = R.evaluate(prob, nx, ny, nz, ref.u.astype(R.LD) + h * ref.v.astype(R.LD), ref.v, R.LD).f
-    um = R.evaluate(prob, nx, ny, nz, ref.u.astype(R.LD) - h * ref.v.astype(R.LD), ref.v, R.LD).f
+    prob, shape = R.PROBLEMS[name], (5, 4, 3)
+    ref = GC.reference(prob, shape)
+    h = GC.LD(2.0) ** -20
+    up = GC.evaluate(prob, shape, ref.u.astype(GC.LD) + h * ref.v.astype(GC.LD), ref.v, T=GC.LD).f
+    um = GC.evaluate(prob, shape, ref.u.astype(GC.LD) - h * ref.v.astype(GC.LD), ref.v, T=GC.LD).f
     fd = ((up - um) / (2 * h)).astype(np.float64)
     assert np.max(np.abs(fd - ref.jv)) < 1e-8 * max(1.0, np.max(np.abs(ref.jv)))   # O(h²) truncation
     assert np.all(np.abs(ref.spmv - ref.jv) <= ref.spmv_bound + ref.jv_bound)
-    rp, ci = R.pattern(nx, ny, nz, prob.dof, prob.stencil, prob.boundary)
+    rp, ci = GC.pattern(shape, prob.dof, prob.offsets(), prob.sides)
     dense = np.zeros((rp.size - 1, rp.size - 1))
     dense[np.repeat(np.arange(rp.size - 1), np.diff(rp)), ci] = ref.vals
     assert np.allclose(dense.T @ ref.v, ref.jtv, rtol=0, atol=1e-12 * np.abs(ref.vals).max())
-    assert np.array_equal(dense, R.dense_jacobian(prob, nx, ny, nz, ref.u)[0])
+    assert np.array_equal(dense, GC.dense_jacobian(prob, shape, ref.u)[0])
     for k in ("f", "jv", "vals"):
         assert np.all(getattr(ref, k + "_gap") <= getattr(ref, k + "_bound"))
 
 
 def test_brusselator3_tells_directions_and_signs_apart():
     """what the upwinded weights are for: swapping +k with −k, or j with k, changes the restatement's residual far beyond its bound"""
-    nx = ny = nz = 4
+    shape = (4, 4, 4)
     prob = R.PROBLEMS["brusselator3"]
-    ref = R.reference("brusselator3", nx, ny, nz)
+    ref = GC.reference(prob, shape)
     p = list(prob.params)
     for a, b in ((6, 7), (4, 6), (2, 3)):
         q = list(p)
         q[a], q[b] = p[b], p[a]
-        f = R.evaluate(prob, nx, ny, nz, ref.u, ref.v, params=q).f
+        f = GC.evaluate(prob, shape, ref.u, ref.v, params=q).f
         assert np.max(np.abs(f - ref.f)) > 1e10 * ref.f_bound.max()
 
 
@@ -182,7 +183,7 @@ def test_argument_errors_name_their_cause():
 
 def _code_object(p, jac):
     nb = C.c_int64()
-    args = (p.source.encode(), p.dof, R.STENCIL_ID[p.stencil], R.BOUNDARY_ID[p.boundary], len(p.params), jac)
+    args = (p.source.encode(), p.dof, GC.STENCIL_ID[p.stencil], GC.BOUNDARY_ID[p.boundary], len(p.params), jac)
     assert L.lib().nk_grid3_code_object(*args, None, 0, C.byref(nb)) == 0, L.lib().nk_last_error()
     buf = C.create_string_buffer(nb.value)
     assert L.lib().nk_grid3_code_object(*args, buf, nb.value, C.byref(nb)) == 0

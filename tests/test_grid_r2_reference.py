@@ -1,5 +1,5 @@
 """Compiled grid problems with a radius-2 stencil without a GPU: nk_grid_pattern / nk_grid3_pattern against the NumPy
-restatement (tests/grid_r2_reference.py), the restatement against itself (analytic Jacobians against differences of its own
+restatement (tests/grid_core.py, tests/grid_r2_reference.py), the restatement against itself (analytic Jacobians against differences of its own
 residual), the sources through hiprtc for gfx950, the argument errors with their messages, the stencil codes of the header,
 Python and Julia, and the generated kernels' resource notes (no private segment, no spilled register)."""
 import ctypes as C
@@ -10,8 +10,8 @@ import subprocess
 import numpy as np
 import pytest
 
+import grid_core as GC
 import grid_r2_reference as R
-import grid_reference as R1
 from nonlinearsolve_jl_amd import _lib as L
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -58,11 +58,11 @@ def _lib_pattern(shape, dof, stencil, boundary):
 @pytest.mark.parametrize("boundary", ["dirichlet", "periodic"])
 @pytest.mark.parametrize("dim,stencil,dof", R.PERMITTED)
 def test_pattern_equals_the_restatement(dim, stencil, dof, boundary):
-    npts = len(R.STENCILS[(dim, stencil)])
+    npts = len(GC.STENCILS[(dim, stencil)])
     assert npts == {(2, "star2"): 9, (2, "diamond2"): 13, (3, "star2"): 13}[(dim, stencil)]
     for shape in SHAPES[dim]:
         rp, ci = _lib_pattern(shape, dof, stencil, boundary)
-        rp_ref, ci_ref = R.pattern(shape, dof, stencil, boundary)
+        rp_ref, ci_ref = GC.stencil_pattern(shape, dof, stencil, boundary)
         assert rp.dtype == np.int32 and ci.dtype == np.int32
         assert np.array_equal(rp, rp_ref) and np.array_equal(ci, ci_ref), shape
         # columns ascend strictly within every row
@@ -81,7 +81,7 @@ def test_pattern_equals_the_restatement(dim, stencil, dof, boundary):
 @pytest.mark.parametrize("dim,stencil,dof", R.PERMITTED)
 def test_periodic_rows_of_the_smallest_torus_have_distinct_columns(dim, stencil, dof):
     rp, ci = _lib_pattern((5,) * dim, dof, stencil, "periodic")
-    npts = len(R.STENCILS[(dim, stencil)])
+    npts = len(GC.STENCILS[(dim, stencil)])
     for r in range(rp.size - 1):
         row = ci[rp[r]:rp[r + 1]]
         assert row.size == npts * dof == np.unique(row).size
@@ -93,18 +93,18 @@ def test_restatement_jacobians_against_its_own_residual(name):
     restatement's residual in long double, Jᵀv against the values"""
     prob = R.PROBLEMS[name]
     shape = (6, 5) if prob.dim == 2 else (6, 5, 5)
-    ref = R.reference(name, shape)
-    h = R.LD(2.0) ** -20
-    up = R.evaluate(prob, shape, ref.u.astype(R.LD) + h * ref.v.astype(R.LD), ref.v, R.LD).f
-    um = R.evaluate(prob, shape, ref.u.astype(R.LD) - h * ref.v.astype(R.LD), ref.v, R.LD).f
+    ref = GC.reference(prob, shape)
+    h = GC.LD(2.0) ** -20
+    up = GC.evaluate(prob, shape, ref.u.astype(GC.LD) + h * ref.v.astype(GC.LD), ref.v, T=GC.LD).f
+    um = GC.evaluate(prob, shape, ref.u.astype(GC.LD) - h * ref.v.astype(GC.LD), ref.v, T=GC.LD).f
     fd = ((up - um) / (2 * h)).astype(np.float64)
     assert np.max(np.abs(fd - ref.jv)) < 1e-8 * max(1.0, np.max(np.abs(ref.jv)))   # O(h²) truncation
     assert np.all(np.abs(ref.spmv - ref.jv) <= ref.spmv_bound + ref.jv_bound)
-    rp, ci = R.pattern(shape, prob.dof, prob.stencil, prob.boundary)
+    rp, ci = GC.pattern(shape, prob.dof, prob.offsets(), prob.sides)
     dense = np.zeros((rp.size - 1, rp.size - 1))
     dense[np.repeat(np.arange(rp.size - 1), np.diff(rp)), ci] = ref.vals
     assert np.allclose(dense.T @ ref.v, ref.jtv, rtol=0, atol=1e-12 * np.abs(ref.vals).max())
-    assert np.array_equal(dense, R.dense_jacobian(prob, shape, ref.u)[0])
+    assert np.array_equal(dense, GC.dense_jacobian(prob, shape, ref.u)[0])
     for k in ("f", "jv", "vals"):
         assert np.all(getattr(ref, k + "_gap") <= getattr(ref, k + "_bound"))
 
@@ -116,14 +116,14 @@ def test_upwind_tells_directions_signs_and_distances_apart(name):
     prob = R.PROBLEMS[name]
     shape = (6, 5) if prob.dim == 2 else (6, 5, 5)
     m = 8 if prob.dim == 2 else 12
-    ref = R.reference(name, shape)
+    ref = GC.reference(prob, shape)
     p = list(prob.params)
     swaps = [(2, 3), (0, 2), (0, 4), (1, 3), (6, 7)] + ([(4, 8), (10, 11)] if prob.dim == 3 else [])
     for c in (0, 1):
         for a, b in swaps:
             q = list(p)
             q[c * m + a], q[c * m + b] = p[c * m + b], p[c * m + a]
-            f = R.evaluate(prob, shape, ref.u, ref.v, params=q).f
+            f = GC.evaluate(prob, shape, ref.u, ref.v, params=q).f
             assert np.max(np.abs(f - ref.f)) > 1e10 * ref.f_bound.max(), (c, a, b)
 
 
@@ -208,13 +208,13 @@ def test_argument_errors_name_their_cause():
 
 
 def test_stencil_codes_agree():
-    """the header's enum, _lib.GRID_STENCILS and Julia's GRID_STENCILS"""
+    """the header's enum, _lib.GRID_STENCILS, the restatement's STENCIL_ID and Julia's GRID_STENCILS"""
     header = open(os.path.join(ROOT, "include", "mi355x_nk.h"), encoding="utf-8").read()
     enum = re.search(r"enum \{([^}]*NK_GRID_STAR2[^}]*)\}", header).group(1)
     codes = {m.group(1).lower(): int(m.group(2)) for m in re.finditer(r"NK_GRID_(\w+)\s*=\s*(\d+)", enum)}
     assert codes == {"star": 0, "box": 1, "star2": 16, "diamond2": 17}
     assert L.GRID_STENCILS == codes
-    assert {k: codes[k] for k in R.STENCIL_ID} == R.STENCIL_ID and R1.STENCIL_ID == {"star": 0, "box": 1}
+    assert GC.STENCIL_ID == codes
     jl = open(os.path.join(ROOT, "julia", "src", "MI355XNewtonKrylov.jl"), encoding="utf-8").read()
     line = re.search(r"const GRID_STENCILS = Dict\(([^)]*)\)", jl).group(1)
     assert {m.group(1): int(m.group(2)) for m in re.finditer(r":(\w+)\s*=>\s*(\d+)", line)} == codes
@@ -225,7 +225,7 @@ def test_stencil_codes_agree():
 def _code_object(p, jac):
     fn = L.lib().nk_grid3_code_object if p.dim == 3 else L.lib().nk_grid_code_object
     nb = C.c_int64()
-    args = (p.source.encode(), p.dof, R.STENCIL_ID[p.stencil], R.BOUNDARY_ID[p.boundary], len(p.params), jac)
+    args = (p.source.encode(), p.dof, GC.STENCIL_ID[p.stencil], GC.BOUNDARY_ID[p.boundary], len(p.params), jac)
     assert fn(*args, None, 0, C.byref(nb)) == 0, L.lib().nk_last_error()
     buf = C.create_string_buffer(nb.value)
     assert fn(*args, buf, nb.value, C.byref(nb)) == 0
@@ -243,7 +243,7 @@ def test_generated_kernels_have_no_private_segment(tmp_path, monkeypatch, name, 
         pytest.skip("llvm-readelf not installed")
     monkeypatch.setenv("NK_GRID_FILL_DIRECT", str(direct))
     p = R.PROBLEMS[name]
-    npts = len(R.STENCILS[(p.dim, p.stencil)])
+    npts = len(p.offsets())
     for jac, kernels in KERNELS[p.dim].items():
         co = _code_object(p, jac)
         assert co[:4] == b"\x7fELF"

@@ -1,4 +1,4 @@
-"""Compiled grid problems without a GPU: nk_grid_pattern against the NumPy restatement (tests/grid_reference.py), the restatement
+"""Compiled grid problems without a GPU: nk_grid_pattern against the NumPy restatement (tests/grid_core.py, tests/grid_reference.py), the restatement
 against itself (analytic Jacobians against differences of its own residual), the three sources through hiprtc for gfx950, the
 argument errors with their messages, and the generated kernels' resource notes (no private segment)."""
 import ctypes as C
@@ -9,6 +9,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import grid_core as GC
 import grid_reference as R
 from nonlinearsolve_jl_amd import _lib as L
 
@@ -28,14 +29,14 @@ def _lib_pattern(nx, ny, dof, stencil, boundary):
 def test_pattern_equals_the_restatement(nx, ny, stencil, dof, boundary):
     """(the box stops at dof 2: dof 4 with the box is an argument error, test_argument_errors_name_their_cause)"""
     rp, ci = _lib_pattern(nx, ny, dof, stencil, boundary)
-    rp_ref, ci_ref = R.pattern(nx, ny, dof, stencil, boundary)
+    rp_ref, ci_ref = GC.stencil_pattern((nx, ny), dof, stencil, boundary)
     assert rp.dtype == np.int32 and ci.dtype == np.int32
     assert np.array_equal(rp, rp_ref) and np.array_equal(ci, ci_ref)
     # columns ascend strictly within every row
     inner = np.ones(ci.size, dtype=bool)
     inner[rp[:-1]] = False
     assert np.all(np.diff(ci.astype(np.int64))[inner[1:]] > 0)
-    npts = len(R.STENCILS[stencil])
+    npts = len(GC.STENCILS[(2, stencil)])
     if boundary == "periodic":
         assert np.all(np.diff(rp) == npts * dof)
     else:
@@ -46,7 +47,7 @@ def test_pattern_equals_the_restatement(nx, ny, stencil, dof, boundary):
 @pytest.mark.parametrize("stencil,dof", [("star", 1), ("star", 4), ("box", 2)])
 def test_periodic_3x3_rows_have_distinct_columns(stencil, dof):
     rp, ci = _lib_pattern(3, 3, dof, stencil, "periodic")
-    npts = len(R.STENCILS[stencil])
+    npts = len(GC.STENCILS[(2, stencil)])
     for r in range(rp.size - 1):
         row = ci[rp[r]:rp[r + 1]]
         assert row.size == npts * dof == np.unique(row).size
@@ -64,7 +65,7 @@ def test_bratu_pattern_is_the_built_in_order(ns):
 def test_pattern_sizes_only():
     nnz = C.c_int64()
     assert L.lib().nk_grid_pattern(37, 29, 2, 1, 0, None, None, C.byref(nnz)) == 0
-    assert nnz.value == R.pattern(37, 29, 2, "box", "dirichlet")[1].size
+    assert nnz.value == GC.stencil_pattern((37, 29), 2, "box", "dirichlet")[1].size
     rp = np.zeros(2 * 37 * 29 + 1, dtype=np.int32)
     assert L.lib().nk_grid_pattern(37, 29, 2, 1, 0, C.c_void_p(rp.ctypes.data), None, C.byref(nnz)) == 0
     assert rp[-1] == nnz.value
@@ -74,15 +75,15 @@ def test_pattern_sizes_only():
 def test_restatement_jacobians_against_its_own_residual(name):
     """the analytic formulas the device is held against: J·v and the CSR values against central differences of the
     restatement's residual in long double, Jᵀv against the values"""
-    prob, (nx, ny) = R.PROBLEMS[name], (7, 5)
-    ref = R.reference(name, nx, ny)
-    h = R.LD(2.0) ** -20
-    up = R.evaluate(prob, nx, ny, ref.u.astype(R.LD) + h * ref.v.astype(R.LD), ref.v, R.LD).f
-    um = R.evaluate(prob, nx, ny, ref.u.astype(R.LD) - h * ref.v.astype(R.LD), ref.v, R.LD).f
+    prob, shape = R.PROBLEMS[name], (7, 5)
+    ref = GC.reference(prob, shape)
+    h = GC.LD(2.0) ** -20
+    up = GC.evaluate(prob, shape, ref.u.astype(GC.LD) + h * ref.v.astype(GC.LD), ref.v, T=GC.LD).f
+    um = GC.evaluate(prob, shape, ref.u.astype(GC.LD) - h * ref.v.astype(GC.LD), ref.v, T=GC.LD).f
     fd = ((up - um) / (2 * h)).astype(np.float64)
     assert np.max(np.abs(fd - ref.jv)) < 1e-8 * max(1.0, np.max(np.abs(ref.jv)))   # O(h²) truncation
     assert np.all(np.abs(ref.spmv - ref.jv) <= ref.spmv_bound + ref.jv_bound)
-    rp, ci = R.pattern(nx, ny, prob.dof, prob.stencil, prob.boundary)
+    rp, ci = GC.pattern(shape, prob.dof, prob.offsets(), prob.sides)
     dense = np.zeros((rp.size - 1, rp.size - 1))
     dense[np.repeat(np.arange(rp.size - 1), np.diff(rp)), ci] = ref.vals
     assert np.allclose(dense.T @ ref.v, ref.jtv, rtol=0, atol=1e-12 * np.abs(ref.vals).max())
@@ -141,7 +142,7 @@ def test_argument_errors_name_their_cause():
 
 def _code_object(p, jac):
     nb = C.c_int64()
-    args = (p.source.encode(), p.dof, R.STENCIL_ID[p.stencil], R.BOUNDARY_ID[p.boundary], len(p.params), jac)
+    args = (p.source.encode(), p.dof, GC.STENCIL_ID[p.stencil], GC.BOUNDARY_ID[p.boundary], len(p.params), jac)
     assert L.lib().nk_grid_code_object(*args, None, 0, C.byref(nb)) == 0, L.lib().nk_last_error()
     buf = C.create_string_buffer(nb.value)
     assert L.lib().nk_grid_code_object(*args, buf, nb.value, C.byref(nb)) == 0

@@ -1,4 +1,4 @@
-"""Compiled grid problems with a boundary kind per side, without a GPU: the restatement tests/gridbc_reference.py against itself
+"""Compiled grid problems with a boundary kind per side, without a GPU: the restatement (tests/grid_core.py, tests/gridbc_reference.py) against itself
 (analytic merged Jacobians against differences of its own long-double residual; its index maps against examples written out by
 hand), nk_grid_pattern / nk_grid3_pattern against its pattern for every case, every source through the compile-check entry
 points for gfx950, the canonical form of the boundary code (a packed all-periodic or all-Dirichlet code gives the code objects
@@ -13,6 +13,7 @@ import numpy as np
 import pytest
 
 import grid3_reference as G3
+import grid_core as GC
 import grid_reference as G1
 import gridbc_reference as R
 import gridf_reference as GF
@@ -29,15 +30,15 @@ _IDS = [f"{n}-{'x'.join(map(str, s))}" for n, s in _CASES]
 # ------------------------------------------------------------------------------------------------ the restatement against itself
 def test_index_maps_are_numpy_pads():
     """positions −2 … n+1 of an axis of 5 nodes, written out"""
-    assert list(R.axis_map(5, DI, DI)) == [-1, -1, 0, 1, 2, 3, 4, -1, -1]
-    assert list(R.axis_map(5, PE, PE)) == [3, 4, 0, 1, 2, 3, 4, 0, 1]
-    assert list(R.axis_map(5, MN, MN)) == [2, 1, 0, 1, 2, 3, 4, 3, 2]
-    assert list(R.axis_map(5, MF, MF)) == [1, 0, 0, 1, 2, 3, 4, 4, 3]
-    assert list(R.axis_map(5, MN, DI)) == [2, 1, 0, 1, 2, 3, 4, -1, -1]
-    assert list(R.axis_map(3, MF, MN)) == [1, 0, 0, 1, 2, 1, 0]
+    assert list(GC.axis_map(5, DI, DI)) == [-1, -1, 0, 1, 2, 3, 4, -1, -1]
+    assert list(GC.axis_map(5, PE, PE)) == [3, 4, 0, 1, 2, 3, 4, 0, 1]
+    assert list(GC.axis_map(5, MN, MN)) == [2, 1, 0, 1, 2, 3, 4, 3, 2]
+    assert list(GC.axis_map(5, MF, MF)) == [1, 0, 0, 1, 2, 3, 4, 4, 3]
+    assert list(GC.axis_map(5, MN, DI)) == [2, 1, 0, 1, 2, 3, 4, -1, -1]
+    assert list(GC.axis_map(3, MF, MN)) == [1, 0, 0, 1, 2, 1, 0]
     # u and a field next to each other: x mirror-node, y Dirichlet — the Dirichlet side wins at the corner
     F = np.array([[10.0 * j + i for i in range(3)] for j in range(3)])[None]
-    U, A = R.Grid(F, (MN, MN, DI, DI)), R.Fields(F, (MN, MN, DI, DI))
+    U, A = GC.Grid(F, (MN, MN, DI, DI)), GC.Fields(F, (MN, MN, DI, DI))
     assert np.array_equal(U(-1, 0), [[1, 0, 1], [11, 10, 11], [21, 20, 21]])
     assert np.array_equal(U(-1, -1), [[0, 0, 0], [1, 0, 1], [11, 10, 11]])
     assert np.array_equal(A(-1, -1), [[0, 1, 2], [1, 0, 1], [11, 10, 11]])      # outside: the field at the node itself
@@ -51,14 +52,14 @@ def test_restatement_jacobians_against_its_own_residual(name):
     (7 × 6 × 5)"""
     prob = R.PROBLEMS[name]
     for shape in (R.sizes(prob)[0], (7, 6, 5) if prob.dim == 3 else (6, 5)):
-        ref = R.reference(name, shape)
-        h = R.LD(2.0) ** -20
-        up = R.evaluate(prob, shape, ref.u.astype(R.LD) + h * ref.v.astype(R.LD), ref.v, ref.fields, R.LD).f
-        um = R.evaluate(prob, shape, ref.u.astype(R.LD) - h * ref.v.astype(R.LD), ref.v, ref.fields, R.LD).f
+        ref = GC.reference(prob, shape)
+        h = GC.LD(2.0) ** -20
+        up = GC.evaluate(prob, shape, ref.u.astype(GC.LD) + h * ref.v.astype(GC.LD), ref.v, ref.fields, T=GC.LD).f
+        um = GC.evaluate(prob, shape, ref.u.astype(GC.LD) - h * ref.v.astype(GC.LD), ref.v, ref.fields, T=GC.LD).f
         fd = ((up - um) / (2 * h)).astype(np.float64)
         assert np.max(np.abs(fd - ref.jv)) < 1e-8 * max(1.0, np.max(np.abs(ref.jv)))   # O(h²) truncation
         assert np.all(np.abs(ref.spmv - ref.jv) <= ref.spmv_bound + ref.jv_bound)
-        rp, ci = R.pattern(shape, prob.dof, prob.offsets(), prob.boundary)
+        rp, ci = GC.pattern(shape, prob.dof, prob.offsets(), prob.sides)
         dense = np.zeros((rp.size - 1, rp.size - 1))
         dense[np.repeat(np.arange(rp.size - 1), np.diff(rp)), ci] = ref.vals
         assert np.allclose(dense.T @ ref.v, ref.jtv, rtol=0, atol=1e-12 * np.abs(ref.vals).max())
@@ -69,7 +70,7 @@ def test_restatement_jacobians_against_its_own_residual(name):
 # ------------------------------------------------------------------------------------------------ the library's pattern
 def _lib_pattern(prob, shape):
     lib, nnz = L.lib(), C.c_int64()
-    code, st = R.sides_code(prob.boundary), R.STENCIL_ID[prob.stencil]
+    code, st = GC.sides_code(prob.boundary), GC.STENCIL_ID[prob.stencil]
     if prob.dim == 3:
         def call(rp, ci):
             return lib.nk_grid3_pattern(*shape, prob.dof, st, code, rp, ci, C.byref(nnz))
@@ -87,7 +88,7 @@ def test_library_pattern_is_the_restatements(name, shape):
     import nonlinearsolve_jl_amd as nls
     prob = R.PROBLEMS[name]
     rp, ci = _lib_pattern(prob, shape)
-    ref_rp, ref_ci = R.pattern(shape, prob.dof, prob.offsets(), prob.boundary)
+    ref_rp, ref_ci = GC.pattern(shape, prob.dof, prob.offsets(), prob.sides)
     assert np.array_equal(rp, ref_rp) and np.array_equal(ci, ref_ci)
     for r in (0, rp.size // 2, rp.size - 2):                                   # ascending, every column once
         assert np.all(np.diff(ci[rp[r]:rp[r + 1]]) > 0)
@@ -122,7 +123,7 @@ def test_patterns_written_out_by_hand():
 
 # ------------------------------------------------------------------------------------------------ compilation
 def _args(p, code=None):
-    return (p.source.encode(), p.dim, p.dof, R.STENCIL_ID[p.stencil], R.sides_code(p.boundary) if code is None else code,
+    return (p.source.encode(), p.dim, p.dof, GC.STENCIL_ID[p.stencil], GC.sides_code(p.boundary) if code is None else code,
             len(p.params), p.nfields)
 
 
@@ -157,25 +158,25 @@ def test_a_packed_uniform_code_is_the_plain_code(jac):
     lib = L.lib()
     for kind, plain in ((PE, 1), (DI, 0)):
         p = G1.PROBLEMS["box_periodic"]
-        a = (p.source.encode(), p.dof, G1.STENCIL_ID[p.stencil])
-        packed = R.sides_code(R.uniform(kind, 2))
+        a = (p.source.encode(), p.dof, GC.STENCIL_ID[p.stencil])
+        packed = GC.sides_code(GC.uniform(kind, 2))
         assert packed not in (0, 1)
         old = _code_object(lib.nk_grid_code_object, *a, plain, len(p.params), jac)
         assert old[:4] == b"\x7fELF"
         assert _code_object(lib.nk_grid_code_object, *a, packed, len(p.params), jac) == old
         assert _code_object(lib.nk_grid_fields_code_object, a[0], 2, *a[1:], packed, len(p.params), 0, jac) == old
         p3 = G3.PROBLEMS["brusselator3"]
-        a3 = (p3.source.encode(), p3.dof, G1.STENCIL_ID[p3.stencil])
+        a3 = (p3.source.encode(), p3.dof, GC.STENCIL_ID[p3.stencil])
         old3 = _code_object(lib.nk_grid3_code_object, *a3, plain, len(p3.params), jac)
-        assert _code_object(lib.nk_grid3_code_object, *a3, R.sides_code(R.uniform(kind, 3)), len(p3.params), jac) == old3
+        assert _code_object(lib.nk_grid3_code_object, *a3, GC.sides_code(GC.uniform(kind, 3)), len(p3.params), jac) == old3
         pf = GF.PROBLEMS["react2"]
-        af = (pf.source.encode(), 2, pf.dof, GF.STENCIL_ID[pf.stencil])
+        af = (pf.source.encode(), 2, pf.dof, GC.STENCIL_ID[pf.stencil])
         assert (_code_object(lib.nk_grid_fields_code_object, *af, packed, len(pf.params), pf.nfields, jac) ==
                 _code_object(lib.nk_grid_fields_code_object, *af, plain, len(pf.params), pf.nfields, jac))
     # and a mirror program is another program
     p = G1.PROBLEMS["bratu"]
     a = (p.source.encode(), p.dof, 0)
-    assert (_code_object(lib.nk_grid_code_object, *a, R.sides_code(R.uniform(MN, 2)), 2, jac) !=
+    assert (_code_object(lib.nk_grid_code_object, *a, GC.sides_code(GC.uniform(MN, 2)), 2, jac) !=
             _code_object(lib.nk_grid_code_object, *a, 0, 2, jac))
     import nonlinearsolve_jl_amd as nls
     for kind, plain in ((PE, "periodic"), (DI, "dirichlet")):
@@ -193,24 +194,24 @@ def test_argument_errors_name_their_cause():
     lib, nb = L.lib(), C.c_int64()
     src = G1.BRATU_SRC.encode()
     # one side of an axis periodic
-    st, msg = _status(lib.nk_grid_compile_check, src, 1, 0, R.sides_code((PE, MN, DI, DI)), 2, C.byref(nb))
+    st, msg = _status(lib.nk_grid_compile_check, src, 1, 0, GC.sides_code((PE, MN, DI, DI)), 2, C.byref(nb))
     assert st == -1 and "x axis" in msg and "x-lo is NK_GRID_PERIODIC" in msg and "x-hi is NK_GRID_MIRROR_NODE" in msg
-    st, msg = _status(lib.nk_grid3_pattern, 5, 5, 5, 1, 0, R.sides_code((DI, DI, MF, MF, DI, PE)), None, None, C.byref(nb))
+    st, msg = _status(lib.nk_grid3_pattern, 5, 5, 5, 1, 0, GC.sides_code((DI, DI, MF, MF, DI, PE)), None, None, C.byref(nb))
     assert st == -1 and "z axis" in msg and "z-hi is NK_GRID_PERIODIC" in msg
     # an unknown kind
-    st, msg = _status(lib.nk_grid_pattern, 5, 5, 1, 0, R.sides_code((0, 0, 0, 7)), None, None, C.byref(nb))
+    st, msg = _status(lib.nk_grid_pattern, 5, 5, 1, 0, GC.sides_code((0, 0, 0, 7)), None, None, C.byref(nb))
     assert st == -1 and "y-hi = 7" in msg and "unknown kind" in msg
     st, msg = _status(lib.nk_grid_code_object, src, 1, 0, 2, 2, 0, None, 0, C.byref(nb))   # a bare kind is no code
     assert st == -1 and "boundary = 2" in msg and "NK_GRID_SIDES" in msg
     st, msg = _status(lib.nk_grid_pattern, 5, 5, 1, 0, -1, None, None, C.byref(nb))
     assert st == -1 and "boundary = -1" in msg
     # a z kind in 2-D
-    st, msg = _status(lib.nk_grid_pattern, 5, 5, 1, 0, R.sides_code((MN, MN, MN, MN, MN, 0)), None, None, C.byref(nb))
+    st, msg = _status(lib.nk_grid_pattern, 5, 5, 1, 0, GC.sides_code((MN, MN, MN, MN, MN, 0)), None, None, C.byref(nb))
     assert st == -1 and "z-lo = 2" in msg and "2-D" in msg
-    st, msg = _status(lib.nk_grid_fields_compile_check, src, 2, 1, 0, R.sides_code((0, 0, 0, 0, 0, 3)), 2, 0, C.byref(nb))
+    st, msg = _status(lib.nk_grid_fields_compile_check, src, 2, 1, 0, GC.sides_code((0, 0, 0, 0, 0, 3)), 2, 0, C.byref(nb))
     assert st == -1 and "z-hi = 3" in msg
     # the side minimum is unchanged
-    st, msg = _status(lib.nk_grid_pattern, 4, 5, 1, 16, R.sides_code(R.uniform(MN, 2)), None, None, C.byref(nb))
+    st, msg = _status(lib.nk_grid_pattern, 4, 5, 1, 16, GC.sides_code(GC.uniform(MN, 2)), None, None, C.byref(nb))
     assert st == -1 and "nx >= 5" in msg
     # the Python spellings
     with pytest.raises(ValueError, match="mirror"):
@@ -225,7 +226,7 @@ def test_argument_errors_name_their_cause():
         nls.grid_pattern(5, 5, boundary={"z": MN})
     with pytest.raises(nls.NKError, match="y axis"):
         nls.grid_pattern(5, 5, boundary={"y": (PE, DI)})
-    assert L.grid_sides(2, 3, 1, 1) == R.sides_code((MN, MF, PE, PE)) == (1 << 24) | 0x1132
+    assert L.grid_sides(2, 3, 1, 1) == GC.sides_code((MN, MF, PE, PE)) == (1 << 24) | 0x1132
 
 
 # ------------------------------------------------------------------------------------------------ resources
@@ -270,7 +271,7 @@ def test_generated_kernels_have_no_private_segment(tmp_path, monkeypatch, name, 
 # ------------------------------------------------------------------------------------------------ conservation, on the CPU
 def heat_fields(shape, level):
     """the fields of the conservation problem: the previous level, a positive coefficient, no source"""
-    f = GF.seeded_fields(3, shape)
+    f = GC.seeded_fields(3, shape)
     return np.stack([level, f[1], np.zeros_like(level)])
 
 
@@ -285,10 +286,10 @@ def test_conservation_bound_separates_mirror_face_from_dirichlet():
     out = {}
     for tag, prob in (("mirror_face", R.PROBLEMS["vardiff_mirror_face"]), ("dirichlet", R.DIRICHLET_TWIN["vardiff_mirror_face"])):
         fields = heat_fields(shape, a0)
-        u = R.dense_newton(prob, shape, a0, fields, params)
-        f = R.evaluate(prob, shape, u, u, fields, params=params).f
-        drift = abs(float(np.sum(u.astype(R.LD)) - np.sum(a0.astype(R.LD))))
-        bound = dt * float(np.abs(f).sum()) + 8 * nn * R.EPS * float(np.abs(u).sum())
+        u = GC.dense_newton(prob, shape, a0, fields, params=params)
+        f = GC.evaluate(prob, shape, u, u, fields, params=params).f
+        drift = abs(float(np.sum(u.astype(GC.LD)) - np.sum(a0.astype(GC.LD))))
+        bound = dt * float(np.abs(f).sum()) + 8 * nn * GC.EPS * float(np.abs(u).sum())
         print(f"{tag}: |sum u - sum a0| {drift:.3e}, bound {bound:.3e}, |F|_1 {np.abs(f).sum():.3e}")
         out[tag] = (drift, bound)
     assert out["mirror_face"][0] <= out["mirror_face"][1]

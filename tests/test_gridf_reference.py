@@ -1,4 +1,4 @@
-"""Compiled grid problems with fields, without a GPU: the restatement tests/gridf_reference.py against itself (analytic
+"""Compiled grid problems with fields, without a GPU: the restatement (tests/grid_core.py, tests/gridf_reference.py) against itself (analytic
 Jacobians against differences of its own long-double residual; its boundary rule for fields on a 5 × 5 example written out by
 hand), every source through nk_grid_fields_compile_check for gfx950, the generated kernels' resource notes (no private segment;
 VGPR and global-load counts printed), the argument errors with their messages, and nfields = 0 through the new entry point
@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 
 import grid3_reference as G3
+import grid_core as GC
 import grid_reference as G1
 import gridf_reference as R
 from nonlinearsolve_jl_amd import _lib as L
@@ -28,21 +29,21 @@ def test_restatement_jacobians_against_its_own_residual(name):
     restatement's residual in long double, Jᵀv against the values; 6 × 5 and 5 × 5 × 5"""
     prob = R.PROBLEMS[name]
     shape = (5, 5, 5) if prob.dim == 3 else (6, 5)
-    ref = R.reference(name, shape)
-    h = R.LD(2.0) ** -20
-    up = R.evaluate(prob, shape, ref.u.astype(R.LD) + h * ref.v.astype(R.LD), ref.v, ref.fields, R.LD).f
-    um = R.evaluate(prob, shape, ref.u.astype(R.LD) - h * ref.v.astype(R.LD), ref.v, ref.fields, R.LD).f
+    ref = GC.reference(prob, shape)
+    h = GC.LD(2.0) ** -20
+    up = GC.evaluate(prob, shape, ref.u.astype(GC.LD) + h * ref.v.astype(GC.LD), ref.v, ref.fields, T=GC.LD).f
+    um = GC.evaluate(prob, shape, ref.u.astype(GC.LD) - h * ref.v.astype(GC.LD), ref.v, ref.fields, T=GC.LD).f
     fd = ((up - um) / (2 * h)).astype(np.float64)
     assert np.max(np.abs(fd - ref.jv)) < 1e-8 * max(1.0, np.max(np.abs(ref.jv)))   # O(h²) truncation
     assert np.all(np.abs(ref.spmv - ref.jv) <= ref.spmv_bound + ref.jv_bound)
-    rp, ci = R.pattern(shape, prob.dof, prob.stencil, prob.boundary)
+    rp, ci = GC.pattern(shape, prob.dof, prob.offsets(), prob.sides)
     dense = np.zeros((rp.size - 1, rp.size - 1))
     dense[np.repeat(np.arange(rp.size - 1), np.diff(rp)), ci] = ref.vals
     assert np.allclose(dense.T @ ref.v, ref.jtv, rtol=0, atol=1e-12 * np.abs(ref.vals).max())
     for k in ("f", "jv", "vals"):
         assert np.all(getattr(ref, k + "_gap") <= getattr(ref, k + "_bound"))
     # the fields matter: other data, another residual and another Jacobian
-    other = R.reference(name, shape, shift=1.0)
+    other = GC.reference(prob, shape, shift=1.0)
     assert np.max(np.abs(other.f - ref.f)) > 1e-3 and np.max(np.abs(other.vals - ref.vals)) > 1e-3
 
 
@@ -50,7 +51,7 @@ def test_field_boundary_rule_on_a_5x5_example():
     """field value 10·j + i at node (i, j). Dirichlet: a read outside the grid returns the node's own value — at i = nx − 2 an
     offset of +2 gives the centre, not the wall; periodic: the index wraps."""
     F = np.array([[10.0 * j + i for i in range(5)] for j in range(5)])[None]
-    D, P = R.Fields(F, "dirichlet"), R.Fields(F, "periodic")
+    D, P = GC.Fields(F, "dirichlet"), GC.Fields(F, "periodic")
     assert np.array_equal(D(0, 0), F[0])
     assert np.array_equal(D(1, 0), [[1, 2, 3, 4, 4], [11, 12, 13, 14, 14], [21, 22, 23, 24, 24], [31, 32, 33, 34, 34],
                                     [41, 42, 43, 44, 44]])
@@ -64,22 +65,22 @@ def test_field_boundary_rule_on_a_5x5_example():
     assert np.array_equal(P(1, 0)[0], [1, 2, 3, 4, 0]) and np.array_equal(P(2, 0)[3], [32, 33, 34, 30, 31])
     assert np.array_equal(P(0, -1)[0], [40, 41, 42, 43, 44]) and np.array_equal(P(-1, 1)[4], [4, 0, 1, 2, 3])
     # u's rule beside it: 0 outside a Dirichlet boundary
-    assert np.array_equal(R.Grid(F, "dirichlet")(1, 0)[0], [1, 2, 3, 4, 0])
+    assert np.array_equal(GC.Grid(F, "dirichlet")(1, 0)[0], [1, 2, 3, 4, 0])
     # three dimensions: the clamp per node, not per direction
     F3 = np.arange(27, dtype=np.float64).reshape(1, 3, 3, 3)
-    D3 = R.Fields(F3, "dirichlet")
+    D3 = GC.Fields(F3, "dirichlet")
     assert D3(0, 0, 1)[2, 1, 1] == F3[0, 2, 1, 1] and D3(0, 0, 1)[1, 1, 1] == F3[0, 2, 1, 1]
     assert D3(0, 0, -1)[0, 2, 0] == F3[0, 0, 2, 0] and D3(-1, 0, 0)[1, 1, 0] == F3[0, 1, 1, 0]
 
 
 def test_seeded_fields_are_positive_and_distinct():
-    A = R.seeded_fields(4, (37, 29))
+    A = GC.seeded_fields(4, (37, 29))
     assert A.shape == (4, 1073) and A.min() > 0.6 and np.unique(A).size == A.size
 
 
 # ------------------------------------------------------------------------------------------------ compilation
 def _args(p):
-    return (p.source.encode(), p.dim, p.dof, R.STENCIL_ID[p.stencil], R.BOUNDARY_ID[p.boundary], len(p.params), p.nfields)
+    return (p.source.encode(), p.dim, p.dof, GC.STENCIL_ID[p.stencil], GC.BOUNDARY_ID[p.boundary], len(p.params), p.nfields)
 
 
 @pytest.mark.parametrize("name", sorted(R.PROBLEMS))
@@ -138,12 +139,12 @@ def test_no_fields_through_the_new_entry_point_is_the_old_program(jac):
     """nfields = 0: the bytes of nk_grid_code_object / nk_grid3_code_object on this build"""
     lib = L.lib()
     for p in (G1.PROBLEMS["bratu"], G1.PROBLEMS["box_periodic"]):
-        a = (p.source.encode(), p.dof, G1.STENCIL_ID[p.stencil], G1.BOUNDARY_ID[p.boundary], len(p.params))
+        a = (p.source.encode(), p.dof, GC.STENCIL_ID[p.stencil], GC.BOUNDARY_ID[p.boundary], len(p.params))
         old = _code_object(lib.nk_grid_code_object, *a, jac)
         new = _code_object(lib.nk_grid_fields_code_object, a[0], 2, *a[1:], 0, jac)
         assert old == new and old[:4] == b"\x7fELF"
     p = G3.PROBLEMS["bratu3"]
-    a = (p.source.encode(), p.dof, G1.STENCIL_ID[p.stencil], G1.BOUNDARY_ID[p.boundary], len(p.params))
+    a = (p.source.encode(), p.dof, GC.STENCIL_ID[p.stencil], GC.BOUNDARY_ID[p.boundary], len(p.params))
     assert _code_object(lib.nk_grid3_code_object, *a, jac) == _code_object(lib.nk_grid_fields_code_object, a[0], 3, *a[1:], 0, jac)
 
 
@@ -199,7 +200,7 @@ def test_generated_kernels_have_no_private_segment(tmp_path, name):
                   f"global loads {loads.get(k, '?')}")
             assert notes[k][0] == 0, (k, notes)
         if jac == 1 and not os.environ.get("NK_GRID_FILL_DIRECT"):
-            assert notes[kernels[0]][2] == 256 * len(R.offsets(p.dim, p.stencil)) * p.dof * 8
+            assert notes[kernels[0]][2] == 256 * len(p.offsets()) * p.dof * 8
 
 
 def test_a_declared_field_that_is_not_read_costs_no_load(tmp_path):

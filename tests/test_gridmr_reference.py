@@ -12,8 +12,8 @@ import subprocess
 import numpy as np
 import pytest
 
+import grid_core as GC
 import grid_reference as G1
-import gridbc_reference as GB
 import gridf_reference as GF
 import gridmr_reference as R
 import nonlinearsolve_jl_amd as nls
@@ -22,7 +22,7 @@ from nonlinearsolve_jl_amd import _lib as L
 LLVM = "/opt/rocm/llvm/bin"
 KERNELS = {2: {0: ("nk_grid_residual", "nk_grid_jvp"), 1: ("nk_grid_jac",)},
            3: {0: ("nk_grid3_residual", "nk_grid3_jvp"), 1: ("nk_grid3_jac",)}}
-MN, MF, DI, PE = GB.MN, GB.MF, GB.DI, GB.PE
+MN, MF, DI, PE = R.MN, R.MF, R.DI, R.PE
 # (dim, stencil, dof): every stencil the table offers, dof 1, 2 and 4 where allowed
 _STENCILS = [(2, "star", 1), (2, "star", 2), (2, "star", 4), (2, "box", 1), (2, "box", 2), (2, "star2", 1), (2, "star2", 2),
              (2, "diamond2", 1), (3, "star", 1), (3, "star", 2), (3, "star", 4), (3, "box", 1), (3, "star2", 1), (3, "star2", 2)]
@@ -52,7 +52,7 @@ def test_slab_pattern_parity_and_union(dim, stencil, dof):
     """every rank of R = 1..4: lines, rowptr and the global columns equal the restatement's (the permuted one-rank pattern's rows,
     columns renumbered and sorted); then the union check — the library's own slab patterns mapped back through the permutation
     give exactly the one-rank nk_grid_pattern, which catches every zone-order and wrap mistake"""
-    offs = GF.offsets(dim, stencil)
+    offs = GC.STENCILS[(dim, stencil)]
     for nranks in (1, 2, 3, 4):
         shape = _shape(dim, stencil, nranks)
         for xk in _XKINDS:
@@ -127,7 +127,7 @@ _SOURCES = {   # a Bratu source, a 2-component source and a fields source
 
 
 def _code_object(p, dim, nfields, boundary, nranks, rank, jac):
-    args = (p.source.encode(), dim, p.dof, GB.STENCIL_ID[p.stencil], boundary, len(p.params), nfields, nranks, rank, jac)
+    args = (p.source.encode(), dim, p.dof, GC.STENCIL_ID[p.stencil], boundary, len(p.params), nfields, nranks, rank, jac)
     nb = C.c_int64()
     assert L.lib().nk_grid_slab_code_object(*args, None, 0, C.byref(nb)) == 0, L.lib().nk_last_error()
     buf = C.create_string_buffer(nb.value)
@@ -155,7 +155,7 @@ def test_programs_of_every_kind_of_rank_compile_without_a_private_segment(name, 
     (both sides cuts, the one peer's zones in either order)"""
     p, dim, nfields = _SOURCES[name]
     for sides, ranks in (((DI, DI, MF, DI), [(3, 0), (3, 1), (3, 2)]), ((MF, MF, PE, PE), [(2, 0), (2, 1)])):
-        bd = GB.sides_code(sides)
+        bd = GC.sides_code(sides)
         for nranks, rank in ranks:
             assert nls.grid_compile_check(p.source, p.dof, p.stencil, sides, len(p.params), dim=dim, fields=nfields,
                                           nranks=nranks, rank=rank) > 0
@@ -164,8 +164,8 @@ def test_programs_of_every_kind_of_rank_compile_without_a_private_segment(name, 
                 assert sorted(priv) == sorted(KERNELS[dim][jac]), (name, nranks, rank, jac, priv)
                 assert all(v == 0 for v in priv.values()), (name, nranks, rank, jac, priv)
     # the programs of a middle rank and of an end rank are different programs
-    assert _code_object(p, dim, nfields, GB.sides_code((DI, DI, MF, DI)), 3, 0, 0) != \
-        _code_object(p, dim, nfields, GB.sides_code((DI, DI, MF, DI)), 3, 1, 0)
+    assert _code_object(p, dim, nfields, GC.sides_code((DI, DI, MF, DI)), 3, 0, 0) != \
+        _code_object(p, dim, nfields, GC.sides_code((DI, DI, MF, DI)), 3, 1, 0)
 
 
 def test_one_rank_programs_are_the_older_entry_points(tmp_path):
@@ -182,7 +182,7 @@ def test_one_rank_programs_are_the_older_entry_points(tmp_path):
         return buf.raw[:nb.value]
     p2, p3, pf = G1.PROBLEMS["brusselator"], G3.PROBLEMS["brusselator3"], GF.PROBLEMS["vardiff"]
     for jac in (0, 1):
-        for bd in (0, 1, GB.sides_code((PE, PE, MF, DI))):
+        for bd in (0, 1, GC.sides_code((PE, PE, MF, DI))):
             a = older(lib.nk_grid_code_object, p2.source.encode(), p2.dof, 0, bd, len(p2.params), jac)
             assert a == _code_object(p2, 2, 0, bd, 1, 0, jac)
         a = older(lib.nk_grid3_code_object, p3.source.encode(), p3.dof, 0, 1, len(p3.params), jac)
