@@ -358,7 +358,9 @@ int nk_device_free(nk_ctx *ctx, void *ptr);
 int nk_device_copy(nk_ctx *ctx, void *dst, const void *src, int64_t bytes, int kind);
 /* In-place updates of resident vectors (DEVICE pointers, local length n) for host languages whose resident vector type is a
  * library buffer (Julia's DeviceVector): y = a x + b y and y = a — with nk_dot / nk_nrm2 / nk_norm_inf / nk_axpy below, what
- * `@bb axpy!`, `copyto!` and the termination norms of the reference's step! need (FirstOrder/src/solve.jl:403,438,460). */
+ * `@bb axpy!`, `copyto!` and the termination norms of the reference's step! need (FirstOrder/src/solve.jl:403,438,460).
+ * They follow the contract of the BLAS-1 building blocks stated at the end of this header; nk_vec_fill stores the bit pattern of
+ * `a` in every element (so −0.0 stays −0.0 and a NaN keeps its payload). */
 int nk_vec_axpby(nk_ctx *ctx, int64_t n, double a, const double *x, double b, double *y);
 int nk_vec_fill(nk_ctx *ctx, int64_t n, double a, double *y);
 
@@ -1043,7 +1045,21 @@ int nk_batch_solve_trust_region_nlls_f32(nk_batch *B, int64_t nbatch, const floa
                                          int32_t *retcode_out, int32_t *iters_out);
 
 /* ---------------------------------------------------------------- BLAS-1 building blocks (exported for
- * the bench / tests; all on the ctx stream, results of reductions are all-reduced over the ranks) */
+ * the bench / tests; all on the ctx stream, results of reductions are all-reduced over the ranks)
+ *
+ * The contract of these entry points and of nk_vec_axpby / nk_vec_fill:
+ *  - Alignment: every vector (x, y, w, V) starts on a 16-byte boundary and ldv is even and at least n, so that every column of
+ *    V does too. The kernels read pairs of doubles; a pointer that is only 8-byte aligned is not supported.
+ *  - Edges: n = 0 is a no-op (a reduction returns 0) and may come with NULL vectors. n < 0 or nv < 0 is an error, as is
+ *    nv > 64 (nk_multidot, nk_multiaxpy; nv = 0 is allowed there) and nv outside 1..32 (nk_fused_axpy_dot). An error launches
+ *    nothing and leaves every vector as it was.
+ *  - Zero coefficients (nk_vec_axpby, nk_axpy): a coefficient that is exactly zero, of either sign, means that its operand is
+ *    not read: a = 0 gives y = b y whatever x holds (NaN and Inf included), b = 0 gives y = a x whatever y held, and
+ *    a = b = 0 stores +0.0. Nonzero coefficients give a x + b y with one rounding per operation.
+ *  - Aliasing: x may be the same pointer as y (y = a y + b y). Vectors that overlap in part are not allowed.
+ *  - Overflow: nk_nrm2 is the unscaled sqrt(sum x_i^2): entries above about 1e154 overflow to Inf, entries below about 1e-154
+ *    are lost. nk_norm_inf is exact; a NaN anywhere gives NaN.
+ *  - Reductions are summed in a fixed order: the same call on the same data returns the same bits. */
 int nk_dot(nk_ctx *ctx, int64_t n, const double *x, const double *y, double *result);
 int nk_nrm2(nk_ctx *ctx, int64_t n, const double *x, double *result);
 int nk_norm_inf(nk_ctx *ctx, int64_t n, const double *x, double *result);

@@ -5,6 +5,7 @@
 //   multidot   : 8 n (nv + 1)            multiaxpy : 8 n (nv + 2)      scale_to : 16 n
 //   dot        : 16 n    sumsq/norm_inf : 8 n    axpby : 24 n    copy : 16 n
 #include <algorithm>
+#include <cmath>
 
 #include "nk_internal.h"
 
@@ -952,6 +953,37 @@ int nk_blas_axpby(nk_ctx *ctx, int64_t n, double a, const double *x, double b, d
   NK_HIP(hipGetLastError());
   return NK_OK;
 }
+// The exported y = a x + b y (include/mi355x_nk.h): a coefficient that is exactly zero means that its operand is not read, and x
+// may be y. k_axpby keeps its two restrict operands and its arithmetic for the solvers (b = 1, distinct vectors); the cases it
+// cannot serve have kernels of their own, so the solvers' path gains no per-element branch.
+enum { NK_EW_SCALE, NK_EW_SCALED_COPY, NK_EW_IN_PLACE };  // y = b y | y = a x (x may be y) | y = a y + b y
+template <int MODE>
+__global__ __launch_bounds__(NK_BLOCK) void k_axpby_edge(int64_t n, double a, const double *x, double b, double *y) {
+  const double *src = (MODE == NK_EW_SCALED_COPY) ? x : y;
+  const int64_t npair = n >> 1, stride = (int64_t)gridDim.x * NK_BLOCK;
+  for (int64_t i = (int64_t)blockIdx.x * NK_BLOCK + threadIdx.x; i < npair; i += stride) {
+    double2 v = reinterpret_cast<const double2 *>(src)[i];
+    if (MODE == NK_EW_SCALE) { v.x = b * v.x; v.y = b * v.y; }
+    else if (MODE == NK_EW_SCALED_COPY) { v.x = a * v.x; v.y = a * v.y; }
+    else { v.x = a * v.x + b * v.x; v.y = a * v.y + b * v.y; }
+    reinterpret_cast<double2 *>(y)[i] = v;
+  }
+  if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) {
+    const double v = src[n - 1];
+    y[n - 1] = (MODE == NK_EW_SCALE) ? b * v : (MODE == NK_EW_SCALED_COPY) ? a * v : a * v + b * v;
+  }
+}
+int nk_blas_axpby_any(nk_ctx *ctx, int64_t n, double a, const double *x, double b, double *y) {
+  if (n <= 0) return NK_OK;
+  if (a == 0.0 && b == 0.0) return nk_blas_fill(ctx, n, 0.0, y);
+  if (a == 0.0 && b == 1.0) return NK_OK;
+  if (a != 0.0 && b != 0.0 && x != y) return nk_blas_axpby(ctx, n, a, x, b, y);
+  if (a == 0.0) NK_LAUNCH(ctx, k_axpby_edge<NK_EW_SCALE>, dim3(ew_grid(n)), dim3(NK_BLOCK), n, a, x, b, y);
+  else if (b == 0.0) NK_LAUNCH(ctx, k_axpby_edge<NK_EW_SCALED_COPY>, dim3(ew_grid(n)), dim3(NK_BLOCK), n, a, x, b, y);
+  else NK_LAUNCH(ctx, k_axpby_edge<NK_EW_IN_PLACE>, dim3(ew_grid(n)), dim3(NK_BLOCK), n, a, x, b, y);
+  NK_HIP(hipGetLastError());
+  return NK_OK;
+}
 int nk_blas_lincomb(nk_ctx *ctx, int64_t n, double a, const double *x, double b, const double *y, double *z) {
   NK_LAUNCH(ctx, k_lincomb, dim3(nk_grid_for(n, NK_BLOCK * 2, 4096)), dim3(NK_BLOCK), n, a, x, b, y, z);
   NK_HIP(hipGetLastError());
@@ -969,7 +1001,7 @@ int nk_blas_copy(nk_ctx *ctx, int64_t n, const double *x, double *y) {
 }
 int nk_blas_fill(nk_ctx *ctx, int64_t n, double a, double *y) {
   if (n <= 0) return NK_OK;
-  if (a == 0.0) {
+  if (a == 0.0 && !std::signbit(a)) {  // all-zero bytes are +0.0 only: −0.0 goes through the kernel
     NK_HIP(hipMemsetAsync(y, 0, (size_t)n * sizeof(double), ctx->stream));
     return NK_OK;
   }
@@ -1000,39 +1032,43 @@ int nk_scalars_to_host(nk_ctx *ctx, const double *d_src, int count, double *h_ds
 }
 
 // ----------------------------------------------------------------------------- exported BLAS-1 (device pointers)
+// The contract of these entry points is stated once, in include/mi355x_nk.h. n = 0 still runs the launches (they read nothing):
+// on several ranks every rank has to take part in the reduction, also one whose slab is empty.
 extern "C" int nk_dot(nk_ctx *ctx, int64_t n, const double *x, const double *y, double *result) {
-  NK_REQUIRE(ctx && x && y && result, "NULL argument");
+  NK_REQUIRE(ctx && result && n >= 0 && (n == 0 || (x && y)), "bad argument");
   NK_TRY(nk_blas_dot(ctx, n, x, y, ctx->d_scal));
   return nk_scalars_to_host(ctx, ctx->d_scal, 1, result);
 }
 extern "C" int nk_nrm2(nk_ctx *ctx, int64_t n, const double *x, double *result) {
-  NK_REQUIRE(ctx && x && result, "NULL argument");
+  NK_REQUIRE(ctx && result && n >= 0 && (n == 0 || x), "bad argument");
   NK_TRY(nk_blas_dot(ctx, n, x, x, ctx->d_scal));
   NK_TRY(nk_scalars_to_host(ctx, ctx->d_scal, 1, result));
   *result = sqrt(*result);
   return NK_OK;
 }
 extern "C" int nk_norm_inf(nk_ctx *ctx, int64_t n, const double *x, double *result) {
-  NK_REQUIRE(ctx && x && result, "NULL argument");
+  NK_REQUIRE(ctx && result && n >= 0 && (n == 0 || x), "bad argument");
   NK_TRY(nk_blas_norm_inf(ctx, n, x, ctx->d_scal));
   return nk_scalars_to_host(ctx, ctx->d_scal, 1, result);
 }
 extern "C" int nk_axpy(nk_ctx *ctx, int64_t n, double a, const double *x, double *y) {
-  NK_REQUIRE(ctx && x && y, "NULL argument");
-  return nk_blas_axpby(ctx, n, a, x, 1.0, y);
+  NK_REQUIRE(ctx && n >= 0 && (n == 0 || (x && y)), "bad argument");
+  return nk_blas_axpby_any(ctx, n, a, x, 1.0, y);
 }
 extern "C" int nk_multidot(nk_ctx *ctx, int64_t n, int nv, const double *V, int64_t ldv, const double *w,
                            double *h_host) {
-  NK_REQUIRE(ctx && V && w && h_host, "NULL argument");
-  NK_REQUIRE((ldv & 1) == 0, "ldv must be even (16-byte aligned columns)");
+  NK_REQUIRE(ctx && h_host && n >= 0 && (n == 0 || (V && w)), "bad argument");
+  NK_REQUIRE(nv >= 0 && nv <= NK_MAX_NV, "multidot: nv=%d out of range", nv);
+  NK_REQUIRE((ldv & 1) == 0 && ldv >= n, "ldv must be even (16-byte aligned columns) and at least n");
   NK_TRY(nk_blas_multidot(ctx, n, nv, V, ldv, w, ctx->d_scal, false, nullptr, nullptr));
   return nk_scalars_to_host(ctx, ctx->d_scal, nv, h_host);
 }
 // bench/test export of the fused CGS2 pass: w ← w − V(h∘s); h2[j] = s_j ṽ_j·w_new (j<nv), h2[nv] = ‖w_new‖²
 extern "C" int nk_fused_axpy_dot(nk_ctx *ctx, int64_t n, int nv, const double *V, int64_t ldv, const double *h_host,
                                  const double *s_host, double *w, double *h2_host) {
-  NK_REQUIRE(ctx && V && w && h_host && s_host && h2_host, "NULL argument");
+  NK_REQUIRE(ctx && h_host && s_host && h2_host && n >= 0 && (n == 0 || (V && w)), "bad argument");
   NK_REQUIRE(nv >= 1 && nv <= 32, "nv out of range");
+  NK_REQUIRE((ldv & 1) == 0 && ldv >= n, "ldv must be even (16-byte aligned columns) and at least n");
   for (int j = 0; j < nv; ++j) { ctx->h_pinned[j] = h_host[j]; ctx->h_pinned[NK_MAX_NV + j] = s_host[j]; }
   NK_HIP(hipMemcpyAsync(ctx->d_scal, ctx->h_pinned, 2 * NK_MAX_NV * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
   NK_TRY(nk_blas_fused_axpy_dot(ctx, n, nv, V, ldv, ctx->d_scal, ctx->d_scal + NK_MAX_NV, w, ctx->d_scal + 2 * NK_MAX_NV,
@@ -1041,10 +1077,11 @@ extern "C" int nk_fused_axpy_dot(nk_ctx *ctx, int64_t n, int nv, const double *V
 }
 extern "C" int nk_multiaxpy(nk_ctx *ctx, int64_t n, int nv, const double *V, int64_t ldv, const double *h_host,
                             double *w, double *wnorm2) {
-  NK_REQUIRE(ctx && V && w && h_host, "NULL argument");
-  NK_REQUIRE(nv <= NK_MAX_NV && (ldv & 1) == 0, "bad nv/ldv");
+  NK_REQUIRE(ctx && n >= 0 && (n == 0 || (w && (V || nv == 0))) && (h_host || nv == 0), "bad argument");
+  NK_REQUIRE(nv >= 0 && nv <= NK_MAX_NV, "multiaxpy: nv=%d out of range", nv);
+  NK_REQUIRE((ldv & 1) == 0 && ldv >= n, "ldv must be even (16-byte aligned columns) and at least n");
   for (int j = 0; j < nv; ++j) ctx->h_pinned[j] = h_host[j];
-  NK_HIP(hipMemcpyAsync(ctx->d_scal, ctx->h_pinned, nv * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+  if (nv > 0) NK_HIP(hipMemcpyAsync(ctx->d_scal, ctx->h_pinned, nv * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
   NK_TRY(nk_blas_multiaxpy(ctx, n, nv, V, ldv, ctx->d_scal, -1.0, w, wnorm2 ? ctx->d_scal + NK_MAX_NV : nullptr,
                            nullptr, nullptr, nullptr));
   if (wnorm2) return nk_scalars_to_host(ctx, ctx->d_scal + NK_MAX_NV, 1, wnorm2);

@@ -146,7 +146,7 @@ extern "C" int nk_device_copy(nk_ctx *ctx, void *dst, const void *src, int64_t b
 extern "C" int nk_vec_axpby(nk_ctx *ctx, int64_t n, double a, const double *x, double b, double *y) {
   NK_REQUIRE(ctx && (n == 0 || (x && y)) && n >= 0, "bad argument");
   NK_HIP(hipSetDevice(ctx->device));
-  return n ? nk_blas_axpby(ctx, n, a, x, b, y) : NK_OK;
+  return nk_blas_axpby_any(ctx, n, a, x, b, y);
 }
 extern "C" int nk_vec_fill(nk_ctx *ctx, int64_t n, double a, double *y) {
   NK_REQUIRE(ctx && (n == 0 || y) && n >= 0, "bad argument");

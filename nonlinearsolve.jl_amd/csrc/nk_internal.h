@@ -497,7 +497,9 @@ int nk_blas_dcgs2_pass_a(nk_ctx *ctx, int64_t n, int k, double *V, int64_t ldv, 
                          const double *d_scales, double *d_h, const int *d_skip);
 int nk_blas_fused_axpy_dot(nk_ctx *ctx, int64_t n, int nv, const double *V, int64_t ldv, const double *d_h,
                            const double *d_scales, double *w, double *d_h2, const int *d_skip);
-int nk_blas_axpby(nk_ctx *ctx, int64_t n, double a, const double *x, double b, double *y);  // y = a x + b y
+int nk_blas_axpby(nk_ctx *ctx, int64_t n, double a, const double *x, double b, double *y);  // y = a x + b y (both read; x ≠ y)
+// the exported contract: a zero coefficient's operand is not read, a = b = 0 stores +0.0, x may be y
+int nk_blas_axpby_any(nk_ctx *ctx, int64_t n, double a, const double *x, double b, double *y);
 int nk_blas_scale_to(nk_ctx *ctx, int64_t n, const double *d_scale, const double *x, double *y,
                      const int *d_skip);  // y = (*d_scale) * x
 int nk_blas_copy(nk_ctx *ctx, int64_t n, const double *x, double *y);
