@@ -186,7 +186,7 @@ typedef struct {
   int32_t restarts;     /* completed restart cycles                                   */
   int32_t converged;    /* 1: ‖r‖ ≤ atol + rtol‖r0‖ ; 0: iteration cap hit            */
   int32_t failed;       /* 1: non-finite residual (maps to ReturnCode.Failure)        */
-  double  rnorm0;       /* ‖b − A x0‖₂                                                */
+  double  rnorm0;       /* ‖b − A x0‖₂ (‖Pl⁻¹(b − A x0)‖₂ with a left preconditioner) */
   double  rnorm;        /* last (recurrence) residual norm estimate                   */
 } nk_gmres_info;
 
@@ -661,6 +661,8 @@ int nk_grid_slab_code_object(const char *source, int dim, int dof, int stencil, 
 int nk_problem_grid_slab(nk_problem *P, int64_t *line_begin, int64_t *line_end);
 
 /* ---------------------------------------------------------------- GMRES (seam 1) */
+/* restart_m: the restart length m, 1 <= m <= 63 (the dot-product kernels take at most 64 columns at once); restart_m <= 0 means 30;
+ * restart_m >= 64 is NK_E_INVALID with a message that names the limit, before anything is allocated or launched. */
 int nk_gmres_create(nk_ctx *ctx, int64_t n_local, int restart_m, int ortho, nk_gmres **out);
 int nk_gmres_destroy(nk_gmres *G);
 int nk_gmres_set_operator_csr(nk_gmres *G, nk_csr *A);                    /* cache.A = SparseMatrix   */
@@ -815,7 +817,14 @@ int nk_gmres_multigrid_levels(nk_gmres *G, int *levels, int cap, int64_t *sides,
 int nk_gmres_multigrid_level_matrix(nk_gmres *G, int level, nk_csr **out);
 int nk_gmres_multigrid_level_field(nk_gmres *G, int level, int k, double *out, int memspace);
 /* Solve A x = b. use_x0 = 0 ⇒ zero initial guess (our protocol); 1 ⇒ x holds x0.
- * Stop when ‖r‖₂ ≤ atol + rtol‖r0‖₂ or after maxiter Arnoldi steps; fixed_iters>0 overrides both. */
+ * Stop when ‖r‖₂ ≤ atol + rtol‖r0‖₂ or after maxiter Arnoldi steps; fixed_iters>0 overrides both.
+ *  - use_x0 = 1 with a right preconditioner (callback, object, Chebyshev or multigrid) is NK_E_UNSUPPORTED ("not supported"):
+ *    nothing is iterated, x keeps x0, and the object serves the next solve as before.
+ *  - With a left preconditioner every norm of the solve is the preconditioned one: info.rnorm0 = ‖Pl⁻¹(b − A x0)‖,
+ *    info.rnorm = the recurrence estimate of ‖Pl⁻¹(b − A x)‖, and atol / rtol are measured against those.
+ *  - n_local = 0 on one rank: a converged empty solve — NK_OK, info = {0 iterations, 0 restarts, converged = 1, failed = 0,
+ *    rnorm0 = rnorm = 0}; nothing is launched, no callback runs, b and x are not read and may be NULL. (On several ranks a rank
+ *    without rows takes part in the collectives like every other.) */
 int nk_gmres_solve(nk_gmres *G, const double *b, double *x, int memspace, int use_x0,
                    double atol, double rtol, int maxiter, int fixed_iters, nk_gmres_info *info);
 

@@ -1807,7 +1807,15 @@ static int gmres_solve_once(nk_gmres *G, const double *d_b, double *d_x, int use
 
 extern "C" int nk_gmres_solve(nk_gmres *G, const double *b, double *x, int memspace, int use_x0, double atol,
                               double rtol, int maxiter, int fixed_iters, nk_gmres_info *info) {
-  NK_REQUIRE(G && b && x, "NULL argument");
+  NK_REQUIRE(G, "NULL argument");
+  if (G->n == 0 && nk_ctx_is_single(G->ctx)) {   // nothing to solve: converged, no launch, b and x not read (the header's contract)
+    if (info) {
+      memset(info, 0, sizeof(*info));
+      info->converged = 1;
+    }
+    return NK_OK;
+  }
+  NK_REQUIRE(b && x, "NULL argument");
   NK_HIP(hipSetDevice(G->ctx->device));
   if (memspace == NK_DEVICE) return nk_gmres_solve_dev(G, b, x, use_x0, atol, rtol, maxiter, fixed_iters, info);
   nk_ctx *ctx = G->ctx;
