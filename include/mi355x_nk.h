@@ -743,7 +743,13 @@ int nk_precond_create_ilut(nk_csr *A, double tau, nk_precond **out);
  * ≤ coarse_max (≤ 128) rows, inverted densely. nk_precond_update keeps the aggregates and refreshes every number on the
  * device (Galerkin sums, D⁻¹, Gershgorin bounds, the coarse inverse) for the matrix's current values. A fixed linear
  * operator: usable as Pl or Pr. Several ranks: the rank's local block (block-Jacobi AMG). params NULL or zero fields:
- * defaults (nu 2, passes 2, theta 0.25, overcorrection 1.8, cheb_ratio 4, coarse_max 128). */
+ * defaults (nu 2, passes 2, theta 0.25, overcorrection 1.8, cheb_ratio 4, coarse_max 128, matching 0). Every other value is
+ * taken as given or refused with NK_E_INVALID, never replaced: a negative (or NaN) field, cheb_ratio in (0, 1], nu > 16,
+ * passes > 4, coarse_max > 128, matching outside 0..2 (0 automatic, 1 the host's sequential pass, 2 the device's handshaking).
+ * A matrix without rows (a rank may own none) is accepted: one level of 0 rows with the bound 1.0, nothing is launched by
+ * create, update or apply. Columns sorted and unique within every row (NK_E_INVALID otherwise); NK_E_SINGULAR on a zero,
+ * missing or non-finite diagonal entry on any level and on a singular coarsest matrix — from nk_precond_update as well, after
+ * which nk_precond_apply refuses until an update succeeds. */
 typedef struct nk_amg_params {
   int32_t nu, passes, coarse_max, matching;
   double theta, overcorrection, cheb_ratio;
@@ -756,6 +762,10 @@ int nk_precond_amg_matching(nk_precond *P, int *matching);
 int nk_precond_amg_info(nk_precond *P, int *levels, int cap, int64_t *sizes, int64_t *nnzs, double *lmax);
 /* row → coarse row of level `level` (`count` = that level's rows; the coarsest level has none: NK_E_INVALID) */
 int nk_precond_amg_aggregates(nk_precond *P, int level, int32_t *agg, int64_t count);
+/* level `level`'s matrix itself, for inspection (owned by the hierarchy: do not destroy; valid until the preconditioner goes;
+ * its values are those of the last nk_precond_update). Level 0 is the caller's matrix, or on several ranks the private copy of
+ * the rank's local square block. A level outside 0 .. levels − 1: NK_E_INVALID. */
+int nk_precond_amg_level_matrix(nk_precond *P, int level, nk_csr **out);
 int nk_precond_update(nk_precond *P);
 int nk_precond_apply(nk_precond *P, const double *x, double *y, int memspace);   /* y = M⁻¹ x */
 int nk_precond_info(nk_precond *P, int *kind, int *levels_lower, int *levels_upper, int *ncolors);

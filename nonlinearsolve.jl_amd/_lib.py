@@ -231,6 +231,7 @@ SIGNATURES = {
     "nk_precond_amg_info": (_I, [_P, C.POINTER(_I), _I, _P, _P, _P]),
     "nk_precond_amg_aggregates": (_I, [_P, _I, _P, _L]),
     "nk_precond_amg_matching": (_I, [_P, C.POINTER(_I)]),
+    "nk_precond_amg_level_matrix": (_I, [_P, _I, _PP]),
     "nk_precond_update": (_I, [_P]),
     "nk_precond_apply": (_I, [_P, _P, _P, _I]),
     "nk_precond_info": (_I, [_P, C.POINTER(_I), C.POINTER(_I), C.POINTER(_I), C.POINTER(_I)]),

@@ -1007,6 +1007,15 @@ class AMGPreconditioner(Preconditioner):
         check(L.lib().nk_precond_amg_aggregates(self._h, int(level), C.c_void_p(out.ctypes.data), rows))
         return out
 
+    def level_matrix(self, level: int) -> "CSRMatrix":
+        """A_l of the hierarchy: a non-owning view (it lives as long as this object; values as of the last `update()`). Level 0
+        is the matrix the object was built from, or on several ranks the private copy of the rank's local square block."""
+        h = C.c_void_p()
+        check(L.lib().nk_precond_amg_level_matrix(self._h, int(level), C.byref(h)))
+        A = CSRMatrix(h, self.A.ctx, owned=False)
+        A._keep = self   # the view reads this object's arrays
+        return A
+
 
 @dataclass
 class ObjectPrecs:

@@ -667,6 +667,10 @@ static int amg_setup_device(nk_amg *M, const std::function<void(const char *)> &
     L0.n = A->nrows; L0.nnz = A->nnz; L0.A = A;
   }
   lap("arena");
+  if (A->nrows <= prm.coarse_max)   // (no coarsening, so no k_amg_strength: the few rows are checked here)
+    for (int64_t r = 0; r < A->nrows; ++r)
+      for (int32_t k = A->h_rowptr[r] + 1; k < A->h_rowptr[r + 1]; ++k)
+        NK_REQUIRE(A->h_col[k] > A->h_col[k - 1], "AMG: the columns of some row are not sorted / unique");
   while (M->lv.back().n > prm.coarse_max && (int)M->lv.size() < 24) {
     ar.top = 0;
     const int l = (int)M->lv.size() - 1;
@@ -762,14 +766,17 @@ int nk_amg_create(nk_csr *A, const nk_amg_params *prm, nk_amg **out) {
   M->ctx = ctx;
   M->A = A;
   nk_amg_params_default(&M->prm);
-  if (prm) {
+  if (prm) {   // a zero field takes its default; a negative one (NaN included), or a cheb_ratio in (0, 1], is refused
+    NK_REQUIRE(prm->nu >= 0 && prm->passes >= 0 && prm->coarse_max >= 0 && prm->theta >= 0.0 && prm->overcorrection >= 0.0 &&
+                   (prm->cheb_ratio == 0.0 || prm->cheb_ratio > 1.0),
+               "AMG: a parameter field is zero (its default) or positive, cheb_ratio zero or > 1");
     if (prm->nu > 0) M->prm.nu = prm->nu;
     if (prm->passes > 0) M->prm.passes = prm->passes;
-    if (prm->matching > 0) M->prm.matching = prm->matching;
     if (prm->coarse_max > 0) M->prm.coarse_max = prm->coarse_max;
     if (prm->theta > 0.0) M->prm.theta = prm->theta;
     if (prm->overcorrection > 0.0) M->prm.overcorrection = prm->overcorrection;
     if (prm->cheb_ratio > 1.0) M->prm.cheb_ratio = prm->cheb_ratio;
+    M->prm.matching = prm->matching;
   }
   NK_REQUIRE(M->prm.nu <= 16 && M->prm.passes <= 4 && M->prm.coarse_max <= 128, "AMG: nu ≤ 16, passes ≤ 4, coarse_max ≤ 128");
   NK_REQUIRE(M->prm.matching >= 0 && M->prm.matching <= 2, "AMG: matching is 0 (automatic), 1 (sequential, host) or 2 (handshake, device)");
@@ -962,6 +969,7 @@ int nk_amg_update(nk_amg *M) {
   if (fail[0]) NK_FAIL(NK_E_SINGULAR, "AMG: zero or non-finite diagonal entry on some level");
   if (fail[1]) NK_FAIL(NK_E_SINGULAR, "AMG: the coarsest-level matrix is singular");
   for (int l = 0; l < nlev; ++l) {
+    if (M->lv[l].n == 0) { M->lv[l].lmax = 1.0; continue; }   // (a rank may own no rows: nothing was launched for this level)
     if (!(lm[l] > 0.0) || !std::isfinite(lm[l])) NK_FAIL(NK_E_SINGULAR, "AMG: no finite Gershgorin bound on level %d", l);
     M->lv[l].lmax = lm[l];
   }
@@ -1067,3 +1075,4 @@ const int32_t *nk_amg_aggregates(const nk_amg *Mc, int l) {
   return L.h_agg.data();
 }
 int nk_amg_matching(const nk_amg *M) { return M->matching; }
+nk_csr *nk_amg_level_matrix(const nk_amg *M, int l) { return (l < 0 || l >= (int)M->lv.size()) ? nullptr : M->lv[l].A; }

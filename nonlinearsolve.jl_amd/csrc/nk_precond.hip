@@ -604,6 +604,12 @@ extern "C" int nk_precond_amg_aggregates(nk_precond *P, int level, int32_t *agg,
   memcpy(agg, h, (size_t)n * sizeof(int32_t));
   return NK_OK;
 }
+extern "C" int nk_precond_amg_level_matrix(nk_precond *P, int level, nk_csr **out) {
+  NK_REQUIRE(P && P->kind == NK_PRECOND_AMG && P->amg && out, "not an AMG preconditioner");
+  *out = nk_amg_level_matrix(P->amg, level);
+  NK_REQUIRE(*out, "level %d outside 0..%d", level, nk_amg_levels(P->amg) - 1);
+  return NK_OK;
+}
 extern "C" int nk_precond_destroy(nk_precond *P) {
   if (!P) return NK_OK;
   nk_amg_destroy(P->amg);
