@@ -10,7 +10,7 @@
 //   coarse A     Galerkin TᵀA T: every coarse entry = the sum of the fine entries it covers, in ascending position — a gather
 //                plan per level, one thread per coarse entry: bitwise reproducible, refreshed on the DEVICE for every new A.
 //   smoother     ν Chebyshev steps on D⁻¹A over [λmax/ratio, λmax], λmax = max_i Σ_j |a_ij| / |a_ii| (device reduction);
-//                the steps ride in the CSR SpMV's row epilogue (modes 1 / 2 / 4 of nk_spmv_epi: no separate vector pass).
+//                the steps ride in the CSR SpMV's row epilogue (NK_EPI_CHEB_STEP / _RESIDUAL / _RESIDUAL_UPDATE: no separate vector pass).
 //   coarsest     ≤ 128 rows: dense inverse by the in-register Gauss–Jordan of nk_bcr.hip (row pivoting), applied as one
 //                GEMV launch; if coarsening stalls above that, 4ν smoothing steps.
 //   cycle        V, with the coarse correction over-corrected by ω (1.8): plain aggregation under-estimates smooth error by
@@ -243,7 +243,7 @@ __global__ __launch_bounds__(NK_BLOCK) void k_amg_dense_fill(int n, int ld, cons
 // x = M b, M dense column-major (leading dimension ld), n ≤ 128: lanes run along the rows, coalesced
 __global__ __launch_bounds__(128) void k_amg_dense_apply(int n, int ld, const double *__restrict__ M, const double *__restrict__ b,
                                                          double *__restrict__ x, const int *d_skip) {
-  if (d_skip != nullptr && *d_skip != 0) return;
+  if (nk_skip(d_skip)) return;
   __shared__ double sb[128];
   const int t = threadIdx.x;
   if (t < n) sb[t] = b[t];
@@ -253,29 +253,9 @@ __global__ __launch_bounds__(128) void k_amg_dense_apply(int n, int ld, const do
   for (int j = 0; j < n; ++j) s += M[(int64_t)t + (int64_t)j * ld] * sb[j];
   x[t] = s;
 }
-// first Chebyshev step. zero = 1: from x = 0 (r ← b, d = D⁻¹b/θ, x = d); zero = 0: r holds b − A x (d = D⁻¹r/θ, x += d)
-__global__ __launch_bounds__(NK_BLOCK) void k_amg_cheb_first(int64_t n, int zero, const double *__restrict__ b,
-                                                             const double *__restrict__ dinv, double inv_theta,
-                                                             double *__restrict__ r, double *__restrict__ d, double *__restrict__ x,
-                                                             const int *d_skip) {
-  if (d_skip != nullptr && *d_skip != 0) return;
-  const int64_t stride = (int64_t)gridDim.x * NK_BLOCK;
-  for (int64_t i = (int64_t)blockIdx.x * NK_BLOCK + threadIdx.x; i < n; i += stride) {
-    if (zero) {
-      const double bb = b[i], dd = dinv[i] * bb * inv_theta;
-      r[i] = bb;
-      d[i] = dd;
-      x[i] = dd;
-    } else {
-      const double dd = dinv[i] * r[i] * inv_theta;
-      d[i] = dd;
-      x[i] += dd;
-    }
-  }
-}
 __global__ __launch_bounds__(NK_BLOCK) void k_amg_restrict(int64_t nc, const int32_t *__restrict__ aggptr, const int32_t *__restrict__ aggmem,
                                                            const double *__restrict__ r, double *__restrict__ bc, const int *d_skip) {
-  if (d_skip != nullptr && *d_skip != 0) return;
+  if (nk_skip(d_skip)) return;
   const int64_t stride = (int64_t)gridDim.x * NK_BLOCK;
   for (int64_t I = (int64_t)blockIdx.x * NK_BLOCK + threadIdx.x; I < nc; I += stride) {
     double s = 0.0;
@@ -285,7 +265,7 @@ __global__ __launch_bounds__(NK_BLOCK) void k_amg_restrict(int64_t nc, const int
 }
 __global__ __launch_bounds__(NK_BLOCK) void k_amg_prolong(int64_t n, const int32_t *__restrict__ agg, const double *__restrict__ xc,
                                                           double omega, double *__restrict__ x, const int *d_skip) {
-  if (d_skip != nullptr && *d_skip != 0) return;
+  if (nk_skip(d_skip)) return;
   const int64_t stride = (int64_t)gridDim.x * NK_BLOCK;
   for (int64_t i = (int64_t)blockIdx.x * NK_BLOCK + threadIdx.x; i < n; i += stride) x[i] += omega * xc[agg[i]];
 }
@@ -503,7 +483,6 @@ struct amg_arena {
     return NK_OK;
   }
 };
-static inline dim3 amg_g1(int64_t n) { return dim3((unsigned)((n + NK_BLOCK - 1) / NK_BLOCK > 0 ? (n + NK_BLOCK - 1) / NK_BLOCK : 1)); }
 // out[0 .. n) = exclusive prefix sums of in[0 .. n) (n includes the caller's trailing zero: out[n − 1] is the total).
 // An in-tree scan (no vendor primitive in the shipped path): a workgroup scans 2048 entries — eight per thread in registers, the
 // wavefront's 64 thread sums by a shuffle ladder, the four wavefront sums through LDS — and leaves its total; the totals are
@@ -569,19 +548,19 @@ static int amg_handshake_pass_dev(nk_ctx *ctx, amg_arena &ar, const amg_dcsr &F,
   NK_TRY(ar.get(&thr, n)); NK_TRY(ar.get(&sgn, n));
   NK_TRY(ar.get(&match, n)); NK_TRY(ar.get(&best, n)); NK_TRY(ar.get(&flag, n + 1)); NK_TRY(ar.get(&num, n + 1));
   NK_TRY(ar.get(&cid, n));
-  NK_LAUNCH(ctx, k_amg_strength, amg_g1(n), dim3(NK_BLOCK), n, F.rp, F.ci, F.v, theta, thr, sgn, d_fail);
+  NK_LAUNCH(ctx, k_amg_strength, nk_grid1(n), dim3(NK_BLOCK), n, F.rp, F.ci, F.v, theta, thr, sgn, d_fail);
   NK_HIP(hipMemsetAsync(match, 0xFF, n * sizeof(int32_t), ctx->stream));
   for (int r = 0; r < AMG_HS_ROUNDS; ++r) {
-    NK_LAUNCH(ctx, k_amg_propose, amg_g1(n), dim3(NK_BLOCK), n, F.rp, F.ci, F.v, (const double *)thr, (const double *)sgn,
+    NK_LAUNCH(ctx, k_amg_propose, nk_grid1(n), dim3(NK_BLOCK), n, F.rp, F.ci, F.v, (const double *)thr, (const double *)sgn,
               (const int32_t *)match, best, variant);
-    NK_LAUNCH(ctx, k_amg_accept, amg_g1(n), dim3(NK_BLOCK), n, (const int32_t *)best, match);
+    NK_LAUNCH(ctx, k_amg_accept, nk_grid1(n), dim3(NK_BLOCK), n, (const int32_t *)best, match);
   }
-  NK_LAUNCH(ctx, k_amg_rep_flag, amg_g1(n + 1), dim3(NK_BLOCK), n, (const int32_t *)match, flag);
+  NK_LAUNCH(ctx, k_amg_rep_flag, nk_grid1(n + 1), dim3(NK_BLOCK), n, (const int32_t *)match, flag);
   NK_TRY(amg_scan(ctx, ar, flag, num, n + 1));
   int32_t nc = 0;
   NK_TRY(amg_fetch_int(ctx, num + n, &nc));
   NK_TRY(ar.get(&pair, 2 * (size_t)nc + 2));
-  NK_LAUNCH(ctx, k_amg_number, amg_g1(n), dim3(NK_BLOCK), n, (const int32_t *)match, (const int32_t *)num, cid, pair);
+  NK_LAUNCH(ctx, k_amg_number, nk_grid1(n), dim3(NK_BLOCK), n, (const int32_t *)match, (const int32_t *)num, cid, pair);
   *cid_out = cid; *pair_out = pair; *nc_out = nc;
   return NK_OK;
 }
@@ -595,9 +574,9 @@ static int amg_galerkin_plan_dev(nk_ctx *ctx, amg_arena &ar, const amg_dcsr &F, 
   uint64_t *keys;
   NK_TRY(ar.get(&len, (size_t)nc + 1)); NK_TRY(ar.get(&kptr, (size_t)nc + 1)); NK_TRY(ar.get(&cnt, (size_t)nc + 1));
   NK_TRY(ar.get(&crp, (size_t)nc + 1)); NK_TRY(ar.get(&keys, (size_t)F.nnz + 1));
-  NK_LAUNCH(ctx, k_amg_keycount, amg_g1((int64_t)nc + 1), dim3(NK_BLOCK), (int64_t)nc, W, mem, F.rp, len, (int32_t *)nullptr);
+  NK_LAUNCH(ctx, k_amg_keycount, nk_grid1((int64_t)nc + 1), dim3(NK_BLOCK), (int64_t)nc, W, mem, F.rp, len, (int32_t *)nullptr);
   NK_TRY(amg_scan(ctx, ar, len, kptr, (int64_t)nc + 1));
-  NK_LAUNCH(ctx, k_amg_keysort, amg_g1((int64_t)nc + 1), dim3(NK_BLOCK), (int64_t)nc, W, mem, F.rp, F.ci, cid, (const int32_t *)kptr, keys, cnt);
+  NK_LAUNCH(ctx, k_amg_keysort, nk_grid1((int64_t)nc + 1), dim3(NK_BLOCK), (int64_t)nc, W, mem, F.rp, F.ci, cid, (const int32_t *)kptr, keys, cnt);
   NK_TRY(amg_scan(ctx, ar, cnt, crp, (int64_t)nc + 1));
   int32_t nnzc = 0;
   NK_TRY(amg_fetch_int(ctx, crp + nc, &nnzc));
@@ -611,7 +590,7 @@ static int amg_galerkin_plan_dev(nk_ctx *ctx, amg_arena &ar, const amg_dcsr &F, 
     NK_TRY(ar.get(&gptr, (size_t)nnzc + 2)); NK_TRY(ar.get(&gidx, (size_t)F.nnz + 1));
   }
   out->gptr = gptr; out->gidx = gidx;   // (owned by the caller from here on)
-  NK_LAUNCH(ctx, k_amg_keyfill, amg_g1(nc), dim3(NK_BLOCK), (int64_t)nc, (const int32_t *)kptr, (const uint64_t *)keys, (const int32_t *)crp,
+  NK_LAUNCH(ctx, k_amg_keyfill, nk_grid1(nc), dim3(NK_BLOCK), (int64_t)nc, (const int32_t *)kptr, (const uint64_t *)keys, (const int32_t *)crp,
             cci, gptr, gidx);
   out->nc = nc; out->nnzc = nnzc; out->crp = crp; out->cci = cci;
   return NK_OK;
@@ -631,8 +610,8 @@ static int amg_coarsen_dev(nk_ctx *ctx, amg_arena &ar, const amg_dcsr &F, const 
     } else {
       int32_t *m2;
       NK_TRY(ar.get(&m2, (size_t)nc * 2 * W + 2));
-      NK_LAUNCH(ctx, k_amg_compose, amg_g1(nc), dim3(NK_BLOCK), (int64_t)nc, W, (const int32_t *)mem, (const int32_t *)pair, m2);
-      NK_LAUNCH(ctx, k_amg_map, amg_g1(F.n), dim3(NK_BLOCK), F.n, (const int32_t *)cid, agg);
+      NK_LAUNCH(ctx, k_amg_compose, nk_grid1(nc), dim3(NK_BLOCK), (int64_t)nc, W, (const int32_t *)mem, (const int32_t *)pair, m2);
+      NK_LAUNCH(ctx, k_amg_map, nk_grid1(F.n), dim3(NK_BLOCK), F.n, (const int32_t *)cid, agg);
       mem = m2;
     }
     W *= 2;
@@ -701,11 +680,11 @@ static int amg_setup_device(nk_amg *M, const std::function<void(const char *)> &
     {
       int32_t *len, *rows;
       NK_TRY(ar.get(&len, (size_t)nc + 1)); NK_TRY(ar.get(&rows, (size_t)nc + 1));
-      NK_LAUNCH(ctx, k_amg_keycount, amg_g1((int64_t)nc + 1), dim3(NK_BLOCK), (int64_t)nc, W, (const int32_t *)mem, F.rp, len, rows);
+      NK_LAUNCH(ctx, k_amg_keycount, nk_grid1((int64_t)nc + 1), dim3(NK_BLOCK), (int64_t)nc, W, (const int32_t *)mem, F.rp, len, rows);
       NK_TRY(nk_dev_alloc(&L.d_aggptr, (size_t)nc + 2));
       NK_TRY(nk_dev_alloc(&L.d_aggmem, (size_t)F.n + 1));
       NK_TRY(amg_scan(ctx, ar, rows, L.d_aggptr, (int64_t)nc + 1));
-      NK_LAUNCH(ctx, k_amg_members_fill, amg_g1(nc), dim3(NK_BLOCK), (int64_t)nc, W, (const int32_t *)mem, (const int32_t *)L.d_aggptr, L.d_aggmem);
+      NK_LAUNCH(ctx, k_amg_members_fill, nk_grid1(nc), dim3(NK_BLOCK), (int64_t)nc, W, (const int32_t *)mem, (const int32_t *)L.d_aggptr, L.d_aggmem);
     }
     lap("  level Galerkin plan");
     // the next level's matrix object (its pattern through the host: the SpMV's row-block descriptors are built there)
@@ -752,12 +731,6 @@ void nk_amg_destroy(nk_amg *M) {
   }
   hipFree(M->d_src0); hipFree(M->d_inv); hipFree(M->d_lmax); hipFree(M->d_lpart); hipFree(M->d_fail); hipFree(M->d_nparts);
   delete M;
-}
-template <class T>
-static int upload(nk_ctx *ctx, T **dst, const std::vector<T> &src) {
-  NK_TRY(nk_dev_alloc(dst, src.size() + 1));
-  if (!src.empty()) NK_HIP(nk_memcpy(ctx, *dst, src.data(), src.size() * sizeof(T), hipMemcpyHostToDevice));
-  return NK_OK;
 }
 int nk_amg_create(nk_csr *A, const nk_amg_params *prm, nk_amg **out) {
   nk_ctx *ctx = A->ctx;
@@ -903,14 +876,14 @@ int nk_amg_create(nk_csr *A, const nk_amg_params *prm, nk_amg **out) {
           std::vector<int32_t> fill(gptr.begin(), gptr.end() - 1);
           for (int64_t k = 0; k < L.nnz; ++k) gidx[fill[emap[k]]++] = (int32_t)k;
         }
-        NK_TRY(upload(M->ctx, &L.d_agg, agg));
-        NK_TRY(upload(M->ctx, &L.d_aggptr, aptr));
-        NK_TRY(upload(M->ctx, &L.d_aggmem, amem));
-        NK_TRY(upload(M->ctx, &L.d_gptr, gptr));
-        NK_TRY(upload(M->ctx, &L.d_gidx, gidx));
+        NK_TRY(nk_upload(M->ctx, &L.d_agg, agg));
+        NK_TRY(nk_upload(M->ctx, &L.d_aggptr, aptr));
+        NK_TRY(nk_upload(M->ctx, &L.d_aggmem, amem));
+        NK_TRY(nk_upload(M->ctx, &L.d_gptr, gptr));
+        NK_TRY(nk_upload(M->ctx, &L.d_gidx, gidx));
       }
     }
-    if (has_halo) NK_TRY(upload(M->ctx, &M->d_src0, src0));
+    if (has_halo) NK_TRY(nk_upload(M->ctx, &M->d_src0, src0));
     lap("device objects");
   }
   const int nlev = (int)M->lv.size();
@@ -920,7 +893,7 @@ int nk_amg_create(nk_csr *A, const nk_amg_params *prm, nk_amg **out) {
   M->lpart_stride = 1024;
   M->nparts.assign(nlev, 0);
   for (int l = 0; l < nlev; ++l) M->nparts[l] = M->lv[l].n > 0 ? nk_grid_for(M->lv[l].n, NK_BLOCK, M->lpart_stride) : 0;
-  NK_TRY(upload(M->ctx, &M->d_nparts, M->nparts));
+  NK_TRY(nk_upload(M->ctx, &M->d_nparts, M->nparts));
   NK_TRY(nk_dev_alloc(&M->d_lpart, (size_t)nlev * M->lpart_stride));
   NK_TRY(nk_dev_alloc(&M->d_lmax, (size_t)nlev + 1));
   NK_TRY(nk_dev_alloc(&M->d_fail, (size_t)2));
@@ -978,26 +951,26 @@ int nk_amg_update(nk_amg *M) {
 }
 
 // ----------------------------------------------------------------------------- apply: one V-cycle
-// steps 2 … nsteps of the Chebyshev iteration on level L (the first step is k_amg_cheb_first); the current correction ends in *dcur
-static int amg_cheb_rest(nk_amg *M, amg_level &L, int nsteps, double **dcur, double **dnext, const int *d_skip) {
-  const double lmin = L.lmax / M->prm.cheb_ratio, theta = 0.5 * (L.lmax + lmin), delta = 0.5 * (L.lmax - lmin);
-  const double sigma1 = theta / delta;
-  double rho = 1.0 / sigma1;
-  for (int k = 1; k < nsteps; ++k) {
-    const double rho_new = 1.0 / (2.0 * sigma1 - rho);
-    nk_spmv_epi ep;
-    ep.mode = 1;
-    ep.c1 = rho_new * rho;
-    ep.c2 = 2.0 * rho_new / delta;
-    ep.r = L.r;
-    ep.dnew = *dnext;
-    ep.yacc = L.x;
-    ep.dinv = L.d_dinv;
-    NK_TRY(nk_csr_spmv_dev(L.A, *dcur, nullptr, d_skip, nullptr, &ep));   // r −= A d; d' = c1 d + c2 D⁻¹ r; x += d'
-    std::swap(*dcur, *dnext);
-    rho = rho_new;
-  }
-  return NK_OK;
+// nsteps Chebyshev steps on level L (nk_cheb_run on D⁻¹A, every later step in the SpMV's row epilogue): from x = 0, or from the x
+// whose residual L.r holds; *d_last: where the last correction ended (L.d0 or L.d1)
+static int amg_smooth(nk_amg *M, amg_level &L, int nsteps, bool zero, const int *d_skip, double **d_last = nullptr) {
+  nk_cheb_job job;
+  job.n = L.n;
+  job.lmin = L.lmax / M->prm.cheb_ratio;
+  job.lmax = L.lmax;
+  job.steps = nsteps;
+  job.zero = zero;
+  job.fused = true;
+  job.b = L.b;
+  job.dinv = L.d_dinv;
+  job.r = L.r;
+  job.d = L.d0;
+  job.t = L.d1;
+  job.x = L.x;
+  job.d_skip = d_skip;
+  return nk_cheb_run(M->ctx, job, [&](const double *d, double *, const nk_spmv_epi *ep) {
+    return nk_csr_spmv_dev(L.A, d, nullptr, d_skip, nullptr, ep);   // r −= A d; d' = c1 d + c2 D⁻¹ r; x += d'
+  }, d_last);
 }
 int nk_amg_apply_dev(nk_amg *M, const double *d_b, double *d_x, const int *d_skip) {
   nk_ctx *ctx = M->ctx;
@@ -1010,48 +983,35 @@ int nk_amg_apply_dev(nk_amg *M, const double *d_b, double *d_x, const int *d_ski
   M->lv[0].b = const_cast<double *>(d_b);
   M->lv[0].x = d_x;
   const int nu = M->prm.nu;
-  auto grid = [](int64_t n) { return dim3(nk_grid_for(n, NK_BLOCK * 4, 4096)); };
-  std::vector<double *> dcur(nlev), dnext(nlev);
-  auto coarsest = [&](amg_level &L) -> int {
-    if (M->dense) {
-      NK_LAUNCH(ctx, k_amg_dense_apply, dim3(1), dim3(128), (int)L.n, M->ldinv, (const double *)M->d_inv, (const double *)L.b, L.x, d_skip);
-      return NK_OK;
-    }
-    const double lmin = L.lmax / M->prm.cheb_ratio, theta = 0.5 * (L.lmax + lmin);
-    double *dc = L.d0, *dn = L.d1;
-    NK_LAUNCH(ctx, k_amg_cheb_first, grid(L.n), dim3(NK_BLOCK), L.n, 1, (const double *)L.b, (const double *)L.d_dinv, 1.0 / theta, L.r,
-              dc, L.x, d_skip);
-    return amg_cheb_rest(M, L, 4 * nu, &dc, &dn, d_skip);
-  };
   for (int l = 0; l + 1 < nlev; ++l) {   // ---- down: pre-smooth from zero, residual, restrict
     amg_level &L = M->lv[l];
-    const double lmin = L.lmax / M->prm.cheb_ratio, theta = 0.5 * (L.lmax + lmin);
-    dcur[l] = L.d0; dnext[l] = L.d1;
     nk_prof_scope prof_(ctx, NK_K_OTHER, 40.0 * (double)L.n);
-    NK_LAUNCH(ctx, k_amg_cheb_first, grid(L.n), dim3(NK_BLOCK), L.n, 1, (const double *)L.b, (const double *)L.d_dinv, 1.0 / theta, L.r,
-              dcur[l], L.x, d_skip);
-    NK_TRY(amg_cheb_rest(M, L, nu, &dcur[l], &dnext[l], d_skip));
+    double *d_last = nullptr;
+    NK_TRY(amg_smooth(M, L, nu, true, d_skip, &d_last));
     nk_spmv_epi ep;
-    ep.mode = 4;
+    ep.mode = NK_EPI_RESIDUAL_UPDATE;
     ep.r = L.r;
-    NK_TRY(nk_csr_spmv_dev(L.A, dcur[l], nullptr, d_skip, nullptr, &ep));                  // r −= A d: now r = b − A x
-    NK_LAUNCH(ctx, k_amg_restrict, grid(L.nc), dim3(NK_BLOCK), L.nc, (const int32_t *)L.d_aggptr, (const int32_t *)L.d_aggmem,
-              (const double *)L.r, M->lv[l + 1].b, d_skip);
+    NK_TRY(nk_csr_spmv_dev(L.A, d_last, nullptr, d_skip, nullptr, &ep));                   // r −= A d: now r = b − A x
+    NK_LAUNCH(ctx, k_amg_restrict, dim3(nk_grid_for(L.nc, NK_BLOCK * 4, 4096)), dim3(NK_BLOCK), L.nc, (const int32_t *)L.d_aggptr,
+              (const int32_t *)L.d_aggmem, (const double *)L.r, M->lv[l + 1].b, d_skip);
   }
-  NK_TRY(coarsest(M->lv.back()));
+  {
+    amg_level &L = M->lv.back();
+    if (M->dense)
+      NK_LAUNCH(ctx, k_amg_dense_apply, dim3(1), dim3(128), (int)L.n, M->ldinv, (const double *)M->d_inv, (const double *)L.b, L.x, d_skip);
+    else
+      NK_TRY(amg_smooth(M, L, 4 * nu, true, d_skip));
+  }
   for (int l = nlev - 2; l >= 0; --l) {   // ---- up: over-corrected prolongation, post-smooth
     amg_level &L = M->lv[l];
-    const double lmin = L.lmax / M->prm.cheb_ratio, theta = 0.5 * (L.lmax + lmin);
     nk_prof_scope prof_(ctx, NK_K_OTHER, 40.0 * (double)L.n);
-    NK_LAUNCH(ctx, k_amg_prolong, grid(L.n), dim3(NK_BLOCK), L.n, (const int32_t *)L.d_agg, (const double *)M->lv[l + 1].x,
-              M->prm.overcorrection, L.x, d_skip);
+    NK_LAUNCH(ctx, k_amg_prolong, dim3(nk_grid_for(L.n, NK_BLOCK * 4, 4096)), dim3(NK_BLOCK), L.n, (const int32_t *)L.d_agg,
+              (const double *)M->lv[l + 1].x, M->prm.overcorrection, L.x, d_skip);
     nk_spmv_epi ep;
-    ep.mode = 2;
+    ep.mode = NK_EPI_RESIDUAL;
     ep.r = L.b;
     NK_TRY(nk_csr_spmv_dev(L.A, L.x, L.r, d_skip, nullptr, &ep));                          // r = b − A x
-    NK_LAUNCH(ctx, k_amg_cheb_first, grid(L.n), dim3(NK_BLOCK), L.n, 0, (const double *)L.b, (const double *)L.d_dinv, 1.0 / theta, L.r,
-              dcur[l], L.x, d_skip);
-    NK_TRY(amg_cheb_rest(M, L, nu, &dcur[l], &dnext[l], d_skip));
+    NK_TRY(amg_smooth(M, L, nu, false, d_skip));
   }
   NK_HIP(hipGetLastError());
   return NK_OK;

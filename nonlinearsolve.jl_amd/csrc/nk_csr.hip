@@ -30,19 +30,19 @@ __device__ __forceinline__ int xcd_remap(int bid, int nblk) {
 // branch plus a full `s_waitcnt vmcnt(0)` per element (seen in the ISA: one load in flight per wave). Instead
 // every lane issues ALL its col/val loads unconditionally (the arrays are padded by one tile), then all x
 // gathers (out-of-tile lanes gather x[0]), then the LDS writes — TILE/256 independent loads in flight per lane.
-// Row epilogue. mode 0: y[row] = scale·s. mode 1 (fused Chebyshev step, x = d_old): r −= s; d_new = c1·d_old + c2·r;
+// Row epilogue (nk_epi_mode). PLAIN: y[row] = scale·s. CHEB_STEP (x = d_old): r −= s; d_new = c1·d_old + c2·r;
 // yacc += d_new — saves the separate 56 n-byte vector update and a kernel boundary per polynomial degree (epi.dinv: the step
-// runs on D⁻¹A — the algebraic multigrid's smoother, nk_amg.hip). mode 2: y = b − A x. mode 3: shifted. mode 4: r −= A x.
+// runs on D⁻¹A — the algebraic multigrid's smoother, nk_amg.hip). RESIDUAL: y = b − A x. SHIFTED. RESIDUAL_UPDATE: r −= A x.
 __device__ __forceinline__ void spmv_store_row(int row, double s, double *__restrict__ y, const double *out_scale,
                                                double os, const double *__restrict__ x, const nk_spmv_epi &epi) {
-  if (epi.mode == 0) {
+  if (epi.mode == NK_EPI_PLAIN) {
     y[row] = out_scale ? os * s : s;
-  } else if (epi.mode == 3) {  // Newton-basis step of the s-step Arnoldi process: y = scale·(A x − θ x)
+  } else if (epi.mode == NK_EPI_SHIFTED) {  // Newton-basis step of the s-step Arnoldi process: y = scale·(A x − θ x)
     const double v = s - (*epi.theta) * x[row];
     y[row] = out_scale ? os * v : v;
-  } else if (epi.mode == 2) {  // fused residual: y = b − A x (b = epi.r), as the stencil kernels' mode 2
+  } else if (epi.mode == NK_EPI_RESIDUAL) {  // fused residual: y = b − A x (b = epi.r), as in the stencil kernels
     y[row] = epi.r[row] - s;
-  } else if (epi.mode == 4) {  // residual update only: r −= A x
+  } else if (epi.mode == NK_EPI_RESIDUAL_UPDATE) {  // residual update only: r −= A x
     epi.r[row] -= s;
   } else {                     // Chebyshev step (x = d_old); with epi.dinv on D⁻¹A (the multigrid smoothers)
     const double rr = epi.r[row] - s;
@@ -1094,10 +1094,10 @@ extern "C" int nk_spmv_t(nk_csr *A, const double *x, double *y, int memspace) { 
 extern "C" int nk_spmv_epilogue_test(nk_csr *A, int mode, const double *x, double *y, double *r, double *dnew, double *yacc,
                                      const double *dinv, double c1, double c2, double theta, const double *out_scale) {
   NK_REQUIRE(A && x, "NULL argument");
-  NK_REQUIRE(mode >= 0 && mode <= 4, "mode must be 0 … 4");
-  NK_REQUIRE((mode == 1 || mode == 4) || y != nullptr, "this mode writes y");
-  NK_REQUIRE(mode == 0 || mode == 3 || r != nullptr, "this mode reads r");
-  NK_REQUIRE(mode != 1 || (dnew && yacc), "mode 1 writes dnew and yacc");
+  NK_REQUIRE(mode >= NK_EPI_PLAIN && mode <= NK_EPI_RESIDUAL_UPDATE, "mode must be 0 … 4");
+  NK_REQUIRE((mode == NK_EPI_CHEB_STEP || mode == NK_EPI_RESIDUAL_UPDATE) || y != nullptr, "this mode writes y");
+  NK_REQUIRE(mode == NK_EPI_PLAIN || mode == NK_EPI_SHIFTED || r != nullptr, "this mode reads r");
+  NK_REQUIRE(mode != NK_EPI_CHEB_STEP || (dnew && yacc), "mode 1 writes dnew and yacc");
   nk_ctx *ctx = A->ctx;
   NK_HIP(hipSetDevice(ctx->device));
   const size_t n = (size_t)A->nrows;

@@ -770,6 +770,10 @@ extern "C" int nk_gmres_set_right_preconditioner_host(nk_gmres *G, nk_matvec_fn 
   G->prec_host = fn != nullptr;
   return NK_OK;
 }
+// what the right side falls back to when a built-in preconditioner (polynomial, V-cycle) is removed
+static int prec_without_builtin(const nk_gmres *G) {
+  return G->rprec_obj ? NK_PREC_OBJECT : (G->prec ? NK_PREC_CALLBACK : NK_PREC_NONE);
+}
 extern "C" int nk_gmres_set_right_preconditioner(nk_gmres *G, nk_matvec_fn fn, void *user) {
   if (G) G->ahead.valid = false;   // (a cycle begin run ahead of the next solve belongs to the old setting)
   NK_REQUIRE(G, "NULL argument");
@@ -777,7 +781,7 @@ extern "C" int nk_gmres_set_right_preconditioner(nk_gmres *G, nk_matvec_fn fn, v
   G->prec_user = user;
   G->prec_host = false;
   G->rprec_obj = nullptr;
-  G->prec_kind = fn ? 1 : 0;
+  G->prec_kind = fn ? NK_PREC_CALLBACK : NK_PREC_NONE;
   if (fn && !G->z) NK_TRY(nk_dev_alloc(&G->z, (size_t)G->ldv));
   return NK_OK;
 }
@@ -790,7 +794,7 @@ extern "C" int nk_gmres_set_left_preconditioner(nk_gmres *G, nk_matvec_fn fn, vo
   G->lprec_user = user;
   G->lprec_host = false;
   G->lprec_obj = nullptr;
-  G->lprec_kind = fn ? 1 : 0;
+  G->lprec_kind = fn ? NK_PREC_CALLBACK : NK_PREC_NONE;
   if (fn && !G->lz) NK_TRY(nk_dev_alloc(&G->lz, (size_t)G->ldv));
   return NK_OK;
 }
@@ -812,13 +816,13 @@ extern "C" int nk_gmres_set_preconditioner(nk_gmres *G, int side, nk_precond *P)
     G->lprec = nullptr;
     G->lprec_host = false;
     G->lprec_obj = P;
-    G->lprec_kind = P ? 4 : 0;
+    G->lprec_kind = P ? NK_PREC_OBJECT : NK_PREC_NONE;
     if (P && !G->lz) NK_TRY(nk_dev_alloc(&G->lz, (size_t)G->ldv));
   } else {
     G->prec = nullptr;
     G->prec_host = false;
     G->rprec_obj = P;
-    G->prec_kind = P ? 4 : 0;
+    G->prec_kind = P ? NK_PREC_OBJECT : NK_PREC_NONE;
     if (P && !G->z) NK_TRY(nk_dev_alloc(&G->z, (size_t)G->ldv));
   }
   return NK_OK;
@@ -844,7 +848,7 @@ extern "C" int nk_gmres_set_normal_form_damping(nk_gmres *G, const double *d_dia
 __global__ __launch_bounds__(NK_BLOCK) void k_add_diag_scale(int64_t n, double lambda, const double *__restrict__ d,
                                                              const double *__restrict__ x, double *__restrict__ y,
                                                              const double *d_scale, const int *d_skip) {
-  if (d_skip != nullptr && *d_skip != 0) return;
+  if (nk_skip(d_skip)) return;
   const double sc = d_scale ? *d_scale : 1.0;
   const int64_t stride = (int64_t)gridDim.x * NK_BLOCK;
   for (int64_t i = (int64_t)blockIdx.x * NK_BLOCK + threadIdx.x; i < n; i += stride)
@@ -867,7 +871,7 @@ extern "C" int nk_gmres_set_shift_weights(nk_gmres *G, const double *d_m) {
 __global__ __launch_bounds__(NK_BLOCK) void k_add_shift(int64_t n, double sigma, const double *__restrict__ m,
                                                         const double *__restrict__ x, double *__restrict__ y,
                                                         const double *d_scale, const int *d_skip) {
-  if (d_skip != nullptr && *d_skip != 0) return;
+  if (nk_skip(d_skip)) return;
   const double c = sigma * (d_scale ? *d_scale : 1.0);
   const int64_t stride = (int64_t)gridDim.x * NK_BLOCK;
   if (m == nullptr)
@@ -926,80 +930,26 @@ static int op_apply_raw_unshifted(nk_gmres *G, const double *src, double *d_y, c
 // (Saad, Iterative Methods, Alg. 12.1). Operator applications only — no inner products, hence no all-reduce on
 // multi-GPU — and it reuses the fastest kernel of the library (SpMV / fused JVP). The `precs` hook of the
 // reference (test/Core/core_tests__item21.jl) is where a user would plug such a preconditioner in.
-__global__ __launch_bounds__(NK_BLOCK) void k_cheb_init(int64_t n, const double *__restrict__ v, double inv_theta,
-                                                        double *__restrict__ r, double *__restrict__ d,
-                                                        double *__restrict__ y, const int *d_skip) {
-  if (d_skip != nullptr && *d_skip != 0) return;
-  const int64_t stride = (int64_t)gridDim.x * NK_BLOCK;
-  for (int64_t i = (int64_t)blockIdx.x * NK_BLOCK + threadIdx.x; i < n; i += stride) {
-    const double x = v[i], dd = x * inv_theta;
-    r[i] = x;
-    d[i] = dd;
-    y[i] = dd;
-  }
-}
-// r −= A d ; d = c1 d + c2 r ; y += d      (56 n bytes)
-__global__ __launch_bounds__(NK_BLOCK) void k_cheb_update(int64_t n, const double *__restrict__ Ad, double c1, double c2,
-                                                          double *__restrict__ r, double *__restrict__ d,
-                                                          double *__restrict__ y, const int *d_skip) {
-  if (d_skip != nullptr && *d_skip != 0) return;
-  const int64_t npair = n >> 1, stride = (int64_t)gridDim.x * NK_BLOCK;
-  for (int64_t i = (int64_t)blockIdx.x * NK_BLOCK + threadIdx.x; i < npair; i += stride) {
-    const double2 t = reinterpret_cast<const double2 *>(Ad)[i];
-    double2 rr = reinterpret_cast<double2 *>(r)[i], dd = reinterpret_cast<double2 *>(d)[i],
-            yy = reinterpret_cast<double2 *>(y)[i];
-    rr.x -= t.x; rr.y -= t.y;
-    dd.x = c1 * dd.x + c2 * rr.x; dd.y = c1 * dd.y + c2 * rr.y;
-    yy.x += dd.x; yy.y += dd.y;
-    reinterpret_cast<double2 *>(r)[i] = rr;
-    reinterpret_cast<double2 *>(d)[i] = dd;
-    reinterpret_cast<double2 *>(y)[i] = yy;
-  }
-  if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) {
-    const int64_t i = n - 1;
-    r[i] -= Ad[i];
-    d[i] = c1 * d[i] + c2 * r[i];
-    y[i] += d[i];
-  }
-}
-
 static int cheb_apply(nk_gmres *G, const double *src, double *dst, const int *d_skip) {
-  nk_ctx *ctx = G->ctx;
-  const int64_t n = G->n;
-  const double theta = 0.5 * (G->cheb_lmax + G->cheb_lmin), delta = 0.5 * (G->cheb_lmax - G->cheb_lmin);
-  const double sigma1 = theta / delta;
-  double rho = 1.0 / sigma1;
-  const int grid = nk_grid_for(n >> 1, NK_BLOCK * 2, 4096);
-  {
-    nk_prof_scope prof_(ctx, NK_K_OTHER, 32.0 * (double)n);
-    NK_LAUNCH(ctx, k_cheb_init, dim3(grid), dim3(NK_BLOCK), n, src, 1.0 / theta, G->cr, G->cd, dst, d_skip);
-  }
-  // concrete CSR operator: the vector update rides in the SpMV's row epilogue (d ping-pongs between two buffers)
-  const bool fuse = !G->normal && G->shift == 0.0 && ((G->op_kind == 1) || (G->op_kind == 2 && G->P->kind == NK_PROBLEM_BRATU2D));
-  double *dcur = G->cd, *dnext = G->cd2;
-  for (int k = 1; k < G->cheb_degree; ++k) {
-    const double rho_new = 1.0 / (2.0 * sigma1 - rho);
-    if (fuse) {
-      nk_spmv_epi ep;
-      ep.mode = 1;
-      ep.c1 = rho_new * rho;
-      ep.c2 = 2.0 * rho_new / delta;
-      ep.r = G->cr;
-      ep.dnew = dnext;
-      ep.yacc = dst;
-      if (G->op_kind == 1) NK_TRY(nk_csr_spmv_dev(G->A, dcur, nullptr, d_skip, nullptr, &ep));
-      else NK_TRY(nk_problem_jvp_dev(G->P, G->d_u, dcur, nullptr, d_skip, nullptr, &ep));
-      double *tmp = dcur; dcur = dnext; dnext = tmp;
-    } else {
-      NK_TRY(op_apply_raw(G, G->cd, G->ct, d_skip, nullptr));
-      nk_prof_scope prof_(ctx, NK_K_OTHER, 56.0 * (double)n);
-      NK_LAUNCH(ctx, k_cheb_update, dim3(grid), dim3(NK_BLOCK), n, (const double *)G->ct, rho_new * rho,
-                2.0 * rho_new / delta, G->cr, G->cd, dst, d_skip);
-    }
-    rho = rho_new;
-  }
-  NK_HIP(hipGetLastError());
-  return NK_OK;
+  nk_cheb_job job;
+  job.n = G->n;
+  job.lmin = G->cheb_lmin;
+  job.lmax = G->cheb_lmax;
+  job.steps = G->cheb_degree;
+  // concrete CSR operator / Bratu stencil: the vector update rides in the row epilogue (d ping-pongs between cd and cd2)
+  job.fused = !G->normal && G->shift == 0.0 && ((G->op_kind == 1) || (G->op_kind == 2 && G->P->kind == NK_PROBLEM_BRATU2D));
+  job.b = src;
+  job.r = G->cr;
+  job.d = G->cd;
+  job.t = job.fused ? G->cd2 : G->ct;
+  job.x = dst;
+  job.d_skip = d_skip;
+  nk_prof_scope prof_(G->ctx, NK_K_OTHER, 32.0 * (double)G->n);   // (the first step's sweep)
+  return nk_cheb_run(G->ctx, job, [&](const double *d, double *t, const nk_spmv_epi *ep) {
+    if (!ep) return op_apply_raw(G, d, t, d_skip, nullptr);
+    if (G->op_kind == 1) return nk_csr_spmv_dev(G->A, d, nullptr, d_skip, nullptr, ep);
+    return nk_problem_jvp_dev(G->P, G->d_u, d, nullptr, d_skip, nullptr, ep);
+  });
 }
 
 // start vector with energy in every mode (a constant vector has none in the oscillatory ones)
@@ -1096,7 +1046,7 @@ extern "C" int nk_gmres_set_chebyshev_preconditioner(nk_gmres *G, int degree, do
   NK_REQUIRE(G, "NULL argument");
   NK_REQUIRE(G->op_kind != 0, "set the operator before the preconditioner");
   if (degree <= 0) {
-    G->prec_kind = G->rprec_obj ? 4 : (G->prec ? 1 : 0);
+    G->prec_kind = prec_without_builtin(G);
     return NK_OK;
   }
   NK_HIP(hipSetDevice(G->ctx->device));
@@ -1117,7 +1067,7 @@ extern "C" int nk_gmres_set_chebyshev_preconditioner(nk_gmres *G, int degree, do
   G->cheb_degree = degree;
   G->cheb_lmin = lambda_min;
   G->cheb_lmax = lambda_max;
-  G->prec_kind = 2;
+  G->prec_kind = NK_PREC_CHEBYSHEV;
   return NK_OK;
 }
 extern "C" int nk_gmres_get_chebyshev_interval(nk_gmres *G, double *lambda_min, double *lambda_max) {
@@ -1135,7 +1085,7 @@ extern "C" int nk_gmres_set_multigrid_preconditioner(nk_gmres *G, nk_problem *P,
   if (G) G->ahead.valid = false;   // (a cycle begin run ahead of the next solve belongs to the old setting)
   NK_REQUIRE(G, "NULL argument");
   if (nu <= 0 || !P) {  // remove
-    G->prec_kind = G->rprec_obj ? 4 : (G->prec ? 1 : 0);
+    G->prec_kind = prec_without_builtin(G);
     return NK_OK;
   }
   NK_REQUIRE(u, "NULL argument");
@@ -1152,12 +1102,12 @@ extern "C" int nk_gmres_set_multigrid_preconditioner(nk_gmres *G, nk_problem *P,
     if (G->mg) {   // (the object serves the problem of the last call: a hierarchy of the other kind goes)
       nk_mg_destroy(G->mg);
       G->mg = nullptr;
-      if (G->prec_kind == 3) G->prec_kind = G->rprec_obj ? 4 : (G->prec ? 1 : 0);
+      if (G->prec_kind == NK_PREC_MULTIGRID) G->prec_kind = prec_without_builtin(G);
     }
     if (G->gmg && !nk_gridmg_matches(G->gmg, P, nu, coarse_max)) {   // another problem, nu or coarse_max: built again
       nk_gridmg_destroy(G->gmg);
       G->gmg = nullptr;
-      if (G->prec_kind == 3) G->prec_kind = G->rprec_obj ? 4 : (G->prec ? 1 : 0);
+      if (G->prec_kind == NK_PREC_MULTIGRID) G->prec_kind = prec_without_builtin(G);
     }
     if (!G->gmg) NK_TRY(nk_gridmg_create(P, nu, coarse_max, &G->gmg));
     NK_TRY(nk_gridmg_update(G->gmg, du));
@@ -1165,14 +1115,14 @@ extern "C" int nk_gmres_set_multigrid_preconditioner(nk_gmres *G, nk_problem *P,
     if (G->gmg) {
       nk_gridmg_destroy(G->gmg);
       G->gmg = nullptr;
-      if (G->prec_kind == 3) G->prec_kind = G->rprec_obj ? 4 : (G->prec ? 1 : 0);
+      if (G->prec_kind == NK_PREC_MULTIGRID) G->prec_kind = prec_without_builtin(G);
     }
     if (!G->mg) NK_TRY(nk_mg_create(P, nu, coarse_max, &G->mg));
     NK_TRY(nk_problem_jvp_prepare(P, du));
     NK_TRY(nk_mg_update(G->mg, du));
   }
   if (!G->z) NK_TRY(nk_dev_alloc(&G->z, (size_t)G->ldv));
-  G->prec_kind = 3;
+  G->prec_kind = NK_PREC_MULTIGRID;
   return NK_OK;
 }
 
@@ -1202,15 +1152,15 @@ extern "C" int nk_gmres_multigrid_level_field(nk_gmres *G, int level, int k, dou
 }
 
 static int lprec_apply(nk_gmres *G, const double *src, double *dst, const int *d_skip) {
-  if (G->lprec_kind == 4) return nk_precond_apply_dev(G->lprec_obj, src, dst, d_skip);
+  if (G->lprec_kind == NK_PREC_OBJECT) return nk_precond_apply_dev(G->lprec_obj, src, dst, d_skip);
   if (G->lprec_host) return host_callback(G, G->lprec, G->lprec_user, src, dst, "left preconditioner");
   if (G->lprec(G->lprec_user, src, dst, (void *)G->ctx->stream) != 0) NK_FAIL(NK_E_CALLBACK, "left preconditioner failed");
   return NK_OK;
 }
 static int prec_apply(nk_gmres *G, const double *src, double *dst, const int *d_skip) {
-  if (G->prec_kind == 2) return cheb_apply(G, src, dst, d_skip);
-  if (G->prec_kind == 3) return G->gmg ? nk_gridmg_apply(G->gmg, src, dst, d_skip) : nk_mg_apply(G->mg, src, dst, d_skip);
-  if (G->prec_kind == 4) return nk_precond_apply_dev(G->rprec_obj, src, dst, d_skip);
+  if (G->prec_kind == NK_PREC_CHEBYSHEV) return cheb_apply(G, src, dst, d_skip);
+  if (G->prec_kind == NK_PREC_MULTIGRID) return G->gmg ? nk_gridmg_apply(G->gmg, src, dst, d_skip) : nk_mg_apply(G->mg, src, dst, d_skip);
+  if (G->prec_kind == NK_PREC_OBJECT) return nk_precond_apply_dev(G->rprec_obj, src, dst, d_skip);
   if (G->prec_host) return host_callback(G, G->prec, G->prec_user, src, dst, "preconditioner");
   if (G->prec(G->prec_user, src, dst, (void *)G->ctx->stream) != 0) NK_FAIL(NK_E_CALLBACK, "preconditioner failed");
   return NK_OK;
@@ -1228,7 +1178,7 @@ static bool op_fuses_scale(const nk_gmres *G) {
 __global__ __launch_bounds__(NK_BLOCK) void k_sub_theta(int64_t n, const double *__restrict__ theta,
                                                         const double *__restrict__ x, double *__restrict__ y,
                                                         const double *d_scale, const int *d_skip) {
-  if (d_skip != nullptr && *d_skip != 0) return;
+  if (nk_skip(d_skip)) return;
   const double c = (*theta) * (d_scale ? *d_scale : 1.0);
   const int64_t stride = (int64_t)gridDim.x * NK_BLOCK;
   for (int64_t i = (int64_t)blockIdx.x * NK_BLOCK + threadIdx.x; i < n; i += stride) y[i] -= c * x[i];
@@ -1256,7 +1206,7 @@ static int op_apply(nk_gmres *G, const double *d_x, double *d_y, const int *d_sk
                         (G->op_kind == 1 || (G->op_kind == 2 && G->P->kind == NK_PROBLEM_BRATU2D));
     if (epi_ok) {
       nk_spmv_epi ep;
-      ep.mode = 3;
+      ep.mode = NK_EPI_SHIFTED;
       ep.theta = d_theta;
       if (G->op_kind == 1) return nk_csr_spmv_dev(G->A, src, d_y, d_skip, oscale, &ep);
       return nk_problem_jvp_dev(G->P, G->d_u, src, d_y, d_skip, oscale, &ep);
@@ -1353,8 +1303,7 @@ extern "C" int nk_gmres_set_sstep_basis(nk_gmres *G, int basis) {
 // eligible: built-in linear operators (they take the un-normalised pending column as it is) and no callback preconditioner
 static bool dcgs2r_eligible(const nk_gmres *G) {
   const bool op_ok = (G->op_kind == 1) || (G->op_kind == 2 && G->P->kind != NK_PROBLEM_USER);
-  return op_ok && (G->prec_kind == 0 || G->prec_kind == 2 || G->prec_kind == 3 || G->prec_kind == 4) &&
-         (G->lprec_kind == 0 || G->lprec_kind == 4) && G->m <= NK_MAX_NV - 2 &&
+  return op_ok && G->prec_kind != NK_PREC_CALLBACK && G->lprec_kind != NK_PREC_CALLBACK && G->m <= NK_MAX_NV - 2 &&
          G->n <= (int64_t)NK_MAX_ROW_TILES * NK_BLOCK * 8;
 }
 static bool use_dcgs2r(const nk_gmres *G) {
@@ -1694,7 +1643,7 @@ static int gmres_solve_once(nk_gmres *G, const double *d_b, double *d_x, int use
       NK_TRY(nk_ss_cycle(G, steps, wait_progress, &ss_backsolved));
     } else {
       const bool one_red = use_dcgs2r(G);
-      const int ahead = (fixed_iters > 0 || G->run_ahead <= 0) ? 0 : (G->prec_kind == 3 ? 1 : G->run_ahead);
+      const int ahead = (fixed_iters > 0 || G->run_ahead <= 0) ? 0 : (G->prec_kind == NK_PREC_MULTIGRID ? 1 : G->run_ahead);
       // Every rank must enqueue the SAME number of steps (each carries collectives): the stop is therefore not "when this
       // host happens to see `done`" but a function of K, the number of columns closed when the device raised it — a value
       // all ranks compute identically. A host is never more than ahead + one_red steps past the step that closes column K,

@@ -16,7 +16,7 @@
 //              weights on one coarse node added. Restriction = the row-normalised transpose, for residuals, u and fields alike.
 //              Components one by one (vectors are component-major). One pair of kernels for 2-D and 3-D (2-D: nz = 1).
 //   smoother   ν Chebyshev steps on D⁻¹A_l over [ρ/4, ρ], ρ = max_i Σ_j |a_ij| / |a_ii| computed on the device at every update
-//              (a maximum needs no summation order). The recurrence of k_mg_cheb_first / k_mg_cheb_step with r replaced by
+//              (a maximum needs no summation order). The recurrence of nk_cheb_run (coefficients: nk_cheb.h) with r replaced by
 //              D⁻¹r: the sign of a negative-definite operator and the scales of several components need no special case. One
 //              step is ONE launch: CSR row product, b − A x, the division by a_ii, the updates of d and x; x ping-pongs between
 //              two buffers so that no row reads a value another row has replaced.
@@ -38,6 +38,7 @@
 #include <vector>
 
 #include "nk_internal.h"
+#include "nk_cheb.h"
 
 // coarse_max when the caller names none (< 3): the sweep is in DESIGN.md §6f addendum 7
 constexpr int NK_GRIDMG_COARSE_MAX_DEFAULT = 8;
@@ -119,9 +120,6 @@ struct nk_gridmg {
 };
 
 // ----------------------------------------------------------------------------- kernels
-#define GMG_SKIP(p) if ((p) != nullptr && *(p) != 0) return
-static inline dim3 gmg_grid(int64_t n) { return dim3((unsigned)((n + NK_BLOCK - 1) / NK_BLOCK)); }
-
 struct gmg_dims { int nx, ny, nz, cx, cy, cz; };   // fine and coarse sides (2-D: nz = cz = 1)
 
 // x_f += P e_c, one fine unknown per thread: the tensor product of the (at most) two entries per axis. A missing entry has the
@@ -131,7 +129,7 @@ __global__ __launch_bounds__(NK_BLOCK) void k_gmg_prolong_add(gmg_dims g, int nc
                                                               const double *__restrict__ wy, const int32_t *__restrict__ iz,
                                                               const double *__restrict__ wz, const double *__restrict__ ec,
                                                               double *__restrict__ xf, const int *d_skip) {
-  GMG_SKIP(d_skip);
+  if (nk_skip(d_skip)) return;
   const int nnf = g.nx * g.ny * g.nz, nnc = g.cx * g.cy * g.cz;
   const int e = (int)blockIdx.x * NK_BLOCK + (int)threadIdx.x;
   if (e >= ncomp * nnf) return;
@@ -162,7 +160,7 @@ __global__ __launch_bounds__(NK_BLOCK) void k_gmg_restrict(gmg_dims g, int ncomp
                                                            const int32_t *__restrict__ jz, const double *__restrict__ wz,
                                                            const double *__restrict__ rf, double *__restrict__ rc,
                                                            const int *d_skip) {
-  GMG_SKIP(d_skip);
+  if (nk_skip(d_skip)) return;
   const int nnf = g.nx * g.ny * g.nz, nnc = g.cx * g.cy * g.cz;
   const int e = (int)blockIdx.x * NK_BLOCK + (int)threadIdx.x;
   if (e >= ncomp * nnc) return;
@@ -190,7 +188,7 @@ __global__ __launch_bounds__(NK_BLOCK) void k_gmg_smooth(int n, const int32_t *_
                                                          const double *__restrict__ b, const double *__restrict__ xin,
                                                          double *__restrict__ d, double *__restrict__ xout, double c1, double c2,
                                                          int first, int zero, const int *d_skip) {
-  GMG_SKIP(d_skip);
+  if (nk_skip(d_skip)) return;
   const int i = (int)blockIdx.x * NK_BLOCK + (int)threadIdx.x;
   if (i >= n) return;
   double s = 0.0, xi = 0.0;
@@ -209,7 +207,7 @@ __global__ __launch_bounds__(NK_BLOCK) void k_gmg_smooth(int n, const int32_t *_
 __global__ __launch_bounds__(NK_BLOCK) void k_gmg_residual(int n, const int32_t *__restrict__ rowptr, const int32_t *__restrict__ col,
                                                            const double *__restrict__ val, const double *__restrict__ b,
                                                            const double *__restrict__ x, double *__restrict__ r, const int *d_skip) {
-  GMG_SKIP(d_skip);
+  if (nk_skip(d_skip)) return;
   const int i = (int)blockIdx.x * NK_BLOCK + (int)threadIdx.x;
   if (i >= n) return;
   double s = 0.0;
@@ -273,13 +271,6 @@ void nk_gridmg_destroy(nk_gridmg *M) {
   delete M;
 }
 
-template <class T>
-static int gmg_upload(nk_ctx *ctx, T **dst, const std::vector<T> &src) {
-  NK_TRY(nk_dev_alloc(dst, src.size()));
-  NK_HIP(nk_memcpy(ctx, *dst, src.data(), src.size() * sizeof(T), hipMemcpyHostToDevice));
-  return NK_OK;
-}
-
 // the tables of one axis on the device; coarsen = false: the identity (the axis keeps its side)
 static int gmg_axis_make(nk_ctx *ctx, int n, int lo, int hi, bool coarsen, gmg_axis *out) {
   std::vector<int32_t> idx((size_t)2 * n, -1);
@@ -310,11 +301,11 @@ static int gmg_axis_make(nk_ctx *ctx, int n, int lo, int hi, bool coarsen, gmg_a
     }
   out->n = n;
   out->nc = (int)nc;
-  NK_TRY(gmg_upload(ctx, &out->pidx, idx));
-  NK_TRY(gmg_upload(ctx, &out->pw, w));
-  NK_TRY(gmg_upload(ctx, &out->rptr, rptr));
-  NK_TRY(gmg_upload(ctx, &out->ridx, ridx));
-  NK_TRY(gmg_upload(ctx, &out->rw, rw));
+  NK_TRY(nk_upload(ctx, &out->pidx, idx));
+  NK_TRY(nk_upload(ctx, &out->pw, w));
+  NK_TRY(nk_upload(ctx, &out->rptr, rptr));
+  NK_TRY(nk_upload(ctx, &out->ridx, ridx));
+  NK_TRY(nk_upload(ctx, &out->rw, rw));
   return NK_OK;
 }
 
@@ -390,7 +381,7 @@ static gmg_dims gmg_dims_of(const gmg_level &F, const gmg_level &C) {
 }
 static int gmg_restrict(nk_gridmg *M, gmg_level &F, gmg_level &C, int ncomp, const double *src, double *dst, const int *d_skip) {
   const gmg_axis *a = F.ax;
-  NK_LAUNCH(M->ctx, k_gmg_restrict, gmg_grid(C.nn * ncomp), dim3(NK_BLOCK), gmg_dims_of(F, C), ncomp, (const int32_t *)a[0].rptr,
+  NK_LAUNCH(M->ctx, k_gmg_restrict, nk_grid1(C.nn * ncomp), dim3(NK_BLOCK), gmg_dims_of(F, C), ncomp, (const int32_t *)a[0].rptr,
             (const int32_t *)a[0].ridx, (const double *)a[0].rw, (const int32_t *)a[1].rptr, (const int32_t *)a[1].ridx,
             (const double *)a[1].rw, (const int32_t *)a[2].rptr, (const int32_t *)a[2].ridx, (const double *)a[2].rw, src, dst, d_skip);
   NK_HIP(hipGetLastError());
@@ -398,7 +389,7 @@ static int gmg_restrict(nk_gridmg *M, gmg_level &F, gmg_level &C, int ncomp, con
 }
 static int gmg_prolong_add(nk_gridmg *M, gmg_level &F, gmg_level &C, const double *ec, double *xf, const int *d_skip) {
   const gmg_axis *a = F.ax;
-  NK_LAUNCH(M->ctx, k_gmg_prolong_add, gmg_grid(F.n), dim3(NK_BLOCK), gmg_dims_of(F, C), M->dof, (const int32_t *)a[0].pidx,
+  NK_LAUNCH(M->ctx, k_gmg_prolong_add, nk_grid1(F.n), dim3(NK_BLOCK), gmg_dims_of(F, C), M->dof, (const int32_t *)a[0].pidx,
             (const double *)a[0].pw, (const int32_t *)a[1].pidx, (const double *)a[1].pw, (const int32_t *)a[2].pidx,
             (const double *)a[2].pw, ec, xf, d_skip);
   NK_HIP(hipGetLastError());
@@ -428,7 +419,7 @@ int nk_gridmg_update(nk_gridmg *M, const double *d_u) {
   for (int l = 0; l < nl; ++l) {
     gmg_level &L = M->lv[l];
     NK_TRY(nk_problem_jac_values_dev(L.P, L.u, L.A));
-    NK_LAUNCH(ctx, k_gmg_diag, gmg_grid(L.n), dim3(NK_BLOCK), (int)L.n, (const int32_t *)L.A->d_rowptr, (const int32_t *)L.A->d_col,
+    NK_LAUNCH(ctx, k_gmg_diag, nk_grid1(L.n), dim3(NK_BLOCK), (int)L.n, (const int32_t *)L.A->d_rowptr, (const int32_t *)L.A->d_col,
               (const double *)L.A->d_val, L.dinv, M->d_stat + l);
   }
   NK_HIP(hipGetLastError());
@@ -454,20 +445,13 @@ int nk_gridmg_update(nk_gridmg *M, const double *d_u) {
 // last step may be told to write into `last_out` instead
 static int gmg_smooth(nk_gridmg *M, gmg_level &L, const double *b, bool zero_guess, double **x, double *last_out, const int *d_skip) {
   nk_ctx *ctx = M->ctx;
-  const double lmax = L.rho, lmin = lmax / 4.0;
-  const double theta = 0.5 * (lmax + lmin), delta = 0.5 * (lmax - lmin), sigma = theta / delta;
-  double rho = 1.0 / sigma;
+  nk_cheb_coef co(L.rho / 4.0, L.rho);
   double *cur = *x;
   for (int k = 0; k < M->nu; ++k) {
-    double c1 = 0.0, c2 = 1.0 / theta;
-    if (k > 0) {
-      const double rho_new = 1.0 / (2.0 * sigma - rho);
-      c1 = rho_new * rho;
-      c2 = 2.0 * rho_new / delta;
-      rho = rho_new;
-    }
+    double c1 = 0.0, c2 = co.inv_theta();
+    if (k > 0) co.next(&c1, &c2);
     double *nxt = (k == M->nu - 1 && last_out) ? last_out : (cur == L.xa ? L.xb : L.xa);
-    NK_LAUNCH(ctx, k_gmg_smooth, gmg_grid(L.n), dim3(NK_BLOCK), (int)L.n, (const int32_t *)L.A->d_rowptr, (const int32_t *)L.A->d_col,
+    NK_LAUNCH(ctx, k_gmg_smooth, nk_grid1(L.n), dim3(NK_BLOCK), (int)L.n, (const int32_t *)L.A->d_rowptr, (const int32_t *)L.A->d_col,
               (const double *)L.A->d_val, (const double *)L.dinv, b, (const double *)cur, L.d, nxt, c1, c2, k == 0 ? 1 : 0,
               (zero_guess && k == 0) ? 1 : 0, d_skip);
     cur = nxt;
@@ -492,7 +476,7 @@ int nk_gridmg_apply(nk_gridmg *M, const double *src, double *dst, const int *d_s
     const double *b = l == 0 ? src : F.b;
     x[l] = F.xa;
     NK_TRY(gmg_smooth(M, F, b, true, &x[l], nullptr, d_skip));
-    NK_LAUNCH(ctx, k_gmg_residual, gmg_grid(F.n), dim3(NK_BLOCK), (int)F.n, (const int32_t *)F.A->d_rowptr, (const int32_t *)F.A->d_col,
+    NK_LAUNCH(ctx, k_gmg_residual, nk_grid1(F.n), dim3(NK_BLOCK), (int)F.n, (const int32_t *)F.A->d_rowptr, (const int32_t *)F.A->d_col,
               (const double *)F.A->d_val, b, (const double *)x[l], F.r, d_skip);
     NK_TRY(gmg_restrict(M, F, C, M->dof, F.r, C.b, d_skip));
   }

@@ -232,15 +232,17 @@ int nk_comm_alltoallv(nk_ctx *ctx, const void *send, const int64_t *soff, const 
                       void *recv, const int64_t *roff, const int64_t *rbytes, hipStream_t stream = nullptr /* ctx->stream */);
 void nk_comm_destroy(nk_ctx *ctx);
 
-// optional row epilogue of the SpMV / JVP kernels: mode 1 fuses one Chebyshev-iteration vector update, mode 2 (stencil JVP
-// only) the residual b − J v, mode 3 a shift read from device memory: y = scale·(A x − θ x) — one step of the s-step Arnoldi
-// process's Newton basis (nk_sstep.hip); x[row] is the diagonal gather the row has just made, so the shift moves no extra bytes
+// optional row epilogue of the SpMV / JVP kernels: NK_EPI_CHEB_STEP fuses one Chebyshev-iteration vector update, NK_EPI_RESIDUAL
+// the residual b − A x, NK_EPI_SHIFTED a shift read from device memory: y = scale·(A x − θ x) — one step of the s-step Arnoldi
+// process's Newton basis (nk_sstep.hip); x[row] is the diagonal gather the row has just made, so the shift moves no extra bytes.
+// NK_EPI_RESIDUAL_UPDATE (CSR kernel only): r −= A x. (The values are what nk_spmv_epilogue_test takes from Python.)
+enum nk_epi_mode { NK_EPI_PLAIN = 0, NK_EPI_CHEB_STEP = 1, NK_EPI_RESIDUAL = 2, NK_EPI_SHIFTED = 3, NK_EPI_RESIDUAL_UPDATE = 4 };
 struct nk_spmv_epi {
-  int mode = 0;
+  int mode = NK_EPI_PLAIN;
   double c1 = 0, c2 = 0;
   double *r = nullptr, *dnew = nullptr, *yacc = nullptr;
   const double *theta = nullptr;
-  const double *dinv = nullptr;   // mode 1 (CSR kernel): the step runs on D⁻¹A. CSR modes 2 / 4: y = r − A x / r −= A x
+  const double *dinv = nullptr;   // NK_EPI_CHEB_STEP (CSR kernel): the step runs on D⁻¹A
 };
 
 // ----------------------------------------------------------------------------- halo plan
@@ -554,6 +556,9 @@ struct nk_ss_fix {
   // D = C₂ R₂⁻¹ (k0 × sb), left by the workgroup that derives the block's Hessenberg columns
   const double *Wi[NK_SS_NFIX], *D[NK_SS_NFIX];
 };
+// what sits on a side of the operator (nk_gmres::prec_kind / lprec_kind)
+enum nk_prec_kind { NK_PREC_NONE = 0, NK_PREC_CALLBACK, NK_PREC_CHEBYSHEV /* built-in polynomial */, NK_PREC_MULTIGRID /* built-in V-cycle */,
+                    NK_PREC_OBJECT /* nk_precond */ };
 struct nk_gmres {
   nk_ctx *ctx = nullptr;
   int64_t n = 0, ldv = 0;
@@ -593,10 +598,10 @@ struct nk_gmres {
   const double *d_shift_w = nullptr;  // m (borrowed, local rows); NULL = identity
   bool fn_host = false, prec_host = false;  // the callbacks take HOST pointers: vectors are staged through h_stage
   double *h_stage = nullptr;                // pinned, 2 n doubles
-  int prec_kind = 0;  // 0 none, 1 callback, 2 built-in Chebyshev polynomial, 3 built-in multigrid V-cycle, 4 nk_precond object
+  int prec_kind = NK_PREC_NONE;
   struct nk_precond *rprec_obj = nullptr;
   // left preconditioner: Arnoldi runs on Pl⁻¹ A Pr⁻¹, residual norms are the preconditioned ones
-  int lprec_kind = 0; // 0 none, 1 callback, 4 nk_precond object
+  int lprec_kind = NK_PREC_NONE;   // NK_PREC_NONE, _CALLBACK or _OBJECT
   nk_matvec_fn lprec = nullptr;
   void *lprec_user = nullptr;
   bool lprec_host = false;
@@ -973,3 +978,38 @@ static inline int nk_grid_for(int64_t work_items, int per_block, int max_blocks)
   if (b > max_blocks) b = max_blocks;
   return (int)b;
 }
+// one thread per work item (kernels that return on i >= n), at least one workgroup
+static inline dim3 nk_grid1(int64_t n) { return dim3((unsigned)nk_grid_for(n, NK_BLOCK, INT32_MAX)); }
+// a host vector into fresh device memory (one element more than it holds, so that an empty vector still gets a pointer)
+template <class T>
+static inline int nk_upload(const nk_ctx *ctx, T **dst, const std::vector<T> &src) {
+  NK_TRY(nk_dev_alloc(dst, src.size() + 1));
+  if (!src.empty()) NK_HIP(nk_memcpy(ctx, *dst, src.data(), src.size() * sizeof(T), hipMemcpyHostToDevice));
+  return NK_OK;
+}
+#ifdef __HIPCC__
+// the early exit of everything enqueued behind a solve that has finished: the flag is the GMRES control block's `done`
+__device__ __forceinline__ bool nk_skip(const int *d_skip) { return d_skip != nullptr && *d_skip != 0; }
+#endif
+
+// ----------------------------------------------------------------------------- Chebyshev iteration (nk_cheb.hip)
+// `steps` steps for A x = b (with dinv: D⁻¹A x = D⁻¹b) on [lmin, lmax] — the polynomial preconditioner of nk_gmres.hip and the
+// smoothers of nk_mg.hip and nk_amg.hip. First step: d = [dinv·]r/θ, x = zero ? d : x + d. Later steps: r −= A d,
+// d' = c1·d + c2·[dinv·]r, x += d' (coefficients: nk_cheb.h) — `fused`: in the operator's NK_EPI_CHEB_STEP row epilogue, d
+// ping-ponging between d and t; otherwise the plain product into t and one vector pass.
+struct nk_cheb_job {
+  int64_t n = 0;
+  double lmin = 0, lmax = 0;
+  int steps = 1;
+  bool zero = true;               // from x = 0: r ← b in the first step's sweep; false: r holds b − A x already
+  bool fused = false;
+  const double *b = nullptr;      // read when `zero`
+  const double *dinv = nullptr;   // nullable (fused only)
+  double *r = nullptr;            // may be NULL for a single step from zero (no copy of b is kept)
+  double *d = nullptr, *t = nullptr, *x = nullptr;
+  const int *d_skip = nullptr;
+};
+// the operator on `d`: ep != NULL — apply with this epilogue (nothing else to write); ep == NULL — the plain product into t
+typedef std::function<int(const double *d, double *t, const nk_spmv_epi *ep)> nk_cheb_op;
+// *d_last (nullable): where the last correction d ended (job.d or job.t)
+int nk_cheb_run(nk_ctx *ctx, const nk_cheb_job &job, const nk_cheb_op &op, double **d_last = nullptr);

@@ -87,12 +87,11 @@ struct nk_mg {
 };
 
 // ----------------------------------------------------------------------------- kernels
-#define MG_SKIP(p) if ((p) != nullptr && *(p) != 0) return
 // x_f += P e_c   (bilinear, homogeneous Dirichlet: neighbours outside the coarse grid are zero)
 __global__ __launch_bounds__(NK_BLOCK) void k_mg_prolong_add(int nf, int nc, const int32_t *__restrict__ I0,
                                                              const double *__restrict__ w1, const double *__restrict__ ec,
                                                              double *__restrict__ xf, const int *d_skip) {
-  MG_SKIP(d_skip);
+  if (nk_skip(d_skip)) return;
   const int k = blockIdx.x * NK_BLOCK + threadIdx.x;
   if (k >= nf * nf) return;
   const int j = k / nf, i = k - j * nf;
@@ -110,7 +109,7 @@ __global__ __launch_bounds__(NK_BLOCK) void k_mg_prolong_add(int nf, int nc, con
 __global__ __launch_bounds__(NK_BLOCK) void k_mg_restrict(int nf, int nc, const int32_t *__restrict__ lo,
                                                           const double *__restrict__ w, const double *__restrict__ rf,
                                                           double *__restrict__ rc, const int *d_skip) {
-  MG_SKIP(d_skip);
+  if (nk_skip(d_skip)) return;
   const int k = blockIdx.x * NK_BLOCK + threadIdx.x;
   if (k >= nc * nc) return;
   const int J = k / nc, I = k - J * nc;
@@ -132,7 +131,7 @@ __global__ __launch_bounds__(NK_BLOCK) void k_mg_restrict(int nf, int nc, const 
 __global__ __launch_bounds__(NK_BLOCK) void k_mg_prolong_add_dist(int nf, int nc, int jf0, int nlf, const int32_t *__restrict__ I0,
                                                                   const double *__restrict__ w1, mg_lines ec,
                                                                   double *__restrict__ xf, const int *d_skip) {
-  MG_SKIP(d_skip);
+  if (nk_skip(d_skip)) return;
   const int k = blockIdx.x * NK_BLOCK + threadIdx.x;
   if (k >= nf * nlf) return;
   const int jl = k / nf, i = k - jl * nf, j = jf0 + jl;
@@ -148,7 +147,7 @@ __global__ __launch_bounds__(NK_BLOCK) void k_mg_prolong_add_dist(int nf, int nc
 __global__ __launch_bounds__(NK_BLOCK) void k_mg_restrict_dist(int nf, int nc, int jc0, int nlc, const int32_t *__restrict__ lo,
                                                                const double *__restrict__ w, mg_lines rf,
                                                                double *__restrict__ rc, const int *d_skip) {
-  MG_SKIP(d_skip);
+  if (nk_skip(d_skip)) return;
   const int k = blockIdx.x * NK_BLOCK + threadIdx.x;
   if (k >= nc * nlc) return;
   const int Jl = k / nc, I = k - Jl * nc, J = jc0 + Jl;
@@ -173,21 +172,6 @@ __global__ __launch_bounds__(NK_BLOCK) void k_mg_scatter_lines(int64_t nfull, in
   full[i] = (i >= off && i < off + cnt) ? loc[i - off] : 0.0;
 }
 
-// Chebyshev smoother: the first step; the later steps and the residual are fused into the stencil JVP's row epilogue
-// d = r/θ ; x = (zero ? 0 : x) + d ; r_copy = r (optional: the recurrence continues on a private copy of b)
-__global__ __launch_bounds__(NK_BLOCK) void k_mg_cheb_first(int64_t n, const double *__restrict__ r, double inv_theta, int zero,
-                                                            double *__restrict__ d, double *__restrict__ x,
-                                                            double *__restrict__ r_copy, const int *d_skip) {
-  MG_SKIP(d_skip);
-  const int64_t i = (int64_t)blockIdx.x * NK_BLOCK + threadIdx.x;
-  if (i >= n) return;
-  const double rv = r[i], dd = rv * inv_theta;
-  d[i] = dd;
-  x[i] = zero ? dd : x[i] + dd;
-  if (r_copy) r_copy[i] = rv;
-}
-static inline dim3 g1(int64_t n) { return dim3((unsigned)((n + NK_BLOCK - 1) / NK_BLOCK)); }
-
 // ---- Brusselator: nested periodic grids, two species stored one after the other (idx = i + N·j + N²·s)
 // r_c = ¼ Pᵀ r_f (full weighting): 1/16 · [1 2 1; 2 4 2; 1 2 1] around the fine point (2I, 2J), periodic.
 // Slabs of whole lines (several ranks; every rank's first line is even on every level but the coarsest): coarse local line Jl
@@ -196,7 +180,7 @@ static inline dim3 g1(int64_t n) { return dim3((unsigned)((n + NK_BLOCK - 1) / N
 __global__ __launch_bounds__(NK_BLOCK) void k_mgb_restrict(int nf, int nlf, const double *__restrict__ rf,
                                                            const double *__restrict__ lo, double *__restrict__ rc,
                                                            const int *d_skip) {
-  MG_SKIP(d_skip);
+  if (nk_skip(d_skip)) return;
   const int nc = nf >> 1, nlc = nlf >> 1;
   const int k = blockIdx.x * NK_BLOCK + threadIdx.x;
   if (k >= 2 * nc * nlc) return;
@@ -214,7 +198,7 @@ __global__ __launch_bounds__(NK_BLOCK) void k_mgb_restrict(int nf, int nlf, cons
 __global__ __launch_bounds__(NK_BLOCK) void k_mgb_prolong_add(int nf, int nlf, const double *__restrict__ ec,
                                                               const double *__restrict__ hi, double *__restrict__ xf,
                                                               const int *d_skip) {
-  MG_SKIP(d_skip);
+  if (nk_skip(d_skip)) return;
   const int nc = nf >> 1, nlc = nlf >> 1;
   const int k = blockIdx.x * NK_BLOCK + threadIdx.x;
   if (k >= 2 * nf * nlf) return;
@@ -246,22 +230,10 @@ __global__ __launch_bounds__(NK_BLOCK) void k_mgb_take_lines(int N, int j0, int 
   const int jl = (int)(kk / N), i = (int)(kk - (int64_t)jl * N);
   loc[e] = full[(size_t)i + (size_t)N * (j0 + jl) + (size_t)N * N * sp];
 }
-// one Chebyshev step after the first, unfused: r −= J d (t holds J d); d = c1 d + c2 r; x += d
-__global__ __launch_bounds__(NK_BLOCK) void k_mg_cheb_step(int64_t n, double c1, double c2, const double *__restrict__ t,
-                                                           double *__restrict__ r, double *__restrict__ d,
-                                                           double *__restrict__ x, const int *d_skip) {
-  MG_SKIP(d_skip);
-  const int64_t i = (int64_t)blockIdx.x * NK_BLOCK + threadIdx.x;
-  if (i >= n) return;
-  const double rn = r[i] - t[i], dn = c1 * d[i] + c2 * rn;
-  r[i] = rn;
-  d[i] = dn;
-  x[i] += dn;
-}
 // out = b − t
 __global__ __launch_bounds__(NK_BLOCK) void k_mg_sub(int64_t n, const double *__restrict__ b, const double *__restrict__ t,
                                                      double *__restrict__ out, const int *d_skip) {
-  MG_SKIP(d_skip);
+  if (nk_skip(d_skip)) return;
   const int64_t i = (int64_t)blockIdx.x * NK_BLOCK + threadIdx.x;
   if (i < n) out[i] = b[i] - t[i];
 }
@@ -510,9 +482,9 @@ static int mg_gather_coarse(nk_mg *M, const double *loc, double *full) {
   nk_mg_level &C = M->lv.back();
   const int64_t nfull = (M->kind == 1 ? 2 : 1) * C.ns * C.ns;
   if (M->kind == 1)
-    NK_LAUNCH(ctx, k_mgb_scatter_lines, g1(nfull), dim3(NK_BLOCK), (int)C.ns, (int)C.j0, (int)(C.j1 - C.j0), loc, full);
+    NK_LAUNCH(ctx, k_mgb_scatter_lines, nk_grid1(nfull), dim3(NK_BLOCK), (int)C.ns, (int)C.j0, (int)(C.j1 - C.j0), loc, full);
   else
-    NK_LAUNCH(ctx, k_mg_scatter_lines, g1(nfull), dim3(NK_BLOCK), nfull, C.j0 * C.ns, C.n, loc, full);
+    NK_LAUNCH(ctx, k_mg_scatter_lines, nk_grid1(nfull), dim3(NK_BLOCK), nfull, C.j0 * C.ns, C.n, loc, full);
   NK_HIP(hipGetLastError());
   for (int64_t o = 0; o < nfull; o += 1 << 20) {  // (int-sized messages)
     const int c = (int)std::min<int64_t>(1 << 20, nfull - o);
@@ -526,14 +498,14 @@ static int mg_restrict(nk_mg *M, nk_mg_level &F, nk_mg_level &C, const double *s
   if (M->kind == 1) {
     const double *lo = nullptr, *hi = nullptr;
     if (ctx->nranks > 1) NK_TRY(nk_problem_ghost_lines(F.P, src, &lo, &hi));
-    NK_LAUNCH(ctx, k_mgb_restrict, g1(C.n), dim3(NK_BLOCK), (int)F.ns, (int)(F.j1 - F.j0), src, lo, dst, d_skip);
+    NK_LAUNCH(ctx, k_mgb_restrict, nk_grid1(C.n), dim3(NK_BLOCK), (int)F.ns, (int)(F.j1 - F.j0), src, lo, dst, d_skip);
   } else if (ctx->nranks == 1) {
-    NK_LAUNCH(ctx, k_mg_restrict, g1(C.n), dim3(NK_BLOCK), (int)F.ns, (int)C.ns, (const int32_t *)F.rlo, (const double *)F.rw, src,
+    NK_LAUNCH(ctx, k_mg_restrict, nk_grid1(C.n), dim3(NK_BLOCK), (int)F.ns, (int)C.ns, (const int32_t *)F.rlo, (const double *)F.rw, src,
               dst, d_skip);
   } else {
     NK_TRY(nk_halo_exchange(ctx, &F.gh_f, src));
     const mg_lines ln = make_lines(F.gh_f, src, F.rf_lo, F.rf_hi, F.j0, F.j1, F.ns);
-    NK_LAUNCH(ctx, k_mg_restrict_dist, g1(C.n), dim3(NK_BLOCK), (int)F.ns, (int)C.ns, (int)C.j0, (int)(C.j1 - C.j0),
+    NK_LAUNCH(ctx, k_mg_restrict_dist, nk_grid1(C.n), dim3(NK_BLOCK), (int)F.ns, (int)C.ns, (int)C.j0, (int)(C.j1 - C.j0),
               (const int32_t *)F.rlo, (const double *)F.rw, ln, dst, d_skip);
   }
   NK_HIP(hipGetLastError());
@@ -544,14 +516,14 @@ static int mg_prolong_add(nk_mg *M, nk_mg_level &F, nk_mg_level &C, const double
   if (M->kind == 1) {
     const double *lo = nullptr, *hi = nullptr;
     if (ctx->nranks > 1) NK_TRY(nk_problem_ghost_lines(C.P, ec, &lo, &hi));
-    NK_LAUNCH(ctx, k_mgb_prolong_add, g1(F.n), dim3(NK_BLOCK), (int)F.ns, (int)(F.j1 - F.j0), ec, hi, xf, d_skip);
+    NK_LAUNCH(ctx, k_mgb_prolong_add, nk_grid1(F.n), dim3(NK_BLOCK), (int)F.ns, (int)(F.j1 - F.j0), ec, hi, xf, d_skip);
   } else if (ctx->nranks == 1) {
-    NK_LAUNCH(ctx, k_mg_prolong_add, g1(F.n), dim3(NK_BLOCK), (int)F.ns, (int)C.ns, (const int32_t *)F.pI0, (const double *)F.pw1, ec,
+    NK_LAUNCH(ctx, k_mg_prolong_add, nk_grid1(F.n), dim3(NK_BLOCK), (int)F.ns, (int)C.ns, (const int32_t *)F.pI0, (const double *)F.pw1, ec,
               xf, d_skip);
   } else {
     NK_TRY(nk_halo_exchange(ctx, &F.gh_c, ec));
     const mg_lines ln = make_lines(F.gh_c, ec, F.pc_lo, F.pc_hi, C.j0, C.j1, C.ns);
-    NK_LAUNCH(ctx, k_mg_prolong_add_dist, g1(F.n), dim3(NK_BLOCK), (int)F.ns, (int)C.ns, (int)F.j0, (int)(F.j1 - F.j0),
+    NK_LAUNCH(ctx, k_mg_prolong_add_dist, nk_grid1(F.n), dim3(NK_BLOCK), (int)F.ns, (int)C.ns, (int)F.j0, (int)(F.j1 - F.j0),
               (const int32_t *)F.pI0, (const double *)F.pw1, ln, xf, d_skip);
   }
   NK_HIP(hipGetLastError());
@@ -597,62 +569,40 @@ int nk_mg_update(nk_mg *M, const double *d_u) {
   return NK_OK;
 }
 
-// ν Chebyshev steps for J_l x = b on [λmax/4, λmax]; zero_guess: x starts at 0 (then r = b)
-// b − J x in ONE kernel: the stencil JVP's row epilogue subtracts from b (nk_spmv_epi mode 2)
+// b − J x in ONE kernel: the stencil JVP's row epilogue subtracts from b (NK_EPI_RESIDUAL)
 static int mg_residual(nk_mg *M, nk_mg_level &L, const double *x, double *out, const int *d_skip) {
   if (M->kind == 1) {  // (the Brusselator JVP kernel has no row epilogue: J x, then b − J x)
     NK_TRY(nk_problem_jvp_dev(L.P, L.u, x, out, d_skip));
-    NK_LAUNCH(M->ctx, k_mg_sub, g1(L.n), dim3(NK_BLOCK), L.n, (const double *)L.b, (const double *)out, out, d_skip);
+    NK_LAUNCH(M->ctx, k_mg_sub, nk_grid1(L.n), dim3(NK_BLOCK), L.n, (const double *)L.b, (const double *)out, out, d_skip);
     NK_HIP(hipGetLastError());
     return NK_OK;
   }
   nk_spmv_epi ep;
-  ep.mode = 2;
+  ep.mode = NK_EPI_RESIDUAL;
   ep.r = L.b;
   return nk_problem_jvp_dev(L.P, L.u, x, out, d_skip, nullptr, &ep);
 }
 
+// ν Chebyshev steps for J_l x = b on [λmax/4, λmax] (nk_cheb_run); zero_guess: x starts at 0 (then r = b)
 static int mg_smooth(nk_mg *M, nk_mg_level &L, bool zero_guess, const int *d_skip) {
-  nk_ctx *ctx = M->ctx;
-  const double lmax = L.lmax, lmin = lmax / 4.0;
-  const double theta = 0.5 * (lmax + lmin), delta = 0.5 * (lmax - lmin), sigma = theta / delta;
-  double rho = 1.0 / sigma;
-  if (!zero_guess) {
-    NK_TRY(mg_residual(M, L, L.x, L.r, d_skip));
-    NK_LAUNCH(ctx, k_mg_cheb_first, g1(L.n), dim3(NK_BLOCK), L.n, (const double *)L.r, 1.0 / theta, 0, L.d, L.x,
-              (double *)nullptr, d_skip);
-  } else {  // x0 = 0: r = b; the recurrence below updates r in place, so it gets its own copy in the same sweep
-    NK_LAUNCH(ctx, k_mg_cheb_first, g1(L.n), dim3(NK_BLOCK), L.n, (const double *)L.b, 1.0 / theta, 1, L.d, L.x,
-              M->nu > 1 ? L.r : (double *)nullptr, d_skip);
-  }
-  if (M->kind == 1) {
-    for (int k = 1; k < M->nu; ++k) {
-      const double rho_new = 1.0 / (2.0 * sigma - rho);
-      NK_TRY(nk_problem_jvp_dev(L.P, L.u, L.d, L.t, d_skip));
-      NK_LAUNCH(ctx, k_mg_cheb_step, g1(L.n), dim3(NK_BLOCK), L.n, rho_new * rho, 2.0 * rho_new / delta, (const double *)L.t,
-                L.r, L.d, L.x, d_skip);
-      rho = rho_new;
-    }
-    NK_HIP(hipGetLastError());
-    return NK_OK;
-  }
-  double *dcur = L.d, *dalt = L.t;
-  for (int k = 1; k < M->nu; ++k) {
-    // r −= J d ; d_new = c1 d + c2 r ; x += d_new — fused into the JVP's row epilogue (mode 1); d ping-pongs because the
-    // stencil reads the neighbours' old d
-    const double rho_new = 1.0 / (2.0 * sigma - rho);
-    nk_spmv_epi ep;
-    ep.mode = 1;
-    ep.c1 = rho_new * rho;
-    ep.c2 = 2.0 * rho_new / delta;
-    ep.r = L.r;
-    ep.dnew = dalt;
-    ep.yacc = L.x;
-    NK_TRY(nk_problem_jvp_dev(L.P, L.u, dcur, dalt, d_skip, nullptr, &ep));
-    double *tmp = dcur; dcur = dalt; dalt = tmp;
-    rho = rho_new;
-  }
-  return NK_OK;
+  if (!zero_guess) NK_TRY(mg_residual(M, L, L.x, L.r, d_skip));
+  nk_cheb_job job;
+  job.n = L.n;
+  job.lmin = L.lmax / 4.0;
+  job.lmax = L.lmax;
+  job.steps = M->nu;
+  job.zero = zero_guess;
+  job.fused = M->kind != 1;   // (the Brusselator JVP kernel has no row epilogue)
+  job.b = L.b;
+  // x0 = 0: r = b; the recurrence updates r in place, so it gets its own copy in the first step's sweep — if a second step follows
+  job.r = (zero_guess && M->nu == 1) ? nullptr : L.r;
+  job.d = L.d;
+  job.t = L.t;
+  job.x = L.x;
+  job.d_skip = d_skip;
+  return nk_cheb_run(M->ctx, job, [&](const double *d, double *t, const nk_spmv_epi *ep) {
+    return nk_problem_jvp_dev(L.P, L.u, d, t, d_skip, nullptr, ep);
+  });
 }
 
 // the V-cycle proper: lv[0].b → lv[0].x (every pointer and scalar argument is fixed for the lifetime of the hierarchy)
@@ -725,7 +675,7 @@ static int mg_vcycle_body(nk_mg *M, const int *d_skip) {
       NK_TRY(mg_gather_coarse(M, C.b, M->rep_b));
       NK_TRY(nk_bandlu_solve(M->LU, M->rep_b, M->rep_x));
       if (M->kind == 1)
-        NK_LAUNCH(ctx, k_mgb_take_lines, g1(C.n), dim3(NK_BLOCK), (int)C.ns, (int)C.j0, (int)(C.j1 - C.j0),
+        NK_LAUNCH(ctx, k_mgb_take_lines, nk_grid1(C.n), dim3(NK_BLOCK), (int)C.ns, (int)C.j0, (int)(C.j1 - C.j0),
                   (const double *)M->rep_x, C.x);
       else
         NK_TRY(nk_blas_copy(ctx, C.n, M->rep_x + C.j0 * C.ns, C.x));

@@ -920,7 +920,7 @@ extern "C" int nk_csr_powers(nk_csr *A, const double *x, double *Y, int64_t ldy,
     int r = NK_OK;
     for (int p = 0; p < s && r == NK_OK; ++p) {
       nk_spmv_epi ep;
-      if (theta) { ep.mode = 3; ep.theta = dsc + 1 + p; }
+      if (theta) { ep.mode = NK_EPI_SHIFTED; ep.theta = dsc + 1 + p; }
       r = nk_csr_spmv_dev(A, p == 0 ? dx : dY + (size_t)(p - 1) * ldy, dY + (size_t)p * ldy, nullptr, dsc, &ep);
     }
     return r;

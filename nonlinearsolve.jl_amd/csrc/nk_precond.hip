@@ -73,7 +73,7 @@ __global__ __launch_bounds__(NK_BLOCK) void k_jacobi_setup(int64_t n, const int3
 __global__ __launch_bounds__(NK_BLOCK) void k_jacobi_apply(int64_t n, const double *__restrict__ dinv,
                                                            const double *__restrict__ x, double *__restrict__ y,
                                                            const int *d_skip) {
-  if (d_skip != nullptr && *d_skip != 0) return;
+  if (nk_skip(d_skip)) return;
   const int64_t stride = (int64_t)gridDim.x * NK_BLOCK;
   for (int64_t i = (int64_t)blockIdx.x * NK_BLOCK + threadIdx.x; i < n; i += stride) y[i] = dinv[i] * x[i];
 }
@@ -126,14 +126,14 @@ __global__ __launch_bounds__(NK_BLOCK) void k_ilu_factor_level(ilu_dev d, const 
 }
 __global__ __launch_bounds__(NK_BLOCK) void k_ilu_lower_level(ilu_dev d, const int32_t *__restrict__ rows, int lo, int hi,
                                                               const double *__restrict__ b, double *y, const int *d_skip) {
-  if (d_skip != nullptr && *d_skip != 0) return;
+  if (nk_skip(d_skip)) return;
   const int idx = lo + blockIdx.x * NK_BLOCK + threadIdx.x;
   if (idx < hi) ilu_lower_row(rows[idx], d.rp, d.ci, d.dg, d.lu, d.perm, b, y);
 }
 __global__ __launch_bounds__(NK_BLOCK) void k_ilu_upper_level(ilu_dev d, const int32_t *__restrict__ rows, int lo, int hi,
                                                               const double *__restrict__ y, double *z, double *out,
                                                               const int *d_skip) {
-  if (d_skip != nullptr && *d_skip != 0) return;
+  if (nk_skip(d_skip)) return;
   const int idx = lo + blockIdx.x * NK_BLOCK + threadIdx.x;
   if (idx < hi) ilu_upper_row(rows[idx], d.rp, d.ci, d.dg, d.lu, d.perm, y, z, out);
 }
@@ -153,7 +153,7 @@ __global__ __launch_bounds__(ILU_CHAIN_THREADS) void k_ilu_lower_chain(ilu_dev d
                                                                        const int32_t *__restrict__ ptr, int nlev,
                                                                        const double *__restrict__ b, double *y,
                                                                        const int *d_skip) {
-  if (d_skip != nullptr && *d_skip != 0) return;
+  if (nk_skip(d_skip)) return;
   for (int lev = 0; lev < nlev; ++lev) {
     for (int idx = ptr[lev] + threadIdx.x; idx < ptr[lev + 1]; idx += ILU_CHAIN_THREADS)
       ilu_lower_row(rows[idx], d.rp, d.ci, d.dg, d.lu, d.perm, b, y);
@@ -165,7 +165,7 @@ __global__ __launch_bounds__(ILU_CHAIN_THREADS) void k_ilu_upper_chain(ilu_dev d
                                                                        const int32_t *__restrict__ ptr, int nlev,
                                                                        const double *__restrict__ y, double *z, double *out,
                                                                        const int *d_skip) {
-  if (d_skip != nullptr && *d_skip != 0) return;
+  if (nk_skip(d_skip)) return;
   for (int lev = 0; lev < nlev; ++lev) {
     for (int idx = ptr[lev] + threadIdx.x; idx < ptr[lev + 1]; idx += ILU_CHAIN_THREADS)
       ilu_upper_row(rows[idx], d.rp, d.ci, d.dg, d.lu, d.perm, y, z, out);
@@ -180,12 +180,6 @@ __global__ __launch_bounds__(NK_BLOCK) void k_ilu_gather_values(int64_t nnzp, co
 }
 
 // ----------------------------------------------------------------------------- ILU(0): symbolic phase (host)
-template <typename T>
-static int upload(nk_ctx *ctx, T **dst, const std::vector<T> &v) {
-  NK_TRY(nk_dev_alloc(dst, v.size() + 1));
-  if (!v.empty()) NK_HIP(nk_memcpy(ctx, *dst, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
-  return NK_OK;
-}
 // greedy distance-1 colouring of the symmetrised pattern in natural order (smallest free colour); rows are then ordered by
 // (colour, original index) — restated in oracle/reference_restatement.py::multicolor_permutation
 static void multicolor_perm(int64_t n, const std::vector<int32_t> &rp, const std::vector<int32_t> &ci,
@@ -310,18 +304,18 @@ static int ilu_symbolic(nk_precond *P) {
   P->chainL = chain_pays(P->h_ptrL);
   P->chainU = chain_pays(P->h_ptrU);
   if (P->ordering != NK_ILU_MULTICOLOR) P->ncolors = 0;
-  if (P->ordering == NK_ILU_MULTICOLOR) NK_TRY(upload(P->ctx, &P->d_perm, perm));
-  NK_TRY(upload(P->ctx, &P->d_rp, rp));
-  NK_TRY(upload(P->ctx, &P->d_ci, ci));
-  NK_TRY(upload(P->ctx, &P->d_dg, dg));
-  NK_TRY(upload(P->ctx, &P->d_src, src));
-  NK_TRY(upload(P->ctx, &P->d_planptr, planptr));
-  NK_TRY(upload(P->ctx, &P->d_planq, planq));
-  NK_TRY(upload(P->ctx, &P->d_plans, plans));
-  NK_TRY(upload(P->ctx, &P->d_rowsL, rowsL));
-  NK_TRY(upload(P->ctx, &P->d_ptrL, P->h_ptrL));
-  NK_TRY(upload(P->ctx, &P->d_rowsU, rowsU));
-  NK_TRY(upload(P->ctx, &P->d_ptrU, P->h_ptrU));
+  if (P->ordering == NK_ILU_MULTICOLOR) NK_TRY(nk_upload(P->ctx, &P->d_perm, perm));
+  NK_TRY(nk_upload(P->ctx, &P->d_rp, rp));
+  NK_TRY(nk_upload(P->ctx, &P->d_ci, ci));
+  NK_TRY(nk_upload(P->ctx, &P->d_dg, dg));
+  NK_TRY(nk_upload(P->ctx, &P->d_src, src));
+  NK_TRY(nk_upload(P->ctx, &P->d_planptr, planptr));
+  NK_TRY(nk_upload(P->ctx, &P->d_planq, planq));
+  NK_TRY(nk_upload(P->ctx, &P->d_plans, plans));
+  NK_TRY(nk_upload(P->ctx, &P->d_rowsL, rowsL));
+  NK_TRY(nk_upload(P->ctx, &P->d_ptrL, P->h_ptrL));
+  NK_TRY(nk_upload(P->ctx, &P->d_rowsU, rowsU));
+  NK_TRY(nk_upload(P->ctx, &P->d_ptrU, P->h_ptrU));
   NK_TRY(nk_dev_alloc(&P->d_lu, (size_t)P->nnzp + 1));
   NK_TRY(nk_dev_alloc(&P->d_y, (size_t)n + 1));
   NK_TRY(nk_dev_alloc(&P->d_z, (size_t)n + 1));
@@ -507,14 +501,14 @@ static int ilut_update(nk_precond *P) {
   hipFree(P->d_rowsL); hipFree(P->d_ptrL); hipFree(P->d_rowsU); hipFree(P->d_ptrU);
   P->d_rp = P->d_ci = P->d_dg = P->d_rowsL = P->d_ptrL = P->d_rowsU = P->d_ptrU = nullptr;
   P->d_lu = nullptr;
-  NK_TRY(upload(P->ctx, &P->d_rp, rp));
-  NK_TRY(upload(P->ctx, &P->d_ci, ci));
-  NK_TRY(upload(P->ctx, &P->d_dg, dg));
-  NK_TRY(upload(P->ctx, &P->d_rowsL, rowsL));
-  NK_TRY(upload(P->ctx, &P->d_ptrL, P->h_ptrL));
-  NK_TRY(upload(P->ctx, &P->d_rowsU, rowsU));
-  NK_TRY(upload(P->ctx, &P->d_ptrU, P->h_ptrU));
-  NK_TRY(upload(P->ctx, &P->d_lu, lu));
+  NK_TRY(nk_upload(P->ctx, &P->d_rp, rp));
+  NK_TRY(nk_upload(P->ctx, &P->d_ci, ci));
+  NK_TRY(nk_upload(P->ctx, &P->d_dg, dg));
+  NK_TRY(nk_upload(P->ctx, &P->d_rowsL, rowsL));
+  NK_TRY(nk_upload(P->ctx, &P->d_ptrL, P->h_ptrL));
+  NK_TRY(nk_upload(P->ctx, &P->d_rowsU, rowsU));
+  NK_TRY(nk_upload(P->ctx, &P->d_ptrU, P->h_ptrU));
+  NK_TRY(nk_upload(P->ctx, &P->d_lu, lu));
   if (!P->d_y) NK_TRY(nk_dev_alloc(&P->d_y, (size_t)n + 1));
   if (!P->d_z) NK_TRY(nk_dev_alloc(&P->d_z, (size_t)n + 1));
   P->factored = true;

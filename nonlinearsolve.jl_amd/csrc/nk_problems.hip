@@ -168,11 +168,11 @@ __global__ __launch_bounds__(NK_BLOCK) void k_bratu_jvp(int64_t ns, int64_t nl, 
   const int64_t jl = k / ns, i = k - jl * ns;
   const double vk = v[k];
   const double res = c_lap * bratu_lap(v, lo, hi, ns, nl, i, jl, k) - d[k] * vk;
-  if (epi.mode == 0) {
+  if (epi.mode == NK_EPI_PLAIN) {
     jv[k] = os * res;
-  } else if (epi.mode == 3) {  // Newton-basis step of the s-step Arnoldi process: scale·(J v − θ v)
+  } else if (epi.mode == NK_EPI_SHIFTED) {  // Newton-basis step of the s-step Arnoldi process: scale·(J v − θ v)
     jv[k] = os * (res - (*epi.theta) * vk);
-  } else if (epi.mode == 2) {  // fused residual: out = b − J v (b = epi.r)
+  } else if (epi.mode == NK_EPI_RESIDUAL) {  // fused residual: out = b − J v (b = epi.r)
     jv[k] = epi.r[k] - res;
   } else {  // fused Chebyshev step (v = d_old): r −= J d; d_new = c1 d_old + c2 r; y += d_new
     const double rr = epi.r[k] - res;
@@ -213,7 +213,7 @@ __global__ __launch_bounds__(NK_BLOCK) void k_bratu_jvp_tile(int ns, int nl, dou
     w[r] = v[row + iw];
     e[r] = v[row + ie];
     dg[r] = d[row + i];
-    rr[r] = (epi.mode == 1 || epi.mode == 2) ? epi.r[row + i] : 0.0;
+    rr[r] = (epi.mode == NK_EPI_CHEB_STEP || epi.mode == NK_EPI_RESIDUAL) ? epi.r[row + i] : 0.0;
   }
   if (j0 == 0 && lo) col[0] = lo[i];                                  // uniform per workgroup
   const double hiv = (j0 + TY >= nl && hi) ? hi[i] : 0.0;             // line nl: the upper neighbour rank's first line
@@ -227,11 +227,11 @@ __global__ __launch_bounds__(NK_BLOCK) void k_bratu_jvp_tile(int ns, int nl, dou
       const double nn = (jl == nl - 1) ? hiv : col[r + 2];  // (weight mn = 0 without an upper neighbour)
       const double res = c_lap * (4.0 * c - mw * w[r] - me * e[r] - ms * col[r] - mn * nn) - dg[r] * c;
       const size_t k = (size_t)jl * ns + i;
-      if (epi.mode == 0) {
+      if (epi.mode == NK_EPI_PLAIN) {
         jv[k] = os * res;
-      } else if (epi.mode == 3) {  // Newton-basis step of the s-step Arnoldi process: scale·(J v − θ v)
+      } else if (epi.mode == NK_EPI_SHIFTED) {  // Newton-basis step of the s-step Arnoldi process: scale·(J v − θ v)
         jv[k] = os * (res - (*epi.theta) * c);
-      } else if (epi.mode == 2) {  // fused residual: out = b − J v (b = epi.r)
+      } else if (epi.mode == NK_EPI_RESIDUAL) {  // fused residual: out = b − J v (b = epi.r)
         jv[k] = rr[r] - res;
       } else {  // fused Chebyshev step (v = d_old): r −= J d; d_new = c1 d_old + c2 r; y += d_new
         const double rn = rr[r] - res;
@@ -776,8 +776,7 @@ __global__ __launch_bounds__(NK_BLOCK) void k_fd_diff(int64_t n, const double *_
 
 int nk_problem_jvp_dev(nk_problem *P, const double *d_u, const double *d_v, double *d_jv, const int *d_skip,
                        const double *d_out_scale, const nk_spmv_epi *epi) {
-  if (epi && epi->mode != 0 && P->kind != NK_PROBLEM_BRATU2D)  // (modes: 1 fused Chebyshev step, 2 fused residual b − Jv)
-    NK_FAIL(NK_E_UNSUPPORTED, "internal: fused epilogue only exists for the Bratu JVP");
+  if (epi && epi->mode != NK_EPI_PLAIN && P->kind != NK_PROBLEM_BRATU2D)    NK_FAIL(NK_E_UNSUPPORTED, "internal: fused epilogue only exists for the Bratu JVP");
   nk_spmv_epi ep{};
   if (epi) ep = *epi;
   nk_ctx *ctx = P->ctx;

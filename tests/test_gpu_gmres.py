@@ -453,7 +453,7 @@ def test_failing_host_callback_is_an_error_and_the_object_lives(nls):
 @pytest.mark.parametrize("n", [63, 65])
 @pytest.mark.parametrize("form", ["mgs", "dcgs2"])
 def test_chebyshev_unfused_and_fused(nls, dev, form, n, deg):
-    """callable and shifted CSR operators take k_cheb_update (double2 body, odd-n tail); the CSR operator with no shift takes the
+    """callable and shifted CSR operators take k_cheb_step (double2 body, odd-n tail); the CSR operator with no shift takes the
     update fused into the SpMV: all against the long-double transcription of the oracle's chebyshev_preconditioner"""
     L = lib()
     specs = GR.group_specs()
