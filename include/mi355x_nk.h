@@ -660,6 +660,73 @@ int nk_grid_slab_code_object(const char *source, int dim, int dof, int stencil, 
                              int rank, int jac, void *buf, int64_t capacity, int64_t *bytes);
 int nk_problem_grid_slab(nk_problem *P, int64_t *line_begin, int64_t *line_end);
 
+/* ---------------------------------------------------------------- compiled graph problems (kernel generation, full size)
+ * A residual given node by node over ANY sparse adjacency — a network, an unstructured mesh — what the reference's user writes
+ * as `f` with NonlinearFunction(f; jac_prototype = any sparse pattern). The user supplies a CSR graph of the nodes and HIP C++
+ * source defining, per node, a function that loops over the node's edges:
+ *
+ *     template <typename T> __device__ void nk_node(const nk_nbrs<T> &u, const nk_real *p, nk_vertex s, T *f);
+ *
+ *       u.self(c = 0)      the node's own unknown c                u.deg()         its number of edges
+ *       u.nbr(e, c = 0)    unknown c of the e-th neighbour, e a run-time loop counter in 0 .. deg() − 1
+ *       u.node(e)          that neighbour's index                  u.w(e, k = 0)   datum k of that edge
+ *       u.a(k = 0)         the node's own datum k                  u.an(e, k = 0)  the neighbour's node datum k
+ *       s                  {i, nn, deg}: the node, the node count, the degree
+ *       p                  the parameters;  f: the node's dof residuals (entries not written are zero);  nk_real is double
+ *
+ * Data are nk_real, never duals: constants of the differentiation. A k outside the declared count reads NaN — the project's
+ * rule for a wrong source — and so do an e outside 0 .. deg() − 1 and a c outside 0 .. dof − 1 (node(e): −1). The source is
+ * compiled by hiprtc behind the dual-number prelude with the grid programs' options (-O3 -ffp-contract=off -std=c++17, gfx950)
+ * into nk_graph_residual and nk_graph_jvp (one node per thread; the JVP is exact: value from u, partial from v) and
+ * nk_graph_jac (the fill, one slot per thread, below). A source that does not compile is NK_E_INVALID with this contract and
+ * the compiler's log in nk_last_error.
+ *
+ * The graph: nn >= 1 nodes; rowptr[nn + 1] and colind[ne] host arrays, 0-based; columns strictly ascending within a row; no
+ * self-loops (the node itself is always an argument of its residual and always a column); it may be structurally nonsymmetric
+ * (a directed network) and ne may be 0. Anything else — a decreasing rowptr, a column outside 0 .. nn − 1, a duplicate or
+ * descending column, a self-loop — is NK_E_INVALID, decided on the host before anything is compiled or allocated, with a
+ * message that names the first offending row and the rule it breaks. Limits: dof = 1..4, nparams = 0..32, nedge and nnode =
+ * 0..4 data arrays per edge and per node, dof·dof·(ne + nn) <= INT32_MAX. A context of more than one rank gets
+ * NK_E_UNSUPPORTED: partitioning an arbitrary graph is not built.
+ *
+ * Numbering is component-major as everywhere: unknown c of node i is element c·nn + i. Edge datum k of edge e (its position
+ * in colind) is element k·ne + e and node datum k of node i element k·nn + i of two device buffers the problem owns, both zero
+ * at creation. nk_problem_set_graph_data (on_edges = 1: an edge datum of ne doubles, 0: a node datum of nn doubles) copies from
+ * host or device on the context's stream and, like nk_problem_set_field, marks the problem changed, so a Jacobian cached for
+ * the same u is filled again; nk_problem_get_graph_data copies out. A k out of range, or a problem that is not a compiled graph
+ * problem, is NK_E_INVALID naming the value.
+ *
+ * The pattern: row (c, i) holds, for every component c2 in order, the node itself and its neighbours in ascending node order —
+ * dof·(deg_i + 1) entries with ascending columns c2·nn + node, structural even where a derivative vanishes. The deg_i + 1
+ * column nodes of node i are its slots; the self slot sits at spos_i = the number of neighbours smaller than i, edge e at
+ * e + (e >= spos_i). All ne + nn slots are numbered node after node: slot s of node i is global slot rowptr[i] + i + s, and the
+ * value of dF_c(i)/du_c2(slot s) is element c·dof·(ne + nn) + dof·(rowptr[i] + i) + c2·(deg_i + 1) + s. nk_graph_pattern
+ * returns exactly this CSR (host only; NULL arrays: the sizes only), nk_problem_jac_csr the one the problem owns.
+ *
+ * Cost. Algorithmic bytes per node of the residual: 16·dof + 4 + deg·(4 + 8·r_e) + 8·r_n with r_e, r_n the data arrays the
+ * source reads; the JVP adds 8·dof. nbr(e, c) is one gathered load u[c·nn + colind[e]]: neighbour values are expected from
+ * cache, which holds for a bandwidth-reducing ordering of the nodes and not for a random one — the library does not reorder the
+ * user's graph. The fill evaluates nk_node once per slot with unit seeds on the dof unknowns of that slot: Σ (deg_i + 1)·deg_i
+ * edge terms, the price of a run-time degree with a compile-time dual width. No atomics; every sum runs in the source's own
+ * edge order, so all three kernels are bit-reproducible. NK_GRAPH_FILL_NODE=1 in the environment at creation selects the A/B
+ * form of the fill (one node per thread, the slots in an inner loop; slower, tools/graph_problem_bench.py).
+ *
+ * The object is an NK_PROBLEM_USER problem like a compiled grid problem: matrix-free GMRES, the concrete-J path, the coloured
+ * assembly, Jᵀv through the transposed SpMV and every `precs` object take it; nk_problem_set_params replaces p,
+ * nk_problem_initial_guess gives zeros, nk_problem_destroy frees everything. nk_gmres_set_multigrid_preconditioner refuses it
+ * (NK_E_INVALID; the aggregation AMG object is the multigrid of a general CSR). */
+int nk_graph_pattern(int64_t nn, const int32_t *rowptr, const int32_t *colind, int dof, int32_t *jrowptr, int32_t *jcolind,
+                     int64_t *nnz);
+int nk_graph_compile_check(const char *source, int dof, int nparams, int nedge, int nnode, int64_t *code_bytes);
+/* the code object of one of the two programs, for inspection (jac = 0: nk_graph_residual and nk_graph_jvp; 1: nk_graph_jac);
+ * buf NULL: the size only. Host only */
+int nk_graph_code_object(const char *source, int dof, int nparams, int nedge, int nnode, int jac, void *buf, int64_t capacity,
+                         int64_t *bytes);
+int nk_problem_create_graph(nk_ctx *ctx, const char *source, int64_t nn, const int32_t *rowptr, const int32_t *colind, int dof,
+                            const double *params, int nparams, int nedge, int nnode, nk_problem **out);
+int nk_problem_set_graph_data(nk_problem *P, int on_edges, int k, const double *data, int memspace);
+int nk_problem_get_graph_data(nk_problem *P, int on_edges, int k, double *out, int memspace);
+
 /* ---------------------------------------------------------------- GMRES (seam 1) */
 /* restart_m: the restart length m, 1 <= m <= 63 (the dot-product kernels take at most 64 columns at once); restart_m <= 0 means 30;
  * restart_m >= 64 is NK_E_INVALID with a message that names the limit, before anything is allocated or launched. */

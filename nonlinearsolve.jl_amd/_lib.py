@@ -211,6 +211,12 @@ SIGNATURES = {
     "nk_grid_slab_compile_check": (_I, [C.c_char_p, _I, _I, _I, _I, _I, _I, _I, _I, C.POINTER(_L)]),
     "nk_grid_slab_code_object": (_I, [C.c_char_p, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _L, C.POINTER(_L)]),
     "nk_problem_grid_slab": (_I, [_P, C.POINTER(_L), C.POINTER(_L)]),
+    "nk_graph_pattern": (_I, [_L, _P, _P, _I, _P, _P, C.POINTER(_L)]),
+    "nk_graph_compile_check": (_I, [C.c_char_p, _I, _I, _I, _I, C.POINTER(_L)]),
+    "nk_graph_code_object": (_I, [C.c_char_p, _I, _I, _I, _I, _I, _P, _L, C.POINTER(_L)]),
+    "nk_problem_create_graph": (_I, [_P, C.c_char_p, _L, _P, _P, _I, C.POINTER(_D), _I, _I, _I, _PP]),
+    "nk_problem_set_graph_data": (_I, [_P, _I, _I, _P, _I]),
+    "nk_problem_get_graph_data": (_I, [_P, _I, _I, _P, _I]),
     "nk_gmres_create": (_I, [_P, _L, _I, _I, _PP]),
     "nk_gmres_destroy": (_I, [_P]),
     "nk_gmres_set_operator_csr": (_I, [_P, _P]),

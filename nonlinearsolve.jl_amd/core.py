@@ -737,6 +737,138 @@ def CompiledGridProblem(source: str, nx: int, ny: int, dof: int = 1, stencil: st
     return P
 
 
+# ------------------------------------------------------------------------------------------- compiled graph problems
+def _graph_arrays(rowptr, colind):
+    """the adjacency as contiguous int32 host arrays (nn from rowptr; colind may be empty)"""
+    rp = np.ascontiguousarray(np.asarray(rowptr), dtype=np.int32).ravel()
+    ci = np.ascontiguousarray(np.asarray(colind), dtype=np.int32).ravel()
+    if rp.size < 2:
+        raise ValueError(f"rowptr has {rp.size} entries: a graph of nn >= 1 nodes has nn + 1")
+    if rp[-1] != ci.size:
+        raise ValueError(f"rowptr[-1] = {int(rp[-1])} but colind has {ci.size} entries")
+    return rp, ci, rp.size - 1
+
+
+def graph_pattern(rowptr, colind, dof: int = 1):
+    """(jrowptr, jcolind), int32, of the Jacobian of a compiled graph problem over the adjacency (rowptr, colind): row c·nn + i
+    holds, for every component c2 in order, node i itself and its neighbours in ascending node order — dof·(deg_i + 1) ascending
+    columns c2·nn + node. Host only. An adjacency that breaks a rule of CompiledGraphProblem raises NKError naming the first
+    offending row."""
+    rp, ci, nn = _graph_arrays(rowptr, colind)
+    nnz = C.c_int64()
+    prp, pci = C.c_void_p(rp.ctypes.data), C.c_void_p(ci.ctypes.data)
+    check(L.lib().nk_graph_pattern(nn, prp, pci, int(dof), None, None, C.byref(nnz)))
+    jrp, jci = np.empty(dof * nn + 1, dtype=np.int32), np.empty(nnz.value, dtype=np.int32)
+    check(L.lib().nk_graph_pattern(nn, prp, pci, int(dof), C.c_void_p(jrp.ctypes.data), C.c_void_p(jci.ctypes.data), C.byref(nnz)))
+    return jrp, jci
+
+
+def graph_compile_check(source: str, dof: int = 1, nparams: int = 0, edge_data: int = 0, node_data: int = 0) -> int:
+    """Compile the residual, JVP and Jacobian kernels of a CompiledGraphProblem source for gfx950 (no device needed); the size of
+    the code objects. A source that does not compile raises NKError with the contract and the compiler's log."""
+    nb = C.c_int64()
+    check(L.lib().nk_graph_compile_check(source.encode(), int(dof), int(nparams), int(edge_data), int(node_data), C.byref(nb)))
+    return nb.value
+
+
+class _GraphDeviceProblem(DeviceProblem):
+    """the nk_problem of CompiledGraphProblem: the Jacobian pattern belongs to the problem, `p` is the source's whole p, and the
+    edge and node data live in device buffers the problem owns"""
+
+    def jac_csr(self) -> CSRMatrix:
+        h = C.c_void_p()
+        check(L.lib().nk_problem_jac_csr(self._h, C.byref(h)))
+        return CSRMatrix(h, self.ctx, owned=False)   # freed with the problem
+
+    def set_p(self, p):
+        p = [float(p)] if isinstance(p, (int, float)) else [float(x) for x in p]
+        if len(p) != len(self.p):
+            raise ValueError(f"the source was compiled for {len(self.p)} parameters, got {len(p)}")
+        self.set_params(p)
+        self.p = p
+
+    def _set_data(self, on_edges, k, x):
+        what, n = ("edge", self.ne) if on_edges else ("node", self.nn)
+        size = x.numel() if _is_torch(x) else np.size(x)
+        if size != n:
+            raise ValueError(f"{what} datum {k}: expected {n} elements (one per {what}), got {size}")
+        px, ms, _keep = _ptr(x, n) if n else (None, L.HOST, None)
+        check(L.lib().nk_problem_set_graph_data(self._h, on_edges, int(k), px, ms))
+
+    def _get_data(self, on_edges, k):
+        out = torch.empty(self.ne if on_edges else self.nn, dtype=torch.float64, device=f"cuda:{self.ctx.device}")
+        check(L.lib().nk_problem_get_graph_data(self._h, on_edges, int(k), C.c_void_p(out.data_ptr()), L.DEVICE))
+        return out
+
+    def set_edge_data(self, k: int, x):
+        """Replace edge datum k (0 .. edge_data − 1) by x: a device tensor or a NumPy array of one float64 per edge, in the order
+        of colind. The data is copied; a Jacobian cached for the same u is filled again."""
+        self._set_data(1, k, x)
+
+    def set_node_data(self, k: int, x):
+        """Replace node datum k (0 .. node_data − 1) by x: one float64 per node. Copied, like set_edge_data."""
+        self._set_data(0, k, x)
+
+    def edge_data(self, k: int):
+        """a copy of edge datum k as a device tensor"""
+        return self._get_data(1, k)
+
+    def node_data(self, k: int):
+        """a copy of node datum k as a device tensor"""
+        return self._get_data(0, k)
+
+
+def CompiledGraphProblem(source: str, rowptr, colind, dof: int = 1, params: Sequence[float] = (), ctx=None, *, edge_data: int = 0,
+                         node_data: int = 0) -> DeviceProblem:
+    """A residual given node by node over any sparse adjacency — a network, an unstructured mesh — as HIP source
+        template <typename T> __device__ void nk_node(const nk_nbrs<T> &u, const nk_real *p, nk_vertex s, T *f);
+    compiled (hiprtc, gfx950) into the residual kernel, the exact dual-number JVP kernel and the Jacobian fill on the graph's
+    CSR pattern (include/mi355x_nk.h, "compiled graph problems"): what NonlinearFunction(f; jac_prototype = any sparse pattern)
+    is in the reference. Every solver, linear solver and `precs` object takes it (the scalable one for a general graph is
+    ObjectPrecs("amg"); MultigridPrecs needs a grid and is refused). u0 defaults to zeros; NonlinearProblem(..., p) and
+    reinit_(cache, p=...) replace the source's p[0..nparams). One rank, Float64.
+    The graph: (rowptr, colind) is a CSR adjacency of nn = len(rowptr) − 1 nodes, 0-based, columns strictly ascending within a
+    row, no self-loops (the node itself is always an argument and always a column); it may be nonsymmetric (a directed network)
+    and may have no edges. Anything else raises NKError naming the first offending row. dof = 1..4, up to 32 parameters,
+    edge_data and node_data = 0..4 arrays of one double per edge and per node, dof²·(ne + nn) <= 2³¹ − 1.
+    The source: u.self(c = 0) is the node's own unknown c, u.deg() its number of edges, u.nbr(e, c = 0) unknown c of the e-th
+    neighbour (e a run-time loop counter in 0 .. deg() − 1), u.node(e) that neighbour's index, u.w(e, k = 0) datum k of that
+    edge, u.a(k = 0) the node's own datum k and u.an(e, k = 0) the neighbour's; s = {i, nn, deg}; f receives the node's dof
+    residuals, entries not written are zero; nk_real is double. Data are nk_real, never duals. A k outside the declared count
+    (and an e or c out of range) reads NaN.
+    Numbering is component-major: unknown c of node i is element c·nn + i; edge datum k is one double per edge in the order of
+    colind, node datum k one per node. Data are zero until P.set_edge_data(k, x) / P.set_node_data(k, x) — a device tensor or a
+    NumPy array, copied — and P.edge_data(k) / P.node_data(k) return device copies. P.nn, P.ne, P.dof describe the graph.
+    The pattern (graph_pattern, P.jac_csr()): row c·nn + i holds, for c2 = 0 .. dof − 1, node i and its neighbours in ascending
+    node order, dof·(deg_i + 1) entries, structural even where a derivative vanishes.
+    Cost: per node 16·dof + 4 + deg·(4 + 8·r_e) + 8·r_n bytes with r_e, r_n the data arrays the source reads; neighbour values
+    come from cache for a bandwidth-reducing numbering of the nodes and not for a random one — the graph is not reordered for
+    you. The fill evaluates the source once per (node, column node) pair.
+    AC power flow (dof 2 = θ, V; edge data g, b; node data P, Q), every bus a PQ bus:
+        SRC = '''template <typename T>
+        __device__ void nk_node(const nk_nbrs<T> &u, const nk_real *p, nk_vertex s, T *f) {
+          const T th = u.self(0), V = u.self(1);
+          T fp = T(0.0) - u.a(0), fq = T(0.0) - u.a(1);
+          for (int e = 0; e < u.deg(); ++e) {
+            const T d = th - u.nbr(e, 0), VV = V * u.nbr(e, 1);
+            fp = fp + (u.w(e, 0) * V * V - VV * (u.w(e, 0) * cos(d) + u.w(e, 1) * sin(d)));
+            fq = fq + (-u.w(e, 1) * V * V - VV * (u.w(e, 0) * sin(d) - u.w(e, 1) * cos(d)));
+          }
+          f[0] = fp; f[1] = fq;
+        }'''
+        P = CompiledGraphProblem(SRC, rowptr, colind, dof=2, edge_data=2, node_data=2)"""
+    ctx = ctx or default_context()
+    rp, ci, nn = _graph_arrays(rowptr, colind)
+    params = [float(x) for x in params]
+    arr = (C.c_double * max(len(params), 1))(*params)
+    h = C.c_void_p()
+    check(L.lib().nk_problem_create_graph(ctx._h, source.encode(), nn, C.c_void_p(rp.ctypes.data), C.c_void_p(ci.ctypes.data),
+                                          int(dof), arr, len(params), int(edge_data), int(node_data), C.byref(h)))
+    P = _GraphDeviceProblem(h, ctx)
+    P.p, P.nn, P.ne, P.dof, P.n_edge_data, P.n_node_data = params, nn, int(ci.size), int(dof), int(edge_data), int(node_data)
+    return P
+
+
 @dataclass
 class NonlinearFunction:
     """NonlinearFunction{true}(f!; jvp, vjp, jac, jac_prototype) with torch-tensor callbacks on the device:
@@ -819,7 +951,7 @@ class NonlinearProblem:
     def set_p(self, p):
         self.p = p
         dp = self.device_problem
-        if isinstance(dp, _GridDeviceProblem):   # a compiled grid problem: p is the source's p[0..nparams)
+        if isinstance(dp, (_GridDeviceProblem, _GraphDeviceProblem)):   # a compiled problem: p is the source's p[0..nparams)
             dp.set_p(p)
         elif hasattr(dp, "params"):
             params = list(dp.params)

@@ -374,6 +374,9 @@ struct nk_problem {
   // compiled grid problem (nk_problem_create_grid, nk_grid.hip): a user problem whose callbacks launch kernels generated from
   // the user's pointwise source; owns its modules, its parameter buffer and user_pattern (nk_grid_state_destroy)
   struct nk_grid_state *grid = nullptr;
+  // compiled graph problem (nk_problem_create_graph, nk_graph.hip): the same over an arbitrary adjacency; owns its modules, the
+  // graph, its parameter and data buffers and user_pattern (nk_graph_state_destroy)
+  struct nk_graph_state *graph = nullptr;
   // forward-difference JVP for user problems without a jvp callback: f(u) at the linearisation point, u + εv, f(u + εv)
   double *d_fd_f0 = nullptr, *d_fd_up = nullptr, *d_fd_f1 = nullptr;
   // operator fallbacks through the Jacobian (prepare_jvp / prepare_vjp, SciMLJacobianOperators.jl:296-362,373-431): a private
@@ -388,6 +391,8 @@ struct nk_problem {
 };
 void nk_grid_state_destroy(struct nk_grid_state *S);
 int nk_grid_set_params(nk_problem *P, const double *params, int nparams);   // nk_problem_set_params of a compiled grid problem
+void nk_graph_state_destroy(struct nk_graph_state *S);
+int nk_graph_set_params(nk_problem *P, const double *params, int nparams);  // nk_problem_set_params of a compiled graph problem
 // what the geometric multigrid of compiled grid problems (nk_gridmg.hip) asks of nk_grid.hip
 struct nk_grid_shape_info {
   int dim, n[3] /* nx, ny, nz (2-D: nz = 1) */, dof, nfields, radius, kind[6] /* x-lo, x-hi, y-lo, y-hi, z-lo, z-hi */;

@@ -583,6 +583,7 @@ extern "C" int nk_problem_destroy(nk_problem *P) {
   nk_halo_free(&P->halo);
   nk_csr_destroy(P->lin_J);
   nk_grid_state_destroy(P->grid);
+  nk_graph_state_destroy(P->graph);
   delete P;
   return NK_OK;
 }
@@ -594,8 +595,9 @@ extern "C" int nk_problem_size(nk_problem *P, int64_t *n_local, int64_t *n_globa
   return NK_OK;
 }
 extern "C" int nk_problem_set_params(nk_problem *P, const double *params, int nparams) {
-  NK_REQUIRE(P && (params || (P->grid && nparams == 0)), "NULL argument");
+  NK_REQUIRE(P && (params || ((P->grid || P->graph) && nparams == 0)), "NULL argument");
   if (P->grid) return nk_grid_set_params(P, params, nparams);   // up to 32 values, kept on the device for the generated kernels
+  if (P->graph) return nk_graph_set_params(P, params, nparams);
   NK_REQUIRE(nparams == P->nparams, "nparams mismatch (%d vs %d)", nparams, P->nparams);
   if (P->kind == NK_PROBLEM_QUADRATIC) {
     NK_REQUIRE((int64_t)params[0] == P->n_global, "cannot change the problem size");
@@ -1056,8 +1058,8 @@ extern "C" int nk_problem_initial_guess(nk_problem *P, double *u0, int memspace)
       NK_HIP(hipGetLastError());
       break;
     default:
-      if (!P->grid) NK_FAIL(NK_E_UNSUPPORTED, "no built-in initial guess for this problem kind");
-      NK_TRY(nk_blas_fill(P->ctx, P->n_local, 0.0, d));   // compiled grid problem
+      if (!P->grid && !P->graph) NK_FAIL(NK_E_UNSUPPORTED, "no built-in initial guess for this problem kind");
+      NK_TRY(nk_blas_fill(P->ctx, P->n_local, 0.0, d));   // compiled grid or graph problem
       break;
   }
   return out_end(P, u0, memspace, d);

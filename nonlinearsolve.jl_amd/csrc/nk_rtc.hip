@@ -1,5 +1,6 @@
 // hiprtc through dlopen, and the device-side prelude every run-time compiled kernel set starts with: the working precision
-// and the forward-mode dual numbers. Shared by the ensemble kernels (nk_batch.hip) and the compiled grid problems (nk_grid.hip).
+// and the forward-mode dual numbers. Shared by the ensemble kernels (nk_batch.hip), the compiled grid problems (nk_grid.hip)
+// and the compiled graph problems (nk_graph.hip).
 #include <dlfcn.h>
 
 #include <string>
