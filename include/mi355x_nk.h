@@ -727,6 +727,80 @@ int nk_problem_create_graph(nk_ctx *ctx, const char *source, int64_t nn, const i
 int nk_problem_set_graph_data(nk_problem *P, int on_edges, int k, const double *data, int memspace);
 int nk_problem_get_graph_data(nk_problem *P, int on_edges, int k, double *out, int memspace);
 
+/* ---------------------------------------------------------------- compiled element problems (kernel generation, full size)
+ * A finite-element or finite-volume residual given ELEMENT BY ELEMENT on any mesh — in the reference the ordinary assembly loop
+ * inside `f` with jac_prototype = the mesh's sparsity. An element (a triangle, a quad, a tet, a hex, a bar of a truss) reads the
+ * unknowns and the data of its few nodes, does its quadrature once and contributes to the residuals of all its nodes. The user
+ * supplies the connectivity and HIP C++ source defining, per element,
+ *
+ *     template <typename T> __device__ void nk_element(const nk_elemv<T> &u, const nk_real *p, nk_cell s, T *f);
+ *
+ *       u.at(a, c = 0)     unknown c at the element's a-th node, a = 0 .. NK_NPE − 1
+ *       u.node(a)          that node's index
+ *       u.x(a, k = 0)      node datum k at that node (coordinates, a source term, a nodal coefficient)
+ *       u.w(k = 0)         datum k of the element (a conductivity, a thickness, a material number)
+ *       s                  {e, ne, nn}: the element, the element count, the node count
+ *       p                  the parameters;  nk_real is double
+ *       f[a·NK_DOF + c]    the element's contribution to residual c of its a-th node; entries not written are zero
+ *
+ * NK_NPE and NK_DOF are visible to the source as macros. Data are nk_real, never duals: constants of the differentiation. An
+ * a, c or k out of range reads NaN — the project's rule for a wrong source — and node(a) then gives −1. The source is compiled
+ * by hiprtc behind the dual-number prelude with the graph programs' options (-O3 -ffp-contract=off -std=c++17, gfx950) and the
+ * same code-object cache (options + source) into nk_elem_residual and nk_elem_jvp (one element per thread; the JVP is exact:
+ * value from u, partial from v) and nk_elem_jac (one (element, local node b) pair per thread, unit seeds on the dof unknowns of
+ * local node b, so the dual width is dof whatever npe is). A source that does not compile is NK_E_INVALID with this contract
+ * and the compiler's log in nk_last_error. Write loops over a with compile-time bounds (`#pragma unroll`, a < NK_NPE): an f[]
+ * or a local array indexed by a run-time value may be placed in scratch memory, which costs bandwidth, not correctness.
+ *
+ * The mesh: conn[ne·npe], int32, row-major — the nodes of element e are conn[e·npe + a]; all elements have one npe; nn nodes.
+ * Limits: ne >= 1, npe = 2..8, dof = 1..4, npe·dof <= 16, nnode and nelem = 0..4 data arrays per node and per element,
+ * nparams = 0..32; ne·(npe·dof)² and the pattern's entry count both fit in int32. Refused on the host (NK_E_INVALID) before
+ * anything is compiled or allocated, the first offending element named: a node index outside 0 .. nn − 1, a node twice in one
+ * element, and the limits. A node that is in no element is allowed: its rows hold the diagonal only (structural, value 0 unless
+ * the unknown is fixed) and its residual is 0 unless it is fixed. A context of more than one rank gets NK_E_UNSUPPORTED.
+ *
+ * The pattern: two nodes are adjacent when they share an element, and the Jacobian's CSR is nk_graph_pattern of that node
+ * graph — the same slots, the same value layout. nk_elem_adjacency returns the node graph (ascending columns, no self-loops;
+ * NULL arrays: the sizes only), nk_elem_pattern the CSR (NULL arrays: the sizes only); both host only.
+ *
+ * Numbering is component-major: unknown c of node i is element c·nn + i. Node datum k of node i is element k·nn + i and element
+ * datum k of element e element k·ne + e of two device buffers the problem owns, zero at creation; nk_problem_set_elem_data
+ * (on_elements = 1: ne doubles, 0: nn doubles) copies from host or device and marks the problem changed, so a Jacobian cached
+ * for the same u is filled again; nk_problem_get_elem_data copies out.
+ *
+ * Fixed unknowns (Dirichlet rows): nk_problem_set_elem_fixed takes mask[dof·nn] (int32, component-major, 0 = free) and
+ * values[dof·nn] (NULL: zeros); default nothing fixed. A fixed row r has F_r = u_r − g_r, its row of J is the unit row on the
+ * row's structural entries (1 on the diagonal, 0 on the others) and (Jv)_r = v_r. Columns of fixed unknowns stay in the free
+ * rows: the matrix is nonsymmetric. Setting it invalidates a cached Jacobian; nk_problem_get_elem_fixed copies both arrays out
+ * (either may be NULL). nk_problem_initial_guess gives zeros with the fixed values written in.
+ *
+ * Kernels. Every callback is two launches on the stream it is given, both inside the context's per-kernel event timing: the
+ * generated kernel computes every element once and writes its npe·dof numbers (the fill: its (npe·dof)² numbers) into a buffer
+ * the problem owns as coalesced streams — number q of element e at q·ne + e; the device copy of conn is node-major for the same
+ * reason — and k_elem_gather, an ordinary kernel of the library, writes one output per thread: the sum of the row's (the
+ * entry's) list of buffer positions in ascending element order, or what a fixed row holds. The lists are built on the host at
+ * creation, one int32 per (element, a) and one per (element, a, b). No atomics, a fixed order: every result is bit-reproducible
+ * from run to run. A node in very many elements is walked by one thread: correct, not fast.
+ *
+ * The object is an NK_PROBLEM_USER problem like a compiled graph problem: matrix-free GMRES, the concrete-J path, the coloured
+ * assembly, Jᵀv through the transposed SpMV and every `precs` object take it; nk_problem_set_params replaces p,
+ * nk_problem_destroy frees everything; nk_gmres_set_multigrid_preconditioner refuses it (NK_E_INVALID; the aggregation AMG
+ * object is the multigrid of a general CSR). */
+int nk_elem_adjacency(int64_t nn, int64_t ne, int npe, const int32_t *conn, int32_t *rowptr, int32_t *colind, int64_t *nedges);
+int nk_elem_pattern(int64_t nn, int64_t ne, int npe, const int32_t *conn, int dof, int32_t *jrowptr, int32_t *jcolind,
+                    int64_t *nnz);
+int nk_elem_compile_check(const char *source, int npe, int dof, int nparams, int nnode, int nelem, int64_t *code_bytes);
+/* the code object of one of the two programs, for inspection (jac = 0: nk_elem_residual and nk_elem_jvp; 1: nk_elem_jac);
+ * buf NULL: the size only. Host only */
+int nk_elem_code_object(const char *source, int npe, int dof, int nparams, int nnode, int nelem, int jac, void *buf,
+                        int64_t capacity, int64_t *bytes);
+int nk_problem_create_elements(nk_ctx *ctx, const char *source, int64_t nn, int64_t ne, int npe, const int32_t *conn, int dof,
+                               const double *params, int nparams, int nnode, int nelem, nk_problem **out);
+int nk_problem_set_elem_data(nk_problem *P, int on_elements, int k, const double *data, int memspace);
+int nk_problem_get_elem_data(nk_problem *P, int on_elements, int k, double *out, int memspace);
+int nk_problem_set_elem_fixed(nk_problem *P, const int32_t *mask, const double *values, int memspace);
+int nk_problem_get_elem_fixed(nk_problem *P, int32_t *mask, double *values, int memspace);
+
 /* ---------------------------------------------------------------- GMRES (seam 1) */
 /* restart_m: the restart length m, 1 <= m <= 63 (the dot-product kernels take at most 64 columns at once); restart_m <= 0 means 30;
  * restart_m >= 64 is NK_E_INVALID with a message that names the limit, before anything is allocated or launched. */

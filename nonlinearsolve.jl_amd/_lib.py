@@ -217,6 +217,15 @@ SIGNATURES = {
     "nk_problem_create_graph": (_I, [_P, C.c_char_p, _L, _P, _P, _I, C.POINTER(_D), _I, _I, _I, _PP]),
     "nk_problem_set_graph_data": (_I, [_P, _I, _I, _P, _I]),
     "nk_problem_get_graph_data": (_I, [_P, _I, _I, _P, _I]),
+    "nk_elem_adjacency": (_I, [_L, _L, _I, _P, _P, _P, C.POINTER(_L)]),
+    "nk_elem_pattern": (_I, [_L, _L, _I, _P, _I, _P, _P, C.POINTER(_L)]),
+    "nk_elem_compile_check": (_I, [C.c_char_p, _I, _I, _I, _I, _I, C.POINTER(_L)]),
+    "nk_elem_code_object": (_I, [C.c_char_p, _I, _I, _I, _I, _I, _I, _P, _L, C.POINTER(_L)]),
+    "nk_problem_create_elements": (_I, [_P, C.c_char_p, _L, _L, _I, _P, _I, C.POINTER(_D), _I, _I, _I, _PP]),
+    "nk_problem_set_elem_data": (_I, [_P, _I, _I, _P, _I]),
+    "nk_problem_get_elem_data": (_I, [_P, _I, _I, _P, _I]),
+    "nk_problem_set_elem_fixed": (_I, [_P, _P, _P, _I]),
+    "nk_problem_get_elem_fixed": (_I, [_P, _P, _P, _I]),
     "nk_gmres_create": (_I, [_P, _L, _I, _I, _PP]),
     "nk_gmres_destroy": (_I, [_P]),
     "nk_gmres_set_operator_csr": (_I, [_P, _P]),

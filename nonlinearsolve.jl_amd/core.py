@@ -869,6 +869,148 @@ def CompiledGraphProblem(source: str, rowptr, colind, dof: int = 1, params: Sequ
     return P
 
 
+# ------------------------------------------------------------------------------------------- compiled element problems
+def _elem_arrays(conn, nn):
+    """the connectivity as a contiguous int32 host array [ne, npe]"""
+    cn = np.ascontiguousarray(np.asarray(conn), dtype=np.int32)
+    if cn.ndim != 2 or cn.shape[0] < 1:
+        raise ValueError(f"conn has shape {cn.shape}: a mesh is [ne >= 1, npe] node indices, one row per element")
+    return cn, int(nn), int(cn.shape[0]), int(cn.shape[1])
+
+
+def elem_adjacency(conn, nn: int):
+    """(rowptr, colind), int32: the node graph of the mesh conn[ne, npe] over nn nodes — two nodes are adjacent when they share
+    an element; ascending columns, no self-loops. Host only. A mesh that breaks a rule of CompiledElementProblem raises NKError
+    naming the first offending element."""
+    cn, nn, ne, npe = _elem_arrays(conn, nn)
+    pc, nedges = C.c_void_p(cn.ctypes.data), C.c_int64()
+    check(L.lib().nk_elem_adjacency(nn, ne, npe, pc, None, None, C.byref(nedges)))
+    rp, ci = np.empty(nn + 1, dtype=np.int32), np.empty(nedges.value, dtype=np.int32)
+    check(L.lib().nk_elem_adjacency(nn, ne, npe, pc, C.c_void_p(rp.ctypes.data), C.c_void_p(ci.ctypes.data), C.byref(nedges)))
+    return rp, ci
+
+
+def elem_pattern(conn, nn: int, dof: int = 1):
+    """(jrowptr, jcolind), int32, of the Jacobian of a compiled element problem on the mesh conn[ne, npe] over nn nodes:
+    graph_pattern of elem_adjacency(conn, nn). Host only."""
+    cn, nn, ne, npe = _elem_arrays(conn, nn)
+    pc, nnz = C.c_void_p(cn.ctypes.data), C.c_int64()
+    check(L.lib().nk_elem_pattern(nn, ne, npe, pc, int(dof), None, None, C.byref(nnz)))
+    jrp, jci = np.empty(dof * nn + 1, dtype=np.int32), np.empty(nnz.value, dtype=np.int32)
+    check(L.lib().nk_elem_pattern(nn, ne, npe, pc, int(dof), C.c_void_p(jrp.ctypes.data), C.c_void_p(jci.ctypes.data), C.byref(nnz)))
+    return jrp, jci
+
+
+def elem_compile_check(source: str, npe: int, dof: int = 1, nparams: int = 0, node_data: int = 0, elem_data: int = 0) -> int:
+    """Compile the residual, JVP and element-matrix kernels of a CompiledElementProblem source for gfx950 (no device needed); the
+    size of the code objects. A source that does not compile raises NKError with the contract and the compiler's log."""
+    nb = C.c_int64()
+    check(L.lib().nk_elem_compile_check(source.encode(), int(npe), int(dof), int(nparams), int(node_data), int(elem_data), C.byref(nb)))
+    return nb.value
+
+
+class _ElemDeviceProblem(DeviceProblem):
+    """the nk_problem of CompiledElementProblem: the pattern, the node and element data and the fixed unknowns belong to it"""
+    jac_csr, set_p = _GraphDeviceProblem.jac_csr, _GraphDeviceProblem.set_p
+
+    def _set_data(self, on_elements, k, x):
+        what, n = ("element", self.ne) if on_elements else ("node", self.nn)
+        size = x.numel() if _is_torch(x) else np.size(x)
+        if size != n:
+            raise ValueError(f"{what} datum {k}: expected {n} elements (one per {what}), got {size}")
+        px, ms, _keep = _ptr(x, n)
+        check(L.lib().nk_problem_set_elem_data(self._h, on_elements, int(k), px, ms))
+
+    def _get_data(self, on_elements, k):
+        out = torch.empty(self.ne if on_elements else self.nn, dtype=torch.float64, device=f"cuda:{self.ctx.device}")
+        check(L.lib().nk_problem_get_elem_data(self._h, on_elements, int(k), C.c_void_p(out.data_ptr()), L.DEVICE))
+        return out
+
+    def set_node_data(self, k: int, x):
+        """Replace node datum k (0 .. node_data − 1) by x: one float64 per node. Copied, like set_elem_data."""
+        self._set_data(0, k, x)
+
+    def node_data(self, k: int):
+        """a copy of node datum k as a device tensor"""
+        return self._get_data(0, k)
+
+    def set_elem_data(self, k: int, x):
+        """Replace element datum k (0 .. elem_data − 1) by x: a device tensor or a NumPy array of one float64 per element. The
+        data is copied; a Jacobian cached for the same u is filled again."""
+        self._set_data(1, k, x)
+
+    def elem_data(self, k: int):
+        """a copy of element datum k as a device tensor"""
+        return self._get_data(1, k)
+
+    def set_fixed(self, mask, values=None):
+        """Fix the unknowns with mask != 0 (dof·nn entries, component-major) at `values` (dof·nn float64; None: zeros): their
+        rows become F_r = u_r − g_r with the unit row in J. A mask of zeros frees everything again. Host arrays, copied."""
+        n = self.dof * self.nn
+        m = np.ascontiguousarray(np.asarray(mask).ravel() != 0, dtype=np.int32)
+        if m.size != n:
+            raise ValueError(f"mask: expected {n} entries (dof·nn, component-major), got {m.size}")
+        g = None
+        if values is not None:
+            g = np.ascontiguousarray(values.detach().cpu().numpy() if _is_torch(values) else values, dtype=np.float64).ravel()
+            if g.size != n:
+                raise ValueError(f"values: expected {n} entries (dof·nn, component-major), got {g.size}")
+        check(L.lib().nk_problem_set_elem_fixed(self._h, C.c_void_p(m.ctypes.data), None if g is None else C.c_void_p(g.ctypes.data),
+                                                L.HOST))
+
+    def fixed(self):
+        """(mask int32, values float64) as NumPy arrays of dof·nn entries"""
+        n = self.dof * self.nn
+        m, g = np.empty(n, dtype=np.int32), np.empty(n, dtype=np.float64)
+        check(L.lib().nk_problem_get_elem_fixed(self._h, C.c_void_p(m.ctypes.data), C.c_void_p(g.ctypes.data), L.HOST))
+        return m, g
+
+
+def CompiledElementProblem(source: str, conn, nn: int, dof: int = 1, params: Sequence[float] = (), ctx=None, *, node_data: int = 0,
+                           elem_data: int = 0) -> DeviceProblem:
+    """A finite-element / finite-volume residual given element by element on any mesh, as HIP source
+        template <typename T> __device__ void nk_element(const nk_elemv<T> &u, const nk_real *p, nk_cell s, T *f);
+    compiled (hiprtc, gfx950) into the element-residual kernel, the exact dual-number JVP kernel and the element-matrix kernel;
+    a gather kernel of the library sums an element's contributions into rows of F, of J·v and entries of J in ascending
+    element order, without atomics (include/mi355x_nk.h, "compiled element problems"). In the reference this is the assembly
+    loop inside `f` with jac_prototype = the mesh's sparsity. Every solver, linear solver and `precs` object takes it (the
+    scalable one is ObjectPrecs("amg"); MultigridPrecs needs a grid and is refused). One rank, Float64.
+    The mesh: conn[ne, npe] int32, the nodes of every element (all elements have one npe = 2..8), over nn nodes; dof = 1..4 with
+    npe·dof <= 16; up to 32 parameters and node_data, elem_data = 0..4 arrays of one double per node and per element. A node
+    index outside 0..nn−1 or a node twice in one element raises NKError naming the first offending element. A node in no
+    element is allowed (its residual is 0 unless it is fixed).
+    The source: u.at(a, c = 0) is unknown c at the element's a-th node (a = 0 .. NK_NPE − 1), u.node(a) that node's index,
+    u.x(a, k = 0) node datum k at that node, u.w(k = 0) datum k of the element, s = {e, ne, nn}, and f[a·NK_DOF + c] receives
+    the element's contribution to residual c of its a-th node (entries not written are zero). Data are nk_real, never duals; an
+    a, c or k out of range reads NaN. Write loops over a with compile-time bounds (#pragma unroll).
+    Numbering is component-major: unknown c of node i is element c·nn + i. Data are zero until P.set_node_data(k, x) /
+    P.set_elem_data(k, x); P.node_data(k) / P.elem_data(k) return device copies. P.nn, P.ne, P.npe, P.dof describe the mesh.
+    Fixed unknowns: P.set_fixed(mask, values=None) makes the rows with mask != 0 Dirichlet rows, F_r = u_r − g_r, unit row in J
+    (columns of fixed unknowns stay in the free rows); P.fixed() returns (mask, values); P.initial_guess() is zeros with the
+    fixed values written in. The pattern (elem_pattern, P.jac_csr()) is graph_pattern of elem_adjacency(conn, nn).
+    P1 Bratu −Δu = λ·exp(u) on triangles (node data x, y; the exponential lumped at the nodes):
+        SRC = '''template <typename T>
+        __device__ void nk_element(const nk_elemv<T> &u, const nk_real *p, nk_cell s, T *f) {
+          const nk_real x1 = u.x(1, 0) - u.x(0, 0), y1 = u.x(1, 1) - u.x(0, 1), x2 = u.x(2, 0) - u.x(0, 0), y2 = u.x(2, 1) - u.x(0, 1);
+          const nk_real det = x1 * y2 - x2 * y1, area = 0.5 * fabs(det);
+          const nk_real bx[3] = {(y1 - y2) / det, y2 / det, -y1 / det}, by[3] = {(x2 - x1) / det, -x2 / det, x1 / det};
+          const T gx = bx[0] * u.at(0) + bx[1] * u.at(1) + bx[2] * u.at(2), gy = by[0] * u.at(0) + by[1] * u.at(1) + by[2] * u.at(2);
+        #pragma unroll
+          for (int a = 0; a < 3; ++a) f[a] = area * (gx * bx[a] + gy * by[a]) - (p[0] * area / 3.0) * exp(u.at(a));
+        }'''
+        P = CompiledElementProblem(SRC, conn, nn, params=[1.0], node_data=2); P.set_fixed(boundary_mask)"""
+    ctx = ctx or default_context()
+    cn, nn, ne, npe = _elem_arrays(conn, nn)
+    params = [float(x) for x in params]
+    arr = (C.c_double * max(len(params), 1))(*params)
+    h = C.c_void_p()
+    check(L.lib().nk_problem_create_elements(ctx._h, source.encode(), nn, ne, npe, C.c_void_p(cn.ctypes.data), int(dof), arr,
+                                             len(params), int(node_data), int(elem_data), C.byref(h)))
+    P = _ElemDeviceProblem(h, ctx)
+    P.p, P.nn, P.ne, P.npe, P.dof, P.n_node_data, P.n_elem_data = params, nn, ne, npe, int(dof), int(node_data), int(elem_data)
+    return P
+
+
 @dataclass
 class NonlinearFunction:
     """NonlinearFunction{true}(f!; jvp, vjp, jac, jac_prototype) with torch-tensor callbacks on the device:
@@ -951,7 +1093,7 @@ class NonlinearProblem:
     def set_p(self, p):
         self.p = p
         dp = self.device_problem
-        if isinstance(dp, (_GridDeviceProblem, _GraphDeviceProblem)):   # a compiled problem: p is the source's p[0..nparams)
+        if isinstance(dp, (_GridDeviceProblem, _GraphDeviceProblem, _ElemDeviceProblem)):   # a compiled problem: p is the source's p[0..nparams)
             dp.set_p(p)
         elif hasattr(dp, "params"):
             params = list(dp.params)

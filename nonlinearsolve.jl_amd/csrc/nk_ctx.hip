@@ -170,7 +170,8 @@ extern "C" int nk_ctx_set_deterministic(nk_ctx *ctx, int d) {
 
 // ----------------------------------------------------------------------------- kernel-family profiling
 static const char *k_names[NK_K_COUNT] = {"spmv", "multidot", "multiaxpy", "jvp", "residual", "scale",
-                                          "reduce_small", "jacfill", "newton_update", "other", "spmv_powers"};
+                                          "reduce_small", "jacfill", "newton_update", "other", "spmv_powers",
+                                          "elem_gather"};
 void nk_prof_scope_begin(nk_ctx *ctx, int id, double bytes) {
   ctx->prof.cur_id = id;
   ctx->prof.cur_bytes = bytes;
@@ -205,7 +206,7 @@ void nk_prof_flush(nk_ctx *ctx) {
     if (hipEventElapsedTime(&ms, p.ev[2 * r], p.ev[2 * r + 1]) == hipSuccess) {
       p.ms[p.ids[r]] += ms;
       p.bytes[p.ids[r]] += p.nbytes[r];
-      if (p.nbytes[r] > 0.0 || p.ids[r] == NK_K_REDUCE_SMALL || p.ids[r] == NK_K_OTHER) p.count[p.ids[r]]++;
+      if (p.nbytes[r] > 0.0 || p.ids[r] == NK_K_REDUCE_SMALL || p.ids[r] == NK_K_OTHER || p.ids[r] == NK_K_ELEM_GATHER) p.count[p.ids[r]]++;
     }
   }
   p.ids.clear();

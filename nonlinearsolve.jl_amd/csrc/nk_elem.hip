@@ -1,0 +1,685 @@
+// Compiled element problems: a finite-element / finite-volume residual given element by element on any mesh, handed over as
+// HIP C++ source
+//     template <typename T> __device__ void nk_element(const nk_elemv<T> &u, const nk_real *p, nk_cell s, T *f);
+// and compiled at run time (hiprtc, gfx950) — the third compiled kind beside grids (nk_grid.hip) and graphs (nk_graph.hip). In
+// the reference this is the ordinary assembly loop inside `f` with jac_prototype = the mesh's sparsity. An element reads the
+// unknowns and the data of its NK_NPE nodes, does its quadrature ONCE and contributes to the residuals of all its nodes.
+//
+//   nk_elem_residual   T = nk_real                              one element per thread            → B
+//   nk_elem_jvp        T = Dual, NK_CH = 1: value u, partial v  one element per thread            → B
+//   nk_elem_jac        T = Dual, NK_CH = dof, unit seeds        one (element, local node b) pair  → M
+//   k_elem_gather      (not generated) one output per thread: the sum of a list of buffer entries in ascending element order
+//
+// Layout. L = npe·dof numbers per element. The device copy of the connectivity is node-major, node a of element e at a·ne + e,
+// so a wavefront's index loads are consecutive. B holds L streams of ne doubles, number (a, c) of element e at (a·dof + c)·ne + e;
+// M holds L² streams, dF_{a,c}/du_{b,c2} of element e at ((a·dof + c)·L + b·dof + c2)·ne + e. Every store of a generated kernel
+// is therefore one coalesced stream per register. Node datum k of node i is element k·nn + i, element datum k of element e
+// element k·ne + e of two buffers the problem owns (zero at creation).
+//
+// The gather. Two nodes are adjacent when they share an element; the Jacobian's CSR is the graph pattern of that adjacency
+// (nk_graph_pattern's slots and value layout). Built on the host at creation:
+//   the row list of node i          one int32 per (element, a) with conn[e, a] = i:  a·dof·ne + e, elements ascending
+//   the entry list of slot (i, j)   one int32 per (element, a, b) with conn[e, a] = i and conn[e, b] = j:
+//                                   (a·dof·L + b·dof)·ne + e, elements ascending
+// The component offsets are arithmetic (c·ne; (c·L + c2)·ne), so the lists are not multiplied by the components. One thread
+// walks one list per component (pair) and adds in list order: no atomics, a fixed order, bit-reproducible. A node in 300
+// elements is walked by one thread — correct, not fast (the stance nk_graph.hip takes for a hub).
+//
+// Fixed unknowns (nk_problem_set_elem_fixed): a mask and values of dof·nn entries, component-major. The gather writes
+// F_r = u_r − g_r, (Jv)_r = v_r and the unit row (1 on the diagonal, 0 on the row's other structural entries) for a fixed row
+// r; columns of fixed unknowns stay in the free rows, so J is nonsymmetric.
+//
+// The result is an NK_PROBLEM_USER problem with user_pattern set, exactly as nk_problem_create_graph builds one. One rank.
+#include <stdlib.h>
+#include <string.h>
+
+#include <algorithm>
+#include <initializer_list>
+#include <map>
+#include <mutex>
+#include <string>
+#include <vector>
+
+#include "nk_internal.h"
+
+// ----------------------------------------------------------------------------- the mesh (host only)
+static int elem_check_shape(int npe, int dof) {
+  NK_REQUIRE(npe >= 2 && npe <= 8, "npe = %d outside 2..8 (nodes per element)", npe);
+  NK_REQUIRE(dof >= 1 && dof <= 4, "dof = %d outside 1..4 (components per node)", dof);
+  NK_REQUIRE(npe * dof <= 16, "npe·dof = %d·%d = %d exceeds 16 (the numbers one element contributes)", npe, dof, npe * dof);
+  return NK_OK;
+}
+
+// every rule of the header, the first offending element named
+static int elem_validate(int64_t nn, int64_t ne, int npe, const int32_t *conn, int dof) {
+  NK_TRY(elem_check_shape(npe, dof));
+  NK_REQUIRE(nn >= 1 && nn <= INT32_MAX, "nn = %lld: a mesh has 1..INT32_MAX nodes", (long long)nn);
+  NK_REQUIRE(ne >= 1, "ne = %lld: a mesh has at least one element", (long long)ne);
+  const int64_t L = (int64_t)npe * dof;
+  NK_REQUIRE(ne <= (int64_t)INT32_MAX / (L * L), "%lld elements with npe = %d, dof = %d: ne·(npe·dof)² exceeds INT32_MAX, the "
+             "element-matrix buffer's 32-bit indices cannot hold it", (long long)ne, npe, dof);
+  NK_REQUIRE(conn, "NULL conn");
+  for (int64_t e = 0; e < ne; ++e)
+    for (int a = 0; a < npe; ++a) {
+      const int64_t j = conn[e * npe + a];
+      NK_REQUIRE(j >= 0 && j < nn, "element %lld: node %lld (local node %d) outside 0..%lld", (long long)e, (long long)j, a,
+                 (long long)nn - 1);
+      for (int b = 0; b < a; ++b)
+        NK_REQUIRE(conn[e * npe + b] != j, "element %lld: node %lld twice (local nodes %d and %d) — the nodes of one element are "
+                   "distinct", (long long)e, (long long)j, b, a);
+    }
+  return NK_OK;
+}
+
+// the node graph of a validated mesh: i and j adjacent when an element holds both; ascending columns, no self-loops
+static int elem_adjacency_build(int64_t nn, int64_t ne, int npe, const int32_t *conn, std::vector<int32_t> *rp,
+                                std::vector<int32_t> *ci) {
+  std::vector<int64_t> at((size_t)nn + 1, 0);
+  for (int64_t q = 0; q < ne * npe; ++q) at[(size_t)conn[q] + 1] += npe - 1;
+  for (int64_t i = 0; i < nn; ++i) at[(size_t)i + 1] += at[(size_t)i];
+  std::vector<int32_t> all((size_t)at[(size_t)nn]);
+  std::vector<int64_t> fill(at.begin(), at.end() - 1);
+  for (int64_t e = 0; e < ne; ++e)
+    for (int a = 0; a < npe; ++a)
+      for (int b = 0; b < npe; ++b)
+        if (b != a) all[(size_t)fill[(size_t)conn[e * npe + a]]++] = conn[e * npe + b];
+  rp->assign((size_t)nn + 1, 0);
+  int64_t total = 0;
+  for (int64_t i = 0; i < nn; ++i) {
+    int32_t *b = all.data() + at[(size_t)i], *e = all.data() + at[(size_t)i + 1];
+    std::sort(b, e);
+    const int64_t cnt = std::unique(b, e) - b;
+    // (compacted in place: the rows before i have already shrunk, so `total` never passes at[i])
+    std::copy(b, b + cnt, all.data() + total);
+    total += cnt;
+    NK_REQUIRE(total <= INT32_MAX, "the node graph of the mesh has more than INT32_MAX edges");
+    (*rp)[(size_t)i + 1] = (int32_t)total;
+  }
+  all.resize((size_t)total);
+  ci->swap(all);
+  return NK_OK;
+}
+
+extern "C" int nk_elem_adjacency(int64_t nn, int64_t ne, int npe, const int32_t *conn, int32_t *rowptr, int32_t *colind,
+                                 int64_t *nedges) {
+  NK_REQUIRE(rowptr || nedges, "NULL argument");
+  NK_TRY(elem_validate(nn, ne, npe, conn, 1));
+  std::vector<int32_t> rp, ci;
+  NK_TRY(elem_adjacency_build(nn, ne, npe, conn, &rp, &ci));
+  if (rowptr) memcpy(rowptr, rp.data(), rp.size() * sizeof(int32_t));
+  if (colind && !ci.empty()) memcpy(colind, ci.data(), ci.size() * sizeof(int32_t));
+  if (nedges) *nedges = (int64_t)ci.size();
+  return NK_OK;
+}
+
+// the Jacobian's CSR: nk_graph_pattern of the node graph (its slot numbering, its value layout, its int32 limit)
+extern "C" int nk_elem_pattern(int64_t nn, int64_t ne, int npe, const int32_t *conn, int dof, int32_t *jrowptr, int32_t *jcolind,
+                               int64_t *nnz) {
+  NK_REQUIRE(jrowptr || nnz, "NULL argument");
+  NK_TRY(elem_validate(nn, ne, npe, conn, dof));
+  std::vector<int32_t> rp, ci;
+  NK_TRY(elem_adjacency_build(nn, ne, npe, conn, &rp, &ci));
+  return nk_graph_pattern(nn, rp.data(), ci.data(), dof, jrowptr, jcolind, nnz);
+}
+
+// ----------------------------------------------------------------------------- device source (compiled by hiprtc)
+// The program is: nk_dual_prelude, k_elem_types, the user's source, k_elem_kernels. What a program is comes from its options:
+// -DNK_NPE, -DNK_DOF, -DNK_NNODE, -DNK_NELEM (the data arrays per node and per element), -DNK_CH and -DNK_ELEM_SET (0: residual
+// and JVP, 1: the fill).
+static const char *k_elem_types = R"NKSRC(
+// ---- compiled element problems: the element and its nodes
+#define NK_ELEM_BLOCK 256
+struct nk_cell { int e, ne, nn; };
+// an nk_real read from u becomes the source's T: itself, the dual with its one partial from v (NK_ELEM_SET == 0), or the dual
+// with the unit seed of component c if the value belongs to the thread's local node (`hot`) and no partial otherwise
+template <typename T> struct nk_elem_lift;
+template <> struct nk_elem_lift<nk_real> {
+  static __device__ __forceinline__ nk_real at(nk_real x, const nk_real *, int, int, bool) { return x; }
+};
+template <> struct nk_elem_lift<Dual> {
+  static __device__ __forceinline__ Dual at(nk_real x, const nk_real *__restrict__ v, int el, int c, bool hot) {
+    Dual r;
+    r.v = x;
+#if NK_ELEM_SET == 0
+    r.d[0] = v[el];
+#else
+#pragma unroll
+    for (int t = 0; t < NK_CH; ++t) r.d[t] = (hot && t == c) ? NK_R(1) : NK_R(0);
+#endif
+    return r;
+  }
+};
+// What the source sees of element e. Unknowns are T, data are nk_real (constants of the differentiation). A local node a
+// outside 0..NK_NPE-1, a component outside 0..NK_DOF-1 and a datum k outside the declared count read NaN (node(a): -1): a wrong
+// source shows at once and reads nothing it does not own
+template <typename T>
+struct nk_elemv {
+  const nk_real *__restrict__ nk_u;
+  const nk_real *__restrict__ nk_v;
+  const int *__restrict__ nk_conn;     // node-major, already at the element: local node a at nk_conn[a·ne]
+  const nk_real *__restrict__ nk_nd;   // datum k of node j: nk_nd[k·nn + j]
+  const nk_real *__restrict__ nk_ed;   // already at the element: datum k at nk_ed[k·ne]
+  int nk_nn, nk_ne, nk_hot;            // nk_hot: the local node that carries the unit seeds (the fill), else -1
+  __device__ __forceinline__ int node(int a) const { return (unsigned)a < (unsigned)NK_NPE ? nk_conn[(long)a * nk_ne] : -1; }
+  __device__ __forceinline__ T at(int a, int c = 0) const {
+    if ((unsigned)a >= (unsigned)NK_NPE || (unsigned)c >= (unsigned)NK_DOF) return T(NK_R(__builtin_nan("")));
+    const int el = c * nk_nn + nk_conn[(long)a * nk_ne];
+    return nk_elem_lift<T>::at(nk_u[el], nk_v, el, c, nk_hot == a);
+  }
+  __device__ __forceinline__ nk_real x(int a, int k = 0) const {
+    if ((unsigned)a >= (unsigned)NK_NPE || (unsigned)k >= (unsigned)NK_NNODE) return NK_R(__builtin_nan(""));
+    return nk_nd[(long)k * nk_nn + nk_conn[(long)a * nk_ne]];
+  }
+  __device__ __forceinline__ nk_real w(int k = 0) const {
+    if ((unsigned)k >= (unsigned)NK_NELEM) return NK_R(__builtin_nan(""));
+    return nk_ed[(long)k * nk_ne];
+  }
+};
+)NKSRC";
+
+static const char *k_elem_kernels = R"NKSRC(
+// ---- generated kernels
+#define NK_EL (NK_NPE * NK_DOF)
+// the mesh as every kernel gets it: nn, ne, the node-major connectivity, then p, the node data and the element data
+#define NK_ELEM_PARAMS int nn, int ne, const int *__restrict__ conn, const nk_real *__restrict__ p, \
+                       const nk_real *__restrict__ nd, const nk_real *__restrict__ ed
+template <typename T>
+__device__ __forceinline__ nk_elemv<T> nk_elem_view(int nn, int ne, const int *__restrict__ conn, const nk_real *__restrict__ nd,
+                                                    const nk_real *__restrict__ ed, const nk_real *__restrict__ u,
+                                                    const nk_real *__restrict__ v, int e, int hot) {
+  nk_elemv<T> w;
+  w.nk_u = u, w.nk_v = v, w.nk_conn = conn + e, w.nk_nd = nd, w.nk_ed = ed + e;
+  w.nk_nn = nn, w.nk_ne = ne, w.nk_hot = hot;
+  return w;
+}
+
+#if NK_ELEM_SET == 0
+extern "C" __global__ void __launch_bounds__(NK_ELEM_BLOCK)
+nk_elem_residual(NK_ELEM_PARAMS, const nk_real *__restrict__ u, nk_real *__restrict__ B) {
+  const int e = (int)blockIdx.x * NK_ELEM_BLOCK + (int)threadIdx.x;
+  if (e >= ne) return;
+  const nk_elemv<nk_real> w = nk_elem_view<nk_real>(nn, ne, conn, nd, ed, u, nullptr, e, -1);
+  nk_real out[NK_EL];
+#pragma unroll
+  for (int q = 0; q < NK_EL; ++q) out[q] = NK_R(0);
+  nk_element<nk_real>(w, p, nk_cell{e, ne, nn}, out);
+#pragma unroll
+  for (int q = 0; q < NK_EL; ++q) B[q * ne + e] = out[q];
+}
+
+// the element's share of J(u)·v exactly: the value of every unknown from u, its one partial from v
+extern "C" __global__ void __launch_bounds__(NK_ELEM_BLOCK)
+nk_elem_jvp(NK_ELEM_PARAMS, const nk_real *__restrict__ u, const nk_real *__restrict__ v, nk_real *__restrict__ B) {
+  const int e = (int)blockIdx.x * NK_ELEM_BLOCK + (int)threadIdx.x;
+  if (e >= ne) return;
+  const nk_elemv<Dual> w = nk_elem_view<Dual>(nn, ne, conn, nd, ed, u, v, e, -1);
+  Dual out[NK_EL];
+#pragma unroll
+  for (int q = 0; q < NK_EL; ++q) out[q] = Dual(NK_R(0));
+  nk_element<Dual>(w, p, nk_cell{e, ne, nn}, out);
+#pragma unroll
+  for (int q = 0; q < NK_EL; ++q) B[q * ne + e] = out[q].d[0];
+}
+#else
+// The element matrices: thread t takes local node b = t / ne of element e = t − b·ne (consecutive threads, consecutive
+// elements), seeds the dof unknowns of local node b and stores dF_{a,c}/du_{b,c2} for all a, c, c2 — one stream each
+extern "C" __global__ void __launch_bounds__(NK_ELEM_BLOCK)
+nk_elem_jac(NK_ELEM_PARAMS, const nk_real *__restrict__ u, nk_real *__restrict__ M) {
+  const unsigned tu = blockIdx.x * (unsigned)NK_ELEM_BLOCK + threadIdx.x;
+  if (tu >= (unsigned)ne * (unsigned)NK_NPE) return;
+  const int b = (int)(tu / (unsigned)ne), e = (int)(tu - (unsigned)b * (unsigned)ne);
+  const nk_elemv<Dual> w = nk_elem_view<Dual>(nn, ne, conn, nd, ed, u, nullptr, e, b);
+  Dual out[NK_EL];
+#pragma unroll
+  for (int q = 0; q < NK_EL; ++q) out[q] = Dual(NK_R(0));
+  nk_element<Dual>(w, p, nk_cell{e, ne, nn}, out);
+#pragma unroll
+  for (int q = 0; q < NK_EL; ++q) {
+#pragma unroll
+    for (int c2 = 0; c2 < NK_DOF; ++c2) M[(q * NK_EL + b * NK_DOF + c2) * ne + e] = out[q].d[c2];
+  }
+}
+#endif
+)NKSRC";
+
+// what the user's source is held to, for the message of a source that does not compile
+static const char *k_elem_contract =
+    "the contract is `template <typename T> __device__ void nk_element(const nk_elemv<T> &u, const nk_real *p, nk_cell s, T *f)` "
+    "with u.at(a, c) unknown c at the element's a-th node (a = 0..NK_NPE-1), u.node(a) that node's index, u.x(a, k) node datum k "
+    "at that node, u.w(k) datum k of the element (data are nk_real, never duals), s = {e, ne, nn}, p the parameters and "
+    "f[a*NK_DOF + c] the element's contribution to residual c of its a-th node (nk_real = double)";
+
+// ----------------------------------------------------------------------------- compilation
+enum { ESET_F = 0 /* nk_elem_residual + nk_elem_jvp, NK_CH = 1 */, ESET_JAC = 1 /* nk_elem_jac, NK_CH = dof */ };
+
+static int elem_check_counts(int npe, int dof, int np, int nnode, int nelem) {
+  NK_TRY(elem_check_shape(npe, dof));
+  NK_REQUIRE(np >= 0 && np <= 32, "nparams = %d outside 0..32", np);
+  NK_REQUIRE(nnode >= 0 && nnode <= 4, "nnode = %d outside 0..4 (data arrays of one double per node)", nnode);
+  NK_REQUIRE(nelem >= 0 && nelem <= 4, "nelem = %d outside 0..4 (data arrays of one double per element)", nelem);
+  return NK_OK;
+}
+
+static int elem_compile(const char *source, int npe, int dof, int np, int nnode, int nelem, int eset, std::vector<char> *code,
+                        std::string *log) {
+  NK_REQUIRE(source, "NULL source");
+  NK_TRY(elem_check_counts(npe, dof, np, nnode, nelem));
+  const std::string full = std::string(nk_dual_prelude) + k_elem_types + "\n// ---- user source\n" + source + "\n" + k_elem_kernels;
+  const std::string defs[] = {"-DNK_NPE=" + std::to_string(npe), "-DNK_DOF=" + std::to_string(dof),
+                              "-DNK_NNODE=" + std::to_string(nnode), "-DNK_NELEM=" + std::to_string(nelem),
+                              "-DNK_CH=" + std::to_string(eset == ESET_JAC ? dof : 1), "-DNK_ELEM_SET=" + std::to_string(eset)};
+  std::vector<const char *> opts = {"--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-std=c++17"};
+  for (const std::string &d : defs) opts.push_back(d.c_str());
+  // the same source with the same options gives the same code object: a problem created again (another mesh, another context)
+  // skips the compiler
+  static std::mutex mtx;
+  static std::map<std::string, std::vector<char>> cache;
+  std::string key;
+  for (const char *o : opts) { key += o; key += ' '; }
+  key += source;
+  {
+    std::lock_guard<std::mutex> lock(mtx);
+    auto it = cache.find(key);
+    if (it != cache.end()) { *code = it->second; return NK_OK; }
+  }
+  bool failed = false;
+  NK_TRY(nk_rtc_compile(full, "nk_elem_user.hip", opts, code, log, &failed));
+  if (failed)
+    NK_FAIL(NK_E_INVALID, "element residual source does not compile (%s): %.900s", k_elem_contract,
+            log && !log->empty() ? log->c_str() : "(no log)");
+  std::lock_guard<std::mutex> lock(mtx);
+  cache[key] = *code;
+  return NK_OK;
+}
+
+// compile only (no device needed): both programs
+extern "C" int nk_elem_compile_check(const char *source, int npe, int dof, int nparams, int nnode, int nelem, int64_t *code_bytes) {
+  std::vector<char> code;
+  std::string log;
+  int64_t total = 0;
+  for (int eset : {ESET_F, ESET_JAC}) {
+    log.clear();
+    NK_TRY(elem_compile(source, npe, dof, nparams, nnode, nelem, eset, &code, &log));
+    total += (int64_t)code.size();
+  }
+  if (code_bytes) *code_bytes = total;
+  return NK_OK;
+}
+
+// the code object of one program (jac = 0: the residual and JVP kernels; 1: the element-matrix kernel) for inspection
+extern "C" int nk_elem_code_object(const char *source, int npe, int dof, int nparams, int nnode, int nelem, int jac, void *buf,
+                                   int64_t capacity, int64_t *bytes) {
+  NK_REQUIRE(bytes, "NULL argument");
+  std::vector<char> code;
+  std::string log;
+  NK_TRY(elem_compile(source, npe, dof, nparams, nnode, nelem, jac != 0 ? ESET_JAC : ESET_F, &code, &log));
+  *bytes = (int64_t)code.size();
+  if (!buf) return NK_OK;
+  NK_REQUIRE(capacity >= *bytes, "buffer of %lld bytes, the code object has %lld", (long long)capacity, (long long)*bytes);
+  memcpy(buf, code.data(), code.size());
+  return NK_OK;
+}
+
+// ----------------------------------------------------------------------------- the gather
+enum { GATHER_F = 0, GATHER_JV = 1, GATHER_J = 2 };
+
+// One output per thread (x: the list, y: the component c, or the pair c·dof + c2): out = Σ buf[list[q] + offset] over the
+// thread's list in list order (ascending elements), or what a fixed row holds instead.
+//   GATHER_F / GATHER_JV  item t = node i, offset c·ne, out[c·nn + i]; fixed: x[r] − g[r] / x[r] with x = u / v
+//   GATHER_J              item t = global slot of the pattern (node i = slotnode[t], slot s = t − (arp[i] + i)), offset
+//                         (c·L + c2)·ne, out at nk_graph_pattern's value index; fixed row (c, i): 1 at c2 = c, s = spos[i], else 0
+// Every index is below ne·L² or the pattern's entry count, both checked against INT32_MAX at creation.
+__global__ void __launch_bounds__(256)
+k_elem_gather(int mode, int items, int dof, int nn, int ne, int L, const int *__restrict__ lptr, const int *__restrict__ list,
+              const double *__restrict__ buf, const int *__restrict__ mask, const double *__restrict__ x,
+              const double *__restrict__ g, const int *__restrict__ slotnode, const int *__restrict__ arp,
+              const int *__restrict__ spos, double *__restrict__ out) {
+  const int t = (int)blockIdx.x * 256 + (int)threadIdx.x;
+  if (t >= items) return;
+  const int k = (int)blockIdx.y;
+  int o, off;
+  if (mode != GATHER_J) {
+    o = k * nn + t;
+    off = k * ne;
+    if (mask[o] != 0) {
+      out[o] = mode == GATHER_F ? x[o] - g[o] : x[o];
+      return;
+    }
+  } else {
+    const int c = k / dof, c2 = k - c * dof, i = slotnode[t];
+    const int b = arp[i] + i, wd = arp[i + 1] - arp[i] + 1, s = t - b;
+    o = c * dof * items + dof * b + c2 * wd + s;
+    off = (c * L + c2) * ne;
+    if (mask[c * nn + i] != 0) {
+      out[o] = (c2 == c && s == spos[i]) ? 1.0 : 0.0;
+      return;
+    }
+  }
+  double sum = 0.0;
+  const int q1 = lptr[t + 1];
+  for (int q = lptr[t]; q < q1; ++q) sum += buf[list[q] + off];
+  out[o] = sum;
+}
+
+__global__ void __launch_bounds__(256)
+k_elem_fixed_values(int n, const int *__restrict__ mask, const double *__restrict__ g, double *__restrict__ u) {
+  const int r = (int)blockIdx.x * 256 + (int)threadIdx.x;
+  if (r < n) u[r] = mask[r] != 0 ? g[r] : 0.0;
+}
+
+// ----------------------------------------------------------------------------- the problem object
+struct nk_elem_state {
+  nk_ctx *ctx = nullptr;
+  int nn = 0, ne = 0, npe = 0, dof = 0, np = 0, nnode = 0, nelem = 0, nslots = 0;
+  hipModule_t mod_f = nullptr, mod_jac = nullptr;
+  hipFunction_t fn_res = nullptr, fn_jvp = nullptr, fn_jac = nullptr;
+  int32_t *d_conn = nullptr;                         // node-major: local node a of element e at a·ne + e
+  int32_t *d_arp = nullptr;                          // rowptr of the node graph (nn + 1)
+  int32_t *d_slotnode = nullptr, *d_spos = nullptr;  // the node of every global slot; the self slot of every node
+  int32_t *d_rptr = nullptr, *d_rlist = nullptr;     // the row lists: per node (nn + 1; ne·npe)
+  int32_t *d_eptr = nullptr, *d_elist = nullptr;     // the entry lists: per global slot (nslots + 1; ne·npe²)
+  int32_t *d_mask = nullptr;                         // dof·nn: 0 = free
+  double *d_fixed = nullptr;                         // dof·nn: the value of a fixed unknown
+  double *d_params = nullptr;                        // np doubles (at least one allocated): the source's p
+  double *d_node = nullptr;                          // nnode·nn doubles, zero at creation
+  double *d_elem = nullptr;                          // nelem·ne doubles, zero at creation
+  double *d_B = nullptr;                             // npe·dof·ne: the element vectors
+  double *d_M = nullptr;                             // (npe·dof)²·ne: the element matrices
+  nk_csr *pattern = nullptr;                         // the problem's user_pattern
+};
+
+void nk_elem_state_destroy(nk_elem_state *S) {
+  if (!S) return;
+  if (S->mod_f) hipModuleUnload(S->mod_f);
+  if (S->mod_jac) hipModuleUnload(S->mod_jac);
+  hipFree(S->d_conn);
+  hipFree(S->d_arp);
+  hipFree(S->d_slotnode);
+  hipFree(S->d_spos);
+  hipFree(S->d_rptr);
+  hipFree(S->d_rlist);
+  hipFree(S->d_eptr);
+  hipFree(S->d_elist);
+  hipFree(S->d_mask);
+  hipFree(S->d_fixed);
+  hipFree(S->d_params);
+  hipFree(S->d_node);
+  hipFree(S->d_elem);
+  hipFree(S->d_B);
+  hipFree(S->d_M);
+  nk_csr_destroy(S->pattern);
+  delete S;
+}
+
+// One launch of a generated kernel over `items` threads on `stream`: the mesh and what the problem owns, then `rest`. Inside a
+// profiled scope of the context the launch carries start / stop events like every NK_LAUNCH (as graph_launch does)
+static int elem_launch(nk_elem_state *S, hipFunction_t fn, int64_t items, std::initializer_list<void *> rest, void *stream) {
+  void *args[10] = {&S->nn, &S->ne, &S->d_conn, &S->d_params, &S->d_node, &S->d_elem};
+  int n = 6;
+  for (void *a : rest) args[n++] = a;
+  const unsigned blocks = (unsigned)((items + 255) / 256);
+  hipEvent_t e0, e1;
+  hipError_t e;
+  if (S->ctx->prof.on && (hipStream_t)stream == S->ctx->stream && nk_prof_next(S->ctx, &e0, &e1))
+    e = hipExtModuleLaunchKernel(fn, blocks * 256u, 1, 1, 256, 1, 1, 0, (hipStream_t)stream, args, nullptr, e0, e1, 0);   // (sizes in threads)
+  else
+    e = hipModuleLaunchKernel(fn, blocks, 1, 1, 256, 1, 1, 0, (hipStream_t)stream, args, nullptr);
+  return e != hipSuccess;
+}
+
+// the gather of one callback on the same stream, timed the same way; its time goes to the family "elem_gather", so that the
+// callback's family (residual, jvp, jacfill) holds the generated kernel alone and the two launches can be told apart
+static bool elem_gather_events(nk_ctx *ctx, void *stream, hipEvent_t *e0, hipEvent_t *e1) {
+  nk_prof &p = ctx->prof;
+  if (!p.on || (hipStream_t)stream != ctx->stream || p.cur_id < 0) return false;
+  const int family = p.cur_id;
+  p.cur_id = NK_K_ELEM_GATHER;
+  const bool ok = nk_prof_next(ctx, e0, e1);
+  p.cur_id = family;
+  return ok;
+}
+static int elem_gather(nk_elem_state *S, int mode, const double *x, double *out, void *stream) {
+  const bool jac = mode == GATHER_J;
+  const int items = jac ? S->nslots : S->nn, L = S->npe * S->dof;
+  const dim3 grid((unsigned)((items + 255) / 256), (unsigned)(jac ? S->dof * S->dof : S->dof)), block(256);
+  const int32_t *lptr = jac ? S->d_eptr : S->d_rptr, *list = jac ? S->d_elist : S->d_rlist;
+  const double *buf = jac ? S->d_M : S->d_B;
+  hipEvent_t e0, e1;
+  if (elem_gather_events(S->ctx, stream, &e0, &e1))
+    hipExtLaunchKernelGGL(k_elem_gather, grid, block, 0, (hipStream_t)stream, e0, e1, 0, mode, items, S->dof, S->nn, S->ne, L, lptr,
+                          list, buf, S->d_mask, x, S->d_fixed, S->d_slotnode, S->d_arp, S->d_spos, out);
+  else
+    hipLaunchKernelGGL(k_elem_gather, grid, block, 0, (hipStream_t)stream, mode, items, S->dof, S->nn, S->ne, L, lptr, list, buf,
+                       S->d_mask, x, S->d_fixed, S->d_slotnode, S->d_arp, S->d_spos, out);
+  return hipGetLastError() != hipSuccess;
+}
+
+static int elem_cb_residual(void *user, const double *u, double *f, void *stream) {
+  nk_elem_state *S = (nk_elem_state *)user;
+  if (elem_launch(S, S->fn_res, S->ne, {&u, &S->d_B}, stream)) return 1;
+  return elem_gather(S, GATHER_F, u, f, stream);
+}
+static int elem_cb_jvp(void *user, const double *v, const double *u, double *jv, void *stream) {
+  nk_elem_state *S = (nk_elem_state *)user;
+  if (elem_launch(S, S->fn_jvp, S->ne, {&u, &v, &S->d_B}, stream)) return 1;
+  return elem_gather(S, GATHER_JV, v, jv, stream);
+}
+static int elem_cb_jac(void *user, const double *u, double *vals, void *stream) {
+  nk_elem_state *S = (nk_elem_state *)user;
+  if (elem_launch(S, S->fn_jac, (int64_t)S->ne * S->npe, {&u, &S->d_M}, stream)) return 1;
+  return elem_gather(S, GATHER_J, u, vals, stream);
+}
+
+int nk_elem_set_params(nk_problem *P, const double *params, int nparams) {
+  nk_elem_state *S = P->elem;
+  NK_REQUIRE(nparams == S->np, "nparams mismatch (%d vs %d)", nparams, S->np);
+  NK_HIP(hipSetDevice(S->ctx->device));
+  if (nparams > 0) NK_HIP(nk_memcpy(S->ctx, S->d_params, params, (size_t)nparams * sizeof(double), hipMemcpyHostToDevice));
+  for (int i = 0; i < nparams && i < 8; ++i) P->params[i] = params[i];   // (the first eight, for inspection; the kernels read d_params)
+  P->params_version++;
+  nk_problem_invalidate(P);   // a Jacobian cached for the same u belongs to the old parameters
+  return NK_OK;
+}
+
+// zeros, with the values of the fixed unknowns written in
+int nk_elem_initial_guess(nk_problem *P, double *d_u) {
+  nk_elem_state *S = P->elem;
+  const int n = S->nn * S->dof;
+  NK_LAUNCH(S->ctx, k_elem_fixed_values, dim3((unsigned)((n + 255) / 256)), dim3(256), n, S->d_mask, S->d_fixed, d_u);
+  NK_HIP(hipGetLastError());
+  return NK_OK;
+}
+
+// datum k of the elements or of the nodes: its doubles on the device
+static int elem_data_ptr(nk_problem *P, int on_elements, int k, double **d, size_t *bytes) {
+  NK_REQUIRE(P, "NULL argument");
+  NK_REQUIRE(P->elem, "the problem is not a compiled element problem (kind %d): it has no node or element data", (int)P->kind);
+  nk_elem_state *S = P->elem;
+  const int cnt = on_elements ? S->nelem : S->nnode;
+  NK_REQUIRE(k >= 0 && k < cnt, "%s datum k = %d outside 0..%d (the problem was created with %s = %d)",
+             on_elements ? "element" : "node", k, cnt - 1, on_elements ? "nelem" : "nnode", cnt);
+  const size_t len = on_elements ? (size_t)S->ne : (size_t)S->nn;
+  *d = (on_elements ? S->d_elem : S->d_node) + (size_t)k * len;
+  *bytes = len * sizeof(double);
+  return NK_OK;
+}
+extern "C" int nk_problem_set_elem_data(nk_problem *P, int on_elements, int k, const double *data, int memspace) {
+  double *d = nullptr;
+  size_t bytes = 0;
+  NK_TRY(elem_data_ptr(P, on_elements, k, &d, &bytes));
+  NK_REQUIRE(data, "NULL data");
+  NK_REQUIRE(memspace == NK_HOST || memspace == NK_DEVICE, "memspace = %d is neither NK_HOST nor NK_DEVICE", memspace);
+  NK_HIP(hipSetDevice(P->elem->ctx->device));
+  NK_HIP(nk_memcpy(P->elem->ctx, d, data, bytes, memspace == NK_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice));
+  P->params_version++;
+  nk_problem_invalidate(P);   // a Jacobian cached for the same u belongs to the old data
+  return NK_OK;
+}
+extern "C" int nk_problem_get_elem_data(nk_problem *P, int on_elements, int k, double *out, int memspace) {
+  double *d = nullptr;
+  size_t bytes = 0;
+  NK_TRY(elem_data_ptr(P, on_elements, k, &d, &bytes));
+  NK_REQUIRE(out, "NULL out");
+  NK_REQUIRE(memspace == NK_HOST || memspace == NK_DEVICE, "memspace = %d is neither NK_HOST nor NK_DEVICE", memspace);
+  NK_HIP(hipSetDevice(P->elem->ctx->device));
+  NK_HIP(nk_memcpy(P->elem->ctx, out, d, bytes, memspace == NK_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost));
+  return NK_OK;
+}
+
+extern "C" int nk_problem_set_elem_fixed(nk_problem *P, const int32_t *mask, const double *values, int memspace) {
+  NK_REQUIRE(P && mask, "NULL argument");
+  NK_REQUIRE(P->elem, "the problem is not a compiled element problem (kind %d): it has no fixed unknowns", (int)P->kind);
+  NK_REQUIRE(memspace == NK_HOST || memspace == NK_DEVICE, "memspace = %d is neither NK_HOST nor NK_DEVICE", memspace);
+  nk_elem_state *S = P->elem;
+  const size_t n = (size_t)S->nn * (size_t)S->dof;
+  const hipMemcpyKind kind = memspace == NK_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
+  NK_HIP(hipSetDevice(S->ctx->device));
+  NK_HIP(nk_memcpy(S->ctx, S->d_mask, mask, n * sizeof(int32_t), kind));
+  if (values)
+    NK_HIP(nk_memcpy(S->ctx, S->d_fixed, values, n * sizeof(double), kind));
+  else
+    NK_HIP(nk_memset(S->ctx, S->d_fixed, 0, n * sizeof(double)));
+  P->params_version++;
+  nk_problem_invalidate(P);   // a Jacobian cached for the same u has the old rows
+  return NK_OK;
+}
+extern "C" int nk_problem_get_elem_fixed(nk_problem *P, int32_t *mask, double *values, int memspace) {
+  NK_REQUIRE(P && (mask || values), "NULL argument");
+  NK_REQUIRE(P->elem, "the problem is not a compiled element problem (kind %d): it has no fixed unknowns", (int)P->kind);
+  NK_REQUIRE(memspace == NK_HOST || memspace == NK_DEVICE, "memspace = %d is neither NK_HOST nor NK_DEVICE", memspace);
+  nk_elem_state *S = P->elem;
+  const size_t n = (size_t)S->nn * (size_t)S->dof;
+  const hipMemcpyKind kind = memspace == NK_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+  NK_HIP(hipSetDevice(S->ctx->device));
+  if (mask) NK_HIP(nk_memcpy(S->ctx, mask, S->d_mask, n * sizeof(int32_t), kind));
+  if (values) NK_HIP(nk_memcpy(S->ctx, values, S->d_fixed, n * sizeof(double), kind));
+  return NK_OK;
+}
+
+// a zero-filled device array (at least one element allocated, so that a kernel always gets a pointer)
+template <class T>
+static int elem_zeros(nk_ctx *ctx, T **d, size_t count) {
+  NK_TRY(nk_dev_alloc(d, count > 0 ? count : 1));
+  NK_HIP(nk_memset(ctx, *d, 0, (count > 0 ? count : 1) * sizeof(T)));
+  return NK_OK;
+}
+
+extern "C" int nk_problem_create_elements(nk_ctx *ctx, const char *source, int64_t nn, int64_t ne, int npe, const int32_t *conn,
+                                          int dof, const double *params, int nparams, int nnode, int nelem, nk_problem **out) {
+  NK_REQUIRE(ctx && source && out, "NULL argument");
+  NK_REQUIRE(params || nparams == 0, "NULL params with nparams = %d", nparams);
+  // the mesh and the counts first: every refusal comes before anything is compiled or allocated
+  NK_TRY(elem_validate(nn, ne, npe, conn, dof));
+  NK_TRY(elem_check_counts(npe, dof, nparams, nnode, nelem));
+  std::vector<int32_t> arp, aci;
+  NK_TRY(elem_adjacency_build(nn, ne, npe, conn, &arp, &aci));
+  const int64_t nedges = (int64_t)aci.size(), slots = nedges + nn, n = nn * dof, nnz = (int64_t)dof * dof * slots;
+  NK_REQUIRE(slots <= (int64_t)INT32_MAX / (dof * dof), "%lld nodes and %lld node pairs with dof = %d: the pattern's entry count "
+             "dof·dof·(pairs + nn) exceeds INT32_MAX, its 32-bit indices cannot hold it", (long long)nn, (long long)nedges, dof);
+  if (ctx->nranks > 1)
+    NK_FAIL(NK_E_UNSUPPORTED, "a compiled element problem runs on one rank, the context has %d (partitioning a mesh is not "
+            "built)", ctx->nranks);
+  NK_HIP(hipSetDevice(ctx->device));
+  std::vector<char> code_f, code_j;
+  std::string log;
+  NK_TRY(elem_compile(source, npe, dof, nparams, nnode, nelem, ESET_F, &code_f, &log));
+  log.clear();
+  NK_TRY(elem_compile(source, npe, dof, nparams, nnode, nelem, ESET_JAC, &code_j, &log));
+
+  // the pattern (nk_graph_pattern's), the slot tables, the node-major connectivity and the two sets of lists
+  const int L = npe * dof;
+  std::vector<int32_t> rp((size_t)n + 1), jc((size_t)nnz), slotnode((size_t)slots), spos((size_t)nn);
+  int64_t nnz_out = 0;
+  NK_TRY(nk_graph_pattern(nn, arp.data(), aci.data(), dof, rp.data(), jc.data(), &nnz_out));
+  std::vector<int64_t> gc(jc.begin(), jc.end());
+  for (int64_t i = 0; i < nn; ++i) {
+    int32_t below = 0;
+    for (int64_t q = arp[(size_t)i]; q < arp[(size_t)i + 1] && aci[(size_t)q] < i; ++q) ++below;
+    spos[(size_t)i] = below;
+    for (int64_t s = arp[(size_t)i] + i; s < arp[(size_t)i + 1] + i + 1; ++s) slotnode[(size_t)s] = (int32_t)i;
+  }
+  std::vector<int32_t> connT((size_t)(ne * npe)), rptr((size_t)nn + 1, 0), rlist((size_t)(ne * npe));
+  std::vector<int32_t> eptr((size_t)slots + 1, 0), elist((size_t)(ne * npe * npe)), eslot((size_t)(ne * npe * npe));
+  for (int64_t e = 0; e < ne; ++e)
+    for (int a = 0; a < npe; ++a) {
+      const int32_t i = conn[e * npe + a];
+      connT[(size_t)(a * ne + e)] = i;
+      rptr[(size_t)i + 1]++;
+      const int32_t *row = aci.data() + arp[(size_t)i], *end = aci.data() + arp[(size_t)i + 1];
+      for (int b = 0; b < npe; ++b) {
+        const int32_t j = conn[e * npe + b];
+        int64_t s = spos[(size_t)i];
+        if (j != i) {
+          const int64_t pos = std::lower_bound(row, end, j) - row;
+          s = pos + (pos >= spos[(size_t)i] ? 1 : 0);
+        }
+        const int64_t t = arp[(size_t)i] + i + s;
+        eslot[(size_t)((e * npe + a) * npe + b)] = (int32_t)t;
+        eptr[(size_t)t + 1]++;
+      }
+    }
+  for (int64_t i = 0; i < nn; ++i) rptr[(size_t)i + 1] += rptr[(size_t)i];
+  for (int64_t t = 0; t < slots; ++t) eptr[(size_t)t + 1] += eptr[(size_t)t];
+  {
+    std::vector<int32_t> rat(rptr.begin(), rptr.end() - 1), eat(eptr.begin(), eptr.end() - 1);
+    for (int64_t e = 0; e < ne; ++e)   // elements ascending: every list comes out in ascending element order
+      for (int a = 0; a < npe; ++a) {
+        rlist[(size_t)rat[(size_t)conn[e * npe + a]]++] = (int32_t)((int64_t)a * dof * ne + e);
+        for (int b = 0; b < npe; ++b)
+          elist[(size_t)eat[(size_t)eslot[(size_t)((e * npe + a) * npe + b)]]++] = (int32_t)(((int64_t)a * dof * L + b * dof) * ne + e);
+      }
+  }
+
+  nk_elem_state *S = new nk_elem_state();
+  auto guard = nk_make_guard(S, nk_elem_state_destroy);
+  S->ctx = ctx;
+  S->nn = (int)nn;
+  S->ne = (int)ne;
+  S->npe = npe;
+  S->dof = dof;
+  S->np = nparams;
+  S->nnode = nnode;
+  S->nelem = nelem;
+  S->nslots = (int)slots;
+  if (hipModuleLoadData(&S->mod_f, code_f.data()) != hipSuccess || hipModuleLoadData(&S->mod_jac, code_j.data()) != hipSuccess)
+    NK_FAIL(NK_E_HIP, "hipModuleLoadData failed");
+  if (hipModuleGetFunction(&S->fn_res, S->mod_f, "nk_elem_residual") != hipSuccess ||
+      hipModuleGetFunction(&S->fn_jvp, S->mod_f, "nk_elem_jvp") != hipSuccess ||
+      hipModuleGetFunction(&S->fn_jac, S->mod_jac, "nk_elem_jac") != hipSuccess)
+    NK_FAIL(NK_E_HIP, "a generated element kernel is missing from the compiled module");
+  NK_TRY(nk_upload(ctx, &S->d_conn, connT));
+  NK_TRY(nk_upload(ctx, &S->d_arp, arp));
+  NK_TRY(nk_upload(ctx, &S->d_slotnode, slotnode));
+  NK_TRY(nk_upload(ctx, &S->d_spos, spos));
+  NK_TRY(nk_upload(ctx, &S->d_rptr, rptr));
+  NK_TRY(nk_upload(ctx, &S->d_rlist, rlist));
+  NK_TRY(nk_upload(ctx, &S->d_eptr, eptr));
+  NK_TRY(nk_upload(ctx, &S->d_elist, elist));
+  NK_TRY(nk_dev_alloc(&S->d_params, (size_t)(nparams > 0 ? nparams : 1)));
+  if (nparams > 0) NK_HIP(nk_memcpy(ctx, S->d_params, params, (size_t)nparams * sizeof(double), hipMemcpyHostToDevice));
+  NK_TRY(elem_zeros(ctx, &S->d_node, (size_t)nnode * (size_t)nn));   // zero until nk_problem_set_elem_data
+  NK_TRY(elem_zeros(ctx, &S->d_elem, (size_t)nelem * (size_t)ne));
+  NK_TRY(elem_zeros(ctx, &S->d_mask, (size_t)n));                    // nothing fixed until nk_problem_set_elem_fixed
+  NK_TRY(elem_zeros(ctx, &S->d_fixed, (size_t)n));
+  NK_TRY(nk_dev_alloc(&S->d_B, (size_t)L * (size_t)ne));
+  NK_TRY(nk_dev_alloc(&S->d_M, (size_t)L * (size_t)L * (size_t)ne));
+  NK_TRY(nk_csr_create_local(ctx, n, n, 0, rp, gc, nullptr, &S->pattern));
+
+  nk_problem *P = new nk_problem();
+  P->ctx = ctx;
+  P->kind = NK_PROBLEM_USER;
+  P->n_local = n;
+  P->n_global = n;
+  P->row_begin = 0;
+  P->nparams = nparams;
+  for (int i = 0; i < nparams && i < 8; ++i) P->params[i] = params[i];
+  P->cb.residual = elem_cb_residual;
+  P->cb.jvp = elem_cb_jvp;
+  P->cb.vjp = nullptr;   // Jᵀv: user_lin_J + the transposed SpMV
+  P->cb.jac_values = elem_cb_jac;
+  P->user = S;
+  P->user_pattern = S->pattern;
+  P->elem = guard.release();
+  *out = P;
+  return NK_OK;
+}

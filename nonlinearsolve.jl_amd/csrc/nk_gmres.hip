@@ -1093,6 +1093,9 @@ extern "C" int nk_gmres_set_multigrid_preconditioner(nk_gmres *G, nk_problem *P,
   NK_REQUIRE(!P->graph, "the geometric multigrid preconditioner needs a grid (BRATU2D, BRUSSELATOR2D, a compiled grid problem); a "
              "compiled graph problem has none — use the aggregation algebraic multigrid object instead (nk_precond_create_amg on "
              "the Jacobian, ObjectPrecs(\"amg\"))");
+  NK_REQUIRE(!P->elem, "the geometric multigrid preconditioner needs a grid (BRATU2D, BRUSSELATOR2D, a compiled grid problem); a "
+             "compiled element problem has a mesh, not a grid — use the aggregation algebraic multigrid object instead "
+             "(nk_precond_create_amg on the Jacobian, ObjectPrecs(\"amg\"))");
   NK_REQUIRE(G->op_kind != 0, "set the operator before the preconditioner");
   NK_REQUIRE(P->n_local == G->n, "problem size %lld != GMRES size %lld", (long long)P->n_local, (long long)G->n);
   NK_HIP(hipSetDevice(G->ctx->device));

@@ -64,7 +64,9 @@ constexpr int NK_MAX_NV = 64;          // max simultaneous dot products (restart
 // per-kernel-family timing with HIP events on the launch stream (bench/roofline evidence; off by default)
 enum nk_kernel_id {
   NK_K_SPMV = 0, NK_K_MULTIDOT, NK_K_MULTIAXPY, NK_K_JVP, NK_K_RESIDUAL, NK_K_SCALE, NK_K_REDUCE_SMALL,
-  NK_K_JACFILL, NK_K_NEWTON_UPDATE, NK_K_OTHER, NK_K_POWERS, NK_K_COUNT
+  NK_K_JACFILL, NK_K_NEWTON_UPDATE, NK_K_OTHER, NK_K_POWERS,
+  NK_K_ELEM_GATHER,   // k_elem_gather, the second launch of every callback of a compiled element problem (nk_elem.hip)
+  NK_K_COUNT
 };
 struct nk_prof {
   bool on = false;
@@ -377,6 +379,9 @@ struct nk_problem {
   // compiled graph problem (nk_problem_create_graph, nk_graph.hip): the same over an arbitrary adjacency; owns its modules, the
   // graph, its parameter and data buffers and user_pattern (nk_graph_state_destroy)
   struct nk_graph_state *graph = nullptr;
+  // compiled element problem (nk_problem_create_elements, nk_elem.hip): a residual given element by element on a mesh; owns its
+  // modules, the mesh tables, the gather lists, the element buffers, its data and fixed-unknown buffers and user_pattern
+  struct nk_elem_state *elem = nullptr;
   // forward-difference JVP for user problems without a jvp callback: f(u) at the linearisation point, u + εv, f(u + εv)
   double *d_fd_f0 = nullptr, *d_fd_up = nullptr, *d_fd_f1 = nullptr;
   // operator fallbacks through the Jacobian (prepare_jvp / prepare_vjp, SciMLJacobianOperators.jl:296-362,373-431): a private
@@ -393,6 +398,9 @@ void nk_grid_state_destroy(struct nk_grid_state *S);
 int nk_grid_set_params(nk_problem *P, const double *params, int nparams);   // nk_problem_set_params of a compiled grid problem
 void nk_graph_state_destroy(struct nk_graph_state *S);
 int nk_graph_set_params(nk_problem *P, const double *params, int nparams);  // nk_problem_set_params of a compiled graph problem
+void nk_elem_state_destroy(struct nk_elem_state *S);
+int nk_elem_set_params(nk_problem *P, const double *params, int nparams);   // nk_problem_set_params of a compiled element problem
+int nk_elem_initial_guess(nk_problem *P, double *d_u);                      // zeros, the fixed values written in
 // what the geometric multigrid of compiled grid problems (nk_gridmg.hip) asks of nk_grid.hip
 struct nk_grid_shape_info {
   int dim, n[3] /* nx, ny, nz (2-D: nz = 1) */, dof, nfields, radius, kind[6] /* x-lo, x-hi, y-lo, y-hi, z-lo, z-hi */;

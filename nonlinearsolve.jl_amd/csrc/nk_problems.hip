@@ -584,6 +584,7 @@ extern "C" int nk_problem_destroy(nk_problem *P) {
   nk_csr_destroy(P->lin_J);
   nk_grid_state_destroy(P->grid);
   nk_graph_state_destroy(P->graph);
+  nk_elem_state_destroy(P->elem);
   delete P;
   return NK_OK;
 }
@@ -595,9 +596,10 @@ extern "C" int nk_problem_size(nk_problem *P, int64_t *n_local, int64_t *n_globa
   return NK_OK;
 }
 extern "C" int nk_problem_set_params(nk_problem *P, const double *params, int nparams) {
-  NK_REQUIRE(P && (params || ((P->grid || P->graph) && nparams == 0)), "NULL argument");
+  NK_REQUIRE(P && (params || ((P->grid || P->graph || P->elem) && nparams == 0)), "NULL argument");
   if (P->grid) return nk_grid_set_params(P, params, nparams);   // up to 32 values, kept on the device for the generated kernels
   if (P->graph) return nk_graph_set_params(P, params, nparams);
+  if (P->elem) return nk_elem_set_params(P, params, nparams);
   NK_REQUIRE(nparams == P->nparams, "nparams mismatch (%d vs %d)", nparams, P->nparams);
   if (P->kind == NK_PROBLEM_QUADRATIC) {
     NK_REQUIRE((int64_t)params[0] == P->n_global, "cannot change the problem size");
@@ -1058,6 +1060,7 @@ extern "C" int nk_problem_initial_guess(nk_problem *P, double *u0, int memspace)
       NK_HIP(hipGetLastError());
       break;
     default:
+      if (P->elem) { NK_TRY(nk_elem_initial_guess(P, d)); break; }   // zeros, the fixed values written in
       if (!P->grid && !P->graph) NK_FAIL(NK_E_UNSUPPORTED, "no built-in initial guess for this problem kind");
       NK_TRY(nk_blas_fill(P->ctx, P->n_local, 0.0, d));   // compiled grid or graph problem
       break;
