@@ -606,8 +606,25 @@ def grid_compile_check(source: str, dof: int = 1, stencil: str = "star", boundar
     return nb.value
 
 
-class _GridDeviceProblem(DeviceProblem):
-    """the nk_problem of CompiledGridProblem: the Jacobian pattern belongs to the problem, and `p` is the source's whole p"""
+def _params_array(params):
+    """(the parameters as floats, a c_double array of them with at least one element)"""
+    params = [float(x) for x in params]
+    return params, (C.c_double * max(len(params), 1))(*params)
+
+
+def _sized_call(fn, args, shapes):
+    """a two-pass pattern function of the library, fn(*args, a, b, &count): once for the count, then into int32 arrays of
+    shapes(count) = the two lengths"""
+    cnt = C.c_int64()
+    check(fn(*args, None, None, C.byref(cnt)))
+    a, b = (np.empty(m, dtype=np.int32) for m in shapes(cnt.value))
+    check(fn(*args, C.c_void_p(a.ctypes.data), C.c_void_p(b.ctypes.data), C.byref(cnt)))
+    return a, b
+
+
+class _CompiledDeviceProblem(DeviceProblem):
+    """the nk_problem of a compiled grid, graph or element problem: the Jacobian pattern belongs to the problem, `p` is the
+    source's whole p, and its read-only data arrays live in device buffers the problem owns"""
 
     def jac_csr(self) -> CSRMatrix:
         h = C.c_void_p()
@@ -620,6 +637,24 @@ class _GridDeviceProblem(DeviceProblem):
             raise ValueError(f"the source was compiled for {len(self.p)} parameters, got {len(p)}")
         self.set_params(p)
         self.p = p
+
+    def _set_datum(self, setter, index, x, n, what):
+        """x (n elements, a device tensor or a NumPy array) through setter(problem, *index, pointer, memspace)"""
+        size = x.numel() if _is_torch(x) else np.size(x)
+        if size != n:
+            raise ValueError(f"{what}, got {size}")
+        px, ms, _keep = _ptr(x, n) if n else (None, L.HOST, None)
+        check(setter(self._h, *index, px, ms))
+
+    def _get_datum(self, getter, index, n):
+        """a device tensor of n elements filled by getter(problem, *index, pointer, memspace)"""
+        out = torch.empty(n, dtype=torch.float64, device=f"cuda:{self.ctx.device}")
+        check(getter(self._h, *index, C.c_void_p(out.data_ptr()), L.DEVICE))
+        return out
+
+
+class _GridDeviceProblem(_CompiledDeviceProblem):
+    """the nk_problem of CompiledGridProblem"""
 
     nfields = 0   # CompiledGridProblem(..., fields=k)
 
@@ -655,17 +690,12 @@ class _GridDeviceProblem(DeviceProblem):
         this rank's slab (one rank: per grid node), node (i, j[, k]) at (k·ny + j)·nx + i with the slab's own lines. The data
         is copied; a Jacobian cached for the same u is filled again. On several ranks the call is collective: the ghost lines
         of the field are exchanged here, once."""
-        size = x.numel() if _is_torch(x) else np.size(x)
-        if size != self.nn:
-            raise ValueError(f"field {k}: expected {self.nn} elements (one per node of the rank's slab), got {size}")
-        px, ms, _keep = _ptr(x, self.nn)
-        check(L.lib().nk_problem_set_field(self._h, int(k), px, ms))
+        self._set_datum(L.lib().nk_problem_set_field, (int(k),), x, self.nn,
+                        f"field {k}: expected {self.nn} elements (one per node of the rank's slab)")
 
     def field(self, k: int):
         """a copy of field k as a device tensor"""
-        out = torch.empty(self.nn, dtype=torch.float64, device=f"cuda:{self.ctx.device}")
-        check(L.lib().nk_problem_get_field(self._h, int(k), C.c_void_p(out.data_ptr()), L.DEVICE))
-        return out
+        return self._get_datum(L.lib().nk_problem_get_field, (int(k),), self.nn)
 
 
 def CompiledGridProblem(source: str, nx: int, ny: int, dof: int = 1, stencil: str = "star", boundary="dirichlet",
@@ -716,8 +746,7 @@ def CompiledGridProblem(source: str, nx: int, ny: int, dof: int = 1, stencil: st
     s.nx, s.ny[, s.nz] are the sides of the level the kernel runs on (see MultigridPrecs)."""
     ctx = ctx or default_context()
     st, bd = _grid_ids(stencil, boundary, 2 if nz is None else 3)
-    params = [float(x) for x in params]
-    arr = (C.c_double * max(len(params), 1))(*params)
+    params, arr = _params_array(params)
     h = C.c_void_p()
     if fields:
         check(L.lib().nk_problem_create_grid_fields(ctx._h, source.encode(), nx, ny, 0 if nz is None else nz, dof, st, bd, arr,
@@ -755,12 +784,8 @@ def graph_pattern(rowptr, colind, dof: int = 1):
     columns c2·nn + node. Host only. An adjacency that breaks a rule of CompiledGraphProblem raises NKError naming the first
     offending row."""
     rp, ci, nn = _graph_arrays(rowptr, colind)
-    nnz = C.c_int64()
-    prp, pci = C.c_void_p(rp.ctypes.data), C.c_void_p(ci.ctypes.data)
-    check(L.lib().nk_graph_pattern(nn, prp, pci, int(dof), None, None, C.byref(nnz)))
-    jrp, jci = np.empty(dof * nn + 1, dtype=np.int32), np.empty(nnz.value, dtype=np.int32)
-    check(L.lib().nk_graph_pattern(nn, prp, pci, int(dof), C.c_void_p(jrp.ctypes.data), C.c_void_p(jci.ctypes.data), C.byref(nnz)))
-    return jrp, jci
+    return _sized_call(L.lib().nk_graph_pattern, (nn, C.c_void_p(rp.ctypes.data), C.c_void_p(ci.ctypes.data), int(dof)),
+                       lambda nnz: (dof * nn + 1, nnz))
 
 
 def graph_compile_check(source: str, dof: int = 1, nparams: int = 0, edge_data: int = 0, node_data: int = 0) -> int:
@@ -771,34 +796,16 @@ def graph_compile_check(source: str, dof: int = 1, nparams: int = 0, edge_data: 
     return nb.value
 
 
-class _GraphDeviceProblem(DeviceProblem):
-    """the nk_problem of CompiledGraphProblem: the Jacobian pattern belongs to the problem, `p` is the source's whole p, and the
-    edge and node data live in device buffers the problem owns"""
-
-    def jac_csr(self) -> CSRMatrix:
-        h = C.c_void_p()
-        check(L.lib().nk_problem_jac_csr(self._h, C.byref(h)))
-        return CSRMatrix(h, self.ctx, owned=False)   # freed with the problem
-
-    def set_p(self, p):
-        p = [float(p)] if isinstance(p, (int, float)) else [float(x) for x in p]
-        if len(p) != len(self.p):
-            raise ValueError(f"the source was compiled for {len(self.p)} parameters, got {len(p)}")
-        self.set_params(p)
-        self.p = p
+class _GraphDeviceProblem(_CompiledDeviceProblem):
+    """the nk_problem of CompiledGraphProblem: its data are one array per edge and per node"""
 
     def _set_data(self, on_edges, k, x):
         what, n = ("edge", self.ne) if on_edges else ("node", self.nn)
-        size = x.numel() if _is_torch(x) else np.size(x)
-        if size != n:
-            raise ValueError(f"{what} datum {k}: expected {n} elements (one per {what}), got {size}")
-        px, ms, _keep = _ptr(x, n) if n else (None, L.HOST, None)
-        check(L.lib().nk_problem_set_graph_data(self._h, on_edges, int(k), px, ms))
+        self._set_datum(L.lib().nk_problem_set_graph_data, (on_edges, int(k)), x, n,
+                        f"{what} datum {k}: expected {n} elements (one per {what})")
 
     def _get_data(self, on_edges, k):
-        out = torch.empty(self.ne if on_edges else self.nn, dtype=torch.float64, device=f"cuda:{self.ctx.device}")
-        check(L.lib().nk_problem_get_graph_data(self._h, on_edges, int(k), C.c_void_p(out.data_ptr()), L.DEVICE))
-        return out
+        return self._get_datum(L.lib().nk_problem_get_graph_data, (on_edges, int(k)), self.ne if on_edges else self.nn)
 
     def set_edge_data(self, k: int, x):
         """Replace edge datum k (0 .. edge_data − 1) by x: a device tensor or a NumPy array of one float64 per edge, in the order
@@ -859,8 +866,7 @@ def CompiledGraphProblem(source: str, rowptr, colind, dof: int = 1, params: Sequ
         P = CompiledGraphProblem(SRC, rowptr, colind, dof=2, edge_data=2, node_data=2)"""
     ctx = ctx or default_context()
     rp, ci, nn = _graph_arrays(rowptr, colind)
-    params = [float(x) for x in params]
-    arr = (C.c_double * max(len(params), 1))(*params)
+    params, arr = _params_array(params)
     h = C.c_void_p()
     check(L.lib().nk_problem_create_graph(ctx._h, source.encode(), nn, C.c_void_p(rp.ctypes.data), C.c_void_p(ci.ctypes.data),
                                           int(dof), arr, len(params), int(edge_data), int(node_data), C.byref(h)))
@@ -883,22 +889,15 @@ def elem_adjacency(conn, nn: int):
     an element; ascending columns, no self-loops. Host only. A mesh that breaks a rule of CompiledElementProblem raises NKError
     naming the first offending element."""
     cn, nn, ne, npe = _elem_arrays(conn, nn)
-    pc, nedges = C.c_void_p(cn.ctypes.data), C.c_int64()
-    check(L.lib().nk_elem_adjacency(nn, ne, npe, pc, None, None, C.byref(nedges)))
-    rp, ci = np.empty(nn + 1, dtype=np.int32), np.empty(nedges.value, dtype=np.int32)
-    check(L.lib().nk_elem_adjacency(nn, ne, npe, pc, C.c_void_p(rp.ctypes.data), C.c_void_p(ci.ctypes.data), C.byref(nedges)))
-    return rp, ci
+    return _sized_call(L.lib().nk_elem_adjacency, (nn, ne, npe, C.c_void_p(cn.ctypes.data)), lambda nedges: (nn + 1, nedges))
 
 
 def elem_pattern(conn, nn: int, dof: int = 1):
     """(jrowptr, jcolind), int32, of the Jacobian of a compiled element problem on the mesh conn[ne, npe] over nn nodes:
     graph_pattern of elem_adjacency(conn, nn). Host only."""
     cn, nn, ne, npe = _elem_arrays(conn, nn)
-    pc, nnz = C.c_void_p(cn.ctypes.data), C.c_int64()
-    check(L.lib().nk_elem_pattern(nn, ne, npe, pc, int(dof), None, None, C.byref(nnz)))
-    jrp, jci = np.empty(dof * nn + 1, dtype=np.int32), np.empty(nnz.value, dtype=np.int32)
-    check(L.lib().nk_elem_pattern(nn, ne, npe, pc, int(dof), C.c_void_p(jrp.ctypes.data), C.c_void_p(jci.ctypes.data), C.byref(nnz)))
-    return jrp, jci
+    return _sized_call(L.lib().nk_elem_pattern, (nn, ne, npe, C.c_void_p(cn.ctypes.data), int(dof)),
+                       lambda nnz: (dof * nn + 1, nnz))
 
 
 def elem_compile_check(source: str, npe: int, dof: int = 1, nparams: int = 0, node_data: int = 0, elem_data: int = 0) -> int:
@@ -909,22 +908,16 @@ def elem_compile_check(source: str, npe: int, dof: int = 1, nparams: int = 0, no
     return nb.value
 
 
-class _ElemDeviceProblem(DeviceProblem):
-    """the nk_problem of CompiledElementProblem: the pattern, the node and element data and the fixed unknowns belong to it"""
-    jac_csr, set_p = _GraphDeviceProblem.jac_csr, _GraphDeviceProblem.set_p
+class _ElemDeviceProblem(_CompiledDeviceProblem):
+    """the nk_problem of CompiledElementProblem: its data are one array per node and per element, and it has fixed unknowns"""
 
     def _set_data(self, on_elements, k, x):
         what, n = ("element", self.ne) if on_elements else ("node", self.nn)
-        size = x.numel() if _is_torch(x) else np.size(x)
-        if size != n:
-            raise ValueError(f"{what} datum {k}: expected {n} elements (one per {what}), got {size}")
-        px, ms, _keep = _ptr(x, n)
-        check(L.lib().nk_problem_set_elem_data(self._h, on_elements, int(k), px, ms))
+        self._set_datum(L.lib().nk_problem_set_elem_data, (on_elements, int(k)), x, n,
+                        f"{what} datum {k}: expected {n} elements (one per {what})")
 
     def _get_data(self, on_elements, k):
-        out = torch.empty(self.ne if on_elements else self.nn, dtype=torch.float64, device=f"cuda:{self.ctx.device}")
-        check(L.lib().nk_problem_get_elem_data(self._h, on_elements, int(k), C.c_void_p(out.data_ptr()), L.DEVICE))
-        return out
+        return self._get_datum(L.lib().nk_problem_get_elem_data, (on_elements, int(k)), self.ne if on_elements else self.nn)
 
     def set_node_data(self, k: int, x):
         """Replace node datum k (0 .. node_data − 1) by x: one float64 per node. Copied, like set_elem_data."""
@@ -1001,8 +994,7 @@ def CompiledElementProblem(source: str, conn, nn: int, dof: int = 1, params: Seq
         P = CompiledElementProblem(SRC, conn, nn, params=[1.0], node_data=2); P.set_fixed(boundary_mask)"""
     ctx = ctx or default_context()
     cn, nn, ne, npe = _elem_arrays(conn, nn)
-    params = [float(x) for x in params]
-    arr = (C.c_double * max(len(params), 1))(*params)
+    params, arr = _params_array(params)
     h = C.c_void_p()
     check(L.lib().nk_problem_create_elements(ctx._h, source.encode(), nn, ne, npe, C.c_void_p(cn.ctypes.data), int(dof), arr,
                                              len(params), int(node_data), int(elem_data), C.byref(h)))

@@ -898,8 +898,8 @@ static int batch_compile(const char *source, int n, int np, int flags, std::vect
   const int ch = wave || kset == KSET_JF ? 1 : (n < 8 ? n : 8);
   const std::string dn = "-DNK_N=" + std::to_string(n), dp = "-DNK_NP=" + std::to_string(np), dc = "-DNK_CH=" + std::to_string(ch),
                     db = wave ? "-DNK_BLOCK_T=256" : "-DNK_BLOCK_T=64";
-  std::vector<const char *> opts = {"--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-std=c++17", dn.c_str(), dp.c_str(), dc.c_str(),
-                                    db.c_str()};
+  std::vector<const char *> opts = nk_rtc_base_options();
+  opts.insert(opts.end(), {dn.c_str(), dp.c_str(), dc.c_str(), db.c_str()});
   const std::string dm = "-DNK_M=" + std::to_string(m);
   if (nlls) opts.push_back(dm.c_str());
   if ((flags & NK_BATCH_ANALYTIC_JAC) && (kset == KSET_NEWTON || nlls)) opts.push_back("-DNK_HAS_JAC=1");
@@ -940,11 +940,7 @@ extern "C" int nk_batch_code_object(const char *source, int n, int nparams, int 
   std::vector<char> code;
   std::string log;
   NK_TRY(batch_compile(source, n, nparams, flags, &code, &log, wave != 0 ? KSET_WAVE : KSET_NEWTON));
-  *bytes = (int64_t)code.size();
-  if (!buf) return NK_OK;
-  NK_REQUIRE(capacity >= *bytes, "buffer of %lld bytes, the code object has %lld", (long long)capacity, (long long)*bytes);
-  memcpy(buf, code.data(), code.size());
-  return NK_OK;
+  return nk_rtc_copy_out(code, buf, capacity, bytes);
 }
 
 // the same for the Jacobian-free kernel set (nk_batch_broyden, nk_batch_klement, nk_batch_dfsane)
@@ -954,11 +950,7 @@ extern "C" int nk_batch_jf_code_object(const char *source, int n, int nparams, i
   std::vector<char> code;
   std::string log;
   NK_TRY(batch_compile(source, n, nparams, flags, &code, &log, KSET_JF));
-  *bytes = (int64_t)code.size();
-  if (!buf) return NK_OK;
-  NK_REQUIRE(capacity >= *bytes, "buffer of %lld bytes, the code object has %lld", (long long)capacity, (long long)*bytes);
-  memcpy(buf, code.data(), code.size());
-  return NK_OK;
+  return nk_rtc_copy_out(code, buf, capacity, bytes);
 }
 
 // ---- least squares: compile check, code object and object creation for the NLLS kernel set
@@ -976,11 +968,7 @@ extern "C" int nk_batch_nlls_code_object(const char *source, int n, int m, int n
   std::vector<char> code;
   std::string log;
   NK_TRY(batch_compile(source, n, nparams, flags, &code, &log, KSET_NLLS, m));
-  *bytes = (int64_t)code.size();
-  if (!buf) return NK_OK;
-  NK_REQUIRE(capacity >= *bytes, "buffer of %lld bytes, the code object has %lld", (long long)capacity, (long long)*bytes);
-  memcpy(buf, code.data(), code.size());
-  return NK_OK;
+  return nk_rtc_copy_out(code, buf, capacity, bytes);
 }
 
 extern "C" int nk_batch_create_nlls(nk_ctx *ctx, const char *source, int n, int m, int nparams, int flags, nk_batch **out) {

@@ -35,8 +35,6 @@
 
 #include <algorithm>
 #include <initializer_list>
-#include <map>
-#include <mutex>
 #include <string>
 #include <vector>
 
@@ -123,32 +121,13 @@ extern "C" int nk_elem_pattern(int64_t nn, int64_t ne, int npe, const int32_t *c
 }
 
 // ----------------------------------------------------------------------------- device source (compiled by hiprtc)
-// The program is: nk_dual_prelude, k_elem_types, the user's source, k_elem_kernels. What a program is comes from its options:
-// -DNK_NPE, -DNK_DOF, -DNK_NNODE, -DNK_NELEM (the data arrays per node and per element), -DNK_CH and -DNK_ELEM_SET (0: residual
-// and JVP, 1: the fill).
+// The program is: nk_dual_prelude, nk_seed_lift, k_elem_types, the user's source, k_elem_kernels. What a program is comes from
+// its options: -DNK_NPE, -DNK_DOF, -DNK_NNODE, -DNK_NELEM (the data arrays per node and per element), -DNK_CH and -DNK_ELEM_SET =
+// -DNK_SEED_SET (0: residual and JVP, 1: the fill).
 static const char *k_elem_types = R"NKSRC(
 // ---- compiled element problems: the element and its nodes
 #define NK_ELEM_BLOCK 256
 struct nk_cell { int e, ne, nn; };
-// an nk_real read from u becomes the source's T: itself, the dual with its one partial from v (NK_ELEM_SET == 0), or the dual
-// with the unit seed of component c if the value belongs to the thread's local node (`hot`) and no partial otherwise
-template <typename T> struct nk_elem_lift;
-template <> struct nk_elem_lift<nk_real> {
-  static __device__ __forceinline__ nk_real at(nk_real x, const nk_real *, int, int, bool) { return x; }
-};
-template <> struct nk_elem_lift<Dual> {
-  static __device__ __forceinline__ Dual at(nk_real x, const nk_real *__restrict__ v, int el, int c, bool hot) {
-    Dual r;
-    r.v = x;
-#if NK_ELEM_SET == 0
-    r.d[0] = v[el];
-#else
-#pragma unroll
-    for (int t = 0; t < NK_CH; ++t) r.d[t] = (hot && t == c) ? NK_R(1) : NK_R(0);
-#endif
-    return r;
-  }
-};
 // What the source sees of element e. Unknowns are T, data are nk_real (constants of the differentiation). A local node a
 // outside 0..NK_NPE-1, a component outside 0..NK_DOF-1 and a datum k outside the declared count read NaN (node(a): -1): a wrong
 // source shows at once and reads nothing it does not own
@@ -164,7 +143,7 @@ struct nk_elemv {
   __device__ __forceinline__ T at(int a, int c = 0) const {
     if ((unsigned)a >= (unsigned)NK_NPE || (unsigned)c >= (unsigned)NK_DOF) return T(NK_R(__builtin_nan("")));
     const int el = c * nk_nn + nk_conn[(long)a * nk_ne];
-    return nk_elem_lift<T>::at(nk_u[el], nk_v, el, c, nk_hot == a);
+    return nk_lift<T>::at(nk_u[el], nk_v, el, c, nk_hot == a);
   }
   __device__ __forceinline__ nk_real x(int a, int k = 0) const {
     if ((unsigned)a >= (unsigned)NK_NPE || (unsigned)k >= (unsigned)NK_NNODE) return NK_R(__builtin_nan(""));
@@ -264,32 +243,13 @@ static int elem_compile(const char *source, int npe, int dof, int np, int nnode,
                         std::string *log) {
   NK_REQUIRE(source, "NULL source");
   NK_TRY(elem_check_counts(npe, dof, np, nnode, nelem));
-  const std::string full = std::string(nk_dual_prelude) + k_elem_types + "\n// ---- user source\n" + source + "\n" + k_elem_kernels;
-  const std::string defs[] = {"-DNK_NPE=" + std::to_string(npe), "-DNK_DOF=" + std::to_string(dof),
-                              "-DNK_NNODE=" + std::to_string(nnode), "-DNK_NELEM=" + std::to_string(nelem),
-                              "-DNK_CH=" + std::to_string(eset == ESET_JAC ? dof : 1), "-DNK_ELEM_SET=" + std::to_string(eset)};
-  std::vector<const char *> opts = {"--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-std=c++17"};
-  for (const std::string &d : defs) opts.push_back(d.c_str());
-  // the same source with the same options gives the same code object: a problem created again (another mesh, another context)
-  // skips the compiler
-  static std::mutex mtx;
-  static std::map<std::string, std::vector<char>> cache;
-  std::string key;
-  for (const char *o : opts) { key += o; key += ' '; }
-  key += source;
-  {
-    std::lock_guard<std::mutex> lock(mtx);
-    auto it = cache.find(key);
-    if (it != cache.end()) { *code = it->second; return NK_OK; }
-  }
-  bool failed = false;
-  NK_TRY(nk_rtc_compile(full, "nk_elem_user.hip", opts, code, log, &failed));
-  if (failed)
-    NK_FAIL(NK_E_INVALID, "element residual source does not compile (%s): %.900s", k_elem_contract,
-            log && !log->empty() ? log->c_str() : "(no log)");
-  std::lock_guard<std::mutex> lock(mtx);
-  cache[key] = *code;
-  return NK_OK;
+  const std::string full = std::string(nk_dual_prelude) + nk_seed_lift + k_elem_types + "\n// ---- user source\n" + source + "\n" +
+                           k_elem_kernels;
+  const std::vector<std::string> defs = {
+      "-DNK_NPE=" + std::to_string(npe), "-DNK_DOF=" + std::to_string(dof), "-DNK_NNODE=" + std::to_string(nnode),
+      "-DNK_NELEM=" + std::to_string(nelem), "-DNK_CH=" + std::to_string(eset == ESET_JAC ? dof : 1),
+      "-DNK_ELEM_SET=" + std::to_string(eset), "-DNK_SEED_SET=" + std::to_string(eset)};
+  return nk_rtc_program(full, "nk_elem_user.hip", defs, source, "element", k_elem_contract, code, log);
 }
 
 // compile only (no device needed): both programs
@@ -313,11 +273,7 @@ extern "C" int nk_elem_code_object(const char *source, int npe, int dof, int npa
   std::vector<char> code;
   std::string log;
   NK_TRY(elem_compile(source, npe, dof, nparams, nnode, nelem, jac != 0 ? ESET_JAC : ESET_F, &code, &log));
-  *bytes = (int64_t)code.size();
-  if (!buf) return NK_OK;
-  NK_REQUIRE(capacity >= *bytes, "buffer of %lld bytes, the code object has %lld", (long long)capacity, (long long)*bytes);
-  memcpy(buf, code.data(), code.size());
-  return NK_OK;
+  return nk_rtc_copy_out(code, buf, capacity, bytes);
 }
 
 // ----------------------------------------------------------------------------- the gather
@@ -369,10 +325,8 @@ k_elem_fixed_values(int n, const int *__restrict__ mask, const double *__restric
 
 // ----------------------------------------------------------------------------- the problem object
 struct nk_elem_state {
-  nk_ctx *ctx = nullptr;
-  int nn = 0, ne = 0, npe = 0, dof = 0, np = 0, nnode = 0, nelem = 0, nslots = 0;
-  hipModule_t mod_f = nullptr, mod_jac = nullptr;
-  hipFunction_t fn_res = nullptr, fn_jvp = nullptr, fn_jac = nullptr;
+  nk_compiled c;                                     // the context, the programs, p and the pattern
+  int nn = 0, ne = 0, npe = 0, dof = 0, nnode = 0, nelem = 0, nslots = 0;
   int32_t *d_conn = nullptr;                         // node-major: local node a of element e at a·ne + e
   int32_t *d_arp = nullptr;                          // rowptr of the node graph (nn + 1)
   int32_t *d_slotnode = nullptr, *d_spos = nullptr;  // the node of every global slot; the self slot of every node
@@ -380,18 +334,15 @@ struct nk_elem_state {
   int32_t *d_eptr = nullptr, *d_elist = nullptr;     // the entry lists: per global slot (nslots + 1; ne·npe²)
   int32_t *d_mask = nullptr;                         // dof·nn: 0 = free
   double *d_fixed = nullptr;                         // dof·nn: the value of a fixed unknown
-  double *d_params = nullptr;                        // np doubles (at least one allocated): the source's p
   double *d_node = nullptr;                          // nnode·nn doubles, zero at creation
   double *d_elem = nullptr;                          // nelem·ne doubles, zero at creation
   double *d_B = nullptr;                             // npe·dof·ne: the element vectors
   double *d_M = nullptr;                             // (npe·dof)²·ne: the element matrices
-  nk_csr *pattern = nullptr;                         // the problem's user_pattern
 };
 
 void nk_elem_state_destroy(nk_elem_state *S) {
   if (!S) return;
-  if (S->mod_f) hipModuleUnload(S->mod_f);
-  if (S->mod_jac) hipModuleUnload(S->mod_jac);
+  nk_compiled_free(&S->c);
   hipFree(S->d_conn);
   hipFree(S->d_arp);
   hipFree(S->d_slotnode);
@@ -402,29 +353,19 @@ void nk_elem_state_destroy(nk_elem_state *S) {
   hipFree(S->d_elist);
   hipFree(S->d_mask);
   hipFree(S->d_fixed);
-  hipFree(S->d_params);
   hipFree(S->d_node);
   hipFree(S->d_elem);
   hipFree(S->d_B);
   hipFree(S->d_M);
-  nk_csr_destroy(S->pattern);
   delete S;
 }
 
-// One launch of a generated kernel over `items` threads on `stream`: the mesh and what the problem owns, then `rest`. Inside a
-// profiled scope of the context the launch carries start / stop events like every NK_LAUNCH (as graph_launch does)
+// One launch of a generated kernel over `items` threads on `stream`: the mesh and what the problem owns, then `rest`
 static int elem_launch(nk_elem_state *S, hipFunction_t fn, int64_t items, std::initializer_list<void *> rest, void *stream) {
-  void *args[10] = {&S->nn, &S->ne, &S->d_conn, &S->d_params, &S->d_node, &S->d_elem};
+  void *args[10] = {&S->nn, &S->ne, &S->d_conn, &S->c.d_params, &S->d_node, &S->d_elem};
   int n = 6;
   for (void *a : rest) args[n++] = a;
-  const unsigned blocks = (unsigned)((items + 255) / 256);
-  hipEvent_t e0, e1;
-  hipError_t e;
-  if (S->ctx->prof.on && (hipStream_t)stream == S->ctx->stream && nk_prof_next(S->ctx, &e0, &e1))
-    e = hipExtModuleLaunchKernel(fn, blocks * 256u, 1, 1, 256, 1, 1, 0, (hipStream_t)stream, args, nullptr, e0, e1, 0);   // (sizes in threads)
-  else
-    e = hipModuleLaunchKernel(fn, blocks, 1, 1, 256, 1, 1, 0, (hipStream_t)stream, args, nullptr);
-  return e != hipSuccess;
+  return nk_compiled_launch(&S->c, fn, items, args, stream);
 }
 
 // the gather of one callback on the same stream, timed the same way; its time goes to the family "elem_gather", so that the
@@ -445,7 +386,7 @@ static int elem_gather(nk_elem_state *S, int mode, const double *x, double *out,
   const int32_t *lptr = jac ? S->d_eptr : S->d_rptr, *list = jac ? S->d_elist : S->d_rlist;
   const double *buf = jac ? S->d_M : S->d_B;
   hipEvent_t e0, e1;
-  if (elem_gather_events(S->ctx, stream, &e0, &e1))
+  if (elem_gather_events(S->c.ctx, stream, &e0, &e1))
     hipExtLaunchKernelGGL(k_elem_gather, grid, block, 0, (hipStream_t)stream, e0, e1, 0, mode, items, S->dof, S->nn, S->ne, L, lptr,
                           list, buf, S->d_mask, x, S->d_fixed, S->d_slotnode, S->d_arp, S->d_spos, out);
   else
@@ -456,36 +397,25 @@ static int elem_gather(nk_elem_state *S, int mode, const double *x, double *out,
 
 static int elem_cb_residual(void *user, const double *u, double *f, void *stream) {
   nk_elem_state *S = (nk_elem_state *)user;
-  if (elem_launch(S, S->fn_res, S->ne, {&u, &S->d_B}, stream)) return 1;
+  if (elem_launch(S, S->c.fn_res, S->ne, {&u, &S->d_B}, stream)) return 1;
   return elem_gather(S, GATHER_F, u, f, stream);
 }
 static int elem_cb_jvp(void *user, const double *v, const double *u, double *jv, void *stream) {
   nk_elem_state *S = (nk_elem_state *)user;
-  if (elem_launch(S, S->fn_jvp, S->ne, {&u, &v, &S->d_B}, stream)) return 1;
+  if (elem_launch(S, S->c.fn_jvp, S->ne, {&u, &v, &S->d_B}, stream)) return 1;
   return elem_gather(S, GATHER_JV, v, jv, stream);
 }
 static int elem_cb_jac(void *user, const double *u, double *vals, void *stream) {
   nk_elem_state *S = (nk_elem_state *)user;
-  if (elem_launch(S, S->fn_jac, (int64_t)S->ne * S->npe, {&u, &S->d_M}, stream)) return 1;
+  if (elem_launch(S, S->c.fn_jac, (int64_t)S->ne * S->npe, {&u, &S->d_M}, stream)) return 1;
   return elem_gather(S, GATHER_J, u, vals, stream);
-}
-
-int nk_elem_set_params(nk_problem *P, const double *params, int nparams) {
-  nk_elem_state *S = P->elem;
-  NK_REQUIRE(nparams == S->np, "nparams mismatch (%d vs %d)", nparams, S->np);
-  NK_HIP(hipSetDevice(S->ctx->device));
-  if (nparams > 0) NK_HIP(nk_memcpy(S->ctx, S->d_params, params, (size_t)nparams * sizeof(double), hipMemcpyHostToDevice));
-  for (int i = 0; i < nparams && i < 8; ++i) P->params[i] = params[i];   // (the first eight, for inspection; the kernels read d_params)
-  P->params_version++;
-  nk_problem_invalidate(P);   // a Jacobian cached for the same u belongs to the old parameters
-  return NK_OK;
 }
 
 // zeros, with the values of the fixed unknowns written in
 int nk_elem_initial_guess(nk_problem *P, double *d_u) {
   nk_elem_state *S = P->elem;
   const int n = S->nn * S->dof;
-  NK_LAUNCH(S->ctx, k_elem_fixed_values, dim3((unsigned)((n + 255) / 256)), dim3(256), n, S->d_mask, S->d_fixed, d_u);
+  NK_LAUNCH(S->c.ctx, k_elem_fixed_values, dim3((unsigned)((n + 255) / 256)), dim3(256), n, S->d_mask, S->d_fixed, d_u);
   NK_HIP(hipGetLastError());
   return NK_OK;
 }
@@ -507,23 +437,15 @@ extern "C" int nk_problem_set_elem_data(nk_problem *P, int on_elements, int k, c
   double *d = nullptr;
   size_t bytes = 0;
   NK_TRY(elem_data_ptr(P, on_elements, k, &d, &bytes));
-  NK_REQUIRE(data, "NULL data");
-  NK_REQUIRE(memspace == NK_HOST || memspace == NK_DEVICE, "memspace = %d is neither NK_HOST nor NK_DEVICE", memspace);
-  NK_HIP(hipSetDevice(P->elem->ctx->device));
-  NK_HIP(nk_memcpy(P->elem->ctx, d, data, bytes, memspace == NK_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice));
-  P->params_version++;
-  nk_problem_invalidate(P);   // a Jacobian cached for the same u belongs to the old data
+  NK_TRY(nk_compiled_data_copy(P, d, bytes, data, memspace, true));
+  nk_compiled_data_changed(P);
   return NK_OK;
 }
 extern "C" int nk_problem_get_elem_data(nk_problem *P, int on_elements, int k, double *out, int memspace) {
   double *d = nullptr;
   size_t bytes = 0;
   NK_TRY(elem_data_ptr(P, on_elements, k, &d, &bytes));
-  NK_REQUIRE(out, "NULL out");
-  NK_REQUIRE(memspace == NK_HOST || memspace == NK_DEVICE, "memspace = %d is neither NK_HOST nor NK_DEVICE", memspace);
-  NK_HIP(hipSetDevice(P->elem->ctx->device));
-  NK_HIP(nk_memcpy(P->elem->ctx, out, d, bytes, memspace == NK_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost));
-  return NK_OK;
+  return nk_compiled_data_copy(P, d, bytes, out, memspace, false);
 }
 
 extern "C" int nk_problem_set_elem_fixed(nk_problem *P, const int32_t *mask, const double *values, int memspace) {
@@ -533,14 +455,13 @@ extern "C" int nk_problem_set_elem_fixed(nk_problem *P, const int32_t *mask, con
   nk_elem_state *S = P->elem;
   const size_t n = (size_t)S->nn * (size_t)S->dof;
   const hipMemcpyKind kind = memspace == NK_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
-  NK_HIP(hipSetDevice(S->ctx->device));
-  NK_HIP(nk_memcpy(S->ctx, S->d_mask, mask, n * sizeof(int32_t), kind));
+  NK_HIP(hipSetDevice(S->c.ctx->device));
+  NK_HIP(nk_memcpy(S->c.ctx, S->d_mask, mask, n * sizeof(int32_t), kind));
   if (values)
-    NK_HIP(nk_memcpy(S->ctx, S->d_fixed, values, n * sizeof(double), kind));
+    NK_HIP(nk_memcpy(S->c.ctx, S->d_fixed, values, n * sizeof(double), kind));
   else
-    NK_HIP(nk_memset(S->ctx, S->d_fixed, 0, n * sizeof(double)));
-  P->params_version++;
-  nk_problem_invalidate(P);   // a Jacobian cached for the same u has the old rows
+    NK_HIP(nk_memset(S->c.ctx, S->d_fixed, 0, n * sizeof(double)));
+  nk_compiled_data_changed(P);   // a Jacobian cached for the same u has the old rows
   return NK_OK;
 }
 extern "C" int nk_problem_get_elem_fixed(nk_problem *P, int32_t *mask, double *values, int memspace) {
@@ -550,17 +471,9 @@ extern "C" int nk_problem_get_elem_fixed(nk_problem *P, int32_t *mask, double *v
   nk_elem_state *S = P->elem;
   const size_t n = (size_t)S->nn * (size_t)S->dof;
   const hipMemcpyKind kind = memspace == NK_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
-  NK_HIP(hipSetDevice(S->ctx->device));
-  if (mask) NK_HIP(nk_memcpy(S->ctx, mask, S->d_mask, n * sizeof(int32_t), kind));
-  if (values) NK_HIP(nk_memcpy(S->ctx, values, S->d_fixed, n * sizeof(double), kind));
-  return NK_OK;
-}
-
-// a zero-filled device array (at least one element allocated, so that a kernel always gets a pointer)
-template <class T>
-static int elem_zeros(nk_ctx *ctx, T **d, size_t count) {
-  NK_TRY(nk_dev_alloc(d, count > 0 ? count : 1));
-  NK_HIP(nk_memset(ctx, *d, 0, (count > 0 ? count : 1) * sizeof(T)));
+  NK_HIP(hipSetDevice(S->c.ctx->device));
+  if (mask) NK_HIP(nk_memcpy(S->c.ctx, mask, S->d_mask, n * sizeof(int32_t), kind));
+  if (values) NK_HIP(nk_memcpy(S->c.ctx, values, S->d_fixed, n * sizeof(double), kind));
   return NK_OK;
 }
 
@@ -588,16 +501,10 @@ extern "C" int nk_problem_create_elements(nk_ctx *ctx, const char *source, int64
 
   // the pattern (nk_graph_pattern's), the slot tables, the node-major connectivity and the two sets of lists
   const int L = npe * dof;
-  std::vector<int32_t> rp((size_t)n + 1), jc((size_t)nnz), slotnode((size_t)slots), spos((size_t)nn);
-  int64_t nnz_out = 0;
-  NK_TRY(nk_graph_pattern(nn, arp.data(), aci.data(), dof, rp.data(), jc.data(), &nnz_out));
-  std::vector<int64_t> gc(jc.begin(), jc.end());
-  for (int64_t i = 0; i < nn; ++i) {
-    int32_t below = 0;
-    for (int64_t q = arp[(size_t)i]; q < arp[(size_t)i + 1] && aci[(size_t)q] < i; ++q) ++below;
-    spos[(size_t)i] = below;
-    for (int64_t s = arp[(size_t)i] + i; s < arp[(size_t)i + 1] + i + 1; ++s) slotnode[(size_t)s] = (int32_t)i;
-  }
+  std::vector<int32_t> rp((size_t)n + 1), slotnode, spos;
+  std::vector<int64_t> gc((size_t)nnz);
+  nk_graph_pattern_fill64(nn, nedges, arp.data(), aci.data(), dof, rp.data(), gc.data());
+  nk_graph_slots(nn, arp.data(), aci.data(), &slotnode, &spos);
   std::vector<int32_t> connT((size_t)(ne * npe)), rptr((size_t)nn + 1, 0), rlist((size_t)(ne * npe));
   std::vector<int32_t> eptr((size_t)slots + 1, 0), elist((size_t)(ne * npe * npe)), eslot((size_t)(ne * npe * npe));
   for (int64_t e = 0; e < ne; ++e)
@@ -632,21 +539,15 @@ extern "C" int nk_problem_create_elements(nk_ctx *ctx, const char *source, int64
 
   nk_elem_state *S = new nk_elem_state();
   auto guard = nk_make_guard(S, nk_elem_state_destroy);
-  S->ctx = ctx;
+  S->c.ctx = ctx;
   S->nn = (int)nn;
   S->ne = (int)ne;
   S->npe = npe;
   S->dof = dof;
-  S->np = nparams;
   S->nnode = nnode;
   S->nelem = nelem;
   S->nslots = (int)slots;
-  if (hipModuleLoadData(&S->mod_f, code_f.data()) != hipSuccess || hipModuleLoadData(&S->mod_jac, code_j.data()) != hipSuccess)
-    NK_FAIL(NK_E_HIP, "hipModuleLoadData failed");
-  if (hipModuleGetFunction(&S->fn_res, S->mod_f, "nk_elem_residual") != hipSuccess ||
-      hipModuleGetFunction(&S->fn_jvp, S->mod_f, "nk_elem_jvp") != hipSuccess ||
-      hipModuleGetFunction(&S->fn_jac, S->mod_jac, "nk_elem_jac") != hipSuccess)
-    NK_FAIL(NK_E_HIP, "a generated element kernel is missing from the compiled module");
+  NK_TRY(nk_compiled_load(&S->c, code_f, code_j, "nk_elem_residual", "nk_elem_jvp", "nk_elem_jac", "element"));
   NK_TRY(nk_upload(ctx, &S->d_conn, connT));
   NK_TRY(nk_upload(ctx, &S->d_arp, arp));
   NK_TRY(nk_upload(ctx, &S->d_slotnode, slotnode));
@@ -655,31 +556,15 @@ extern "C" int nk_problem_create_elements(nk_ctx *ctx, const char *source, int64
   NK_TRY(nk_upload(ctx, &S->d_rlist, rlist));
   NK_TRY(nk_upload(ctx, &S->d_eptr, eptr));
   NK_TRY(nk_upload(ctx, &S->d_elist, elist));
-  NK_TRY(nk_dev_alloc(&S->d_params, (size_t)(nparams > 0 ? nparams : 1)));
-  if (nparams > 0) NK_HIP(nk_memcpy(ctx, S->d_params, params, (size_t)nparams * sizeof(double), hipMemcpyHostToDevice));
-  NK_TRY(elem_zeros(ctx, &S->d_node, (size_t)nnode * (size_t)nn));   // zero until nk_problem_set_elem_data
-  NK_TRY(elem_zeros(ctx, &S->d_elem, (size_t)nelem * (size_t)ne));
-  NK_TRY(elem_zeros(ctx, &S->d_mask, (size_t)n));                    // nothing fixed until nk_problem_set_elem_fixed
-  NK_TRY(elem_zeros(ctx, &S->d_fixed, (size_t)n));
+  NK_TRY(nk_compiled_params_init(&S->c, params, nparams));
+  NK_TRY(nk_compiled_zeros(ctx, &S->d_node, (size_t)nnode * (size_t)nn));   // zero until nk_problem_set_elem_data
+  NK_TRY(nk_compiled_zeros(ctx, &S->d_elem, (size_t)nelem * (size_t)ne));
+  NK_TRY(nk_compiled_zeros(ctx, &S->d_mask, (size_t)n));                    // nothing fixed until nk_problem_set_elem_fixed
+  NK_TRY(nk_compiled_zeros(ctx, &S->d_fixed, (size_t)n));
   NK_TRY(nk_dev_alloc(&S->d_B, (size_t)L * (size_t)ne));
   NK_TRY(nk_dev_alloc(&S->d_M, (size_t)L * (size_t)L * (size_t)ne));
-  NK_TRY(nk_csr_create_local(ctx, n, n, 0, rp, gc, nullptr, &S->pattern));
-
-  nk_problem *P = new nk_problem();
-  P->ctx = ctx;
-  P->kind = NK_PROBLEM_USER;
-  P->n_local = n;
-  P->n_global = n;
-  P->row_begin = 0;
-  P->nparams = nparams;
-  for (int i = 0; i < nparams && i < 8; ++i) P->params[i] = params[i];
-  P->cb.residual = elem_cb_residual;
-  P->cb.jvp = elem_cb_jvp;
-  P->cb.vjp = nullptr;   // Jᵀv: user_lin_J + the transposed SpMV
-  P->cb.jac_values = elem_cb_jac;
-  P->user = S;
-  P->user_pattern = S->pattern;
-  P->elem = guard.release();
-  *out = P;
+  NK_TRY(nk_csr_create_local(ctx, n, n, 0, rp, gc, nullptr, &S->c.pattern));
+  NK_TRY(nk_compiled_problem(&S->c, n, n, 0, params, nparams, {elem_cb_residual, elem_cb_jvp, nullptr, elem_cb_jac}, S, out));
+  (*out)->elem = guard.release();
   return NK_OK;
 }

@@ -38,8 +38,6 @@
 #include <string.h>
 
 #include <initializer_list>
-#include <map>
-#include <mutex>
 #include <string>
 #include <vector>
 
@@ -105,34 +103,30 @@ extern "C" int nk_graph_pattern(int64_t nn, const int32_t *rowptr, const int32_t
   if (nnz) *nnz = (int64_t)dof * dof * (ne + nn);
   return NK_OK;
 }
+void nk_graph_pattern_fill64(int64_t nn, int64_t ne, const int32_t *rowptr, const int32_t *colind, int dof, int32_t *jrowptr,
+                             int64_t *jcolind) {
+  graph_pattern_fill<int64_t>(nn, ne, rowptr, colind, dof, jrowptr, jcolind);
+}
+// the node of every global slot and, per node, its self slot: the number of neighbours smaller than the node
+void nk_graph_slots(int64_t nn, const int32_t *rowptr, const int32_t *colind, std::vector<int32_t> *slotnode, std::vector<int32_t> *spos) {
+  slotnode->resize((size_t)(rowptr[nn] + nn));
+  spos->resize((size_t)nn);
+  for (int64_t i = 0; i < nn; ++i) {
+    int32_t below = 0;
+    for (int64_t e = rowptr[i]; e < rowptr[i + 1] && colind[e] < i; ++e) ++below;
+    (*spos)[(size_t)i] = below;
+    for (int64_t s = rowptr[i] + i; s < rowptr[i + 1] + i + 1; ++s) (*slotnode)[(size_t)s] = (int32_t)i;
+  }
+}
 
 // ----------------------------------------------------------------------------- device source (compiled by hiprtc)
-// The program is: nk_dual_prelude, k_graph_types, the user's source, k_graph_kernels. What a program is comes from its options:
-// -DNK_DOF, -DNK_NEDGE, -DNK_NNODE (the data arrays per edge and per node), -DNK_CH, -DNK_GRAPH_SET (0: residual and JVP,
-// 1: the fill) and -DNK_GRAPH_FILL_NODE (the A/B form of the fill).
+// The program is: nk_dual_prelude, nk_seed_lift, k_graph_types, the user's source, k_graph_kernels. What a program is comes from
+// its options: -DNK_DOF, -DNK_NEDGE, -DNK_NNODE (the data arrays per edge and per node), -DNK_CH, -DNK_GRAPH_SET = -DNK_SEED_SET
+// (0: residual and JVP, 1: the fill) and -DNK_GRAPH_FILL_NODE (the A/B form of the fill).
 static const char *k_graph_types = R"NKSRC(
 // ---- compiled graph problems: the node and its neighbours
 #define NK_GRAPH_BLOCK 256
 struct nk_vertex { int i, nn, deg; };
-// an nk_real read from u becomes the source's T: itself, the dual with its one partial from v (NK_GRAPH_SET == 0), or the dual
-// with the unit seed of component c if the value belongs to the thread's slot (`hot`) and no partial otherwise
-template <typename T> struct nk_graph_lift;
-template <> struct nk_graph_lift<nk_real> {
-  static __device__ __forceinline__ nk_real at(nk_real x, const nk_real *, int, int, bool) { return x; }
-};
-template <> struct nk_graph_lift<Dual> {
-  static __device__ __forceinline__ Dual at(nk_real x, const nk_real *__restrict__ v, int el, int c, bool hot) {
-    Dual r;
-    r.v = x;
-#if NK_GRAPH_SET == 0
-    r.d[0] = v[el];
-#else
-#pragma unroll
-    for (int t = 0; t < NK_CH; ++t) r.d[t] = (hot && t == c) ? NK_R(1) : NK_R(0);
-#endif
-    return r;
-  }
-};
 // What the source sees of node i. Unknowns are T, data are nk_real (constants of the differentiation). An edge e outside
 // 0..deg()-1, a component outside 0..NK_DOF-1 and a datum k outside the declared count read NaN (node(e): -1): a wrong source
 // shows at once and reads nothing it does not own
@@ -148,12 +142,12 @@ struct nk_nbrs {
   __device__ __forceinline__ int deg() const { return nk_dg; }
   __device__ __forceinline__ T self(int c = 0) const {
     if ((unsigned)c >= (unsigned)NK_DOF) return T(NK_R(__builtin_nan("")));
-    return nk_graph_lift<T>::at(nk_u[c * nk_nn + nk_i], nk_v, c * nk_nn + nk_i, c, nk_hot == nk_spos);
+    return nk_lift<T>::at(nk_u[c * nk_nn + nk_i], nk_v, c * nk_nn + nk_i, c, nk_hot == nk_spos);
   }
   __device__ __forceinline__ T nbr(int e, int c = 0) const {
     if (!nk_edge_ok(e) || (unsigned)c >= (unsigned)NK_DOF) return T(NK_R(__builtin_nan("")));
     const int j = nk_col[e];
-    return nk_graph_lift<T>::at(nk_u[c * nk_nn + j], nk_v, c * nk_nn + j, c, nk_hot == e + (e >= nk_spos ? 1 : 0));
+    return nk_lift<T>::at(nk_u[c * nk_nn + j], nk_v, c * nk_nn + j, c, nk_hot == e + (e >= nk_spos ? 1 : 0));
   }
   __device__ __forceinline__ int node(int e) const { return nk_edge_ok(e) ? nk_col[e] : -1; }
   __device__ __forceinline__ nk_real w(int e, int k = 0) const {
@@ -291,32 +285,13 @@ static int graph_compile(const char *source, int dof, int np, int nedge, int nno
                          std::string *log) {
   NK_REQUIRE(source, "NULL source");
   NK_TRY(graph_check_counts(dof, np, nedge, nnode));
-  const std::string full = std::string(nk_dual_prelude) + k_graph_types + "\n// ---- user source\n" + source + "\n" + k_graph_kernels;
-  const std::string defs[] = {"-DNK_DOF=" + std::to_string(dof), "-DNK_NEDGE=" + std::to_string(nedge),
-                              "-DNK_NNODE=" + std::to_string(nnode), "-DNK_CH=" + std::to_string(gset == GSET_JAC ? dof : 1),
-                              "-DNK_GRAPH_SET=" + std::to_string(gset), std::string("-DNK_GRAPH_FILL_NODE=") + (fill_node ? "1" : "0")};
-  std::vector<const char *> opts = {"--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-std=c++17"};
-  for (const std::string &d : defs) opts.push_back(d.c_str());
-  // the same source with the same options gives the same code object: a problem created again (another graph, another context)
-  // skips the compiler
-  static std::mutex mtx;
-  static std::map<std::string, std::vector<char>> cache;
-  std::string key;
-  for (const char *o : opts) { key += o; key += ' '; }
-  key += source;
-  {
-    std::lock_guard<std::mutex> lock(mtx);
-    auto it = cache.find(key);
-    if (it != cache.end()) { *code = it->second; return NK_OK; }
-  }
-  bool failed = false;
-  NK_TRY(nk_rtc_compile(full, "nk_graph_user.hip", opts, code, log, &failed));
-  if (failed)
-    NK_FAIL(NK_E_INVALID, "graph residual source does not compile (%s): %.900s", k_graph_contract,
-            log && !log->empty() ? log->c_str() : "(no log)");
-  std::lock_guard<std::mutex> lock(mtx);
-  cache[key] = *code;
-  return NK_OK;
+  const std::string full = std::string(nk_dual_prelude) + nk_seed_lift + k_graph_types + "\n// ---- user source\n" + source + "\n" +
+                           k_graph_kernels;
+  const std::vector<std::string> defs = {
+      "-DNK_DOF=" + std::to_string(dof), "-DNK_NEDGE=" + std::to_string(nedge), "-DNK_NNODE=" + std::to_string(nnode),
+      "-DNK_CH=" + std::to_string(gset == GSET_JAC ? dof : 1), "-DNK_GRAPH_SET=" + std::to_string(gset),
+      "-DNK_SEED_SET=" + std::to_string(gset), std::string("-DNK_GRAPH_FILL_NODE=") + (fill_node ? "1" : "0")};
+  return nk_rtc_program(full, "nk_graph_user.hip", defs, source, "graph", k_graph_contract, code, log);
 }
 
 // compile only (no device needed): both programs
@@ -340,80 +315,50 @@ extern "C" int nk_graph_code_object(const char *source, int dof, int nparams, in
   std::vector<char> code;
   std::string log;
   NK_TRY(graph_compile(source, dof, nparams, nedge, nnode, jac != 0 ? GSET_JAC : GSET_F, graph_fill_node(), &code, &log));
-  *bytes = (int64_t)code.size();
-  if (!buf) return NK_OK;
-  NK_REQUIRE(capacity >= *bytes, "buffer of %lld bytes, the code object has %lld", (long long)capacity, (long long)*bytes);
-  memcpy(buf, code.data(), code.size());
-  return NK_OK;
+  return nk_rtc_copy_out(code, buf, capacity, bytes);
 }
 
 // ----------------------------------------------------------------------------- the problem object
 struct nk_graph_state {
-  nk_ctx *ctx = nullptr;
-  int nn = 0, ne = 0, dof = 0, np = 0, nedge = 0, nnode = 0;
+  nk_compiled c;   // the context, the programs, p and the pattern
+  int nn = 0, ne = 0, dof = 0, nedge = 0, nnode = 0;
   bool fill_node = false;   // the fill was compiled in its A/B form: one node per thread
-  hipModule_t mod_f = nullptr, mod_jac = nullptr;
-  hipFunction_t fn_res = nullptr, fn_jvp = nullptr, fn_jac = nullptr;
   int32_t *d_rowptr = nullptr, *d_colind = nullptr;   // the adjacency
   int32_t *d_slotnode = nullptr, *d_spos = nullptr;   // the node of every global slot (ne + nn); the self slot of every node (nn)
-  double *d_params = nullptr;   // np doubles (at least one allocated): the source's p
   double *d_edge = nullptr;     // nedge·ne doubles, datum k of edge e at k·ne + e (at least one allocated); zero at creation
   double *d_node = nullptr;     // nnode·nn doubles, datum k of node i at k·nn + i (at least one allocated); zero at creation
-  nk_csr *pattern = nullptr;    // the problem's user_pattern
 };
 
 void nk_graph_state_destroy(nk_graph_state *S) {
   if (!S) return;
-  if (S->mod_f) hipModuleUnload(S->mod_f);
-  if (S->mod_jac) hipModuleUnload(S->mod_jac);
+  nk_compiled_free(&S->c);
   hipFree(S->d_rowptr);
   hipFree(S->d_colind);
   hipFree(S->d_slotnode);
   hipFree(S->d_spos);
-  hipFree(S->d_params);
   hipFree(S->d_edge);
   hipFree(S->d_node);
-  nk_csr_destroy(S->pattern);
   delete S;
 }
 
-// One launch of a generated kernel over `items` threads on `stream`: the graph and what the problem owns, then `rest`. Inside a
-// profiled scope of the context the launch carries start / stop events like every NK_LAUNCH (as the generated grid kernels do)
+// One launch of a generated kernel over `items` threads on `stream`: the graph and what the problem owns, then `rest`
 static int graph_launch(nk_graph_state *S, hipFunction_t fn, int64_t items, std::initializer_list<void *> rest, void *stream) {
-  void *args[12] = {&S->nn, &S->ne, &S->d_rowptr, &S->d_colind, &S->d_params, &S->d_edge, &S->d_node};
+  void *args[12] = {&S->nn, &S->ne, &S->d_rowptr, &S->d_colind, &S->c.d_params, &S->d_edge, &S->d_node};
   int n = 7;
   for (void *a : rest) args[n++] = a;
-  const unsigned blocks = (unsigned)((items + 255) / 256);
-  hipEvent_t e0, e1;
-  hipError_t e;
-  if (S->ctx->prof.on && (hipStream_t)stream == S->ctx->stream && nk_prof_next(S->ctx, &e0, &e1))
-    e = hipExtModuleLaunchKernel(fn, blocks * 256u, 1, 1, 256, 1, 1, 0, (hipStream_t)stream, args, nullptr, e0, e1, 0);   // (sizes in threads)
-  else
-    e = hipModuleLaunchKernel(fn, blocks, 1, 1, 256, 1, 1, 0, (hipStream_t)stream, args, nullptr);
-  return e != hipSuccess;
+  return nk_compiled_launch(&S->c, fn, items, args, stream);
 }
 static int graph_cb_residual(void *user, const double *u, double *f, void *stream) {
   nk_graph_state *S = (nk_graph_state *)user;
-  return graph_launch(S, S->fn_res, S->nn, {&u, &f}, stream);
+  return graph_launch(S, S->c.fn_res, S->nn, {&u, &f}, stream);
 }
 static int graph_cb_jvp(void *user, const double *v, const double *u, double *jv, void *stream) {
   nk_graph_state *S = (nk_graph_state *)user;
-  return graph_launch(S, S->fn_jvp, S->nn, {&u, &v, &jv}, stream);
+  return graph_launch(S, S->c.fn_jvp, S->nn, {&u, &v, &jv}, stream);
 }
 static int graph_cb_jac(void *user, const double *u, double *vals, void *stream) {
   nk_graph_state *S = (nk_graph_state *)user;
-  return graph_launch(S, S->fn_jac, S->fill_node ? (int64_t)S->nn : (int64_t)S->ne + S->nn, {&S->d_slotnode, &S->d_spos, &u, &vals}, stream);
-}
-
-int nk_graph_set_params(nk_problem *P, const double *params, int nparams) {
-  nk_graph_state *S = P->graph;
-  NK_REQUIRE(nparams == S->np, "nparams mismatch (%d vs %d)", nparams, S->np);
-  NK_HIP(hipSetDevice(S->ctx->device));
-  if (nparams > 0) NK_HIP(nk_memcpy(S->ctx, S->d_params, params, (size_t)nparams * sizeof(double), hipMemcpyHostToDevice));
-  for (int i = 0; i < nparams && i < 8; ++i) P->params[i] = params[i];   // (the first eight, for inspection; the kernels read d_params)
-  P->params_version++;
-  nk_problem_invalidate(P);   // a Jacobian cached for the same u belongs to the old parameters
-  return NK_OK;
+  return graph_launch(S, S->c.fn_jac, S->fill_node ? (int64_t)S->nn : (int64_t)S->ne + S->nn, {&S->d_slotnode, &S->d_spos, &u, &vals}, stream);
 }
 
 // datum k of the edges or of the nodes: its doubles on the device
@@ -433,32 +378,15 @@ extern "C" int nk_problem_set_graph_data(nk_problem *P, int on_edges, int k, con
   double *d = nullptr;
   size_t bytes = 0;
   NK_TRY(graph_data_ptr(P, on_edges, k, &d, &bytes));
-  NK_REQUIRE(data || bytes == 0, "NULL data");
-  NK_REQUIRE(memspace == NK_HOST || memspace == NK_DEVICE, "memspace = %d is neither NK_HOST nor NK_DEVICE", memspace);
-  NK_HIP(hipSetDevice(P->graph->ctx->device));
-  if (bytes > 0)
-    NK_HIP(nk_memcpy(P->graph->ctx, d, data, bytes, memspace == NK_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice));
-  P->params_version++;
-  nk_problem_invalidate(P);   // a Jacobian cached for the same u belongs to the old data
+  NK_TRY(nk_compiled_data_copy(P, d, bytes, data, memspace, true));
+  nk_compiled_data_changed(P);
   return NK_OK;
 }
 extern "C" int nk_problem_get_graph_data(nk_problem *P, int on_edges, int k, double *out, int memspace) {
   double *d = nullptr;
   size_t bytes = 0;
   NK_TRY(graph_data_ptr(P, on_edges, k, &d, &bytes));
-  NK_REQUIRE(out || bytes == 0, "NULL out");
-  NK_REQUIRE(memspace == NK_HOST || memspace == NK_DEVICE, "memspace = %d is neither NK_HOST nor NK_DEVICE", memspace);
-  NK_HIP(hipSetDevice(P->graph->ctx->device));
-  if (bytes > 0)
-    NK_HIP(nk_memcpy(P->graph->ctx, out, d, bytes, memspace == NK_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost));
-  return NK_OK;
-}
-
-// a zero-filled device array of `count` doubles (at least one allocated, so that a kernel always gets a pointer)
-static int graph_zeros(nk_ctx *ctx, double **d, size_t count) {
-  NK_TRY(nk_dev_alloc(d, count > 0 ? count : 1));
-  NK_HIP(nk_memset(ctx, *d, 0, (count > 0 ? count : 1) * sizeof(double)));
-  return NK_OK;
+  return nk_compiled_data_copy(P, d, bytes, out, memspace, false);
 }
 
 extern "C" int nk_problem_create_graph(nk_ctx *ctx, const char *source, int64_t nn, const int32_t *rowptr, const int32_t *colind,
@@ -481,57 +409,30 @@ extern "C" int nk_problem_create_graph(nk_ctx *ctx, const char *source, int64_t 
   NK_TRY(graph_compile(source, dof, nparams, nedge, nnode, GSET_JAC, fill_node, &code_j, &log));
 
   const int64_t slots = ne + nn, n = nn * dof, nnz = (int64_t)dof * dof * slots;
-  std::vector<int32_t> rp((size_t)n + 1), slotnode((size_t)slots), spos((size_t)nn);
+  std::vector<int32_t> rp((size_t)n + 1), slotnode, spos;
   std::vector<int64_t> gc((size_t)nnz);
   graph_pattern_fill<int64_t>(nn, ne, rowptr, colind, dof, rp.data(), gc.data());
-  for (int64_t i = 0; i < nn; ++i) {
-    int32_t below = 0;
-    for (int64_t e = rowptr[i]; e < rowptr[i + 1] && colind[e] < i; ++e) ++below;
-    spos[(size_t)i] = below;
-    for (int64_t s = rowptr[i] + i; s < rowptr[i + 1] + i + 1; ++s) slotnode[(size_t)s] = (int32_t)i;
-  }
+  nk_graph_slots(nn, rowptr, colind, &slotnode, &spos);
 
   nk_graph_state *S = new nk_graph_state();
   auto guard = nk_make_guard(S, nk_graph_state_destroy);
-  S->ctx = ctx;
+  S->c.ctx = ctx;
   S->nn = (int)nn;
   S->ne = (int)ne;
   S->dof = dof;
-  S->np = nparams;
   S->nedge = nedge;
   S->nnode = nnode;
   S->fill_node = fill_node;
-  if (hipModuleLoadData(&S->mod_f, code_f.data()) != hipSuccess || hipModuleLoadData(&S->mod_jac, code_j.data()) != hipSuccess)
-    NK_FAIL(NK_E_HIP, "hipModuleLoadData failed");
-  if (hipModuleGetFunction(&S->fn_res, S->mod_f, "nk_graph_residual") != hipSuccess ||
-      hipModuleGetFunction(&S->fn_jvp, S->mod_f, "nk_graph_jvp") != hipSuccess ||
-      hipModuleGetFunction(&S->fn_jac, S->mod_jac, "nk_graph_jac") != hipSuccess)
-    NK_FAIL(NK_E_HIP, "a generated graph kernel is missing from the compiled module");
+  NK_TRY(nk_compiled_load(&S->c, code_f, code_j, "nk_graph_residual", "nk_graph_jvp", "nk_graph_jac", "graph"));
   NK_TRY(nk_upload(ctx, &S->d_rowptr, std::vector<int32_t>(rowptr, rowptr + nn + 1)));
   NK_TRY(nk_upload(ctx, &S->d_colind, std::vector<int32_t>(colind, colind + ne)));
   NK_TRY(nk_upload(ctx, &S->d_slotnode, slotnode));
   NK_TRY(nk_upload(ctx, &S->d_spos, spos));
-  NK_TRY(nk_dev_alloc(&S->d_params, (size_t)(nparams > 0 ? nparams : 1)));
-  if (nparams > 0) NK_HIP(nk_memcpy(ctx, S->d_params, params, (size_t)nparams * sizeof(double), hipMemcpyHostToDevice));
-  NK_TRY(graph_zeros(ctx, &S->d_edge, (size_t)nedge * (size_t)ne));   // zero until nk_problem_set_graph_data
-  NK_TRY(graph_zeros(ctx, &S->d_node, (size_t)nnode * (size_t)nn));
-  NK_TRY(nk_csr_create_local(ctx, n, n, 0, rp, gc, nullptr, &S->pattern));
-
-  nk_problem *P = new nk_problem();
-  P->ctx = ctx;
-  P->kind = NK_PROBLEM_USER;
-  P->n_local = n;
-  P->n_global = n;
-  P->row_begin = 0;
-  P->nparams = nparams;
-  for (int i = 0; i < nparams && i < 8; ++i) P->params[i] = params[i];
-  P->cb.residual = graph_cb_residual;
-  P->cb.jvp = graph_cb_jvp;
-  P->cb.vjp = nullptr;   // Jᵀv: user_lin_J + the transposed SpMV
-  P->cb.jac_values = graph_cb_jac;
-  P->user = S;
-  P->user_pattern = S->pattern;
-  P->graph = guard.release();
-  *out = P;
+  NK_TRY(nk_compiled_params_init(&S->c, params, nparams));
+  NK_TRY(nk_compiled_zeros(ctx, &S->d_edge, (size_t)nedge * (size_t)ne));   // zero until nk_problem_set_graph_data
+  NK_TRY(nk_compiled_zeros(ctx, &S->d_node, (size_t)nnode * (size_t)nn));
+  NK_TRY(nk_csr_create_local(ctx, n, n, 0, rp, gc, nullptr, &S->c.pattern));
+  NK_TRY(nk_compiled_problem(&S->c, n, n, 0, params, nparams, {graph_cb_residual, graph_cb_jvp, nullptr, graph_cb_jac}, S, out));
+  (*out)->graph = guard.release();
   return NK_OK;
 }

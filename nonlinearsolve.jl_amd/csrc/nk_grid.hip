@@ -71,8 +71,6 @@
 
 #include <algorithm>
 #include <initializer_list>
-#include <map>
-#include <mutex>
 #include <string>
 #include <vector>
 
@@ -900,46 +898,23 @@ static int grid_compile(const char *source, int dim, int dof, int stencil, int b
   const std::string stencil_text = grid_stencil_text(*st);
   const std::string full = std::string(nk_dual_prelude) + stencil_text + k_grid_types + k_grid_fields + "\n// ---- user source\n" +
                            source + "\n" + k_grid_kernels;
-  const std::string defs[] = {"-DNK_DIM=" + std::to_string(dim), "-DNK_NFIELDS=" + std::to_string(nf),
-                              "-DNK_DOF=" + std::to_string(dof),
-                              "-DNK_XLO=" + std::to_string(sd.kind[0]), "-DNK_XHI=" + std::to_string(sd.kind[1]),
-                              "-DNK_YLO=" + std::to_string(sd.kind[2]), "-DNK_YHI=" + std::to_string(sd.kind[3]),
-                              "-DNK_ZLO=" + std::to_string(sd.kind[4]), "-DNK_ZHI=" + std::to_string(sd.kind[5]),
-                              "-DNK_CH=" + std::to_string(gset == GSET_JAC ? st->npts * dof : 1),
-                              "-DNK_GRID_SET=" + std::to_string(gset), std::string("-DNK_GRID_DIRECT=") + (direct ? "1" : "0")};
-  std::vector<const char *> opts = {"--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-std=c++17"};
-  for (const std::string &d : defs) opts.push_back(d.c_str());
-  std::string zdefs[6];
+  std::vector<std::string> defs = {"-DNK_DIM=" + std::to_string(dim), "-DNK_NFIELDS=" + std::to_string(nf),
+                                   "-DNK_DOF=" + std::to_string(dof),
+                                   "-DNK_XLO=" + std::to_string(sd.kind[0]), "-DNK_XHI=" + std::to_string(sd.kind[1]),
+                                   "-DNK_YLO=" + std::to_string(sd.kind[2]), "-DNK_YHI=" + std::to_string(sd.kind[3]),
+                                   "-DNK_ZLO=" + std::to_string(sd.kind[4]), "-DNK_ZHI=" + std::to_string(sd.kind[5]),
+                                   "-DNK_CH=" + std::to_string(gset == GSET_JAC ? st->npts * dof : 1),
+                                   "-DNK_GRID_SET=" + std::to_string(gset), std::string("-DNK_GRID_DIRECT=") + (direct ? "1" : "0")};
   if (cut.any()) {
     const char *const zn[3] = {"OWN", "LO", "HI"};
     for (int z = 0; z < 3; ++z) {
-      zdefs[2 * z] = std::string("-DNK_ZORD_") + zn[z] + "=" + std::to_string(cut.zord[z]);
-      zdefs[2 * z + 1] = std::string("-DNK_ZGRP_") + zn[z] + "=" + std::to_string(cut.zgrp[z]);
+      defs.push_back(std::string("-DNK_ZORD_") + zn[z] + "=" + std::to_string(cut.zord[z]));
+      defs.push_back(std::string("-DNK_ZGRP_") + zn[z] + "=" + std::to_string(cut.zgrp[z]));
     }
-    for (const std::string &d : zdefs) opts.push_back(d.c_str());
   }
-  // the same source for the same stencil with the same options gives the same code object: problems created again (another grid
-  // size, another context) skip the compiler. The key holds all that varies between two programs: the options, the stencil's
-  // lines and the user's source (the rest of the text is the same for all)
-  static std::mutex mtx;
-  static std::map<std::string, std::vector<char>> cache;
-  std::string key;
-  for (const char *o : opts) { key += o; key += ' '; }
-  key += stencil_text;
-  key += source;
-  {
-    std::lock_guard<std::mutex> lock(mtx);
-    auto it = cache.find(key);
-    if (it != cache.end()) { *code = it->second; return NK_OK; }
-  }
-  bool failed = false;
-  NK_TRY(nk_rtc_compile(full, "nk_grid_user.hip", opts, code, log, &failed));
-  if (failed)
-    NK_FAIL(NK_E_INVALID, "grid residual source does not compile (%s): %.900s", grid_contract(dim, nf).c_str(),
-            log && !log->empty() ? log->c_str() : "(no log)");
-  std::lock_guard<std::mutex> lock(mtx);
-  cache[key] = *code;
-  return NK_OK;
+  // what varies between two grid programs beside the options: the stencil's lines and the user's source (the rest of the text is
+  // the same for all)
+  return nk_rtc_program(full, "nk_grid_user.hip", defs, stencil_text + source, "grid", grid_contract(dim, nf).c_str(), code, log);
 }
 
 // A/B switch: every thread of the Jacobian fill stores its own partials (no staging in LDS)
@@ -982,11 +957,7 @@ static int grid_code_object(const char *source, int dim, int dof, int stencil, i
   std::string log;
   NK_TRY(grid_compile(source, dim, dof, stencil, boundary, nparams, nfields, jac != 0 ? GSET_JAC : GSET_F, grid_fill_direct(), &code,
                       &log, nranks, rank));
-  *bytes = (int64_t)code.size();
-  if (!buf) return NK_OK;
-  NK_REQUIRE(capacity >= *bytes, "buffer of %lld bytes, the code object has %lld", (long long)capacity, (long long)*bytes);
-  memcpy(buf, code.data(), code.size());
-  return NK_OK;
+  return nk_rtc_copy_out(code, buf, capacity, bytes);
 }
 extern "C" int nk_grid_code_object(const char *source, int dof, int stencil, int boundary, int nparams, int jac, void *buf,
                                    int64_t capacity, int64_t *bytes) {
@@ -1022,16 +993,12 @@ struct grid_slab_arg {
   const double *ulo = nullptr, *uhi = nullptr, *vlo = nullptr, *vhi = nullptr, *alo = nullptr, *ahi = nullptr;
 };
 struct nk_grid_state {
-  nk_ctx *ctx = nullptr;
-  int nx = 0, ny = 0, nz = 0 /* 0: a 2-D problem */, dof = 0, np = 0, nfields = 0;
+  nk_compiled c;   // the context, the programs, p and the pattern
+  int nx = 0, ny = 0, nz = 0 /* 0: a 2-D problem */, dof = 0, nfields = 0;
   int stencil = 0, boundary = 0;   // as the problem was created (nk_grid_level_create builds the same problem on a smaller grid)
   std::vector<char> code_f, code_j;   // the two code objects, kept by a problem made from source: a level of the geometric multigrid
                                       // loads them again (nothing is compiled twice) and keeps no copy of its own
-  hipModule_t mod_f = nullptr, mod_jac = nullptr;
-  hipFunction_t fn_res = nullptr, fn_jvp = nullptr, fn_jac = nullptr;
-  double *d_params = nullptr;   // np doubles (at least one allocated): the source's p
   double *d_fields = nullptr;   // nfields·nn doubles, field k of node m at k·nn + m (NULL without fields); zero at creation
-  nk_csr *pattern = nullptr;    // the problem's user_pattern
   // several ranks (nranks > 1; on one rank the slab is the grid and none of the rest is used)
   int64_t l0 = 0, l1 = 0, nn_loc = 0;   // the slab's lines (planes) of the outermost axis and its nodes
   bool cut = false, cut_lo = false, cut_hi = false;
@@ -1044,11 +1011,8 @@ struct nk_grid_state {
 
 void nk_grid_state_destroy(nk_grid_state *S) {
   if (!S) return;
-  if (S->mod_f) hipModuleUnload(S->mod_f);
-  if (S->mod_jac) hipModuleUnload(S->mod_jac);
-  hipFree(S->d_params);
+  nk_compiled_free(&S->c);
   hipFree(S->d_fields);
-  nk_csr_destroy(S->pattern);
   nk_halo_free(&S->halo_u);
   nk_halo_free(&S->halo_v);
   nk_halo_free(&S->halo_a);
@@ -1056,22 +1020,9 @@ void nk_grid_state_destroy(nk_grid_state *S) {
   delete S;
 }
 
-// One launch of a generated kernel on `stream`. Inside a profiled scope of the context (nk_problem_residual_dev,
-// nk_problem_jvp_dev and nk_problem_jac_values_dev open one around the callback) the launch carries start / stop events like
-// every NK_LAUNCH, so the generated kernels are timed by the same clock as the built-in ones.
-static int grid_launch(nk_grid_state *S, hipFunction_t fn, void **args, void *stream) {
-  const unsigned blocks = (unsigned)((S->nn_loc + 255) / 256);   // (one rank: the slab is the grid)
-  hipEvent_t e0, e1;
-  hipError_t e;
-  if (S->ctx->prof.on && (hipStream_t)stream == S->ctx->stream && nk_prof_next(S->ctx, &e0, &e1))
-    e = hipExtModuleLaunchKernel(fn, blocks * 256u, 1, 1, 256, 1, 1, 0, (hipStream_t)stream, args, nullptr, e0, e1, 0);   // (sizes in threads)
-  else
-    e = hipModuleLaunchKernel(fn, blocks, 1, 1, 256, 1, 1, 0, (hipStream_t)stream, args, nullptr);
-  return e != hipSuccess;
-}
-
-// the callbacks of the problem: launches of the generated kernels on the stream they are handed. The argument list is
-// nx, ny, [nz,] [the slab,] p, [fields,] and the kernel's own vectors: the sizes, then what the problem owns, then `rest`
+// the callbacks of the problem: launches of the generated kernels on the stream they are handed, one thread per node of the slab
+// (one rank: the slab is the grid). The argument list is nx, ny, [nz,] [the slab,] p, [fields,] and the kernel's own vectors:
+// the sizes, then what the problem owns, then `rest`
 static int grid_launch_args(nk_grid_state *S, hipFunction_t fn, std::initializer_list<void *> rest, void *stream) {
   void *args[11];
   int n = 0;
@@ -1079,10 +1030,10 @@ static int grid_launch_args(nk_grid_state *S, hipFunction_t fn, std::initializer
   args[n++] = &S->ny;
   if (S->nz > 0) args[n++] = &S->nz;
   if (S->cut) args[n++] = &S->slab;
-  args[n++] = &S->d_params;
+  args[n++] = &S->c.d_params;
   if (S->nfields > 0) args[n++] = &S->d_fields;
   for (void *a : rest) args[n++] = a;
-  return grid_launch(S, fn, args, stream);
+  return nk_compiled_launch(&S->c, fn, S->nn_loc, args, stream);
 }
 // Where the low and the high ghost lines of a plan are in its receive area, after an exchange (the peer transport alternates
 // between two areas). The layout rule of the built-in grid problems: a peer's block is [what serves as my low ghost][what
@@ -1103,7 +1054,7 @@ static int grid_stream_order(nk_grid_state *S, hipStream_t from, hipStream_t to)
 // what a callback reads across the cuts, exchanged before its launch: u, and v for the JVP
 static int grid_exchange(nk_grid_state *S, const double *u, const double *v, void *stream) {
   if (!S->cut) return NK_OK;
-  nk_ctx *ctx = S->ctx;
+  nk_ctx *ctx = S->c.ctx;
   NK_TRY(grid_stream_order(S, (hipStream_t)stream, ctx->stream));
   NK_TRY(nk_halo_exchange(ctx, &S->halo_u, u));
   grid_ghost_ptrs(S, S->halo_u, S->dof, &S->slab.ulo, &S->slab.uhi);
@@ -1116,29 +1067,18 @@ static int grid_exchange(nk_grid_state *S, const double *u, const double *v, voi
 static int grid_cb_residual(void *user, const double *u, double *f, void *stream) {
   nk_grid_state *S = (nk_grid_state *)user;
   if (grid_exchange(S, u, nullptr, stream) != NK_OK) return 1;
-  return grid_launch_args(S, S->fn_res, {&u, &f}, stream);
+  return grid_launch_args(S, S->c.fn_res, {&u, &f}, stream);
 }
 static int grid_cb_jvp(void *user, const double *v, const double *u, double *jv, void *stream) {
   nk_grid_state *S = (nk_grid_state *)user;
   if (grid_exchange(S, u, v, stream) != NK_OK) return 1;
-  return grid_launch_args(S, S->fn_jvp, {&u, &v, &jv}, stream);
+  return grid_launch_args(S, S->c.fn_jvp, {&u, &v, &jv}, stream);
 }
 static int grid_cb_jac(void *user, const double *u, double *vals, void *stream) {
   nk_grid_state *S = (nk_grid_state *)user;
   if (grid_exchange(S, u, nullptr, stream) != NK_OK) return 1;
-  const int32_t *rowptr = S->pattern->d_rowptr;
-  return grid_launch_args(S, S->fn_jac, {&u, &rowptr, &vals}, stream);
-}
-
-int nk_grid_set_params(nk_problem *P, const double *params, int nparams) {
-  nk_grid_state *S = P->grid;
-  NK_REQUIRE(nparams == S->np, "nparams mismatch (%d vs %d)", nparams, S->np);
-  NK_HIP(hipSetDevice(S->ctx->device));
-  if (nparams > 0) NK_HIP(nk_memcpy(S->ctx, S->d_params, params, (size_t)nparams * sizeof(double), hipMemcpyHostToDevice));
-  for (int i = 0; i < nparams && i < 8; ++i) P->params[i] = params[i];   // (the first eight, for inspection; the kernels read d_params)
-  P->params_version++;
-  nk_problem_invalidate(P);   // a Jacobian cached for the same u belongs to the old parameters
-  return NK_OK;
+  const int32_t *rowptr = S->c.pattern->d_rowptr;
+  return grid_launch_args(S, S->c.fn_jac, {&u, &rowptr, &vals}, stream);
 }
 
 // field k of a problem with fields: its doubles on the device, one per node of the rank's slab (one rank: of the grid)
@@ -1156,7 +1096,7 @@ static int grid_field_ptr(nk_problem *P, int k, double **d_field, size_t *bytes)
 }
 static int grid_exchange_fields(nk_grid_state *S) {
   if (!S->cut || S->nfields == 0) return NK_OK;
-  NK_TRY(nk_halo_exchange(S->ctx, &S->halo_a, S->d_fields));
+  NK_TRY(nk_halo_exchange(S->c.ctx, &S->halo_a, S->d_fields));
   grid_ghost_ptrs(S, S->halo_a, S->nfields, &S->slab.alo, &S->slab.ahi);
   return NK_OK;
 }
@@ -1164,24 +1104,16 @@ extern "C" int nk_problem_set_field(nk_problem *P, int k, const double *data, in
   double *d = nullptr;
   size_t bytes = 0;
   NK_TRY(grid_field_ptr(P, k, &d, &bytes));
-  NK_REQUIRE(data, "NULL data");
-  NK_REQUIRE(memspace == NK_HOST || memspace == NK_DEVICE, "memspace = %d is neither NK_HOST nor NK_DEVICE", memspace);
-  NK_HIP(hipSetDevice(P->grid->ctx->device));
-  NK_HIP(nk_memcpy(P->grid->ctx, d, data, bytes, memspace == NK_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice));
+  NK_TRY(nk_compiled_data_copy(P, d, bytes, data, memspace, true));
   NK_TRY(grid_exchange_fields(P->grid));   // several ranks: the ghost lines of the fields, once, here (collective)
-  P->params_version++;
-  nk_problem_invalidate(P);   // a Jacobian cached for the same u belongs to the old field
+  nk_compiled_data_changed(P);
   return NK_OK;
 }
 extern "C" int nk_problem_get_field(nk_problem *P, int k, double *out, int memspace) {
   double *d = nullptr;
   size_t bytes = 0;
   NK_TRY(grid_field_ptr(P, k, &d, &bytes));
-  NK_REQUIRE(out, "NULL out");
-  NK_REQUIRE(memspace == NK_HOST || memspace == NK_DEVICE, "memspace = %d is neither NK_HOST nor NK_DEVICE", memspace);
-  NK_HIP(hipSetDevice(P->grid->ctx->device));
-  NK_HIP(nk_memcpy(P->grid->ctx, out, d, bytes, memspace == NK_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost));
-  return NK_OK;
+  return nk_compiled_data_copy(P, d, bytes, out, memspace, false);
 }
 
 // Several ranks: the halo plans of a slab. The last `radius` lines (planes) of every component go up, the first `radius` down
@@ -1190,7 +1122,7 @@ extern "C" int nk_problem_get_field(nk_problem *P, int k, double *out, int memsp
 // One plan per vector a launch reads (nk_halo has one receive area) and one over all fields; the fields' ghost lines are
 // exchanged here once, so that they are the zeros of the fields themselves.
 static int grid_setup_halos(nk_grid_state *S, int dim, int stencil, int boundary) {
-  nk_ctx *ctx = S->ctx;
+  nk_ctx *ctx = S->c.ctx;
   const int R = ctx->nranks, r = ctx->rank;
   const grid_stencil *st = grid_find(dim, stencil);
   grid_sides sd;
@@ -1257,12 +1189,11 @@ static int grid_assemble(nk_ctx *ctx, int dim, int64_t nx, int64_t ny, int64_t n
 
   nk_grid_state *S = new nk_grid_state();
   auto guard = nk_make_guard(S, nk_grid_state_destroy);
-  S->ctx = ctx;
+  S->c.ctx = ctx;
   S->nx = (int)nx;
   S->ny = (int)ny;
   S->nz = dim == 3 ? (int)nz : 0;
   S->dof = dof;
-  S->np = nparams;
   S->nfields = nfields;
   S->stencil = stencil;
   S->boundary = boundary;
@@ -1273,38 +1204,18 @@ static int grid_assemble(nk_ctx *ctx, int dim, int64_t nx, int64_t ny, int64_t n
   S->l0 = l0;
   S->l1 = l1;
   S->nn_loc = nn_loc;
-  if (hipModuleLoadData(&S->mod_f, code_f.data()) != hipSuccess || hipModuleLoadData(&S->mod_jac, code_j.data()) != hipSuccess)
-    NK_FAIL(NK_E_HIP, "hipModuleLoadData failed");
-  if (hipModuleGetFunction(&S->fn_res, S->mod_f, dim == 3 ? "nk_grid3_residual" : "nk_grid_residual") != hipSuccess ||
-      hipModuleGetFunction(&S->fn_jvp, S->mod_f, dim == 3 ? "nk_grid3_jvp" : "nk_grid_jvp") != hipSuccess ||
-      hipModuleGetFunction(&S->fn_jac, S->mod_jac, dim == 3 ? "nk_grid3_jac" : "nk_grid_jac") != hipSuccess)
-    NK_FAIL(NK_E_HIP, "a generated grid kernel is missing from the compiled module");
-  NK_TRY(nk_dev_alloc(&S->d_params, (size_t)(nparams > 0 ? nparams : 1)));
-  if (nparams > 0 && params) NK_HIP(nk_memcpy(ctx, S->d_params, params, (size_t)nparams * sizeof(double), hipMemcpyHostToDevice));
-  if (nfields > 0) {   // zero until nk_problem_set_field: nothing is ever read uninitialised
-    const size_t cnt = (size_t)nfields * (size_t)nn_loc;
-    NK_TRY(nk_dev_alloc(&S->d_fields, cnt));
-    NK_HIP(nk_memset(ctx, S->d_fields, 0, cnt * sizeof(double)));
-  }
+  if (dim == 3)
+    NK_TRY(nk_compiled_load(&S->c, code_f, code_j, "nk_grid3_residual", "nk_grid3_jvp", "nk_grid3_jac", "grid"));
+  else
+    NK_TRY(nk_compiled_load(&S->c, code_f, code_j, "nk_grid_residual", "nk_grid_jvp", "nk_grid_jac", "grid"));
+  NK_TRY(nk_compiled_params_init(&S->c, params, nparams));
+  // zero until nk_problem_set_field: nothing is ever read uninitialised
+  if (nfields > 0) NK_TRY(nk_compiled_zeros(ctx, &S->d_fields, (size_t)nfields * (size_t)nn_loc));
   if (R > 1) NK_TRY(grid_setup_halos(S, dim, stencil, boundary));   // (collective, like the pattern's own plan below)
-  NK_TRY(nk_csr_create_local(ctx, n, n_global, dof * line * l0, rp, gc, nullptr, &S->pattern));
-
-  nk_problem *P = new nk_problem();
-  P->ctx = ctx;
-  P->kind = NK_PROBLEM_USER;
-  P->n_local = n;
-  P->n_global = n_global;
-  P->row_begin = dof * line * l0;
-  P->nparams = nparams;
-  for (int i = 0; params && i < nparams && i < 8; ++i) P->params[i] = params[i];
-  P->cb.residual = grid_cb_residual;
-  P->cb.jvp = grid_cb_jvp;
-  P->cb.vjp = nullptr;   // Jᵀv: user_lin_J + the transposed SpMV
-  P->cb.jac_values = grid_cb_jac;
-  P->user = S;
-  P->user_pattern = S->pattern;
-  P->grid = guard.release();
-  *out = P;
+  NK_TRY(nk_csr_create_local(ctx, n, n_global, dof * line * l0, rp, gc, nullptr, &S->c.pattern));
+  NK_TRY(nk_compiled_problem(&S->c, n, n_global, dof * line * l0, params, nparams,
+                             {grid_cb_residual, grid_cb_jvp, nullptr, grid_cb_jac}, S, out));
+  (*out)->grid = guard.release();
   return NK_OK;
 }
 
@@ -1353,10 +1264,10 @@ int nk_grid_level_create(nk_problem *fine, int64_t nx, int64_t ny, int64_t nz, n
   NK_REQUIRE(fine && fine->grid && out, "the problem is not a compiled grid problem");
   nk_grid_state *F = fine->grid;
   NK_REQUIRE(!F->code_f.empty() && !F->code_j.empty(), "a level is built from a problem made from source, not from another level");
-  NK_REQUIRE(F->ctx->nranks == 1, "a level of a compiled grid problem is built on one rank, the context has %d", F->ctx->nranks);
-  NK_HIP(hipSetDevice(F->ctx->device));
+  NK_REQUIRE(F->c.ctx->nranks == 1, "a level of a compiled grid problem is built on one rank, the context has %d", F->c.ctx->nranks);
+  NK_HIP(hipSetDevice(F->c.ctx->device));
   const int dim = F->nz > 0 ? 3 : 2;
-  NK_TRY(grid_assemble(F->ctx, dim, nx, ny, dim == 3 ? nz : 1, F->dof, F->stencil, F->boundary, nullptr, F->np, F->nfields, F->code_f,
+  NK_TRY(grid_assemble(F->c.ctx, dim, nx, ny, dim == 3 ? nz : 1, F->dof, F->stencil, F->boundary, nullptr, F->c.np, F->nfields, F->code_f,
                        F->code_j, -1, 0, 0, false, out));
   const int st = nk_grid_level_sync_params(fine, *out);
   if (st != NK_OK) { nk_problem_destroy(*out); *out = nullptr; }
@@ -1365,7 +1276,7 @@ int nk_grid_level_create(nk_problem *fine, int64_t nx, int64_t ny, int64_t nz, n
 // p of the fine problem, as it is now, into a level's
 int nk_grid_level_sync_params(nk_problem *fine, nk_problem *level) {
   nk_grid_state *F = fine->grid, *S = level->grid;
-  if (F->np > 0) NK_HIP(hipMemcpyAsync(S->d_params, F->d_params, (size_t)F->np * sizeof(double), hipMemcpyDeviceToDevice, F->ctx->stream));
+  if (F->c.np > 0) NK_HIP(hipMemcpyAsync(S->c.d_params, F->c.d_params, (size_t)F->c.np * sizeof(double), hipMemcpyDeviceToDevice, F->c.ctx->stream));
   for (int i = 0; i < 8; ++i) level->params[i] = fine->params[i];
   nk_problem_invalidate(level);
   return NK_OK;

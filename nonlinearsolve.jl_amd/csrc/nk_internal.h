@@ -52,6 +52,18 @@ extern const char *const nk_dual_prelude;
 // hiprtc (through dlopen) on `full`: code object into `code`, compiler log into `log` (nullable); *failed = it did not compile
 int nk_rtc_compile(const std::string &full, const char *name, const std::vector<const char *> &opts, std::vector<char> *code,
                    std::string *log, bool *failed);
+// the lift of an nk_real to the source's T, after the prelude in the graph and element programs (-DNK_SEED_SET = the program's set)
+extern const char *const nk_seed_lift;
+// --offload-arch=gfx950 -O3 -ffp-contract=off -std=c++17: what every program is compiled with
+std::vector<const char *> nk_rtc_base_options();
+// One program of a compiled problem kind, through the one cache of code objects: `full` under the file name `name` with the base
+// options and the kind's `defs`. `varying` is the part of `full` that differs between two programs of that name (the user's
+// source; for grids the stencil's lines too) — with `name` and the options it is the cache key. A source that does not compile:
+// NK_E_INVALID "<what> residual source does not compile (<contract>): <log>"
+int nk_rtc_program(const std::string &full, const char *name, const std::vector<std::string> &defs, const std::string &varying,
+                   const char *what, const char *contract, std::vector<char> *code, std::string *log);
+// the tail of every *_code_object entry point: the size into *bytes, the bytes into buf if there is one and it is large enough
+int nk_rtc_copy_out(const std::vector<char> &code, void *buf, int64_t capacity, int64_t *bytes);
 
 // ----------------------------------------------------------------------------- context
 constexpr int NK_BLOCK = 256;          // 4 wavefronts of 64
@@ -382,6 +394,8 @@ struct nk_problem {
   // compiled element problem (nk_problem_create_elements, nk_elem.hip): a residual given element by element on a mesh; owns its
   // modules, the mesh tables, the gather lists, the element buffers, its data and fixed-unknown buffers and user_pattern
   struct nk_elem_state *elem = nullptr;
+  // what the three compiled kinds have in common (nk_compiled.hip): a member of the state above, not owned separately
+  struct nk_compiled *compiled = nullptr;
   // forward-difference JVP for user problems without a jvp callback: f(u) at the linearisation point, u + εv, f(u + εv)
   double *d_fd_f0 = nullptr, *d_fd_up = nullptr, *d_fd_f1 = nullptr;
   // operator fallbacks through the Jacobian (prepare_jvp / prepare_vjp, SciMLJacobianOperators.jl:296-362,373-431): a private
@@ -395,12 +409,14 @@ struct nk_problem {
   bool pw_tried = false;
 };
 void nk_grid_state_destroy(struct nk_grid_state *S);
-int nk_grid_set_params(nk_problem *P, const double *params, int nparams);   // nk_problem_set_params of a compiled grid problem
 void nk_graph_state_destroy(struct nk_graph_state *S);
-int nk_graph_set_params(nk_problem *P, const double *params, int nparams);  // nk_problem_set_params of a compiled graph problem
 void nk_elem_state_destroy(struct nk_elem_state *S);
-int nk_elem_set_params(nk_problem *P, const double *params, int nparams);   // nk_problem_set_params of a compiled element problem
 int nk_elem_initial_guess(nk_problem *P, double *d_u);                      // zeros, the fixed values written in
+// what nk_elem.hip asks of nk_graph.hip: for a validated adjacency, the node of every global slot (ne + nn) and the self slot of
+// every node (nn); and the Jacobian's CSR with 64-bit columns (jrowptr: dof·nn + 1, jcolind: dof²·(ne + nn))
+void nk_graph_slots(int64_t nn, const int32_t *rowptr, const int32_t *colind, std::vector<int32_t> *slotnode, std::vector<int32_t> *spos);
+void nk_graph_pattern_fill64(int64_t nn, int64_t ne, const int32_t *rowptr, const int32_t *colind, int dof, int32_t *jrowptr,
+                             int64_t *jcolind);
 // what the geometric multigrid of compiled grid problems (nk_gridmg.hip) asks of nk_grid.hip
 struct nk_grid_shape_info {
   int dim, n[3] /* nx, ny, nz (2-D: nz = 1) */, dof, nfields, radius, kind[6] /* x-lo, x-hi, y-lo, y-hi, z-lo, z-hi */;
@@ -998,6 +1014,41 @@ template <class T>
 static inline int nk_upload(const nk_ctx *ctx, T **dst, const std::vector<T> &src) {
   NK_TRY(nk_dev_alloc(dst, src.size() + 1));
   if (!src.empty()) NK_HIP(nk_memcpy(ctx, *dst, src.data(), src.size() * sizeof(T), hipMemcpyHostToDevice));
+  return NK_OK;
+}
+
+// ----------------------------------------------------------------------------- compiled problems (nk_compiled.hip)
+// What every compiled problem kind (nk_grid.hip, nk_graph.hip, nk_elem.hip) owns and does alike. A kind writes its device types
+// and kernels, its host tables, its contract and its validation; its state holds one nk_compiled as a member.
+struct nk_compiled {
+  nk_ctx *ctx = nullptr;
+  hipModule_t mod_f = nullptr, mod_jac = nullptr;   // the residual + JVP program; the fill's
+  hipFunction_t fn_res = nullptr, fn_jvp = nullptr, fn_jac = nullptr;
+  double *d_params = nullptr;   // np doubles (at least one allocated): the source's p
+  int np = 0;
+  nk_csr *pattern = nullptr;    // the problem's user_pattern
+};
+// the two code objects loaded and the three kernels looked up; `what` words the message of a missing kernel ("grid", …)
+int nk_compiled_load(nk_compiled *C, const std::vector<char> &code_f, const std::vector<char> &code_j, const char *name_res,
+                     const char *name_jvp, const char *name_jac, const char *what);
+// d_params of max(nparams, 1) doubles; params (NULL: the caller fills the buffer on the device) copied in
+int nk_compiled_params_init(nk_compiled *C, const double *params, int nparams);
+// one launch of a generated kernel over `items` threads in blocks of 256 on `stream`; nonzero on failure (a callback's return)
+int nk_compiled_launch(nk_compiled *C, hipFunction_t fn, int64_t items, void **args, void *stream);
+void nk_compiled_free(nk_compiled *C);   // the modules, d_params and the pattern
+int nk_compiled_set_params(nk_problem *P, const double *params, int nparams);   // nk_problem_set_params of a compiled problem
+// the NK_PROBLEM_USER problem over C (C->pattern is its user_pattern); the caller sets its typed state pointer
+int nk_compiled_problem(nk_compiled *C, int64_t n_local, int64_t n_global, int64_t row_begin, const double *params, int nparams,
+                        const nk_user_callbacks &cb, void *user, nk_problem **out);
+// One read-only data array of a compiled problem, to the device (user_ptr → device_ptr) or back, after the kind's own lookup of
+// device_ptr and bytes. A setter then calls nk_compiled_data_changed: a Jacobian cached for the same u belongs to the old data
+int nk_compiled_data_copy(nk_problem *P, double *device_ptr, size_t bytes, const void *user_ptr, int memspace, bool to_device);
+void nk_compiled_data_changed(nk_problem *P);
+// a zero-filled device array (at least one element allocated, so that a kernel always gets a pointer)
+template <class T>
+static inline int nk_compiled_zeros(const nk_ctx *ctx, T **d, size_t count) {
+  NK_TRY(nk_dev_alloc(d, count > 0 ? count : 1));
+  NK_HIP(nk_memset(ctx, *d, 0, (count > 0 ? count : 1) * sizeof(T)));
   return NK_OK;
 }
 #ifdef __HIPCC__

@@ -596,10 +596,8 @@ extern "C" int nk_problem_size(nk_problem *P, int64_t *n_local, int64_t *n_globa
   return NK_OK;
 }
 extern "C" int nk_problem_set_params(nk_problem *P, const double *params, int nparams) {
-  NK_REQUIRE(P && (params || ((P->grid || P->graph || P->elem) && nparams == 0)), "NULL argument");
-  if (P->grid) return nk_grid_set_params(P, params, nparams);   // up to 32 values, kept on the device for the generated kernels
-  if (P->graph) return nk_graph_set_params(P, params, nparams);
-  if (P->elem) return nk_elem_set_params(P, params, nparams);
+  NK_REQUIRE(P && (params || (P->compiled && nparams == 0)), "NULL argument");
+  if (P->compiled) return nk_compiled_set_params(P, params, nparams);   // up to 32 values, kept on the device for the generated kernels
   NK_REQUIRE(nparams == P->nparams, "nparams mismatch (%d vs %d)", nparams, P->nparams);
   if (P->kind == NK_PROBLEM_QUADRATIC) {
     NK_REQUIRE((int64_t)params[0] == P->n_global, "cannot change the problem size");

@@ -1,8 +1,12 @@
 // hiprtc through dlopen, and the device-side prelude every run-time compiled kernel set starts with: the working precision
-// and the forward-mode dual numbers. Shared by the ensemble kernels (nk_batch.hip), the compiled grid problems (nk_grid.hip)
-// and the compiled graph problems (nk_graph.hip).
+// and the forward-mode dual numbers; the cache of compiled programs and the copy-out of a code object. Shared by the ensemble
+// kernels (nk_batch.hip: the prelude, the base options and the copy-out; it does not cache) and the compiled grid, graph and
+// element problems (nk_grid.hip, nk_graph.hip, nk_elem.hip).
 #include <dlfcn.h>
+#include <string.h>
 
+#include <map>
+#include <mutex>
 #include <string>
 #include <vector>
 
@@ -72,6 +76,29 @@ __device__ inline Dual pow(const Dual &a, double e) { return pow(a, (nk_real)e);
 __device__ inline Dual pow(const Dual &a, const Dual &b) { return exp(b * log(a)); }
 )NKSRC";
 
+// after the prelude in the graph and element programs (-DNK_SEED_SET: 0 in the residual and JVP program, 1 in the fill's)
+const char *const nk_seed_lift = R"NKSRC(
+// an nk_real read from u becomes the source's T: itself, the dual with its one partial from v (NK_SEED_SET == 0), or the dual
+// with the unit seed of component c if the value belongs to what the thread seeds (`hot`) and no partial otherwise
+template <typename T> struct nk_lift;
+template <> struct nk_lift<nk_real> {
+  static __device__ __forceinline__ nk_real at(nk_real x, const nk_real *, int, int, bool) { return x; }
+};
+template <> struct nk_lift<Dual> {
+  static __device__ __forceinline__ Dual at(nk_real x, const nk_real *__restrict__ v, int el, int c, bool hot) {
+    Dual r;
+    r.v = x;
+#if NK_SEED_SET == 0
+    r.d[0] = v[el];
+#else
+#pragma unroll
+    for (int t = 0; t < NK_CH; ++t) r.d[t] = (hot && t == c) ? NK_R(1) : NK_R(0);
+#endif
+    return r;
+  }
+};
+)NKSRC";
+
 // ----------------------------------------------------------------------------- hiprtc through dlopen
 typedef void *rtc_program;
 static struct {
@@ -129,5 +156,45 @@ int nk_rtc_compile(const std::string &full, const char *name, const std::vector<
   code->resize(cs);
   RTC.Code(prog, code->data());
   RTC.Destroy(&prog);
+  return NK_OK;
+}
+
+// ----------------------------------------------------------------------------- the programs of the compiled problems
+std::vector<const char *> nk_rtc_base_options() { return {"--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-std=c++17"}; }
+
+// The same text with the same options gives the same code object: a problem created again (another size, another context) skips
+// the compiler. One cache for all kinds; the key holds all that varies between two programs — the program's name (so that two
+// kinds never share an entry), its options and `varying`, the part of `full` that is not the same for every program of the name.
+// A source that does not compile is not cached.
+int nk_rtc_program(const std::string &full, const char *name, const std::vector<std::string> &defs, const std::string &varying,
+                   const char *what, const char *contract, std::vector<char> *code, std::string *log) {
+  std::vector<const char *> opts = nk_rtc_base_options();
+  for (const std::string &d : defs) opts.push_back(d.c_str());
+  static std::mutex mtx;
+  static std::map<std::string, std::vector<char>> cache;
+  std::string key = std::string(name) + ' ';
+  for (const char *o : opts) { key += o; key += ' '; }
+  key += varying;
+  {
+    std::lock_guard<std::mutex> lock(mtx);
+    auto it = cache.find(key);
+    if (it != cache.end()) { *code = it->second; return NK_OK; }
+  }
+  bool failed = false;
+  NK_TRY(nk_rtc_compile(full, name, opts, code, log, &failed));
+  if (failed)
+    NK_FAIL(NK_E_INVALID, "%s residual source does not compile (%s): %.900s", what, contract,
+            log && !log->empty() ? log->c_str() : "(no log)");
+  std::lock_guard<std::mutex> lock(mtx);
+  cache[key] = *code;
+  return NK_OK;
+}
+
+// a code object handed out for inspection: *bytes gets its size; buf may be NULL to ask for the size only
+int nk_rtc_copy_out(const std::vector<char> &code, void *buf, int64_t capacity, int64_t *bytes) {
+  *bytes = (int64_t)code.size();
+  if (!buf) return NK_OK;
+  NK_REQUIRE(capacity >= *bytes, "buffer of %lld bytes, the code object has %lld", (long long)capacity, (long long)*bytes);
+  memcpy(buf, code.data(), code.size());
   return NK_OK;
 }
