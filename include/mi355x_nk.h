@@ -467,7 +467,9 @@ int nk_csr_colsumsq(nk_csr *A, double *out, int memspace);
 
 /* ---------------------------------------------------------------- problems (seam 2) */
 /* params: QUADRATIC {n, p}; BRATU2D {n_side, lambda, scale (0 → h², i.e. h²F)};
- *         BRUSSELATOR2D {N_g, A, B, alpha, dx}.  The problem partitions itself over the ctx's ranks. */
+ *         BRUSSELATOR2D {N_g, A, B, alpha, dx}.  The problem partitions itself over the ctx's ranks.
+ * Accepted sizes: BRATU2D 1 <= n_side < 2^30 (the JVP kernel indexes a grid line with an int; anything else, NaN included, is
+ * NK_E_INVALID with a message), and n_side >= the number of ranks; BRUSSELATOR2D N_g >= 3. */
 int nk_problem_create(nk_ctx *ctx, int kind, const double *params, int nparams, nk_problem **out);
 /* csr pattern (local rows, global columns, 0-based int32/int64) is optional: NULL ⇒ no concrete J. */
 int nk_problem_create_user(nk_ctx *ctx, int64_t n_local, int64_t n_global, int64_t row_begin,

@@ -156,35 +156,10 @@ __global__ __launch_bounds__(NK_BLOCK) void k_bratu_diag(int64_t n, double c_exp
   const int64_t k = (int64_t)blockIdx.x * NK_BLOCK + threadIdx.x;
   if (k < n) d[k] = c_exp * exp(u[k]);
 }
-__global__ __launch_bounds__(NK_BLOCK) void k_bratu_jvp(int64_t ns, int64_t nl, double c_lap,
-                                                        const double *__restrict__ d, const double *__restrict__ v,
-                                                        const double *__restrict__ lo, const double *__restrict__ hi,
-                                                        double *__restrict__ jv, const int *d_skip,
-                                                        const double *__restrict__ out_scale, const nk_spmv_epi epi) {
-  SKIP_GUARD(d_skip);
-  const double os = out_scale ? *out_scale : 1.0;
-  const int64_t k = (int64_t)blockIdx.x * NK_BLOCK + threadIdx.x;
-  if (k >= ns * nl) return;
-  const int64_t jl = k / ns, i = k - jl * ns;
-  const double vk = v[k];
-  const double res = c_lap * bratu_lap(v, lo, hi, ns, nl, i, jl, k) - d[k] * vk;
-  if (epi.mode == NK_EPI_PLAIN) {
-    jv[k] = os * res;
-  } else if (epi.mode == NK_EPI_SHIFTED) {  // Newton-basis step of the s-step Arnoldi process: scale·(J v − θ v)
-    jv[k] = os * (res - (*epi.theta) * vk);
-  } else if (epi.mode == NK_EPI_RESIDUAL) {  // fused residual: out = b − J v (b = epi.r)
-    jv[k] = epi.r[k] - res;
-  } else {  // fused Chebyshev step (v = d_old): r −= J d; d_new = c1 d_old + c2 r; y += d_new
-    const double rr = epi.r[k] - res;
-    epi.r[k] = rr;
-    const double dn = epi.c1 * vk + epi.c2 * rr;
-    epi.dnew[k] = dn;
-    epi.yacc[k] += dn;
-  }
-}
-// Tiled form of k_bratu_jvp: a thread owns column i of TY consecutive grid lines, so the TY+2 values of its column are
-// loaded once (6 instead of 12 vertical loads for TY = 4), the index arithmetic is 32-bit with no division (blockIdx.y is
-// the line tile), and every load of the tile is issued before the first use. Same arithmetic, term by term, as bratu_lap.
+// The Bratu JVP, tiled: a thread owns column i of TY consecutive grid lines, so the TY+2 values of its column are loaded once
+// (6 instead of 12 vertical loads for TY = 4), the index arithmetic is 32-bit with no division (blockIdx.y is the line tile), and
+// every load of the tile is issued before the first use. Same arithmetic, term by term, as bratu_lap. It is the only form:
+// nk_problem_create accepts 1 ≤ n_side < 2³⁰, so ns and nl fit an int (the element index is formed in size_t).
 template <int TY>
 __global__ __launch_bounds__(NK_BLOCK) void k_bratu_jvp_tile(int ns, int nl, double c_lap, const double *__restrict__ d,
                                                              const double *__restrict__ v,
@@ -403,16 +378,68 @@ __global__ __launch_bounds__(NK_BLOCK) void k_brus_u0(brus_par q, double *__rest
 // ============================================================================ host side
 static inline int grid1(int64_t n) { return (int)((n + NK_BLOCK - 1) / NK_BLOCK); }
 
-static brus_par brus_params(const nk_problem *P) {
+// ---------------------------------------------------------------------------- launches
+// One function per kernel family chooses kernel, grid and block from the raw slab: ns points per line, nl owned lines, the first
+// of them global line j0 (Brusselator), the ghost lines lo / hi (nullptr: none). nk_problem_*_dev and the development hooks at
+// the end of this file both come through here, so what the hooks measure is what a solve runs.
+static void bratu_coefficients(int64_t ns, double lambda, double scale, double *c_lap, double *c_exp) {
+  const double h = 1.0 / (double)(ns + 1);
+  const double s = (scale == 0.0) ? h * h : scale;
+  *c_lap = s / (h * h);
+  *c_exp = s * lambda;
+}
+static int launch_bratu_residual(nk_ctx *ctx, int64_t ns, int64_t nl, double c_lap, double c_exp, const double *d_u,
+                                 const double *lo, const double *hi, double *d_f) {
+  NK_LAUNCH(ctx, k_bratu_residual, dim3(grid1(ns * nl)), dim3(NK_BLOCK), ns, nl, c_lap, c_exp, d_u, lo, hi, d_f);
+  return NK_OK;
+}
+// *grid_out = the number of workgroups = the length of either half of `partials` (and of gpart). The discs' radii depend on the
+// GLOBAL position of a row, so gpart is filled only for a slab that is the whole grid (nl == ns, no ghost line)
+static int launch_bratu_residual_norms(nk_ctx *ctx, int64_t ns, int64_t nl, double c_lap, double c_exp, const double *d_u,
+                                       const double *lo, const double *hi, double *d_f, double *partials, double *f_copy,
+                                       double *ss_copy, double *gpart, int *grid_out) {
+  const int grid = nk_grid_for(ns * nl, NK_BLOCK * 4, NK_MAX_RED_BLOCKS);   // (k_absmax_sumsq's grid: nk_blas_norms_inf2)
+  const bool whole = nl == ns && lo == nullptr && hi == nullptr;
+  NK_LAUNCH(ctx, k_bratu_residual_norms, dim3(grid), dim3(NK_BLOCK), ns, nl, c_lap, c_exp, d_u, lo, hi, d_f, partials, f_copy,
+            ss_copy, whole ? gpart : (double *)nullptr);
+  *grid_out = grid;
+  return NK_OK;
+}
+static int launch_bratu_jvp(nk_ctx *ctx, int64_t ns, int64_t nl, double c_lap, const double *d_diag, const double *d_v,
+                            const double *lo, const double *hi, double *d_jv, const int *d_skip, const double *d_out_scale,
+                            const nk_spmv_epi &ep) {
+  if (ep.mode < NK_EPI_PLAIN || ep.mode > NK_EPI_SHIFTED)
+    NK_FAIL(NK_E_UNSUPPORTED, "internal: the Bratu JVP has no row epilogue %d (it has 0 plain, 1 Chebyshev step, 2 residual, 3 shifted)",
+            ep.mode);
+  constexpr int TY = 4;
+  const dim3 grid((unsigned)((ns + NK_BLOCK - 1) / NK_BLOCK), (unsigned)((nl + TY - 1) / TY));
+  NK_LAUNCH(ctx, k_bratu_jvp_tile<TY>, grid, dim3(NK_BLOCK), (int)ns, (int)nl, c_lap, d_diag, d_v, lo, hi, d_jv, d_skip,
+            d_out_scale, ep);
+  return NK_OK;
+}
+static int launch_brus_residual(nk_ctx *ctx, const brus_par &q, const double *d_u, const double *lo, const double *hi,
+                                double *d_f) {
+  NK_LAUNCH(ctx, k_brus_residual, dim3(grid1(q.N * q.nl)), dim3(NK_BLOCK), q, d_u, lo, hi, d_f);
+  return NK_OK;
+}
+static int launch_brus_jvp(nk_ctx *ctx, const brus_par &q, int transpose, const double *d_u, const double *d_v, const double *lo,
+                           const double *hi, double *d_jv, const int *d_skip, const double *d_out_scale) {
+  NK_LAUNCH(ctx, k_brus_jvp, dim3(grid1(q.N * q.nl)), dim3(NK_BLOCK), q, transpose, d_u, d_v, lo, hi, d_jv, d_skip, d_out_scale);
+  return NK_OK;
+}
+
+static brus_par brus_slab(int64_t N, int64_t nl, int64_t j0, double A, double B, double alpha, double dx) {
   brus_par q;
-  q.N = P->ns;
-  q.nl = P->j1 - P->j0;
-  q.j0 = P->j0;
-  q.A = P->params[1];
-  q.B = P->params[2];
-  const double dx = P->params[4];
-  q.alpha = P->params[3] / (dx * dx);
+  q.N = N;
+  q.nl = nl;
+  q.j0 = j0;
+  q.A = A;
+  q.B = B;
+  q.alpha = alpha / (dx * dx);
   return q;
+}
+static brus_par brus_params(const nk_problem *P) {
+  return brus_slab(P->ns, P->j1 - P->j0, P->j0, P->params[1], P->params[2], P->params[3], P->params[4]);
 }
 
 static int setup_grid_partition(nk_problem *P, int64_t ns, int dof_per_node, bool periodic) {
@@ -485,12 +512,13 @@ extern "C" int nk_problem_create(nk_ctx *ctx, int kind, const double *params, in
     P->n_local = e - b;
   } else if (kind == NK_PROBLEM_BRATU2D) {
     if (nparams < 2) { delete P; NK_FAIL(NK_E_INVALID, "BRATU2D needs {n_side, lambda[, scale]}"); }
+    // (the comparison is made on the double: a NaN or a value beyond int64_t must not reach the conversion)
+    if (!(params[0] >= 1.0 && params[0] < 1073741824.0)) {
+      delete P;
+      NK_FAIL(NK_E_INVALID, "BRATU2D needs 1 <= n_side < 2^30 (got %g): the JVP kernel indexes a grid line with an int", params[0]);
+    }
     const int64_t ns = (int64_t)params[0];
-    const double lam = params[1], sc = nparams >= 3 ? params[2] : 0.0;
-    const double h = 1.0 / (double)(ns + 1);
-    const double s = (sc == 0.0) ? h * h : sc;
-    P->c_lap = s / (h * h);
-    P->c_exp = s * lam;
+    bratu_coefficients(ns, params[1], nparams >= 3 ? params[2] : 0.0, &P->c_lap, &P->c_exp);
     st = setup_grid_partition(P, ns, 1, false);
   } else if (kind == NK_PROBLEM_BRUSSELATOR2D) {
     if (nparams < 5) { delete P; NK_FAIL(NK_E_INVALID, "BRUSSELATOR2D needs {N, A, B, alpha, dx}"); }
@@ -516,9 +544,7 @@ int nk_problem_create_bratu_replicated(nk_ctx *ctx, int64_t ns, double lambda, d
   P->params[0] = (double)ns;
   P->params[1] = lambda;
   P->params[2] = scale;
-  const double h = 1.0 / (double)(ns + 1), s = (scale == 0.0) ? h * h : scale;
-  P->c_lap = s / (h * h);
-  P->c_exp = s * lambda;
+  bratu_coefficients(ns, lambda, scale, &P->c_lap, &P->c_exp);
   P->ns = ns;
   P->j0 = 0;
   P->j1 = ns;
@@ -606,12 +632,7 @@ extern "C" int nk_problem_set_params(nk_problem *P, const double *params, int np
   }
   for (int i = 0; i < nparams; ++i) P->params[i] = params[i];
   P->params_version++;
-  if (P->kind == NK_PROBLEM_BRATU2D) {
-    const double h = 1.0 / (double)(P->ns + 1);
-    const double sc = nparams >= 3 ? params[2] : 0.0, s = (sc == 0.0) ? h * h : sc;
-    P->c_lap = s / (h * h);
-    P->c_exp = s * params[1];
-  }
+  if (P->kind == NK_PROBLEM_BRATU2D) bratu_coefficients(P->ns, params[1], nparams >= 3 ? params[2] : 0.0, &P->c_lap, &P->c_exp);
   return NK_OK;
 }
 
@@ -625,17 +646,14 @@ int nk_problem_residual_norms_dev(nk_problem *P, const double *d_u, double *d_f,
   nk_ctx *ctx = P->ctx;
   const int64_t n = P->n_local;
   if (off || n == 0 || P->kind != NK_PROBLEM_BRATU2D) return NK_OK;
-  const int grid = nk_grid_for(n, NK_BLOCK * 4, NK_MAX_RED_BLOCKS);   // (k_absmax_sumsq's grid: nk_blas_norms_inf2)
   nk_prof_scope prof_(ctx, NK_K_RESIDUAL, (f_copy ? 24.0 : 16.0) * (double)n);
   const double *lo, *hi;
   NK_TRY(nk_halo_exchange(ctx, &P->halo, d_u));
   halo_lines(P, 1, false, &lo, &hi);
-  // (the discs' radii depend on the GLOBAL position of a row: one rank with the whole grid only)
-  const bool whole = ctx->nranks == 1 && P->j0 == 0 && P->j1 == P->ns && !P->replicated;
-  NK_LAUNCH(ctx, k_bratu_residual_norms, dim3(grid), dim3(NK_BLOCK), P->ns, P->j1 - P->j0, P->c_lap, P->c_exp, d_u, lo, hi, d_f,
-            partials, f_copy, ss_copy, whole ? gpart : (double *)nullptr);
+  // (a replicated problem is a whole grid on every rank, but nobody asks for its bounds)
+  NK_TRY(launch_bratu_residual_norms(ctx, P->ns, P->j1 - P->j0, P->c_lap, P->c_exp, d_u, lo, hi, d_f, partials, f_copy, ss_copy,
+                                     P->replicated ? nullptr : gpart, grid_out));
   NK_HIP(hipGetLastError());
-  *grid_out = grid;
   return NK_OK;
 }
 int nk_problem_residual_dev(nk_problem *P, const double *d_u, double *d_f) {
@@ -651,16 +669,14 @@ int nk_problem_residual_dev(nk_problem *P, const double *d_u, double *d_f) {
       const double *lo, *hi;
       NK_TRY(nk_halo_exchange(ctx, &P->halo, d_u));
       halo_lines(P, 1, false, &lo, &hi);
-      NK_LAUNCH(ctx, k_bratu_residual, dim3(grid1(n)), dim3(NK_BLOCK), P->ns, P->j1 - P->j0,
-                         P->c_lap, P->c_exp, d_u, lo, hi, d_f);
+      NK_TRY(launch_bratu_residual(ctx, P->ns, P->j1 - P->j0, P->c_lap, P->c_exp, d_u, lo, hi, d_f));
       break;
     }
     case NK_PROBLEM_BRUSSELATOR2D: {
       const double *lo, *hi;
       NK_TRY(nk_halo_exchange(ctx, &P->halo, d_u));
       halo_lines(P, 2, true, &lo, &hi);
-      NK_LAUNCH(ctx, k_brus_residual, dim3(grid1(n / 2)), dim3(NK_BLOCK), brus_params(P), d_u, lo,
-                         hi, d_f);
+      NK_TRY(launch_brus_residual(ctx, brus_params(P), d_u, lo, hi, d_f));
       break;
     }
     case NK_PROBLEM_USER:
@@ -779,6 +795,7 @@ __global__ __launch_bounds__(NK_BLOCK) void k_fd_diff(int64_t n, const double *_
 int nk_problem_jvp_dev(nk_problem *P, const double *d_u, const double *d_v, double *d_jv, const int *d_skip,
                        const double *d_out_scale, const nk_spmv_epi *epi) {
   if (epi && epi->mode != NK_EPI_PLAIN && P->kind != NK_PROBLEM_BRATU2D)    NK_FAIL(NK_E_UNSUPPORTED, "internal: fused epilogue only exists for the Bratu JVP");
+  // (NK_EPI_RESIDUAL_UPDATE is the CSR kernel's alone; launch_bratu_jvp refuses it and anything else out of range)
   nk_spmv_epi ep{};
   if (epi) ep = *epi;
   nk_ctx *ctx = P->ctx;
@@ -803,24 +820,14 @@ int nk_problem_jvp_dev(nk_problem *P, const double *d_u, const double *d_v, doub
       const double *lo, *hi;
       NK_TRY(nk_halo_exchange(ctx, &P->halo, d_v));
       halo_lines(P, 1, false, &lo, &hi);
-      const int64_t nl = P->j1 - P->j0;
-      if (P->ns >= (1ll << 30)) {   // one point per thread: the tiled form indexes with int
-        NK_LAUNCH(ctx, k_bratu_jvp, dim3(grid1(n)), dim3(NK_BLOCK), P->ns, nl, P->c_lap, P->d_diag, d_v, lo, hi, d_jv,
-                  d_skip, d_out_scale, ep);
-      } else {
-        constexpr int TY = 4;
-        const dim3 grid((unsigned)((P->ns + NK_BLOCK - 1) / NK_BLOCK), (unsigned)((nl + TY - 1) / TY));
-        NK_LAUNCH(ctx, k_bratu_jvp_tile<TY>, grid, dim3(NK_BLOCK), (int)P->ns, (int)nl, P->c_lap, P->d_diag, d_v, lo, hi,
-                  d_jv, d_skip, d_out_scale, ep);
-      }
+      NK_TRY(launch_bratu_jvp(ctx, P->ns, P->j1 - P->j0, P->c_lap, P->d_diag, d_v, lo, hi, d_jv, d_skip, d_out_scale, ep));
       break;
     }
     case NK_PROBLEM_BRUSSELATOR2D: {
       const double *lo, *hi;
       NK_TRY(nk_halo_exchange(ctx, &P->halo, d_v));
       halo_lines(P, 2, true, &lo, &hi);
-      NK_LAUNCH(ctx, k_brus_jvp, dim3(grid1(n / 2)), dim3(NK_BLOCK), brus_params(P), 0, d_u, d_v,
-                         lo, hi, d_jv, d_skip, d_out_scale);
+      NK_TRY(launch_brus_jvp(ctx, brus_params(P), 0, d_u, d_v, lo, hi, d_jv, d_skip, d_out_scale));
       break;
     }
     case NK_PROBLEM_USER:
@@ -852,8 +859,7 @@ int nk_problem_vjp_dev(nk_problem *P, const double *d_u, const double *d_v, doub
     const double *lo, *hi;
     NK_TRY(nk_halo_exchange(ctx, &P->halo, d_v));
     halo_lines(P, 2, true, &lo, &hi);
-    NK_LAUNCH(ctx, k_brus_jvp, dim3(grid1(n / 2)), dim3(NK_BLOCK), brus_params(P), 1, d_u, d_v, lo,
-                       hi, d_vj, (const int *)nullptr, (const double *)nullptr);
+    NK_TRY(launch_brus_jvp(ctx, brus_params(P), 1, d_u, d_v, lo, hi, d_vj, nullptr, nullptr));
     NK_HIP(hipGetLastError());
     return NK_OK;
   }
@@ -1251,4 +1257,199 @@ extern "C" int nk_jac_values_colored(nk_problem *P, const double *u, int memspac
   NK_HIP(hipStreamSynchronize(P->ctx->stream));
   if (ncolors_out) *ncolors_out = J->ncolors;
   return NK_OK;
+}
+
+// ---------------------------------------------------------------------------- development harness (not in the public header)
+// Test hooks of tests/test_gpu_problem_kernels.py, exported like nk_spmv_epilogue_test. All arrays are HOST arrays; one rank.
+// Every hook reaches its kernel through the launch_* function the production entry point uses. Every device buffer a hook makes
+// lies between two guards of 8 doubles holding a canary; an output starts as canary throughout, so the caller sees an entry a
+// mode must not touch or a ragged tile failed to write. A changed guard word fails the call (after the outputs are delivered).
+namespace {
+constexpr size_t NK_T_GUARD = 8;
+constexpr double NK_T_CANARY = -6.02214076e23;
+struct test_bufs {
+  nk_ctx *ctx;
+  struct ent { double *d; size_t n; const char *name; };
+  std::vector<ent> all;
+  explicit test_bufs(nk_ctx *c) : ctx(c) {}
+  ~test_bufs() { for (ent &e : all) hipFree(e.d); }
+  // n doubles with the contents of `host` (nullptr: canary)
+  int make(const char *name, const double *host, size_t n, double **out) {
+    std::vector<double> w(n + 2 * NK_T_GUARD, NK_T_CANARY);
+    if (host && n) memcpy(w.data() + NK_T_GUARD, host, n * sizeof(double));
+    double *d = nullptr;
+    NK_TRY(nk_dev_alloc(&d, w.size()));
+    all.push_back({d, n, name});
+    NK_HIP(nk_memcpy(ctx, d, w.data(), w.size() * sizeof(double), hipMemcpyHostToDevice));
+    *out = d + NK_T_GUARD;
+    return NK_OK;
+  }
+  // the same for an optional argument: no host array, no device array
+  int opt(const char *name, const double *host, size_t n, double **out) {
+    *out = nullptr;
+    return host ? make(name, host, n, out) : NK_OK;
+  }
+  int fetch(double *host, const double *dev, size_t n) {
+    if (host && dev && n) NK_HIP(nk_memcpy(ctx, host, dev, n * sizeof(double), hipMemcpyDeviceToHost));
+    return NK_OK;
+  }
+  int check_guards() {
+    const double c = NK_T_CANARY;
+    for (const ent &e : all) {
+      double g[2 * NK_T_GUARD];
+      NK_HIP(nk_memcpy(ctx, g, e.d, NK_T_GUARD * sizeof(double), hipMemcpyDeviceToHost));
+      NK_HIP(nk_memcpy(ctx, g + NK_T_GUARD, e.d + NK_T_GUARD + e.n, NK_T_GUARD * sizeof(double), hipMemcpyDeviceToHost));
+      for (size_t i = 0; i < 2 * NK_T_GUARD; ++i)
+        if (memcmp(&g[i], &c, sizeof(double)) != 0)
+          NK_FAIL(NK_E_HIP, "test hook: guard word %d %s `%s` (%zu doubles) was overwritten", (int)(i % NK_T_GUARD),
+                  i < NK_T_GUARD ? "in front of" : "behind", e.name, e.n);
+    }
+    return NK_OK;
+  }
+};
+static int test_slab_ok(nk_ctx *ctx, int64_t ns, int64_t nl) {
+  NK_REQUIRE(ctx, "NULL argument");
+  NK_REQUIRE(nk_ctx_is_single(ctx), "test hook: one rank only");
+  NK_REQUIRE(ns >= 1 && ns < (1ll << 30) && nl >= 1 && nl < (1ll << 30) && ns * nl < (1ll << 31), "test hook: needs 1 <= ns, nl and ns*nl < 2^31");
+  NK_HIP(hipSetDevice(ctx->device));
+  return NK_OK;
+}
+}  // namespace
+
+// One Bratu JVP launch on a slab of nl lines of ns points: jv = [out_scale·] (c_lap·L v − d.*v) through row epilogue `mode` (0 … 3;
+// anything else must come back as an error with nothing launched). d, v, jv: ns·nl; lo, hi (nullable): ns; r, dnew, yacc: ns·nl,
+// uploaded and delivered back where given; out_scale (nullable): one double; skip: the device flag's value.
+extern "C" int nk_bratu_jvp_test(nk_ctx *ctx, int64_t ns, int64_t nl, double c_lap, const double *d, const double *v,
+                                 const double *lo, const double *hi, int mode, double *r, double *dnew, double *yacc, double c1,
+                                 double c2, double theta, const double *out_scale, int skip, double *jv) {
+  NK_TRY(test_slab_ok(ctx, ns, nl));
+  NK_REQUIRE(d && v && jv, "NULL argument");
+  NK_REQUIRE(!(mode == NK_EPI_CHEB_STEP || mode == NK_EPI_RESIDUAL) || r != nullptr, "this mode reads r");
+  NK_REQUIRE(mode != NK_EPI_CHEB_STEP || (dnew && yacc), "mode 1 writes dnew and yacc");
+  const size_t n = (size_t)(ns * nl);
+  test_bufs B(ctx);
+  double *d_d, *d_v, *d_lo, *d_hi, *d_r, *d_dnew, *d_yacc, *d_jv, *d_sc;
+  NK_TRY(B.make("d", d, n, &d_d));
+  NK_TRY(B.make("v", v, n, &d_v));
+  NK_TRY(B.opt("lo", lo, (size_t)ns, &d_lo));
+  NK_TRY(B.opt("hi", hi, (size_t)ns, &d_hi));
+  NK_TRY(B.opt("r", r, n, &d_r));
+  NK_TRY(B.opt("dnew", dnew, n, &d_dnew));
+  NK_TRY(B.opt("yacc", yacc, n, &d_yacc));
+  NK_TRY(B.make("jv", nullptr, n, &d_jv));
+  double sc[3] = {theta, out_scale ? *out_scale : 1.0, 0.0};   // the third word carries the skip flag (an int)
+  memcpy(&sc[2], &skip, sizeof(int));
+  NK_TRY(B.make("scalars", sc, 3, &d_sc));
+  nk_spmv_epi ep{};
+  ep.mode = mode; ep.c1 = c1; ep.c2 = c2;
+  ep.r = d_r; ep.dnew = d_dnew; ep.yacc = d_yacc;
+  ep.theta = d_sc;
+  const int st = launch_bratu_jvp(ctx, ns, nl, c_lap, d_d, d_v, d_lo, d_hi, d_jv, (const int *)(d_sc + 2),
+                                  out_scale ? d_sc + 1 : nullptr, ep);
+  if (st == NK_OK) NK_HIP(hipGetLastError());
+  NK_HIP(hipStreamSynchronize(ctx->stream));
+  NK_TRY(B.fetch(jv, d_jv, n));
+  NK_TRY(B.fetch(r, d_r, n));
+  NK_TRY(B.fetch(dnew, d_dnew, n));
+  NK_TRY(B.fetch(yacc, d_yacc, n));
+  if (st != NK_OK) return st;
+  return B.check_guards();
+}
+
+// The Bratu residual on a slab. fused = 0: k_bratu_residual into f. fused = 1: k_bratu_residual_norms into f, f_copy (ns·nl each),
+// partials (2·1024: the launch's 2·*grid_out results, canary behind them), ss_copy (1024) and gpart (2·1024; stays canary unless the
+// slab is the whole grid) — and into partials_ref (2·1024) what k_absmax_sumsq, through nk_blas_norms_inf2, leaves for that f.
+extern "C" int nk_bratu_residual_test(nk_ctx *ctx, int64_t ns, int64_t nl, double lambda, double scale, const double *u,
+                                      const double *lo, const double *hi, int fused, double *f, double *f_copy, double *partials,
+                                      double *ss_copy, double *gpart, double *partials_ref, int *grid_out) {
+  NK_TRY(test_slab_ok(ctx, ns, nl));
+  NK_REQUIRE(u && f, "NULL argument");
+  NK_REQUIRE(!fused || (f_copy && partials && ss_copy && gpart && partials_ref && grid_out), "NULL argument (fused form)");
+  const size_t n = (size_t)(ns * nl), nb = (size_t)NK_MAX_RED_BLOCKS;
+  double c_lap, c_exp;
+  bratu_coefficients(ns, lambda, scale, &c_lap, &c_exp);
+  test_bufs B(ctx);
+  double *d_u, *d_lo, *d_hi, *d_f;
+  NK_TRY(B.make("u", u, n, &d_u));
+  NK_TRY(B.opt("lo", lo, (size_t)ns, &d_lo));
+  NK_TRY(B.opt("hi", hi, (size_t)ns, &d_hi));
+  NK_TRY(B.make("f", nullptr, n, &d_f));
+  if (!fused) {
+    NK_TRY(launch_bratu_residual(ctx, ns, nl, c_lap, c_exp, d_u, d_lo, d_hi, d_f));
+    NK_HIP(hipGetLastError());
+    NK_HIP(hipStreamSynchronize(ctx->stream));
+    NK_TRY(B.fetch(f, d_f, n));
+    return B.check_guards();
+  }
+  double *d_fc, *d_part, *d_ss, *d_g, *d_out;
+  NK_TRY(B.make("f_copy", nullptr, n, &d_fc));
+  NK_TRY(B.make("partials", nullptr, 2 * nb, &d_part));
+  NK_TRY(B.make("ss_copy", nullptr, nb, &d_ss));
+  NK_TRY(B.make("gpart", nullptr, 2 * nb, &d_g));
+  NK_TRY(B.make("norms", nullptr, 3, &d_out));
+  int grid = 0;
+  NK_TRY(launch_bratu_residual_norms(ctx, ns, nl, c_lap, c_exp, d_u, d_lo, d_hi, d_f, d_part, d_fc, d_ss, d_g, &grid));
+  NK_HIP(hipGetLastError());
+  NK_TRY(nk_blas_norms_inf2(ctx, (int64_t)n, d_f, d_out, nullptr, 0, 0));   // stage 1 of the two-launch form → ctx->d_partials
+  NK_HIP(hipStreamSynchronize(ctx->stream));
+  *grid_out = grid;
+  NK_TRY(B.fetch(f, d_f, n));
+  NK_TRY(B.fetch(f_copy, d_fc, n));
+  NK_TRY(B.fetch(partials, d_part, 2 * nb));
+  NK_TRY(B.fetch(ss_copy, d_ss, nb));
+  NK_TRY(B.fetch(gpart, d_g, 2 * nb));
+  NK_TRY(B.fetch(partials_ref, ctx->d_partials, 2 * (size_t)grid));
+  return B.check_guards();
+}
+
+// The linearisation data of a whole-grid Bratu problem at u (n_local doubles): diag = d_diag after nk_problem_jvp_prepare, and
+// interval2 = the two doubles of nk_problem_spectrum_interval_dev.
+extern "C" int nk_bratu_linearisation_test(nk_problem *P, const double *u, double *diag, double *interval2) {
+  NK_REQUIRE(P && u && diag && interval2, "NULL argument");
+  NK_REQUIRE(P->kind == NK_PROBLEM_BRATU2D && P->n_local == P->n_global && P->n_local > 0, "test hook: a whole-grid Bratu problem");
+  nk_ctx *ctx = P->ctx;
+  NK_HIP(hipSetDevice(ctx->device));
+  const size_t n = (size_t)P->n_local;
+  test_bufs B(ctx);
+  double *d_u, *d_iv;
+  NK_TRY(B.make("u", u, n, &d_u));
+  NK_TRY(B.make("interval", nullptr, 2, &d_iv));
+  NK_TRY(nk_problem_jvp_prepare(P, d_u));
+  const int st = nk_problem_spectrum_interval_dev(P, d_u, d_iv);
+  hipStreamSynchronize(ctx->stream);
+  nk_problem_invalidate(P);   // d_u is about to be freed: the problem must not believe it is still linearised there
+  NK_TRY(st);
+  NK_TRY(B.fetch(diag, P->d_diag, n));
+  NK_TRY(B.fetch(interval2, d_iv, 2));
+  return B.check_guards();
+}
+
+// The Brusselator on a slab of nl lines of N points whose first line is global line j0. op 0: F(U) (lo, hi: ghost lines of U);
+// op 1: J(U)·V, op 2: J(U)ᵀ·V (lo, hi: ghost lines of V). U, V, out: 2·N·nl; lo, hi (nullable; without them the slab wraps onto
+// itself): 2·N, [species 0 | species 1]; out_scale (nullable) and skip as in nk_bratu_jvp_test (the residual has neither).
+extern "C" int nk_brus_test(nk_ctx *ctx, int64_t N, int64_t nl, int64_t j0, double A, double Bp, double alpha, double dx,
+                            const double *U, const double *V, const double *lo, const double *hi, int op, const double *out_scale,
+                            int skip, double *out) {
+  NK_TRY(test_slab_ok(ctx, N, nl));
+  NK_REQUIRE(N >= 3 && j0 >= 0 && j0 + nl <= N, "test hook: needs N >= 3 and 0 <= j0, j0 + nl <= N");
+  NK_REQUIRE(U && out && op >= 0 && op <= 2 && (op == 0 || V), "NULL argument / op must be 0, 1 or 2");
+  NK_REQUIRE(op != 0 || (!out_scale && !skip), "the residual has neither an output scale nor a skip flag");
+  const size_t n = (size_t)(2 * N * nl);
+  const brus_par q = brus_slab(N, nl, j0, A, Bp, alpha, dx);
+  test_bufs B(ctx);
+  double *d_U, *d_V, *d_lo, *d_hi, *d_out, *d_sc;
+  NK_TRY(B.make("U", U, n, &d_U));
+  NK_TRY(B.opt("V", V, n, &d_V));
+  NK_TRY(B.opt("lo", lo, (size_t)(2 * N), &d_lo));
+  NK_TRY(B.opt("hi", hi, (size_t)(2 * N), &d_hi));
+  NK_TRY(B.make("out", nullptr, n, &d_out));
+  double sc[2] = {out_scale ? *out_scale : 1.0, 0.0};
+  memcpy(&sc[1], &skip, sizeof(int));
+  NK_TRY(B.make("scalars", sc, 2, &d_sc));
+  if (op == 0) NK_TRY(launch_brus_residual(ctx, q, d_U, d_lo, d_hi, d_out));
+  else NK_TRY(launch_brus_jvp(ctx, q, op == 2, d_U, d_V, d_lo, d_hi, d_out, (const int *)(d_sc + 1), out_scale ? d_sc : nullptr));
+  NK_HIP(hipGetLastError());
+  NK_HIP(hipStreamSynchronize(ctx->stream));
+  NK_TRY(B.fetch(out, d_out, n));
+  return B.check_guards();
 }
