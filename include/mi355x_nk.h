@@ -754,7 +754,8 @@ int nk_problem_get_graph_data(nk_problem *P, int on_edges, int k, double *out, i
  * and the compiler's log in nk_last_error. Write loops over a with compile-time bounds (`#pragma unroll`, a < NK_NPE): an f[]
  * or a local array indexed by a run-time value may be placed in scratch memory, which costs bandwidth, not correctness.
  *
- * The mesh: conn[ne·npe], int32, row-major — the nodes of element e are conn[e·npe + a]; all elements have one npe; nn nodes.
+ * The mesh: conn[ne·npe], int32, row-major — the nodes of element e are conn[e·npe + a]; all elements have one npe; nn nodes
+ * (several element types, boundary terms and point terms in one mesh: "Several element blocks" below).
  * Limits: ne >= 1, npe = 2..8, dof = 1..4, npe·dof <= 16, nnode and nelem = 0..4 data arrays per node and per element,
  * nparams = 0..32; ne·(npe·dof)² and the pattern's entry count both fit in int32. Refused on the host (NK_E_INVALID) before
  * anything is compiled or allocated, the first offending element named: a node index outside 0 .. nn − 1, a node twice in one
@@ -802,6 +803,55 @@ int nk_problem_set_elem_data(nk_problem *P, int on_elements, int k, const double
 int nk_problem_get_elem_data(nk_problem *P, int on_elements, int k, double *out, int memspace);
 int nk_problem_set_elem_fixed(nk_problem *P, const int32_t *mask, const double *values, int memspace);
 int nk_problem_get_elem_fixed(nk_problem *P, int32_t *mask, double *values, int memspace);
+
+/* Several element blocks in one mesh. One element problem made of nblocks = 1..8 BLOCKS: every block has its own connectivity
+ * conn[k] (ne[k]·npe[k], row-major), its own npe[k], its own source sources[k] (its own nk_element) and its own nelem[k] = 0..4
+ * element data; all blocks share nn, dof, p, the node data, the fixed-unknown mask, the pattern and the output vectors. This is
+ * how a boundary term (Neumann, Robin, radiation: bars on the boundary edges of a triangulation, faces of a tet mesh), a mixed
+ * mesh (triangles beside quads, tets beside hexes), a truss on top of a continuum and point terms are written: in the
+ * reference, several loops inside `f`. A row of F, a row of J·v and an entry of J are the sums of the contributions of all
+ * blocks in one fixed order — block 0's elements ascending, then block 1's, and so on, starting from 0 — without atomics:
+ * bit-reproducible.
+ *
+ * The source of block k sees the contract above with NK_NPE and NK_NELEM of its own block, s = {e, ne, nn} with e and ne
+ * counting within the block, u.w(k) its block's own element data, and the macro NK_BLOCK = k (0 in a plain problem). A source
+ * that does not compile names its block ("element block 2 residual source does not compile") in front of the contract and the
+ * log.
+ *
+ * Limits: per block ne >= 1, npe = 1..8 and npe·dof <= 16; npe = 1 is a point element (a nodal spring, a point load, a lumped
+ * term) and adds no node pairs. dof²·Σ npe_k²·ne_k and the pattern's entry count fit in int32. Every refusal comes on the host
+ * before anything is compiled or allocated and names the block and the first offending element: "block 2, element 17: node 301
+ * (local node 1) outside 0..299". A context of more than one rank gets NK_E_UNSUPPORTED.
+ *
+ * The pattern: two nodes are adjacent when they share an element of any block; the CSR is nk_graph_pattern of that union graph.
+ * A pair that only a bar block creates is a structural entry like any other. nk_elem_blocks_adjacency and
+ * nk_elem_blocks_pattern are nk_elem_adjacency and nk_elem_pattern of the union (NULL arrays: the sizes only; host only).
+ *
+ * One block with npe >= 2 is nk_problem_create_elements: the same programs, buffers and launches. On any element problem
+ * nk_problem_set_elem_data / nk_problem_get_elem_data with on_elements = 1 mean block 0 (0: the node data);
+ * nk_problem_set_elem_block_data / nk_problem_get_elem_block_data address datum k of block `block` (ne[block] doubles) and
+ * work on a one-block problem with block = 0. nk_problem_elem_blocks returns the block count and, for the first `cap` blocks,
+ * ne, npe and nelem (any array may be NULL).
+ *
+ * Kernels. With TB = Σ npe_k·ne_k and TM = Σ npe_k²·ne_k, base_k and mbase_k the same sums over the blocks before k: number
+ * (a, c) of element e of block k lives at c·TB + base_k + a·ne_k + e of the element-vector buffer and dF_(a,c)/du_(b,c2) at
+ * (c·dof + c2)·TM + mbase_k + (a·npe_k + b)·ne_k + e of the element-matrix buffer — the component offset does not depend on
+ * the block, every store is still one coalesced stream per register. A callback is one generated launch per block (compiled
+ * with -DNK_ELEM_BLOCKS=1: the block's base and the total stride as two further arguments), on the stream it is given and in
+ * the callback's profile family, and then ONE k_elem_gather launch (family elem_gather) over lists that walk the blocks in
+ * order. nk_elem_block_code_object is nk_elem_code_object for the block form of block `block` = 0..7 (npe = 1 allowed). */
+int nk_elem_blocks_adjacency(int64_t nn, int nblocks, const int64_t *ne, const int *npe, const int32_t *const *conn,
+                             int32_t *rowptr, int32_t *colind, int64_t *nedges);
+int nk_elem_blocks_pattern(int64_t nn, int nblocks, const int64_t *ne, const int *npe, const int32_t *const *conn, int dof,
+                           int32_t *jrowptr, int32_t *jcolind, int64_t *nnz);
+int nk_elem_block_code_object(const char *source, int block, int npe, int dof, int nparams, int nnode, int nelem, int jac,
+                              void *buf, int64_t capacity, int64_t *bytes);
+int nk_problem_create_element_blocks(nk_ctx *ctx, int64_t nn, int dof, int nblocks, const char *const *sources, const int64_t *ne,
+                                     const int *npe, const int32_t *const *conn, const int *nelem, const double *params,
+                                     int nparams, int nnode, nk_problem **out);
+int nk_problem_set_elem_block_data(nk_problem *P, int block, int k, const double *data, int memspace);
+int nk_problem_get_elem_block_data(nk_problem *P, int block, int k, double *out, int memspace);
+int nk_problem_elem_blocks(nk_problem *P, int *nblocks, int cap, int64_t *ne, int *npe, int *nelem);
 
 /* ---------------------------------------------------------------- GMRES (seam 1) */
 /* restart_m: the restart length m, 1 <= m <= 63 (the dot-product kernels take at most 64 columns at once); restart_m <= 0 means 30;

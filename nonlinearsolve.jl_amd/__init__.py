@@ -9,7 +9,7 @@ from .core import (  # noqa: F401
     Context, default_context, set_default_context, partition_range, comm_unique_id,
     CSRMatrix, DeviceProblem, Quadratic, Bratu2D, Brusselator2D, CompiledGridProblem, grid_pattern, grid_mg_axis, grid_slab_pattern, grid_compile_check,
     CompiledGraphProblem, graph_pattern, graph_compile_check,
-    CompiledElementProblem, elem_adjacency, elem_pattern, elem_compile_check,
+    CompiledElementProblem, ElementBlock, elem_adjacency, elem_pattern, elem_compile_check,
     NonlinearFunction, NonlinearProblem,
     KrylovJL_GMRES, ChebyshevPrecs, MultigridPrecs, ObjectPrecs, LinearSolveParameters, Preconditioner, JacobiPreconditioner,
     ILU0Preconditioner, ILUTPreconditioner, AMGPreconditioner, IDENTITY, EisenstatWalkerForcing2, RadiusUpdateSchemes, BackTracking, LineSearchesJL, NewtonRaphson, TrustRegion, GaussNewton, LevenbergMarquardt, PseudoTransient, LimitedMemoryBroyden, DFSane, Broyden, Klement,

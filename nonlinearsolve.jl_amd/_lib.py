@@ -226,6 +226,13 @@ SIGNATURES = {
     "nk_problem_get_elem_data": (_I, [_P, _I, _I, _P, _I]),
     "nk_problem_set_elem_fixed": (_I, [_P, _P, _P, _I]),
     "nk_problem_get_elem_fixed": (_I, [_P, _P, _P, _I]),
+    "nk_elem_blocks_adjacency": (_I, [_L, _I, _P, _P, _P, _P, _P, C.POINTER(_L)]),
+    "nk_elem_blocks_pattern": (_I, [_L, _I, _P, _P, _P, _I, _P, _P, C.POINTER(_L)]),
+    "nk_elem_block_code_object": (_I, [C.c_char_p, _I, _I, _I, _I, _I, _I, _I, _P, _L, C.POINTER(_L)]),
+    "nk_problem_create_element_blocks": (_I, [_P, _L, _I, _I, _P, _P, _P, _P, _P, C.POINTER(_D), _I, _I, _PP]),
+    "nk_problem_set_elem_block_data": (_I, [_P, _I, _I, _P, _I]),
+    "nk_problem_get_elem_block_data": (_I, [_P, _I, _I, _P, _I]),
+    "nk_problem_elem_blocks": (_I, [_P, _P, _I, _P, _P, _P]),
     "nk_gmres_create": (_I, [_P, _L, _I, _I, _PP]),
     "nk_gmres_destroy": (_I, [_P]),
     "nk_gmres_set_operator_csr": (_I, [_P, _P]),

@@ -17,7 +17,7 @@ from __future__ import annotations
 
 import ctypes as C
 from dataclasses import dataclass, field
-from typing import Callable, Optional, Sequence
+from typing import Any, Callable, Optional, Sequence
 
 import numpy as np
 
@@ -884,17 +884,45 @@ def _elem_arrays(conn, nn):
     return cn, int(nn), int(cn.shape[0]), int(cn.shape[1])
 
 
-def elem_adjacency(conn, nn: int):
+@dataclass
+class ElementBlock:
+    """a further element block of a CompiledElementProblem: its own source (its own nk_element), its own connectivity
+    conn[ne, npe] (npe = 1..8; 1 is a point element) and its own count of element data arrays"""
+    source: str
+    conn: Any
+    elem_data: int = 0
+
+
+def _elem_block_arrays(conns, nn):
+    """the parallel arrays of the block entry points for the connectivities `conns`: (arguments nn, nblocks, ne, npe, conn;
+    what keeps them alive)"""
+    cns = [_elem_arrays(c, nn)[0] for c in conns]
+    k = len(cns)
+    ne = (C.c_int64 * k)(*[c.shape[0] for c in cns])
+    npe = (C.c_int * k)(*[c.shape[1] for c in cns])
+    ptrs = (C.c_void_p * k)(*[c.ctypes.data for c in cns])
+    return (int(nn), k, ne, npe, ptrs), cns
+
+
+def elem_adjacency(conn, nn: int, blocks=None):
     """(rowptr, colind), int32: the node graph of the mesh conn[ne, npe] over nn nodes — two nodes are adjacent when they share
     an element; ascending columns, no self-loops. Host only. A mesh that breaks a rule of CompiledElementProblem raises NKError
-    naming the first offending element."""
+    naming the first offending element. blocks=[conn_b, …]: the further connectivities of a mesh of several element blocks
+    (the union graph; the message names the block too)."""
+    if blocks is not None:
+        args, _keep = _elem_block_arrays([conn, *blocks], nn)
+        return _sized_call(L.lib().nk_elem_blocks_adjacency, args, lambda nedges: (args[0] + 1, nedges))
     cn, nn, ne, npe = _elem_arrays(conn, nn)
     return _sized_call(L.lib().nk_elem_adjacency, (nn, ne, npe, C.c_void_p(cn.ctypes.data)), lambda nedges: (nn + 1, nedges))
 
 
-def elem_pattern(conn, nn: int, dof: int = 1):
+def elem_pattern(conn, nn: int, dof: int = 1, blocks=None):
     """(jrowptr, jcolind), int32, of the Jacobian of a compiled element problem on the mesh conn[ne, npe] over nn nodes:
-    graph_pattern of elem_adjacency(conn, nn). Host only."""
+    graph_pattern of elem_adjacency(conn, nn). Host only. blocks=[conn_b, …]: the further connectivities of a mesh of several
+    element blocks."""
+    if blocks is not None:
+        args, _keep = _elem_block_arrays([conn, *blocks], nn)
+        return _sized_call(L.lib().nk_elem_blocks_pattern, (*args, int(dof)), lambda nnz: (dof * args[0] + 1, nnz))
     cn, nn, ne, npe = _elem_arrays(conn, nn)
     return _sized_call(L.lib().nk_elem_pattern, (nn, ne, npe, C.c_void_p(cn.ctypes.data), int(dof)),
                        lambda nnz: (dof * nn + 1, nnz))
@@ -927,14 +955,25 @@ class _ElemDeviceProblem(_CompiledDeviceProblem):
         """a copy of node datum k as a device tensor"""
         return self._get_data(0, k)
 
-    def set_elem_data(self, k: int, x):
-        """Replace element datum k (0 .. elem_data − 1) by x: a device tensor or a NumPy array of one float64 per element. The
-        data is copied; a Jacobian cached for the same u is filled again."""
-        self._set_data(1, k, x)
+    def _block_ne(self, block):
+        """the element count of a block; a block the problem does not have is the library's error"""
+        return self.blocks[block][0] if 0 <= block < len(self.blocks) else 0
 
-    def elem_data(self, k: int):
-        """a copy of element datum k as a device tensor"""
-        return self._get_data(1, k)
+    def set_elem_data(self, k: int, x, block: int = 0):
+        """Replace element datum k (0 .. elem_data − 1) of block `block` by x: a device tensor or a NumPy array of one float64
+        per element of that block. The data is copied; a Jacobian cached for the same u is filled again."""
+        if block == 0:
+            return self._set_data(1, k, x)
+        n = self._block_ne(int(block))
+        size = x.numel() if _is_torch(x) else np.size(x)
+        self._set_datum(L.lib().nk_problem_set_elem_block_data, (int(block), int(k)), x, n if n else size,
+                        f"element datum {k} of block {block}: expected {n} elements (one per element)")
+
+    def elem_data(self, k: int, block: int = 0):
+        """a copy of element datum k of block `block` as a device tensor"""
+        if block == 0:
+            return self._get_data(1, k)
+        return self._get_datum(L.lib().nk_problem_get_elem_block_data, (int(block), int(k)), self._block_ne(int(block)))
 
     def set_fixed(self, mask, values=None):
         """Fix the unknowns with mask != 0 (dof·nn entries, component-major) at `values` (dof·nn float64; None: zeros): their
@@ -960,7 +999,7 @@ class _ElemDeviceProblem(_CompiledDeviceProblem):
 
 
 def CompiledElementProblem(source: str, conn, nn: int, dof: int = 1, params: Sequence[float] = (), ctx=None, *, node_data: int = 0,
-                           elem_data: int = 0) -> DeviceProblem:
+                           elem_data: int = 0, blocks: Sequence[ElementBlock] = ()) -> DeviceProblem:
     """A finite-element / finite-volume residual given element by element on any mesh, as HIP source
         template <typename T> __device__ void nk_element(const nk_elemv<T> &u, const nk_real *p, nk_cell s, T *f);
     compiled (hiprtc, gfx950) into the element-residual kernel, the exact dual-number JVP kernel and the element-matrix kernel;
@@ -991,15 +1030,47 @@ def CompiledElementProblem(source: str, conn, nn: int, dof: int = 1, params: Seq
         #pragma unroll
           for (int a = 0; a < 3; ++a) f[a] = area * (gx * bx[a] + gy * by[a]) - (p[0] * area / 3.0) * exp(u.at(a));
         }'''
-        P = CompiledElementProblem(SRC, conn, nn, params=[1.0], node_data=2); P.set_fixed(boundary_mask)"""
+        P = CompiledElementProblem(SRC, conn, nn, params=[1.0], node_data=2); P.set_fixed(boundary_mask)
+    Several element blocks in one mesh: blocks=[ElementBlock(source, conn, elem_data=0), …] adds up to 7 further blocks, each
+    with its own source, connectivity (npe = 1..8; 1 is a point element) and element data; the positional source, conn and
+    elem_data are block 0, and nn, dof, params, the node data, the fixed unknowns and the pattern (the union of all blocks'
+    node pairs) are shared. This is how boundary terms, mixed meshes (triangles beside quads), a truss on a continuum and
+    nodal springs are written. A row sums block 0's elements ascending, then block 1's, …: no atomics, the same bits every
+    run. The source of block k sees NK_NPE and NK_NELEM of its block, s.e and s.ne counting within it, u.w(k) its own data
+    and NK_BLOCK = k; errors name the block. P.set_elem_data(k, x, block=0) and P.elem_data(k, block=0) address a block;
+    P.blocks lists every block's (ne, npe, elem_data); P.ne and P.npe stay block 0's. A Robin (radiation) condition
+    −∂u/∂n = p[1]·(u⁴ − w⁴) on the boundary edges of the Bratu triangulation above, the ambient value w an element datum of
+    the bars (consistent 2 × 2 weights (2, 1; 1, 2)/6):
+        ROBIN = '''template <typename T>
+        __device__ void nk_element(const nk_elemv<T> &u, const nk_real *p, nk_cell s, T *f) {
+          const nk_real dx = u.x(1, 0) - u.x(0, 0), dy = u.x(1, 1) - u.x(0, 1), len = sqrt(dx * dx + dy * dy);
+          const nk_real w4 = u.w(0) * u.w(0) * u.w(0) * u.w(0);
+          const T q0 = u.at(0) * u.at(0) * u.at(0) * u.at(0) - w4, q1 = u.at(1) * u.at(1) * u.at(1) * u.at(1) - w4;
+          f[0] = (p[1] * len / 6.0) * (2.0 * q0 + q1);
+          f[1] = (p[1] * len / 6.0) * (q0 + 2.0 * q1);
+        }'''
+        P = CompiledElementProblem(SRC, conn, nn, params=[1.0, 0.5], node_data=2,
+                                   blocks=[ElementBlock(ROBIN, boundary_edges, elem_data=1)])
+        P.set_elem_data(0, ambient, block=1)"""
     ctx = ctx or default_context()
     cn, nn, ne, npe = _elem_arrays(conn, nn)
     params, arr = _params_array(params)
     h = C.c_void_p()
-    check(L.lib().nk_problem_create_elements(ctx._h, source.encode(), nn, ne, npe, C.c_void_p(cn.ctypes.data), int(dof), arr,
-                                             len(params), int(node_data), int(elem_data), C.byref(h)))
+    if not blocks:
+        check(L.lib().nk_problem_create_elements(ctx._h, source.encode(), nn, ne, npe, C.c_void_p(cn.ctypes.data), int(dof), arr,
+                                                 len(params), int(node_data), int(elem_data), C.byref(h)))
+        shapes = [(ne, npe, int(elem_data))]
+    else:
+        blocks = list(blocks)
+        (_nn, k, nes, npes, ptrs), cns = _elem_block_arrays([cn] + [b.conn for b in blocks], nn)
+        srcs = (C.c_char_p * k)(source.encode(), *[b.source.encode() for b in blocks])
+        nel = (C.c_int * k)(int(elem_data), *[int(b.elem_data) for b in blocks])
+        check(L.lib().nk_problem_create_element_blocks(ctx._h, nn, int(dof), k, srcs, nes, npes, ptrs, nel, arr, len(params),
+                                                       int(node_data), C.byref(h)))
+        shapes = [(int(c.shape[0]), int(c.shape[1]), int(m)) for c, m in zip(cns, nel)]
     P = _ElemDeviceProblem(h, ctx)
     P.p, P.nn, P.ne, P.npe, P.dof, P.n_node_data, P.n_elem_data = params, nn, ne, npe, int(dof), int(node_data), int(elem_data)
+    P.blocks = shapes
     return P
 
 

@@ -5,7 +5,7 @@
 // tables, its contract, its validation and the argument list of its kernels.
 #include "nk_internal.h"
 
-int nk_compiled_load(nk_compiled *C, const std::vector<char> &code_f, const std::vector<char> &code_j, const char *name_res,
+int nk_compiled_load(nk_compiled_programs *C, const std::vector<char> &code_f, const std::vector<char> &code_j, const char *name_res,
                      const char *name_jvp, const char *name_jac, const char *what) {
   if (hipModuleLoadData(&C->mod_f, code_f.data()) != hipSuccess || hipModuleLoadData(&C->mod_jac, code_j.data()) != hipSuccess)
     NK_FAIL(NK_E_HIP, "hipModuleLoadData failed");
@@ -37,9 +37,14 @@ int nk_compiled_launch(nk_compiled *C, hipFunction_t fn, int64_t items, void **a
   return e != hipSuccess;
 }
 
-void nk_compiled_free(nk_compiled *C) {
+void nk_compiled_unload(nk_compiled_programs *C) {
   if (C->mod_f) hipModuleUnload(C->mod_f);
   if (C->mod_jac) hipModuleUnload(C->mod_jac);
+  C->mod_f = C->mod_jac = nullptr;
+}
+
+void nk_compiled_free(nk_compiled *C) {
+  nk_compiled_unload(C);
   hipFree(C->d_params);
   nk_csr_destroy(C->pattern);
 }

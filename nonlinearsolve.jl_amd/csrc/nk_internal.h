@@ -1020,17 +1020,21 @@ static inline int nk_upload(const nk_ctx *ctx, T **dst, const std::vector<T> &sr
 // ----------------------------------------------------------------------------- compiled problems (nk_compiled.hip)
 // What every compiled problem kind (nk_grid.hip, nk_graph.hip, nk_elem.hip) owns and does alike. A kind writes its device types
 // and kernels, its host tables, its contract and its validation; its state holds one nk_compiled as a member.
-struct nk_compiled {
-  nk_ctx *ctx = nullptr;
+// the programs alone: what a further element block (nk_elem.hip) adds to a problem whose p, pattern and context stay single
+struct nk_compiled_programs {
   hipModule_t mod_f = nullptr, mod_jac = nullptr;   // the residual + JVP program; the fill's
   hipFunction_t fn_res = nullptr, fn_jvp = nullptr, fn_jac = nullptr;
+};
+struct nk_compiled : nk_compiled_programs {
+  nk_ctx *ctx = nullptr;
   double *d_params = nullptr;   // np doubles (at least one allocated): the source's p
   int np = 0;
   nk_csr *pattern = nullptr;    // the problem's user_pattern
 };
 // the two code objects loaded and the three kernels looked up; `what` words the message of a missing kernel ("grid", …)
-int nk_compiled_load(nk_compiled *C, const std::vector<char> &code_f, const std::vector<char> &code_j, const char *name_res,
+int nk_compiled_load(nk_compiled_programs *C, const std::vector<char> &code_f, const std::vector<char> &code_j, const char *name_res,
                      const char *name_jvp, const char *name_jac, const char *what);
+void nk_compiled_unload(nk_compiled_programs *C);   // the two modules
 // d_params of max(nparams, 1) doubles; params (NULL: the caller fills the buffer on the device) copied in
 int nk_compiled_params_init(nk_compiled *C, const double *params, int nparams);
 // one launch of a generated kernel over `items` threads in blocks of 256 on `stream`; nonzero on failure (a callback's return)
