@@ -451,6 +451,10 @@ int nk_spmv_t(nk_csr *A, const double *x, double *y, int memspace);
  * (i, j, species) ordering of a two-species system, docs/src/tutorials/large_systems.md) and / or whose bands close to a ring
  * (periodic boundaries); any other matrix takes s streaming SpMV launches. The columns are bit-identical either way.
  * NK_SPMV_POWERS=0 disables the resident kernel.
+ * Device memory: a matrix that takes the plain band form keeps, for as long as it lives, a packed table of its pattern beside
+ * rowptr / col (built once with the plan, never when values change; csrc/nk_pw_pack.h): 12 / 20 / 36 bytes per row of every band
+ * at ≤ 5 / 8 / 16 entries per row — 12.6 MB for the 1024² Bratu Jacobian. A pattern the table's 16-bit fields cannot hold is
+ * not eligible and keeps the streaming launches.
  * Several ranks: whether the resident kernel applies is decided ONCE per matrix by all ranks together — the first nk_csr_powers
  * or s-step linear solve on a row-partitioned matrix is COLLECTIVE (two small all-reduces through the communicator); every rank
  * must reach it, also a rank whose share would not qualify. */

@@ -4,8 +4,11 @@
 // Why: the streaming SpMV (nk_csr.hip) reads the whole matrix for every application — 15 × 74 MB per block at 1024², 2.2 GB of
 // the 3.9 GB a fixed-work Newton step moves. An MI355X has 256 CUs × 512 KB of vector registers = 128 MB; a matrix of up to
 // ≈ 8 M non-zeros fits there. So: one 1024-thread workgroup per CU owns a BAND of 1024·RPT consecutive rows and loads its
-// slice of val / col into registers ONCE per launch (thread t holds rows t, t + 1024, … of its band, ≤ W entries each, in CSR
-// order). The band's slice of the current vector lives in LDS ([halo above | own rows | halo below], two buffers); a power is
+// slice of the matrix into registers ONCE per launch (thread t holds rows t, t + 1024, … of its band, ≤ W entries each, in CSR
+// order). Only the VALUES are read from the matrix: which LDS word each entry gathers, how long a row is and where it starts in
+// its slice of val never change while the matrix object lives, so they come from a packed table the plan builds once per
+// pattern on the host (nk_pw_pack.h: 12 bytes per row at W = 5 — 12.6 MB at 1024² against the 25 MB of rowptr + col every launch
+// used to re-read and re-derive; profiles/r08_powers_packed_load.md). k_spmv_powers_seg still derives them per launch. The band's slice of the current vector lives in LDS ([halo above | own rows | halo below], two buffers); a power is
 // RPT·W LDS gathers and multiply-adds per thread, one 8-byte store per row into the basis column — and the only data that
 // crosses workgroups are the ≤ 1024 rows either neighbour band reads (a grid line of the 5-point stencil): the boundary rows
 // are stored write-through (`sc1`), a per-band flag word is released behind them, the neighbour polls it and reads the rows
@@ -27,23 +30,25 @@
 // redundantly. Half the hand-off chains, but the two extra slices per round cost what the saved chain cost: 68.6 – 70.0 µs per
 // 15-power launch against 59.4 (4 slices per band), 50.4 against 49.3 (2 slices per band).
 // Eligibility (host, once per pattern — nk_csr_powers_plan): one rank, no halo; rows ≤ #CUs × 1024 × RPT_max; every row ≤ W
-// entries; every column of band b inside [first row of b − 1024, last row of b + 1024]. Everything else keeps the streaming
-// kernel. All workgroups must be resident at once (grid ≤ #CUs, one per CU by its LDS footprint); every wait is bounded by a
+// entries; every column of band b inside [first row of b − 1024, last row of b + 1024]; the pattern fits the operand table's
+// 16-bit fields (pw_pack says no otherwise). Everything else keeps the streaming kernel. The table costs device memory for the
+// life of the plan: 4·⌈(W + 2)/2⌉ bytes per row of every band (12 / 20 / 36 at W = 5 / 8 / 16) + 8 bytes per slice. All workgroups must be resident at once (grid ≤ #CUs, one per CU by its LDS footprint); every wait is bounded by a
 // wall-clock time-out that raises the plan's error word (host-visible), after which the object falls back for good.
 #include <algorithm>
 #include <stdlib.h>
 #include <vector>
 
 #include "nk_internal.h"
+#include "nk_pw_pack.h"   // PW_T, PW_HALO, the operand table's record format and its packer
 
-constexpr int PW_T = 1024;          // threads per workgroup = rows per slice
-constexpr int PW_HALO = 1024;       // rows a band may read from either neighbour
 constexpr int PW_FLAG_STRIDE = 16;  // uint64 words between two bands' flags (128 B)
 constexpr int PW_NXCD = 8;
 
 struct pw_args {
   int nrows, nb, s, stall;   // stall (development hook): band 0 never publishes — its neighbour times out
-  const int32_t *rowptr, *col;
+  const int32_t *rowptr, *col;   // (k_spmv_powers_seg only: k_spmv_powers reads the plan's operand table instead)
+  const uint32_t *rec;           // the packed per-row records [band][slice][word][PW_T] (nk_pw_pack.h) …
+  const int32_t *ext;            // … and the slices' extents in val, {kb, ke} per (band, slice)
   const double *val;
   const double *x0;
   double *Y;
@@ -65,7 +70,6 @@ struct pw_args {
   // operator application, here once per power inside ONE launch)
   struct {
     int up, dn;                          // there is a rank above / below
-    const int32_t *halo_vl;              // halo slot → row relative to this rank's first row (negative: above)
     double *push_up, *push_dn;           // the neighbours' receive areas for my slices (4 buffers of PW_T), in MY address space
     uint64_t *flag_up, *flag_dn;         // the neighbours' flags for me
     const double *recv_up, *recv_dn;     // my receive areas (4 buffers of PW_T each)
@@ -169,11 +173,16 @@ __global__ __launch_bounds__(PW_T) void k_spmv_powers(const pw_args a) {
   double *xa = pw_x, *xb = pw_x + XN;
   // PEER: the first band's upper and the last band's lower neighbour are bands of other ranks
   const bool pup = PEER && b == 0 && a.pr.up != 0, pdn = PEER && b == a.nb - 1 && a.pr.dn != 0;
+  PW_STAMP(0, 10);   // the kernel starts (the load phase is the first power's start minus this)
 
-  // ---- the band's matrix slice → registers (once per launch). A slice's entries are contiguous in val / col: the workgroup
-  // streams them with lane-contiguous loads into LDS (the vector buffers are idle until the first power) and every thread then
-  // picks its row's ≤ W entries from there — a thread reading its own row straight from memory touches every 128-byte line of
-  // the slice W times over (measured: 17.7 → 12 µs for this phase at 1024²). val / col are padded by a tile: k + j stays in bounds.
+  // ---- the band's matrix slice → registers (once per launch). Where a row's entries lie and which LDS words they gather is the
+  // same in every launch: it comes packed from the plan's operand table (nk_pw_pack.h: 12 bytes per row at W = 5), not from
+  // rowptr / col. A slice's values are contiguous in val: the workgroup streams them with lane-contiguous loads into LDS (the
+  // vector buffers are idle until the first power) and every thread then picks its row's ≤ W entries from there — a thread reading
+  // its own row straight from memory touches every 128-byte line of the slice W times over (measured: 17.7 → 12 µs for this phase
+  // at 1024²). Nothing waits for anything it does not need: every slice's records, the start vector's rows and the first slice's
+  // values are requested before the first wait, slice i + 1's values are in flight while slice i is picked (two staging buffers),
+  // and the start vector's rows wait in registers until the last pick has freed the staging area.
   double v[RPT][W];
   int ci[RPT][W];
   int len[RPT];
@@ -205,56 +214,79 @@ __global__ __launch_bounds__(PW_T) void k_spmv_powers(const pw_args a) {
       }
       len[i] = r < a.nrows ? n : 0;
     }
-  } else if constexpr (W > 8) {
-    // wide rows (W = 16): the slice does not fit the LDS staging area — every thread reads its own row
+  } else {
+    using F = pw_rec<W>;
+    constexpr int NW = F::NW;
+    static_assert(F::OFF_MAX >= (uint32_t)XN - 1, "an LDS offset of the band's window fits its field");
+    const uint32_t *rp = a.rec + (size_t)b * RPT * NW * PW_T + t;
+    const int32_t *ex = a.ext + (size_t)b * RPT * 2;   // (uniform: scalar loads)
+    uint32_t rec[RPT][NW];
 #pragma unroll
-    for (int i = 0; i < RPT; ++i) {
-      const int r = r0 + t + PW_T * i;
-      const int rc = r < a.nrows ? r : a.nrows - 1;
-      const int k0 = a.rowptr[rc], k1 = a.rowptr[rc + 1];
-      len[i] = r < a.nrows ? k1 - k0 : 0;
+    for (int i = 0; i < RPT; ++i)
 #pragma unroll
-      for (int j = 0; j < W; ++j) {
-        v[i][j] = a.val[k0 + j];
-        int c = a.col[k0 + j];
-        if (PEER && (pup || pdn) && j < len[i] && c >= a.nrows) c = a.pr.halo_vl[c - a.nrows];
-        ci[i][j] = (j < len[i]) ? c - (r0 - PW_HALO) : PW_HALO + t + PW_T * i;
+      for (int k = 0; k < NW; ++k) rec[i][k] = rp[(size_t)(i * NW + k) * PW_T];
+    double x0r[RPT + 2];
+#pragma unroll
+    for (int k = 0; k < RPT + 2; ++k) {
+      const int g = r0 - PW_HALO + t + PW_T * k;
+      x0r[k] = (g >= 0 && g < a.nrows) ? a.x0[g] : 0.0;
+    }
+    if constexpr (W > 8) {
+      // wide rows (W = 16): the slice does not fit the LDS staging area — every thread reads its own row
+#pragma unroll
+      for (int i = 0; i < RPT; ++i) {
+        const int k0 = ex[2 * i] + F::start(rec[i]), n = F::len(rec[i]);
+#pragma unroll
+        for (int j = 0; j < W; ++j) v[i][j] = (j < n) ? a.val[k0 + j] : 0.0;
+      }
+    } else {
+      constexpr int NBUF = RPT > 1 ? 2 : 1;
+      double tv[W];
+      auto request = [&](int i) {   // slice i's values, lane-contiguous
+        const int kb = ex[2 * i], ke = ex[2 * i + 1];
+#pragma unroll
+        for (int j = 0; j < W; ++j) {
+          const int e = t + PW_T * j;
+          tv[j] = (kb + e < ke) ? a.val[kb + e] : 0.0;
+        }
+      };
+      request(0);
+#pragma unroll
+      for (int i = 0; i < RPT; ++i) {
+        double *sv = pw_x + (size_t)(i % NBUF) * PW_T * W;
+#pragma unroll
+        for (int j = 0; j < W; ++j) sv[t + PW_T * j] = tv[j];
+        if (i + 1 < RPT) request(i + 1);
+        // one barrier per slice: buffer i mod 2 is written again two slices on, behind the barrier every thread reaches only
+        // after its pick from it
+        __syncthreads();
+        const int k0 = F::start(rec[i]), n = F::len(rec[i]);
+#pragma unroll
+        for (int j = 0; j < W; ++j) {
+          const double vv = sv[(j < n) ? k0 + j : 0];
+          v[i][j] = (j < n) ? vv : 0.0;
+        }
       }
     }
-  } else {
-    double *sv = pw_x;                                             // PW_T·W values …
-    int *sc = reinterpret_cast<int *>(pw_x + (size_t)PW_T * W);    // … and as many column ids
 #pragma unroll
     for (int i = 0; i < RPT; ++i) {
-      const int rfirst = r0 + PW_T * i;
-      const int r = rfirst + t;
-      const int rc = r < a.nrows ? r : a.nrows - 1;
-      const int k0 = a.rowptr[rc], k1 = a.rowptr[rc + 1];
-      const int rl = rfirst < a.nrows ? (rfirst + PW_T <= a.nrows ? rfirst + PW_T : a.nrows) : rfirst;   // end row of the slice
-      const int kb = rfirst < a.nrows ? a.rowptr[rfirst] : 0, ke = rfirst < a.nrows ? a.rowptr[rl] : 0;
-      len[i] = r < a.nrows ? k1 - k0 : 0;
+      len[i] = F::len(rec[i]);
 #pragma unroll
-      for (int j = 0; j < W; ++j) {
-        const int e = t + PW_T * j;
-        if (kb + e < ke) { sv[e] = a.val[kb + e]; sc[e] = a.col[kb + e]; }
-      }
-      __syncthreads();
+      for (int j = 0; j < W; ++j) ci[i][j] = F::off(rec[i], j);
+    }
+    __syncthreads();   // the last pick is done: the staging area becomes the vector buffers
 #pragma unroll
-      for (int j = 0; j < W; ++j) {
-        const int e = (j < len[i]) ? k0 - kb + j : 0;
-        const double vv = sv[e];
-        int c = sc[e];
-        if (PEER && (pup || pdn) && j < len[i] && c >= a.nrows) c = a.pr.halo_vl[c - a.nrows];   // a halo slot → its row next door
-        v[i][j] = (j < len[i]) ? vv : 0.0;
-        ci[i][j] = (j < len[i]) ? c - (r0 - PW_HALO) : PW_HALO + t + PW_T * i;   // (slots past the row's end: never summed)
-      }
-      __syncthreads();
+    for (int k = 0; k < RPT + 2; ++k) {
+      xa[t + PW_T * k] = x0r[k];
+      xb[t + PW_T * k] = 0.0;
     }
   }
-  for (int idx = t; idx < XN; idx += PW_T) {
-    const int g = r0 - PW_HALO + idx;
-    xa[idx] = (g >= 0 && g < a.nrows) ? a.x0[g] : 0.0;
-    xb[idx] = 0.0;
+  if constexpr (GEN == 1) {
+    for (int idx = t; idx < XN; idx += PW_T) {
+      const int g = r0 - PW_HALO + idx;
+      xa[idx] = (g >= 0 && g < a.nrows) ? a.x0[g] : 0.0;
+      xb[idx] = 0.0;
+    }
   }
   if (t == 0) s_abort = 0;
   __syncthreads();
@@ -530,12 +562,16 @@ struct nk_powers_plan {
   // several ranks: the neighbours' and my receive areas in the peer-mapped arenas, the halo slots' rows next door
   bool peer = false;
   nk_peer_powers pp;
-  int32_t *d_halo_vl = nullptr;
+  // the per-pattern operand table of k_spmv_powers with a stored matrix (nk_pw_pack.h): built where the plan is made, never again
+  // — values are not in it. 12 bytes per row at W = 5 (12.6 MB at 1024²), 20 at W = 8, 36 at W = 16.
+  uint32_t *d_rec = nullptr;
+  int32_t *d_ext = nullptr;
 };
 void nk_powers_plan_destroy(nk_powers_plan *P) {
   if (!P) return;
   hipFree(P->d_flags);
-  hipFree(P->d_halo_vl);
+  hipFree(P->d_rec);
+  hipFree(P->d_ext);
   if (P->h_err) hipHostFree(P->h_err);
   delete P;
 }
@@ -569,8 +605,12 @@ static bool pw_enabled() {
 //  context on another GPU at the default 64 KB)
 template <int RPT, int W, int GEN, bool PEER = false>
 static int pw_launch(nk_ctx *ctx, const pw_args &a, bool query, int *occ) {
-  constexpr size_t lds_x = (size_t)2 * (PW_T * RPT + 2 * PW_HALO) * sizeof(double), lds_m = (W > 8 || GEN == 1) ? 0 : (size_t)PW_T * W * 12;
+  // the two vector buffers, or the value staging of the load phase where that is larger: one buffer of PW_T·W doubles per slice
+  // in flight, two where a band has more than one slice (2 × 5, 2 × 8: 80 and 128 KB of the CU's 160)
+  constexpr size_t lds_x = (size_t)2 * (PW_T * RPT + 2 * PW_HALO) * sizeof(double);
+  constexpr size_t lds_m = (W > 8 || GEN == 1) ? 0 : (size_t)(RPT > 1 ? 2 : 1) * PW_T * W * sizeof(double);
   constexpr size_t lds = lds_x > lds_m ? lds_x : lds_m;
+  static_assert(lds <= 160 * 1024, "the CU's LDS");
   if (lds > 64 * 1024)
     NK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_spmv_powers<RPT, W, GEN, PEER>),
                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
@@ -657,6 +697,14 @@ static int pw_plan_new(nk_ctx *ctx, int rpt, int w, int nb, nk_powers_plan **out
   *out = guard.release();
   return NK_OK;
 }
+// the packed operand table → the device, owned by the plan
+static int pw_plan_table(nk_ctx *ctx, nk_powers_plan *P, const pw_pack_out &T) {
+  NK_HIP(hipMalloc((void **)&P->d_rec, T.rec.size() * sizeof(uint32_t)));
+  NK_HIP(hipMalloc((void **)&P->d_ext, T.ext.size() * sizeof(int32_t)));
+  NK_HIP(nk_memcpy(ctx, P->d_rec, T.rec.data(), T.rec.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+  NK_HIP(nk_memcpy(ctx, P->d_ext, T.ext.data(), T.ext.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+  return NK_OK;
+}
 
 // Which layout of the resident kernel a pattern fits — host arithmetic only (no device): candidates in the order plain bands, one
 // segment on a ring, two segments, two segments on rings. `skip` candidates have been rejected by the caller (occupancy).
@@ -716,6 +764,13 @@ static pw_layout pw_find_layout(int64_t n, const int32_t *rowptr, const int32_t 
   return L;
 }
 static int pw_layout_index(const pw_layout &L) { return L.kind == 1 ? 0 : (L.seg == 1 ? 1 : (L.ring ? 3 : 2)); }
+// the plain band layout's operand table (host); false: the pattern does not fit the table's fields — no plan
+static bool pw_pack_plain(const nk_csr *A, const pw_layout &L, const int32_t *hvl, int nh, pw_pack_out *T) {
+  pw_pack_in in;
+  in.n = A->nrows; in.rowptr = A->h_rowptr.data(); in.col = A->h_col.data();
+  in.rpt = L.rpt; in.w = L.w; in.nb = L.nb; in.hvl = hvl; in.nh = nh;
+  return pw_pack(in, T) == PW_PACK_OK;
+}
 extern "C" int nk_csr_powers_layout(int64_t nrows, const int32_t *rowptr, const int32_t *col, int num_cus, int layout[6]) {
   NK_REQUIRE(rowptr && col && layout && nrows >= 0 && num_cus >= 1, "bad argument");
   const pw_layout L = pw_find_layout(nrows, rowptr, col, num_cus, 0);
@@ -754,6 +809,8 @@ static int pw_plan_ranks(nk_csr *A) {
       ok = occ >= 1 && L.nb <= ctx->num_cus * occ;
     }
   }
+  pw_pack_out table;   // (before the ranks agree: a pattern the table does not hold is this rank's "no")
+  ok = ok && pw_pack_plain(A, L, hvl.data(), nh, &table);
   nk_peer_powers pp;
   bool all = false;
   NK_TRY(nk_peer_powers_setup(ctx, ok, &pp, &all));
@@ -761,9 +818,7 @@ static int pw_plan_ranks(nk_csr *A) {
   NK_TRY(pw_plan_new(A->ctx, L.rpt, L.w, L.nb, &A->pw));
   A->pw->peer = true;
   A->pw->pp = pp;
-  NK_HIP(hipMalloc((void **)&A->pw->d_halo_vl, hvl.size() * sizeof(int32_t)));
-  NK_HIP(nk_memcpy(ctx, A->pw->d_halo_vl, hvl.data(), hvl.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-  return NK_OK;
+  return pw_plan_table(ctx, A->pw, table);
 }
 static int pw_plan(nk_csr *A) {
   if (A->pw_tried) return NK_OK;
@@ -780,8 +835,11 @@ static int pw_plan(nk_csr *A) {
     if (L.kind == 1) NK_TRY(pw_dispatch(ctx, L.rpt, L.w, probe, true, &occ));
     else NK_TRY(pw_dispatch_seg(ctx, L.rpt, L.w, L.seg, probe, true, &occ));
     if (occ >= 1 && L.nb <= ctx->num_cus * occ) {
+      pw_pack_out table;
+      if (L.kind == 1 && !pw_pack_plain(A, L, nullptr, 0, &table)) return NK_OK;
       NK_TRY(pw_plan_new(A->ctx, L.rpt, L.w, L.nb, &A->pw));
       if (L.kind == 2) { A->pw->seg = L.seg; A->pw->ring = L.ring; A->pw->seg_len = (int)L.M; }
+      else NK_TRY(pw_plan_table(ctx, A->pw, table));
       return NK_OK;
     }
     skip = pw_layout_index(L) + 1;
@@ -789,7 +847,11 @@ static int pw_plan(nk_csr *A) {
   return NK_OK;
 }
 bool nk_csr_powers_ready(nk_csr *A) {
-  if (!A->pw_tried && pw_plan(A) != NK_OK) return false;
+  if (!A->pw_tried && pw_plan(A) != NK_OK) {   // (a plan without its table is no plan)
+    nk_powers_plan_destroy(A->pw);
+    A->pw = nullptr;
+    return false;
+  }
   return A->pw != nullptr && !A->pw->broken && A->pw->h_err[0] == 0;
 }
 // a time-out of an earlier launch (workgroups not resident together: another stream or process held compute units): the plan is
@@ -820,6 +882,7 @@ int nk_csr_powers_dev(nk_csr *A, const double *d_x0, double *d_Y, int64_t ldy, i
   pw_args a{};
   a.nrows = (int)A->nrows; a.nb = P->nb; a.s = s; a.stall = pw_stall_hook();
   a.rowptr = A->d_rowptr; a.col = A->d_col; a.val = A->d_val;
+  a.rec = P->d_rec; a.ext = P->d_ext;
   a.x0 = d_x0; a.Y = d_Y; a.ldy = ldy;
   a.scal_first = d_scal_first; a.scal_rest = d_scal_rest; a.theta = d_theta; a.d_skip = d_skip;
   a.flags = P->d_flags; a.base = (++P->epoch) << 8; a.err = P->h_err_dev;
@@ -832,7 +895,6 @@ int nk_csr_powers_dev(nk_csr *A, const double *d_x0, double *d_Y, int64_t ldy, i
   }
   if (P->peer) {
     a.pr.up = ctx->rank > 0; a.pr.dn = ctx->rank + 1 < ctx->nranks;
-    a.pr.halo_vl = P->d_halo_vl;
     a.pr.push_up = P->pp.push_up; a.pr.push_dn = P->pp.push_dn; a.pr.flag_up = P->pp.flag_up; a.pr.flag_dn = P->pp.flag_dn;
     a.pr.recv_up = P->pp.recv_up; a.pr.recv_dn = P->pp.recv_dn; a.pr.myflag_up = P->pp.myflag_up; a.pr.myflag_dn = P->pp.myflag_dn;
     a.pr.err = nk_peer_err_ptr(ctx);

@@ -3,7 +3,8 @@
 Development: where the time of ONE POWER of the resident matrix-powers kernel goes — phase stamps of every band's wavefront 0
 (100 MHz wall clock, 10 ns resolution), Bratu 1024² (256 bands of 4 slices, W = 5), 15 powers per launch, the steady-state powers
 2 … 13 of the last of `reps` launches. Wavefront 0 is the oldest wavefront of its SIMD and is served first: what the other fifteen
-still have to do shows up in the barrier rows (profiles/r07_powers_gathers_and_ghost_depth2.md).
+still have to do shows up in the barrier rows (profiles/r07_powers_gathers_and_ghost_depth2.md). One more row: the launch's load
+phase, kernel start → first power's start (profiles/r08_powers_packed_load.md).
 
     python tools/pw_stamps.py [grid=1024] [s=15] [reps=20]
 """
@@ -63,6 +64,11 @@ tot = np.array([st[b, p + 1, 0] - st[b, p, 0] for b in range(1, nb - 1) for p in
 print(f"| {'one power (start to next start)':48s} | {np.median(tot):6.2f} | [{np.percentile(tot, 10):5.2f}, {np.percentile(tot, 90):5.2f}] |")
 whole = np.array([st[b, s - 1, 4] - st[b, 0, 0] for b in range(nb) if st[b, s - 1, 4] > 0])
 print(f"| {'powers 0 … s−1 (first start to last compute)':48s} | {np.median(whole):6.2f} |")
+# the load phase: the kernel's start (stamp 10 of power 0) to the first power's start — the band's matrix slice into registers,
+# the start vector's rows into LDS
+load = np.array([st[b, 0, 0] - st[b, 0, 10] for b in range(nb) if st[b, 0, 10] > 0 and st[b, 0, 0] > 0])
+if load.size:
+    print(f"| {'load phase (kernel start to first power start)':48s} | {np.median(load):6.2f} | [{np.percentile(load, 10):5.2f}, {np.percentile(load, 90):5.2f}] |")
 # bands whose neighbour sits on another XCD (the band → XCD map is 32 consecutive bands per XCD at 256 bands)
 q = nb // 8
 if q > 1:
