@@ -449,7 +449,8 @@ static void tr_defaults(nk_solver *S) {
     default: break;
   }
 }
-static int tr_radii(nk_solver *S) {
+// J_at_u: the concrete J holds the values of J(S->u) (init fills it; reinit! does not)
+static int tr_radii(nk_solver *S, bool J_at_u) {
   const int m = S->o.radius_update_scheme;
   nk_ctx *ctx = S->ctx;
   NK_TRY(nk_blas_sumsq(ctx, S->n, S->u, slot(S, 0)));
@@ -467,6 +468,13 @@ static int tr_radii(nk_solver *S) {
   else if (m == NK_RUS_FAN) S->init_tr = pow(fu_norm, 0.99) / 10.0;
   else S->init_tr = S->max_tr / 11.0;
   if (m == NK_RUS_YUAN) {
+    if (!J_at_u) {
+      // after reinit! the concrete J still holds the last iterate's values, and Jᵀfu is wanted at the NEW u0 (trust_region.jl:308-312):
+      // the values are filled as init fills them, so that a run after reinit! repeats a run after init bit for bit; the
+      // reference's vjp operator evaluates no Jacobian here, so the count stays
+      NK_TRY(refresh_J(S));
+      S->stats.njacs--;
+    }
     NK_TRY(apply_JT(S, S->u, S->fu, S->JTfu));
     NK_TRY(nk_blas_sumsq(ctx, S->n, S->JTfu, slot(S, 0)));
     NK_TRY(fetch(S, 1, v));
@@ -839,7 +847,7 @@ static int solver_start(nk_solver *S, bool first = true) {  // everything after 
   S->lin_reltol = S->o.lin_reltol >= 0.0 ? S->o.lin_reltol : S->tcc.reltol;
   if (is_tr(S)) {
     tr_defaults(S);
-    NK_TRY(tr_radii(S));
+    NK_TRY(tr_radii(S, first || !concrete(S)));
     S->tr = S->init_tr;
     S->rho = 0.0;
     S->shrink_counter = 0;
@@ -1101,14 +1109,18 @@ static int newton_descent(nk_solver *S, double *du_out, bool *ok, bool new_jacob
     if (lu_ok) {
       NK_TRY(nk_bandlu_solve(S->B, S->fu, du_out));
       // The direct engines (block cyclic reduction, band LU) pivot on the diagonal only, so the solve is verified: ‖J x − b‖₂ ≤ 1e-10 ‖b‖₂, with one step of iterative
-      // refinement before giving up on the factorisation.
+      // refinement before giving up on the factorisation. Under a trust region the step is taken whenever the first residual is above 64 u ‖b‖₂ (what a
+      // backward-stable solve of a well-conditioned system leaves): a plain Newton iteration corrects a direction that is 1e-10 off with its next step,
+      // but the dogleg's segment and the ratio ρ are formed FROM this direction — on an indefinite J (Bratu above its turning point) the reduction's x,
+      // accepted at 1e-10, was 3e-10 off and δu with it (tests/test_gpu_trust_region.py).
+      const double refine_above = is_tr(S) ? 64.0 * 1.1102230246251565e-16 : 1e-10;
       for (int pass = 0; pass < 2; ++pass) {
         NK_TRY(nk_csr_spmv_dev(S->J, du_out, S->stage, nullptr));
         NK_TRY(nk_blas_lincomb(S->ctx, S->n, 1.0, S->fu, -1.0, S->stage, S->stage));  // r = b − J x
         const double *xs[2] = {S->stage, S->fu}, *ys[2] = {S->stage, S->fu};
         NK_TRY(nk_blas_multi_reduce(S->ctx, S->n, 2, xs, ys, nullptr, nullptr, 0, 0, slot(S, 0)));
         NK_TRY(fetch(S, 2, v));
-        if (!(v[0] == v[0]) || sqrt(v[0]) <= 1e-10 * sqrt(v[1]) + 1e-300 || pass == 1) break;
+        if (!(v[0] == v[0]) || sqrt(v[0]) <= refine_above * sqrt(v[1]) + 1e-300 || pass == 1) break;
         if (!S->stage2) NK_TRY(nk_dev_alloc(&S->stage2, (size_t)S->n + 2));
         NK_TRY(nk_bandlu_solve(S->B, S->stage, S->stage2));                             // J dx = r
         NK_TRY(nk_blas_axpby(S->ctx, S->n, 1.0, S->stage2, 1.0, du_out));

@@ -250,6 +250,7 @@ def test_linear_solve_failure_on_stale_jacobian_retries_with_a_new_one(nls, dev,
 @pytest.mark.parametrize("scheme", ["Simple", "NLsolve", "NocedalWright", "Hei", "Yuan", "Fan", "Bastin"])
 @pytest.mark.parametrize("concrete", [False, True])
 def test_trust_region_fused_step_matches_oracle(nls, scheme, concrete):
+    """Whole solves; the step itself, branch by branch, is tests/test_gpu_trust_region.py."""
     N = 12
     rs = getattr(nls.RadiusUpdateSchemes, scheme)
     ro = {"Simple": R.SIMPLE, "NLsolve": R.NLSOLVE, "NocedalWright": R.NOCEDAL_WRIGHT, "Hei": R.HEI, "Yuan": R.YUAN,
