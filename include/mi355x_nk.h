@@ -1132,15 +1132,23 @@ int nk_newton_solve(nk_problem *P, const double *u0, int memspace, const nk_opti
  * (a source written with nk_real compiles in both modes; one written with `const double *p` fails in Float32 mode with the
  * contract in nk_last_error). Such an object is solved through the _f32 entry points, which take float arrays; scalar
  * arguments stay double and are rounded to float (T(abstol)). Calling an object through the other precision's entry point is
- * NK_E_INVALID. nk_batch_compile_check compiles only (no device needed). */
-enum { NK_BATCH_ANALYTIC_JAC = 1, NK_BATCH_FLOAT32 = 2 };   /* bits of `flags` */
+ * NK_E_INVALID. nk_batch_compile_check compiles only (no device needed).
+ * Medium systems, 8 < n <= 64, run one system per WAVEFRONT where such a kernel exists (nk_batch_newton_wave,
+ * nk_batch_trust_region_wave: lane j owns column j of the dual-number Jacobian; nk_jac is not used by them). flags &
+ * NK_BATCH_PER_THREAD switches that off for an object: no wavefront module is built or used and every method runs one system
+ * per thread (the A/B handle; nk_batch_last_kernel tells which kernel ran). */
+enum { NK_BATCH_ANALYTIC_JAC = 1, NK_BATCH_FLOAT32 = 2, NK_BATCH_PER_THREAD = 4 };   /* bits of `flags` */
 int nk_batch_compile_check(const char *source, int n, int nparams, int flags, int64_t *code_bytes);
 /* the compiled code object of one kernel set (wave = 0: nk_batch_newton and nk_batch_trust_region; 1: the one-system-per-
- * wavefront nk_batch_newton_wave), for inspection; *bytes gets its size, buf = NULL asks for the size only */
+ * wavefront nk_batch_newton_wave; 2: the one-system-per-wavefront nk_batch_trust_region_wave; wave > 2 is NK_E_INVALID), for
+ * inspection; *bytes gets its size, buf = NULL asks for the size only */
 int nk_batch_code_object(const char *source, int n, int nparams, int flags, int wave, void *buf, int64_t capacity,
                          int64_t *bytes);
 int nk_batch_create(nk_ctx *ctx, const char *source, int n, int nparams, int flags, nk_batch **out);
 int nk_batch_destroy(nk_batch *B);
+/* the name of the kernel the last solve on B launched ("nk_batch_newton_wave", "nk_batch_trust_region", ...): "" before any
+ * solve, NULL for a NULL object. The string is static. */
+const char *nk_batch_last_kernel(nk_batch *B);
 /* u0: n doubles shared by all systems (u0_per_system = 0) or nbatch×n; p: nbatch×nparams; outputs nbatch×n, nbatch×n,
  * nbatch, nbatch (retcode/iters nullable); abstol ≤ 0 and maxiters ≤ 0 select the defaults. */
 int nk_batch_solve(nk_batch *B, int64_t nbatch, const double *u0, int u0_per_system, const double *p, int memspace,
@@ -1149,7 +1157,11 @@ int nk_batch_solve_f32(nk_batch *B, int64_t nbatch, const float *u0, int u0_per_
                        double abstol, int maxiters, float *u_out, float *resid_out, int32_t *retcode_out, int32_t *iters_out);
 /* SimpleTrustRegion (lib/SimpleNonlinearSolve/src/trust_region.jl:57-229, default radius update) per system; thresholds and
  * factors ≤ 0, max_shrink_times < 0 select the reference defaults (1e-4, 0.25, 0.75, 0.25, 2, 32). Retcodes: NK_RET_SUCCESS,
- * NK_RET_MAXITERS, NK_RET_SHRINK_THRESHOLD_EXCEEDED. */
+ * NK_RET_MAXITERS, NK_RET_SHRINK_THRESHOLD_EXCEEDED.
+ * For 8 < n <= 64 (from NK_BATCH_TR_WAVE_MIN_N of nk_batch.hip on) the first such solve on an object compiles and loads
+ * nk_batch_trust_region_wave, a module of its own, and this and later solves launch it; with NK_BATCH_PER_THREAD, at other
+ * n, or if that module does not build, nk_batch_trust_region runs, one system per thread. The two differ at rounding level
+ * only: column instead of row pivoting in the LU, ‖Jδ‖² for δᵀJᵀJδ, and butterfly instead of sequential sums. */
 int nk_batch_solve_trust_region(nk_batch *B, int64_t nbatch, const double *u0, int u0_per_system, const double *p, int memspace,
                                 double abstol, int maxiters, double step_threshold, double shrink_threshold,
                                 double expand_threshold, double shrink_factor, double expand_factor, int max_shrink_times,

@@ -17,7 +17,7 @@ class NKError(RuntimeError):
 
 # ---------------------------------------------------------------------------- enums (mirror the header)
 HOST, DEVICE = 0, 1
-BATCH_ANALYTIC_JAC, BATCH_FLOAT32 = 1, 2   # nk_batch_create / nk_batch_compile_check flags
+BATCH_ANALYTIC_JAC, BATCH_FLOAT32, BATCH_PER_THREAD = 1, 2, 4   # nk_batch_create / nk_batch_compile_check flags
 GRID_STENCILS = {"star": 0, "box": 1, "star2": 16, "diamond2": 17}               # nk_problem_create_grid / nk_grid_pattern
 GRID_BOUNDARIES = {"dirichlet": 0, "periodic": 1}                                 # the two uniform boundaries
 GRID_SIDE_KINDS = {"dirichlet": 0, "periodic": 1, "mirror_node": 2, "mirror_face": 3}   # NK_GRID_DIRICHLET0 … NK_GRID_MIRROR_FACE
@@ -282,6 +282,7 @@ SIGNATURES = {
     "nk_batch_compile_check": (_I, [C.c_char_p, _I, _I, _I, C.POINTER(_L)]),
     "nk_batch_create": (_I, [_P, C.c_char_p, _I, _I, _I, _PP]),
     "nk_batch_destroy": (_I, [_P]),
+    "nk_batch_last_kernel": (C.c_char_p, [_P]),
     "nk_batch_solve": (_I, [_P, _L, _P, _I, _P, _I, _D, _I, _P, _P, _P, _P]),
     "nk_batch_solve_trust_region": (_I, [_P, _L, _P, _I, _P, _I, _D, _I, _D, _D, _D, _D, _D, _I, _P, _P, _P, _P]),
     "nk_batch_solve_f32": (_I, [_P, _L, _P, _I, _P, _I, _D, _I, _P, _P, _P, _P]),

@@ -2302,7 +2302,12 @@ SimpleGaussNewton = SimpleNewtonRaphson
 
 @dataclass
 class SimpleTrustRegion:
-    """lib/SimpleNonlinearSolve/src/trust_region.jl:44-55 (default radius update rule); None = reference default."""
+    """lib/SimpleNonlinearSolve/src/trust_region.jl:44-55 (default radius update rule); None = reference default.
+
+    In `vectorized_solve` a square ensemble with 8 < n ≤ 64 runs one system per wavefront (`nk_batch_trust_region_wave`: lane j
+    owns column j of the dual-number Jacobian; `jac=True` is not used there); n ≤ 8, `per_wavefront=False` and least-squares
+    problems run one system per thread (`nk_batch_trust_region`, `nk_batch_trust_region_nlls`). The two forms differ at
+    rounding level only; `EnsembleSolution.kernel` names the one that ran."""
     jac: bool = False
     step_threshold: float = 1e-4
     shrink_threshold: Optional[float] = None   # 0.25
@@ -2392,6 +2397,7 @@ class EnsembleSolution:
     retcode: np.ndarray  # (nbatch,) strings
     iters: np.ndarray    # (nbatch,)
     retcode_raw: np.ndarray = None
+    kernel: str = ""     # the kernel that solved the ensemble (nk_batch_last_kernel), e.g. "nk_batch_trust_region_wave"
 
 
 def _is_float32(eltype) -> bool:
@@ -2422,15 +2428,25 @@ class _BatchKernel:
         return cls._cache[key]
 
 
-def vectorized_solve(prob: ImmutableNonlinearProblem, alg=None, abstol=None, maxiters=1000):
+def vectorized_solve(prob: ImmutableNonlinearProblem, alg=None, abstol=None, maxiters=1000, per_wavefront=None):
     """`vectorized_solve(prob, alg; backend = ROCBackend())` of the tutorial (nonlinear_solve_gpus.md:106-114): solve
     every parameter set with SimpleNewtonRaphson, one system per GPU thread, in one kernel launch. The problem's eltype
     picks the precision (Float64 unless it was built with eltype=float32). `alg` may also be SimpleTrustRegion or one of the
     Jacobian-free SimpleBroyden, SimpleKlement, SimpleDFSane (their kernels are compiled on first use). On an
     ImmutableNonlinearLeastSquaresProblem `alg` is SimpleGaussNewton (= SimpleNewtonRaphson) or SimpleTrustRegion, and
-    `resid` has shape (nbatch, m)."""
+    `resid` has shape (nbatch, m).
+
+    `per_wavefront`: None picks the form per method and size (SimpleNewtonRaphson and SimpleTrustRegion run one system per
+    wavefront for 8 < n ≤ 64); False runs every method one system per thread (NK_BATCH_PER_THREAD); True insists on a
+    per-wavefront kernel: ValueError where there is none to ask for (n ≤ 8, n > 64, a least-squares problem, a Jacobian-free
+    method), RuntimeError if it did not build. `EnsembleSolution.kernel` names the kernel that ran."""
     alg = alg or SimpleNewtonRaphson()
     nlls = isinstance(prob, ImmutableNonlinearLeastSquaresProblem)
+    if per_wavefront and (nlls or not 8 < prob.n <= 64):
+        raise ValueError("per_wavefront=True: the per-wavefront kernels solve square systems with 8 < n <= 64" +
+                         (" (this is a least-squares problem)" if nlls else f" (n = {prob.n})"))
+    if per_wavefront and not isinstance(alg, (SimpleNewtonRaphson, SimpleTrustRegion)):
+        raise ValueError(f"per_wavefront=True: {getattr(alg, 'name', type(alg).__name__)} has no per-wavefront kernel")
     if nlls and not isinstance(alg, (SimpleNewtonRaphson, SimpleTrustRegion)):
         raise TypeError(f"{getattr(alg, 'name', type(alg).__name__)} is not defined on a least-squares problem (nor is it in "
                         "the reference): use SimpleGaussNewton or SimpleTrustRegion")
@@ -2439,7 +2455,8 @@ def vectorized_solve(prob: ImmutableNonlinearProblem, alg=None, abstol=None, max
     if isinstance(alg, SimpleDFSane) and not (1 <= int(alg.M) <= 32 and int(alg.n_exp) in (1, 2)):
         raise ValueError(f"SimpleDFSane: M = {alg.M} must lie in 1..32 and n_exp = {alg.n_exp} must be 1 or 2")
     f32 = prob.float32
-    flags = (L.BATCH_ANALYTIC_JAC if getattr(alg, "jac", False) else 0) | (L.BATCH_FLOAT32 if f32 else 0)
+    flags = (L.BATCH_ANALYTIC_JAC if getattr(alg, "jac", False) else 0) | (L.BATCH_FLOAT32 if f32 else 0) | \
+        (L.BATCH_PER_THREAD if per_wavefront is False else 0)
     h = _BatchKernel.get(prob.ctx, prob.f_source, prob.n, prob.nparams, flags, prob.m if nlls else None)
     on_dev = _is_torch(prob.p) and prob.p.is_cuda
     nb, n = prob.nbatch, prob.n
@@ -2491,7 +2508,10 @@ def vectorized_solve(prob: ImmutableNonlinearProblem, alg=None, abstol=None, max
                     0.0 if abstol is None else float(abstol), int(maxiters), ptr(u), ptr(r), ptr(rc), ptr(it)))
     rch = rc.cpu().numpy() if on_dev else rc
     ith = it.cpu().numpy() if on_dev else it
-    return EnsembleSolution(u, r, np.asarray(L.RET_NAMES)[rch], ith.copy(), rch.copy())
+    kernel = (L.lib().nk_batch_last_kernel(h) or b"").decode()
+    if per_wavefront and not kernel.endswith("_wave"):
+        raise RuntimeError(f"per_wavefront=True, but {kernel} ran: the per-wavefront kernel did not build")
+    return EnsembleSolution(u, r, np.asarray(L.RET_NAMES)[rch], ith.copy(), rch.copy(), kernel)
 
 
 # ------------------------------------------------------------------------------------------- Jacobian operators

@@ -231,7 +231,9 @@ nk_batch_trust_region(long nbatch, const nk_real *__restrict__ u0, int u0_per_sy
 // wave reduction, so no register ever moves; the multipliers l_r = a[r][p]/a[c][p] live in lane p and reach the others through
 // v_readlane with a scalar lane index; every lane then updates its own column with register indices that are compile-time
 // constants. The right-hand side, x and f(x) are replicated in all lanes. (nk_jac, if supplied, is not used by this kernel.)
-static const char *k_kernel_wave = R"NKSRC(
+// The lane helpers come first in the program text of both wavefront kernel sets (k_kernel_wave and k_kernel_wave_tr continue the
+// text where this string ends, so that the Newton program reads exactly as it did as one string).
+static const char *k_wave_helpers = R"NKSRC(
 __device__ inline nk_real nk_rl(nk_real v, int lane) {
 #ifdef NK_F32
   return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), lane));   // one 32-bit readlane
@@ -246,7 +248,8 @@ __device__ inline nk_real nk_wave_max(nk_real v) {
   for (int o = 32; o > 0; o >>= 1) { const nk_real w = __shfl_xor(v, o, 64); v = w > v ? w : v; }
   return v;
 }
-extern "C" __global__ void __launch_bounds__(NK_BLOCK_T)
+)NKSRC";
+static const char *k_kernel_wave = R"NKSRC(extern "C" __global__ void __launch_bounds__(NK_BLOCK_T)
 nk_batch_newton_wave(long nbatch, const nk_real *__restrict__ u0, int u0_per_system, const nk_real *__restrict__ p, nk_real abstol,
                      int maxiters, nk_real *__restrict__ u_out, nk_real *__restrict__ r_out, int *__restrict__ retcode,
                      int *__restrict__ iters) {
@@ -324,6 +327,174 @@ nk_batch_newton_wave(long nbatch, const nk_real *__restrict__ u0, int u0_per_sys
         break;
       }
       nk_f<nk_real>(x, pp, fx);
+    }
+    if (it > maxiters) it = maxiters;
+  }
+  if (lane == 0) {
+#pragma unroll
+    for (int i = 0; i < NK_N; ++i) { u_out[b * NK_N + i] = x[i]; r_out[b * NK_N + i] = fx[i]; }
+    retcode[b] = rc;
+    iters[b] = it;
+  }
+}
+)NKSRC";
+
+// ---- SimpleTrustRegion, one system per wavefront (8 < n ≤ 64): the semantics of nk_batch_trust_region above, the layout of
+// nk_batch_newton_wave. Lane j owns column j of J, so g_j = col·f needs no other lane, and g, δN, δsd, δ, xₒ and the trial point
+// live one entry per lane; x, f(x) and p are replicated, as nk_f needs them. ‖·‖₂ and the dogleg's dot products are 64-lane
+// xor butterflies (a + b and b + a are the same bits, so every lane ends with the same sum). There is no second copy of the
+// column: g is formed before the LU factors the column in place, and the next step — after a rejected trial too — gets the
+// column again by a dual sweep at xₒ. δᵀJᵀJδ = ‖Jδ‖², with Jδ from one more dual sweep seeded with δ itself (replicated in all
+// lanes): no transposed product. Every scalar that steers a branch is the same in all lanes; each decision still goes through
+// v_readfirstlane, so that the branches are scalar ones.
+// Rounding-level differences from nk_batch_trust_region: column instead of row pivoting in the LU; ‖Jδ‖² instead of
+// δ·(Jᵀ(Jδ)); butterfly sums instead of sequential ones for the per-lane vectors (‖f‖₂ and g are summed in its order).
+static const char *k_kernel_wave_tr = R"NKSRC(
+__device__ inline nk_real nk_wave_sum(nk_real v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+// a decision that every lane takes alike, as a scalar
+__device__ inline bool nk_uniform(bool c) { return __builtin_amdgcn_readfirstlane((int)c) != 0; }
+// AbsNormTerminationMode(maximum∘abs): maximum propagates NaN, and NaN <= abstol is false
+__device__ inline bool nk_absmax_ok(const nk_real *f, nk_real abstol) {
+  nk_real nrm = NK_R(0);
+  bool nan = false;
+#pragma unroll
+  for (int i = 0; i < NK_N; ++i) { const nk_real a = fabs(f[i]); nan = nan || (a != a); nrm = a > nrm ? a : nrm; }
+  return !nan && nrm <= abstol;
+}
+__device__ inline nk_real nk_norm2(const nk_real *v) {
+  nk_real s = NK_R(0);
+#pragma unroll
+  for (int i = 0; i < NK_N; ++i) s += v[i] * v[i];
+  return sqrt(s);
+}
+extern "C" __global__ void __launch_bounds__(NK_BLOCK_T)
+nk_batch_trust_region_wave(long nbatch, const nk_real *__restrict__ u0, int u0_per_system, const nk_real *__restrict__ p,
+                           nk_real abstol, int maxiters, nk_real eta1, nk_real eta2, nk_real eta3, nk_real t1, nk_real t2,
+                           int max_shrink, nk_real *__restrict__ u_out, nk_real *__restrict__ r_out, int *__restrict__ retcode,
+                           int *__restrict__ iters) {
+  const int lane = threadIdx.x & 63;
+  const long b = (long)blockIdx.x * (NK_BLOCK_T / 64) + (threadIdx.x >> 6);
+  if (b >= nbatch) return;   // whole wavefronts leave together
+  nk_real x[NK_N], fx[NK_N], col[NK_N], pp[NK_NP > 0 ? NK_NP : 1];  // fx doubles as the right-hand side of the solve
+#pragma unroll
+  for (int i = 0; i < NK_N; ++i) x[i] = u0[(u0_per_system ? b * NK_N : 0) + i];
+#pragma unroll
+  for (int i = 0; i < NK_NP; ++i) pp[i] = p[b * NK_NP + i];
+  // per lane: entry `lane` of the accepted point xₒ, of the trial point and of g; lanes without a column hold zeros
+  const bool own = lane < NK_N;
+  nk_real xo = u0[(u0_per_system ? b * NK_N : 0) + (own ? lane : 0)];
+  xo = own ? xo : NK_R(0);
+  nk_real xt = xo, g = NK_R(0);
+  nk_f<nk_real>(x, pp, fx);
+  const nk_real norm_fx = nk_norm2(fx);
+  nk_real xmax = x[0], xmin = x[0];
+#pragma unroll
+  for (int i = 1; i < NK_N; ++i) { xmax = x[i] > xmax ? x[i] : xmax; xmin = x[i] < xmin ? x[i] : xmin; }
+  const nk_real dmax = norm_fx > xmax - xmin ? norm_fx : xmax - xmin;
+  nk_real delta = dmax / NK_R(11);
+  nk_real fk = NK_R(0.5) * norm_fx * norm_fx;
+  int shrink = 0, rc = 2, it = 0;
+  bool at_xo = true;   // fx is the residual at xₒ (the start, or an accepted trial): g is due
+  if (nk_uniform(nk_absmax_ok(fx, abstol))) rc = 1;
+  else {
+    for (it = 1; it <= maxiters; ++it) {
+#pragma unroll
+      for (int i = 0; i < NK_N; ++i) x[i] = nk_rl(xo, i);   // xₒ, replicated (after a rejected trial x holds the trial point)
+      {  // column `lane` of J(xₒ) by one dual-number sweep
+        Dual xd[NK_N], fd[NK_N];
+#pragma unroll
+        for (int i = 0; i < NK_N; ++i) { xd[i].v = x[i]; xd[i].d[0] = (i == lane) ? NK_R(1) : NK_R(0); }
+        nk_f<Dual>(xd, pp, fd);
+#pragma unroll
+        for (int i = 0; i < NK_N; ++i) col[i] = own ? fd[i].d[0] : NK_R(0);
+      }
+      if (at_xo) {   // g = Jᵀf at the accepted point; after a rejected trial g stays while fx is the trial's residual
+        nk_real s = NK_R(0);
+#pragma unroll
+        for (int i = 0; i < NK_N; ++i) s += col[i] * fx[i];
+        g = own ? s : NK_R(0);   // (0·NaN of an idle lane must not reach the sums)
+      }
+      // ---- δN = −J \ fx: LU with column pivoting, applied to the right-hand side on the fly (as nk_batch_newton_wave)
+      nk_real *rhs = fx;
+      bool used = !own;   // lanes without a column never pivot
+      int perm[NK_N];
+#pragma unroll
+      for (int c = 0; c < NK_N; ++c) {
+        const nk_real mine = used ? -NK_R(1) : fabs(col[c]);
+        const nk_real best = nk_wave_max(mine);
+        const unsigned long long m = __ballot(!used && mine == best);
+        const int pl = m ? (int)__ffsll((long long)m) - 1 : 0;   // (a NaN row: every compare fails — take lane 0, NaNs propagate)
+        const int pv = __builtin_amdgcn_readfirstlane(pl);
+        perm[c] = pv;
+        const nk_real inv = NK_R(1) / nk_rl(col[c], pv);
+        if (lane == pv) used = true;
+        const nk_real cc = col[c];
+#pragma unroll
+        for (int r = c + 1; r < NK_N; ++r) {
+          const nk_real l = nk_rl(col[r], pv) * inv;
+          if (!used) col[r] -= l * cc;
+          rhs[r] -= l * rhs[c];
+        }
+      }
+      nk_real dN = NK_R(0);
+#pragma unroll
+      for (int c = NK_N - 1; c >= 0; --c) {
+        const int pv = perm[c];
+        const nk_real xc = rhs[c] / nk_rl(col[c], pv);
+        if (lane == pv) dN = -xc;
+#pragma unroll
+        for (int r = 0; r < c; ++r) rhs[r] -= nk_rl(col[r], pv) * xc;
+      }
+      // ---- dogleg: the Newton step inside the region, else −g clipped to Δ, else the boundary point of the segment
+      nk_real dl;
+      if (nk_uniform(sqrt(nk_wave_sum(dN * dN)) <= delta)) dl = dN;
+      else {
+        const nk_real dsd = -g;
+        const nk_real nsd = sqrt(nk_wave_sum(dsd * dsd));
+        if (nk_uniform(nsd >= delta)) dl = dsd * (delta / nsd);
+        else {
+          const nk_real q = dN - dsd;
+          const nk_real dNN = nk_wave_sum(q * q), dSN = nk_wave_sum(dsd * q), dSS = nk_wave_sum(dsd * dsd);
+          const nk_real fact = dSN * dSN - dNN * (dSS - delta * delta);
+          const nk_real tau = (-dSN + sqrt(fact)) / dNN;
+          dl = dsd + tau * q;
+        }
+        dl = own ? dl : NK_R(0);   // (a NaN or infinite factor must not reach the sums through the idle lanes)
+      }
+      // ---- δᵀJᵀJδ = ‖Jδ‖²: one dual sweep at xₒ seeded with δ
+      nk_real dHd = NK_R(0);
+      {
+        Dual xd[NK_N], fd[NK_N];
+#pragma unroll
+        for (int i = 0; i < NK_N; ++i) { xd[i].v = x[i]; xd[i].d[0] = nk_rl(dl, i); }
+        nk_f<Dual>(xd, pp, fd);
+#pragma unroll
+        for (int i = 0; i < NK_N; ++i) dHd += fd[i].d[0] * fd[i].d[0];
+      }
+      xt = xo + dl;
+#pragma unroll
+      for (int i = 0; i < NK_N; ++i) x[i] = nk_rl(xt, i);
+      nk_f<nk_real>(x, pp, fx);
+      const nk_real nf = nk_norm2(fx);
+      const nk_real fk1 = nf * nf / NK_R(2);
+      const nk_real r = (fk1 - fk) / (nk_wave_sum(dl * g) + dHd / NK_R(2));
+      at_xo = false;
+      if (nk_uniform(r >= eta2)) shrink = 0;
+      else {
+        delta = t1 * delta;
+        if (++shrink > max_shrink) { rc = 6; break; }   // ShrinkThresholdExceeded
+      }
+      if (nk_uniform(r >= eta1)) {
+        if (nk_uniform(nk_absmax_ok(fx, abstol))) { rc = 1; break; }
+        xo = xt;
+        if (nk_uniform(r > eta3)) delta = t2 * delta < dmax ? t2 * delta : dmax;
+        fk = fk1;
+        at_xo = true;
+      }
     }
     if (it > maxiters) it = maxiters;
   }
@@ -863,6 +1034,11 @@ struct nk_batch {
   hipFunction_t fn_gn = nullptr, fn_tr_nlls = nullptr;
   hipModule_t mod = nullptr, mod_wave = nullptr;
   hipFunction_t fn = nullptr, fn_tr = nullptr, fn_wave = nullptr;  // fn_wave: one system per wavefront (8 < n ≤ 64)
+  // the per-wavefront trust-region kernel: a module of its own, compiled on the first trust-region solve that can use it
+  hipModule_t mod_tr_wave = nullptr;
+  hipFunction_t fn_tr_wave = nullptr;
+  bool tr_wave_tried = false;      // one attempt per object: a failed build leaves the per-thread kernel in charge
+  const char *last_kernel = "";    // the kernel the last solve launched (nk_batch_last_kernel)
   // the Jacobian-free kernels: a module of their own, compiled on the first call that needs it (from source / flags)
   hipModule_t mod_jf = nullptr;
   hipFunction_t fn_broyden = nullptr, fn_klement = nullptr, fn_dfsane = nullptr;
@@ -878,13 +1054,19 @@ struct nk_batch {
 // the kernel sets, one hiprtc program each
 enum { KSET_NEWTON = 0 /* nk_batch_newton + nk_batch_trust_region */, KSET_WAVE = 1 /* nk_batch_newton_wave */,
        KSET_JF = 2 /* nk_batch_broyden + nk_batch_klement + nk_batch_dfsane */,
-       KSET_NLLS = 3 /* nk_batch_gauss_newton + nk_batch_trust_region_nlls (m residuals, -DNK_M) */ };
+       KSET_NLLS = 3 /* nk_batch_gauss_newton + nk_batch_trust_region_nlls (m residuals, -DNK_M) */,
+       KSET_WAVE_TR = 4 /* nk_batch_trust_region_wave */ };
+
+// SimpleTrustRegion runs one system per wavefront from this n on (up to 64), one per thread below: the smallest measured n
+// from which nk_batch_trust_region_wave solved at least as many systems per second as nk_batch_trust_region at every larger
+// measured n, in Float64 and in Float32 ("Ensemble SimpleTrustRegion per wavefront")
+#define NK_BATCH_TR_WAVE_MIN_N 9
 
 // compile `source` (+ prelude + solver kernels) for n unknowns / np parameters (and, for KSET_NLLS, m residuals); code
 // object into `code`, log into `log`
 static int batch_compile(const char *source, int n, int np, int flags, std::vector<char> *code, std::string *log,
                          int kset = KSET_NEWTON, int m = 0) {
-  const bool wave = kset == KSET_WAVE, nlls = kset == KSET_NLLS;
+  const bool wave = kset == KSET_WAVE || kset == KSET_WAVE_TR, nlls = kset == KSET_NLLS;
   NK_REQUIRE(source, "NULL source");
   NK_REQUIRE(n >= 1 && n <= 64, "n = %d outside 1..64 (one system per thread)", n);
   NK_REQUIRE(!nlls || (m >= n && m <= 64),
@@ -893,8 +1075,10 @@ static int batch_compile(const char *source, int n, int np, int flags, std::vect
              "minimum-norm solution of an underdetermined problem is not offered)", m, n);
   NK_REQUIRE(np >= 0 && np <= 256, "nparams = %d outside 0..256", np);
   std::string full = std::string(nk_dual_prelude) + "\n// ---- user source\n" + source + "\n" +
-                     (wave ? k_kernel_wave : kset == KSET_JF ? k_kernel_jf : nlls ? k_kernel_nlls : k_kernel);
-  // dual-number partials per residual sweep (wave kernel: one per lane; the Jacobian-free kernels sweep no duals)
+                     (wave ? k_wave_helpers : "") +
+                     (kset == KSET_WAVE ? k_kernel_wave : kset == KSET_WAVE_TR ? k_kernel_wave_tr : kset == KSET_JF ? k_kernel_jf
+                      : nlls ? k_kernel_nlls : k_kernel);
+  // dual-number partials per residual sweep (wave kernels: one per lane; the Jacobian-free kernels sweep no duals)
   const int ch = wave || kset == KSET_JF ? 1 : (n < 8 ? n : 8);
   const std::string dn = "-DNK_N=" + std::to_string(n), dp = "-DNK_NP=" + std::to_string(np), dc = "-DNK_CH=" + std::to_string(ch),
                     db = wave ? "-DNK_BLOCK_T=256" : "-DNK_BLOCK_T=64";
@@ -917,13 +1101,14 @@ static int batch_compile(const char *source, int n, int np, int flags, std::vect
   return NK_OK;
 }
 
-// compile only (no device needed): the "does the user's residual build for gfx950" check
+// compile only (no device needed): the "does the user's residual build for gfx950" check. (The per-wavefront trust-region
+// kernel instantiates nk_f exactly as the per-wavefront Newton kernel does, so it is not compiled here as well.)
 extern "C" int nk_batch_compile_check(const char *source, int n, int nparams, int flags, int64_t *code_bytes) {
   std::vector<char> code;
   std::string log;
   NK_TRY(batch_compile(source, n, nparams, flags, &code, &log));
   if (code_bytes) *code_bytes = (int64_t)code.size();
-  if (n > 8) {  // medium systems also get the per-wavefront Newton kernel
+  if (n > 8 && !(flags & NK_BATCH_PER_THREAD)) {  // medium systems also get the per-wavefront Newton kernel
     std::vector<char> wcode;
     std::string wlog;
     NK_TRY(batch_compile(source, n, nparams, flags, &wcode, &wlog, KSET_WAVE));
@@ -932,14 +1117,16 @@ extern "C" int nk_batch_compile_check(const char *source, int n, int nparams, in
   return NK_OK;
 }
 
-// the code object hiprtc makes for one kernel set (wave = 0: nk_batch_newton + nk_batch_trust_region; 1: nk_batch_newton_wave),
-// for inspection (disassembly, resource notes). *bytes gets its size; buf may be NULL to ask for the size only.
+// the code object hiprtc makes for one kernel set (wave = 0: nk_batch_newton + nk_batch_trust_region; 1: nk_batch_newton_wave;
+// 2: nk_batch_trust_region_wave), for inspection (disassembly, resource notes). *bytes gets its size; buf may be NULL to ask
+// for the size only.
 extern "C" int nk_batch_code_object(const char *source, int n, int nparams, int flags, int wave, void *buf, int64_t capacity,
                                     int64_t *bytes) {
   NK_REQUIRE(bytes, "NULL argument");
   std::vector<char> code;
   std::string log;
-  NK_TRY(batch_compile(source, n, nparams, flags, &code, &log, wave != 0 ? KSET_WAVE : KSET_NEWTON));
+  NK_REQUIRE(wave <= 2, "wave = %d: 0 (per thread), 1 (nk_batch_newton_wave) or 2 (nk_batch_trust_region_wave)", wave);
+  NK_TRY(batch_compile(source, n, nparams, flags, &code, &log, wave == 2 ? KSET_WAVE_TR : wave != 0 ? KSET_WAVE : KSET_NEWTON));
   return nk_rtc_copy_out(code, buf, capacity, bytes);
 }
 
@@ -1016,7 +1203,7 @@ extern "C" int nk_batch_create(nk_ctx *ctx, const char *source, int n, int npara
     NK_FAIL(NK_E_HIP, "kernel nk_batch_newton not found in the compiled module");
   }
   if (hipModuleGetFunction(&B->fn_tr, B->mod, "nk_batch_trust_region") != hipSuccess) B->fn_tr = nullptr;
-  if (n > 8) {  // Newton for medium systems: the per-wavefront kernel
+  if (n > 8 && !(flags & NK_BATCH_PER_THREAD)) {  // Newton for medium systems: the per-wavefront kernel
     std::vector<char> wcode;
     std::string wlog;
     if (batch_compile(source, n, nparams, flags, &wcode, &wlog, KSET_WAVE) == NK_OK &&
@@ -1034,6 +1221,7 @@ extern "C" int nk_batch_destroy(nk_batch *B) {
   if (B->mod) hipModuleUnload(B->mod);
   if (B->mod_wave) hipModuleUnload(B->mod_wave);
   if (B->mod_jf) hipModuleUnload(B->mod_jf);
+  if (B->mod_tr_wave) hipModuleUnload(B->mod_tr_wave);
   delete B;
   return NK_OK;
 }
@@ -1070,6 +1258,26 @@ static int batch_load_jf(nk_batch *B) {
   return NK_OK;
 }
 
+// the per-wavefront trust-region module, compiled and loaded on the first trust-region solve of an object that can use it
+// (NK_BATCH_TR_WAVE_MIN_N ≤ n ≤ 64, no NK_BATCH_PER_THREAD). As with the Newton wave kernel, a failure is not an error: fn_tr_wave
+// stays NULL and the per-thread kernel runs; nk_batch_last_kernel says which one did.
+static void batch_load_tr_wave(nk_batch *B) {
+  if (B->tr_wave_tried) return;
+  B->tr_wave_tried = true;
+  std::vector<char> code;
+  std::string log;
+  hipModule_t m = nullptr;
+  if (batch_compile(B->source.c_str(), B->n, B->np, B->flags, &code, &log, KSET_WAVE_TR) != NK_OK ||
+      hipModuleLoadData(&m, code.data()) != hipSuccess)
+    return;
+  if (hipModuleGetFunction(&B->fn_tr_wave, m, "nk_batch_trust_region_wave") != hipSuccess) {
+    B->fn_tr_wave = nullptr;
+    hipModuleUnload(m);
+    return;
+  }
+  B->mod_tr_wave = m;
+}
+
 static int batch_run(nk_batch *B, bool f32, int method, int64_t nbatch, const void *u0, int u0_per_system, const void *p,
                      int memspace, double abstol, int maxiters, const double *prm, void *u_out, void *resid_out,
                      int32_t *retcode_out, int32_t *iters_out) {
@@ -1087,6 +1295,8 @@ static int batch_run(nk_batch *B, bool f32, int method, int64_t nbatch, const vo
   NK_HIP(hipSetDevice(ctx->device));
   if (nbatch == 0) return NK_OK;
   if (method >= BATCH_BROYDEN && method <= BATCH_DFSANE) NK_TRY(batch_load_jf(B));
+  if (method == BATCH_TRUST_REGION && !(B->flags & NK_BATCH_PER_THREAD) && B->n >= NK_BATCH_TR_WAVE_MIN_N && B->n <= 64)
+    batch_load_tr_wave(B);
   if (maxiters <= 0) maxiters = 1000;                             // raphson.jl:42 / trust_region.jl:60 / broyden.jl:33 / ...
   const int n = B->n, np = B->np;
   const int nr = B->m > 0 ? B->m : n;   // residuals per system
@@ -1139,6 +1349,12 @@ static int batch_run(nk_batch *B, bool f32, int method, int64_t nbatch, const vo
     void *args[] = {&nb, &du0, &ups, &dp, sa[0], &maxiters, &du, &dr, &drc, &dit};
     st = hipModuleLaunchKernel(B->fn, grid, 1, 1, B->block, 1, 1, 0, ctx->stream, args, nullptr);
     kname = "nk_batch_newton";
+  } else if (method == BATCH_TRUST_REGION && B->fn_tr_wave) {
+    int ms = (int)prm[5];
+    void *args[] = {&nb, &du0, &ups, &dp, sa[0], &maxiters, sa[1], sa[2], sa[3], sa[4], sa[5], &ms, &du, &dr, &drc, &dit};
+    const unsigned wgrid = (unsigned)((nbatch + 3) / 4);  // 4 wavefronts = 4 systems per 256-thread workgroup
+    st = hipModuleLaunchKernel(B->fn_tr_wave, wgrid, 1, 1, 256, 1, 1, 0, ctx->stream, args, nullptr);
+    kname = "nk_batch_trust_region_wave";
   } else if (method == BATCH_TRUST_REGION) {
     int ms = (int)prm[5];
     void *args[] = {&nb, &du0, &ups, &dp, sa[0], &maxiters, sa[1], sa[2], sa[3], sa[4], sa[5], &ms, &du, &dr, &drc, &dit};
@@ -1169,6 +1385,7 @@ static int batch_run(nk_batch *B, bool f32, int method, int64_t nbatch, const vo
     kname = "nk_batch_dfsane";
   }
   if (st != hipSuccess) NK_FAIL(NK_E_HIP, "launch of %s failed", kname);
+  B->last_kernel = kname;
   if (memspace != NK_DEVICE) {
     NK_HIP(hipMemcpyAsync(u_out, du, (size_t)nbatch * n * es, hipMemcpyDeviceToHost, ctx->stream));
     NK_HIP(hipMemcpyAsync(resid_out, dr, (size_t)nbatch * nr * es, hipMemcpyDeviceToHost, ctx->stream));
@@ -1183,6 +1400,9 @@ static int batch_run(nk_batch *B, bool f32, int method, int64_t nbatch, const vo
   if (memspace != NK_DEVICE) NK_HIP(hipStreamSynchronize(ctx->stream));
   return NK_OK;
 }
+
+// the name of the kernel the last solve on B launched: "" before any solve, NULL for a NULL object
+extern "C" const char *nk_batch_last_kernel(nk_batch *B) { return B ? B->last_kernel : nullptr; }
 
 extern "C" int nk_batch_solve(nk_batch *B, int64_t nbatch, const double *u0, int u0_per_system, const double *p, int memspace,
                               double abstol, int maxiters, double *u_out, double *resid_out, int32_t *retcode_out,
